@@ -93,6 +93,16 @@ def resident_gate_state(device):
     return {"census": int(o[0]), "timeouts": int(o[1]), "enqueued": int(o[2])}
 
 
+def dump_records(folder, recs):
+    """--dump-outputs: one .npy per record field, pairs along axis 0 (R: 3x3 row-major rotation, T: translation,
+    integer fields as exact float64)"""
+    os.makedirs(folder, exist_ok=True)
+    fields = {"R": np.float32, "T": np.float32, "err": np.float32, "good": np.float64, "bad": np.float64,
+              "status": np.float64, "evals": np.float64, "flags": np.float64, "n_pts0": np.float64}
+    for name, dt in fields.items():
+        np.save(os.path.join(folder, name + ".npy"), np.stack([np.asarray(r[name], dt) for r in recs]))
+
+
 def baseline_config(w, h, levels, pairs, world):
     """Which BASELINE.json configuration a run IS, by geometry (VERDICT r04 #10), not by world size alone."""
     if (w, h, levels) == (640, 480, 4):
@@ -368,7 +378,14 @@ def main():
                     help="orchestration check without a GPU: the rank plumbing of this file (spawn, rendezvous, shard, records, "
                          "gather, max-over-ranks, one JSON line from rank 0) on the gloo backend with a stubbed step; the line "
                          "carries dry_run=true and no measurement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the pair records of the last timed step (every rank's, in rank order) "
+                         "as DIR/<field>.npy, float32 / float64: the arrays a caller of the pipelined path receives")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     from revo_amd import parallel
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -390,6 +407,8 @@ def main():
     if "WORLD_SIZE" in os.environ and a.gpus != world and rank == 0:
         print("bench: --gpus %d ignored, the launcher set WORLD_SIZE=%d" % (a.gpus, world), file=sys.stderr)
     if a.dry_run_cpu:
+        if a.dump_outputs:
+            raise SystemExit("bench: --dump-outputs needs the GPU path (--dry-run-cpu computes nothing)")
         return dry_run_cpu(a, world, rank, json_fd)
 
     # ---- synthetic input (rendered on the host BEFORE any GPU state exists) ----
@@ -675,6 +694,17 @@ def main():
     if bad_flags:
         raise SystemExit("bench: the tracker flagged invalid results (step, pair, flags): %s" % bad_flags[:8])
     res = all_res[(n_slots - 1) * a.pairs:]
+    if a.dump_outputs:  # the last timed step's records, before anything below reuses the result buffers
+        last = d_res_all[(n_slots - 1) * a.pairs * 96:n_slots * a.pairs * 96]
+        if world > 1:
+            src = last.to(ctl_dev)
+            parts = [torch.empty_like(src) for _ in range(world)]
+            dist.all_gather(parts, src)
+            rec = b"".join(x.cpu().numpy().tobytes() for x in parts)
+        else:
+            rec = last.cpu().numpy().tobytes()
+        if rank == 0:
+            dump_records(a.dump_outputs, api.results_from_buffer(rec, world * a.pairs))
     # step t read input batch t mod nin (on batch object t mod nbuf): equal inputs must give equal bits, whichever step
     for t in range(nin, n_slots):
         x, y = all_res[(t - nin) * a.pairs:(t - nin + 1) * a.pairs], all_res[t * a.pairs:(t + 1) * a.pairs]

@@ -1129,13 +1129,14 @@ static int check_pair(const revo_ctx* c, const revo_pyr* ref, const revo_pyr* cu
 
 // Waits for a sequence word a kernel writes (system scope) after its results in pinned host memory: a short spin
 // (the kernel is usually about to finish: a stream synchronise costs a sleep / wake-up of the calling thread),
-// then the stream.
+// then the stream `s` the kernel was launched on (the vote runs on the vote stream: synchronising the tracker's
+// stream there returned before a vote queued behind other work had run).
 // (debug: how often the spin below ran out and what the longest wait was -- profiles/slow_run_probe.py prints them)
 static std::atomic<unsigned long long> g_wait_fallbacks{0}, g_wait_max_ns{0}, g_wait_calls{0};
 extern "C" void revo_debug_wait_stats_(unsigned long long out[3]) {
   out[0] = g_wait_calls.load(); out[1] = g_wait_fallbacks.load(); out[2] = g_wait_max_ns.load();
 }
-static int wait_seq(revo_ctx* c, volatile unsigned* word, unsigned want) {
+static int wait_seq(hipStream_t s, volatile unsigned* word, unsigned want) {
   static const int spin_limit = env_int("REVO_WAIT_SPINS", 200000, 1000, 2000000000);
   const auto t0 = std::chrono::steady_clock::now();
   g_wait_calls.fetch_add(1, std::memory_order_relaxed);
@@ -1149,7 +1150,7 @@ static int wait_seq(revo_ctx* c, volatile unsigned* word, unsigned want) {
     __builtin_ia32_pause();
   }
   g_wait_fallbacks.fetch_add(1, std::memory_order_relaxed);
-  HIPCHECK(hipStreamSynchronize(c->stream));
+  HIPCHECK(hipStreamSynchronize(s));
   note();
   if (*word != want) return fail(REVO_ERR_HIP, "a kernel finished without publishing its result");
   return REVO_OK;
@@ -1178,7 +1179,7 @@ static int track_launch(revo_ctx* c, const revo_pyr* ref, const revo_pyr* curr, 
   *seq_out = seq;
   return REVO_OK;
 }
-static int track_wait(revo_ctx* c, int slot, unsigned seq) { return wait_seq(c, c->h_seq + slot, seq); }
+static int track_wait(revo_ctx* c, int slot, unsigned seq) { return wait_seq(c->stream, c->h_seq + slot, seq); }
 
 enum { SINGLE_SLOT = 2 };
 static int run_single(revo_ctx* c, const revo_pyr* ref, const revo_pyr* curr, const float* R, const float* T,
@@ -1333,7 +1334,8 @@ static int assess_launch(revo_ctx* c, const float T_w_curr[16], const revo_pyr* 
 static int assess_wait(revo_ctx* c, int nframes, unsigned seq, int* status, int32_t hist4[4], int32_t overlaps4[4]) {
   if (status) *status = REVO_TRACKER_STATE_OK;
   if (nframes < 0) return REVO_OK;
-  { int rc = wait_seq(c, (volatile unsigned*)(c->h_hist8 + 8), seq); if (rc) return rc; }
+  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;  // where assess_launch enqueued the vote
+  { int rc = wait_seq(vs, (volatile unsigned*)(c->h_hist8 + 8), seq); if (rc) return rc; }
   const int* hist = c->h_hist8;
   const int* ov = c->h_hist8 + 4;
   const float wts[4] = {0.f, 1.f, 1.25f, 1.5f};  // tracker.cpp:231-234

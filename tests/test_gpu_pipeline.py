@@ -15,6 +15,9 @@ from revo_amd import synth  # noqa: E402
 from revo_amd.settings import ImgPyramidSettings, TrackerSettings, PLANE_DT  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# hardware queues HIP spreads a process's streams over (GPU_MAX_HW_QUEUES, default 4): the most streams that can sit on
+# pairwise distinct queues
+HW_QUEUES = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
 
 
 @pytest.fixture(scope="module")
@@ -71,8 +74,9 @@ def test_pipeline_handle_equals_the_single_batch_path(api, ro, depth):
     assert info["batches"] == depth and info["pairs_per_step"] == n
     want_streams = 1 if depth == 1 else (3 if depth == 2 else 4)
     assert len(set(info["streams"])) == want_streams
-    # the handle checked its streams: pairwise distinct hardware queues (HIP's default four suffice for four streams)
-    assert info["distinct_hw_queues"] == want_streams, info
+    # the handle checked its streams: pairwise distinct hardware queues, as many as the runtime has (HIP's default four
+    # suffice for four streams)
+    assert info["distinct_hw_queues"] == min(want_streams, HW_QUEUES), info
     steps = 5 * max(2, depth) + 1
     outs = [torch.zeros(n * 96, dtype=torch.uint8, device=dev) for _ in range(steps)]
     copies = [torch.zeros(n * 96, dtype=torch.uint8, device=dev) for _ in range(steps)]
@@ -182,7 +186,7 @@ def test_cpp_host_drives_the_pipeline_through_the_c_abi(tmp_path):
     out = subprocess.run([exe, "320", "240", str(n), str(tmp_path / "bgr.bin"), str(tmp_path / "depth.bin")],
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "PIPELINE_HOST_OK" in out.stdout, out.stdout + out.stderr
-    assert "4 distinct hardware queues" in out.stdout, out.stdout
+    assert "%d distinct hardware queues" % min(4, HW_QUEUES) in out.stdout, out.stdout
     assert "native collective:" in out.stdout and "3 windows + 1 flushed step(s) gathered" in out.stdout, out.stdout
 
 

@@ -275,3 +275,34 @@ def test_in_place_upload_of_padded_rows_kernel_and_memcpy_paths(monkeypatch):
             got = planes(api.ImgPyramidRGBD(s, cam, _handle=hnd))
             for a, b in zip(got, want):
                 assert np.array_equal(a, b), (knob, pad_b, pad_d)
+
+
+def test_vo_waits_on_the_stream_that_publishes_the_result(tmp_path):
+    """The sequence-word waits (revo_host.hip wait_seq) fall back to a stream synchronise once their spin runs out; the
+    quality vote publishes from the vote stream, so that is the stream the fallback must wait for.  A child process with the
+    shortest spin (REVO_WAIT_SPINS=1000, read once per process) takes the fallback on nearly every wait: the same trajectory
+    and keyframes, bit for bit, as the default spin in this process."""
+    import subprocess
+    import sys
+    from revo_amd import synth, vo
+    from revo_amd.settings import ImgPyramidSettings
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child = (
+        "import sys; sys.path.insert(0, %r)\n"
+        "import numpy as np\n"
+        "from revo_amd import synth, vo\n"
+        "from revo_amd.settings import ImgPyramidSettings\n"
+        "s = ImgPyramidSettings.scaled(320, 240, 3, hist_patch=(10, 5, 0, 0, 0, 0))\n"
+        "frames = synth.make_sequence(4, s, 45, max_t=0.01, max_rot_deg=0.4, bias=[0.004, 0, 0, 0, np.deg2rad(1.0), 0])\n"
+        "res = vo.REVO(s).run([(f[0], f[1], f[2]) for f in frames])\n"
+        "np.savez(%r, poses=np.stack([r[0] for r in res]), kf=np.array([bool(r[1]) for r in res]))\n"
+        % (root, str(tmp_path / "short_spin.npz")))
+    env = dict(os.environ, REVO_WAIT_SPINS="1000")
+    r = subprocess.run([sys.executable, "-c", child], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    s = ImgPyramidSettings.scaled(320, 240, 3, hist_patch=(10, 5, 0, 0, 0, 0))
+    frames = synth.make_sequence(4, s, 45, max_t=0.01, max_rot_deg=0.4, bias=[0.004, 0, 0, 0, np.deg2rad(1.0), 0])
+    want = vo.REVO(s).run([(f[0], f[1], f[2]) for f in frames])
+    got = np.load(str(tmp_path / "short_spin.npz"))
+    assert got["kf"].tolist() == [bool(w[1]) for w in want] and sum(got["kf"]) >= 3
+    assert np.array_equal(got["poses"], np.stack([w[0] for w in want]))
