@@ -95,7 +95,10 @@ typedef struct revo_opt_settings {
 typedef struct revo_tracker_settings {
   int32_t check_tracking_results;   /* tracker.h:45 (1) */
   int32_t check_init_values;        /* tracker.h:43 (1) */
-  int32_t n_frames_hist_voting;     /* tracker.h:47 (3) */
+  int32_t n_frames_hist_voting;     /* tracker.h:47 (3); the vote uses min(n, past clouds, 3) clouds, the oldest first:
+                                       values above 3 vote like 3 (the reference would throw std::out_of_range from
+                                       histWeights.at(4), tracker.cpp:179); below 3 it never asks for a new keyframe
+                                       (hsize < 4, tracker.cpp:184) */
   int32_t histogram_level;          /* tracker.cpp:229 (2) */
 } revo_tracker_settings;
 
@@ -131,7 +134,8 @@ int revo_ctx_create(int device, const revo_pyr_settings* pyr,
 void revo_ctx_destroy(revo_ctx* ctx);
 /* TrackerNew(const TrackerSettings&, const ImgPyramidSettings&) (tracker.cpp:225-235)
  * is constructed AFTER CameraPyr and the IO thread in the reference
- * (system.cpp:96,107): applies tracker/optimizer settings to an existing ctx. */
+ * (system.cpp:96,107): applies tracker/optimizer settings to an existing ctx and, like the
+ * reference's constructor, starts with empty past lists (the clouds of an earlier tracker are dropped). */
 int revo_ctx_set_tracker(revo_ctx* ctx, const revo_opt_settings* opt,
                          const revo_tracker_settings* trk);
 

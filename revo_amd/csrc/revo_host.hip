@@ -692,6 +692,9 @@ extern "C" int revo_ctx_set_tracker(revo_ctx* c, const revo_opt_settings* opt, c
   if (opt) c->os = *opt;
   if (trk) c->ts = *trk;
   build_track_params(c, &c->tp);
+  // a new TrackerNew starts with empty past lists (tracker.h:92-95): the clouds an earlier tracker on this context added must
+  // not vote for this one (stream-ordered reuse of the buffers, as in revo_tracker_clear_past)
+  while (!c->past.empty()) { c->past_pool.push_back(c->past.front()); c->past.pop_front(); }
   return REVO_OK;
 }
 

@@ -145,3 +145,54 @@ def test_decode_pool_delivers_the_same_frames_in_order(tmp_path):
     with tum.DecodePool(folder, rows, 160, 120, workers=2, pin=False) as pool:
         with pytest.raises(RuntimeError):
             list(pool)
+
+
+def test_shipped_reference_configs_load_with_their_values(tmp_path):
+    """The reference's five dataset files and its settings file (values in tests/golden/reference_configs.json), written back
+    out as OpenCV FileStorage YAML: the structs the readers fill carry exactly those values, and the keys a file leaves out
+    take the reference's defaults (camerapyr.h:40-64, tracker.h:43-47) -- realsense / orbbec_normal / orbbec_pro have no
+    nPercentage, so they get 0.3."""
+    import json
+    import os
+    from revo_amd.settings import TrackerSettings
+    fix = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_configs.json")))
+    assert sorted(fix["datasets"]) == ["dataset_tum1", "orbbec_dataset", "orbbec_normal", "orbbec_pro", "realsense"]
+    f32 = lambda x: float(np.float32(x))  # noqa: E731
+    loaded = {}
+    for name, v in fix["datasets"].items():
+        p = tmp_path / (name + ".yaml")
+        p.write_text("%YAML:1.0\n" + "".join("%s: %r\n" % kv for kv in v.items()))
+        s, io = config.load_dataset_yaml(str(p))
+        assert (s.width, s.height) == (v.get("width", 640), v.get("height", 480)), name
+        assert (s.fx, s.fy, s.cx, s.cy) == tuple(f32(v[k]) for k in ("Camera.fx", "Camera.fy", "Camera.cx", "Camera.cy")), name
+        assert (s.canny_threshold1, s.canny_threshold2) == (v["cannyThreshold1"], v["cannyThreshold2"]), name
+        assert (s.pyr_min_lvl, s.pyr_max_lvl) == (v["PYR_MIN_LVL"], v["PYR_MAX_LVL"]) and s.nLevels() == 3, name
+        assert (s.depth_min, s.depth_max) == (f32(v["DEPTH_MIN"]), f32(v["DEPTH_MAX"])), name
+        assert s.use_edge_hist == v["USE_EDGE_HIST"] == 1, name
+        assert s.n_percentage == f32(v.get("nPercentage", 0.3)) == f32(0.3), name
+        assert list(s.hist_patch) == [20, 10, 5, 0, 0, 0], name
+        assert io["depth_scale_factor"] == v["DEPTH_SCALE_FACTOR"], name
+        assert (io["img_width"], io["img_height"]) == (v["Camera.width"], v["Camera.height"]) == (640, 480), name
+        loaded[name] = (bytes(s), io["depth_scale_factor"])
+    # the values each file sets
+    d = fix["datasets"]
+    assert (d["dataset_tum1"]["cannyThreshold1"], d["dataset_tum1"]["DEPTH_SCALE_FACTOR"]) == (150, 5000.0)
+    assert all((d[n]["cannyThreshold1"], d[n]["cannyThreshold2"], d[n]["DEPTH_SCALE_FACTOR"]) == (60, 20, 1000.0)
+               for n in ("orbbec_dataset", "orbbec_normal", "orbbec_pro"))
+    assert (d["realsense"]["cannyThreshold1"], d["realsense"]["cannyThreshold2"]) == (80, 50)
+    assert [n for n in sorted(d) if "nPercentage" not in d[n]] == ["orbbec_normal", "orbbec_pro", "realsense"]
+    # orbbec_normal and orbbec_pro are the same configuration as far as the port reads, and so is orbbec_dataset once the
+    # default nPercentage is filled in: three distinct configurations (the GPU tests run each once)
+    assert d["orbbec_normal"] == d["orbbec_pro"]
+    assert loaded["orbbec_dataset"] == loaded["orbbec_normal"] == loaded["orbbec_pro"]
+    assert len(set(loaded.values())) == 3
+    # the settings file: TUM1's tracker values are the library defaults
+    v = fix["settings"]["revo_settings"]
+    p = tmp_path / "revo_settings.yaml"
+    p.write_text("%YAML:1.0\n" + "".join("%s: %r\n" % kv for kv in v.items()))
+    ts, filt, sysd = config.load_settings_yaml(str(p))
+    assert bytes(ts) == bytes(TrackerSettings())
+    assert (ts.check_tracking_results, ts.check_init_values, ts.n_frames_hist_voting) == (
+        v["CHECK_TRACKING_RESULTS"], v["CHECK_INIT_VALUES"], v["N_FRAMES_HIST_VOTING"])
+    assert filt == v["USE_EDGE_FILTER"] == 1
+    assert sysd == dict(do_output_poses=v["DO_OUTPUT_POSES"], do_generate_dense_pcl=v["DO_GENERATE_DENSE_PCL"])

@@ -20,7 +20,8 @@ def _same(a, b):
             and a["evals"].tolist() == b["evals"].tolist() and a["flags"] == b["flags"] and a["good"] == b["good"])
 
 
-def test_host_buffer_batch_equals_device_pointer_batch(api):
+@pytest.mark.parametrize("scale", [5000.0, 1000.0])  # TUM's DEPTH_SCALE_FACTOR and the Orbbec / RealSense files'
+def test_host_buffer_batch_equals_device_pointer_batch(api, scale):
     import torch
     s = ImgPyramidSettings.scaled(320, 240, 3, hist_patch=(10, 5, 0, 0, 0, 0))
     n = 5
@@ -31,15 +32,15 @@ def test_host_buffer_batch_equals_device_pointer_batch(api):
     init = [(prior[:3, :3], prior[:3, 3]) if i % 2 else (np.eye(3), np.zeros(3)) for i in range(n)]
     bt = api.BatchTracker(cam, n)
     d_res = torch.zeros(n * 96, dtype=torch.uint8, device="cuda")
-    for u16 in (False, True):
+    for u16 in ((False, True) if scale == 5000.0 else (True,)):  # (the float-depth half does not depend on the scale)
         if u16:
-            deps = [[np.clip(p[k][1] * 5000.0, 0, 65535).astype(np.uint16) for k in ("ref", "curr")] for p in pairs]
+            deps = [[np.clip(p[k][1] * scale, 0, 65535).astype(np.uint16) for k in ("ref", "curr")] for p in pairs]
         else:
             deps = [[p[k][1] for k in ("ref", "curr")] for p in pairs]
         d_bgr = torch.from_numpy(np.stack([p[k][0] for p in pairs for k in ("ref", "curr")])).cuda()
         d_dep = torch.from_numpy(np.stack([d for dd in deps for d in dd])).cuda()
         if u16:
-            bt.build_u16(d_bgr.data_ptr(), d_dep.data_ptr(), 5000.0)
+            bt.build_u16(d_bgr.data_ptr(), d_dep.data_ptr(), scale)
         else:
             bt.build(d_bgr.data_ptr(), d_dep.data_ptr())
         bt.track_only(d_res.data_ptr(), init_RT=api.pack_init_RT([r for r, _ in init], [t for _, t in init]))
@@ -59,7 +60,7 @@ def test_host_buffer_batch_equals_device_pointer_batch(api):
                     d = torch.from_numpy(np.ascontiguousarray(d)).pin_memory().numpy()
                 fr.append((b, d))
             host.append(tuple(fr))
-        hb = api.HostBatchTracker(cam, depth_scale_factor=5000.0 if u16 else None)
+        hb = api.HostBatchTracker(cam, depth_scale_factor=scale if u16 else None)
         got = hb.track(host, init_RT=init)
         assert all(_same(a, b) for a, b in zip(got, want)), ("u16" if u16 else "f32")
         # three jobs in flight, a fourth is refused, results independent of the pipelining

@@ -1,5 +1,6 @@
 """Randomised soak of the build path against the oracle (not collected by pytest: run it by hand on a GPU box,
-`python tests/tools/soak_gpu_parity.py [n_scenes]`).  Scene families chosen to reach the rare paths of the round-2
+`python tests/tools/soak_gpu_parity.py [n_scenes] [seed] [--canny LO,HI]`; --canny runs every scene at those Canny thresholds
+instead of TUM1's 150/100, e.g. the Orbbec files' 60,20 or RealSense's 80,50).  Scene families chosen to reach the rare paths of the round-2
 kernels: low-contrast noise (thousands of weak runs per level: banded union-find / table overgrowth of E / flood-fill
 fallback), smooth fields (long weak chains), sparse corners (fill-in -> bitmap update in k_fill), invalid depths
 (validity bits), sizes whose levels are / are not multiples of 32 pixels wide (bit-tile vs byte paths)."""
@@ -43,14 +44,21 @@ def scene(rng, w, h, kind):
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 48
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 2026)
+    args = sys.argv[1:]
+    canny = {}
+    if "--canny" in args:
+        i = args.index("--canny")
+        lo, hi = (int(x) for x in args[i + 1].split(","))
+        canny = dict(canny_threshold1=lo, canny_threshold2=hi)
+        del args[i:i + 2]
+    n = int(args[0]) if len(args) > 0 else 48
+    rng = np.random.default_rng(int(args[1]) if len(args) > 1 else 2026)
     bad = 0
     for i in range(n):
         w, h, lv, hist = SIZES[i % len(SIZES)] if i % 12 else SIZES[5]
         if (w, h) == (1280, 960) and i % 12:
             w, h, lv, hist = SIZES[0]
-        s = ImgPyramidSettings.scaled(w, h, lv, hist_patch=hist)
+        s = ImgPyramidSettings.scaled(w, h, lv, hist_patch=hist, **canny)
         cam = api.CameraPyr(s)
         bgr, d = scene(rng, w, h, i % 4)
         gp = api.ImgPyramidRGBD(s, cam, bgr, d)
@@ -69,7 +77,8 @@ def main():
         print("scene %3d kind %d %4dx%-4d L%d edges %s %s" % (i, i % 4, w, h, lv, ne, "MISMATCH " + ",".join(names) if names else "ok"), flush=True)
         bad += bool(names)
         del gp, op, cam
-    print("SOAK %s: %d of %d scenes differ" % ("FAILED" if bad else "OK", bad, n))
+    print("SOAK %s: %d of %d scenes differ (Canny %s)" % ("FAILED" if bad else "OK", bad, n,
+                                                          "%d/%d" % (s.canny_threshold1, s.canny_threshold2)))
     return 1 if bad else 0
 
 
