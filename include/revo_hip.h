@@ -496,6 +496,44 @@ int revo_vo_num_keyframes(const revo_vo* vo);
  * borrowed: valid until the next revo_vo_track_next / revo_vo_destroy. */
 int revo_vo_keyframe(const revo_vo* v, revo_pyr** kf_out, float T_w_kf[16]);
 
+/* ---------------------------------------------------------------------------
+ * Many independent sequential-VO streams in lockstep (revo_vo_multi).
+ * Each stream is one REVO::start (system.cpp:84-305) with its own keyframe, past clouds and
+ * constant-velocity initialisation; per stream the poses equal what a revo_vo computes.  One
+ * revo_vo_multi_step issues ONE tracker grid and ONE quality vote for every stream that has work.
+ * A keyframe change is deferred: the step whose vote asks for it promotes the stream's previous
+ * frame and reports nothing for that stream; the next step re-tracks the same frame against the
+ * new keyframe and reports it with new_keyframe = 1.
+ * ------------------------------------------------------------------------- */
+typedef struct revo_vo_multi revo_vo_multi;
+typedef struct revo_stream_frame {  /* one frame of one stream, host memory (cv::Mat layout) */
+  int32_t stream;                   /* 0 .. n_streams-1 */
+  const uint8_t* bgr; size_t bgr_stride;
+  const void* depth; size_t depth_stride;  /* f32 metres, or raw u16 (depth_is_u16) */
+  double timestamp;
+} revo_stream_frame;
+typedef struct revo_stream_result {
+  int32_t stream, new_keyframe;
+  double timestamp;
+  float pose[16];                   /* curr->world, column-major, as revo_vo_track_next */
+} revo_stream_result;
+/* n_streams >= 1; max_queue >= 1: frames a stream may hold submitted and not yet reported.  The
+ * tracker's cluster size is fixed here from n_streams (REVO_TRACK_CLUSTER / REVO_TRACK_REDUNDANT_BATCH
+ * apply as for a batch): a stream's results do not depend on what its neighbours do. */
+int revo_vo_multi_create(revo_ctx* ctx, int n_streams, int max_queue, revo_vo_multi** out);
+void revo_vo_multi_destroy(revo_vo_multi* m);
+/* At most one frame per stream per call; REVO_ERR_CAPACITY if a stream's queue is full.  All n
+ * frames are built in one batched build (asynchronous); returns once the host rows are consumed. */
+int revo_vo_multi_submit(revo_vo_multi* m, int n, const revo_stream_frame* frames,
+                         int depth_is_u16, double depth_scale_factor);
+/* One loop body of REVO::start for every stream with work; out: n_streams records, *n_out of them written. */
+int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int* n_out);
+int revo_vo_multi_pending(const revo_vo_multi* m, int stream);  /* submitted, not yet reported (-1: bad stream) */
+int revo_vo_multi_reset(revo_vo_multi* m, int stream);          /* new sequence on an idle stream (system.cpp:107) */
+int revo_vo_multi_num_keyframes(const revo_vo_multi* m, int stream);
+/* The stream's current keyframe (borrowed, valid until the next revo_vo_multi_step) and its pose in the world. */
+int revo_vo_multi_keyframe(const revo_vo_multi* m, int stream, revo_pyr** kf, float T_w_kf[16]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,15 @@ def lib():
     L.revo_vo_close.argtypes = [vp]
     L.revo_vo_wait_frame.argtypes = [vp]
     L.revo_vo_num_keyframes.argtypes = [vp]
+    L.revo_vo_multi_create.argtypes = [vp, C.c_int, C.c_int, vpp]
+    L.revo_vo_multi_destroy.argtypes = [vp]
+    L.revo_vo_multi_destroy.restype = None
+    L.revo_vo_multi_submit.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double]
+    L.revo_vo_multi_step.argtypes = [vp, vp, C.POINTER(C.c_int)]
+    L.revo_vo_multi_pending.argtypes = [vp, C.c_int]
+    L.revo_vo_multi_reset.argtypes = [vp, C.c_int]
+    L.revo_vo_multi_num_keyframes.argtypes = [vp, C.c_int]
+    L.revo_vo_multi_keyframe.argtypes = [vp, C.c_int, vpp, f32p]
     L.revo_pipeline_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, vpp]
     L.revo_pipeline_destroy.argtypes = [vp]
     L.revo_pipeline_destroy.restype = None

@@ -174,3 +174,15 @@ void launch_vote(const PyrGeom& g, const FramePlanes& curr, int curr_frame, int 
                  int* h_out8 /*pinned host: hist[4], overlaps[4], then the sequence word*/, unsigned seq_val, int use_orig_edges,
                  hipStream_t s);
 void launch_copy_cloud(float4* dst, const float4* src, int* dst_n, const int* src_n, hipStream_t s);
+// revo_vo_multi (one launch for many streams): per-stream vote descriptors, past-cloud copies and plane copies, all in device memory
+struct VoteDesc {
+  float RT[3][12]; const float4* pts[3]; const int* n[3]; int n_clouds;  // as VoteArgs, plus how many clouds vote
+  const uint8_t* edges; const float* depth;                              // the current frame's planes at the histogram level
+  int* marks; int* hist8; unsigned* done;                                // the stream's own scratch (all-zero in / out)
+  int* host_out;                                                         // pinned: hist[4], overlaps[4], then the sequence word
+};
+struct CloudCopyDesc { float4* dst; const float4* src; int* dst_n; const int* src_n; };
+struct CopySeg { const void* src; void* dst; size_t bytes; };
+void launch_vote_multi(const PyrGeom& g, int lvl, int n, const VoteDesc* d_descs, unsigned seq_val, hipStream_t s);
+void launch_copy_cloud_multi(int n, const CloudCopyDesc* d_descs, hipStream_t s);
+void launch_copy_segments(int n, const CopySeg* d_segs, hipStream_t s);

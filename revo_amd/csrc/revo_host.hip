@@ -17,6 +17,7 @@
 
 #include "revo_dev.h"
 #include "revo_mat4.h"
+#include "revo_multi.h"
 
 // ------------------------------------------------------------------ errors --
 static thread_local std::string g_err;
@@ -174,6 +175,7 @@ struct revo_pyr {
   bool table_built;
   bool ref_list_built;  // edges3DPyr in the reference's order (the hot path only writes the tile-ordered list)
   bool dt_ready = false;  // the distance transforms are already enqueued on the tracker stream (revo_pyramid_prepare_keyframe_)
+  bool has_colour = false;  // a view whose set keeps the colour image of its frame (revo_vo_multi's keyframe slots)
 };
 
 struct revo_batch {
@@ -450,7 +452,8 @@ static size_t mail_bytes(int n_pairs, int cluster) { return sizeof(unsigned long
 // --------------------------------------------------------------- FrameSets --
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static int frameset_create(revo_ctx* c, int B, bool with_staging, FrameSet** out) {
+// host_staging = false: device-side input planes only (inputs go straight from the caller's rows to the device)
+static int frameset_create(revo_ctx* c, int B, bool with_staging, FrameSet** out, bool host_staging = true) {
   const PyrGeom& g = c->geom;
   FrameSet* fs = new FrameSet();
   fs->B = B;
@@ -503,7 +506,7 @@ static int frameset_create(revo_ctx* c, int B, bool with_staging, FrameSet** out
       if (e != hipSuccess) { delete fs; return fail(REVO_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     }
   }
-  if (with_staging) {
+  if (with_staging && host_staging) {
     HIPCHECK(hipHostMalloc((void**)&fs->h_bgr, (size_t)g.lv[0].npix * 3 * B));
     HIPCHECK(hipHostMalloc((void**)&fs->h_depth, (size_t)g.lv[0].npix * 4 * B));
   }
@@ -1072,7 +1075,7 @@ extern "C" int revo_pyramid_colored_pcl(revo_pyr* p, int lvl, int dense, float* 
   revo_ctx* c = p->ctx;
   HIPCHECK(hipSetDevice(c->device));
   if (lvl < 0 || lvl >= c->geom.n_levels) return fail(REVO_ERR_LEVEL, "level out of range");
-  if (!p->owns_fs || !p->fs->d_bgr)
+  if (!(p->owns_fs || p->has_colour) || !p->fs->d_bgr)
     return fail(REVO_ERR_INVALID_ARG, "batch views keep no colour image (rgbFullSize): use revo_pyramid_create");
   { int rc = wait_ready(c, p); if (rc) return rc; }
   std::lock_guard<std::mutex> lk(c->mu);
@@ -1089,7 +1092,7 @@ extern "C" int revo_pyramid_colored_pcl(revo_pyr* p, int lvl, int dense, float* 
     c->d_pcl_chunk = (int*)(c->d_pcl + o_ch); c->d_pcl_mask = (unsigned*)(c->d_pcl + o_m); c->d_pcl_total = (int*)(c->d_pcl + o_t);
   }
   hipStream_t s = c->stream;
-  const uint8_t* clr = p->fs->d_bgr;  // the full-resolution clone (imgpyramidrgbd.cpp:51), pyrDown'ed lvl times
+  const uint8_t* clr = p->fs->d_bgr + (size_t)p->frame * n0 * 3;  // the full-resolution clone (imgpyramidrgbd.cpp:51), pyrDown'ed lvl times
   for (int l = 0; l < lvl; ++l) {
     uint8_t* d = c->d_pcl_clr[l & 1];
     launch_pyrdown_bgr(clr, g.lv[l].w, g.lv[l].h, d, s);
@@ -2058,3 +2061,392 @@ extern "C" int revo_batch_time_tracker(revo_batch* b, const float* h_init_RT, re
   *ms_mean = total / (float)reps;
   return batch_mark_tracker(b, s);
 }
+
+// ------------------------------------------------- multi-stream VO (device) --
+// The device half of revo_vo_multi (revo_vo_multi.hip runs the per-stream REVO::start logic on top of it).
+//   * Step sets: one FrameSet of n_streams frames per submit (one batched build), pooled.  The host side releases a set once
+//     none of its frames is queued, current or previous any more; its reuse is ordered by ev_free / ev_free2 like a
+//     single-frame set's.
+//   * Keyframes: ONE persistent set of n_streams frames, slot s = stream s.  Promotion copies the frame's planes out of its
+//     step set and runs the EDT on the slot, so a keyframe never pins a step set (n_streams keyframes in n_streams different
+//     step sets would otherwise hold n_streams^2 frames).
+//   * Past clouds: per stream, owned here (never revo_ctx::past: a revo_vo on the same context keeps its own).
+//   * Streams: the context's tracker stream (grids, promotions), build stream (uploads and builds) and vote stream (votes,
+//     cloud copies).  No graph capture.
+//   * Tracker settings: a snapshot of the context's, taken when the handle is created (a later revo_ctx_set_tracker does
+//     not reach the handle, and the handle never changes the context's).
+struct revo_mdev {
+  revo_ctx* c = nullptr;
+  int S = 0, cluster = 1, hl = 0;
+  TrackParams tp;
+  revo_tracker_settings ts;  // the context's tracker settings when the handle was created (with tp: one consistent snapshot)
+  FrameSet* kf = nullptr;
+  std::vector<revo_pyr> kf_views;
+  std::vector<FrameSet*> pool, all;
+  PairDesc* h_descs = nullptr; PairDesc* d_descs = nullptr;
+  revo_pair_result* d_res = nullptr; revo_pair_result* h_res = nullptr;
+  unsigned long long* d_mail = nullptr;
+  unsigned mail_epoch = 0;
+  VoteDesc* h_vdesc = nullptr; VoteDesc* d_vdesc = nullptr;
+  int* d_marks = nullptr; int* d_hist8 = nullptr; unsigned* d_done = nullptr; int* h_vout = nullptr;  // h_vout: [S][16]
+  unsigned seq = 0;
+  CloudCopyDesc* h_cdesc = nullptr; CloudCopyDesc* d_cdesc = nullptr;
+  CopySeg* h_segs = nullptr; CopySeg* d_segs = nullptr; size_t seg_cap = 0;
+  std::vector<std::deque<Past>> past;
+  std::vector<Past> past_pool;
+  size_t cloud_cap = 0;
+  hipEvent_t ev_trk = nullptr, ev_vdesc = nullptr, ev_cdesc = nullptr, ev_segs = nullptr, ev_h2d = nullptr;
+};
+
+extern "C" void revo_mdev_destroy_(revo_mdev* m) {
+  if (!m) return;
+  revo_ctx* c = m->c;
+  hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipStreamSynchronize(c->build_stream);
+  if (c->vote_stream) (void)hipStreamSynchronize(c->vote_stream);
+  for (FrameSet* fs : m->all) frameset_destroy(fs);
+  frameset_destroy(m->kf);
+  for (auto& q : m->past) for (auto& p : q) { hipFree(p.d_pts); hipFree(p.d_n); }
+  for (auto& p : m->past_pool) { hipFree(p.d_pts); hipFree(p.d_n); }
+  hipHostFree(m->h_descs); hipFree(m->d_descs); hipFree(m->d_res); hipHostFree(m->h_res); hipFree(m->d_mail);
+  hipHostFree(m->h_vdesc); hipFree(m->d_vdesc); hipFree(m->d_marks); hipFree(m->d_hist8); hipFree(m->d_done); hipHostFree(m->h_vout);
+  hipHostFree(m->h_cdesc); hipFree(m->d_cdesc); hipHostFree(m->h_segs); hipFree(m->d_segs);
+  for (hipEvent_t e : {m->ev_trk, m->ev_vdesc, m->ev_cdesc, m->ev_segs, m->ev_h2d}) if (e) hipEventDestroy(e);
+  (void)hipGetLastError();  // a partially built handle frees null pointers on purpose
+  delete m;
+  ctx_unref(c);
+}
+
+extern "C" int revo_mdev_create_(revo_ctx* c, int S, revo_mdev** out) {
+  if (!c || !out || S < 1) return fail(REVO_ERR_INVALID_ARG, "bad argument");
+  HIPCHECK(hipSetDevice(c->device));
+  const int hl = c->ts.histogram_level;
+  if (hl < 0 || hl >= c->geom.n_levels) return fail(REVO_ERR_LEVEL, "histogram_level outside the pyramid");
+  revo_mdev* m = new revo_mdev();
+  m->c = c; m->S = S; m->hl = hl;
+  ctx_ref(c);
+  struct Guard { revo_mdev* m; ~Guard() { if (m) revo_mdev_destroy_(m); } } guard{m};
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    m->tp = c->tp;
+    m->ts = c->ts;
+  }
+  m->tp.eval_only = 0;
+  // Fixed for the handle's lifetime, as for a batch of n_streams pairs (REVO_TRACK_CLUSTER applies): every grid partitions a
+  // pair's point lists the same way whatever else it carries, so a stream's poses do not depend on its neighbours.  (A larger
+  // cluster -- the single-grid share, since the handle waits for each of its grids -- was tried: it moves the float sums of the
+  // partition, and one 640x480 test sequence moved from within 5e-4 to 9e-4 per frame of the CPU restatement.  Not kept.)
+  m->cluster = pick_cluster(c, S);
+  { int rc = frameset_create(c, S, true, &m->kf, false); if (rc) return rc; }
+  for (int s = 0; s < S; ++s) {
+    revo_pyr v{c, m->kf, s, false, true, 0.0, false, false};
+    v.has_colour = true;
+    m->kf_views.push_back(v);
+  }
+  HIPCHECK(hipHostMalloc((void**)&m->h_descs, sizeof(PairDesc) * S));
+  HIPCHECK(hipMalloc((void**)&m->d_descs, sizeof(PairDesc) * S));
+  HIPCHECK(hipMalloc((void**)&m->d_res, sizeof(revo_pair_result) * S));
+  HIPCHECK(hipHostMalloc((void**)&m->h_res, sizeof(revo_pair_result) * S));
+  HIPCHECK(hipMalloc((void**)&m->d_mail, mail_bytes(S, m->cluster)));
+  HIPCHECK(hipMemset(m->d_mail, 0, mail_bytes(S, m->cluster)));
+  const size_t np = (size_t)c->geom.lv[hl].npix;
+  m->cloud_cap = np;
+  HIPCHECK(hipHostMalloc((void**)&m->h_vdesc, sizeof(VoteDesc) * S));
+  HIPCHECK(hipMalloc((void**)&m->d_vdesc, sizeof(VoteDesc) * S));
+  HIPCHECK(hipMalloc((void**)&m->d_marks, sizeof(int) * np * S));
+  HIPCHECK(hipMalloc((void**)&m->d_hist8, sizeof(int) * 8 * S));
+  HIPCHECK(hipMalloc((void**)&m->d_done, sizeof(unsigned) * S));
+  HIPCHECK(hipMemset(m->d_marks, 0, sizeof(int) * np * S));  // the vote kernels leave their scratch clean: zero it once
+  HIPCHECK(hipMemset(m->d_hist8, 0, sizeof(int) * 8 * S));
+  HIPCHECK(hipMemset(m->d_done, 0, sizeof(unsigned) * S));
+  HIPCHECK(hipHostMalloc((void**)&m->h_vout, sizeof(int) * 16 * S));
+  memset(m->h_vout, 0, sizeof(int) * 16 * S);
+  HIPCHECK(hipHostMalloc((void**)&m->h_cdesc, sizeof(CloudCopyDesc) * S));
+  HIPCHECK(hipMalloc((void**)&m->d_cdesc, sizeof(CloudCopyDesc) * S));
+  for (hipEvent_t* e : {&m->ev_trk, &m->ev_vdesc, &m->ev_cdesc, &m->ev_segs, &m->ev_h2d})
+    HIPCHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  // (recorded once so that the first wait on each finds a completed event)
+  for (hipEvent_t e : {m->ev_vdesc, m->ev_cdesc, m->ev_segs}) HIPCHECK(hipEventRecord(e, c->stream));
+  m->past.resize(S);
+  HIPCHECK(hipDeviceSynchronize());  // the zeroing above runs on the NULL stream; the context's streams are non-blocking
+  guard.m = nullptr;
+  *out = m;
+  return REVO_OK;
+}
+
+extern "C" int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* fr, int is_u16, double scale, void** set_out) {
+  revo_ctx* c = m->c;
+  HIPCHECK(hipSetDevice(c->device));
+  FrameSet* fs = nullptr;
+  if (!m->pool.empty()) { fs = m->pool.back(); m->pool.pop_back(); }
+  else {
+    int rc = frameset_create(c, m->S, true, &fs, false);
+    if (rc) return rc;
+    m->all.push_back(fs);
+  }
+  // the uploads go on the build stream, in front of the build that reads them (no stream of their own)
+  hipStream_t cs = c->build_stream, bs = c->build_stream;
+  // the set's last consumers (tracker, vote) are done with its planes (its previous build is on this stream already)
+  if (fs->has_free) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_free, 0));
+  if (fs->has_free2) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_free2, 0));
+  const int w = c->geom.lv[0].w, h = c->geom.lv[0].h;
+  const size_t npix = (size_t)w * h, brow = (size_t)w * 3, drow = (size_t)w * (is_u16 ? 2 : 4);
+  // frames whose rows lie back to back in the caller's memory (a decoder filling one slab per plane type) go in one copy
+  struct Run { char* dst; const char* src; size_t bytes; };
+  auto flush = [&](Run& r) -> hipError_t {
+    if (!r.bytes) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyHostToDevice, cs);
+    r.bytes = 0;
+    return e;
+  };
+  auto upload = [&](Run& r, void* dst, const void* src, size_t stride, size_t row) -> hipError_t {
+    if (stride != row) {
+      const hipError_t e = flush(r);
+      if (e != hipSuccess) return e;
+      return hipMemcpy2DAsync(dst, row, src, stride, row, h, hipMemcpyHostToDevice, cs);
+    }
+    if (r.bytes && r.src + r.bytes == (const char*)src && r.dst + r.bytes == (char*)dst) { r.bytes += row * h; return hipSuccess; }
+    const hipError_t e = flush(r);
+    if (e != hipSuccess) return e;
+    r.dst = (char*)dst; r.src = (const char*)src; r.bytes = row * h;
+    return hipSuccess;
+  };
+  Run rc_{nullptr, nullptr, 0}, rd_{nullptr, nullptr, 0};
+  for (int i = 0; i < n; ++i) {
+    HIPCHECK(upload(rc_, fs->d_bgr + (size_t)i * npix * 3, fr[i].bgr, fr[i].bgr_stride, brow));
+    HIPCHECK(upload(rd_, (char*)fs->d_depth + (size_t)i * npix * (is_u16 ? 2 : 4), fr[i].depth, fr[i].depth_stride, drow));
+  }
+  HIPCHECK(flush(rc_));
+  HIPCHECK(flush(rd_));
+  HIPCHECK(hipEventRecord(m->ev_h2d, cs));
+  const float alpha = is_u16 ? (float)(1.0f / scale) : 0.0f;  // iowrapperRGBD.cpp:327, fused into the first build kernel
+  enqueue_build(c, fs, fs->d_bgr, is_u16 ? nullptr : fs->d_depth, is_u16 ? (const uint16_t*)fs->d_depth : nullptr, alpha, bs, true,
+                true, 0, n);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(fs->ev_ready, bs));
+  fs->has_ready = true;
+  fs->ready_stream = bs;
+  // the host rows are consumed once the copies are done; the build runs on
+  HIPCHECK(hipEventSynchronize(m->ev_h2d));
+  *set_out = fs;
+  return REVO_OK;
+}
+
+extern "C" void revo_mdev_release_set_(revo_mdev* m, void* set) {
+  FrameSet* fs = (FrameSet*)set;
+  revo_ctx* c = m->c;
+  hipSetDevice(c->device);
+  hipEventRecord(fs->ev_free, c->stream);
+  fs->has_free = true;
+  if (c->vote_stream) { hipEventRecord(fs->ev_free2, c->vote_stream); fs->has_free2 = true; }
+  m->pool.push_back(fs);
+}
+
+extern "C" int revo_mdev_track_(revo_mdev* m, int n, MultiTrack* pairs) {
+  if (n <= 0) return REVO_OK;
+  revo_ctx* c = m->c;
+  HIPCHECK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  FrameSet* waited[64];
+  int nw = 0;
+  for (int i = 0; i < n; ++i) {
+    FrameSet* fs = (FrameSet*)pairs[i].set;
+    const revo_pyr curr{c, fs, pairs[i].frame, false, false, 0.0, false, false};
+    fill_desc(&m->h_descs[i], &m->kf_views[pairs[i].stream], &curr, pairs[i].R, pairs[i].T);
+    bool seen = false;
+    for (int k = 0; k < nw && !seen; ++k) seen = waited[k] == fs;
+    if (!seen) {
+      if (fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ready, 0));
+      if (nw < 64) waited[nw++] = fs;
+    }
+  }
+  // the previous grid read d_descs on this stream: the copy queues behind it
+  HIPCHECK(hipMemcpyAsync(m->d_descs, m->h_descs, sizeof(PairDesc) * n, hipMemcpyHostToDevice, s));
+  if (m->mail_epoch > 0xffffffffu - 4 * 8192u) {  // the whole mailbox, before launch_track's own wrap (sized for n pairs) comes due
+    HIPCHECK(hipMemsetAsync(m->d_mail, 0, mail_bytes(m->S, m->cluster), s));
+    m->mail_epoch = 0;
+  }
+  int rc = chained_track_launch(c->device, c->knobs.track_depth, s, [&](unsigned* d_resident) {
+    return launch_track(m->d_descs, m->tp, m->d_res, nullptr, n, m->d_mail, &m->mail_epoch, m->cluster, d_resident, s);
+  });
+  if (rc) return rc;
+  HIPCHECK(hipMemcpyAsync(m->h_res, m->d_res, sizeof(revo_pair_result) * n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipEventRecord(m->ev_trk, s));
+  if ((rc = wait_event_polled(m->ev_trk))) return rc;
+  for (int i = 0; i < n; ++i) {
+    const revo_pair_result& r = m->h_res[i];
+    if (r.flags & 8)
+      return fail(REVO_ERR_HIP, "tracker: stream " + std::to_string(pairs[i].stream) + ": the workgroups of the pair could not exchange "
+                  "partial sums in time (device shared with another process?) -- its pose is not valid");
+    if ((rc = decode_track(r, pairs[i].R, pairs[i].T, nullptr, &pairs[i].status, nullptr, nullptr))) return rc;
+  }
+  return REVO_OK;
+}
+
+// assessTrackingQuality (tracker.cpp:118-201) for n streams: one mark and one count launch
+extern "C" int revo_mdev_vote_(revo_mdev* m, int n, MultiVote* votes) {
+  revo_ctx* c = m->c;
+  HIPCHECK(hipSetDevice(c->device));
+  const int nfh = m->ts.n_frames_hist_voting;
+  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;
+  HIPCHECK(hipEventSynchronize(m->ev_vdesc));  // the previous upload of the descriptors has read them
+  int nv = 0, idx[1024];
+  const LevelGeom& lv = c->geom.lv[m->hl];
+  const int use_orig = lv.has_orig;  // returnOrigEdges(lvl), imgpyramidrgbd.h:67-75
+  for (int i = 0; i < n; ++i) {
+    MultiVote& v = votes[i];
+    v.status = REVO_TRACKER_STATE_OK;
+    const std::deque<Past>& past = m->past[v.stream];
+    if (past.empty() || !m->ts.check_tracking_results) continue;  // nothing to vote on (tracker.cpp:121)
+    FrameSet* fs = (FrameSet*)v.set;
+    if (fs->has_ready && fs->ready_stream != vs) HIPCHECK(hipStreamWaitEvent(vs, fs->ev_ready, 0));
+    VoteDesc& d = m->h_vdesc[nv];
+    memset(&d, 0, sizeof(d));
+    float inv[16];
+    mat4_inverse(v.T_w_curr, inv);
+    int nframes = 0;
+    for (int fr = 0; fr < nfh && fr < (int)past.size() && fr < 3; ++fr) {
+      float tf[16];
+      mat4_mul(inv, past[fr].T_w, tf);
+      float* RT = d.RT[fr];
+      for (int cc = 0; cc < 3; ++cc) for (int r = 0; r < 3; ++r) RT[cc * 3 + r] = tf[cc * 4 + r];
+      RT[9] = tf[12]; RT[10] = tf[13]; RT[11] = tf[14];
+      d.pts[fr] = past[fr].d_pts;
+      d.n[fr] = past[fr].d_n;
+      ++nframes;
+    }
+    d.n_clouds = nframes;
+    const size_t f = (size_t)v.frame * lv.npix;
+    d.edges = (use_orig ? fs->p.edges_orig[m->hl] : fs->p.edges[m->hl]) + f;
+    d.depth = fs->p.depth[m->hl] + f;
+    d.marks = m->d_marks + (size_t)v.stream * m->cloud_cap;
+    d.hist8 = m->d_hist8 + 8 * v.stream;
+    d.done = m->d_done + v.stream;
+    d.host_out = m->h_vout + 16 * v.stream;
+    idx[nv++] = i;
+  }
+  if (!nv) return REVO_OK;
+  const unsigned seq = ++m->seq ? m->seq : ++m->seq;
+  HIPCHECK(hipMemcpyAsync(m->d_vdesc, m->h_vdesc, sizeof(VoteDesc) * nv, hipMemcpyHostToDevice, vs));
+  HIPCHECK(hipEventRecord(m->ev_vdesc, vs));
+  launch_vote_multi(c->geom, m->hl, nv, m->d_vdesc, seq, vs);
+  HIPCHECK(hipGetLastError());
+  const float wts[4] = {0.f, 1.f, 1.25f, 1.5f};  // tracker.cpp:231-234
+  for (int k = 0; k < nv; ++k) {
+    MultiVote& v = votes[idx[k]];
+    const int* o = m->h_vout + 16 * v.stream;
+    { int rc = wait_seq(vs, (volatile unsigned*)(o + 8), seq); if (rc) return rc; }
+    const int* ov = o + 4;
+    const int hsize = 1 + m->h_vdesc[k].n_clouds;
+    float overlapMeasure = 0.0f;
+    for (int j = 1; j < hsize; ++j) overlapMeasure += (ov[j] * wts[j]);
+    v.status = (overlapMeasure >= ov[0] || hsize < 4) ? REVO_TRACKER_STATE_OK : REVO_TRACKER_STATE_NEW_KF;  // tracker.cpp:184
+  }
+  return REVO_OK;
+}
+
+// mPastPcl.push_back (tracker.cpp:209-223) for n streams, one copy launch.  Only 3 + N_FRAMES_HIST_VOTING clouds of a stream
+// can ever matter: the vote reads the OLDEST min(N, 3) (tracker.cpp:138) and a keyframe change keeps the NEWEST N
+// (tracker.cpp:248-257).  Beyond that the fourth-oldest is neither and goes back to the pool (the reference keeps it).
+extern "C" int revo_mdev_add_clouds_(revo_mdev* m, int n, const MultiFrame* f) {
+  if (n <= 0) return REVO_OK;
+  revo_ctx* c = m->c;
+  HIPCHECK(hipSetDevice(c->device));
+  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;
+  HIPCHECK(hipEventSynchronize(m->ev_cdesc));
+  const size_t keep = 3 + (size_t)std::max(0, m->ts.n_frames_hist_voting);
+  for (int i = 0; i < n; ++i) {
+    FrameSet* fs = (FrameSet*)f[i].set;
+    if (fs->has_ready && fs->ready_stream != vs) HIPCHECK(hipStreamWaitEvent(vs, fs->ev_ready, 0));
+    Past p{};
+    if (!m->past_pool.empty()) { p = m->past_pool.back(); m->past_pool.pop_back(); }
+    else {
+      p.cap = m->cloud_cap;
+      HIPCHECK(hipMalloc((void**)&p.d_pts, sizeof(float4) * p.cap));
+      HIPCHECK(hipMalloc((void**)&p.d_n, sizeof(int)));
+    }
+    const size_t fr = (size_t)f[i].frame;
+    m->h_cdesc[i] = CloudCopyDesc{p.d_pts, fs->p.pts_trk[m->hl] + fr * m->cloud_cap, p.d_n, fs->p.npts + fr * REVO_L + m->hl};
+    p.n = -1;
+    memcpy(p.T_w, f[i].T_w, sizeof(float) * 16);
+    p.ts = f[i].ts;
+    std::deque<Past>& q = m->past[f[i].stream];
+    q.push_back(p);
+    // (stream-ordered reuse: the next copy into a recycled buffer runs on the vote stream behind every vote that read it)
+    if (q.size() > keep) { m->past_pool.push_back(q[3]); q.erase(q.begin() + 3); }
+  }
+  HIPCHECK(hipMemcpyAsync(m->d_cdesc, m->h_cdesc, sizeof(CloudCopyDesc) * n, hipMemcpyHostToDevice, vs));
+  HIPCHECK(hipEventRecord(m->ev_cdesc, vs));
+  launch_copy_cloud_multi(n, m->d_cdesc, vs);
+  HIPCHECK(hipGetLastError());
+  return REVO_OK;
+}
+
+// keep < 0: N_FRAMES_HIST_VOTING (clearPastLists, tracker.cpp:248-257); 0: a reset
+extern "C" void revo_mdev_clear_past_(revo_mdev* m, int stream, int keep) {
+  if (keep < 0) keep = m->ts.n_frames_hist_voting;
+  std::deque<Past>& q = m->past[stream];
+  while ((int)q.size() > std::max(0, keep)) { m->past_pool.push_back(q.front()); q.pop_front(); }
+}
+
+// kfPyr = prevPyr; kfPyr->makeKeyframe() (system.cpp:205-215) for n streams: the frames' planes into the streams' keyframe
+// slots (one copy launch), then the distance transforms of each slot
+extern "C" int revo_mdev_promote_(revo_mdev* m, int n, const MultiFrame* f) {
+  if (n <= 0) return REVO_OK;
+  revo_ctx* c = m->c;
+  HIPCHECK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const PyrGeom& g = c->geom;
+  std::vector<CopySeg> segs;
+  for (int i = 0; i < n; ++i) {
+    FrameSet* src = (FrameSet*)f[i].set;
+    if (src->has_ready && src->ready_stream != s) HIPCHECK(hipStreamWaitEvent(s, src->ev_ready, 0));
+    const size_t sf = (size_t)f[i].frame, df = (size_t)f[i].stream;
+    const FramePlanes& a = src->p;
+    const FramePlanes& b = m->kf->p;
+    auto add = [&](const void* sp, void* dp, size_t per_frame) {
+      if (per_frame) segs.push_back(CopySeg{(const char*)sp + sf * per_frame, (char*)dp + df * per_frame, per_frame});
+    };
+    for (int l = 0; l < g.n_levels; ++l) {
+      const LevelGeom& v = g.lv[l];
+      const size_t np = (size_t)v.npix, words = (size_t)v.h * v.wpr, cols = (size_t)v.w * v.nchunk;
+      add(a.gray[l], b.gray[l], np);
+      add(a.depth[l], b.depth[l], np * 4);
+      add(a.cs[l], b.cs[l], words * 8);
+      add(a.edges[l], b.edges[l], np);
+      add(a.edges_orig[l], b.edges_orig[l], np);
+      add(a.pts_trk[l], b.pts_trk[l], np * 16);
+      if (v.patch > 0) add(a.hist[l], b.hist[l], (size_t)v.hist_w * v.hist_h);
+      add(a.chunk[l], b.chunk[l], cols * 4);
+      add(a.cmask[l], b.cmask[l], cols * 4);
+      if (l < g.n_levels - 1) add(a.vb[l], b.vb[l], np / 8);
+    }
+    add(a.npts, b.npts, sizeof(int) * REVO_L);
+    add(a.hist_nz, b.hist_nz, sizeof(int) * REVO_L);
+    add(a.strip_tot, b.strip_tot, sizeof(int) * (size_t)g.total_strips);
+    add(a.tile_base, b.tile_base, sizeof(int) * (size_t)g.total_tiles);
+    add(src->d_bgr, m->kf->d_bgr, (size_t)g.lv[0].npix * 3);  // rgbFullSize (the coloured cloud)
+  }
+  HIPCHECK(hipEventSynchronize(m->ev_segs));
+  if (segs.size() > m->seg_cap) {
+    (void)hipHostFree(m->h_segs); (void)hipFree(m->d_segs);
+    m->h_segs = nullptr; m->d_segs = nullptr; m->seg_cap = 0;
+    HIPCHECK(hipHostMalloc((void**)&m->h_segs, sizeof(CopySeg) * segs.size()));
+    HIPCHECK(hipMalloc((void**)&m->d_segs, sizeof(CopySeg) * segs.size()));
+    m->seg_cap = segs.size();
+  }
+  memcpy(m->h_segs, segs.data(), sizeof(CopySeg) * segs.size());
+  HIPCHECK(hipMemcpyAsync(m->d_segs, m->h_segs, sizeof(CopySeg) * segs.size(), hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(m->ev_segs, s));
+  launch_copy_segments((int)segs.size(), m->d_segs, s);
+  for (int i = 0; i < n; ++i) {
+    launch_keyframe(g, m->kf->p, f[i].stream, 1, 1, s);
+    revo_pyr& v = m->kf_views[f[i].stream];
+    v.ts = f[i].ts; v.table_built = false; v.ref_list_built = false;
+  }
+  HIPCHECK(hipGetLastError());
+  return REVO_OK;
+}
+
+extern "C" revo_pyr* revo_mdev_keyframe_(revo_mdev* m, int stream) { return &m->kf_views[stream]; }

@@ -2230,6 +2230,89 @@ __global__ void __launch_bounds__(256) k_copy_cloud(float4* __restrict__ dst, co
   if (blockIdx.x == 0 && threadIdx.x == 0) *dst_n = n;
 }
 
+// ---------------------------------------------------------------------------
+// revo_vo_multi: the quality vote, the past-cloud copy and the keyframe promotion of many streams in one launch each.
+// blockIdx.y (mark: blockIdx.z) = stream entry; every entry has its own marks plane, counters and host record, so the counts
+// are those of k_vote_mark / k_vote_hist on that stream alone (same arithmetic, same operation order).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_vote_mark_multi(const VoteDesc* __restrict__ descs, float fx, float fy, float cx,
+                                                         float cy, int W, int H) {
+  const VoteDesc& d = descs[blockIdx.z];
+  const int c = blockIdx.y;
+  if (c >= d.n_clouds) return;
+  const int n = *d.n[c];
+  const float* R = d.RT[c];
+  const float* T = R + 9;
+  const float4* pts = d.pts[c];
+  int* marks = d.marks;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const float4 p = pts[i];
+    float q[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = ((R[r] * p.x + R[3 + r] * p.y) + R[6 + r] * p.z) + T[r];
+    const float u = __fdiv_rn(fx * q[0], q[2]) + cx;  // tracker.cpp:153-154 operation order
+    const float v = __fdiv_rn(fy * q[1], q[2]) + cy;
+    if (u >= 0 && u < (float)W && v >= 0 && v < (float)H)
+      atomicOr(&marks[(int)floorf(v) * W + (int)floorf(u)], 1 << c);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_vote_hist_multi(const VoteDesc* __restrict__ descs, int npix, float dmin, float dmax,
+                                                         unsigned seq_val) {
+  const VoteDesc& d = descs[blockIdx.y];
+  int* marks = d.marks;
+  __shared__ int s_h[8];
+  __shared__ bool s_last;
+  if (threadIdx.x < 8) s_h[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
+    const int m = marks[i];
+    if (m) marks[i] = 0;
+    const float Z = d.depth[i];
+    if (depth_ok(Z, dmin, dmax)) {
+      const int val = __popc(m);
+      atomicAdd(&s_h[val], 1);
+      if (d.edges[i] > 0) atomicAdd(&s_h[4 + val], 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 8 && s_h[threadIdx.x]) atomicAdd(&d.hist8[threadIdx.x], s_h[threadIdx.x]);
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = (atomicAdd(d.done, 1u) == gridDim.x - 1);
+  __syncthreads();
+  if (s_last) {
+    if (threadIdx.x < 8) d.host_out[threadIdx.x] = atomicExch(&d.hist8[threadIdx.x], 0);
+    if (threadIdx.x == 0) *d.done = 0u;
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) *(volatile int*)&d.host_out[8] = (int)seq_val;  // the host polls this word
+  }
+}
+
+__global__ void __launch_bounds__(256) k_copy_cloud_multi(const CloudCopyDesc* __restrict__ descs) {
+  const CloudCopyDesc& d = descs[blockIdx.y];
+  const int n = *d.src_n;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d.dst[i] = d.src[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *d.dst_n = n;
+}
+
+// byte ranges (one per plane of a promoted frame): 16-byte words where both ends and the size allow, bytes otherwise
+__global__ void __launch_bounds__(256) k_copy_segments(const CopySeg* __restrict__ segs) {
+  const CopySeg& sg = segs[blockIdx.y];
+  const char* src = (const char*)sg.src;
+  char* dst = (char*)sg.dst;
+  const size_t bytes = sg.bytes;
+  const size_t step = (size_t)gridDim.x * 256;
+  if ((((uintptr_t)src | (uintptr_t)dst | bytes) & 15) == 0) {
+    const uint4* s4 = (const uint4*)src;
+    uint4* d4 = (uint4*)dst;
+    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < bytes / 16; i += step) d4[i] = s4[i];
+  } else {
+    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < bytes; i += step) dst[i] = src[i];
+  }
+}
+
 }  // namespace
 
 // ============================ launchers =====================================
@@ -2422,4 +2505,19 @@ void launch_vote(const PyrGeom& g, const FramePlanes& curr, int curr_frame, int 
 
 void launch_copy_cloud(float4* dst, const float4* src, int* dst_n, const int* src_n, hipStream_t s) {
   hipLaunchKernelGGL(k_copy_cloud, dim3(16), dim3(256), 0, s, dst, src, dst_n, src_n);
+}
+
+void launch_vote_multi(const PyrGeom& g, int lvl, int n, const VoteDesc* d_descs, unsigned seq_val, hipStream_t s) {
+  // every entry's marks, counters and done word are all-zero on entry (zeroed at allocation, left clean by k_vote_hist_multi)
+  const LevelGeom& lv = g.lv[lvl];
+  hipLaunchKernelGGL(k_vote_mark_multi, dim3(32, 3, n), dim3(256), 0, s, d_descs, lv.fx, lv.fy, lv.cx, lv.cy, lv.w, lv.h);
+  hipLaunchKernelGGL(k_vote_hist_multi, dim3(16, n), dim3(256), 0, s, d_descs, lv.npix, g.depth_min, g.depth_max, seq_val);
+}
+
+void launch_copy_cloud_multi(int n, const CloudCopyDesc* d_descs, hipStream_t s) {
+  hipLaunchKernelGGL(k_copy_cloud_multi, dim3(16, n), dim3(256), 0, s, d_descs);
+}
+
+void launch_copy_segments(int n, const CopySeg* d_segs, hipStream_t s) {
+  hipLaunchKernelGGL(k_copy_segments, dim3(64, n), dim3(256), 0, s, d_segs);
 }

@@ -1,0 +1,274 @@
+// revo_vo_multi.hip -- many independent REVO::start streams (system/system.cpp:84-305) advanced in lockstep.
+// Host-only code: per stream the state of revo_vo.hip (keyframe, previous frame, the last two poses, the constant-velocity
+// initialisation); the device work of a step -- one tracker grid, one quality vote, one cloud copy, the keyframe promotions --
+// is what revo_mdev_* (revo_host.hip) enqueue for all streams at once.  No look-ahead: a step waits for its grid and its vote.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <string>
+#include <vector>
+
+#include "../../include/revo_hip.h"
+#include "revo_mat4.h"
+#include "revo_multi.h"
+
+extern "C" void revo_ctx_retain_(revo_ctx*);
+extern "C" void revo_ctx_release_(revo_ctx*);
+extern "C" void revo_set_error_(const char* msg);
+
+namespace {
+struct M4 {  // column-major 4x4, Eigen::Matrix4f storage
+  float m[16];
+  static M4 identity() { M4 o; memset(o.m, 0, sizeof(o.m)); o.m[0] = o.m[5] = o.m[10] = o.m[15] = 1.f; return o; }
+};
+M4 mul(const M4& A, const M4& B) { M4 o; mat4_mul(A.m, B.m, o.m); return o; }
+M4 inverse(const M4& A) { M4 o; mat4_inverse(A.m, o.m); return o; }
+M4 from_RT(const float* R, const float* T) {  // transformFromRT
+  M4 o = M4::identity();
+  for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) o.m[c * 4 + r] = R[c * 3 + r];
+  o.m[12] = T[0]; o.m[13] = T[1]; o.m[14] = T[2];
+  return o;
+}
+void to_RT(const M4& M, float* R, float* T) {
+  for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) R[c * 3 + r] = M.m[c * 4 + r];
+  T[0] = M.m[12]; T[1] = M.m[13]; T[2] = M.m[14];
+}
+struct Pose { M4 T_kf_curr, T_w_kf; M4 world() const { return mul(T_w_kf, T_kf_curr); } };  // REVO::Pose, system.h:89-152
+struct Ref { void* set; int frame; double ts; };  // a frame of a step set
+int bad(int code, const char* msg) { revo_set_error_(msg); return code; }
+
+// revo_vo's per-driver state, per stream
+struct Stream {
+  std::deque<Ref> queue;
+  bool has_prev = false;
+  Ref prev{nullptr, 0, 0.0};
+  M4 T_w_kf = M4::identity();
+  Pose last{M4::identity(), M4::identity()}, before_last{M4::identity(), M4::identity()};
+  M4 T_NM1_N = M4::identity();
+  float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0};
+  int no_frames = 0, n_keyframes = 0;
+  bool just_added_kf = false;
+  bool retrack = false;  // a keyframe change is owed its re-track of `cur` (the step after the vote that asked for it)
+  Ref cur{nullptr, 0, 0.0};
+};
+}  // namespace
+
+struct revo_vo_multi {
+  revo_ctx* ctx = nullptr;
+  revo_mdev* dev = nullptr;
+  int S = 0, max_queue = 1;
+  std::vector<Stream> st;
+  std::vector<std::pair<void*, int>> refs;  // step sets and how many queued / current / previous frames still point into them
+};
+
+static void ref_add(revo_vo_multi* m, void* set) {
+  for (auto& r : m->refs) if (r.first == set) { ++r.second; return; }
+  m->refs.push_back({set, 1});
+}
+static void ref_drop(revo_vo_multi* m, void* set) {
+  for (size_t k = 0; k < m->refs.size(); ++k)
+    if (m->refs[k].first == set) {
+      if (--m->refs[k].second == 0) { revo_mdev_release_set_(m->dev, set); m->refs.erase(m->refs.begin() + k); }
+      return;
+    }
+}
+
+extern "C" int revo_vo_multi_create(revo_ctx* ctx, int n_streams, int max_queue, revo_vo_multi** out) {
+  if (!ctx || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (n_streams < 1 || n_streams > 1024) return bad(REVO_ERR_INVALID_ARG, "n_streams must be 1..1024");
+  if (max_queue < 1) return bad(REVO_ERR_INVALID_ARG, "max_queue must be >= 1");
+  revo_mdev* d = nullptr;
+  const int rc = revo_mdev_create_(ctx, n_streams, &d);
+  if (rc) return rc;
+  revo_vo_multi* m = new revo_vo_multi();
+  m->ctx = ctx;
+  revo_ctx_retain_(ctx);
+  m->dev = d;
+  m->S = n_streams;
+  m->max_queue = max_queue;
+  m->st.resize(n_streams);
+  *out = m;
+  return REVO_OK;
+}
+
+extern "C" void revo_vo_multi_destroy(revo_vo_multi* m) {
+  if (!m) return;
+  revo_mdev_destroy_(m->dev);  // (synchronises the context's streams; the step sets go with it)
+  revo_ctx_release_(m->ctx);
+  delete m;
+}
+
+static bool stream_ok(const revo_vo_multi* m, int s) { return m && s >= 0 && s < m->S; }
+
+extern "C" int revo_vo_multi_pending(const revo_vo_multi* m, int s) {
+  if (!stream_ok(m, s)) return -1;
+  return (int)m->st[s].queue.size() + (m->st[s].retrack ? 1 : 0);
+}
+extern "C" int revo_vo_multi_num_keyframes(const revo_vo_multi* m, int s) { return stream_ok(m, s) ? m->st[s].n_keyframes : -1; }
+
+extern "C" int revo_vo_multi_keyframe(const revo_vo_multi* m, int s, revo_pyr** kf, float T_w_kf[16]) {
+  if (!stream_ok(m, s)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
+  if (m->st[s].n_keyframes == 0) return bad(REVO_ERR_INVALID_ARG, "the stream has no keyframe yet");
+  if (kf) *kf = revo_mdev_keyframe_(m->dev, s);
+  if (T_w_kf) memcpy(T_w_kf, m->st[s].T_w_kf.m, sizeof(float) * 16);
+  return REVO_OK;
+}
+
+// a new sequence on this stream: REVO::start's fresh TrackerNew and empty pose graph (system.cpp:107)
+extern "C" int revo_vo_multi_reset(revo_vo_multi* m, int s) {
+  if (!stream_ok(m, s)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
+  Stream& x = m->st[s];
+  if (!x.queue.empty() || x.retrack) return bad(REVO_ERR_INVALID_ARG, "the stream still has frames pending");
+  if (x.has_prev) ref_drop(m, x.prev.set);
+  revo_mdev_clear_past_(m->dev, s, 0);
+  x = Stream();
+  return REVO_OK;
+}
+
+extern "C" int revo_vo_multi_submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16,
+                                    double depth_scale_factor) {
+  if (!m || n < 0 || (n > 0 && !frames)) return bad(REVO_ERR_INVALID_ARG, "bad argument");
+  if (n == 0) return REVO_OK;
+  if (depth_is_u16 && !(depth_scale_factor > 0)) return bad(REVO_ERR_INVALID_ARG, "depth_scale_factor must be > 0");
+  if (n > m->S) return bad(REVO_ERR_INVALID_ARG, "more frames than streams");
+  std::vector<char> seen(m->S, 0);
+  for (int i = 0; i < n; ++i) {
+    const revo_stream_frame& f = frames[i];
+    if (!stream_ok(m, f.stream)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
+    if (seen[f.stream]) return bad(REVO_ERR_INVALID_ARG, "two frames for one stream in one submit");
+    seen[f.stream] = 1;
+    if (!f.bgr || !f.depth) return bad(REVO_ERR_INVALID_ARG, "null image pointer");
+  }
+  // strides are checked here, before anything is uploaded: a failed submit leaves every queue as it was
+  float cam[6];
+  { const int rc = revo_ctx_camera(m->ctx, 0, cam); if (rc) return rc; }
+  const size_t w = (size_t)cam[4];
+  for (int i = 0; i < n; ++i)
+    if (frames[i].bgr_stride < w * 3 || frames[i].depth_stride < w * (depth_is_u16 ? 2 : 4))
+      return bad(REVO_ERR_INVALID_ARG, "stride smaller than a row");
+  for (int i = 0; i < n; ++i)
+    if (revo_vo_multi_pending(m, frames[i].stream) >= m->max_queue)
+      return bad(REVO_ERR_CAPACITY, "the stream's queue is full: call revo_vo_multi_step first");
+  void* set = nullptr;
+  const int rc = revo_mdev_submit_(m->dev, n, frames, depth_is_u16, depth_scale_factor, &set);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i) {
+    m->st[frames[i].stream].queue.push_back(Ref{set, i, frames[i].timestamp});
+    ref_add(m, set);
+  }
+  return REVO_OK;
+}
+
+// One body of the while loop of REVO::start (system.cpp:128-284) for every stream that has work, in revo_vo_track_next's order.
+extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int* n_out) {
+  if (!m || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (n_out) *n_out = 0;
+  const M4 I = M4::identity();
+  std::vector<MultiTrack> trk;
+  std::vector<MultiFrame> promote, clouds;
+  std::vector<int> first;  // streams whose first frame becomes their keyframe this step
+  int n_res = 0;
+  auto report = [&](int s, const M4& pose, int new_kf, double ts) {
+    revo_stream_result& r = out[n_res++];
+    r.stream = s; r.new_keyframe = new_kf; r.timestamp = ts;
+    memcpy(r.pose, pose.m, sizeof(pose.m));
+  };
+  for (int s = 0; s < m->S; ++s) {
+    Stream& x = m->st[s];
+    if (x.retrack) {  // the frame whose vote asked for a keyframe, against the new one, initialised with T_NM1_N (system.cpp:217-221)
+      MultiTrack t{s, x.cur.set, x.cur.frame, {}, {}, 0};
+      memcpy(t.R, x.R, sizeof(t.R)); memcpy(t.T, x.T, sizeof(t.T));
+      trk.push_back(t);
+      continue;
+    }
+    if (x.queue.empty()) continue;
+    x.cur = x.queue.front();
+    x.queue.pop_front();
+    if (x.no_frames == 0) {  // system.cpp:151-175: the first frame is the keyframe
+      first.push_back(s);
+      continue;
+    }
+    ++x.no_frames;
+    MultiTrack t{s, x.cur.set, x.cur.frame, {}, {}, 0};
+    memcpy(t.R, x.R, sizeof(t.R)); memcpy(t.T, x.T, sizeof(t.T));
+    trk.push_back(t);
+  }
+  int rc = revo_mdev_track_(m->dev, (int)trk.size(), trk.data());
+  if (rc) return rc;
+  // the votes of the streams that tracked a new frame (a re-track's second vote is discarded by revo_vo: not run here)
+  std::vector<MultiVote> votes;
+  std::vector<M4> T_KF_N(trk.size()), world(trk.size());
+  for (size_t k = 0; k < trk.size(); ++k) {
+    Stream& x = m->st[trk[k].stream];
+    memcpy(x.R, trk[k].R, sizeof(x.R)); memcpy(x.T, trk[k].T, sizeof(x.T));
+    T_KF_N[k] = from_RT(x.R, x.T);
+    world[k] = mul(x.T_w_kf, T_KF_N[k]);
+    if (!x.retrack) {
+      MultiVote v{trk[k].stream, trk[k].set, trk[k].frame, {}, 0};
+      memcpy(v.T_w_curr, world[k].m, sizeof(v.T_w_curr));
+      votes.push_back(v);
+    }
+  }
+  if ((rc = revo_mdev_vote_(m->dev, (int)votes.size(), votes.data()))) return rc;
+  size_t vk = 0;
+  for (size_t k = 0; k < trk.size(); ++k) {
+    const int s = trk[k].stream;
+    Stream& x = m->st[s];
+    int new_kf = 0;
+    if (x.retrack) {
+      x.retrack = false;
+      x.just_added_kf = true;
+      new_kf = 1;
+    } else {
+      const int status = votes[vk++].status;
+      if (status == REVO_TRACKER_STATE_NEW_KF && !x.just_added_kf) {  // system.cpp:203-241, the re-track deferred to the next step
+        x.T_w_kf = x.last.world();  // kfPyr->setTwf(mPoseGraph.back().getCurrToWorld())
+        promote.push_back(MultiFrame{s, x.prev.set, x.prev.frame, {}, x.prev.ts});
+        x.last = Pose{I, x.T_w_kf};  // mPoseGraph.back().setKfFrame(kfPyr)
+        ++x.n_keyframes;
+        revo_mdev_clear_past_(m->dev, s, -1);  // clearPastLists: the newest N_FRAMES_HIST_VOTING stay
+        to_RT(x.T_NM1_N, x.R, x.T);
+        x.retrack = true;
+        continue;
+      }
+      x.just_added_kf = false;
+    }
+    x.before_last = x.last;
+    x.last = Pose{T_KF_N[k], x.T_w_kf};  // mPoseGraph.push_back(Pose(T_KF_N, ts, kfPyr))
+    MultiFrame cl{s, x.cur.set, x.cur.frame, {}, x.cur.ts};
+    memcpy(cl.T_w, world[k].m, sizeof(cl.T_w));
+    clouds.push_back(cl);
+    // T_NM1_N = graph[size-2].T_N_W() * graph.back().T_W_N(); T_init = back().T_kf_N() * T_NM1_N (system.cpp:267-271)
+    const M4 w1 = x.last.world();
+    x.T_NM1_N = mul(inverse(x.before_last.world()), w1);
+    to_RT(mul(x.last.T_kf_curr, x.T_NM1_N), x.R, x.T);
+    report(s, w1, new_kf, x.cur.ts);
+    if (x.has_prev) ref_drop(m, x.prev.set);  // prevPyr = currPyr
+    x.prev = x.cur;
+    x.has_prev = true;
+  }
+  for (int s : first) {
+    Stream& x = m->st[s];
+    x.T_w_kf = I;
+    promote.push_back(MultiFrame{s, x.cur.set, x.cur.frame, {}, x.cur.ts});
+    x.last = Pose{I, I};
+    ++x.n_keyframes;
+    ++x.no_frames;
+    x.just_added_kf = true;
+    MultiFrame cl{s, x.cur.set, x.cur.frame, {}, x.cur.ts};
+    memcpy(cl.T_w, I.m, sizeof(cl.T_w));
+    clouds.push_back(cl);
+    report(s, I, 1, x.cur.ts);
+    x.prev = x.cur;
+    x.has_prev = true;
+  }
+  if ((rc = revo_mdev_promote_(m->dev, (int)promote.size(), promote.data()))) return rc;
+  if ((rc = revo_mdev_add_clouds_(m->dev, (int)clouds.size(), clouds.data()))) return rc;
+  // results come out in stream order
+  std::vector<revo_stream_result> tmp(out, out + n_res);
+  std::sort(tmp.begin(), tmp.end(), [](const revo_stream_result& a, const revo_stream_result& b) { return a.stream < b.stream; });
+  std::copy(tmp.begin(), tmp.end(), out);
+  if (n_out) *n_out = n_res;
+  return REVO_OK;
+}

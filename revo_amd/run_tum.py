@@ -1,6 +1,9 @@
 """`python -m revo_amd.run_tum <settings.yaml> <dataset.yaml>` -- the reference's command line
 (main.cpp:22-47: REVO <settings.yaml> <dataset.yaml>) for TUM-layout datasets: runs the sequential
-VO on one GPU and writes poses_<dataset>.txt in TUM format (system.cpp:48-49,76-80)."""
+VO on one GPU and writes poses_<dataset>.txt in TUM format (system.cpp:48-49,76-80).
+
+--streams N runs the YAML's Datasets list N at a time through one vo.MultiREVO handle (a finished dataset's stream takes the
+next one) and writes the same poses_<dataset>.txt files; the PNG decoders are split among the datasets that run at once."""
 import os
 import sys
 import time
@@ -11,7 +14,8 @@ import numpy as np
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
-        print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N]")
+        print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
+              "[--streams N]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -24,11 +28,25 @@ def main(argv=None):
         i = argv.index("--decoders")
         decoders = int(argv[i + 1])
         argv = argv[:i] + argv[i + 2:]
+    streams = 0  # > 0: the Datasets list N at a time through one multi-stream handle
+    if "--streams" in argv:
+        i = argv.index("--streams")
+        streams = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+        if streams < 1:
+            print("--streams needs a positive number of streams")
+            return 2
+        if model_dir is not None:
+            print("--save-model is not supported together with --streams: the model export runs on the sequential driver only "
+                  "(drop --streams to export the model)")
+            return 2
     from .settings import OptimizerSettings
     trk_settings, use_edge_filter, sysd = config.load_settings_yaml(argv[0])
     pyr_settings, io = config.load_dataset_yaml(argv[1])
     device = int(argv[2]) if len(argv) > 2 else 0
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
+    if streams:
+        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device)
@@ -57,18 +75,61 @@ def main(argv=None):
         if drawer is not None:
             out = drawer.saveModel(os.path.join(model_dir, name) if len(io["datasets"]) > 1 else model_dir)
             print("model: %d points of %d keyframes -> %s, %s" % (drawer.nPts, len(drawer.vpKfsF), out[0], out[1]))
-        gt_file = os.path.join(folder, "groundtruth.txt")  # positions only: ATE (the RPE evaluator needs full poses)
-        if os.path.exists(gt_file):
-            gt = tum.read_groundtruth_positions(gt_file)
-            est, ref = [], []
-            for ts, M in drv.poses:
-                if round(ts, 6) in gt:
-                    est.append(M)
-                    G = np.eye(4)
-                    G[:3, 3] = gt[round(ts, 6)]
-                    ref.append(G)
-            if len(est) > 2:
-                print("ATE RMSE vs groundtruth.txt: %.4f m over %d poses" % (synth.ate_rmse(est, ref), len(est)))
+        _report_ate(folder, drv.poses)
+    return 0
+
+
+def _report_ate(folder, poses):
+    gt_file = os.path.join(folder, "groundtruth.txt")  # positions only: ATE (the RPE evaluator needs full poses)
+    if os.path.exists(gt_file):
+        from . import synth, tum
+        gt = tum.read_groundtruth_positions(gt_file)
+        est, ref = [], []
+        for ts, M in poses:
+            if round(ts, 6) in gt:
+                est.append(M)
+                G = np.eye(4)
+                G[:3, 3] = gt[round(ts, 6)]
+                ref.append(G)
+        if len(est) > 2:
+            print("ATE RMSE vs groundtruth.txt: %.4f m over %d poses" % (synth.ate_rmse(est, ref), len(est)))
+
+
+def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders):
+    """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
+    from . import tum, vo
+    names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
+    folders = [os.path.join(io["main_folder"], ds) for ds in io["datasets"]]
+    nd = tum.default_decoders() if decoders is None else decoders
+    per = max(1, nd // max(1, min(streams, len(folders)))) if nd >= 1 else 0  # decoders of one running dataset
+
+    def frames(folder):  # opened when the dataset's stream first asks for a frame, closed when it has none left
+        if per >= 1:
+            rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
+                                      read_n_images=io["read_n_images"])
+            with tum.DecodePool(folder, rows, pyr_settings.width, pyr_settings.height, workers=per,
+                                use_depth_timestamp=bool(io["use_depth_timestamp"])) as pool:
+                for f in pool:
+                    yield f
+        else:
+            for f in tum.frames(folder, io["associate"], bool(io["use_depth_timestamp"]),
+                                skip_first_n_frames=io["skip_first_n_frames"], read_n_images=io["read_n_images"]):
+                yield f
+
+    drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"])
+    t0 = time.perf_counter()
+    res = drv.run([frames(f) for f in folders])
+    dt = time.perf_counter() - t0
+    total = 0
+    for name, folder, r in zip(names, folders, res):
+        if sysd["do_output_poses"]:
+            with open("poses_%s.txt" % name, "w") as f:
+                f.write("\n".join(r.tum_lines()) + "\n")
+        total += len(r)
+        print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
+        _report_ate(folder, r.poses)
+    print("%d datasets on %d streams: %.1f frames/s (incl. PNG decode, %s)"
+          % (len(folders), streams, total / dt, ("%d decoder processes per dataset" % per) if per else "decoded on this thread"))
     return 0
 
 

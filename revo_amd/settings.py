@@ -125,6 +125,21 @@ class PairResult(C.Structure):
 assert C.sizeof(PairResult) == 96
 
 
+class StreamFrame(C.Structure):
+    """revo_stream_frame (include/revo_hip.h): one frame of one stream of revo_vo_multi, host memory."""
+    _fields_ = [
+        ("stream", C.c_int32), ("bgr", C.c_void_p), ("bgr_stride", C.c_size_t),
+        ("depth", C.c_void_p), ("depth_stride", C.c_size_t), ("timestamp", C.c_double),
+    ]
+
+
+class StreamResult(C.Structure):
+    """revo_stream_result (include/revo_hip.h): the pose revo_vo_multi_step reports for one stream."""
+    _fields_ = [
+        ("stream", C.c_int32), ("new_keyframe", C.c_int32), ("timestamp", C.c_double), ("pose", C.c_float * 16),
+    ]
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

@@ -7,8 +7,9 @@ frame N+1 is built while frame N is tracked), `track_next` one body of the consu
 is submit + track_next (no look-ahead); `run` drives both sides like the reference: a producer
 (IO) thread feeding a bounded queue and the consumer loop on the calling thread.
 
-Single stream = one GPU (frame N's initial pose and keyframe depend on frame N-1); see
-api.BatchTracker for the throughput mode.
+Single stream = one GPU (frame N's initial pose and keyframe depend on frame N-1); MultiREVO runs many
+independent sequences at once (one tracker grid per step for all of them), api.BatchTracker is the frame-pair
+throughput mode.
 """
 import ctypes as C
 
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import _lib, api
 from ._lib import check, f32p, u16p, u8p, vp
-from .settings import TrackerSettings
+from .settings import StreamFrame, StreamResult, TrackerSettings
 
 
 class REVO:
@@ -144,13 +145,173 @@ class REVO:
         return out
 
     def tum_lines(self):
-        """REVO::writePose, system.cpp:76-80: 'ts tx ty tz qx qy qz qw', std::fixed.  The stream's precision is set to 9
-        AFTER the time stamp has been written and stays set (std::setprecision is sticky): the first line carries the time
-        stamp with the default 6 decimals, every later line with 9 -- reproduced as the reference's file has it."""
-        out = []
-        for i, (ts, M) in enumerate(self.poses):
-            q = _quat_xyzw(M[:3, :3])
-            out.append(("%.6f" if i == 0 else "%.9f") % ts + " %.9f %.9f %.9f %.9f %.9f %.9f %.9f" % (tuple(M[:3, 3]) + tuple(q)))
+        """REVO::writePose, system.cpp:76-80 (see tum_lines below)."""
+        return tum_lines(self.poses)
+
+
+def tum_lines(poses):
+    """REVO::writePose, system.cpp:76-80: 'ts tx ty tz qx qy qz qw', std::fixed, for [(timestamp, 4x4 pose)].  The stream's
+    precision is set to 9 AFTER the time stamp has been written and stays set (std::setprecision is sticky): the first line
+    carries the time stamp with the default 6 decimals, every later line with 9 -- reproduced as the reference's file has it."""
+    out = []
+    for i, (ts, M) in enumerate(poses):
+        q = _quat_xyzw(M[:3, :3])
+        out.append(("%.6f" if i == 0 else "%.9f") % ts + " %.9f %.9f %.9f %.9f %.9f %.9f %.9f" % (tuple(M[:3, 3]) + tuple(q)))
+    return out
+
+
+class SequenceResult(list):
+    """One sequence of MultiREVO.run: [(4x4 pose, new_keyframe)] in frame order, `poses` [(timestamp, 4x4)], tum_lines()."""
+
+    def __init__(self):
+        super().__init__()
+        self.poses = []
+
+    def tum_lines(self):
+        return tum_lines(self.poses)
+
+
+class MultiREVO:
+    """Many independent sequences at once (revo_vo_multi_* in include/revo_hip.h): n_streams REVO::start loops advanced in
+    lockstep, one tracker grid and one quality vote per step for all of them.  Per stream the poses, keyframe decisions and
+    time stamps are those of a REVO on that sequence alone.
+
+    The tracker settings are a snapshot taken when the handle is created.
+
+    submit([(stream, bgr, depth, timestamp), ...]) queues at most one frame per stream (one batched build), step() runs one
+    loop body for every stream with work and returns [(stream, 4x4 pose, new_keyframe, timestamp)].  A keyframe change is
+    reported one step late: the step whose vote asks for it reports nothing for that stream, the next one reports the frame
+    (re-tracked against the new keyframe) with new_keyframe = True."""
+
+    def __init__(self, settingsPyr, n_streams, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
+                 max_queue=2):
+        self.settingsPyr = settingsPyr
+        self.settingsTracker = settingsTracker or TrackerSettings()
+        if cameraPyr is None:
+            self.camPyr = api.CameraPyr(settingsPyr, device=device)
+            self.mTracker = api.TrackerNew(self.settingsTracker, settingsPyr, self.camPyr)  # the context's tracker settings
+        else:
+            # A context handed in may be shared with a running REVO: setting its tracker would clear that driver's past clouds
+            # and change its settings.  The handle takes the context's tracker settings as they are.
+            if settingsTracker is not None:
+                raise ValueError("MultiREVO on a given cameraPyr uses that context's tracker settings: pass settingsTracker=None")
+            self.camPyr = cameraPyr
+        self.n_streams = int(n_streams)
+        self.max_queue = int(max_queue)
+        self.depth_scale_factor = depth_scale_factor  # set: depth arrives as raw uint16
+        self._h = vp()
+        check(_lib.lib().revo_vo_multi_create(self.camPyr._h, self.n_streams, self.max_queue, C.byref(self._h)))
+        self._out = (StreamResult * self.n_streams)()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.lib().revo_vo_multi_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def submit(self, frames):
+        """frames: [(stream, bgr, depth, timestamp)], at most one per stream; all f32 metres or (depth_scale_factor set) all
+        raw uint16."""
+        frames = list(frames)
+        if not frames:
+            return
+        w, h = self.settingsPyr.width, self.settingsPyr.height
+        u16 = self.depth_scale_factor is not None and np.asarray(frames[0][2]).dtype == np.uint16
+        arr = (StreamFrame * len(frames))()
+        keep = []
+        for i, (s, bgr, depth, ts) in enumerate(frames):
+            bgr = np.ascontiguousarray(bgr, np.uint8)
+            depth = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32)
+            if bgr.shape != (h, w, 3) or depth.shape != (h, w):
+                raise ValueError("image size does not match the settings")
+            keep += [bgr, depth]
+            arr[i].stream = int(s)
+            arr[i].bgr, arr[i].bgr_stride = bgr.ctypes.data, w * 3
+            arr[i].depth, arr[i].depth_stride = depth.ctypes.data, w * depth.itemsize
+            arr[i].timestamp = float(ts)
+        check(_lib.lib().revo_vo_multi_submit(self._h, len(frames), arr, 1 if u16 else 0,
+                                              float(self.depth_scale_factor) if u16 else 0.0))
+
+    def step(self):
+        n = C.c_int()
+        check(_lib.lib().revo_vo_multi_step(self._h, self._out, C.byref(n)))
+        res = []
+        for r in self._out[:n.value]:
+            M = np.ctypeslib.as_array(r.pose).reshape(4, 4).T.copy()
+            res.append((int(r.stream), M, bool(r.new_keyframe), float(r.timestamp)))
+        return res
+
+    def pending(self, stream):
+        return _lib.lib().revo_vo_multi_pending(self._h, int(stream))
+
+    def reset(self, stream):
+        check(_lib.lib().revo_vo_multi_reset(self._h, int(stream)))
+
+    def nKeyFrames(self, stream):
+        return _lib.lib().revo_vo_multi_num_keyframes(self._h, int(stream))
+
+    def keyframe(self, stream):
+        """(kfPyr, getTransKFtoWorld()) of one stream; the pyramid is borrowed -- valid until the next step."""
+        hp = vp()
+        T = np.empty(16, np.float32)
+        check(_lib.lib().revo_vo_multi_keyframe(self._h, int(stream), C.byref(hp), T.ctypes.data_as(f32p)))
+        pyr = api.ImgPyramidRGBD(self.settingsPyr, self.camPyr, _handle=hp, _owned=False)
+        pyr._vo = self
+        return pyr, T.reshape(4, 4).T.copy()
+
+    def run(self, sequences):
+        """sequences: any number of iterables of (bgr, depth, timestamp).  Runs them n_streams at a time (a stream that
+        finishes its sequence is reset and takes the next one, lowest stream first) and returns one SequenceResult per
+        sequence, in the order given.  The frames of step t+1 are submitted before step t runs, so their build overlaps it."""
+        seqs = list(sequences)
+        out = [SequenceResult() for _ in seqs]
+        seq_of = [None] * self.n_streams      # stream -> sequence index
+        it_of = [None] * self.n_streams
+        done_of = [True] * self.n_streams     # the stream's sequence has no more frames
+        nxt = 0
+
+        def refill():
+            nonlocal nxt
+            for s in range(self.n_streams):
+                if seq_of[s] is not None and done_of[s] and self.pending(s) == 0:
+                    seq_of[s] = None
+                    self.reset(s)
+                if seq_of[s] is None and nxt < len(seqs):
+                    seq_of[s], it_of[s], done_of[s] = nxt, iter(seqs[nxt]), False
+                    nxt += 1
+
+        def feed():  # one submit: the next frame of every stream with room in its queue
+            frames = []
+            for s in range(self.n_streams):
+                if seq_of[s] is None or done_of[s] or self.pending(s) >= self.max_queue:
+                    continue
+                try:
+                    f = next(it_of[s])
+                except StopIteration:
+                    done_of[s] = True
+                    continue
+                frames.append((s, f[0], f[1], f[2]))
+            if frames:
+                self.submit(frames)
+            return len(frames)
+
+        while True:
+            refill()
+            for _ in range(self.max_queue):
+                if not feed():
+                    break
+            if not any(self.pending(s) > 0 for s in range(self.n_streams)):
+                if nxt >= len(seqs) and all(q is None or done_of[s] for s, q in enumerate(seq_of)):
+                    refill()
+                    if all(q is None for q in seq_of):
+                        break
+                continue
+            for s, M, kf, ts in self.step():
+                r = out[seq_of[s]]
+                r.append((M, kf))
+                r.poses.append((ts, M))
         return out
 
 
