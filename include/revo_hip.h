@@ -43,7 +43,9 @@ enum {
   REVO_ERR_NOT_KEYFRAME = -3, /* imgpyramidrgbd.h:113-116 "optimizationStructure not built" */
   REVO_ERR_NOT_ORTHOGONAL = -4, /* Sophus SO3(R) ENSURE, so3.hpp:419-424       */
   REVO_ERR_CAPACITY = -5,
-  REVO_ERR_LEVEL = -6         /* assert(lvl < size) in imgpyramidrgbd.h:59-94  */
+  REVO_ERR_LEVEL = -6,        /* assert(lvl < size) in imgpyramidrgbd.h:59-94  */
+  REVO_ERR_UNSUPPORTED = -7,  /* a valid PNG the device decoder does not handle (revo_png_*) */
+  REVO_ERR_CORRUPT = -8       /* a malformed PNG / zlib stream (revo_png_*)     */
 };
 
 /* TrackerNew::TrackerStatus, tracker.h:61-66 */
@@ -533,6 +535,57 @@ int revo_vo_multi_reset(revo_vo_multi* m, int stream);          /* new sequence 
 int revo_vo_multi_num_keyframes(const revo_vo_multi* m, int stream);
 /* The stream's current keyframe (borrowed, valid until the next revo_vo_multi_step) and its pose in the world. */
 int revo_vo_multi_keyframe(const revo_vo_multi* m, int stream, revo_pyr** kf, float T_w_kf[16]);
+
+/* Device frames for revo_vo_multi: revo_vo_multi_submit with DEVICE pointers (on the context's device), e.g. the output of
+ * revo_png_decode_submit.  The build stream waits for `producer_stream` (an event); the frames are copied device-to-device
+ * into the step set (runs of adjacent frames in one copy; the step set owns its copy, a keyframe keeps its colour); then the
+ * same batched build runs.  Returns once the copies are done: the caller may reuse its buffers.  Per stream the results are
+ * bit-identical to revo_vo_multi_submit on the same pixels.  Argument checks as revo_vo_multi_submit's, plus: every pointer is
+ * device memory and the depth rows are aligned to their element size. */
+int revo_vo_multi_submit_device(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16,
+                                double depth_scale_factor, void* producer_stream);
+
+/* ---------------------------------------------------------------------------
+ * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
+ * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,
+ * Adler-32 checked) runs one wave64 per image; the row filters (None, Sub, Up, Average, Paeth) are undone in a second
+ * kernel that writes the caller's layout.  Throughput comes from many images per launch: one image is a serial decode.
+ * ------------------------------------------------------------------------- */
+typedef struct revo_png_info {
+  int32_t width, height, bit_depth, color_type, interlace;
+  uint64_t idat_bytes;  /* the zlib stream: all IDAT payloads together */
+  uint64_t raw_bytes;   /* its inflated size: height * (1 + row bytes) */
+} revo_png_info;
+/* Host only, never touches a device: checks the signature, every chunk's CRC and the IHDR, skips ancillary chunks and
+ * reports the layout.  REVO_ERR_CORRUPT: malformed (bad signature or CRC, no IHDR / IEND / IDAT, zero size, bad IHDR
+ * fields).  REVO_ERR_UNSUPPORTED (info still filled): interlaced, palette, bit depth < 8, 16-bit colour, an unknown critical
+ * chunk -- the caller decodes those on the CPU. */
+int revo_png_probe(const uint8_t* png, size_t len, revo_png_info* out);
+
+enum { REVO_PNG_BGR8 = 0, /* [H][W][3] u8 B,G,R: cv::imread(IMREAD_COLOR).  From RGB8 (swapped), RGBA8 (alpha dropped),
+                             gray8 and gray+alpha 8 (gray replicated) */
+       REVO_PNG_U16 = 1   /* [H][W] u16, native order: cv::imread(IMREAD_UNCHANGED) of a depth map.  From gray16 (big-endian
+                             in the file) or gray8 (zero-extended) */ };
+typedef struct revo_png_decoder revo_png_decoder;
+/* ctx: the device to decode on (NULL: the calling thread's current device).  Capacity: max_images files per submit,
+ * max_compressed_bytes of image data per submit (page-locked host + device), max_raw_bytes_per_image of inflated rows per
+ * image (device scratch: max_images of them).  Rows of at most 8192 bytes (e.g. 2048 RGBA pixels). */
+int revo_png_decoder_create(revo_ctx* ctx, int max_images, size_t max_compressed_bytes, size_t max_raw_bytes_per_image,
+                            revo_png_decoder** out);
+void revo_png_decoder_destroy(revo_png_decoder* d);
+typedef struct revo_png_job {
+  const uint8_t* png; size_t len;  /* host bytes of one file; reusable once revo_png_decode_submit returns */
+  int32_t format;                  /* REVO_PNG_BGR8 | REVO_PNG_U16 */
+  int32_t width, height;           /* expected; a mismatch is that image's REVO_ERR_INVALID_ARG */
+  void* d_dst; size_t dst_stride;  /* device rows the image is written to */
+} revo_png_job;
+/* Parses on the host, packs the image data of all n files into one page-locked slab, issues ONE host-to-device copy and
+ * the decode kernels on `stream`, and returns.  REVO_ERR_CAPACITY: the batch exceeds the decoder's capacity, or two
+ * tickets are outstanding.  A failed image never affects another; its destination rows are then undefined. */
+int revo_png_decode_submit(revo_png_decoder* d, int n, const revo_png_job* jobs, void* stream, uint64_t* ticket);
+/* Waits for a ticket and writes its n per-image codes: REVO_OK, REVO_ERR_CORRUPT, REVO_ERR_UNSUPPORTED, REVO_ERR_INVALID_ARG
+ * (size mismatch). */
+int revo_png_decode_wait(revo_png_decoder* d, uint64_t ticket, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,13 @@ def lib():
     L.revo_vo_multi_reset.argtypes = [vp, C.c_int]
     L.revo_vo_multi_num_keyframes.argtypes = [vp, C.c_int]
     L.revo_vo_multi_keyframe.argtypes = [vp, C.c_int, vpp, f32p]
+    L.revo_vo_multi_submit_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, vp]
+    L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
+    L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
+    L.revo_png_decoder_destroy.argtypes = [vp]
+    L.revo_png_decoder_destroy.restype = None
+    L.revo_png_decode_submit.argtypes = [vp, C.c_int, vp, vp, C.POINTER(C.c_uint64)]
+    L.revo_png_decode_wait.argtypes = [vp, C.c_uint64, i32p]
     L.revo_pipeline_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, vpp]
     L.revo_pipeline_destroy.argtypes = [vp]
     L.revo_pipeline_destroy.restype = None

@@ -2095,7 +2095,7 @@ struct revo_mdev {
   std::vector<std::deque<Past>> past;
   std::vector<Past> past_pool;
   size_t cloud_cap = 0;
-  hipEvent_t ev_trk = nullptr, ev_vdesc = nullptr, ev_cdesc = nullptr, ev_segs = nullptr, ev_h2d = nullptr;
+  hipEvent_t ev_trk = nullptr, ev_vdesc = nullptr, ev_cdesc = nullptr, ev_segs = nullptr, ev_h2d = nullptr, ev_prod = nullptr;
 };
 
 extern "C" void revo_mdev_destroy_(revo_mdev* m) {
@@ -2112,7 +2112,7 @@ extern "C" void revo_mdev_destroy_(revo_mdev* m) {
   hipHostFree(m->h_descs); hipFree(m->d_descs); hipFree(m->d_res); hipHostFree(m->h_res); hipFree(m->d_mail);
   hipHostFree(m->h_vdesc); hipFree(m->d_vdesc); hipFree(m->d_marks); hipFree(m->d_hist8); hipFree(m->d_done); hipHostFree(m->h_vout);
   hipHostFree(m->h_cdesc); hipFree(m->d_cdesc); hipHostFree(m->h_segs); hipFree(m->d_segs);
-  for (hipEvent_t e : {m->ev_trk, m->ev_vdesc, m->ev_cdesc, m->ev_segs, m->ev_h2d}) if (e) hipEventDestroy(e);
+  for (hipEvent_t e : {m->ev_trk, m->ev_vdesc, m->ev_cdesc, m->ev_segs, m->ev_h2d, m->ev_prod}) if (e) hipEventDestroy(e);
   (void)hipGetLastError();  // a partially built handle frees null pointers on purpose
   delete m;
   ctx_unref(c);
@@ -2164,7 +2164,7 @@ extern "C" int revo_mdev_create_(revo_ctx* c, int S, revo_mdev** out) {
   memset(m->h_vout, 0, sizeof(int) * 16 * S);
   HIPCHECK(hipHostMalloc((void**)&m->h_cdesc, sizeof(CloudCopyDesc) * S));
   HIPCHECK(hipMalloc((void**)&m->d_cdesc, sizeof(CloudCopyDesc) * S));
-  for (hipEvent_t* e : {&m->ev_trk, &m->ev_vdesc, &m->ev_cdesc, &m->ev_segs, &m->ev_h2d})
+  for (hipEvent_t* e : {&m->ev_trk, &m->ev_vdesc, &m->ev_cdesc, &m->ev_segs, &m->ev_h2d, &m->ev_prod})
     HIPCHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
   // (recorded once so that the first wait on each finds a completed event)
   for (hipEvent_t e : {m->ev_vdesc, m->ev_cdesc, m->ev_segs}) HIPCHECK(hipEventRecord(e, c->stream));
@@ -2175,7 +2175,8 @@ extern "C" int revo_mdev_create_(revo_ctx* c, int S, revo_mdev** out) {
   return REVO_OK;
 }
 
-extern "C" int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* fr, int is_u16, double scale, void** set_out) {
+extern "C" int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* fr, int is_u16, double scale, int device_src,
+                                 void* producer, void** set_out) {
   revo_ctx* c = m->c;
   HIPCHECK(hipSetDevice(c->device));
   FrameSet* fs = nullptr;
@@ -2190,13 +2191,18 @@ extern "C" int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* f
   // the set's last consumers (tracker, vote) are done with its planes (its previous build is on this stream already)
   if (fs->has_free) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_free, 0));
   if (fs->has_free2) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_free2, 0));
+  if (device_src) {  // the producer's writes of the frames come first
+    HIPCHECK(hipEventRecord(m->ev_prod, (hipStream_t)producer));
+    HIPCHECK(hipStreamWaitEvent(cs, m->ev_prod, 0));
+  }
+  const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   const int w = c->geom.lv[0].w, h = c->geom.lv[0].h;
   const size_t npix = (size_t)w * h, brow = (size_t)w * 3, drow = (size_t)w * (is_u16 ? 2 : 4);
   // frames whose rows lie back to back in the caller's memory (a decoder filling one slab per plane type) go in one copy
   struct Run { char* dst; const char* src; size_t bytes; };
   auto flush = [&](Run& r) -> hipError_t {
     if (!r.bytes) return hipSuccess;
-    const hipError_t e = hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyHostToDevice, cs);
+    const hipError_t e = hipMemcpyAsync(r.dst, r.src, r.bytes, kind, cs);
     r.bytes = 0;
     return e;
   };
@@ -2204,7 +2210,7 @@ extern "C" int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* f
     if (stride != row) {
       const hipError_t e = flush(r);
       if (e != hipSuccess) return e;
-      return hipMemcpy2DAsync(dst, row, src, stride, row, h, hipMemcpyHostToDevice, cs);
+      return hipMemcpy2DAsync(dst, row, src, stride, row, h, kind, cs);
     }
     if (r.bytes && r.src + r.bytes == (const char*)src && r.dst + r.bytes == (char*)dst) { r.bytes += row * h; return hipSuccess; }
     const hipError_t e = flush(r);
@@ -2227,7 +2233,7 @@ extern "C" int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* f
   HIPCHECK(hipEventRecord(fs->ev_ready, bs));
   fs->has_ready = true;
   fs->ready_stream = bs;
-  // the host rows are consumed once the copies are done; the build runs on
+  // the caller's rows (host or device) are consumed once the copies are done; the build runs on
   HIPCHECK(hipEventSynchronize(m->ev_h2d));
   *set_out = fs;
   return REVO_OK;

@@ -12,7 +12,9 @@ struct MultiFrame { int stream; void* set; int frame; float T_w[16]; double ts; 
 extern "C" {
 int revo_mdev_create_(revo_ctx* c, int n_streams, revo_mdev** out);
 void revo_mdev_destroy_(revo_mdev* m);
-int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* frames, int depth_is_u16, double scale, void** set_out);
+// device_src: the frames are device pointers, copied device-to-device after the build stream waits for `producer`
+int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* frames, int depth_is_u16, double scale, int device_src,
+                      void* producer, void** set_out);
 void revo_mdev_release_set_(revo_mdev* m, void* set);  // no frame of the set is queued, current or previous any more
 int revo_mdev_track_(revo_mdev* m, int n, MultiTrack* pairs);            // one tracker grid, waits for the poses
 int revo_mdev_vote_(revo_mdev* m, int n, MultiVote* votes);              // one batched vote, waits for the counts

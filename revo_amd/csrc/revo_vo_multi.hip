@@ -2,6 +2,8 @@
 // Host-only code: per stream the state of revo_vo.hip (keyframe, previous frame, the last two poses, the constant-velocity
 // initialisation); the device work of a step -- one tracker grid, one quality vote, one cloud copy, the keyframe promotions --
 // is what revo_mdev_* (revo_host.hip) enqueue for all streams at once.  No look-ahead: a step waits for its grid and its vote.
+#include <hip/hip_runtime.h>
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -16,6 +18,7 @@
 extern "C" void revo_ctx_retain_(revo_ctx*);
 extern "C" void revo_ctx_release_(revo_ctx*);
 extern "C" void revo_set_error_(const char* msg);
+extern "C" int revo_ctx_device_(const revo_ctx*);
 
 namespace {
 struct M4 {  // column-major 4x4, Eigen::Matrix4f storage
@@ -37,6 +40,11 @@ void to_RT(const M4& M, float* R, float* T) {
 struct Pose { M4 T_kf_curr, T_w_kf; M4 world() const { return mul(T_w_kf, T_kf_curr); } };  // REVO::Pose, system.h:89-152
 struct Ref { void* set; int frame; double ts; };  // a frame of a step set
 int bad(int code, const char* msg) { revo_set_error_(msg); return code; }
+bool on_device(const void* p, int dev) {  // device memory of `dev` (not host, not another device)
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return a.type == hipMemoryTypeDevice && a.device == dev;
+}
 
 // revo_vo's per-driver state, per stream
 struct Stream {
@@ -126,8 +134,8 @@ extern "C" int revo_vo_multi_reset(revo_vo_multi* m, int s) {
   return REVO_OK;
 }
 
-extern "C" int revo_vo_multi_submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16,
-                                    double depth_scale_factor) {
+static int submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16, double depth_scale_factor,
+                  int device_src, void* producer) {
   if (!m || n < 0 || (n > 0 && !frames)) return bad(REVO_ERR_INVALID_ARG, "bad argument");
   if (n == 0) return REVO_OK;
   if (depth_is_u16 && !(depth_scale_factor > 0)) return bad(REVO_ERR_INVALID_ARG, "depth_scale_factor must be > 0");
@@ -147,17 +155,37 @@ extern "C" int revo_vo_multi_submit(revo_vo_multi* m, int n, const revo_stream_f
   for (int i = 0; i < n; ++i)
     if (frames[i].bgr_stride < w * 3 || frames[i].depth_stride < w * (depth_is_u16 ? 2 : 4))
       return bad(REVO_ERR_INVALID_ARG, "stride smaller than a row");
+  if (device_src) {
+    const int dev = revo_ctx_device_(m->ctx);
+    const size_t esz = depth_is_u16 ? 2 : 4;
+    for (int i = 0; i < n; ++i) {
+      if (((uintptr_t)frames[i].depth | frames[i].depth_stride) % esz)
+        return bad(REVO_ERR_INVALID_ARG, "depth rows not aligned to their element size");
+      if (!on_device(frames[i].bgr, dev) || !on_device(frames[i].depth, dev))
+        return bad(REVO_ERR_INVALID_ARG, "a frame pointer is not device memory of the context's device");
+    }
+  }
   for (int i = 0; i < n; ++i)
     if (revo_vo_multi_pending(m, frames[i].stream) >= m->max_queue)
       return bad(REVO_ERR_CAPACITY, "the stream's queue is full: call revo_vo_multi_step first");
   void* set = nullptr;
-  const int rc = revo_mdev_submit_(m->dev, n, frames, depth_is_u16, depth_scale_factor, &set);
+  const int rc = revo_mdev_submit_(m->dev, n, frames, depth_is_u16, depth_scale_factor, device_src, producer, &set);
   if (rc) return rc;
   for (int i = 0; i < n; ++i) {
     m->st[frames[i].stream].queue.push_back(Ref{set, i, frames[i].timestamp});
     ref_add(m, set);
   }
   return REVO_OK;
+}
+
+extern "C" int revo_vo_multi_submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16,
+                                    double depth_scale_factor) {
+  return submit(m, n, frames, depth_is_u16, depth_scale_factor, 0, nullptr);
+}
+
+extern "C" int revo_vo_multi_submit_device(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16,
+                                           double depth_scale_factor, void* producer_stream) {
+  return submit(m, n, frames, depth_is_u16, depth_scale_factor, 1, producer_stream);
 }
 
 // One body of the while loop of REVO::start (system.cpp:128-284) for every stream that has work, in revo_vo_track_next's order.

@@ -3,7 +3,8 @@
 VO on one GPU and writes poses_<dataset>.txt in TUM format (system.cpp:48-49,76-80).
 
 --streams N runs the YAML's Datasets list N at a time through one vo.MultiREVO handle (a finished dataset's stream takes the
-next one) and writes the same poses_<dataset>.txt files; the PNG decoders are split among the datasets that run at once."""
+next one) and writes the same poses_<dataset>.txt files; the PNG decoders are split among the datasets that run at once.
+--gpu-decode (with --streams) decodes the PNGs on the GPU instead (tum.GpuFrameSource): same pose files."""
 import os
 import sys
 import time
@@ -15,7 +16,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N]")
+              "[--streams N [--gpu-decode]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -28,6 +29,9 @@ def main(argv=None):
         i = argv.index("--decoders")
         decoders = int(argv[i + 1])
         argv = argv[:i] + argv[i + 2:]
+    gpu_decode = "--gpu-decode" in argv  # PNG decoding on the GPU (multi-stream driver only)
+    if gpu_decode:
+        argv = [a for a in argv if a != "--gpu-decode"]
     streams = 0  # > 0: the Datasets list N at a time through one multi-stream handle
     if "--streams" in argv:
         i = argv.index("--streams")
@@ -40,13 +44,19 @@ def main(argv=None):
             print("--save-model is not supported together with --streams: the model export runs on the sequential driver only "
                   "(drop --streams to export the model)")
             return 2
+    if gpu_decode and not streams:
+        print("--gpu-decode is supported together with --streams only: the GPU decoder feeds the multi-stream driver "
+              "(use --streams 1 for a single dataset)")
+        return 2
+    if gpu_decode and decoders is not None:
+        print("--decoders has no effect with --gpu-decode: the PNGs are decoded on the GPU")
     from .settings import OptimizerSettings
     trk_settings, use_edge_filter, sysd = config.load_settings_yaml(argv[0])
     pyr_settings, io = config.load_dataset_yaml(argv[1])
     device = int(argv[2]) if len(argv) > 2 else 0
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
-        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders)
+        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device)
@@ -95,7 +105,7 @@ def _report_ate(folder, poses):
             print("ATE RMSE vs groundtruth.txt: %.4f m over %d poses" % (synth.ate_rmse(est, ref), len(est)))
 
 
-def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders):
+def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -103,8 +113,17 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
     nd = tum.default_decoders() if decoders is None else decoders
     per = max(1, nd // max(1, min(streams, len(folders)))) if nd >= 1 else 0  # decoders of one running dataset
 
+    group = tum.GpuDecodeGroup(pyr_settings.width, pyr_settings.height, batch=8, device=device,
+                               max_sources=min(streams, len(folders))) if gpu_decode else None
+
     def frames(folder):  # opened when the dataset's stream first asks for a frame, closed when it has none left
-        if per >= 1:
+        if group is not None:
+            rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
+                                      read_n_images=io["read_n_images"])
+            for f in tum.GpuFrameSource(folder, rows, pyr_settings.width, pyr_settings.height, group,
+                                        use_depth_timestamp=bool(io["use_depth_timestamp"])):
+                yield f
+        elif per >= 1:
             rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
                                       read_n_images=io["read_n_images"])
             with tum.DecodePool(folder, rows, pyr_settings.width, pyr_settings.height, workers=per,
@@ -118,7 +137,11 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
 
     drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"])
     t0 = time.perf_counter()
-    res = drv.run([frames(f) for f in folders])
+    try:
+        res = drv.run([frames(f) for f in folders])
+    finally:
+        if group is not None:
+            group.close()
     dt = time.perf_counter() - t0
     total = 0
     for name, folder, r in zip(names, folders, res):
@@ -129,7 +152,9 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
         print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
         _report_ate(folder, r.poses)
     print("%d datasets on %d streams: %.1f frames/s (incl. PNG decode, %s)"
-          % (len(folders), streams, total / dt, ("%d decoder processes per dataset" % per) if per else "decoded on this thread"))
+          % (len(folders), streams, total / dt,
+             ("decoded on the GPU, %d frames on the CPU fallback" % group.fallbacks) if group is not None else
+             ("%d decoder processes per dataset" % per) if per else "decoded on this thread"))
     return 0
 
 

@@ -188,6 +188,182 @@ class DecodePool:
             pass
 
 
+class GpuDecodeGroup:
+    """Decodes the next `batch` frames of many GpuFrameSources in ONE launch of a png.GpuPngDecoder (one image decode is a
+    serial inflate: throughput comes from many images per launch).  A launch covers every source that has taken its last
+    decoded batch; it is issued as soon as all running sources have (so in a lockstep run it overlaps the tracking of the
+    batch in use), or at once when a source needs a batch nobody asked for yet.  A reader thread loads the file bytes of
+    each source's following batch while the current one decodes."""
+
+    def __init__(self, width, height, batch=8, device=0, max_sources=1, decoder=None):
+        from concurrent.futures import ThreadPoolExecutor
+        from . import png
+        import torch
+        self.w, self.h, self.batch = int(width), int(height), max(1, int(batch))
+        self.device = torch.device("cuda", device)
+        self.max_sources = max(1, int(max_sources))
+        self.max_images = 2 * self.batch * self.max_sources
+        self.raw = png.raw_bytes(self.w, self.h, png.BGR8)
+        self.decoder = decoder
+        self._cap = 0
+        self.stream = torch.cuda.Stream(self.device)
+        self._reader = ThreadPoolExecutor(1)
+        self._sources = []
+        self._inflight = {}  # ticket -> [(source, files ...)]
+        self.fallbacks = 0
+
+    def _read(self, src, rows):
+        out = []
+        for rts, rf, dts, df in rows:
+            with open(os.path.join(src.folder, rf), "rb") as f:
+                a = f.read()
+            with open(os.path.join(src.folder, df), "rb") as f:
+                b = f.read()
+            out.append((a, b))
+        return out
+
+    def _launch(self, srcs):
+        from . import png
+        jobs = []
+        for src in srcs:
+            rows, files = src._take_next_files()
+            src._requested = True
+            for k, (a, b) in enumerate(files):
+                jobs.append((src, rows[k], k, a, b))
+        if not jobs:
+            return
+        total = sum(len(a) + len(b) for _, _, _, a, b in jobs)
+        if self.decoder is None or total > self._cap:
+            for t in list(self._inflight):  # (a bigger decoder: the outstanding batches finish first)
+                self._finish(t)
+            if self.decoder is not None:
+                self.decoder.close()
+            self._cap = max(2 * total, 1 << 24)
+            self.decoder = png.GpuPngDecoder(self.max_images, self._cap, self.raw, device=self.device.index)
+        files, fmts, outs = [], [], []
+        for src, row, k, a, b in jobs:
+            bgr, depth = src._slot(src._fill_half, k)
+            files += [a, b]
+            fmts += [png.BGR8, png.U16]
+            outs += [bgr, depth]
+        t = self.decoder.submit(files, fmts, outs, self.stream)
+        self._inflight[t] = jobs
+        for src in srcs:
+            src._ticket = t
+            src._half_of[t] = src._fill_half
+
+    def _finish(self, t):
+        """Waits for a launch and decodes on the CPU what the device could not (uploaded into the same slots)."""
+        import torch
+        jobs = self._inflight.pop(t)
+        codes = self.decoder.wait(t)
+        for j, (src, row, k, a, b) in enumerate(jobs):
+            if codes[2 * j] == 0 and codes[2 * j + 1] == 0:
+                continue
+            self.fallbacks += 1
+            rts, rf, dts, df = row
+            bgr, depth = load_frame(src.folder, rf, df)  # (a file PIL cannot read either fails here, as DecodePool does)
+            if bgr.shape != (self.h, self.w, 3) or depth.shape != (self.h, self.w):
+                raise ValueError("%s: frame is %s / %s, the source holds %dx%d frames" % (rf, bgr.shape, depth.shape, self.w, self.h))
+            d_bgr, d_depth = src._slot(src._half_of[t], k)
+            with torch.cuda.stream(self.stream):
+                d_bgr.copy_(torch.from_numpy(bgr.copy()))
+                d_depth.copy_(torch.from_numpy(depth.view(np.int16).copy()).view(torch.uint16))
+            self.stream.synchronize()
+
+    def need(self, src):
+        """src has used up its batch: make sure its next one is (being) decoded and wait for it."""
+        if not src._requested:
+            self._launch([s for s in self._sources if s._wants()])
+        t = src._ticket
+        if t in self._inflight:
+            self._finish(t)
+
+    def maybe_prefetch(self):
+        live = [s for s in self._sources if not s._exhausted_files()]
+        if live and all(s._wants() for s in live):
+            self._launch(live)
+
+    def close(self):
+        for t in list(self._inflight):
+            try:
+                self._finish(t)
+            except Exception:
+                pass
+        self._reader.shutdown(wait=True)
+        if self.decoder is not None:
+            self.decoder.close()
+
+
+class GpuFrameSource:
+    """tum.frames() decoded on the GPU: yields (bgr [H,W,3] uint8, depth [H,W] uint16, timestamp) as device tensors, views
+    of a double-buffered ring of 2 x `batch` frames (valid until the next frame is taken; vo.MultiREVO.submit_device copies
+    them before that).  The frames of the next batch decode while this batch is tracked.  A file the device reports as
+    UNSUPPORTED or CORRUPT is decoded by load_frame and uploaded instead.  `decoder` is a GpuDecodeGroup shared by the
+    sources that run together (None: one of its own)."""
+
+    def __init__(self, folder, rows, width, height, decoder=None, batch=8, use_depth_timestamp=False, device=0):
+        import torch
+        self.folder, self.rows = folder, list(rows)
+        self.group = decoder if decoder is not None else GpuDecodeGroup(width, height, batch, device)
+        self._own_group = decoder is None
+        g = self.group
+        self.use_depth_timestamp = bool(use_depth_timestamp)
+        self._bgr = torch.empty((2, g.batch, g.h, g.w, 3), dtype=torch.uint8, device=g.device)
+        self._depth = torch.empty((2, g.batch, g.h, g.w), dtype=torch.uint16, device=g.device)
+        self._next_row = 0          # first row not yet handed to a launch
+        self._fill_half = 0         # the half the next launch writes
+        self._half_of = {}          # ticket -> half
+        self._requested = False     # the next batch is launched (or there is none)
+        self._ticket = None
+        self._prefetch = None       # future: file bytes of rows[_next_row : _next_row + batch]
+        g._sources.append(self)
+        self._schedule_read()
+
+    def _slot(self, half, k):
+        return self._bgr[half, k], self._depth[half, k]
+
+    def _schedule_read(self):
+        rows = self.rows[self._next_row:self._next_row + self.group.batch]
+        self._prefetch = (rows, self.group._reader.submit(self.group._read, self, rows)) if rows else None
+
+    def _exhausted_files(self):
+        return self._prefetch is None
+
+    def _wants(self):
+        return not self._requested and self._prefetch is not None
+
+    def _take_next_files(self):
+        rows, fut = self._prefetch
+        files = fut.result()
+        self._next_row += len(rows)
+        self._schedule_read()
+        return rows, files
+
+    def __iter__(self):
+        g = self.group
+        try:
+            i = 0
+            while i < len(self.rows):
+                g.need(self)
+                t = self._ticket
+                half = self._half_of.pop(t)
+                n = min(g.batch, len(self.rows) - i)
+                self._requested = False
+                self._fill_half = 1 - half
+                g.maybe_prefetch()
+                for k in range(n):
+                    rts, rf, dts, df = self.rows[i + k]
+                    bgr, depth = self._slot(half, k)
+                    yield bgr, depth, (dts if self.use_depth_timestamp else rts)
+                i += n
+        finally:
+            if self in g._sources:
+                g._sources.remove(self)
+            if self._own_group:
+                g.close()
+
+
 def usable_cpus():
     """CPUs this process may really use: the affinity mask capped by the cgroup CPU quota (the GPU boxes expose 256 hardware
     threads and grant 16 CPUs: cpu.max = "1600000 100000")."""

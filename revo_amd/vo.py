@@ -196,6 +196,7 @@ class MultiREVO:
             if settingsTracker is not None:
                 raise ValueError("MultiREVO on a given cameraPyr uses that context's tracker settings: pass settingsTracker=None")
             self.camPyr = cameraPyr
+        self.device = int(device)
         self.n_streams = int(n_streams)
         self.max_queue = int(max_queue)
         self.depth_scale_factor = depth_scale_factor  # set: depth arrives as raw uint16
@@ -234,6 +235,35 @@ class MultiREVO:
         check(_lib.lib().revo_vo_multi_submit(self._h, len(frames), arr, 1 if u16 else 0,
                                               float(self.depth_scale_factor) if u16 else 0.0))
 
+    def submit_device(self, frames, producer_stream=None):
+        """submit() with torch device tensors: [(stream, bgr [H,W,3] uint8, depth [H,W] float32 metres or (depth_scale_factor
+        set) uint16, timestamp)], rows packed.  The frames are copied on the device after `producer_stream` (default: the
+        current torch stream) reaches this point; returns once they are copied, so the tensors may be reused.  Per stream the
+        results are bit-identical to submit() on the same pixels."""
+        import torch
+        frames = list(frames)
+        if not frames:
+            return
+        w, h = self.settingsPyr.width, self.settingsPyr.height
+        u16 = frames[0][2].dtype == torch.uint16
+        if u16 and self.depth_scale_factor is None:
+            raise ValueError("uint16 depth needs depth_scale_factor")
+        arr = (StreamFrame * len(frames))()
+        for i, (s, bgr, depth, ts) in enumerate(frames):
+            if bgr.dtype != torch.uint8 or tuple(bgr.shape) != (h, w, 3) or tuple(depth.shape) != (h, w):
+                raise ValueError("image size or type does not match the settings")
+            if depth.dtype != (torch.uint16 if u16 else torch.float32):
+                raise ValueError("all depth maps of one submit are uint16 or all float32")
+            if bgr.stride() != (w * 3, 3, 1) or depth.stride(1) != 1:
+                raise ValueError("rows must be packed")
+            arr[i].stream = int(s)
+            arr[i].bgr, arr[i].bgr_stride = bgr.data_ptr(), w * 3
+            arr[i].depth, arr[i].depth_stride = depth.data_ptr(), depth.stride(0) * depth.element_size()
+            arr[i].timestamp = float(ts)
+        ps = producer_stream if producer_stream is not None else torch.cuda.current_stream(frames[0][1].device)
+        check(_lib.lib().revo_vo_multi_submit_device(self._h, len(frames), arr, 1 if u16 else 0,
+                                                     float(self.depth_scale_factor) if u16 else 0.0, C.c_void_p(ps.cuda_stream)))
+
     def step(self):
         n = C.c_int()
         check(_lib.lib().revo_vo_multi_step(self._h, self._out, C.byref(n)))
@@ -262,7 +292,8 @@ class MultiREVO:
         return pyr, T.reshape(4, 4).T.copy()
 
     def run(self, sequences):
-        """sequences: any number of iterables of (bgr, depth, timestamp).  Runs them n_streams at a time (a stream that
+        """sequences: any number of iterables of (bgr, depth, timestamp), host arrays or device tensors (submit_device,
+        complete when yielded, e.g. tum.GpuFrameSource).  Runs them n_streams at a time (a stream that
         finishes its sequence is reset and takes the next one, lowest stream first) and returns one SequenceResult per
         sequence, in the order given.  The frames of step t+1 are submitted before step t runs, so their build overlaps it."""
         seqs = list(sequences)
@@ -293,8 +324,12 @@ class MultiREVO:
                     done_of[s] = True
                     continue
                 frames.append((s, f[0], f[1], f[2]))
-            if frames:
-                self.submit(frames)
+            dev = [fr for fr in frames if hasattr(fr[1], "data_ptr")]
+            host = [fr for fr in frames if not hasattr(fr[1], "data_ptr")]
+            if host:
+                self.submit(host)
+            if dev:
+                self.submit_device(dev)
             return len(frames)
 
         while True:
