@@ -144,6 +144,17 @@ int revo_ctx_set_tracker(revo_ctx* ctx, const revo_opt_settings* opt,
 /* TrackerNew::histogramLevel (tracker.h:67, tracker.cpp:229). */
 int revo_ctx_histogram_level(const revo_ctx* ctx);
 
+/* Exact-sums mode (off by default).  On: the tracker forms the reference's own per-point float terms
+ * (calculateWarpUpdate, LGS6::update) and every sum it compares or solves with -- the 27 entries of the
+ * normal equations, the error sums of every LM candidate, the init-check costs -- is the float nearest
+ * the exact sum of those terms, whatever the cluster size, batch size, speculation depth or stream count
+ * (DESIGN 4.1 states the guarantee).  Poses, evaluation counts and keyframe decisions then depend on the
+ * inputs alone.  The flag is read by each tracker launch: it applies from the next single-pair call,
+ * batch, pipeline step or revo_vo frame of this context; a revo_vo_multi handle keeps the value it had
+ * when it was created.  Returns REVO_OK / the flag (0 or 1), or an error / -1 for a null context. */
+int revo_ctx_set_exact_sums(revo_ctx* ctx, int on);
+int revo_ctx_exact_sums(const revo_ctx* ctx);
+
 /* Camera(fx,fy,cx,cy,w,h,scale) for level lvl, camerapyr.h:98-103,139-144:
  * out6 = {fx,fy,cx,cy,width,height}. */
 int revo_ctx_camera(const revo_ctx* ctx, int lvl, float out6[6]);

@@ -103,6 +103,8 @@ def lib():
     L.revo_batch_time_tracker.argtypes = [vp, f32p, vp, vp, C.c_int, f32p]
     L.revo_batch_profile_build.argtypes = [vp, vp, vp, C.c_int, vp]
     L.revo_ctx_histogram_level.argtypes = [vp]
+    L.revo_ctx_set_exact_sums.argtypes = [vp, C.c_int]
+    L.revo_ctx_exact_sums.argtypes = [vp]
     L.revo_vo_create.argtypes = [vp, vpp]
     L.revo_vo_destroy.argtypes = [vp]
     L.revo_vo_destroy.restype = None

@@ -50,17 +50,28 @@ class Camera:
 class CameraPyr:
     """camerapyr.h:113-193.  Also owns the HIP context (device, stream, HBM pools)."""
 
-    def __init__(self, settingsPyr, device=0, optimizerSettings=None, trackerSettings=None):
+    def __init__(self, settingsPyr, device=0, optimizerSettings=None, trackerSettings=None, exact_sums=False):
         self.settings = settingsPyr
         self._h = vp()
         opt = optimizerSettings or OptimizerSettings()
         trk = trackerSettings or TrackerSettings()
         check(_lib.lib().revo_ctx_create(device, C.byref(settingsPyr), C.byref(opt), C.byref(trk), C.byref(self._h)))
+        if exact_sums:
+            self.setExactSums(True)
         self.camPyr = []
         for lvl in range(settingsPyr.nLevels()):
             out = np.empty(6, np.float32)
             check(_lib.lib().revo_ctx_camera(self._h, lvl, _p(out, f32p)))
             self.camPyr.append(Camera(*[float(x) for x in out[:4]], out[4], out[5]))
+
+    def setExactSums(self, on):
+        """Exact-sums mode of the tracker (revo_ctx_set_exact_sums): applies from the next tracker
+        launch of this context."""
+        check(_lib.lib().revo_ctx_set_exact_sums(self._h, 1 if on else 0))
+
+    @property
+    def exact_sums(self):
+        return bool(_lib.lib().revo_ctx_exact_sums(self._h))
 
     def size(self):
         return len(self.camPyr)

@@ -106,6 +106,8 @@ struct TrackParams {
   float huber_edge;
   int use_edge_filter;
   struct { float fx, fy, cx, cy; int w, h; } cam[REVO_L];
+  int exact_sums;                 // host side only: launch the exact-sums instantiation (revo_ctx_set_exact_sums); the kernels
+                                  // never read it (it fills the tail padding in front of the next kernel argument)
 };
 
 // eval_only output (parity tests): LGS6 after finish() + ResidualInfo
@@ -132,6 +134,8 @@ struct EvalOut {
 #endif
 #define TRACK_KMAX 4               // speculative LM candidates per pass
 #define TRACK_NVAL 48              // values a workgroup publishes per pass: 32 normal-equation + 16 error slots
+#define TRACK_NVAL_X 132           // the exact-sums variant: 32 double-double slots as 4 words each + TRACK_KMAX good counts
+#define TRACK_MAIL_NVAL TRACK_NVAL_X  // mailbox granules per member and parity: sized for the larger of the two layouts
 
 // ---- launchers (defined in the kernel translation units) -------------------
 void launch_gray_depth(const PyrGeom& g, const FramePlanes& p, const uint8_t* d_bgr, const float* d_depth_f32,

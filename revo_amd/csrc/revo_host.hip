@@ -447,7 +447,8 @@ extern "C" int revo_debug_census_(int device, unsigned out3[3]) {
   out3[2] = ch.started_total;
   return 0;
 }
-static size_t mail_bytes(int n_pairs, int cluster) { return sizeof(unsigned long long) * (size_t)n_pairs * 2 * cluster * TRACK_NVAL; }
+// sized for the larger of the two tracker layouts: the exact-sums instantiation may run on any mailbox
+static size_t mail_bytes(int n_pairs, int cluster) { return sizeof(unsigned long long) * (size_t)n_pairs * 2 * cluster * TRACK_MAIL_NVAL; }
 
 // --------------------------------------------------------------- FrameSets --
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -694,7 +695,9 @@ extern "C" int revo_ctx_set_tracker(revo_ctx* c, const revo_opt_settings* opt, c
   std::lock_guard<std::mutex> lk(c->mu);
   if (opt) c->os = *opt;
   if (trk) c->ts = *trk;
+  const int exact = c->tp.exact_sums;  // not a tracker setting: it stays as revo_ctx_set_exact_sums left it
   build_track_params(c, &c->tp);
+  c->tp.exact_sums = exact;
   // a new TrackerNew starts with empty past lists (tracker.h:92-95): the clouds an earlier tracker on this context added must
   // not vote for this one (stream-ordered reuse of the buffers, as in revo_tracker_clear_past)
   while (!c->past.empty()) { c->past_pool.push_back(c->past.front()); c->past.pop_front(); }
@@ -702,6 +705,16 @@ extern "C" int revo_ctx_set_tracker(revo_ctx* c, const revo_opt_settings* opt, c
 }
 
 extern "C" int revo_ctx_histogram_level(const revo_ctx* c) { return c ? c->ts.histogram_level : -1; }
+
+// Exact-sums mode: every tracker launch takes the instantiation from the TrackParams it copies, so the flag applies
+// to the next launch of any path of this context; a revo_vo_multi handle keeps the value of its creation.
+extern "C" int revo_ctx_set_exact_sums(revo_ctx* c, int on) {
+  if (!c) return fail(REVO_ERR_INVALID_ARG, "null context");
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->tp.exact_sums = on ? 1 : 0;
+  return REVO_OK;
+}
+extern "C" int revo_ctx_exact_sums(const revo_ctx* c) { return c ? c->tp.exact_sums : -1; }
 
 extern "C" int revo_ctx_camera(const revo_ctx* c, int lvl, float out6[6]) {
   if (!c || !out6) return fail(REVO_ERR_INVALID_ARG, "null argument");

@@ -67,6 +67,12 @@ enum { PH_FIRST = 0, PH_LM = 1, PH_REFILL = 2, PH_EVAL_ONLY = 3 };
 #define SPIN_LIMIT 400000      // bounded cluster wait (~0.5 s): never hang the GPU
 #define MAX_TOTAL_EVALS 6000  // hang guard; the reference bound is 100 outer iterations x retries
 static_assert(CSLOT + KMAX <= 32 && NVAL == 48 && NSUM == 40 && 1 + KMAX <= 8, "slot layout");
+// The exact-sums variant (k_track<ONE, true>, TrackParams::exact_sums) carries every sum as a double-double
+// (hi + lo): 32 slots = 27 normal equations + XERR + k = double slot k of the default layout (DSLOT below), plus KMAX good counts.
+#define XERR 27
+#define NVAL_X TRACK_NVAL_X      // granules per workgroup and pass: 32 slots as four words (hi lo/hi word, lo lo/hi word), then KMAX counts
+#define NSUM_X 68                // per-wave partials in LDS: 32 hi, 32 lo, KMAX counts (as double)
+static_assert(XERR + 1 + KMAX <= 32 && NVAL_X == 4 * 32 + KMAX && NSUM_X == 64 + KMAX && NVAL_X <= TRACK_MAIL_NVAL, "exact slot layout");
 
 struct Cand {  // one pose to evaluate (R, T: what the evaluating waves read); for LM candidates also what the decision needs
   float R[9], T[3];    // R column-major; T is also the translation of Sophus::SE3f new_referenceToFrame (optimizer.cpp:266)
@@ -396,6 +402,64 @@ __device__ __forceinline__ void reduce8d(double* v, int lane) {
 }
 __device__ __forceinline__ int idx8(int lane) { return ((lane & 1) << 2) | (lane & 2) | ((lane & 4) >> 2); }
 
+// ---- the exact-sums variant: double-double arithmetic -------------------------------------------------------------
+// dd_acc: (h, l) += x with Knuth's TwoSum -- the rounding error of h + x is formed exactly and lands in l.  The per-point
+// terms are floats, so a thread's (h, l) is their exact sum up to l's own roundings (~2^-106 of the largest partial).
+__device__ __forceinline__ void dd_acc(double& h, double& l, double x) {
+  const double s = h + x, bb = s - h;
+  l += (h - (s - bb)) + (x - bb);
+  h = s;
+}
+// (h, l) += (h2, l2): TwoSum of the heads, the tails added to the error, renormalised (Fast2Sum).  Symmetric in its two
+// operands (TwoSum's error is exact whatever the order), so the two lanes of a butterfly pair hold the same bits.
+__device__ __forceinline__ void dd_add(double& h, double& l, double h2, double l2) {
+  const double s = h + h2, bb = s - h;
+  double e = (h - (s - bb)) + (h2 - bb);
+  e += l + l2;
+  h = s + e;
+  l = e - (h - s);
+}
+// h + l rounded ONCE to float: h + l rounded to odd in double (53 >= 24 + 2 bits), then to nearest float.  A plain
+// (float)(h + l) could round twice (to double, then to float) and miss the float nearest h + l at a midpoint.
+__device__ __forceinline__ float dd_to_float(double h, double l) {
+  const double s = h + l, bb = s - h;
+  const double e = (h - (s - bb)) + (l - bb);
+  long long bits = __double_as_longlong(s);
+  if (e != 0.0 && (bits & 1) == 0 && __builtin_isfinite(s)) bits += ((e > 0.0) == (s > 0.0)) ? 1 : -1;
+  return (float)__longlong_as_double(bits);
+}
+// 32 double-double values (h[], l[]): lane L ends with the wave total of value idx32(L) in h[0], l[0] -- reduce32's tree
+template <int HALF, int MASK>
+__device__ __forceinline__ void butterfly_step_x(double* h, double* l, int lane) {
+  const bool up = (lane & MASK) != 0;
+#pragma unroll
+  for (int i = 0; i < HALF; ++i) {
+    const double sh = up ? h[i] : h[HALF + i], sl = up ? l[i] : l[HALF + i];
+    double kh = up ? h[HALF + i] : h[i], kl = up ? l[HALF + i] : l[i];
+    dd_add(kh, kl, lane_xor_d<MASK>(sh), lane_xor_d<MASK>(sl));
+    h[i] = kh; l[i] = kl;
+  }
+}
+__device__ __forceinline__ void reduce32x(double* h, double* l, int lane) {
+  butterfly_step_x<16, 1>(h, l, lane);
+  butterfly_step_x<8, 2>(h, l, lane);
+  butterfly_step_x<4, 4>(h, l, lane);
+  butterfly_step_x<2, 8>(h, l, lane);
+  butterfly_step_x<1, 16>(h, l, lane);
+  dd_add(h[0], l[0], lane_xor_d<32>(h[0]), lane_xor_d<32>(l[0]));
+}
+// KMAX = 4 good counts (float, exact: < 2^24): lane L ends with the wave total of count idx4(L) in v[0]
+__device__ __forceinline__ void reduce4(float* v, int lane) {
+  butterfly_step<2, 1>(v, lane);
+  butterfly_step<1, 2>(v, lane);
+  v[0] += lane_xor<4>(v[0]);
+  v[0] += lane_xor<8>(v[0]);
+  v[0] += lane_xor<16>(v[0]);
+  v[0] += lane_xor<32>(v[0]);
+}
+__device__ __forceinline__ int idx4(int lane) { return ((lane & 1) << 1) | ((lane & 2) >> 1); }
+static_assert(KMAX == 4, "reduce4");
+
 // ---- cluster all-gather of the per-workgroup partials -------------------------
 typedef unsigned long long u64;
 // mail layout per pair: [2 (epoch parity)][cluster][NVAL] granules of {epoch << 32 | 32 payload bits}.  Granules 0..31 carry
@@ -473,6 +537,68 @@ __device__ __forceinline__ bool cluster_gather(const u64* __restrict__ mail_pair
     default: return cluster_poll<0>(slot, cluster, epoch, lane, tot_out);
   }
 }
+// The exact variant's exchange: mail layout per pair [2][cluster][NVAL_X].  Lane v < 32 publishes slot v's (h, l) as granules
+// 4v .. 4v + 3 (h low / high word, l low / high word), lane 32 + j the good count of candidate j as granule 128 + j.
+__device__ __forceinline__ void cluster_publish_x(u64* __restrict__ mail_pair, int cluster, int member, unsigned epoch, double h,
+                                                  double l, int lane) {
+  u64* slot = mail_pair + (size_t)(epoch & 1u) * cluster * NVAL_X + (size_t)member * NVAL_X;
+  const u64 e = (u64)epoch << 32;
+  if (lane < 32) {
+    const u64 hb = (u64)__double_as_longlong(h), lb = (u64)__double_as_longlong(l);
+    u64* g = slot + 4 * lane;
+    __hip_atomic_store(&g[0], e | (hb & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&g[1], e | (hb >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&g[2], e | (lb & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&g[3], e | (lb >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if (lane < 32 + KMAX) {
+    __hip_atomic_store(&slot[128 + lane - 32], e | (u64)__float_as_uint((float)h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// Sums the members' (h, l) in the fixed order 0 .. cluster-1 (the same bits in every member).  Four members' granules are in
+// flight per poll; the wait is bounded by SPIN_LIMIT polls in all.
+__device__ __forceinline__ bool cluster_gather_x(const u64* __restrict__ mail_pair, int cluster, unsigned epoch, int lane, double* h_out,
+                                                 double* l_out) {
+  const u64* slot = mail_pair + (size_t)(epoch & 1u) * cluster * NVAL_X;
+  const bool dd = lane < 32;
+  const int g0 = dd ? 4 * lane : (lane < 32 + KMAX ? 128 + lane - 32 : 128);
+  const int gs = dd ? 1 : 0;  // granule step: the count lanes read their one granule four times
+  double h = 0.0, l = 0.0;
+  unsigned spins = 0;
+  for (int j0 = 0; j0 < cluster; j0 += 4) {
+    u64 g[4][4];
+    for (;; ++spins) {
+      bool all = true;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int j = j0 + jj < cluster ? j0 + jj : cluster - 1;
+        const u64* m = slot + (size_t)j * NVAL_X + g0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[jj][k] = __hip_atomic_load(&m[k * gs], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) all = all && ((unsigned)(g[jj][k] >> 32) == epoch);
+      if (__all(all)) break;
+      if (spins > SPIN_LIMIT) return false;
+      __builtin_amdgcn_s_sleep(1);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      if (j0 + jj >= cluster) break;
+      if (dd) {
+        const double mh = __longlong_as_double((long long)(((u64)(unsigned)g[jj][1] << 32) | (u64)(unsigned)g[jj][0]));
+        const double ml = __longlong_as_double((long long)(((u64)(unsigned)g[jj][3] << 32) | (u64)(unsigned)g[jj][2]));
+        dd_add(h, l, mh, ml);
+      } else {
+        h += (double)__uint_as_float((unsigned)g[jj][0]);
+      }
+    }
+  }
+  *h_out = h;
+  *l_out = l;
+  return true;
+}
 
 // explicit global address space: the pointers come out of the descriptor (generic), and
 // flat loads would tie up both vmcnt and lgkmcnt
@@ -540,9 +666,49 @@ __device__ __forceinline__ void accumulate_error(float res, float wr, bool good,
   if (WITH_UNWEIGHTED) ed[1] += (double)r2;
   *cnt += good ? 1.0f : 0.0f;
 }
+// The exact variant: the same float terms into double-double slot XERR + k (k = the default layout's double slot); (r*r)*w is
+// also LGS6::update's error term (LGSX.h:398).  cnt: the candidate's good count.
+template <bool WITH_UNWEIGHTED>
+__device__ __forceinline__ void accumulate_error_x(float res, float wr, bool good, double* xd, int k, float* cnt) {
+  const float r2 = res * res;
+  dd_acc(xd[XERR + k], xd[32 + XERR + k], (double)(r2 * wr));
+  if (WITH_UNWEIGHTED) dd_acc(xd[XERR + k + 1], xd[32 + XERR + k + 1], (double)r2);
+  *cnt += good ? 1.0f : 0.0f;
+}
+
+// The exact variant's per-point terms: calculateWarpUpdate (optimizer.cpp:211-228) and LGS6::update (LGSX.h:392-398) as the
+// reference forms them -- z and z_sqr as two correctly rounded divisions, v[3] / v[4] evaluated in DOUBLE (the `1.0` literal
+// promotes the expression) and rounded to float once, the terms (v[a]*v[c])*w and v[a]*(r*w) as separate float products.
+// xd[k] / xd[32 + k]: head / tail of slot k (0..20: A, upper triangle; 21..26: sum v[a]*(r*w), b = its negation).
+__device__ __forceinline__ void accumulate_terms_x(const PtState& s, float gx, float gy, float res, float wr, bool good, float* cnt,
+                                                   double* xd) {
+  const float px = s.X, py = s.Y;
+  const float z = revo_div_with(1.0f, s.Z, s.rz);  // 1.0f / pz
+  const float zs = revo_div(1.0f, s.Z * s.Z);      // 1.0f / (pz*pz)
+  float v[6];
+  v[0] = z * gx;
+  v[1] = z * gy;
+  v[2] = (-px * zs) * gx + (-py * zs) * gy;
+  v[3] = (float)((double)((-px * py * zs) * gx) + (-(1.0 + (double)(py * py * zs))) * (double)gy);
+  v[4] = (float)((1.0 + (double)(px * px * zs)) * (double)gx + (double)((px * py * zs) * gy));
+  v[5] = (-py * z) * gx + (px * z) * gy;
+  {
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int c = a; c < 6; ++c) { dd_acc(xd[k], xd[32 + k], (double)((v[a] * v[c]) * wr)); ++k; }
+  }
+  const float rw = res * wr;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) dd_acc(xd[21 + a], xd[53 + a], (double)(v[a] * rw));
+  accumulate_error_x<true>(res, wr, good, xd, 0, cnt);
+}
 
 // calcErrorAndBuffers' interpolation + filter + Huber (optimizer.cpp:106-133, optimizer.h:156-185)
 // fused with calculateWarpUpdate's Jacobian (optimizer.cpp:218-228) and LGS6::update.
+// EXACT: acc = the KMAX good counts, ed = the 32 double-double slots (heads, then tails).
+template <bool EXACT>
 __device__ __forceinline__ void accumulate_point(const PtState& s, const DtPatch& q, float fx, float fy, float edist, bool filt,
                                                  float huber, float* acc, double* ed) {
   // the reference's table entries at the four corners: (0.5(prev-next), 0.5(up-down), dt)
@@ -559,6 +725,10 @@ __device__ __forceinline__ void accumulate_point(const PtState& s, const DtPatch
   if (!good) { r0 = 0.0f; r1 = 0.0f; res = 0.0f; }
   const float wr = (res <= huber) ? 1.0f : revo_div(huber, res);
   const float gx = fx * r0, gy = fy * r1;
+  if constexpr (EXACT) {
+    accumulate_terms_x(s, gx, gy, res, wr, good, acc, ed);
+    return;
+  }
   const float z = revo_div_with(1.0f, s.Z, s.rz);
   const float zs = z * z;  // reference: 1/(pz*pz), optimizer.cpp:213; differs by <= 1 ulp
   float jv[6];
@@ -583,11 +753,12 @@ __device__ __forceinline__ void accumulate_point(const PtState& s, const DtPatch
   accumulate_error<true>(res, wr, good, ed, acc + CSLOT);
 }
 
+template <bool EXACT>
 __device__ __forceinline__ void full_point(const f4v p, gf32p dtm, const float* R, const float* T, const Cam& c, float edist,
                                            bool filt, float huber, float* acc, double* ed) {
   const PtState s = project_point(p, R, T, c, true);
   const DtPatch q = load_patch(dtm, c.w, s.ix, s.iy);
-  accumulate_point(s, q, c.fx, c.fy, edist, filt, huber, acc, ed);
+  accumulate_point<EXACT>(s, q, c.fx, c.fy, edist, filt, huber, acc, ed);
 }
 
 // TrackerNew::evalCostFunction's per-point term, tracker.cpp:371-389
@@ -631,7 +802,7 @@ __device__ __forceinline__ void load_pose(const Cand& c, float* R, float* T) {
 // picked out of registers instead of costing the vector L1 another ~27 tag lookups per gather.  Lanes whose retry moved
 // farther gather as before, under the exec mask (a gather is priced by the distinct lines of its ACTIVE lanes).  Same
 // values from the same addresses, same accumulation order per candidate: the sums do not change by a bit.
-template <int NE>
+template <int NE, bool EXACT>
 __device__ __forceinline__ void fused_point(const f4v p, gf32p dtm, const float* R0, const float* T0, const float (*R)[9],
                                             const float (*T)[3], const Cam& c, float edist, bool filt, float huber, float* acc,
                                             double* ed) {
@@ -654,7 +825,7 @@ __device__ __forceinline__ void fused_point(const f4v p, gf32p dtm, const float*
       g00[j] = t[0]; g10[j] = t[1]; g01[j] = t[c.w]; g11[j] = t[c.w + 1];
     }
   }
-  accumulate_point(s0, q, c.fx, c.fy, edist, filt, huber, acc, ed);
+  accumulate_point<EXACT>(s0, q, c.fx, c.fy, edist, filt, huber, acc, ed);
 #pragma unroll
   for (int j = 0; j < NE; ++j) {
     float d00 = g00[j], d10 = g10[j], d01 = g01[j], d11 = g11[j];
@@ -672,11 +843,12 @@ __device__ __forceinline__ void fused_point(const f4v p, gf32p dtm, const float*
     const bool good = s[j].valid && !(res > edist && filt);
     if (!good) res = 0.0f;
     const float wr = (res <= huber) ? 1.0f : revo_div(huber, res);
-    accumulate_error<false>(res, wr, good, ed + 2 + j, acc + CSLOT + 1 + j);
+    if constexpr (EXACT) accumulate_error_x<false>(res, wr, good, ed, 2 + j, acc + 1 + j);
+    else accumulate_error<false>(res, wr, good, ed + 2 + j, acc + CSLOT + 1 + j);
   }
 }
 
-template <int NE>
+template <int NE, bool EXACT>
 __device__ __forceinline__ void fused_block(const Cand* cand, const f4v* preg, gf4p pts, int first, int stride, int N, gf32p dtm,
                                             const Cam& cam, float edist, bool filt, float huber, float* acc, double* ed) {
   float R0[9], T0[3], R[NE][9], T[NE][3];
@@ -685,12 +857,16 @@ __device__ __forceinline__ void fused_block(const Cand* cand, const f4v* preg, g
   for (int j = 0; j < NE; ++j) load_pose(cand[1 + j], R[j], T[j]);
 #pragma unroll
   for (int k = 0; k < TRACK_MAXP; ++k)
-    if (first + k * stride < N) fused_point<NE>(preg[k], dtm, R0, T0, R, T, cam, edist, filt, huber, acc, ed);
-  for (int i = first + TRACK_MAXP * stride; i < N; i += stride) fused_point<NE>(pts[i], dtm, R0, T0, R, T, cam, edist, filt, huber, acc, ed);
+    if (first + k * stride < N) fused_point<NE, EXACT>(preg[k], dtm, R0, T0, R, T, cam, edist, filt, huber, acc, ed);
+  for (int i = first + TRACK_MAXP * stride; i < N; i += stride) fused_point<NE, EXACT>(pts[i], dtm, R0, T0, R, T, cam, edist, filt, huber, acc, ed);
 }
 
 // ---- the kernel ---------------------------------------------------------------
-#define TRACK_OCC __attribute__((amdgpu_waves_per_eu(TRACK_WAVES_PER_EU, TRACK_WAVES_PER_EU)))
+// The exact variant's double-double accumulators (128 VGPRs) do not fit the 3-waves budget: 2 waves per SIMD (256 VGPRs) still
+// hold one 512-thread workgroup per CU, which is what track_blocks_per_cu() and the cluster sizes assume.
+#define TRACK_WAVES_PER_EU_X 2
+#define TRACK_OCC __attribute__((amdgpu_waves_per_eu(EXACT ? TRACK_WAVES_PER_EU_X : TRACK_WAVES_PER_EU, \
+                                                     EXACT ? TRACK_WAVES_PER_EU_X : TRACK_WAVES_PER_EU)))
 // ONE: the single pair of the sequential API arrives by value in the kernel-argument segment (no
 // H2D copy of the descriptor in front of the launch); otherwise descs[] lives in HBM (batches).
 // epoch_base: mailbox epochs keep counting across launches, so the mailbox is never re-zeroed.
@@ -704,7 +880,9 @@ __device__ __forceinline__ void fused_block(const Cand* cand, const f4v* preg, g
 // conditions are wave-uniform scalars (UNI / readfirstlane), so the accept / reject ladder of optimizer.cpp:258-304 is scalar
 // branches over a dozen values instead of exec-masked code that copies two 19-word states and a pose through every arm; what a
 // pass hands to the next one (candidate poses, the single pose of a refill / level entry) is written to LDS where it is produced.
-template <bool ONE>
+// EXACT (TrackParams::exact_sums): the reference's own per-point float terms, summed as double-double from the
+// first addition on (per thread, butterflies, LDS, mailbox) and rounded to float once.  Everything else is shared.
+template <bool ONE, bool EXACT>
 __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDesc one, const PairDesc* __restrict__ descs,
                                                                    TrackParams prm, revo_pair_result* __restrict__ out,
                                                                    EvalOut* __restrict__ eval_out, u64* __restrict__ mail,
@@ -714,7 +892,7 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
   __shared__ Cand s_cand[2][KMAX];
   __shared__ PassCtl s_pass[2];
   __shared__ SolverState s_sv[KMAX];
-  __shared__ double s_part[NWAVES][NSUM];
+  __shared__ double s_part[NWAVES][EXACT ? NSUM_X : NSUM];
   __shared__ int s_evals[REVO_L];  // residual evaluations per level, in the reference's count (wave 0 / lane 0 only)
 #ifdef REVO_TRACK_PROFILE
   // [12 + l]: cycles spent in level l, [12 + L + l]: its passes, [12 + 2L + l]: evaluation, [12 + 3L + l]: barrier + sums +
@@ -734,7 +912,7 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
   if (resident && threadIdx.x == 0) __hip_atomic_fetch_add(resident, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (pair >= n_pairs) return;
   const PairDesc& d = ONE ? one : descs[pair];
-  u64* mail_pair = mail + (size_t)pair * 2 * cluster * NVAL;
+  u64* mail_pair = mail + (size_t)pair * 2 * cluster * (EXACT ? NVAL_X : NVAL);
   const int tid = threadIdx.x, lane = tid & 63, lane_inv = lane, wave = rfl_i(tid >> 6);
   int kmax = 1;  // solver waves: the deepest speculation of any level
 #pragma unroll
@@ -844,13 +1022,14 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
     const float edist = prm.edge_distance[l];
     const bool filt = prm.use_edge_filter != 0;
     // per thread: 27 normal-equation sums + the candidates' good counts (float, slots CSLOT..), and per candidate
-    // sum w r^2 / sum r^2 in double
-    float acc[32];
-    double ed[8];
+    // sum w r^2 / sum r^2 in double.  EXACT: acc = the KMAX good counts, ed = 32 double-double slots (heads, then tails)
+    constexpr int NACC = EXACT ? KMAX : 32, NED = EXACT ? 64 : 8;
+    float acc[NACC];
+    double ed[NED];
 #pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.0f;
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) ed[k] = 0.0;
+    for (int k = 0; k < NED; ++k) ed[k] = 0.0;
     if (mode == MODE_COST) {
       // TrackerNew::evalCostFunction, tracker.cpp:357-393: nearest-pixel DT lookup, both poses in one pass
       float R[2][9], T[2][3];
@@ -859,36 +1038,53 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
 #pragma unroll
       for (int k = 0; k < TRACK_MAXP; ++k)
         if (first + k * stride < N) {
-          ed[0] += (double)cost_point(preg[k], dtm, R[0], T[0], cam, edist, filt);
-          ed[2] += (double)cost_point(preg[k], dtm, R[1], T[1], cam, edist, filt);
+          if constexpr (EXACT) {
+            dd_acc(ed[XERR], ed[32 + XERR], (double)cost_point(preg[k], dtm, R[0], T[0], cam, edist, filt));
+            dd_acc(ed[XERR + 2], ed[32 + XERR + 2], (double)cost_point(preg[k], dtm, R[1], T[1], cam, edist, filt));
+          } else {
+            ed[0] += (double)cost_point(preg[k], dtm, R[0], T[0], cam, edist, filt);
+            ed[2] += (double)cost_point(preg[k], dtm, R[1], T[1], cam, edist, filt);
+          }
         }
       for (int i = first + TRACK_MAXP * stride; i < N; i += stride) {
         const f4v pt = pts[i];
-        ed[0] += (double)cost_point(pt, dtm, R[0], T[0], cam, edist, filt);
-        ed[2] += (double)cost_point(pt, dtm, R[1], T[1], cam, edist, filt);
+        if constexpr (EXACT) {
+          dd_acc(ed[XERR], ed[32 + XERR], (double)cost_point(pt, dtm, R[0], T[0], cam, edist, filt));
+          dd_acc(ed[XERR + 2], ed[32 + XERR + 2], (double)cost_point(pt, dtm, R[1], T[1], cam, edist, filt));
+        } else {
+          ed[0] += (double)cost_point(pt, dtm, R[0], T[0], cam, edist, filt);
+          ed[2] += (double)cost_point(pt, dtm, R[1], T[1], cam, edist, filt);
+        }
       }
     } else {
       const float huber = prm.huber_edge;
-      if (ncand == 4) fused_block<3>(s_cand[pb], preg, pts, first, stride, N, dtm, cam, edist, filt, huber, acc, ed);
-      else if (ncand == 3) fused_block<2>(s_cand[pb], preg, pts, first, stride, N, dtm, cam, edist, filt, huber, acc, ed);
-      else if (ncand == 2) fused_block<1>(s_cand[pb], preg, pts, first, stride, N, dtm, cam, edist, filt, huber, acc, ed);
+      if (ncand == 4) fused_block<3, EXACT>(s_cand[pb], preg, pts, first, stride, N, dtm, cam, edist, filt, huber, acc, ed);
+      else if (ncand == 3) fused_block<2, EXACT>(s_cand[pb], preg, pts, first, stride, N, dtm, cam, edist, filt, huber, acc, ed);
+      else if (ncand == 2) fused_block<1, EXACT>(s_cand[pb], preg, pts, first, stride, N, dtm, cam, edist, filt, huber, acc, ed);
       else {  // a single candidate in full: residual + Jacobian + normal equations
         float R[9], T[3];
         load_pose(s_cand[pb][0], R, T);
 #pragma unroll
         for (int k = 0; k < TRACK_MAXP; ++k)
-          if (first + k * stride < N) full_point(preg[k], dtm, R, T, cam, edist, filt, huber, acc, ed);
-        for (int i = first + TRACK_MAXP * stride; i < N; i += stride) full_point(pts[i], dtm, R, T, cam, edist, filt, huber, acc, ed);
+          if (first + k * stride < N) full_point<EXACT>(preg[k], dtm, R, T, cam, edist, filt, huber, acc, ed);
+        for (int i = first + TRACK_MAXP * stride; i < N; i += stride) full_point<EXACT>(pts[i], dtm, R, T, cam, edist, filt, huber, acc, ed);
       }
     }
     PROF_MARK(te1);
     {
       int lane_r = lane;  // (opaque per pass, like the solver section's: the butterflies' `lane & MASK` predicates are nine SGPR pairs)
       asm volatile("" : "+v"(lane_r));
-      reduce32(acc, lane_r);
-      reduce8d(ed, lane_r);
-      if (lane_r < 32) s_part[wave][idx32(lane_r)] = (double)acc[0];
-      if (lane_r < 8) s_part[wave][32 + idx8(lane_r)] = ed[0];
+      if constexpr (EXACT) {
+        reduce32x(ed, ed + 32, lane_r);
+        reduce4(acc, lane_r);
+        if (lane_r < 32) { s_part[wave][idx32(lane_r)] = ed[0]; s_part[wave][32 + idx32(lane_r)] = ed[32]; }
+        if (lane_r < KMAX) s_part[wave][64 + idx4(lane_r)] = (double)acc[0];
+      } else {
+        reduce32(acc, lane_r);
+        reduce8d(ed, lane_r);
+        if (lane_r < 32) s_part[wave][idx32(lane_r)] = (double)acc[0];
+        if (lane_r < 8) s_part[wave][32 + idx8(lane_r)] = ed[0];
+      }
     }
 #ifdef REVO_TRACK_PROFILE
     const long long tp1 = clock64();
@@ -906,22 +1102,41 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
       // v_readlane pairs from spill registers on the serial path.  Derived from an opaque value they are one v_cmp where used.
       int lane = lane_inv;
       asm volatile("" : "+v"(lane));
-      // lane v < 32: total of float slot v; lanes 32 + 2k, 33 + 2k: total of double slot k (both lanes of the pair)
-      const int ri = lane < 32 ? lane : (lane < NVAL ? 32 + ((lane - 32) >> 1) : 0);
-      double tot = 0.0;
+      float tf;
       bool xok = true;
-      if (redundant || wave == 0) {
+      if constexpr (!EXACT) {
+        // lane v < 32: total of float slot v; lanes 32 + 2k, 33 + 2k: total of double slot k (both lanes of the pair)
+        const int ri = lane < 32 ? lane : (lane < NVAL ? 32 + ((lane - 32) >> 1) : 0);
+        double tot = 0.0;
+        if (redundant || wave == 0) {
 #pragma unroll
-        for (int wv = 0; wv < NWAVES; ++wv) tot += s_part[wv][ri];
+          for (int wv = 0; wv < NWAVES; ++wv) tot += s_part[wv][ri];
+        }
+        if (!redundant) {
+          if (wave == 0) cluster_publish(mail_pair, cluster, member, epoch, tot, lane);
+          xok = cluster_gather(mail_pair, cluster, epoch, lane, &tot);
+        }
+        tf = (float)tot;  // the reference's float accumulators, read once (optimizer.cpp:190, LGSX.h:320-326)
+      } else {
+        // lane v < 32: double-double slot v; lane 32 + j: good count of candidate j.  Waves, then members, in a fixed order;
+        // the float is the one rounding of the (double-double) total
+        const int ri = lane < 32 ? lane : (lane < 32 + KMAX ? 64 + lane - 32 : 64);
+        double th = 0.0, tl = 0.0;
+        if (redundant || wave == 0) {
+#pragma unroll
+          for (int wv = 0; wv < NWAVES; ++wv) dd_add(th, tl, s_part[wv][ri], lane < 32 ? s_part[wv][32 + ri] : 0.0);
+        }
+        if (!redundant) {
+          if (wave == 0) cluster_publish_x(mail_pair, cluster, member, epoch, th, tl, lane);
+          xok = cluster_gather_x(mail_pair, cluster, epoch, lane, &th, &tl);
+        }
+        tf = lane < 32 ? dd_to_float(th, tl) : (float)th;
       }
-      if (!redundant) {
-        if (wave == 0) cluster_publish(mail_pair, cluster, member, epoch, tot, lane);
-        xok = cluster_gather(mail_pair, cluster, epoch, lane, &tot);
-      }
-      const float tf = (float)tot;  // the reference's float accumulators, read once (optimizer.cpp:190, LGSX.h:320-326)
+      // lanes of the totals: sum w r^2 / sum r^2 of candidate 0, the good count of candidate 0
+      constexpr int L_SW0 = EXACT ? XERR : 32, L_SU0 = EXACT ? XERR + 1 : 34, L_N0 = EXACT ? 32 : CSLOT;
 #define TOT(v) rl(tf, (v))
-#define TOT_SW(j) rl(tf, 32 + 2 * DSLOT(j))   // sum w r^2 of candidate j
-#define TOT_N(j) rl(tf, CSLOT + (j))     // its good count
+#define TOT_SW(j) rl(tf, EXACT ? XERR + DSLOT(j) : 32 + 2 * DSLOT(j))   // sum w r^2 of candidate j
+#define TOT_N(j) rl(tf, L_N0 + (j))     // its good count
 #ifdef REVO_TRACK_PROFILE
       tp3 = clock64();
 #endif
@@ -937,7 +1152,7 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
         flags |= 8;
         nmode = MODE_DONE;
       } else if (mode == MODE_COST) {  // tracker.cpp:272-282
-        const float costEye = TOT(32), costInit = TOT(36);  // double slots 0 and 2
+        const float costEye = TOT(L_SW0), costInit = TOT(EXACT ? XERR + 2 : 36);  // double slots 0 and 2
         float Rs[9], Ts[3];
 #pragma unroll
         for (int i = 0; i < 9; ++i) Rs[i] = d.R[i];
@@ -977,11 +1192,11 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
             eo.A[(r + k) * 6 + r] = an;
           } else if (lane < 27) {
             eo.b[lane - 21] = -an;
-          } else if (lane == 32) {
+          } else if (lane == L_SW0) {
             eo.error = an; eo.mean_err = an; eo.sum_w = tf;
-          } else if (lane == 34) {
+          } else if (lane == L_SU0) {
             eo.sum_u = tf;
-          } else if (lane == CSLOT) {
+          } else if (lane == L_N0) {
             eo.good = (int)tf; eo.bad = N - (int)tf;
           }
         }
@@ -1080,7 +1295,7 @@ __global__ void __launch_bounds__(TRACK_THREADS) TRACK_OCC k_track(const PairDes
             for (int i = 0; i < 3; ++i) sv.t[i] = t[i];
           }
           if (consumed) {  // ResidualInfo of the last evaluation the reference's sequence has seen
-            const int g = (int)rl(tf, CSLOT - 1 + consumed);
+            const int g = (int)rl(tf, L_N0 - 1 + consumed);
             sv.good = g; sv.bad = N - g;
           }
         }
@@ -1238,10 +1453,17 @@ void launch_solve6(const float* d_Ab, int n, float* d_x, hipStream_t s) {
   hipLaunchKernelGGL(k_solve6, dim3(n < 256 ? n : 256), dim3(64), 0, s, d_Ab, n, d_x);
 }
 
+// the smallest over every instantiation a context may launch (a cluster's members must all be resident at once)
 int track_blocks_per_cu() {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_track<false>, TRACK_THREADS, 0) != hipSuccess) nb = 1;
-  return nb < 1 ? 1 : nb;
+  int best = 1 << 30;
+  const void* fns[4] = {(const void*)k_track<false, false>, (const void*)k_track<true, false>, (const void*)k_track<false, true>,
+                        (const void*)k_track<true, true>};
+  for (const void* f : fns) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, TRACK_THREADS, 0) != hipSuccess) nb = 1;
+    best = nb < best ? nb : best;
+  }
+  return best < 1 ? 1 : best;
 }
 
 // Mailbox granules carry {epoch, value}; a launch uses at most MAX_TOTAL_EVALS + a few epochs, so every
@@ -1269,7 +1491,7 @@ void launch_track_gate(unsigned* d_resident, unsigned want, hipStream_t s) {
 int launch_track(const PairDesc* d_descs, const TrackParams& prm, revo_pair_result* d_out, EvalOut* d_eval, int n_pairs,
                  unsigned long long* d_mail, unsigned* epoch_io, int cluster, unsigned* d_resident, hipStream_t s) {
   static_assert(MAX_TOTAL_EVALS + 64 < TRACK_EPOCH_WINDOW, "epoch window too small");
-  const unsigned base = next_epoch_base(epoch_io, d_mail, sizeof(unsigned long long) * (size_t)n_pairs * 2 * cluster * NVAL, s);
+  const unsigned base = next_epoch_base(epoch_io, d_mail, sizeof(unsigned long long) * (size_t)n_pairs * 2 * cluster * TRACK_MAIL_NVAL, s);
   const int groups = (n_pairs + 7) / 8;
   float* prof = nullptr;
 #ifdef REVO_TRACK_PROFILE
@@ -1280,8 +1502,12 @@ int launch_track(const PairDesc* d_descs, const TrackParams& prm, revo_pair_resu
   }
   prof = g_prof_cap >= n_pairs ? g_prof_dev : nullptr;
 #endif
-  hipLaunchKernelGGL(k_track<false>, dim3(groups * 8 * cluster), dim3(TRACK_THREADS), 0, s, PairDesc{}, d_descs, prm, d_out,
-                     d_eval, (u64*)d_mail, n_pairs, cluster, base, (unsigned*)nullptr, 0u, prof, d_resident);
+  if (prm.exact_sums)
+    hipLaunchKernelGGL((k_track<false, true>), dim3(groups * 8 * cluster), dim3(TRACK_THREADS), 0, s, PairDesc{}, d_descs, prm, d_out,
+                       d_eval, (u64*)d_mail, n_pairs, cluster, base, (unsigned*)nullptr, 0u, prof, d_resident);
+  else
+    hipLaunchKernelGGL((k_track<false, false>), dim3(groups * 8 * cluster), dim3(TRACK_THREADS), 0, s, PairDesc{}, d_descs, prm, d_out,
+                       d_eval, (u64*)d_mail, n_pairs, cluster, base, (unsigned*)nullptr, 0u, prof, d_resident);
   return groups * 8 * cluster;
 }
 // profile builds: per pair 64 floats of cycle counters of the last batch launch (layout: k_track's s_prof, [63] = passes)
@@ -1300,8 +1526,12 @@ extern "C" int revo_debug_batch_profile_(float* out, int n_pairs) {
 int launch_track_one(const PairDesc& desc, const TrackParams& prm, revo_pair_result* out, EvalOut* eval_out,
                      unsigned long long* d_mail, unsigned* epoch_io, int cluster, unsigned* seq_ptr, unsigned seq_val,
                      unsigned* d_resident, hipStream_t s) {
-  const unsigned base = next_epoch_base(epoch_io, d_mail, sizeof(unsigned long long) * 2 * (size_t)cluster * NVAL, s);
-  hipLaunchKernelGGL(k_track<true>, dim3(8 * cluster), dim3(TRACK_THREADS), 0, s, desc, (const PairDesc*)nullptr, prm, out,
-                     eval_out, (u64*)d_mail, 1, cluster, base, seq_ptr, seq_val, (float*)nullptr, d_resident);
+  const unsigned base = next_epoch_base(epoch_io, d_mail, sizeof(unsigned long long) * 2 * (size_t)cluster * TRACK_MAIL_NVAL, s);
+  if (prm.exact_sums)
+    hipLaunchKernelGGL((k_track<true, true>), dim3(8 * cluster), dim3(TRACK_THREADS), 0, s, desc, (const PairDesc*)nullptr, prm, out,
+                       eval_out, (u64*)d_mail, 1, cluster, base, seq_ptr, seq_val, (float*)nullptr, d_resident);
+  else
+    hipLaunchKernelGGL((k_track<true, false>), dim3(8 * cluster), dim3(TRACK_THREADS), 0, s, desc, (const PairDesc*)nullptr, prm, out,
+                       eval_out, (u64*)d_mail, 1, cluster, base, seq_ptr, seq_val, (float*)nullptr, d_resident);
   return 8 * cluster;
 }

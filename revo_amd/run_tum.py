@@ -4,7 +4,8 @@ VO on one GPU and writes poses_<dataset>.txt in TUM format (system.cpp:48-49,76-
 
 --streams N runs the YAML's Datasets list N at a time through one vo.MultiREVO handle (a finished dataset's stream takes the
 next one) and writes the same poses_<dataset>.txt files; the PNG decoders are split among the datasets that run at once.
---gpu-decode (with --streams) decodes the PNGs on the GPU instead (tum.GpuFrameSource): same pose files."""
+--gpu-decode (with --streams) decodes the PNGs on the GPU instead (tum.GpuFrameSource): same pose files.
+--exact-sums runs the tracker in its exact-sums mode (api.CameraPyr.setExactSums): sequential or with --streams."""
 import os
 import sys
 import time
@@ -16,7 +17,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]]")
+              "[--streams N [--gpu-decode]] [--exact-sums]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -29,6 +30,9 @@ def main(argv=None):
         i = argv.index("--decoders")
         decoders = int(argv[i + 1])
         argv = argv[:i] + argv[i + 2:]
+    exact_sums = "--exact-sums" in argv  # the tracker's exact-sums mode (both drivers)
+    if exact_sums:
+        argv = [a for a in argv if a != "--exact-sums"]
     gpu_decode = "--gpu-decode" in argv  # PNG decoding on the GPU (multi-stream driver only)
     if gpu_decode:
         argv = [a for a in argv if a != "--gpu-decode"]
@@ -56,10 +60,10 @@ def main(argv=None):
     device = int(argv[2]) if len(argv) > 2 else 0
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
-        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode)
+        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
-        cam = api.CameraPyr(pyr_settings, device=device)
+        cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
         drawer = ply.ModelExporter() if model_dir else None
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
                       mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"])
@@ -105,7 +109,7 @@ def _report_ate(folder, poses):
             print("ATE RMSE vs groundtruth.txt: %.4f m over %d poses" % (synth.ate_rmse(est, ref), len(est)))
 
 
-def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False):
+def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -135,7 +139,8 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
                                 skip_first_n_frames=io["skip_first_n_frames"], read_n_images=io["read_n_images"]):
                 yield f
 
-    drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"])
+    drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"],
+                       exact_sums=exact_sums)
     t0 = time.perf_counter()
     try:
         res = drv.run([frames(f) for f in folders])

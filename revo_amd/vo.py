@@ -176,7 +176,8 @@ class MultiREVO:
     lockstep, one tracker grid and one quality vote per step for all of them.  Per stream the poses, keyframe decisions and
     time stamps are those of a REVO on that sequence alone.
 
-    The tracker settings are a snapshot taken when the handle is created.
+    The tracker settings are a snapshot taken when the handle is created, and so is the exact-sums mode (exact_sums: it
+    applies to the context the handle creates; a cameraPyr handed in keeps its own, see api.CameraPyr.setExactSums).
 
     submit([(stream, bgr, depth, timestamp), ...]) queues at most one frame per stream (one batched build), step() runs one
     loop body for every stream with work and returns [(stream, 4x4 pose, new_keyframe, timestamp)].  A keyframe change is
@@ -184,17 +185,19 @@ class MultiREVO:
     (re-tracked against the new keyframe) with new_keyframe = True."""
 
     def __init__(self, settingsPyr, n_streams, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 max_queue=2):
+                 max_queue=2, exact_sums=False):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         if cameraPyr is None:
-            self.camPyr = api.CameraPyr(settingsPyr, device=device)
+            self.camPyr = api.CameraPyr(settingsPyr, device=device, exact_sums=exact_sums)
             self.mTracker = api.TrackerNew(self.settingsTracker, settingsPyr, self.camPyr)  # the context's tracker settings
         else:
             # A context handed in may be shared with a running REVO: setting its tracker would clear that driver's past clouds
             # and change its settings.  The handle takes the context's tracker settings as they are.
             if settingsTracker is not None:
                 raise ValueError("MultiREVO on a given cameraPyr uses that context's tracker settings: pass settingsTracker=None")
+            if exact_sums:
+                raise ValueError("MultiREVO on a given cameraPyr uses that context's exact-sums mode: set it on the cameraPyr")
             self.camPyr = cameraPyr
         self.device = int(device)
         self.n_streams = int(n_streams)
