@@ -557,6 +557,60 @@ int revo_vo_multi_submit_device(revo_vo_multi* m, int n, const revo_stream_frame
                                 double depth_scale_factor, void* producer_stream);
 
 /* ---------------------------------------------------------------------------
+ * World-frame voxel map: what MapDrawer shows (gui/MapDrawer.cc, fed one coloured keyframe cloud + T_w_kf per keyframe from
+ * system.cpp:162-168,232-238), fused on the device into one point per voxel.  A keyframe's input points are exactly the
+ * level-0 points of revo_pyramid_colored_pcl(kf, 0, dense) with its full-resolution BGR bytes, read from the pyramid's planes
+ * (no cloud is formed).  Per point, in float32 with every operation rounded on its own: pw = ((R0*X + R1*Y) + R2*Z) + t, key
+ * k = (int)floorf(pw / voxel), fixed point q = llrintf(pw * 2^20).  A point is dropped (and counted) when some |pw| >= 2048 m,
+ * some key lies outside [-2^20, 2^20 - 1] or some pw is not finite.  Per voxel: count, sum q (int64 x 3), sum B, G, R (u64),
+ * all accumulated with integer atomics: the map depends on its input points and poses only -- not on the order or the
+ * batching of integrations, the launch, the stream count or the driver (DESIGN 11 states the contract).
+ * Extraction: one point per voxel in ascending order of the key packed as (kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20);
+ * xyz = (float)((double)sum_q / (double)count * 2^-20), colour = (sum_c + count / 2) / count.  The float64 mean is exact
+ * while count <= 2^22 points per voxel.
+ * All work of a map runs on its context's tracker stream.  One handle must not be used concurrently.
+ * ------------------------------------------------------------------------- */
+typedef struct revo_map revo_map;
+/* voxel: edge in metres (finite, > 0); dense: the cloud mode of generateColoredPcl's densePcl (imgpyramidrgbd.cpp:279-327);
+ * initial_voxels: starting capacity (the table grows by rehashing on the device, no point is lost); max_voxels (1 .. 2^28): hard
+ * bound on the voxels of the map. */
+int revo_map_create(revo_ctx* ctx, float voxel, int dense, size_t initial_voxels, size_t max_voxels, revo_map** out);
+/* Waits for the map's work.  A map still attached to revo_vo_multi streams is detached from them first. */
+void revo_map_destroy(revo_map* m);
+/* MapDrawer::addPclAndKfPoseToQueue(kfPyr->generateColoredPcl(0, dense), T_w_kf) (system.cpp:165-167,235-237), fused into
+ * the map.  Asynchronous: enqueued on the context's tracker stream behind the keyframe's build; the pyramid may be destroyed
+ * right after the call.  kf: a pyramid of revo_pyramid_create* / revo_vo_keyframe / revo_vo_multi_keyframe of the map's
+ * context (batch views keep no colour: REVO_ERR_INVALID_ARG).  T_w_kf: finite, column-major.
+ * REVO_ERR_CAPACITY: the keyframe would take the map past max_voxels.  The integration is then all or nothing: none of its
+ * points is in the map, the counters are unchanged except keyframes_rejected, and the map stays usable.  (Only when the map
+ * could reach max_voxels does the call wait for the device to decide; otherwise it returns at once.) */
+int revo_map_integrate(revo_map* m, const revo_pyr* kf, const float T_w_kf_colmajor[16]);
+/* n keyframes in one launch; the result is the same as n revo_map_integrate calls in any order.  All or nothing as a whole. */
+int revo_map_integrate_many(revo_map* m, int n, const revo_pyr* const* kfs, const float* T_w_kf_colmajor_n16);
+/* Empties the map (capacity and settings stay). */
+int revo_map_clear(revo_map* m);
+typedef struct revo_map_info_t {
+  size_t voxels;              /* occupied voxels                                                    */
+  size_t points_integrated;   /* input points accumulated                                           */
+  size_t points_dropped;      /* input points outside the range above                               */
+  size_t capacity;            /* hash-table slots (a power of two; load factor <= 0.5)              */
+  int32_t keyframes;          /* integrations that took effect                                      */
+  int32_t keyframes_rejected; /* integrations refused for max_voxels (revo_vo_multi attachments too) */
+  int32_t rehashes;           /* table growths                                                      */
+} revo_map_info_t;
+/* Waits for the map. */
+int revo_map_info(revo_map* m, revo_map_info_t* out);
+/* Waits for the map, then writes the voxels with count >= max(min_count, 1) in key order: xyz (3 floats), rgb (3 bytes R,G,B),
+ * count (1 u32) per voxel, at most cap of them; *n = how many there are.  xyz == NULL only counts (rgb, count may be NULL).
+ * REVO_ERR_CAPACITY (nothing written) if cap < *n. */
+int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8_t* rgb, uint32_t* count, size_t cap, size_t* n);
+/* Every keyframe the stream promotes from now on is integrated into m, in the step's one batched launch on the tracker stream,
+ * right behind the promotion (the first frame of a sequence included).  m == NULL detaches.  m must belong to the handle's
+ * context.  revo_vo_multi_reset detaches the stream's map; a step never fails for a map: a refused integration (max_voxels)
+ * is counted in its keyframes_rejected. */
+int revo_vo_multi_attach_map(revo_vo_multi* mv, int stream, revo_map* m);
+
+/* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,
  * Adler-32 checked) runs one wave64 per image; the row filters (None, Sub, Up, Average, Paeth) are undone in a second

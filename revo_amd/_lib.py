@@ -127,6 +127,15 @@ def lib():
     L.revo_vo_multi_num_keyframes.argtypes = [vp, C.c_int]
     L.revo_vo_multi_keyframe.argtypes = [vp, C.c_int, vpp, f32p]
     L.revo_vo_multi_submit_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, vp]
+    L.revo_map_create.argtypes = [vp, C.c_float, C.c_int, C.c_size_t, C.c_size_t, vpp]
+    L.revo_map_destroy.argtypes = [vp]
+    L.revo_map_destroy.restype = None
+    L.revo_map_integrate.argtypes = [vp, vp, f32p]
+    L.revo_map_integrate_many.argtypes = [vp, C.c_int, vpp, f32p]
+    L.revo_map_clear.argtypes = [vp]
+    L.revo_map_info.argtypes = [vp, vp]
+    L.revo_map_extract.argtypes = [vp, C.c_size_t, f32p, u8p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.revo_vo_multi_attach_map.argtypes = [vp, C.c_int, vp]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairIn,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairIn, MapInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -220,6 +220,70 @@ class ImgPyramidRGBD:
 
     def prepareKfForStorage(self):  # imgpyramidrgbd.h:156-169: effectively a no-op in the reference
         return None
+
+
+class VoxelMap:
+    """World-frame voxel map fused on the device (revo_map_* in include/revo_hip.h): what MapDrawer shows, one coloured point
+    per voxel of edge `voxel` metres.  integrate(pyr, T_w) adds the level-0 points of pyr.generateColoredPcl(0, dense) at the
+    keyframe pose T_w (4x4, keyframe -> world); the map depends on those points and poses only, not on the order, batching or
+    driver of the integrations.  The table grows on the device; max_voxels is a hard bound (REVO_ERR_CAPACITY: the keyframe
+    is not integrated, the map is unchanged)."""
+
+    def __init__(self, cameraPyr, voxel, dense=False, max_voxels=1 << 24, initial_voxels=1 << 16):
+        self.cameraPyr = cameraPyr  # the map lives on this context
+        self.voxel = float(voxel)
+        self.dense = bool(dense)
+        self._h = vp()
+        check(_lib.lib().revo_map_create(cameraPyr._h, C.c_float(voxel), 1 if dense else 0, int(initial_voxels),
+                                         int(max_voxels), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().revo_map_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def integrate(self, pyr, T_w):
+        """Asynchronous on the device; the pyramid may go right after the call."""
+        check(_lib.lib().revo_map_integrate(self._h, pyr._h, _p(_cm4(T_w), f32p)))
+
+    def integrate_many(self, pyrs, T_ws):
+        """Several keyframes in one launch: the same map as integrating them one by one, in any order."""
+        pyrs = list(pyrs)
+        hs = (vp * max(1, len(pyrs)))(*[p._h.value for p in pyrs])
+        T = np.ascontiguousarray(np.concatenate([_cm4(M) for M in T_ws]) if pyrs else np.zeros(16, np.float32))
+        check(_lib.lib().revo_map_integrate_many(self._h, len(pyrs), hs, _p(T, f32p)))
+
+    def clear(self):
+        check(_lib.lib().revo_map_clear(self._h))
+
+    def info(self):
+        i = MapInfo()
+        check(_lib.lib().revo_map_info(self._h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in MapInfo._fields_}
+
+    def points(self, min_count=1):
+        """(N x 3 float32 xyz, N x 3 uint8 RGB, N uint32 count) in ascending packed-key order."""
+        L = _lib.lib()
+        n = C.c_size_t()
+        check(L.revo_map_extract(self._h, int(min_count), None, None, None, 0, C.byref(n)))
+        xyz = np.empty((n.value, 3), np.float32)
+        rgb = np.empty((n.value, 3), np.uint8)
+        cnt = np.empty(n.value, np.uint32)
+        m = C.c_size_t()
+        check(L.revo_map_extract(self._h, int(min_count), _p(xyz, f32p), _p(rgb, u8p), cnt.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                 n.value, C.byref(m)))
+        return xyz[:m.value], rgb[:m.value], cnt[:m.value]
+
+    def save_ply(self, path, min_count=1):
+        """Binary little-endian PLY, one vertex per voxel in key order: xyz float32, RGB uchar, `count` uint32."""
+        from . import ply
+        return ply.write_voxel_ply(path, *self.points(min_count))
 
 
 class Optimizer:

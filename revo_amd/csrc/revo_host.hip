@@ -18,6 +18,7 @@
 #include "revo_dev.h"
 #include "revo_mat4.h"
 #include "revo_multi.h"
+#include "revo_map.h"
 
 // ------------------------------------------------------------------ errors --
 static thread_local std::string g_err;
@@ -1123,6 +1124,30 @@ extern "C" int revo_pyramid_colored_pcl(revo_pyr* p, int lvl, int dense, float* 
     if ((size_t)total > cap_points) return fail(REVO_ERR_CAPACITY, "host buffer too small");
     if (total) HIPCHECK(hipMemcpy(dst8, c->d_pcl_out, (size_t)total * 32, hipMemcpyDeviceToHost));
   }
+  return REVO_OK;
+}
+
+// The voxel map (revo_map.hip) reads level 0 of a keyframe and its colour on the context's tracker stream, behind the build
+// (and any deferred work) of the pyramid, like revo_pyramid_colored_pcl.  A single-frame pyramid's set goes back to the pool
+// behind ev_free, recorded on that stream (revo_pyramid_destroy); a revo_vo_multi keyframe slot is rewritten on it.
+extern "C" int revo_map_source_(revo_pyr* p, MapSource* out) {
+  if (!p || !out) return fail(REVO_ERR_INVALID_ARG, "null pyramid");
+  revo_ctx* c = p->ctx;
+  HIPCHECK(hipSetDevice(c->device));
+  if (!(p->owns_fs || p->has_colour) || !p->fs->d_bgr)
+    return fail(REVO_ERR_INVALID_ARG, "batch views keep no colour image (rgbFullSize): use revo_pyramid_create");
+  { int rc = wait_ready(c, p); if (rc) return rc; }
+  const size_t n0 = c->geom.lv[0].npix, f = (size_t)p->frame;
+  out->ctx = c;
+  out->depth = p->fs->p.depth[0] + f * n0;
+  out->edges = p->fs->p.edges[0] + f * n0;
+  out->bgr = p->fs->d_bgr + f * n0 * 3;
+  return REVO_OK;
+}
+extern "C" int revo_map_ctx_geom_(const revo_ctx* c, MapCtxGeom* out) {
+  if (!c || !out) return fail(REVO_ERR_INVALID_ARG, "null context");
+  const LevelGeom& l = c->geom.lv[0];
+  *out = MapCtxGeom{c->device, l.w, l.h, l.fx, l.fy, l.cx, l.cy, c->geom.depth_min, c->geom.depth_max, (void*)c->stream};
   return REVO_OK;
 }
 

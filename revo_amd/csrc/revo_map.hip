@@ -1,0 +1,580 @@
+// revo_map.hip -- world-frame voxel map fused on the device from keyframe clouds (revo_map_* in include/revo_hip.h).
+//
+// The reference draws every keyframe's coloured cloud at its keyframe pose (gui/MapDrawer.cc, fed by system.cpp:162-168,
+// 232-238).  Here each keyframe is integrated straight from its level-0 planes into an open-addressing hash of voxels:
+//   * keys: the voxel index packed into 63 bits ((kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20)), inserted by a 64-bit
+//     CAS, linear probing from a mixed hash, table size a power of two at a load factor <= 0.5;
+//   * values: count, the three 2^-20 m fixed-point coordinate sums (int64) and the three colour sums (u64), 64 B per slot,
+//     updated by integer atomics only -- the sums are exact, so no launch order, batching or combining can change them;
+//   * a wave first sums runs of equal keys among its 64 adjacent pixels (segmented shuffle reduction): in dense mode at small
+//     voxels most neighbours share a voxel, and one lane per run does the atomics.
+// Capacity: the host keeps an upper bound of the voxels (the last count the device published into pinned memory plus the
+// points of every integration since), grows the table before an integration could pass a load of 0.5 (one rehash kernel into
+// a table of the next power of two that fits), and only when the bound could pass max_voxels does it take the checked path:
+// insert the keys, decide on the device (count <= max_voxels), take the new keys out again if refused, then accumulate.
+// All of it runs on the context's tracker stream, behind the keyframe's build (revo_map_source_).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "../../include/revo_hip.h"
+#include "revo_map.h"
+
+extern "C" void revo_ctx_retain_(revo_ctx*);
+extern "C" void revo_ctx_release_(revo_ctx*);
+extern "C" void revo_set_error_(const char* msg);
+
+#define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
+#define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
+#define MAP_MAX_CAP (1ull << 31)
+#define MAP_MAX_VOXELS (1ull << 28)
+
+typedef unsigned long long u64;
+
+struct MapVal { u64 n, qx, qy, qz, sb, sg, sr, pad; };  // count, sum q (two's complement int64), sum B, G, R
+struct MapStats {
+  u64 occ, pts, drop, kfs, rejected, fault;
+  u64 ok, pad;
+  u64 shard[MAP_SHARDS][16];  // [0] new voxels, [1] points, [2] dropped points of the batch in flight
+};
+struct MapDesc {  // one keyframe of a launch
+  const float* depth; const uint8_t* edges; const uint8_t* bgr;
+  float R[9], t[3];  // T_w_kf, R row-major
+  float voxel; int dense;
+  u64* keys; MapVal* vals; unsigned mask;
+  MapStats* st;
+};
+struct MapCommit {  // one map of a launch
+  MapStats* st; u64* pub; u64 max_voxels, seq; int n_kf, check;
+};
+struct MapGeomK { int w, npix; float fx, fy, cx, cy, dmin, dmax; };
+enum { MAP_FUSED = 0, MAP_INSERT = 1, MAP_ACCUM = 2 };
+
+__device__ __forceinline__ bool map_depth_ok(float Z, float dmin, float dmax) {
+  return isfinite(Z) && Z > dmin && Z < dmax;  // depth_ok of revo_pyramid.hip (imgpyramidrgbd.cpp:208)
+}
+__device__ __forceinline__ u64 map_hash(u64 k) {  // splitmix64 finaliser
+  k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+  k ^= k >> 27; k *= 0x94d049bb133111ebull;
+  return k ^ (k >> 31);
+}
+// The slot of `key`, inserted if absent (INSERT) or looked up.  Probing is bounded by the table size (the host keeps the
+// load <= 0.5, so a full table means a broken invariant: counted in fault, never a hang).
+template <bool INSERT>
+__device__ __forceinline__ unsigned map_slot(u64* keys, unsigned mask, u64 key, unsigned* n_new, u64* fault) {
+  unsigned s = (unsigned)map_hash(key) & mask;
+  for (unsigned i = 0; i <= mask; ++i) {
+    u64 k = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == key) return s;
+    if (k == MAP_EMPTY) {
+      if (!INSERT) break;
+      k = atomicCAS(&keys[s], MAP_EMPTY, key);
+      if (k == MAP_EMPTY) { if (n_new) atomicAdd(n_new, 1u); return s; }
+      if (k == key) return s;
+    }
+    s = (s + 1) & mask;
+  }
+  atomicOr(fault, 1ull);
+  return ~0u;
+}
+
+// One thread per level-0 pixel of each keyframe (blockIdx.x / nb = keyframe): the selection of k_pcl_walk (dense || edge,
+// usable depth), its back-projection, the world point, key and fixed point; then per wave a segmented sum over runs of equal
+// keys and one lane per run updates the voxel.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_map_walk(const MapDesc* __restrict__ descs, int nb, MapGeomK g) {
+  __shared__ unsigned s_cnt[3];
+  const int di = blockIdx.x / nb;
+  const MapDesc& d = descs[di];
+  if (MODE == MAP_ACCUM && !d.st->ok) return;  // refused: nothing of this map's batch is accumulated
+  if (MODE != MAP_ACCUM) {
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+  }
+  const int p = (blockIdx.x - di * nb) * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  u64 key = MAP_EMPTY;
+  long long qx = 0, qy = 0, qz = 0;
+  unsigned n = 0, cb = 0, cg = 0, cr = 0;
+  bool dropped = false;
+  if (p < g.npix) {
+    const float Z = d.depth[p];
+    if ((d.dense || d.edges[p]) && map_depth_ok(Z, g.dmin, g.dmax)) {
+      const int x = p % g.w, y = p / g.w;
+      const float X = __fdiv_rn(Z * ((float)x - g.cx), g.fx);  // k_pcl_walk<true>
+      const float Y = __fdiv_rn(Z * ((float)y - g.cy), g.fy);
+      float pw[3];
+      int k[3];
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        pw[i] = ((d.R[3 * i] * X + d.R[3 * i + 1] * Y) + d.R[3 * i + 2] * Z) + d.t[i];
+        const float f = floorf(__fdiv_rn(pw[i], d.voxel));
+        ok = ok && fabsf(pw[i]) < 2048.0f && f >= -1048576.0f && f <= 1048575.0f;  // NaN / inf fail every comparison
+        k[i] = ok ? (int)f : 0;
+      }
+      if (ok) {
+        key = ((u64)(k[0] + (1 << 20)) << 42) | ((u64)(k[1] + (1 << 20)) << 21) | (u64)(k[2] + (1 << 20));
+        qx = (long long)rintf(pw[0] * 1048576.0f);  // exact product; rint = llrintf's round-to-nearest-even
+        qy = (long long)rintf(pw[1] * 1048576.0f);
+        qz = (long long)rintf(pw[2] * 1048576.0f);
+        const uint8_t* px = d.bgr + (size_t)p * 3;
+        cb = px[0]; cg = px[1]; cr = px[2];
+        n = 1;
+      } else {
+        dropped = true;
+      }
+    }
+  }
+  // runs of equal keys inside the wave: run id = number of run heads up to this lane; suffix sums restricted to the run
+  const u64 kup = __shfl_up((unsigned long long)key, 1, 64);
+  const bool head = lane == 0 || kup != key;
+  const u64 hb = __ballot(head);
+  const int rid = __popcll(lane == 63 ? hb : (hb & ((2ull << lane) - 1ull)));
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int ro = __shfl_down(rid, off, 64);
+    const long long ax = __shfl_down(qx, off, 64), ay = __shfl_down(qy, off, 64), az = __shfl_down(qz, off, 64);
+    const unsigned an = __shfl_down(n, off, 64), ab = __shfl_down(cb, off, 64), ag = __shfl_down(cg, off, 64),
+                   ar = __shfl_down(cr, off, 64);
+    if (lane + off < 64 && ro == rid) { qx += ax; qy += ay; qz += az; n += an; cb += ab; cg += ag; cr += ar; }
+  }
+  if (head && key != MAP_EMPTY) {
+    const unsigned s = MODE == MAP_ACCUM ? map_slot<false>(d.keys, d.mask, key, nullptr, &d.st->fault)
+                                         : map_slot<true>(d.keys, d.mask, key, &s_cnt[0], &d.st->fault);
+    if (MODE != MAP_INSERT && s != ~0u) {
+      MapVal* v = d.vals + s;
+      atomicAdd(&v->n, (u64)n);
+      atomicAdd(&v->qx, (u64)qx); atomicAdd(&v->qy, (u64)qy); atomicAdd(&v->qz, (u64)qz);
+      atomicAdd(&v->sb, (u64)cb); atomicAdd(&v->sg, (u64)cg); atomicAdd(&v->sr, (u64)cr);
+    }
+    if (MODE != MAP_ACCUM) atomicAdd(&s_cnt[1], n);
+  }
+  if (MODE != MAP_ACCUM) {
+    if (dropped) atomicAdd(&s_cnt[2], 1u);
+    __syncthreads();
+    if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(&d.st->shard[blockIdx.x & (MAP_SHARDS - 1)][threadIdx.x], (u64)s_cnt[threadIdx.x]);
+  }
+}
+
+// One thread per map of the launch: fold the batch counters, decide (checked path: the new voxel count against max_voxels),
+// publish the voxel count to the host (pinned memory, read as a lagged upper bound for the growth check).
+__global__ void __launch_bounds__(64) k_map_commit(const MapCommit* __restrict__ cm, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const MapCommit c = cm[i];
+  MapStats* s = c.st;
+  u64 nw = 0, np = 0, nd = 0;
+  for (int k = 0; k < MAP_SHARDS; ++k) {
+    nw += s->shard[k][0]; np += s->shard[k][1]; nd += s->shard[k][2];
+    s->shard[k][0] = 0; s->shard[k][1] = 0; s->shard[k][2] = 0;
+  }
+  const bool ok = !c.check || s->occ + nw <= c.max_voxels;
+  s->ok = ok ? 1 : 0;
+  if (ok) { s->occ += nw; s->pts += np; s->drop += nd; s->kfs += (u64)c.n_kf; }
+  else s->rejected += (u64)c.n_kf;
+  c.pub[0] = s->occ;
+  c.pub[2] = ok ? 1 : 0;
+  __threadfence_system();
+  *(volatile u64*)&c.pub[1] = c.seq;  // the host reads the sequence word first
+}
+
+// Refused batch: its keys are exactly the occupied slots with count 0 (a committed voxel has count >= 1).  Taking them out
+// restores the table as it was -- every older key's probe path only crosses keys older than itself.
+__global__ void __launch_bounds__(256) k_map_rollback(u64* keys, const MapVal* vals, unsigned cap, const MapStats* st) {
+  if (st->ok) return;
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i < cap && keys[i] != MAP_EMPTY && vals[i].n == 0) keys[i] = MAP_EMPTY;
+}
+
+__global__ void __launch_bounds__(256) k_map_rehash(const u64* __restrict__ okeys, const MapVal* __restrict__ ovals, unsigned ocap,
+                                                    u64* nkeys, MapVal* nvals, unsigned nmask, u64* fault) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= ocap) return;
+  const u64 key = okeys[i];
+  if (key == MAP_EMPTY) return;
+  const unsigned s = map_slot<true>(nkeys, nmask, key, nullptr, fault);
+  if (s != ~0u) nvals[s] = ovals[i];
+}
+
+// Occupied slots with count >= min_count, compacted in arrival order (the host sorts by key): key, xyz, packed RGB, count.
+__global__ void __launch_bounds__(256) k_map_extract(const u64* __restrict__ keys, const MapVal* __restrict__ vals, unsigned cap,
+                                                     u64 min_count, unsigned* total, u64* okey, float* oxyz, unsigned* orgb,
+                                                     unsigned* ocount) {
+  __shared__ unsigned s_n, s_base;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  const u64 key = i < cap ? keys[i] : MAP_EMPTY;
+  MapVal v{};
+  bool sel = false;
+  if (key != MAP_EMPTY) { v = vals[i]; sel = v.n >= min_count; }
+  const unsigned o = sel ? atomicAdd(&s_n, 1u) : 0u;
+  __syncthreads();
+  if (threadIdx.x == 0) s_base = s_n ? atomicAdd(total, s_n) : 0u;
+  __syncthreads();
+  if (!sel) return;
+  const unsigned j = s_base + o;
+  const double inv = (double)v.n;
+  okey[j] = key;
+  oxyz[3 * j + 0] = (float)((double)(long long)v.qx / inv * 0x1p-20);
+  oxyz[3 * j + 1] = (float)((double)(long long)v.qy / inv * 0x1p-20);
+  oxyz[3 * j + 2] = (float)((double)(long long)v.qz / inv * 0x1p-20);
+  const u64 h = v.n / 2;
+  orgb[j] = (unsigned)((v.sr + h) / v.n) | ((unsigned)((v.sg + h) / v.n) << 8) | ((unsigned)((v.sb + h) / v.n) << 16);
+  ocount[j] = (unsigned)v.n;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side --
+namespace {
+int bad(int code, const std::string& msg) { revo_set_error_(msg.c_str()); return code; }
+#define MCHECK(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t e__ = (expr);                                                                      \
+    if (e__ != hipSuccess) return bad(REVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+  } while (0)
+}  // namespace
+
+// pinned staging of a launch's descriptors (reused once the previous upload out of it has completed)
+struct revo_map_stage {
+  MapDesc* h_desc = nullptr; MapDesc* d_desc = nullptr; int cap_desc = 0;
+  MapCommit* h_com = nullptr; MapCommit* d_com = nullptr; int cap_com = 0;
+  hipEvent_t ev = nullptr; bool recorded = false;
+};
+
+struct revo_map {
+  revo_ctx* ctx = nullptr;
+  MapCtxGeom g{};
+  float voxel = 0.f;
+  int dense = 0;
+  size_t max_voxels = 0;
+  u64* d_keys = nullptr; MapVal* d_vals = nullptr; size_t cap = 0;
+  MapStats* d_st = nullptr;
+  u64* h_pub = nullptr;  // pinned [4]: voxels, sequence of the batch that published them, that batch accepted
+  u64 seq = 0;
+  std::deque<std::pair<u64, size_t>> pending;  // (sequence, points bound) of batches the host has not seen published
+  int rehashes = 0;
+  revo_map_stage* stage = nullptr;
+  std::vector<std::pair<revo_vo_multi*, int>> attached;
+};
+
+extern "C" int revo_map_stage_create_(revo_map_stage** out) {
+  revo_map_stage* st = new revo_map_stage();
+  if (hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    delete st;
+    return bad(REVO_ERR_HIP, "hipEventCreate failed");
+  }
+  *out = st;
+  return REVO_OK;
+}
+extern "C" void revo_map_stage_destroy_(revo_map_stage* st) {
+  if (!st) return;
+  if (st->recorded) (void)hipEventSynchronize(st->ev);
+  hipHostFree(st->h_desc); hipFree(st->d_desc); hipHostFree(st->h_com); hipFree(st->d_com);
+  hipEventDestroy(st->ev);
+  (void)hipGetLastError();
+  delete st;
+}
+static int stage_reserve(revo_map_stage* st, int nd, int nc) {
+  if (st->recorded) MCHECK(hipEventSynchronize(st->ev));  // the previous upload has read the pinned rows
+  if (nd > st->cap_desc) {
+    (void)hipHostFree(st->h_desc); (void)hipFree(st->d_desc);
+    st->h_desc = nullptr; st->d_desc = nullptr; st->cap_desc = 0;
+    MCHECK(hipHostMalloc((void**)&st->h_desc, sizeof(MapDesc) * nd));
+    MCHECK(hipMalloc((void**)&st->d_desc, sizeof(MapDesc) * nd));
+    st->cap_desc = nd;
+  }
+  if (nc > st->cap_com) {
+    (void)hipHostFree(st->h_com); (void)hipFree(st->d_com);
+    st->h_com = nullptr; st->d_com = nullptr; st->cap_com = 0;
+    MCHECK(hipHostMalloc((void**)&st->h_com, sizeof(MapCommit) * nc));
+    MCHECK(hipMalloc((void**)&st->d_com, sizeof(MapCommit) * nc));
+    st->cap_com = nc;
+  }
+  return REVO_OK;
+}
+
+// upper bound of the map's voxels: the last count the device published + the points of every batch enqueued after it
+static size_t occ_bound(revo_map* m) {
+  const u64 seen = *(volatile u64*)&m->h_pub[1];
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  const u64 occ = *(volatile u64*)&m->h_pub[0];  // written before the sequence word: at least as new
+  while (!m->pending.empty() && m->pending.front().first <= seen) m->pending.pop_front();
+  size_t b = (size_t)occ;
+  for (auto& p : m->pending) b += p.second;
+  return b;
+}
+
+// a table of `newcap` slots (power of two) holding every voxel of the old one
+static int grow(revo_map* m, size_t newcap) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  u64* nk = nullptr; MapVal* nv = nullptr;
+  MCHECK(hipMalloc((void**)&nk, sizeof(u64) * newcap));
+  if (hipMalloc((void**)&nv, sizeof(MapVal) * newcap) != hipSuccess) {
+    (void)hipGetLastError(); hipFree(nk);
+    return bad(REVO_ERR_HIP, "voxel map: no device memory for a table of " + std::to_string(newcap) + " slots");
+  }
+  MCHECK(hipMemsetAsync(nk, 0xff, sizeof(u64) * newcap, s));
+  MCHECK(hipMemsetAsync(nv, 0, sizeof(MapVal) * newcap, s));
+  if (m->cap) {
+    hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals,
+                       (unsigned)m->cap, nk, nv, (unsigned)(newcap - 1), &m->d_st->fault);
+    MCHECK(hipGetLastError());
+    ++m->rehashes;
+    MCHECK(hipStreamSynchronize(s));  // the old table is free once the rehash has read it
+  }
+  hipFree(m->d_keys); hipFree(m->d_vals);
+  m->d_keys = nk; m->d_vals = nv; m->cap = newcap;
+  return REVO_OK;
+}
+
+static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, const MapSource* src, const float* T16,
+                          std::vector<revo_map*>* checked) {
+  if (n <= 0) return REVO_OK;
+  const MapCtxGeom& g = maps[0]->g;
+  hipStream_t s = (hipStream_t)g.stream;
+  MCHECK(hipSetDevice(g.device));
+  const size_t npix = (size_t)g.w * g.h;
+  std::vector<revo_map*> dm;  // distinct maps, first appearance first
+  std::vector<int> nk;
+  for (int i = 0; i < n; ++i) {
+    size_t j = std::find(dm.begin(), dm.end(), maps[i]) - dm.begin();
+    if (j == dm.size()) { dm.push_back(maps[i]); nk.push_back(0); }
+    ++nk[j];
+  }
+  std::vector<int> chk(dm.size(), 0);
+  for (size_t j = 0; j < dm.size(); ++j) {
+    revo_map* m = dm[j];
+    const size_t ub = occ_bound(m), bound = (size_t)nk[j] * npix;
+    chk[j] = ub + bound > m->max_voxels;
+    // the checked path inserts every new key before it decides: room for what the map may hold + all points of the batch
+    const size_t need = 2 * (std::min(ub, m->max_voxels) + bound);
+    if (need > MAP_MAX_CAP) return bad(REVO_ERR_CAPACITY, "voxel map: a batch this large needs more than 2^31 table slots");
+    if (m->cap < need) {
+      size_t c = std::max<size_t>(m->cap * 2, 1024);
+      while (c < need) c *= 2;
+      const int rc = grow(m, c);
+      if (rc) return rc;
+    }
+  }
+  { const int rc = stage_reserve(st, n, (int)dm.size()); if (rc) return rc; }
+  for (int i = 0; i < n; ++i) {
+    revo_map* m = maps[i];
+    MapDesc& d = st->h_desc[i];
+    d.depth = src[i].depth; d.edges = src[i].edges; d.bgr = src[i].bgr;
+    const float* T = T16 + 16 * (size_t)i;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) d.R[3 * r + c] = T[4 * c + r];
+      d.t[r] = T[12 + r];
+    }
+    d.voxel = m->voxel; d.dense = m->dense;
+    d.keys = m->d_keys; d.vals = m->d_vals; d.mask = (unsigned)(m->cap - 1);
+    d.st = m->d_st;
+  }
+  bool any_check = false;
+  for (size_t j = 0; j < dm.size(); ++j) {
+    revo_map* m = dm[j];
+    ++m->seq;
+    st->h_com[j] = MapCommit{m->d_st, m->h_pub, (u64)m->max_voxels, m->seq, nk[j], chk[j]};
+    m->pending.push_back({m->seq, (size_t)nk[j] * npix});
+    any_check = any_check || chk[j];
+    if (chk[j] && checked) checked->push_back(m);
+  }
+  MCHECK(hipMemcpyAsync(st->d_desc, st->h_desc, sizeof(MapDesc) * n, hipMemcpyHostToDevice, s));
+  MCHECK(hipMemcpyAsync(st->d_com, st->h_com, sizeof(MapCommit) * dm.size(), hipMemcpyHostToDevice, s));
+  MCHECK(hipEventRecord(st->ev, s));
+  st->recorded = true;
+  const int nb = (int)((npix + 255) / 256);
+  const MapGeomK gk{g.w, (int)npix, g.fx, g.fy, g.cx, g.cy, g.dmin, g.dmax};
+  const dim3 grid((unsigned)(nb * n)), blk(256), cgrid((unsigned)((dm.size() + 63) / 64)), cblk(64);
+  if (!any_check) {
+    hipLaunchKernelGGL(k_map_walk<MAP_FUSED>, grid, blk, 0, s, st->d_desc, nb, gk);
+    hipLaunchKernelGGL(k_map_commit, cgrid, cblk, 0, s, st->d_com, (int)dm.size());
+  } else {
+    hipLaunchKernelGGL(k_map_walk<MAP_INSERT>, grid, blk, 0, s, st->d_desc, nb, gk);
+    hipLaunchKernelGGL(k_map_commit, cgrid, cblk, 0, s, st->d_com, (int)dm.size());
+    for (size_t j = 0; j < dm.size(); ++j)
+      if (chk[j])
+        hipLaunchKernelGGL(k_map_rollback, dim3((unsigned)((dm[j]->cap + 255) / 256)), blk, 0, s, dm[j]->d_keys, dm[j]->d_vals,
+                           (unsigned)dm[j]->cap, dm[j]->d_st);
+    hipLaunchKernelGGL(k_map_walk<MAP_ACCUM>, grid, blk, 0, s, st->d_desc, nb, gk);
+  }
+  MCHECK(hipGetLastError());
+  return REVO_OK;
+}
+
+static bool pose_finite(const float* T) {
+  for (int i = 0; i < 16; ++i) if (!std::isfinite(T[i])) return false;
+  return true;
+}
+
+extern "C" int revo_map_create(revo_ctx* ctx, float voxel, int dense, size_t initial_voxels, size_t max_voxels, revo_map** out) {
+  if (!ctx || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!std::isfinite(voxel) || !(voxel > 0.0f)) return bad(REVO_ERR_INVALID_ARG, "voxel must be finite and > 0");
+  if (dense != 0 && dense != 1) return bad(REVO_ERR_INVALID_ARG, "dense must be 0 or 1");
+  if (max_voxels < 1 || max_voxels > MAP_MAX_VOXELS) return bad(REVO_ERR_INVALID_ARG, "max_voxels must be 1 .. 2^28");
+  MapCtxGeom g;
+  { const int rc = revo_map_ctx_geom_(ctx, &g); if (rc) return rc; }
+  MCHECK(hipSetDevice(g.device));
+  revo_map* m = new revo_map();
+  m->ctx = ctx; m->g = g; m->voxel = voxel; m->dense = dense; m->max_voxels = max_voxels;
+  revo_ctx_retain_(ctx);
+  struct Guard { revo_map* m; ~Guard() { if (m) revo_map_destroy(m); } } guard{m};
+  MCHECK(hipMalloc((void**)&m->d_st, sizeof(MapStats)));
+  MCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), (hipStream_t)g.stream));
+  MCHECK(hipHostMalloc((void**)&m->h_pub, sizeof(u64) * 4));
+  memset(m->h_pub, 0, sizeof(u64) * 4);
+  { const int rc = revo_map_stage_create_(&m->stage); if (rc) return rc; }
+  size_t c = 1024;
+  const size_t want = std::min<size_t>(std::max<size_t>(initial_voxels, 1), max_voxels) * 2;
+  while (c < want) c *= 2;
+  { const int rc = grow(m, c); if (rc) return rc; }
+  MCHECK(hipStreamSynchronize((hipStream_t)g.stream));
+  guard.m = nullptr;
+  *out = m;
+  return REVO_OK;
+}
+
+extern "C" void revo_map_destroy(revo_map* m) {
+  if (!m) return;
+  const auto att = m->attached;
+  for (auto& a : att) revo_vo_multi_forget_map_(a.first, a.second, m);
+  hipSetDevice(m->g.device);
+  (void)hipStreamSynchronize((hipStream_t)m->g.stream);
+  revo_map_stage_destroy_(m->stage);
+  hipFree(m->d_keys); hipFree(m->d_vals); hipFree(m->d_st); hipHostFree(m->h_pub);
+  (void)hipGetLastError();
+  revo_ctx_release_(m->ctx);
+  delete m;
+}
+
+extern "C" int revo_map_integrate_many(revo_map* m, int n, const revo_pyr* const* kfs, const float* T) {
+  if (!m || n < 0 || (n > 0 && (!kfs || !T))) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (n == 0) return REVO_OK;
+  for (int i = 0; i < n; ++i) {
+    if (!kfs[i]) return bad(REVO_ERR_INVALID_ARG, "null pyramid");
+    if (!pose_finite(T + 16 * (size_t)i)) return bad(REVO_ERR_INVALID_ARG, "T_w_kf is not finite");
+  }
+  std::vector<MapSource> src(n);
+  for (int i = 0; i < n; ++i) {
+    const int rc = revo_map_source_(const_cast<revo_pyr*>(kfs[i]), &src[i]);
+    if (rc) return rc;
+    if (src[i].ctx != m->ctx) return bad(REVO_ERR_INVALID_ARG, "the pyramid belongs to another context than the map");
+  }
+  std::vector<revo_map*> maps(n, m), checked;
+  { const int rc = integrate_core(m->stage, n, maps.data(), src.data(), T, &checked); if (rc) return rc; }
+  if (!checked.empty()) {  // the map could have reached max_voxels: the device has decided, wait for it
+    MCHECK(hipStreamSynchronize((hipStream_t)m->g.stream));
+    if (!m->h_pub[2]) return bad(REVO_ERR_CAPACITY, "voxel map: the keyframes would take it past max_voxels (not integrated)");
+  }
+  return REVO_OK;
+}
+extern "C" int revo_map_integrate(revo_map* m, const revo_pyr* kf, const float T[16]) {
+  if (!m || !kf || !T) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  return revo_map_integrate_many(m, 1, &kf, T);
+}
+
+extern "C" int revo_map_integrate_views_(revo_map_stage* st, int n, revo_map* const* maps, revo_pyr* const* kfs, const float* T) {
+  if (n <= 0) return REVO_OK;
+  std::vector<MapSource> src(n);
+  for (int i = 0; i < n; ++i) {
+    const int rc = revo_map_source_(kfs[i], &src[i]);
+    if (rc) return rc;
+  }
+  return integrate_core(st, n, maps, src.data(), T, nullptr);
+}
+
+extern "C" int revo_map_clear(revo_map* m) {
+  if (!m) return bad(REVO_ERR_INVALID_ARG, "null map");
+  MCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  MCHECK(hipMemsetAsync(m->d_keys, 0xff, sizeof(u64) * m->cap, s));
+  MCHECK(hipMemsetAsync(m->d_vals, 0, sizeof(MapVal) * m->cap, s));
+  MCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), s));
+  MCHECK(hipStreamSynchronize(s));
+  m->pending.clear();
+  m->h_pub[0] = 0; m->h_pub[2] = 1; m->h_pub[1] = m->seq;
+  m->rehashes = 0;
+  return REVO_OK;
+}
+
+static int read_stats(revo_map* m, MapStats* out) {
+  MCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  MCHECK(hipStreamSynchronize(s));
+  MCHECK(hipMemcpy(out, m->d_st, sizeof(MapStats), hipMemcpyDeviceToHost));
+  if (out->fault) return bad(REVO_ERR_HIP, "voxel map: a probe ran through the whole table (load invariant broken)");
+  return REVO_OK;
+}
+
+extern "C" int revo_map_info(revo_map* m, revo_map_info_t* out) {
+  if (!m || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  MapStats st;
+  { const int rc = read_stats(m, &st); if (rc) return rc; }
+  out->voxels = (size_t)st.occ;
+  out->points_integrated = (size_t)st.pts;
+  out->points_dropped = (size_t)st.drop;
+  out->capacity = m->cap;
+  out->keyframes = (int32_t)st.kfs;
+  out->keyframes_rejected = (int32_t)st.rejected;
+  out->rehashes = m->rehashes;
+  return REVO_OK;
+}
+
+extern "C" int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8_t* rgb, uint32_t* count, size_t cap, size_t* n) {
+  if (!m || !n) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  MapStats st;
+  { const int rc = read_stats(m, &st); if (rc) return rc; }
+  hipStream_t s = (hipStream_t)m->g.stream;
+  const size_t nv = std::max<size_t>((size_t)st.occ, 1);
+  char* buf = nullptr;
+  const size_t o_key = 0, o_xyz = o_key + 8 * nv, o_rgb = o_xyz + 12 * nv, o_cnt = o_rgb + 4 * nv, o_tot = o_cnt + 4 * nv;
+  MCHECK(hipMalloc((void**)&buf, o_tot + 256));
+  struct Free { char* p; ~Free() { hipFree(p); } } fr{buf};
+  unsigned* d_tot = (unsigned*)(buf + o_tot);
+  MCHECK(hipMemsetAsync(d_tot, 0, sizeof(unsigned), s));
+  hipLaunchKernelGGL(k_map_extract, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals, (unsigned)m->cap,
+                     (u64)std::max<size_t>(min_count, 1), d_tot, (u64*)(buf + o_key), (float*)(buf + o_xyz),
+                     (unsigned*)(buf + o_rgb), (unsigned*)(buf + o_cnt));
+  MCHECK(hipGetLastError());
+  unsigned tot = 0;
+  MCHECK(hipMemcpyAsync(&tot, d_tot, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  MCHECK(hipStreamSynchronize(s));
+  *n = tot;
+  if (!xyz) return REVO_OK;
+  if (cap < tot) return bad(REVO_ERR_CAPACITY, "voxel map: the output holds fewer voxels than the map has");
+  std::vector<u64> key(tot);
+  std::vector<float> p(3 * (size_t)tot);
+  std::vector<unsigned> c(tot), k(tot);
+  if (tot) {
+    MCHECK(hipMemcpy(key.data(), buf + o_key, 8 * (size_t)tot, hipMemcpyDeviceToHost));
+    MCHECK(hipMemcpy(p.data(), buf + o_xyz, 12 * (size_t)tot, hipMemcpyDeviceToHost));
+    MCHECK(hipMemcpy(c.data(), buf + o_rgb, 4 * (size_t)tot, hipMemcpyDeviceToHost));
+    MCHECK(hipMemcpy(k.data(), buf + o_cnt, 4 * (size_t)tot, hipMemcpyDeviceToHost));
+  }
+  std::vector<unsigned> idx(tot);
+  std::iota(idx.begin(), idx.end(), 0u);
+  std::sort(idx.begin(), idx.end(), [&](unsigned a, unsigned b) { return key[a] < key[b]; });  // keys are distinct
+  for (size_t j = 0; j < tot; ++j) {
+    const unsigned i = idx[j];
+    memcpy(xyz + 3 * j, &p[3 * (size_t)i], 12);
+    if (rgb) { rgb[3 * j] = (uint8_t)c[i]; rgb[3 * j + 1] = (uint8_t)(c[i] >> 8); rgb[3 * j + 2] = (uint8_t)(c[i] >> 16); }
+    if (count) count[j] = k[i];
+  }
+  return REVO_OK;
+}
+
+extern "C" void revo_map_note_attach_(revo_map* m, revo_vo_multi* mv, int stream, int attach) {
+  if (!m) return;
+  auto it = std::find(m->attached.begin(), m->attached.end(), std::make_pair(mv, stream));
+  if (attach && it == m->attached.end()) m->attached.push_back({mv, stream});
+  if (!attach && it != m->attached.end()) m->attached.erase(it);
+}
+extern "C" const revo_ctx* revo_map_ctx_(const revo_map* m) { return m ? m->ctx : nullptr; }

@@ -14,6 +14,7 @@
 #include "../../include/revo_hip.h"
 #include "revo_mat4.h"
 #include "revo_multi.h"
+#include "revo_map.h"
 
 extern "C" void revo_ctx_retain_(revo_ctx*);
 extern "C" void revo_ctx_release_(revo_ctx*);
@@ -68,6 +69,8 @@ struct revo_vo_multi {
   int S = 0, max_queue = 1;
   std::vector<Stream> st;
   std::vector<std::pair<void*, int>> refs;  // step sets and how many queued / current / previous frames still point into them
+  std::vector<revo_map*> maps;              // per stream: the voxel map its promoted keyframes go into (revo_vo_multi_attach_map)
+  revo_map_stage* map_stage = nullptr;      // descriptors of the step's batched map integration
 };
 
 static void ref_add(revo_vo_multi* m, void* set) {
@@ -96,13 +99,16 @@ extern "C" int revo_vo_multi_create(revo_ctx* ctx, int n_streams, int max_queue,
   m->S = n_streams;
   m->max_queue = max_queue;
   m->st.resize(n_streams);
+  m->maps.assign(n_streams, nullptr);
   *out = m;
   return REVO_OK;
 }
 
 extern "C" void revo_vo_multi_destroy(revo_vo_multi* m) {
   if (!m) return;
+  for (int s = 0; s < m->S; ++s) revo_map_note_attach_(m->maps[s], m, s, 0);
   revo_mdev_destroy_(m->dev);  // (synchronises the context's streams; the step sets go with it)
+  revo_map_stage_destroy_(m->map_stage);
   revo_ctx_release_(m->ctx);
   delete m;
 }
@@ -131,7 +137,28 @@ extern "C" int revo_vo_multi_reset(revo_vo_multi* m, int s) {
   if (x.has_prev) ref_drop(m, x.prev.set);
   revo_mdev_clear_past_(m->dev, s, 0);
   x = Stream();
+  revo_map_note_attach_(m->maps[s], m, s, 0);  // the next sequence starts without a map
+  m->maps[s] = nullptr;
   return REVO_OK;
+}
+
+// The map's work (and the integration of promoted slots) is ordered on the tracker stream behind each promotion; a map
+// attached here must live on the handle's context (its stream and its keyframe slots).
+extern "C" int revo_vo_multi_attach_map(revo_vo_multi* m, int s, revo_map* map) {
+  if (!stream_ok(m, s)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
+  if (map && revo_map_ctx_(map) != m->ctx) return bad(REVO_ERR_INVALID_ARG, "the map belongs to another context than the handle");
+  if (map && !m->map_stage) {
+    const int rc = revo_map_stage_create_(&m->map_stage);
+    if (rc) return rc;
+  }
+  revo_map_note_attach_(m->maps[s], m, s, 0);
+  m->maps[s] = map;
+  revo_map_note_attach_(map, m, s, 1);
+  return REVO_OK;
+}
+// revo_map_destroy of an attached map
+extern "C" void revo_vo_multi_forget_map_(revo_vo_multi* m, int s, revo_map* map) {
+  if (stream_ok(m, s) && m->maps[s] == map) m->maps[s] = nullptr;
 }
 
 static int submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16, double depth_scale_factor,
@@ -253,6 +280,7 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
       if (status == REVO_TRACKER_STATE_NEW_KF && !x.just_added_kf) {  // system.cpp:203-241, the re-track deferred to the next step
         x.T_w_kf = x.last.world();  // kfPyr->setTwf(mPoseGraph.back().getCurrToWorld())
         promote.push_back(MultiFrame{s, x.prev.set, x.prev.frame, {}, x.prev.ts});
+        memcpy(promote.back().T_w, x.T_w_kf.m, sizeof(x.T_w_kf.m));
         x.last = Pose{I, x.T_w_kf};  // mPoseGraph.back().setKfFrame(kfPyr)
         ++x.n_keyframes;
         revo_mdev_clear_past_(m->dev, s, -1);  // clearPastLists: the newest N_FRAMES_HIST_VOTING stay
@@ -280,6 +308,7 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
     Stream& x = m->st[s];
     x.T_w_kf = I;
     promote.push_back(MultiFrame{s, x.cur.set, x.cur.frame, {}, x.cur.ts});
+    memcpy(promote.back().T_w, I.m, sizeof(I.m));
     x.last = Pose{I, I};
     ++x.n_keyframes;
     ++x.no_frames;
@@ -292,6 +321,20 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
     x.has_prev = true;
   }
   if ((rc = revo_mdev_promote_(m->dev, (int)promote.size(), promote.data()))) return rc;
+  {  // MapDrawer's cloud of each new keyframe (system.cpp:165-167,235-237): one launch for every attached map, on the tracker
+     // stream behind the promotion's copy and distance transforms; the next promotion into a slot queues behind it
+    std::vector<revo_map*> maps;
+    std::vector<revo_pyr*> kfs;
+    std::vector<float> T;
+    for (const MultiFrame& f : promote)
+      if (m->maps[f.stream]) {
+        maps.push_back(m->maps[f.stream]);
+        kfs.push_back(revo_mdev_keyframe_(m->dev, f.stream));
+        T.insert(T.end(), f.T_w, f.T_w + 16);
+      }
+    if (!maps.empty() && (rc = revo_map_integrate_views_(m->map_stage, (int)maps.size(), maps.data(), kfs.data(), T.data())))
+      return rc;
+  }
   if ((rc = revo_mdev_add_clouds_(m->dev, (int)clouds.size(), clouds.data()))) return rc;
   // results come out in stream order
   std::vector<revo_stream_result> tmp(out, out + n_res);

@@ -81,6 +81,46 @@ class ModelExporter:
         return pcl_path, kf_path
 
 
+VOXEL_PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
+                            ("count", "<u4")])  # 19 bytes per vertex, packed
+
+
+def voxel_ply_header(n):
+    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            "property uint count\nend_header\n" % n).encode("ascii")
+
+
+def write_voxel_ply(path, xyz, rgb, count):
+    """The voxel map (api.VoxelMap) as binary little-endian PLY: one vertex per voxel in the order given (key order),
+    xyz float32, rgb uchar, and the number of points fused into the voxel as `count` (uint32)."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.uint8).reshape(-1, 3)
+    count = np.asarray(count, np.uint32).reshape(-1)
+    if not (len(xyz) == len(rgb) == len(count)):
+        raise ValueError("xyz, rgb and count must have one row per voxel")
+    v = np.empty(len(xyz), VOXEL_PLY_DTYPE)
+    v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    v["count"] = count
+    with open(path, "wb") as f:
+        f.write(voxel_ply_header(len(v)))
+        f.write(v.tobytes())
+    return path
+
+
+def read_voxel_ply(path):
+    """Reader for write_voxel_ply's files -> (xyz N x 3 float32, rgb N x 3 uint8, count N uint32)."""
+    data = open(path, "rb").read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    n = int([l for l in data[:end].decode("ascii").split("\n") if l.startswith("element vertex")][0].split()[2])
+    if data[:end] != voxel_ply_header(n):
+        raise ValueError("not a voxel map PLY")
+    v = np.frombuffer(data, VOXEL_PLY_DTYPE, count=n, offset=end)
+    return (np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["red"], v["green"], v["blue"]], 1), v["count"].copy())
+
+
 def read_ply_vertices(path):
     """Minimal reader for the files above (tests): -> (V x 6 float array, list of edge tuples)."""
     with open(path) as f:

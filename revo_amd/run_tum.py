@@ -5,7 +5,10 @@ VO on one GPU and writes poses_<dataset>.txt in TUM format (system.cpp:48-49,76-
 --streams N runs the YAML's Datasets list N at a time through one vo.MultiREVO handle (a finished dataset's stream takes the
 next one) and writes the same poses_<dataset>.txt files; the PNG decoders are split among the datasets that run at once.
 --gpu-decode (with --streams) decodes the PNGs on the GPU instead (tum.GpuFrameSource): same pose files.
---exact-sums runs the tracker in its exact-sums mode (api.CameraPyr.setExactSums): sequential or with --streams."""
+--exact-sums runs the tracker in its exact-sums mode (api.CameraPyr.setExactSums): sequential or with --streams.
+--map VOXEL fuses every keyframe into a world-frame voxel map of that edge (metres) on the GPU (api.VoxelMap; the settings'
+DO_GENERATE_DENSE_PCL picks dense or edge clouds) and writes map_<dataset>.ply next to the pose file: sequential or with
+--streams, the same file either way."""
 import os
 import sys
 import time
@@ -17,7 +20,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--map VOXEL]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -30,6 +33,14 @@ def main(argv=None):
         i = argv.index("--decoders")
         decoders = int(argv[i + 1])
         argv = argv[:i] + argv[i + 2:]
+    map_voxel = None  # api.VoxelMap edge in metres: map_<dataset>.ply
+    if "--map" in argv:
+        i = argv.index("--map")
+        map_voxel = float(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+        if not (np.isfinite(map_voxel) and map_voxel > 0):
+            print("--map needs a positive voxel edge in metres")
+            return 2
     exact_sums = "--exact-sums" in argv  # the tracker's exact-sums mode (both drivers)
     if exact_sums:
         argv = [a for a in argv if a != "--exact-sums"]
@@ -60,13 +71,14 @@ def main(argv=None):
     device = int(argv[2]) if len(argv) > 2 else 0
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
-        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums)
+        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
         drawer = ply.ModelExporter() if model_dir else None
+        vmap = api.VoxelMap(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"])) if map_voxel else None
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
-                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"])
+                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap)
         nd = tum.default_decoders() if decoders is None else decoders
         rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
                                   read_n_images=io["read_n_images"])
@@ -86,11 +98,21 @@ def main(argv=None):
                 f.write("\n".join(drv.tum_lines()) + "\n")
         print("-----VO Report-----\nFrames Tracked: %d\nKeyframes Tracked: %d\nframes/s (incl. PNG decode, %s): %.1f"
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
+        if vmap is not None:
+            _save_map(vmap, name)
         if drawer is not None:
             out = drawer.saveModel(os.path.join(model_dir, name) if len(io["datasets"]) > 1 else model_dir)
             print("model: %d points of %d keyframes -> %s, %s" % (drawer.nPts, len(drawer.vpKfsF), out[0], out[1]))
         _report_ate(folder, drv.poses)
     return 0
+
+
+def _save_map(vmap, name):
+    info = vmap.info()
+    path = vmap.save_ply("map_%s.ply" % name)
+    print("Map: %d voxels of %g m from %d keyframes, %d points fused, %d points dropped (outside +-2048 m or the key range)%s -> %s"
+          % (info["voxels"], vmap.voxel, info["keyframes"], info["points_integrated"], info["points_dropped"],
+             (", %d keyframes refused (max_voxels)" % info["keyframes_rejected"]) if info["keyframes_rejected"] else "", path))
 
 
 def _report_ate(folder, poses):
@@ -109,7 +131,8 @@ def _report_ate(folder, poses):
             print("ATE RMSE vs groundtruth.txt: %.4f m over %d poses" % (synth.ate_rmse(est, ref), len(est)))
 
 
-def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False):
+def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
+                 map_voxel=None):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -140,7 +163,7 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
                 yield f
 
     drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"],
-                       exact_sums=exact_sums)
+                       exact_sums=exact_sums, map_voxel=map_voxel, map_dense=bool(sysd["do_generate_dense_pcl"]))
     t0 = time.perf_counter()
     try:
         res = drv.run([frames(f) for f in folders])
@@ -155,6 +178,8 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
                 f.write("\n".join(r.tum_lines()) + "\n")
         total += len(r)
         print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
+        if r.map is not None:
+            _save_map(r.map, name)
         _report_ate(folder, r.poses)
     print("%d datasets on %d streams: %.1f frames/s (incl. PNG decode, %s)"
           % (len(folders), streams, total / dt,

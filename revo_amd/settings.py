@@ -140,6 +140,14 @@ class StreamResult(C.Structure):
     ]
 
 
+class MapInfo(C.Structure):
+    """revo_map_info_t (include/revo_hip.h): the state of a voxel map."""
+    _fields_ = [
+        ("voxels", C.c_size_t), ("points_integrated", C.c_size_t), ("points_dropped", C.c_size_t), ("capacity", C.c_size_t),
+        ("keyframes", C.c_int32), ("keyframes_rejected", C.c_int32), ("rehashes", C.c_int32),
+    ]
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

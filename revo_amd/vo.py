@@ -22,7 +22,7 @@ from .settings import StreamFrame, StreamResult, TrackerSettings
 
 class REVO:
     def __init__(self, settingsPyr, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 mapDrawer=None, generate_dense_pcl=False):
+                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         self.camPyr = cameraPyr or api.CameraPyr(settingsPyr, device=device)
@@ -35,6 +35,9 @@ class REVO:
         # system.cpp:162-168,232-238; generate_dense_pcl is DO_GENERATE_DENSE_PCL
         self.mpMapDrawer = mapDrawer
         self.generate_dense_pcl = bool(generate_dense_pcl)
+        # api.VoxelMap: every keyframe the driver reports (the first frame included) is fused into it at its T_w_kf, the moment
+        # the drawer gets its cloud; on the device, no cloud goes through the host
+        self.voxelMap = voxelMap
 
     def __del__(self):
         try:
@@ -74,9 +77,12 @@ class REVO:
         check(_lib.lib().revo_vo_track_next(self._h, pose.ctypes.data_as(f32p), C.byref(kf), C.byref(ts)))
         M = pose.reshape(4, 4).T.copy()
         self.poses.append((ts.value, M))
-        if kf.value and self.mpMapDrawer is not None:
+        if kf.value and (self.mpMapDrawer is not None or self.voxelMap is not None):
             kfPyr, T_w_kf = self.keyframe()
-            self.mpMapDrawer.addPclAndKfPoseToQueue(kfPyr.generateColoredPcl(0, self.generate_dense_pcl), T_w_kf)
+            if self.mpMapDrawer is not None:
+                self.mpMapDrawer.addPclAndKfPoseToQueue(kfPyr.generateColoredPcl(0, self.generate_dense_pcl), T_w_kf)
+            if self.voxelMap is not None:
+                self.voxelMap.integrate(kfPyr, T_w_kf)
         return M, bool(kf.value)
 
     def keyframe(self):
@@ -161,11 +167,13 @@ def tum_lines(poses):
 
 
 class SequenceResult(list):
-    """One sequence of MultiREVO.run: [(4x4 pose, new_keyframe)] in frame order, `poses` [(timestamp, 4x4)], tum_lines()."""
+    """One sequence of MultiREVO.run: [(4x4 pose, new_keyframe)] in frame order, `poses` [(timestamp, 4x4)], tum_lines(),
+    and `map`: its api.VoxelMap (MultiREVO(map_voxel=...)) or None."""
 
     def __init__(self):
         super().__init__()
         self.poses = []
+        self.map = None
 
     def tum_lines(self):
         return tum_lines(self.poses)
@@ -184,8 +192,10 @@ class MultiREVO:
     reported one step late: the step whose vote asks for it reports nothing for that stream, the next one reports the frame
     (re-tracked against the new keyframe) with new_keyframe = True."""
 
+    map_voxel, map_dense, map_max_voxels = None, False, 1 << 24  # run()'s per-sequence maps: off unless __init__ sets them
+
     def __init__(self, settingsPyr, n_streams, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 max_queue=2, exact_sums=False):
+                 max_queue=2, exact_sums=False, map_voxel=None, map_dense=False, map_max_voxels=1 << 24):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         if cameraPyr is None:
@@ -206,6 +216,17 @@ class MultiREVO:
         self._h = vp()
         check(_lib.lib().revo_vo_multi_create(self.camPyr._h, self.n_streams, self.max_queue, C.byref(self._h)))
         self._out = (StreamResult * self.n_streams)()
+        # run(): one api.VoxelMap per sequence (voxel edge map_voxel, cloud mode map_dense = DO_GENERATE_DENSE_PCL), fed by the
+        # step's batched integration of the keyframes its stream promotes
+        self.map_voxel = map_voxel
+        self.map_dense = bool(map_dense)
+        self.map_max_voxels = int(map_max_voxels)
+        self._maps = [None] * self.n_streams
+
+    def attach_map(self, stream, voxelMap):
+        """Every keyframe `stream` promotes from now on is integrated into voxelMap (None detaches); reset() detaches."""
+        check(_lib.lib().revo_vo_multi_attach_map(self._h, int(stream), voxelMap._h if voxelMap is not None else None))
+        self._maps[int(stream)] = voxelMap
 
     def __del__(self):
         try:
@@ -281,6 +302,7 @@ class MultiREVO:
 
     def reset(self, stream):
         check(_lib.lib().revo_vo_multi_reset(self._h, int(stream)))
+        self._maps[int(stream)] = None
 
     def nKeyFrames(self, stream):
         return _lib.lib().revo_vo_multi_num_keyframes(self._h, int(stream))
@@ -314,6 +336,10 @@ class MultiREVO:
                     self.reset(s)
                 if seq_of[s] is None and nxt < len(seqs):
                     seq_of[s], it_of[s], done_of[s] = nxt, iter(seqs[nxt]), False
+                    if self.map_voxel is not None:
+                        out[nxt].map = api.VoxelMap(self.camPyr, self.map_voxel, dense=self.map_dense,
+                                                    max_voxels=self.map_max_voxels)
+                        self.attach_map(s, out[nxt].map)
                     nxt += 1
 
         def feed():  # one submit: the next frame of every stream with room in its queue
