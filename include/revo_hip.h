@@ -32,6 +32,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* librevo_hip.so is built with hidden visibility: what this header declares is all it exports */
+#pragma GCC visibility push(default)
 
 #define REVO_MAX_LEVELS 6 /* optimizer.h:37 PYRAMID_LEVELS */
 
@@ -652,6 +654,24 @@ int revo_png_decode_submit(revo_png_decoder* d, int n, const revo_png_job* jobs,
  * (size mismatch). */
 int revo_png_decode_wait(revo_png_decoder* d, uint64_t ticket, int32_t* status);
 
+/* ---------------------------------------------------------------------------
+ * Diagnostics for bench.py and profiles/, not a stable interface: names, arguments and meaning may change in any release.
+ * ------------------------------------------------------------------------- */
+/* out3 = {workgroups of the tracker grids that have started, resident gates that gave up waiting, workgroups enqueued}
+ * on `device`; after hipDeviceSynchronize the first equals the third in a healthy process.  -1: no tracker launch yet. */
+int revo_debug_census_(int device, unsigned out3[3]);
+/* how many resident gates of `device` gave up waiting so far (0 in a healthy process); -1: no tracker launch yet */
+int revo_debug_gate_timeouts_(int device);
+/* the longest time (ns) each of 12 sections of a frame submission has taken so far; reset != 0 clears them after reading */
+void revo_debug_section_max_(unsigned long long out[12], int reset);
+/* out = {waits for a device result, waits that fell back to a blocking synchronise, longest wait in ns} */
+void revo_debug_wait_stats_(unsigned long long out[3]);
+/* builds with -DREVO_TRACK_PROFILE: the phase cycle counters of the context's last single-pair tracker launch */
+int revo_debug_track_profile_(revo_ctx* ctx, float out13[13]);
+/* builds with -DREVO_TRACK_PROFILE: 64 floats of cycle counters per pair of the last batch tracker launch */
+int revo_debug_batch_profile_(float* out, int n_pairs);
+
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -21,19 +21,9 @@
 #include <mutex>
 #include <string>
 
-#include "../../include/revo_hip.h"
-
-extern "C" void revo_ctx_retain_(revo_ctx*);
-extern "C" void revo_ctx_release_(revo_ctx*);
-extern "C" int revo_ctx_device_(const revo_ctx*);
-extern "C" void revo_set_error_(const char* msg);
+#include "revo_internal.h"
 
 namespace {
-
-int fail(int code, const std::string& msg) {
-  revo_set_error_(msg.c_str());
-  return code;
-}
 
 // the slice of rccl.h this file needs (rccl.h:40-43,187,220,260,339,678): opaque communicator, by-value 128-byte id
 typedef struct ncclComm* ncclComm_t;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "revo_dev.h"
+#include "revo_internal.h"
 #include "revo_mat4.h"
 #include "revo_multi.h"
 #include "revo_map.h"
@@ -24,19 +25,7 @@
 static thread_local std::string g_err;
 extern "C" const char* revo_last_error(void) { return g_err.c_str(); }
 extern "C" const char* revo_version(void) { return "0.1.0 gfx950"; }
-
-static int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-// used by the other translation units of the library (revo_pipeline.hip): one error string per thread
-extern "C" void revo_set_error_(const char* msg) { g_err = msg ? msg : ""; }
-#define HIPCHECK(expr)                                                                      \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess)                                                                  \
-      return fail(REVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
+extern "C" void revo_set_error_(const char* msg) { g_err = msg ? msg : ""; }  // fail() of revo_internal.h: one string per thread
 
 // ---------------------------------------------------------------- defaults --
 extern "C" void revo_pyr_settings_default(revo_pyr_settings* s) {  // config/dataset_tum1.yaml
@@ -205,14 +194,6 @@ struct revo_batch {
   const revo_pair_result* last_results = nullptr;  // device records of the last track launch (revo_batch_sync decodes their flags)
   revo_pair_result* h_flags = nullptr;             // pinned scratch for that
 };
-
-// experiment knobs (environment): clamped integers, defaults are what ships
-static int env_int(const char* name, int dflt, int lo, int hi) {
-  const char* e = getenv(name);
-  if (!e || !*e) return dflt;
-  const int v = atoi(e);
-  return v < lo ? lo : (v > hi ? hi : v);
-}
 
 // ---------------------------------------------------------------- geometry --
 static int build_geom(const revo_pyr_settings& s, PyrGeom* g, std::string* why) {

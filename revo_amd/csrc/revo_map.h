@@ -1,6 +1,6 @@
 // revo_map.h -- what the voxel map (revo_map.hip) needs from the rest of the library.  Internal: not part of the C ABI.
 #pragma once
-#include "../../include/revo_hip.h"
+#include "revo_internal.h"
 
 struct MapSource {  // one keyframe as the map integration reads it: level 0 of its pyramid + its full-resolution colour
   revo_ctx* ctx;

@@ -23,12 +23,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/revo_hip.h"
+#include "revo_internal.h"
 #include "revo_map.h"
-
-extern "C" void revo_ctx_retain_(revo_ctx*);
-extern "C" void revo_ctx_release_(revo_ctx*);
-extern "C" void revo_set_error_(const char* msg);
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -232,15 +228,6 @@ __global__ void __launch_bounds__(256) k_map_extract(const u64* __restrict__ key
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side --
-namespace {
-int bad(int code, const std::string& msg) { revo_set_error_(msg.c_str()); return code; }
-#define MCHECK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e__ = (expr);                                                                      \
-    if (e__ != hipSuccess) return bad(REVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-}  // namespace
-
 // pinned staging of a launch's descriptors (reused once the previous upload out of it has completed)
 struct revo_map_stage {
   MapDesc* h_desc = nullptr; MapDesc* d_desc = nullptr; int cap_desc = 0;
@@ -269,7 +256,7 @@ extern "C" int revo_map_stage_create_(revo_map_stage** out) {
   if (hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
     delete st;
-    return bad(REVO_ERR_HIP, "hipEventCreate failed");
+    return fail(REVO_ERR_HIP, "hipEventCreate failed");
   }
   *out = st;
   return REVO_OK;
@@ -283,19 +270,19 @@ extern "C" void revo_map_stage_destroy_(revo_map_stage* st) {
   delete st;
 }
 static int stage_reserve(revo_map_stage* st, int nd, int nc) {
-  if (st->recorded) MCHECK(hipEventSynchronize(st->ev));  // the previous upload has read the pinned rows
+  if (st->recorded) HIPCHECK(hipEventSynchronize(st->ev));  // the previous upload has read the pinned rows
   if (nd > st->cap_desc) {
     (void)hipHostFree(st->h_desc); (void)hipFree(st->d_desc);
     st->h_desc = nullptr; st->d_desc = nullptr; st->cap_desc = 0;
-    MCHECK(hipHostMalloc((void**)&st->h_desc, sizeof(MapDesc) * nd));
-    MCHECK(hipMalloc((void**)&st->d_desc, sizeof(MapDesc) * nd));
+    HIPCHECK(hipHostMalloc((void**)&st->h_desc, sizeof(MapDesc) * nd));
+    HIPCHECK(hipMalloc((void**)&st->d_desc, sizeof(MapDesc) * nd));
     st->cap_desc = nd;
   }
   if (nc > st->cap_com) {
     (void)hipHostFree(st->h_com); (void)hipFree(st->d_com);
     st->h_com = nullptr; st->d_com = nullptr; st->cap_com = 0;
-    MCHECK(hipHostMalloc((void**)&st->h_com, sizeof(MapCommit) * nc));
-    MCHECK(hipMalloc((void**)&st->d_com, sizeof(MapCommit) * nc));
+    HIPCHECK(hipHostMalloc((void**)&st->h_com, sizeof(MapCommit) * nc));
+    HIPCHECK(hipMalloc((void**)&st->d_com, sizeof(MapCommit) * nc));
     st->cap_com = nc;
   }
   return REVO_OK;
@@ -316,19 +303,19 @@ static size_t occ_bound(revo_map* m) {
 static int grow(revo_map* m, size_t newcap) {
   hipStream_t s = (hipStream_t)m->g.stream;
   u64* nk = nullptr; MapVal* nv = nullptr;
-  MCHECK(hipMalloc((void**)&nk, sizeof(u64) * newcap));
+  HIPCHECK(hipMalloc((void**)&nk, sizeof(u64) * newcap));
   if (hipMalloc((void**)&nv, sizeof(MapVal) * newcap) != hipSuccess) {
     (void)hipGetLastError(); hipFree(nk);
-    return bad(REVO_ERR_HIP, "voxel map: no device memory for a table of " + std::to_string(newcap) + " slots");
+    return fail(REVO_ERR_HIP, "voxel map: no device memory for a table of " + std::to_string(newcap) + " slots");
   }
-  MCHECK(hipMemsetAsync(nk, 0xff, sizeof(u64) * newcap, s));
-  MCHECK(hipMemsetAsync(nv, 0, sizeof(MapVal) * newcap, s));
+  HIPCHECK(hipMemsetAsync(nk, 0xff, sizeof(u64) * newcap, s));
+  HIPCHECK(hipMemsetAsync(nv, 0, sizeof(MapVal) * newcap, s));
   if (m->cap) {
     hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals,
                        (unsigned)m->cap, nk, nv, (unsigned)(newcap - 1), &m->d_st->fault);
-    MCHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     ++m->rehashes;
-    MCHECK(hipStreamSynchronize(s));  // the old table is free once the rehash has read it
+    HIPCHECK(hipStreamSynchronize(s));  // the old table is free once the rehash has read it
   }
   hipFree(m->d_keys); hipFree(m->d_vals);
   m->d_keys = nk; m->d_vals = nv; m->cap = newcap;
@@ -340,7 +327,7 @@ static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, cons
   if (n <= 0) return REVO_OK;
   const MapCtxGeom& g = maps[0]->g;
   hipStream_t s = (hipStream_t)g.stream;
-  MCHECK(hipSetDevice(g.device));
+  HIPCHECK(hipSetDevice(g.device));
   const size_t npix = (size_t)g.w * g.h;
   std::vector<revo_map*> dm;  // distinct maps, first appearance first
   std::vector<int> nk;
@@ -356,7 +343,7 @@ static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, cons
     chk[j] = ub + bound > m->max_voxels;
     // the checked path inserts every new key before it decides: room for what the map may hold + all points of the batch
     const size_t need = 2 * (std::min(ub, m->max_voxels) + bound);
-    if (need > MAP_MAX_CAP) return bad(REVO_ERR_CAPACITY, "voxel map: a batch this large needs more than 2^31 table slots");
+    if (need > MAP_MAX_CAP) return fail(REVO_ERR_CAPACITY, "voxel map: a batch this large needs more than 2^31 table slots");
     if (m->cap < need) {
       size_t c = std::max<size_t>(m->cap * 2, 1024);
       while (c < need) c *= 2;
@@ -387,9 +374,9 @@ static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, cons
     any_check = any_check || chk[j];
     if (chk[j] && checked) checked->push_back(m);
   }
-  MCHECK(hipMemcpyAsync(st->d_desc, st->h_desc, sizeof(MapDesc) * n, hipMemcpyHostToDevice, s));
-  MCHECK(hipMemcpyAsync(st->d_com, st->h_com, sizeof(MapCommit) * dm.size(), hipMemcpyHostToDevice, s));
-  MCHECK(hipEventRecord(st->ev, s));
+  HIPCHECK(hipMemcpyAsync(st->d_desc, st->h_desc, sizeof(MapDesc) * n, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(st->d_com, st->h_com, sizeof(MapCommit) * dm.size(), hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(st->ev, s));
   st->recorded = true;
   const int nb = (int)((npix + 255) / 256);
   const MapGeomK gk{g.w, (int)npix, g.fx, g.fy, g.cx, g.cy, g.dmin, g.dmax};
@@ -406,7 +393,7 @@ static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, cons
                            (unsigned)dm[j]->cap, dm[j]->d_st);
     hipLaunchKernelGGL(k_map_walk<MAP_ACCUM>, grid, blk, 0, s, st->d_desc, nb, gk);
   }
-  MCHECK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
   return REVO_OK;
 }
 
@@ -416,27 +403,27 @@ static bool pose_finite(const float* T) {
 }
 
 extern "C" int revo_map_create(revo_ctx* ctx, float voxel, int dense, size_t initial_voxels, size_t max_voxels, revo_map** out) {
-  if (!ctx || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
-  if (!std::isfinite(voxel) || !(voxel > 0.0f)) return bad(REVO_ERR_INVALID_ARG, "voxel must be finite and > 0");
-  if (dense != 0 && dense != 1) return bad(REVO_ERR_INVALID_ARG, "dense must be 0 or 1");
-  if (max_voxels < 1 || max_voxels > MAP_MAX_VOXELS) return bad(REVO_ERR_INVALID_ARG, "max_voxels must be 1 .. 2^28");
+  if (!ctx || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (!std::isfinite(voxel) || !(voxel > 0.0f)) return fail(REVO_ERR_INVALID_ARG, "voxel must be finite and > 0");
+  if (dense != 0 && dense != 1) return fail(REVO_ERR_INVALID_ARG, "dense must be 0 or 1");
+  if (max_voxels < 1 || max_voxels > MAP_MAX_VOXELS) return fail(REVO_ERR_INVALID_ARG, "max_voxels must be 1 .. 2^28");
   MapCtxGeom g;
   { const int rc = revo_map_ctx_geom_(ctx, &g); if (rc) return rc; }
-  MCHECK(hipSetDevice(g.device));
+  HIPCHECK(hipSetDevice(g.device));
   revo_map* m = new revo_map();
   m->ctx = ctx; m->g = g; m->voxel = voxel; m->dense = dense; m->max_voxels = max_voxels;
   revo_ctx_retain_(ctx);
   struct Guard { revo_map* m; ~Guard() { if (m) revo_map_destroy(m); } } guard{m};
-  MCHECK(hipMalloc((void**)&m->d_st, sizeof(MapStats)));
-  MCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), (hipStream_t)g.stream));
-  MCHECK(hipHostMalloc((void**)&m->h_pub, sizeof(u64) * 4));
+  HIPCHECK(hipMalloc((void**)&m->d_st, sizeof(MapStats)));
+  HIPCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), (hipStream_t)g.stream));
+  HIPCHECK(hipHostMalloc((void**)&m->h_pub, sizeof(u64) * 4));
   memset(m->h_pub, 0, sizeof(u64) * 4);
   { const int rc = revo_map_stage_create_(&m->stage); if (rc) return rc; }
   size_t c = 1024;
   const size_t want = std::min<size_t>(std::max<size_t>(initial_voxels, 1), max_voxels) * 2;
   while (c < want) c *= 2;
   { const int rc = grow(m, c); if (rc) return rc; }
-  MCHECK(hipStreamSynchronize((hipStream_t)g.stream));
+  HIPCHECK(hipStreamSynchronize((hipStream_t)g.stream));
   guard.m = nullptr;
   *out = m;
   return REVO_OK;
@@ -456,28 +443,28 @@ extern "C" void revo_map_destroy(revo_map* m) {
 }
 
 extern "C" int revo_map_integrate_many(revo_map* m, int n, const revo_pyr* const* kfs, const float* T) {
-  if (!m || n < 0 || (n > 0 && (!kfs || !T))) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m || n < 0 || (n > 0 && (!kfs || !T))) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n == 0) return REVO_OK;
   for (int i = 0; i < n; ++i) {
-    if (!kfs[i]) return bad(REVO_ERR_INVALID_ARG, "null pyramid");
-    if (!pose_finite(T + 16 * (size_t)i)) return bad(REVO_ERR_INVALID_ARG, "T_w_kf is not finite");
+    if (!kfs[i]) return fail(REVO_ERR_INVALID_ARG, "null pyramid");
+    if (!pose_finite(T + 16 * (size_t)i)) return fail(REVO_ERR_INVALID_ARG, "T_w_kf is not finite");
   }
   std::vector<MapSource> src(n);
   for (int i = 0; i < n; ++i) {
     const int rc = revo_map_source_(const_cast<revo_pyr*>(kfs[i]), &src[i]);
     if (rc) return rc;
-    if (src[i].ctx != m->ctx) return bad(REVO_ERR_INVALID_ARG, "the pyramid belongs to another context than the map");
+    if (src[i].ctx != m->ctx) return fail(REVO_ERR_INVALID_ARG, "the pyramid belongs to another context than the map");
   }
   std::vector<revo_map*> maps(n, m), checked;
   { const int rc = integrate_core(m->stage, n, maps.data(), src.data(), T, &checked); if (rc) return rc; }
   if (!checked.empty()) {  // the map could have reached max_voxels: the device has decided, wait for it
-    MCHECK(hipStreamSynchronize((hipStream_t)m->g.stream));
-    if (!m->h_pub[2]) return bad(REVO_ERR_CAPACITY, "voxel map: the keyframes would take it past max_voxels (not integrated)");
+    HIPCHECK(hipStreamSynchronize((hipStream_t)m->g.stream));
+    if (!m->h_pub[2]) return fail(REVO_ERR_CAPACITY, "voxel map: the keyframes would take it past max_voxels (not integrated)");
   }
   return REVO_OK;
 }
 extern "C" int revo_map_integrate(revo_map* m, const revo_pyr* kf, const float T[16]) {
-  if (!m || !kf || !T) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m || !kf || !T) return fail(REVO_ERR_INVALID_ARG, "null argument");
   return revo_map_integrate_many(m, 1, &kf, T);
 }
 
@@ -492,13 +479,13 @@ extern "C" int revo_map_integrate_views_(revo_map_stage* st, int n, revo_map* co
 }
 
 extern "C" int revo_map_clear(revo_map* m) {
-  if (!m) return bad(REVO_ERR_INVALID_ARG, "null map");
-  MCHECK(hipSetDevice(m->g.device));
+  if (!m) return fail(REVO_ERR_INVALID_ARG, "null map");
+  HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MCHECK(hipMemsetAsync(m->d_keys, 0xff, sizeof(u64) * m->cap, s));
-  MCHECK(hipMemsetAsync(m->d_vals, 0, sizeof(MapVal) * m->cap, s));
-  MCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), s));
-  MCHECK(hipStreamSynchronize(s));
+  HIPCHECK(hipMemsetAsync(m->d_keys, 0xff, sizeof(u64) * m->cap, s));
+  HIPCHECK(hipMemsetAsync(m->d_vals, 0, sizeof(MapVal) * m->cap, s));
+  HIPCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), s));
+  HIPCHECK(hipStreamSynchronize(s));
   m->pending.clear();
   m->h_pub[0] = 0; m->h_pub[2] = 1; m->h_pub[1] = m->seq;
   m->rehashes = 0;
@@ -506,16 +493,16 @@ extern "C" int revo_map_clear(revo_map* m) {
 }
 
 static int read_stats(revo_map* m, MapStats* out) {
-  MCHECK(hipSetDevice(m->g.device));
+  HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MCHECK(hipStreamSynchronize(s));
-  MCHECK(hipMemcpy(out, m->d_st, sizeof(MapStats), hipMemcpyDeviceToHost));
-  if (out->fault) return bad(REVO_ERR_HIP, "voxel map: a probe ran through the whole table (load invariant broken)");
+  HIPCHECK(hipStreamSynchronize(s));
+  HIPCHECK(hipMemcpy(out, m->d_st, sizeof(MapStats), hipMemcpyDeviceToHost));
+  if (out->fault) return fail(REVO_ERR_HIP, "voxel map: a probe ran through the whole table (load invariant broken)");
   return REVO_OK;
 }
 
 extern "C" int revo_map_info(revo_map* m, revo_map_info_t* out) {
-  if (!m || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   MapStats st;
   { const int rc = read_stats(m, &st); if (rc) return rc; }
   out->voxels = (size_t)st.occ;
@@ -529,35 +516,35 @@ extern "C" int revo_map_info(revo_map* m, revo_map_info_t* out) {
 }
 
 extern "C" int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8_t* rgb, uint32_t* count, size_t cap, size_t* n) {
-  if (!m || !n) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
   MapStats st;
   { const int rc = read_stats(m, &st); if (rc) return rc; }
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t nv = std::max<size_t>((size_t)st.occ, 1);
   char* buf = nullptr;
   const size_t o_key = 0, o_xyz = o_key + 8 * nv, o_rgb = o_xyz + 12 * nv, o_cnt = o_rgb + 4 * nv, o_tot = o_cnt + 4 * nv;
-  MCHECK(hipMalloc((void**)&buf, o_tot + 256));
+  HIPCHECK(hipMalloc((void**)&buf, o_tot + 256));
   struct Free { char* p; ~Free() { hipFree(p); } } fr{buf};
   unsigned* d_tot = (unsigned*)(buf + o_tot);
-  MCHECK(hipMemsetAsync(d_tot, 0, sizeof(unsigned), s));
+  HIPCHECK(hipMemsetAsync(d_tot, 0, sizeof(unsigned), s));
   hipLaunchKernelGGL(k_map_extract, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals, (unsigned)m->cap,
                      (u64)std::max<size_t>(min_count, 1), d_tot, (u64*)(buf + o_key), (float*)(buf + o_xyz),
                      (unsigned*)(buf + o_rgb), (unsigned*)(buf + o_cnt));
-  MCHECK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
   unsigned tot = 0;
-  MCHECK(hipMemcpyAsync(&tot, d_tot, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  MCHECK(hipStreamSynchronize(s));
+  HIPCHECK(hipMemcpyAsync(&tot, d_tot, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
   *n = tot;
   if (!xyz) return REVO_OK;
-  if (cap < tot) return bad(REVO_ERR_CAPACITY, "voxel map: the output holds fewer voxels than the map has");
+  if (cap < tot) return fail(REVO_ERR_CAPACITY, "voxel map: the output holds fewer voxels than the map has");
   std::vector<u64> key(tot);
   std::vector<float> p(3 * (size_t)tot);
   std::vector<unsigned> c(tot), k(tot);
   if (tot) {
-    MCHECK(hipMemcpy(key.data(), buf + o_key, 8 * (size_t)tot, hipMemcpyDeviceToHost));
-    MCHECK(hipMemcpy(p.data(), buf + o_xyz, 12 * (size_t)tot, hipMemcpyDeviceToHost));
-    MCHECK(hipMemcpy(c.data(), buf + o_rgb, 4 * (size_t)tot, hipMemcpyDeviceToHost));
-    MCHECK(hipMemcpy(k.data(), buf + o_cnt, 4 * (size_t)tot, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(key.data(), buf + o_key, 8 * (size_t)tot, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(p.data(), buf + o_xyz, 12 * (size_t)tot, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(c.data(), buf + o_rgb, 4 * (size_t)tot, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(k.data(), buf + o_cnt, 4 * (size_t)tot, hipMemcpyDeviceToHost));
   }
   std::vector<unsigned> idx(tot);
   std::iota(idx.begin(), idx.end(), 0u);

@@ -2,7 +2,7 @@
 // Internal: not part of the C ABI.  A "set" is one FrameSet of n_streams frames built by one submit; frames are addressed
 // as (set, frame index inside the set).
 #pragma once
-#include "../../include/revo_hip.h"
+#include "revo_internal.h"
 
 struct revo_mdev;
 struct MultiTrack { int stream; void* set; int frame; float R[9], T[3]; int status; };  // R/T in: init, out: result

@@ -26,33 +26,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/revo_hip.h"
-
-extern "C" void revo_ctx_retain_(revo_ctx*);
-extern "C" void revo_ctx_release_(revo_ctx*);
-extern "C" int revo_ctx_device_(const revo_ctx*);
-extern "C" void revo_set_error_(const char* msg);
-extern "C" void revo_batch_time_next_grid_(revo_batch*, void* ev0, void* ev1);
+#include "revo_internal.h"
 
 namespace {
-
-int fail(int code, const std::string& msg) {
-  revo_set_error_(msg.c_str());
-  return code;
-}
-#define PCHECK(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e__ = (expr);                                                                \
-    if (e__ != hipSuccess)                                                                  \
-      return fail(REVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
-int env_int(const char* name, int dflt, int lo, int hi) {
-  const char* e = getenv(name);
-  if (!e || !*e) return dflt;
-  const int v = atoi(e);
-  return v < lo ? lo : (v > hi ? hi : v);
-}
 
 // out[0] = start, out[1] = end of this one-lane kernel on the device's constant-rate clock; spin_ticks > 0: stay that long
 __global__ void __launch_bounds__(64) k_pipe_probe(unsigned long long* __restrict__ out, unsigned long long spin_ticks) {
@@ -119,11 +95,11 @@ namespace {
 int streams_alias(hipStream_t a, hipStream_t b, unsigned long long* d_buf, unsigned long long spin_ticks, bool* alias) {
   hipLaunchKernelGGL(k_pipe_probe, dim3(1), dim3(64), 0, a, d_buf, spin_ticks);
   hipLaunchKernelGGL(k_pipe_probe, dim3(1), dim3(64), 0, b, d_buf + 2, 0ull);
-  PCHECK(hipGetLastError());
-  PCHECK(hipStreamSynchronize(a));
-  PCHECK(hipStreamSynchronize(b));
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(a));
+  HIPCHECK(hipStreamSynchronize(b));
   unsigned long long h[4];
-  PCHECK(hipMemcpy(h, d_buf, sizeof(h), hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(h, d_buf, sizeof(h), hipMemcpyDeviceToHost));
   *alias = h[2] >= h[1];  // the stamp on b was taken after the probe on a had ended
   return REVO_OK;
 }
@@ -137,7 +113,7 @@ int pick_streams(revo_pipeline* p, int want, std::vector<hipStream_t>* out) {
   struct BufGuard { unsigned long long** p; ~BufGuard() { if (*p) (void)hipFree(*p); } } buf_guard{&d_buf};
   int rate_khz = 0;
   if (probe) {
-    PCHECK(hipMalloc((void**)&d_buf, 4 * sizeof(unsigned long long)));
+    HIPCHECK(hipMalloc((void**)&d_buf, 4 * sizeof(unsigned long long)));
     if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, p->device) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
   }
   const unsigned long long spin = (unsigned long long)rate_khz * 150ull / 1000ull;  // 150 us
@@ -147,13 +123,13 @@ int pick_streams(revo_pipeline* p, int want, std::vector<hipStream_t>* out) {
   while ((int)kept.size() < want && tries < want + 8) {
     ++tries;
     hipStream_t s = nullptr;
-    PCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     p->owned.push_back(s);
     bool bad = false;
     if (probe) {
       // first use of a stream binds it to its hardware queue: touch it before probing
       hipLaunchKernelGGL(k_pipe_probe, dim3(1), dim3(64), 0, s, d_buf, 0ull);
-      PCHECK(hipStreamSynchronize(s));
+      HIPCHECK(hipStreamSynchronize(s));
       for (hipStream_t k : kept) {
         bool a1 = false, a2 = false;
         int rc = streams_alias(k, s, d_buf, spin, &a1);
@@ -185,7 +161,7 @@ int pick_streams(revo_pipeline* p, int want, std::vector<hipStream_t>* out) {
 // waits for the step), so that it also covers what the caller enqueued behind the grid.
 int finalize_slot(revo_pipeline* p, Slot& sl) {
   if (sl.ticket && !sl.done_recorded) {
-    PCHECK(hipEventRecord(sl.ev_done, p->s_trk[sl.trk]));
+    HIPCHECK(hipEventRecord(sl.ev_done, p->s_trk[sl.trk]));
     sl.done_recorded = true;
   }
   return REVO_OK;
@@ -193,9 +169,9 @@ int finalize_slot(revo_pipeline* p, Slot& sl) {
 
 int harvest_timing(revo_pipeline* p, Slot& sl) {
   if (!sl.timed) return REVO_OK;
-  PCHECK(hipEventSynchronize(sl.t1));
+  HIPCHECK(hipEventSynchronize(sl.t1));
   float ms = 0.f;
-  PCHECK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
+  HIPCHECK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
   p->timed_ms += ms;
   p->timed_n += 1;
   sl.timed = false;
@@ -209,14 +185,14 @@ extern "C" int revo_pipeline_create(revo_ctx* ctx, int n_pairs, int depth, int h
   if (depth == 0) depth = 4;  // build(t+3) | edge lists + EDT(t+2) | tracker grids t+1 and t  (profiles/r04_ab_around_default.txt)
   if (depth < 1 || depth > 8) return fail(REVO_ERR_INVALID_ARG, "pipeline depth must be 1..8 (0 = default 4)");
   const int device = revo_ctx_device_(ctx);
-  PCHECK(hipSetDevice(device));
+  HIPCHECK(hipSetDevice(device));
   revo_pipeline* p = new revo_pipeline();
   p->ctx = ctx; p->device = device; p->n_pairs = n_pairs; p->nb = depth; p->host_results = host_results ? 1 : 0;
   revo_ctx_retain_(ctx);
   struct Guard { revo_pipeline* p; ~Guard() { if (p) revo_pipeline_destroy(p); } } guard{p};
   // the tracker streams first (the order the measured shape was created in), then build, then auxiliary
   if (depth == 1) {
-    PCHECK(hipStreamCreateWithFlags(&p->s_trk[0], hipStreamNonBlocking));
+    HIPCHECK(hipStreamCreateWithFlags(&p->s_trk[0], hipStreamNonBlocking));
     p->owned.push_back(p->s_trk[0]);
     p->s_trk[1] = p->s_build = p->s_aux = p->s_trk[0];
     p->ntrk = 1; p->distinct_queues = 1;
@@ -236,14 +212,14 @@ extern "C" int revo_pipeline_create(revo_ctx* ctx, int n_pairs, int depth, int h
   for (Slot& sl : p->slots) {
     int rc = revo_batch_create(ctx, n_pairs, &sl.batch);
     if (rc) return rc;
-    PCHECK(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
-    PCHECK(hipEventCreate(&sl.t0));
-    PCHECK(hipEventCreate(&sl.t1));
-    PCHECK(hipMalloc((void**)&sl.d_res, sizeof(revo_pair_result) * n_pairs));
-    PCHECK(hipMemset(sl.d_res, 0, sizeof(revo_pair_result) * n_pairs));
-    if (p->host_results) PCHECK(hipHostMalloc((void**)&sl.h_res, sizeof(revo_pair_result) * n_pairs));
+    HIPCHECK(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
+    HIPCHECK(hipEventCreate(&sl.t0));
+    HIPCHECK(hipEventCreate(&sl.t1));
+    HIPCHECK(hipMalloc((void**)&sl.d_res, sizeof(revo_pair_result) * n_pairs));
+    HIPCHECK(hipMemset(sl.d_res, 0, sizeof(revo_pair_result) * n_pairs));
+    if (p->host_results) HIPCHECK(hipHostMalloc((void**)&sl.h_res, sizeof(revo_pair_result) * n_pairs));
   }
-  PCHECK(hipStreamSynchronize(nullptr));  // the zeroing above (NULL stream; the pipeline's streams are non-blocking)
+  HIPCHECK(hipStreamSynchronize(nullptr));  // the zeroing above (NULL stream; the pipeline's streams are non-blocking)
   guard.p = nullptr;
   *out = p;
   return REVO_OK;
@@ -283,7 +259,7 @@ extern "C" int revo_pipeline_submit(revo_pipeline* p, const uint8_t* d_bgr, cons
   if (!d_results && !p->host_results && !p->comm)
     return fail(REVO_ERR_INVALID_ARG, "d_results is NULL and the pipeline neither copies records to the host (host_results) nor gathers them "
                                       "(revo_pipeline_set_comm): the step's records would be unreachable");
-  PCHECK(hipSetDevice(p->device));
+  HIPCHECK(hipSetDevice(p->device));
   const unsigned long long t = p->submitted;
   Slot& sl = p->slots[t % p->nb];
   const int trk = (int)(t % p->ntrk);
@@ -295,7 +271,7 @@ extern "C" int revo_pipeline_submit(revo_pipeline* p, const uint8_t* d_bgr, cons
   for (Slot& o : p->slots)
     if (o.ticket && !o.done_recorded && o.trk == trk) { int rc = finalize_slot(p, o); if (rc) return rc; }
   { int rc = harvest_timing(p, sl); if (rc) return rc; }
-  if (input_ready_event) PCHECK(hipStreamWaitEvent(p->s_build, (hipEvent_t)input_ready_event, 0));
+  if (input_ready_event) HIPCHECK(hipStreamWaitEvent(p->s_build, (hipEvent_t)input_ready_event, 0));
   // (the batch's build orders itself behind the batch's previous tracker grid and deferred work: revo_host.hip)
   int rc;
   if (depth_kind == 2) {
@@ -315,7 +291,7 @@ extern "C" int revo_pipeline_submit(revo_pipeline* p, const uint8_t* d_bgr, cons
   if (p->comm) {
     d_out = p->d_send + ((size_t)ws * p->every + wj) * p->n_pairs;
     // the collective that read this send window `ring` windows ago may still be in flight on the other tracker stream
-    if (p->coll_pending[ws]) PCHECK(hipStreamWaitEvent(s_tr, p->ev_coll[ws], 0));
+    if (p->coll_pending[ws]) HIPCHECK(hipStreamWaitEvent(s_tr, p->ev_coll[ws], 0));
   }
   const bool time_it = p->time_every > 0 && ((t + 1) % (unsigned long long)p->time_every) == 0;
   // the event pair is recorded inside the tracker chain, directly around the grid: behind the waits for older grids, the
@@ -325,27 +301,27 @@ extern "C" int revo_pipeline_submit(revo_pipeline* p, const uint8_t* d_bgr, cons
   if (rc) { if (time_it) revo_batch_time_next_grid_(sl.batch, nullptr, nullptr); return rc; }
   if (time_it) sl.timed = true;
   if (p->comm) {
-    if (d_results) PCHECK(hipMemcpyAsync(d_results, d_out, sizeof(revo_pair_result) * p->n_pairs, hipMemcpyDeviceToDevice, s_tr));
+    if (d_results) HIPCHECK(hipMemcpyAsync(d_results, d_out, sizeof(revo_pair_result) * p->n_pairs, hipMemcpyDeviceToDevice, s_tr));
     if (wj == 0) p->coll_pending[ws] = 0;  // a new window starts in this slot
     if (wj + 1 < p->every) {
-      PCHECK(hipEventRecord(p->ev_step[(size_t)ws * p->every + wj], s_tr));
+      HIPCHECK(hipEventRecord(p->ev_step[(size_t)ws * p->every + wj], s_tr));
     } else {
       // the window is complete with this grid: its earlier steps ran on the other tracker stream (alternating), order them
       // in front, then ONE all-gather of the window's records in this step's after-grid slot
       if (p->ntrk > 1)
         for (int j = 0; j < wj; ++j)
           if ((int)((t - (unsigned long long)(wj - j)) % (unsigned long long)p->ntrk) != trk)
-            PCHECK(hipStreamWaitEvent(s_tr, p->ev_step[(size_t)ws * p->every + j], 0));
+            HIPCHECK(hipStreamWaitEvent(s_tr, p->ev_step[(size_t)ws * p->every + j], 0));
       rc = revo_comm_allgather_records(p->comm, p->d_send + (size_t)ws * p->every * p->n_pairs,
                                        p->d_gathered + (size_t)ws * p->world * p->every * p->n_pairs, p->every * p->n_pairs, (void*)s_tr);
       if (rc) return rc;
-      PCHECK(hipEventRecord(p->ev_coll[ws], s_tr));
+      HIPCHECK(hipEventRecord(p->ev_coll[ws], s_tr));
       p->coll_pending[ws] = 1;
       p->collectives += 1;
     }
   }
   if (p->host_results)
-    PCHECK(hipMemcpyAsync(sl.h_res, d_out, sizeof(revo_pair_result) * p->n_pairs, hipMemcpyDeviceToHost, s_tr));
+    HIPCHECK(hipMemcpyAsync(sl.h_res, d_out, sizeof(revo_pair_result) * p->n_pairs, hipMemcpyDeviceToHost, s_tr));
   p->submitted = t + 1;
   sl.ticket = t + 1;
   sl.trk = trk;
@@ -359,7 +335,7 @@ extern "C" int revo_pipeline_submit(revo_pipeline* p, const uint8_t* d_bgr, cons
 extern "C" int revo_pipeline_wait(revo_pipeline* p, uint64_t ticket, revo_pair_result* h_out) {
   if (!p || ticket == 0) return fail(REVO_ERR_INVALID_ARG, "bad argument");
   std::lock_guard<std::mutex> lk(p->mu);
-  PCHECK(hipSetDevice(p->device));
+  HIPCHECK(hipSetDevice(p->device));
   if (ticket > p->submitted) return fail(REVO_ERR_INVALID_ARG, "no such step");
   Slot& sl = p->slots[(ticket - 1) % p->nb];
   if (sl.ticket != ticket) {
@@ -368,11 +344,11 @@ extern "C" int revo_pipeline_wait(revo_pipeline* p, uint64_t ticket, revo_pair_r
     // the newer step that holds the slot is NOT finalized by this -- its after-grid slot stays open.
     if (h_out || p->host_results)
       return fail(REVO_ERR_INVALID_ARG, "step " + std::to_string(ticket) + ": its records have been overwritten by a later step");
-    PCHECK(hipStreamSynchronize(p->s_trk[(ticket - 1) % (unsigned long long)p->ntrk]));
+    HIPCHECK(hipStreamSynchronize(p->s_trk[(ticket - 1) % (unsigned long long)p->ntrk]));
     return REVO_OK;
   }
   { int rc = finalize_slot(p, sl); if (rc) return rc; }
-  PCHECK(hipEventSynchronize(sl.ev_done));
+  HIPCHECK(hipEventSynchronize(sl.ev_done));
   { int rc = harvest_timing(p, sl); if (rc) return rc; }
   sl.waited = true;
   if (p->host_results) {
@@ -391,10 +367,10 @@ extern "C" int revo_pipeline_wait(revo_pipeline* p, uint64_t ticket, revo_pair_r
 extern "C" int revo_pipeline_drain(revo_pipeline* p) {
   if (!p) return fail(REVO_ERR_INVALID_ARG, "null pipeline");
   std::lock_guard<std::mutex> lk(p->mu);
-  PCHECK(hipSetDevice(p->device));
+  HIPCHECK(hipSetDevice(p->device));
   for (Slot& sl : p->slots) { int rc = finalize_slot(p, sl); if (rc) return rc; }
   hipStream_t all[4] = {p->s_build, p->s_aux, p->s_trk[0], p->s_trk[1]};
-  for (int i = 0; i < 4; ++i) PCHECK(hipStreamSynchronize(all[i]));
+  for (int i = 0; i < 4; ++i) HIPCHECK(hipStreamSynchronize(all[i]));
   for (Slot& sl : p->slots) { int rc = harvest_timing(p, sl); if (rc) return rc; }
   return REVO_OK;
 }
@@ -443,12 +419,12 @@ extern "C" int revo_pipeline_tracker_ms(revo_pipeline* p, float* mean_ms, int* l
 extern "C" int revo_pipeline_set_comm(revo_pipeline* p, revo_comm* comm, int every, revo_pair_result* d_gathered, int ring) {
   if (!p) return fail(REVO_ERR_INVALID_ARG, "null pipeline");
   std::lock_guard<std::mutex> lk(p->mu);
-  PCHECK(hipSetDevice(p->device));
+  HIPCHECK(hipSetDevice(p->device));
   if (p->submitted % (unsigned long long)(p->every > 0 ? p->every : 1) != 0)
     return fail(REVO_ERR_INVALID_ARG, "a window of the current communicator is incomplete: revo_pipeline_flush_comm first");
   // detach / re-attach only with nothing in flight
   hipStream_t all[4] = {p->s_build, p->s_aux, p->s_trk[0], p->s_trk[1]};
-  for (int i = 0; i < 4; ++i) PCHECK(hipStreamSynchronize(all[i]));
+  for (int i = 0; i < 4; ++i) HIPCHECK(hipStreamSynchronize(all[i]));
   for (hipEvent_t e : p->ev_step) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : p->ev_coll) if (e) (void)hipEventDestroy(e);
   p->ev_step.clear(); p->ev_coll.clear(); p->coll_pending.clear();
@@ -461,14 +437,14 @@ extern "C" int revo_pipeline_set_comm(revo_pipeline* p, revo_comm* comm, int eve
     return fail(REVO_ERR_INVALID_ARG, "set_comm: attach at a multiple of `every` submitted steps");
   int world = 1, rank = 0;
   { int rc = revo_comm_world(comm, &world, &rank); if (rc) return rc; }
-  PCHECK(hipMalloc((void**)&p->d_send, sizeof(revo_pair_result) * (size_t)ring * every * p->n_pairs));
-  PCHECK(hipMemset(p->d_send, 0, sizeof(revo_pair_result) * (size_t)ring * every * p->n_pairs));
-  PCHECK(hipStreamSynchronize(nullptr));
+  HIPCHECK(hipMalloc((void**)&p->d_send, sizeof(revo_pair_result) * (size_t)ring * every * p->n_pairs));
+  HIPCHECK(hipMemset(p->d_send, 0, sizeof(revo_pair_result) * (size_t)ring * every * p->n_pairs));
+  HIPCHECK(hipStreamSynchronize(nullptr));
   p->ev_step.assign((size_t)ring * every, nullptr);
   p->ev_coll.assign((size_t)ring, nullptr);
   p->coll_pending.assign((size_t)ring, 0);
-  for (hipEvent_t& e : p->ev_step) PCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (hipEvent_t& e : p->ev_coll) PCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (hipEvent_t& e : p->ev_step) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (hipEvent_t& e : p->ev_coll) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   p->comm = comm; p->every = every; p->ring = ring; p->world = world; p->d_gathered = d_gathered;
   return REVO_OK;
 }
@@ -480,7 +456,7 @@ extern "C" int revo_pipeline_flush_comm(revo_pipeline* p, int* steps_out, int* s
   if (!p) return fail(REVO_ERR_INVALID_ARG, "null pipeline");
   std::lock_guard<std::mutex> lk(p->mu);
   if (!p->comm) return fail(REVO_ERR_INVALID_ARG, "no communicator attached");
-  PCHECK(hipSetDevice(p->device));
+  HIPCHECK(hipSetDevice(p->device));
   const int have = (int)(p->submitted % (unsigned long long)p->every);
   const unsigned long long win = p->submitted / (unsigned long long)p->every;
   const int ws = (int)(win % (unsigned long long)p->ring);
@@ -492,11 +468,11 @@ extern "C" int revo_pipeline_flush_comm(revo_pipeline* p, int* steps_out, int* s
   hipStream_t s_tr = p->s_trk[trk];
   for (int j = 0; j < have; ++j)
     if ((int)((win * p->every + j) % (unsigned long long)p->ntrk) != trk)
-      PCHECK(hipStreamWaitEvent(s_tr, p->ev_step[(size_t)ws * p->every + j], 0));
+      HIPCHECK(hipStreamWaitEvent(s_tr, p->ev_step[(size_t)ws * p->every + j], 0));
   int rc = revo_comm_allgather_records(p->comm, p->d_send + (size_t)ws * p->every * p->n_pairs,
                                        p->d_gathered + (size_t)ws * p->world * p->every * p->n_pairs, p->every * p->n_pairs, (void*)s_tr);
   if (rc) return rc;
-  PCHECK(hipEventRecord(p->ev_coll[ws], s_tr));
+  HIPCHECK(hipEventRecord(p->ev_coll[ws], s_tr));
   p->coll_pending[ws] = 1;
   p->collectives += 1;
   // the window is closed: the next submit starts a fresh one (the step counter moves to the next multiple of `every`)

@@ -15,25 +15,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/revo_hip.h"
+#include "revo_internal.h"
 #include "revo_inflate.h"
 
-extern "C" void revo_set_error_(const char* msg);
-extern "C" void revo_ctx_retain_(revo_ctx*);
-extern "C" void revo_ctx_release_(revo_ctx*);
-extern "C" int revo_ctx_device_(const revo_ctx*);
-
 namespace {
-
-int bad(int code, const std::string& msg) {
-  revo_set_error_(msg.c_str());
-  return code;
-}
-#define PCHECK(expr)                                                                                     \
-  do {                                                                                                   \
-    hipError_t e__ = (expr);                                                                             \
-    if (e__ != hipSuccess) return bad(REVO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------- host parse --
 uint32_t crc_table[256];
@@ -215,10 +200,10 @@ __global__ void __launch_bounds__(256) k_png_unfilter(const PngDesc* __restrict_
 
 // ------------------------------------------------------------------------------------------------------------------- C ABI --
 extern "C" int revo_png_probe(const uint8_t* png, size_t len, revo_png_info* out) {
-  if (!out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   std::string why;
   const int rc = parse(png, len, out, nullptr, &why);
-  if (rc) return bad(rc, why);
+  if (rc) return fail(rc, why);
   return REVO_OK;
 }
 
@@ -269,10 +254,10 @@ extern "C" void revo_png_decoder_destroy(revo_png_decoder* d) {
 
 extern "C" int revo_png_decoder_create(revo_ctx* ctx, int max_images, size_t max_compressed_bytes, size_t max_raw_bytes_per_image,
                                        revo_png_decoder** out) {
-  if (!out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (max_images < 1 || max_images > (1 << 20) || max_compressed_bytes < 1 || max_raw_bytes_per_image < 1)
-    return bad(REVO_ERR_INVALID_ARG, "max_images, max_compressed_bytes and max_raw_bytes_per_image must be positive");
+    return fail(REVO_ERR_INVALID_ARG, "max_images, max_compressed_bytes and max_raw_bytes_per_image must be positive");
   revo_png_decoder* d = new revo_png_decoder();
   struct Guard { revo_png_decoder* d; ~Guard() { if (d) revo_png_decoder_destroy(d); } } guard{d};
   if (ctx) {
@@ -280,22 +265,22 @@ extern "C" int revo_png_decoder_create(revo_ctx* ctx, int max_images, size_t max
     revo_ctx_retain_(ctx);
     d->device = revo_ctx_device_(ctx);
   } else {
-    PCHECK(hipGetDevice(&d->device));
+    HIPCHECK(hipGetDevice(&d->device));
   }
-  PCHECK(hipSetDevice(d->device));
+  HIPCHECK(hipSetDevice(d->device));
   d->max_images = max_images;
   d->max_comp = max_compressed_bytes;
   d->max_raw = align_up(max_raw_bytes_per_image, 256);
   d->slab_bytes = align_up(sizeof(PngDesc) * (size_t)max_images, 256) + max_compressed_bytes;
-  PCHECK(hipHostMalloc((void**)&d->h_slab, d->slab_bytes));
-  PCHECK(hipMalloc((void**)&d->d_slab, d->slab_bytes));
-  PCHECK(hipMalloc((void**)&d->d_raw, d->max_raw * (size_t)max_images));
-  PCHECK(hipEventCreateWithFlags(&d->ev_h2d, hipEventDisableTiming));
-  PCHECK(hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming));
+  HIPCHECK(hipHostMalloc((void**)&d->h_slab, d->slab_bytes));
+  HIPCHECK(hipMalloc((void**)&d->d_slab, d->slab_bytes));
+  HIPCHECK(hipMalloc((void**)&d->d_raw, d->max_raw * (size_t)max_images));
+  HIPCHECK(hipEventCreateWithFlags(&d->ev_h2d, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming));
   for (Slot& s : d->slot) {
-    PCHECK(hipHostMalloc((void**)&s.h_status, sizeof(int32_t) * max_images));
-    PCHECK(hipMalloc((void**)&s.d_status, sizeof(int32_t) * max_images));
-    PCHECK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    HIPCHECK(hipHostMalloc((void**)&s.h_status, sizeof(int32_t) * max_images));
+    HIPCHECK(hipMalloc((void**)&s.d_status, sizeof(int32_t) * max_images));
+    HIPCHECK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     s.host_status.assign(max_images, 0);
   }
   guard.d = nullptr;
@@ -304,24 +289,24 @@ extern "C" int revo_png_decoder_create(revo_ctx* ctx, int max_images, size_t max
 }
 
 extern "C" int revo_png_decode_submit(revo_png_decoder* d, int n, const revo_png_job* jobs, void* stream, uint64_t* ticket) {
-  if (!d || !ticket || n < 0 || (n > 0 && !jobs)) return bad(REVO_ERR_INVALID_ARG, "bad argument");
-  if (n > d->max_images) return bad(REVO_ERR_CAPACITY, "more images than the decoder was created for");
+  if (!d || !ticket || n < 0 || (n > 0 && !jobs)) return fail(REVO_ERR_INVALID_ARG, "bad argument");
+  if (n > d->max_images) return fail(REVO_ERR_CAPACITY, "more images than the decoder was created for");
   Slot* sl = nullptr;
   for (Slot& s : d->slot)
     if (!s.busy) { sl = &s; break; }
-  if (!sl) return bad(REVO_ERR_CAPACITY, "two decodes are outstanding: revo_png_decode_wait for one first");
+  if (!sl) return fail(REVO_ERR_CAPACITY, "two decodes are outstanding: revo_png_decode_wait for one first");
   for (int i = 0; i < n; ++i) {
     const revo_png_job& j = jobs[i];
-    if (j.format != REVO_PNG_BGR8 && j.format != REVO_PNG_U16) return bad(REVO_ERR_INVALID_ARG, "unknown output format");
-    if (!j.d_dst || j.width < 1 || j.height < 1) return bad(REVO_ERR_INVALID_ARG, "null destination or bad size");
+    if (j.format != REVO_PNG_BGR8 && j.format != REVO_PNG_U16) return fail(REVO_ERR_INVALID_ARG, "unknown output format");
+    if (!j.d_dst || j.width < 1 || j.height < 1) return fail(REVO_ERR_INVALID_ARG, "null destination or bad size");
     const size_t px = j.format == REVO_PNG_BGR8 ? 3 : 2;
     if (j.dst_stride < (size_t)j.width * px || (j.format == REVO_PNG_U16 && (((uintptr_t)j.d_dst | j.dst_stride) & 1)))
-      return bad(REVO_ERR_INVALID_ARG, "destination stride smaller than a row, or a u16 destination not 2-byte aligned");
+      return fail(REVO_ERR_INVALID_ARG, "destination stride smaller than a row, or a u16 destination not 2-byte aligned");
   }
-  PCHECK(hipSetDevice(d->device));
+  HIPCHECK(hipSetDevice(d->device));
   hipStream_t s = (hipStream_t)stream;
   // the previous batch's copy has read the page-locked slab
-  if (d->has_h2d) PCHECK(hipEventSynchronize(d->ev_h2d));
+  if (d->has_h2d) HIPCHECK(hipEventSynchronize(d->ev_h2d));
   // host side: parse every file, keep the ones the device decodes, pack their IDAT payloads
   const size_t desc_bytes = align_up(sizeof(PngDesc) * (size_t)n, 256);
   PngDesc* descs = (PngDesc*)d->h_slab;
@@ -341,11 +326,11 @@ extern "C" int revo_png_decode_submit(revo_png_decoder* d, int n, const revo_png
       const bool fits = j.format == REVO_PNG_BGR8 ? bd == 8 : ct == 0;
       const uint64_t rb = info.raw_bytes / (uint64_t)info.height - 1;
       if (!fits || rb > (uint64_t)MAX_ROW) st = REVO_ERR_UNSUPPORTED;
-      else if (info.raw_bytes > d->max_raw) return bad(REVO_ERR_CAPACITY, "an image is larger than max_raw_bytes_per_image");
+      else if (info.raw_bytes > d->max_raw) return fail(REVO_ERR_CAPACITY, "an image is larger than max_raw_bytes_per_image");
     }
     sl->host_status[i] = st;
     if (st != REVO_OK) continue;
-    if (info.idat_bytes > data_cap - used) return bad(REVO_ERR_CAPACITY, "the batch's image data exceed max_compressed_bytes");
+    if (info.idat_bytes > data_cap - used) return fail(REVO_ERR_CAPACITY, "the batch's image data exceed max_compressed_bytes");
     PngDesc& pd = descs[nl];
     pd.comp_off = desc_bytes + used;
     pd.comp_len = info.idat_bytes;
@@ -360,21 +345,21 @@ extern "C" int revo_png_decode_submit(revo_png_decoder* d, int n, const revo_png
     ++nl;
   }
   // the previous batch's kernels are done with the device slab, the scratch and (same slot) the status words
-  if (d->has_done) PCHECK(hipStreamWaitEvent(s, d->ev_done, 0));
+  if (d->has_done) HIPCHECK(hipStreamWaitEvent(s, d->ev_done, 0));
   if (nl > 0) {
-    PCHECK(hipMemcpyAsync(d->d_slab, d->h_slab, desc_bytes + used, hipMemcpyHostToDevice, s));
-    PCHECK(hipEventRecord(d->ev_h2d, s));
+    HIPCHECK(hipMemcpyAsync(d->d_slab, d->h_slab, desc_bytes + used, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipEventRecord(d->ev_h2d, s));
     d->has_h2d = true;
     const PngDesc* dd = (const PngDesc*)d->d_slab;
     hipLaunchKernelGGL(k_png_inflate, dim3(nl), dim3(64), 0, s, dd, d->d_slab, d->d_raw, sl->d_status);
-    PCHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     hipLaunchKernelGGL(k_png_unfilter, dim3(nl), dim3(256), 0, s, dd, d->d_raw, sl->d_status);
-    PCHECK(hipGetLastError());
-    PCHECK(hipMemcpyAsync(sl->h_status, sl->d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(sl->h_status, sl->d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
   }
-  PCHECK(hipEventRecord(d->ev_done, s));
+  HIPCHECK(hipEventRecord(d->ev_done, s));
   d->has_done = true;
-  PCHECK(hipEventRecord(sl->done, s));
+  HIPCHECK(hipEventRecord(sl->done, s));
   sl->busy = true;
   sl->n = n;
   sl->ticket = d->next_ticket++;
@@ -383,13 +368,13 @@ extern "C" int revo_png_decode_submit(revo_png_decoder* d, int n, const revo_png
 }
 
 extern "C" int revo_png_decode_wait(revo_png_decoder* d, uint64_t ticket, int32_t* status) {
-  if (!d) return bad(REVO_ERR_INVALID_ARG, "null decoder");
+  if (!d) return fail(REVO_ERR_INVALID_ARG, "null decoder");
   Slot* sl = nullptr;
   for (Slot& s : d->slot)
     if (s.busy && s.ticket == ticket) sl = &s;
-  if (!sl) return bad(REVO_ERR_INVALID_ARG, "unknown or already waited ticket");
-  PCHECK(hipSetDevice(d->device));
-  PCHECK(hipEventSynchronize(sl->done));
+  if (!sl) return fail(REVO_ERR_INVALID_ARG, "unknown or already waited ticket");
+  HIPCHECK(hipSetDevice(d->device));
+  HIPCHECK(hipEventSynchronize(sl->done));
   sl->busy = false;
   if (status)
     for (int i = 0; i < sl->n; ++i) status[i] = sl->host_status[i] != REVO_OK ? sl->host_status[i] : sl->h_status[i];

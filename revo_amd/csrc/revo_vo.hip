@@ -8,22 +8,8 @@
 #include <condition_variable>
 #include <mutex>
 
-#include "../../include/revo_hip.h"
+#include "revo_internal.h"
 #include "revo_mat4.h"
-
-extern "C" void revo_ctx_retain_(revo_ctx*);
-extern "C" void revo_ctx_release_(revo_ctx*);
-extern "C" void revo_tracker_reset_past_(revo_ctx*);
-extern "C" int revo_ctx_reserve_framesets_(revo_ctx*, int total);
-// split single-pair calls (revo_host.hip): launch now, read the result later
-extern "C" int revo_track_launch_(revo_ctx*, const revo_pyr* ref, const revo_pyr* curr, const float R[9], const float T[3], int slot,
-                                  unsigned* seq_out);
-extern "C" int revo_track_wait_(revo_ctx*, int slot, unsigned seq, float R[9], float T[3], float* err, int* status);
-extern "C" int revo_assess_launch_(revo_ctx*, const float T_w_curr[16], const revo_pyr* curr, int* nframes_out, unsigned* seq_out);
-extern "C" int revo_assess_wait_(revo_ctx*, int nframes, unsigned seq, int* status, float* ratio_out);
-extern "C" int revo_vote_overlaps_(const revo_ctx*);
-extern "C" int revo_pyramid_prepare_keyframe_(revo_pyr*);
-extern "C" void revo_debug_section_note_(int i, unsigned long long ns);
 
 namespace {
 struct M4 {  // column-major 4x4, Eigen::Matrix4f storage

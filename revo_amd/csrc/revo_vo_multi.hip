@@ -11,15 +11,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/revo_hip.h"
+#include "revo_internal.h"
 #include "revo_mat4.h"
 #include "revo_multi.h"
 #include "revo_map.h"
-
-extern "C" void revo_ctx_retain_(revo_ctx*);
-extern "C" void revo_ctx_release_(revo_ctx*);
-extern "C" void revo_set_error_(const char* msg);
-extern "C" int revo_ctx_device_(const revo_ctx*);
 
 namespace {
 struct M4 {  // column-major 4x4, Eigen::Matrix4f storage
@@ -40,7 +35,6 @@ void to_RT(const M4& M, float* R, float* T) {
 }
 struct Pose { M4 T_kf_curr, T_w_kf; M4 world() const { return mul(T_w_kf, T_kf_curr); } };  // REVO::Pose, system.h:89-152
 struct Ref { void* set; int frame; double ts; };  // a frame of a step set
-int bad(int code, const char* msg) { revo_set_error_(msg); return code; }
 bool on_device(const void* p, int dev) {  // device memory of `dev` (not host, not another device)
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -86,9 +80,9 @@ static void ref_drop(revo_vo_multi* m, void* set) {
 }
 
 extern "C" int revo_vo_multi_create(revo_ctx* ctx, int n_streams, int max_queue, revo_vo_multi** out) {
-  if (!ctx || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
-  if (n_streams < 1 || n_streams > 1024) return bad(REVO_ERR_INVALID_ARG, "n_streams must be 1..1024");
-  if (max_queue < 1) return bad(REVO_ERR_INVALID_ARG, "max_queue must be >= 1");
+  if (!ctx || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n_streams < 1 || n_streams > 1024) return fail(REVO_ERR_INVALID_ARG, "n_streams must be 1..1024");
+  if (max_queue < 1) return fail(REVO_ERR_INVALID_ARG, "max_queue must be >= 1");
   revo_mdev* d = nullptr;
   const int rc = revo_mdev_create_(ctx, n_streams, &d);
   if (rc) return rc;
@@ -122,8 +116,8 @@ extern "C" int revo_vo_multi_pending(const revo_vo_multi* m, int s) {
 extern "C" int revo_vo_multi_num_keyframes(const revo_vo_multi* m, int s) { return stream_ok(m, s) ? m->st[s].n_keyframes : -1; }
 
 extern "C" int revo_vo_multi_keyframe(const revo_vo_multi* m, int s, revo_pyr** kf, float T_w_kf[16]) {
-  if (!stream_ok(m, s)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
-  if (m->st[s].n_keyframes == 0) return bad(REVO_ERR_INVALID_ARG, "the stream has no keyframe yet");
+  if (!stream_ok(m, s)) return fail(REVO_ERR_INVALID_ARG, "stream out of range");
+  if (m->st[s].n_keyframes == 0) return fail(REVO_ERR_INVALID_ARG, "the stream has no keyframe yet");
   if (kf) *kf = revo_mdev_keyframe_(m->dev, s);
   if (T_w_kf) memcpy(T_w_kf, m->st[s].T_w_kf.m, sizeof(float) * 16);
   return REVO_OK;
@@ -131,9 +125,9 @@ extern "C" int revo_vo_multi_keyframe(const revo_vo_multi* m, int s, revo_pyr** 
 
 // a new sequence on this stream: REVO::start's fresh TrackerNew and empty pose graph (system.cpp:107)
 extern "C" int revo_vo_multi_reset(revo_vo_multi* m, int s) {
-  if (!stream_ok(m, s)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
+  if (!stream_ok(m, s)) return fail(REVO_ERR_INVALID_ARG, "stream out of range");
   Stream& x = m->st[s];
-  if (!x.queue.empty() || x.retrack) return bad(REVO_ERR_INVALID_ARG, "the stream still has frames pending");
+  if (!x.queue.empty() || x.retrack) return fail(REVO_ERR_INVALID_ARG, "the stream still has frames pending");
   if (x.has_prev) ref_drop(m, x.prev.set);
   revo_mdev_clear_past_(m->dev, s, 0);
   x = Stream();
@@ -145,8 +139,8 @@ extern "C" int revo_vo_multi_reset(revo_vo_multi* m, int s) {
 // The map's work (and the integration of promoted slots) is ordered on the tracker stream behind each promotion; a map
 // attached here must live on the handle's context (its stream and its keyframe slots).
 extern "C" int revo_vo_multi_attach_map(revo_vo_multi* m, int s, revo_map* map) {
-  if (!stream_ok(m, s)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
-  if (map && revo_map_ctx_(map) != m->ctx) return bad(REVO_ERR_INVALID_ARG, "the map belongs to another context than the handle");
+  if (!stream_ok(m, s)) return fail(REVO_ERR_INVALID_ARG, "stream out of range");
+  if (map && revo_map_ctx_(map) != m->ctx) return fail(REVO_ERR_INVALID_ARG, "the map belongs to another context than the handle");
   if (map && !m->map_stage) {
     const int rc = revo_map_stage_create_(&m->map_stage);
     if (rc) return rc;
@@ -163,17 +157,17 @@ extern "C" void revo_vo_multi_forget_map_(revo_vo_multi* m, int s, revo_map* map
 
 static int submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16, double depth_scale_factor,
                   int device_src, void* producer) {
-  if (!m || n < 0 || (n > 0 && !frames)) return bad(REVO_ERR_INVALID_ARG, "bad argument");
+  if (!m || n < 0 || (n > 0 && !frames)) return fail(REVO_ERR_INVALID_ARG, "bad argument");
   if (n == 0) return REVO_OK;
-  if (depth_is_u16 && !(depth_scale_factor > 0)) return bad(REVO_ERR_INVALID_ARG, "depth_scale_factor must be > 0");
-  if (n > m->S) return bad(REVO_ERR_INVALID_ARG, "more frames than streams");
+  if (depth_is_u16 && !(depth_scale_factor > 0)) return fail(REVO_ERR_INVALID_ARG, "depth_scale_factor must be > 0");
+  if (n > m->S) return fail(REVO_ERR_INVALID_ARG, "more frames than streams");
   std::vector<char> seen(m->S, 0);
   for (int i = 0; i < n; ++i) {
     const revo_stream_frame& f = frames[i];
-    if (!stream_ok(m, f.stream)) return bad(REVO_ERR_INVALID_ARG, "stream out of range");
-    if (seen[f.stream]) return bad(REVO_ERR_INVALID_ARG, "two frames for one stream in one submit");
+    if (!stream_ok(m, f.stream)) return fail(REVO_ERR_INVALID_ARG, "stream out of range");
+    if (seen[f.stream]) return fail(REVO_ERR_INVALID_ARG, "two frames for one stream in one submit");
     seen[f.stream] = 1;
-    if (!f.bgr || !f.depth) return bad(REVO_ERR_INVALID_ARG, "null image pointer");
+    if (!f.bgr || !f.depth) return fail(REVO_ERR_INVALID_ARG, "null image pointer");
   }
   // strides are checked here, before anything is uploaded: a failed submit leaves every queue as it was
   float cam[6];
@@ -181,20 +175,20 @@ static int submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int 
   const size_t w = (size_t)cam[4];
   for (int i = 0; i < n; ++i)
     if (frames[i].bgr_stride < w * 3 || frames[i].depth_stride < w * (depth_is_u16 ? 2 : 4))
-      return bad(REVO_ERR_INVALID_ARG, "stride smaller than a row");
+      return fail(REVO_ERR_INVALID_ARG, "stride smaller than a row");
   if (device_src) {
     const int dev = revo_ctx_device_(m->ctx);
     const size_t esz = depth_is_u16 ? 2 : 4;
     for (int i = 0; i < n; ++i) {
       if (((uintptr_t)frames[i].depth | frames[i].depth_stride) % esz)
-        return bad(REVO_ERR_INVALID_ARG, "depth rows not aligned to their element size");
+        return fail(REVO_ERR_INVALID_ARG, "depth rows not aligned to their element size");
       if (!on_device(frames[i].bgr, dev) || !on_device(frames[i].depth, dev))
-        return bad(REVO_ERR_INVALID_ARG, "a frame pointer is not device memory of the context's device");
+        return fail(REVO_ERR_INVALID_ARG, "a frame pointer is not device memory of the context's device");
     }
   }
   for (int i = 0; i < n; ++i)
     if (revo_vo_multi_pending(m, frames[i].stream) >= m->max_queue)
-      return bad(REVO_ERR_CAPACITY, "the stream's queue is full: call revo_vo_multi_step first");
+      return fail(REVO_ERR_CAPACITY, "the stream's queue is full: call revo_vo_multi_step first");
   void* set = nullptr;
   const int rc = revo_mdev_submit_(m->dev, n, frames, depth_is_u16, depth_scale_factor, device_src, producer, &set);
   if (rc) return rc;
@@ -217,7 +211,7 @@ extern "C" int revo_vo_multi_submit_device(revo_vo_multi* m, int n, const revo_s
 
 // One body of the while loop of REVO::start (system.cpp:128-284) for every stream that has work, in revo_vo_track_next's order.
 extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int* n_out) {
-  if (!m || !out) return bad(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n_out) *n_out = 0;
   const M4 I = M4::identity();
   std::vector<MultiTrack> trk;

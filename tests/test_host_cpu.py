@@ -23,6 +23,13 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(L, s), "librevo_hip.so does not export %s" % s
     assert b"gfx950" in L.revo_version()
+    # exactly the header: every defined dynamic symbol, of any type, is one of its functions
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    leaked = sorted(s for s in exported if s.startswith(("_Z", "__device_stub__", "__hip_cuid_")))
+    assert not leaked, "librevo_hip.so exports internals: %s" % leaked[:10]
+    assert exported == set(syms), ("exported but not declared: %s; declared but not exported: %s"
+                                   % (sorted(exported - set(syms)), sorted(set(syms) - exported)))
 
 
 def test_struct_layouts_and_defaults_match_the_header():
