@@ -68,17 +68,13 @@ struct FrameSet {
   float* h_depth = nullptr;
   hipEvent_t ev_ready = nullptr;  // recorded on the build stream after the last build kernel
   hipStream_t ready_stream = nullptr;  // ... that stream (a consumer on it is ordered already)
-  hipEvent_t ev_aux = nullptr;    // (batches) the keyframe EDT on the batch's side stream: not owned by the set
-  bool has_aux = false;
-  // (batches) the keyframes' EDT has been DEFERRED to whoever needs it first -- normally the tracker launch of the batch, on
-  // the tracker's stream: the build stream is the critical one of the pipelined step and the tracker streams have slack
+  // (batches) the end of the build has been DEFERRED to whoever needs it first -- normally the tracker launch of the batch, on
+  // the tracker's stream: the build stream is the critical one of the pipelined step and the tracker streams have slack.  The
+  // build ran only the gray half of pyrDown; the depth half, the tile-ordered edge lists of ALL frames and the keyframes' EDT
+  // are left to run_pending_edt
   std::mutex edt_mu;
-  std::atomic<bool> edt_pending{false};  // set by a batch build, cleared under edt_mu by whoever runs the EDT
+  std::atomic<bool> edt_pending{false};  // set by a batch build, cleared under edt_mu by whoever runs the deferred work
   int edt_count = 0;              // keyframes: frames 0, 2, 4, ...
-  bool pts_pending = false;       // (REVO_DEFER >= 2) the tile-ordered edge lists of ALL frames were left to the same consumer too
-  bool depth_pending = false;     // ... and the build ran only the gray half of pyrDown: the depth half goes in front of the lists
-  bool hyst_pending = false;      // (REVO_DEFER = 3) ... and hysteresis + fill-in: the build stopped behind the Canny NMS
-  bool fill_pending = false;      // (REVO_DEFER = 2, REVO_DEFER_FILL) ... fill-in alone: the build stopped behind the hysteresis
   // whoever ran the deferred EDT recorded this on ITS stream: consumers (and the next build into these planes) on any other
   // stream order themselves behind it (`edt_pending == false` alone says "enqueued somewhere", not "visible here")
   hipEvent_t ev_edt = nullptr;
@@ -101,14 +97,12 @@ struct Knobs {
   int track_depth;     // REVO_TRACK_DEPTH (1..4, default 2; REVO_TRACK_SERIAL=1 forces 1): tracker grids the resident gate keeps in flight
   int cluster_one;     // REVO_TRACK_CLUSTER_ONE (0 = automatic): workgroups of the single-pair launch
   int redundant_one;   // REVO_TRACK_REDUNDANT_ONE: levels up to this many points are evaluated redundantly by the single-pair launch
-  int h2d_mode;        // REVO_H2D_STREAMS: 0 = colour and depth planes on two copy streams, 1 = one stream, 2 = swapped
   int direct_h2d;      // REVO_DIRECT_H2D (default 1): revo_pyramid_create reads page-locked caller rows in place (no staging copy)
   int h2d_max_run_mb;  // REVO_H2D_MAX_RUN_MB: host-buffer batches merge adjacent frames into copies of at most this many MB
   bool kspec_one_set;  // REVO_TRACK_KSPEC_ONE (or no REVO_TRACK_KSPEC at all): the single-pair launches' own speculation depths
   int kspec_one[REVO_L];
   int upload_blocks;   // REVO_UPLOAD_BLOCKS: workgroups of the upload kernel for one contiguous plane
-  int h2d_kernel;      // REVO_H2D_KERNEL (default 0): 1 = the in-place frame upload is a copy KERNEL reading the page-locked rows, not hipMemcpyAsync (2: on the build stream)
-  int h2d_wait_poll;   // REVO_H2D_WAIT_POLL (default 1): the in-place frame upload is waited for by polling the event, not by hipEventSynchronize
+  int h2d_kernel;      // REVO_H2D_KERNEL (default 0): 1 = the in-place frame upload is a copy KERNEL reading the page-locked rows, not hipMemcpyAsync
   int stage_edge_depths;  // REVO_STAGE_EDGE_DEPTHS (default 0): pipelined batches stage the edge pixels' depths in the depth pass
 };
 
@@ -144,9 +138,9 @@ struct revo_ctx {
   // host-buffer batches (revo_track_pairs_*): up to 3 jobs in flight, slots recycled per (n, depth type)
   std::vector<struct revo_pairs_job*> jobs;
   hipStream_t copy_stream = nullptr, copy_stream2 = nullptr, pair_streams[2] = {nullptr, nullptr};
-  // The quality vote and the past-cloud copies run on a stream of their own (REVO_VOTE_STREAM=0: on the tracker stream, as up
-  // to round 5): nothing the NEXT frame's tracker reads comes out of them, so in the sequential loop tracker N+1 follows
-  // tracker N directly instead of queueing behind vote N and copy N-1 (profiles/r06_single_stream_timeline.txt: ~35 us of 240).
+  // The quality vote and the past-cloud copies run on a stream of their own: nothing the NEXT frame's tracker reads comes out
+  // of them, so in the sequential loop tracker N+1 follows tracker N directly instead of queueing behind vote N and copy N-1
+  // (profiles/r06_single_stream_timeline.txt: ~35 us of 240).
   hipStream_t vote_stream = nullptr;
   hipEvent_t ev_vote = nullptr;
   hipStream_t frame_copy_stream = nullptr;  // single-frame API: H2D straight out of page-locked caller rows (pyramid_create_common)
@@ -178,12 +172,8 @@ struct revo_batch {
   unsigned mail_epoch = 0;
   bool identity_uploaded = false;  // d_descs already holds the identity initial poses (nothing to upload)
   int cluster;
-  int defer = 2;                   // REVO_DEFER / REVO_EDT_DEFER, read when the batch is created (env_defer_level)
-  int split_depth = 1;             // REVO_SPLIT_DEPTH (default 1): with the lists deferred, the depth half of the pyramid is deferred with them
-  int defer_fill = 0;              // REVO_DEFER_FILL: with the lists deferred, fill-in is deferred with them
+  bool defer = true;               // REVO_DEFER / REVO_EDT_DEFER, read when the batch is created (env_defer)
   hipStream_t stream;
-  hipStream_t side = nullptr;                      // the EDT of the keyframes runs here, next to the edge lists
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev0, ev1, ev_upload;
   // the batch's last tracker grid: a later launch of the SAME batch on another stream shares its mailbox and descriptors,
   // and the next build rewrites what it reads -- both order themselves behind this event
@@ -523,25 +513,22 @@ static void frameset_destroy(FrameSet* fs) {
 // with_points = false: stops after fillInEdges; the caller enqueues launch_tile_points itself (batches run it next to the EDT)
 static void enqueue_build(revo_ctx* c, FrameSet* fs, const uint8_t* d_bgr, const float* d_depth_f32,
                           const uint16_t* d_depth_u16, float alpha, hipStream_t s, bool borrow_depth = false,
-                          bool with_points = true, int frame0 = 0, int nframes = -1, bool with_hyst = true, bool gray_only = false,
-                          bool with_fill = true) {
+                          bool with_points = true, int frame0 = 0, int nframes = -1, bool gray_only = false) {
   PyrGeom g = c->geom;
   g.frame0 = frame0;
   const int B = nframes < 0 ? fs->B : nframes;
   fs->p.depth[0] = (borrow_depth && d_depth_f32) ? const_cast<float*>(d_depth_f32) : fs->own_depth0;
   launch_gray_depth(g, fs->p, d_bgr, d_depth_f32, d_depth_u16, alpha, B, s);
-  // gray_only (batches that leave their edge lists to the first consumer): the depth half of the pyramid is left to it too
+  // gray_only (batches that defer): the depth half of the pyramid is left to the first consumer with the edge lists
   for (int l = 1; l < g.n_levels; ++l) launch_pyrdown(g, fs->p, l, B, s, gray_only ? 1 : 3);
   launch_canny_nms(g, fs->p, B, s);
-  if (!with_hyst) return;  // (batches with REVO_DEFER = 3: the rest is left to the first consumer, run_pending_edt)
   launch_hyst(g, fs->p, B, s);
-  if (with_fill) launch_fill(g, fs->p, B, s);  // (pipelined batches may leave it to the first consumer: only the edge lists and the EDT read its result)
+  launch_fill(g, fs->p, B, s);
   if (with_points) launch_tile_points(g, fs->p, B, s);  // the tracker's (tile-ordered) edge list; the reference's order is built on demand
 }
 
-// The tail of a batch build: the edge lists of all frames (two kernels) and the EDT of the keyframes (two kernels) only
-// depend on the edge maps, not on each other, and all four are latency-bound with idle CUs around them: the EDT runs on a
-// side stream next to the lists (fork after fillInEdges, join before the batch's stream goes on).
+// The tail of a batch build: the edge lists of all frames (two kernels) and the EDT of the keyframes (two kernels), or nothing
+// when they are deferred to the first consumer.
 static int enqueue_batch_tail(revo_batch* b, hipStream_t s);
 static int batch_wait_tracker(revo_batch* b, hipStream_t s);
 
@@ -561,7 +548,6 @@ extern "C" int revo_ctx_create(int device, const revo_pyr_settings* pyr, const r
   c->knobs.track_depth = env_track_depth();
   c->knobs.cluster_one = env_int("REVO_TRACK_CLUSTER_ONE", 0, 0, TRACK_MAX_CLUSTER);
   c->knobs.redundant_one = env_int("REVO_TRACK_REDUNDANT_ONE", 1024, 0, 1 << 30);
-  c->knobs.h2d_mode = env_int("REVO_H2D_STREAMS", 0, 0, 2);
   c->knobs.direct_h2d = env_int("REVO_DIRECT_H2D", 1, 0, 1);
   c->knobs.stage_edge_depths = env_int("REVO_STAGE_EDGE_DEPTHS", 0, 0, 1);  // built, bit-exact, 80 MB less traffic per step and 2.6 % SLOWER: off (profiles/r06_ab_stage_edge_depths.txt)
   {
@@ -576,8 +562,7 @@ extern "C" int revo_ctx_create(int device, const revo_pyr_settings* pyr, const r
     }
   }
   c->knobs.upload_blocks = env_int("REVO_UPLOAD_BLOCKS", 64, 1, 4096);
-  c->knobs.h2d_kernel = env_int("REVO_H2D_KERNEL", 0, 0, 2);
-  c->knobs.h2d_wait_poll = env_int("REVO_H2D_WAIT_POLL", 1, 0, 1);
+  c->knobs.h2d_kernel = env_int("REVO_H2D_KERNEL", 0, 0, 1);
   c->knobs.h2d_max_run_mb = env_int("REVO_H2D_MAX_RUN_MB", 64, 1, 4096);  // (profiles/r06_h2d_run_sizes.txt: 2 / 8 / 24 / 64 MB / unbounded)
   if (opt) c->os = *opt; else revo_opt_settings_default(&c->os);
   if (trk) c->ts = *trk; else revo_tracker_settings_default(&c->ts);
@@ -587,10 +572,8 @@ extern "C" int revo_ctx_create(int device, const revo_pyr_settings* pyr, const r
   struct Guard { revo_ctx* c; ~Guard() { if (c) ctx_free(c); } } guard{c};  // a HIP failure below frees what exists so far
   HIPCHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   HIPCHECK(hipStreamCreateWithFlags(&c->build_stream, hipStreamNonBlocking));
-  if (env_int("REVO_VOTE_STREAM", 1, 0, 1)) {
-    HIPCHECK(hipStreamCreateWithFlags(&c->vote_stream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&c->ev_vote, hipEventDisableTiming));
-  }
+  HIPCHECK(hipStreamCreateWithFlags(&c->vote_stream, hipStreamNonBlocking));
+  HIPCHECK(hipEventCreateWithFlags(&c->ev_vote, hipEventDisableTiming));
   HIPCHECK(hipHostMalloc((void**)&c->h_desc, sizeof(PairDesc)));
   HIPCHECK(hipHostMalloc((void**)&c->h_res, sizeof(revo_pair_result) * 3));
   HIPCHECK(hipHostMalloc((void**)&c->h_seq, sizeof(unsigned) * 4));
@@ -708,7 +691,8 @@ extern "C" int revo_ctx_camera(const revo_ctx* c, int lvl, float out6[6]) {
 
 // ----------------------------------------------------------------- pyramids --
 // Order the consumer stream after the (asynchronous) build of a single-frame pyramid.
-// Runs a deferred keyframe EDT of the set on stream s (which is first ordered behind the build).
+// Runs the deferred end of a batch build on stream s (which is first ordered behind the build): the depth half of the pyramid,
+// the edge lists and the keyframes' EDT.
 static int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s) {
   std::lock_guard<std::mutex> lk(fs->edt_mu);
   if (!fs->edt_pending) {
@@ -717,32 +701,22 @@ static int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s) {
     return REVO_OK;
   }
   if (fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ready, 0));
-  if (fs->hyst_pending) { launch_hyst(c->geom, fs->p, fs->B, s); launch_fill(c->geom, fs->p, fs->B, s); fs->hyst_pending = false; fs->fill_pending = false; }
-  if (fs->fill_pending) { launch_fill(c->geom, fs->p, fs->B, s); fs->fill_pending = false; }
   // (the edge lists and the EDT do not depend on each other; running the EDT first -- next to the memory-bound first kernels of
   // the following build instead of its VALU-bound NMS -- was measured equal: profiles/r04_ab_aux_order.txt)
-  if (fs->pts_pending) {
-    // ... with the depth half of the pyramid in front of them when the build left it out (nothing on the build stream reads the
-    // coarser depth levels or the validity bits: they feed the edge lists only).  Only then: with REVO_SPLIT_DEPTH=0 the build ran
-    // the fused kernel and the depth half must not run a second time.
-    PyrGeom gp = c->geom;
-    if (fs->depth_pending) {
-      // ... and the edges are final by now, so the depth pass -- which streams every depth of a level anyway -- also leaves the
-      // depths of the level's EDGE pixels behind, compact and in list order (k_edge_prefix tells it where): the edge-list
-      // write then reads ~10 MB of staged depths instead of every 128-byte line of the depth planes that holds an edge
-      // pixel (~100 MB per 64-frame batch).  Measured (profiles/r06_ab_stage_edge_depths.txt): k_pts_tiles
-      // moves 61 MB instead of 141 (1.09x its algorithmic bytes), the step 72 MB less -- and is 2.6 % SLOWER: 2.3 M scattered
-      // 4-byte stores and the prefix kernel cost the depth pass more time than the sparse line reads they replace, and no kernel
-      // of this chain is bandwidth-bound.  Bit-exact, OFF by default (REVO_STAGE_EDGE_DEPTHS=1 turns it on).
-      const bool stage = c->knobs.stage_edge_depths && fs->p.stage[0] != nullptr && c->geom.n_levels > 1;
-      if (stage) launch_edge_prefix(c->geom, fs->p, fs->B, s);
-      for (int l = 1; l < c->geom.n_levels; ++l) launch_pyrdown(c->geom, fs->p, l, fs->B, s, 2, stage);
-      gp.pts_staged = stage ? 1 : 0;
-      fs->depth_pending = false;
-    }
-    launch_tile_points(gp, fs->p, fs->B, s);
-    fs->pts_pending = false;
-  }
+  // The depth half of the pyramid goes in front of the edge lists (nothing on the build stream reads the coarser depth levels
+  // or the validity bits: they feed the edge lists only).  The edges are final by now, so the depth pass -- which streams every
+  // depth of a level anyway -- can also leave the depths of the level's EDGE pixels behind, compact and in list order
+  // (k_edge_prefix tells it where): the edge-list write then reads ~10 MB of staged depths instead of every 128-byte line of
+  // the depth planes that holds an edge pixel (~100 MB per 64-frame batch).  Measured (profiles/r06_ab_stage_edge_depths.txt): k_pts_tiles
+  // moves 61 MB instead of 141 (1.09x its algorithmic bytes), the step 72 MB less -- and is 2.6 % SLOWER: 2.3 M scattered
+  // 4-byte stores and the prefix kernel cost the depth pass more time than the sparse line reads they replace, and no kernel
+  // of this chain is bandwidth-bound.  Bit-exact, OFF by default (REVO_STAGE_EDGE_DEPTHS=1 turns it on).
+  PyrGeom gp = c->geom;
+  const bool stage = c->knobs.stage_edge_depths && fs->p.stage[0] != nullptr && c->geom.n_levels > 1;
+  if (stage) launch_edge_prefix(c->geom, fs->p, fs->B, s);
+  for (int l = 1; l < c->geom.n_levels; ++l) launch_pyrdown(c->geom, fs->p, l, fs->B, s, 2, stage);
+  gp.pts_staged = stage ? 1 : 0;
+  launch_tile_points(gp, fs->p, fs->B, s);
   launch_keyframe(c->geom, fs->p, 0, 2, fs->edt_count, s);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(fs->ev_edt, s));
@@ -818,7 +792,7 @@ struct SecTimer {
 };
 // Waits for an event by POLLING it (the in-place frame upload, ~50-100 us): the IO thread gets its answer a few microseconds after the
 // copy has finished instead of after hipEventSynchronize's park-and-wake; the sequential stream runs 1-3 % faster with it
-// (profiles/r06_slow_run_probe.txt, REVO_H2D_WAIT_POLL=0 / 1 alternating on one box: 4.05-4.19 k against 4.09-4.24 k frames/s).
+// (profiles/r06_slow_run_probe.txt: 4.05-4.19 k frames/s with hipEventSynchronize against 4.09-4.24 k).
 static int wait_event_polled(hipEvent_t ev) {
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spin = 0;; ++spin) {
@@ -836,7 +810,6 @@ static int wait_ready_on(revo_ctx* c, const revo_pyr* p, hipStream_t s) {
   // single-frame pyramids: built on the build stream; batch views: built on the batch's / the caller's stream
   // (revo_batch_build records the event) -- either way the consumer stream is ordered behind the build
   if (p->fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, p->fs->ev_ready, 0));
-  if (p->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, p->fs->ev_aux, 0));
   // an accessor / single-pair call on a batch view: runs the deferred EDT if it is still pending, waits for it otherwise
   return run_pending_edt(c, p->fs, s);
 }
@@ -845,7 +818,7 @@ static int wait_ready(revo_ctx* c, const revo_pyr* p) { return wait_ready_on(c, 
 // (revo_pyramid_destroy); a batch view's planes belong to the caller, whose ordering promises are all about the tracker
 // stream -- so that stream waits here (batch views are not what the sequential loop runs on).
 static int vote_enqueued(revo_ctx* c, const revo_pyr* p) {
-  if (!c->vote_stream || p->owns_fs) return REVO_OK;
+  if (p->owns_fs) return REVO_OK;
   HIPCHECK(hipEventRecord(c->ev_vote, c->vote_stream));
   HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_vote, 0));
   return REVO_OK;
@@ -893,17 +866,10 @@ static int pyramid_create_common(revo_ctx* c, const uint8_t* bgr, size_t bgr_str
   if (direct) {
     {
       std::lock_guard<std::mutex> lk(c->mu);
-      if (!c->frame_copy_stream) {
-        // (experiment knob REVO_COPY_STREAM_PRIO: 1 = a high-priority stream, which HIP serves from a hardware-queue pool of its own)
-        int lo = 0, hi = 0;
-        if (env_int("REVO_COPY_STREAM_PRIO", 0, 0, 1) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo)
-          HIPCHECK(hipStreamCreateWithPriority(&c->frame_copy_stream, hipStreamNonBlocking, hi));
-        else
-          HIPCHECK(hipStreamCreateWithFlags(&c->frame_copy_stream, hipStreamNonBlocking));
-      }
+      if (!c->frame_copy_stream) HIPCHECK(hipStreamCreateWithFlags(&c->frame_copy_stream, hipStreamNonBlocking));
     }
     if (!fs->ev_h2d) HIPCHECK(hipEventCreateWithFlags(&fs->ev_h2d, hipEventDisableTiming));
-    hipStream_t cs = c->knobs.h2d_kernel == 2 ? bs : c->frame_copy_stream;  // (2: experiment -- the upload kernel in front of the build, same stream)
+    hipStream_t cs = c->frame_copy_stream;
     if (fs->has_ready) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_ready, 0));  // the previous build out of this set's input planes is done
     if (fs->has_free) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_free, 0));    // ... and its last consumer (depth level 0 is read in place)
     if (fs->has_free2) HIPCHECK(hipStreamWaitEvent(cs, fs->ev_free2, 0));
@@ -922,8 +888,7 @@ static int pyramid_create_common(revo_ctx* c, const uint8_t* bgr, size_t bgr_str
     HIPCHECK(hipStreamWaitEvent(bs, fs->ev_h2d, 0));
     sec.lap(2);  // the build stream's wait for the copies
     // the clone exists: the caller's buffers are free again
-    if (c->knobs.h2d_wait_poll) { int rc = wait_event_polled(fs->ev_h2d); if (rc) return rc; }
-    else HIPCHECK(hipEventSynchronize(fs->ev_h2d));
+    { int rc = wait_event_polled(fs->ev_h2d); if (rc) return rc; }
     sec.lap(3);  // waiting for them
   } else {
     if (fs->has_ready) HIPCHECK(hipEventSynchronize(fs->ev_ready));  // previous upload out of this staging is done
@@ -967,7 +932,8 @@ extern "C" void revo_pyramid_destroy(revo_pyr* p) {
     std::lock_guard<std::mutex> lk(p->ctx->mu);
     hipEventRecord(p->fs->ev_free, p->ctx->stream);
     p->fs->has_free = true;
-    if (p->ctx->vote_stream) { hipEventRecord(p->fs->ev_free2, p->ctx->vote_stream); p->fs->has_free2 = true; }
+    hipEventRecord(p->fs->ev_free2, p->ctx->vote_stream);
+    p->fs->has_free2 = true;
     p->ctx->pool.push_back(p->fs);
   }
   revo_ctx* c = p->owns_fs ? p->ctx : nullptr;
@@ -1329,7 +1295,7 @@ static int assess_launch(revo_ctx* c, const float T_w_curr[16], const revo_pyr* 
   if (c->past.empty() || !c->ts.check_tracking_results) return REVO_OK;
   const int hl = c->ts.histogram_level;
   if (hl < 0 || hl >= c->geom.n_levels) return fail(REVO_ERR_LEVEL, "histogram_level outside the pyramid");
-  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;
+  hipStream_t vs = c->vote_stream;
   { int rc = wait_ready_on(c, curr, vs); if (rc) return rc; }
   float inv[16];
   mat4_inverse(T_w_curr, inv);
@@ -1359,7 +1325,7 @@ static int assess_launch(revo_ctx* c, const float T_w_curr[16], const revo_pyr* 
 static int assess_wait(revo_ctx* c, int nframes, unsigned seq, int* status, int32_t hist4[4], int32_t overlaps4[4]) {
   if (status) *status = REVO_TRACKER_STATE_OK;
   if (nframes < 0) return REVO_OK;
-  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;  // where assess_launch enqueued the vote
+  hipStream_t vs = c->vote_stream;  // where assess_launch enqueued the vote
   { int rc = wait_seq(vs, (volatile unsigned*)(c->h_hist8 + 8), seq); if (rc) return rc; }
   const int* hist = c->h_hist8;
   const int* ov = c->h_hist8 + 4;
@@ -1389,8 +1355,6 @@ extern "C" int revo_tracker_assess_quality(revo_ctx* c, const float T_w_curr[16]
   return assess_wait(c, nframes, seq, status, hist4, overlaps4);
 }
 // split form for the VO driver's look-ahead (revo_vo.hip); not part of the public ABI
-// 1: the vote runs beside the tracker stream (revo_vo.hip then launches the look-ahead tracker FIRST)
-extern "C" int revo_vote_overlaps_(const revo_ctx* c) { return c && c->vote_stream ? 1 : 0; }
 extern "C" int revo_assess_launch_(revo_ctx* c, const float T_w_curr[16], const revo_pyr* curr, int* nframes_out, unsigned* seq_out) {
   if (!c || !T_w_curr || !curr || curr->ctx != c) return fail(REVO_ERR_INVALID_ARG, "bad argument");
   HIPCHECK(hipSetDevice(c->device));
@@ -1436,7 +1400,7 @@ extern "C" int revo_tracker_add_old_pcl(revo_ctx* c, const revo_pyr* src, int lv
   std::lock_guard<std::mutex> lk(c->mu);
   // the reference copies the Eigen matrix (tracker.cpp:219); the copy stays in HBM, in a
   // recycled buffer sized for the level
-  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;  // the votes that read the copy run there
+  hipStream_t vs = c->vote_stream;  // the votes that read the copy run there
   { int rc = wait_ready_on(c, src, vs); if (rc) return rc; }
   Past p{};
   const size_t f = (size_t)src->frame;
@@ -1464,7 +1428,7 @@ extern "C" int revo_tracker_add_old_pcl_host(revo_ctx* c, const float* pcl, size
   { int rc = past_take(c, n, &p); if (rc) return rc; }
   const int ni = (int)n;
   // pageable source: the runtime has read it when the call returns (the caller's matrix may die right after)
-  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;
+  hipStream_t vs = c->vote_stream;
   if (n) HIPCHECK(hipMemcpyAsync(p.d_pts, pcl, sizeof(float4) * n, hipMemcpyHostToDevice, vs));
   HIPCHECK(hipMemcpyAsync(p.d_n, &ni, sizeof(int), hipMemcpyHostToDevice, vs));
   HIPCHECK(hipStreamSynchronize(vs));
@@ -1494,11 +1458,10 @@ extern "C" void revo_tracker_reset_past_(revo_ctx* c) {
 extern "C" int revo_tracker_past_size(const revo_ctx* c) { return c ? (int)c->past.size() : 0; }
 
 // -------------------------------------------------------------------- batch --
-static int env_defer_level() {  // read when a batch is created
-  if (!env_int("REVO_EDT_DEFER", 1, 0, 1)) return 0;
-  // default 2 (round 4: 87.1 k -> 95.6 k frames/s together with a stream of their own for the deferred kernels and four batches
-  // in rotation, profiles/r04_ab_defer_levels.txt; 3 was measured too: 92.8 k)
-  return env_int("REVO_DEFER", 2, 0, 3);
+static bool env_defer() {  // read when a batch is created: REVO_EDT_DEFER=0 or REVO_DEFER=0 defers nothing
+  // (round 4: 87.1 k -> 95.6 k frames/s together with a stream of their own for the deferred kernels and four batches in
+  // rotation; measured, not kept: the other levels, profiles/r04_ab_defer_levels.txt)
+  return env_int("REVO_EDT_DEFER", 1, 0, 1) && env_int("REVO_DEFER", 2, 0, 3) != 0;
 }
 extern "C" int revo_batch_create(revo_ctx* c, int n_pairs, revo_batch** out) {
   if (!c || !out || n_pairs <= 0) return fail(REVO_ERR_INVALID_ARG, "bad argument");
@@ -1513,19 +1476,8 @@ extern "C" int revo_batch_create(revo_ctx* c, int n_pairs, revo_batch** out) {
   HIPCHECK(hipEventCreate(&b->ev0)); HIPCHECK(hipEventCreate(&b->ev1));
   HIPCHECK(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
   HIPCHECK(hipEventCreateWithFlags(&b->ev_trk, hipEventDisableTiming));
-  // REVO_BUILD_FORK=1: the keyframes' EDT on a side stream next to the edge-list kernels.  Off by default: when the two
-  // really run concurrently (their streams on different hardware queues) the pipelined step collapses (GPU_MAX_HW_QUEUES=8:
-  // 78.5 k -> 47.4 k frames/s), and with HIP's default four queues, where they mostly share a queue, it gains nothing
-  // (77.1 k with the fork, 78.7 k without).
-  if (env_int("REVO_BUILD_FORK", 0, 0, 1)) {
-    HIPCHECK(hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-    HIPCHECK(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
-  }
   b->cluster = pick_cluster(c, n_pairs);
-  b->defer = env_defer_level();
-  b->split_depth = env_int("REVO_SPLIT_DEPTH", 1, 0, 1);
-  b->defer_fill = env_int("REVO_DEFER_FILL", 0, 0, 1);
+  b->defer = env_defer();
   HIPCHECK(hipMalloc((void**)&b->d_mail, mail_bytes(n_pairs, b->cluster)));
   HIPCHECK(hipMemset(b->d_mail, 0, mail_bytes(n_pairs, b->cluster)));
   for (int f = 0; f < 2 * n_pairs; ++f) b->views.push_back(revo_pyr{c, b->fs, f, false, (f % 2) == 0, 0.0, false, false});
@@ -1543,9 +1495,6 @@ extern "C" void revo_batch_destroy(revo_batch* b) {
   if (!b) return;
   hipSetDevice(b->ctx->device);
   if (b->stream) hipStreamSynchronize(b->stream);
-  if (b->side) { hipStreamSynchronize(b->side); hipStreamDestroy(b->side); }
-  if (b->ev_fork) hipEventDestroy(b->ev_fork);
-  if (b->ev_join) hipEventDestroy(b->ev_join);
   hipHostFree(b->h_descs); hipHostFree(b->h_flags); hipFree(b->d_descs); hipFree(b->d_mail);
   if (b->ev0) hipEventDestroy(b->ev0);
   if (b->ev1) hipEventDestroy(b->ev1);
@@ -1563,12 +1512,12 @@ static int batch_wait_tracker(revo_batch* b, hipStream_t s) {
   return REVO_OK;
 }
 // A tracker grid on a stream other than the build's: ordered behind the build whatever was deferred (with
-// REVO_DEFER=0 / REVO_EDT_DEFER=0 / REVO_BUILD_FORK=1 nothing is pending, so run_pending_edt orders nothing -- and the edge
-// lists, counts and DT planes the grid reads are written by the build stream).  Cheap and idempotent.
+// REVO_DEFER=0 / REVO_EDT_DEFER=0 nothing is pending, so run_pending_edt orders nothing -- and the edge lists, counts and DT
+// planes the grid reads are written by the build stream).  Cheap and idempotent.
 static int batch_wait_build(revo_batch* b, hipStream_t s) {
   // (with work deferred to the first consumer, run_pending_edt does the ordering: it either runs that work on s behind the
   // "built" event or waits for the "prepared" event of whoever ran it -- no second barrier packet on the tracker's stream)
-  if (b->defer >= 1 && !b->side) return REVO_OK;
+  if (b->defer) return REVO_OK;
   if (b->fs->has_ready && b->fs->ready_stream != s) HIPCHECK(hipStreamWaitEvent(s, b->fs->ev_ready, 0));
   return REVO_OK;
 }
@@ -1579,37 +1528,14 @@ static int batch_mark_tracker(revo_batch* b, hipStream_t s) {
   return REVO_OK;
 }
 
-// the depth half of the pyramid travels with the deferred edge lists (REVO_DEFER >= 2, no side stream; REVO_SPLIT_DEPTH=0 keeps it
-// in the build: an experiment knob read when the batch is created)
-static bool batch_splits_depth(const revo_batch* b) { return !b->side && b->defer >= 2 && b->split_depth; }
-// fillInEdges travels with the deferred work too (REVO_DEFER = 2, REVO_DEFER_FILL: read when the batch is created): nothing on the
-// build stream reads its result -- the next kernels of that stream belong to the NEXT build
-static bool batch_defers_fill(const revo_batch* b) { return !b->side && b->defer == 2 && b->defer_fill; }
 static int enqueue_batch_tail(revo_batch* b, hipStream_t s) {
   const PyrGeom& g = b->ctx->geom;
-  if (b->side) {
-    // The batch's stream does NOT wait for the EDT: what needs it -- the tracker of this batch, the accessors of its views,
-    // the next build into the same planes -- waits for ev_join itself, so the next batch's first build kernels (on the
-    // caller's stream) can start while this batch's EDT is still running.
-    HIPCHECK(hipEventRecord(b->ev_fork, s));
-    HIPCHECK(hipStreamWaitEvent(b->side, b->ev_fork, 0));
-    launch_keyframe(g, b->fs->p, 0, 2, b->n_pairs, b->side);  // frame 2i = keyframe of pair i
-    HIPCHECK(hipEventRecord(b->ev_join, b->side));
-    b->fs->ev_aux = b->ev_join; b->fs->has_aux = true;
-    launch_tile_points(g, b->fs->p, b->fs->B, s);
-  } else if (b->defer >= 1) {
+  if (b->defer) {
     // Work left to the batch's first consumer (run_pending_edt: the tracker launch on ITS stream, revo_batch_prepare on a
     // stream of the caller's choice, an accessor, revo_batch_sync) -- the build stream is the critical chain of the
-    // pipelined step.  REVO_DEFER = 1: the keyframes' EDT (97 us less on the build stream; round 3);  2: the edge lists of all
-    // frames too (they only depend on the edge maps and nothing on the build stream reads them);  3: hysteresis + fill-in as
-    // well (the build ends behind the Canny NMS).  REVO_EDT_DEFER=0 / REVO_DEFER=0: nothing is deferred.
-    const int lvl = b->defer;
-    if (lvl < 2) launch_tile_points(g, b->fs->p, b->fs->B, s);
+    // pipelined step: the depth half of the pyramid, the edge lists of all frames (they only depend on the edge maps and
+    // nothing on the build stream reads them) and the keyframes' EDT.  REVO_EDT_DEFER=0 / REVO_DEFER=0: nothing is deferred.
     std::lock_guard<std::mutex> lk(b->fs->edt_mu);
-    b->fs->hyst_pending = lvl >= 3;
-    b->fs->fill_pending = batch_defers_fill(b);
-    b->fs->pts_pending = lvl >= 2;
-    b->fs->depth_pending = batch_splits_depth(b);
     b->fs->edt_pending = true; b->fs->edt_count = b->n_pairs;
   } else {
     launch_tile_points(g, b->fs->p, b->fs->B, s);
@@ -1627,12 +1553,10 @@ static int batch_build_f32(revo_batch* b, const uint8_t* d_bgr, const float* d_d
   // kernels are throughput-limited, smaller launches only add tails.)
   // (last_results stays: a caller that pipelines track_only(k) -> build(k) -> sync still gets the flag-8 check of launch k;
   // the result buffer must stay valid until revo_batch_sync or the next revo_batch_track_only)
-  if (b->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, b->ev_join, 0));  // the previous build's EDT still reads these planes
-  { int rc = wait_edt_before_rebuild(b->fs, s); if (rc) return rc; }     // ... or its deferred EDT, on whichever stream ran it
+  { int rc = wait_edt_before_rebuild(b->fs, s); if (rc) return rc; }     // the previous build's deferred EDT still reads these planes
   { int rc = batch_wait_tracker(b, s); if (rc) return rc; }              // ... and its tracker grid still reads lists and DT planes
   // (Measured and not kept: the two halves of the batch as two concurrent kernel chains -- 78.4 k -> 70.5 k frames/s.)
-  enqueue_build(b->ctx, b->fs, d_bgr, d_depth, nullptr, 0.f, s, borrow, false, 0, -1, b->side || b->defer < 3, batch_splits_depth(b),
-                !batch_defers_fill(b));
+  enqueue_build(b->ctx, b->fs, d_bgr, d_depth, nullptr, 0.f, s, borrow, false, 0, -1, b->defer);
   { int rc = enqueue_batch_tail(b, s); if (rc) return rc; }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(b->fs->ev_ready, s));  // accessors / single-pair calls on the batch's views wait for this
@@ -1667,7 +1591,6 @@ extern "C" int revo_batch_prepare(revo_batch* b, void* stream) {
   if (!b) return fail(REVO_ERR_INVALID_ARG, "null argument");
   HIPCHECK(hipSetDevice(b->ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-  if (b->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, b->ev_join, 0));
   return run_pending_edt(b->ctx, b->fs, s);
 }
 
@@ -1682,8 +1605,7 @@ extern "C" int revo_batch_track_only(revo_batch* b, const float* h_init_RT, revo
   TrackParams tp = b->ctx->tp;
   tp.eval_only = 0;
   { int rc1 = batch_wait_build(b, s); if (rc1) return rc1; }
-  if (b->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, b->ev_join, 0));  // the keyframes' EDT (side stream of the build)
-  { int rc2 = run_pending_edt(b->ctx, b->fs, s); if (rc2) return rc2; }   // ... or deferred to this launch
+  { int rc2 = run_pending_edt(b->ctx, b->fs, s); if (rc2) return rc2; }   // the work deferred to this launch
   b->last_results = d_results;
   rc = chained_track_launch(b->ctx->device, b->ctx->knobs.track_depth, s, [&](unsigned* d_resident) {
     // (live timing, ADVICE r05: the pair sits INSIDE the chain -- behind the waits for older grids, the pose upload and the
@@ -1710,11 +1632,10 @@ extern "C" int revo_batch_build_u16(revo_batch* b, const uint8_t* d_bgr, const u
   if (!(depth_scale_factor > 0.0)) return fail(REVO_ERR_INVALID_ARG, "depth_scale_factor must be positive");
   HIPCHECK(hipSetDevice(b->ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-  if (b->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, b->ev_join, 0));
   { int rc = wait_edt_before_rebuild(b->fs, s); if (rc) return rc; }
   { int rc = batch_wait_tracker(b, s); if (rc) return rc; }
   enqueue_build(b->ctx, b->fs, d_bgr, nullptr, d_depth_raw, (float)(1.0f / depth_scale_factor), s, false, false, 0, -1,
-                b->side || b->defer < 3, batch_splits_depth(b), !batch_defers_fill(b));
+                b->defer);
   { int rc = enqueue_batch_tail(b, s); if (rc) return rc; }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(b->fs->ev_ready, s));  // accessors / single-pair calls on the batch's views wait for this
@@ -1736,7 +1657,6 @@ extern "C" int revo_batch_sync(revo_batch* b, void* stream) {
   HIPCHECK(hipSetDevice(b->ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : b->stream;
   HIPCHECK(hipStreamSynchronize(s));
-  if (b->side) HIPCHECK(hipStreamSynchronize(b->side));  // (the keyframes' EDT of the last build)
   if (b->fs->edt_pending) { int rc2 = run_pending_edt(b->ctx, b->fs, s); if (rc2) return rc2; HIPCHECK(hipStreamSynchronize(s)); }
   // A record with bit 3 carries no pose (its workgroups could not exchange partial sums: device shared with
   // another process): that is an error of the call, not something to find by decoding flags.
@@ -1850,10 +1770,7 @@ extern "C" int revo_track_pairs_submit(revo_ctx* c, int n, const revo_pair_in* p
   // reaches 40 (profiles/r03_host_buffer_streams.txt: GPU_MAX_HW_QUEUES=8 lifts f32 to 45 GB/s -- and costs the pipelined
   // device-buffer batches a third of their throughput, so the library does not ask for it; swapping the planes' streams
   // helped in one order of events and not in another: the mapping depends on the process's stream history).
-  // REVO_H2D_STREAMS: 1 = one copy stream for both planes, 2 = planes swapped (experiments).
-  const int h2d_mode = c->knobs.h2d_mode;
-  hipStream_t cs = c->copy_stream, cs2 = h2d_mode == 1 ? c->copy_stream : c->copy_stream2;  // cs: colour, cs2: depth
-  if (h2d_mode == 2) std::swap(cs, cs2);
+  hipStream_t cs = c->copy_stream, cs2 = c->copy_stream2;  // cs: colour, cs2: depth
   // Any failure below must not leave the slot busy for ever (three of those and the context only ever answers
   // REVO_ERR_CAPACITY), nor return while the DMA engines may still be reading the caller's buffers.
   struct SlotGuard {
@@ -1964,7 +1881,6 @@ extern "C" int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, con
   revo_ctx* c = b->ctx;
   HIPCHECK(hipSetDevice(c->device));
   hipStream_t s = b->stream;
-  if (b->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, b->ev_join, 0));
   { int rc = wait_edt_before_rebuild(b->fs, s); if (rc) return rc; }
   { int rc = batch_wait_tracker(b, s); if (rc) return rc; }
   memset(out, 0, sizeof(*out));
@@ -2033,13 +1949,12 @@ extern "C" int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, con
   }
   {  // the state a build + prepare leaves behind
     std::lock_guard<std::mutex> lk(fs->edt_mu);
-    fs->edt_pending = false; fs->pts_pending = false; fs->depth_pending = false; fs->hyst_pending = false; fs->fill_pending = false;
+    fs->edt_pending = false;
     HIPCHECK(hipEventRecord(fs->ev_edt, s));
     fs->has_edt = true; fs->edt_stream = s;
   }
   HIPCHECK(hipEventRecord(fs->ev_ready, s));
   fs->has_ready = true; fs->ready_stream = s;
-  fs->has_aux = false;
   for (auto& v : b->views) { v.table_built = false; v.ref_list_built = false; }
   return REVO_OK;
 }
@@ -2062,7 +1977,6 @@ extern "C" int revo_batch_time_tracker(revo_batch* b, const float* h_init_RT, re
   TrackParams tp = b->ctx->tp;
   tp.eval_only = 0;
   { int rc1 = batch_wait_build(b, s); if (rc1) return rc1; }
-  if (b->fs->has_aux) HIPCHECK(hipStreamWaitEvent(s, b->ev_join, 0));
   { int rc2 = run_pending_edt(b->ctx, b->fs, s); if (rc2) return rc2; }
   float total = 0.f;
   for (int r = 0; r < reps; ++r) {  // events bracket exactly one kernel on its own stream
@@ -2123,7 +2037,7 @@ extern "C" void revo_mdev_destroy_(revo_mdev* m) {
   hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   (void)hipStreamSynchronize(c->build_stream);
-  if (c->vote_stream) (void)hipStreamSynchronize(c->vote_stream);
+  (void)hipStreamSynchronize(c->vote_stream);
   for (FrameSet* fs : m->all) frameset_destroy(fs);
   frameset_destroy(m->kf);
   for (auto& q : m->past) for (auto& p : q) { hipFree(p.d_pts); hipFree(p.d_n); }
@@ -2264,7 +2178,8 @@ extern "C" void revo_mdev_release_set_(revo_mdev* m, void* set) {
   hipSetDevice(c->device);
   hipEventRecord(fs->ev_free, c->stream);
   fs->has_free = true;
-  if (c->vote_stream) { hipEventRecord(fs->ev_free2, c->vote_stream); fs->has_free2 = true; }
+  hipEventRecord(fs->ev_free2, c->vote_stream);
+  fs->has_free2 = true;
   m->pool.push_back(fs);
 }
 
@@ -2314,7 +2229,7 @@ extern "C" int revo_mdev_vote_(revo_mdev* m, int n, MultiVote* votes) {
   revo_ctx* c = m->c;
   HIPCHECK(hipSetDevice(c->device));
   const int nfh = m->ts.n_frames_hist_voting;
-  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;
+  hipStream_t vs = c->vote_stream;
   HIPCHECK(hipEventSynchronize(m->ev_vdesc));  // the previous upload of the descriptors has read them
   int nv = 0, idx[1024];
   const LevelGeom& lv = c->geom.lv[m->hl];
@@ -2378,7 +2293,7 @@ extern "C" int revo_mdev_add_clouds_(revo_mdev* m, int n, const MultiFrame* f) {
   if (n <= 0) return REVO_OK;
   revo_ctx* c = m->c;
   HIPCHECK(hipSetDevice(c->device));
-  hipStream_t vs = c->vote_stream ? c->vote_stream : c->stream;
+  hipStream_t vs = c->vote_stream;
   HIPCHECK(hipEventSynchronize(m->ev_cdesc));
   const size_t keep = 3 + (size_t)std::max(0, m->ts.n_frames_hist_voting);
   for (int i = 0; i < n; ++i) {

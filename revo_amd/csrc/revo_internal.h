@@ -24,7 +24,6 @@ int revo_track_launch_(revo_ctx* c, const revo_pyr* ref, const revo_pyr* curr, c
 int revo_track_wait_(revo_ctx* c, int slot, unsigned seq, float R[9], float T[3], float* err, int* status);
 int revo_assess_launch_(revo_ctx* c, const float T_w_curr[16], const revo_pyr* curr, int* nframes_out, unsigned* seq_out);
 int revo_assess_wait_(revo_ctx* c, int nframes, unsigned seq, int* status, float* ratio_out);
-int revo_vote_overlaps_(const revo_ctx* c);
 int revo_pyramid_prepare_keyframe_(revo_pyr* p);
 void revo_tracker_reset_past_(revo_ctx* c);
 void revo_debug_section_note_(int i, unsigned long long ns);

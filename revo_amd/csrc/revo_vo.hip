@@ -12,23 +12,6 @@
 #include "revo_mat4.h"
 
 namespace {
-struct M4 {  // column-major 4x4, Eigen::Matrix4f storage
-  float m[16];
-  static M4 identity() { M4 o; memset(o.m, 0, sizeof(o.m)); o.m[0] = o.m[5] = o.m[10] = o.m[15] = 1.f; return o; }
-};
-M4 mul(const M4& A, const M4& B) { M4 o; mat4_mul(A.m, B.m, o.m); return o; }
-M4 inverse(const M4& A) { M4 o; mat4_inverse(A.m, o.m); return o; }  // Eigen Matrix4f::inverse()
-M4 from_RT(const float* R, const float* T) {  // transformFromRT
-  M4 o = M4::identity();
-  for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) o.m[c * 4 + r] = R[c * 3 + r];
-  o.m[12] = T[0]; o.m[13] = T[1]; o.m[14] = T[2];
-  return o;
-}
-void to_RT(const M4& M, float* R, float* T) {
-  for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) R[c * 3 + r] = M.m[c * 4 + r];
-  T[0] = M.m[12]; T[1] = M.m[13]; T[2] = M.m[14];
-}
-struct Pose { M4 T_kf_curr, T_w_kf; M4 world() const { return mul(T_w_kf, T_kf_curr); } };  // REVO::Pose, system.h:89-152
 struct Frame { revo_pyr* pyr; double ts; M4 T_w_f; };
 }  // namespace
 
@@ -201,13 +184,11 @@ extern "C" int revo_vo_track_next(revo_vo* v, float pose_out[16], int* new_kf_ou
   int nvote = -1;
   unsigned vseq = 0;
   // The vote has a stream of its own (revo_host.hip, vote_stream): the look-ahead tracker goes out FIRST, so that it starts one
-  // host hop behind the tracker that just finished instead of behind the vote's two launches as well.  With REVO_VOTE_STREAM=0
-  // both share the tracker stream and the vote must stay in front (its answer is waited for below).
-  const bool spec_first = revo_vote_overlaps_(v->ctx) != 0;
+  // host hop behind the tracker that just finished instead of behind the vote's two launches as well.
   // (the previous vote was close to a keyframe change and this frame's vote counts -- the one right behind a new keyframe is
   // ignored, system.cpp:203: hold the look-ahead until the vote is in)
-  const bool hold = spec_first && !v->just_added_kf && v->last_ratio < v->kf_guard;
-  if ((!spec_first || hold) && (rc = revo_assess_launch_(v->ctx, currPoseInWorld.m, curr.pyr, &nvote, &vseq))) return rc;
+  const bool hold = !v->just_added_kf && v->last_ratio < v->kf_guard;
+  if (hold && (rc = revo_assess_launch_(v->ctx, currPoseInWorld.m, curr.pyr, &nvote, &vseq))) return rc;
   // what the loop body does when the vote says OK (system.cpp:243-271), computed now so that the next frame's
   // tracker can start behind the vote kernels instead of behind a host round trip
   const Pose ok_last{T_KF_N, v->kf.T_w_f};
@@ -233,7 +214,7 @@ extern "C" int revo_vo_track_next(revo_vo* v, float pose_out[16], int* new_kf_ou
   // held back: the tracker stream is idle while the vote runs -- the distance transforms of the frame that would become the keyframe
   // (the previous one, system.cpp:205-215) go there now; makeKeyframe below finds them done
   else if (v->prev.pyr && v->prev.pyr != v->kf.pyr) (void)revo_pyramid_prepare_keyframe_(v->prev.pyr);
-  if (spec_first && !hold && (rc = revo_assess_launch_(v->ctx, currPoseInWorld.m, curr.pyr, &nvote, &vseq))) return rc;
+  if (!hold && (rc = revo_assess_launch_(v->ctx, currPoseInWorld.m, curr.pyr, &nvote, &vseq))) return rc;
   float ratio = INFINITY;
   if ((rc = revo_assess_wait_(v->ctx, nvote, vseq, &status, &ratio))) return rc;
   v->last_ratio = ratio;
@@ -252,13 +233,11 @@ extern "C" int revo_vo_track_next(revo_vo* v, float pose_out[16], int* new_kf_ou
     if ((rc = revo_tracker_track_frames(v->ctx, v->kf.pyr, curr.pyr, v->R, v->T, &err, &status, nullptr, nullptr))) return rc;
     T_KF_N = from_RT(v->R, v->T);
     currPoseInWorld = mul(v->kf.T_w_f, T_KF_N);
-    if (spec_first) {
-      // the next frame's tracker goes out before the second vote (nobody acts on its answer: just_added_kf) -- its initialisation
-      // is what the end of this body computes from the same matrices in the same order (system.cpp:267-271)
-      const Pose nl{T_KF_N, v->kf.T_w_f};
-      to_RT(mul(nl.T_kf_curr, mul(inverse(v->last.world()), nl.world())), ok_R, ok_T);
-      look_ahead();
-    }
+    // the next frame's tracker goes out before the second vote (nobody acts on its answer: just_added_kf) -- its initialisation
+    // is what the end of this body computes from the same matrices in the same order (system.cpp:267-271)
+    const Pose nl{T_KF_N, v->kf.T_w_f};
+    to_RT(mul(nl.T_kf_curr, mul(inverse(v->last.world()), nl.world())), ok_R, ok_T);
+    look_ahead();
     if ((rc = revo_tracker_assess_quality(v->ctx, currPoseInWorld.m, curr.pyr, &status, nullptr, nullptr))) return rc;
     v->just_added_kf = true;
     new_kf = 1;

@@ -17,23 +17,6 @@
 #include "revo_map.h"
 
 namespace {
-struct M4 {  // column-major 4x4, Eigen::Matrix4f storage
-  float m[16];
-  static M4 identity() { M4 o; memset(o.m, 0, sizeof(o.m)); o.m[0] = o.m[5] = o.m[10] = o.m[15] = 1.f; return o; }
-};
-M4 mul(const M4& A, const M4& B) { M4 o; mat4_mul(A.m, B.m, o.m); return o; }
-M4 inverse(const M4& A) { M4 o; mat4_inverse(A.m, o.m); return o; }
-M4 from_RT(const float* R, const float* T) {  // transformFromRT
-  M4 o = M4::identity();
-  for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) o.m[c * 4 + r] = R[c * 3 + r];
-  o.m[12] = T[0]; o.m[13] = T[1]; o.m[14] = T[2];
-  return o;
-}
-void to_RT(const M4& M, float* R, float* T) {
-  for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) R[c * 3 + r] = M.m[c * 4 + r];
-  T[0] = M.m[12]; T[1] = M.m[13]; T[2] = M.m[14];
-}
-struct Pose { M4 T_kf_curr, T_w_kf; M4 world() const { return mul(T_w_kf, T_kf_curr); } };  // REVO::Pose, system.h:89-152
 struct Ref { void* set; int frame; double ts; };  // a frame of a step set
 bool on_device(const void* p, int dev) {  // device memory of `dev` (not host, not another device)
   hipPointerAttribute_t a;
