@@ -612,6 +612,38 @@ int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8_t* rgb, ui
  * is counted in its keyframes_rejected. */
 int revo_vo_multi_attach_map(revo_vo_multi* mv, int stream, revo_map* m);
 
+/* Views of the map: what the reference's viewer shows from the camera's pose (MapDrawer + SetCurrentCameraPose), as a depth
+ * image and a BGR image per view, splatted through a z-buffer on the device with integer atomics only.
+ * All arithmetic is float32 with every operation rounded on its own.  Per view, on the host: Rc = R^T of T_w_c,
+ * tc_i = -(((Rc_i0*tx) + (Rc_i1*ty)) + (Rc_i2*tz)).  Per voxel with count >= max(min_count, 1): p and colour exactly as
+ * revo_map_extract returns them; pc = ((Rc[:,0]*px + Rc[:,1]*py) + Rc[:,2]*pz) + tc.  Skipped unless pc is finite and
+ * z > zmin, z < zmax (imgpyramidrgbd.h:170-173).  Centre pixel (tracker.cpp:153-156): u = (fx*x)/z + cx, v = (fy*y)/z + cy,
+ * iu = (int)floorf(u), iv = (int)floorf(v); skipped if u or v is not finite or |u| or |v| >= 2^20.  Footprint:
+ * ru = min(splat_max, (int)ceilf(((0.5f*voxel)*fx)/z)), rv likewise with fy; the voxel writes every pixel of
+ * [iu-ru, iu+ru] x [iv-rv, iv+rv] inside the image.  It writes the 64-bit word (bits of z) << 32 | R << 16 | G << 8 | B and a
+ * pixel keeps the MINIMUM word written to it (z > 0: float bits order like the floats; equal z: the smaller colour word) --
+ * a minimum does not depend on order, so a view is the same bytes whatever the table size, integration order or launch.
+ * Outputs: depth (h x w floats, 0 where nothing was written), bgr (h x w x 3 bytes, 0 there), covered = written pixels. */
+typedef struct revo_map_view {
+  int32_t width, height;            /* 1 .. 2048 each                                                              */
+  float fx, fy, cx, cy, zmin, zmax; /* all six zero: the context's level-0 camera and DEPTH_MIN / DEPTH_MAX;       */
+                                    /* else finite, fx > 0, fy > 0, 0 <= zmin < zmax                                 */
+  float T_w_c[16];                  /* camera -> world, column-major, finite                                       */
+  int32_t splat_max;                /* 0 .. 8: bound of the footprint's half width in pixels (0: one pixel/voxel)   */
+  uint32_t min_count;               /* as revo_map_extract's                                                       */
+} revo_map_view;
+/* n views (sizes may differ) of the map as it is behind every integration enqueued so far, in one splat launch and one resolve
+ * launch on the context's tracker stream.  depth[i], bgr[i]: the outputs of view i, rows packed; covered: n entries or NULL.
+ * device_out = 0: host pointers, the call waits.  device_out = 1: device pointers (depth[i], bgr[i] and covered 16-byte
+ * aligned), the call only enqueues.  An empty map renders empty views.  The map is not changed.
+ * REVO_ERR_INVALID_ARG: n < 1, a NULL array or output, a size outside 1 .. 2048, a pose, intrinsic or range that is not finite,
+ * fx or fy <= 0, zmin < 0 or zmin >= zmax, splat_max outside 0 .. 8, a misaligned device output. */
+int revo_map_render(revo_map* m, int n, const revo_map_view* views, float* const* depth, uint8_t* const* bgr, uint32_t* covered,
+                    int device_out);
+/* Waits for the last revo_map_render of m and gives the device time between the start of its splat and the end of its resolve
+ * (HIP events on the tracker stream), in milliseconds.  REVO_ERR_INVALID_ARG if m has rendered nothing yet. */
+int revo_map_render_last_ms(revo_map* m, float* ms);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -136,6 +136,8 @@ def lib():
     L.revo_map_info.argtypes = [vp, vp]
     L.revo_map_extract.argtypes = [vp, C.c_size_t, f32p, u8p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
     L.revo_vo_multi_attach_map.argtypes = [vp, C.c_int, vp]
+    L.revo_map_render.argtypes = [vp, C.c_int, vp, vpp, vpp, vp, C.c_int]
+    L.revo_map_render_last_ms.argtypes = [vp, f32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

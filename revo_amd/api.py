@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairIn, MapInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairIn, MapInfo, MapView,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -284,6 +284,84 @@ class VoxelMap:
         """Binary little-endian PLY, one vertex per voxel in key order: xyz float32, RGB uchar, `count` uint32."""
         from . import ply
         return ply.write_voxel_ply(path, *self.points(min_count))
+
+    def _views(self, T_w_c, camera, zrange, splat_max, min_count):
+        """-> (MapView array, single): camera None = the context's level-0 camera and depth range (zrange must be None too),
+        else an api.Camera or (fx, fy, cx, cy, width, height) and zrange (zmin, zmax) or None = the context's range."""
+        T = np.asarray(T_w_c, np.float32)
+        single = T.ndim == 2
+        T = T.reshape(-1, 4, 4)
+        s = self.cameraPyr.settings
+        if camera is None:
+            if zrange is not None:
+                c0 = self.cameraPyr.at(0)
+                camera = (c0.fx, c0.fy, c0.cx, c0.cy, c0.width, c0.height)
+            else:
+                w, h, k = s.width, s.height, (0.0,) * 6
+        if camera is not None:
+            if isinstance(camera, Camera):
+                camera = (camera.fx, camera.fy, camera.cx, camera.cy, camera.width, camera.height)
+            fx, fy, cx, cy, w, h = camera
+            zmin, zmax = zrange if zrange is not None else (s.depth_min, s.depth_max)
+            k = (fx, fy, cx, cy, zmin, zmax)
+        views = (MapView * max(1, len(T)))()
+        for v, M in zip(views, T):
+            v.width, v.height = int(w), int(h)
+            v.fx, v.fy, v.cx, v.cy, v.zmin, v.zmax = [float(x) for x in k]
+            v.T_w_c[:] = _cm4(M).tolist()
+            v.splat_max, v.min_count = int(splat_max), int(min_count)
+        return views, len(T), single
+
+    def render(self, T_w_c, camera=None, zrange=None, splat_max=4, min_count=1):
+        """The map seen from the camera pose T_w_c (4x4, camera -> world) as (depth [h, w] float32 metres, 0 = nothing there;
+        bgr [h, w, 3] uint8; covered = written pixels): a z-buffered splat on the device (revo_map_render), the same
+        bytes whatever the order of the integrations.  A list or (n, 4, 4) array of poses renders n views in ONE library call
+        and returns three lists.  camera, zrange: see _views; splat_max 0 .. 8 bounds a voxel's footprint in pixels."""
+        views, n, single = self._views(T_w_c, camera, zrange, splat_max, min_count)
+        if n == 0:
+            return [], [], []
+        depth = [np.empty((v.height, v.width), np.float32) for v in views]
+        bgr = [np.empty((v.height, v.width, 3), np.uint8) for v in views]
+        cov = np.zeros(n, np.uint32)
+        dp = (vp * n)(*[a.ctypes.data for a in depth])
+        bp = (vp * n)(*[a.ctypes.data for a in bgr])
+        check(_lib.lib().revo_map_render(self._h, n, views, dp, bp, cov.ctypes.data_as(vp), 0))
+        if single:
+            return depth[0], bgr[0], int(cov[0])
+        return depth, bgr, [int(c) for c in cov]
+
+    def render_into(self, d_depth, d_bgr, T_w_c, camera=None, zrange=None, splat_max=4, min_count=1, d_covered=None, wait=True):
+        """render() into torch device tensors: d_depth [n, h, w] float32 (or [h, w] for one pose), d_bgr [n, h, w, 3] uint8,
+        d_covered None or an int32 / uint32 tensor of n entries; contiguous, on the map's device.  The work is enqueued on the
+        context's tracker stream, not on a torch stream: wait=True returns when it is done, wait=False at once (sync() or any
+        waiting call of the map orders later reads)."""
+        views, n, single = self._views(T_w_c, camera, zrange, splat_max, min_count)
+        h, w = views[0].height, views[0].width
+        if tuple(d_depth.shape) != ((h, w) if single else (n, h, w)) or tuple(d_bgr.shape) != tuple(d_depth.shape) + (3,):
+            raise ValueError("output tensors do not match the views")
+        if str(d_depth.dtype) != "torch.float32" or str(d_bgr.dtype) != "torch.uint8":
+            raise ValueError("d_depth must be float32 and d_bgr uint8")
+        if not (d_depth.is_contiguous() and d_bgr.is_contiguous() and d_depth.is_cuda and d_bgr.is_cuda):
+            raise ValueError("output tensors must be contiguous device tensors")
+        if d_covered is not None and (d_covered.numel() != n or d_covered.element_size() != 4 or not d_covered.is_contiguous()):
+            raise ValueError("d_covered needs n 32-bit entries")
+        dp = (vp * n)(*[d_depth.data_ptr() + 4 * h * w * i for i in range(n)])
+        bp = (vp * n)(*[d_bgr.data_ptr() + 3 * h * w * i for i in range(n)])
+        import torch
+        torch.cuda.current_stream(d_depth.device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
+        check(_lib.lib().revo_map_render(self._h, n, views, dp, bp, vp(d_covered.data_ptr()) if d_covered is not None else None, 1))
+        if wait:
+            self.sync()
+
+    def sync(self):
+        """Waits for the map's enqueued work (integrations and render_into calls)."""
+        self.info()
+
+    def last_render_ms(self):
+        """Device time of the last render / render_into call (splat + resolve, HIP events), in milliseconds; waits for it."""
+        ms = C.c_float()
+        check(_lib.lib().revo_map_render_last_ms(self._h, C.byref(ms)))
+        return ms.value
 
 
 class Optimizer:

@@ -227,6 +227,79 @@ __global__ void __launch_bounds__(256) k_map_extract(const u64* __restrict__ key
   ocount[j] = (unsigned)v.n;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- views --
+// revo_map_render (contract: include/revo_hip.h).  A z-buffer word is (bits of z) << 32 | R << 16 | G << 8 | B; an
+// untouched pixel holds MAP_EMPTY (z is finite and > 0, so no written word reaches it).  A pixel keeps the minimum word.
+struct MapViewK {  // one view of a launch
+  float Rc[9], tc[3];  // world -> camera, Rc row-major
+  float fx, fy, cx, cy, zmin, zmax;
+  float hv;            // 0.5f * voxel
+  int w, h, splat;
+  u64 min_count;
+  u64* zbuf;
+  float* depth; uint8_t* bgr; unsigned* covered;
+};
+
+// One thread per table slot and view (blockIdx.y = view): the voxel's point and colour as k_map_extract forms them, its
+// projection, and one 64-bit atomicMin per footprint pixel.  SKIP: a load of the pixel first; the word stored there only ever
+// decreases during the launch, so a stored word <= this one (however stale) means the atomic could not change it.
+template <bool SKIP>
+__global__ void __launch_bounds__(256) k_map_splat(const u64* __restrict__ keys, const MapVal* __restrict__ vals, unsigned cap,
+                                                   const MapViewK* __restrict__ views) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cap || keys[i] == MAP_EMPTY) return;
+  const MapViewK& vw = views[blockIdx.y];
+  const MapVal v = vals[i];
+  if (v.n < vw.min_count) return;
+  const double inv = (double)v.n;
+  const float px = (float)((double)(long long)v.qx / inv * 0x1p-20);
+  const float py = (float)((double)(long long)v.qy / inv * 0x1p-20);
+  const float pz = (float)((double)(long long)v.qz / inv * 0x1p-20);
+  float pc[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pc[k] = ((vw.Rc[3 * k] * px + vw.Rc[3 * k + 1] * py) + vw.Rc[3 * k + 2] * pz) + vw.tc[k];
+  const float z = pc[2];
+  if (!isfinite(pc[0]) || !isfinite(pc[1]) || !map_depth_ok(z, vw.zmin, vw.zmax)) return;
+  const float u = __fdiv_rn(vw.fx * pc[0], z) + vw.cx;  // tracker.cpp:153-156
+  const float w = __fdiv_rn(vw.fy * pc[1], z) + vw.cy;
+  if (!(fabsf(u) < 1048576.0f) || !(fabsf(w) < 1048576.0f)) return;  // NaN / inf fail the comparison
+  const int iu = (int)floorf(u), iv = (int)floorf(w);
+  const int ru = (int)fminf((float)vw.splat, ceilf(__fdiv_rn(vw.hv * vw.fx, z)));
+  const int rv = (int)fminf((float)vw.splat, ceilf(__fdiv_rn(vw.hv * vw.fy, z)));
+  const int x0 = max(iu - ru, 0), x1 = min(iu + ru, vw.w - 1), y0 = max(iv - rv, 0), y1 = min(iv + rv, vw.h - 1);
+  const u64 h = v.n / 2;
+  const u64 word = ((u64)__float_as_uint(z) << 32) | (((v.sr + h) / v.n) << 16) | (((v.sg + h) / v.n) << 8) | ((v.sb + h) / v.n);
+  for (int y = y0; y <= y1; ++y) {
+    u64* row = vw.zbuf + (size_t)y * vw.w;
+    for (int x = x0; x <= x1; ++x) {
+      if (SKIP && __hip_atomic_load(&row[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= word) continue;
+      atomicMin(&row[x], word);
+    }
+  }
+}
+
+// One thread per pixel and view: z-buffer word -> depth / BGR, the word goes back to MAP_EMPTY for the next call, and the
+// written pixels are counted per block in LDS, then one atomic per block.
+__global__ void __launch_bounds__(256) k_map_view_resolve(const MapViewK* __restrict__ views) {
+  __shared__ unsigned s_n;
+  const MapViewK& vw = views[blockIdx.y];
+  const unsigned npix = (unsigned)(vw.w * vw.h);
+  if (blockIdx.x * 256u >= npix) return;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const unsigned p = blockIdx.x * 256 + threadIdx.x;
+  if (p < npix) {
+    const u64 word = vw.zbuf[p];
+    const bool hit = word != MAP_EMPTY;
+    vw.depth[p] = hit ? __uint_as_float((unsigned)(word >> 32)) : 0.0f;
+    uint8_t* o = vw.bgr + (size_t)p * 3;
+    o[0] = hit ? (uint8_t)word : 0; o[1] = hit ? (uint8_t)(word >> 8) : 0; o[2] = hit ? (uint8_t)(word >> 16) : 0;
+    if (hit) { vw.zbuf[p] = MAP_EMPTY; atomicAdd(&s_n, 1u); }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_n) atomicAdd(vw.covered, s_n);
+}
+
 // ------------------------------------------------------------------------------------------------------------ host side --
 // pinned staging of a launch's descriptors (reused once the previous upload out of it has completed)
 struct revo_map_stage {
@@ -249,6 +322,12 @@ struct revo_map {
   int rehashes = 0;
   revo_map_stage* stage = nullptr;
   std::vector<std::pair<revo_vo_multi*, int>> attached;
+  // revo_map_render: z-buffers of a call's views (every word MAP_EMPTY between calls: the resolve kernel puts it back), the
+  // device outputs of a host-output call, the views' descriptors (pinned + device) and the call's events
+  u64* d_zbuf = nullptr; size_t zbuf_words = 0; bool zbuf_clean = false;
+  char* d_vout = nullptr; size_t vout_bytes = 0;
+  MapViewK* h_views = nullptr; MapViewK* d_views = nullptr; unsigned* d_cov = nullptr; int cap_views = 0;
+  hipEvent_t ev_views = nullptr, ev_r0 = nullptr, ev_r1 = nullptr; bool views_recorded = false, rendered = false;
 };
 
 extern "C" int revo_map_stage_create_(revo_map_stage** out) {
@@ -437,6 +516,10 @@ extern "C" void revo_map_destroy(revo_map* m) {
   (void)hipStreamSynchronize((hipStream_t)m->g.stream);
   revo_map_stage_destroy_(m->stage);
   hipFree(m->d_keys); hipFree(m->d_vals); hipFree(m->d_st); hipHostFree(m->h_pub);
+  hipFree(m->d_zbuf); hipFree(m->d_vout); hipFree(m->d_views); hipFree(m->d_cov); hipHostFree(m->h_views);
+  if (m->ev_views) hipEventDestroy(m->ev_views);
+  if (m->ev_r0) hipEventDestroy(m->ev_r0);
+  if (m->ev_r1) hipEventDestroy(m->ev_r1);
   (void)hipGetLastError();
   revo_ctx_release_(m->ctx);
   delete m;
@@ -555,6 +638,141 @@ extern "C" int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8
     if (rgb) { rgb[3 * j] = (uint8_t)c[i]; rgb[3 * j + 1] = (uint8_t)(c[i] >> 8); rgb[3 * j + 2] = (uint8_t)(c[i] >> 16); }
     if (count) count[j] = k[i];
   }
+  return REVO_OK;
+}
+
+// room for a call's views: descriptors, counters, z-buffer words (kept MAP_EMPTY), device outputs of a host-output call
+static int render_reserve(revo_map* m, int n, size_t words, size_t out_bytes) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  if (!m->ev_views) {
+    HIPCHECK(hipEventCreateWithFlags(&m->ev_views, hipEventDisableTiming));
+    HIPCHECK(hipEventCreate(&m->ev_r0));
+    HIPCHECK(hipEventCreate(&m->ev_r1));
+  }
+  if (m->views_recorded) HIPCHECK(hipEventSynchronize(m->ev_views));  // the previous upload has read the pinned rows
+  if (n > m->cap_views) {
+    HIPCHECK(hipStreamSynchronize(s));  // the previous call's kernels read the descriptors
+    (void)hipHostFree(m->h_views); (void)hipFree(m->d_views); (void)hipFree(m->d_cov);
+    m->h_views = nullptr; m->d_views = nullptr; m->d_cov = nullptr; m->cap_views = 0;
+    HIPCHECK(hipHostMalloc((void**)&m->h_views, sizeof(MapViewK) * n));
+    HIPCHECK(hipMalloc((void**)&m->d_views, sizeof(MapViewK) * n));
+    HIPCHECK(hipMalloc((void**)&m->d_cov, sizeof(unsigned) * n));
+    m->cap_views = n;
+  }
+  if (words > m->zbuf_words) {
+    HIPCHECK(hipStreamSynchronize(s));
+    (void)hipFree(m->d_zbuf);
+    m->d_zbuf = nullptr; m->zbuf_words = 0;
+    HIPCHECK(hipMalloc((void**)&m->d_zbuf, sizeof(u64) * words));
+    m->zbuf_words = words;
+    m->zbuf_clean = false;
+  }
+  if (!m->zbuf_clean) HIPCHECK(hipMemsetAsync(m->d_zbuf, 0xff, sizeof(u64) * m->zbuf_words, s));
+  if (out_bytes > m->vout_bytes) {
+    HIPCHECK(hipStreamSynchronize(s));
+    (void)hipFree(m->d_vout);
+    m->d_vout = nullptr; m->vout_bytes = 0;
+    HIPCHECK(hipMalloc((void**)&m->d_vout, out_bytes));
+    m->vout_bytes = out_bytes;
+  }
+  return REVO_OK;
+}
+
+extern "C" int revo_map_render(revo_map* m, int n, const revo_map_view* views, float* const* depth, uint8_t* const* bgr,
+                               uint32_t* covered, int device_out) {
+  if (!m || !views || !depth || !bgr) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n < 1) return fail(REVO_ERR_INVALID_ARG, "revo_map_render: n must be >= 1");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_out && ((uintptr_t)covered & 15)) return fail(REVO_ERR_INVALID_ARG, "covered is not 16-byte aligned");
+  std::vector<revo_map_view> vs(views, views + n);
+  size_t words = 0, out_bytes = 0;
+  int max_pix = 0;
+  for (int i = 0; i < n; ++i) {
+    revo_map_view& v = vs[i];
+    const std::string at = "view " + std::to_string(i) + ": ";
+    if (!depth[i] || !bgr[i]) return fail(REVO_ERR_INVALID_ARG, at + "null output");
+    if (device_out && (((uintptr_t)depth[i] | (uintptr_t)bgr[i]) & 15))
+      return fail(REVO_ERR_INVALID_ARG, at + "a device output is not 16-byte aligned");
+    if (v.width < 1 || v.width > 2048 || v.height < 1 || v.height > 2048)
+      return fail(REVO_ERR_INVALID_ARG, at + "width and height must be 1 .. 2048");
+    if (v.splat_max < 0 || v.splat_max > 8) return fail(REVO_ERR_INVALID_ARG, at + "splat_max must be 0 .. 8");
+    if (!pose_finite(v.T_w_c)) return fail(REVO_ERR_INVALID_ARG, at + "T_w_c is not finite");
+    const float k[6] = {v.fx, v.fy, v.cx, v.cy, v.zmin, v.zmax};
+    bool zero = true, finite = true;
+    for (float f : k) { zero = zero && f == 0.0f; finite = finite && std::isfinite(f); }
+    if (zero) {
+      v.fx = m->g.fx; v.fy = m->g.fy; v.cx = m->g.cx; v.cy = m->g.cy; v.zmin = m->g.dmin; v.zmax = m->g.dmax;
+    } else {
+      if (!finite) return fail(REVO_ERR_INVALID_ARG, at + "intrinsics and depth range must be finite");
+      if (!(v.fx > 0.0f) || !(v.fy > 0.0f)) return fail(REVO_ERR_INVALID_ARG, at + "fx and fy must be > 0");
+    }
+    if (!(v.zmin >= 0.0f) || !(v.zmin < v.zmax)) return fail(REVO_ERR_INVALID_ARG, at + "the depth range needs 0 <= zmin < zmax");
+    const size_t np = (size_t)v.width * v.height;
+    words += np;
+    out_bytes += (np * 7 + 15) & ~(size_t)15;
+    max_pix = std::max(max_pix, (int)np);
+  }
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  { const int rc = render_reserve(m, n, words, device_out ? 0 : out_bytes); if (rc) return rc; }
+  unsigned* d_cov = device_out && covered ? covered : m->d_cov;
+  size_t zo = 0, oo = 0;
+  for (int i = 0; i < n; ++i) {
+    const revo_map_view& v = vs[i];
+    MapViewK& d = m->h_views[i];
+    const float* T = v.T_w_c;  // column-major: R(r, c) = T[4 c + r], so Rc(r, c) = R(c, r) = T[4 r + c]
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) d.Rc[3 * r + c] = T[4 * r + c];
+      d.tc[r] = -(((d.Rc[3 * r] * T[12]) + (d.Rc[3 * r + 1] * T[13])) + (d.Rc[3 * r + 2] * T[14]));
+    }
+    d.fx = v.fx; d.fy = v.fy; d.cx = v.cx; d.cy = v.cy; d.zmin = v.zmin; d.zmax = v.zmax;
+    d.hv = 0.5f * m->voxel;
+    d.w = v.width; d.h = v.height; d.splat = v.splat_max;
+    d.min_count = std::max<u64>(v.min_count, 1);
+    const size_t np = (size_t)v.width * v.height;
+    d.zbuf = m->d_zbuf + zo;
+    zo += np;
+    if (device_out) { d.depth = depth[i]; d.bgr = bgr[i]; }
+    else { d.depth = (float*)(m->d_vout + oo); d.bgr = (uint8_t*)(m->d_vout + oo + np * 4); oo += (np * 7 + 15) & ~(size_t)15; }
+    d.covered = d_cov + i;
+  }
+  HIPCHECK(hipMemcpyAsync(m->d_views, m->h_views, sizeof(MapViewK) * n, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(m->ev_views, s));
+  m->views_recorded = true;
+  HIPCHECK(hipMemsetAsync(d_cov, 0, sizeof(unsigned) * n, s));
+  m->zbuf_clean = false;  // until the resolve launch that puts every word back is enqueued
+  HIPCHECK(hipEventRecord(m->ev_r0, s));
+  const dim3 blk(256), sgrid((unsigned)((m->cap + 255) / 256), (unsigned)n), rgrid((unsigned)((max_pix + 255) / 256), (unsigned)n);
+  // REVO_MAP_RENDER_SKIP=0: every footprint pixel takes its atomic without the load in front (profiles/map_render_rates.py)
+  if (env_int("REVO_MAP_RENDER_SKIP", 1, 0, 1))
+    hipLaunchKernelGGL(k_map_splat<true>, sgrid, blk, 0, s, m->d_keys, m->d_vals, (unsigned)m->cap, m->d_views);
+  else
+    hipLaunchKernelGGL(k_map_splat<false>, sgrid, blk, 0, s, m->d_keys, m->d_vals, (unsigned)m->cap, m->d_views);
+  HIPCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_map_view_resolve, rgrid, blk, 0, s, m->d_views);
+  HIPCHECK(hipGetLastError());
+  m->zbuf_clean = true;
+  HIPCHECK(hipEventRecord(m->ev_r1, s));
+  m->rendered = true;
+  if (device_out) return REVO_OK;
+  oo = 0;
+  for (int i = 0; i < n; ++i) {
+    const size_t np = (size_t)vs[i].width * vs[i].height;
+    HIPCHECK(hipMemcpyAsync(depth[i], m->d_vout + oo, np * 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(bgr[i], m->d_vout + oo + np * 4, np * 3, hipMemcpyDeviceToHost, s));
+    oo += (np * 7 + 15) & ~(size_t)15;
+  }
+  if (covered) HIPCHECK(hipMemcpyAsync(covered, d_cov, sizeof(unsigned) * n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+extern "C" int revo_map_render_last_ms(revo_map* m, float* ms) {
+  if (!m || !ms) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m->rendered) return fail(REVO_ERR_INVALID_ARG, "the map has rendered nothing yet");
+  HIPCHECK(hipSetDevice(m->g.device));
+  HIPCHECK(hipEventSynchronize(m->ev_r1));
+  HIPCHECK(hipEventElapsedTime(ms, m->ev_r0, m->ev_r1));
   return REVO_OK;
 }
 

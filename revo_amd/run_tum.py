@@ -8,7 +8,10 @@ next one) and writes the same poses_<dataset>.txt files; the PNG decoders are sp
 --exact-sums runs the tracker in its exact-sums mode (api.CameraPyr.setExactSums): sequential or with --streams.
 --map VOXEL fuses every keyframe into a world-frame voxel map of that edge (metres) on the GPU (api.VoxelMap; the settings'
 DO_GENERATE_DENSE_PCL picks dense or edge clouds) and writes map_<dataset>.ply next to the pose file: sequential or with
---streams, the same file either way."""
+--streams, the same file either way.
+--map-views DIR (with --map) renders the finished map from the estimated pose of every keyframe, or with --map-views-every K
+of every K-th tracked frame, on the GPU (api.VoxelMap.render) and writes a TUM-layout data set into DIR (tum.write_map_views:
+rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset."""
 import os
 import sys
 import time
@@ -20,7 +23,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--map VOXEL]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--map VOXEL [--map-views DIR [--map-views-every K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -41,6 +44,24 @@ def main(argv=None):
         if not (np.isfinite(map_voxel) and map_voxel > 0):
             print("--map needs a positive voxel edge in metres")
             return 2
+    views_dir, views_every = None, 0  # tum.write_map_views of the finished map: every keyframe's pose, or every K-th frame's
+    if "--map-views-every" in argv:
+        i = argv.index("--map-views-every")
+        views_every = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+        if views_every < 1:
+            print("--map-views-every needs a positive number of frames")
+            return 2
+    if "--map-views" in argv:
+        i = argv.index("--map-views")
+        views_dir = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+    if (views_dir is not None or views_every) and map_voxel is None:
+        print("--map-views renders the voxel map: it needs --map VOXEL")
+        return 2
+    if views_every and views_dir is None:
+        print("--map-views-every needs --map-views DIR")
+        return 2
     exact_sums = "--exact-sums" in argv  # the tracker's exact-sums mode (both drivers)
     if exact_sums:
         argv = [a for a in argv if a != "--exact-sums"]
@@ -71,7 +92,8 @@ def main(argv=None):
     device = int(argv[2]) if len(argv) > 2 else 0
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
-        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel)
+        return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel,
+                            views_dir, views_every)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
@@ -100,6 +122,9 @@ def main(argv=None):
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
         if vmap is not None:
             _save_map(vmap, name)
+            if views_dir is not None:
+                _save_views(vmap, os.path.join(views_dir, name) if len(io["datasets"]) > 1 else views_dir,
+                            drv.poses, [kf for _, kf in res], views_every, io["depth_scale_factor"])
         if drawer is not None:
             out = drawer.saveModel(os.path.join(model_dir, name) if len(io["datasets"]) > 1 else model_dir)
             print("model: %d points of %d keyframes -> %s, %s" % (drawer.nPts, len(drawer.vpKfsF), out[0], out[1]))
@@ -113,6 +138,14 @@ def _save_map(vmap, name):
     print("Map: %d voxels of %g m from %d keyframes, %d points fused, %d points dropped (outside +-2048 m or the key range)%s -> %s"
           % (info["voxels"], vmap.voxel, info["keyframes"], info["points_integrated"], info["points_dropped"],
              (", %d keyframes refused (max_voxels)" % info["keyframes_rejected"]) if info["keyframes_rejected"] else "", path))
+
+
+def _save_views(vmap, folder, poses, is_kf, every, depth_scale):
+    """--map-views: the finished map from the pose of every keyframe (every == 0) or of every `every`-th tracked frame."""
+    from . import tum
+    sel = poses[::every] if every else [p for p, kf in zip(poses, is_kf) if kf]
+    n = tum.write_map_views(folder, vmap, sel, depth_scale=depth_scale)
+    print("Map views: %d views (%s) -> %s" % (n, ("every %d frames" % every) if every else "one per keyframe", folder))
 
 
 def _report_ate(folder, poses):
@@ -132,7 +165,7 @@ def _report_ate(folder, poses):
 
 
 def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
-                 map_voxel=None):
+                 map_voxel=None, views_dir=None, views_every=0):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -180,6 +213,9 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
         print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
         if r.map is not None:
             _save_map(r.map, name)
+            if views_dir is not None:
+                _save_views(r.map, os.path.join(views_dir, name), r.poses, [kf for _, kf in r], views_every,
+                            io["depth_scale_factor"])
         _report_ate(folder, r.poses)
     print("%d datasets on %d streams: %.1f frames/s (incl. PNG decode, %s)"
           % (len(folders), streams, total / dt,

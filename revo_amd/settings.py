@@ -148,6 +148,19 @@ class MapInfo(C.Structure):
     ]
 
 
+class MapView(C.Structure):
+    """revo_map_view (include/revo_hip.h): one view of revo_map_render.  Intrinsics and depth range all zero: the context's
+    level-0 camera and DEPTH_MIN / DEPTH_MAX."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("zmin", C.c_float), ("zmax", C.c_float),
+        ("T_w_c", C.c_float * 16), ("splat_max", C.c_int32), ("min_count", C.c_uint32),
+    ]
+
+
+assert C.sizeof(MapView) == 104
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

@@ -412,6 +412,52 @@ def write_synthetic_dataset(folder, seq, depth_scale=5000.0):
             fg.write("%.6f %.9f %.9f %.9f 0 0 0 1\n" % (ts, t[0], t[1], t[2]))
 
 
+def read_poses(path):
+    """A pose file as vo.tum_lines writes it ('ts tx ty tz qx qy qz qw' per line) -> [(timestamp, 4x4 float32 pose)]: the
+    rotation of the normalised quaternion, formed in float64 and rounded once."""
+    out = []
+    for line in open(path):
+        if line.startswith("#") or not line.strip():
+            continue
+        p = [float(x) for x in line.split()]
+        x, y, z, w = np.asarray(p[4:8], np.float64) / np.linalg.norm(p[4:8])
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                              [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                              [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]).astype(np.float32)
+        T[:3, 3] = np.asarray(p[1:4], np.float32)
+        out.append((p[0], T))
+    return out
+
+
+def write_map_views(folder, vmap, poses, depth_scale=5000.0, batch=16, splat_max=4, min_count=1):
+    """Renders the voxel map `vmap` (api.VoxelMap.render, `batch` views per library call) from `poses` [(timestamp, 4x4
+    camera -> world)] and writes a TUM-layout data set: rgb/<ts>.png (8-bit colour), depth/<ts>.png (16-bit: metres x
+    depth_scale, rounded to nearest, saturated at 65535, 0 = nothing there), associate.txt, and poses.txt in the pose
+    file's format (vo.tum_lines).  The views are rendered from the poses as poses.txt states them (read_poses), so the
+    folder describes itself: read_associate / load_frame / read_poses give back what was rendered.  -> number of views."""
+    from PIL import Image
+    from . import vo
+    os.makedirs(os.path.join(folder, "rgb"), exist_ok=True)
+    os.makedirs(os.path.join(folder, "depth"), exist_ok=True)
+    pose_file = os.path.join(folder, "poses.txt")
+    with open(pose_file, "w") as f:
+        f.write("".join(line + "\n" for line in vo.tum_lines(poses)))
+    poses = read_poses(pose_file)
+    with open(os.path.join(folder, "associate.txt"), "w") as fa:
+        fa.write("# rgb depth (views of the voxel map at the poses of poses.txt)\n")
+        for i in range(0, len(poses), batch):
+            part = poses[i:i + batch]
+            depth, bgr, _ = vmap.render([T for _, T in part], splat_max=splat_max, min_count=min_count)
+            for (ts, _), d, c in zip(part, depth, bgr):
+                name = "%.6f.png" % ts
+                Image.fromarray(np.ascontiguousarray(c[..., ::-1])).save(os.path.join(folder, "rgb", name))
+                raw = np.clip(np.rint(d.astype(np.float64) * depth_scale), 0, 65535).astype(np.uint16)
+                Image.fromarray(raw).save(os.path.join(folder, "depth", name))
+                fa.write("%.6f rgb/%s %.6f depth/%s\n" % (ts, name, ts, name))
+    return len(poses)
+
+
 def read_groundtruth_positions(path):
     out = {}
     for line in open(path):
