@@ -297,12 +297,21 @@ void revo_batch_destroy(revo_batch* b);
 int revo_batch_track(revo_batch* b, const uint8_t* d_bgr, const float* d_depth,
                      const float* h_init_RT, revo_pair_result* d_results,
                      void* stream);
-/* Stage-wise variants used by bench.py for per-kernel timing. */
+/* Stage-wise variants used by bench.py for per-kernel timing.
+ * What a build leaves to later (default; REVO_DEFER=0 or REVO_EDT_DEFER=0, read by revo_batch_create, builds everything
+ * for every frame at once): the tracker reads a pair's CURRENT frame only through its edge lists and its KEYFRAME only
+ * through its distance transforms.  So the depth levels >= 1 and the edge lists of the current frames (odd) and the distance
+ * transforms of the keyframes (even) are built by the batch's first consumer (revo_batch_prepare), and the depth levels >= 1,
+ * the depth-validity bits and the edge lists of the keyframe-role frames (even) only when somebody asks for them: any
+ * accessor or single-pair / vote call on an even view of revo_batch_frame.  The same kernels run on the same inputs
+ * either way: every plane, list and record is bit-identical to an eager build's.  That late work reads the edge maps and
+ * level 0 of the depth pyramid, so the next revo_batch_build* of the batch is ordered behind it by the library. */
 int revo_batch_build(revo_batch* b, const uint8_t* d_bgr, const float* d_depth,
                      void* stream);
 /* revo_batch_build without the copy of the depth input: level 0 of the depth pyramid IS d_depth (the reference's
  * level 0 is the input image as well, imgpyramidrgbd.cpp:62-64).  d_depth must stay valid and unchanged until the
- * batch is built again or destroyed -- accessors, the tracker's point lists and the keyframe promotion read it. */
+ * batch is built again or destroyed -- accessors, the tracker's point lists and the keyframe promotion read it, and so
+ * does the work an even view triggers on first access (above), whenever that access comes. */
 int revo_batch_build_borrow(revo_batch* b, const uint8_t* d_bgr, const float* d_depth,
                             void* stream);
 /* revo_batch_build for raw uint16 depth [2*n_pairs][H][W] (depth = raw * (float)(1/scale),
@@ -312,19 +321,23 @@ int revo_batch_build_u16(revo_batch* b, const uint8_t* d_bgr, const uint16_t* d_
 int revo_batch_track_only(revo_batch* b, const float* h_init_RT,
                           revo_pair_result* d_results, void* stream);
 /* Runs, on `stream`, whatever part of the last build was left to the batch's first consumer (default: the depth levels >= 1 of the
- * pyramid, imgpyramidrgbd.h:218-249, which only the edge lists read; the 3-D edge lists,
- * imgpyramidrgbd.cpp:199-226, and the keyframes' distance transforms, imgpyramidrgbd.cpp:231-252 -- the build stream is the
- * critical one of a pipelined caller).  revo_batch_track_only does this itself on ITS stream; call this first to run that work
+ * pyramid, imgpyramidrgbd.h:218-249, which only the edge lists read, and the 3-D edge lists, imgpyramidrgbd.cpp:199-226, of the
+ * CURRENT frames 1, 3, 5, ...; the distance transforms, imgpyramidrgbd.cpp:231-252, of the keyframes 0, 2, 4, ... -- the build
+ * stream is the critical one of a pipelined caller).  It does not build the keyframe-role frames' own edge lists: no tracker
+ * grid of the batch reads them (an even view does, on first access).  revo_batch_track_only does this itself on ITS stream; call this first to run that work
  * on another stream (the library orders every later consumer and the next build of the batch behind it) or to keep it outside a
  * timed tracker launch.  On a stream other than the build's it waits for the build.  No-op when nothing is pending. */
 int revo_batch_prepare(revo_batch* b, void* stream);
-/* Waits for `stream` (NULL = the batch's own), runs whatever the last build still left pending, waits for the batch's last
+/* Waits for `stream` (NULL = the batch's own), runs whatever the last build still left pending for the tracker (as
+ * revo_batch_prepare: not the keyframe-role frames' edge lists), waits for the batch's last
  * tracker grid WHEREVER it ran, and decodes the flags of that grid's records: a record with bit 3 makes the call return
  * REVO_ERR_HIP.  Lifetime contract: the d_results buffer of the last revo_batch_track_only / revo_batch_track must stay
  * valid (not freed, not reused for something else) until this call or the batch's next tracker launch -- the call reads it.
  * A later revo_batch_build* does not end that obligation (a pipelined caller builds step k+1 before it syncs step k). */
 int revo_batch_sync(revo_batch* b, void* stream);
-/* Pyramid view of frame f of the batch (owned by the batch). */
+/* Pyramid view of frame f of the batch (owned by the batch).  A view of an even frame builds that role's depth levels >= 1
+ * and edge lists on its first use after a build (all even frames in one go, on the context's stream, behind the build);
+ * what it returns is what a single-frame pyramid of the same input returns. */
 int revo_batch_frame(revo_batch* b, int frame, revo_pyr** out);
 /* Time one launch of the dominant (tracker) kernel with HIP events on its own
  * stream: returns the mean duration in ms over `reps` launches. */
@@ -335,7 +348,8 @@ int revo_batch_time_tracker(revo_batch* b, const float* h_init_RT,
 /* Measurement aid (bench.py's per-kernel roofline table): every kernel of revo_batch_build_borrow + revo_batch_prepare run
  * ALONE on the batch's own stream with HIP events between the launches; us[i] = mean duration of stage i over `reps` passes
  * (event to event: kernel + a few us of dispatch), name[i] = the kernel ("hysteresis" = k_hyst, or the banded kernels where a
- * level takes that path).  Leaves the batch built. */
+ * level takes that path).  Every launch covers all 2*n_pairs frames (n_pairs keyframes for the distance transforms), whatever
+ * a pipelined build would leave for later.  Leaves the batch built, every frame's edge lists included. */
 #define REVO_MAX_STAGES 24
 typedef struct revo_stage_times {
   int32_t n;

@@ -35,6 +35,8 @@ struct LevelGeom {
 
 struct PyrGeom {
   int frame0;  // first frame of this launch (blockIdx.z counts from it): lets a batch be split across streams
+  int fstride; // frame step of the edge-list side (k_pyrdown, k_edge_prefix, k_tile_count, k_pts_tiles): frame0, frame0 + fstride, ...
+               // -- 2 picks the frames of one role out of a batch (keyframes even, current frames odd); every other kernel steps by 1
   int n_levels;
   int total_nms_blocks, total_pix, total_edt_blocks, total_strips, total_cc;
   int total_bands, any_banded;  // hysteresis bands of all levels; 1 if some level has more than one

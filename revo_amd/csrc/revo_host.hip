@@ -70,8 +70,8 @@ struct FrameSet {
   hipStream_t ready_stream = nullptr;  // ... that stream (a consumer on it is ordered already)
   // (batches) the end of the build has been DEFERRED to whoever needs it first -- normally the tracker launch of the batch, on
   // the tracker's stream: the build stream is the critical one of the pipelined step and the tracker streams have slack.  The
-  // build ran only the gray half of pyrDown; the depth half, the tile-ordered edge lists of ALL frames and the keyframes' EDT
-  // are left to run_pending_edt
+  // build ran only the gray half of pyrDown; the depth half and the tile-ordered edge lists of the CURRENT frames (odd) and the
+  // keyframes' EDT (even frames) are left to run_pending_edt -- that is all a tracker grid reads (PairDesc)
   std::mutex edt_mu;
   std::atomic<bool> edt_pending{false};  // set by a batch build, cleared under edt_mu by whoever runs the deferred work
   int edt_count = 0;              // keyframes: frames 0, 2, 4, ...
@@ -80,6 +80,13 @@ struct FrameSet {
   hipEvent_t ev_edt = nullptr;
   hipStream_t edt_stream = nullptr;
   bool has_edt = false;
+  // ... and the KEYFRAME-role frames' depth half and edge lists (even frames: no tracker grid of the batch reads them) are left to
+  // whoever asks for them through an even view (wait_ready_on): same kernels, same inputs, frames 0, 2, 4, ...  Same lock, same
+  // event discipline as the EDT: set by every batch build, cleared by whoever runs the work, ev_ref for consumers on other streams
+  std::atomic<bool> ref_lists_pending{false};
+  hipEvent_t ev_ref = nullptr;
+  hipStream_t ref_stream = nullptr;
+  bool has_ref = false;
   hipEvent_t ev_free = nullptr;   // recorded on the tracker stream when the set goes back to the pool
   hipEvent_t ev_free2 = nullptr;  // ... and on the vote stream (the quality vote and the cloud copy read the set there)
   hipEvent_t ev_h2d = nullptr;    // (single-frame API) the copy out of page-locked caller rows has finished
@@ -188,6 +195,7 @@ struct revo_batch {
 // ---------------------------------------------------------------- geometry --
 static int build_geom(const revo_pyr_settings& s, PyrGeom* g, std::string* why) {
   memset(g, 0, sizeof(*g));
+  g->fstride = 1;
   const int L = s.pyr_min_lvl - s.pyr_max_lvl + 1;  // camerapyr.h:68-71
   if (s.pyr_max_lvl != 0) { *why = "pyr_max_lvl must be 0 (the reference indexes per-level vectors by level)"; return -1; }
   if (L < 1 || L > REVO_L) { *why = "1..6 pyramid levels supported"; return -1; }
@@ -487,6 +495,7 @@ static int frameset_create(revo_ctx* c, int B, bool with_staging, FrameSet** out
   HIPCHECK(hipEventCreateWithFlags(&fs->ev_free, hipEventDisableTiming));
   HIPCHECK(hipEventCreateWithFlags(&fs->ev_free2, hipEventDisableTiming));
   HIPCHECK(hipEventCreateWithFlags(&fs->ev_edt, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&fs->ev_ref, hipEventDisableTiming));
   // counts start at zero so an accessor on a not-yet-built pyramid is well defined
   hipMemsetAsync(fs->p.npts, 0, sizeof(int) * REVO_L * B, c->stream);
   HIPCHECK(hipStreamSynchronize(c->stream));
@@ -502,6 +511,7 @@ static void frameset_destroy(FrameSet* fs) {
   if (fs->ev_free) hipEventDestroy(fs->ev_free);
   if (fs->ev_free2) hipEventDestroy(fs->ev_free2);
   if (fs->ev_edt) hipEventDestroy(fs->ev_edt);
+  if (fs->ev_ref) hipEventDestroy(fs->ev_ref);
   if (fs->ev_h2d) hipEventDestroy(fs->ev_h2d);
   delete fs;
 }
@@ -528,7 +538,7 @@ static void enqueue_build(revo_ctx* c, FrameSet* fs, const uint8_t* d_bgr, const
 }
 
 // The tail of a batch build: the edge lists of all frames (two kernels) and the EDT of the keyframes (two kernels), or nothing
-// when they are deferred to the first consumer.
+// but the two pending flags when they are deferred (run_pending_edt).
 static int enqueue_batch_tail(revo_batch* b, hipStream_t s);
 static int batch_wait_tracker(revo_batch* b, hipStream_t s);
 
@@ -690,19 +700,8 @@ extern "C" int revo_ctx_camera(const revo_ctx* c, int lvl, float out6[6]) {
 }
 
 // ----------------------------------------------------------------- pyramids --
-// Order the consumer stream after the (asynchronous) build of a single-frame pyramid.
-// Runs the deferred end of a batch build on stream s (which is first ordered behind the build): the depth half of the pyramid,
-// the edge lists and the keyframes' EDT.
-static int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(fs->edt_mu);
-  if (!fs->edt_pending) {
-    // already enqueued by an earlier consumer: a consumer on ANOTHER stream must still wait for it
-    if (fs->has_edt && fs->edt_stream != s) HIPCHECK(hipStreamWaitEvent(s, fs->ev_edt, 0));
-    return REVO_OK;
-  }
-  if (fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ready, 0));
-  // (the edge lists and the EDT do not depend on each other; running the EDT first -- next to the memory-bound first kernels of
-  // the following build instead of its VALU-bound NMS -- was measured equal: profiles/r04_ab_aux_order.txt)
+// The depth half + edge lists of the frames f0, f0 + fstride, ... (count frames)
+static void enqueue_list_side(revo_ctx* c, FrameSet* fs, int f0, int fstride, int count, hipStream_t s) {
   // The depth half of the pyramid goes in front of the edge lists (nothing on the build stream reads the coarser depth levels
   // or the validity bits: they feed the edge lists only).  The edges are final by now, so the depth pass -- which streams every
   // depth of a level anyway -- can also leave the depths of the level's EDGE pixels behind, compact and in list order
@@ -712,23 +711,56 @@ static int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s) {
   // 4-byte stores and the prefix kernel cost the depth pass more time than the sparse line reads they replace, and no kernel
   // of this chain is bandwidth-bound.  Bit-exact, OFF by default (REVO_STAGE_EDGE_DEPTHS=1 turns it on).
   PyrGeom gp = c->geom;
+  gp.frame0 = f0; gp.fstride = fstride;
   const bool stage = c->knobs.stage_edge_depths && fs->p.stage[0] != nullptr && c->geom.n_levels > 1;
-  if (stage) launch_edge_prefix(c->geom, fs->p, fs->B, s);
-  for (int l = 1; l < c->geom.n_levels; ++l) launch_pyrdown(c->geom, fs->p, l, fs->B, s, 2, stage);
+  if (stage) launch_edge_prefix(gp, fs->p, count, s);
+  for (int l = 1; l < c->geom.n_levels; ++l) launch_pyrdown(gp, fs->p, l, count, s, 2, stage);
   gp.pts_staged = stage ? 1 : 0;
-  launch_tile_points(gp, fs->p, fs->B, s);
-  launch_keyframe(c->geom, fs->p, 0, 2, fs->edt_count, s);
+  launch_tile_points(gp, fs->p, count, s);
+}
+// Runs the deferred end of a batch build on stream s (which is first ordered behind the build): the depth half of the pyramid
+// and the edge lists of the CURRENT frames (odd), and the keyframes' EDT (even).  need_ref_lists (an accessor or a single-pair
+// call on an EVEN view): also the depth half and the edge lists of the keyframe-role frames, which no tracker grid of the
+// batch reads -- the same kernels over frames 0, 2, 4, ..., so what an accessor returns is what an eager build returns.
+static int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s, bool need_ref_lists = false) {
+  std::lock_guard<std::mutex> lk(fs->edt_mu);
+  bool behind_build = false;  // s already waits for the build
+  if (!fs->edt_pending) {
+    // already enqueued by an earlier consumer: a consumer on ANOTHER stream must still wait for it
+    if (fs->has_edt && fs->edt_stream != s) HIPCHECK(hipStreamWaitEvent(s, fs->ev_edt, 0));
+  } else {
+    if (fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ready, 0));
+    behind_build = true;
+    // (the edge lists and the EDT do not depend on each other; running the EDT first -- next to the memory-bound first kernels of
+    // the following build instead of its VALU-bound NMS -- was measured equal: profiles/r04_ab_aux_order.txt)
+    enqueue_list_side(c, fs, 1, 2, fs->edt_count, s);  // frame 2i + 1 is pair i's current frame: the only lists a grid reads
+    launch_keyframe(c->geom, fs->p, 0, 2, fs->edt_count, s);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(fs->ev_edt, s));
+    fs->has_edt = true;
+    fs->edt_stream = s;
+    fs->edt_pending = false;
+  }
+  if (!need_ref_lists) return REVO_OK;
+  if (!fs->ref_lists_pending) {
+    if (fs->has_ref && fs->ref_stream != s) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ref, 0));
+    return REVO_OK;
+  }
+  if (!behind_build && fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ready, 0));
+  enqueue_list_side(c, fs, 0, 2, fs->edt_count, s);
   HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(fs->ev_edt, s));
-  fs->has_edt = true;
-  fs->edt_stream = s;
-  fs->edt_pending = false;
+  HIPCHECK(hipEventRecord(fs->ev_ref, s));
+  fs->has_ref = true;
+  fs->ref_stream = s;
+  fs->ref_lists_pending = false;
   return REVO_OK;
 }
-// the next build into a set's planes: the deferred EDT of the previous build may still be reading its edge maps on another stream
+// the next build into a set's planes: the deferred EDT of the previous build may still be reading its edge maps on another
+// stream, and so may the keyframe-role frames' edge lists (edge bitmaps, depth level 0)
 static int wait_edt_before_rebuild(FrameSet* fs, hipStream_t s) {
   std::lock_guard<std::mutex> lk(fs->edt_mu);
   if (fs->has_edt && fs->edt_stream != s) HIPCHECK(hipStreamWaitEvent(s, fs->ev_edt, 0));
+  if (fs->has_ref && fs->ref_stream != s) HIPCHECK(hipStreamWaitEvent(s, fs->ev_ref, 0));
   return REVO_OK;
 }
 // The in-place upload of a frame (revo_pyramid_create*, rows in page-locked host memory) as a KERNEL (REVO_H2D_KERNEL=1; the default
@@ -806,12 +838,14 @@ static int wait_event_polled(hipEvent_t ev) {
   HIPCHECK(hipEventSynchronize(ev));
   return REVO_OK;
 }
+// Order the consumer stream after the (asynchronous) build of a single-frame pyramid.
 static int wait_ready_on(revo_ctx* c, const revo_pyr* p, hipStream_t s) {
   // single-frame pyramids: built on the build stream; batch views: built on the batch's / the caller's stream
   // (revo_batch_build records the event) -- either way the consumer stream is ordered behind the build
   if (p->fs->has_ready) HIPCHECK(hipStreamWaitEvent(s, p->fs->ev_ready, 0));
-  // an accessor / single-pair call on a batch view: runs the deferred EDT if it is still pending, waits for it otherwise
-  return run_pending_edt(c, p->fs, s);
+  // an accessor / single-pair call on a batch view: runs the deferred EDT if it is still pending, waits for it otherwise; an
+  // EVEN view (keyframe role) also gets its own edge lists and coarser depth levels, which the batch's trackers never needed
+  return run_pending_edt(c, p->fs, s, (p->frame & 1) == 0);
 }
 static int wait_ready(revo_ctx* c, const revo_pyr* p) { return wait_ready_on(c, p, c->stream); }
 // The vote stream's work on a pyramid `p` is enqueued.  A single-frame pyramid's planes are recycled behind ev_free2
@@ -1533,10 +1567,12 @@ static int enqueue_batch_tail(revo_batch* b, hipStream_t s) {
   if (b->defer) {
     // Work left to the batch's first consumer (run_pending_edt: the tracker launch on ITS stream, revo_batch_prepare on a
     // stream of the caller's choice, an accessor, revo_batch_sync) -- the build stream is the critical chain of the
-    // pipelined step: the depth half of the pyramid, the edge lists of all frames (they only depend on the edge maps and
-    // nothing on the build stream reads them) and the keyframes' EDT.  REVO_EDT_DEFER=0 / REVO_DEFER=0: nothing is deferred.
+    // pipelined step: the depth half of the pyramid and the edge lists of the current frames (they only depend on the edge maps
+    // and nothing on the build stream reads them) and the keyframes' EDT.  The keyframe-role frames' depth half and edge lists
+    // wait for an accessor or a single-pair call on an even view.  REVO_EDT_DEFER=0 / REVO_DEFER=0: nothing is deferred.
     std::lock_guard<std::mutex> lk(b->fs->edt_mu);
     b->fs->edt_pending = true; b->fs->edt_count = b->n_pairs;
+    b->fs->ref_lists_pending = true;
   } else {
     launch_tile_points(g, b->fs->p, b->fs->B, s);
     launch_keyframe(g, b->fs->p, 0, 2, b->n_pairs, s);
@@ -1875,7 +1911,8 @@ extern "C" int revo_track_pairs(revo_ctx* c, int n, const revo_pair_in* pairs, i
 
 // Every kernel of the batch build ALONE, HIP events between the launches on one stream, mean of `reps` passes: the per-kernel
 // table of bench.py's roofline (VERDICT r04 #6b: the kernel furthest below its roofline must be visible in the driver's record).
-// Leaves the batch built exactly like revo_batch_build_borrow + revo_batch_prepare.
+// Every launch covers all B frames (the byte model of the driver's table is per 2 x pairs frames), so it leaves the batch built
+// like revo_batch_build_borrow + revo_batch_prepare PLUS the keyframe-role frames' edge lists.
 extern "C" int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, const float* d_depth, int reps, revo_stage_times* out) {
   if (!b || !d_bgr || !d_depth || !out || reps <= 0) return fail(REVO_ERR_INVALID_ARG, "bad argument");
   revo_ctx* c = b->ctx;
@@ -1950,8 +1987,10 @@ extern "C" int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, con
   {  // the state a build + prepare leaves behind
     std::lock_guard<std::mutex> lk(fs->edt_mu);
     fs->edt_pending = false;
+    fs->ref_lists_pending = false;  // (every kernel above ran over all B frames)
     HIPCHECK(hipEventRecord(fs->ev_edt, s));
     fs->has_edt = true; fs->edt_stream = s;
+    fs->has_ref = false;            // ev_edt covers the even frames' lists too
   }
   HIPCHECK(hipEventRecord(fs->ev_ready, s));
   fs->has_ready = true; fs->ready_stream = s;

@@ -5,7 +5,7 @@
 // resident batches over FOUR device streams:
 //
 //     build stream     : pyramids of step t            (gray, pyrDown, Canny NMS, hysteresis, fill-in)
-//     auxiliary stream : what that build leaves to its first consumer (edge lists of all frames + the keyframes' EDT)
+//     auxiliary stream : what that build leaves to its first consumer (edge lists of the current frames + the keyframes' EDT)
 //     tracker stream 0/1: the tracker grids of consecutive steps alternate (the library's resident gate keeps two in flight)
 //
 // Up to round 4 this choreography lived in bench.py; an integrator who rebuilt it with one stream more or in another

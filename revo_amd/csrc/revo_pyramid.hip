@@ -116,10 +116,10 @@ struct EdgeStage {
 template <bool GRAY, bool DEPTH, bool STAGE = false>
 __global__ void __launch_bounds__(256) k_pyrdown(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst,
                                                  int dw, int dh, const float* __restrict__ dsrc, float* __restrict__ ddst, int frame0,
-                                                 uint8_t* __restrict__ vsrc, float dmin, float dmax, EdgeStage es) {
+                                                 int fstride, uint8_t* __restrict__ vsrc, float dmin, float dmax, EdgeStage es) {
   BUILD_PRIO();
   static_assert(!STAGE || DEPTH, "staging rides on the depth half");
-  const int f = frame0 + blockIdx.z;
+  const int f = frame0 + fstride * blockIdx.z;
   src += (size_t)f * sw * sh;
   dst += (size_t)f * dw * dh;
   dsrc += (size_t)f * sw * sh;
@@ -1687,7 +1687,7 @@ __global__ void __launch_bounds__(1024) k_edge_prefix(PyrGeom g, FramePlanes pl)
   const int nL = g.n_levels - 1;
   const int nB = gridDim.x / nL;
   const int l = blockIdx.x / nB;
-  const int f = g.frame0 + blockIdx.x % nB;
+  const int f = g.frame0 + g.fstride * (blockIdx.x % nB);
   const LevelGeom& lv = g.lv[l];
   const int wpr = lv.wpr, h = lv.h, ntiles = wpr * lv.nchunk;
   const uint2* csw = pl.cs[l] + (size_t)f * h * wpr;
@@ -1743,7 +1743,7 @@ __global__ void __launch_bounds__(1024) k_tile_count(PyrGeom g, FramePlanes pl) 
   __shared__ int s_wsum[16];
   const int nB = gridDim.x / g.n_levels;
   const int l = blockIdx.x / nB;
-  const int f = g.frame0 + blockIdx.x % nB;
+  const int f = g.frame0 + g.fstride * (blockIdx.x % nB);
   const LevelGeom& lv = g.lv[l];
   const int wpr = lv.wpr, h = lv.h, ntiles = wpr * lv.nchunk;
   const bool has_vb = l < g.n_levels - 1;
@@ -1820,7 +1820,7 @@ __global__ void __launch_bounds__(32 * PT_TILES) k_pts_tiles(PyrGeom g, FramePla
   // 1-D grid, frame fastest (the tile groups of a frame share one XCD's L2)
   const int groups = (g.total_tiles + PT_TILES - 1) / PT_TILES;
   const int nB = gridDim.x / groups;
-  const int f = g.frame0 + blockIdx.x % nB;
+  const int f = g.frame0 + g.fstride * (blockIdx.x % nB);
   const int tg = (blockIdx.x / nB) * PT_TILES + (threadIdx.x >> 5);
   if (tg >= g.total_tiles) return;
   int l = 0, t = tg;
@@ -2335,7 +2335,7 @@ void launch_pyrdown(const PyrGeom& g, const FramePlanes& p, int lvl, int B, hipS
     es.cs = p.cs[lvl - 1]; es.epre = p.epre[lvl - 1]; es.base = p.stage_base + tb; es.out = p.stage[lvl - 1];
     es.wpr = sl.wpr; es.tiles_total = g.total_tiles;
   }
-#define PYRDOWN_ARGS p.gray[lvl - 1], sl.w, sl.h, p.gray[lvl], d.w, d.h, p.depth[lvl - 1], p.depth[lvl], g.frame0, p.vb[lvl - 1], g.depth_min, g.depth_max, es
+#define PYRDOWN_ARGS p.gray[lvl - 1], sl.w, sl.h, p.gray[lvl], d.w, d.h, p.depth[lvl - 1], p.depth[lvl], g.frame0, g.fstride, p.vb[lvl - 1], g.depth_min, g.depth_max, es
   if (parts == 1) hipLaunchKernelGGL((k_pyrdown<true, false>), grid, dim3(256), 0, s, PYRDOWN_ARGS);
   else if (parts == 2 && stage_edges) hipLaunchKernelGGL((k_pyrdown<false, true, true>), grid, dim3(256), 0, s, PYRDOWN_ARGS);
   else if (parts == 2) hipLaunchKernelGGL((k_pyrdown<false, true>), grid, dim3(256), 0, s, PYRDOWN_ARGS);
