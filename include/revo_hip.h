@@ -658,6 +658,36 @@ int revo_map_render(revo_map* m, int n, const revo_map_view* views, float* const
  * (HIP events on the tracker stream), in milliseconds.  REVO_ERR_INVALID_ARG if m has rendered nothing yet. */
 int revo_map_render_last_ms(revo_map* m, float* ms);
 
+/* The map as data.  A voxel is nothing but integer sums, so they can leave the handle and come back without loss:
+ * the union of two maps is the slot-wise integer sum -- exact, commutative, associative -- and a map merged from parts is byte
+ * for byte the map one handle would have built from all their keyframes. */
+typedef struct revo_map_voxel_raw {   /* 64 bytes, little-endian, no padding */
+  uint64_t key;        /* (kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20), bit 63 clear */
+  uint64_t count;      /* >= 1 */
+  int64_t  sum_q[3];   /* x, y, z in 2^-20 m */
+  uint64_t sum_bgr[3]; /* B, G, R */
+} revo_map_voxel_raw;
+/* Waits for the map, sets *n to its voxels and writes one record per voxel, at most cap of them.  dst == NULL only counts.
+ * REVO_ERR_CAPACITY (nothing written) if cap < *n.  device_out = 0: host memory, ascending key order -- the canonical form:
+ * equal maps give equal bytes.  device_out = 1: device memory of the map's device, 16-byte aligned, in unspecified order. */
+int revo_map_export_raw(revo_map* m, revo_map_voxel_raw* dst, size_t cap, size_t* n, int device_out);
+/* Adds n records into m (device_in = 0: host memory; 1: device memory, 16-byte aligned).  A key may occur several times: the
+ * exports of several maps go in one call, concatenated.  On success points_integrated += sum of count, points_dropped +=
+ * points_dropped, keyframes += keyframes and voxels is the true count.  All or nothing: REVO_ERR_CAPACITY if the result
+ * would pass max_voxels, REVO_ERR_INVALID_ARG if some record has count == 0 or key bit 63 set; a merge refused for either
+ * changes no voxel and no counter except keyframes_rejected += keyframes, and the map stays usable (the table may have
+ * grown).  Other argument errors (NULL, a misaligned device pointer, keyframes < 0) change nothing at all.  Enqueued on the
+ * context's tracker stream behind pending integrations; the call waits for the device when the device has to decide (device
+ * input, or a map that could reach max_voxels) and for host input.  n == 0 is a no-op. */
+int revo_map_merge_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int device_in, size_t points_dropped,
+                       int32_t keyframes);
+/* revo_map_merge_raw straight from src's table on the device, with src's points_dropped and keyframes.  Waits for src; src is
+ * not changed.  REVO_ERR_INVALID_ARG: NULL, dst == src, voxel edges whose float bits differ, maps on different devices.
+ * dense may differ. */
+int revo_map_merge(revo_map* dst, revo_map* src);
+/* The voxel edge and cloud mode the map was created with (either output may be NULL). */
+int revo_map_voxel_size(revo_map* m, float* voxel, int* dense);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -138,6 +138,10 @@ def lib():
     L.revo_vo_multi_attach_map.argtypes = [vp, C.c_int, vp]
     L.revo_map_render.argtypes = [vp, C.c_int, vp, vpp, vpp, vp, C.c_int]
     L.revo_map_render_last_ms.argtypes = [vp, f32p]
+    L.revo_map_export_raw.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.revo_map_merge_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, C.c_int32]
+    L.revo_map_merge.argtypes = [vp, vp]
+    L.revo_map_voxel_size.argtypes = [vp, f32p, C.POINTER(C.c_int)]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -231,11 +231,21 @@ class VoxelMap:
 
     def __init__(self, cameraPyr, voxel, dense=False, max_voxels=1 << 24, initial_voxels=1 << 16):
         self.cameraPyr = cameraPyr  # the map lives on this context
-        self.voxel = float(voxel)
-        self.dense = bool(dense)
         self._h = vp()
         check(_lib.lib().revo_map_create(cameraPyr._h, C.c_float(voxel), 1 if dense else 0, int(initial_voxels),
                                          int(max_voxels), C.byref(self._h)))
+        v, d = C.c_float(), C.c_int()
+        check(_lib.lib().revo_map_voxel_size(self._h, C.byref(v), C.byref(d)))
+        self._voxel, self._dense = float(v.value), bool(d.value)
+
+    @property
+    def voxel(self):
+        """The voxel edge in metres as the map holds it (float32)."""
+        return self._voxel
+
+    @property
+    def dense(self):
+        return self._dense
 
     def close(self):
         if getattr(self, "_h", None):
@@ -284,6 +294,80 @@ class VoxelMap:
         """Binary little-endian PLY, one vertex per voxel in key order: xyz float32, RGB uchar, `count` uint32."""
         from . import ply
         return ply.write_voxel_ply(path, *self.points(min_count))
+
+    # -- the map as data (revo_map_export_raw / revo_map_merge*, DESIGN 13; records and files: revo_amd/mapfile.py)
+    def export_raw(self):
+        """Every voxel's integer sums as a structured array of mapfile.RAW_DTYPE in ascending key order: the canonical form,
+        equal maps give equal bytes."""
+        from . import mapfile
+        L = _lib.lib()
+        n = C.c_size_t()
+        check(L.revo_map_export_raw(self._h, None, 0, C.byref(n), 0))
+        rec = np.zeros(n.value, mapfile.RAW_DTYPE)
+        m = C.c_size_t()
+        check(L.revo_map_export_raw(self._h, rec.ctypes.data_as(vp) if n.value else None, n.value, C.byref(m), 0))
+        return rec[:m.value]
+
+    @staticmethod
+    def _raw_tensor(t):
+        if not (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.uint8"):
+            raise ValueError("voxel records on the device are a contiguous uint8 device tensor, 64 bytes per record")
+        return t.numel() // 64
+
+    def export_raw_into(self, d_tensor):
+        """export_raw() into a torch uint8 device tensor (64 bytes per record, 16-byte aligned, on the map's device), in
+        unspecified order; returns the number of records written.  Waits for the map."""
+        import torch
+        cap = self._raw_tensor(d_tensor)
+        torch.cuda.current_stream(d_tensor.device).synchronize()  # the tensor's earlier use is over before the tracker stream writes
+        n = C.c_size_t()
+        check(_lib.lib().revo_map_export_raw(self._h, vp(d_tensor.data_ptr()), cap, C.byref(n), 1))
+        return n.value
+
+    def merge_raw(self, records, points_dropped=0, keyframes=0, n=None):
+        """Adds voxel records to the map: a mapfile.RAW_DTYPE array (or its bytes) from host memory, or a torch uint8 device
+        tensor (its first n records; all of them by default).  Keys may repeat: several exports go in one call, concatenated.
+        All or nothing (REVO_ERR_CAPACITY past max_voxels, REVO_ERR_INVALID_ARG for a record with count 0 or key bit 63)."""
+        L = _lib.lib()
+        if hasattr(records, "data_ptr"):
+            import torch
+            have = self._raw_tensor(records)
+            n = have if n is None else int(n)
+            if n < 0 or n > have:
+                raise ValueError("the tensor holds %d records" % have)
+            torch.cuda.current_stream(records.device).synchronize()  # the tensor is written before the tracker stream reads it
+            check(L.revo_map_merge_raw(self._h, vp(records.data_ptr()), n, 1, int(points_dropped), int(keyframes)))
+            self.sync()  # the tensor may go
+            return
+        from . import mapfile
+        rec = mapfile.as_records(records)
+        if n is not None:
+            rec = rec[:int(n)]
+        check(L.revo_map_merge_raw(self._h, rec.ctypes.data_as(vp) if len(rec) else None, len(rec), 0, int(points_dropped),
+                                   int(keyframes)))
+
+    def merge(self, other):
+        """Adds every voxel of `other` (same voxel edge, same device) with its points_dropped and keyframes, straight from its
+        table on the device; `other` is unchanged.  The result is the map one handle would have built from both maps' keyframes."""
+        check(_lib.lib().revo_map_merge(self._h, other._h))
+
+    def save(self, path):
+        """The map as a .rvm file (mapfile): header and canonical records.  Equal maps give equal files."""
+        from . import mapfile
+        rec = self.export_raw()
+        info = self.info()
+        return mapfile.write(path, mapfile.make_header(self.voxel, self.dense, rec, info["points_dropped"], info["keyframes"]), rec)
+
+    @classmethod
+    def load(cls, cameraPyr, path, max_voxels=1 << 24, initial_voxels=1 << 16):
+        """A map on cameraPyr's context holding what the .rvm file holds: voxels, counters, voxel edge and cloud mode.
+        Integrations and merges continue it exactly as if it had never left the device."""
+        from . import mapfile
+        header, rec = mapfile.read(path)
+        m = cls(cameraPyr, header["voxel"], dense=bool(header["dense"]), max_voxels=max_voxels,
+                initial_voxels=max(int(initial_voxels), len(rec)))
+        m.merge_raw(rec, header["points_dropped"], header["keyframes"])
+        return m
 
     def _views(self, T_w_c, camera, zrange, splat_max, min_count):
         """-> (MapView array, single): camera None = the context's level-0 camera and depth range (zrange must be None too),

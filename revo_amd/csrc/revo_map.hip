@@ -36,7 +36,7 @@ typedef unsigned long long u64;
 struct MapVal { u64 n, qx, qy, qz, sb, sg, sr, pad; };  // count, sum q (two's complement int64), sum B, G, R
 struct MapStats {
   u64 occ, pts, drop, kfs, rejected, fault;
-  u64 ok, pad;
+  u64 ok, bad;  // bad: k_map_merge met a record with count 0 or key bit 63 (the host clears it before such a launch)
   u64 shard[MAP_SHARDS][16];  // [0] new voxels, [1] points, [2] dropped points of the batch in flight
 };
 struct MapDesc {  // one keyframe of a launch
@@ -225,6 +225,99 @@ __global__ void __launch_bounds__(256) k_map_extract(const u64* __restrict__ key
   const u64 h = v.n / 2;
   orgb[j] = (unsigned)((v.sr + h) / v.n) | ((unsigned)((v.sg + h) / v.n) << 8) | ((unsigned)((v.sb + h) / v.n) << 16);
   ocount[j] = (unsigned)v.n;
+}
+
+// ------------------------------------------------------------------------------------------------- the map as data (13) --
+// A raw record (revo_map_voxel_raw) is key, count, sum q x y z, sum B G R: eight 64-bit words, moved as four 16-byte words.
+struct MapMergeK {
+  const u64* skeys; const MapVal* svals;  // MERGE_TABLE: the source map's table, n slots
+  const ulonglong2* recs;                 // MERGE_RAW: n records
+  unsigned n;
+  u64* keys; MapVal* vals; unsigned mask;
+  MapStats* st;
+  u64 dropped;  // joins the batch's dropped points once
+};
+enum { MERGE_RAW = 0, MERGE_TABLE = 1 };
+#define MAP_POISON (1ull << 40)  // > MAP_MAX_VOXELS: a batch whose new-voxel count holds it is refused by k_map_commit
+
+// Occupied slots as raw records, compacted in arrival order (the host sorts by key); at most cap_out are written.
+__global__ void __launch_bounds__(256) k_map_export(const u64* __restrict__ keys, const MapVal* __restrict__ vals, unsigned cap,
+                                                    unsigned* total, ulonglong2* out, unsigned cap_out) {
+  __shared__ unsigned s_n, s_base;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  const u64 key = i < cap ? keys[i] : MAP_EMPTY;
+  const bool sel = key != MAP_EMPTY;
+  const unsigned o = sel ? atomicAdd(&s_n, 1u) : 0u;
+  __syncthreads();
+  if (threadIdx.x == 0) s_base = s_n ? atomicAdd(total, s_n) : 0u;
+  __syncthreads();
+  if (!sel) return;
+  const unsigned j = s_base + o;
+  if (j >= cap_out) return;
+  const ulonglong2* v = (const ulonglong2*)(vals + i);
+  const ulonglong2 a = v[0], b = v[1], c = v[2], d = v[3];  // n qx | qy qz | sb sg | sr -
+  ulonglong2* r = out + 4 * (size_t)j;
+  r[0] = make_ulonglong2(key, a.x); r[1] = make_ulonglong2(a.y, b.x); r[2] = make_ulonglong2(b.y, c.x); r[3] = make_ulonglong2(c.y, d.x);
+}
+
+// One thread per input record (MERGE_RAW) or per slot of the source table (MERGE_TABLE): the voxel's sums are added to the
+// slot of its key as k_map_walk adds a run's, in the same three modes, and the block's new voxels and points go through LDS
+// to the map's sharded counters.  A record with count 0 or key bit 63 is never inserted (the rollback invariant is "a new
+// key's slot has count 0"); the first one met poisons the batch's new-voxel count, so k_map_commit refuses the batch, and
+// sets st->bad, so the host can tell why.  Only the checked path (MAP_INSERT) takes records that nobody has validated.
+template <int MODE, int SRC>
+__global__ void __launch_bounds__(256) k_map_merge(const MapMergeK a) {
+  __shared__ unsigned s_new;
+  __shared__ u64 s_pts;
+  if (MODE == MAP_ACCUM && !a.st->ok) return;  // refused: nothing is accumulated
+  if (MODE != MAP_ACCUM) {
+    if (threadIdx.x == 0) { s_new = 0; s_pts = 0; }
+    __syncthreads();
+  }
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  u64 key = MAP_EMPTY;
+  ulonglong2 r0{}, r1{}, r2{}, r3{};  // key n | qx qy | qz sb | sg sr
+  bool bad = false;
+  if (i < a.n) {
+    if (SRC == MERGE_TABLE) {
+      key = a.skeys[i];
+      if (key != MAP_EMPTY) {
+        const ulonglong2* v = (const ulonglong2*)(a.svals + i);
+        const ulonglong2 p = v[0], q = v[1], c = v[2], d = v[3];
+        r0 = make_ulonglong2(key, p.x); r1 = make_ulonglong2(p.y, q.x); r2 = make_ulonglong2(q.y, c.x); r3 = make_ulonglong2(c.y, d.x);
+        if (r0.y == 0) key = MAP_EMPTY;  // a committed voxel has count >= 1
+      }
+    } else {
+      const ulonglong2* v = a.recs + 4 * (size_t)i;
+      r0 = v[0]; r1 = v[1]; r2 = v[2]; r3 = v[3];
+      key = r0.x;
+      bad = (key >> 63) != 0 || r0.y == 0;
+      if (bad) key = MAP_EMPTY;
+    }
+  }
+  if (key != MAP_EMPTY) {
+    const unsigned s = MODE == MAP_ACCUM ? map_slot<false>(a.keys, a.mask, key, nullptr, &a.st->fault)
+                                         : map_slot<true>(a.keys, a.mask, key, &s_new, &a.st->fault);
+    if (MODE != MAP_INSERT && s != ~0u) {
+      MapVal* v = a.vals + s;
+      atomicAdd(&v->n, r0.y);
+      atomicAdd(&v->qx, r1.x); atomicAdd(&v->qy, r1.y); atomicAdd(&v->qz, r2.x);
+      atomicAdd(&v->sb, r2.y); atomicAdd(&v->sg, r3.x); atomicAdd(&v->sr, r3.y);
+    }
+    if (MODE != MAP_ACCUM) atomicAdd(&s_pts, r0.y);
+  }
+  if (MODE != MAP_ACCUM) {
+    if (SRC == MERGE_RAW && bad && atomicOr(&a.st->bad, 1ull) == 0) atomicAdd(&a.st->shard[0][0], MAP_POISON);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      u64* sh = a.st->shard[blockIdx.x & (MAP_SHARDS - 1)];
+      if (s_new) atomicAdd(&sh[0], (u64)s_new);
+      if (s_pts) atomicAdd(&sh[1], s_pts);
+      if (blockIdx.x == 0 && a.dropped) atomicAdd(&sh[2], a.dropped);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- views --
@@ -639,6 +732,144 @@ extern "C" int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8
     if (count) count[j] = k[i];
   }
   return REVO_OK;
+}
+
+static_assert(sizeof(revo_map_voxel_raw) == 64 && sizeof(MapVal) == 64, "a voxel record is four 16-byte words");
+
+extern "C" int revo_map_voxel_size(revo_map* m, float* voxel, int* dense) {
+  if (!m) return fail(REVO_ERR_INVALID_ARG, "null map");
+  if (voxel) *voxel = m->voxel;
+  if (dense) *dense = m->dense;
+  return REVO_OK;
+}
+
+extern "C" int revo_map_export_raw(revo_map* m, revo_map_voxel_raw* dst, size_t cap, size_t* n, int device_out) {
+  if (!m || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_out && ((uintptr_t)dst & 15)) return fail(REVO_ERR_INVALID_ARG, "the device output is not 16-byte aligned");
+  MapStats st;
+  { const int rc = read_stats(m, &st); if (rc) return rc; }
+  const size_t nv = (size_t)st.occ;
+  *n = nv;
+  if (!dst) return REVO_OK;
+  if (cap < nv) return fail(REVO_ERR_CAPACITY, "voxel map: the output holds fewer records than the map has voxels");
+  if (!nv) return REVO_OK;
+  hipStream_t s = (hipStream_t)m->g.stream;
+  char* buf = nullptr;  // the launch's counter, and the records of a host-output call behind it
+  HIPCHECK(hipMalloc((void**)&buf, 256 + (device_out ? 0 : sizeof(revo_map_voxel_raw) * nv)));
+  struct Free { char* p; ~Free() { hipFree(p); } } fr{buf};
+  unsigned* d_tot = (unsigned*)buf;
+  ulonglong2* d_rec = device_out ? (ulonglong2*)dst : (ulonglong2*)(buf + 256);
+  HIPCHECK(hipMemsetAsync(d_tot, 0, sizeof(unsigned), s));
+  hipLaunchKernelGGL(k_map_export, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals, (unsigned)m->cap,
+                     d_tot, d_rec, (unsigned)nv);
+  HIPCHECK(hipGetLastError());
+  unsigned tot = 0;
+  HIPCHECK(hipMemcpyAsync(&tot, d_tot, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (tot != nv) return fail(REVO_ERR_HIP, "voxel map: the table holds " + std::to_string(tot) + " keys, its counter says " + std::to_string(nv));
+  if (device_out) return REVO_OK;
+  HIPCHECK(hipMemcpy(dst, d_rec, sizeof(revo_map_voxel_raw) * nv, hipMemcpyDeviceToHost));
+  std::sort(dst, dst + nv, [](const revo_map_voxel_raw& a, const revo_map_voxel_raw& b) { return a.key < b.key; });  // keys are distinct
+  return REVO_OK;
+}
+
+// One merge into m: `src` names the input (its table fields are filled here), `bound` its keys at most, `trusted` that no
+// record can be bad (validated on the host, or a map's own table).  Grows for bound more keys, then the fused launch, or the
+// checked path (insert, commit, rollback, accumulate) when the device has to decide -- max_voxels in reach, or records nobody
+// has looked at -- and then waits for the decision.
+static int merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool trusted, int keyframes) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  const size_t ub = occ_bound(m);
+  const bool chk = !trusted || ub + bound > m->max_voxels;
+  const size_t need = 2 * (std::min(ub, m->max_voxels) + bound);
+  if (need > MAP_MAX_CAP) return fail(REVO_ERR_CAPACITY, "voxel map: a merge this large needs more than 2^31 table slots");
+  if (m->cap < need) {
+    size_t c = std::max<size_t>(m->cap * 2, 1024);
+    while (c < need) c *= 2;
+    const int rc = grow(m, c);
+    if (rc) return rc;
+  }
+  revo_map_stage* st = m->stage;
+  { const int rc = stage_reserve(st, 0, 1); if (rc) return rc; }
+  ++m->seq;
+  st->h_com[0] = MapCommit{m->d_st, m->h_pub, (u64)m->max_voxels, m->seq, keyframes, chk ? 1 : 0};
+  m->pending.push_back({m->seq, bound});
+  HIPCHECK(hipMemcpyAsync(st->d_com, st->h_com, sizeof(MapCommit), hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(st->ev, s));
+  st->recorded = true;
+  if (!trusted) HIPCHECK(hipMemsetAsync(&m->d_st->bad, 0, sizeof(u64), s));
+  a.keys = m->d_keys; a.vals = m->d_vals; a.mask = (unsigned)(m->cap - 1); a.st = m->d_st;
+  const dim3 grid((a.n + 255) / 256), blk(256);
+  const bool tab = src_kind == MERGE_TABLE;
+  if (!chk) {
+    if (tab) hipLaunchKernelGGL((k_map_merge<MAP_FUSED, MERGE_TABLE>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((k_map_merge<MAP_FUSED, MERGE_RAW>), grid, blk, 0, s, a);
+    hipLaunchKernelGGL(k_map_commit, dim3(1), dim3(64), 0, s, st->d_com, 1);
+    HIPCHECK(hipGetLastError());
+    return REVO_OK;
+  }
+  if (tab) hipLaunchKernelGGL((k_map_merge<MAP_INSERT, MERGE_TABLE>), grid, blk, 0, s, a);
+  else hipLaunchKernelGGL((k_map_merge<MAP_INSERT, MERGE_RAW>), grid, blk, 0, s, a);
+  hipLaunchKernelGGL(k_map_commit, dim3(1), dim3(64), 0, s, st->d_com, 1);
+  hipLaunchKernelGGL(k_map_rollback, dim3((unsigned)((m->cap + 255) / 256)), blk, 0, s, m->d_keys, m->d_vals, (unsigned)m->cap, m->d_st);
+  if (tab) hipLaunchKernelGGL((k_map_merge<MAP_ACCUM, MERGE_TABLE>), grid, blk, 0, s, a);
+  else hipLaunchKernelGGL((k_map_merge<MAP_ACCUM, MERGE_RAW>), grid, blk, 0, s, a);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));  // the device has decided
+  if (m->h_pub[2]) return REVO_OK;
+  u64 bad = 0;
+  if (!trusted) HIPCHECK(hipMemcpy(&bad, &m->d_st->bad, sizeof(u64), hipMemcpyDeviceToHost));
+  if (bad) return fail(REVO_ERR_INVALID_ARG, "voxel map: a record has count 0 or key bit 63 set (nothing merged)");
+  return fail(REVO_ERR_CAPACITY, "voxel map: the merge would take it past max_voxels (nothing merged)");
+}
+
+extern "C" int revo_map_merge_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int device_in, size_t points_dropped,
+                                  int32_t keyframes) {
+  if (!m) return fail(REVO_ERR_INVALID_ARG, "null map");
+  if (device_in != 0 && device_in != 1) return fail(REVO_ERR_INVALID_ARG, "device_in must be 0 or 1");
+  if (keyframes < 0) return fail(REVO_ERR_INVALID_ARG, "keyframes must be >= 0");
+  if (n == 0) return REVO_OK;
+  if (!src) return fail(REVO_ERR_INVALID_ARG, "null records");
+  if (device_in && ((uintptr_t)src & 15)) return fail(REVO_ERR_INVALID_ARG, "the device records are not 16-byte aligned");
+  if (n > MAP_MAX_CAP / 2) return fail(REVO_ERR_CAPACITY, "voxel map: a merge this large needs more than 2^31 table slots");
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  MapMergeK a{};
+  a.n = (unsigned)n;
+  a.dropped = (u64)points_dropped;
+  if (device_in) {
+    a.recs = (const ulonglong2*)src;
+    return merge_core(m, a, MERGE_RAW, n, false, keyframes);
+  }
+  bool valid = true;  // a bad record still goes to the device, which refuses the merge and counts it
+  for (size_t i = 0; i < n && valid; ++i) valid = src[i].count != 0 && !(src[i].key >> 63);
+  char* buf = nullptr;
+  HIPCHECK(hipMalloc((void**)&buf, sizeof(revo_map_voxel_raw) * n));
+  struct Free { char* p; ~Free() { hipFree(p); } } fr{buf};
+  HIPCHECK(hipMemcpyAsync(buf, src, sizeof(revo_map_voxel_raw) * n, hipMemcpyHostToDevice, s));
+  a.recs = (const ulonglong2*)buf;
+  const int rc = merge_core(m, a, MERGE_RAW, n, valid, keyframes);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) return fail(REVO_ERR_HIP, "hipStreamSynchronize failed");  // buf is read
+  return rc;
+}
+
+extern "C" int revo_map_merge(revo_map* dst, revo_map* src) {
+  if (!dst || !src) return fail(REVO_ERR_INVALID_ARG, "null map");
+  if (dst == src) return fail(REVO_ERR_INVALID_ARG, "a map cannot be merged into itself");
+  if (memcmp(&dst->voxel, &src->voxel, sizeof(float))) return fail(REVO_ERR_INVALID_ARG, "the maps' voxel edges differ");
+  if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
+  MapStats ss;  // waits for src: its table is complete, and its counters say what comes
+  { const int rc = read_stats(src, &ss); if (rc) return rc; }
+  if (ss.kfs > 0x7fffffffull) return fail(REVO_ERR_INVALID_ARG, "the source map's keyframe count does not fit");
+  MapMergeK a{};
+  a.skeys = src->d_keys; a.svals = src->d_vals; a.n = (unsigned)src->cap;
+  a.dropped = ss.drop;
+  const int rc = merge_core(dst, a, MERGE_TABLE, (size_t)ss.occ, true, (int)ss.kfs);
+  // maps of two contexts run on two streams: src's table must outlive the launch that reads it
+  if (dst->g.stream != src->g.stream && hipStreamSynchronize((hipStream_t)dst->g.stream) != hipSuccess && !rc)
+    return fail(REVO_ERR_HIP, "hipStreamSynchronize failed");
+  return rc;
 }
 
 // room for a call's views: descriptors, counters, z-buffer words (kept MAP_EMPTY), device outputs of a host-output call

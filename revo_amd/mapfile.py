@@ -1,0 +1,183 @@
+"""The voxel map as data: raw voxel records and the .rvm file (include/revo_hip.h revo_map_voxel_raw).
+
+Pure numpy: nothing here needs the GPU or the HIP library, so maps can be inspected, merged and converted anywhere.
+
+A record is one voxel's integer sums, 64 bytes little-endian: key (u64, (kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20),
+bit 63 clear), count (u64, >= 1), sum_q (3 x i64: x, y, z in 2^-20 m), sum_bgr (3 x u64: B, G, R).
+
+A .rvm file is a 64-byte header -- magic "REVOMAP1", u32 version 1, f32 voxel, i32 dense, u32 zero, u64 voxels,
+u64 points_integrated, u64 points_dropped, u64 keyframes, zero padding -- followed by `voxels` records in ascending key order.
+Equal maps give equal files.
+
+    python -m revo_amd.mapfile info FILE...            what each file holds
+    python -m revo_amd.mapfile merge OUT FILE...       the union of the files' maps (same voxel edge), without a GPU
+    python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
+"""
+import struct
+import sys
+
+import numpy as np
+
+RAW_DTYPE = np.dtype([("key", "<u8"), ("count", "<u8"), ("sum_q", "<i8", (3,)), ("sum_bgr", "<u8", (3,))])
+MAGIC = b"REVOMAP1"
+VERSION = 1
+HEADER_BYTES = 64
+_HEADER = struct.Struct("<8sIfiIQQQQ")  # 56 bytes, then zero padding
+HEADER_FIELDS = ("voxel", "dense", "voxels", "points_integrated", "points_dropped", "keyframes")
+
+assert RAW_DTYPE.itemsize == 64
+
+
+def as_records(a):
+    """Records from a structured array of RAW_DTYPE or from their bytes (bytes, or a uint8 array)."""
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(a, np.uint8)
+    a = np.asarray(a)
+    if a.dtype == RAW_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.dtype != np.uint8 or a.size % RAW_DTYPE.itemsize:
+        raise ValueError("voxel records are %d bytes each (RAW_DTYPE)" % RAW_DTYPE.itemsize)
+    return np.ascontiguousarray(a).reshape(-1).view(RAW_DTYPE)
+
+
+def check_records(rec, canonical=True):
+    """ValueError unless every record has count >= 1 and key bit 63 clear and (canonical) the keys strictly ascend."""
+    if len(rec) == 0:
+        return
+    if np.any(rec["count"] == 0):
+        raise ValueError("a voxel record has count 0")
+    if np.any(rec["key"] >> np.uint64(63)):
+        raise ValueError("a voxel record's key has bit 63 set")
+    if canonical:
+        k = rec["key"]
+        if np.any(k[1:] == k[:-1]):
+            raise ValueError("voxel records with the same key")
+        if np.any(k[1:] < k[:-1]):
+            raise ValueError("voxel records are not in ascending key order")
+
+
+def make_header(voxel, dense, records, points_dropped=0, keyframes=0):
+    records = as_records(records)
+    return {"voxel": float(np.float32(voxel)), "dense": int(dense), "voxels": len(records),
+            "points_integrated": int(records["count"].sum(dtype=np.uint64)), "points_dropped": int(points_dropped),
+            "keyframes": int(keyframes)}
+
+
+def pack(header, records):
+    """The bytes of a .rvm file.  The header's voxels and points_integrated must say what the records hold."""
+    rec = as_records(records)
+    check_records(rec)
+    if int(header["voxels"]) != len(rec):
+        raise ValueError("the header says %d voxels, there are %d records" % (header["voxels"], len(rec)))
+    if int(header["points_integrated"]) != int(rec["count"].sum(dtype=np.uint64)):
+        raise ValueError("the header's points_integrated is not the sum of the records' counts")
+    h = _HEADER.pack(MAGIC, VERSION, float(header["voxel"]), int(header["dense"]), 0, int(header["voxels"]),
+                     int(header["points_integrated"]), int(header["points_dropped"]), int(header["keyframes"]))
+    return h + bytes(HEADER_BYTES - len(h)) + rec.tobytes()
+
+
+def unpack(data):
+    """(header dict, records) of a .rvm file's bytes; ValueError if anything about them is wrong."""
+    data = bytes(data)
+    if len(data) < HEADER_BYTES:
+        raise ValueError("not a voxel map file: shorter than its header")
+    magic, version, voxel, dense, zero, voxels, pts, dropped, kfs = _HEADER.unpack_from(data)
+    if magic != MAGIC:
+        raise ValueError("not a voxel map file: bad magic")
+    if version != VERSION:
+        raise ValueError("voxel map file of version %d (this reader knows %d)" % (version, VERSION))
+    if len(data) != HEADER_BYTES + RAW_DTYPE.itemsize * voxels:
+        raise ValueError("voxel map file of %d bytes, its header says %d voxels" % (len(data), voxels))
+    if zero != 0 or any(data[_HEADER.size:HEADER_BYTES]) or dense not in (0, 1) or not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel map file with a malformed header")
+    rec = np.frombuffer(data, RAW_DTYPE, count=voxels, offset=HEADER_BYTES).copy()
+    check_records(rec)
+    if int(rec["count"].sum(dtype=np.uint64)) != pts:
+        raise ValueError("the header's points_integrated is not the sum of the records' counts")
+    return {"voxel": float(voxel), "dense": int(dense), "voxels": int(voxels), "points_integrated": int(pts),
+            "points_dropped": int(dropped), "keyframes": int(kfs)}, rec
+
+
+def write(path, header, records):
+    data = pack(header, records)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path
+
+
+def read(path):
+    with open(path, "rb") as f:
+        return unpack(f.read())
+
+
+def merge_records(a, b):
+    """The union of two record sets (keys may repeat, within and across them): per key the integer sums, ascending keys."""
+    rec = np.concatenate([as_records(a), as_records(b)])
+    check_records(rec, canonical=False)
+    keys, inv = np.unique(rec["key"], return_inverse=True)
+    out = np.zeros(len(keys), RAW_DTYPE)
+    out["key"] = keys
+    np.add.at(out["count"], inv, rec["count"])
+    np.add.at(out["sum_q"], inv, rec["sum_q"])
+    np.add.at(out["sum_bgr"], inv, rec["sum_bgr"])
+    return out
+
+
+def to_points(records, min_count=1):
+    """(xyz N x 3 float32, rgb N x 3 uint8 as R,G,B, count N uint32) of the records with count >= max(min_count, 1), in their
+    order -- what revo_map_extract gives: xyz = float32(float64(sum_q) / float64(count) * 2^-20), colour = (sum + count // 2)
+    // count."""
+    rec = as_records(records)
+    rec = rec[rec["count"] >= np.uint64(max(1, int(min_count)))]
+    cnt = rec["count"]
+    xyz = ((rec["sum_q"].astype(np.float64) / cnt.astype(np.float64)[:, None]) * 2.0 ** -20).astype(np.float32)
+    c = cnt[:, None]
+    bgr = ((rec["sum_bgr"] + c // np.uint64(2)) // c).astype(np.uint8)
+    return xyz.reshape(-1, 3), np.ascontiguousarray(bgr[:, ::-1]).reshape(-1, 3), cnt.astype(np.uint32)
+
+
+def merge_files(paths):
+    """(header, records) of the union of the files' maps: same voxel edge; dense of the first; counters added."""
+    header, rec = read(paths[0])
+    for p in paths[1:]:
+        h, r = read(p)
+        if np.float32(h["voxel"]).tobytes() != np.float32(header["voxel"]).tobytes():
+            raise ValueError("%s has voxels of %g m, %s of %g m" % (p, h["voxel"], paths[0], header["voxel"]))
+        rec = merge_records(rec, r)
+        header = dict(header, voxels=len(rec), points_integrated=header["points_integrated"] + h["points_integrated"],
+                      points_dropped=header["points_dropped"] + h["points_dropped"], keyframes=header["keyframes"] + h["keyframes"])
+    return header, rec
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    cmd, args = (argv[0], argv[1:]) if argv else (None, [])
+    try:
+        if cmd == "info" and args:
+            for p in args:
+                h, _ = read(p)
+                print("%s: %d voxels of %g m (%s clouds) from %d keyframes, %d points fused, %d points dropped"
+                      % (p, h["voxels"], h["voxel"], "dense" if h["dense"] else "edge", h["keyframes"], h["points_integrated"],
+                         h["points_dropped"]))
+            return 0
+        if cmd == "merge" and len(args) >= 2:
+            h, rec = merge_files(args[1:])
+            write(args[0], h, rec)
+            print("%s: %d voxels from %d files" % (args[0], len(rec), len(args) - 1))
+            return 0
+        if cmd == "ply" and len(args) in (1, 2):
+            from . import ply
+            out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
+            _, rec = read(args[0])
+            ply.write_voxel_ply(out, *to_points(rec))
+            print("%s: %d voxels -> %s" % (args[0], len(rec), out))
+            return 0
+    except (ValueError, OSError) as e:
+        print("mapfile: %s" % e)
+        return 1
+    print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | ply FILE [OUT.ply]")
+    return 2
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -104,6 +104,42 @@ def ranks_seen(world, device="cpu"):
     return [int(x) for x in out.cpu().tolist()], int(dist.get_world_size())
 
 
+def allmerge_map(vmap, world, group=None):
+    """Every rank's api.VoxelMap becomes the union of all ranks' maps: each rank exports its voxel records (integer sums, so
+    the union is exact and the same in any order), the ranks exchange sizes, counters and padded byte tensors with all_gather on
+    the live group, and every rank merges the other ranks' records in one all-or-nothing call.  gloo: host tensors; otherwise
+    (RCCL) device tensors through export_raw_into and a device merge_raw.  Afterwards all ranks hold the same map, byte for byte
+    the map one process would have built from all the keyframes.  world == 1 or no process group: nothing to do."""
+    import torch
+    import torch.distributed as dist
+    if world == 1 or not _group_live():
+        return vmap
+    rank, size = dist.get_rank(group), dist.get_world_size(group)
+    on_host = dist.get_backend(group) == "gloo"
+    info = vmap.info()
+    n = info["voxels"]
+    dev = torch.device("cpu") if on_host else torch.device("cuda", torch.cuda.current_device())
+    meta = torch.tensor([n, info["points_dropped"], info["keyframes"]], dtype=torch.int64, device=dev)
+    metas = [torch.empty_like(meta) for _ in range(size)]
+    dist.all_gather(metas, meta, group=group)
+    metas = [[int(x) for x in m.cpu().tolist()] for m in metas]
+    pad = 64 * max(1, max(m[0] for m in metas))  # one size for every rank's tensor
+    mine = torch.zeros(pad, dtype=torch.uint8, device=dev)
+    if on_host:
+        mine[:64 * n] = torch.from_numpy(vmap.export_raw().view(np.uint8).copy())
+    elif vmap.export_raw_into(mine) != n:
+        raise RuntimeError("the map changed during allmerge_map")
+    parts = [torch.empty_like(mine) for _ in range(size)]
+    dist.all_gather(parts, mine, group=group)
+    others = [r for r in range(size) if r != rank and metas[r][0]]
+    dropped = sum(metas[r][1] for r in range(size) if r != rank)
+    kfs = sum(metas[r][2] for r in range(size) if r != rank)
+    if others:
+        rec = torch.cat([parts[r][:64 * metas[r][0]] for r in others])
+        vmap.merge_raw(rec.numpy() if on_host else rec, dropped, kfs)
+    return vmap
+
+
 def records_to_poses(buf, n):
     """uint8 numpy/bytes of n records -> (R [n,3,3] row-major, T [n,3], err [n])."""
     a = np.frombuffer(bytes(buf), dtype=np.float32).reshape(n, RECORD_BYTES // 4)

@@ -9,6 +9,9 @@ next one) and writes the same poses_<dataset>.txt files; the PNG decoders are sp
 --map VOXEL fuses every keyframe into a world-frame voxel map of that edge (metres) on the GPU (api.VoxelMap; the settings'
 DO_GENERATE_DENSE_PCL picks dense or edge clouds) and writes map_<dataset>.ply next to the pose file: sequential or with
 --streams, the same file either way.
+--map-save FILE (with --map) also writes the finished map's integer sums as a .rvm file (revo_amd/mapfile.py) that
+api.VoxelMap.load continues and `python -m revo_amd.mapfile` merges; FILE with _<dataset> in front of its extension with
+--streams or more than one dataset.
 --map-views DIR (with --map) renders the finished map from the estimated pose of every keyframe, or with --map-views-every K
 of every K-th tracked frame, on the GPU (api.VoxelMap.render) and writes a TUM-layout data set into DIR (tum.write_map_views:
 rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset."""
@@ -23,7 +26,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--map VOXEL [--map-views DIR [--map-views-every K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--map VOXEL [--map-save FILE] [--map-views DIR [--map-views-every K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -43,6 +46,14 @@ def main(argv=None):
         argv = argv[:i] + argv[i + 2:]
         if not (np.isfinite(map_voxel) and map_voxel > 0):
             print("--map needs a positive voxel edge in metres")
+            return 2
+    map_save = None  # the finished map's integer sums as a .rvm file (mapfile): it can be loaded, continued and merged
+    if "--map-save" in argv:
+        i = argv.index("--map-save")
+        map_save = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+        if map_voxel is None:
+            print("--map-save writes the voxel map: it needs --map VOXEL")
             return 2
     views_dir, views_every = None, 0  # tum.write_map_views of the finished map: every keyframe's pose, or every K-th frame's
     if "--map-views-every" in argv:
@@ -93,7 +104,7 @@ def main(argv=None):
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
         return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel,
-                            views_dir, views_every)
+                            views_dir, views_every, map_save)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
@@ -121,7 +132,7 @@ def main(argv=None):
         print("-----VO Report-----\nFrames Tracked: %d\nKeyframes Tracked: %d\nframes/s (incl. PNG decode, %s): %.1f"
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
         if vmap is not None:
-            _save_map(vmap, name)
+            _save_map(vmap, name, _rvm_path(map_save, name, len(io["datasets"]) > 1))
             if views_dir is not None:
                 _save_views(vmap, os.path.join(views_dir, name) if len(io["datasets"]) > 1 else views_dir,
                             drv.poses, [kf for _, kf in res], views_every, io["depth_scale_factor"])
@@ -132,9 +143,19 @@ def main(argv=None):
     return 0
 
 
-def _save_map(vmap, name):
+def _rvm_path(map_save, name, per_dataset):
+    """--map-save FILE: FILE itself for one sequential dataset, else FILE with _<dataset> in front of its extension."""
+    if map_save is None or not per_dataset:
+        return map_save
+    stem, ext = os.path.splitext(map_save)
+    return "%s_%s%s" % (stem, name, ext)
+
+
+def _save_map(vmap, name, rvm=None):
     info = vmap.info()
     path = vmap.save_ply("map_%s.ply" % name)
+    if rvm is not None:
+        print("Map file: %s" % vmap.save(rvm))
     print("Map: %d voxels of %g m from %d keyframes, %d points fused, %d points dropped (outside +-2048 m or the key range)%s -> %s"
           % (info["voxels"], vmap.voxel, info["keyframes"], info["points_integrated"], info["points_dropped"],
              (", %d keyframes refused (max_voxels)" % info["keyframes_rejected"]) if info["keyframes_rejected"] else "", path))
@@ -165,7 +186,7 @@ def _report_ate(folder, poses):
 
 
 def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
-                 map_voxel=None, views_dir=None, views_every=0):
+                 map_voxel=None, views_dir=None, views_every=0, map_save=None):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -212,7 +233,7 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
         total += len(r)
         print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
         if r.map is not None:
-            _save_map(r.map, name)
+            _save_map(r.map, name, _rvm_path(map_save, name, True))
             if views_dir is not None:
                 _save_views(r.map, os.path.join(views_dir, name), r.poses, [kf for _, kf in r], views_every,
                             io["depth_scale_factor"])
