@@ -358,6 +358,54 @@ typedef struct revo_stage_times {
 } revo_stage_times;
 int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, const float* d_depth, int reps, revo_stage_times* out);
 
+/* ---- the information matrix and covariance of tracked poses (new) --------------------------------------
+ * What the tracker minimises at a pose (R, T) of one level is sum_i w_i r_i^2 over the GOOD points of the current
+ * frame (optimizer.cpp:74-191); its normal equations are H x = -g with H = sum_i w_i v_i v_i^T, g = sum_i v_i (r_i w_i)
+ * (calculateWarpUpdate + LGS6::update, optimizer.cpp:192-234, LGSX.h:392-398).  H is the Gauss-Newton information
+ * matrix of the relative pose, up to the residual variance; revo_pair_info_covariance turns it into a covariance.
+ * Unknown order is LGS6's: translation 0-2, rotation 3-5, the tangent parameters of the increment the LM solves for
+ * (optimizer.cpp:258-266): the update is T_new = exp(x) * T_old -- applied on the LEFT, i.e. in the KEYFRAME's frame
+ * (se3_exp_mul in revo_amd/csrc/revo_track.hip, called with the accepted pose as its right factor).
+ * The per-point terms are exactly those of exact-sums mode (revo_ctx_set_exact_sums): the reference's own
+ * float terms (v_a*v_c)*w, v_a*(r*w), (r*r)*w, r*r with v[3], v[4] evaluated in double and rounded once.  Each of the
+ * 29 sums is the float nearest the exact sum of its float terms (DESIGN 4.1's midpoint caveat applies) -- whatever
+ * the context's exact_sums flag, the batch size, the grid shape or the stream.  Consequence: in exact-sums mode
+ * revo_optimizer_eval's A[a][c] equals H/(float)good and its b[a] equals -(g/(float)good), bit for bit. */
+typedef struct revo_pair_info {      /* 192 bytes, little-endian, no padding holes */
+  float   H[21];    /* upper triangle, row-major (00,01,..,05,11,..,55) of sum_i (v_a*v_c)*w over the good points */
+  float   g[6];     /* sum_i v_a*(r*w)   (LGS6's b is minus this, LGSX.h:392-398)                                   */
+  float   sum_w;    /* sum_i (r*r)*w                                                                               */
+  float   sum_u;    /* sum_i r*r                                                                                   */
+  int32_t good, bad;/* Optimizer::ResidualInfo counts at this pose and level                                       */
+  int32_t level;
+  int32_t flags;    /* bit0: no evaluation (pose not finite / not orthogonal, or the source record had bit1 or bit3):
+                       the record is then all zero except level, flags, R and T                                    */
+  float   R[9], T[3]; /* the pose the sums were taken at (curr -> keyframe, column-major), copied from the input   */
+  int32_t reserved[3]; /* zero */
+} revo_pair_info;
+
+/* The level-lvl information of all n_pairs pairs of a batch in ONE launch.  Exactly one of d_results (n_pairs records in
+ * DEVICE memory, e.g. the ones the batch's grid just wrote; the kernel reads the poses itself, a record with flag bit1 or
+ * bit3 gives flags bit0) and h_RT (n_pairs x 12 HOST floats: R column-major, T) is non-NULL, else REVO_ERR_INVALID_ARG.  A host
+ * pose that is not finite or not orthogonal (the test revo_tracker_track_frames applies) gives that pair flags bit0; the
+ * call still returns REVO_OK.  d_info: n_pairs records in device memory, 16-byte aligned.  lvl outside the pyramid:
+ * REVO_ERR_LEVEL.  Asynchronous on `stream` (NULL = the batch's own).  Like revo_batch_track_only it first runs, on its
+ * stream, whatever the last build left pending for the tracker (never the keyframe-role frames' edge lists) and orders
+ * itself behind the batch's last tracker grid; the batch's next build waits for it.  It reads what the tracker reads: the
+ * current frames' tile-ordered edge lists and the keyframes' distance transforms.  On a revo_pipeline_batch batch, call it
+ * with the after_grid_stream of the step's submit: the information of step t rides in the after-grid slot. */
+int revo_batch_pair_info(revo_batch* b, const revo_pair_result* d_results, const float* h_RT, int lvl,
+                         revo_pair_info* d_info, void* stream);
+/* One pair, host output, waits.  REVO_ERR_NOT_KEYFRAME / REVO_ERR_NOT_ORTHOGONAL / REVO_ERR_LEVEL as the other single-pair
+ * calls; a T that is not finite is REVO_ERR_INVALID_ARG. */
+int revo_tracker_pair_info(revo_ctx* ctx, const revo_pyr* ref, const revo_pyr* curr, const float R_colmajor[9],
+                           const float T[3], int lvl, revo_pair_info* out);
+/* Host only, touches no device.  H widened to double; *sigma2 = sum_w / (good - 6) (the weighted residual variance at 6
+ * estimated parameters); cov (6x6, symmetric, row == column major) = sigma2 * H^-1 by a double Cholesky factorisation,
+ * symmetrised.  sigma2 may be NULL.  REVO_ERR_INVALID_ARG, nothing written: flags bit0, good <= 6, or a pivot that is not
+ * positive beyond rounding (pivot <= 64 * 2^-52 * H[j][j]: a rank-deficient system). */
+int revo_pair_info_covariance(const revo_pair_info* info, double cov[36], double* sigma2);
+
 /* ---- host-buffer batches: what a producer like IOWrapperRGBD::readNextFrame hands over ------------ */
 
 /* One frame-pair in HOST memory, as the reference's producer thread holds it after cv::imread
@@ -525,6 +573,15 @@ int revo_vo_num_keyframes(const revo_vo* vo);
  * borrowed: valid until the next revo_vo_track_next / revo_vo_destroy. */
 int revo_vo_keyframe(const revo_vo* v, revo_pyr** kf_out, float T_w_kf[16]);
 
+/* Off by default; off, revo_vo_track_next enqueues exactly what it enqueues without this option.  On: every reported frame's
+ * level-0 revo_pair_info is taken at its FINAL pose against the keyframe it was reported against (after a keyframe change:
+ * the re-track's pose and the new keyframe), enqueued behind that frame's tracker launch, and available from
+ * revo_vo_last_pair_info once revo_vo_track_next has returned (*kf_timestamp, may be NULL: that keyframe's time stamp).
+ * The first frame of a sequence IS the keyframe: its record has flags bit0 (identity pose).  Poses do not depend on the option.
+ * revo_vo_last_pair_info: REVO_ERR_INVALID_ARG while the option is off or before the first frame. */
+int revo_vo_set_pair_info(revo_vo* vo, int on);
+int revo_vo_last_pair_info(const revo_vo* vo, revo_pair_info* out, double* kf_timestamp);
+
 /* ---------------------------------------------------------------------------
  * Many independent sequential-VO streams in lockstep (revo_vo_multi).
  * Each stream is one REVO::start (system.cpp:84-305) with its own keyframe, past clouds and
@@ -562,6 +619,12 @@ int revo_vo_multi_reset(revo_vo_multi* m, int stream);          /* new sequence 
 int revo_vo_multi_num_keyframes(const revo_vo_multi* m, int stream);
 /* The stream's current keyframe (borrowed, valid until the next revo_vo_multi_step) and its pose in the world. */
 int revo_vo_multi_keyframe(const revo_vo_multi* m, int stream, revo_pyr** kf, float T_w_kf[16]);
+
+/* revo_vo_set_pair_info / revo_vo_last_pair_info per stream: ONE k_pair_info launch per step, on the tracker stream behind the
+ * step's grid, covers every stream the step tracks; revo_vo_multi_pair_info returns the record of the stream's last REPORTED
+ * frame (per stream the same bytes as a revo_vo's when the poses agree).  Off by default. */
+int revo_vo_multi_set_pair_info(revo_vo_multi* m, int on);
+int revo_vo_multi_pair_info(const revo_vo_multi* m, int stream, revo_pair_info* out, double* kf_timestamp);
 
 /* Device frames for revo_vo_multi: revo_vo_multi_submit with DEVICE pointers (on the context's device), e.g. the output of
  * revo_png_decode_submit.  The build stream waits for `producer_stream` (an event); the frames are copied device-to-device

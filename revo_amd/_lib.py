@@ -8,7 +8,7 @@ import os
 import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
-                       PairResult, MAX_LEVELS)
+                       PairResult, PairInfo, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -167,6 +167,13 @@ def lib():
     L.revo_comm_allgather_records.argtypes = [vp, vp, vp, C.c_int, vp]
     L.revo_pipeline_set_comm.argtypes = [vp, vp, C.c_int, vp, C.c_int]
     L.revo_pipeline_flush_comm.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.revo_batch_pair_info.argtypes = [vp, vp, f32p, C.c_int, vp, vp]
+    L.revo_tracker_pair_info.argtypes = [vp, vp, vp, f32p, f32p, C.c_int, C.POINTER(PairInfo)]
+    L.revo_pair_info_covariance.argtypes = [C.POINTER(PairInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.revo_vo_set_pair_info.argtypes = [vp, C.c_int]
+    L.revo_vo_last_pair_info.argtypes = [vp, C.POINTER(PairInfo), C.POINTER(C.c_double)]
+    L.revo_vo_multi_set_pair_info.argtypes = [vp, C.c_int]
+    L.revo_vo_multi_pair_info.argtypes = [vp, C.c_int, C.POINTER(PairInfo), C.POINTER(C.c_double)]
     _lib = L
     return L
 

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairIn, MapInfo, MapView,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -517,6 +517,14 @@ class TrackerNew:
         self.last_evals, self.last_info = evals, info
         return status.value, Rc.reshape(3, 3).T.copy(), Tc, err.value
 
+    def pairInfo(self, refFrame, currFrame, R, T, lvl):
+        """-> PairInfo: the sums of the pair's normal equations at pose (R, T) of level lvl (revo_tracker_pair_info)."""
+        Rc, Tc = _cm3(R), np.ascontiguousarray(T, np.float32).reshape(3)
+        out = PairInfo()
+        check(_lib.lib().revo_tracker_pair_info(self._cam._h, refFrame._h, currFrame._h, _p(Rc, f32p), _p(Tc, f32p), lvl,
+                                                C.byref(out)))
+        return out
+
     def assessTrackingQuality(self, estimatedPose, currFrame, return_hist=False):
         Mc = _cm4(estimatedPose)
         st = C.c_int()
@@ -594,6 +602,23 @@ class BatchTracker:
     def track_only(self, d_results, init_RT=None, stream=None):
         keep, ptr = self._init(init_RT)
         check(_lib.lib().revo_batch_track_only(self._h, ptr, d_results, stream))
+
+    def pair_info(self, d_results=None, RT=None, lvl=0, d_info=None, stream=None):
+        """revo_batch_pair_info: the level-lvl PairInfo of every pair in one launch, at the poses of d_results (raw device
+        pointer to n_pairs PairResult records, e.g. the ones track_only just wrote) or of RT (host, [n_pairs, 12]: R
+        column-major, T) -- exactly one of the two.  d_info: raw device pointer to n_pairs * 192 bytes, 16-byte aligned; the call
+        only enqueues.  d_info=None: a buffer of the call's own, and the records come back as a list of PairInfo (waits)."""
+        keep, ptr = self._init(RT)
+        own = None
+        if d_info is None:
+            import torch
+            own = torch.empty(self.n_pairs * C.sizeof(PairInfo), dtype=torch.uint8, device="cuda")
+            d_info = own.data_ptr()
+        check(_lib.lib().revo_batch_pair_info(self._h, d_results, ptr, lvl, d_info, stream))
+        if own is None:
+            return None
+        check(_lib.lib().revo_batch_sync(self._h, stream))
+        return pair_infos_from_buffer(own.cpu().numpy().tobytes(), self.n_pairs)
 
     def sync(self, stream=None):
         """Waits for the stream and for the batch's last tracker grid (on whichever stream it ran) and checks its records'
@@ -690,6 +715,14 @@ class Pipeline:
         check(_lib.lib().revo_pipeline_batch(self._h, ticket, C.byref(b)))
         check(_lib.lib().revo_batch_frame(b, f, C.byref(h)))
         return ImgPyramidRGBD(settings, self._cam, _handle=h, _owned=False)
+
+    def pair_info(self, ticket, stream, d_info, d_results=None, RT=None, lvl=0):
+        """The PairInfo records of step `ticket`, enqueued on `stream` -- pass the stream submit() returned: the launch then rides
+        in the step's after-grid slot (revo_batch_pair_info on revo_pipeline_batch).  d_results: the step's device records."""
+        keep, ptr = BatchTracker._init(RT)
+        b = vp()
+        check(_lib.lib().revo_pipeline_batch(self._h, ticket, C.byref(b)))
+        check(_lib.lib().revo_batch_pair_info(b, d_results, ptr, lvl, d_info, stream))
 
     def time_tracker(self, every_n):
         check(_lib.lib().revo_pipeline_time_tracker(self._h, every_n))
@@ -829,3 +862,19 @@ def results_from_buffer(buf, n):
                         err=r.err, good=r.good, bad=r.bad, status=r.status,
                         evals=np.array(r.evals, np.int32), flags=r.flags, n_pts0=r.n_pts0))
     return out
+
+
+def pair_infos_from_buffer(buf, n):
+    """n PairInfo records out of a bytes-like object (e.g. a device buffer copied to the host)."""
+    arr = (PairInfo * n).from_buffer_copy(bytes(buf)[:n * C.sizeof(PairInfo)])
+    return [arr[i] for i in range(n)]
+
+
+def pair_covariance(info):
+    """-> (cov [6, 6] float64, sigma2): revo_pair_info_covariance -- sigma2 = sum_w / (good - 6), cov = sigma2 * H^-1 (translation
+    0-2, rotation 3-5, the left-multiplied increment's tangent parameters).  RevoError(REVO_ERR_INVALID_ARG) when the record
+    carries no evaluation, has good <= 6 or a rank-deficient H."""
+    cov = np.empty(36, np.float64)
+    s2 = C.c_double()
+    check(_lib.lib().revo_pair_info_covariance(C.byref(info), cov.ctypes.data_as(C.POINTER(C.c_double)), C.byref(s2)))
+    return cov.reshape(6, 6), s2.value

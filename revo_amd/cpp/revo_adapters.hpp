@@ -301,6 +301,17 @@ class Optimizer {  // optimizer.h:114-186
           "Optimizer::trackFrames");
     return err;
   }
+  // New: the sums of the pair's normal equations at (R, T) of level lvl (revo_tracker_pair_info): the 6x6 information
+  // matrix of the relative pose currFrame -> refFrame; revo_pair_info_covariance turns the record into a covariance.
+  template <class M3, class V3>
+  revo_pair_info pairInfo(const std::shared_ptr<ImgPyramidRGBD>& refFrame, const std::shared_ptr<ImgPyramidRGBD>& currFrame,
+                          const M3& R, const V3& T, int lvl) {
+    revo_pair_info info;
+    if (!cam_) cam_ = refFrame->cameraPyr;
+    check(revo_tracker_pair_info(cam_->ctx(), refFrame->handle(), currFrame->handle(), R.data(), T.data(), lvl, &info),
+          "Optimizer::pairInfo");
+    return info;
+  }
 
  private:
   OptimizerSettings mSettings;

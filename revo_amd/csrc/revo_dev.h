@@ -192,3 +192,26 @@ struct CopySeg { const void* src; void* dst; size_t bytes; };
 void launch_vote_multi(const PyrGeom& g, int lvl, int n, const VoteDesc* d_descs, unsigned seq_val, hipStream_t s);
 void launch_copy_cloud_multi(int n, const CloudCopyDesc* d_descs, hipStream_t s);
 void launch_copy_segments(int n, const CopySeg* d_segs, hipStream_t s);
+
+// ---- k_pair_info (revo_info.hip): the 6x6 information matrix of tracked poses, one launch for n pairs ----
+#define INFO_THREADS 256      // four waves per workgroup
+#define INFO_CHUNK 1024       // points per chunk: a workgroup takes the chunks g, g + G, g + 2G, ... of its pair's level
+#define INFO_MAX_GROUPS 32    // G, workgroups per pair, is at most this (info_groups)
+// per-workgroup partials: 64 doubles (29 of 32 double-double slots in use: heads, then tails) and the good count
+#define INFO_PART_DOUBLES 64
+struct InfoParams {  // one level's camera and the optimizer's per-point constants
+  float fx, fy, cx, cy;
+  int w, h;
+  float edge_distance, huber_edge;
+  int use_edge_filter, level;
+};
+// workgroups per pair for a level of npix pixels: one per 8 chunks' worth of PIXELS (about one chunk of edge points each)
+static inline int info_groups(int npix) {
+  const int g = (npix + 8 * INFO_CHUNK - 1) / (8 * INFO_CHUNK);
+  return g < 1 ? 1 : (g > INFO_MAX_GROUPS ? INFO_MAX_GROUPS : g);
+}
+// d_pose: n records of pose_stride 32-bit words each: R (9, column-major) at word 0, T at word 9 and, at flag_word, a flag word
+// of which bits 1 and 3 mean "no pose" (revo_pair_result: stride 24, flag word 22).  d_part: n * INFO_MAX_GROUPS *
+// INFO_PART_DOUBLES doubles, d_cnt: n * INFO_MAX_GROUPS ints, d_ticket: n words padded to 16 bytes (zeroed here, on s).
+void launch_pair_info(const PairDesc* d_descs, const void* d_pose, int pose_stride, int flag_word, const InfoParams& prm,
+                      int n_pairs, double* d_part, int* d_cnt, unsigned* d_ticket, revo_pair_info* d_out, hipStream_t s);

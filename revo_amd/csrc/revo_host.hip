@@ -93,6 +93,17 @@ struct FrameSet {
   bool has_ready = false, has_free = false, has_free2 = false;
 };
 
+// Scratch of k_pair_info launches for up to n pairs: created on first use by whoever owns it (a batch, the
+// context's single-pair calls, a revo_vo_multi handle).  One launch at a time per workspace, ordered by the owner's stream.
+struct InfoWs {
+  int n = 0;
+  PairDesc* h_descs = nullptr; PairDesc* d_descs = nullptr;
+  float* h_rt = nullptr; float* d_rt = nullptr;        // n x 16: R (9), T (3), a zero flag word, padding
+  double* d_part = nullptr; int* d_cnt = nullptr; unsigned* d_ticket = nullptr;
+  revo_pair_info* d_out = nullptr; revo_pair_info* h_out = nullptr;
+  hipEvent_t ev_up = nullptr, ev_done = nullptr;
+};
+
 struct Past {  // one entry of mPastPcl / mPastWorldPoses / mPastTimeStamps (tracker.h:92-95)
   float4* d_pts; int* d_n; int n; float T_w[16]; double ts;
   size_t cap;  // points the buffer holds
@@ -154,6 +165,7 @@ struct revo_ctx {
   unsigned long long jobs_submitted = 0;
   // coloured point cloud (generateColoredPcl), allocated on first use
   char* d_pcl = nullptr; float* d_pcl_out; uint8_t* d_pcl_clr[2]; int* d_pcl_chunk; unsigned* d_pcl_mask; int* d_pcl_total;
+  InfoWs* info_ws = nullptr;  // revo_tracker_pair_info, allocated on first use
 };
 
 struct revo_pyr {
@@ -190,6 +202,7 @@ struct revo_batch {
   hipEvent_t tev0 = nullptr, tev1 = nullptr;       // (revo_batch_time_next_grid_) recorded directly around the NEXT tracker grid, then cleared
   const revo_pair_result* last_results = nullptr;  // device records of the last track launch (revo_batch_sync decodes their flags)
   revo_pair_result* h_flags = nullptr;             // pinned scratch for that
+  InfoWs* info_ws = nullptr;                       // revo_batch_pair_info, allocated on first use
 };
 
 // ---------------------------------------------------------------- geometry --
@@ -544,6 +557,7 @@ static int batch_wait_tracker(revo_batch* b, hipStream_t s);
 
 // ------------------------------------------------------------------ context --
 static void ctx_free(revo_ctx* c);
+static void infows_destroy(InfoWs* w);
 extern "C" int revo_ctx_create(int device, const revo_pyr_settings* pyr, const revo_opt_settings* opt,
                                const revo_tracker_settings* trk, revo_ctx** out) {
   if (!pyr || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
@@ -629,6 +643,7 @@ static void ctx_free(revo_ctx* c) {
   hipHostFree(c->h_desc); hipHostFree(c->h_res); hipHostFree(c->h_eval); hipHostFree(c->h_seq); hipFree(c->d_mail);
   hipFree(c->d_marks); hipFree(c->d_hist8); hipHostFree(c->h_hist8); hipFree(c->d_vote_done);
   hipFree(c->d_pcl);
+  infows_destroy(c->info_ws);
   if (c->stream) hipStreamDestroy(c->stream);
   (void)hipGetLastError();  // a partially built context frees null handles on purpose
   delete c;
@@ -1530,6 +1545,7 @@ extern "C" void revo_batch_destroy(revo_batch* b) {
   hipSetDevice(b->ctx->device);
   if (b->stream) hipStreamSynchronize(b->stream);
   hipHostFree(b->h_descs); hipHostFree(b->h_flags); hipFree(b->d_descs); hipFree(b->d_mail);
+  infows_destroy(b->info_ws);
   if (b->ev0) hipEventDestroy(b->ev0);
   if (b->ev1) hipEventDestroy(b->ev1);
   if (b->ev_upload) hipEventDestroy(b->ev_upload);
@@ -1707,6 +1723,119 @@ extern "C" int revo_batch_sync(revo_batch* b, void* stream) {
         return fail(REVO_ERR_HIP, "tracker: pair " + std::to_string(i) + ": the workgroups of the pair could not exchange "
                     "partial sums in time (device shared with another process?) -- its pose is not valid");
   }
+  return REVO_OK;
+}
+
+// ------------------------------------------------- information matrices --
+static void infows_destroy(InfoWs* w) {
+  if (!w) return;
+  hipHostFree(w->h_descs); hipFree(w->d_descs); hipHostFree(w->h_rt); hipFree(w->d_rt);
+  hipFree(w->d_part); hipFree(w->d_cnt); hipFree(w->d_ticket); hipFree(w->d_out); hipHostFree(w->h_out);
+  if (w->ev_up) hipEventDestroy(w->ev_up);
+  if (w->ev_done) hipEventDestroy(w->ev_done);
+  (void)hipGetLastError();
+  delete w;
+}
+// own_out: the workspace also holds n output records on the device and their pinned host copy
+static int infows_create(int n, bool own_out, InfoWs** out) {
+  InfoWs* w = new InfoWs();
+  w->n = n;
+  struct Guard { InfoWs* w; ~Guard() { infows_destroy(w); } } guard{w};
+  HIPCHECK(hipHostMalloc((void**)&w->h_descs, sizeof(PairDesc) * n));
+  HIPCHECK(hipMalloc((void**)&w->d_descs, sizeof(PairDesc) * n));
+  HIPCHECK(hipHostMalloc((void**)&w->h_rt, sizeof(float) * 16 * n));
+  HIPCHECK(hipMalloc((void**)&w->d_rt, sizeof(float) * 16 * n));
+  HIPCHECK(hipMalloc((void**)&w->d_part, sizeof(double) * INFO_PART_DOUBLES * INFO_MAX_GROUPS * (size_t)n));
+  HIPCHECK(hipMalloc((void**)&w->d_cnt, sizeof(int) * INFO_MAX_GROUPS * (size_t)n));
+  HIPCHECK(hipMalloc((void**)&w->d_ticket, align_up(sizeof(unsigned) * (size_t)n, 16)));
+  if (own_out) {
+    HIPCHECK(hipMalloc((void**)&w->d_out, sizeof(revo_pair_info) * n));
+    HIPCHECK(hipHostMalloc((void**)&w->h_out, sizeof(revo_pair_info) * n));
+  }
+  HIPCHECK(hipEventCreateWithFlags(&w->ev_up, hipEventDisableTiming));
+  HIPCHECK(hipEventCreateWithFlags(&w->ev_done, hipEventDisableTiming));
+  guard.w = nullptr;
+  *out = w;
+  return REVO_OK;
+}
+static InfoParams info_params(const TrackParams& tp, int lvl) {
+  InfoParams ip;
+  ip.fx = tp.cam[lvl].fx; ip.fy = tp.cam[lvl].fy; ip.cx = tp.cam[lvl].cx; ip.cy = tp.cam[lvl].cy;
+  ip.w = tp.cam[lvl].w; ip.h = tp.cam[lvl].h;
+  ip.edge_distance = tp.edge_distance[lvl]; ip.huber_edge = tp.huber_edge;
+  ip.use_edge_filter = tp.use_edge_filter; ip.level = lvl;
+  return ip;
+}
+// n host poses (12 floats each) -> the workspace's device copy, on s
+static int infows_upload_rt(InfoWs* w, int n, const float* h_RT, hipStream_t s) {
+  HIPCHECK(hipEventSynchronize(w->ev_up));  // the previous upload has read h_rt
+  for (int i = 0; i < n; ++i) {
+    memcpy(w->h_rt + 16 * i, h_RT + 12 * i, sizeof(float) * 12);
+    memset(w->h_rt + 16 * i + 12, 0, sizeof(float) * 4);
+  }
+  HIPCHECK(hipMemcpyAsync(w->d_rt, w->h_rt, sizeof(float) * 16 * n, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(w->ev_up, s));
+  return REVO_OK;
+}
+
+extern "C" int revo_batch_pair_info(revo_batch* b, const revo_pair_result* d_results, const float* h_RT, int lvl,
+                                    revo_pair_info* d_info, void* stream) {
+  if (!b || !d_info) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if ((d_results != nullptr) == (h_RT != nullptr)) return fail(REVO_ERR_INVALID_ARG, "exactly one of d_results and h_RT must be given");
+  if ((uintptr_t)d_info % 16) return fail(REVO_ERR_INVALID_ARG, "d_info is not 16-byte aligned");
+  revo_ctx* c = b->ctx;
+  if (lvl < 0 || lvl >= c->geom.n_levels) return fail(REVO_ERR_LEVEL, "level out of range");
+  HIPCHECK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+  if (!b->info_ws) {
+    int rc = infows_create(b->n_pairs, false, &b->info_ws);
+    if (rc) return rc;
+    // the plane pointers of a batch's descriptors never change (the poses in them are not read here)
+    HIPCHECK(hipMemcpy(b->info_ws->d_descs, b->h_descs, sizeof(PairDesc) * b->n_pairs, hipMemcpyHostToDevice));
+  }
+  InfoWs* w = b->info_ws;
+  { int rc = batch_wait_tracker(b, s); if (rc) return rc; }   // the grid that wrote d_results, and an earlier launch on this workspace
+  if (h_RT) { int rc = infows_upload_rt(w, b->n_pairs, h_RT, s); if (rc) return rc; }
+  { int rc = batch_wait_build(b, s); if (rc) return rc; }
+  { int rc = run_pending_edt(c, b->fs, s); if (rc) return rc; }  // what the tracker needs; never the even views' lazy work
+  InfoParams ip;
+  { std::lock_guard<std::mutex> lk(c->mu); ip = info_params(c->tp, lvl); }
+  launch_pair_info(w->d_descs, h_RT ? (const void*)w->d_rt : (const void*)d_results, h_RT ? 16 : (int)(sizeof(revo_pair_result) / 4),
+                   h_RT ? 12 : (int)(offsetof(revo_pair_result, flags) / 4), ip, b->n_pairs, w->d_part, w->d_cnt, w->d_ticket, d_info, s);
+  HIPCHECK(hipGetLastError());
+  return batch_mark_tracker(b, s);  // the batch's next build (and its next grid on another stream) waits for this launch too
+}
+
+// one launch for one pair of pyramids on the context's tracker stream, result in w->h_out[0]; waits
+static int pair_info_single(revo_ctx* c, const revo_pyr* ref, const revo_pyr* curr, const float* R, const float* T, int lvl) {
+  if (!c->info_ws) { int rc = infows_create(1, true, &c->info_ws); if (rc) return rc; }
+  InfoWs* w = c->info_ws;
+  hipStream_t s = c->stream;
+  { int rc = wait_ready(c, ref); if (rc) return rc; rc = wait_ready(c, curr); if (rc) return rc; }
+  float rt[12];
+  memcpy(rt, R, sizeof(float) * 9); memcpy(rt + 9, T, sizeof(float) * 3);
+  { int rc = infows_upload_rt(w, 1, rt, s); if (rc) return rc; }
+  fill_desc(w->h_descs, ref, curr, R, T);  // (the previous call waited for its stream: nothing reads h_descs any more)
+  HIPCHECK(hipMemcpyAsync(w->d_descs, w->h_descs, sizeof(PairDesc), hipMemcpyHostToDevice, s));
+  launch_pair_info(w->d_descs, w->d_rt, 16, 12, info_params(c->tp, lvl), 1, w->d_part, w->d_cnt, w->d_ticket, w->d_out, s);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(w->h_out, w->d_out, sizeof(revo_pair_info), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+extern "C" int revo_tracker_pair_info(revo_ctx* c, const revo_pyr* ref, const revo_pyr* curr, const float R[9], const float T[3],
+                                      int lvl, revo_pair_info* out) {
+  int rc = check_pair(c, ref, curr);
+  if (rc) return rc;
+  if (!R || !T || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (lvl < 0 || lvl >= c->geom.n_levels) return fail(REVO_ERR_LEVEL, "level out of range");
+  for (int i = 0; i < 3; ++i) if (!std::isfinite(T[i])) return fail(REVO_ERR_INVALID_ARG, "T is not finite");
+  HIPCHECK(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  rc = pair_info_single(c, ref, curr, R, T, lvl);
+  if (rc) return rc;
+  if (c->info_ws->h_out[0].flags & 1) return fail(REVO_ERR_NOT_ORTHOGONAL, "R is not orthogonal (Sophus::SO3 precondition)");
+  *out = c->info_ws->h_out[0];
   return REVO_OK;
 }
 
@@ -2068,6 +2197,7 @@ struct revo_mdev {
   std::vector<Past> past_pool;
   size_t cloud_cap = 0;
   hipEvent_t ev_trk = nullptr, ev_vdesc = nullptr, ev_cdesc = nullptr, ev_segs = nullptr, ev_h2d = nullptr, ev_prod = nullptr;
+  InfoWs* info_ws = nullptr;  // revo_mdev_pair_info_*, allocated on first use
 };
 
 extern "C" void revo_mdev_destroy_(revo_mdev* m) {
@@ -2084,6 +2214,7 @@ extern "C" void revo_mdev_destroy_(revo_mdev* m) {
   hipHostFree(m->h_descs); hipFree(m->d_descs); hipFree(m->d_res); hipHostFree(m->h_res); hipFree(m->d_mail);
   hipHostFree(m->h_vdesc); hipFree(m->d_vdesc); hipFree(m->d_marks); hipFree(m->d_hist8); hipFree(m->d_done); hipHostFree(m->h_vout);
   hipHostFree(m->h_cdesc); hipFree(m->d_cdesc); hipHostFree(m->h_segs); hipFree(m->d_segs);
+  infows_destroy(m->info_ws);
   for (hipEvent_t e : {m->ev_trk, m->ev_vdesc, m->ev_cdesc, m->ev_segs, m->ev_h2d, m->ev_prod}) if (e) hipEventDestroy(e);
   (void)hipGetLastError();  // a partially built handle frees null pointers on purpose
   delete m;
@@ -2260,6 +2391,32 @@ extern "C" int revo_mdev_track_(revo_mdev* m, int n, MultiTrack* pairs) {
                   "partial sums in time (device shared with another process?) -- its pose is not valid");
     if ((rc = decode_track(r, pairs[i].R, pairs[i].T, nullptr, &pairs[i].status, nullptr, nullptr))) return rc;
   }
+  return REVO_OK;
+}
+
+// The level-0 information of the n pairs revo_mdev_track_ just tracked, at the poses its grid wrote: one k_pair_info launch
+// on the tracker stream behind that grid (descriptors and records are still the step's), copied to pinned memory.
+extern "C" int revo_mdev_pair_info_enqueue_(revo_mdev* m, int n) {
+  if (n <= 0) return REVO_OK;
+  revo_ctx* c = m->c;
+  HIPCHECK(hipSetDevice(c->device));
+  if (!m->info_ws) { int rc = infows_create(m->S, true, &m->info_ws); if (rc) return rc; }
+  InfoWs* w = m->info_ws;
+  hipStream_t s = c->stream;
+  launch_pair_info(m->d_descs, m->d_res, (int)(sizeof(revo_pair_result) / 4), (int)(offsetof(revo_pair_result, flags) / 4),
+                   info_params(m->tp, 0), n, w->d_part, w->d_cnt, w->d_ticket, w->d_out, s);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(w->h_out, w->d_out, sizeof(revo_pair_info) * n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipEventRecord(w->ev_done, s));
+  return REVO_OK;
+}
+// waits for that launch; out: its n records, in the order of revo_mdev_track_'s pairs
+extern "C" int revo_mdev_pair_info_wait_(revo_mdev* m, int n, revo_pair_info* out) {
+  if (n <= 0) return REVO_OK;
+  if (!m->info_ws) return fail(REVO_ERR_INVALID_ARG, "no information launch to wait for");
+  const int rc = wait_event_polled(m->info_ws->ev_done);
+  if (rc) return rc;
+  memcpy(out, m->info_ws->h_out, sizeof(revo_pair_info) * n);
   return REVO_OK;
 }
 

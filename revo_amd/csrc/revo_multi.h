@@ -17,6 +17,8 @@ int revo_mdev_submit_(revo_mdev* m, int n, const revo_stream_frame* frames, int 
                       void* producer, void** set_out);
 void revo_mdev_release_set_(revo_mdev* m, void* set);  // no frame of the set is queued, current or previous any more
 int revo_mdev_track_(revo_mdev* m, int n, MultiTrack* pairs);            // one tracker grid, waits for the poses
+int revo_mdev_pair_info_enqueue_(revo_mdev* m, int n);                   // k_pair_info for the n pairs just tracked (asynchronous)
+int revo_mdev_pair_info_wait_(revo_mdev* m, int n, revo_pair_info* out); // ... their records
 int revo_mdev_vote_(revo_mdev* m, int n, MultiVote* votes);              // one batched vote, waits for the counts
 int revo_mdev_add_clouds_(revo_mdev* m, int n, const MultiFrame* f);     // one batched cloud copy (asynchronous)
 int revo_mdev_promote_(revo_mdev* m, int n, const MultiFrame* f);        // keyframe slots <- frames, then their EDT

@@ -43,7 +43,31 @@ struct revo_vo {
   // it changes.  Launch timing only: every launch that counts has the same arguments either way.  REVO_KF_GUARD=0 switches it off.
   float last_ratio = INFINITY;
   float kf_guard = 1.08f;
+  // revo_vo_set_pair_info: the level-0 information of the last reported frame at its final pose, and its keyframe's time stamp
+  bool pair_info = false, has_info = false;
+  revo_pair_info info{};
+  double info_kf_ts = 0.0;
 };
+
+// a record without evaluation (flags bit0) at the identity pose: the first frame of a sequence is its own keyframe
+static void no_info_record(revo_pair_info* r) {
+  memset(r, 0, sizeof(*r));
+  r->flags = 1;
+  r->R[0] = r->R[4] = r->R[8] = 1.f;
+}
+extern "C" int revo_vo_set_pair_info(revo_vo* v, int on) {
+  if (!v) return REVO_ERR_INVALID_ARG;
+  v->pair_info = on != 0;
+  if (!v->pair_info) v->has_info = false;
+  return REVO_OK;
+}
+extern "C" int revo_vo_last_pair_info(const revo_vo* v, revo_pair_info* out, double* kf_timestamp) {
+  if (!v || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (!v->pair_info || !v->has_info) return fail(REVO_ERR_INVALID_ARG, "no pair information: the option is off or no frame was tracked yet");
+  *out = v->info;
+  if (kf_timestamp) *kf_timestamp = v->info_kf_ts;
+  return REVO_OK;
+}
 
 extern "C" int revo_vo_create(revo_ctx* ctx, revo_vo** out) {
   if (!ctx || !out) return REVO_ERR_INVALID_ARG;
@@ -163,6 +187,7 @@ extern "C" int revo_vo_track_next(revo_vo* v, float pose_out[16], int* new_kf_ou
     ++v->no_frames;
     v->just_added_kf = true;
     if ((rc = revo_tracker_add_old_pcl(v->ctx, v->kf.pyr, v->hist_level, I.m, curr.ts))) return rc;
+    if (v->pair_info) { no_info_record(&v->info); v->info_kf_ts = curr.ts; v->has_info = true; }
     if (pose_out) memcpy(pose_out, I.m, sizeof(I.m));
     if (new_kf_out) *new_kf_out = 1;
     return REVO_OK;
@@ -244,6 +269,13 @@ extern "C" int revo_vo_track_next(revo_vo* v, float pose_out[16], int* new_kf_ou
     if (old_kf != v->kf.pyr) revo_pyramid_destroy(old_kf);
   } else {
     v->just_added_kf = false;
+  }
+  if (v->pair_info) {  // behind this frame's tracker (and whatever look-ahead went out since) on the tracker stream; final pose, final keyframe
+    float Rf[9], Tf[3];
+    to_RT(T_KF_N, Rf, Tf);
+    if ((rc = revo_tracker_pair_info(v->ctx, v->kf.pyr, curr.pyr, Rf, Tf, 0, &v->info))) return rc;
+    v->info_kf_ts = v->kf.ts;
+    v->has_info = true;
   }
   v->slot = v->spec_valid ? (v->spec_slot ^ 1) : 0;
   v->before_last = v->last;

@@ -37,6 +37,10 @@ struct Stream {
   bool just_added_kf = false;
   bool retrack = false;  // a keyframe change is owed its re-track of `cur` (the step after the vote that asked for it)
   Ref cur{nullptr, 0, 0.0};
+  double kf_ts = 0.0;     // time stamp of the stream's keyframe
+  bool has_info = false;  // revo_vo_multi_set_pair_info: the record of the last reported frame
+  revo_pair_info info{};
+  double info_kf_ts = 0.0;
 };
 }  // namespace
 
@@ -48,6 +52,7 @@ struct revo_vo_multi {
   std::vector<std::pair<void*, int>> refs;  // step sets and how many queued / current / previous frames still point into them
   std::vector<revo_map*> maps;              // per stream: the voxel map its promoted keyframes go into (revo_vo_multi_attach_map)
   revo_map_stage* map_stage = nullptr;      // descriptors of the step's batched map integration
+  bool pair_info = false;                   // revo_vo_multi_set_pair_info
 };
 
 static void ref_add(revo_vo_multi* m, void* set) {
@@ -103,6 +108,20 @@ extern "C" int revo_vo_multi_keyframe(const revo_vo_multi* m, int s, revo_pyr** 
   if (m->st[s].n_keyframes == 0) return fail(REVO_ERR_INVALID_ARG, "the stream has no keyframe yet");
   if (kf) *kf = revo_mdev_keyframe_(m->dev, s);
   if (T_w_kf) memcpy(T_w_kf, m->st[s].T_w_kf.m, sizeof(float) * 16);
+  return REVO_OK;
+}
+
+extern "C" int revo_vo_multi_set_pair_info(revo_vo_multi* m, int on) {
+  if (!m) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  m->pair_info = on != 0;
+  if (!m->pair_info) for (Stream& x : m->st) x.has_info = false;
+  return REVO_OK;
+}
+extern "C" int revo_vo_multi_pair_info(const revo_vo_multi* m, int s, revo_pair_info* out, double* kf_timestamp) {
+  if (!stream_ok(m, s) || !out) return fail(REVO_ERR_INVALID_ARG, "bad argument");
+  if (!m->pair_info || !m->st[s].has_info) return fail(REVO_ERR_INVALID_ARG, "no pair information: the option is off or the stream has reported nothing yet");
+  *out = m->st[s].info;
+  if (kf_timestamp) *kf_timestamp = m->st[s].info_kf_ts;
   return REVO_OK;
 }
 
@@ -228,6 +247,10 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
   }
   int rc = revo_mdev_track_(m->dev, (int)trk.size(), trk.data());
   if (rc) return rc;
+  // one k_pair_info launch behind the grid, at the poses it wrote, for every stream it tracked (the records of those that
+  // report nothing this step -- a vote asking for a keyframe change -- are dropped below)
+  std::vector<revo_pair_info> infos(m->pair_info ? trk.size() : 0);
+  if (m->pair_info && (rc = revo_mdev_pair_info_enqueue_(m->dev, (int)trk.size()))) return rc;
   // the votes of the streams that tracked a new frame (a re-track's second vote is discarded by revo_vo: not run here)
   std::vector<MultiVote> votes;
   std::vector<M4> T_KF_N(trk.size()), world(trk.size());
@@ -243,6 +266,7 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
     }
   }
   if ((rc = revo_mdev_vote_(m->dev, (int)votes.size(), votes.data()))) return rc;
+  if (m->pair_info && (rc = revo_mdev_pair_info_wait_(m->dev, (int)trk.size(), infos.data()))) return rc;
   size_t vk = 0;
   for (size_t k = 0; k < trk.size(); ++k) {
     const int s = trk[k].stream;
@@ -256,6 +280,7 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
       const int status = votes[vk++].status;
       if (status == REVO_TRACKER_STATE_NEW_KF && !x.just_added_kf) {  // system.cpp:203-241, the re-track deferred to the next step
         x.T_w_kf = x.last.world();  // kfPyr->setTwf(mPoseGraph.back().getCurrToWorld())
+        x.kf_ts = x.prev.ts;
         promote.push_back(MultiFrame{s, x.prev.set, x.prev.frame, {}, x.prev.ts});
         memcpy(promote.back().T_w, x.T_w_kf.m, sizeof(x.T_w_kf.m));
         x.last = Pose{I, x.T_w_kf};  // mPoseGraph.back().setKfFrame(kfPyr)
@@ -277,6 +302,7 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
     x.T_NM1_N = mul(inverse(x.before_last.world()), w1);
     to_RT(mul(x.last.T_kf_curr, x.T_NM1_N), x.R, x.T);
     report(s, w1, new_kf, x.cur.ts);
+    if (m->pair_info) { x.info = infos[k]; x.info_kf_ts = x.kf_ts; x.has_info = true; }
     if (x.has_prev) ref_drop(m, x.prev.set);  // prevPyr = currPyr
     x.prev = x.cur;
     x.has_prev = true;
@@ -284,6 +310,14 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
   for (int s : first) {
     Stream& x = m->st[s];
     x.T_w_kf = I;
+    x.kf_ts = x.cur.ts;
+    if (m->pair_info) {  // the first frame is its own keyframe: no evaluation (flags bit0), identity pose
+      memset(&x.info, 0, sizeof(x.info));
+      x.info.flags = 1;
+      x.info.R[0] = x.info.R[4] = x.info.R[8] = 1.f;
+      x.info_kf_ts = x.cur.ts;
+      x.has_info = true;
+    }
     promote.push_back(MultiFrame{s, x.cur.set, x.cur.frame, {}, x.cur.ts});
     memcpy(promote.back().T_w, I.m, sizeof(I.m));
     x.last = Pose{I, I};

@@ -14,7 +14,12 @@ api.VoxelMap.load continues and `python -m revo_amd.mapfile` merges; FILE with _
 --streams or more than one dataset.
 --map-views DIR (with --map) renders the finished map from the estimated pose of every keyframe, or with --map-views-every K
 of every K-th tracked frame, on the GPU (api.VoxelMap.render) and writes a TUM-layout data set into DIR (tum.write_map_views:
-rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset."""
+rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset.
+--covariances writes cov_<dataset>.txt next to the pose file, one line per pose line in the same order: the frame's time stamp,
+its keyframe's time stamp, the good-point count, sigma2 and the 21 upper-triangle entries (row-major) of the 6x6 covariance of the
+relative pose frame -> keyframe (api.pair_covariance of the level-0 settings.PairInfo at the final pose; translation 0-2,
+rotation 3-5); `nan` for sigma2 and the 21 entries where no covariance exists (a sequence's first frame, too few points, a rank-deficient
+system).  Sequential or with --streams; the pose files do not depend on it."""
 import os
 import sys
 import time
@@ -26,7 +31,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--map VOXEL [--map-save FILE] [--map-views DIR [--map-views-every K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-save FILE] [--map-views DIR [--map-views-every K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -76,6 +81,9 @@ def main(argv=None):
     exact_sums = "--exact-sums" in argv  # the tracker's exact-sums mode (both drivers)
     if exact_sums:
         argv = [a for a in argv if a != "--exact-sums"]
+    covariances = "--covariances" in argv  # cov_<dataset>.txt: the covariance of every reported relative pose
+    if covariances:
+        argv = [a for a in argv if a != "--covariances"]
     gpu_decode = "--gpu-decode" in argv  # PNG decoding on the GPU (multi-stream driver only)
     if gpu_decode:
         argv = [a for a in argv if a != "--gpu-decode"]
@@ -104,14 +112,14 @@ def main(argv=None):
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
         return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel,
-                            views_dir, views_every, map_save)
+                            views_dir, views_every, map_save, covariances)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
         drawer = ply.ModelExporter() if model_dir else None
         vmap = api.VoxelMap(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"])) if map_voxel else None
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
-                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap)
+                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances)
         nd = tum.default_decoders() if decoders is None else decoders
         rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
                                   read_n_images=io["read_n_images"])
@@ -129,6 +137,8 @@ def main(argv=None):
         if sysd["do_output_poses"]:
             with open("poses_%s.txt" % name, "w") as f:
                 f.write("\n".join(drv.tum_lines()) + "\n")
+        if covariances:
+            _save_covariances(name, drv.poses, drv.pair_infos)
         print("-----VO Report-----\nFrames Tracked: %d\nKeyframes Tracked: %d\nframes/s (incl. PNG decode, %s): %.1f"
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
         if vmap is not None:
@@ -149,6 +159,29 @@ def _rvm_path(map_save, name, per_dataset):
         return map_save
     stem, ext = os.path.splitext(map_save)
     return "%s_%s%s" % (stem, name, ext)
+
+
+def covariance_lines(poses, pair_infos):
+    """One line per pose: 'ts kf_ts good sigma2 c00 c01 .. c55' (21 upper-triangle entries, row-major), %.9e; `nan` for sigma2
+    and the 21 entries where api.pair_covariance refuses the record."""
+    from . import api
+    out = []
+    iu = np.triu_indices(6)
+    for (ts, _), (info, kf_ts) in zip(poses, pair_infos):
+        try:
+            cov, s2 = api.pair_covariance(info)
+            nums = ["%d" % info.good, "%.9e" % s2] + ["%.9e" % c for c in cov[iu]]
+        except api.RevoError:
+            nums = ["%d" % info.good] + ["nan"] * 22
+        out.append("%.9f %.9f " % (ts, kf_ts) + " ".join(nums))
+    return out
+
+
+def _save_covariances(name, poses, pair_infos):
+    lines = covariance_lines(poses, pair_infos)
+    with open("cov_%s.txt" % name, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("Covariances: %d lines (%d without a covariance) -> cov_%s.txt" % (len(lines), sum("nan" in ln for ln in lines), name))
 
 
 def _save_map(vmap, name, rvm=None):
@@ -186,7 +219,7 @@ def _report_ate(folder, poses):
 
 
 def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
-                 map_voxel=None, views_dir=None, views_every=0, map_save=None):
+                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -217,7 +250,8 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
                 yield f
 
     drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"],
-                       exact_sums=exact_sums, map_voxel=map_voxel, map_dense=bool(sysd["do_generate_dense_pcl"]))
+                       exact_sums=exact_sums, map_voxel=map_voxel, map_dense=bool(sysd["do_generate_dense_pcl"]),
+                       pair_info=covariances)
     t0 = time.perf_counter()
     try:
         res = drv.run([frames(f) for f in folders])
@@ -230,6 +264,8 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
         if sysd["do_output_poses"]:
             with open("poses_%s.txt" % name, "w") as f:
                 f.write("\n".join(r.tum_lines()) + "\n")
+        if covariances:
+            _save_covariances(name, r.poses, r.pair_infos)
         total += len(r)
         print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
         if r.map is not None:

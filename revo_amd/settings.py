@@ -125,6 +125,26 @@ class PairResult(C.Structure):
 assert C.sizeof(PairResult) == 96
 
 
+class PairInfo(C.Structure):
+    """revo_pair_info (include/revo_hip.h), 192 bytes: the sums of a pair's normal equations at a pose of one level -- H (upper
+    triangle, row-major), g, sum w r^2, sum r^2, the good / bad counts -- each the float nearest the exact sum of its terms."""
+    _fields_ = [
+        ("H", C.c_float * 21), ("g", C.c_float * 6), ("sum_w", C.c_float), ("sum_u", C.c_float),
+        ("good", C.c_int32), ("bad", C.c_int32), ("level", C.c_int32), ("flags", C.c_int32),
+        ("R", C.c_float * 9), ("T", C.c_float * 3), ("reserved", C.c_int32 * 3),
+    ]
+
+
+assert C.sizeof(PairInfo) == 192
+PAIR_INFO_CHUNK = 1024  # points per chunk of k_pair_info (INFO_CHUNK, revo_amd/csrc/revo_dev.h)
+PAIR_INFO_MAX_GROUPS = 32
+
+
+def pair_info_groups(npix):
+    """Workgroups per pair of a k_pair_info launch at a level of npix pixels (info_groups, revo_amd/csrc/revo_dev.h)."""
+    return max(1, min(PAIR_INFO_MAX_GROUPS, (npix + 8 * PAIR_INFO_CHUNK - 1) // (8 * PAIR_INFO_CHUNK)))
+
+
 class StreamFrame(C.Structure):
     """revo_stream_frame (include/revo_hip.h): one frame of one stream of revo_vo_multi, host memory."""
     _fields_ = [

@@ -17,12 +17,12 @@ import numpy as np
 
 from . import _lib, api
 from ._lib import check, f32p, u16p, u8p, vp
-from .settings import StreamFrame, StreamResult, TrackerSettings
+from .settings import PairInfo, StreamFrame, StreamResult, TrackerSettings
 
 
 class REVO:
     def __init__(self, settingsPyr, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None):
+                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         self.camPyr = cameraPyr or api.CameraPyr(settingsPyr, device=device)
@@ -38,6 +38,18 @@ class REVO:
         # api.VoxelMap: every keyframe the driver reports (the first frame included) is fused into it at its T_w_kf, the moment
         # the drawer gets its cloud; on the device, no cloud goes through the host
         self.voxelMap = voxelMap
+        # pair_info: every reported pose comes with its level-0 settings.PairInfo (the information matrix of the relative pose
+        # curr -> keyframe at the final pose) and that keyframe's time stamp: pair_infos[i] belongs to poses[i]
+        self.pair_info = bool(pair_info)
+        self.pair_infos = []  # (PairInfo, keyframe timestamp)
+        if self.pair_info:
+            check(_lib.lib().revo_vo_set_pair_info(self._h, 1))
+
+    def last_pair_info(self):
+        """(PairInfo, keyframe timestamp) of the frame track_next reported last (pair_info=True)."""
+        info, kts = PairInfo(), C.c_double()
+        check(_lib.lib().revo_vo_last_pair_info(self._h, C.byref(info), C.byref(kts)))
+        return info, kts.value
 
     def __del__(self):
         try:
@@ -77,6 +89,8 @@ class REVO:
         check(_lib.lib().revo_vo_track_next(self._h, pose.ctypes.data_as(f32p), C.byref(kf), C.byref(ts)))
         M = pose.reshape(4, 4).T.copy()
         self.poses.append((ts.value, M))
+        if self.pair_info:
+            self.pair_infos.append(self.last_pair_info())
         if kf.value and (self.mpMapDrawer is not None or self.voxelMap is not None):
             kfPyr, T_w_kf = self.keyframe()
             if self.mpMapDrawer is not None:
@@ -173,6 +187,7 @@ class SequenceResult(list):
     def __init__(self):
         super().__init__()
         self.poses = []
+        self.pair_infos = []  # MultiREVO(pair_info=True): (PairInfo, keyframe timestamp) per pose
         self.map = None
 
     def tum_lines(self):
@@ -193,9 +208,10 @@ class MultiREVO:
     (re-tracked against the new keyframe) with new_keyframe = True."""
 
     map_voxel, map_dense, map_max_voxels = None, False, 1 << 24  # run()'s per-sequence maps: off unless __init__ sets them
+    pair_info = False  # run() collects each pose's PairInfo: off unless __init__ sets it
 
     def __init__(self, settingsPyr, n_streams, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 max_queue=2, exact_sums=False, map_voxel=None, map_dense=False, map_max_voxels=1 << 24):
+                 max_queue=2, exact_sums=False, map_voxel=None, map_dense=False, map_max_voxels=1 << 24, pair_info=False):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         if cameraPyr is None:
@@ -222,6 +238,16 @@ class MultiREVO:
         self.map_dense = bool(map_dense)
         self.map_max_voxels = int(map_max_voxels)
         self._maps = [None] * self.n_streams
+        # pair_info: one information launch per step for all streams; last_pair_info(stream) belongs to the stream's last reported pose
+        self.pair_info = bool(pair_info)
+        if self.pair_info:
+            check(_lib.lib().revo_vo_multi_set_pair_info(self._h, 1))
+
+    def last_pair_info(self, stream):
+        """(PairInfo, keyframe timestamp) of the frame the stream reported last (pair_info=True)."""
+        info, kts = PairInfo(), C.c_double()
+        check(_lib.lib().revo_vo_multi_pair_info(self._h, int(stream), C.byref(info), C.byref(kts)))
+        return info, kts.value
 
     def attach_map(self, stream, voxelMap):
         """Every keyframe `stream` promotes from now on is integrated into voxelMap (None detaches); reset() detaches."""
@@ -376,6 +402,8 @@ class MultiREVO:
                 r = out[seq_of[s]]
                 r.append((M, kf))
                 r.poses.append((ts, M))
+                if self.pair_info:
+                    r.pair_infos.append(self.last_pair_info(s))
         return out
 
 
