@@ -748,6 +748,24 @@ int revo_map_merge_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int
  * not changed.  REVO_ERR_INVALID_ARG: NULL, dst == src, voxel edges whose float bits differ, maps on different devices.
  * dense may differ. */
 int revo_map_merge(revo_map* dst, revo_map* src);
+/* The exact inverse of revo_map_merge_raw: per record the voxel of `key` loses count, sum_q and sum_bgr; a key may
+ * occur several times.  A voxel whose count reaches 0 is gone: absent from every export, extraction, view and merge, and no
+ * longer counted against max_voxels.  On success points_integrated -= sum of count, points_dropped -= points_dropped,
+ * keyframes -= keyframes and voxels is the true count; merging the same records again restores the map byte for byte.
+ * All or nothing: REVO_ERR_INVALID_ARG if some record has count == 0 or key bit 63 set, some key is not in the map, the
+ * records of a voxel together take more than its count, a voxel would keep count 0 with a non-zero sum, or points_dropped or
+ * keyframes is larger than the map's own; the map is then as it was, bit for bit, keyframes_rejected included.  Other
+ * argument errors (NULL, a misaligned device pointer, keyframes < 0) change nothing either.  n == 0 is a no-op.
+ * What the call cannot see is the caller's responsibility: records that leave every voxel they touch a positive count but
+ * were never part of this map are subtracted, and the map is then not one that any set of keyframes builds.
+ * Enqueued on the context's tracker stream behind pending integrations; the call always waits for the device's decision.
+ * The table keeps its capacity (no occupied slot is left with count 0; rehashes does not count the clean-up). */
+int revo_map_subtract_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int device_in, size_t points_dropped,
+                          int32_t keyframes);
+/* revo_map_subtract_raw straight from src's table on the device, with src's points_dropped and keyframes: the inverse of
+ * revo_map_merge(dst, src).  Waits for src; src is not changed.  REVO_ERR_INVALID_ARG as above, and for NULL, dst == src,
+ * voxel edges whose float bits differ, maps on different devices. */
+int revo_map_subtract(revo_map* dst, revo_map* src);
 /* The voxel edge and cloud mode the map was created with (either output may be NULL). */
 int revo_map_voxel_size(revo_map* m, float* voxel, int* dense);
 

@@ -141,6 +141,8 @@ def lib():
     L.revo_map_export_raw.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.revo_map_merge_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, C.c_int32]
     L.revo_map_merge.argtypes = [vp, vp]
+    L.revo_map_subtract_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, C.c_int32]
+    L.revo_map_subtract.argtypes = [vp, vp]
     L.revo_map_voxel_size.argtypes = [vp, f32p, C.POINTER(C.c_int)]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]

@@ -52,6 +52,7 @@ class CameraPyr:
 
     def __init__(self, settingsPyr, device=0, optimizerSettings=None, trackerSettings=None, exact_sums=False):
         self.settings = settingsPyr
+        self.device = int(device)
         self._h = vp()
         opt = optimizerSettings or OptimizerSettings()
         trk = trackerSettings or TrackerSettings()
@@ -351,6 +352,35 @@ class VoxelMap:
         table on the device; `other` is unchanged.  The result is the map one handle would have built from both maps' keyframes."""
         check(_lib.lib().revo_map_merge(self._h, other._h))
 
+    # -- taking voxels out again (revo_map_subtract*, DESIGN 15)
+    def subtract_raw(self, records, points_dropped=0, keyframes=0, n=None):
+        """The exact inverse of merge_raw: the records' sums leave their voxels, and a voxel whose count reaches 0 is gone.
+        Takes what merge_raw takes.  All or nothing (REVO_ERR_INVALID_ARG, the map unchanged bit for bit): a record with count 0
+        or key bit 63, a key the map does not hold, more than a voxel has, a voxel left at count 0 with another sum, or more
+        points_dropped or keyframes than the map counts.  Records that fit but never were part of the map cannot be told
+        apart: that is the caller's responsibility.  Waits for the device."""
+        L = _lib.lib()
+        if hasattr(records, "data_ptr"):
+            import torch
+            have = self._raw_tensor(records)
+            n = have if n is None else int(n)
+            if n < 0 or n > have:
+                raise ValueError("the tensor holds %d records" % have)
+            torch.cuda.current_stream(records.device).synchronize()  # the tensor is written before the tracker stream reads it
+            check(L.revo_map_subtract_raw(self._h, vp(records.data_ptr()), n, 1, int(points_dropped), int(keyframes)))
+            return
+        from . import mapfile
+        rec = mapfile.as_records(records)
+        if n is not None:
+            rec = rec[:int(n)]
+        check(L.revo_map_subtract_raw(self._h, rec.ctypes.data_as(vp) if len(rec) else None, len(rec), 0, int(points_dropped),
+                                      int(keyframes)))
+
+    def subtract(self, other):
+        """The inverse of merge(other): every voxel of `other` (same voxel edge, same device) leaves the map with its
+        points_dropped and keyframes, straight from its table on the device; `other` is unchanged.  All or nothing."""
+        check(_lib.lib().revo_map_subtract(self._h, other._h))
+
     def save(self, path):
         """The map as a .rvm file (mapfile): header and canonical records.  Equal maps give equal files."""
         from . import mapfile
@@ -446,6 +476,83 @@ class VoxelMap:
         ms = C.c_float()
         check(_lib.lib().revo_map_render_last_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+class MapWindow:
+    """A voxel map that holds exactly the last `window` integrated keyframes: the bounded local map of a long run.  It is
+    byte for byte the VoxelMap a fresh handle would build from those keyframes alone.  integrate(kf, T_w_kf) is
+    VoxelMap's, so vo.REVO(voxelMap=MapWindow(...)) works unchanged; every other attribute (info, points, render, save, ...)
+    is the inner VoxelMap's (`.map`).  keyframes: the poses currently in the map, oldest first; timestamps: their time stamps.
+
+    Per keyframe: it is integrated into a private scratch map on the same context, the scratch map's records are kept in a
+    device buffer and merged into the map, and once more than `window` keyframes are held the oldest one's records are
+    subtracted again.  Device memory held: 64 bytes x voxels per kept keyframe (at most 64 B x width x height each), beside
+    the map and the scratch map of one keyframe.  map_kw: VoxelMap's max_voxels / initial_voxels for the map itself."""
+
+    def __init__(self, cameraPyr, voxel, dense=False, window=1, **map_kw):
+        import collections
+        if int(window) < 1:
+            raise ValueError("window must be >= 1 keyframe")
+        self.window = int(window)
+        self.map = VoxelMap(cameraPyr, voxel, dense=dense, **map_kw)
+        npix = cameraPyr.settings.width * cameraPyr.settings.height  # a keyframe has at most one voxel per pixel
+        self._scratch = VoxelMap(cameraPyr, voxel, dense=dense, max_voxels=npix, initial_voxels=npix)
+        self._held = collections.deque()  # (T_w_kf, device records or None, voxels, points_dropped, time stamp)
+
+    def __getattr__(self, name):
+        if name in ("map", "_scratch", "_held", "window"):
+            raise AttributeError(name)
+        return getattr(self.map, name)
+
+    @property
+    def keyframes(self):
+        return [h[0].copy() for h in self._held]
+
+    @property
+    def timestamps(self):
+        return [h[4] for h in self._held]
+
+    def integrate(self, pyr, T_w):
+        import torch
+        T_w = np.array(T_w, np.float32).reshape(4, 4)
+        sc = self._scratch
+        sc.clear()
+        sc.integrate(pyr, T_w)
+        i = sc.info()
+        buf = None
+        if i["voxels"]:
+            buf = torch.empty(64 * i["voxels"], dtype=torch.uint8, device="cuda:%d" % self.map.cameraPyr.device)
+            if sc.export_raw_into(buf) != i["voxels"]:
+                raise RuntimeError("the scratch map's export does not match its voxel count")
+        self.map.merge(sc)  # REVO_ERR_CAPACITY past max_voxels: the keyframe is not in the map and not in the window
+        self._held.append((T_w, buf, i["voxels"], i["points_dropped"], float(pyr.returnTimestamp())))
+        while len(self._held) > self.window:
+            self._evict()
+
+    def integrate_many(self, pyrs, T_ws):
+        for p, T in zip(pyrs, T_ws):
+            self.integrate(p, T)
+
+    def _evict(self):
+        _, buf, n, dropped, _ = self._held[0]
+        if n:
+            self.map.subtract_raw(buf, points_dropped=dropped, keyframes=1, n=n)
+        else:  # a keyframe without a voxel still counted: an empty subtraction is a no-op, so its counters ride on one record
+            from . import mapfile
+            one = np.zeros(1, mapfile.RAW_DTYPE)
+            one["count"] = 1
+            self.map.merge_raw(one)
+            self.map.subtract_raw(one, points_dropped=dropped, keyframes=1)
+        self._held.popleft()
+
+    def clear(self):
+        self.map.clear()
+        self._held.clear()
+
+    def close(self):
+        self._held.clear()
+        self._scratch.close()
+        self.map.close()
 
 
 class Optimizer:

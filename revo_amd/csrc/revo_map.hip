@@ -38,6 +38,8 @@ struct MapStats {
   u64 occ, pts, drop, kfs, rejected, fault;
   u64 ok, bad;  // bad: k_map_merge met a record with count 0 or key bit 63 (the host clears it before such a launch)
   u64 shard[MAP_SHARDS][16];  // [0] new voxels, [1] points, [2] dropped points of the batch in flight
+  // the subtraction in flight (behind the shards: no older field moves): refused, points taken, voxels whose count reached 0
+  u64 sub_bad, sub_pts, sub_freed;
 };
 struct MapDesc {  // one keyframe of a launch
   const float* depth; const uint8_t* edges; const uint8_t* bgr;
@@ -320,6 +322,175 @@ __global__ void __launch_bounds__(256) k_map_merge(const MapMergeK a) {
   }
 }
 
+// --------------------------------------------------------------------------------------- taking voxels out again (15) --
+// revo_map_subtract_raw / revo_map_subtract: the inverse of k_map_merge.  Four launches and a decision between them:
+//   k_map_sub<SRC, false>  every record's sums leave the slot of its key (looked up, never inserted);
+//   k_map_sub_verify<SRC>  a slot left with count 0 must have every other sum 0;
+//   k_map_sub_commit       decides, moves the counters, publishes as k_map_commit does;
+//   k_map_sub<SRC, true>   refused: the same records are added back -- integer addition restores the table exactly;
+//   k_map_rehash_live      accepted and voxels died: the live slots go into a fresh table of the same size (host: compact()).
+struct MapSubCommit { MapStats* st; u64* pub; u64 seq, dropped, kfs; };
+
+// The slot of `key`, or ~0u: a lookup that touches nothing (a miss is the caller's bad record, not a broken table).  No key
+// of the table changes while a subtraction's passes run, so plain loads do.
+__device__ __forceinline__ unsigned map_find(const u64* __restrict__ keys, unsigned mask, u64 key) {
+  unsigned s = (unsigned)map_hash(key) & mask;
+  for (unsigned i = 0; i <= mask; ++i) {
+    const u64 k = keys[s];
+    if (k == key) return s;
+    if (k == MAP_EMPTY) break;
+    s = (s + 1) & mask;
+  }
+  return ~0u;
+}
+
+// One thread per input record (MERGE_RAW) or per slot of the source table (MERGE_TABLE), loaded as k_map_merge loads them.
+// The count's atomic returns what the voxel held before this record: less than the record takes means the voxel's records
+// together take more than it has (the first record to cross zero always sees it, whatever the order); exactly as much means
+// this record emptied it, and nothing may follow, so those are the freed voxels.  Block sums go through LDS.
+template <int SRC, bool UNDO>
+__global__ void __launch_bounds__(256) k_map_sub(const MapMergeK a) {
+  __shared__ unsigned s_freed, s_bad;
+  __shared__ u64 s_pts;
+  if (UNDO && a.st->ok) return;  // accepted: nothing to put back
+  if (!UNDO) {
+    if (threadIdx.x == 0) { s_freed = 0; s_bad = 0; s_pts = 0; }
+    __syncthreads();
+  }
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  u64 key = MAP_EMPTY;
+  ulonglong2 r0{}, r1{}, r2{}, r3{};  // key n | qx qy | qz sb | sg sr
+  bool bad = false;
+  if (i < a.n) {
+    if (SRC == MERGE_TABLE) {
+      key = a.skeys[i];
+      if (key != MAP_EMPTY) {
+        const ulonglong2* v = (const ulonglong2*)(a.svals + i);
+        const ulonglong2 p = v[0], q = v[1], c = v[2], d = v[3];
+        r0 = make_ulonglong2(key, p.x); r1 = make_ulonglong2(p.y, q.x); r2 = make_ulonglong2(q.y, c.x); r3 = make_ulonglong2(c.y, d.x);
+        if (r0.y == 0) key = MAP_EMPTY;  // a committed voxel has count >= 1
+      }
+    } else {
+      const ulonglong2* v = a.recs + 4 * (size_t)i;
+      r0 = v[0]; r1 = v[1]; r2 = v[2]; r3 = v[3];
+      key = r0.x;
+      bad = (key >> 63) != 0 || r0.y == 0;
+      if (bad) key = MAP_EMPTY;
+    }
+  }
+  if (key != MAP_EMPTY) {
+    const unsigned s = map_find(a.keys, a.mask, key);
+    if (s == ~0u) {
+      bad = true;
+    } else {
+      MapVal* v = a.vals + s;
+      if (UNDO) {
+        atomicAdd(&v->n, r0.y);
+        atomicAdd(&v->qx, r1.x); atomicAdd(&v->qy, r1.y); atomicAdd(&v->qz, r2.x);
+        atomicAdd(&v->sb, r2.y); atomicAdd(&v->sg, r3.x); atomicAdd(&v->sr, r3.y);
+      } else {
+        const u64 old = atomicAdd(&v->n, 0ull - r0.y);
+        atomicAdd(&v->qx, 0ull - r1.x); atomicAdd(&v->qy, 0ull - r1.y); atomicAdd(&v->qz, 0ull - r2.x);
+        atomicAdd(&v->sb, 0ull - r2.y); atomicAdd(&v->sg, 0ull - r3.x); atomicAdd(&v->sr, 0ull - r3.y);
+        if (old < r0.y) bad = true;
+        else if (old == r0.y) atomicAdd(&s_freed, 1u);
+        atomicAdd(&s_pts, r0.y);
+      }
+    }
+  }
+  if (!UNDO) {
+    if (bad) atomicOr(&s_bad, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (s_bad) atomicOr(&a.st->sub_bad, 1ull);
+      if (s_pts) atomicAdd(&a.st->sub_pts, s_pts);
+      if (s_freed) atomicAdd(&a.st->sub_freed, (u64)s_freed);
+    }
+  }
+}
+
+// One thread per record or source slot again, behind every subtraction: the slot of its key, and if the count there is 0,
+// the other six sums.  (Several records of one voxel check the same slot; a refusal is a flag, so that costs nothing.)
+template <int SRC>
+__global__ void __launch_bounds__(256) k_map_sub_verify(const MapMergeK a) {
+  __shared__ unsigned s_bad;
+  if (threadIdx.x == 0) s_bad = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  u64 key = MAP_EMPTY;
+  if (i < a.n) {
+    if (SRC == MERGE_TABLE) {
+      key = a.skeys[i];
+      if (key != MAP_EMPTY && a.svals[i].n == 0) key = MAP_EMPTY;
+    } else {
+      const ulonglong2 r0 = a.recs[4 * (size_t)i];
+      key = r0.x;
+      if ((key >> 63) != 0 || r0.y == 0) key = MAP_EMPTY;
+    }
+  }
+  if (key != MAP_EMPTY) {
+    const unsigned s = map_find(a.keys, a.mask, key);
+    if (s != ~0u) {
+      const ulonglong2* v = (const ulonglong2*)(a.vals + s);
+      const ulonglong2 p = v[0];
+      if (p.x == 0) {
+        const ulonglong2 q = v[1], c = v[2], d = v[3];
+        if (p.y | q.x | q.y | c.x | c.y | d.x) atomicOr(&s_bad, 1u);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_bad) atomicOr(&a.st->sub_bad, 1ull);
+}
+
+// One thread: the decision of a subtraction, its counters, and the publication of k_map_commit (voxels, accepted, the
+// sequence word last) with the freed voxels in the fourth pinned word for the host, which then drops the dead slots.
+__global__ void __launch_bounds__(64) k_map_sub_commit(const MapSubCommit c) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  MapStats* s = c.st;
+  const u64 pts = s->sub_pts, freed = s->sub_freed;
+  const bool ok = !s->sub_bad && pts <= s->pts && freed <= s->occ && c.dropped <= s->drop && c.kfs <= s->kfs;
+  s->ok = ok ? 1 : 0;
+  if (ok) { s->occ -= freed; s->pts -= pts; s->drop -= c.dropped; s->kfs -= c.kfs; }
+  c.pub[0] = s->occ;
+  c.pub[2] = ok ? 1 : 0;
+  c.pub[3] = ok ? freed : 0;
+  __threadfence_system();
+  *(volatile u64*)&c.pub[1] = c.seq;
+}
+
+// An accepted subtraction that cannot get its fresh table is taken back: the counters here, the sums by k_map_sub<.., true>.
+__global__ void __launch_bounds__(64) k_map_sub_revert(const MapSubCommit c) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  MapStats* s = c.st;
+  if (!s->ok) return;
+  s->occ += s->sub_freed; s->pts += s->sub_pts; s->drop += c.dropped; s->kfs += c.kfs;
+  s->ok = 0;
+  c.pub[0] = s->occ;
+  c.pub[2] = 0;
+  c.pub[3] = 0;
+  __threadfence_system();
+  *(volatile u64*)&c.pub[1] = c.seq;
+}
+
+// k_map_rehash that leaves the slots with count 0 behind: the new table holds the live voxels only, each reachable from its
+// hash through occupied slots (it was inserted there), so it is a table no kernel can tell from one that never held the rest.
+__global__ void __launch_bounds__(256) k_map_rehash_live(const u64* __restrict__ okeys, const MapVal* __restrict__ ovals, unsigned ocap,
+                                                         u64* nkeys, MapVal* nvals, unsigned nmask, u64* fault) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= ocap) return;
+  const u64 key = okeys[i];
+  if (key == MAP_EMPTY) return;
+  const ulonglong2* v = (const ulonglong2*)(ovals + i);
+  const ulonglong2 p = v[0];
+  if (p.x == 0) return;
+  const ulonglong2 q = v[1], c = v[2], d = v[3];
+  const unsigned s = map_slot<true>(nkeys, nmask, key, nullptr, fault);
+  if (s == ~0u) return;
+  ulonglong2* o = (ulonglong2*)(nvals + s);
+  o[0] = p; o[1] = q; o[2] = c; o[3] = d;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- views --
 // revo_map_render (contract: include/revo_hip.h).  A z-buffer word is (bits of z) << 32 | R << 16 | G << 8 | B; an
 // untouched pixel holds MAP_EMPTY (z is finite and > 0, so no written word reaches it).  A pixel keeps the minimum word.
@@ -471,8 +642,9 @@ static size_t occ_bound(revo_map* m) {
   return b;
 }
 
-// a table of `newcap` slots (power of two) holding every voxel of the old one
-static int grow(revo_map* m, size_t newcap) {
+// a table of `newcap` slots (power of two) holding every voxel of the old one; live_only: every voxel with count >= 1 (what
+// an accepted subtraction leaves; not a growth, so not counted as a rehash)
+static int grow(revo_map* m, size_t newcap, bool live_only = false) {
   hipStream_t s = (hipStream_t)m->g.stream;
   u64* nk = nullptr; MapVal* nv = nullptr;
   HIPCHECK(hipMalloc((void**)&nk, sizeof(u64) * newcap));
@@ -483,10 +655,14 @@ static int grow(revo_map* m, size_t newcap) {
   HIPCHECK(hipMemsetAsync(nk, 0xff, sizeof(u64) * newcap, s));
   HIPCHECK(hipMemsetAsync(nv, 0, sizeof(MapVal) * newcap, s));
   if (m->cap) {
-    hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals,
-                       (unsigned)m->cap, nk, nv, (unsigned)(newcap - 1), &m->d_st->fault);
+    if (live_only)
+      hipLaunchKernelGGL(k_map_rehash_live, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals,
+                         (unsigned)m->cap, nk, nv, (unsigned)(newcap - 1), &m->d_st->fault);
+    else
+      hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals,
+                         (unsigned)m->cap, nk, nv, (unsigned)(newcap - 1), &m->d_st->fault);
     HIPCHECK(hipGetLastError());
-    ++m->rehashes;
+    if (!live_only) ++m->rehashes;
     HIPCHECK(hipStreamSynchronize(s));  // the old table is free once the rehash has read it
   }
   hipFree(m->d_keys); hipFree(m->d_vals);
@@ -870,6 +1046,86 @@ extern "C" int revo_map_merge(revo_map* dst, revo_map* src) {
   if (dst->g.stream != src->g.stream && hipStreamSynchronize((hipStream_t)dst->g.stream) != hipSuccess && !rc)
     return fail(REVO_ERR_HIP, "hipStreamSynchronize failed");
   return rc;
+}
+
+// One subtraction from m (contract: include/revo_hip.h): `a` names the input as in merge_core.  Subtract, verify,
+// decide, undo if refused -- all enqueued at once behind the map's pending work -- then the call waits for the decision, and
+// an accepted one that emptied voxels moves the live ones into a fresh table of the same size.
+static int subtract_core(revo_map* m, MapMergeK a, int src_kind, u64 dropped, u64 keyframes) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  ++m->seq;
+  const MapSubCommit c{m->d_st, m->h_pub, m->seq, dropped, keyframes};
+  HIPCHECK(hipMemsetAsync(&m->d_st->sub_bad, 0, 3 * sizeof(u64), s));
+  a.keys = m->d_keys; a.vals = m->d_vals; a.mask = (unsigned)(m->cap - 1); a.st = m->d_st;
+  const dim3 grid((a.n + 255) / 256), blk(256);
+  const bool tab = src_kind == MERGE_TABLE;
+  if (tab) {
+    hipLaunchKernelGGL((k_map_sub<MERGE_TABLE, false>), grid, blk, 0, s, a);
+    hipLaunchKernelGGL((k_map_sub_verify<MERGE_TABLE>), grid, blk, 0, s, a);
+  } else {
+    hipLaunchKernelGGL((k_map_sub<MERGE_RAW, false>), grid, blk, 0, s, a);
+    hipLaunchKernelGGL((k_map_sub_verify<MERGE_RAW>), grid, blk, 0, s, a);
+  }
+  hipLaunchKernelGGL(k_map_sub_commit, dim3(1), dim3(64), 0, s, c);
+  if (tab) hipLaunchKernelGGL((k_map_sub<MERGE_TABLE, true>), grid, blk, 0, s, a);
+  else hipLaunchKernelGGL((k_map_sub<MERGE_RAW, true>), grid, blk, 0, s, a);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));  // the device has decided
+  if (!m->h_pub[2])
+    return fail(REVO_ERR_INVALID_ARG, "voxel map: the records are not part of the map -- a record with count 0 or key bit 63, a key "
+                                      "the map does not hold, more than a voxel has, sums left in an emptied voxel, or more "
+                                      "dropped points or keyframes than the map counts (nothing subtracted)");
+  if (!m->h_pub[3]) return REVO_OK;
+  const int rc = grow(m, m->cap, true);
+  if (!rc) return REVO_OK;
+  // no memory for the fresh table: the dead slots cannot stay, so the subtraction is taken back as a refused one is
+  const std::string why = revo_last_error();
+  ++m->seq;
+  const MapSubCommit r{m->d_st, m->h_pub, m->seq, dropped, keyframes};
+  hipLaunchKernelGGL(k_map_sub_revert, dim3(1), dim3(64), 0, s, r);
+  if (tab) hipLaunchKernelGGL((k_map_sub<MERGE_TABLE, true>), grid, blk, 0, s, a);
+  else hipLaunchKernelGGL((k_map_sub<MERGE_RAW, true>), grid, blk, 0, s, a);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));
+  return fail(rc, why + " (nothing subtracted)");
+}
+
+extern "C" int revo_map_subtract_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int device_in, size_t points_dropped,
+                                     int32_t keyframes) {
+  if (!m) return fail(REVO_ERR_INVALID_ARG, "null map");
+  if (device_in != 0 && device_in != 1) return fail(REVO_ERR_INVALID_ARG, "device_in must be 0 or 1");
+  if (keyframes < 0) return fail(REVO_ERR_INVALID_ARG, "keyframes must be >= 0");
+  if (n == 0) return REVO_OK;
+  if (!src) return fail(REVO_ERR_INVALID_ARG, "null records");
+  if (device_in && ((uintptr_t)src & 15)) return fail(REVO_ERR_INVALID_ARG, "the device records are not 16-byte aligned");
+  if (n > MAP_MAX_CAP) return fail(REVO_ERR_INVALID_ARG, "voxel map: more than 2^31 records in one subtraction");
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  MapMergeK a{};
+  a.n = (unsigned)n;
+  if (device_in) {
+    a.recs = (const ulonglong2*)src;
+    return subtract_core(m, a, MERGE_RAW, (u64)points_dropped, (u64)keyframes);
+  }
+  char* buf = nullptr;
+  HIPCHECK(hipMalloc((void**)&buf, sizeof(revo_map_voxel_raw) * n));
+  struct Free { char* p; ~Free() { hipFree(p); } } fr{buf};
+  HIPCHECK(hipMemcpyAsync(buf, src, sizeof(revo_map_voxel_raw) * n, hipMemcpyHostToDevice, s));
+  a.recs = (const ulonglong2*)buf;
+  return subtract_core(m, a, MERGE_RAW, (u64)points_dropped, (u64)keyframes);  // has waited: buf is read
+}
+
+extern "C" int revo_map_subtract(revo_map* dst, revo_map* src) {
+  if (!dst || !src) return fail(REVO_ERR_INVALID_ARG, "null map");
+  if (dst == src) return fail(REVO_ERR_INVALID_ARG, "a map cannot be subtracted from itself (revo_map_clear empties it)");
+  if (memcmp(&dst->voxel, &src->voxel, sizeof(float))) return fail(REVO_ERR_INVALID_ARG, "the maps' voxel edges differ");
+  if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
+  MapStats ss;  // waits for src: its table is complete, and its counters say what goes
+  { const int rc = read_stats(src, &ss); if (rc) return rc; }
+  HIPCHECK(hipSetDevice(dst->g.device));
+  MapMergeK a{};
+  a.skeys = src->d_keys; a.svals = src->d_vals; a.n = (unsigned)src->cap;
+  return subtract_core(dst, a, MERGE_TABLE, ss.drop, ss.kfs);  // has waited for dst's stream: src's table is read
 }
 
 // room for a call's views: descriptors, counters, z-buffer words (kept MAP_EMPTY), device outputs of a host-output call

@@ -11,6 +11,7 @@ Equal maps give equal files.
 
     python -m revo_amd.mapfile info FILE...            what each file holds
     python -m revo_amd.mapfile merge OUT FILE...       the union of the files' maps (same voxel edge), without a GPU
+    python -m revo_amd.mapfile subtract A B -o OUT      map A without map B's sums: undoes `merge A OUT B`, without a GPU
     python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
 """
 import struct
@@ -123,6 +124,31 @@ def merge_records(a, b):
     return out
 
 
+def subtract_records(a, b):
+    """The records of `a` without the sums of `b`: the inverse of merge_records (keys may repeat in either), ascending keys,
+    voxels whose count reaches 0 left out.  ValueError, as revo_map_subtract_raw refuses: a key of b that a does not hold, more
+    than a voxel's count, or a voxel left at count 0 with another sum not 0."""
+    a, b = as_records(a), as_records(b)
+    e = np.zeros(0, RAW_DTYPE)
+    a, b = merge_records(a, e), merge_records(b, e)  # canonical: one record per key, checked
+    if len(b) == 0:
+        return a
+    i = np.searchsorted(a["key"], b["key"])
+    i[i == len(a)] = 0
+    if len(a) == 0 or np.any(a["key"][i] != b["key"]):
+        raise ValueError("a voxel record to subtract has a key the map does not hold")
+    if np.any(b["count"] > a["count"][i]):
+        raise ValueError("the records to subtract take more than a voxel's count")
+    out = a.copy()
+    out["count"][i] -= b["count"]
+    out["sum_q"][i] -= b["sum_q"]
+    out["sum_bgr"][i] -= b["sum_bgr"]
+    dead = out["count"] == 0
+    if np.any(out["sum_q"][dead] != 0) or np.any(out["sum_bgr"][dead] != 0):
+        raise ValueError("a voxel would be left with count 0 and a sum that is not 0")
+    return out[~dead]
+
+
 def to_points(records, min_count=1):
     """(xyz N x 3 float32, rgb N x 3 uint8 as R,G,B, count N uint32) of the records with count >= max(min_count, 1), in their
     order -- what revo_map_extract gives: xyz = float32(float64(sum_q) / float64(count) * 2^-20), colour = (sum + count // 2)
@@ -149,6 +175,20 @@ def merge_files(paths):
     return header, rec
 
 
+def subtract_files(path_a, path_b):
+    """(header, records) of map A without map B: same voxel edge; dense of A; B's counters leave A's (ValueError if larger)."""
+    header, rec = read(path_a)
+    h, r = read(path_b)
+    if np.float32(h["voxel"]).tobytes() != np.float32(header["voxel"]).tobytes():
+        raise ValueError("%s has voxels of %g m, %s of %g m" % (path_b, h["voxel"], path_a, header["voxel"]))
+    for k in ("points_dropped", "keyframes"):
+        if h[k] > header[k]:
+            raise ValueError("%s counts %d %s, %s only %d" % (path_b, h[k], k, path_a, header[k]))
+    rec = subtract_records(rec, r)
+    return dict(header, voxels=len(rec), points_integrated=header["points_integrated"] - h["points_integrated"],
+                points_dropped=header["points_dropped"] - h["points_dropped"], keyframes=header["keyframes"] - h["keyframes"]), rec
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     cmd, args = (argv[0], argv[1:]) if argv else (None, [])
@@ -165,6 +205,14 @@ def main(argv=None):
             write(args[0], h, rec)
             print("%s: %d voxels from %d files" % (args[0], len(rec), len(args) - 1))
             return 0
+        if cmd == "subtract" and len(args) == 4 and "-o" in args[:3]:
+            i = args.index("-o")
+            out = args[i + 1]
+            a, b = args[:i] + args[i + 2:]
+            h, rec = subtract_files(a, b)
+            write(out, h, rec)
+            print("%s: %d voxels (%s without %s)" % (out, len(rec), a, b))
+            return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -175,7 +223,7 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         print("mapfile: %s" % e)
         return 1
-    print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | ply FILE [OUT.ply]")
+    print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | ply FILE [OUT.ply]")
     return 2
 
 

@@ -15,6 +15,10 @@ api.VoxelMap.load continues and `python -m revo_amd.mapfile` merges; FILE with _
 --map-views DIR (with --map) renders the finished map from the estimated pose of every keyframe, or with --map-views-every K
 of every K-th tracked frame, on the GPU (api.VoxelMap.render) and writes a TUM-layout data set into DIR (tum.write_map_views:
 rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset.
+--map-window N (with --map, sequential driver only) keeps only the last N keyframes in the map (api.MapWindow: each older
+keyframe's voxel sums are subtracted again, exactly): map_<dataset>.ply, --map-save and --map-views then describe that windowed
+map, and map_window_<dataset>.txt lists the keyframes it holds, oldest first: time stamp and the 16 entries of T_w_kf (row-major,
+%.9g: float32 exactly).  The pose file does not depend on it.
 --covariances writes cov_<dataset>.txt next to the pose file, one line per pose line in the same order: the frame's time stamp,
 its keyframe's time stamp, the good-point count, sigma2 and the 21 upper-triangle entries (row-major) of the 6x6 covariance of the
 relative pose frame -> keyframe (api.pair_covariance of the level-0 settings.PairInfo at the final pose; translation 0-2,
@@ -31,7 +35,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-save FILE] [--map-views DIR [--map-views-every K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-views DIR [--map-views-every K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -59,6 +63,21 @@ def main(argv=None):
         argv = argv[:i] + argv[i + 2:]
         if map_voxel is None:
             print("--map-save writes the voxel map: it needs --map VOXEL")
+            return 2
+    map_window = 0  # api.MapWindow: the map holds the last N keyframes only
+    if "--map-window" in argv:
+        i = argv.index("--map-window")
+        map_window = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+        if map_window < 1:
+            print("--map-window needs a positive number of keyframes")
+            return 2
+        if map_voxel is None:
+            print("--map-window bounds the voxel map: it needs --map VOXEL")
+            return 2
+        if "--streams" in argv:
+            print("--map-window is not supported together with --streams: the windowed map runs on the sequential driver only "
+                  "(drop --streams)")
             return 2
     views_dir, views_every = None, 0  # tum.write_map_views of the finished map: every keyframe's pose, or every K-th frame's
     if "--map-views-every" in argv:
@@ -118,6 +137,8 @@ def main(argv=None):
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
         drawer = ply.ModelExporter() if model_dir else None
         vmap = api.VoxelMap(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"])) if map_voxel else None
+        if map_window:
+            vmap = api.MapWindow(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"]), window=map_window)
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
                       mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances)
         nd = tum.default_decoders() if decoders is None else decoders
@@ -143,6 +164,11 @@ def main(argv=None):
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
         if vmap is not None:
             _save_map(vmap, name, _rvm_path(map_save, name, len(io["datasets"]) > 1))
+            if map_window:
+                with open("map_window_%s.txt" % name, "w") as f:
+                    for ts, T in zip(vmap.timestamps, vmap.keyframes):
+                        f.write("%.9f %s\n" % (ts, " ".join("%.9g" % x for x in T.reshape(16))))
+                print("Map window: the last %d of %d keyframes -> map_window_%s.txt" % (len(vmap.keyframes), drv.nKeyFrames, name))
             if views_dir is not None:
                 _save_views(vmap, os.path.join(views_dir, name) if len(io["datasets"]) > 1 else views_dir,
                             drv.poses, [kf for _, kf in res], views_every, io["depth_scale_factor"])
