@@ -769,6 +769,96 @@ int revo_map_subtract(revo_map* dst, revo_map* src);
 /* The voxel edge and cloud mode the map was created with (either output may be NULL). */
 int revo_map_voxel_size(revo_map* m, float* voxel, int* dense);
 
+/* ---- registration of voxel maps -----------------------------------------------------------------------
+ * Every map operation above assumes the maps share one world frame.  These calls say how two maps lie relative to each
+ * other: point-to-point ICP between the voxels' mean points, with the nearest destination voxel found in the 27 voxels
+ * around the transformed source point.  A record of sums is, like every record of this library, a pure function of the
+ * two maps and the pose: the same bytes whatever the table sizes, the integration order, the grid shape or the stream.
+ *
+ * revo_map_coarsen: every voxel of src is added into dst under the key whose axis indices are src's shifted right by
+ * `shift` (1 .. 20) arithmetically -- floor(k / 2^shift) on the unbiased index, repacked with the 2^20 bias; count, sum_q
+ * and sum_bgr are carried unchanged.  dst's voxel edge must be, bit for bit, src's times 2^shift.  All or nothing on
+ * max_voxels and counters exactly as revo_map_merge (points_dropped and keyframes come from src); waits for src; src is
+ * not changed.  REVO_ERR_INVALID_ARG: NULL, dst == src, shift outside 1 .. 20, another edge ratio, different devices.
+ * Contract: the result is byte for byte (revo_map_export_raw) the map a handle with the coarse edge builds from the same
+ * keyframes, provided no input point was dropped for key range -- with |pw| < 2048 m that is guaranteed for
+ * voxel >= 2^-9 m.  (fdiv_rn(pw, 2^s v) = 2^-s fdiv_rn(pw, v) exactly in the normal range, floor(floor(y) / 2^s) =
+ * floor(y / 2^s), and q and the colours do not depend on the edge.) */
+int revo_map_coarsen(revo_map* dst, revo_map* src, int shift);
+
+typedef struct revo_map_align_params {
+  float    max_dist;       /* finite, 0 < max_dist <= dst's voxel edge: a match farther than this is rejected        */
+  uint32_t min_count_dst;  /* as revo_map_extract's min_count, for the destination voxels                            */
+  uint32_t min_count_src;  /* ... and for the source voxels                                                          */
+  float    centre[3];      /* finite: the point (destination frame) the rotation increment turns about               */
+} revo_map_align_params;
+
+/* Per source voxel with count >= max(min_count_src, 1), in float32 with every operation rounded on its own:
+ *   p   the voxel's point exactly as revo_map_extract returns it;
+ *   p'  = ((R[:,0]*px + R[:,1]*py) + R[:,2]*pz) + t;
+ *   k_i = floorf(p'_i / voxel_dst); the voxel is SKIPPED (and counted) if p' is not finite, some |p'_i| >= 2048 or
+ *         some k_i lies outside [-2^20, 2^20 - 1];
+ *   candidates: the up to 27 destination voxels with indices k + {-1,0,1}^3 that lie in range, are present and have
+ *         count >= max(min_count_dst, 1); for each, q as revo_map_extract gives it, d = p' - q per axis,
+ *         d2 = (dx*dx + dy*dy) + dz*dz;
+ *   the match is the candidate with the smallest (d2, packed key) pair, accepted iff d2 <= max_dist*max_dist (one float
+ *         product, formed on the host).
+ * Per accepted match, with u = p' - centre and r = p' - q, these float terms are summed:
+ *   S[0..2]   u_x, u_y, u_z
+ *   S[3..8]   u_x*u_x, u_x*u_y, u_x*u_z, u_y*u_y, u_y*u_z, u_z*u_z
+ *   S[9..11]  r_x, r_y, r_z
+ *   S[12..14] u x r, two terms per point and axis: u_y*r_z and -(u_z*r_y); u_z*r_x and -(u_x*r_z); u_x*r_y and -(u_y*r_x)
+ *   S[15]     r_x*r_x, r_y*r_y, r_z*r_z (three terms)
+ * Each S is the float nearest the exact sum of its float terms (carried as a double-double from the first addition on
+ * and rounded once; DESIGN 4.1's midpoint caveat applies).  The counts are exact. */
+typedef struct revo_map_align_info {   /* 160 bytes, little-endian, no padding holes */
+  float    S[16];
+  uint64_t matched;      /* accepted matches                                                                          */
+  uint64_t considered;   /* source voxels with count >= max(min_count_src, 1)                                         */
+  uint64_t skipped;      /* of those, the ones whose p' left the key range                                            */
+  float    centre[3], max_dist;  /* copied from the parameters                                                        */
+  float    R[9], T[3];   /* the pose the sums were taken at (source -> destination, R column-major), as given         */
+  int32_t  flags;        /* bit0: no evaluation (pose not finite or not orthogonal): everything else in the record is
+                            then zero except the pose, centre and max_dist                                            */
+  int32_t  reserved;     /* zero */
+} revo_map_align_info;
+
+/* One record per pose (n >= 1 poses, 4x4 column-major, source -> destination frame).  The call caches the source's points
+ * and the destination's means (two small launches), evaluates all n poses in ONE launch on dst's context's tracker stream
+ * -- behind the pending integrations of both maps; it waits for src as revo_map_merge does -- and waits for the result.
+ * out: n records, host memory (device_out = 0) or device memory of the maps' device, 16-byte aligned (device_out = 1).
+ * Neither map is changed; dst == src is allowed; the voxel edges may differ.  An empty source or destination gives
+ * matched = 0 and zero sums.  REVO_ERR_INVALID_ARG: NULL, n < 1, max_dist outside its range, a centre that is not finite,
+ * maps on different devices, a misaligned device output. */
+int revo_map_align_eval(revo_map* dst, revo_map* src, int n, const float* T_dst_src_n16, const revo_map_align_params* prm,
+                        revo_map_align_info* out, int device_out);
+
+/* Host only.  The record's sums widened into the Gauss-Newton system of point-to-point ICP for the increment
+ * x = (v, w) applied on the left about centre, p'(x) = centre + exp(w)(p' - centre) + v; with n = matched:
+ *   H = [[n I, -[Su]x], [[Su]x, S(|u|^2 I - u u^T)]]  (6x6, row == column major),  g = [Sr ; S u x r];  cost = S[15].
+ * The step is the solution of H x = -g.  REVO_ERR_INVALID_ARG: NULL, or a record with flags bit0. */
+int revo_map_align_system(const revo_map_align_info* info, double H[36], double g[6]);
+
+typedef struct revo_map_align_opts {
+  int32_t  max_iters;    /* >= 1                                                                                      */
+  int32_t  reserved;     /* zero                                                                                      */
+  double   eps_t, eps_r; /* converged when max|v| < eps_t (m) and max|w| < eps_r (rad)                                */
+  uint64_t min_matched;  /* fewer accepted matches than this: lost                                                    */
+} revo_map_align_opts;
+enum { REVO_ALIGN_CONVERGED = 0, REVO_ALIGN_ITER_LIMIT = 1, REVO_ALIGN_LOST = 2 };
+
+/* Gauss-Newton in double on the host over revo_map_align_eval's records (the caches are built once per call): evaluate at
+ * the current pose rounded to float; solve H x = -g with the Cholesky and pivot rule of revo_pair_info_covariance; update
+ * T <- Tr(c) exp(x) Tr(-c) T (exp: the SE(3) exponential, x = (v, w)); stop when the step is below eps_t / eps_r
+ * (converged) or after max_iters evaluations (iteration limit).  Lost: matched < min_matched or a rank-deficient H; T_out
+ * is then the last pose that had a system (T_init if none had).  info_out is the record at T_out, from one more
+ * evaluation, so (T_out, info_out) satisfies the eval contract on its own.  *iterations = systems evaluated.
+ * opt == NULL: 30 iterations, 1e-6 m, 1e-6 rad, 12 matches.  info_out, iterations may be NULL.
+ * REVO_ERR_INVALID_ARG: as revo_map_align_eval, a T_init that is not finite, max_iters < 1. */
+int revo_map_align(revo_map* dst, revo_map* src, const float T_init[16], const revo_map_align_params* prm,
+                   const revo_map_align_opts* opt, float T_out[16], revo_map_align_info* info_out, int32_t* iterations,
+                   int32_t* status);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -399,6 +399,59 @@ class VoxelMap:
         m.merge_raw(rec, header["points_dropped"], header["keyframes"])
         return m
 
+    # -- registration (revo_map_coarsen / revo_map_align*)
+    def coarsen(self, shift, max_voxels=1 << 24):
+        """A new map on the same context with a voxel edge 2^shift times as long, holding this map's sums: byte for byte the
+        map built at that edge from the same keyframes (while no point was dropped for key range).  This map is unchanged."""
+        out = VoxelMap(self.cameraPyr, float(np.ldexp(np.float32(self.voxel), int(shift))), dense=self.dense, max_voxels=max_voxels,
+                       initial_voxels=max(1, self.info()["voxels"]))
+        check(_lib.lib().revo_map_coarsen(out._h, self._h, int(shift)))
+        return out
+
+    def _align_params(self, max_dist, min_count_dst, min_count_src, centre):
+        p = MapAlignParams()
+        p.max_dist = self.voxel if max_dist is None else float(max_dist)
+        p.min_count_dst, p.min_count_src = int(min_count_dst), int(min_count_src)
+        p.centre[:] = [float(x) for x in np.asarray(centre, np.float32).reshape(3)]
+        return p
+
+    def align_eval(self, src, poses, max_dist=None, min_count_dst=1, min_count_src=1, centre=(0.0, 0.0, 0.0), d_out=None):
+        """The registration sums of `src` against this map (the destination) at each pose (4x4, source -> destination frame; one
+        pose or a list / (n, 4, 4) array): MapAlignInfo records, all from one launch.  max_dist defaults to this map's voxel
+        edge.  d_out: a torch uint8 device tensor of n x 160 bytes takes the records instead (returns None).  Waits."""
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        T = T.reshape(-1, 4, 4)
+        n = len(T)
+        flat = np.ascontiguousarray(np.concatenate([_cm4(M) for M in T]))
+        p = self._align_params(max_dist, min_count_dst, min_count_src, centre)
+        if d_out is not None:
+            if not (d_out.is_cuda and d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= n * C.sizeof(MapAlignInfo)):
+                raise ValueError("d_out must be a contiguous device tensor of n x %d bytes" % C.sizeof(MapAlignInfo))
+            import torch
+            torch.cuda.current_stream(d_out.device).synchronize()
+            check(_lib.lib().revo_map_align_eval(self._h, src._h, n, _p(flat, f32p), C.byref(p), vp(d_out.data_ptr()), 1))
+            return None
+        out = (MapAlignInfo * n)()
+        check(_lib.lib().revo_map_align_eval(self._h, src._h, n, _p(flat, f32p), C.byref(p), C.cast(out, vp), 0))
+        return out[0] if single else list(out)
+
+    def align(self, src, T_init=None, max_dist=None, min_count_dst=1, min_count_src=1, centre=(0.0, 0.0, 0.0), max_iters=30,
+              eps_t=1e-6, eps_r=1e-6, min_matched=12):
+        """Point-to-point ICP of `src` onto this map from T_init (4x4, source -> destination; identity by default): Gauss-Newton
+        on the host over align_eval's records.  -> dict: T (4x4 float32), info (the MapAlignInfo at T), iterations, status
+        (settings.ALIGN_CONVERGED / ALIGN_ITER_LIMIT / ALIGN_LOST), cov (6x6, sigma2 H^-1 with sigma2 = S[15] / (3 matched - 6);
+        None when H cannot be inverted) and sigma2."""
+        p = self._align_params(max_dist, min_count_dst, min_count_src, centre)
+        o = MapAlignOpts(int(max_iters), 0, float(eps_t), float(eps_r), int(min_matched))
+        T0 = _cm4(np.eye(4) if T_init is None else T_init)
+        T1 = np.zeros(16, np.float32)
+        info, it, st = MapAlignInfo(), C.c_int32(), C.c_int32()
+        check(_lib.lib().revo_map_align(self._h, src._h, _p(T0, f32p), C.byref(p), C.byref(o), _p(T1, f32p), C.byref(info),
+                                        C.byref(it), C.byref(st)))
+        cov, s2 = align_covariance(info)
+        return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2}
+
     def _views(self, T_w_c, camera, zrange, splat_max, min_count):
         """-> (MapView array, single): camera None = the context's level-0 camera and depth range (zrange must be None too),
         else an api.Camera or (fx, fy, cx, cy, width, height) and zrange (zmin, zmax) or None = the context's range."""
@@ -476,6 +529,48 @@ class VoxelMap:
         ms = C.c_float()
         check(_lib.lib().revo_map_render_last_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+def align_system(info):
+    """(H [6, 6], g [6]) float64 of a MapAlignInfo: the Gauss-Newton system of revo_map_align_system (unknowns v, w)."""
+    H, g = np.zeros(36, np.float64), np.zeros(6, np.float64)
+    check(_lib.lib().revo_map_align_system(C.byref(info), _p(H, C.POINTER(C.c_double)), _p(g, C.POINTER(C.c_double))))
+    return H.reshape(6, 6), g
+
+
+def align_covariance(info):
+    """(cov [6, 6] = sigma2 H^-1, sigma2 = S[15] / (3 matched - 6)) of a record; (None, None) without an evaluation, with too
+    few matches or with a singular H."""
+    if (info.flags & 1) or 3 * info.matched <= 6:
+        return None, None
+    H, _ = align_system(info)
+    s2 = float(info.S[15]) / float(3 * info.matched - 6)
+    try:
+        X = np.linalg.inv(H)
+    except np.linalg.LinAlgError:
+        return None, None
+    return s2 * 0.5 * (X + X.T), s2
+
+
+def align_maps(dst, src, T_init=None, shifts=(2, 1, 0), centre=None, min_count_dst=1, min_count_src=1, **align_kw):
+    """Coarse-to-fine registration of `src` onto `dst` (two VoxelMaps of the same voxel edge): per level of `shifts` both maps
+    are coarsened by that shift (0: the maps themselves), aligned with max_dist = that level's edge, and the pose is handed
+    down.  centre defaults to the mean of the source's points under T_init, rounded to float32, and stays fixed for the
+    whole ladder.  -> the finest level's align() result, with "levels": every level's result."""
+    T = np.eye(4, dtype=np.float32) if T_init is None else np.asarray(T_init, np.float32)
+    if centre is None:
+        xyz = src.points(min_count_src)[0].astype(np.float64)
+        centre = (T[:3, :3].astype(np.float64) @ xyz.mean(0) + T[:3, 3]).astype(np.float32) if len(xyz) else np.zeros(3, np.float32)
+    levels = []
+    for sh in shifts:
+        d, s_ = (dst, src) if sh == 0 else (dst.coarsen(sh), src.coarsen(sh))
+        r = d.align(s_, T, max_dist=d.voxel, min_count_dst=min_count_dst, min_count_src=min_count_src, centre=centre, **align_kw)
+        if sh != 0:
+            d.close()
+            s_.close()
+        levels.append(r)
+        T = r["T"]
+    return dict(levels[-1], levels=levels, centre=np.asarray(centre, np.float32))
 
 
 class MapWindow:

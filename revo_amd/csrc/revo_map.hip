@@ -25,6 +25,8 @@
 
 #include "revo_internal.h"
 #include "revo_map.h"
+#include "revo_track_dev.h"
+#include "revo_align_host.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -238,8 +240,16 @@ struct MapMergeK {
   u64* keys; MapVal* vals; unsigned mask;
   MapStats* st;
   u64 dropped;  // joins the batch's dropped points once
+  int shift;    // MERGE_COARSE: every axis index of a source key is shifted right by this (revo_map_coarsen)
 };
-enum { MERGE_RAW = 0, MERGE_TABLE = 1 };
+enum { MERGE_RAW = 0, MERGE_TABLE = 1, MERGE_COARSE = 2 };  // MERGE_COARSE: MERGE_TABLE with the keys rewritten
+
+// The key of the voxel of edge 2^shift times as long that holds this one: floor(k / 2^shift) per axis on the unbiased index.
+__device__ __forceinline__ u64 map_coarse_key(u64 key, int shift) {
+  const int kx = (int)((key >> 42) & 0x1fffffu) - (1 << 20), ky = (int)((key >> 21) & 0x1fffffu) - (1 << 20),
+            kz = (int)(key & 0x1fffffu) - (1 << 20);
+  return ((u64)((kx >> shift) + (1 << 20)) << 42) | ((u64)((ky >> shift) + (1 << 20)) << 21) | (u64)((kz >> shift) + (1 << 20));
+}
 #define MAP_POISON (1ull << 40)  // > MAP_MAX_VOXELS: a batch whose new-voxel count holds it is refused by k_map_commit
 
 // Occupied slots as raw records, compacted in arrival order (the host sorts by key); at most cap_out are written.
@@ -283,11 +293,12 @@ __global__ void __launch_bounds__(256) k_map_merge(const MapMergeK a) {
   ulonglong2 r0{}, r1{}, r2{}, r3{};  // key n | qx qy | qz sb | sg sr
   bool bad = false;
   if (i < a.n) {
-    if (SRC == MERGE_TABLE) {
+    if (SRC != MERGE_RAW) {
       key = a.skeys[i];
       if (key != MAP_EMPTY) {
         const ulonglong2* v = (const ulonglong2*)(a.svals + i);
         const ulonglong2 p = v[0], q = v[1], c = v[2], d = v[3];
+        if (SRC == MERGE_COARSE) key = map_coarse_key(key, a.shift);
         r0 = make_ulonglong2(key, p.x); r1 = make_ulonglong2(p.y, q.x); r2 = make_ulonglong2(q.y, c.x); r3 = make_ulonglong2(c.y, d.x);
         if (r0.y == 0) key = MAP_EMPTY;  // a committed voxel has count >= 1
       }
@@ -954,6 +965,12 @@ extern "C" int revo_map_export_raw(revo_map* m, revo_map_voxel_raw* dst, size_t 
 // record can be bad (validated on the host, or a map's own table).  Grows for bound more keys, then the fused launch, or the
 // checked path (insert, commit, rollback, accumulate) when the device has to decide -- max_voxels in reach, or records nobody
 // has looked at -- and then waits for the decision.
+template <int MODE>
+static void launch_merge(int src_kind, dim3 grid, hipStream_t s, const MapMergeK& a) {
+  if (src_kind == MERGE_TABLE) hipLaunchKernelGGL((k_map_merge<MODE, MERGE_TABLE>), grid, dim3(256), 0, s, a);
+  else if (src_kind == MERGE_COARSE) hipLaunchKernelGGL((k_map_merge<MODE, MERGE_COARSE>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_map_merge<MODE, MERGE_RAW>), grid, dim3(256), 0, s, a);
+}
 static int merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool trusted, int keyframes) {
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t ub = occ_bound(m);
@@ -977,20 +994,16 @@ static int merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool
   if (!trusted) HIPCHECK(hipMemsetAsync(&m->d_st->bad, 0, sizeof(u64), s));
   a.keys = m->d_keys; a.vals = m->d_vals; a.mask = (unsigned)(m->cap - 1); a.st = m->d_st;
   const dim3 grid((a.n + 255) / 256), blk(256);
-  const bool tab = src_kind == MERGE_TABLE;
   if (!chk) {
-    if (tab) hipLaunchKernelGGL((k_map_merge<MAP_FUSED, MERGE_TABLE>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_map_merge<MAP_FUSED, MERGE_RAW>), grid, blk, 0, s, a);
+    launch_merge<MAP_FUSED>(src_kind, grid, s, a);
     hipLaunchKernelGGL(k_map_commit, dim3(1), dim3(64), 0, s, st->d_com, 1);
     HIPCHECK(hipGetLastError());
     return REVO_OK;
   }
-  if (tab) hipLaunchKernelGGL((k_map_merge<MAP_INSERT, MERGE_TABLE>), grid, blk, 0, s, a);
-  else hipLaunchKernelGGL((k_map_merge<MAP_INSERT, MERGE_RAW>), grid, blk, 0, s, a);
+  launch_merge<MAP_INSERT>(src_kind, grid, s, a);
   hipLaunchKernelGGL(k_map_commit, dim3(1), dim3(64), 0, s, st->d_com, 1);
   hipLaunchKernelGGL(k_map_rollback, dim3((unsigned)((m->cap + 255) / 256)), blk, 0, s, m->d_keys, m->d_vals, (unsigned)m->cap, m->d_st);
-  if (tab) hipLaunchKernelGGL((k_map_merge<MAP_ACCUM, MERGE_TABLE>), grid, blk, 0, s, a);
-  else hipLaunchKernelGGL((k_map_merge<MAP_ACCUM, MERGE_RAW>), grid, blk, 0, s, a);
+  launch_merge<MAP_ACCUM>(src_kind, grid, s, a);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(s));  // the device has decided
   if (m->h_pub[2]) return REVO_OK;
@@ -1270,3 +1283,377 @@ extern "C" void revo_map_note_attach_(revo_map* m, revo_vo_multi* mv, int stream
   if (!attach && it != m->attached.end()) m->attached.erase(it);
 }
 extern "C" const revo_ctx* revo_map_ctx_(const revo_map* m) { return m ? m->ctx : nullptr; }
+
+// ------------------------------------------------------------------------------------------------- registration (16) --
+// revo_map_coarsen / revo_map_align_eval / revo_map_align (contract: include/revo_hip.h).
+extern "C" int revo_map_coarsen(revo_map* dst, revo_map* src, int shift) {
+  if (!dst || !src) return fail(REVO_ERR_INVALID_ARG, "null map");
+  if (dst == src) return fail(REVO_ERR_INVALID_ARG, "a map cannot be coarsened into itself");
+  if (shift < 1 || shift > 20) return fail(REVO_ERR_INVALID_ARG, "shift must be 1 .. 20");
+  const float want = std::ldexp(src->voxel, shift);  // exact, or inf
+  if (memcmp(&dst->voxel, &want, sizeof(float)))
+    return fail(REVO_ERR_INVALID_ARG, "the destination's voxel edge is not the source's times 2^shift");
+  if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
+  MapStats ss;  // waits for src: its table is complete, and its counters say what comes
+  { const int rc = read_stats(src, &ss); if (rc) return rc; }
+  if (ss.kfs > 0x7fffffffull) return fail(REVO_ERR_INVALID_ARG, "the source map's keyframe count does not fit");
+  HIPCHECK(hipSetDevice(dst->g.device));
+  MapMergeK a{};
+  a.skeys = src->d_keys; a.svals = src->d_vals; a.n = (unsigned)src->cap;
+  a.dropped = ss.drop;
+  a.shift = shift;
+  const int rc = merge_core(dst, a, MERGE_COARSE, (size_t)ss.occ, true, (int)ss.kfs);
+  if (dst->g.stream != src->g.stream && hipStreamSynchronize((hipStream_t)dst->g.stream) != hipSuccess && !rc)
+    return fail(REVO_ERR_HIP, "hipStreamSynchronize failed");
+  return rc;
+}
+
+#define ALIGN_THREADS 256
+#define ALIGN_WAVES (ALIGN_THREADS / 64)
+#define ALIGN_CHUNK 512        // source points per chunk: workgroup g of a pose takes the chunks g, g + G, ...
+#define ALIGN_MAX_GROUPS 1024  // workgroups per pose at most
+#define ALIGN_PART 32          // doubles of a workgroup's partial: 16 heads, 16 tails
+enum { AW_MATCHED = 16, AW_CONSIDERED = 18, AW_SKIPPED = 20, AW_CENTRE = 22, AW_MAXD = 25, AW_R = 26, AW_T = 35, AW_FLAGS = 38,
+       AW_END = 40 };  // words of a revo_map_align_info record
+static_assert(sizeof(revo_map_align_info) == 4 * AW_END && sizeof(revo_map_align_info) % 16 == 0 &&
+              offsetof(revo_map_align_info, matched) == 4 * AW_MATCHED && offsetof(revo_map_align_info, considered) == 4 * AW_CONSIDERED &&
+              offsetof(revo_map_align_info, skipped) == 4 * AW_SKIPPED && offsetof(revo_map_align_info, centre) == 4 * AW_CENTRE &&
+              offsetof(revo_map_align_info, max_dist) == 4 * AW_MAXD && offsetof(revo_map_align_info, R) == 4 * AW_R &&
+              offsetof(revo_map_align_info, T) == 4 * AW_T && offsetof(revo_map_align_info, flags) == 4 * AW_FLAGS,
+              "record layout");
+
+typedef u64 __attribute__((address_space(1)))* map_gu64p;
+typedef unsigned __attribute__((address_space(1)))* map_gu32p;
+#define MAP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+struct MapAlignK {  // what every pose of a launch shares
+  const float4* pts; const unsigned* npts;                   // the source's points, compacted (k_map_align_points)
+  const u64* dkeys; const float4* dmean; unsigned dmask;     // the destination's keys and, per slot, its mean (k_map_align_means)
+  float voxel, maxd, maxd2, centre[3];
+  const float* poses;                                        // per pose 12 floats: R column-major, t
+  double* part; unsigned* cnt; unsigned* ticket;
+  revo_map_align_info* out;
+};
+
+__device__ __forceinline__ float map_mean(u64 q, double n) { return (float)((double)(long long)q / n * 0x1p-20); }  // k_map_extract
+
+// The per-call caches.  Source: the points of the slots with count >= min_count, compacted in arrival order (every sum over
+// them is exact, so the order cannot show).  Destination: per slot the mean and, in w, whether the voxel is a candidate
+// (present and count >= min_count; a slot emptied by a subtraction in flight has count 0 and is absent).
+__global__ void __launch_bounds__(256) k_map_align_points(const u64* __restrict__ keys, const MapVal* __restrict__ vals, unsigned cap,
+                                                          u64 min_count, unsigned* total, float4* out, unsigned cap_out) {
+  __shared__ unsigned s_n, s_base;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  MapVal v{};
+  bool sel = false;
+  if (i < cap && keys[i] != MAP_EMPTY) { v = vals[i]; sel = v.n >= min_count; }
+  const unsigned o = sel ? atomicAdd(&s_n, 1u) : 0u;
+  __syncthreads();
+  if (threadIdx.x == 0) s_base = s_n ? atomicAdd(total, s_n) : 0u;
+  __syncthreads();
+  if (!sel) return;
+  const unsigned j = s_base + o;
+  if (j >= cap_out) return;
+  const double n = (double)v.n;
+  out[j] = make_float4(map_mean(v.qx, n), map_mean(v.qy, n), map_mean(v.qz, n), 0.0f);
+}
+__global__ void __launch_bounds__(256) k_map_align_means(const u64* __restrict__ keys, const MapVal* __restrict__ vals, unsigned cap,
+                                                         u64 min_count, float4* out) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cap) return;
+  float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (keys[i] != MAP_EMPTY) {
+    const MapVal v = vals[i];
+    if (v.n >= min_count) { const double n = (double)v.n; m = make_float4(map_mean(v.qx, n), map_mean(v.qy, n), map_mean(v.qz, n), 1.0f); }
+  }
+  out[i] = m;
+}
+
+// 16 double-double values: lane L ends with the wave total of value align_slot(L & 15) in h[0], l[0] (reduce32x's tree)
+__device__ __forceinline__ int align_slot(int lane) { return ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3); }
+__device__ __forceinline__ void align_reduce16(double* h, double* l, int lane) {
+  butterfly_step_x<8, 1>(h, l, lane);
+  butterfly_step_x<4, 2>(h, l, lane);
+  butterfly_step_x<2, 4>(h, l, lane);
+  butterfly_step_x<1, 8>(h, l, lane);
+  dd_add(h[0], l[0], lane_xor_d<16>(h[0]), lane_xor_d<16>(l[0]));
+  dd_add(h[0], l[0], lane_xor_d<32>(h[0]), lane_xor_d<32>(l[0]));
+}
+
+// Grid (G, poses), revo_info.hip's shape: workgroup g of a pose takes the chunks g, g + G, ... of the source's points, one
+// point per thread and round.  Per point: p', its voxel index in the destination, the nearest of the up to 27 candidates
+// around it by (d2, key) -- a bounded probe per candidate that touches nothing, a miss being the normal case -- and, if the
+// match is accepted, the point's float terms into 16 double-double sums.  Per workgroup: wave butterfly, LDS, the partial
+// published write-through, a ticket; whoever draws the last one adds the G partials in a fixed order and writes the record.
+__global__ void __launch_bounds__(ALIGN_THREADS) k_map_align(const MapAlignK a) {
+  __shared__ double s_h[ALIGN_WAVES][16], s_l[ALIGN_WAVES][16];
+  __shared__ unsigned s_c[ALIGN_WAVES][2];
+  const int pose = blockIdx.y, grp = blockIdx.x, G = gridDim.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  unsigned* const rec = (unsigned*)(a.out + pose);
+
+  const float* P = a.poses + 12 * (size_t)pose;
+  float R[9], T[3];
+  unsigned Rb[9], Tb[3];
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { R[i] = P[i]; Rb[i] = __float_as_uint(R[i]); finite = finite && __builtin_isfinite(R[i]); }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { T[i] = P[9 + i]; Tb[i] = __float_as_uint(T[i]); finite = finite && __builtin_isfinite(T[i]); }
+  const bool no_eval = !finite || !is_orthogonal(R);
+  // the record's tail (centre, max_dist, pose, flags, reserved): the same whether or not the pose is evaluated
+  unsigned tail = 0u;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tail = lane == AW_CENTRE + i ? __float_as_uint(a.centre[i]) : tail;
+  tail = lane == AW_MAXD ? __float_as_uint(a.maxd) : tail;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) tail = lane == AW_R + i ? Rb[i] : tail;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tail = lane == AW_T + i ? Tb[i] : tail;
+  tail = lane == AW_FLAGS ? (no_eval ? 1u : 0u) : tail;
+  if (no_eval) {  // the same for every workgroup of the pose
+    if (grp == 0 && tid < AW_END) rec[tid] = tail;
+    return;
+  }
+
+  unsigned N = *a.npts;
+  double xd[32];  // 16 double-double slots: heads, then tails
+#pragma unroll
+  for (int k = 0; k < 32; ++k) xd[k] = 0.0;
+  unsigned matched = 0, skipped = 0;
+  const unsigned nchunks = (N + ALIGN_CHUNK - 1) / ALIGN_CHUNK;
+  for (unsigned ch = grp; ch < nchunks; ch += G) {
+    const unsigned end = (ch + 1) * ALIGN_CHUNK < N ? (ch + 1) * ALIGN_CHUNK : N;
+#pragma unroll 1
+    for (unsigned i = ch * ALIGN_CHUNK + tid; i < end; i += ALIGN_THREADS) {
+      const float4 p = a.pts[i];
+      float pt[3];
+      int k[3];
+      bool ok = true;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        pt[c] = ((R[c] * p.x + R[3 + c] * p.y) + R[6 + c] * p.z) + T[c];
+        const float f = floorf(__fdiv_rn(pt[c], a.voxel));
+        ok = ok && fabsf(pt[c]) < 2048.0f && f >= -1048576.0f && f <= 1048575.0f;  // NaN / inf fail every comparison
+        k[c] = ok ? (int)f : 0;
+      }
+      if (!ok) { ++skipped; continue; }
+      float best = 0.0f, bq[3] = {0.0f, 0.0f, 0.0f};
+      u64 bkey = MAP_EMPTY;  // no candidate yet: every packed key is smaller
+#pragma unroll 1
+      for (int c = 0; c < 27; ++c) {
+        const int kx = k[0] + c / 9 - 1, ky = k[1] + (c / 3) % 3 - 1, kz = k[2] + c % 3 - 1;
+        if (((kx + (1 << 20)) | (ky + (1 << 20)) | (kz + (1 << 20))) >> 21) continue;  // an index outside [-2^20, 2^20 - 1]
+        const u64 key = ((u64)(kx + (1 << 20)) << 42) | ((u64)(ky + (1 << 20)) << 21) | (u64)(kz + (1 << 20));
+        const unsigned s = map_find(a.dkeys, a.dmask, key);
+        if (s == ~0u) continue;
+        const float4 q = a.dmean[s];
+        if (q.w == 0.0f) continue;
+        const float dx = pt[0] - q.x, dy = pt[1] - q.y, dz = pt[2] - q.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (bkey == MAP_EMPTY || d2 < best || (d2 == best && key < bkey)) { best = d2; bkey = key; bq[0] = q.x; bq[1] = q.y; bq[2] = q.z; }
+      }
+      if (bkey == MAP_EMPTY || !(best <= a.maxd2)) continue;
+      ++matched;
+      const float ux = pt[0] - a.centre[0], uy = pt[1] - a.centre[1], uz = pt[2] - a.centre[2];
+      const float rx = pt[0] - bq[0], ry = pt[1] - bq[1], rz = pt[2] - bq[2];
+#define ALIGN_ACC(slot, term) dd_acc(xd[slot], xd[16 + (slot)], (double)(term))
+      ALIGN_ACC(0, ux); ALIGN_ACC(1, uy); ALIGN_ACC(2, uz);
+      ALIGN_ACC(3, ux * ux); ALIGN_ACC(4, ux * uy); ALIGN_ACC(5, ux * uz); ALIGN_ACC(6, uy * uy); ALIGN_ACC(7, uy * uz); ALIGN_ACC(8, uz * uz);
+      ALIGN_ACC(9, rx); ALIGN_ACC(10, ry); ALIGN_ACC(11, rz);
+      ALIGN_ACC(12, uy * rz); ALIGN_ACC(12, -(uz * ry));
+      ALIGN_ACC(13, uz * rx); ALIGN_ACC(13, -(ux * rz));
+      ALIGN_ACC(14, ux * ry); ALIGN_ACC(14, -(uy * rx));
+      ALIGN_ACC(15, rx * rx); ALIGN_ACC(15, ry * ry); ALIGN_ACC(15, rz * rz);
+#undef ALIGN_ACC
+    }
+  }
+  align_reduce16(xd, xd + 16, lane);  // lane L: the wave's total of slot align_slot(L & 15)
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { matched += __shfl_xor(matched, off, 64); skipped += __shfl_xor(skipped, off, 64); }
+  if (lane < 16) { s_h[wave][align_slot(lane)] = xd[0]; s_l[wave][align_slot(lane)] = xd[16]; }
+  if (lane == 0) { s_c[wave][0] = matched; s_c[wave][1] = skipped; }
+  __syncthreads();
+  if (wave != 0) return;
+
+  // wave 0: the workgroup's partial (waves in index order), published write-through, then the ticket
+  const int k = lane & 15;
+  double h = s_h[0][k], l = s_l[0][k];
+  unsigned c = lane < 2 ? s_c[0][lane] : 0u;
+#pragma unroll
+  for (int w = 1; w < ALIGN_WAVES; ++w) { dd_add(h, l, s_h[w][k], s_l[w][k]); c += lane < 2 ? s_c[w][lane] : 0u; }
+  map_gu64p mine = (map_gu64p)(a.part + ((size_t)pose * G + grp) * ALIGN_PART);
+  if (lane < 16) {
+    __hip_atomic_store(mine + k, (u64)__double_as_longlong(h), MAP_RLX_AGENT);
+    __hip_atomic_store(mine + 16 + k, (u64)__double_as_longlong(l), MAP_RLX_AGENT);
+  }
+  map_gu32p cnts = (map_gu32p)(a.cnt + ((size_t)pose * G) * 2);
+  if (lane < 2) __hip_atomic_store(cnts + 2 * grp + lane, c, MAP_RLX_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial has left this CU before the ticket is drawn
+  unsigned drawn = 0u;
+  if (lane == 0) drawn = __hip_atomic_fetch_add((map_gu32p)(a.ticket + pose), 1u, MAP_RLX_AGENT);
+  drawn = (unsigned)__builtin_amdgcn_readfirstlane((int)drawn);
+  if (drawn != (unsigned)(G - 1)) return;
+
+  // the last workgroup of the pose to arrive: every partial is published.  Lane L adds slot L & 15 of the groups L >> 4,
+  // (L >> 4) + 4, ... in index order; the four quarter sums meet across the lanes.
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  map_gu64p all = (map_gu64p)(a.part + (size_t)pose * G * ALIGN_PART);
+  h = 0.0; l = 0.0;
+  u64 n_matched = 0, n_skipped = 0;
+  for (int g = lane >> 4; g < G; g += 4) {
+    const double gh = __longlong_as_double((long long)__hip_atomic_load(all + (size_t)g * ALIGN_PART + k, MAP_RLX_AGENT));
+    const double gl = __longlong_as_double((long long)__hip_atomic_load(all + (size_t)g * ALIGN_PART + 16 + k, MAP_RLX_AGENT));
+    dd_add(h, l, gh, gl);
+  }
+  dd_add(h, l, lane_xor_d<16>(h), lane_xor_d<16>(l));
+  dd_add(h, l, lane_xor_d<32>(h), lane_xor_d<32>(l));
+  for (int g = 0; g < G; ++g) {
+    n_matched += __hip_atomic_load(cnts + 2 * g, MAP_RLX_AGENT);
+    n_skipped += __hip_atomic_load(cnts + 2 * g + 1, MAP_RLX_AGENT);
+  }
+  const float f = dd_to_float(h, l);
+  unsigned w = tail;
+  w = lane < 16 ? __float_as_uint(f) : w;
+  w = lane == AW_MATCHED ? (unsigned)n_matched : (lane == AW_MATCHED + 1 ? (unsigned)(n_matched >> 32) : w);
+  w = lane == AW_CONSIDERED ? N : w;
+  w = lane == AW_SKIPPED ? (unsigned)n_skipped : (lane == AW_SKIPPED + 1 ? (unsigned)(n_skipped >> 32) : w);
+  if (lane < AW_END) rec[lane] = w;
+}
+
+// The caches and scratch of one registration call: built once, used by every evaluation of the call, freed at its end.
+struct MapAlignCall {
+  revo_map* dst = nullptr;
+  char* buf = nullptr;
+  MapAlignK k{};
+  float* h_pose = nullptr;  // pinned, n_max x 12
+  float* d_pose = nullptr;
+  revo_map_align_info* d_out = nullptr;  // n_max records
+  int n_max = 0, groups = 1;
+  ~MapAlignCall() {
+    if (dst) { (void)hipStreamSynchronize((hipStream_t)dst->g.stream); }
+    (void)hipFree(buf); (void)hipHostFree(h_pose);
+    (void)hipGetLastError();
+  }
+};
+
+static int align_check(revo_map* dst, revo_map* src, const revo_map_align_params* prm) {
+  if (!dst || !src || !prm) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (!std::isfinite(prm->max_dist) || !(prm->max_dist > 0.0f) || !(prm->max_dist <= dst->voxel))
+    return fail(REVO_ERR_INVALID_ARG, "max_dist must be finite, > 0 and at most the destination's voxel edge");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(prm->centre[i])) return fail(REVO_ERR_INVALID_ARG, "the centre is not finite");
+  if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
+  return REVO_OK;
+}
+
+// Waits for src (as revo_map_merge does), then enqueues the two cache launches on dst's stream.
+static int align_begin(MapAlignCall* c, revo_map* dst, revo_map* src, const revo_map_align_params* prm, int n_max) {
+  MapStats ss;
+  { const int rc = read_stats(src, &ss); if (rc) return rc; }
+  HIPCHECK(hipSetDevice(dst->g.device));
+  hipStream_t s = (hipStream_t)dst->g.stream;
+  const size_t npts = std::max<size_t>((size_t)ss.occ, 1);
+  c->n_max = n_max;
+  c->groups = (int)std::min<size_t>(ALIGN_MAX_GROUPS, (npts + ALIGN_CHUNK - 1) / ALIGN_CHUNK);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  // the words a launch zeroes (tickets) and the point count open the allocation, each a block of its own
+  const size_t o_tick = 0, o_npts = o_tick + up(sizeof(unsigned) * n_max), o_pts = o_npts + 256, o_mean = o_pts + up(sizeof(float4) * npts),
+               o_pose = o_mean + up(sizeof(float4) * dst->cap), o_part = o_pose + up(sizeof(float) * 12 * n_max),
+               o_cnt = o_part + up(sizeof(double) * ALIGN_PART * c->groups * n_max), o_out = o_cnt + up(sizeof(unsigned) * 2 * c->groups * n_max),
+               total = o_out + up(sizeof(revo_map_align_info) * n_max);
+  HIPCHECK(hipMalloc((void**)&c->buf, total));
+  HIPCHECK(hipHostMalloc((void**)&c->h_pose, sizeof(float) * 12 * n_max));
+  c->dst = dst;
+  MapAlignK& k = c->k;
+  k.ticket = (unsigned*)(c->buf + o_tick);
+  unsigned* d_npts = (unsigned*)(c->buf + o_npts);
+  float4* d_pts = (float4*)(c->buf + o_pts);
+  float4* d_mean = (float4*)(c->buf + o_mean);
+  c->d_pose = (float*)(c->buf + o_pose);
+  k.pts = d_pts; k.npts = d_npts; k.dkeys = dst->d_keys; k.dmean = d_mean; k.dmask = (unsigned)(dst->cap - 1);
+  k.voxel = dst->voxel; k.maxd = prm->max_dist; k.maxd2 = prm->max_dist * prm->max_dist;
+  for (int i = 0; i < 3; ++i) k.centre[i] = prm->centre[i];
+  k.poses = c->d_pose;
+  k.part = (double*)(c->buf + o_part); k.cnt = (unsigned*)(c->buf + o_cnt);
+  c->d_out = (revo_map_align_info*)(c->buf + o_out);
+  HIPCHECK(hipMemsetAsync(d_npts, 0, 16, s));
+  hipLaunchKernelGGL(k_map_align_points, dim3((unsigned)((src->cap + 255) / 256)), dim3(256), 0, s, src->d_keys, src->d_vals,
+                     (unsigned)src->cap, (u64)std::max<uint32_t>(prm->min_count_src, 1), d_npts, d_pts, (unsigned)npts);
+  hipLaunchKernelGGL(k_map_align_means, dim3((unsigned)((dst->cap + 255) / 256)), dim3(256), 0, s, dst->d_keys, dst->d_vals,
+                     (unsigned)dst->cap, (u64)std::max<uint32_t>(prm->min_count_dst, 1), d_mean);
+  HIPCHECK(hipGetLastError());
+  return REVO_OK;
+}
+
+// n <= n_max poses (4x4 column-major) in one launch; records to `out` (device memory) or, out == NULL, to the call's own.
+static int align_launch(MapAlignCall* c, int n, const float* T16, revo_map_align_info* d_out) {
+  hipStream_t s = (hipStream_t)c->dst->g.stream;
+  HIPCHECK(hipStreamSynchronize(s));  // the previous upload has read the pinned poses
+  for (int i = 0; i < n; ++i) {
+    const float* T = T16 + 16 * (size_t)i;
+    float* P = c->h_pose + 12 * (size_t)i;
+    for (int col = 0; col < 3; ++col)
+      for (int r = 0; r < 3; ++r) P[3 * col + r] = T[4 * col + r];
+    for (int r = 0; r < 3; ++r) P[9 + r] = T[12 + r];
+  }
+  HIPCHECK(hipMemcpyAsync(c->d_pose, c->h_pose, sizeof(float) * 12 * n, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemsetAsync(c->k.ticket, 0, (sizeof(unsigned) * n + 15) / 16 * 16, s));
+  MapAlignK k = c->k;
+  k.out = d_out ? d_out : c->d_out;
+  hipLaunchKernelGGL(k_map_align, dim3((unsigned)c->groups, (unsigned)n), dim3(ALIGN_THREADS), 0, s, k);
+  HIPCHECK(hipGetLastError());
+  return REVO_OK;
+}
+
+static int align_eval_host(MapAlignCall* c, const float T[16], revo_map_align_info* out) {
+  { const int rc = align_launch(c, 1, T, nullptr); if (rc) return rc; }
+  hipStream_t s = (hipStream_t)c->dst->g.stream;
+  HIPCHECK(hipMemcpyAsync(out, c->d_out, sizeof(revo_map_align_info), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+extern "C" int revo_map_align_eval(revo_map* dst, revo_map* src, int n, const float* T, const revo_map_align_params* prm,
+                                   revo_map_align_info* out, int device_out) {
+  { const int rc = align_check(dst, src, prm); if (rc) return rc; }
+  if (!T || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n < 1 || n > 65535) return fail(REVO_ERR_INVALID_ARG, "revo_map_align_eval: n must be 1 .. 65535");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_out && ((uintptr_t)out & 15)) return fail(REVO_ERR_INVALID_ARG, "the device output is not 16-byte aligned");
+  MapAlignCall c;
+  { const int rc = align_begin(&c, dst, src, prm, n); if (rc) return rc; }
+  { const int rc = align_launch(&c, n, T, device_out ? out : nullptr); if (rc) return rc; }
+  hipStream_t s = (hipStream_t)dst->g.stream;
+  if (!device_out) HIPCHECK(hipMemcpyAsync(out, c.d_out, sizeof(revo_map_align_info) * n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+extern "C" int revo_map_align_system(const revo_map_align_info* info, double H[36], double g[6]) {
+  if (!info || !H || !g) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (info->flags & 1) return fail(REVO_ERR_INVALID_ARG, "the record carries no evaluation (flags bit0)");
+  align_system_fill(info, H, g);
+  return REVO_OK;
+}
+
+extern "C" int revo_map_align(revo_map* dst, revo_map* src, const float T_init[16], const revo_map_align_params* prm,
+                              const revo_map_align_opts* opt, float T_out[16], revo_map_align_info* info_out, int32_t* iterations,
+                              int32_t* status) {
+  { const int rc = align_check(dst, src, prm); if (rc) return rc; }
+  if (!T_init || !T_out || !status) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (!pose_finite(T_init)) return fail(REVO_ERR_INVALID_ARG, "T_init is not finite");
+  revo_map_align_opts o{30, 0, 1e-6, 1e-6, 12};
+  if (opt) o = *opt;
+  if (o.max_iters < 1) return fail(REVO_ERR_INVALID_ARG, "max_iters must be >= 1");
+  MapAlignCall c;
+  { const int rc = align_begin(&c, dst, src, prm, 1); if (rc) return rc; }
+  int32_t it = 0;
+  const int rc = align_loop(T_init, prm->centre, o, [&](const float* Tf, revo_map_align_info* rec) { return align_eval_host(&c, Tf, rec); },
+                            T_out, info_out, &it, status);
+  if (rc) return rc;
+  if (iterations) *iterations = it;
+  return REVO_OK;
+}

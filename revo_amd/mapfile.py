@@ -12,6 +12,7 @@ Equal maps give equal files.
     python -m revo_amd.mapfile info FILE...            what each file holds
     python -m revo_amd.mapfile merge OUT FILE...       the union of the files' maps (same voxel edge), without a GPU
     python -m revo_amd.mapfile subtract A B -o OUT      map A without map B's sums: undoes `merge A OUT B`, without a GPU
+    python -m revo_amd.mapfile coarsen A SHIFT -o OUT   map A with a voxel edge 2^SHIFT times as long (revo_map_coarsen), without a GPU
     python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
 """
 import struct
@@ -149,6 +150,30 @@ def subtract_records(a, b):
     return out[~dead]
 
 
+def coarsen_records(records, shift):
+    """The records of the map with a voxel edge 2^shift times as long (revo_map_coarsen): every axis index of a key becomes
+    floor(k / 2^shift) on the unbiased index; records that meet under one key are added."""
+    shift = int(shift)
+    if not 1 <= shift <= 20:
+        raise ValueError("shift must be 1 .. 20")
+    rec = as_records(records).copy()
+    check_records(rec, canonical=False)
+    key, bias, m = rec["key"], np.int64(1 << 20), np.uint64(0x1fffff)
+    ax = [((((key >> np.uint64(sh)) & m).astype(np.int64) - bias) >> np.int64(shift)) + bias for sh in (42, 21, 0)]
+    rec["key"] = (ax[0].astype(np.uint64) << np.uint64(42)) | (ax[1].astype(np.uint64) << np.uint64(21)) | ax[2].astype(np.uint64)
+    return merge_records(rec, np.zeros(0, RAW_DTYPE))
+
+
+def coarsen_file(path, shift):
+    """(header, records) of the file's map coarsened by `shift`: the voxel edge times 2^shift, the counters unchanged."""
+    header, rec = read(path)
+    out = coarsen_records(rec, shift)
+    voxel = float(np.ldexp(np.float32(header["voxel"]), int(shift)))
+    if not np.isfinite(voxel):
+        raise ValueError("the coarse voxel edge is not finite")
+    return dict(header, voxel=voxel, voxels=len(out)), out
+
+
 def to_points(records, min_count=1):
     """(xyz N x 3 float32, rgb N x 3 uint8 as R,G,B, count N uint32) of the records with count >= max(min_count, 1), in their
     order -- what revo_map_extract gives: xyz = float32(float64(sum_q) / float64(count) * 2^-20), colour = (sum + count // 2)
@@ -213,6 +238,14 @@ def main(argv=None):
             write(out, h, rec)
             print("%s: %d voxels (%s without %s)" % (out, len(rec), a, b))
             return 0
+        if cmd == "coarsen" and len(args) == 4 and "-o" in args[:3]:
+            i = args.index("-o")
+            out = args[i + 1]
+            a, shift = args[:i] + args[i + 2:]
+            h, rec = coarsen_file(a, int(shift))
+            write(out, h, rec)
+            print("%s: %d voxels of %g m (%s coarsened by %d)" % (out, len(rec), h["voxel"], a, int(shift)))
+            return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -223,7 +256,8 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         print("mapfile: %s" % e)
         return 1
-    print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | ply FILE [OUT.ply]")
+    print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | coarsen A SHIFT -o OUT | "
+          "ply FILE [OUT.ply]")
     return 2
 
 

@@ -181,6 +181,31 @@ class MapView(C.Structure):
 assert C.sizeof(MapView) == 104
 
 
+class MapAlignParams(C.Structure):
+    """revo_map_align_params (include/revo_hip.h): the gate, the count thresholds and the rotation centre of a registration."""
+    _fields_ = [("max_dist", C.c_float), ("min_count_dst", C.c_uint32), ("min_count_src", C.c_uint32), ("centre", C.c_float * 3)]
+
+
+class MapAlignInfo(C.Structure):
+    """revo_map_align_info (include/revo_hip.h), 160 bytes: the 16 sums of point-to-point ICP between two voxel maps at a
+    pose -- each the float nearest the exact sum of its terms -- the exact counts, and the inputs they were taken at."""
+    _fields_ = [
+        ("S", C.c_float * 16), ("matched", C.c_uint64), ("considered", C.c_uint64), ("skipped", C.c_uint64),
+        ("centre", C.c_float * 3), ("max_dist", C.c_float), ("R", C.c_float * 9), ("T", C.c_float * 3),
+        ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class MapAlignOpts(C.Structure):
+    """revo_map_align_opts (include/revo_hip.h): where revo_map_align's Gauss-Newton iteration stops."""
+    _fields_ = [("max_iters", C.c_int32), ("reserved", C.c_int32), ("eps_t", C.c_double), ("eps_r", C.c_double),
+                ("min_matched", C.c_uint64)]
+
+
+assert C.sizeof(MapAlignParams) == 24 and C.sizeof(MapAlignInfo) == 160 and C.sizeof(MapAlignOpts) == 32
+ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_LOST = 0, 1, 2
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
