@@ -859,6 +859,82 @@ int revo_map_align(revo_map* dst, revo_map* src, const float T_init[16], const r
                    const revo_map_align_opts* opt, float T_out[16], revo_map_align_info* info_out, int32_t* iterations,
                    int32_t* status);
 
+/* ---- point-to-plane registration: per-voxel normals ---------------------------------------------------
+ * Point-to-point ICP penalises sliding along a surface, so on dense maps every step is short.  The point-to-plane metric
+ * needs a surface normal per destination voxel; a normal is, like a voxel's point, a pure function of the map.
+ *
+ * revo_map_normals: the voxels of revo_map_extract(m, min_count, ...) in the same (ascending key) order, each with its
+ * point xyz[3], normal[3], lambda[3] (l0 <= l1 <= l2) and neighbours.  Every output pointer except n may be NULL; with all
+ * four NULL only *n is written (cap is then ignored), otherwise cap < *n is REVO_ERR_CAPACITY.  All arithmetic is float32
+ * with every operation rounded on its own.  For a voxel with index k, count >= max(min_count, 1) and point m0:
+ *   neighbours: the voxels at k + {-1,0,1}^3 (the voxel itself included) that are in key range, present and have
+ *         count >= max(min_count, 1), visited with the x offset outermost and the z offset innermost, each -1, 0, 1;
+ *         m_j is the neighbour's point exactly as revo_map_extract gives it; nb is their number;
+ *   with d = m_j - m0, added sequentially in that order from +0: S1 += d (3 sums), S2 += d d^T (6 sums: xx, xy, xz, yy,
+ *         yz, zz, one product each);
+ *   C_ij = S2_ij - (S1_i * S1_j) / (float)nb   (one product, one division, one subtraction; 6 entries, C symmetric);
+ *   eigen-decomposition: A = C, V = I, then 6 cyclic Jacobi sweeps over (p,q) = (0,1), (0,2), (1,2).  A rotation is skipped
+ *         when a_pq == 0; otherwise, with r the third index,
+ *           theta = (a_qq - a_pp) / (2 * a_pq);  t = copysign(1, theta) / (|theta| + sqrt(theta*theta + 1));
+ *           c = 1 / sqrt(t*t + 1);  s = t*c;  h = t * a_pq;  a_pp = a_pp - h;  a_qq = a_qq + h;  a_pq = 0;
+ *           (a_rp, a_rq) <- (c*a_rp - s*a_rq, s*a_rp + c*a_rq);
+ *           (V_ip, V_iq) <- (c*V_ip - s*V_iq, s*V_ip + c*V_iq) for the rows i = 0, 1, 2;
+ *   l0 <= l1 <= l2: a_00, a_11, a_22 after the sweeps, sorted with ties to the lower index; the normal is the column of V
+ *         that belongs to l0, each component divided by norm = sqrt((x*x + y*y) + z*z); then negated if its component of
+ *         largest magnitude (lowest index at ties) is negative;
+ *   valid iff nb >= min_neighbours, the three components are finite, l1 > 0, l0 <= planarity * l1 and
+ *         l1 >= min_spread * l2 (one product each); an invalid normal is reported as (0, 0, 0).  lambda and neighbours are
+ *         reported either way.
+ * The map is not written; an empty map gives *n = 0.  REVO_ERR_INVALID_ARG: NULL map or n, min_neighbours < 3, a
+ * planarity outside (0, 1) or a min_spread outside [0, 1) (or not finite). */
+typedef struct revo_map_normals_params {
+  uint32_t min_count;       /* as revo_map_extract's: voxels below it neither get a normal nor count as neighbours */
+  uint32_t min_neighbours;  /* >= 3; neighbours include the voxel itself                                            */
+  float    planarity;       /* finite, 0 < planarity < 1: valid only if l0 <= planarity * l1                        */
+  float    min_spread;      /* finite, 0 <= min_spread < 1: valid only if l1 > 0 and l1 >= min_spread * l2          */
+} revo_map_normals_params;   /* NULL: 1, 5, 0.1f, 0.1f */
+int revo_map_normals(revo_map* m, const revo_map_normals_params* prm, float* xyz, float* normal, float* lambda,
+                     uint32_t* neighbours, size_t cap, size_t* n);
+
+/* The point-to-plane record of one pose.  Everything up to the match is revo_map_align_eval's contract, word for word
+ * (p, p', skipping, the 27 candidates, d2, the (d2, packed key) minimum, the inclusive gate), with one change: a
+ * destination voxel is a candidate only if it also has a valid normal under nprm, whose min_count must equal
+ * max(prm->min_count_dst, 1).  Per accepted match, with u = p' - centre, r = p' - q, (nx, ny, nz) the matched voxel's
+ * normal, float32 with every operation rounded on its own:
+ *   e  = (nx*rx + ny*ry) + nz*rz;
+ *   a  = u x n:  ax = uy*nz - uz*ny,  ay = uz*nx - ux*nz,  az = ux*ny - uy*nx  (two products and one subtraction each);
+ *   J  = (nx, ny, nz, ax, ay, az);
+ *   S[0..20]  J_i*J_j for i <= j, row by row (00 01 .. 05 11 .. 55);  S[21..26]  J_i*e;  S[27]  e*e  (one product each).
+ * Each S is the float nearest the exact sum of its float terms (double-double from the first addition, rounded once;
+ * DESIGN 4.1's midpoint caveat applies).  The counts are exact. */
+typedef struct revo_map_plane_info {   /* 208 bytes, little-endian, no padding holes */
+  float    S[28];
+  uint64_t matched, considered, skipped;  /* as revo_map_align_info's                                                 */
+  float    centre[3], max_dist;
+  float    R[9], T[3];
+  int32_t  flags;        /* bit0 as revo_map_align_info's: everything else is then zero except pose, centre, max_dist */
+  int32_t  dst_normals;  /* destination voxels with a valid normal, exact (saturating at INT32_MAX)                   */
+} revo_map_plane_info;
+
+/* revo_map_align_eval for the point-to-plane metric: the same arguments, caches, launch shape, streams and waits, plus
+ * the destination's normal table (nprm == NULL: the defaults with min_count = max(prm->min_count_dst, 1)), built once per
+ * call.  A destination without any valid normal gives matched = 0, zero sums and dst_normals = 0.
+ * REVO_ERR_INVALID_ARG: as revo_map_align_eval and revo_map_normals, and nprm->min_count != max(prm->min_count_dst, 1). */
+int revo_map_align_plane_eval(revo_map* dst, revo_map* src, int n, const float* T_dst_src_n16,
+                              const revo_map_align_params* prm, const revo_map_normals_params* nprm,
+                              revo_map_plane_info* out, int device_out);
+
+/* Host only.  For the increment x = (v, w) applied on the left about centre (revo_map_align_system's convention),
+ * e(x) ~ e + n.v + w.(u x n) = e + J.x:  H = sum J J^T, the symmetric 6x6 matrix whose upper triangle is S[0..20];
+ * g = sum J e = S[21..26];  cost = S[27].  The step solves H x = -g.  REVO_ERR_INVALID_ARG: NULL, or flags bit0. */
+int revo_map_align_plane_system(const revo_map_plane_info* info, double H[36], double g[6]);
+
+/* revo_map_align's Gauss-Newton loop over revo_map_align_plane_eval's records: the same options, Cholesky and pivot rule,
+ * update T <- Tr(c) exp(x) Tr(-c) T, stopping rule and statuses.  A single plane leaves H rank-deficient: lost. */
+int revo_map_align_plane(revo_map* dst, revo_map* src, const float T_init[16], const revo_map_align_params* prm,
+                         const revo_map_normals_params* nprm, const revo_map_align_opts* opt, float T_out[16],
+                         revo_map_plane_info* info_out, int32_t* iterations, int32_t* status);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

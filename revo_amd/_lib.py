@@ -8,7 +8,7 @@ import os
 import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
-                       PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MAX_LEVELS)
+                       PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -149,6 +149,12 @@ def lib():
     L.revo_map_align_system.argtypes = [C.POINTER(MapAlignInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.revo_map_align.argtypes = [vp, vp, f32p, C.POINTER(MapAlignParams), C.POINTER(MapAlignOpts), f32p,
                                  C.POINTER(MapAlignInfo), i32p, i32p]
+    L.revo_map_normals.argtypes = [vp, C.POINTER(MapNormalsParams), f32p, f32p, f32p, C.POINTER(C.c_uint32), C.c_size_t,
+                                   C.POINTER(C.c_size_t)]
+    L.revo_map_align_plane_eval.argtypes = [vp, vp, C.c_int, f32p, C.POINTER(MapAlignParams), C.POINTER(MapNormalsParams), vp, C.c_int]
+    L.revo_map_align_plane_system.argtypes = [C.POINTER(MapPlaneInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.revo_map_align_plane.argtypes = [vp, vp, f32p, C.POINTER(MapAlignParams), C.POINTER(MapNormalsParams), C.POINTER(MapAlignOpts),
+                                       f32p, C.POINTER(MapPlaneInfo), i32p, i32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

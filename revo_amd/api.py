@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -291,9 +291,12 @@ class VoxelMap:
                                  n.value, C.byref(m)))
         return xyz[:m.value], rgb[:m.value], cnt[:m.value]
 
-    def save_ply(self, path, min_count=1):
-        """Binary little-endian PLY, one vertex per voxel in key order: xyz float32, RGB uchar, `count` uint32."""
+    def save_ply(self, path, min_count=1, normals=False):
+        """Binary little-endian PLY, one vertex per voxel in key order: xyz float32, RGB uchar, `count` uint32; with
+        normals=True also nx ny nz float32 (normals(min_count) at its defaults; (0, 0, 0) where there is no valid normal)."""
         from . import ply
+        if normals:
+            return ply.write_voxel_ply_normals(path, *self.points(min_count), self.normals(min_count)[1])
         return ply.write_voxel_ply(path, *self.points(min_count))
 
     # -- the map as data (revo_map_export_raw / revo_map_merge*, DESIGN 13; records and files: revo_amd/mapfile.py)
@@ -452,6 +455,62 @@ class VoxelMap:
         cov, s2 = align_covariance(info)
         return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2}
 
+    # -- point-to-plane registration (revo_map_normals / revo_map_align_plane*)
+    @staticmethod
+    def _normals_params(min_count, min_neighbours, planarity, min_spread):
+        return MapNormalsParams(max(1, int(min_count)), int(min_neighbours), float(planarity), float(min_spread))
+
+    def normals(self, min_count=1, min_neighbours=5, planarity=0.1, min_spread=0.1):
+        """Per voxel of points(min_count), in its order: (xyz N x 3 float32, normal N x 3 float32 -- (0, 0, 0) where the
+        neighbourhood is no plane --, lambda N x 3 float32 ascending, neighbours N uint32).  A pure function of the map."""
+        L = _lib.lib()
+        p = MapNormalsParams(int(min_count), int(min_neighbours), float(planarity), float(min_spread))
+        n = C.c_size_t()
+        check(L.revo_map_normals(self._h, C.byref(p), None, None, None, None, 0, C.byref(n)))
+        xyz, nrm, lam = (np.empty((n.value, 3), np.float32) for _ in range(3))
+        nb = np.empty(n.value, np.uint32)
+        m = C.c_size_t()
+        check(L.revo_map_normals(self._h, C.byref(p), _p(xyz, f32p), _p(nrm, f32p), _p(lam, f32p), nb.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                 n.value, C.byref(m)))
+        return xyz[:m.value], nrm[:m.value], lam[:m.value], nb[:m.value]
+
+    def align_plane_eval(self, src, poses, max_dist=None, min_count_dst=1, min_count_src=1, centre=(0.0, 0.0, 0.0), min_neighbours=5,
+                         planarity=0.1, min_spread=0.1, d_out=None):
+        """align_eval for the point-to-plane metric: MapPlaneInfo records (208 bytes), all from one launch; only destination
+        voxels with a valid normal (min_neighbours, planarity, min_spread: see normals) are matched."""
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        T = T.reshape(-1, 4, 4)
+        n = len(T)
+        flat = np.ascontiguousarray(np.concatenate([_cm4(M) for M in T]))
+        p = self._align_params(max_dist, min_count_dst, min_count_src, centre)
+        q = self._normals_params(min_count_dst, min_neighbours, planarity, min_spread)
+        if d_out is not None:
+            if not (d_out.is_cuda and d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= n * C.sizeof(MapPlaneInfo)):
+                raise ValueError("d_out must be a contiguous device tensor of n x %d bytes" % C.sizeof(MapPlaneInfo))
+            import torch
+            torch.cuda.current_stream(d_out.device).synchronize()
+            check(_lib.lib().revo_map_align_plane_eval(self._h, src._h, n, _p(flat, f32p), C.byref(p), C.byref(q), vp(d_out.data_ptr()), 1))
+            return None
+        out = (MapPlaneInfo * n)()
+        check(_lib.lib().revo_map_align_plane_eval(self._h, src._h, n, _p(flat, f32p), C.byref(p), C.byref(q), C.cast(out, vp), 0))
+        return out[0] if single else list(out)
+
+    def align_plane(self, src, T_init=None, max_dist=None, min_count_dst=1, min_count_src=1, centre=(0.0, 0.0, 0.0), max_iters=30,
+                    eps_t=1e-6, eps_r=1e-6, min_matched=12, min_neighbours=5, planarity=0.1, min_spread=0.1):
+        """align() with the point-to-plane metric over align_plane_eval's records: the same loop, options and statuses.
+        -> dict as align's, info a MapPlaneInfo, cov = sigma2 H^-1 with sigma2 = S[27] / (matched - 6)."""
+        p = self._align_params(max_dist, min_count_dst, min_count_src, centre)
+        q = self._normals_params(min_count_dst, min_neighbours, planarity, min_spread)
+        o = MapAlignOpts(int(max_iters), 0, float(eps_t), float(eps_r), int(min_matched))
+        T0 = _cm4(np.eye(4) if T_init is None else T_init)
+        T1 = np.zeros(16, np.float32)
+        info, it, st = MapPlaneInfo(), C.c_int32(), C.c_int32()
+        check(_lib.lib().revo_map_align_plane(self._h, src._h, _p(T0, f32p), C.byref(p), C.byref(q), C.byref(o), _p(T1, f32p),
+                                              C.byref(info), C.byref(it), C.byref(st)))
+        cov, s2 = align_plane_covariance(info)
+        return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2}
+
     def _views(self, T_w_c, camera, zrange, splat_max, min_count):
         """-> (MapView array, single): camera None = the context's level-0 camera and depth range (zrange must be None too),
         else an api.Camera or (fx, fy, cx, cy, width, height) and zrange (zmin, zmax) or None = the context's range."""
@@ -552,11 +611,35 @@ def align_covariance(info):
     return s2 * 0.5 * (X + X.T), s2
 
 
-def align_maps(dst, src, T_init=None, shifts=(2, 1, 0), centre=None, min_count_dst=1, min_count_src=1, **align_kw):
+def align_plane_system(info):
+    """(H [6, 6], g [6]) float64 of a MapPlaneInfo: the Gauss-Newton system of revo_map_align_plane_system (unknowns v, w)."""
+    H, g = np.zeros(36, np.float64), np.zeros(6, np.float64)
+    check(_lib.lib().revo_map_align_plane_system(C.byref(info), _p(H, C.POINTER(C.c_double)), _p(g, C.POINTER(C.c_double))))
+    return H.reshape(6, 6), g
+
+
+def align_plane_covariance(info):
+    """(cov [6, 6] = sigma2 H^-1, sigma2 = S[27] / (matched - 6)) of a point-to-plane record (one residual per match);
+    (None, None) without an evaluation, with too few matches or with a singular H."""
+    if (info.flags & 1) or info.matched <= 6:
+        return None, None
+    H, _ = align_plane_system(info)
+    s2 = float(info.S[27]) / float(info.matched - 6)
+    try:
+        X = np.linalg.inv(H)
+    except np.linalg.LinAlgError:
+        return None, None
+    return s2 * 0.5 * (X + X.T), s2
+
+
+def align_maps(dst, src, T_init=None, shifts=(2, 1, 0), centre=None, min_count_dst=1, min_count_src=1, metric="point", **align_kw):
     """Coarse-to-fine registration of `src` onto `dst` (two VoxelMaps of the same voxel edge): per level of `shifts` both maps
     are coarsened by that shift (0: the maps themselves), aligned with max_dist = that level's edge, and the pose is handed
     down.  centre defaults to the mean of the source's points under T_init, rounded to float32, and stays fixed for the
-    whole ladder.  -> the finest level's align() result, with "levels": every level's result."""
+    whole ladder.  metric: "point" (align) or "plane" (align_plane, whose normal parameters go through align_kw).
+    -> the finest level's align() result, with "levels": every level's result."""
+    if metric not in ("point", "plane"):
+        raise ValueError("metric must be 'point' or 'plane'")
     T = np.eye(4, dtype=np.float32) if T_init is None else np.asarray(T_init, np.float32)
     if centre is None:
         xyz = src.points(min_count_src)[0].astype(np.float64)
@@ -564,7 +647,8 @@ def align_maps(dst, src, T_init=None, shifts=(2, 1, 0), centre=None, min_count_d
     levels = []
     for sh in shifts:
         d, s_ = (dst, src) if sh == 0 else (dst.coarsen(sh), src.coarsen(sh))
-        r = d.align(s_, T, max_dist=d.voxel, min_count_dst=min_count_dst, min_count_src=min_count_src, centre=centre, **align_kw)
+        r = (d.align_plane if metric == "plane" else d.align)(s_, T, max_dist=d.voxel, min_count_dst=min_count_dst,
+                                                               min_count_src=min_count_src, centre=centre, **align_kw)
         if sh != 0:
             d.close()
             s_.close()

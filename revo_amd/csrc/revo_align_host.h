@@ -1,4 +1,4 @@
-// revo_align_host.h -- the host arithmetic of revo_map_align (include/revo_hip.h): the Gauss-Newton system of a
+// revo_align_host.h -- the host arithmetic of revo_map_align and revo_map_align_plane (include/revo_hip.h): the Gauss-Newton system of a
 // record, its Cholesky solve, the SE(3) exponential and the iteration itself, over any evaluator of records.  Plain C++ with no
 // device code: revo_map.hip runs it over k_map_align, tests/cpp/align_host.cpp over recorded records.  Internal.
 #pragma once
@@ -95,10 +95,20 @@ inline void se3_exp_d(const double x[6], double* E) {
   }
 }
 
-// revo_map_align's loop.  eval(T column-major float[16], record*) -> 0 or an error code, which ends the loop and is returned.
-template <class Eval>
-inline int align_loop(const float T_init[16], const float centre[3], const revo_map_align_opts& o, Eval&& eval, float T_out[16],
-                      revo_map_align_info* rec_out, int* iterations, int* status) {
+// revo_map_align_plane_system's arithmetic: H = sum J J^T from its upper triangle, g = sum J e
+inline void align_plane_system_fill(const revo_map_plane_info* info, double H[36], double g[6]) {
+  const float* S = info->S;
+  int k = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[i * 6 + j] = H[j * 6 + i] = (double)S[k]; ++k; }
+  for (int i = 0; i < 6; ++i) g[i] = (double)S[21 + i];
+}
+
+// The Gauss-Newton loop of revo_map_align and revo_map_align_plane over records of type Rec (flags, matched) and their system
+// fill(const Rec*, H, g).  eval(T column-major float[16], Rec*) -> 0 or an error code, which ends the loop and is returned.
+template <class Rec, class Fill, class Eval>
+inline int align_loop_over(const float T_init[16], const float centre[3], const revo_map_align_opts& o, Fill&& fill, Eval&& eval,
+                           float T_out[16], Rec* rec_out, int* iterations, int* status) {
   double T[16], Tsys[16];  // row-major: the current pose, and the last pose that had a system
   for (int r = 0; r < 4; ++r)
     for (int col = 0; col < 4; ++col) T[4 * r + col] = (double)T_init[4 * col + r];
@@ -110,14 +120,14 @@ inline int align_loop(const float T_init[16], const float centre[3], const revo_
       for (int col = 0; col < 4; ++col) F[4 * col + r] = (float)M[4 * r + col];
   };
   int st = REVO_ALIGN_ITER_LIMIT, it = 0;
-  revo_map_align_info rec;
+  Rec rec;
   float Tf[16];
   while (it < o.max_iters) {
     to_float(T, Tf);
     { const int rc = eval(Tf, &rec); if (rc) return rc; }
     double H[36], g[6], x[6];
     bool have = !(rec.flags & 1) && rec.matched >= o.min_matched;
-    if (have) { align_system_fill(&rec, H, g); have = align_solve(H, g, x); }
+    if (have) { fill(&rec, H, g); have = align_solve(H, g, x); }
     if (!have) {
       st = REVO_ALIGN_LOST;
       memcpy(T, Tsys, sizeof(T));
@@ -141,4 +151,11 @@ inline int align_loop(const float T_init[16], const float centre[3], const revo_
   if (iterations) *iterations = it;
   *status = st;
   return 0;
+}
+
+// revo_map_align's loop: point-to-point records
+template <class Eval>
+inline int align_loop(const float T_init[16], const float centre[3], const revo_map_align_opts& o, Eval&& eval, float T_out[16],
+                      revo_map_align_info* rec_out, int* iterations, int* status) {
+  return align_loop_over<revo_map_align_info>(T_init, centre, o, align_system_fill, eval, T_out, rec_out, iterations, status);
 }

@@ -110,6 +110,44 @@ def write_voxel_ply(path, xyz, rgb, count):
     return path
 
 
+VOXEL_PLY_NORMALS_DTYPE = np.dtype(VOXEL_PLY_DTYPE.descr + [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")])  # 31 bytes per vertex
+
+
+def voxel_ply_normals_header(n):
+    return voxel_ply_header(n).replace(b"end_header\n", b"property float nx\nproperty float ny\nproperty float nz\nend_header\n")
+
+
+def write_voxel_ply_normals(path, xyz, rgb, count, normal):
+    """write_voxel_ply's file with the voxel's normal (api.VoxelMap.normals) as nx ny nz behind `count`."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.uint8).reshape(-1, 3)
+    count = np.asarray(count, np.uint32).reshape(-1)
+    normal = np.asarray(normal, np.float32).reshape(-1, 3)
+    if not (len(xyz) == len(rgb) == len(count) == len(normal)):
+        raise ValueError("xyz, rgb, count and normal must have one row per voxel")
+    v = np.empty(len(xyz), VOXEL_PLY_NORMALS_DTYPE)
+    v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    v["count"] = count
+    v["nx"], v["ny"], v["nz"] = normal[:, 0], normal[:, 1], normal[:, 2]
+    with open(path, "wb") as f:
+        f.write(voxel_ply_normals_header(len(v)))
+        f.write(v.tobytes())
+    return path
+
+
+def read_voxel_ply_normals(path):
+    """Reader for write_voxel_ply_normals' files -> (xyz, rgb, count as read_voxel_ply's, normal N x 3 float32)."""
+    data = open(path, "rb").read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    n = int([l for l in data[:end].decode("ascii").split("\n") if l.startswith("element vertex")][0].split()[2])
+    if data[:end] != voxel_ply_normals_header(n):
+        raise ValueError("not a voxel map PLY with normals")
+    v = np.frombuffer(data, VOXEL_PLY_NORMALS_DTYPE, count=n, offset=end)
+    return (np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["red"], v["green"], v["blue"]], 1), v["count"].copy(),
+            np.stack([v["nx"], v["ny"], v["nz"]], 1))
+
+
 def read_voxel_ply(path):
     """Reader for write_voxel_ply's files -> (xyz N x 3 float32, rgb N x 3 uint8, count N uint32)."""
     data = open(path, "rb").read()

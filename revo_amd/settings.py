@@ -206,6 +206,24 @@ assert C.sizeof(MapAlignParams) == 24 and C.sizeof(MapAlignInfo) == 160 and C.si
 ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_LOST = 0, 1, 2
 
 
+class MapNormalsParams(C.Structure):
+    """revo_map_normals_params (include/revo_hip.h): which voxels count, and when a neighbourhood is a plane."""
+    _fields_ = [("min_count", C.c_uint32), ("min_neighbours", C.c_uint32), ("planarity", C.c_float), ("min_spread", C.c_float)]
+
+
+class MapPlaneInfo(C.Structure):
+    """revo_map_plane_info (include/revo_hip.h), 208 bytes: the 28 sums of point-to-plane ICP between two voxel maps at a pose
+    (the upper triangle of sum J J^T, sum J e, sum e e), the exact counts, the inputs, and the destination's valid normals."""
+    _fields_ = [
+        ("S", C.c_float * 28), ("matched", C.c_uint64), ("considered", C.c_uint64), ("skipped", C.c_uint64),
+        ("centre", C.c_float * 3), ("max_dist", C.c_float), ("R", C.c_float * 9), ("T", C.c_float * 3),
+        ("flags", C.c_int32), ("dst_normals", C.c_int32),
+    ]
+
+
+assert C.sizeof(MapNormalsParams) == 16 and C.sizeof(MapPlaneInfo) == 208
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
