@@ -935,6 +935,64 @@ int revo_map_align_plane(revo_map* dst, revo_map* src, const float T_init[16], c
                          const revo_map_normals_params* nprm, const revo_map_align_opts* opt, float T_out[16],
                          revo_map_plane_info* info_out, int32_t* iterations, int32_t* status);
 
+/* ---- maps under a pose: posed merge and subtract ------------------------------------------------------
+ * Registration ends with a pose T (source -> destination).  These calls put a source map into the destination's frame.
+ * A voxel is integer sums, its point a pure function of them, and a float32 rigid transform with every operation rounded on
+ * its own a pure function of the point and the pose: "the source map seen under T" is a well-defined set of raw records,
+ * the same bytes whatever the table size, integration order, launch shape or stream.
+ *
+ * The posed record of a source voxel (key, n, sum_q, sum_bgr) under T (column-major, float32) at the destination edge
+ * voxel_dst, float32 with every operation rounded on its own:
+ *   p    the voxel's point exactly as revo_map_extract returns it: (float)((double)sum_q / (double)n * 2^-20);
+ *   p'_i = ((R_i0*px + R_i1*py) + R_i2*pz) + t_i   (revo_map_align_eval's p');
+ *   k_i  = floorf(p'_i / voxel_dst)   (one correctly rounded division);
+ *   the voxel is DROPPED when some p'_i is not finite, some |p'_i| >= 2048 or some k_i lies outside [-2^20, 2^20 - 1]
+ *        (revo_map_integrate's test);
+ *   otherwise q_i = (int64)rintf(p'_i * 2^20), and the posed record is: the key packed from k, count = n,
+ *        sum_q = n * q (an exact int64 product: |q| <= 2^31, n < 2^32), sum_bgr carried unchanged --
+ *        n points at the moved mean, with the voxel's own colour sums.
+ * Voxels with n < max(min_count, 1) are SKIPPED: neither moved nor dropped.  A source voxel with n >= 2^32 is a bad record
+ * (REVO_ERR_INVALID_ARG, nothing changed), as count 0 and key bit 63 are for revo_map_merge_raw.
+ * Counts and colour sums are conserved exactly; only positions are resampled. */
+typedef struct revo_map_pose_info {   /* 64 bytes, little-endian, no padding */
+  uint64_t voxels_in;       /* voxels of the source: moved + dropped + skipped */
+  uint64_t voxels_moved;    /* posed records made (before equal keys are summed) */
+  uint64_t voxels_dropped;
+  uint64_t voxels_skipped;
+  uint64_t points_moved;    /* the sums of count over the moved, dropped and skipped voxels */
+  uint64_t points_dropped;
+  uint64_t points_skipped;
+  uint64_t reserved;        /* zero */
+} revo_map_pose_info;
+
+/* The posed records of src; src is not changed.  Waits for src, runs on its context's tracker stream.
+ * device_out = 1: one record per moved voxel in unspecified order, keys may repeat (revo_map_merge_raw accepts that), into
+ *   device memory of src's device, 16-byte aligned; *n = voxels_moved.  A counting launch runs first, so that a refused call
+ *   writes nothing; the call then waits for the counters only: the records
+ *   are complete once the stream has run (any waiting call of the map, or work enqueued behind it on that stream).
+ * device_out = 0: the canonical form in host memory -- ascending keys, equal keys summed; *n = the keys.  Byte for byte what
+ *   revo_map_export_raw gives for an empty map of edge voxel_dst (max_voxels out of reach) after revo_map_merge_posed.
+ * out == NULL only counts (cap is ignored); cap < *n is REVO_ERR_CAPACITY with nothing written.  info may be NULL.
+ * REVO_ERR_INVALID_ARG, nothing written: NULL src, T or n; device_out not 0 or 1; a misaligned device output; voxel_dst not
+ * finite or not > 0; a T that is not finite (all 16 numbers); a rotation that fails the is_orthogonal rule of
+ * revo_map_align_eval (|R R^T - I|_F < 1e-5 and det > 0, float32); a source voxel with n >= 2^32. */
+int revo_map_pose_raw(revo_map* src, const float T_dst_src[16], float voxel_dst, size_t min_count, revo_map_voxel_raw* out,
+                      size_t cap, size_t* n, int device_out, revo_map_pose_info* info);
+/* By definition revo_map_merge_raw(dst, the device posed records of src at dst's voxel edge, voxels_moved, 1,
+ * src's points_dropped + info.points_dropped, src's keyframes): all or nothing on max_voxels exactly as there
+ * (REVO_ERR_CAPACITY, no voxel changed, keyframes_rejected += src's keyframes), and a no-op when no voxel moves.  The two
+ * edges and dense may differ.  The pose is checked before any table is touched.  Runs on dst's context's tracker stream
+ * behind both maps' pending work (it waits for src as revo_map_merge does) and waits for the device; the record buffer
+ * (64 bytes per source voxel) is freed once the stream has consumed it.  info may be NULL; it is filled whenever the posed
+ * records were made, also when the merge is then refused.
+ * REVO_ERR_INVALID_ARG, nothing changed: as revo_map_pose_raw's pose rules, NULL dst or src, dst == src, maps on different
+ * devices, a source voxel with n >= 2^32, a source keyframe count past INT32_MAX. */
+int revo_map_merge_posed(revo_map* dst, revo_map* src, const float T_dst_src[16], size_t min_count, revo_map_pose_info* info);
+/* The exact inverse: revo_map_subtract_raw over the same records and counters.  After revo_map_merge_posed followed by
+ * revo_map_subtract_posed with the same src, T and min_count dst is byte for byte what it was, counters included.  Every
+ * refusal rule of revo_map_subtract_raw applies, and dst is then untouched. */
+int revo_map_subtract_posed(revo_map* dst, revo_map* src, const float T_dst_src[16], size_t min_count, revo_map_pose_info* info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

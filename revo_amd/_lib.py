@@ -8,7 +8,7 @@ import os
 import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
-                       PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MAX_LEVELS)
+                       PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -155,6 +155,10 @@ def lib():
     L.revo_map_align_plane_system.argtypes = [C.POINTER(MapPlaneInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.revo_map_align_plane.argtypes = [vp, vp, f32p, C.POINTER(MapAlignParams), C.POINTER(MapNormalsParams), C.POINTER(MapAlignOpts),
                                        f32p, C.POINTER(MapPlaneInfo), i32p, i32p]
+    L.revo_map_pose_raw.argtypes = [vp, f32p, C.c_float, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int,
+                                    C.POINTER(MapPoseInfo)]
+    L.revo_map_merge_posed.argtypes = [vp, vp, f32p, C.c_size_t, C.POINTER(MapPoseInfo)]
+    L.revo_map_subtract_posed.argtypes = [vp, vp, f32p, C.c_size_t, C.POINTER(MapPoseInfo)]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -511,6 +511,62 @@ class VoxelMap:
         cov, s2 = align_plane_covariance(info)
         return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2}
 
+    # -- maps under a pose (revo_map_pose_raw / revo_map_merge_posed / revo_map_subtract_posed)
+    @staticmethod
+    def _pose_info(i):
+        return {k: int(getattr(i, k)) for k, _ in MapPoseInfo._fields_ if k != "reserved"}
+
+    def pose_raw(self, T, voxel=None, min_count=1, device=False):
+        """This map seen under the pose T (4x4, this map's frame -> the destination's) at the destination edge `voxel` (this
+        map's by default): per voxel with count >= min_count its count and colour sums at the moved mean point.
+        -> (records, info).  device=False: a mapfile.RAW_DTYPE array in the canonical form (ascending keys, equal keys summed):
+        what an empty map of that edge exports after merge_posed.  device=True: a torch uint8 device tensor, one 64-byte record
+        per moved voxel in unspecified order, keys may repeat -- what merge_raw / subtract_raw take.  info: a dict of
+        voxels_in, voxels_moved, voxels_dropped, voxels_skipped, points_moved, points_dropped, points_skipped."""
+        from . import mapfile
+        L = _lib.lib()
+        v = C.c_float(self.voxel if voxel is None else float(voxel))
+        Tc = _cm4(T)
+        n, i = C.c_size_t(), MapPoseInfo()
+        if device:
+            import torch
+            cap = self.info()["voxels"]
+            buf = torch.empty(64 * max(cap, 1), dtype=torch.uint8, device="cuda:%d" % self.cameraPyr.device)
+            check(L.revo_map_pose_raw(self._h, _p(Tc, f32p), v, int(min_count), vp(buf.data_ptr()), cap, C.byref(n), 1, C.byref(i)))
+            self.sync()  # the records are written
+            return buf[:64 * n.value], self._pose_info(i)
+        cap = self.info()["voxels"]  # the canonical form has at most one record per source voxel
+        rec = np.zeros(cap, mapfile.RAW_DTYPE)
+        check(L.revo_map_pose_raw(self._h, _p(Tc, f32p), v, int(min_count), rec.ctypes.data_as(vp) if cap else None, cap,
+                                  C.byref(n), 0, C.byref(i)))
+        return rec[:n.value], self._pose_info(i)
+
+    def merge_posed(self, src, T, min_count=1):
+        """Adds `src` (same device; the voxel edges and cloud modes may differ) as it lies under T (4x4, source -> this map's
+        frame): merge_raw of src.pose_raw(T, self.voxel, min_count) with src's points_dropped plus the move's and src's
+        keyframes, made on the device.  All or nothing on max_voxels (REVO_ERR_CAPACITY).  `src` is unchanged.  -> the info dict."""
+        i = MapPoseInfo()
+        check(_lib.lib().revo_map_merge_posed(self._h, src._h, _p(_cm4(T), f32p), int(min_count), C.byref(i)))
+        return self._pose_info(i)
+
+    def subtract_posed(self, src, T, min_count=1):
+        """The exact inverse of merge_posed(src, T, min_count): afterwards this map is byte for byte what it was before it,
+        counters included.  Refused (REVO_ERR_INVALID_ARG, nothing changed) as subtract_raw refuses.  -> the info dict."""
+        i = MapPoseInfo()
+        check(_lib.lib().revo_map_subtract_posed(self._h, src._h, _p(_cm4(T), f32p), int(min_count), C.byref(i)))
+        return self._pose_info(i)
+
+    def repose(self, src, T_old, T_new, min_count=1):
+        """A submap follows its corrected pose: subtract_posed(src, T_old) then merge_posed(src, T_new).  If the merge is
+        refused, src is merged back at T_old -- which restores this map exactly -- and the error is raised.
+        -> (info of the subtraction, info of the merge)."""
+        out = self.subtract_posed(src, T_old, min_count)
+        try:
+            return out, self.merge_posed(src, T_new, min_count)
+        except RevoError:
+            self.merge_posed(src, T_old, min_count)
+            raise
+
     def _views(self, T_w_c, camera, zrange, splat_max, min_count):
         """-> (MapView array, single): camera None = the context's level-0 camera and depth range (zrange must be None too),
         else an api.Camera or (fx, fy, cx, cy, width, height) and zrange (zmin, zmax) or None = the context's range."""
@@ -655,6 +711,19 @@ def align_maps(dst, src, T_init=None, shifts=(2, 1, 0), centre=None, min_count_d
         levels.append(r)
         T = r["T"]
     return dict(levels[-1], levels=levels, centre=np.asarray(centre, np.float32))
+
+
+def align_merge(dst, src, T_init=None, metric="plane", accept_limit=False, min_count=1, **ladder_kw):
+    """Registers `src` onto `dst` with align_maps(dst, src, T_init, metric=metric, **ladder_kw) and, if the ladder converged
+    (or stopped at its iteration limit and accept_limit is set), merges it at the pose found: dst.merge_posed(src, T,
+    min_count).  -> align_maps' result with "pose_info": merge_posed's info.  RuntimeError, dst unchanged: the ladder was lost,
+    or hit its iteration limit without accept_limit."""
+    from .settings import ALIGN_CONVERGED, ALIGN_ITER_LIMIT
+    r = align_maps(dst, src, T_init, metric=metric, **ladder_kw)
+    if not (r["status"] == ALIGN_CONVERGED or (accept_limit and r["status"] == ALIGN_ITER_LIMIT)):
+        raise RuntimeError("align_merge: the registration %s (nothing merged)"
+                           % ("stopped at its iteration limit" if r["status"] == ALIGN_ITER_LIMIT else "was lost"))
+    return dict(r, pose_info=dst.merge_posed(src, r["T"], min_count))
 
 
 class MapWindow:

@@ -27,6 +27,7 @@
 #include "revo_map.h"
 #include "revo_track_dev.h"
 #include "revo_align_host.h"
+#include "revo_pose_host.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -1958,4 +1959,206 @@ extern "C" int revo_map_align_plane(revo_map* dst, revo_map* src, const float T_
   if (rc) return rc;
   if (iterations) *iterations = it;
   return REVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------- maps under a pose (18) --
+// revo_map_pose_raw / revo_map_merge_posed / revo_map_subtract_posed (contract: include/revo_hip.h).
+struct MapPose { float r00, r01, r02, r10, r11, r12, r20, r21, r22, tx, ty, tz, voxel; };  // r_ij: row i, column j; the destination edge
+struct MapPoseK {
+  const u64* keys; const MapVal* vals; unsigned cap;  // the source table
+  u64 min_count;
+  MapPose T;
+  ulonglong2* out; unsigned cap_out;  // the posed records, at most cap_out of them (0: count only)
+  u64* info;                          // one 64-byte line: revo_map_pose_info's seven counters, then "a bad record was met"
+};
+enum { POSED_MOVED = 0, POSED_DROPPED = 1, POSED_SKIPPED = 2, POSED_BAD = 3 };
+
+// one axis of k_map_walk's test: the voxel index of p, and whether p and the index are in range (NaN / inf fail every comparison)
+__device__ __forceinline__ bool map_posed_axis(float p, float voxel, int& k) {
+  const float f = floorf(__fdiv_rn(p, voxel));
+  const bool ok = fabsf(p) < 2048.0f && f >= -1048576.0f && f <= 1048575.0f;
+  k = ok ? (int)f : 0;
+  return ok;
+}
+// The posed record of a voxel with count n >= 1 and coordinate sums sx, sy, sz: its key and its three sums n * q (the count
+// and the colour sums are carried by the caller).  The one text of the contract's arithmetic.
+__device__ __forceinline__ int map_posed_record(u64 n, u64 sx, u64 sy, u64 sz, const MapPose& T, u64 min_count, u64& key, u64& qx,
+                                                u64& qy, u64& qz) {
+  if (n >> 32) return POSED_BAD;
+  if (n < min_count) return POSED_SKIPPED;
+  const double inv = (double)n;
+  const float px = map_mean(sx, inv), py = map_mean(sy, inv), pz = map_mean(sz, inv);
+  const float x = ((T.r00 * px + T.r01 * py) + T.r02 * pz) + T.tx;
+  const float y = ((T.r10 * px + T.r11 * py) + T.r12 * pz) + T.ty;
+  const float z = ((T.r20 * px + T.r21 * py) + T.r22 * pz) + T.tz;
+  int kx, ky, kz;
+  bool ok = map_posed_axis(x, T.voxel, kx);
+  ok = map_posed_axis(y, T.voxel, ky) && ok;
+  ok = map_posed_axis(z, T.voxel, kz) && ok;
+  if (!ok) return POSED_DROPPED;
+  key = ((u64)(kx + (1 << 20)) << 42) | ((u64)(ky + (1 << 20)) << 21) | (u64)(kz + (1 << 20));
+  const long long m = (long long)n;  // < 2^32, and |q| <= 2^31: the products are exact
+  qx = (u64)(m * (long long)rintf(x * 1048576.0f));
+  qy = (u64)(m * (long long)rintf(y * 1048576.0f));
+  qz = (u64)(m * (long long)rintf(z * 1048576.0f));
+  return POSED_MOVED;
+}
+
+// One thread per slot of the source table: the value as four 16-byte loads, the posed record in registers, the moved ones
+// compacted as k_map_export compacts (LDS counter, one global atomic per block), the seven counters through LDS to the info
+// line with one atomic per block and counter.
+__global__ void __launch_bounds__(256) k_map_pose(const MapPoseK a) {
+  __shared__ unsigned s_n, s_base, s_bad;
+  __shared__ unsigned s_vox[4];  // voxels in, moved, dropped, skipped
+  __shared__ u64 s_pts[3];       // points moved, dropped, skipped
+  if (threadIdx.x < 4) s_vox[threadIdx.x] = 0;
+  if (threadIdx.x < 3) s_pts[threadIdx.x] = 0;
+  if (threadIdx.x == 0) { s_n = 0; s_bad = 0; }
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  const u64 skey = i < a.cap ? a.keys[i] : MAP_EMPTY;
+  ulonglong2 r0{}, r1{}, r2{}, r3{};  // key n | qx qy | qz sb | sg sr
+  int what = -1;
+  if (skey != MAP_EMPTY) {
+    const ulonglong2* v = (const ulonglong2*)(a.vals + i);
+    const ulonglong2 p = v[0], q = v[1], c = v[2], d = v[3];  // n qx | qy qz | sb sg | sr -
+    if (p.x != 0) {  // a committed voxel has count >= 1
+      u64 key = 0, qx = 0, qy = 0, qz = 0;
+      what = map_posed_record(p.x, p.y, q.x, q.y, a.T, a.min_count, key, qx, qy, qz);
+      r0 = make_ulonglong2(key, p.x); r1 = make_ulonglong2(qx, qy); r2 = make_ulonglong2(qz, c.x); r3 = make_ulonglong2(c.y, d.x);
+      if (what == POSED_BAD) {
+        atomicOr(&s_bad, 1u);
+      } else {
+        atomicAdd(&s_vox[0], 1u);
+        atomicAdd(&s_vox[1 + what], 1u);
+        atomicAdd(&s_pts[what], p.x);
+      }
+    }
+  }
+  const bool sel = what == POSED_MOVED;
+  const unsigned o = sel ? atomicAdd(&s_n, 1u) : 0u;
+  __syncthreads();
+  if (threadIdx.x == 0) s_base = s_n ? (unsigned)atomicAdd(&a.info[1], (u64)s_n) : 0u;  // voxels_moved doubles as the compaction's counter
+  if (threadIdx.x == 1 && s_vox[0]) atomicAdd(&a.info[0], (u64)s_vox[0]);
+  if ((threadIdx.x == 2 || threadIdx.x == 3) && s_vox[threadIdx.x]) atomicAdd(&a.info[threadIdx.x], (u64)s_vox[threadIdx.x]);
+  if (threadIdx.x >= 4 && threadIdx.x < 7 && s_pts[threadIdx.x - 4]) atomicAdd(&a.info[threadIdx.x], s_pts[threadIdx.x - 4]);
+  if (threadIdx.x == 7 && s_bad) atomicOr(&a.info[7], 1ull);
+  __syncthreads();
+  if (!sel) return;
+  const unsigned j = s_base + o;
+  if (j >= a.cap_out) return;
+  ulonglong2* r = a.out + 4 * (size_t)j;
+  r[0] = r0; r[1] = r1; r[2] = r2; r[3] = r3;
+}
+
+static_assert(sizeof(revo_map_pose_info) == 64 && offsetof(revo_map_pose_info, voxels_in) == 0 && offsetof(revo_map_pose_info, voxels_moved) == 8 &&
+              offsetof(revo_map_pose_info, voxels_dropped) == 16 && offsetof(revo_map_pose_info, voxels_skipped) == 24 &&
+              offsetof(revo_map_pose_info, points_moved) == 32 && offsetof(revo_map_pose_info, points_dropped) == 40 &&
+              offsetof(revo_map_pose_info, points_skipped) == 48 && offsetof(revo_map_pose_info, reserved) == 56,
+              "the info record is the kernel's counter line");
+
+// the pose rules of the three calls, checked before any table is touched
+static int pose_check(const float* T, float voxel_dst) {
+  if (!std::isfinite(voxel_dst) || !(voxel_dst > 0.0f)) return fail(REVO_ERR_INVALID_ARG, "the destination's voxel edge must be finite and > 0");
+  if (!pose_is_finite(T)) return fail(REVO_ERR_INVALID_ARG, "T_dst_src is not finite");
+  if (!pose_is_orthogonal(T)) return fail(REVO_ERR_INVALID_ARG, "the rotation of T_dst_src is not orthogonal");
+  return REVO_OK;
+}
+
+// One k_map_pose launch over src's table on stream s (src has been waited for), then the wait for its counters.  d_out NULL:
+// the records go into the run's own buffer (room for every voxel of src), which lives as long as the run.
+struct MapPoseRun {
+  char* buf = nullptr;
+  revo_map_pose_info info{};
+  ~MapPoseRun() { (void)hipFree(buf); (void)hipGetLastError(); }
+  const ulonglong2* recs() const { return (const ulonglong2*)(buf + 256); }
+};
+static int pose_run(MapPoseRun* r, revo_map* src, hipStream_t s, size_t voxels, const float* T, float voxel_dst, size_t min_count,
+                    ulonglong2* d_out, size_t cap_out, bool own) {
+  const size_t room = own ? std::max<size_t>(voxels, 1) : 0;
+  if (!r->buf) HIPCHECK(hipMalloc((void**)&r->buf, 256 + sizeof(revo_map_voxel_raw) * room));
+  MapPoseK a{};
+  a.keys = src->d_keys; a.vals = src->d_vals; a.cap = (unsigned)src->cap;
+  a.min_count = (u64)std::max<size_t>(min_count, 1);
+  a.T = MapPose{T[0], T[4], T[8], T[1], T[5], T[9], T[2], T[6], T[10], T[12], T[13], T[14], voxel_dst};
+  a.out = own ? (ulonglong2*)(r->buf + 256) : d_out;
+  a.cap_out = (unsigned)std::min<size_t>(own ? room : cap_out, MAP_MAX_CAP);
+  a.info = (u64*)r->buf;
+  HIPCHECK(hipMemsetAsync(r->buf, 0, sizeof(revo_map_pose_info), s));
+  hipLaunchKernelGGL(k_map_pose, dim3((unsigned)((src->cap + 255) / 256)), dim3(256), 0, s, a);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(&r->info, r->buf, sizeof(revo_map_pose_info), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const bool bad = r->info.reserved != 0;
+  r->info.reserved = 0;
+  if (bad) return fail(REVO_ERR_INVALID_ARG, "voxel map: a source voxel has a count of 2^32 or more (nothing posed)");
+  return REVO_OK;
+}
+
+extern "C" int revo_map_pose_raw(revo_map* src, const float T[16], float voxel_dst, size_t min_count, revo_map_voxel_raw* out, size_t cap,
+                                 size_t* n, int device_out, revo_map_pose_info* info) {
+  if (!src || !T || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_out && ((uintptr_t)out & 15)) return fail(REVO_ERR_INVALID_ARG, "the device output is not 16-byte aligned");
+  { const int rc = pose_check(T, voxel_dst); if (rc) return rc; }
+  MapStats ss;
+  { const int rc = read_stats(src, &ss); if (rc) return rc; }
+  hipStream_t s = (hipStream_t)src->g.stream;
+  const size_t nv = (size_t)ss.occ;
+  MapPoseRun r;
+  if (device_out) {
+    // nothing may be written when cap is too small or a source voxel is a bad record: count first, then write
+    { const int rc = pose_run(&r, src, s, nv, T, voxel_dst, min_count, nullptr, 0, false); if (rc) return rc; }
+    *n = (size_t)r.info.voxels_moved;
+    if (info) *info = r.info;
+    if (!out) return REVO_OK;
+    if (cap < *n) return fail(REVO_ERR_CAPACITY, "voxel map: the output holds fewer records than voxels move");
+    if (!*n) return REVO_OK;
+    return pose_run(&r, src, s, nv, T, voxel_dst, min_count, (ulonglong2*)out, cap, false);
+  }
+  { const int rc = pose_run(&r, src, s, nv, T, voxel_dst, min_count, nullptr, 0, true); if (rc) return rc; }
+  const size_t moved = (size_t)r.info.voxels_moved;
+  std::vector<revo_map_voxel_raw> rec(moved);
+  if (moved) HIPCHECK(hipMemcpy(rec.data(), r.recs(), sizeof(revo_map_voxel_raw) * moved, hipMemcpyDeviceToHost));
+  const size_t m = pose_canonicalise(rec.data(), moved);
+  *n = m;
+  if (info) *info = r.info;
+  if (!out) return REVO_OK;
+  if (cap < m) return fail(REVO_ERR_CAPACITY, "voxel map: the output holds fewer records than the posed map has voxels");
+  if (m) memcpy(out, rec.data(), sizeof(revo_map_voxel_raw) * m);
+  return REVO_OK;
+}
+
+// merge_posed and subtract_posed: the argument rules, the wait for src, the posed records of src at dst's edge on dst's
+// stream, then merge_core or subtract_core over them with src's counters plus the drops of the move.
+static int posed_apply(revo_map* dst, revo_map* src, const float* T, size_t min_count, revo_map_pose_info* info, bool subtract) {
+  if (!dst || !src || !T) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (dst == src) return fail(REVO_ERR_INVALID_ARG, "a map cannot be posed into itself");
+  if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
+  { const int rc = pose_check(T, dst->voxel); if (rc) return rc; }
+  MapStats ss;  // waits for src: its table is complete, and its counters say what comes
+  { const int rc = read_stats(src, &ss); if (rc) return rc; }
+  if (ss.kfs > 0x7fffffffull) return fail(REVO_ERR_INVALID_ARG, "the source map's keyframe count does not fit");
+  HIPCHECK(hipSetDevice(dst->g.device));
+  hipStream_t s = (hipStream_t)dst->g.stream;
+  MapPoseRun r;
+  { const int rc = pose_run(&r, src, s, (size_t)ss.occ, T, dst->voxel, min_count, nullptr, 0, true); if (rc) return rc; }
+  if (info) *info = r.info;
+  const size_t moved = (size_t)r.info.voxels_moved;
+  if (!moved) return REVO_OK;  // as revo_map_merge_raw / revo_map_subtract_raw with n == 0
+  MapMergeK a{};
+  a.recs = r.recs();
+  a.n = (unsigned)moved;
+  a.dropped = ss.drop + r.info.points_dropped;
+  if (subtract) return subtract_core(dst, a, MERGE_RAW, a.dropped, ss.kfs);  // has waited: the records are read
+  // device-made records need no validation: the device decides only when max_voxels is in reach
+  const int rc = merge_core(dst, a, MERGE_RAW, moved, true, (int)ss.kfs);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) return fail(REVO_ERR_HIP, "hipStreamSynchronize failed");  // the records are read
+  return rc;
+}
+extern "C" int revo_map_merge_posed(revo_map* dst, revo_map* src, const float T[16], size_t min_count, revo_map_pose_info* info) {
+  return posed_apply(dst, src, T, min_count, info, false);
+}
+extern "C" int revo_map_subtract_posed(revo_map* dst, revo_map* src, const float T[16], size_t min_count, revo_map_pose_info* info) {
+  return posed_apply(dst, src, T, min_count, info, true);
 }

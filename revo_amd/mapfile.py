@@ -13,6 +13,9 @@ Equal maps give equal files.
     python -m revo_amd.mapfile merge OUT FILE...       the union of the files' maps (same voxel edge), without a GPU
     python -m revo_amd.mapfile subtract A B -o OUT      map A without map B's sums: undoes `merge A OUT B`, without a GPU
     python -m revo_amd.mapfile coarsen A SHIFT -o OUT   map A with a voxel edge 2^SHIFT times as long (revo_map_coarsen), without a GPU
+    python -m revo_amd.mapfile transform A POSE.txt -o OUT [--voxel V] [--min-count N]
+                                                        map A seen under a pose (revo_map_pose_raw), without a GPU:
+                                                        POSE.txt holds 16 or 12 numbers, a row-major 4x4 or 3x4, A's frame -> OUT's
     python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
 """
 import struct
@@ -174,6 +177,92 @@ def coarsen_file(path, shift):
     return dict(header, voxel=voxel, voxels=len(out)), out
 
 
+def pose_is_orthogonal(R):
+    """The is_orthogonal rule of revo_map_align_eval on a row-major 3x3: |R R^T - I|_F < 1e-5 and det > 0, float32 with every
+    operation rounded on its own."""
+    R = np.asarray(R, np.float32).reshape(3, 3)
+    one, zero = np.float32(1), np.float32(0)
+    n2 = zero
+    for r in range(3):
+        for c in range(3):
+            v = (R[r, 0] * R[c, 0] + R[r, 1] * R[c, 1]) + R[r, 2] * R[c, 2]
+            v = v - (one if r == c else zero)
+            n2 = n2 + v * v
+    det = ((R[0, 0] * (R[1, 1] * R[2, 2] - R[1, 2] * R[2, 1]) - R[0, 1] * (R[1, 0] * R[2, 2] - R[1, 2] * R[2, 0]))
+           + R[0, 2] * (R[1, 0] * R[2, 1] - R[1, 1] * R[2, 0]))
+    return bool(np.sqrt(n2) < np.float32(1e-5) and det > 0)
+
+
+def _pose_matrix(T):
+    T = np.asarray(T, np.float32)
+    if T.shape == (3, 4):
+        T = np.vstack([T, np.float32([0, 0, 0, 1])])
+    if T.shape != (4, 4):
+        raise ValueError("a pose is a 4x4 or 3x4 matrix")
+    if not np.all(np.isfinite(T)):
+        raise ValueError("the pose is not finite")
+    if not pose_is_orthogonal(T[:3, :3]):
+        raise ValueError("the pose's rotation is not orthogonal")
+    return T
+
+
+def pose_records(records, T, voxel_dst, min_count=1):
+    """The records of a map seen under the pose T (4x4 or 3x4, the map's frame -> the destination's) at the destination edge
+    voxel_dst: revo_map_pose_raw's canonical form, float32 operation by operation.  Per voxel with count >=
+    max(min_count, 1): its point p as to_points gives it, p' = ((R0 px + R1 py) + R2 pz) + t, key = floor(p' / voxel_dst),
+    dropped when p' is not finite, some |p'| >= 2048 or some index leaves [-2^20, 2^20 - 1]; else count and colour sums are
+    carried and sum_q = count * rint(p' 2^20).  -> (records in ascending key order with equal keys summed, info dict of
+    voxels_in, voxels_moved, voxels_dropped, voxels_skipped, points_moved, points_dropped, points_skipped).
+    ValueError: a bad record (count 0, key bit 63, count >= 2^32), an edge that is not finite and > 0, a pose that is not
+    finite or whose rotation is not orthogonal."""
+    rec = as_records(records)
+    check_records(rec, canonical=False)
+    if np.any(rec["count"] >> np.uint64(32)):
+        raise ValueError("a voxel record has a count of 2^32 or more")
+    v = np.float32(voxel_dst)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError("the destination's voxel edge must be finite and > 0")
+    T = _pose_matrix(T)
+    sel = rec["count"] >= np.uint64(max(1, int(min_count)))
+    r = rec[sel]
+    cnt = r["count"]
+    p = ((r["sum_q"].astype(np.float64) / cnt.astype(np.float64)[:, None]) * 2.0 ** -20).astype(np.float32).reshape(-1, 3)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        pt = np.stack([((T[i, 0] * p[:, 0] + T[i, 1] * p[:, 1]) + T[i, 2] * p[:, 2]) + T[i, 3] for i in range(3)], 1).astype(np.float32)
+        f = np.floor(pt / v)
+        ok = np.all((np.abs(pt) < np.float32(2048.0)) & (f >= -(1 << 20)) & (f <= (1 << 20) - 1), 1)
+        k = f[ok].astype(np.int64) + np.int64(1 << 20)
+        q = np.rint(pt[ok] * np.float32(1 << 20)).astype(np.int64)
+    out = np.zeros(int(ok.sum()), RAW_DTYPE)
+    out["key"] = (k[:, 0].astype(np.uint64) << np.uint64(42)) | (k[:, 1].astype(np.uint64) << np.uint64(21)) | k[:, 2].astype(np.uint64)
+    out["count"] = cnt[ok]
+    out["sum_q"] = cnt[ok].astype(np.int64)[:, None] * q
+    out["sum_bgr"] = r["sum_bgr"][ok]
+    total = lambda c: int(c.sum(dtype=np.uint64))  # noqa: E731
+    info = {"voxels_in": len(rec), "voxels_moved": int(ok.sum()), "voxels_dropped": int((~ok).sum()), "voxels_skipped": int((~sel).sum()),
+            "points_moved": total(cnt[ok]), "points_dropped": total(cnt[~ok]), "points_skipped": total(rec["count"][~sel])}
+    return merge_records(out, np.zeros(0, RAW_DTYPE)), info
+
+
+def read_pose(path):
+    """A pose from a text file of 16 or 12 numbers: a row-major 4x4 or 3x4."""
+    with open(path) as f:
+        a = [float(x) for x in f.read().replace(",", " ").split()]
+    if len(a) not in (12, 16):
+        raise ValueError("%s holds %d numbers; a pose is 16 (4x4) or 12 (3x4), row-major" % (path, len(a)))
+    return _pose_matrix(np.float32(a).reshape(-1, 4))
+
+
+def transform_file(path, T, voxel=None, min_count=1):
+    """(header, records, info) of the file's map under the pose T at the edge `voxel` (the file's by default): the header
+    carries that edge, the file's cloud mode and keyframes, and its dropped points plus those the move dropped."""
+    header, rec = read(path)
+    voxel = header["voxel"] if voxel is None else float(np.float32(voxel))
+    out, info = pose_records(rec, T, voxel, min_count)
+    h = make_header(voxel, header["dense"], out, header["points_dropped"] + info["points_dropped"], header["keyframes"])
+    return h, out, info
+
+
 def to_points(records, min_count=1):
     """(xyz N x 3 float32, rgb N x 3 uint8 as R,G,B, count N uint32) of the records with count >= max(min_count, 1), in their
     order -- what revo_map_extract gives: xyz = float32(float64(sum_q) / float64(count) * 2^-20), colour = (sum + count // 2)
@@ -246,6 +335,23 @@ def main(argv=None):
             write(out, h, rec)
             print("%s: %d voxels of %g m (%s coarsened by %d)" % (out, len(rec), h["voxel"], a, int(shift)))
             return 0
+        if cmd == "transform" and "-o" in args:
+            opt = {"-o": None, "--voxel": None, "--min-count": "1"}
+            pos, i = [], 0
+            while i < len(args):
+                if args[i] in opt and i + 1 < len(args):
+                    opt[args[i]] = args[i + 1]
+                    i += 2
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 2 and opt["-o"] is not None:
+                h, rec, info = transform_file(pos[0], read_pose(pos[1]), None if opt["--voxel"] is None else float(opt["--voxel"]),
+                                              int(opt["--min-count"]))
+                write(opt["-o"], h, rec)
+                print("%s: %d voxels of %g m (%s under %s: %d voxels moved, %d dropped, %d skipped)"
+                      % (opt["-o"], len(rec), h["voxel"], pos[0], pos[1], info["voxels_moved"], info["voxels_dropped"], info["voxels_skipped"]))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -257,7 +363,7 @@ def main(argv=None):
         print("mapfile: %s" % e)
         return 1
     print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | coarsen A SHIFT -o OUT | "
-          "ply FILE [OUT.ply]")
+          "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | ply FILE [OUT.ply]")
     return 2
 
 

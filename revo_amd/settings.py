@@ -224,6 +224,15 @@ class MapPlaneInfo(C.Structure):
 assert C.sizeof(MapNormalsParams) == 16 and C.sizeof(MapPlaneInfo) == 208
 
 
+class MapPoseInfo(C.Structure):
+    """revo_map_pose_info (include/revo_hip.h), 64 bytes: what became of a source map's voxels and points under a pose."""
+    _fields_ = [(k, C.c_uint64) for k in ("voxels_in", "voxels_moved", "voxels_dropped", "voxels_skipped", "points_moved",
+                                          "points_dropped", "points_skipped", "reserved")]
+
+
+assert C.sizeof(MapPoseInfo) == 64
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
