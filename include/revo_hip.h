@@ -993,6 +993,87 @@ int revo_map_merge_posed(revo_map* dst, revo_map* src, const float T_dst_src[16]
  * refusal rule of revo_map_subtract_raw applies, and dst is then untouched. */
 int revo_map_subtract_posed(revo_map* dst, revo_map* src, const float T_dst_src[16], size_t min_count, revo_map_pose_info* info);
 
+/* ---- free-space carving: voxels a later view looks through leave the map --------------------------------
+ * Whether a view sees through a voxel depends on that voxel's sums, the view's depth image and its pose only, so a carve is
+ * a pure function of its inputs: the same bytes whatever the table size, integration order, launch shape or stream.
+ * All arithmetic is float32 with every operation rounded on its own.
+ *
+ * Per view, on the host: Rc and tc exactly as revo_map_render forms them from T_w_c; intrinsics fx, fy, cx, cy; the depth
+ * range zmin, zmax; the depth image D, h x w float32 metres, rows packed.
+ * Candidates: the voxels with count >= max(min_count, 1), and count <= max_count when max_count != 0; p exactly as
+ * revo_map_extract returns it.  Per view a candidate falls into exactly one of six classes:
+ *   OUTSIDE    pc = ((Rc[:,0]*px + Rc[:,1]*py) + Rc[:,2]*pz) + tc is not finite, or z <= zmin, or z >= zmax, or
+ *              u = (fx*x)/z + cx, v = (fy*y)/z + cy is not finite or |u| or |v| >= 2^20, or, with iu = (int)floorf(u + 0.5f)
+ *              and iv likewise (the nearest pixel: back-projection puts pixel x at u = x), the window
+ *              [iu-r, iu+r] x [iv-r, iv+r] (r = radius) is not wholly inside the image;
+ *   UNKNOWN    some pixel of the window is not a usable depth (usable: finite, > zmin, < zmax);
+ *   FREE       z < dmin - (margin + margin_rel*dmin), dmin the minimum of the window's depths (a product, a sum and a
+ *              difference, each rounded);
+ *   otherwise, with dc = D[iv, iu] and mc = margin + margin_rel*dc:
+ *   CONFIRMED  fabsf(z - dc) <= mc;
+ *   OCCLUDED   z > dc + mc;
+ *   EDGE       the rest: in front of the centre pixel, but a neighbour of the window is nearer.
+ * A voxel's votes are the views in which it is FREE; it is carved iff votes >= max(min_views, 1).  The class of a voxel
+ * does not look at any other voxel, so: a second identical carve removes nothing; the order of the views cannot show; with
+ * min_views = 1, carving with views A and then with views B equals one carve with A and B together.
+ * A carved voxel leaves with its whole record (key, count, sum_q, sum_bgr) through revo_map_subtract_raw's exact
+ * subtraction: points_integrated falls by its count, keyframes and points_dropped do not move, voxels is the true count and
+ * no occupied slot keeps count 0. */
+typedef struct revo_map_carve_view {   /* 112 bytes */
+  const revo_pyr* kf;               /* a pyramid of the map's context: its level-0 depth plane, the context's level-0 camera   */
+                                    /* and DEPTH_MIN / DEPTH_MAX (depth must be NULL; the other image fields are ignored) ...   */
+  const float* depth;               /* ... or a raw depth image, rows packed (kf must be NULL)                                 */
+  int32_t width, height;            /* 1 .. 2048 each                                                                          */
+  float fx, fy, cx, cy, zmin, zmax; /* all six zero: the context's, as in revo_map_view; else finite, fx, fy > 0,              */
+                                    /* 0 <= zmin < zmax                                                                        */
+  float T_w_c[16];                  /* camera -> world, column-major, finite, rotation orthogonal (revo_map_align_eval's rule) */
+} revo_map_carve_view;
+typedef struct revo_map_carve_params { /* 24 bytes; NULL: 1, 1, 1, 0, the map's voxel edge, 0 */
+  int32_t radius;        /* 0 .. 3: half width of the pixel window                                   */
+  uint32_t min_views;    /* votes a voxel needs (0 counts as 1)                                      */
+  uint32_t min_count;    /* as revo_map_extract's                                                    */
+  uint32_t max_count;    /* 0: no upper bound                                                        */
+  float margin;          /* metres, finite, >= 0                                                     */
+  float margin_rel;      /* per metre of depth, finite, >= 0                                         */
+} revo_map_carve_params;
+typedef struct revo_map_carve_info {   /* 64 bytes, little-endian, no padding */
+  uint64_t voxels_considered;  /* the candidates                                   */
+  uint64_t voxels_carved;
+  uint64_t points_carved;      /* the sum of count over the carved voxels          */
+  uint64_t votes;              /* FREE classifications over all candidates, views  */
+  uint64_t reserved[4];        /* zero */
+} revo_map_carve_info;
+typedef struct revo_map_carve_view_info { /* 32 bytes per view: the candidates by class; they sum to voxels_considered */
+  uint32_t outside, unknown, free_space, confirmed, occluded, edge;
+  uint32_t reserved[2];        /* zero */
+} revo_map_carve_view_info;
+/* The records that revo_map_carve would remove; the map is untouched.  n: 1 .. 64 views.  device_in: where the raw depth
+ * images live (0: host memory -- uploaded to a temporary buffer that is freed after the stream has consumed it; 1: device
+ * memory of the map's device, 4-byte aligned).  Runs on the context's tracker stream behind the map's pending work and, for a
+ * pyramid view, behind that pyramid's build (as revo_map_integrate), and waits for the result.  A counting launch runs first
+ * and the records are written by a second one, so a refused call writes nothing.
+ * device_out = 0: records in host memory in ascending key order.  device_out = 1: device memory, 16-byte aligned, unspecified
+ * order.  records == NULL: counts only (cap is ignored).  *n_records = voxels_carved.  REVO_ERR_CAPACITY, nothing written, when
+ * cap < *n_records.  info and view_info (n entries, host memory) may be NULL.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued: NULL m, views or n_records; n outside 1 .. 64; device_in or device_out
+ * not 0 or 1; a view with both or neither of kf / depth; a pyramid of another context, or a batch view -- a pyramid
+ * revo_map_integrate does not take: the frames of revo_batch_frame, not the keyframe slots of
+ * revo_vo_keyframe / revo_vo_multi_keyframe (every pyramid is checked before any of them orders the stream); a size outside
+ * 1 .. 2048; an intrinsic, range or pose that is not finite; fx or fy <= 0; zmin < 0 or zmin >= zmax; a rotation that fails
+ * the is_orthogonal rule of revo_map_align_eval; radius outside 0 .. 3; margin or margin_rel not finite or negative; a
+ * misaligned device pointer. */
+int revo_map_carve_eval(revo_map* m, int n, const revo_map_carve_view* views, int device_in, const revo_map_carve_params* prm,
+                        revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
+                        revo_map_carve_view_info* view_info);
+/* The same arguments and outputs; the carved voxels then leave the map: revo_map_subtract_raw(m, the device records,
+ * voxels_carved, 1, 0, 0).  revo_map_merge_raw(m, records, n_records, ., 0, 0) afterwards restores the map byte for byte,
+ * counters included.  When cap is too small nothing is written and nothing is removed; host records are written after the
+ * removal has succeeded, so a call that fails (REVO_ERR_HIP: no memory for the clean-up table, the map as it was) writes none;
+ * a device buffer may then hold the records that were to go. */
+int revo_map_carve(revo_map* m, int n, const revo_map_carve_view* views, int device_in, const revo_map_carve_params* prm,
+                   revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
+                   revo_map_carve_view_info* view_info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

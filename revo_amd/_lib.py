@@ -8,7 +8,8 @@ import os
 import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
-                       PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MAX_LEVELS)
+                       PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -159,6 +160,9 @@ def lib():
                                     C.POINTER(MapPoseInfo)]
     L.revo_map_merge_posed.argtypes = [vp, vp, f32p, C.c_size_t, C.POINTER(MapPoseInfo)]
     L.revo_map_subtract_posed.argtypes = [vp, vp, f32p, C.c_size_t, C.POINTER(MapPoseInfo)]
+    for fn in (L.revo_map_carve_eval, L.revo_map_carve):
+        fn.argtypes = [vp, C.c_int, C.POINTER(MapCarveView), C.c_int, C.POINTER(MapCarveParams), vp, C.c_size_t, C.POINTER(C.c_size_t),
+                       C.c_int, C.POINTER(MapCarveInfo), C.POINTER(MapCarveViewInfo)]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

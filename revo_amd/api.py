@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -567,6 +567,89 @@ class VoxelMap:
             self.merge_posed(src, T_old, min_count)
             raise
 
+    # -- free-space carving (revo_map_carve_eval / revo_map_carve)
+    def _carve(self, fn, views, radius, min_views, min_count, max_count, margin, margin_rel, device, records=True):
+        from . import mapfile
+        views = list(views)
+        n = len(views)
+        if not 1 <= n <= 64:
+            raise ValueError("a carve takes 1 .. 64 views")
+        cv = (MapCarveView * n)()
+        keep, on_device = [], []
+        for v, view in zip(cv, views):
+            src, T = view[0], view[1]
+            k = view[2] if len(view) > 2 and view[2] is not None else (0.0,) * 6
+            if isinstance(src, ImgPyramidRGBD):
+                v.kf = src._h
+            elif hasattr(src, "data_ptr"):
+                if not (src.is_cuda and src.is_contiguous() and str(src.dtype) == "torch.float32" and src.dim() == 2):
+                    raise ValueError("a depth image on the device is a contiguous [h, w] float32 device tensor")
+                import torch
+                torch.cuda.current_stream(src.device).synchronize()  # the tensor is written before the tracker stream reads it
+                v.depth, v.height, v.width = src.data_ptr(), int(src.shape[0]), int(src.shape[1])
+                on_device.append(True)
+                keep.append(src)
+            else:
+                a = np.ascontiguousarray(np.asarray(src, np.float32))
+                if a.ndim != 2:
+                    raise ValueError("a depth image is an [h, w] float32 array")
+                v.depth, v.height, v.width = a.ctypes.data, int(a.shape[0]), int(a.shape[1])
+                on_device.append(False)
+                keep.append(a)
+            if len(k) != 6:
+                raise ValueError("the intrinsics of a view are (fx, fy, cx, cy, zmin, zmax)")
+            v.fx, v.fy, v.cx, v.cy, v.zmin, v.zmax = [float(x) for x in k]
+            v.T_w_c[:] = _cm4(T).tolist()
+        if len(set(on_device)) > 1:
+            raise ValueError("the raw depth images of one carve are all host arrays or all device tensors")
+        device_in = 1 if on_device and on_device[0] else 0
+        prm = MapCarveParams(int(radius), int(min_views), int(min_count), int(max_count),
+                             float(self.voxel if margin is None else margin), float(margin_rel))
+        L = _lib.lib()
+        n_rec, info, vinfo = C.c_size_t(), MapCarveInfo(), (MapCarveViewInfo * n)()
+        if not records:  # the driver's path: one call, nothing comes back but the counters
+            check(fn(self._h, n, cv, device_in, C.byref(prm), None, 0, C.byref(n_rec), 0, C.byref(info), vinfo))
+            rec = None
+        elif device:
+            import torch
+            check(L.revo_map_carve_eval(self._h, n, cv, device_in, C.byref(prm), None, 0, C.byref(n_rec), 1, None, None))
+            out = torch.empty(64 * max(n_rec.value, 1), dtype=torch.uint8, device="cuda:%d" % self.cameraPyr.device)
+            torch.cuda.current_stream(out.device).synchronize()
+            check(fn(self._h, n, cv, device_in, C.byref(prm), vp(out.data_ptr()), n_rec.value, C.byref(n_rec), 1, C.byref(info), vinfo))
+            self.sync()  # the records are written
+            rec = out[:64 * n_rec.value]
+        else:
+            check(L.revo_map_carve_eval(self._h, n, cv, device_in, C.byref(prm), None, 0, C.byref(n_rec), 0, None, None))
+            rec = np.zeros(n_rec.value, mapfile.RAW_DTYPE)
+            check(fn(self._h, n, cv, device_in, C.byref(prm), rec.ctypes.data_as(vp) if n_rec.value else None, n_rec.value, C.byref(n_rec),
+                     0, C.byref(info), vinfo))
+            rec = rec[:n_rec.value]
+        del keep
+        names = (("outside", "outside"), ("unknown", "unknown"), ("free", "free_space"), ("confirmed", "confirmed"),
+                 ("occluded", "occluded"), ("edge", "edge"))
+        return (rec, {k: int(getattr(info, k)) for k in mapfile.CARVE_INFO_KEYS},
+                [{name: int(getattr(vi, field)) for name, field in names} for vi in vinfo])
+
+    def carve_eval(self, views, radius=1, min_views=1, min_count=1, max_count=0, margin=None, margin_rel=0.0, device=False, records=True):
+        """What carve() would remove; the map is untouched.  views: 1 .. 64 of (pyr, T_w_c) -- a pyramid of this map's context:
+        its level-0 depth plane with the context's camera -- or (depth, T_w_c[, (fx, fy, cx, cy, zmin, zmax)]) with an [h, w]
+        float32 numpy array or torch device tensor of metres (no intrinsics: the context's).  T_w_c: 4x4, camera -> world.
+        Per voxel with min_count <= count (<= max_count unless 0) and per view one of six classes: outside the
+        image or depth range; unknown (a hole in the (2 radius + 1)^2 pixel window); free (nearer than every depth of the window
+        by more than margin + margin_rel * depth; margin None: the voxel edge); confirmed; occluded; edge.  A voxel free in
+        at least min_views views is carved.  -> (records, info, per-view class counts): records as a mapfile.RAW_DTYPE array
+        in ascending key order, or with device=True a torch uint8 device tensor in unspecified order; info: voxels_considered,
+        voxels_carved, points_carved, votes.  records=False: one library call that brings no records back (None in their
+        place): the counters only."""
+        return self._carve(_lib.lib().revo_map_carve_eval, views, radius, min_views, min_count, max_count, margin, margin_rel, device, records)
+
+    def carve(self, views, radius=1, min_views=1, min_count=1, max_count=0, margin=None, margin_rel=0.0, device=False, records=True):
+        """Free-space carving: the voxels carve_eval names leave the map with their whole records (exact subtraction:
+        points_integrated falls by their counts, keyframes and points_dropped stay).  merge_raw(records) afterwards restores
+        the map byte for byte.  Takes and returns what carve_eval does (records=False: the voxels go, only the counters come
+        back)."""
+        return self._carve(_lib.lib().revo_map_carve, views, radius, min_views, min_count, max_count, margin, margin_rel, device, records)
+
     def _views(self, T_w_c, camera, zrange, splat_max, min_count):
         """-> (MapView array, single): camera None = the context's level-0 camera and depth range (zrange must be None too),
         else an api.Camera or (fx, fy, cx, cy, width, height) and zrange (zmin, zmax) or None = the context's range."""
@@ -780,6 +863,12 @@ class MapWindow:
     def integrate_many(self, pyrs, T_ws):
         for p, T in zip(pyrs, T_ws):
             self.integrate(p, T)
+
+    def carve(self, *args, **kw):
+        """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost
+        sums those records still hold -- the subtraction would be refused.  Carve a plain VoxelMap (carve_eval, which changes
+        nothing, is the inner map's)."""
+        raise NotImplementedError("MapWindow cannot be carved: its per-keyframe records must stay subtractable")
 
     def _evict(self):
         _, buf, n, dropped, _ = self._held[0]

@@ -1140,6 +1140,14 @@ extern "C" int revo_map_source_(revo_pyr* p, MapSource* out) {
   out->bgr = p->fs->d_bgr + f * n0 * 3;
   return REVO_OK;
 }
+// What revo_map_carve asks of a pyramid before anything is enqueued: its context, and whether it is a batch view whose planes
+// the map calls do not take (the rule of revo_map_source_).  Touches no stream.
+extern "C" int revo_map_source_kind_(const revo_pyr* p, const revo_ctx** ctx, int* batch_view) {
+  if (!p || !ctx || !batch_view) return fail(REVO_ERR_INVALID_ARG, "null pyramid");
+  *ctx = p->ctx;
+  *batch_view = (!(p->owns_fs || p->has_colour) || !p->fs->d_bgr) ? 1 : 0;
+  return REVO_OK;
+}
 extern "C" int revo_map_ctx_geom_(const revo_ctx* c, MapCtxGeom* out) {
   if (!c || !out) return fail(REVO_ERR_INVALID_ARG, "null context");
   const LevelGeom& l = c->geom.lv[0];

@@ -18,6 +18,8 @@ extern "C" {
 // the keyframe's planes, with the context's tracker stream ordered behind everything that writes them
 int revo_map_source_(revo_pyr* kf, MapSource* out);
 int revo_map_ctx_geom_(const revo_ctx* ctx, MapCtxGeom* out);
+// a pyramid's context and whether revo_map_source_ would refuse it as a batch view; enqueues nothing
+int revo_map_source_kind_(const revo_pyr* kf, const revo_ctx** ctx, int* batch_view);
 // revo_vo_multi: integrate the keyframe slots a step has just promoted (n entries, T_w_kf column-major, 16 floats each)
 struct revo_map_stage;
 int revo_map_stage_create_(revo_map_stage** out);

@@ -28,6 +28,7 @@
 #include "revo_track_dev.h"
 #include "revo_align_host.h"
 #include "revo_pose_host.h"
+#include "revo_carve_host.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -2161,4 +2162,249 @@ extern "C" int revo_map_merge_posed(revo_map* dst, revo_map* src, const float T[
 }
 extern "C" int revo_map_subtract_posed(revo_map* dst, revo_map* src, const float T[16], size_t min_count, revo_map_pose_info* info) {
   return posed_apply(dst, src, T, min_count, info, true);
+}
+
+// ---------------------------------------------------------------------------------------------- free-space carving (19) --
+// revo_map_carve_eval / revo_map_carve (contract: include/revo_hip.h).
+struct MapCarveView {  // one view of a launch, in device memory
+  CarveView v;
+  const float* depth;
+};
+struct MapCarveK {
+  const u64* keys; const MapVal* vals; unsigned cap;  // the map's table
+  const MapCarveView* views; int n;
+  int radius; unsigned min_views;
+  u64 min_count, max_count;  // max_count 0: no upper bound
+  float margin, margin_rel;
+  ulonglong2* out; unsigned cap_out;  // the carved records, at most cap_out of them (0: count only)
+  u64* info;                          // one 64-byte line: revo_map_carve_info's four counters
+  unsigned* vinfo;                    // 8 words per view: revo_map_carve_view_info
+};
+enum { CARVE_OUTSIDE = 0, CARVE_UNKNOWN = 1, CARVE_FREE = 2, CARVE_CONFIRMED = 3, CARVE_OCCLUDED = 4, CARVE_EDGE = 5, CARVE_CLASSES = 6 };
+#define CARVE_MAX_VIEWS 64
+
+// The class of the point p in one view: the one text of the contract's rule.  Every read of the depth image lies inside a
+// window that has been tested against the image size first, and |u|, |v| < 2^20 bounds the integers the test is made on.
+__device__ __forceinline__ int map_carve_class(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel) {
+  const CarveView& c = vw.v;
+  const float x = ((c.Rc[0] * px + c.Rc[1] * py) + c.Rc[2] * pz) + c.tc[0];
+  const float y = ((c.Rc[3] * px + c.Rc[4] * py) + c.Rc[5] * pz) + c.tc[1];
+  const float z = ((c.Rc[6] * px + c.Rc[7] * py) + c.Rc[8] * pz) + c.tc[2];
+  if (!isfinite(x) || !isfinite(y) || !map_depth_ok(z, c.zmin, c.zmax)) return CARVE_OUTSIDE;
+  const float u = __fdiv_rn(c.fx * x, z) + c.cx;
+  const float v = __fdiv_rn(c.fy * y, z) + c.cy;
+  if (!(fabsf(u) < 1048576.0f) || !(fabsf(v) < 1048576.0f)) return CARVE_OUTSIDE;  // NaN / inf fail the comparison
+  const int iu = (int)floorf(u + 0.5f), iv = (int)floorf(v + 0.5f);
+  if (iu - r < 0 || iu + r > c.w - 1 || iv - r < 0 || iv + r > c.h - 1) return CARVE_OUTSIDE;
+  bool usable = true;
+  float dmin = INFINITY;
+  for (int dy = -r; dy <= r; ++dy) {
+    const float* row = vw.depth + (size_t)(iv + dy) * c.w + iu;
+    for (int dx = -r; dx <= r; ++dx) {
+      const float d = row[dx];
+      usable = usable && map_depth_ok(d, c.zmin, c.zmax);
+      dmin = fminf(dmin, d);  // only looked at when every depth is usable
+    }
+  }
+  if (!usable) return CARVE_UNKNOWN;
+  if (z < dmin - (margin + margin_rel * dmin)) return CARVE_FREE;
+  const float dc = vw.depth[(size_t)iv * c.w + iu];
+  const float mc = margin + margin_rel * dc;
+  if (fabsf(z - dc) <= mc) return CARVE_CONFIRMED;
+  return z > dc + mc ? CARVE_OCCLUDED : CARVE_EDGE;
+}
+
+// One thread per slot of the table: the value as four 16-byte loads, the point once, then the views one after another with
+// the votes in a register.  Per view the classes of a wave are counted by ballots into LDS; the carved records are compacted
+// as k_map_export compacts (LDS counter, one global atomic per block); every counter takes one global atomic per block.
+__global__ void __launch_bounds__(256) k_map_carve(const MapCarveK a) {
+  __shared__ unsigned s_n, s_base, s_cand, s_votes;
+  __shared__ u64 s_pts;
+  __shared__ unsigned s_cls[CARVE_MAX_VIEWS * CARVE_CLASSES];
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256) s_cls[k] = 0;
+  if (threadIdx.x == 0) { s_n = 0; s_cand = 0; s_votes = 0; s_pts = 0; }
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const u64 key = i < a.cap ? a.keys[i] : MAP_EMPTY;
+  ulonglong2 p{}, q{}, c{}, d{};  // n qx | qy qz | sb sg | sr -
+  bool cand = false;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (key != MAP_EMPTY) {
+    const ulonglong2* v = (const ulonglong2*)(a.vals + i);
+    p = v[0]; q = v[1]; c = v[2]; d = v[3];
+    cand = p.x >= a.min_count && (a.max_count == 0 || p.x <= a.max_count);  // min_count >= 1: a committed voxel
+    if (cand) {
+      const double inv = (double)p.x;
+      px = map_mean(p.y, inv); py = map_mean(q.x, inv); pz = map_mean(q.y, inv);
+    }
+  }
+  unsigned votes = 0;
+  for (int vi = 0; vi < a.n; ++vi) {  // uniform: the ballots see whole waves
+    const int cls = cand ? map_carve_class(px, py, pz, a.views[vi], a.radius, a.margin, a.margin_rel) : -1;
+    votes += cls == CARVE_FREE ? 1u : 0u;
+#pragma unroll
+    for (int k = 0; k < CARVE_CLASSES; ++k) {
+      const u64 b = __ballot(cls == k);
+      if (lane == 0 && b) atomicAdd(&s_cls[vi * CARVE_CLASSES + k], (unsigned)__popcll(b));
+    }
+  }
+  const bool sel = cand && votes >= a.min_views;
+  const u64 bc = __ballot(cand);
+  if (lane == 0 && bc) atomicAdd(&s_cand, (unsigned)__popcll(bc));
+  if (votes) atomicAdd(&s_votes, votes);
+  if (sel) atomicAdd(&s_pts, p.x);
+  const unsigned o = sel ? atomicAdd(&s_n, 1u) : 0u;
+  __syncthreads();
+  if (threadIdx.x == 0) s_base = s_n ? (unsigned)atomicAdd(&a.info[1], (u64)s_n) : 0u;  // voxels_carved doubles as the compaction's counter
+  if (threadIdx.x == 1 && s_cand) atomicAdd(&a.info[0], (u64)s_cand);
+  if (threadIdx.x == 2 && s_pts) atomicAdd(&a.info[2], s_pts);
+  if (threadIdx.x == 3 && s_votes) atomicAdd(&a.info[3], (u64)s_votes);
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256)
+    if (s_cls[k]) atomicAdd(&a.vinfo[(k / CARVE_CLASSES) * 8 + k % CARVE_CLASSES], s_cls[k]);
+  __syncthreads();
+  if (!sel) return;
+  const unsigned j = s_base + o;
+  if (j >= a.cap_out) return;
+  ulonglong2* r = a.out + 4 * (size_t)j;
+  r[0] = make_ulonglong2(key, p.x); r[1] = make_ulonglong2(p.y, q.x); r[2] = make_ulonglong2(q.y, c.x); r[3] = make_ulonglong2(c.y, d.x);
+}
+
+static_assert(sizeof(revo_map_carve_info) == 64 && offsetof(revo_map_carve_info, voxels_considered) == 0 &&
+              offsetof(revo_map_carve_info, voxels_carved) == 8 && offsetof(revo_map_carve_info, points_carved) == 16 &&
+              offsetof(revo_map_carve_info, votes) == 24 && offsetof(revo_map_carve_info, reserved) == 32,
+              "the info record is the kernel's counter line");
+static_assert(sizeof(revo_map_carve_view_info) == 32 && offsetof(revo_map_carve_view_info, outside) == 4 * CARVE_OUTSIDE &&
+              offsetof(revo_map_carve_view_info, unknown) == 4 * CARVE_UNKNOWN && offsetof(revo_map_carve_view_info, free_space) == 4 * CARVE_FREE &&
+              offsetof(revo_map_carve_view_info, confirmed) == 4 * CARVE_CONFIRMED && offsetof(revo_map_carve_view_info, occluded) == 4 * CARVE_OCCLUDED &&
+              offsetof(revo_map_carve_view_info, edge) == 4 * CARVE_EDGE && offsetof(revo_map_carve_view_info, reserved) == 24,
+              "a view's record is the kernel's eight counter words");
+static_assert(sizeof(revo_map_carve_view) == 112 && offsetof(revo_map_carve_view, kf) == 0 && offsetof(revo_map_carve_view, depth) == 8 &&
+              offsetof(revo_map_carve_view, width) == 16 && offsetof(revo_map_carve_view, fx) == 24 && offsetof(revo_map_carve_view, T_w_c) == 48 &&
+              sizeof(revo_map_carve_params) == 24, "the view and parameter records are the documented layout");
+
+// One carve call's device memory: the counter lines, the view descriptors, the uploaded host images, the records.
+struct MapCarveRun {
+  char* buf = nullptr;      // [0, 64) the info line, [256, 256 + 32 n) the views' counters, then the descriptors
+  char* images = nullptr;   // host depth images of the call, uploaded
+  char* recs = nullptr;     // the carved records of a host-output call or of revo_map_carve
+  ~MapCarveRun() { (void)hipFree(buf); (void)hipFree(images); (void)hipFree(recs); (void)hipGetLastError(); }
+};
+
+static int carve_launch(revo_map* m, hipStream_t s, MapCarveRun* r, MapCarveK a, revo_map_carve_info* info, revo_map_carve_view_info* vinfo) {
+  a.info = (u64*)r->buf;
+  a.vinfo = (unsigned*)(r->buf + 256);
+  HIPCHECK(hipMemsetAsync(r->buf, 0, 256 + sizeof(revo_map_carve_view_info) * a.n, s));
+  hipLaunchKernelGGL(k_map_carve, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, a);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(info, r->buf, sizeof(revo_map_carve_info), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(vinfo, r->buf + 256, sizeof(revo_map_carve_view_info) * a.n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int device_in, const revo_map_carve_params* prm,
+                       revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
+                       revo_map_carve_view_info* view_info, bool remove) {
+  if (!m || !views || !n_records) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n < 1 || n > CARVE_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, "revo_map_carve: n must be 1 .. 64 views");
+  if (device_in != 0 && device_in != 1) return fail(REVO_ERR_INVALID_ARG, "device_in must be 0 or 1");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_out && ((uintptr_t)records & 15)) return fail(REVO_ERR_INVALID_ARG, "the device output is not 16-byte aligned");
+  revo_map_carve_params pp;
+  if (const char* why = carve_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_carve: ") + why);
+  const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
+  std::vector<MapCarveView> hv(n);
+  size_t up_bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    const std::string at = "view " + std::to_string(i) + ": ";
+    if (const char* why = carve_view_check(&views[i], cam, m->g.w, m->g.h, &hv[i].v)) return fail(REVO_ERR_INVALID_ARG, at + why);
+    hv[i].depth = views[i].depth;
+    if (views[i].depth) {
+      if (device_in && ((uintptr_t)views[i].depth & 3)) return fail(REVO_ERR_INVALID_ARG, at + "the device depth image is not 4-byte aligned");
+      if (!device_in) up_bytes += ((size_t)hv[i].v.w * hv[i].v.h * sizeof(float) + 255) & ~(size_t)255;
+    }
+  }
+  for (int i = 0; i < n; ++i) {  // every pyramid's context and kind, before any of them orders a stream
+    if (!views[i].kf) continue;
+    const revo_ctx* pc = nullptr;
+    int batch_view = 0;
+    { const int rc = revo_map_source_kind_(views[i].kf, &pc, &batch_view); if (rc) return rc; }
+    const std::string at = "view " + std::to_string(i) + ": ";
+    if (pc != m->ctx) return fail(REVO_ERR_INVALID_ARG, at + "the pyramid belongs to another context than the map");
+    if (batch_view)
+      return fail(REVO_ERR_INVALID_ARG, at + "a batch view is not a keyframe the map calls take (pass its depth plane as a raw image)");
+  }
+  for (int i = 0; i < n; ++i) {  // nothing is refused from here on: the tracker stream is ordered behind the pyramids' builds
+    if (!views[i].kf) continue;
+    MapSource src;
+    { const int rc = revo_map_source_(const_cast<revo_pyr*>(views[i].kf), &src); if (rc) return rc; }
+    hv[i].depth = src.depth;
+  }
+  MapStats st;  // waits for the map: its table is complete
+  { const int rc = read_stats(m, &st); if (rc) return rc; }
+  hipStream_t s = (hipStream_t)m->g.stream;
+  MapCarveRun r;
+  const size_t o_views = 256 + ((sizeof(revo_map_carve_view_info) * n + 255) & ~(size_t)255);
+  HIPCHECK(hipMalloc((void**)&r.buf, o_views + sizeof(MapCarveView) * n));
+  if (up_bytes) {
+    HIPCHECK(hipMalloc((void**)&r.images, up_bytes));
+    size_t o = 0;
+    for (int i = 0; i < n; ++i) {
+      if (!views[i].depth) continue;
+      const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * sizeof(float);
+      HIPCHECK(hipMemcpyAsync(r.images + o, views[i].depth, bytes, hipMemcpyHostToDevice, s));
+      hv[i].depth = (const float*)(r.images + o);
+      o += (bytes + 255) & ~(size_t)255;
+    }
+  }
+  HIPCHECK(hipMemcpyAsync(r.buf + o_views, hv.data(), sizeof(MapCarveView) * n, hipMemcpyHostToDevice, s));
+  MapCarveK a{};
+  a.keys = m->d_keys; a.vals = m->d_vals; a.cap = (unsigned)m->cap;
+  a.views = (const MapCarveView*)(r.buf + o_views); a.n = n;
+  a.radius = pp.radius; a.min_views = pp.min_views;
+  a.min_count = pp.min_count; a.max_count = pp.max_count;
+  a.margin = pp.margin; a.margin_rel = pp.margin_rel;
+  revo_map_carve_info ci{};
+  std::vector<revo_map_carve_view_info> vi(n);
+  // nothing may be written when cap is too small: count first, then write (carve_launch waits, so hv and the images are read)
+  { const int rc = carve_launch(m, s, &r, a, &ci, vi.data()); if (rc) return rc; }
+  const size_t carved = (size_t)ci.voxels_carved;
+  *n_records = carved;
+  if (info) *info = ci;
+  if (view_info) memcpy(view_info, vi.data(), sizeof(revo_map_carve_view_info) * n);
+  if (records && cap < carved) return fail(REVO_ERR_CAPACITY, "voxel map: the output holds fewer records than voxels are carved");
+  if (!carved || (!records && !remove)) return REVO_OK;
+  ulonglong2* d_rec = (ulonglong2*)records;
+  if (!records || !device_out) {
+    HIPCHECK(hipMalloc((void**)&r.recs, sizeof(revo_map_voxel_raw) * carved));
+    d_rec = (ulonglong2*)r.recs;
+  }
+  a.out = d_rec; a.cap_out = (unsigned)carved;
+  revo_map_carve_info ci2{};
+  { const int rc = carve_launch(m, s, &r, a, &ci2, vi.data()); if (rc) return rc; }
+  if (ci2.voxels_carved != ci.voxels_carved) return fail(REVO_ERR_HIP, "voxel map: two carve launches over one table disagree");
+  if (remove) {
+    MapMergeK sub{};
+    sub.recs = d_rec;
+    sub.n = (unsigned)carved;
+    const int rc = subtract_core(m, sub, MERGE_RAW, 0, 0);  // has waited: the records are read
+    if (rc) return rc;  // nothing removed: the host output stays untouched
+  }
+  if (records && !device_out) {  // after the removal, so that host records are only ever records that left (or would leave) the map
+    HIPCHECK(hipMemcpy(records, d_rec, sizeof(revo_map_voxel_raw) * carved, hipMemcpyDeviceToHost));
+    carve_canonicalise(records, carved);
+  }
+  return REVO_OK;
+}
+
+extern "C" int revo_map_carve_eval(revo_map* m, int n, const revo_map_carve_view* views, int device_in, const revo_map_carve_params* prm,
+                                   revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
+                                   revo_map_carve_view_info* view_info) {
+  return carve_apply(m, n, views, device_in, prm, records, cap, n_records, device_out, info, view_info, false);
+}
+extern "C" int revo_map_carve(revo_map* m, int n, const revo_map_carve_view* views, int device_in, const revo_map_carve_params* prm,
+                              revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
+                              revo_map_carve_view_info* view_info) {
+  return carve_apply(m, n, views, device_in, prm, records, cap, n_records, device_out, info, view_info, true);
 }

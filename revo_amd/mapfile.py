@@ -16,6 +16,13 @@ Equal maps give equal files.
     python -m revo_amd.mapfile transform A POSE.txt -o OUT [--voxel V] [--min-count N]
                                                         map A seen under a pose (revo_map_pose_raw), without a GPU:
                                                         POSE.txt holds 16 or 12 numbers, a row-major 4x4 or 3x4, A's frame -> OUT's
+    python -m revo_amd.mapfile carve A --views DIR -o OUT [--removed R] [--radius N] [--margin M] [--margin-rel F] [--min-views K]
+                                                        [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX]
+                                                        [--depth-scale S]
+                                                        map A without the voxels the views of DIR look through (revo_map_carve,
+                                                        DESIGN 19), without a GPU: DIR is a `run_tum --map-views` folder (depth/,
+                                                        associate.txt, poses.txt); R gets the removed voxels, so that
+                                                        `merge X OUT R` holds A's voxels again
     python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
 """
 import struct
@@ -244,6 +251,141 @@ def pose_records(records, T, voxel_dst, min_count=1):
     return merge_records(out, np.zeros(0, RAW_DTYPE)), info
 
 
+CARVE_CLASSES = ("outside", "unknown", "free", "confirmed", "occluded", "edge")
+CARVE_INFO_KEYS = ("voxels_considered", "voxels_carved", "points_carved", "votes")
+
+
+def carve_view(depth, T_w_c, intrinsics):
+    """One view of carve_records, checked as revo_map_carve checks it: depth [h, w] float32 metres (1 .. 2048 each way), T_w_c a
+    4x4 or 3x4 camera -> world pose (finite, rotation orthogonal), intrinsics (fx, fy, cx, cy, zmin, zmax) finite with fx, fy > 0
+    and 0 <= zmin < zmax.  -> (depth, Rc, tc, k): the world -> camera rotation and translation as revo_map_render forms them."""
+    D = np.ascontiguousarray(np.asarray(depth, np.float32))
+    if D.ndim != 2 or not (1 <= D.shape[0] <= 2048 and 1 <= D.shape[1] <= 2048):
+        raise ValueError("a depth image is h x w with 1 .. 2048 pixels each way")
+    T = _pose_matrix(T_w_c)
+    k = np.asarray(intrinsics, np.float32).reshape(-1)
+    if k.shape != (6,) or not np.all(np.isfinite(k)):
+        raise ValueError("the intrinsics are six finite numbers: fx, fy, cx, cy, zmin, zmax")
+    if not (k[0] > 0 and k[1] > 0):
+        raise ValueError("fx and fy must be > 0")
+    if not (k[4] >= 0 and k[4] < k[5]):
+        raise ValueError("the depth range needs 0 <= zmin < zmax")
+    Rc = T[:3, :3].T.copy()
+    t = T[:3, 3]
+    tc = np.array([-(((Rc[i, 0] * t[0]) + (Rc[i, 1] * t[1])) + (Rc[i, 2] * t[2])) for i in range(3)], np.float32)
+    return D, Rc, tc, k
+
+
+def carve_classes(p, view, radius, margin, margin_rel):
+    """The class (index into CARVE_CLASSES) of every point p [N, 3] float32 in one checked view (carve_view): revo_map_carve's
+    rule (include/revo_hip.h), float32 operation by operation."""
+    D, Rc, tc, k = view
+    f32 = np.float32
+    fx, fy, cx, cy, zmin, zmax = (f32(x) for x in k)
+    r, margin, margin_rel = int(radius), f32(margin), f32(margin_rel)
+    h, w = D.shape
+    px, py, pz = p[:, 0], p[:, 1], p[:, 2]
+    cls = np.zeros(len(p), np.int64)  # outside
+    with np.errstate(all="ignore"):
+        x, y, z = (((Rc[i, 0] * px + Rc[i, 1] * py) + Rc[i, 2] * pz) + tc[i] for i in range(3))
+        ok = np.isfinite(x) & np.isfinite(y) & np.isfinite(z) & (z > zmin) & (z < zmax)
+        u = (fx * x) / z + cx
+        v = (fy * y) / z + cy
+        ok &= (np.abs(u) < f32(1 << 20)) & (np.abs(v) < f32(1 << 20))  # NaN / inf fail the comparison
+        iu = np.floor(np.where(ok, u, f32(0)) + f32(0.5)).astype(np.int64)
+        iv = np.floor(np.where(ok, v, f32(0)) + f32(0.5)).astype(np.int64)
+        ok &= (iu - r >= 0) & (iu + r <= w - 1) & (iv - r >= 0) & (iv + r <= h - 1)
+        j = np.nonzero(ok)[0]
+        iu, iv, z = iu[j], iv[j], z[j]
+        usable = np.ones(len(j), bool)
+        dmin = np.full(len(j), np.inf, f32)
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                d = D[iv + dy, iu + dx]
+                good = np.isfinite(d) & (d > zmin) & (d < zmax)
+                usable &= good
+                dmin = np.where(good, np.minimum(dmin, d), dmin)
+        dc = D[iv, iu]
+        mc = margin + margin_rel * dc
+        c = np.where(z < dmin - (margin + margin_rel * dmin), 2,
+                     np.where(np.abs(z - dc) <= mc, 3, np.where(z > dc + mc, 4, 5)))
+    cls[j] = np.where(usable, c, 1)
+    return cls
+
+
+def carve_records(records, voxel, views, radius=1, min_views=1, min_count=1, max_count=0, margin=None, margin_rel=0.0):
+    """Free-space carving without a GPU: revo_map_carve_eval's contract in vectorised numpy.  views: a list of
+    (depth [h, w] float32, T_w_c, (fx, fy, cx, cy, zmin, zmax)).  Per voxel with count >= max(min_count, 1) (and <= max_count
+    unless that is 0) and per view its class; a voxel that is `free` in at least max(min_views, 1) views is carved.  margin
+    None: the voxel edge.  -> (the carved voxels' records in ascending key order -- subtract_records(records, them) is the carved
+    map --, info dict of CARVE_INFO_KEYS, one dict of CARVE_CLASSES counts per view).  ValueError as the library's
+    REVO_ERR_INVALID_ARG."""
+    rec = as_records(records)
+    check_records(rec)
+    if not 0 <= int(radius) <= 3:
+        raise ValueError("radius must be 0 .. 3")
+    margin = np.float32(voxel if margin is None else margin)
+    margin_rel = np.float32(margin_rel)
+    if not (np.isfinite(margin) and margin >= 0 and np.isfinite(margin_rel) and margin_rel >= 0):
+        raise ValueError("margin and margin_rel must be finite and >= 0")
+    views = list(views)
+    if not 1 <= len(views) <= 64:
+        raise ValueError("a carve takes 1 .. 64 views")
+    views = [carve_view(*v) for v in views]
+    sel = rec["count"] >= np.uint64(max(1, int(min_count)))
+    if int(max_count):
+        sel &= rec["count"] <= np.uint64(int(max_count))
+    cand = rec[sel]
+    p = ((cand["sum_q"].astype(np.float64) / cand["count"].astype(np.float64)[:, None]) * 2.0 ** -20).astype(np.float32).reshape(-1, 3)
+    votes = np.zeros(len(cand), np.int64)
+    counts = []
+    for vw in views:
+        cls = carve_classes(p, vw, radius, margin, margin_rel)
+        votes += cls == 2
+        counts.append({name: int((cls == i).sum()) for i, name in enumerate(CARVE_CLASSES)})
+    gone = cand[votes >= max(1, int(min_views))]
+    info = {"voxels_considered": len(cand), "voxels_carved": len(gone), "points_carved": int(gone["count"].sum(dtype=np.uint64)),
+            "votes": int(votes.sum())}
+    return gone.copy(), info, counts
+
+
+def carve_file(path, views_dir, camera, zrange, depth_scale=5000.0, **params):
+    """(header, records, removed header, removed records, info) of the file's map carved with the views of a `run_tum
+    --map-views` folder: depth/*.png (16-bit, metres x depth_scale), associate.txt and poses.txt (the pose of each depth
+    image by time stamp).  camera (fx, fy, cx, cy) and zrange (zmin, zmax) say how the views were taken.  The removed voxels
+    carry no dropped points and no keyframes, so the two headers add up to the file's."""
+    import os
+    from . import tum
+    header, rec = read(path)
+    rows = tum.read_associate(os.path.join(views_dir, "associate.txt"))
+    poses = {round(ts, 6): T for ts, T in tum.read_poses(os.path.join(views_dir, "poses.txt"))}
+    views = []
+    for rgb_ts, rgb_file, depth_ts, depth_file in rows:
+        T = poses.get(round(float(rgb_ts), 6), poses.get(round(float(depth_ts), 6)))
+        if T is None:
+            raise ValueError("%s: no pose in poses.txt for the view at %s" % (views_dir, rgb_ts))
+        raw = tum.load_frame(views_dir, rgb_file, depth_file)[1]
+        views.append((raw.astype(np.float32) / np.float32(depth_scale), T, tuple(camera) + tuple(zrange)))
+    if not views:
+        raise ValueError("%s holds no views" % views_dir)
+    gone = np.zeros(0, RAW_DTYPE)
+    info = dict.fromkeys(CARVE_INFO_KEYS, 0)
+    if int(params.get("min_views", 1)) <= 1:  # 64 views per carve; with min_views 1 carving in parts is carving at once
+        for i in range(0, len(views), 64):
+            g, part, _ = carve_records(rec, header["voxel"], views[i:i + 64], **params)
+            rec = subtract_records(rec, g)
+            gone = merge_records(gone, g)
+            # considered: the map's candidates, counted once (the first part sees them all); votes: those cast on voxels still there
+            info = dict({k: info[k] + part[k] for k in info}, voxels_considered=part["voxels_considered"] if i == 0 else info["voxels_considered"])
+    else:
+        if len(views) > 64:
+            raise ValueError("a carve with --min-views above 1 takes at most 64 views, %s holds %d" % (views_dir, len(views)))
+        gone, info, _ = carve_records(rec, header["voxel"], views, **params)
+        rec = subtract_records(rec, gone)
+    h = dict(header, voxels=len(rec), points_integrated=header["points_integrated"] - int(gone["count"].sum(dtype=np.uint64)))
+    return h, rec, make_header(header["voxel"], header["dense"], gone), gone, info
+
+
 def read_pose(path):
     """A pose from a text file of 16 or 12 numbers: a row-major 4x4 or 3x4."""
     with open(path) as f:
@@ -352,6 +494,33 @@ def main(argv=None):
                 print("%s: %d voxels of %g m (%s under %s: %d voxels moved, %d dropped, %d skipped)"
                       % (opt["-o"], len(rec), h["voxel"], pos[0], pos[1], info["voxels_moved"], info["voxels_dropped"], info["voxels_skipped"]))
                 return 0
+        if cmd == "carve" and "-o" in args and "--views" in args:
+            opt = {"-o": 1, "--views": 1, "--removed": 1, "--radius": 1, "--margin": 1, "--margin-rel": 1, "--min-views": 1,
+                   "--min-count": 1, "--max-count": 1, "--camera": 4, "--zrange": 2, "--depth-scale": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1:
+                params = {name: conv(val[o][0]) for o, name, conv in (("--radius", "radius", int), ("--margin", "margin", float),
+                                                                       ("--margin-rel", "margin_rel", float), ("--min-views", "min_views", int),
+                                                                       ("--min-count", "min_count", int), ("--max-count", "max_count", int))
+                          if o in val}
+                camera = [float(x) for x in val.get("--camera", (525.0, 525.0, 319.5, 239.5))]  # the TUM default camera
+                zrange = [float(x) for x in val.get("--zrange", (0.1, 5.2))]
+                h, rec, hg, gone, info = carve_file(pos[0], val["--views"][0], camera, zrange, float(val.get("--depth-scale", [5000.0])[0]),
+                                                    **params)
+                write(val["-o"][0], h, rec)
+                if "--removed" in val:
+                    write(val["--removed"][0], hg, gone)
+                print("%s: %d voxels (%s carved with the views of %s: %d voxels, %d points removed)"
+                      % (val["-o"][0], len(rec), pos[0], val["--views"][0], len(gone), int(gone["count"].sum(dtype=np.uint64))))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -363,7 +532,8 @@ def main(argv=None):
         print("mapfile: %s" % e)
         return 1
     print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | coarsen A SHIFT -o OUT | "
-          "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | ply FILE [OUT.ply]")
+          "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | carve A --views DIR -o OUT [--removed R] [--radius N] [--margin M] "
+          "[--margin-rel F] [--min-views K] [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | ply FILE [OUT.ply]")
     return 2
 
 

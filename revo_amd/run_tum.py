@@ -19,6 +19,11 @@ rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more t
 keyframe's voxel sums are subtracted again, exactly): map_<dataset>.ply, --map-save and --map-views then describe that windowed
 map, and map_window_<dataset>.txt lists the keyframes it holds, oldest first: time stamp and the 16 entries of T_w_kf (row-major,
 %.9g: float32 exactly).  The pose file does not depend on it.
+--map-carve (with --map, sequential driver only) carves free space with every new keyframe before it is integrated (vo.REVO's
+carve): voxels the keyframe's depth image looks through -- moved objects, people, mixed-depth points -- leave the
+map.  --map-carve-margin M sets the margin in metres (default: the voxel edge), --map-carve-views K the views a voxel must be
+free in (default 1; a keyframe is one view, so K > 1 carves nothing).  An error with --map-window and with --streams.  The pose
+file does not depend on it.
 --covariances writes cov_<dataset>.txt next to the pose file, one line per pose line in the same order: the frame's time stamp,
 its keyframe's time stamp, the good-point count, sigma2 and the 21 upper-triangle entries (row-major) of the 6x6 covariance of the
 relative pose frame -> keyframe (api.pair_covariance of the level-0 settings.PairInfo at the final pose; translation 0-2,
@@ -35,7 +40,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-views DIR [--map-views-every K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-views DIR [--map-views-every K]] [--map-carve [--map-carve-margin M] [--map-carve-views K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -97,6 +102,35 @@ def main(argv=None):
     if views_every and views_dir is None:
         print("--map-views-every needs --map-views DIR")
         return 2
+    map_carve = None  # vo.REVO's carve: free-space carving with every new keyframe
+    for opt, key, conv in (("--map-carve-margin", "margin", float), ("--map-carve-views", "min_views", int)):
+        if opt in argv:
+            i = argv.index(opt)
+            try:
+                map_carve = dict(map_carve or {}, **{key: conv(argv[i + 1])})
+            except (IndexError, ValueError):
+                print("%s needs a number: --map-carve-margin a margin >= 0 in metres, --map-carve-views a positive number of views" % opt)
+                return 2
+            argv = argv[:i] + argv[i + 2:]
+    if "--map-carve" in argv:
+        argv = [a for a in argv if a != "--map-carve"]
+        map_carve = map_carve or {}
+    elif map_carve is not None:
+        print("--map-carve-margin and --map-carve-views need --map-carve")
+        return 2
+    if map_carve is not None:
+        if map_voxel is None:
+            print("--map-carve carves the voxel map: it needs --map VOXEL")
+            return 2
+        if map_window:
+            print("--map-carve is not supported together with --map-window: the window's per-keyframe records must stay subtractable")
+            return 2
+        if "--streams" in argv:
+            print("--map-carve is not supported together with --streams: carving runs on the sequential driver only (drop --streams)")
+            return 2
+        if not (np.isfinite(map_carve.get("margin", 0.0)) and map_carve.get("margin", 0.0) >= 0) or map_carve.get("min_views", 1) < 1:
+            print("--map-carve-margin needs a margin >= 0 in metres, --map-carve-views a positive number of views")
+            return 2
     exact_sums = "--exact-sums" in argv  # the tracker's exact-sums mode (both drivers)
     if exact_sums:
         argv = [a for a in argv if a != "--exact-sums"]
@@ -140,7 +174,7 @@ def main(argv=None):
         if map_window:
             vmap = api.MapWindow(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"]), window=map_window)
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
-                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances)
+                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances, carve=map_carve)
         nd = tum.default_decoders() if decoders is None else decoders
         rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
                                   read_n_images=io["read_n_images"])
@@ -164,6 +198,12 @@ def main(argv=None):
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
         if vmap is not None:
             _save_map(vmap, name, _rvm_path(map_save, name, len(io["datasets"]) > 1))
+            if map_carve is not None:
+                done = [c[2] for c in drv.carves if c[2] is not None]
+                print("Map carve: %d voxels (%d points) carved by %d keyframes%s"
+                      % (sum(i["voxels_carved"] for i in done), sum(i["points_carved"] for i in done), len(done),
+                         (" -- %d keyframes carved NOTHING: their pose's rotation had drifted past the orthogonality rule"
+                          % drv.carve_skipped) if drv.carve_skipped else ""))
             if map_window:
                 with open("map_window_%s.txt" % name, "w") as f:
                     for ts, T in zip(vmap.timestamps, vmap.keyframes):

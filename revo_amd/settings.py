@@ -233,6 +233,34 @@ class MapPoseInfo(C.Structure):
 assert C.sizeof(MapPoseInfo) == 64
 
 
+class MapCarveView(C.Structure):
+    """revo_map_carve_view (include/revo_hip.h), 112 bytes: one view of revo_map_carve -- a pyramid (kf) or a raw depth image."""
+    _fields_ = [
+        ("kf", C.c_void_p), ("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("zmin", C.c_float), ("zmax", C.c_float),
+        ("T_w_c", C.c_float * 16),
+    ]
+
+
+class MapCarveParams(C.Structure):
+    """revo_map_carve_params (include/revo_hip.h), 24 bytes."""
+    _fields_ = [("radius", C.c_int32), ("min_views", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32),
+                ("margin", C.c_float), ("margin_rel", C.c_float)]
+
+
+class MapCarveInfo(C.Structure):
+    """revo_map_carve_info (include/revo_hip.h), 64 bytes: what a carve considered and removed."""
+    _fields_ = [(k, C.c_uint64) for k in ("voxels_considered", "voxels_carved", "points_carved", "votes")] + [("reserved", C.c_uint64 * 4)]
+
+
+class MapCarveViewInfo(C.Structure):
+    """revo_map_carve_view_info (include/revo_hip.h), 32 bytes: the candidates of one view by class."""
+    _fields_ = [(k, C.c_uint32) for k in ("outside", "unknown", "free_space", "confirmed", "occluded", "edge")] + [("reserved", C.c_uint32 * 2)]
+
+
+assert (C.sizeof(MapCarveView), C.sizeof(MapCarveParams), C.sizeof(MapCarveInfo), C.sizeof(MapCarveViewInfo)) == (112, 24, 64, 32)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

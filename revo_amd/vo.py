@@ -22,7 +22,7 @@ from .settings import PairInfo, StreamFrame, StreamResult, TrackerSettings
 
 class REVO:
     def __init__(self, settingsPyr, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False):
+                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False, carve=None):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         self.camPyr = cameraPyr or api.CameraPyr(settingsPyr, device=device)
@@ -38,6 +38,19 @@ class REVO:
         # api.VoxelMap: every keyframe the driver reports (the first frame included) is fused into it at its T_w_kf, the moment
         # the drawer gets its cloud; on the device, no cloud goes through the host
         self.voxelMap = voxelMap
+        # carve: True or a dict of api.VoxelMap.carve's parameters (radius, min_views, min_count, max_count, margin, margin_rel):
+        # free-space carving with every new keyframe's own pyramid at its T_w_kf, BEFORE that keyframe is
+        # integrated -- what the keyframe looks through leaves the map, then what it sees joins it.  carves[i]: (keyframe time
+        # stamp, T_w_kf, info dict) per keyframe, info None where the pose's rotation fails the library's is_orthogonal rule
+        # (that keyframe carves nothing, is counted in carve_skipped and warned about once; it is integrated all the same).  Off by default: nothing new is enqueued.
+        self.carve = None if carve is None or carve is False else ({} if carve is True else dict(carve))
+        self.carves = []
+        self.carve_skipped = 0  # keyframes that carved nothing for their pose (warned about once)
+        if self.carve is not None:
+            if voxelMap is None:
+                raise ValueError("carve needs a voxelMap")
+            if isinstance(voxelMap, api.MapWindow):
+                raise ValueError("carve is not supported with a MapWindow: its per-keyframe records must stay subtractable")
         # pair_info: every reported pose comes with its level-0 settings.PairInfo (the information matrix of the relative pose
         # curr -> keyframe at the final pose) and that keyframe's time stamp: pair_infos[i] belongs to poses[i]
         self.pair_info = bool(pair_info)
@@ -96,8 +109,23 @@ class REVO:
             if self.mpMapDrawer is not None:
                 self.mpMapDrawer.addPclAndKfPoseToQueue(kfPyr.generateColoredPcl(0, self.generate_dense_pcl), T_w_kf)
             if self.voxelMap is not None:
+                if self.carve is not None:
+                    self._carve_with(kfPyr, T_w_kf)
                 self.voxelMap.integrate(kfPyr, T_w_kf)
         return M, bool(kf.value)
+
+    def _carve_with(self, kfPyr, T_w_kf):
+        from . import mapfile
+        info = None
+        if mapfile.pose_is_orthogonal(np.asarray(T_w_kf, np.float32)[:3, :3]):
+            _, info, _ = self.voxelMap.carve([(kfPyr, T_w_kf)], records=False, **self.carve)
+        else:
+            self.carve_skipped += 1
+            if self.carve_skipped == 1:
+                import warnings
+                warnings.warn("REVO carve: the rotation of a keyframe pose is no longer orthogonal to 1e-5 (float32 drift); that "
+                              "keyframe carves nothing -- see REVO.carve_skipped for how many", RuntimeWarning, stacklevel=3)
+        self.carves.append((kfPyr.returnTimestamp(), np.array(T_w_kf, np.float32), info))
 
     def keyframe(self):
         """(kfPyr, kfPyr->getTransKFtoWorld()); the pyramid is borrowed -- valid until the next track_next."""
