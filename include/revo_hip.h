@@ -1074,6 +1074,82 @@ int revo_map_carve(revo_map* m, int n, const revo_map_carve_view* views, int dev
                    revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
                    revo_map_carve_view_info* view_info);
 
+/* ---- rays through the map: hole-free views and range queries ---------------------------------------------
+ * A ray visits the cells of the voxel grid in an order fixed by float32 arithmetic, one thread walks one ray alone and a hit
+ * is a table lookup: no atomics decide anything, so the outputs are a pure function of the map's bytes and the rays -- the same
+ * bytes whatever the table size, integration order, batching of views or launch.
+ * All arithmetic is float32 with every operation rounded on its own; a / b is the correctly rounded quotient.
+ *
+ * A ray is o[3], s0, d[3], s1: the points o + s*d for s0 <= s < s1.  d is not normalised: s is in the unit d gives it.
+ * The march, with `voxel` the map's edge:
+ *  1. Start cell: g_i = o_i + s0*d_i, f_i = floorf(g_i / voxel).  The ray is OUTSIDE with 0 cells unless s0 < s1 (false for
+ *     NaN), s1 is finite, every g_i is finite and -1048576 <= f_i <= 1048575.  k_i = (int)f_i.
+ *  2. Per axis: inv_i = 1 / d_i.  d_i > 0: step_i = +1, pos_i = 1.  d_i < 0: step_i = -1, pos_i = 0.  d_i zero or NaN, or inv_i
+ *     not finite: step_i = 0 and t_i = +inf.  Otherwise t_i = (((float)(k_i + pos_i)) * voxel - o_i) * inv_i.
+ *  3. Loop, starting with s = s0 and cells = 0:
+ *     - if cells == max_steps the ray is EXHAUSTED;
+ *     - cells += 1; the cell k, packed into a key as integration packs it, is examined at entry parameter s: if it is solid,
+ *       the ray is a HIT;
+ *     - a = 0; if (t_1 < t_a) a = 1; if (t_2 < t_a) a = 2 (ties go to the lowest axis, NaN never wins); sn = t_a;
+ *     - if !(sn < s1) the ray is a RANGE miss;
+ *     - k_a += step_a; if k_a leaves [-2^20, 2^20 - 1] the ray is OUTSIDE;
+ *     - s = sn, then t_a = (((float)(k_a + pos_a)) * voxel - o_a) * inv_a: recomputed from the integer index, never
+ *       accumulated, so there is no drift.
+ * Solid: the table holds the key with count >= max(min_count, 1).  For the rays of a view there is one more condition: the
+ * voxel's point p, exactly as revo_map_extract forms it, taken to the camera exactly as revo_map_render does (Rc, tc formed on
+ * the host, pc = ((Rc[:,0]*px + Rc[:,1]*py) + Rc[:,2]*pz) + tc), must be finite with zmin < z < zmax; a voxel that fails this is
+ * transparent, as it is invisible to revo_map_render.  Cells that are not solid are marched through.
+ *
+ * A view is a revo_map_view with revo_map_render's rules and all-zero defaults; splat_max is not read.  Pixel (x, y) casts
+ * dcx = ((float)x - cx)/fx, dcy = ((float)y - cy)/fy, d_i = ((R_i0*dcx) + (R_i1*dcy)) + R_i2 (R the rotation of T_w_c),
+ * o = the translation of T_w_c, s0 = zmin, s1 = zmax: s is camera depth.
+ * Hit: depth = z of the hit voxel's pc (> 0, so never the 0 of a miss), bgr = its colour as revo_map_extract rounds it,
+ * key = its key: the voxel's mean, not the face of its cell.  Miss: depth 0, bgr 0, key all ones. */
+typedef struct revo_map_ray_params {  /* 16 bytes; NULL: max_steps 4096 */
+  uint32_t max_steps;       /* 1 .. 2^20: the cells a ray examines at most */
+  uint32_t reserved[3];     /* zero */
+} revo_map_ray_params;
+typedef struct revo_map_ray {         /* 32 bytes */
+  float o[3], s0, d[3], s1;
+} revo_map_ray;
+#define REVO_RAY_HIT 0u
+#define REVO_RAY_RANGE 1u
+#define REVO_RAY_OUTSIDE 2u
+#define REVO_RAY_EXHAUSTED 3u
+typedef struct revo_map_ray_hit {     /* 16 bytes per ray */
+  uint64_t key;             /* the hit voxel's key; all ones unless the ray is a hit                               */
+  float s;                  /* the entry parameter of the last cell examined (0 when no cell was)                  */
+  uint32_t cells;           /* bits 0-23: the cells examined; bits 30-31: the status REVO_RAY_*; the rest zero      */
+} revo_map_ray_hit;
+typedef struct revo_map_ray_info {    /* 64 bytes, little-endian, no padding: integer sums over the rays of a call */
+  uint64_t rays, hits, range, outside, exhausted;   /* rays = the sum of the four statuses */
+  uint64_t cells;           /* cells examined in total */
+  uint64_t reserved[2];     /* zero */
+} revo_map_ray_info;
+/* n views (1 .. 64, sizes may differ) of the map as it is behind every integration enqueued so far: one launch that builds the
+ * table of occupied 8 x 8 x 8 blocks and one that marches a ray per pixel, on the context's tracker stream.  depth[i] (h x w
+ * floats) is required; bgr (h x w x 3 bytes per view), key (h x w uint64 per view), hits (n entries: the hit pixels of each
+ * view) and info (one record for the call) may be NULL, and bgr[i] / key[i] follow their array.  Every view must carry the
+ * same max(min_count, 1).  device_out = 0: host pointers, the call waits.  device_out = 1: device pointers (every output,
+ * hits and info included, 16-byte aligned), the call only enqueues.  An empty map gives all misses.  The map is not changed.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, views or depth, a NULL depth[i], bgr[i]
+ * or key[i] of a given array; n outside 1 .. 64; revo_map_render's view rules (size, pose, intrinsics, depth range); views of
+ * different min_count; max_steps outside 1 .. 2^20; a reserved word that is not 0; device_out not 0 or 1; a misaligned device
+ * pointer. */
+int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, const revo_map_ray_params* prm, float* const* depth,
+                     uint8_t* const* bgr, uint64_t* const* key, uint32_t* hits, int device_out, revo_map_ray_info* info);
+/* n rays (1 .. 2^24) against the voxels with count >= max(min_count, 1): one revo_map_ray_hit per ray.  device_in: where the
+ * rays live (0: host memory, uploaded to a temporary buffer, the call waits; 1: device memory of the map's device, 16-byte
+ * aligned).  device_out: as above, for out and info (NULL allowed).  A ray that is not finite or has s0 >= s1 is no argument
+ * error: it comes back OUTSIDE with 0 cells.  REVO_ERR_INVALID_ARG as above: NULL m, rays or out; n outside 1 .. 2^24; the
+ * parameter rules; a flag outside 0 / 1; a misaligned device pointer. */
+int revo_map_cast_rays(revo_map* m, size_t n, const revo_map_ray* rays, int device_in, uint32_t min_count,
+                       const revo_map_ray_params* prm, revo_map_ray_hit* out, int device_out, revo_map_ray_info* info);
+/* Waits for the last revo_map_raycast / revo_map_cast_rays of m and gives the device time from the start of its block-table
+ * launch to the end of its march (HIP events on the tracker stream), in milliseconds.  REVO_ERR_INVALID_ARG if m has cast
+ * nothing yet. */
+int revo_map_raycast_last_ms(revo_map* m, float* ms);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

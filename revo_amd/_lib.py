@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -163,6 +163,9 @@ def lib():
     for fn in (L.revo_map_carve_eval, L.revo_map_carve):
         fn.argtypes = [vp, C.c_int, C.POINTER(MapCarveView), C.c_int, C.POINTER(MapCarveParams), vp, C.c_size_t, C.POINTER(C.c_size_t),
                        C.c_int, C.POINTER(MapCarveInfo), C.POINTER(MapCarveViewInfo)]
+    L.revo_map_raycast.argtypes = [vp, C.c_int, vp, C.POINTER(MapRayParams), vpp, vpp, vpp, vp, C.c_int, vp]
+    L.revo_map_cast_rays.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_uint32, C.POINTER(MapRayParams), vp, C.c_int, vp]
+    L.revo_map_raycast_last_ms.argtypes = [vp, f32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -718,9 +718,113 @@ class VoxelMap:
         if wait:
             self.sync()
 
+    # -- rays through the map (revo_map_raycast / revo_map_cast_rays)
+    @staticmethod
+    def _ray_info(i):
+        from . import mapfile
+        return {k: int(getattr(i, k)) for k in mapfile.RAY_INFO_KEYS}
+
+    def raycast(self, T_w_c, camera=None, zrange=None, min_count=1, max_steps=4096, keys=False):
+        """The map seen from the camera pose T_w_c by marching one ray per pixel through the voxel grid (revo_map_raycast,
+        DESIGN 20): (depth [h, w] float32 metres, 0 = no voxel on the ray; bgr [h, w, 3] uint8; hits = pixels with a depth) and,
+        with keys=True, a fourth value: the hit voxel's key per pixel ([h, w] uint64, all ones = miss).  No footprint
+        parameter and no holes: a pixel shows the nearest voxel whose cell its ray crosses, at that voxel's mean.  A list or
+        (n, 4, 4) array of poses is ONE library call and returns lists.  camera, zrange: see _views.  `ray_info` holds the
+        call's counters afterwards (mapfile.RAY_INFO_KEYS)."""
+        views, n, single = self._views(T_w_c, camera, zrange, 0, min_count)
+        if n == 0:
+            return ([], [], [], []) if keys else ([], [], [])
+        depth = [np.empty((v.height, v.width), np.float32) for v in views]
+        bgr = [np.empty((v.height, v.width, 3), np.uint8) for v in views]
+        key = [np.empty((v.height, v.width), np.uint64) for v in views] if keys else None
+        hits = np.zeros(n, np.uint32)
+        info = MapRayInfo()
+        dp = (vp * n)(*[a.ctypes.data for a in depth])
+        bp = (vp * n)(*[a.ctypes.data for a in bgr])
+        kp = (vp * n)(*[a.ctypes.data for a in key]) if keys else None
+        prm = MapRayParams(int(max_steps))
+        check(_lib.lib().revo_map_raycast(self._h, n, views, C.byref(prm), dp, bp, kp, hits.ctypes.data_as(vp), 0, C.byref(info)))
+        self.ray_info = self._ray_info(info)
+        out = (depth[0], bgr[0], int(hits[0])) if single else (depth, bgr, [int(c) for c in hits])
+        return out + ((key[0] if single else key,) if keys else ())
+
+    def raycast_into(self, d_depth, d_bgr, T_w_c, camera=None, zrange=None, min_count=1, max_steps=4096, d_keys=None, d_hits=None,
+                     d_info=None, wait=True):
+        """raycast() into torch device tensors: d_depth [n, h, w] float32 (or [h, w] for one pose), d_bgr [n, h, w, 3] uint8 or
+        None, d_keys None or an int64 / uint64 tensor shaped like d_depth, d_hits None or n 32-bit entries, d_info None or a
+        64-byte tensor (revo_map_ray_info); contiguous, on the map's device, every view's part 16-byte aligned.  Enqueued on
+        the context's tracker stream: wait=True returns when it is done, wait=False at once (sync() orders later reads)."""
+        views, n, single = self._views(T_w_c, camera, zrange, 0, min_count)
+        h, w = views[0].height, views[0].width
+        shape = (h, w) if single else (n, h, w)
+        if tuple(d_depth.shape) != shape or (d_bgr is not None and tuple(d_bgr.shape) != shape + (3,)) or \
+                (d_keys is not None and tuple(d_keys.shape) != shape):
+            raise ValueError("output tensors do not match the views")
+        if str(d_depth.dtype) != "torch.float32" or (d_bgr is not None and str(d_bgr.dtype) != "torch.uint8") or \
+                (d_keys is not None and d_keys.element_size() != 8):
+            raise ValueError("d_depth must be float32, d_bgr uint8 and d_keys a 64-bit integer tensor")
+        for t_ in (d_depth, d_bgr, d_keys, d_hits, d_info):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("output tensors must be contiguous device tensors")
+        if d_hits is not None and (d_hits.numel() != n or d_hits.element_size() != 4):
+            raise ValueError("d_hits needs n 32-bit entries")
+        if d_info is not None and d_info.numel() * d_info.element_size() != 64:
+            raise ValueError("d_info needs 64 bytes")
+        dp = (vp * n)(*[d_depth.data_ptr() + 4 * h * w * i for i in range(n)])
+        bp = (vp * n)(*[d_bgr.data_ptr() + 3 * h * w * i for i in range(n)]) if d_bgr is not None else None
+        kp = (vp * n)(*[d_keys.data_ptr() + 8 * h * w * i for i in range(n)]) if d_keys is not None else None
+        import torch
+        torch.cuda.current_stream(d_depth.device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
+        prm = MapRayParams(int(max_steps))
+        check(_lib.lib().revo_map_raycast(self._h, n, views, C.byref(prm), dp, bp, kp, vp(d_hits.data_ptr()) if d_hits is not None else None,
+                                          1, vp(d_info.data_ptr()) if d_info is not None else None))
+        if wait:
+            self.sync()
+
+    def cast_rays(self, origins, dirs, s0, s1, min_count=1, max_steps=4096, device=False):
+        """Range queries (revo_map_cast_rays): ray i is the points origins[i] + s dirs[i] for s0[i] <= s < s1[i]
+        (dirs need not be normalised; s0, s1 scalars or [N]), marched through the voxel grid until it meets a voxel with count
+        >= min_count.  -> (keys uint64 [N], all ones unless a hit; s float32 [N], the entry parameter of the last cell examined
+        -- of the hit voxel's cell for a hit; cells uint32 [N]; status uint8 [N], the index into mapfile.RAY_STATUS: hit, range,
+        outside, exhausted; info dict of mapfile.RAY_INFO_KEYS).  A ray that is not finite or has s0 >= s1 comes back
+        `outside` with 0 cells.  device=True: the rays go through a torch device tensor and the results come back through one
+        (the library's device path); the return values are the same."""
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        n = len(o)
+        rays = np.empty((n, 8), np.float32)
+        rays[:, 0:3], rays[:, 4:7] = o, np.asarray(dirs, np.float32).reshape(-1, 3)
+        rays[:, 3], rays[:, 7] = np.asarray(s0, np.float32), np.asarray(s1, np.float32)
+        prm = MapRayParams(int(max_steps))
+        from . import mapfile
+        L = _lib.lib()
+        if device:
+            import torch
+            dev = "cuda:%d" % self.cameraPyr.device
+            d_rays = torch.from_numpy(rays).to(dev)
+            d_out = torch.empty(16 * n, dtype=torch.uint8, device=dev)
+            d_info = torch.empty(64, dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(d_out.device).synchronize()
+            check(L.revo_map_cast_rays(self._h, n, vp(d_rays.data_ptr()), 1, int(min_count), C.byref(prm), vp(d_out.data_ptr()), 1,
+                                       vp(d_info.data_ptr())))
+            self.sync()
+            out, info = d_out.cpu().numpy(), d_info.cpu().numpy().view(np.uint64)
+        else:
+            out, info = np.zeros(16 * n, np.uint8), np.zeros(8, np.uint64)
+            check(L.revo_map_cast_rays(self._h, n, rays.ctypes.data_as(vp), 0, int(min_count), C.byref(prm), out.ctypes.data_as(vp), 0,
+                                       info.ctypes.data_as(vp)))
+        r = out.view(np.dtype([("key", "<u8"), ("s", "<f4"), ("cells", "<u4")]))
+        return (r["key"].copy(), r["s"].copy(), r["cells"] & np.uint32(0xFFFFFF), (r["cells"] >> np.uint32(30)).astype(np.uint8),
+                dict(zip(mapfile.RAY_INFO_KEYS, (int(x) for x in info[:6]))))
+
     def sync(self):
         """Waits for the map's enqueued work (integrations and render_into calls)."""
         self.info()
+
+    def last_raycast_ms(self):
+        """Device time of the last raycast / raycast_into / cast_rays call (block table + march, HIP events), in milliseconds."""
+        ms = C.c_float()
+        check(_lib.lib().revo_map_raycast_last_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def last_render_ms(self):
         """Device time of the last render / render_into call (splat + resolve, HIP events), in milliseconds; waits for it."""
@@ -863,6 +967,16 @@ class MapWindow:
     def integrate_many(self, pyrs, T_ws):
         for p, T in zip(pyrs, T_ws):
             self.integrate(p, T)
+
+    def raycast(self, *args, **kw):
+        """The inner map's raycast (the window only decides which keyframes the map holds)."""
+        return self.map.raycast(*args, **kw)
+
+    def raycast_into(self, *args, **kw):
+        return self.map.raycast_into(*args, **kw)
+
+    def cast_rays(self, *args, **kw):
+        return self.map.cast_rays(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

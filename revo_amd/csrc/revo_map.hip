@@ -29,6 +29,7 @@
 #include "revo_align_host.h"
 #include "revo_pose_host.h"
 #include "revo_carve_host.h"
+#include "revo_ray_host.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -605,6 +606,13 @@ struct revo_map {
   char* d_vout = nullptr; size_t vout_bytes = 0;
   MapViewK* h_views = nullptr; MapViewK* d_views = nullptr; unsigned* d_cov = nullptr; int cap_views = 0;
   hipEvent_t ev_views = nullptr, ev_r0 = nullptr, ev_r1 = nullptr; bool views_recorded = false, rendered = false;
+  // revo_map_raycast / revo_map_cast_rays: the block table (bcap slots), the counter lines, the views' descriptors (pinned +
+  // device; struct MapRayView), the device outputs of a host-output call and the call's events
+  u64* d_bkeys = nullptr; size_t bcap = 0;
+  char* d_rcnt = nullptr;
+  struct MapRayView* h_rviews = nullptr; struct MapRayView* d_rviews = nullptr; int cap_rviews = 0;
+  char* d_rout = nullptr; size_t rout_bytes = 0;
+  hipEvent_t ev_rviews = nullptr, ev_c0 = nullptr, ev_c1 = nullptr; bool rviews_recorded = false, raycast = false;
 };
 
 extern "C" int revo_map_stage_create_(revo_map_stage** out) {
@@ -802,6 +810,10 @@ extern "C" void revo_map_destroy(revo_map* m) {
   if (m->ev_views) hipEventDestroy(m->ev_views);
   if (m->ev_r0) hipEventDestroy(m->ev_r0);
   if (m->ev_r1) hipEventDestroy(m->ev_r1);
+  hipFree(m->d_bkeys); hipFree(m->d_rcnt); hipFree(m->d_rviews); hipFree(m->d_rout); hipHostFree(m->h_rviews);
+  if (m->ev_rviews) hipEventDestroy(m->ev_rviews);
+  if (m->ev_c0) hipEventDestroy(m->ev_c0);
+  if (m->ev_c1) hipEventDestroy(m->ev_c1);
   (void)hipGetLastError();
   revo_ctx_release_(m->ctx);
   delete m;
@@ -2407,4 +2419,373 @@ extern "C" int revo_map_carve(revo_map* m, int n, const revo_map_carve_view* vie
                               revo_map_voxel_raw* records, size_t cap, size_t* n_records, int device_out, revo_map_carve_info* info,
                               revo_map_carve_view_info* view_info) {
   return carve_apply(m, n, views, device_in, prm, records, cap, n_records, device_out, info, view_info, true);
+}
+
+// --------------------------------------------------------------------------------------------- rays through the map (20) --
+// revo_map_raycast / revo_map_cast_rays (contract: include/revo_hip.h).
+struct MapRayK {  // what every ray of a launch shares
+  const u64* keys; const MapVal* vals; unsigned mask;  // the map's table
+  const u64* bkeys; unsigned bmask;                    // the keys of the occupied 8 x 8 x 8 blocks (NULL: every cell is looked up)
+  u64 min_count;                                       // >= 1
+  unsigned max_steps;
+  float voxel;
+  u64* info;                                           // one 64-byte line: revo_map_ray_info's counters
+};
+struct MapRayView {  // one view of a launch, in device memory
+  RayView v;
+  float* depth; uint8_t* bgr; u64* key; unsigned* hits;  // bgr, key: NULL when not asked for
+};
+struct MapRayOut { u64 key; float s; unsigned cells; float z; unsigned bgr; };  // z, bgr (B | G << 8 | R << 16): view rays only
+enum { RAY_HIT = 0, RAY_RANGE = 1, RAY_OUTSIDE = 2, RAY_EXHAUSTED = 3, RAY_STATUSES = 4 };
+
+__device__ __forceinline__ u64 map_ray_key(int kx, int ky, int kz) {
+  return ((u64)(kx + (1 << 20)) << 42) | ((u64)(ky + (1 << 20)) << 21) | (u64)(kz + (1 << 20));
+}
+// step, pos and the first crossing parameter of one axis
+__device__ __forceinline__ void map_ray_axis(float o, float d, int k, float voxel, int& step, int& pos, float& inv, float& t) {
+  inv = __fdiv_rn(1.0f, d);
+  step = d > 0.0f ? 1 : (d < 0.0f ? -1 : 0);
+  pos = d > 0.0f ? 1 : 0;
+  if (!isfinite(inv)) step = 0;
+  t = step ? ((float)(k + pos) * voxel - o) * inv : INFINITY;
+}
+
+// The one text of the contract's march.  VIEW: the voxel must also lie in the view's depth range (vw's Rc, tc, zmin, zmax).
+// The axis choice is written with selects on scalars: no private array is indexed at run time.  The block table only decides
+// whether the fine table is asked; the stepping does not know of it.
+template <bool VIEW>
+__device__ __forceinline__ int map_ray_march(const MapRayK& a, const RayView* vw, float ox, float oy, float oz, float s0, float dx,
+                                             float dy, float dz, float s1, MapRayOut& out) {
+  out.key = MAP_EMPTY; out.s = 0.0f; out.cells = 0; out.z = 0.0f; out.bgr = 0;
+  const float gx = ox + s0 * dx, gy = oy + s0 * dy, gz = oz + s0 * dz;
+  const float fx = floorf(__fdiv_rn(gx, a.voxel)), fy = floorf(__fdiv_rn(gy, a.voxel)), fz = floorf(__fdiv_rn(gz, a.voxel));
+  if (!(s0 < s1) || !isfinite(s1) || !isfinite(gx) || !isfinite(gy) || !isfinite(gz)) return RAY_OUTSIDE;
+  if (!(fx >= -1048576.0f && fx <= 1048575.0f && fy >= -1048576.0f && fy <= 1048575.0f && fz >= -1048576.0f && fz <= 1048575.0f))
+    return RAY_OUTSIDE;
+  int kx = (int)fx, ky = (int)fy, kz = (int)fz;
+  int stx, sty, stz, psx, psy, psz;
+  float ivx, ivy, ivz, tx, ty, tz;
+  map_ray_axis(ox, dx, kx, a.voxel, stx, psx, ivx, tx);
+  map_ray_axis(oy, dy, ky, a.voxel, sty, psy, ivy, ty);
+  map_ray_axis(oz, dz, kz, a.voxel, stz, psz, ivz, tz);
+  float s = s0;
+  unsigned cells = 0;
+  u64 last_block = MAP_EMPTY;  // no block key reaches it
+  bool block_occupied = true;
+  for (;;) {
+    if (cells == a.max_steps) { out.cells = cells; return RAY_EXHAUSTED; }
+    ++cells;
+    out.s = s;
+    const u64 key = map_ray_key(kx, ky, kz);
+    if (a.bkeys) {
+      const u64 bk = map_ray_key(kx >> 3, ky >> 3, kz >> 3);  // map_coarse_key(key, 3)
+      if (bk != last_block) { last_block = bk; block_occupied = map_find(a.bkeys, a.bmask, bk) != ~0u; }
+    }
+    if (block_occupied) {
+      const unsigned slot = map_find(a.keys, a.mask, key);
+      if (slot != ~0u) {
+        const ulonglong2* v = (const ulonglong2*)(a.vals + slot);
+        const ulonglong2 p = v[0];  // n qx
+        if (p.x >= a.min_count) {
+          bool solid = true;
+          if (VIEW) {
+            const ulonglong2 q = v[1], c = v[2], e = v[3];  // qy qz | sb sg | sr -
+            const double inv = (double)p.x;
+            const float px = map_mean(p.y, inv), py = map_mean(q.x, inv), pz = map_mean(q.y, inv);
+            const float x = ((vw->Rc[0] * px + vw->Rc[1] * py) + vw->Rc[2] * pz) + vw->tc[0];
+            const float y = ((vw->Rc[3] * px + vw->Rc[4] * py) + vw->Rc[5] * pz) + vw->tc[1];
+            const float z = ((vw->Rc[6] * px + vw->Rc[7] * py) + vw->Rc[8] * pz) + vw->tc[2];
+            solid = isfinite(x) && isfinite(y) && map_depth_ok(z, vw->zmin, vw->zmax);
+            if (solid) {
+              const u64 h = p.x / 2;
+              out.z = z;
+              out.bgr = (unsigned)((c.x + h) / p.x) | ((unsigned)((c.y + h) / p.x) << 8) | ((unsigned)((e.x + h) / p.x) << 16);
+            }
+          }
+          if (solid) { out.key = key; out.cells = cells; return RAY_HIT; }
+        }
+      }
+    }
+    int ax = 0;
+    float sn = tx;
+    if (ty < sn) { ax = 1; sn = ty; }
+    if (tz < sn) { ax = 2; sn = tz; }
+    if (!(sn < s1)) { out.cells = cells; return RAY_RANGE; }
+    const int kn = (ax == 0 ? kx + stx : (ax == 1 ? ky + sty : kz + stz));
+    if (kn < -(1 << 20) || kn > (1 << 20) - 1) { out.cells = cells; return RAY_OUTSIDE; }
+    const int pn = kn + (ax == 0 ? psx : (ax == 1 ? psy : psz));
+    const float tn = ((float)pn * a.voxel - (ax == 0 ? ox : (ax == 1 ? oy : oz))) * (ax == 0 ? ivx : (ax == 1 ? ivy : ivz));
+    s = sn;
+    if (ax == 0) { kx = kn; tx = tn; } else if (ax == 1) { ky = kn; ty = tn; } else { kz = kn; tz = tn; }
+  }
+}
+
+// One thread per slot of the table: the key of the 8 x 8 x 8 block around every voxel with count >= min_count goes into a
+// keys-only table of as many slots (a block holds at least one voxel, so its load is at most the map's).
+__global__ void __launch_bounds__(256) k_map_ray_blocks(const u64* __restrict__ keys, const MapVal* __restrict__ vals, unsigned cap,
+                                                        u64 min_count, u64* bkeys, unsigned bmask, u64* fault) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cap) return;
+  const u64 key = keys[i];
+  if (key == MAP_EMPTY || vals[i].n < min_count) return;
+  map_slot<true>(bkeys, bmask, map_coarse_key(key, 3), nullptr, fault);
+}
+
+// The statuses and cells of a block's rays: ballots per wave into LDS, then one global atomic per counter.  Every thread of
+// the block calls it (status < 0: no ray).
+__device__ __forceinline__ void map_ray_count(const MapRayK& a, int status, unsigned cells, unsigned* s_cnt, u64* s_cells, unsigned* hits) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < RAY_STATUSES; ++k) {
+    const u64 b = __ballot(status == k);
+    if (lane == 0 && b) atomicAdd(&s_cnt[k], (unsigned)__popcll(b));
+  }
+  unsigned c = status < 0 ? 0u : cells;  // <= 2^20 per ray: a wave's sum fits
+#pragma unroll
+  for (int off = 32; off; off >>= 1) c += __shfl_down(c, off, 64);
+  if (lane == 0 && c) atomicAdd(s_cells, (u64)c);
+  __syncthreads();
+  if (threadIdx.x < RAY_STATUSES && s_cnt[threadIdx.x]) atomicAdd(&a.info[1 + threadIdx.x], (u64)s_cnt[threadIdx.x]);
+  if (threadIdx.x == 4 && *s_cells) atomicAdd(&a.info[5], *s_cells);
+  if (threadIdx.x == 5) {
+    const unsigned rays = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (rays) atomicAdd(&a.info[0], (u64)rays);
+  }
+  if (threadIdx.x == 6 && hits && s_cnt[RAY_HIT]) atomicAdd(hits, s_cnt[RAY_HIT]);
+}
+
+// One thread per pixel, blockIdx.y = view.  A wave is an 8 x 8 pixel tile (its rays end after similar numbers of steps), a
+// block four tiles side by side; blocks past a view's tiles leave at once.
+__global__ void __launch_bounds__(256) k_map_raycast(const MapRayK a, const MapRayView* __restrict__ views) {
+  __shared__ unsigned s_cnt[RAY_STATUSES];
+  __shared__ u64 s_cells;
+  const MapRayView& vw = views[blockIdx.y];
+  const RayView& c = vw.v;
+  const unsigned bw = (unsigned)(c.w + 31) / 32, bh = (unsigned)(c.h + 7) / 8;
+  if (blockIdx.x >= bw * bh) return;
+  if (threadIdx.x < RAY_STATUSES) s_cnt[threadIdx.x] = 0;
+  if (threadIdx.x == 4) s_cells = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int x = (int)((blockIdx.x % bw) * 32 + (threadIdx.x >> 6) * 8 + (lane & 7));
+  const int y = (int)((blockIdx.x / bw) * 8 + (lane >> 3));
+  int status = -1;
+  MapRayOut o{};
+  if (x < c.w && y < c.h) {
+    const float dcx = __fdiv_rn((float)x - c.cx, c.fx), dcy = __fdiv_rn((float)y - c.cy, c.fy);
+    const float dx = ((c.R[0] * dcx) + (c.R[1] * dcy)) + c.R[2];
+    const float dy = ((c.R[3] * dcx) + (c.R[4] * dcy)) + c.R[5];
+    const float dz = ((c.R[6] * dcx) + (c.R[7] * dcy)) + c.R[8];
+    status = map_ray_march<true>(a, &c, c.o[0], c.o[1], c.o[2], c.zmin, dx, dy, dz, c.zmax, o);
+    const size_t p = (size_t)y * c.w + x;
+    vw.depth[p] = o.z;  // 0 unless a hit
+    if (vw.bgr) {
+      uint8_t* b = vw.bgr + p * 3;
+      b[0] = (uint8_t)o.bgr; b[1] = (uint8_t)(o.bgr >> 8); b[2] = (uint8_t)(o.bgr >> 16);
+    }
+    if (vw.key) vw.key[p] = o.key;
+  }
+  map_ray_count(a, status, o.cells, s_cnt, &s_cells, vw.hits);
+}
+
+// One thread per given ray: two 16-byte loads, the march, one 16-byte store.
+__global__ void __launch_bounds__(256) k_map_cast_rays(const MapRayK a, const float4* __restrict__ rays, unsigned n, ulonglong2* out) {
+  __shared__ unsigned s_cnt[RAY_STATUSES];
+  __shared__ u64 s_cells;
+  if (threadIdx.x < RAY_STATUSES) s_cnt[threadIdx.x] = 0;
+  if (threadIdx.x == 4) s_cells = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  int status = -1;
+  MapRayOut o{};
+  if (i < n) {
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];  // o s0 | d s1
+    status = map_ray_march<false>(a, nullptr, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, o);
+    out[i] = make_ulonglong2(o.key, (u64)__float_as_uint(o.s) | ((u64)(o.cells | ((unsigned)status << 30)) << 32));
+  }
+  map_ray_count(a, status, o.cells, s_cnt, &s_cells, nullptr);
+}
+
+static_assert(sizeof(revo_map_ray_params) == 16 && offsetof(revo_map_ray_params, max_steps) == 0 && offsetof(revo_map_ray_params, reserved) == 4,
+              "the parameter record is the documented layout");
+static_assert(sizeof(revo_map_ray) == 32 && offsetof(revo_map_ray, o) == 0 && offsetof(revo_map_ray, s0) == 12 &&
+              offsetof(revo_map_ray, d) == 16 && offsetof(revo_map_ray, s1) == 28, "a ray is the kernel's two 16-byte words");
+static_assert(sizeof(revo_map_ray_hit) == 16 && offsetof(revo_map_ray_hit, key) == 0 && offsetof(revo_map_ray_hit, s) == 8 &&
+              offsetof(revo_map_ray_hit, cells) == 12, "a ray's result is the kernel's one 16-byte word");
+static_assert(sizeof(revo_map_ray_info) == 64 && offsetof(revo_map_ray_info, rays) == 0 && offsetof(revo_map_ray_info, hits) == 8 * (1 + RAY_HIT) &&
+              offsetof(revo_map_ray_info, range) == 8 * (1 + RAY_RANGE) && offsetof(revo_map_ray_info, outside) == 8 * (1 + RAY_OUTSIDE) &&
+              offsetof(revo_map_ray_info, exhausted) == 8 * (1 + RAY_EXHAUSTED) && offsetof(revo_map_ray_info, cells) == 40 &&
+              offsetof(revo_map_ray_info, reserved) == 48, "the info record is the kernel's counter line");
+static_assert(REVO_RAY_HIT == RAY_HIT && REVO_RAY_RANGE == RAY_RANGE && REVO_RAY_OUTSIDE == RAY_OUTSIDE && REVO_RAY_EXHAUSTED == RAY_EXHAUSTED,
+              "the header's statuses are the kernel's");
+
+// Room for a call: the block table (as many slots as the map's table), the counter lines, the views' descriptors (pinned +
+// device), the device outputs of a host-output call.
+static int ray_reserve(revo_map* m, int n_views, size_t out_bytes) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  if (!m->ev_rviews) {
+    HIPCHECK(hipEventCreateWithFlags(&m->ev_rviews, hipEventDisableTiming));
+    HIPCHECK(hipEventCreate(&m->ev_c0));
+    HIPCHECK(hipEventCreate(&m->ev_c1));
+    HIPCHECK(hipMalloc((void**)&m->d_rcnt, 512));  // [0, 64) the info line, [64, 64 + 4 x 64) the views' hits
+  }
+  if (m->rviews_recorded) HIPCHECK(hipEventSynchronize(m->ev_rviews));  // the previous upload has read the pinned rows
+  if (n_views > m->cap_rviews) {
+    HIPCHECK(hipStreamSynchronize(s));  // the previous call's kernel reads the descriptors
+    (void)hipHostFree(m->h_rviews); (void)hipFree(m->d_rviews);
+    m->h_rviews = nullptr; m->d_rviews = nullptr; m->cap_rviews = 0;
+    HIPCHECK(hipHostMalloc((void**)&m->h_rviews, sizeof(MapRayView) * n_views));
+    HIPCHECK(hipMalloc((void**)&m->d_rviews, sizeof(MapRayView) * n_views));
+    m->cap_rviews = n_views;
+  }
+  if (m->cap > m->bcap) {
+    HIPCHECK(hipStreamSynchronize(s));
+    (void)hipFree(m->d_bkeys);
+    m->d_bkeys = nullptr; m->bcap = 0;
+    HIPCHECK(hipMalloc((void**)&m->d_bkeys, sizeof(u64) * m->cap));
+    m->bcap = m->cap;
+  }
+  if (out_bytes > m->rout_bytes) {
+    HIPCHECK(hipStreamSynchronize(s));
+    (void)hipFree(m->d_rout);
+    m->d_rout = nullptr; m->rout_bytes = 0;
+    HIPCHECK(hipMalloc((void**)&m->d_rout, out_bytes));
+    m->rout_bytes = out_bytes;
+  }
+  return REVO_OK;
+}
+
+// What both entry points share: the first event, the block table of the map as it is on the stream, the cleared counters.
+// REVO_MAP_RAYCAST_BLOCKS=0: no block table, every cell is looked up (the exactness test and profiles/map_raycast_rates.py).
+static int ray_begin(revo_map* m, MapRayK* a, u64 min_count, unsigned max_steps, u64* d_info, unsigned* d_hits, int n_hits) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  a->keys = m->d_keys; a->vals = m->d_vals; a->mask = (unsigned)(m->cap - 1);
+  a->min_count = min_count; a->max_steps = max_steps; a->voxel = m->voxel;
+  a->info = d_info;
+  HIPCHECK(hipEventRecord(m->ev_c0, s));
+  a->bkeys = nullptr; a->bmask = 0;
+  if (env_int("REVO_MAP_RAYCAST_BLOCKS", 1, 0, 1)) {
+    HIPCHECK(hipMemsetAsync(m->d_bkeys, 0xff, sizeof(u64) * m->cap, s));
+    hipLaunchKernelGGL(k_map_ray_blocks, dim3((unsigned)((m->cap + 255) / 256)), dim3(256), 0, s, m->d_keys, m->d_vals, (unsigned)m->cap,
+                       min_count, m->d_bkeys, (unsigned)(m->cap - 1), &m->d_st->fault);
+    HIPCHECK(hipGetLastError());
+    a->bkeys = m->d_bkeys; a->bmask = (unsigned)(m->cap - 1);
+  }
+  HIPCHECK(hipMemsetAsync(d_info, 0, sizeof(revo_map_ray_info), s));
+  if (n_hits) HIPCHECK(hipMemsetAsync(d_hits, 0, sizeof(unsigned) * n_hits, s));
+  return REVO_OK;
+}
+
+extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, const revo_map_ray_params* prm, float* const* depth,
+                                uint8_t* const* bgr, uint64_t* const* key, uint32_t* hits, int device_out, revo_map_ray_info* info) {
+  if (!m || !views || !depth) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n < 1 || n > RAY_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, "revo_map_raycast: n must be 1 .. 64 views");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_out && (((uintptr_t)hits | (uintptr_t)info) & 15)) return fail(REVO_ERR_INVALID_ARG, "hits or info is not 16-byte aligned");
+  uint32_t max_steps = 0;
+  if (const char* why = ray_params_check(prm, &max_steps)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_raycast: ") + why);
+  const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
+  std::vector<RayView> rv(n);
+  size_t out_bytes = 0;
+  int max_blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const std::string at = "view " + std::to_string(i) + ": ";
+    if (!depth[i] || (bgr && !bgr[i]) || (key && !key[i])) return fail(REVO_ERR_INVALID_ARG, at + "null output");
+    if (device_out && (((uintptr_t)depth[i] | (uintptr_t)(bgr ? bgr[i] : nullptr) | (uintptr_t)(key ? key[i] : nullptr)) & 15))
+      return fail(REVO_ERR_INVALID_ARG, at + "a device output is not 16-byte aligned");
+    if (const char* why = ray_view_check(&views[i], cam, &rv[i])) return fail(REVO_ERR_INVALID_ARG, at + why);
+    const size_t np = (size_t)rv[i].w * rv[i].h;
+    out_bytes += (np * (4 + (bgr ? 3 : 0) + (key ? 8 : 0)) + 15) & ~(size_t)15;
+    max_blocks = std::max(max_blocks, ((rv[i].w + 31) / 32) * ((rv[i].h + 7) / 8));
+  }
+  const uint32_t min_count = ray_views_min_count(views, n);
+  if (!min_count) return fail(REVO_ERR_INVALID_ARG, "revo_map_raycast: every view of a call must carry the same min_count");
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  { const int rc = ray_reserve(m, n, device_out ? 0 : out_bytes); if (rc) return rc; }
+  u64* d_info = device_out && info ? (u64*)info : (u64*)m->d_rcnt;
+  unsigned* d_hits = device_out && hits ? hits : (unsigned*)(m->d_rcnt + 64);
+  size_t oo = 0;
+  for (int i = 0; i < n; ++i) {
+    MapRayView& d = m->h_rviews[i];
+    d.v = rv[i];
+    const size_t np = (size_t)rv[i].w * rv[i].h;
+    if (device_out) {
+      d.depth = depth[i]; d.bgr = bgr ? bgr[i] : nullptr; d.key = key ? (u64*)key[i] : nullptr;
+    } else {  // keys, depth, colour: the widest first
+      char* b = m->d_rout + oo;
+      d.key = key ? (u64*)b : nullptr;
+      b += key ? np * 8 : 0;
+      d.depth = (float*)b;
+      d.bgr = bgr ? (uint8_t*)(b + np * 4) : nullptr;
+      oo += (np * (4 + (bgr ? 3 : 0) + (key ? 8 : 0)) + 15) & ~(size_t)15;
+    }
+    d.hits = d_hits + i;
+  }
+  HIPCHECK(hipMemcpyAsync(m->d_rviews, m->h_rviews, sizeof(MapRayView) * n, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(m->ev_rviews, s));
+  m->rviews_recorded = true;
+  MapRayK a{};
+  { const int rc = ray_begin(m, &a, min_count, max_steps, d_info, d_hits, n); if (rc) return rc; }
+  hipLaunchKernelGGL(k_map_raycast, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), 0, s, a, m->d_rviews);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(m->ev_c1, s));
+  m->raycast = true;
+  if (device_out) return REVO_OK;
+  for (int i = 0; i < n; ++i) {
+    const MapRayView& d = m->h_rviews[i];
+    const size_t np = (size_t)rv[i].w * rv[i].h;
+    HIPCHECK(hipMemcpyAsync(depth[i], d.depth, np * 4, hipMemcpyDeviceToHost, s));
+    if (bgr) HIPCHECK(hipMemcpyAsync(bgr[i], d.bgr, np * 3, hipMemcpyDeviceToHost, s));
+    if (key) HIPCHECK(hipMemcpyAsync(key[i], d.key, np * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (hits) HIPCHECK(hipMemcpyAsync(hits, d_hits, sizeof(unsigned) * n, hipMemcpyDeviceToHost, s));
+  if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_ray_info), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+extern "C" int revo_map_cast_rays(revo_map* m, size_t n, const revo_map_ray* rays, int device_in, uint32_t min_count,
+                                  const revo_map_ray_params* prm, revo_map_ray_hit* out, int device_out, revo_map_ray_info* info) {
+  if (!m || !rays || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n < 1 || n > RAY_MAX_RAYS) return fail(REVO_ERR_INVALID_ARG, "revo_map_cast_rays: n must be 1 .. 2^24 rays");
+  if (device_in != 0 && device_in != 1) return fail(REVO_ERR_INVALID_ARG, "device_in must be 0 or 1");
+  if (device_out != 0 && device_out != 1) return fail(REVO_ERR_INVALID_ARG, "device_out must be 0 or 1");
+  if (device_in && ((uintptr_t)rays & 15)) return fail(REVO_ERR_INVALID_ARG, "the device rays are not 16-byte aligned");
+  if (device_out && (((uintptr_t)out | (uintptr_t)info) & 15)) return fail(REVO_ERR_INVALID_ARG, "a device output is not 16-byte aligned");
+  uint32_t max_steps = 0;
+  if (const char* why = ray_params_check(prm, &max_steps)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_cast_rays: ") + why);
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  { const int rc = ray_reserve(m, 0, device_out ? 0 : sizeof(revo_map_ray_hit) * n); if (rc) return rc; }
+  struct Upload { void* p = nullptr; ~Upload() { (void)hipFree(p); (void)hipGetLastError(); } } up;  // freed after the wait below
+  const float4* d_rays = (const float4*)rays;
+  if (!device_in) {
+    HIPCHECK(hipMalloc(&up.p, sizeof(revo_map_ray) * n));
+    HIPCHECK(hipMemcpyAsync(up.p, rays, sizeof(revo_map_ray) * n, hipMemcpyHostToDevice, s));
+    d_rays = (const float4*)up.p;
+  }
+  u64* d_info = device_out && info ? (u64*)info : (u64*)m->d_rcnt;
+  ulonglong2* d_out = device_out ? (ulonglong2*)out : (ulonglong2*)m->d_rout;
+  MapRayK a{};
+  { const int rc = ray_begin(m, &a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0); if (rc) { (void)hipStreamSynchronize(s); return rc; } }
+  hipLaunchKernelGGL(k_map_cast_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, d_rays, (unsigned)n, d_out);
+  if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); return fail(REVO_ERR_HIP, "k_map_cast_rays: the launch failed"); }
+  HIPCHECK(hipEventRecord(m->ev_c1, s));
+  m->raycast = true;
+  if (!device_out) {
+    HIPCHECK(hipMemcpyAsync(out, d_out, sizeof(revo_map_ray_hit) * n, hipMemcpyDeviceToHost, s));
+    if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_ray_info), hipMemcpyDeviceToHost, s));
+  }
+  if (!device_out || !device_in) HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+extern "C" int revo_map_raycast_last_ms(revo_map* m, float* ms) {
+  if (!m || !ms) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (!m->raycast) return fail(REVO_ERR_INVALID_ARG, "the map has cast nothing yet");
+  HIPCHECK(hipSetDevice(m->g.device));
+  HIPCHECK(hipEventSynchronize(m->ev_c1));
+  HIPCHECK(hipEventElapsedTime(ms, m->ev_c0, m->ev_c1));
+  return REVO_OK;
 }

@@ -386,6 +386,191 @@ def carve_file(path, views_dir, camera, zrange, depth_scale=5000.0, **params):
     return h, rec, make_header(header["voxel"], header["dense"], gone), gone, info
 
 
+RAY_STATUS = ("hit", "range", "outside", "exhausted")
+RAY_INFO_KEYS = ("rays", "hits", "range", "outside", "exhausted", "cells")
+RAY_EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+RAY_MAX_STEPS = 1 << 20
+
+
+def _ray_march(o, s0, d, s1, voxel, solid_keys, max_steps):
+    """The march of revo_map_raycast / revo_map_cast_rays (include/revo_hip.h) for N rays at once, float32 operation
+    by operation: every ray still under way advances one cell per iteration.  o, d [N, 3], s0, s1 [N] float32; solid_keys: the
+    ascending keys of the solid voxels.  -> (index into solid_keys or -1, s float32, cells int64, status int64), [N] each."""
+    f32 = np.float32
+    voxel = f32(voxel)
+    o, d = np.asarray(o, f32).reshape(-1, 3), np.asarray(d, f32).reshape(-1, 3)
+    s0, s1 = np.asarray(s0, f32).reshape(-1), np.asarray(s1, f32).reshape(-1)
+    n = len(o)
+    hit = np.full(n, -1, np.int64)
+    s_out = np.zeros(n, f32)
+    cells = np.zeros(n, np.int64)
+    status = np.full(n, 2, np.int64)  # outside
+    lo, hi = -(1 << 20), (1 << 20) - 1
+    with np.errstate(all="ignore"):
+        g = o + s0[:, None] * d
+        f = np.floor(g / voxel)
+        ok = (s0 < s1) & np.isfinite(s1) & np.all(np.isfinite(g), 1) & np.all((f >= f32(lo)) & (f <= f32(hi)), 1)
+        idx = np.nonzero(ok)[0]
+        o, d, s1 = o[idx], d[idx], s1[idx]
+        k = f[idx].astype(np.int64)
+        inv = f32(1) / d
+        step = np.where(d > 0, 1, np.where(d < 0, -1, 0)).astype(np.int64)
+        step[~np.isfinite(inv)] = 0
+        pos = (d > 0).astype(np.int64)
+        t = np.where(step != 0, ((k + pos).astype(f32) * voxel - o) * inv, f32(np.inf)).astype(f32)
+        s = s0[idx].copy()
+        bias = np.int64(1 << 20)
+        done = 0
+        while len(idx):
+            if done == int(max_steps):
+                status[idx] = 3
+                break
+            done += 1
+            cells[idx] = done
+            s_out[idx] = s
+            kb = (k + bias).astype(np.uint64)
+            key = (kb[:, 0] << np.uint64(42)) | (kb[:, 1] << np.uint64(21)) | kb[:, 2]
+            j = np.searchsorted(solid_keys, key)
+            j[j >= len(solid_keys)] = 0
+            found = solid_keys[j] == key if len(solid_keys) else np.zeros(len(idx), bool)
+            hit[idx[found]] = j[found]
+            status[idx[found]] = 0
+            a = np.zeros(len(idx), np.int64)
+            sn = t[:, 0].copy()
+            for ax in (1, 2):
+                m = t[:, ax] < sn
+                a[m] = ax
+                sn[m] = t[m, ax]
+            far = ~found & ~(sn < s1)
+            status[idx[far]] = 1
+            r = np.arange(len(idx))
+            kn = k[r, a] + step[r, a]
+            out = ~found & ~far & ((kn < lo) | (kn > hi))  # status stays outside
+            go = ~found & ~far & ~out
+            k[r, a] = kn
+            t[r, a] = ((kn + pos[r, a]).astype(f32) * voxel - o[r, a]) * inv[r, a]
+            idx, o, s1, k, inv, step, pos, t, s = idx[go], o[go], s1[go], k[go], inv[go], step[go], pos[go], t[go], sn[go]
+    return hit, s_out, cells, status
+
+
+def _ray_info(status, cells):
+    return {"rays": int(len(status)), "hits": int((status == 0).sum()), "range": int((status == 1).sum()),
+            "outside": int((status == 2).sum()), "exhausted": int((status == 3).sum()), "cells": int(cells.sum())}
+
+
+def _ray_args(records, voxel, min_count, max_steps):
+    rec = as_records(records)
+    check_records(rec)
+    v = np.float32(voxel)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError("the voxel edge must be finite and > 0")
+    if not 1 <= int(max_steps) <= RAY_MAX_STEPS:
+        raise ValueError("max_steps must be 1 .. 2^20")
+    return rec[rec["count"] >= np.uint64(max(1, int(min_count)))], v
+
+
+def ray_view(T_w_c, intrinsics, size):
+    """One view of raycast_records, checked as revo_map_raycast checks it (revo_map_render's rules): T_w_c a finite 4x4 or 3x4
+    camera -> world pose, intrinsics (fx, fy, cx, cy, zmin, zmax) finite with fx, fy > 0 and 0 <= zmin < zmax, size (width,
+    height), 1 .. 2048 each.  -> (o, R, Rc, tc, k, (w, h)): the rays' origin and rotation, and the world -> camera transform as
+    revo_map_render forms it."""
+    T = np.asarray(T_w_c, np.float32)
+    if T.shape == (3, 4):
+        T = np.vstack([T, np.float32([0, 0, 0, 1])])
+    if T.shape != (4, 4) or not np.all(np.isfinite(T)):
+        raise ValueError("a pose is a finite 4x4 or 3x4 matrix")
+    w, h = int(size[0]), int(size[1])
+    if not (1 <= w <= 2048 and 1 <= h <= 2048):
+        raise ValueError("width and height must be 1 .. 2048")
+    k = np.asarray(intrinsics, np.float32).reshape(-1)
+    if k.shape != (6,) or not np.all(np.isfinite(k)):
+        raise ValueError("the intrinsics are six finite numbers: fx, fy, cx, cy, zmin, zmax")
+    if not (k[0] > 0 and k[1] > 0):
+        raise ValueError("fx and fy must be > 0")
+    if not (k[4] >= 0 and k[4] < k[5]):
+        raise ValueError("the depth range needs 0 <= zmin < zmax")
+    R = T[:3, :3].copy()
+    Rc = R.T.copy()
+    t = T[:3, 3].copy()
+    tc = np.array([-(((Rc[i, 0] * t[0]) + (Rc[i, 1] * t[1])) + (Rc[i, 2] * t[2])) for i in range(3)], np.float32)
+    return t, R, Rc, tc, k, (w, h)
+
+
+def ray_view_rays(view):
+    """(o [N, 3], s0 [N], d [N, 3], s1 [N]) of a checked view's pixels in row order: pixel (x, y) casts dcx = (x - cx) / fx,
+    dcy = (y - cy) / fy, d_i = ((R_i0 dcx) + (R_i1 dcy)) + R_i2 from the camera's position over [zmin, zmax)."""
+    o, R, _, _, k, (w, h) = view
+    f32 = np.float32
+    xs, ys = np.meshgrid(np.arange(w, dtype=f32), np.arange(h, dtype=f32))
+    dcx = ((xs - k[2]) / k[0]).ravel()
+    dcy = ((ys - k[3]) / k[1]).ravel()
+    d = np.stack([((R[i, 0] * dcx) + (R[i, 1] * dcy)) + R[i, 2] for i in range(3)], 1).astype(f32)
+    n = w * h
+    return np.broadcast_to(o, (n, 3)).copy(), np.full(n, k[4], f32), d, np.full(n, k[5], f32)
+
+
+def ray_view_solid(rec, view):
+    """The voxels of `rec` (count already selected) that are solid to a checked view: their point as to_points forms it, taken
+    to the camera as revo_map_render does, is finite with zmin < z < zmax.  -> (keys, z float32, bgr uint8 [n, 3])."""
+    _, _, Rc, tc, k, _ = view
+    cnt = rec["count"]
+    p = ((rec["sum_q"].astype(np.float64) / cnt.astype(np.float64)[:, None]) * 2.0 ** -20).astype(np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        x, y, z = (((Rc[i, 0] * p[:, 0] + Rc[i, 1] * p[:, 1]) + Rc[i, 2] * p[:, 2]) + tc[i] for i in range(3))
+        ok = np.isfinite(x) & np.isfinite(y) & np.isfinite(z) & (z > k[4]) & (z < k[5])
+    c = cnt[:, None]
+    bgr = ((rec["sum_bgr"] + c // np.uint64(2)) // c).astype(np.uint8).reshape(-1, 3)
+    return rec["key"][ok], z[ok].astype(np.float32), bgr[ok]
+
+
+def raycast_records(records, voxel, views, min_count=1, max_steps=4096):
+    """Ray-cast views of a map without a GPU: revo_map_raycast's contract in vectorised numpy.  records: canonical
+    (ascending keys); views: a list of (T_w_c, (fx, fy, cx, cy, zmin, zmax), (width, height)).  -> a dict of per-view lists
+    depth ([h, w] float32, 0 = miss), bgr ([h, w, 3] uint8), key ([h, w] uint64, all ones = miss), hits, and -- beyond what the
+    library returns -- s, cells, status ([h, w] each: the entry parameter of the last cell examined, the cells examined, the
+    index into RAY_STATUS), plus info: the call's RAY_INFO_KEYS sums.  ValueError as the library's REVO_ERR_INVALID_ARG."""
+    rec, v = _ray_args(records, voxel, min_count, max_steps)
+    views = list(views)
+    if not 1 <= len(views) <= 64:
+        raise ValueError("a ray cast takes 1 .. 64 views")
+    views = [ray_view(*vw) for vw in views]
+    out = {k: [] for k in ("depth", "bgr", "key", "hits", "s", "cells", "status")}
+    total = dict.fromkeys(RAY_INFO_KEYS, 0)
+    for vw in views:
+        w, h = vw[5]
+        keys, z, bgr = ray_view_solid(rec, vw)
+        hit, s, cells, status = _ray_march(*ray_view_rays(vw), v, keys, max_steps)
+        got = hit >= 0
+        j = np.maximum(hit, 0)
+        if len(keys) == 0:  # nothing is solid to this view: j has nothing to index
+            keys, z, bgr = np.full(1, RAY_EMPTY, np.uint64), np.zeros(1, np.float32), np.zeros((1, 3), np.uint8)
+        out["depth"].append(np.where(got, z[j], np.float32(0)).astype(np.float32).reshape(h, w))
+        out["bgr"].append(np.where(got[:, None], bgr[j], np.uint8(0)).astype(np.uint8).reshape(h, w, 3))
+        out["key"].append(np.where(got, keys[j], RAY_EMPTY).astype(np.uint64).reshape(h, w))
+        out["hits"].append(int(got.sum()))
+        out["s"].append(s.reshape(h, w))
+        out["cells"].append(cells.reshape(h, w))
+        out["status"].append(status.reshape(h, w))
+        for name, x in _ray_info(status, cells).items():
+            total[name] += x
+    out["info"] = total
+    return out
+
+
+def cast_rays_records(records, voxel, rays, min_count=1, max_steps=4096):
+    """Range queries without a GPU: revo_map_cast_rays' contract in vectorised numpy.  rays: [N, 8] float32 rows of
+    o (3), s0, d (3), s1.  A ray that is not finite or has s0 >= s1 comes back `outside` with 0 cells.  -> (key uint64 [N], all
+    ones unless a hit; s float32 [N]; cells uint32 [N]; status uint8 [N], the index into RAY_STATUS; info dict of RAY_INFO_KEYS)."""
+    rec, v = _ray_args(records, voxel, min_count, max_steps)
+    r = np.ascontiguousarray(np.asarray(rays, np.float32)).reshape(-1, 8)
+    if not 1 <= len(r) <= 1 << 24:
+        raise ValueError("a call takes 1 .. 2^24 rays")
+    keys = rec["key"]
+    hit, s, cells, status = _ray_march(r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7], v, keys, max_steps)
+    key = np.where(hit >= 0, keys[np.maximum(hit, 0)] if len(keys) else RAY_EMPTY, RAY_EMPTY).astype(np.uint64)
+    return key, s, cells.astype(np.uint32), status.astype(np.uint8), _ray_info(status, cells)
+
+
 def read_pose(path):
     """A pose from a text file of 16 or 12 numbers: a row-major 4x4 or 3x4."""
     with open(path) as f:

@@ -15,6 +15,8 @@ api.VoxelMap.load continues and `python -m revo_amd.mapfile` merges; FILE with _
 --map-views DIR (with --map) renders the finished map from the estimated pose of every keyframe, or with --map-views-every K
 of every K-th tracked frame, on the GPU (api.VoxelMap.render) and writes a TUM-layout data set into DIR (tum.write_map_views:
 rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset.
+--map-views-raycast (with --map-views) writes those views with the ray march (api.VoxelMap.raycast) in place of the
+splat: no footprint parameter, no holes.  The pose file does not depend on it.
 --map-window N (with --map, sequential driver only) keeps only the last N keyframes in the map (api.MapWindow: each older
 keyframe's voxel sums are subtracted again, exactly): map_<dataset>.ply, --map-save and --map-views then describe that windowed
 map, and map_window_<dataset>.txt lists the keyframes it holds, oldest first: time stamp and the 16 entries of T_w_kf (row-major,
@@ -40,7 +42,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-views DIR [--map-views-every K]] [--map-carve [--map-carve-margin M] [--map-carve-views K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -92,6 +94,9 @@ def main(argv=None):
         if views_every < 1:
             print("--map-views-every needs a positive number of frames")
             return 2
+    views_raycast = "--map-views-raycast" in argv  # the views by api.VoxelMap.raycast in place of render
+    if views_raycast:
+        argv = [a for a in argv if a != "--map-views-raycast"]
     if "--map-views" in argv:
         i = argv.index("--map-views")
         views_dir = argv[i + 1]
@@ -101,6 +106,9 @@ def main(argv=None):
         return 2
     if views_every and views_dir is None:
         print("--map-views-every needs --map-views DIR")
+        return 2
+    if views_raycast and views_dir is None:
+        print("--map-views-raycast needs --map-views DIR")
         return 2
     map_carve = None  # vo.REVO's carve: free-space carving with every new keyframe
     for opt, key, conv in (("--map-carve-margin", "margin", float), ("--map-carve-views", "min_views", int)):
@@ -165,7 +173,7 @@ def main(argv=None):
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
         return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel,
-                            views_dir, views_every, map_save, covariances)
+                            views_dir, views_every, map_save, covariances, views_raycast)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
@@ -211,7 +219,7 @@ def main(argv=None):
                 print("Map window: the last %d of %d keyframes -> map_window_%s.txt" % (len(vmap.keyframes), drv.nKeyFrames, name))
             if views_dir is not None:
                 _save_views(vmap, os.path.join(views_dir, name) if len(io["datasets"]) > 1 else views_dir,
-                            drv.poses, [kf for _, kf in res], views_every, io["depth_scale_factor"])
+                            drv.poses, [kf for _, kf in res], views_every, io["depth_scale_factor"], views_raycast)
         if drawer is not None:
             out = drawer.saveModel(os.path.join(model_dir, name) if len(io["datasets"]) > 1 else model_dir)
             print("model: %d points of %d keyframes -> %s, %s" % (drawer.nPts, len(drawer.vpKfsF), out[0], out[1]))
@@ -260,12 +268,12 @@ def _save_map(vmap, name, rvm=None):
              (", %d keyframes refused (max_voxels)" % info["keyframes_rejected"]) if info["keyframes_rejected"] else "", path))
 
 
-def _save_views(vmap, folder, poses, is_kf, every, depth_scale):
+def _save_views(vmap, folder, poses, is_kf, every, depth_scale, raycast=False):
     """--map-views: the finished map from the pose of every keyframe (every == 0) or of every `every`-th tracked frame."""
     from . import tum
     sel = poses[::every] if every else [p for p, kf in zip(poses, is_kf) if kf]
-    n = tum.write_map_views(folder, vmap, sel, depth_scale=depth_scale)
-    print("Map views: %d views (%s) -> %s" % (n, ("every %d frames" % every) if every else "one per keyframe", folder))
+    n = tum.write_map_views(folder, vmap, sel, depth_scale=depth_scale, raycast=raycast)
+    print("Map views: %d views (%s%s) -> %s" % (n, ("every %d frames" % every) if every else "one per keyframe", ", ray-cast" if raycast else "", folder))
 
 
 def _report_ate(folder, poses):
@@ -285,7 +293,7 @@ def _report_ate(folder, poses):
 
 
 def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
-                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False):
+                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False, views_raycast=False):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -338,7 +346,7 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
             _save_map(r.map, name, _rvm_path(map_save, name, True))
             if views_dir is not None:
                 _save_views(r.map, os.path.join(views_dir, name), r.poses, [kf for _, kf in r], views_every,
-                            io["depth_scale_factor"])
+                            io["depth_scale_factor"], views_raycast)
         _report_ate(folder, r.poses)
     print("%d datasets on %d streams: %.1f frames/s (incl. PNG decode, %s)"
           % (len(folders), streams, total / dt,

@@ -261,6 +261,29 @@ class MapCarveViewInfo(C.Structure):
 assert (C.sizeof(MapCarveView), C.sizeof(MapCarveParams), C.sizeof(MapCarveInfo), C.sizeof(MapCarveViewInfo)) == (112, 24, 64, 32)
 
 
+class MapRayParams(C.Structure):
+    """revo_map_ray_params (include/revo_hip.h), 16 bytes: the cells a ray examines at most (1 .. 2^20)."""
+    _fields_ = [("max_steps", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class MapRay(C.Structure):
+    """revo_map_ray (include/revo_hip.h), 32 bytes: the points o + s d for s0 <= s < s1."""
+    _fields_ = [("o", C.c_float * 3), ("s0", C.c_float), ("d", C.c_float * 3), ("s1", C.c_float)]
+
+
+class MapRayHit(C.Structure):
+    """revo_map_ray_hit (include/revo_hip.h), 16 bytes: cells holds the cells examined (bits 0-23) and the status (bits 30-31)."""
+    _fields_ = [("key", C.c_uint64), ("s", C.c_float), ("cells", C.c_uint32)]
+
+
+class MapRayInfo(C.Structure):
+    """revo_map_ray_info (include/revo_hip.h), 64 bytes: integer sums over the rays of a call."""
+    _fields_ = [(k, C.c_uint64) for k in ("rays", "hits", "range", "outside", "exhausted", "cells")] + [("reserved", C.c_uint64 * 2)]
+
+
+assert (C.sizeof(MapRayParams), C.sizeof(MapRay), C.sizeof(MapRayHit), C.sizeof(MapRayInfo)) == (16, 32, 16, 64)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

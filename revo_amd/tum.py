@@ -430,9 +430,9 @@ def read_poses(path):
     return out
 
 
-def write_map_views(folder, vmap, poses, depth_scale=5000.0, batch=16, splat_max=4, min_count=1):
-    """Renders the voxel map `vmap` (api.VoxelMap.render, `batch` views per library call) from `poses` [(timestamp, 4x4
-    camera -> world)] and writes a TUM-layout data set: rgb/<ts>.png (8-bit colour), depth/<ts>.png (16-bit: metres x
+def write_map_views(folder, vmap, poses, depth_scale=5000.0, batch=16, splat_max=4, min_count=1, raycast=False):
+    """Renders the voxel map `vmap` (api.VoxelMap.render, or with raycast=True api.VoxelMap.raycast: the ray march in place of
+    the splat, no footprint and no holes; `batch` views per library call) from `poses` [(timestamp, 4x4 camera -> world)] and writes a TUM-layout data set: rgb/<ts>.png (8-bit colour), depth/<ts>.png (16-bit: metres x
     depth_scale, rounded to nearest, saturated at 65535, 0 = nothing there), associate.txt, and poses.txt in the pose
     file's format (vo.tum_lines).  The views are rendered from the poses as poses.txt states them (read_poses), so the
     folder describes itself: read_associate / load_frame / read_poses give back what was rendered.  -> number of views."""
@@ -448,7 +448,10 @@ def write_map_views(folder, vmap, poses, depth_scale=5000.0, batch=16, splat_max
         fa.write("# rgb depth (views of the voxel map at the poses of poses.txt)\n")
         for i in range(0, len(poses), batch):
             part = poses[i:i + batch]
-            depth, bgr, _ = vmap.render([T for _, T in part], splat_max=splat_max, min_count=min_count)
+            if raycast:
+                depth, bgr, _ = vmap.raycast([T for _, T in part], min_count=min_count)
+            else:
+                depth, bgr, _ = vmap.render([T for _, T in part], splat_max=splat_max, min_count=min_count)
             for (ts, _), d, c in zip(part, depth, bgr):
                 name = "%.6f.png" % ts
                 Image.fromarray(np.ascontiguousarray(c[..., ::-1])).save(os.path.join(folder, "rgb", name))
