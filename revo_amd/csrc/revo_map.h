@@ -1,4 +1,4 @@
-// revo_map.h -- what the voxel map (revo_map.hip) needs from the rest of the library.  Internal: not part of the C ABI.
+// revo_map.h -- what the voxel map (revo_map*.hip) needs from the rest of the library.  Internal: not part of the C ABI.
 #pragma once
 #include "revo_internal.h"
 

@@ -1,0 +1,339 @@
+// revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
+// revo_map_edit.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
+// units include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "revo_internal.h"
+#include "revo_map.h"
+#include "revo_pose_host.h"
+
+#define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
+#define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
+#define MAP_MAX_CAP (1ull << 31)
+#define MAP_MAX_VOXELS (1ull << 28)
+#define MAP_POISON (1ull << 40)  // > MAP_MAX_VOXELS: a batch whose new-voxel count holds it is refused by k_map_commit
+
+typedef unsigned long long u64;
+
+struct MapVal { u64 n, qx, qy, qz, sb, sg, sr, pad; };  // count, sum q (two's complement int64), sum B, G, R
+struct MapStats {
+  u64 occ, pts, drop, kfs, rejected, fault;
+  u64 ok, bad;  // bad: k_map_merge met a record with count 0 or key bit 63 (the host clears it before such a launch)
+  u64 shard[MAP_SHARDS][16];  // [0] new voxels, [1] points, [2] dropped points of the batch in flight
+  // the subtraction in flight (behind the shards: no older field moves): refused, points taken, voxels whose count reached 0
+  u64 sub_bad, sub_pts, sub_freed;
+};
+enum { MAP_FUSED = 0, MAP_INSERT = 1, MAP_ACCUM = 2 };
+struct MapMergeK {
+  const u64* skeys; const MapVal* svals;  // MERGE_TABLE: the source map's table, n slots
+  const ulonglong2* recs;                 // MERGE_RAW: n records
+  unsigned n;
+  u64* keys; MapVal* vals; unsigned mask;
+  MapStats* st;
+  u64 dropped;  // joins the batch's dropped points once
+  int shift;    // MERGE_COARSE: every axis index of a source key is shifted right by this (revo_map_coarsen)
+};
+enum { MERGE_RAW = 0, MERGE_TABLE = 1, MERGE_COARSE = 2 };  // MERGE_COARSE: MERGE_TABLE with the keys rewritten
+static_assert(sizeof(revo_map_voxel_raw) == 64 && sizeof(MapVal) == 64, "a voxel record is four 16-byte words");
+
+// ------------------------------------------------------------------------------------------------- device vocabulary --
+__device__ __forceinline__ bool map_depth_ok(float Z, float dmin, float dmax) {
+  return isfinite(Z) && Z > dmin && Z < dmax;  // depth_ok of revo_pyramid.hip (imgpyramidrgbd.cpp:208)
+}
+__device__ __forceinline__ u64 map_hash(u64 k) {  // splitmix64 finaliser
+  k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+  k ^= k >> 27; k *= 0x94d049bb133111ebull;
+  return k ^ (k >> 31);
+}
+// The slot of `key`, inserted if absent (INSERT) or looked up.  Probing is bounded by the table size (the host keeps the
+// load <= 0.5, so a full table means a broken invariant: counted in fault, never a hang).
+template <bool INSERT>
+__device__ __forceinline__ unsigned map_slot(u64* keys, unsigned mask, u64 key, unsigned* n_new, u64* fault) {
+  unsigned s = (unsigned)map_hash(key) & mask;
+  for (unsigned i = 0; i <= mask; ++i) {
+    u64 k = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == key) return s;
+    if (k == MAP_EMPTY) {
+      if (!INSERT) break;
+      k = atomicCAS(&keys[s], MAP_EMPTY, key);
+      if (k == MAP_EMPTY) { if (n_new) atomicAdd(n_new, 1u); return s; }
+      if (k == key) return s;
+    }
+    s = (s + 1) & mask;
+  }
+  atomicOr(fault, 1ull);
+  return ~0u;
+}
+// The slot of `key`, or ~0u: a lookup that touches nothing (a miss is the caller's business, not a broken table).  For tables
+// whose keys do not change while the kernel runs, so plain loads do.
+__device__ __forceinline__ unsigned map_find(const u64* __restrict__ keys, unsigned mask, u64 key) {
+  unsigned s = (unsigned)map_hash(key) & mask;
+  for (unsigned i = 0; i <= mask; ++i) {
+    const u64 k = keys[s];
+    if (k == key) return s;
+    if (k == MAP_EMPTY) break;
+    s = (s + 1) & mask;
+  }
+  return ~0u;
+}
+
+// The packed key of the voxel index (kx, ky, kz), each in [-2^20, 2^20 - 1]: 21 bits per axis, biased by 2^20.
+__device__ __forceinline__ u64 map_key(int kx, int ky, int kz) {
+  return ((u64)(kx + (1 << 20)) << 42) | ((u64)(ky + (1 << 20)) << 21) | (u64)(kz + (1 << 20));
+}
+__device__ __forceinline__ void map_key_axes(u64 key, int& kx, int& ky, int& kz) {
+  kx = (int)((key >> 42) & 0x1fffffu) - (1 << 20); ky = (int)((key >> 21) & 0x1fffffu) - (1 << 20); kz = (int)(key & 0x1fffffu) - (1 << 20);
+}
+// whether (kx, ky, kz) is a voxel index at all: the neighbours of a voxel at the rim are not
+__device__ __forceinline__ bool map_key_in_range(int kx, int ky, int kz) {
+  return !(((kx + (1 << 20)) | (ky + (1 << 20)) | (kz + (1 << 20))) >> 21);
+}
+// The key of the voxel of edge 2^shift times as long that holds this one: floor(k / 2^shift) per axis.
+__device__ __forceinline__ u64 map_coarse_key(u64 key, int shift) {
+  int kx, ky, kz;
+  map_key_axes(key, kx, ky, kz);
+  return map_key(kx >> shift, ky >> shift, kz >> shift);
+}
+
+// A raw record (revo_map_voxel_raw): key, count, sum q x y z, sum B G R -- eight 64-bit words, moved as four 16-byte words.
+struct MapRec {
+  ulonglong2 a, b, c, d;  // key n | qx qy | qz sb | sg sr
+  __device__ __forceinline__ u64 key() const { return a.x; }
+  __device__ __forceinline__ u64 n() const { return a.y; }
+};
+__device__ __forceinline__ MapRec map_rec_from_slot(const MapVal* val, u64 key) {
+  const ulonglong2* v = (const ulonglong2*)val;
+  const ulonglong2 p = v[0], q = v[1], c = v[2], d = v[3];  // n qx | qy qz | sb sg | sr -
+  return MapRec{make_ulonglong2(key, p.x), make_ulonglong2(p.y, q.x), make_ulonglong2(q.y, c.x), make_ulonglong2(c.y, d.x)};
+}
+__device__ __forceinline__ MapRec map_rec_from_raw(const ulonglong2* recs, size_t i) {
+  const ulonglong2* v = recs + 4 * i;
+  return MapRec{v[0], v[1], v[2], v[3]};
+}
+__device__ __forceinline__ void map_rec_store(ulonglong2* out, size_t j, const MapRec& r) {
+  ulonglong2* o = out + 4 * j;
+  o[0] = r.a; o[1] = r.b; o[2] = r.c; o[3] = r.d;
+}
+// a raw record nobody has validated: count 0 or key bit 63 must never reach the table
+__device__ __forceinline__ bool map_rec_bad(const MapRec& r) { return (r.a.x >> 63) != 0 || r.a.y == 0; }
+// The record's seven sums into (out of) a slot: integer atomics, so no order of records can change the result.
+__device__ __forceinline__ void map_rec_add(MapVal* v, const MapRec& r) {
+  atomicAdd(&v->n, r.a.y);
+  atomicAdd(&v->qx, r.b.x); atomicAdd(&v->qy, r.b.y); atomicAdd(&v->qz, r.c.x);
+  atomicAdd(&v->sb, r.c.y); atomicAdd(&v->sg, r.d.x); atomicAdd(&v->sr, r.d.y);
+}
+__device__ __forceinline__ u64 map_rec_sub(MapVal* v, const MapRec& r) {  // returns the count the slot held before
+  const u64 old = atomicAdd(&v->n, 0ull - r.a.y);
+  atomicAdd(&v->qx, 0ull - r.b.x); atomicAdd(&v->qy, 0ull - r.b.y); atomicAdd(&v->qz, 0ull - r.c.x);
+  atomicAdd(&v->sb, 0ull - r.c.y); atomicAdd(&v->sg, 0ull - r.d.x); atomicAdd(&v->sr, 0ull - r.d.y);
+  return old;
+}
+
+// A voxel's point is the mean of its fixed-point sums, one axis at a time (n: the count as a double); its colour the rounded
+// mean of each channel.  Two packings are in use and stay apart: the extracted cloud's R | G << 8 | B << 16, and the views'
+// B | G << 8 | R << 16 (the low word of a z-buffer entry, the ray output).
+__device__ __forceinline__ float map_mean(u64 q, double n) { return (float)((double)(long long)q / n * 0x1p-20); }
+__device__ __forceinline__ u64 map_channel(u64 s, u64 n) { return (s + n / 2) / n; }
+__device__ __forceinline__ unsigned map_colour_rgb(u64 n, u64 sb, u64 sg, u64 sr) {
+  return (unsigned)map_channel(sr, n) | ((unsigned)map_channel(sg, n) << 8) | ((unsigned)map_channel(sb, n) << 16);
+}
+__device__ __forceinline__ u64 map_colour_bgr(u64 n, u64 sb, u64 sg, u64 sr) {
+  return map_channel(sb, n) | (map_channel(sg, n) << 8) | (map_channel(sr, n) << 16);
+}
+
+// Block compaction in arrival order.  s_n (LDS) is zero behind the kernel's first barrier; every selected thread draws its
+// place in the block; behind a barrier thread 0 draws the block's base from `counter` (an unsigned total, or the u64 word of
+// an info line) with one global atomic; behind another barrier s_base + place is the thread's output index.  The pair leaves
+// the barriers to the kernel (k_map_pose and k_map_carve flush their other counters between the same two); map_compact is
+// the whole of it for a kernel with nothing else to flush.
+__device__ __forceinline__ unsigned map_compact_begin(bool sel, unsigned& s_n) { return sel ? atomicAdd(&s_n, 1u) : 0u; }
+template <typename C>
+__device__ __forceinline__ void map_compact_end(unsigned& s_n, unsigned& s_base, C* counter) {
+  if (threadIdx.x == 0) s_base = s_n ? (unsigned)atomicAdd(counter, (C)s_n) : 0u;
+}
+template <typename C>
+__device__ __forceinline__ unsigned map_compact(bool sel, unsigned& s_n, unsigned& s_base, C* counter) {
+  const unsigned o = map_compact_begin(sel, s_n);
+  __syncthreads();
+  map_compact_end(s_n, s_base, counter);
+  __syncthreads();
+  return s_base + o;
+}
+
+// ------------------------------------------------------------------------------------------------------- host pieces --
+#define MAP_TRY(expr) do { const int rc__ = (expr); if (rc__) return rc__; } while (0)
+
+// the argument rules every entry point states the same way
+inline int map_check_side(int flag, const char* name) {
+  return flag != 0 && flag != 1 ? fail(REVO_ERR_INVALID_ARG, std::string(name) + " must be 0 or 1") : REVO_OK;
+}
+inline int map_check_aligned(uintptr_t bits, int align, const std::string& what) {  // what: "the device output is", ...
+  return bits & (uintptr_t)(align - 1) ? fail(REVO_ERR_INVALID_ARG, what + " not " + std::to_string(align) + "-byte aligned") : REVO_OK;
+}
+
+struct MapOwner {  // what the types below are: owners of device resources, released by their destructors, never copied
+  MapOwner() = default;
+  MapOwner(const MapOwner&) = delete;
+  MapOwner& operator=(const MapOwner&) = delete;
+};
+
+// Device memory of one call: freed when the call returns, whichever way, and a failed call leaves no sticky error behind.
+struct MapScratch : MapOwner {
+  char* p = nullptr;
+  ~MapScratch() { (void)hipFree(p); (void)hipGetLastError(); }
+  int alloc(size_t bytes) { HIPCHECK(hipMalloc((void**)&p, bytes)); return REVO_OK; }
+};
+
+// A device buffer of the handle that only grows.  The stream is waited for first: its work may still use the old one.
+struct MapBuf : MapOwner {
+  char* p = nullptr; size_t bytes = 0;
+  ~MapBuf() { (void)hipFree(p); }
+  int reserve(size_t need, hipStream_t s) {
+    if (need <= bytes) return REVO_OK;
+    HIPCHECK(hipStreamSynchronize(s));
+    (void)hipFree(p);
+    p = nullptr; bytes = 0;
+    HIPCHECK(hipMalloc((void**)&p, need));
+    bytes = need;
+    return REVO_OK;
+  }
+};
+
+// Descriptor rows of a launch: written into pinned memory, uploaded, read by the kernels from device memory.  The event
+// (recorded behind the upload) is waited for before the pinned rows are rewritten, the stream before device rows that a
+// kernel may still read are reallocated (none exist yet when the rows are first reserved: no wait then).  The event is made
+// on first use, or ahead of it by create(), where its cost must not fall into the first launch.
+template <typename Row>
+struct MapRows : MapOwner {
+  Row* h = nullptr; Row* d = nullptr; int cap = 0;
+  hipEvent_t ev = nullptr; bool recorded = false;
+  ~MapRows() {
+    if (recorded) (void)hipEventSynchronize(ev);
+    (void)hipHostFree(h); (void)hipFree(d);
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  int create() { if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); return REVO_OK; }
+  int reserve(int n, hipStream_t s) {
+    if (recorded) HIPCHECK(hipEventSynchronize(ev));  // the previous upload has read the pinned rows
+    if (n <= cap) return REVO_OK;
+    if (cap) HIPCHECK(hipStreamSynchronize(s));  // the previous call's kernels read the device rows
+    (void)hipHostFree(h); (void)hipFree(d);
+    h = nullptr; d = nullptr; cap = 0;
+    HIPCHECK(hipHostMalloc((void**)&h, sizeof(Row) * n));
+    HIPCHECK(hipMalloc((void**)&d, sizeof(Row) * n));
+    cap = n;
+    return REVO_OK;
+  }
+  int upload(int n, hipStream_t s, bool mark = true) {  // mark: record the event behind it
+    HIPCHECK(hipMemcpyAsync(d, h, sizeof(Row) * n, hipMemcpyHostToDevice, s));
+    if (!mark) return REVO_OK;
+    MAP_TRY(create());
+    HIPCHECK(hipEventRecord(ev, s));
+    recorded = true;
+    return REVO_OK;
+  }
+};
+
+// The two events around a feature's device work and what *_last_ms makes of them.
+struct MapTimer : MapOwner {
+  hipEvent_t e0 = nullptr, e1 = nullptr; bool ready = false;
+  ~MapTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  int begin(hipStream_t s) {
+    if (!e0) HIPCHECK(hipEventCreate(&e0));
+    if (!e1) HIPCHECK(hipEventCreate(&e1));
+    HIPCHECK(hipEventRecord(e0, s));
+    return REVO_OK;
+  }
+  int end(hipStream_t s) {
+    HIPCHECK(hipEventRecord(e1, s));
+    ready = true;
+    return REVO_OK;
+  }
+  int last_ms(float* ms) {
+    HIPCHECK(hipEventSynchronize(e1));
+    HIPCHECK(hipEventElapsedTime(ms, e0, e1));
+    return REVO_OK;
+  }
+};
+
+struct MapDesc {  // one keyframe of a launch
+  const float* depth; const uint8_t* edges; const uint8_t* bgr;
+  float R[9], t[3];  // T_w_kf, R row-major
+  float voxel; int dense;
+  u64* keys; MapVal* vals; unsigned mask;
+  MapStats* st;
+};
+struct MapCommit {  // one map of a launch
+  MapStats* st; u64* pub; u64 max_voxels, seq; int n_kf, check;
+};
+// The descriptors of an integration or merge launch (a merge has no keyframe rows: nd = 0).  One event guards both sets of
+// rows, `com`'s, recorded behind both uploads: a second hipEventRecord per integration would be stream work the launch never
+// had.  Callers go through reserve() and upload(), which keep that order; h and d of the two members are theirs to fill.
+struct revo_map_stage {
+  MapRows<MapDesc> desc;
+  MapRows<MapCommit> com;
+  int reserve(int nd, int nc, hipStream_t s) { MAP_TRY(com.reserve(nc, s)); return desc.reserve(nd, s); }  // com: waits for the event
+  int upload(int nd, int nc, hipStream_t s) { if (nd) MAP_TRY(desc.upload(nd, s, false)); return com.upload(nc, s); }
+};
+struct MapViewK;    // revo_map_view.hip: one view of a render launch
+struct MapRayView;  // revo_map_view.hip: one view of a raycast launch
+
+struct revo_map {
+  revo_ctx* ctx = nullptr;
+  MapCtxGeom g{};
+  float voxel = 0.f;
+  int dense = 0;
+  size_t max_voxels = 0;
+  u64* d_keys = nullptr; MapVal* d_vals = nullptr; size_t cap = 0;
+  MapStats* d_st = nullptr;
+  u64* h_pub = nullptr;  // pinned [4]: voxels, sequence of the batch that published them, that batch accepted
+  u64 seq = 0;
+  std::deque<std::pair<u64, size_t>> pending;  // (sequence, points bound) of batches the host has not seen published
+  int rehashes = 0;
+  revo_map_stage* stage = nullptr;
+  std::vector<std::pair<revo_vo_multi*, int>> attached;
+  // revo_map_render: z-buffers of a call's views (every word MAP_EMPTY between calls: the resolve kernel puts it back), the
+  // device outputs of a host-output call, the views' descriptors and covered counters, the call's events
+  MapBuf zbuf; bool zbuf_clean = false;
+  MapBuf vout, cov;
+  MapRows<MapViewK> views;
+  MapTimer render_time;
+  // revo_map_raycast / revo_map_cast_rays: the block table (as many slots as the map's), the counter lines, the views'
+  // descriptors, the device outputs of a host-output call, the call's events
+  MapBuf bkeys, rcnt, rout;
+  MapRows<MapRayView> rviews;
+  MapTimer ray_time;
+};
+
+// revo_map.hip, for the other units.  map_read_stats waits for the map's stream; map_grow(live_only) is the compaction an
+// accepted subtraction ends with; map_merge_core / map_subtract_core: one merge into (subtraction from) m of the input `a` names.
+size_t map_occ_bound(revo_map* m);
+int map_grow(revo_map* m, size_t newcap, bool live_only = false);
+int map_read_stats(revo_map* m, MapStats* out);
+int map_merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool trusted, int keyframes);
+int map_subtract_core(revo_map* m, MapMergeK a, int src_kind, u64 dropped, u64 keyframes);
+
+// Room in m's table for `bound` more keys at a load <= 0.5 (the checked path inserts every new key before it decides: what
+// the map may hold + all of them); *ub: the bound of the voxels it holds now.  what: "batch", "merge".
+inline int map_need_slots(revo_map* m, size_t bound, const char* what, size_t* ub) {
+  *ub = map_occ_bound(m);
+  const size_t need = 2 * (std::min(*ub, m->max_voxels) + bound);
+  if (need > MAP_MAX_CAP) return fail(REVO_ERR_CAPACITY, std::string("voxel map: a ") + what + " this large needs more than 2^31 table slots");
+  if (m->cap >= need) return REVO_OK;
+  size_t c = std::max<size_t>(m->cap * 2, 1024);
+  while (c < need) c *= 2;
+  return map_grow(m, c);
+}

@@ -53,7 +53,7 @@ def difference(a, b):
 
 
 def splitmix64(k):
-    """map_hash of revo_map.hip."""
+    """map_hash of revo_map_impl.h."""
     k &= M64
     k ^= k >> 30
     k = (k * 0xbf58476d1ce4e5b9) & M64
