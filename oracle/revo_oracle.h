@@ -37,6 +37,10 @@ extern "C" {
 void ro_set_accum_double(int on);
 /* test hook: +-1 ulp of seeded noise on every entry of the finished normal equations (0 = off) */
 void ro_set_ab_ulp_noise(unsigned seed);
+/* LM trace (single-threaded analysis aid): ro_lm_trace(1) empties the trace and records, for every residual evaluation
+ * after a level's first, the byte lvl * 2 + accepted; ro_lm_trace_get copies at most cap bytes and returns how many there are. */
+void ro_lm_trace(int on);
+int ro_lm_trace_get(unsigned char* dst, int cap);
 
 /* ---- image primitives --------------------------------------------------- */
 void ro_bgr2gray(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* gray);
