@@ -1150,6 +1150,63 @@ int revo_map_cast_rays(revo_map* m, size_t n, const revo_map_ray* rays, int devi
  * nothing yet. */
 int revo_map_raycast_last_ms(revo_map* m, float* ms);
 
+/* The map's distance field: what a planner asks -- how far is the nearest surface from here, and in which
+ * direction.  The field is the exact squared Euclidean distance, in cells, from every cell of a box of voxel indices to the
+ * nearest solid voxel inside the box: an integer with one value, so a pure function of the map's records -- the same bytes
+ * whatever the table size, integration order or launch.
+ *
+ * The box: cell (ix, iy, iz) is the voxel index lo + (ix, iy, iz) and lives at out[(ix*n[1] + iy)*n[2] + iz] (z fastest, the
+ * key's own order).  Every lo[i] and lo[i] + n[i] - 1 lies in [-2^20, 2^20 - 1], and n[0]*n[1]*n[2] <= 2^27.
+ * The field: a voxel is solid when its count >= max(min_count, 1).  out[c] = the minimum, over the solid voxels s whose index
+ * lies inside the box, of (cx-sx)^2 + (cy-sy)^2 + (cz-sz)^2; REVO_DF_NONE when the box holds no solid voxel.  With clamp > 0
+ * every value other than REVO_DF_NONE is written as min(value, clamp).  Voxels outside the box are NOT seen: a value is exact
+ * only up to the cell's distance to the nearest face, so the caller pads the box by the distance it cares about.  The largest
+ * possible value is 3 * 1023^2 < 2^24, so (float)out[c] is exact. */
+typedef struct revo_map_df_box {
+  int32_t lo[3];            /* voxel index of the first cell, per axis x, y, z */
+  int32_t n[3];             /* cells per axis, 1 .. 1024 */
+} revo_map_df_box;
+#define REVO_DF_NONE 0xFFFFFFFFu
+typedef struct revo_map_df_info {     /* 64 bytes, little-endian, no padding: integer sums and maxima, so order-free */
+  uint64_t cells;           /* n[0]*n[1]*n[2] */
+  uint64_t solid;           /* solid voxels inside the box */
+  uint64_t outside;         /* solid voxels outside it */
+  uint64_t below;           /* voxels under max(min_count, 1) */
+  uint64_t max_d2;          /* the largest value written other than REVO_DF_NONE, after the clamp; 0 if there is none */
+  uint64_t reserved[3];     /* zero */
+} revo_map_df_info;
+typedef struct revo_map_df_sample_t { /* 16 bytes per point */
+  float dist;               /* metres to the nearest solid voxel's cell; -1: the point is outside the box; +inf: no solid voxel */
+  float grad[3];            /* central difference of the distance in cells per cell, dimensionless; one-sided at a face */
+} revo_map_df_sample_t;
+/* The field of `box` over the map as it is behind every integration enqueued so far, on the context's tracker stream: n[0]*
+ * n[1]*n[2] values into d2, the call's counters into info (may be NULL).  device_out = 0: host pointers, the call waits.
+ * device_out = 1: device pointers (d2 and info 16-byte aligned), the call only enqueues.  An empty map gives all
+ * REVO_DF_NONE.  The map is not changed.  REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m,
+ * box or d2; a size outside 1 .. 1024; more than 2^27 cells; a box that leaves the index range; device_out not 0 or 1; a
+ * misaligned device pointer. */
+int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, uint32_t min_count, uint32_t clamp, uint32_t* d2, int device_out,
+                            revo_map_df_info* info);
+/* Waits for the map and gives the smallest (lo) and largest (hi) voxel index per axis over the voxels with count >=
+ * max(min_count, 1), and how many there are (n).  With *n == 0, lo and hi are written as zeros. */
+int revo_map_bounds(revo_map* m, uint32_t min_count, int32_t lo[3], int32_t hi[3], size_t* n);
+/* n points (1 .. 2^24; xyz: 3 floats each, metres in the map's frame) against the field d2 of `box` (device_field: where d2
+ * lives; a host field is uploaded to a temporary buffer).  All arithmetic is float32 with every operation rounded on its own;
+ * sqrtf and / are correctly rounded.  Per axis f_i = floorf(p_i / voxel), voxel the map's edge.  The point is OUTSIDE unless
+ * every p_i and f_i is finite and lo_i <= f_i <= lo_i + n_i - 1: then dist = -1 and grad = 0.  Otherwise, with a the cell
+ * f - lo: d2[a] == REVO_DF_NONE gives dist = +inf and grad = 0; else dist = sqrtf((float)d2[a]) * voxel and, per axis i with
+ * a_i the cell's index along it, lo' = max(a_i - 1, 0), hi' = min(a_i + 1, n_i - 1), span = hi' - lo', grad_i = span == 0 ? 0
+ * : (sqrtf((float)d2[a with a_i = hi']) - sqrtf((float)d2[a with a_i = lo'])) / (float)span.
+ * device_in / device_out: where xyz and out live (device pointers 16-byte aligned); the call only enqueues when all three
+ * flags are 1 and waits otherwise.  A point that is not finite is no argument error: it comes back OUTSIDE.
+ * REVO_ERR_INVALID_ARG, with nothing written: a NULL pointer; n outside 1 .. 2^24; the box rules above; a flag outside 0 / 1;
+ * a misaligned device pointer. */
+int revo_map_df_sample(revo_map* m, const revo_map_df_box* box, const uint32_t* d2, int device_field, size_t n, const float* xyz,
+                       int device_in, revo_map_df_sample_t* out, int device_out);
+/* Waits for the last revo_map_distance_field of m and gives the device time from its first memset to the end of its last pass
+ * (HIP events on the tracker stream), in milliseconds.  REVO_ERR_INVALID_ARG if m has built no field yet. */
+int revo_map_distance_field_last_ms(revo_map* m, float* ms);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

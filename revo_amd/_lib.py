@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -166,6 +166,10 @@ def lib():
     L.revo_map_raycast.argtypes = [vp, C.c_int, vp, C.POINTER(MapRayParams), vpp, vpp, vpp, vp, C.c_int, vp]
     L.revo_map_cast_rays.argtypes = [vp, C.c_size_t, vp, C.c_int, C.c_uint32, C.POINTER(MapRayParams), vp, C.c_int, vp]
     L.revo_map_raycast_last_ms.argtypes = [vp, f32p]
+    L.revo_map_distance_field.argtypes = [vp, C.POINTER(MapDfBox), C.c_uint32, C.c_uint32, vp, C.c_int, vp]
+    L.revo_map_bounds.argtypes = [vp, C.c_uint32, i32p, i32p, C.POINTER(C.c_size_t)]
+    L.revo_map_df_sample.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_int]
+    L.revo_map_distance_field_last_ms.argtypes = [vp, f32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -816,6 +816,99 @@ class VoxelMap:
         return (r["key"].copy(), r["s"].copy(), r["cells"] & np.uint32(0xFFFFFF), (r["cells"] >> np.uint32(30)).astype(np.uint8),
                 dict(zip(mapfile.RAY_INFO_KEYS, (int(x) for x in info[:6]))))
 
+    # -- the distance field (revo_map_distance_field / revo_map_bounds / revo_map_df_sample)
+    def bounds(self, min_count=1):
+        """(lo [3], hi [3] int32, n): the smallest and largest voxel index per axis over the voxels with count >= min_count, and
+        how many there are (zeros when there are none).  Waits for the map."""
+        lo, hi, n = np.zeros(3, np.int32), np.zeros(3, np.int32), C.c_size_t()
+        check(_lib.lib().revo_map_bounds(self._h, int(min_count), _p(lo, i32p), _p(hi, i32p), C.byref(n)))
+        return lo, hi, int(n.value)
+
+    def _df_box(self, lo, n, pad, min_count):
+        from . import mapfile
+        if (lo is None) != (n is None):
+            raise ValueError("give both lo and n, or neither (the map's bounds grown by pad)")
+        if lo is None:
+            b = self.bounds(min_count)
+            lo, n = mapfile.padded_box(b[0], b[1], pad)
+        else:
+            lo, n = mapfile.check_box(lo, n)
+        return MapDfBox((C.c_int32 * 3)(*[int(x) for x in lo]), (C.c_int32 * 3)(*[int(x) for x in n]))
+
+    @staticmethod
+    def _df_info(i):
+        from . import mapfile
+        return {k: int(getattr(i, k)) for k in mapfile.DF_INFO_KEYS}
+
+    def distance_field(self, lo=None, n=None, pad=8, min_count=1, clamp=0):
+        """The exact squared Euclidean distance, in cells, from every cell of a box of voxel indices to the nearest voxel with
+        count >= min_count inside the box (revo_map_distance_field) -> DistanceField.  lo, n: the box's first voxel
+        index and its cells (1 .. 1024) per axis, at most 2^27 cells; by default the map's bounds grown by `pad` cells.  Voxels
+        outside the box are not seen, so pad by the distance that matters.  clamp > 0: values are min(value, clamp)."""
+        box = self._df_box(lo, n, pad, min_count)
+        d2 = np.empty(tuple(box.n), np.uint32)
+        info = MapDfInfo()
+        check(_lib.lib().revo_map_distance_field(self._h, C.byref(box), int(min_count), int(clamp), d2.ctypes.data_as(vp), 0, C.byref(info)))
+        return DistanceField(d2, np.array(list(box.lo), np.int32), self.voxel, self._df_info(info), self)
+
+    def distance_field_into(self, d_d2, lo, n, min_count=1, clamp=0, d_info=None, wait=True):
+        """distance_field() into a torch device tensor: d_d2 of shape n with 32-bit integers, d_info None or a 64-byte tensor
+        (revo_map_df_info); contiguous, 16-byte aligned, on the map's device.  Enqueued on the context's tracker stream: wait=True
+        returns when it is done, wait=False at once (sync() orders later reads)."""
+        box = self._df_box(lo, n, 0, min_count)
+        if tuple(d_d2.shape) != tuple(box.n) or d_d2.element_size() != 4 or d_d2.is_floating_point():
+            raise ValueError("d_d2 must be a 32-bit integer tensor of the box's shape")
+        for t_ in (d_d2, d_info):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("output tensors must be contiguous device tensors")
+        if d_info is not None and d_info.numel() * d_info.element_size() != 64:
+            raise ValueError("d_info needs 64 bytes")
+        import torch
+        torch.cuda.current_stream(d_d2.device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
+        check(_lib.lib().revo_map_distance_field(self._h, C.byref(box), int(min_count), int(clamp), vp(d_d2.data_ptr()), 1,
+                                                 vp(d_info.data_ptr()) if d_info is not None else None))
+        if wait:
+            self.sync()
+
+    def df_sample(self, field, points):
+        """Distance and gradient at points ([N, 3] float32 metres, the map's frame) from a DistanceField of a map with this
+        map's voxel edge (revo_map_df_sample) -> a mapfile.DF_SAMPLE_DTYPE array: dist in metres (-1: outside the box, +inf:
+        the box holds no voxel), grad dimensionless."""
+        from . import mapfile
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        out = np.zeros(len(p), mapfile.DF_SAMPLE_DTYPE)
+        if len(p) == 0:
+            return out
+        d2 = np.ascontiguousarray(field.d2, np.uint32)
+        box = self._df_box(field.lo, d2.shape, 0, 1)
+        check(_lib.lib().revo_map_df_sample(self._h, C.byref(box), d2.ctypes.data_as(vp), 0, len(p), p.ctypes.data_as(vp), 0,
+                                            out.ctypes.data_as(vp), 0))
+        return out
+
+    def sample_into(self, d_out, d_d2, lo, d_points, wait=True):
+        """df_sample() between torch device tensors: d_d2 the field (32-bit integers, its shape is the box's n), d_points
+        [N, 3] float32, d_out [N, 4] float32 (dist, grad x y z); contiguous, 16-byte aligned, on the map's device."""
+        if d_d2.dim() != 3 or d_d2.element_size() != 4 or d_d2.is_floating_point():
+            raise ValueError("d_d2 must be a 3-D tensor of 32-bit integers")
+        n = int(d_points.shape[0])
+        if tuple(d_points.shape) != (n, 3) or tuple(d_out.shape) != (n, 4) or str(d_points.dtype) != "torch.float32" or str(d_out.dtype) != "torch.float32":
+            raise ValueError("d_points must be [N, 3] and d_out [N, 4] float32")
+        for t_ in (d_out, d_d2, d_points):
+            if not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("tensors must be contiguous device tensors")
+        box = self._df_box(lo, tuple(d_d2.shape), 0, 1)
+        import torch
+        torch.cuda.current_stream(d_out.device).synchronize()  # the inputs are written, the output's earlier use is over
+        check(_lib.lib().revo_map_df_sample(self._h, C.byref(box), vp(d_d2.data_ptr()), 1, n, vp(d_points.data_ptr()), 1, vp(d_out.data_ptr()), 1))
+        if wait:
+            self.sync()
+
+    def last_distance_field_ms(self):
+        """Device time of the last distance_field / distance_field_into call (HIP events), in milliseconds; waits for it."""
+        ms = C.c_float()
+        check(_lib.lib().revo_map_distance_field_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def sync(self):
         """Waits for the map's enqueued work (integrations and render_into calls)."""
         self.info()
@@ -831,6 +924,45 @@ class VoxelMap:
         ms = C.c_float()
         check(_lib.lib().revo_map_render_last_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+class DistanceField:
+    """A voxel map's distance field over a box of voxel indices (VoxelMap.distance_field, `mapfile esdf`): lo the
+    box's first voxel index, n its cells per axis, voxel the map's edge in metres, d2 [n0, n1, n2] uint32 the squared distance
+    in cells to the nearest voxel inside the box (settings.DF_NONE everywhere when there is none), info the call's counters
+    (mapfile.DF_INFO_KEYS; None for a loaded field)."""
+
+    def __init__(self, d2, lo, voxel, info=None, map=None):
+        self.d2 = d2
+        self.lo = np.asarray(lo, np.int32).reshape(3)
+        self.n = np.asarray(d2.shape, np.int32)
+        self.voxel = float(np.float32(voxel))
+        self.info = info
+        self._map = map
+
+    def metres(self):
+        """[n0, n1, n2] float32: sqrt(d2) * voxel, +inf where there is no voxel."""
+        from . import mapfile
+        with np.errstate(all="ignore"):
+            return np.where(self.d2 == mapfile.DF_NONE, np.float32(np.inf), np.sqrt(self.d2.astype(np.float32)) * np.float32(self.voxel))
+
+    def sample(self, points):
+        """Distance (metres) and gradient at points ([N, 3] metres): on the device of the map the field came from, and through
+        mapfile.df_sample -- the same bytes -- for a loaded field or a closed map."""
+        from . import mapfile
+        if self._map is not None and getattr(self._map, "_h", None):
+            return self._map.df_sample(self, points)
+        return mapfile.df_sample(self.d2, self.lo, self.voxel, points)
+
+    def save(self, path):
+        """The .npz `python -m revo_amd.mapfile esdf` writes: d2, lo, n, voxel."""
+        from . import mapfile
+        return mapfile.write_field(path, self.d2, self.lo, self.voxel)
+
+    @classmethod
+    def load(cls, path):
+        from . import mapfile
+        return cls(*mapfile.read_field(path))
 
 
 def align_system(info):

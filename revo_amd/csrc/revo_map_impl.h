@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.
 #pragma once
@@ -316,6 +316,10 @@ struct revo_map {
   MapBuf bkeys, rcnt, rout;
   MapRows<MapRayView> rviews;
   MapTimer ray_time;
+  // revo_map_distance_field / revo_map_bounds (revo_map_field.hip): the bit volume of a call's box, the counter lines, the
+  // device field of a host-output call, the call's events
+  MapBuf dfbits, dfcnt, dfout;
+  MapTimer df_time;
 };
 
 // revo_map.hip, for the other units.  map_read_stats waits for the map's stream; map_grow(live_only) is the compaction an

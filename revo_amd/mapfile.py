@@ -23,6 +23,10 @@ Equal maps give equal files.
                                                         DESIGN 19), without a GPU: DIR is a `run_tum --map-views` folder (depth/,
                                                         associate.txt, poses.txt); R gets the removed voxels, so that
                                                         `merge X OUT R` holds A's voxels again
+    python -m revo_amd.mapfile esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2]
+                                                        map A's distance field (revo_map_distance_field), without a GPU:
+                                                        the squared distance in cells to the nearest voxel, over the map's bounds
+                                                        grown by N cells (default 8); OUT.npz holds d2, lo, n, voxel
     python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
 """
 import struct
@@ -571,6 +575,164 @@ def cast_rays_records(records, voxel, rays, min_count=1, max_steps=4096):
     return key, s, cells.astype(np.uint32), status.astype(np.uint8), _ray_info(status, cells)
 
 
+# ------------------------------------------------------------------------------------------ the distance field (DESIGN 21) --
+DF_NONE = np.uint32(0xFFFFFFFF)
+DF_MAX_N = 1024
+DF_MAX_CELLS = 1 << 27
+DF_INFO_KEYS = ("cells", "solid", "outside", "below", "max_d2")
+DF_SAMPLE_DTYPE = np.dtype([("dist", "<f4"), ("grad", "<f4", (3,))])
+_DF_INF = np.int32(1 << 30)  # above 3 * 1023^2; _DF_INF + 1023^2 fits 32 bits
+
+
+def key_axes(keys):
+    """[N, 3] int64 voxel indices (x, y, z) of packed keys."""
+    k = np.asarray(keys, np.uint64)
+    m = np.uint64(0x1FFFFF)
+    return np.stack([(k >> np.uint64(42)) & m, (k >> np.uint64(21)) & m, k & m], -1).astype(np.int64).reshape(-1, 3) - (1 << 20)
+
+
+def check_box(lo, n):
+    """(lo, n) as int64 [3] arrays; ValueError if the box breaks revo_map_df_box's limits."""
+    lo, n = np.asarray(lo, np.int64).reshape(3), np.asarray(n, np.int64).reshape(3)
+    if np.any(n < 1) or np.any(n > DF_MAX_N):
+        raise ValueError("a distance-field box has 1 .. %d cells per axis, not %s" % (DF_MAX_N, n.tolist()))
+    if np.any(lo < -(1 << 20)) or np.any(lo + n - 1 > (1 << 20) - 1):
+        raise ValueError("the distance-field box %s + %s leaves the voxel index range [-2^20, 2^20 - 1]" % (lo.tolist(), n.tolist()))
+    if int(n[0]) * int(n[1]) * int(n[2]) > DF_MAX_CELLS:
+        raise ValueError("the distance-field box %s holds more than 2^27 cells" % (n.tolist(),))
+    return lo, n
+
+
+def bounds_records(records, min_count=1):
+    """(lo [3], hi [3], n) of revo_map_bounds: the smallest and largest voxel index per axis over the records with count >=
+    max(min_count, 1), and how many there are; zeros when there are none."""
+    rec = as_records(records)
+    rec = rec[rec["count"] >= np.uint64(max(1, int(min_count)))]
+    if len(rec) == 0:
+        return np.zeros(3, np.int32), np.zeros(3, np.int32), 0
+    k = key_axes(rec["key"])
+    return k.min(0).astype(np.int32), k.max(0).astype(np.int32), len(rec)
+
+
+def padded_box(lo, hi, pad):
+    """The box (lo, n) of the index bounds lo .. hi grown by `pad` cells on every side, clipped to the index range."""
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError("pad must be >= 0 cells")
+    a = np.maximum(np.asarray(lo, np.int64) - pad, -(1 << 20))
+    b = np.minimum(np.asarray(hi, np.int64) + pad, (1 << 20) - 1)
+    return check_box(a, b - a + 1)
+
+
+def _min_plus(g, axis, chunk=1 << 17):
+    """d(i) = min_j (i - j)^2 + g(j) along one axis of an int32 array (_DF_INF: no entry; _DF_INF + 1023^2 fits).  Only lines
+    with an entry are worked on, `chunk` cells at a time, and the offsets k = |i - j| end once k^2 reaches the largest value
+    left in the chunk: nothing can improve any more."""
+    g = np.moveaxis(g, axis, 0)
+    shape = g.shape
+    L = shape[0]
+    res = g.reshape(L, -1).copy()
+    lines = np.flatnonzero((res < _DF_INF).any(0))
+    step = max(1, chunk // L)
+    for c in range(0, len(lines), step):
+        sel = lines[c:c + step]
+        src = np.ascontiguousarray(res[:, sel])
+        out, tmp = src.copy(), np.empty_like(src)
+        k = 1
+        while k < L and k * k < int(out.max()):
+            kk = np.int32(k * k)
+            np.add(src[:L - k], kk, out=tmp[k:])
+            np.minimum(out[k:], tmp[k:], out=out[k:])
+            np.add(src[k:], kk, out=tmp[:L - k])
+            np.minimum(out[:L - k], tmp[:L - k], out=out[:L - k])
+            k += 1
+        res[:, sel] = out
+    return np.moveaxis(res.reshape(shape), 0, axis)
+
+
+def distance_field_records(records, lo, n, min_count=1, clamp=0):
+    """revo_map_distance_field restated: (d2 uint32 [n0, n1, n2], info dict of DF_INFO_KEYS).  d2[c] is the smallest squared
+    distance, in cells, from cell lo + c to a voxel with count >= max(min_count, 1) inside the box (voxels outside it are not
+    seen), DF_NONE when the box holds none; with clamp > 0 every other value is min(value, clamp).  Written as the three
+    min-plus passes z, y, x over exact integers."""
+    lo, n = check_box(lo, n)
+    rec = as_records(records)
+    solid = rec["count"] >= np.uint64(max(1, int(min_count)))
+    k = key_axes(rec["key"][solid]) - lo
+    inside = np.all((k >= 0) & (k < n), axis=1)
+    k = k[inside]
+    g = np.full(tuple(int(x) for x in n), _DF_INF, np.int32)
+    g[k[:, 0], k[:, 1], k[:, 2]] = 0
+    for axis in (2, 1, 0):
+        g = _min_plus(g, axis)
+    none = g >= _DF_INF
+    g = g.astype(np.uint32)
+    if int(clamp) > 0:
+        g = np.minimum(g, np.uint32(min(int(clamp), 0xFFFFFFFF)))
+    d2 = np.where(none, DF_NONE, g)
+    info = {"cells": int(d2.size), "solid": int(inside.sum()), "outside": int(solid.sum() - inside.sum()), "below": int((~solid).sum()),
+            "max_d2": int(g[~none].max()) if (~none).any() else 0}
+    return d2, info
+
+
+def df_sample(d2, lo, voxel, points):
+    """revo_map_df_sample restated: a DF_SAMPLE_DTYPE array, one entry per point ([N, 3] float32 metres).  All arithmetic is
+    float32, every operation rounded on its own.  dist -1: outside the box (or not finite); +inf: the cell holds DF_NONE."""
+    F = np.float32
+    d2 = np.asarray(d2, np.uint32)
+    n = np.asarray(d2.shape, np.int64)
+    lo = np.asarray(lo, np.int64).reshape(3)
+    p = np.asarray(points, F).reshape(-1, 3)
+    out = np.zeros(len(p), DF_SAMPLE_DTYPE)
+    with np.errstate(all="ignore"):
+        f = np.floor(p / F(voxel))
+        inside = np.all(np.isfinite(p) & np.isfinite(f) & (f >= lo.astype(F)) & (f <= (lo + n - 1).astype(F)), axis=1)
+        a = np.where(inside[:, None], f, lo.astype(F)).astype(np.int64) - lo
+        v = d2[a[:, 0], a[:, 1], a[:, 2]]
+        none = v == DF_NONE
+        root = np.sqrt(d2.astype(F))
+        dist = root[a[:, 0], a[:, 1], a[:, 2]] * F(voxel)
+        out["dist"] = np.where(inside, np.where(none, F(np.inf), dist), F(-1))
+        for i in range(3):
+            lo_, hi_ = a.copy(), a.copy()
+            lo_[:, i] = np.maximum(a[:, i] - 1, 0)
+            hi_[:, i] = np.minimum(a[:, i] + 1, n[i] - 1)
+            span = hi_[:, i] - lo_[:, i]
+            diff = root[hi_[:, 0], hi_[:, 1], hi_[:, 2]] - root[lo_[:, 0], lo_[:, 1], lo_[:, 2]]
+            grad = np.where(span == 0, F(0), diff / np.maximum(span, 1).astype(F))
+            out["grad"][:, i] = np.where(inside & ~none, grad, F(0))
+    return out
+
+
+def write_field(path, d2, lo, voxel):
+    """The .npz of a distance field: d2 (uint32 [n0, n1, n2]), lo, n (int32 [3]), voxel (float32)."""
+    d2 = np.ascontiguousarray(d2, np.uint32)
+    with open(path, "wb") as f:
+        np.savez(f, d2=d2, lo=np.asarray(lo, np.int32).reshape(3), n=np.asarray(d2.shape, np.int32), voxel=np.float32(voxel))
+    return path
+
+
+def read_field(path):
+    """(d2, lo, voxel) of a file write_field wrote; ValueError if its arrays do not fit together."""
+    with np.load(path) as z:
+        if not all(k in z.files for k in ("d2", "lo", "n", "voxel")):
+            raise ValueError("%s is not a distance-field file (d2, lo, n, voxel)" % path)
+        d2, lo, n, voxel = z["d2"], z["lo"], z["n"], z["voxel"]
+    if d2.dtype != np.uint32 or d2.ndim != 3 or lo.shape != (3,) or list(d2.shape) != [int(x) for x in n]:
+        raise ValueError("%s: a distance field is a 3-D uint32 array of the shape its n states" % path)
+    check_box(lo, n)
+    return d2, lo.astype(np.int32), float(np.float32(voxel))
+
+
+def esdf_file(path, pad=8, min_count=1, clamp=0):
+    """(d2, lo, voxel, info) of the file's map over its bounds grown by `pad` cells."""
+    header, rec = read(path)
+    lo, hi, _ = bounds_records(rec, min_count)
+    lo, n = padded_box(lo, hi, pad)
+    d2, info = distance_field_records(rec, lo, n, min_count, clamp)
+    return d2, lo.astype(np.int32), header["voxel"], info
+
+
 def read_pose(path):
     """A pose from a text file of 16 or 12 numbers: a row-major 4x4 or 3x4."""
     with open(path) as f:
@@ -706,6 +868,22 @@ def main(argv=None):
                 print("%s: %d voxels (%s carved with the views of %s: %d voxels, %d points removed)"
                       % (val["-o"][0], len(rec), pos[0], val["--views"][0], len(gone), int(gone["count"].sum(dtype=np.uint64))))
                 return 0
+        if cmd == "esdf" and "-o" in args:
+            opt = {"-o": None, "--pad": "8", "--min-count": "1", "--clamp": "0"}
+            pos, i = [], 0
+            while i < len(args):
+                if args[i] in opt and i + 1 < len(args):
+                    opt[args[i]] = args[i + 1]
+                    i += 2
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1 and opt["-o"] is not None:
+                d2, lo, voxel, info = esdf_file(pos[0], int(opt["--pad"]), int(opt["--min-count"]), int(opt["--clamp"]))
+                write_field(opt["-o"], d2, lo, voxel)
+                print("%s: %d x %d x %d cells from %s (%s), %d voxels in the box, largest d2 %d"
+                      % ((opt["-o"],) + d2.shape + (lo.tolist(), pos[0], info["solid"], info["max_d2"])))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -718,7 +896,8 @@ def main(argv=None):
         return 1
     print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | coarsen A SHIFT -o OUT | "
           "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | carve A --views DIR -o OUT [--removed R] [--radius N] [--margin M] "
-          "[--margin-rel F] [--min-views K] [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | ply FILE [OUT.ply]")
+          "[--margin-rel F] [--min-views K] [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
+          "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] | ply FILE [OUT.ply]")
     return 2
 
 

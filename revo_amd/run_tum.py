@@ -17,6 +17,9 @@ of every K-th tracked frame, on the GPU (api.VoxelMap.render) and writes a TUM-l
 rgb/, depth/, associate.txt, poses.txt); DIR/<dataset>/ with --streams or more than one dataset.
 --map-views-raycast (with --map-views) writes those views with the ray march (api.VoxelMap.raycast) in place of the
 splat: no footprint parameter, no holes.  The pose file does not depend on it.
+--map-esdf FILE (with --map) writes the finished map's distance field (api.VoxelMap.distance_field) over the map's
+bounds grown by --map-esdf-pad N cells (default 8) as a .npz (d2, lo, n, voxel): the file `python -m revo_amd.mapfile esdf`
+writes from --map-save's .rvm; FILE with _<dataset> in front of its extension with --streams or more than one dataset.
 --map-window N (with --map, sequential driver only) keeps only the last N keyframes in the map (api.MapWindow: each older
 keyframe's voxel sums are subtracted again, exactly): map_<dataset>.ply, --map-save and --map-views then describe that windowed
 map, and map_window_<dataset>.txt lists the keyframes it holds, oldest first: time stamp and the 16 entries of T_w_kf (row-major,
@@ -42,7 +45,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -71,6 +74,25 @@ def main(argv=None):
         if map_voxel is None:
             print("--map-save writes the voxel map: it needs --map VOXEL")
             return 2
+    map_esdf, esdf_pad = None, None  # the finished map's distance field as a .npz (api.DistanceField.save)
+    if "--map-esdf-pad" in argv:
+        i = argv.index("--map-esdf-pad")
+        esdf_pad = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+        if esdf_pad < 0:
+            print("--map-esdf-pad needs a number of cells >= 0")
+            return 2
+    if "--map-esdf" in argv:
+        i = argv.index("--map-esdf")
+        map_esdf = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+        if map_voxel is None:
+            print("--map-esdf writes the voxel map's distance field: it needs --map VOXEL")
+            return 2
+    elif esdf_pad is not None:
+        print("--map-esdf-pad needs --map-esdf FILE")
+        return 2
+    esdf = None if map_esdf is None else (map_esdf, 8 if esdf_pad is None else esdf_pad)
     map_window = 0  # api.MapWindow: the map holds the last N keyframes only
     if "--map-window" in argv:
         i = argv.index("--map-window")
@@ -173,7 +195,7 @@ def main(argv=None):
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
         return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel,
-                            views_dir, views_every, map_save, covariances, views_raycast)
+                            views_dir, views_every, map_save, covariances, views_raycast, esdf)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
@@ -206,6 +228,7 @@ def main(argv=None):
               % (len(res), drv.nKeyFrames, ("%d decoder processes" % nd) if nd >= 1 else "decoded on the IO thread", len(res) / dt))
         if vmap is not None:
             _save_map(vmap, name, _rvm_path(map_save, name, len(io["datasets"]) > 1))
+            _save_esdf(vmap, esdf, name, len(io["datasets"]) > 1)
             if map_carve is not None:
                 done = [c[2] for c in drv.carves if c[2] is not None]
                 print("Map carve: %d voxels (%d points) carved by %d keyframes%s"
@@ -268,6 +291,15 @@ def _save_map(vmap, name, rvm=None):
              (", %d keyframes refused (max_voxels)" % info["keyframes_rejected"]) if info["keyframes_rejected"] else "", path))
 
 
+def _save_esdf(vmap, esdf, name, per_dataset):
+    """--map-esdf FILE: the finished map's distance field over its bounds grown by the pad."""
+    if esdf is None:
+        return
+    f = vmap.distance_field(pad=esdf[1])
+    path = f.save(_rvm_path(esdf[0], name, per_dataset))
+    print("Map distance field: %d x %d x %d cells from %s, largest d2 %d -> %s" % (tuple(f.n) + (f.lo.tolist(), f.info["max_d2"], path)))
+
+
 def _save_views(vmap, folder, poses, is_kf, every, depth_scale, raycast=False):
     """--map-views: the finished map from the pose of every keyframe (every == 0) or of every `every`-th tracked frame."""
     from . import tum
@@ -293,7 +325,7 @@ def _report_ate(folder, poses):
 
 
 def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
-                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False, views_raycast=False):
+                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False, views_raycast=False, esdf=None):
     """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
@@ -344,6 +376,7 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
         print("-----VO Report (%s)-----\nFrames Tracked: %d\nKeyframes Tracked: %d" % (name, len(r), sum(1 for _, kf in r if kf)))
         if r.map is not None:
             _save_map(r.map, name, _rvm_path(map_save, name, True))
+            _save_esdf(r.map, esdf, name, True)
             if views_dir is not None:
                 _save_views(r.map, os.path.join(views_dir, name), r.poses, [kf for _, kf in r], views_every,
                             io["depth_scale_factor"], views_raycast)

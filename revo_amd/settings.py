@@ -283,6 +283,27 @@ class MapRayInfo(C.Structure):
 
 assert (C.sizeof(MapRayParams), C.sizeof(MapRay), C.sizeof(MapRayHit), C.sizeof(MapRayInfo)) == (16, 32, 16, 64)
 
+DF_NONE = 0xFFFFFFFF  # REVO_DF_NONE: the value of every cell of a distance field whose box holds no solid voxel
+
+
+class MapDfBox(C.Structure):
+    """revo_map_df_box (include/revo_hip.h), 24 bytes: the first voxel index and the cells (1 .. 1024) per axis x, y, z."""
+    _fields_ = [("lo", C.c_int32 * 3), ("n", C.c_int32 * 3)]
+
+
+class MapDfInfo(C.Structure):
+    """revo_map_df_info (include/revo_hip.h), 64 bytes: integer sums and maxima of a distance-field call."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "solid", "outside", "below", "max_d2")] + [("reserved", C.c_uint64 * 3)]
+
+
+class MapDfSample(C.Structure):
+    """revo_map_df_sample_t (include/revo_hip.h), 16 bytes: a point's distance in metres (-1: outside the box, +inf: no solid
+    voxel) and the dimensionless gradient of the distance."""
+    _fields_ = [("dist", C.c_float), ("grad", C.c_float * 3)]
+
+
+assert (C.sizeof(MapDfBox), C.sizeof(MapDfInfo), C.sizeof(MapDfSample)) == (24, 64, 16)
+
 
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
