@@ -418,10 +418,10 @@ static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, cons
     revo_map* m = dm[j];
     const size_t bound = (size_t)nk[j] * npix;
     size_t ub = 0;
-    MAP_TRY(map_need_slots(m, bound, "batch", &ub));
+    TRY(map_need_slots(m, bound, "batch", &ub));
     chk[j] = ub + bound > m->max_voxels;
   }
-  MAP_TRY(st->reserve(n, (int)dm.size(), s));
+  TRY(st->reserve(n, (int)dm.size(), s));
   for (int i = 0; i < n; ++i) {
     revo_map* m = maps[i];
     MapDesc& d = st->desc.h[i];
@@ -444,7 +444,7 @@ static int integrate_core(revo_map_stage* st, int n, revo_map* const* maps, cons
     any_check = any_check || chk[j];
     if (chk[j] && checked) checked->push_back(m);
   }
-  MAP_TRY(st->upload(n, (int)dm.size(), s));
+  TRY(st->upload(n, (int)dm.size(), s));
   const int nb = (int)((npix + 255) / 256);
   const MapGeomK gk{g.w, (int)npix, g.fx, g.fy, g.cx, g.cy, g.dmin, g.dmax};
   const dim3 grid((unsigned)(nb * n)), blk(256), cgrid((unsigned)((dm.size() + 63) / 64)), cblk(64);
@@ -470,7 +470,7 @@ extern "C" int revo_map_create(revo_ctx* ctx, float voxel, int dense, size_t ini
   if (dense != 0 && dense != 1) return fail(REVO_ERR_INVALID_ARG, "dense must be 0 or 1");
   if (max_voxels < 1 || max_voxels > MAP_MAX_VOXELS) return fail(REVO_ERR_INVALID_ARG, "max_voxels must be 1 .. 2^28");
   MapCtxGeom g;
-  MAP_TRY(revo_map_ctx_geom_(ctx, &g));
+  TRY(revo_map_ctx_geom_(ctx, &g));
   HIPCHECK(hipSetDevice(g.device));
   revo_map* m = new revo_map();
   m->ctx = ctx; m->g = g; m->voxel = voxel; m->dense = dense; m->max_voxels = max_voxels;
@@ -480,11 +480,11 @@ extern "C" int revo_map_create(revo_ctx* ctx, float voxel, int dense, size_t ini
   HIPCHECK(hipMemsetAsync(m->d_st, 0, sizeof(MapStats), (hipStream_t)g.stream));
   HIPCHECK(hipHostMalloc((void**)&m->h_pub, sizeof(u64) * 4));
   memset(m->h_pub, 0, sizeof(u64) * 4);
-  MAP_TRY(revo_map_stage_create_(&m->stage));
+  TRY(revo_map_stage_create_(&m->stage));
   size_t c = 1024;
   const size_t want = std::min<size_t>(std::max<size_t>(initial_voxels, 1), max_voxels) * 2;
   while (c < want) c *= 2;
-  MAP_TRY(map_grow(m, c));
+  TRY(map_grow(m, c));
   HIPCHECK(hipStreamSynchronize((hipStream_t)g.stream));
   guard.m = nullptr;
   *out = m;
@@ -519,7 +519,7 @@ extern "C" int revo_map_integrate_many(revo_map* m, int n, const revo_pyr* const
     if (src[i].ctx != m->ctx) return fail(REVO_ERR_INVALID_ARG, "the pyramid belongs to another context than the map");
   }
   std::vector<revo_map*> maps(n, m), checked;
-  MAP_TRY(integrate_core(m->stage, n, maps.data(), src.data(), T, &checked));
+  TRY(integrate_core(m->stage, n, maps.data(), src.data(), T, &checked));
   if (!checked.empty()) {  // the map could have reached max_voxels: the device has decided, wait for it
     HIPCHECK(hipStreamSynchronize((hipStream_t)m->g.stream));
     if (!m->h_pub[2]) return fail(REVO_ERR_CAPACITY, "voxel map: the keyframes would take it past max_voxels (not integrated)");
@@ -567,7 +567,7 @@ int map_read_stats(revo_map* m, MapStats* out) {
 extern "C" int revo_map_info(revo_map* m, revo_map_info_t* out) {
   if (!m || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   MapStats st;
-  MAP_TRY(map_read_stats(m, &st));
+  TRY(map_read_stats(m, &st));
   out->voxels = (size_t)st.occ;
   out->points_integrated = (size_t)st.pts;
   out->points_dropped = (size_t)st.drop;
@@ -581,12 +581,12 @@ extern "C" int revo_map_info(revo_map* m, revo_map_info_t* out) {
 extern "C" int revo_map_extract(revo_map* m, size_t min_count, float* xyz, uint8_t* rgb, uint32_t* count, size_t cap, size_t* n) {
   if (!m || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
   MapStats st;
-  MAP_TRY(map_read_stats(m, &st));
+  TRY(map_read_stats(m, &st));
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t nv = std::max<size_t>((size_t)st.occ, 1);
   const size_t o_key = 0, o_xyz = o_key + 8 * nv, o_rgb = o_xyz + 12 * nv, o_cnt = o_rgb + 4 * nv, o_tot = o_cnt + 4 * nv;
-  MapScratch scratch;
-  MAP_TRY(scratch.alloc(o_tot + 256));
+  DevScratch scratch;
+  TRY(scratch.alloc(o_tot + 256));
   char* const buf = scratch.p;
   unsigned* d_tot = (unsigned*)(buf + o_tot);
   HIPCHECK(hipMemsetAsync(d_tot, 0, sizeof(unsigned), s));
@@ -630,18 +630,18 @@ extern "C" int revo_map_voxel_size(revo_map* m, float* voxel, int* dense) {
 
 extern "C" int revo_map_export_raw(revo_map* m, revo_map_voxel_raw* dst, size_t cap, size_t* n, int device_out) {
   if (!m || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)dst, 16, "the device output is"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)dst, 16, "the device output is"));
   MapStats st;
-  MAP_TRY(map_read_stats(m, &st));
+  TRY(map_read_stats(m, &st));
   const size_t nv = (size_t)st.occ;
   *n = nv;
   if (!dst) return REVO_OK;
   if (cap < nv) return fail(REVO_ERR_CAPACITY, "voxel map: the output holds fewer records than the map has voxels");
   if (!nv) return REVO_OK;
   hipStream_t s = (hipStream_t)m->g.stream;
-  MapScratch scratch;  // the launch's counter, and the records of a host-output call behind it
-  MAP_TRY(scratch.alloc(256 + (device_out ? 0 : sizeof(revo_map_voxel_raw) * nv)));
+  DevScratch scratch;  // the launch's counter, and the records of a host-output call behind it
+  TRY(scratch.alloc(256 + (device_out ? 0 : sizeof(revo_map_voxel_raw) * nv)));
   char* buf = scratch.p;
   unsigned* d_tot = (unsigned*)buf;
   ulonglong2* d_rec = device_out ? (ulonglong2*)dst : (ulonglong2*)(buf + 256);
@@ -672,14 +672,14 @@ static void launch_merge(int src_kind, dim3 grid, hipStream_t s, const MapMergeK
 int map_merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool trusted, int keyframes) {
   hipStream_t s = (hipStream_t)m->g.stream;
   size_t ub = 0;
-  MAP_TRY(map_need_slots(m, bound, "merge", &ub));
+  TRY(map_need_slots(m, bound, "merge", &ub));
   const bool chk = !trusted || ub + bound > m->max_voxels;
-  MapRows<MapCommit>& com = m->stage->com;
-  MAP_TRY(m->stage->reserve(0, 1, s));
+  HostRows<MapCommit>& com = m->stage->com;
+  TRY(m->stage->reserve(0, 1, s));
   ++m->seq;
   com.h[0] = MapCommit{m->d_st, m->h_pub, (u64)m->max_voxels, m->seq, keyframes, chk ? 1 : 0};
   m->pending.push_back({m->seq, bound});
-  MAP_TRY(m->stage->upload(0, 1, s));
+  TRY(m->stage->upload(0, 1, s));
   if (!trusted) HIPCHECK(hipMemsetAsync(&m->d_st->bad, 0, sizeof(u64), s));
   a.keys = m->d_keys; a.vals = m->d_vals; a.mask = (unsigned)(m->cap - 1); a.st = m->d_st;
   const dim3 grid((a.n + 255) / 256), blk(256);
@@ -705,11 +705,11 @@ int map_merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool tr
 extern "C" int revo_map_merge_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int device_in, size_t points_dropped,
                                   int32_t keyframes) {
   if (!m) return fail(REVO_ERR_INVALID_ARG, "null map");
-  MAP_TRY(map_check_side(device_in, "device_in"));
+  TRY(map_check_side(device_in, "device_in"));
   if (keyframes < 0) return fail(REVO_ERR_INVALID_ARG, "keyframes must be >= 0");
   if (n == 0) return REVO_OK;
   if (!src) return fail(REVO_ERR_INVALID_ARG, "null records");
-  if (device_in) MAP_TRY(map_check_aligned((uintptr_t)src, 16, "the device records are"));
+  if (device_in) TRY(map_check_aligned((uintptr_t)src, 16, "the device records are"));
   if (n > MAP_MAX_CAP / 2) return fail(REVO_ERR_CAPACITY, "voxel map: a merge this large needs more than 2^31 table slots");
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
@@ -722,8 +722,8 @@ extern "C" int revo_map_merge_raw(revo_map* m, const revo_map_voxel_raw* src, si
   }
   bool valid = true;  // a bad record still goes to the device, which refuses the merge and counts it
   for (size_t i = 0; i < n && valid; ++i) valid = src[i].count != 0 && !(src[i].key >> 63);
-  MapScratch up;
-  MAP_TRY(up.alloc(sizeof(revo_map_voxel_raw) * n));
+  DevScratch up;
+  TRY(up.alloc(sizeof(revo_map_voxel_raw) * n));
   HIPCHECK(hipMemcpyAsync(up.p, src, sizeof(revo_map_voxel_raw) * n, hipMemcpyHostToDevice, s));
   a.recs = (const ulonglong2*)up.p;
   const int rc = map_merge_core(m, a, MERGE_RAW, n, valid, keyframes);
@@ -736,7 +736,7 @@ extern "C" int revo_map_merge_raw(revo_map* m, const revo_map_voxel_raw* src, si
 static int merge_table(revo_map* dst, revo_map* src, int src_kind, int shift) {
   if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
   MapStats ss;  // waits for src: its table is complete, and its counters say what comes
-  MAP_TRY(map_read_stats(src, &ss));
+  TRY(map_read_stats(src, &ss));
   if (ss.kfs > 0x7fffffffull) return fail(REVO_ERR_INVALID_ARG, "the source map's keyframe count does not fit");
   HIPCHECK(hipSetDevice(dst->g.device));
   MapMergeK a{};
@@ -809,11 +809,11 @@ int map_subtract_core(revo_map* m, MapMergeK a, int src_kind, u64 dropped, u64 k
 extern "C" int revo_map_subtract_raw(revo_map* m, const revo_map_voxel_raw* src, size_t n, int device_in, size_t points_dropped,
                                      int32_t keyframes) {
   if (!m) return fail(REVO_ERR_INVALID_ARG, "null map");
-  MAP_TRY(map_check_side(device_in, "device_in"));
+  TRY(map_check_side(device_in, "device_in"));
   if (keyframes < 0) return fail(REVO_ERR_INVALID_ARG, "keyframes must be >= 0");
   if (n == 0) return REVO_OK;
   if (!src) return fail(REVO_ERR_INVALID_ARG, "null records");
-  if (device_in) MAP_TRY(map_check_aligned((uintptr_t)src, 16, "the device records are"));
+  if (device_in) TRY(map_check_aligned((uintptr_t)src, 16, "the device records are"));
   if (n > MAP_MAX_CAP) return fail(REVO_ERR_INVALID_ARG, "voxel map: more than 2^31 records in one subtraction");
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
@@ -823,8 +823,8 @@ extern "C" int revo_map_subtract_raw(revo_map* m, const revo_map_voxel_raw* src,
     a.recs = (const ulonglong2*)src;
     return map_subtract_core(m, a, MERGE_RAW, (u64)points_dropped, (u64)keyframes);
   }
-  MapScratch up;
-  MAP_TRY(up.alloc(sizeof(revo_map_voxel_raw) * n));
+  DevScratch up;
+  TRY(up.alloc(sizeof(revo_map_voxel_raw) * n));
   HIPCHECK(hipMemcpyAsync(up.p, src, sizeof(revo_map_voxel_raw) * n, hipMemcpyHostToDevice, s));
   a.recs = (const ulonglong2*)up.p;
   return map_subtract_core(m, a, MERGE_RAW, (u64)points_dropped, (u64)keyframes);  // has waited: the upload is read
@@ -836,7 +836,7 @@ extern "C" int revo_map_subtract(revo_map* dst, revo_map* src) {
   if (memcmp(&dst->voxel, &src->voxel, sizeof(float))) return fail(REVO_ERR_INVALID_ARG, "the maps' voxel edges differ");
   if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
   MapStats ss;  // waits for src: its table is complete, and its counters say what goes
-  MAP_TRY(map_read_stats(src, &ss));
+  TRY(map_read_stats(src, &ss));
   HIPCHECK(hipSetDevice(dst->g.device));
   MapMergeK a{};
   a.skeys = src->d_keys; a.svals = src->d_vals; a.n = (unsigned)src->cap;

@@ -400,7 +400,7 @@ static void normals_launch(hipStream_t s, revo_map* m, const float4* d_mean, con
 static int align_begin(MapAlignCall* c, revo_map* dst, revo_map* src, const revo_map_align_params* prm, int n_max,
                        const revo_map_normals_params* nprm = nullptr) {
   MapStats ss;
-  MAP_TRY(map_read_stats(src, &ss));
+  TRY(map_read_stats(src, &ss));
   HIPCHECK(hipSetDevice(dst->g.device));
   hipStream_t s = (hipStream_t)dst->g.stream;
   const size_t npts = std::max<size_t>((size_t)ss.occ, 1);
@@ -466,7 +466,7 @@ static int align_launch(MapAlignCall* c, int n, const float* T16, void* d_out) {
 }
 
 static int align_eval_host(MapAlignCall* c, const float T[16], void* out) {
-  MAP_TRY(align_launch(c, 1, T, nullptr));
+  TRY(align_launch(c, 1, T, nullptr));
   hipStream_t s = (hipStream_t)c->dst->g.stream;
   HIPCHECK(hipMemcpyAsync(out, c->d_out, c->rec_bytes, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
@@ -478,16 +478,16 @@ static int plane_params(const revo_map_align_params* prm, const revo_map_normals
 // revo_map_align_eval and, plane, revo_map_align_plane_eval (records of rec_bytes bytes): n poses, one launch
 static int align_eval_any(const char* name, revo_map* dst, revo_map* src, int n, const float* T, const revo_map_align_params* prm,
                           bool plane, const revo_map_normals_params* nprm, void* out, size_t rec_bytes, int device_out) {
-  MAP_TRY(align_check(dst, src, prm));
+  TRY(align_check(dst, src, prm));
   if (!T || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n < 1 || n > 65535) return fail(REVO_ERR_INVALID_ARG, std::string(name) + ": n must be 1 .. 65535");
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)out, 16, "the device output is"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)out, 16, "the device output is"));
   revo_map_normals_params np;
-  if (plane) MAP_TRY(plane_params(prm, nprm, &np));
+  if (plane) TRY(plane_params(prm, nprm, &np));
   MapAlignCall c;
-  MAP_TRY(align_begin(&c, dst, src, prm, n, plane ? &np : nullptr));
-  MAP_TRY(align_launch(&c, n, T, device_out ? out : nullptr));
+  TRY(align_begin(&c, dst, src, prm, n, plane ? &np : nullptr));
+  TRY(align_launch(&c, n, T, device_out ? out : nullptr));
   hipStream_t s = (hipStream_t)dst->g.stream;
   if (!device_out) HIPCHECK(hipMemcpyAsync(out, c.d_out, rec_bytes * n, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
@@ -508,14 +508,14 @@ extern "C" int revo_map_align_system(const revo_map_align_info* info, double H[3
 extern "C" int revo_map_align(revo_map* dst, revo_map* src, const float T_init[16], const revo_map_align_params* prm,
                               const revo_map_align_opts* opt, float T_out[16], revo_map_align_info* info_out, int32_t* iterations,
                               int32_t* status) {
-  MAP_TRY(align_check(dst, src, prm));
+  TRY(align_check(dst, src, prm));
   if (!T_init || !T_out || !status) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (!pose_is_finite(T_init)) return fail(REVO_ERR_INVALID_ARG, "T_init is not finite");
   revo_map_align_opts o{30, 0, 1e-6, 1e-6, 12};
   if (opt) o = *opt;
   if (o.max_iters < 1) return fail(REVO_ERR_INVALID_ARG, "max_iters must be >= 1");
   MapAlignCall c;
-  MAP_TRY(align_begin(&c, dst, src, prm, 1));
+  TRY(align_begin(&c, dst, src, prm, 1));
   int32_t it = 0;
   const int rc = align_loop(T_init, prm->centre, o, [&](const float* Tf, revo_map_align_info* rec) { return align_eval_host(&c, Tf, rec); },
                             T_out, info_out, &it, status);
@@ -550,16 +550,16 @@ extern "C" int revo_map_normals(revo_map* m, const revo_map_normals_params* prm,
   if (!m || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
   revo_map_normals_params p{1, 5, 0.1f, 0.1f};
   if (prm) p = *prm;
-  MAP_TRY(normals_check(&p));
+  TRY(normals_check(&p));
   MapStats st;
-  MAP_TRY(map_read_stats(m, &st));
+  TRY(map_read_stats(m, &st));
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t nv = std::max<size_t>((size_t)st.occ, 1), slots = m->cap;
   // per slot: mean, normal, lambda; per voxel: key and the same three rows, compacted; the two counters
   const size_t o_cnt = 0, o_mean = 256, o_norm = o_mean + 16 * slots, o_lam = o_norm + 16 * slots, o_key = o_lam + 16 * slots,
                o_xm = o_key + 16 * ((8 * nv + 15) / 16), o_xn = o_xm + 16 * nv, o_xl = o_xn + 16 * nv, total = o_xl + 16 * nv;
-  MapScratch scratch;
-  MAP_TRY(scratch.alloc(total));
+  DevScratch scratch;
+  TRY(scratch.alloc(total));
   char* buf = scratch.p;
   unsigned* d_cnt = (unsigned*)(buf + o_cnt);  // [0] the voxels exported, [1] the valid normals
   float4* d_mean = (float4*)(buf + o_mean);
@@ -624,16 +624,16 @@ extern "C" int revo_map_align_plane_system(const revo_map_plane_info* info, doub
 extern "C" int revo_map_align_plane(revo_map* dst, revo_map* src, const float T_init[16], const revo_map_align_params* prm,
                                     const revo_map_normals_params* nprm, const revo_map_align_opts* opt, float T_out[16],
                                     revo_map_plane_info* info_out, int32_t* iterations, int32_t* status) {
-  MAP_TRY(align_check(dst, src, prm));
+  TRY(align_check(dst, src, prm));
   if (!T_init || !T_out || !status) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (!pose_is_finite(T_init)) return fail(REVO_ERR_INVALID_ARG, "T_init is not finite");
   revo_map_align_opts o{30, 0, 1e-6, 1e-6, 12};
   if (opt) o = *opt;
   if (o.max_iters < 1) return fail(REVO_ERR_INVALID_ARG, "max_iters must be >= 1");
   revo_map_normals_params np;
-  MAP_TRY(plane_params(prm, nprm, &np));
+  TRY(plane_params(prm, nprm, &np));
   MapAlignCall c;
-  MAP_TRY(align_begin(&c, dst, src, prm, 1, &np));
+  TRY(align_begin(&c, dst, src, prm, 1, &np));
   int32_t it = 0;
   const int rc = align_loop_over<revo_map_plane_info>(T_init, prm->centre, o, align_plane_system_fill,
                                                       [&](const float* Tf, revo_map_plane_info* rec) { return align_eval_host(&c, Tf, rec); },

@@ -107,14 +107,14 @@ static int pose_check(const float* T, float voxel_dst) {
 // One k_map_pose launch over src's table on stream s (src has been waited for), then the wait for its counters.  d_out NULL:
 // the records go into the run's own buffer (room for every voxel of src), which lives as long as the run.
 struct MapPoseRun {
-  MapScratch buf;
+  DevScratch buf;
   revo_map_pose_info info{};
   const ulonglong2* recs() const { return (const ulonglong2*)(buf.p + 256); }
 };
 static int pose_run(MapPoseRun* r, revo_map* src, hipStream_t s, size_t voxels, const float* T, float voxel_dst, size_t min_count,
                     ulonglong2* d_out, size_t cap_out, bool own) {
   const size_t room = own ? std::max<size_t>(voxels, 1) : 0;
-  if (!r->buf.p) MAP_TRY(r->buf.alloc(256 + sizeof(revo_map_voxel_raw) * room));
+  if (!r->buf.p) TRY(r->buf.alloc(256 + sizeof(revo_map_voxel_raw) * room));
   MapPoseK a{};
   a.keys = src->d_keys; a.vals = src->d_vals; a.cap = (unsigned)src->cap;
   a.min_count = (u64)std::max<size_t>(min_count, 1);
@@ -136,17 +136,17 @@ static int pose_run(MapPoseRun* r, revo_map* src, hipStream_t s, size_t voxels, 
 extern "C" int revo_map_pose_raw(revo_map* src, const float T[16], float voxel_dst, size_t min_count, revo_map_voxel_raw* out, size_t cap,
                                  size_t* n, int device_out, revo_map_pose_info* info) {
   if (!src || !T || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)out, 16, "the device output is"));
-  MAP_TRY(pose_check(T, voxel_dst));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)out, 16, "the device output is"));
+  TRY(pose_check(T, voxel_dst));
   MapStats ss;
-  MAP_TRY(map_read_stats(src, &ss));
+  TRY(map_read_stats(src, &ss));
   hipStream_t s = (hipStream_t)src->g.stream;
   const size_t nv = (size_t)ss.occ;
   MapPoseRun r;
   if (device_out) {
     // nothing may be written when cap is too small or a source voxel is a bad record: count first, then write
-    MAP_TRY(pose_run(&r, src, s, nv, T, voxel_dst, min_count, nullptr, 0, false));
+    TRY(pose_run(&r, src, s, nv, T, voxel_dst, min_count, nullptr, 0, false));
     *n = (size_t)r.info.voxels_moved;
     if (info) *info = r.info;
     if (!out) return REVO_OK;
@@ -154,7 +154,7 @@ extern "C" int revo_map_pose_raw(revo_map* src, const float T[16], float voxel_d
     if (!*n) return REVO_OK;
     return pose_run(&r, src, s, nv, T, voxel_dst, min_count, (ulonglong2*)out, cap, false);
   }
-  MAP_TRY(pose_run(&r, src, s, nv, T, voxel_dst, min_count, nullptr, 0, true));
+  TRY(pose_run(&r, src, s, nv, T, voxel_dst, min_count, nullptr, 0, true));
   const size_t moved = (size_t)r.info.voxels_moved;
   std::vector<revo_map_voxel_raw> rec(moved);
   if (moved) HIPCHECK(hipMemcpy(rec.data(), r.recs(), sizeof(revo_map_voxel_raw) * moved, hipMemcpyDeviceToHost));
@@ -173,14 +173,14 @@ static int posed_apply(revo_map* dst, revo_map* src, const float* T, size_t min_
   if (!dst || !src || !T) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (dst == src) return fail(REVO_ERR_INVALID_ARG, "a map cannot be posed into itself");
   if (dst->g.device != src->g.device) return fail(REVO_ERR_INVALID_ARG, "the maps are on different devices");
-  MAP_TRY(pose_check(T, dst->voxel));
+  TRY(pose_check(T, dst->voxel));
   MapStats ss;  // waits for src: its table is complete, and its counters say what comes
-  MAP_TRY(map_read_stats(src, &ss));
+  TRY(map_read_stats(src, &ss));
   if (ss.kfs > 0x7fffffffull) return fail(REVO_ERR_INVALID_ARG, "the source map's keyframe count does not fit");
   HIPCHECK(hipSetDevice(dst->g.device));
   hipStream_t s = (hipStream_t)dst->g.stream;
   MapPoseRun r;
-  MAP_TRY(pose_run(&r, src, s, (size_t)ss.occ, T, dst->voxel, min_count, nullptr, 0, true));
+  TRY(pose_run(&r, src, s, (size_t)ss.occ, T, dst->voxel, min_count, nullptr, 0, true));
   if (info) *info = r.info;
   const size_t moved = (size_t)r.info.voxels_moved;
   if (!moved) return REVO_OK;  // as revo_map_merge_raw / revo_map_subtract_raw with n == 0
@@ -319,9 +319,9 @@ static_assert(sizeof(revo_map_carve_view) == 112 && offsetof(revo_map_carve_view
 
 // One carve call's device memory: the counter lines, the view descriptors, the uploaded host images, the records.
 struct MapCarveRun {
-  MapScratch buf;     // [0, 64) the info line, [256, 256 + 32 n) the views' counters, then the descriptors
-  MapScratch images;  // host depth images of the call, uploaded
-  MapScratch recs;    // the carved records of a host-output call or of revo_map_carve
+  DevScratch buf;     // [0, 64) the info line, [256, 256 + 32 n) the views' counters, then the descriptors
+  DevScratch images;  // host depth images of the call, uploaded
+  DevScratch recs;    // the carved records of a host-output call or of revo_map_carve
 };
 
 static int carve_launch(revo_map* m, hipStream_t s, MapCarveRun* r, MapCarveK a, revo_map_carve_info* info, revo_map_carve_view_info* vinfo) {
@@ -342,9 +342,9 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
                        revo_map_carve_view_info* view_info, bool remove) {
   if (!m || !views || !n_records) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n < 1 || n > CARVE_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, "revo_map_carve: n must be 1 .. 64 views");
-  MAP_TRY(map_check_side(device_in, "device_in"));
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)records, 16, "the device output is"));
+  TRY(map_check_side(device_in, "device_in"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)records, 16, "the device output is"));
   revo_map_carve_params pp;
   if (const char* why = carve_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_carve: ") + why);
   const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
@@ -355,7 +355,7 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
     if (const char* why = carve_view_check(&views[i], cam, m->g.w, m->g.h, &hv[i].v)) return fail(REVO_ERR_INVALID_ARG, at + why);
     hv[i].depth = views[i].depth;
     if (views[i].depth) {
-      if (device_in) MAP_TRY(map_check_aligned((uintptr_t)views[i].depth, 4, at + "the device depth image is"));
+      if (device_in) TRY(map_check_aligned((uintptr_t)views[i].depth, 4, at + "the device depth image is"));
       if (!device_in) up_bytes += ((size_t)hv[i].v.w * hv[i].v.h * sizeof(float) + 255) & ~(size_t)255;
     }
   }
@@ -363,7 +363,7 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
     if (!views[i].kf) continue;
     const revo_ctx* pc = nullptr;
     int batch_view = 0;
-    MAP_TRY(revo_map_source_kind_(views[i].kf, &pc, &batch_view));
+    TRY(revo_map_source_kind_(views[i].kf, &pc, &batch_view));
     const std::string at = "view " + std::to_string(i) + ": ";
     if (pc != m->ctx) return fail(REVO_ERR_INVALID_ARG, at + "the pyramid belongs to another context than the map");
     if (batch_view)
@@ -372,17 +372,17 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
   for (int i = 0; i < n; ++i) {  // nothing is refused from here on: the tracker stream is ordered behind the pyramids' builds
     if (!views[i].kf) continue;
     MapSource src;
-    MAP_TRY(revo_map_source_(const_cast<revo_pyr*>(views[i].kf), &src));
+    TRY(revo_map_source_(const_cast<revo_pyr*>(views[i].kf), &src));
     hv[i].depth = src.depth;
   }
   MapStats st;  // waits for the map: its table is complete
-  MAP_TRY(map_read_stats(m, &st));
+  TRY(map_read_stats(m, &st));
   hipStream_t s = (hipStream_t)m->g.stream;
   MapCarveRun r;
   const size_t o_views = 256 + ((sizeof(revo_map_carve_view_info) * n + 255) & ~(size_t)255);
-  MAP_TRY(r.buf.alloc(o_views + sizeof(MapCarveView) * n));
+  TRY(r.buf.alloc(o_views + sizeof(MapCarveView) * n));
   if (up_bytes) {
-    MAP_TRY(r.images.alloc(up_bytes));
+    TRY(r.images.alloc(up_bytes));
     size_t o = 0;
     for (int i = 0; i < n; ++i) {
       if (!views[i].depth) continue;
@@ -402,7 +402,7 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
   revo_map_carve_info ci{};
   std::vector<revo_map_carve_view_info> vi(n);
   // nothing may be written when cap is too small: count first, then write (carve_launch waits, so hv and the images are read)
-  MAP_TRY(carve_launch(m, s, &r, a, &ci, vi.data()));
+  TRY(carve_launch(m, s, &r, a, &ci, vi.data()));
   const size_t carved = (size_t)ci.voxels_carved;
   *n_records = carved;
   if (info) *info = ci;
@@ -411,12 +411,12 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
   if (!carved || (!records && !remove)) return REVO_OK;
   ulonglong2* d_rec = (ulonglong2*)records;
   if (!records || !device_out) {
-    MAP_TRY(r.recs.alloc(sizeof(revo_map_voxel_raw) * carved));
+    TRY(r.recs.alloc(sizeof(revo_map_voxel_raw) * carved));
     d_rec = (ulonglong2*)r.recs.p;
   }
   a.out = d_rec; a.cap_out = (unsigned)carved;
   revo_map_carve_info ci2{};
-  MAP_TRY(carve_launch(m, s, &r, a, &ci2, vi.data()));
+  TRY(carve_launch(m, s, &r, a, &ci2, vi.data()));
   if (ci2.voxels_carved != ci.voxels_carved) return fail(REVO_ERR_HIP, "voxel map: two carve launches over one table disagree");
   if (remove) {
     MapMergeK sub{};

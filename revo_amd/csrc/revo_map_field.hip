@@ -260,21 +260,21 @@ extern "C" int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, 
   if (!m || !box || !d2) return fail(REVO_ERR_INVALID_ARG, "null argument");
   size_t cells = 0;
   if (const char* why = df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_distance_field: ") + why);
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)d2 | (uintptr_t)info, 16, "a device output is"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)d2 | (uintptr_t)info, 16, "a device output is"));
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
   const revo_map_df_box b = *box;
   const unsigned wz = (unsigned)(b.n[2] + 31) / 32;
   const unsigned lines = (unsigned)b.n[0] * (unsigned)b.n[1];
   const size_t bit_bytes = sizeof(unsigned) * (size_t)lines * wz;
-  MAP_TRY(m->dfbits.reserve(bit_bytes, s));
-  MAP_TRY(m->dfcnt.reserve(128, s));
-  MAP_TRY(m->dfout.reserve(device_out ? 0 : sizeof(unsigned) * cells, s));
+  TRY(m->dfbits.reserve(bit_bytes, s));
+  TRY(m->dfcnt.reserve(128, s));
+  TRY(m->dfout.reserve(device_out ? 0 : sizeof(unsigned) * cells, s));
   unsigned* bits = (unsigned*)m->dfbits.p;
   unsigned* d_out = device_out ? d2 : (unsigned*)m->dfout.p;
   u64* d_info = device_out && info ? (u64*)info : (u64*)m->dfcnt.p;
-  MAP_TRY(m->df_time.begin(s));
+  TRY(m->df_time.begin(s));
   HIPCHECK(hipMemsetAsync(bits, 0, bit_bytes, s));
   HIPCHECK(hipMemsetAsync(d_info, 0, sizeof(revo_map_df_info), s));
   hipLaunchKernelGGL(k_df_occupancy, dim3((unsigned)std::max<size_t>((m->cap + 255) / 256, 1)), dim3(256), 0, s, m->d_keys, m->d_vals,
@@ -286,7 +286,7 @@ extern "C" int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, 
   HIPCHECK(hipGetLastError());
   df_launch_pass<true>(s, d_out, 1, b.n[0], (unsigned)b.n[1] * (unsigned)b.n[2], clamp, d_info);
   HIPCHECK(hipGetLastError());
-  MAP_TRY(m->df_time.end(s));
+  TRY(m->df_time.end(s));
   if (device_out) return REVO_OK;
   HIPCHECK(hipMemcpyAsync(d2, d_out, sizeof(unsigned) * cells, hipMemcpyDeviceToHost, s));
   if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_df_info), hipMemcpyDeviceToHost, s));
@@ -305,7 +305,7 @@ extern "C" int revo_map_bounds(revo_map* m, uint32_t min_count, int32_t lo[3], i
   if (!m || !lo || !hi || !n) return fail(REVO_ERR_INVALID_ARG, "null argument");
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MAP_TRY(m->dfcnt.reserve(128, s));
+  TRY(m->dfcnt.reserve(128, s));
   struct Line { int b[6]; int pad[2]; u64 cnt; } h = {{INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN}, {0, 0}, 0};
   Line* d = (Line*)(m->dfcnt.p + 64);  // behind the field's info line
   HIPCHECK(hipMemcpyAsync(d, &h, sizeof(h), hipMemcpyHostToDevice, s));
@@ -327,30 +327,30 @@ extern "C" int revo_map_df_sample(revo_map* m, const revo_map_df_box* box, const
   if (n < 1 || n > DF_MAX_POINTS) return fail(REVO_ERR_INVALID_ARG, "revo_map_df_sample: n must be 1 .. 2^24 points");
   size_t cells = 0;
   if (const char* why = df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_df_sample: ") + why);
-  MAP_TRY(map_check_side(device_field, "device_field"));
-  MAP_TRY(map_check_side(device_in, "device_in"));
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_field) MAP_TRY(map_check_aligned((uintptr_t)d2, 16, "the device field is"));
-  if (device_in) MAP_TRY(map_check_aligned((uintptr_t)xyz, 16, "the device points are"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)out, 16, "the device output is"));
+  TRY(map_check_side(device_field, "device_field"));
+  TRY(map_check_side(device_in, "device_in"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_field) TRY(map_check_aligned((uintptr_t)d2, 16, "the device field is"));
+  if (device_in) TRY(map_check_aligned((uintptr_t)xyz, 16, "the device points are"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)out, 16, "the device output is"));
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MapScratch field, pts, res;  // freed after the wait below
+  DevScratch field, pts, res;  // freed after the wait below
   const unsigned* d_field = d2;
   const float* d_xyz = xyz;
   float4* d_res = (float4*)out;
   if (!device_field) {
-    MAP_TRY(field.alloc(sizeof(unsigned) * cells));
+    TRY(field.alloc(sizeof(unsigned) * cells));
     HIPCHECK(hipMemcpyAsync(field.p, d2, sizeof(unsigned) * cells, hipMemcpyHostToDevice, s));
     d_field = (const unsigned*)field.p;
   }
   if (!device_in) {
-    MAP_TRY(pts.alloc(sizeof(float) * 3 * n));
+    TRY(pts.alloc(sizeof(float) * 3 * n));
     HIPCHECK(hipMemcpyAsync(pts.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, s));
     d_xyz = (const float*)pts.p;
   }
   if (!device_out) {
-    MAP_TRY(res.alloc(sizeof(float4) * n));
+    TRY(res.alloc(sizeof(float4) * n));
     d_res = (float4*)res.p;
   }
   const bool waits = !device_field || !device_in || !device_out;

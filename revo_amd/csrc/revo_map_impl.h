@@ -1,7 +1,8 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
 // revo_map_edit.hip, revo_map_field.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
-// units include it.
+// units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
+// library's, of revo_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -171,8 +172,6 @@ __device__ __forceinline__ unsigned map_compact(bool sel, unsigned& s_n, unsigne
 }
 
 // ------------------------------------------------------------------------------------------------------- host pieces --
-#define MAP_TRY(expr) do { const int rc__ = (expr); if (rc__) return rc__; } while (0)
-
 // the argument rules every entry point states the same way
 inline int map_check_side(int flag, const char* name) {
   return flag != 0 && flag != 1 ? fail(REVO_ERR_INVALID_ARG, std::string(name) + " must be 0 or 1") : REVO_OK;
@@ -180,94 +179,6 @@ inline int map_check_side(int flag, const char* name) {
 inline int map_check_aligned(uintptr_t bits, int align, const std::string& what) {  // what: "the device output is", ...
   return bits & (uintptr_t)(align - 1) ? fail(REVO_ERR_INVALID_ARG, what + " not " + std::to_string(align) + "-byte aligned") : REVO_OK;
 }
-
-struct MapOwner {  // what the types below are: owners of device resources, released by their destructors, never copied
-  MapOwner() = default;
-  MapOwner(const MapOwner&) = delete;
-  MapOwner& operator=(const MapOwner&) = delete;
-};
-
-// Device memory of one call: freed when the call returns, whichever way, and a failed call leaves no sticky error behind.
-struct MapScratch : MapOwner {
-  char* p = nullptr;
-  ~MapScratch() { (void)hipFree(p); (void)hipGetLastError(); }
-  int alloc(size_t bytes) { HIPCHECK(hipMalloc((void**)&p, bytes)); return REVO_OK; }
-};
-
-// A device buffer of the handle that only grows.  The stream is waited for first: its work may still use the old one.
-struct MapBuf : MapOwner {
-  char* p = nullptr; size_t bytes = 0;
-  ~MapBuf() { (void)hipFree(p); }
-  int reserve(size_t need, hipStream_t s) {
-    if (need <= bytes) return REVO_OK;
-    HIPCHECK(hipStreamSynchronize(s));
-    (void)hipFree(p);
-    p = nullptr; bytes = 0;
-    HIPCHECK(hipMalloc((void**)&p, need));
-    bytes = need;
-    return REVO_OK;
-  }
-};
-
-// Descriptor rows of a launch: written into pinned memory, uploaded, read by the kernels from device memory.  The event
-// (recorded behind the upload) is waited for before the pinned rows are rewritten, the stream before device rows that a
-// kernel may still read are reallocated (none exist yet when the rows are first reserved: no wait then).  The event is made
-// on first use, or ahead of it by create(), where its cost must not fall into the first launch.
-template <typename Row>
-struct MapRows : MapOwner {
-  Row* h = nullptr; Row* d = nullptr; int cap = 0;
-  hipEvent_t ev = nullptr; bool recorded = false;
-  ~MapRows() {
-    if (recorded) (void)hipEventSynchronize(ev);
-    (void)hipHostFree(h); (void)hipFree(d);
-    if (ev) (void)hipEventDestroy(ev);
-  }
-  int create() { if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); return REVO_OK; }
-  int reserve(int n, hipStream_t s) {
-    if (recorded) HIPCHECK(hipEventSynchronize(ev));  // the previous upload has read the pinned rows
-    if (n <= cap) return REVO_OK;
-    if (cap) HIPCHECK(hipStreamSynchronize(s));  // the previous call's kernels read the device rows
-    (void)hipHostFree(h); (void)hipFree(d);
-    h = nullptr; d = nullptr; cap = 0;
-    HIPCHECK(hipHostMalloc((void**)&h, sizeof(Row) * n));
-    HIPCHECK(hipMalloc((void**)&d, sizeof(Row) * n));
-    cap = n;
-    return REVO_OK;
-  }
-  int upload(int n, hipStream_t s, bool mark = true) {  // mark: record the event behind it
-    HIPCHECK(hipMemcpyAsync(d, h, sizeof(Row) * n, hipMemcpyHostToDevice, s));
-    if (!mark) return REVO_OK;
-    MAP_TRY(create());
-    HIPCHECK(hipEventRecord(ev, s));
-    recorded = true;
-    return REVO_OK;
-  }
-};
-
-// The two events around a feature's device work and what *_last_ms makes of them.
-struct MapTimer : MapOwner {
-  hipEvent_t e0 = nullptr, e1 = nullptr; bool ready = false;
-  ~MapTimer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  int begin(hipStream_t s) {
-    if (!e0) HIPCHECK(hipEventCreate(&e0));
-    if (!e1) HIPCHECK(hipEventCreate(&e1));
-    HIPCHECK(hipEventRecord(e0, s));
-    return REVO_OK;
-  }
-  int end(hipStream_t s) {
-    HIPCHECK(hipEventRecord(e1, s));
-    ready = true;
-    return REVO_OK;
-  }
-  int last_ms(float* ms) {
-    HIPCHECK(hipEventSynchronize(e1));
-    HIPCHECK(hipEventElapsedTime(ms, e0, e1));
-    return REVO_OK;
-  }
-};
 
 struct MapDesc {  // one keyframe of a launch
   const float* depth; const uint8_t* edges; const uint8_t* bgr;
@@ -283,10 +194,10 @@ struct MapCommit {  // one map of a launch
 // rows, `com`'s, recorded behind both uploads: a second hipEventRecord per integration would be stream work the launch never
 // had.  Callers go through reserve() and upload(), which keep that order; h and d of the two members are theirs to fill.
 struct revo_map_stage {
-  MapRows<MapDesc> desc;
-  MapRows<MapCommit> com;
-  int reserve(int nd, int nc, hipStream_t s) { MAP_TRY(com.reserve(nc, s)); return desc.reserve(nd, s); }  // com: waits for the event
-  int upload(int nd, int nc, hipStream_t s) { if (nd) MAP_TRY(desc.upload(nd, s, false)); return com.upload(nc, s); }
+  HostRows<MapDesc> desc;
+  HostRows<MapCommit> com;
+  int reserve(int nd, int nc, hipStream_t s) { TRY(com.reserve(nc, s)); return desc.reserve(nd, s); }  // com: waits for the event
+  int upload(int nd, int nc, hipStream_t s) { if (nd) TRY(desc.upload(nd, s, false)); return com.upload(nc, s); }
 };
 struct MapViewK;    // revo_map_view.hip: one view of a render launch
 struct MapRayView;  // revo_map_view.hip: one view of a raycast launch
@@ -307,19 +218,19 @@ struct revo_map {
   std::vector<std::pair<revo_vo_multi*, int>> attached;
   // revo_map_render: z-buffers of a call's views (every word MAP_EMPTY between calls: the resolve kernel puts it back), the
   // device outputs of a host-output call, the views' descriptors and covered counters, the call's events
-  MapBuf zbuf; bool zbuf_clean = false;
-  MapBuf vout, cov;
-  MapRows<MapViewK> views;
-  MapTimer render_time;
+  DevBuf zbuf; bool zbuf_clean = false;
+  DevBuf vout, cov;
+  HostRows<MapViewK> views;
+  EventTimer render_time;
   // revo_map_raycast / revo_map_cast_rays: the block table (as many slots as the map's), the counter lines, the views'
   // descriptors, the device outputs of a host-output call, the call's events
-  MapBuf bkeys, rcnt, rout;
-  MapRows<MapRayView> rviews;
-  MapTimer ray_time;
+  DevBuf bkeys, rcnt, rout;
+  HostRows<MapRayView> rviews;
+  EventTimer ray_time;
   // revo_map_distance_field / revo_map_bounds (revo_map_field.hip): the bit volume of a call's box, the counter lines, the
   // device field of a host-output call, the call's events
-  MapBuf dfbits, dfcnt, dfout;
-  MapTimer df_time;
+  DevBuf dfbits, dfcnt, dfout;
+  EventTimer df_time;
 };
 
 // revo_map.hip, for the other units.  map_read_stats waits for the map's stream; map_grow(live_only) is the compaction an

@@ -76,10 +76,10 @@ __global__ void __launch_bounds__(256) k_map_view_resolve(const MapViewK* __rest
 // room for a call's views: descriptors, counters, z-buffer words (kept MAP_EMPTY), device outputs of a host-output call
 static int render_reserve(revo_map* m, int n, size_t words, size_t out_bytes) {
   hipStream_t s = (hipStream_t)m->g.stream;
-  MAP_TRY(m->views.reserve(n, s));
-  MAP_TRY(m->cov.reserve(sizeof(unsigned) * n, s));
+  TRY(m->views.reserve(n, s));
+  TRY(m->cov.reserve(sizeof(unsigned) * n, s));
   if (sizeof(u64) * words > m->zbuf.bytes) m->zbuf_clean = false;
-  MAP_TRY(m->zbuf.reserve(sizeof(u64) * words, s));
+  TRY(m->zbuf.reserve(sizeof(u64) * words, s));
   if (!m->zbuf_clean) HIPCHECK(hipMemsetAsync(m->zbuf.p, 0xff, m->zbuf.bytes, s));
   return m->vout.reserve(out_bytes, s);
 }
@@ -88,8 +88,8 @@ extern "C" int revo_map_render(revo_map* m, int n, const revo_map_view* views, f
                                uint32_t* covered, int device_out) {
   if (!m || !views || !depth || !bgr) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n < 1) return fail(REVO_ERR_INVALID_ARG, "revo_map_render: n must be >= 1");
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)covered, 16, "covered is"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)covered, 16, "covered is"));
   std::vector<revo_map_view> vs(views, views + n);
   size_t words = 0, out_bytes = 0;
   int max_pix = 0;
@@ -97,7 +97,7 @@ extern "C" int revo_map_render(revo_map* m, int n, const revo_map_view* views, f
     revo_map_view& v = vs[i];
     const std::string at = "view " + std::to_string(i) + ": ";
     if (!depth[i] || !bgr[i]) return fail(REVO_ERR_INVALID_ARG, at + "null output");
-    if (device_out) MAP_TRY(map_check_aligned((uintptr_t)depth[i] | (uintptr_t)bgr[i], 16, at + "a device output is"));
+    if (device_out) TRY(map_check_aligned((uintptr_t)depth[i] | (uintptr_t)bgr[i], 16, at + "a device output is"));
     if (v.width < 1 || v.width > 2048 || v.height < 1 || v.height > 2048)
       return fail(REVO_ERR_INVALID_ARG, at + "width and height must be 1 .. 2048");
     if (v.splat_max < 0 || v.splat_max > 8) return fail(REVO_ERR_INVALID_ARG, at + "splat_max must be 0 .. 8");
@@ -119,7 +119,7 @@ extern "C" int revo_map_render(revo_map* m, int n, const revo_map_view* views, f
   }
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MAP_TRY(render_reserve(m, n, words, device_out ? 0 : out_bytes));
+  TRY(render_reserve(m, n, words, device_out ? 0 : out_bytes));
   unsigned* d_cov = device_out && covered ? covered : (unsigned*)m->cov.p;
   size_t zo = 0, oo = 0;
   for (int i = 0; i < n; ++i) {
@@ -141,10 +141,10 @@ extern "C" int revo_map_render(revo_map* m, int n, const revo_map_view* views, f
     else { d.depth = (float*)(m->vout.p + oo); d.bgr = (uint8_t*)(m->vout.p + oo + np * 4); oo += (np * 7 + 15) & ~(size_t)15; }
     d.covered = d_cov + i;
   }
-  MAP_TRY(m->views.upload(n, s));
+  TRY(m->views.upload(n, s));
   HIPCHECK(hipMemsetAsync(d_cov, 0, sizeof(unsigned) * n, s));
   m->zbuf_clean = false;  // until the resolve launch that puts every word back is enqueued
-  MAP_TRY(m->render_time.begin(s));
+  TRY(m->render_time.begin(s));
   const dim3 blk(256), sgrid((unsigned)((m->cap + 255) / 256), (unsigned)n), rgrid((unsigned)((max_pix + 255) / 256), (unsigned)n);
   // REVO_MAP_RENDER_SKIP=0: every footprint pixel takes its atomic without the load in front (profiles/map_render_rates.py)
   if (env_int("REVO_MAP_RENDER_SKIP", 1, 0, 1))
@@ -155,7 +155,7 @@ extern "C" int revo_map_render(revo_map* m, int n, const revo_map_view* views, f
   hipLaunchKernelGGL(k_map_view_resolve, rgrid, blk, 0, s, m->views.d);
   HIPCHECK(hipGetLastError());
   m->zbuf_clean = true;
-  MAP_TRY(m->render_time.end(s));
+  TRY(m->render_time.end(s));
   if (device_out) return REVO_OK;
   oo = 0;
   for (int i = 0; i < n; ++i) {
@@ -370,9 +370,9 @@ static_assert(REVO_RAY_HIT == RAY_HIT && REVO_RAY_RANGE == RAY_RANGE && REVO_RAY
 // [64, 64 + 4 x 64) the views' hits), the views' descriptors, the device outputs of a host-output call.
 static int ray_reserve(revo_map* m, int n_views, size_t out_bytes) {
   hipStream_t s = (hipStream_t)m->g.stream;
-  MAP_TRY(m->rcnt.reserve(512, s));
-  MAP_TRY(m->rviews.reserve(n_views, s));
-  MAP_TRY(m->bkeys.reserve(sizeof(u64) * m->cap, s));
+  TRY(m->rcnt.reserve(512, s));
+  TRY(m->rviews.reserve(n_views, s));
+  TRY(m->bkeys.reserve(sizeof(u64) * m->cap, s));
   return m->rout.reserve(out_bytes, s);
 }
 
@@ -383,7 +383,7 @@ static int ray_begin(revo_map* m, MapRayK* a, u64 min_count, unsigned max_steps,
   a->keys = m->d_keys; a->vals = m->d_vals; a->mask = (unsigned)(m->cap - 1);
   a->min_count = min_count; a->max_steps = max_steps; a->voxel = m->voxel;
   a->info = d_info;
-  MAP_TRY(m->ray_time.begin(s));
+  TRY(m->ray_time.begin(s));
   a->bkeys = nullptr; a->bmask = 0;
   if (env_int("REVO_MAP_RAYCAST_BLOCKS", 1, 0, 1)) {
     u64* bkeys = (u64*)m->bkeys.p;
@@ -402,8 +402,8 @@ extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, 
                                 uint8_t* const* bgr, uint64_t* const* key, uint32_t* hits, int device_out, revo_map_ray_info* info) {
   if (!m || !views || !depth) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n < 1 || n > RAY_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, "revo_map_raycast: n must be 1 .. 64 views");
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)hits | (uintptr_t)info, 16, "hits or info is"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)hits | (uintptr_t)info, 16, "hits or info is"));
   uint32_t max_steps = 0;
   if (const char* why = ray_params_check(prm, &max_steps)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_raycast: ") + why);
   const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
@@ -414,7 +414,7 @@ extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, 
     const std::string at = "view " + std::to_string(i) + ": ";
     if (!depth[i] || (bgr && !bgr[i]) || (key && !key[i])) return fail(REVO_ERR_INVALID_ARG, at + "null output");
     if (device_out)
-      MAP_TRY(map_check_aligned((uintptr_t)depth[i] | (uintptr_t)(bgr ? bgr[i] : nullptr) | (uintptr_t)(key ? key[i] : nullptr), 16,
+      TRY(map_check_aligned((uintptr_t)depth[i] | (uintptr_t)(bgr ? bgr[i] : nullptr) | (uintptr_t)(key ? key[i] : nullptr), 16,
                                 at + "a device output is"));
     if (const char* why = ray_view_check(&views[i], cam, &rv[i])) return fail(REVO_ERR_INVALID_ARG, at + why);
     const size_t np = (size_t)rv[i].w * rv[i].h;
@@ -425,7 +425,7 @@ extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, 
   if (!min_count) return fail(REVO_ERR_INVALID_ARG, "revo_map_raycast: every view of a call must carry the same min_count");
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MAP_TRY(ray_reserve(m, n, device_out ? 0 : out_bytes));
+  TRY(ray_reserve(m, n, device_out ? 0 : out_bytes));
   u64* d_info = device_out && info ? (u64*)info : (u64*)m->rcnt.p;
   unsigned* d_hits = device_out && hits ? hits : (unsigned*)(m->rcnt.p + 64);
   size_t oo = 0;
@@ -445,12 +445,12 @@ extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, 
     }
     d.hits = d_hits + i;
   }
-  MAP_TRY(m->rviews.upload(n, s));
+  TRY(m->rviews.upload(n, s));
   MapRayK a{};
-  MAP_TRY(ray_begin(m, &a, min_count, max_steps, d_info, d_hits, n));
+  TRY(ray_begin(m, &a, min_count, max_steps, d_info, d_hits, n));
   hipLaunchKernelGGL(k_map_raycast, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), 0, s, a, m->rviews.d);
   HIPCHECK(hipGetLastError());
-  MAP_TRY(m->ray_time.end(s));
+  TRY(m->ray_time.end(s));
   if (device_out) return REVO_OK;
   for (int i = 0; i < n; ++i) {
     const MapRayView& d = m->rviews.h[i];
@@ -469,19 +469,19 @@ extern "C" int revo_map_cast_rays(revo_map* m, size_t n, const revo_map_ray* ray
                                   const revo_map_ray_params* prm, revo_map_ray_hit* out, int device_out, revo_map_ray_info* info) {
   if (!m || !rays || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n < 1 || n > RAY_MAX_RAYS) return fail(REVO_ERR_INVALID_ARG, "revo_map_cast_rays: n must be 1 .. 2^24 rays");
-  MAP_TRY(map_check_side(device_in, "device_in"));
-  MAP_TRY(map_check_side(device_out, "device_out"));
-  if (device_in) MAP_TRY(map_check_aligned((uintptr_t)rays, 16, "the device rays are"));
-  if (device_out) MAP_TRY(map_check_aligned((uintptr_t)out | (uintptr_t)info, 16, "a device output is"));
+  TRY(map_check_side(device_in, "device_in"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_in) TRY(map_check_aligned((uintptr_t)rays, 16, "the device rays are"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)out | (uintptr_t)info, 16, "a device output is"));
   uint32_t max_steps = 0;
   if (const char* why = ray_params_check(prm, &max_steps)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_cast_rays: ") + why);
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
-  MAP_TRY(ray_reserve(m, 0, device_out ? 0 : sizeof(revo_map_ray_hit) * n));
-  MapScratch up;  // freed after the wait below
+  TRY(ray_reserve(m, 0, device_out ? 0 : sizeof(revo_map_ray_hit) * n));
+  DevScratch up;  // freed after the wait below
   const float4* d_rays = (const float4*)rays;
   if (!device_in) {
-    MAP_TRY(up.alloc(sizeof(revo_map_ray) * n));
+    TRY(up.alloc(sizeof(revo_map_ray) * n));
     HIPCHECK(hipMemcpyAsync(up.p, rays, sizeof(revo_map_ray) * n, hipMemcpyHostToDevice, s));
     d_rays = (const float4*)up.p;
   }
@@ -491,7 +491,7 @@ extern "C" int revo_map_cast_rays(revo_map* m, size_t n, const revo_map_ray* ray
   { const int rc = ray_begin(m, &a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0); if (rc) { (void)hipStreamSynchronize(s); return rc; } }
   hipLaunchKernelGGL(k_map_cast_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, d_rays, (unsigned)n, d_out);
   if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); return fail(REVO_ERR_HIP, "k_map_cast_rays: the launch failed"); }
-  MAP_TRY(m->ray_time.end(s));
+  TRY(m->ray_time.end(s));
   if (!device_out) {
     HIPCHECK(hipMemcpyAsync(out, d_out, sizeof(revo_map_ray_hit) * n, hipMemcpyDeviceToHost, s));
     if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_ray_info), hipMemcpyDeviceToHost, s));

@@ -1,4 +1,4 @@
-// revo_mat4.h -- column-major 4x4 float helpers shared by the host code (revo_host.hip, revo_vo.hip, revo_vo_multi.hip).
+// revo_mat4.h -- column-major 4x4 float helpers shared by the host code (the units over revo_host_impl.h, revo_vo.hip, revo_vo_multi.hip).
 // Eigen semantics: Matrix4f::inverse() is the general cofactor inverse in float (tracker.cpp:142,
 // imgpyramidrgbd.h:129), products accumulate left to right.
 #pragma once

@@ -1,4 +1,4 @@
-// revo_multi.h -- the device half of revo_vo_multi (revo_host.hip) as seen by its host-side sequencing (revo_vo_multi.hip).
+// revo_multi.h -- the device half of revo_vo_multi (revo_mdev.hip) as seen by its host-side sequencing (revo_vo_multi.hip).
 // Internal: not part of the C ABI.  A "set" is one FrameSet of n_streams frames built by one submit; frames are addressed
 // as (set, frame index inside the set).
 #pragma once

@@ -272,7 +272,7 @@ extern "C" int revo_pipeline_submit(revo_pipeline* p, const uint8_t* d_bgr, cons
     if (o.ticket && !o.done_recorded && o.trk == trk) { int rc = finalize_slot(p, o); if (rc) return rc; }
   { int rc = harvest_timing(p, sl); if (rc) return rc; }
   if (input_ready_event) HIPCHECK(hipStreamWaitEvent(p->s_build, (hipEvent_t)input_ready_event, 0));
-  // (the batch's build orders itself behind the batch's previous tracker grid and deferred work: revo_host.hip)
+  // (the batch's build orders itself behind the batch's previous tracker grid and deferred work: revo_batch.hip)
   int rc;
   if (depth_kind == 2) {
     rc = revo_batch_build_u16(sl.batch, d_bgr, (const uint16_t*)d_depth, depth_scale_factor, p->s_build);

@@ -208,7 +208,7 @@ extern "C" int revo_vo_track_next(revo_vo* v, float pose_out[16], int* new_kf_ou
   M4 currPoseInWorld = mul(v->kf.T_w_f, T_KF_N);
   int nvote = -1;
   unsigned vseq = 0;
-  // The vote has a stream of its own (revo_host.hip, vote_stream): the look-ahead tracker goes out FIRST, so that it starts one
+  // The vote has a stream of its own (revo_single.hip, vote_stream): the look-ahead tracker goes out FIRST, so that it starts one
   // host hop behind the tracker that just finished instead of behind the vote's two launches as well.
   // (the previous vote was close to a keyframe change and this frame's vote counts -- the one right behind a new keyframe is
   // ignored, system.cpp:203: hold the look-ahead until the vote is in)

@@ -1,7 +1,7 @@
 // revo_vo_multi.hip -- many independent REVO::start streams (system/system.cpp:84-305) advanced in lockstep.
 // Host-only code: per stream the state of revo_vo.hip (keyframe, previous frame, the last two poses, the constant-velocity
 // initialisation); the device work of a step -- one tracker grid, one quality vote, one cloud copy, the keyframe promotions --
-// is what revo_mdev_* (revo_host.hip) enqueue for all streams at once.  No look-ahead: a step waits for its grid and its vote.
+// is what revo_mdev_* (revo_mdev.hip) enqueue for all streams at once.  No look-ahead: a step waits for its grid and its vote.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

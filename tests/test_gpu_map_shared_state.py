@@ -1,5 +1,5 @@
 """The buffers, descriptor staging and timing events that revo_map_render and revo_map_raycast share a type for
-(revo_map_impl.h: MapBuf, MapRows, MapTimer) on ONE handle, features interleaved and view counts growing and shrinking: every
+(revo_internal.h: DevBuf, HostRows, EventTimer) on ONE handle, features interleaved and view counts growing and shrinking: every
 output is byte for byte what the same call gives alone on a fresh handle holding the same records, each *_last_ms call answers
 once its own feature has run and refuses before.  Hand-made map (about 480 voxels in a 1 024-slot table), 64 x 48 views."""
 import ctypes as C
