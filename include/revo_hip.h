@@ -1207,6 +1207,70 @@ int revo_map_df_sample(revo_map* m, const revo_map_df_box* box, const uint32_t* 
  * (HIP events on the tracker stream), in milliseconds.  REVO_ERR_INVALID_ARG if m has built no field yet. */
 int revo_map_distance_field_last_ms(revo_map* m, float* ms);
 
+/* ---- registration against the distance field ----------------------------------------------------------
+ * revo_map_align and revo_map_align_plane match a source voxel among the 27 destination voxels around it, so a pose more
+ * than about a voxel off finds no or wrong matches, and their source must be a map.  Here the residual of a source POINT
+ * under a pose is the field's value at the moved point, read by trilinear interpolation of sqrt(d2) between cell centres,
+ * and its gradient the exact derivative of that interpolant: no neighbour search, any point set as the source, and a basin
+ * as wide as the box the field was built over.
+ *
+ * The record of one pose.  m, box, d2, device_field: revo_map_df_sample's field arguments with its rules; m gives the voxel
+ * edge v, the context and the stream.  Per point p (xyz: npts packed float[3], source frame) and pose (R column-major, t),
+ * float32 with every operation rounded on its own (/ and sqrtf correctly rounded, no fused multiply-add):
+ *   p'_i = ((R_i0*px + R_i1*py) + R_i2*pz) + t_i;
+ *   per axis  g_i = p'_i / v - 0.5f,  f_i = floorf(g_i),  w_i = g_i - f_i,  a_i = f_i - (float)lo_i;
+ *   the point is SKIPPED (and counted) unless every p'_i and g_i is finite and 0 <= a_i <= (float)(n_i - 2) on every axis
+ *         (compared in float before the conversion; an axis of one cell skips every point), or if any of the 8 cells
+ *         a + {0,1}^3 holds REVO_DF_NONE;
+ *   s_abc = sqrtf((float)d2[a + (a,b,c)]);  lerp(x0, x1, w) = x0 + w*(x1 - x0)  (one subtraction, product, addition);
+ *   along z:  m_ab = lerp(s_ab0, s_ab1, w_z),  dz_ab = s_ab1 - s_ab0;
+ *   along y:  l_a = lerp(m_a0, m_a1, w_y),  h_a = m_a1 - m_a0,  k_a = lerp(dz_a0, dz_a1, w_y);
+ *   along x:  c = lerp(l_0, l_1, w_x),  gx = l_1 - l_0,  gy = lerp(h_0, h_1, w_x),  gz = lerp(k_0, k_1, w_x);
+ *   e = c*v, the residual in metres; (gx, gy, gz) its dimensionless gradient, the exact derivative of the interpolant;
+ *   the point is accepted iff e <= max_dist (inclusive), otherwise GATED (the gated count is considered - matched - skipped).
+ * Per accepted point, with u = p' - centre:
+ *   a  = u x g:  ax = uy*gz - uz*gy,  ay = uz*gx - ux*gz,  az = ux*gy - uy*gx  (two products and one subtraction each);
+ *   J  = (gx, gy, gz, ax, ay, az);
+ *   S[0..20]  J_i*J_j for i <= j, row by row (00 01 .. 05 11 .. 55);  S[21..26]  J_i*e;  S[27]  e*e  (one product each).
+ * Each S is the float nearest the exact sum of its float terms (double-double from the first addition, rounded once;
+ * DESIGN 4.1's midpoint caveat applies).  The counts are exact. */
+typedef struct revo_map_df_align_info {   /* 208 bytes, little-endian, no padding holes */
+  float    S[28];
+  uint64_t matched;      /* accepted points                                                                           */
+  uint64_t considered;   /* npts                                                                                      */
+  uint64_t skipped;      /* points outside the interpolation cells of the box, not finite, or next to REVO_DF_NONE    */
+  float    centre[3], max_dist;  /* copied from the parameters                                                        */
+  float    R[9], T[3];   /* the pose the sums were taken at (source -> field frame, R column-major), as given         */
+  int32_t  flags;        /* bit0 as revo_map_align_info's: everything else is then zero except pose, centre, max_dist */
+  int32_t  reserved;     /* zero */
+} revo_map_df_align_info;
+
+/* One record per pose (nposes 1 .. 65535, 4x4 column-major, source -> field frame), all poses in ONE launch on m's
+ * context's tracker stream.  npts: 1 .. 2^24.  prm: max_dist finite and > 0 (no upper bound: the field decides how far a
+ * point may lie), centre finite as in revo_map_align; min_count_dst and min_count_src must be 0.  device_in / device_out:
+ * where xyz and out live (device pointers 16-byte aligned); a host field or host points are uploaded to temporary buffers.
+ * The call only enqueues when field, points and output are all on the device, and waits otherwise (revo_map_df_sample's
+ * rule).  The map is not read or changed.  A point that is not finite is no argument error: it is skipped.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: a NULL pointer; npts or nposes out of range;
+ * the box rules of revo_map_distance_field; a flag outside 0 / 1; a misaligned device pointer; a max_dist or centre that is
+ * not finite, or max_dist <= 0; a min_count field that is not 0. */
+int revo_map_df_align_eval(revo_map* m, const revo_map_df_box* box, const uint32_t* d2, int device_field, size_t npts,
+                           const float* xyz, int device_in, int nposes, const float* T_dst_src_n16,
+                           const revo_map_align_params* prm, revo_map_df_align_info* out, int device_out);
+
+/* Host only.  revo_map_align_plane_system's arithmetic with g in the normal's place: e(x) ~ e + g.v + w.(u x g) = e + J.x,
+ * H = sum J J^T from its upper triangle S[0..20], g = S[21..26], cost = S[27].  REVO_ERR_INVALID_ARG: NULL, or flags bit0. */
+int revo_map_df_align_system(const revo_map_df_align_info* info, double H[36], double g[6]);
+
+/* revo_map_align's Gauss-Newton loop over revo_map_df_align_eval's records: the same options, Cholesky and pivot rule,
+ * update T <- Tr(c) exp(x) Tr(-c) T, stopping rule and statuses; info_out from one more evaluation.  A host field and host
+ * points are uploaded once per call.  The call waits.  REVO_ERR_INVALID_ARG: as revo_map_df_align_eval, a T_init that is
+ * not finite, max_iters < 1. */
+int revo_map_df_align(revo_map* m, const revo_map_df_box* box, const uint32_t* d2, int device_field, size_t npts,
+                      const float* xyz, int device_in, const float T_init[16], const revo_map_align_params* prm,
+                      const revo_map_align_opts* opt, float T_out[16], revo_map_df_align_info* info_out, int32_t* iterations,
+                      int32_t* status);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -170,6 +170,11 @@ def lib():
     L.revo_map_bounds.argtypes = [vp, C.c_uint32, i32p, i32p, C.POINTER(C.c_size_t)]
     L.revo_map_df_sample.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_int]
     L.revo_map_distance_field_last_ms.argtypes = [vp, f32p]
+    L.revo_map_df_align_eval.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, f32p, C.POINTER(MapAlignParams),
+                                         vp, C.c_int]
+    L.revo_map_df_align_system.argtypes = [C.POINTER(MapDfAlignInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.revo_map_df_align.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_size_t, vp, C.c_int, f32p, C.POINTER(MapAlignParams),
+                                    C.POINTER(MapAlignOpts), f32p, C.POINTER(MapDfAlignInfo), i32p, i32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -903,6 +903,87 @@ class VoxelMap:
         if wait:
             self.sync()
 
+    # -- registration against a distance field (revo_map_df_align_eval / revo_map_df_align)
+    def _df_align_args(self, d2, lo, points, max_dist, centre, T_first):
+        """(box, field pointer, its side, points pointer, their side, n, params, what keeps the memory alive) of a call: d2 and
+        points are numpy arrays or, as sample_into takes them, contiguous torch device tensors (then the current stream is
+        waited for).  centre None: the mean of the points under T_first in float64, rounded to float32."""
+        keep = []
+        on_device = False
+        if hasattr(d2, "data_ptr"):
+            if d2.dim() != 3 or d2.element_size() != 4 or d2.is_floating_point() or not (d2.is_contiguous() and d2.is_cuda):
+                raise ValueError("a device field must be a contiguous 3-D tensor of 32-bit integers")
+            shape, fp, fdev, on_device = tuple(d2.shape), vp(d2.data_ptr()), 1, True
+        else:
+            d2 = np.ascontiguousarray(d2, np.uint32)
+            if d2.ndim != 3:
+                raise ValueError("the field is a 3-D array")
+            shape, fp, fdev = d2.shape, d2.ctypes.data_as(vp), 0
+        keep.append(d2)
+        if hasattr(points, "data_ptr"):
+            if points.dim() != 2 or points.shape[1] != 3 or str(points.dtype) != "torch.float32" or not (points.is_contiguous() and points.is_cuda):
+                raise ValueError("device points must be a contiguous [N, 3] float32 tensor")
+            n, pp, pdev, on_device = int(points.shape[0]), vp(points.data_ptr()), 1, True
+            mean = points.double().mean(0).cpu().numpy() if n else np.zeros(3)
+        else:
+            points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+            n, pp, pdev = len(points), points.ctypes.data_as(vp), 0
+            mean = points.astype(np.float64).mean(0) if n else np.zeros(3)
+        keep.append(points)
+        if n < 1:
+            raise ValueError("no points to register")
+        if centre is None:
+            T = np.asarray(T_first, np.float32).astype(np.float64)
+            centre = (T[:3, :3] @ mean + T[:3, 3]).astype(np.float32)
+        p = MapAlignParams()
+        p.max_dist, p.min_count_dst, p.min_count_src = float(max_dist), 0, 0
+        p.centre[:] = [float(x) for x in np.asarray(centre, np.float32).reshape(3)]
+        if on_device:
+            import torch
+            torch.cuda.current_stream("cuda:%d" % self.cameraPyr.device).synchronize()  # the inputs are written
+        return self._df_box(lo, shape, 0, 1), fp, fdev, pp, pdev, n, p, keep
+
+    def df_align_eval(self, d2, lo, points, poses, max_dist, centre=None, d_out=None):
+        """The registration sums of `points` ([N, 3] float32, source frame) against the distance field d2 of the box at lo
+        (a field of a map with this map's voxel edge) at each pose (4x4 source -> field frame; one pose or [n, 4, 4]):
+        MapDfAlignInfo records, all from one launch (revo_map_df_align_eval).  centre defaults to the mean of the points under
+        the first pose.  d_out: a torch uint8 device tensor of n x 208 bytes takes the records instead (returns None; with
+        a device field and device points the call only enqueues: sync() orders later reads)."""
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        T = T.reshape(-1, 4, 4)
+        n = len(T)
+        flat = np.ascontiguousarray(np.concatenate([_cm4(M) for M in T]))
+        box, fp, fdev, pp, pdev, npts, p, keep = self._df_align_args(d2, lo, points, max_dist, centre, T[0])
+        if d_out is not None:
+            if not (d_out.is_cuda and d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= n * C.sizeof(MapDfAlignInfo)):
+                raise ValueError("d_out must be a contiguous device tensor of n x %d bytes" % C.sizeof(MapDfAlignInfo))
+            import torch
+            torch.cuda.current_stream(d_out.device).synchronize()
+            check(_lib.lib().revo_map_df_align_eval(self._h, C.byref(box), fp, fdev, npts, pp, pdev, n, _p(flat, f32p), C.byref(p),
+                                                    vp(d_out.data_ptr()), 1))
+            return None
+        out = (MapDfAlignInfo * n)()
+        check(_lib.lib().revo_map_df_align_eval(self._h, C.byref(box), fp, fdev, npts, pp, pdev, n, _p(flat, f32p), C.byref(p),
+                                                C.cast(out, vp), 0))
+        return out[0] if single else list(out)
+
+    def df_align(self, d2, lo, points, T_init=None, max_dist=None, centre=None, max_iters=30, eps_t=1e-6, eps_r=1e-6, min_matched=12):
+        """Gauss-Newton of `points` onto the distance field from T_init (identity by default) over df_align_eval's records
+        (revo_map_df_align): align()'s loop, options and statuses.  max_dist defaults to 8 voxels.  -> dict: T, info (the
+        MapDfAlignInfo at T), iterations, status, cov = sigma2 H^-1 with sigma2 = S[27] / (matched - 6), sigma2, centre."""
+        T0 = np.eye(4, dtype=np.float32) if T_init is None else np.asarray(T_init, np.float32).reshape(4, 4)
+        max_dist = 8.0 * self.voxel if max_dist is None else max_dist
+        box, fp, fdev, pp, pdev, npts, p, keep = self._df_align_args(d2, lo, points, max_dist, centre, T0)
+        o = MapAlignOpts(int(max_iters), 0, float(eps_t), float(eps_r), int(min_matched))
+        T1 = np.zeros(16, np.float32)
+        info, it, st = MapDfAlignInfo(), C.c_int32(), C.c_int32()
+        check(_lib.lib().revo_map_df_align(self._h, C.byref(box), fp, fdev, npts, pp, pdev, _p(_cm4(T0), f32p), C.byref(p), C.byref(o),
+                                           _p(T1, f32p), C.byref(info), C.byref(it), C.byref(st)))
+        cov, s2 = df_align_covariance(info)
+        return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2,
+                "centre": np.array(list(p.centre), np.float32)}
+
     def last_distance_field_ms(self):
         """Device time of the last distance_field / distance_field_into call (HIP events), in milliseconds; waits for it."""
         ms = C.c_float()
@@ -953,6 +1034,38 @@ class DistanceField:
         if self._map is not None and getattr(self._map, "_h", None):
             return self._map.df_sample(self, points)
         return mapfile.df_sample(self.d2, self.lo, self.voxel, points)
+
+    def _live(self):
+        return self._map is not None and bool(getattr(self._map, "_h", None))
+
+    def align_eval(self, points, poses, max_dist, centre=None):
+        """The registration sums of `points` ([N, 3] float32 or a torch device tensor, source frame) against this field at
+        each pose (4x4 source -> field frame, or [n, 4, 4]) -> MapDfAlignInfo records: on the device of the map the
+        field came from, and through mapfile.df_align_records -- the same bytes -- for a loaded field or a closed map."""
+        if self._live():
+            return self._map.df_align_eval(self.d2, self.lo, points, poses, max_dist, centre)
+        from . import mapfile
+        T = np.asarray(poses, np.float32)
+        if centre is None:
+            centre = mapfile.df_align_centre(points, T.reshape(-1, 4, 4)[0])
+        rec = mapfile.df_align_records(self.d2, self.lo, self.n, self.voxel, points, T, max_dist, centre)
+        out = [MapDfAlignInfo.from_buffer_copy(r.tobytes()) for r in rec]
+        return out[0] if T.ndim == 2 else out
+
+    def align(self, points, T_init=None, max_dist=None, centre=None, **opts):
+        """Registers `points` against this field from T_init (VoxelMap.df_align; opts: max_iters, eps_t, eps_r, min_matched)
+        -> dict: T, info, iterations, status, cov, sigma2, centre.  Without a live map: mapfile.df_align, the same loop."""
+        if self._live():
+            return self._map.df_align(self.d2, self.lo, points, T_init, max_dist, centre, **opts)
+        from . import mapfile
+        T0 = np.eye(4, dtype=np.float32) if T_init is None else np.asarray(T_init, np.float32).reshape(4, 4)
+        if centre is None:
+            centre = mapfile.df_align_centre(points, T0)
+        max_dist = 8.0 * self.voxel if max_dist is None else max_dist
+        T, rec, it, st = mapfile.df_align(self.d2, self.lo, self.n, self.voxel, points, T0, max_dist, centre, **opts)
+        info = MapDfAlignInfo.from_buffer_copy(rec.tobytes())
+        cov, s2 = df_align_covariance(info)
+        return {"T": T, "info": info, "iterations": it, "status": st, "cov": cov, "sigma2": s2, "centre": np.asarray(centre, np.float32)}
 
     def save(self, path):
         """The .npz `python -m revo_amd.mapfile esdf` writes: d2, lo, n, voxel."""
@@ -1007,6 +1120,27 @@ def align_plane_covariance(info):
     return s2 * 0.5 * (X + X.T), s2
 
 
+def df_align_system(info):
+    """(H [6, 6], g [6]) float64 of a MapDfAlignInfo: the Gauss-Newton system of revo_map_df_align_system (unknowns v, w)."""
+    H, g = np.zeros(36, np.float64), np.zeros(6, np.float64)
+    check(_lib.lib().revo_map_df_align_system(C.byref(info), _p(H, C.POINTER(C.c_double)), _p(g, C.POINTER(C.c_double))))
+    return H.reshape(6, 6), g
+
+
+def df_align_covariance(info):
+    """(cov [6, 6] = sigma2 H^-1, sigma2 = S[27] / (matched - 6)) of a distance-field record (one residual per point);
+    (None, None) without an evaluation, with too few points or with a singular H."""
+    if (info.flags & 1) or info.matched <= 6:
+        return None, None
+    H, _ = df_align_system(info)
+    s2 = float(info.S[27]) / float(info.matched - 6)
+    try:
+        X = np.linalg.inv(H)
+    except np.linalg.LinAlgError:
+        return None, None
+    return s2 * 0.5 * (X + X.T), s2
+
+
 def align_maps(dst, src, T_init=None, shifts=(2, 1, 0), centre=None, min_count_dst=1, min_count_src=1, metric="point", **align_kw):
     """Coarse-to-fine registration of `src` onto `dst` (two VoxelMaps of the same voxel edge): per level of `shifts` both maps
     are coarsened by that shift (0: the maps themselves), aligned with max_dist = that level's edge, and the pose is handed
@@ -1043,6 +1177,46 @@ def align_merge(dst, src, T_init=None, metric="plane", accept_limit=False, min_c
         raise RuntimeError("align_merge: the registration %s (nothing merged)"
                            % ("stopped at its iteration limit" if r["status"] == ALIGN_ITER_LIMIT else "was lost"))
     return dict(r, pose_info=dst.merge_posed(src, r["T"], min_count))
+
+
+def localize(dst, source, T_init=None, max_dist=None, pad=None, refine="plane", min_count=1, **opts):
+    """Registers `source` onto the map `dst` from a start that may lie many voxels off: the distance field of
+    dst is built on the device over dst.bounds() grown by `pad` cells (default ceil(max_dist / voxel) + 2), the source's points
+    are registered against it (VoxelMap.df_align; opts are its options), and, when source is a map and refine is "plane" or
+    "point", the pose found is handed to dst.align_plane / dst.align with max_dist = the voxel edge.
+    source: an [N, 3] array of points, a VoxelMap (its points()) or a keyframe pyramid (the xyz of its level-0
+    generateColoredPcl, dense as dst is).  max_dist (metres) defaults to 8 voxels.
+    -> the last stage's result, with "stages": [("field", result), ("plane" | "point", result)] and "box": (lo, n)."""
+    import math
+    import torch
+    from . import mapfile
+    if refine not in ("plane", "point", None):
+        raise ValueError("refine must be 'plane', 'point' or None")
+    m = dst.map if isinstance(dst, MapWindow) else dst
+    src_map = source.map if isinstance(source, MapWindow) else (source if isinstance(source, VoxelMap) else None)
+    if src_map is not None:
+        pts = src_map.points(min_count)[0]
+    elif isinstance(source, ImgPyramidRGBD):
+        pts = np.ascontiguousarray(source.generateColoredPcl(0, m.dense)[:, :3])
+    else:
+        pts = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3))
+    max_dist = 8.0 * m.voxel if max_dist is None else float(max_dist)
+    pad = int(math.ceil(float(np.float32(max_dist) / np.float32(m.voxel)))) + 2 if pad is None else int(pad)  # the ratio in float32: 0.24 / 0.02 is 12
+    lo, hi, n_solid = m.bounds(min_count)
+    if n_solid == 0:
+        raise ValueError("localize: the destination map holds no voxel")
+    lo, n = mapfile.padded_box(lo, hi, pad)
+    dev = "cuda:%d" % m.cameraPyr.device
+    d_d2 = torch.empty(tuple(int(x) for x in n), dtype=torch.int32, device=dev)
+    m.distance_field_into(d_d2, lo, n, min_count=min_count, wait=False)
+    d_pts = torch.from_numpy(pts).to(dev)
+    stages = [("field", m.df_align(d_d2, lo, d_pts, T_init, max_dist, **opts))]
+    if src_map is not None and refine is not None:
+        r = stages[0][1]
+        fine = (m.align_plane if refine == "plane" else m.align)(src_map, r["T"], max_dist=m.voxel, min_count_dst=min_count,
+                                                                   min_count_src=min_count, centre=r["centre"])
+        stages.append((refine, dict(fine, centre=r["centre"])))
+    return dict(stages[-1][1], stages=stages, box=(np.asarray(lo, np.int32), np.asarray(n, np.int32)))
 
 
 class MapWindow:

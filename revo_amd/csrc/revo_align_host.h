@@ -104,7 +104,16 @@ inline void align_plane_system_fill(const revo_map_plane_info* info, double H[36
   for (int i = 0; i < 6; ++i) g[i] = (double)S[21 + i];
 }
 
-// The Gauss-Newton loop of revo_map_align and revo_map_align_plane over records of type Rec (flags, matched) and their system
+// revo_map_df_align_system's arithmetic: the record carries the same 28 sums, so it is align_plane_system_fill's
+inline void align_df_system_fill(const revo_map_df_align_info* info, double H[36], double g[6]) {
+  const float* S = info->S;
+  int k = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[i * 6 + j] = H[j * 6 + i] = (double)S[k]; ++k; }
+  for (int i = 0; i < 6; ++i) g[i] = (double)S[21 + i];
+}
+
+// The Gauss-Newton loop of revo_map_align, revo_map_align_plane and revo_map_df_align over records of type Rec (flags, matched) and their system
 // fill(const Rec*, H, g).  eval(T column-major float[16], Rec*) -> 0 or an error code, which ends the loop and is returned.
 template <class Rec, class Fill, class Eval>
 inline int align_loop_over(const float T_init[16], const float centre[3], const revo_map_align_opts& o, Fill&& fill, Eval&& eval,

@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -201,6 +201,7 @@ struct revo_map_stage {
 };
 struct MapViewK;    // revo_map_view.hip: one view of a render launch
 struct MapRayView;  // revo_map_view.hip: one view of a raycast launch
+struct MapDfPose;   // revo_map_df_align.hip: one pose of a registration launch
 
 struct revo_map {
   revo_ctx* ctx = nullptr;
@@ -231,6 +232,10 @@ struct revo_map {
   // device field of a host-output call, the call's events
   DevBuf dfbits, dfcnt, dfout;
   EventTimer df_time;
+  // revo_map_df_align_eval / revo_map_df_align (revo_map_df_align.hip): the poses of a launch, and its tickets, counts and
+  // published partials
+  HostRows<MapDfPose> dfa_poses;
+  DevBuf dfa_work;
 };
 
 // revo_map.hip, for the other units.  map_read_stats waits for the map's stream; map_grow(live_only) is the compaction an

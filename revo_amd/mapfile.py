@@ -27,6 +27,11 @@ Equal maps give equal files.
                                                         map A's distance field (revo_map_distance_field), without a GPU:
                                                         the squared distance in cells to the nearest voxel, over the map's bounds
                                                         grown by N cells (default 8); OUT.npz holds d2, lo, n, voxel
+    python -m revo_amd.mapfile df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt
+                                                        map SRC's points registered against map DST's distance field
+                                                        (revo_map_df_align), without a GPU: the pose SRC's frame ->
+                                                        DST's as a row-major 4x4; M in metres (default 8 voxels), N the cells the
+                                                        field reaches beyond DST's bounds (default ceil(M / voxel) + 2)
     python -m revo_amd.mapfile ply FILE [OUT.ply]      one coloured point per voxel, as map_<dataset>.ply
 """
 import struct
@@ -704,6 +709,239 @@ def df_sample(d2, lo, voxel, points):
     return out
 
 
+DF_ALIGN_DTYPE = np.dtype([("S", "<f4", (28,)), ("matched", "<u8"), ("considered", "<u8"), ("skipped", "<u8"), ("centre", "<f4", (3,)),
+                           ("max_dist", "<f4"), ("R", "<f4", (9,)), ("T", "<f4", (3,)), ("flags", "<i4"), ("reserved", "<i4")])
+ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_LOST = 0, 1, 2
+assert DF_ALIGN_DTYPE.itemsize == 208
+
+
+def sum_exact_f32(terms):
+    """The float32 nearest the exact sum of float32 terms, ties to even: what a record's S holds.  math.fsum gives the double
+    nearest the exact sum; only when that double is the midpoint of two adjacent floats can the second rounding go wrong, and
+    then rational arithmetic decides."""
+    import math
+    from fractions import Fraction
+    t = np.asarray(terms, np.float32).astype(np.float64).tolist()
+    d = math.fsum(t) + 0.0  # an empty or all-zero sum is +0
+    f = np.float32(d)
+    if float(f) == d or not math.isfinite(d):
+        return f
+    g = np.nextafter(f, np.float32(math.inf if d > float(f) else -math.inf))
+    if d != (float(f) + float(g)) / 2.0:
+        return f
+    exact, mid = sum((Fraction(x) for x in t), Fraction(0)), Fraction(d)
+    lo_, hi_ = (f, g) if float(f) < float(g) else (g, f)
+    if exact != mid:
+        return lo_ if exact < mid else hi_
+    return lo_ if (int(lo_.view(np.uint32)) & 1) == 0 else hi_
+
+
+def df_align_terms(d2, lo, voxel, points, T, max_dist, centre):
+    """The per-point part of revo_map_df_align_eval at one pose T (4x4 float32, finite, orthogonal), float32 with every
+    operation rounded on its own -> (the 28 float32 term arrays of the accepted points, matched, skipped)."""
+    F = np.float32
+    d2 = np.asarray(d2, np.uint32)
+    n = np.asarray(d2.shape, np.int64)
+    lo = np.asarray(lo, np.int64).reshape(3)
+    p = np.asarray(points, F).reshape(-1, 3)
+    T = np.asarray(T, F)
+    v, c = F(voxel), np.asarray(centre, F).reshape(3)
+    with np.errstate(all="ignore"):
+        pt = np.stack([((T[i, 0] * p[:, 0] + T[i, 1] * p[:, 1]) + T[i, 2] * p[:, 2]) + T[i, 3] for i in range(3)], 1).astype(F).reshape(-1, 3)
+        g = (pt / v - F(0.5)).astype(F)
+        f = np.floor(g)
+        w = (g - f).astype(F)
+        a = (f - lo.astype(F)).astype(F)
+        ok = np.all(np.isfinite(pt) & np.isfinite(g) & (a >= F(0)) & (a <= (n - 2).astype(F)), axis=1)
+    idx = np.flatnonzero(ok)
+    a, w, pt = a[idx].astype(np.int64), w[idx], pt[idx]
+    corner = {(i, j, k): d2[a[:, 0] + i, a[:, 1] + j, a[:, 2] + k] for i in (0, 1) for j in (0, 1) for k in (0, 1)}
+    some = np.zeros(len(idx), bool)
+    for q in corner.values():
+        some |= q == DF_NONE
+    keep = ~some
+    w, pt = w[keep], pt[keep]
+    s = {k: np.sqrt(q[keep].astype(F)) for k, q in corner.items()}
+    wx, wy, wz = w[:, 0], w[:, 1], w[:, 2]
+    lerp = lambda x0, x1, t: x0 + t * (x1 - x0)  # noqa: E731
+    m = {(i, j): lerp(s[i, j, 0], s[i, j, 1], wz) for i in (0, 1) for j in (0, 1)}
+    dz = {(i, j): s[i, j, 1] - s[i, j, 0] for i in (0, 1) for j in (0, 1)}
+    l_ = [lerp(m[i, 0], m[i, 1], wy) for i in (0, 1)]
+    h_ = [m[i, 1] - m[i, 0] for i in (0, 1)]
+    k_ = [lerp(dz[i, 0], dz[i, 1], wy) for i in (0, 1)]
+    cc = lerp(l_[0], l_[1], wx)
+    gx, gy, gz = l_[1] - l_[0], lerp(h_[0], h_[1], wx), lerp(k_[0], k_[1], wx)
+    e = cc * v
+    acc = e <= F(max_dist)
+    pt, e, gx, gy, gz = pt[acc], e[acc], gx[acc], gy[acc], gz[acc]
+    u = pt - c
+    ux, uy, uz = u[:, 0], u[:, 1], u[:, 2]
+    J = [gx, gy, gz, uy * gz - uz * gy, uz * gx - ux * gz, ux * gy - uy * gx]
+    terms = [J[i] * J[j] for i in range(6) for j in range(i, 6)] + [J[i] * e for i in range(6)] + [e * e]
+    assert all(t.dtype == F for t in terms)
+    return terms, int(acc.sum()), int(len(p) - len(keep) + some.sum())
+
+
+def df_align_records(d2, lo, n, voxel, points, poses, max_dist, centre):
+    """revo_map_df_align_eval restated: a DF_ALIGN_DTYPE array, one record per pose (4x4, or [N, 4, 4]), of the
+    points ([N, 3] float32, source frame) against the field d2 (uint32, shape n) of the box at lo with the edge `voxel`."""
+    F = np.float32
+    lo, n = check_box(lo, n)
+    d2 = np.asarray(d2, np.uint32).reshape(tuple(int(x) for x in n))
+    p = np.asarray(points, F).reshape(-1, 3)
+    md, c = F(max_dist), np.asarray(centre, F).reshape(3)
+    if not (np.isfinite(md) and md > 0) or not np.all(np.isfinite(c)):
+        raise ValueError("max_dist must be finite and > 0, the centre finite")
+    if not 1 <= len(p) <= 1 << 24:
+        raise ValueError("1 .. 2^24 points")
+    Ts = np.asarray(poses, F).reshape(-1, 4, 4)
+    out = np.zeros(len(Ts), DF_ALIGN_DTYPE)
+    for r, T in zip(out, Ts):
+        r["centre"], r["max_dist"] = c, md
+        r["R"], r["T"] = np.ascontiguousarray(T[:3, :3].T).reshape(9), T[:3, 3]  # column-major, as given (a NaN keeps its bits)
+        if not np.all(np.isfinite(T[:3, :4])) or not pose_is_orthogonal(T[:3, :3]):
+            r["flags"] = 1
+            continue
+        terms, matched, skipped = df_align_terms(d2, lo, voxel, p, T, md, c)
+        r["S"] = [sum_exact_f32(t) for t in terms]
+        r["matched"], r["considered"], r["skipped"] = matched, len(p), skipped
+    return out
+
+
+def df_align_system(rec):
+    """revo_map_df_align_system: (H [6, 6], g [6]) float64 of a record; H from its upper triangle S[0..20], g = S[21..26]."""
+    S = np.asarray(rec["S"], np.float64).reshape(28)
+    H = np.zeros((6, 6))
+    H[np.triu_indices(6)] = S[:21]
+    return H + np.triu(H, 1).T, S[21:27].copy()
+
+
+def _align_solve(H, g):
+    """H x = -g by the Cholesky factorisation and pivot rule of the library's registration loops (revo_align_host.h), in its
+    order of operations; None: rank-deficient."""
+    import math
+    L = [[0.0] * 6 for _ in range(6)]
+    H, g = [[float(x) for x in row] for row in H], [float(x) for x in g]
+    for j in range(6):
+        p = H[j][j]
+        for k in range(j):
+            p -= L[j][k] * L[j][k]
+        if not (p > 64.0 * 2.220446049250313e-16 * H[j][j]) or not math.isfinite(p):
+            return None
+        L[j][j] = math.sqrt(p)
+        for i in range(j + 1, 6):
+            v = H[i][j]
+            for k in range(j):
+                v -= L[i][k] * L[j][k]
+            L[i][j] = v / L[j][j]
+    y, x = [0.0] * 6, [0.0] * 6
+    for i in range(6):
+        v = -g[i]
+        for k in range(i):
+            v -= L[i][k] * y[k]
+        y[i] = v / L[i][i]
+    for i in range(5, -1, -1):
+        v = y[i]
+        for k in range(i + 1, 6):
+            v -= L[k][i] * x[k]
+        x[i] = v / L[i][i]
+    return x if all(math.isfinite(a) for a in x) else None
+
+
+def _mul4(A, B):
+    """Row-major 4 x 4 product, every entry summed over k in index order from 0.0 (mat4_mul of revo_align_host.h)."""
+    out = [[0.0] * 4 for _ in range(4)]
+    for i in range(4):
+        for j in range(4):
+            v = 0.0
+            for k in range(4):
+                v += A[i][k] * B[k][j]
+            out[i][j] = v
+    return out
+
+
+def _se3_exp(x):
+    """expm(hat(x)), x = (v, w), as revo_align_host.h forms it -> 4 x 4 nested lists."""
+    import math
+    v, w = x[:3], x[3:]
+    th = math.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+    W = [0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0]
+    W2 = [W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j] for i in range(3) for j in range(3)]
+    a, b, c, d = 1.0, 0.0, 0.5, 0.0
+    if not th < 1e-10:
+        a, b = math.sin(th) / th, (1.0 - math.cos(th)) / (th * th)
+        c, d = b, (th - math.sin(th)) / (th * th * th)
+    E = [[0.0] * 4 for _ in range(4)]
+    E[3][3] = 1.0
+    for i in range(3):
+        t = 0.0
+        for j in range(3):
+            eye = 1.0 if i == j else 0.0
+            E[i][j] = eye + a * W[3 * i + j] + b * W2[3 * i + j]
+            t += (eye + c * W[3 * i + j] + d * W2[3 * i + j]) * v[j]
+        E[i][3] = t
+    return E
+
+
+def df_align(d2, lo, n, voxel, points, T_init=None, max_dist=None, centre=None, max_iters=30, eps_t=1e-6, eps_r=1e-6, min_matched=12):
+    """revo_map_df_align restated: Gauss-Newton in double over df_align_records' records -> (T 4x4 float32, the record at T,
+    iterations, status).  centre defaults to the mean of the points under T_init, rounded to float32."""
+    F = np.float32
+    p = np.asarray(points, F).reshape(-1, 3)
+    T0 = np.eye(4, dtype=F) if T_init is None else np.asarray(T_init, F).reshape(4, 4)
+    if not np.all(np.isfinite(T0)):
+        raise ValueError("T_init is not finite")
+    if int(max_iters) < 1:
+        raise ValueError("max_iters must be >= 1")
+    if centre is None:
+        centre = df_align_centre(p, T0)
+    c = [float(x) for x in np.asarray(centre, F).reshape(3)]
+    Cp = [[1.0, 0.0, 0.0, c[0]], [0.0, 1.0, 0.0, c[1]], [0.0, 0.0, 1.0, c[2]], [0.0, 0.0, 0.0, 1.0]]
+    Cm = [[1.0, 0.0, 0.0, -c[0]], [0.0, 1.0, 0.0, -c[1]], [0.0, 0.0, 1.0, -c[2]], [0.0, 0.0, 0.0, 1.0]]
+    evaluate = lambda T: df_align_records(d2, lo, n, voxel, p, np.array(T, np.float64).astype(F), max_dist, centre)[0]  # noqa: E731
+    T = [[float(x) for x in row] for row in T0]
+    Tsys, status, it = T, ALIGN_ITER_LIMIT, 0
+    while it < int(max_iters):
+        rec = evaluate(T)
+        x = _align_solve(*df_align_system(rec)) if not (rec["flags"] & 1) and rec["matched"] >= min_matched else None
+        if x is None:
+            status, T = ALIGN_LOST, Tsys
+            break
+        it += 1
+        Tsys = T
+        T = _mul4(_mul4(_mul4(Cp, _se3_exp(x)), Cm), T)
+        if max(abs(a) for a in x[:3]) < eps_t and max(abs(a) for a in x[3:]) < eps_r:
+            status = ALIGN_CONVERGED
+            break
+    Tf = np.array(T, np.float64).astype(F)
+    return Tf, evaluate(Tf), it, status
+
+
+def df_align_centre(points, T_init):
+    """The default rotation centre: the mean of the points under T_init in float64, rounded to float32 (api.align_maps' rule)."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    T = np.asarray(T_init, np.float32).astype(np.float64)
+    return (T[:3, :3] @ p.mean(0) + T[:3, 3]).astype(np.float32) if len(p) else np.zeros(3, np.float32)
+
+
+def df_align_files(dst_path, src_path, T_init=None, max_dist=None, pad=None, min_count=1, **opts):
+    """`mapfile df-align`: the map of src_path (its voxels' points) registered against the distance field of dst_path's map,
+    built over its bounds grown by `pad` cells (default ceil(max_dist / voxel) + 2); max_dist defaults to 8 voxels.
+    -> (T, record, iterations, status)."""
+    import math
+    h, rec = read(dst_path)
+    _, src = read(src_path)
+    voxel = np.float32(h["voxel"])
+    max_dist = float(8 * voxel) if max_dist is None else float(max_dist)
+    pad = int(math.ceil(float(np.float32(max_dist) / voxel))) + 2 if pad is None else int(pad)  # the ratio in float32: 0.24 / 0.02 is 12
+    lo, hi, k = bounds_records(rec, min_count)
+    if k == 0 or len(src) == 0:
+        raise ValueError("df-align needs voxels in both maps")
+    lo, n = padded_box(lo, hi, pad)
+    d2, _ = distance_field_records(rec, lo, n, min_count)
+    return df_align(d2, lo, n, voxel, to_points(src, min_count)[0], T_init, max_dist, **opts)
+
+
 def write_field(path, d2, lo, voxel):
     """The .npz of a distance field: d2 (uint32 [n0, n1, n2]), lo, n (int32 [3]), voxel (float32)."""
     d2 = np.ascontiguousarray(d2, np.uint32)
@@ -884,6 +1122,26 @@ def main(argv=None):
                 print("%s: %d x %d x %d cells from %s (%s), %d voxels in the box, largest d2 %d"
                       % ((opt["-o"],) + d2.shape + (lo.tolist(), pos[0], info["solid"], info["max_d2"])))
                 return 0
+        if cmd == "df-align" and "-o" in args:
+            opt = {"-o": None, "--init": None, "--max-dist": None, "--pad": None}
+            pos, i = [], 0
+            while i < len(args):
+                if args[i] in opt and i + 1 < len(args):
+                    opt[args[i]] = args[i + 1]
+                    i += 2
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 2 and opt["-o"] is not None:
+                T, rec, it, status = df_align_files(pos[0], pos[1], None if opt["--init"] is None else read_pose(opt["--init"]),
+                                                    None if opt["--max-dist"] is None else float(opt["--max-dist"]),
+                                                    None if opt["--pad"] is None else int(opt["--pad"]))
+                with open(opt["-o"], "w") as f:
+                    f.write("".join(" ".join("%.9g" % x for x in row) + "\n" for row in T))
+                print("%s: %s after %d iterations, %d of %d points matched (%d skipped), rms residual %.4g m"
+                      % (opt["-o"], ("converged", "iteration limit", "lost")[status], it, rec["matched"], rec["considered"], rec["skipped"],
+                         float(np.sqrt(rec["S"][27] / max(int(rec["matched"]), 1)))))
+                return 0 if status != ALIGN_LOST else 1
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -897,7 +1155,8 @@ def main(argv=None):
     print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | coarsen A SHIFT -o OUT | "
           "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | carve A --views DIR -o OUT [--removed R] [--radius N] [--margin M] "
           "[--margin-rel F] [--min-views K] [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
-          "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] | ply FILE [OUT.ply]")
+          "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] | df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt | "
+          "ply FILE [OUT.ply]")
     return 2
 
 

@@ -305,6 +305,20 @@ class MapDfSample(C.Structure):
 assert (C.sizeof(MapDfBox), C.sizeof(MapDfInfo), C.sizeof(MapDfSample)) == (24, 64, 16)
 
 
+class MapDfAlignInfo(C.Structure):
+    """revo_map_df_align_info (include/revo_hip.h), 208 bytes: the 28 sums of registering a point set against a distance field
+    at a pose (the upper triangle of sum J J^T, sum J e, sum e e with J = (g, u x g), g the field's gradient), the exact counts
+    and the inputs.  The gated points are considered - matched - skipped."""
+    _fields_ = [
+        ("S", C.c_float * 28), ("matched", C.c_uint64), ("considered", C.c_uint64), ("skipped", C.c_uint64),
+        ("centre", C.c_float * 3), ("max_dist", C.c_float), ("R", C.c_float * 9), ("T", C.c_float * 3),
+        ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(MapDfAlignInfo) == 208
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
