@@ -1271,6 +1271,76 @@ int revo_map_df_align(revo_map* m, const revo_map_df_box* box, const uint32_t* d
                       const revo_map_align_opts* opt, float T_out[16], revo_map_df_align_info* info_out, int32_t* iterations,
                       int32_t* status);
 
+/* ---- planning through the map -------------------------------------------------------------------------
+ * The planner's own step: the clearance-aware cost-to-go from a set of goal cells to every cell of a field's box, and the
+ * paths that descend it.  A shortest-path cost over integer step weights has one value per cell, so it is a pure function of
+ * the field, the clearance and the seeds -- the same bytes on every run, whatever the launch.
+ *
+ * The grid: m, box, d2, device_field are revo_map_df_sample's field arguments with its box rules; m gives the context, the
+ * stream and the voxel edge and is neither read nor changed.  With r2 >= 1 the squared clearance in cells, a cell c is FREE
+ * iff d2[c] >= r2.  REVO_DF_NONE is therefore free (nothing in the box: infinite clearance); a solid cell (d2 = 0) never is.
+ * A field clamped below r2 has no free cell but its REVO_DF_NONE ones: build the field with clamp = 0 or clamp >= r2.
+ * The moves: from a free cell to any of its 26 neighbours inside the box that is free, at the weight 3, 4 or 5 for a step
+ * that changes 1, 2 or 3 coordinates (the 3-4-5 chamfer).  There is no corner rule: the clearance has inflated the obstacles.
+ * The seeds: n_seeds (1 .. 2^20) records in host memory, cell a voxel index (absolute, like box.lo), cost0 <= 2^24.  A seed
+ * outside the box is ignored and counted in seeds_outside, one on a cell that is not free in seeds_blocked, every other one
+ * in seeds_used (seeds_used + seeds_outside + seeds_blocked = n_seeds); seeds of one cell act as the one of smallest cost0.
+ * The cost: cost[c], in the field's own layout (ix*n[1] + iy)*n[2] + iz, is the minimum over the used seeds s and over all
+ * paths of moves from s's cell to c of cost0[s] + the weights; REVO_PLAN_NONE for a cell that is not free or that no seed
+ * reaches.  The largest finite value is below 2^24 + 5 * 2^27 < 2^30.  In a box that is all free the cost from one seed of
+ * cost0 = 0 at the offset (a >= b >= c >= 0), axes sorted, is 3a + b + c. */
+typedef struct revo_map_plan_seed {   /* 16 bytes */
+  int32_t cell[3];          /* voxel index x, y, z */
+  uint32_t cost0;           /* the cost at the seed, <= 2^24 */
+} revo_map_plan_seed;
+#define REVO_PLAN_NONE 0xFFFFFFFFu
+typedef struct revo_map_plan_info {   /* 64 bytes, little-endian, no padding: integer sums and maxima, so order-free */
+  uint64_t cells;           /* n[0]*n[1]*n[2] */
+  uint64_t free;            /* cells with d2 >= r2 */
+  uint64_t reachable;       /* cells with a cost other than REVO_PLAN_NONE */
+  uint64_t max_cost;        /* the largest of them; 0 if nothing is reachable */
+  uint64_t seeds_used, seeds_outside, seeds_blocked;
+  uint64_t reserved;        /* zero */
+} revo_map_plan_info;
+/* The cost field of `box` on the context's tracker stream: n[0]*n[1]*n[2] values into cost, the counters into info (may be
+ * NULL).  device_out: where cost and info live (1: device memory of the map's device, 16-byte aligned).  max_rounds: how
+ * many relaxation rounds may run (0: 65 536).  The call ALWAYS waits: the host decides when the fixed point is reached.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, d2, seeds or cost; the box rules
+ * of revo_map_distance_field; r2 = 0; n_seeds outside 1 .. 2^20; a cost0 above 2^24; a flag outside 0 / 1; a misaligned
+ * device pointer.  REVO_ERR_CAPACITY: the fixed point was not reached within max_rounds; the contents of cost are then
+ * unspecified (upper bounds in an internal encoding, or untouched host memory) and info is not written. */
+int revo_map_plan(revo_map* m, const revo_map_df_box* box, const uint32_t* d2, int device_field, uint32_t r2, size_t n_seeds,
+                  const revo_map_plan_seed* seeds, uint32_t max_rounds, uint32_t* cost, int device_out, revo_map_plan_info* info);
+/* Waits for the last revo_map_plan of m and gives its device time from the first kernel to the end of the last one (HIP
+ * events on the tracker stream, the host's waits between the groups of rounds included), in milliseconds, and the number of
+ * the last relaxation round in which a tile did work.  Both depend on the implementation, so they are not part of
+ * revo_map_plan_info.  Either pointer may be NULL, not both.  REVO_ERR_INVALID_ARG if m has planned nothing yet. */
+int revo_map_plan_last(revo_map* m, float* ms, uint32_t* rounds);
+
+enum { REVO_PLAN_REACHED = 0,     /* the path ends on a seed's cell */
+       REVO_PLAN_UNREACHABLE = 1, /* the start's cost is REVO_PLAN_NONE: length 0 */
+       REVO_PLAN_OUTSIDE = 2,     /* the start is not in the box: length 0, cost REVO_PLAN_NONE */
+       REVO_PLAN_TRUNCATED = 3    /* max_len cells were written before a seed was reached */ };
+typedef struct revo_map_plan_path {   /* 16 bytes per start */
+  uint32_t length;          /* cells written for this start */
+  uint32_t status;          /* REVO_PLAN_* */
+  uint32_t cost;            /* the start's cost */
+  uint32_t reserved;        /* zero */
+} revo_map_plan_path;
+/* Paths down a cost field (cost, device_cost: where it lives; a host field is uploaded to a temporary buffer): one per start
+ * (n_starts 1 .. 2^20, int32[3] voxel indices each, host memory), at most max_len (1 .. 2^20) cells each.  From cell c the
+ * next cell is the FIRST neighbour in the fixed order -- dx outermost, then dy, then dz, each -1, 0, 1, the cell itself
+ * skipped -- that lies inside the box and has cost[nb] != REVO_PLAN_NONE and cost[nb] + w == cost[c], w the move's weight;
+ * where there is none, c is a seed's cell and the path ends there.  cells_out[i][k] (int32[n_starts][max_len][3]) is the
+ * k-th cell of path i as an absolute voxel index, the start first; entries past length are not written.  No d2 is needed:
+ * the cost field says which cells are free.  device_out: where cells_out and path_out live (device pointers 16-byte
+ * aligned); with host outputs cells_out travels to the device and back, so that what the call does not write stays.  The
+ * call only enqueues when cost field and outputs are on the device, and waits otherwise.  REVO_ERR_INVALID_ARG, with
+ * nothing written: a NULL pointer; n_starts or max_len out of range; the box rules; a flag outside 0 / 1; a misaligned
+ * device pointer. */
+int revo_map_plan_paths(revo_map* m, const revo_map_df_box* box, const uint32_t* cost, int device_cost, size_t n_starts,
+                        const int32_t* starts, uint32_t max_len, int32_t* cells_out, revo_map_plan_path* path_out, int device_out);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

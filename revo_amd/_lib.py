@@ -175,6 +175,9 @@ def lib():
     L.revo_map_df_align_system.argtypes = [C.POINTER(MapDfAlignInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.revo_map_df_align.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_size_t, vp, C.c_int, f32p, C.POINTER(MapAlignParams),
                                     C.POINTER(MapAlignOpts), f32p, C.POINTER(MapDfAlignInfo), i32p, i32p]
+    L.revo_map_plan.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_uint32, C.c_size_t, vp, C.c_uint32, vp, C.c_int, vp]
+    L.revo_map_plan_last.argtypes = [vp, f32p, C.POINTER(C.c_uint32)]
+    L.revo_map_plan_paths.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_size_t, vp, C.c_uint32, vp, vp, C.c_int]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -849,7 +849,7 @@ class VoxelMap:
         d2 = np.empty(tuple(box.n), np.uint32)
         info = MapDfInfo()
         check(_lib.lib().revo_map_distance_field(self._h, C.byref(box), int(min_count), int(clamp), d2.ctypes.data_as(vp), 0, C.byref(info)))
-        return DistanceField(d2, np.array(list(box.lo), np.int32), self.voxel, self._df_info(info), self)
+        return DistanceField(d2, np.array(list(box.lo), np.int32), self.voxel, self._df_info(info), self, clamp=int(clamp))
 
     def distance_field_into(self, d_d2, lo, n, min_count=1, clamp=0, d_info=None, wait=True):
         """distance_field() into a torch device tensor: d_d2 of shape n with 32-bit integers, d_info None or a 64-byte tensor
@@ -984,6 +984,100 @@ class VoxelMap:
         return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2,
                 "centre": np.array(list(p.centre), np.float32)}
 
+    # -- planning through the map (revo_map_plan / revo_map_plan_paths)
+    @staticmethod
+    def _plan_seeds(seeds):
+        from . import mapfile
+        s = mapfile.plan_seeds(seeds)
+        rec = np.zeros(len(s), np.dtype([("cell", "<i4", (3,)), ("cost0", "<u4")]))
+        rec["cell"], rec["cost0"] = s[:, :3], s[:, 3]
+        assert rec.itemsize == C.sizeof(MapPlanSeed)
+        return rec
+
+    @staticmethod
+    def _plan_info(i):
+        from . import mapfile
+        return {k: int(getattr(i, k)) for k in mapfile.PLAN_INFO_KEYS}
+
+    def plan(self, field, seeds, r2, max_rounds=0):
+        """The clearance-aware cost-to-go over a DistanceField of a map with this map's voxel edge (revo_map_plan)
+        -> (cost uint32 [n0, n1, n2], info dict of mapfile.PLAN_INFO_KEYS).  A cell is free iff d2 >= r2; seeds: what
+        mapfile.plan_seeds takes as integers ([k, 3] cells or [k, 4] with cost0).  RevoError (REVO_ERR_CAPACITY) when the
+        relaxation has not settled within max_rounds (0: 65 536)."""
+        d2 = np.ascontiguousarray(field.d2, np.uint32)
+        box = self._df_box(field.lo, d2.shape, 0, 1)
+        rec = self._plan_seeds(seeds)
+        cost = np.empty(d2.shape, np.uint32)
+        info = MapPlanInfo()
+        check(_lib.lib().revo_map_plan(self._h, C.byref(box), d2.ctypes.data_as(vp), 0, int(r2), len(rec), rec.ctypes.data_as(vp), int(max_rounds),
+                                       cost.ctypes.data_as(vp), 0, C.byref(info)))
+        return cost, self._plan_info(info)
+
+    def plan_into(self, d_cost, d_d2, lo, n, seeds, r2, max_rounds=0, d_info=None):
+        """plan() between torch device tensors: d_d2 the field and d_cost the cost (32-bit integers of the box's shape n),
+        d_info None or a 64-byte tensor (revo_map_plan_info); contiguous, 16-byte aligned, on the map's device.  The call
+        waits: the host decides when the relaxation has settled."""
+        box = self._df_box(lo, n, 0, 1)
+        for t_ in (d_cost, d_d2):
+            if tuple(t_.shape) != tuple(box.n) or t_.element_size() != 4 or t_.is_floating_point():
+                raise ValueError("d_cost and d_d2 must be 32-bit integer tensors of the box's shape")
+        for t_ in (d_cost, d_d2, d_info):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("tensors must be contiguous device tensors")
+        if d_info is not None and d_info.numel() * d_info.element_size() != 64:
+            raise ValueError("d_info needs 64 bytes")
+        rec = self._plan_seeds(seeds)
+        import torch
+        torch.cuda.current_stream(d_cost.device).synchronize()  # the field is written, the outputs' earlier use is over
+        check(_lib.lib().revo_map_plan(self._h, C.byref(box), vp(d_d2.data_ptr()), 1, int(r2), len(rec), rec.ctypes.data_as(vp), int(max_rounds),
+                                       vp(d_cost.data_ptr()), 1, vp(d_info.data_ptr()) if d_info is not None else None))
+
+    def plan_paths(self, cost, lo, starts, max_len=4096):
+        """Paths down a cost field (revo_map_plan_paths) -> a list of (cells int32 [length, 3], status, cost) per start, what
+        mapfile.plan_paths gives.  cost: a uint32 [n0, n1, n2] array; starts: [k, 3] voxel indices."""
+        cost = np.ascontiguousarray(cost, np.uint32)
+        if cost.ndim != 3:
+            raise ValueError("the cost field is a 3-D array")
+        box = self._df_box(lo, cost.shape, 0, 1)
+        st = np.ascontiguousarray(np.asarray(starts, np.int64).reshape(-1, 3).astype(np.int32))
+        max_len = int(max_len)
+        if len(st) < 1 or max_len < 1 or len(st) * max_len > 1 << 26:
+            raise ValueError("at least one start and one cell, and at most 2^26 path cells per call")
+        cells = np.zeros((len(st), max_len, 3), np.int32)
+        rec = (MapPlanPath * len(st))()
+        check(_lib.lib().revo_map_plan_paths(self._h, C.byref(box), cost.ctypes.data_as(vp), 0, len(st), st.ctypes.data_as(vp), max_len,
+                                             cells.ctypes.data_as(vp), C.cast(rec, vp), 0))
+        return [(cells[i, :r.length].copy(), int(r.status), int(r.cost)) for i, r in enumerate(rec)]
+
+    def plan_paths_into(self, d_cells, d_paths, d_cost, lo, starts, max_len, wait=True):
+        """plan_paths() between torch device tensors: d_cost the cost field (32-bit integers, its shape is the box's n),
+        d_cells [k, max_len, 3] int32, d_paths k x 16 bytes (revo_map_plan_path: length, status, cost, 0); contiguous,
+        16-byte aligned, on the map's device.  starts: [k, 3] voxel indices in host memory.  Entries of d_cells past a
+        path's length are not written.  Enqueued on the context's tracker stream: wait=False returns at once."""
+        if d_cost.dim() != 3 or d_cost.element_size() != 4 or d_cost.is_floating_point():
+            raise ValueError("d_cost must be a 3-D tensor of 32-bit integers")
+        st = np.ascontiguousarray(np.asarray(starts, np.int64).reshape(-1, 3).astype(np.int32))
+        k, max_len = len(st), int(max_len)
+        if tuple(d_cells.shape) != (k, max_len, 3) or str(d_cells.dtype) != "torch.int32" or d_paths.numel() * d_paths.element_size() != 16 * k:
+            raise ValueError("d_cells must be [k, max_len, 3] int32 and d_paths k x 16 bytes")
+        for t_ in (d_cells, d_paths, d_cost):
+            if not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("tensors must be contiguous device tensors")
+        box = self._df_box(lo, tuple(d_cost.shape), 0, 1)
+        import torch
+        torch.cuda.current_stream(d_cost.device).synchronize()  # the cost field is written, the outputs' earlier use is over
+        check(_lib.lib().revo_map_plan_paths(self._h, C.byref(box), vp(d_cost.data_ptr()), 1, k, st.ctypes.data_as(vp), max_len,
+                                             vp(d_cells.data_ptr()), vp(d_paths.data_ptr()), 1))
+        if wait:
+            self.sync()
+
+    def last_plan(self):
+        """(ms, rounds) of the last plan / plan_into call: its device time (HIP events, the host's looks between the groups of
+        rounds included) and the last relaxation round in which a tile did work."""
+        ms, rounds = C.c_float(), C.c_uint32()
+        check(_lib.lib().revo_map_plan_last(self._h, C.byref(ms), C.byref(rounds)))
+        return ms.value, int(rounds.value)
+
     def last_distance_field_ms(self):
         """Device time of the last distance_field / distance_field_into call (HIP events), in milliseconds; waits for it."""
         ms = C.c_float()
@@ -1011,9 +1105,10 @@ class DistanceField:
     """A voxel map's distance field over a box of voxel indices (VoxelMap.distance_field, `mapfile esdf`): lo the
     box's first voxel index, n its cells per axis, voxel the map's edge in metres, d2 [n0, n1, n2] uint32 the squared distance
     in cells to the nearest voxel inside the box (settings.DF_NONE everywhere when there is none), info the call's counters
-    (mapfile.DF_INFO_KEYS; None for a loaded field)."""
+    (mapfile.DF_INFO_KEYS; None for a loaded field), clamp the clamp it was built with (0: none, or not known)."""
 
-    def __init__(self, d2, lo, voxel, info=None, map=None):
+    def __init__(self, d2, lo, voxel, info=None, map=None, clamp=0):
+        self.clamp = int(clamp)
         self.d2 = d2
         self.lo = np.asarray(lo, np.int32).reshape(3)
         self.n = np.asarray(d2.shape, np.int32)
@@ -1067,6 +1162,28 @@ class DistanceField:
         cov, s2 = df_align_covariance(info)
         return {"T": T, "info": info, "iterations": it, "status": st, "cov": cov, "sigma2": s2, "centre": np.asarray(centre, np.float32)}
 
+    def plan(self, goals, clearance=None, r2=None, max_rounds=0):
+        """The cost-to-go from `goals` to every cell that keeps a clearance from every surface -> CostField.
+        goals: [k, 3] integer voxel indices, [k, 4] with a cost0 (<= 2^24) per goal, or [k, 3] floating-point metres (the
+        cell floor(p / voxel)).  clearance: metres, r2 = max(1, ceil((clearance / voxel)^2)); or r2 itself, the squared
+        clearance in cells: a cell is free iff d2 >= r2.  A field built with a clamp below r2 is refused: it would have no
+        free cell.  On the device of the map the field came from, and through mapfile.plan_records -- the same bytes -- for
+        a loaded field or a closed map."""
+        from . import mapfile
+        if (clearance is None) == (r2 is None):
+            raise ValueError("give the clearance in metres or r2 in cells squared, not both")
+        r2 = mapfile.plan_r2(clearance, self.voxel) if r2 is None else int(r2)
+        if r2 < 1:
+            raise ValueError("r2 must be >= 1")
+        if 0 < self.clamp < r2:
+            raise ValueError("the field was built with clamp %d < r2 %d: no cell of it can be free; build it without a clamp" % (self.clamp, r2))
+        seeds = mapfile.plan_seeds(goals, self.voxel)
+        if self._live():
+            cost, info = self._map.plan(self, seeds, r2, max_rounds)
+        else:
+            cost, info = mapfile.plan_records(self.d2, self.lo, self.n, seeds, r2)
+        return CostField(cost, self.lo, self.voxel, r2, info, self._map)
+
     def save(self, path):
         """The .npz `python -m revo_amd.mapfile esdf` writes: d2, lo, n, voxel."""
         from . import mapfile
@@ -1076,6 +1193,62 @@ class DistanceField:
     def load(cls, path):
         from . import mapfile
         return cls(*mapfile.read_field(path))
+
+
+class CostField:
+    """A cost-to-go field over a box of voxel indices (DistanceField.plan, `mapfile plan --cost`): cost [n0, n1, n2]
+    uint32, the cheapest way to a goal over free cells in units of a third of a voxel edge per straight step (3, 4, 5 for a
+    step along 1, 2, 3 axes), settings.PLAN_NONE where a cell is not free or not reachable; lo, n the box, voxel the map's edge
+    in metres, r2 the squared clearance in cells, info the call's counters (mapfile.PLAN_INFO_KEYS; None for a loaded field)."""
+
+    def __init__(self, cost, lo, voxel, r2, info=None, map=None):
+        self.cost = cost
+        self.lo = np.asarray(lo, np.int32).reshape(3)
+        self.n = np.asarray(cost.shape, np.int32)
+        self.voxel = float(np.float32(voxel))
+        self.r2 = int(r2)
+        self.info = info
+        self._map = map
+
+    def reachable(self):
+        """[n0, n1, n2] bool: the cells a goal can be reached from."""
+        from . import mapfile
+        return self.cost != mapfile.PLAN_NONE
+
+    def metres(self):
+        """[n0, n1, n2] float32: cost * voxel / 3, +inf where there is none.  This is the length of the way in the 3-4-5
+        chamfer metric (a diagonal step counts 4/3 or 5/3 of an edge), up to 8 % above or 5 % below the Euclidean length of
+        the same way -- not the Euclidean length."""
+        with np.errstate(all="ignore"):
+            return np.where(self.reachable(), self.cost.astype(np.float32) * np.float32(self.voxel) / np.float32(3), np.float32(np.inf))
+
+    def path(self, starts, max_len=4096):
+        """The paths from `starts` ([k, 3] integer voxel indices, or floating-point metres) down the cost field -> a list of
+        (cells int32 [length, 3] absolute voxel indices from the start to a goal, status settings.PLAN_*, the start's cost):
+        on the device of the map the field came from, and through mapfile.plan_paths -- the same -- otherwise."""
+        from . import mapfile
+        st = np.asarray(starts)
+        if st.dtype.kind == "f":
+            st = np.floor(st.astype(np.float32).reshape(-1, 3) / np.float32(self.voxel))
+        st = st.astype(np.int64).reshape(-1, 3)
+        if self._map is not None and getattr(self._map, "_h", None):
+            return self._map.plan_paths(self.cost, self.lo, st, max_len)
+        return mapfile.plan_paths(self.cost, self.lo, self.n, st, max_len)
+
+    def path_points(self, starts, max_len=4096):
+        """path() with the cells as float32 metres at their centres."""
+        from . import mapfile
+        return [(mapfile.plan_path_points(c, self.voxel), st, cost) for c, st, cost in self.path(starts, max_len)]
+
+    def save(self, path):
+        """The .npz `python -m revo_amd.mapfile plan --cost` writes: cost, lo, n, voxel, r2."""
+        from . import mapfile
+        return mapfile.write_cost(path, self.cost, self.lo, self.voxel, self.r2)
+
+    @classmethod
+    def load(cls, path):
+        from . import mapfile
+        return cls(*mapfile.read_cost(path))
 
 
 def align_system(info):

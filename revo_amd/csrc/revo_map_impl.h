@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -236,6 +236,14 @@ struct revo_map {
   // published partials
   HostRows<MapDfPose> dfa_poses;
   DevBuf dfa_work;
+  // revo_map_plan / revo_map_plan_paths (revo_map_plan.hip): the head line and tile flags, the seeds or starts of a call, the
+  // device cost field of a host-output call, the pinned words the host reads between rounds behind the event, the call's events
+  // and the last round of the last call in which a tile ran
+  DevBuf planwork, planseeds, plancost;
+  PinnedMem<unsigned> plan_pin;
+  OwnedEvent plan_ev;
+  EventTimer plan_time;
+  uint32_t plan_rounds = 0;
 };
 
 // revo_map.hip, for the other units.  map_read_stats waits for the map's stream; map_grow(live_only) is the compaction an

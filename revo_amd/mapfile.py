@@ -942,6 +942,170 @@ def df_align_files(dst_path, src_path, T_init=None, max_dist=None, pad=None, min
     return df_align(d2, lo, n, voxel, to_points(src, min_count)[0], T_init, max_dist, **opts)
 
 
+# ---------------------------------------------------------------------------------- planning through the map --
+PLAN_NONE = np.uint32(0xFFFFFFFF)
+PLAN_INFO_KEYS = ("cells", "free", "reachable", "max_cost", "seeds_used", "seeds_outside", "seeds_blocked")
+PLAN_STATUS = ("reached", "unreachable", "outside", "truncated")
+PLAN_REACHED, PLAN_UNREACHABLE, PLAN_OUTSIDE, PLAN_TRUNCATED = 0, 1, 2, 3
+PLAN_MAX_SEEDS = PLAN_MAX_STARTS = PLAN_MAX_LEN = 1 << 20
+PLAN_MAX_COST0 = 1 << 24
+_PLAN_INF = np.int32(1 << 30)
+# the 26 moves in revo_map_plan_paths' order: dx outermost, then dy, then dz, each -1, 0, 1, the cell itself skipped
+PLAN_MOVES = tuple((dx, dy, dz) for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1) if (dx, dy, dz) != (0, 0, 0))
+
+
+def plan_r2(clearance, voxel):
+    """The squared clearance in cells of a clearance in metres: max(1, ceil((clearance / voxel)^2))."""
+    if not (np.isfinite(clearance) and clearance >= 0):
+        raise ValueError("the clearance must be finite and >= 0 metres")
+    return max(1, int(np.ceil((float(clearance) / float(np.float32(voxel))) ** 2)))
+
+
+def plan_seeds(seeds, voxel=None):
+    """[k, 4] int64 (cell x, y, z, cost0) of goals given as [k, 3] or [k, 4] integers (voxel indices, cost0 0 by default) or as
+    [k, 3] floating-point metres (floor(p / voxel), float32 like revo_map_df_sample)."""
+    s = np.asarray(seeds)
+    if s.ndim == 1:
+        s = s.reshape(1, -1)
+    if s.ndim != 2 or s.shape[1] not in (3, 4) or len(s) < 1 or len(s) > PLAN_MAX_SEEDS:
+        raise ValueError("goals are 1 .. 2^20 rows of 3 (a cell or a point) or 4 (a cell and its cost0) numbers")
+    if s.dtype.kind == "f":
+        if s.shape[1] != 3 or voxel is None or not np.isfinite(s).all():
+            raise ValueError("goals in metres are finite [k, 3] points of a field with a voxel edge")
+        s = np.floor(s.astype(np.float32) / np.float32(voxel)).astype(np.int64)
+    s = s.astype(np.int64)
+    if s.shape[1] == 3:
+        s = np.concatenate([s, np.zeros((len(s), 1), np.int64)], 1)
+    if np.any(s[:, 3] < 0) or np.any(s[:, 3] > PLAN_MAX_COST0):
+        raise ValueError("a goal's cost0 is 0 .. 2^24")
+    if np.any(np.abs(s[:, :3]) >= 1 << 31):
+        raise ValueError("a goal's cell does not fit 32 bits")
+    return s
+
+
+def plan_records(d2, lo, n, seeds, r2):
+    """revo_map_plan restated: (cost uint32 [n0, n1, n2], info dict of PLAN_INFO_KEYS).  A cell is free iff d2 >= r2; cost is
+    the cheapest way from a used seed over free cells by the 26 moves at the weights 3, 4, 5, plus the seed's cost0; PLAN_NONE
+    where a cell is not free or not reached.  Written as whole-array min-plus sweeps over the 26 moves until nothing changes."""
+    lo, n = check_box(lo, n)
+    d2 = np.asarray(d2, np.uint32)
+    if d2.shape != tuple(int(x) for x in n):
+        raise ValueError("the field's shape %s is not the box's %s" % (d2.shape, n.tolist()))
+    r2 = int(r2)
+    if r2 < 1 or r2 > 0xFFFFFFFF:
+        raise ValueError("r2 must be 1 .. 2^32 - 1")
+    s = plan_seeds(seeds)
+    free = d2 >= np.uint32(r2)
+    c = s[:, :3] - lo
+    inside = np.all((c >= 0) & (c < n), axis=1)
+    ci = c[inside]
+    on_free = free[ci[:, 0], ci[:, 1], ci[:, 2]]
+    # one halo cell on every side holds "not free": a move out of the box is a move onto a blocked cell
+    g = np.full(tuple(int(x) + 2 for x in n), _PLAN_INF, np.int32)
+    core = g[1:-1, 1:-1, 1:-1]
+    np.minimum.at(core, tuple(ci[on_free].T), s[inside][on_free, 3].astype(np.int32))
+    moves = [(m, 2 + sum(1 for x in m if x)) for m in PLAN_MOVES if all(x == 0 or n[a] > 1 for a, x in enumerate(m))]
+    changed = bool(on_free.any())
+    while changed:
+        changed = False
+        for (dx, dy, dz), w in moves:
+            nb = g[1 + dx:g.shape[0] - 1 + dx, 1 + dy:g.shape[1] - 1 + dy, 1 + dz:g.shape[2] - 1 + dz] + np.int32(w)
+            lower = free & (nb < core)
+            if lower.any():
+                core[lower] = nb[lower]
+                changed = True
+    reached = core < _PLAN_INF
+    cost = np.where(reached, core.astype(np.int64), np.int64(PLAN_NONE)).astype(np.uint32)
+    info = {"cells": int(cost.size), "free": int(free.sum()), "reachable": int(reached.sum()), "max_cost": int(core[reached].max()) if reached.any() else 0,
+            "seeds_used": int(on_free.sum()), "seeds_outside": int((~inside).sum()), "seeds_blocked": int((~on_free).sum())}
+    return cost, info
+
+
+def plan_paths(cost, lo, n, starts, max_len=4096):
+    """revo_map_plan_paths restated: a list of (cells int32 [length, 3] absolute voxel indices, status, cost) per start.  From a
+    cell the next one is the first of PLAN_MOVES inside the box with cost[nb] != PLAN_NONE and cost[nb] + w == cost[c]."""
+    lo, n = check_box(lo, n)
+    cost = np.asarray(cost, np.uint32)
+    if cost.shape != tuple(int(x) for x in n):
+        raise ValueError("the cost field's shape %s is not the box's %s" % (cost.shape, n.tolist()))
+    st = np.asarray(starts, np.int64).reshape(-1, 3)
+    max_len = int(max_len)
+    if len(st) < 1 or len(st) > PLAN_MAX_STARTS or max_len < 1 or max_len > PLAN_MAX_LEN:
+        raise ValueError("1 .. 2^20 starts and a max_len of 1 .. 2^20 cells")
+    c64 = cost.astype(np.int64)
+    none = int(PLAN_NONE)
+    out = []
+    for p in st:
+        c = p - lo
+        if np.any(c < 0) or np.any(c >= n):
+            out.append((np.zeros((0, 3), np.int32), PLAN_OUTSIDE, none))
+            continue
+        x, y, z = (int(v) for v in c)
+        v = int(c64[x, y, z])
+        if v == none:
+            out.append((np.zeros((0, 3), np.int32), PLAN_UNREACHABLE, none))
+            continue
+        cells, v0 = [], v
+        while True:
+            cells.append((x, y, z))
+            nxt = None
+            for dx, dy, dz in PLAN_MOVES:
+                ux, uy, uz = x + dx, y + dy, z + dz
+                if 0 <= ux < n[0] and 0 <= uy < n[1] and 0 <= uz < n[2]:
+                    u = int(c64[ux, uy, uz])
+                    if u != none and u + 2 + (dx != 0) + (dy != 0) + (dz != 0) == v:
+                        nxt = (ux, uy, uz, u)
+                        break
+            if nxt is None:
+                status = PLAN_REACHED
+                break
+            if len(cells) == max_len:
+                status = PLAN_TRUNCATED
+                break
+            x, y, z, v = nxt
+        out.append(((np.asarray(cells, np.int64) + lo).astype(np.int32), status, v0))
+    return out
+
+
+def plan_path_points(cells, voxel):
+    """[length, 3] float32 metres: the centres of a path's cells."""
+    return ((np.asarray(cells, np.float64).reshape(-1, 3) + 0.5) * float(np.float32(voxel))).astype(np.float32)
+
+
+def write_cost(path, cost, lo, voxel, r2):
+    """The .npz of a cost field: cost (uint32 [n0, n1, n2]), lo, n (int32 [3]), voxel (float32), r2 (uint32)."""
+    cost = np.ascontiguousarray(cost, np.uint32)
+    with open(path, "wb") as f:
+        np.savez(f, cost=cost, lo=np.asarray(lo, np.int32).reshape(3), n=np.asarray(cost.shape, np.int32), voxel=np.float32(voxel), r2=np.uint32(r2))
+    return path
+
+
+def read_cost(path):
+    """(cost, lo, voxel, r2) of a file write_cost wrote; ValueError if its arrays do not fit together."""
+    with np.load(path) as z:
+        if not all(k in z.files for k in ("cost", "lo", "n", "voxel", "r2")):
+            raise ValueError("%s is not a cost-field file (cost, lo, n, voxel, r2)" % path)
+        cost, lo, n, voxel, r2 = z["cost"], z["lo"], z["n"], z["voxel"], z["r2"]
+    if cost.dtype != np.uint32 or cost.ndim != 3 or lo.shape != (3,) or list(cost.shape) != [int(x) for x in n]:
+        raise ValueError("%s: a cost field is a 3-D uint32 array of the shape its n states" % path)
+    check_box(lo, n)
+    return cost, lo.astype(np.int32), float(np.float32(voxel)), int(r2)
+
+
+def plan_file(path, goals, starts, clearance, pad=None, max_len=1 << 20, min_count=1):
+    """Plans through the file's map: the distance field over its bounds grown by `pad` cells (by default the clearance in
+    cells plus 2), the cost field from `goals` at the clearance (metres), and the paths from `starts` (both voxel indices)
+    -> (cost, lo, voxel, r2, info, paths)."""
+    header, rec = read(path)
+    voxel = header["voxel"]
+    r2 = plan_r2(clearance, voxel)
+    lo, hi, _ = bounds_records(rec, min_count)
+    lo, n = padded_box(lo, hi, int(np.ceil(np.sqrt(r2))) + 2 if pad is None else pad)
+    d2, _ = distance_field_records(rec, lo, n, min_count)
+    cost, info = plan_records(d2, lo, n, goals, r2)
+    return cost, lo.astype(np.int32), voxel, r2, info, plan_paths(cost, lo, n, starts, max_len)
+
+
 def write_field(path, d2, lo, voxel):
     """The .npz of a distance field: d2 (uint32 [n0, n1, n2]), lo, n (int32 [3]), voxel (float32)."""
     d2 = np.ascontiguousarray(d2, np.uint32)
@@ -1142,6 +1306,39 @@ def main(argv=None):
                       % (opt["-o"], ("converged", "iteration limit", "lost")[status], it, rec["matched"], rec["considered"], rec["skipped"],
                          float(np.sqrt(rec["S"][27] / max(int(rec["matched"]), 1)))))
                 return 0 if status != ALIGN_LOST else 1
+        if cmd == "plan" and "-o" in args:
+            opt = {"-o": 1, "--goal": 3, "--start": 3, "--clearance": 1, "--pad": 1, "--cost": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val.setdefault(args[i], []).append(args[i + 1:i + 1 + k])
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1 and all(k in val for k in ("-o", "--goal", "--start", "--clearance")):
+                goals = [[int(x) for x in g] for g in val["--goal"]]
+                starts = [[int(x) for x in s] for s in val["--start"]]
+                cost, lo, voxel, r2, info, paths = plan_file(pos[0], goals, starts, float(val["--clearance"][-1][0]),
+                                                             None if "--pad" not in val else int(val["--pad"][-1][0]))
+                if "--cost" in val:
+                    write_cost(val["--cost"][-1][0], cost, lo, voxel, r2)
+                if info["seeds_used"] == 0:
+                    raise ValueError("no goal lies on a free cell of the box (%d outside it, %d closer than the clearance to a surface)"
+                                     % (info["seeds_outside"], info["seeds_blocked"]))
+                if not any(st in (PLAN_REACHED, PLAN_TRUNCATED) for _, st, _ in paths):
+                    raise ValueError("no start reaches a goal: %s" % ", ".join(PLAN_STATUS[st] for _, st, _ in paths))
+                with open(val["-o"][-1][0], "w") as f:
+                    for j, (cells, st, c) in enumerate(paths):
+                        f.write("# path %d from %s: %s, cost %s, %d cells, %.9g m (chamfer)\n"
+                                % (j, starts[j], PLAN_STATUS[st], "none" if c == int(PLAN_NONE) else c, len(cells),
+                                   0.0 if c == int(PLAN_NONE) else c * voxel / 3.0))
+                        f.write("".join(" ".join("%.9g" % x for x in p) + "\n" for p in plan_path_points(cells, voxel)))
+                print("%s: %d paths (%s) through %d x %d x %d cells at r2 = %d: %d free, %d reachable, largest cost %d"
+                      % ((val["-o"][-1][0], len(paths), ", ".join(PLAN_STATUS[st] for _, st, _ in paths)) + cost.shape
+                         + (r2, info["free"], info["reachable"], info["max_cost"])))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -1156,6 +1353,7 @@ def main(argv=None):
           "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | carve A --views DIR -o OUT [--removed R] [--radius N] [--margin M] "
           "[--margin-rel F] [--min-views K] [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
           "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] | df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt | "
+          "plan A --goal X Y Z [--goal ...] --start X Y Z [--start ...] --clearance M [--pad N] -o PATH.txt [--cost OUT.npz] | "
           "ply FILE [OUT.ply]")
     return 2
 

@@ -319,6 +319,28 @@ class MapDfAlignInfo(C.Structure):
 assert C.sizeof(MapDfAlignInfo) == 208
 
 
+PLAN_NONE = 0xFFFFFFFF  # REVO_PLAN_NONE: the cost of a cell that is not free or that no seed reaches
+PLAN_REACHED, PLAN_UNREACHABLE, PLAN_OUTSIDE, PLAN_TRUNCATED = 0, 1, 2, 3  # REVO_PLAN_*: how a path ended
+
+
+class MapPlanSeed(C.Structure):
+    """revo_map_plan_seed (include/revo_hip.h), 16 bytes: a goal's voxel index and the cost there (<= 2^24)."""
+    _fields_ = [("cell", C.c_int32 * 3), ("cost0", C.c_uint32)]
+
+
+class MapPlanInfo(C.Structure):
+    """revo_map_plan_info (include/revo_hip.h), 64 bytes: integer sums and maxima of a planning call."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "free", "reachable", "max_cost", "seeds_used", "seeds_outside", "seeds_blocked", "reserved")]
+
+
+class MapPlanPath(C.Structure):
+    """revo_map_plan_path (include/revo_hip.h), 16 bytes: the cells written for a start, how its path ended, the start's cost."""
+    _fields_ = [("length", C.c_uint32), ("status", C.c_uint32), ("cost", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert (C.sizeof(MapPlanSeed), C.sizeof(MapPlanInfo), C.sizeof(MapPlanPath)) == (16, 64, 16)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
