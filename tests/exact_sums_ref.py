@@ -87,6 +87,25 @@ def point_terms(ref_table, pts, cam, R, T, edge_distance, use_edge_filter, huber
     return np.array(terms, np.float32).reshape(27, n_good), sw, r2, n_good, len(p) - n_good
 
 
+def eval_cost(ref_dt, pts, cam, R, T, edge_distance, use_edge_filter):
+    """TrackerNew::evalCostFunction (tracker.cpp:357-393) at a pose: the keyframe's distance transform [h, w] read at the FLOOR of
+    every projection (fx*X)/Z + cx, (fy*Y)/Z + cy that lies in 0 <= u < w, 0 <= v < h, filtered like the residual, summed in
+    float64 (exact for these terms whatever the order) and rounded to float once."""
+    fx, fy, cx, cy = (f32(c) for c in cam[:4])
+    w, h = int(cam[4]), int(cam[5])
+    R = np.asarray(R, np.float32).reshape(3, 3)
+    T = np.asarray(T, np.float32).reshape(3)
+    p = np.asarray(pts, np.float32)
+    W = [((R[r, 0] * p[:, 0] + R[r, 1] * p[:, 1]) + R[r, 2] * p[:, 2]) + T[r] for r in range(3)]
+    with np.errstate(all="ignore"):
+        u = (fx * W[0]) / W[2] + cx
+        v = (fy * W[1]) / W[2] + cy
+        inside = (u >= 0) & (u < f32(w)) & (v >= 0) & (v < f32(h))
+        r = np.asarray(ref_dt, np.float32)[np.floor(v[inside]).astype(np.int64), np.floor(u[inside]).astype(np.int64)]
+    keep = ~((r > f32(edge_distance)) & bool(use_edge_filter))
+    return f32(r[keep].astype(np.float64).sum())
+
+
 def exact_eval(ref_table, pts, cam, R, T, edge_distance, use_edge_filter, huber):
     """What revo_optimizer_eval returns in exact-sums mode: (mean error, sum_w, sum_u, good, bad, A [6x6], b [6])."""
     terms, sw, su, good, bad = point_terms(ref_table, pts, cam, R, T, edge_distance, use_edge_filter, huber)
@@ -94,10 +113,12 @@ def exact_eval(ref_table, pts, cam, R, T, edge_distance, use_edge_filter, huber)
     sums = [round_exact_f32(terms[k]) for k in range(27)]
     A = np.zeros((6, 6), np.float32)
     k = 0
-    for a in range(6):
-        for c in range(a, 6):
-            A[a, c] = A[c, a] = sums[k] / n
-            k += 1
-    b = np.array([-(sums[21 + a]) / n for a in range(6)], np.float32)
     s_w, s_u = round_exact_f32(sw), round_exact_f32(su)
-    return f32(s_w / n), s_w, s_u, good, bad, A, b
+    with np.errstate(all="ignore"):  # good = 0: 0/0 like the reference (optimizer.cpp:190, LGSX.h:323-325)
+        for a in range(6):
+            for c in range(a, 6):
+                A[a, c] = A[c, a] = sums[k] / n
+                k += 1
+        b = np.array([-(sums[21 + a]) / n for a in range(6)], np.float32)
+        err = f32(s_w / n)
+    return err, s_w, s_u, good, bad, A, b
