@@ -1341,6 +1341,81 @@ typedef struct revo_map_plan_path {   /* 16 bytes per start */
 int revo_map_plan_paths(revo_map* m, const revo_map_df_box* box, const uint32_t* cost, int device_cost, size_t n_starts,
                         const int32_t* starts, uint32_t max_len, int32_t* cells_out, revo_map_plan_path* path_out, int device_out);
 
+/* ---- known space: the seen volume, the known field, the frontiers ------------------------------------------
+ * The map says what is there; the seen volume says what has been looked at.  It is one byte per cell of a distance-field box
+ * (revo_map_df_box with its rules; cell (ix, iy, iz) at seen[(ix*n[1] + iy)*n[2] + iz], z fastest): the low seven bits count
+ * the views that looked through the cell's centre (free votes, saturating at 127), bit 7 says that a view measured a surface
+ * there.  Every value is an integer decided by float32 arithmetic with one definition, so the bytes are a pure function of
+ * the inputs -- the same on every run, whatever the launch.
+ *
+ * The cell's point: for the cell a of the box, p_i = ((float)(lo_i + a_i) + 0.5f) * voxel, voxel the map's edge (the sum is
+ * exact, the product rounded once): the cell's centre.  The cell's class in a view is revo_map_carve_eval's class of p, with
+ * the views, the radius and the margins read exactly as there.  The map's voxels play no part: a solid voxel's cell gets what
+ * its centre's class gives.
+ * The byte: with in = accumulate ? seen[c] : 0, f the number of views of the call in which p is FREE and s = 1 if p is
+ * CONFIRMED in any of them,
+ *     seen[c] = ((in | (s << 7)) & 0x80) | min(127, (in & 0x7F) + f).
+ * Exact properties: the order of the views cannot show; revo_map_observe with views A followed by an accumulating call with
+ * views B leaves the bytes of one call with A and B together, saturation included; a call that does not accumulate does not
+ * read seen. */
+typedef struct revo_map_observe_params { /* 16 bytes; NULL: 1, 0, the map's voxel edge, 0 */
+  int32_t radius;        /* 0 .. 3: half width of the pixel window, as revo_map_carve_params'     */
+  uint32_t accumulate;   /* 0: seen is written; 1: seen is read and updated                        */
+  float margin;          /* metres, finite, >= 0                                                   */
+  float margin_rel;      /* per metre of depth, finite, >= 0                                       */
+} revo_map_observe_params;
+typedef struct revo_map_observe_info {   /* 64 bytes, little-endian, no padding: integer sums, so order-free */
+  uint64_t cells;           /* n[0]*n[1]*n[2]                                               */
+  uint64_t cells_free;      /* cells whose free votes are not 0 after the call              */
+  uint64_t cells_surface;   /* cells whose bit 7 is set after the call                      */
+  uint64_t votes;           /* the sum of f over the cells: this call's FREE classifications */
+  uint64_t newly_known;     /* cells with in == 0 and a byte other than 0 after the call    */
+  uint64_t reserved[3];     /* zero */
+} revo_map_observe_info;
+/* The seen volume of `box` from n views (1 .. 64; revo_map_carve_view with every rule of revo_map_carve_eval: kf or a raw
+ * depth image, the all-zero intrinsics, the pose rules, device_in; every pyramid is checked before anything is enqueued, host
+ * images are uploaded to one temporary buffer).  Runs on the context's tracker stream, for a pyramid view behind that
+ * pyramid's build.  The map gives the context, the stream and the voxel edge and is not changed.
+ * device_seen = 0: seen, info and view_info (n records: the cells of the box by class, summing to cells) are host pointers
+ * and the call waits.  device_seen = 1: all three are device pointers of the map's device, 16-byte aligned; with device images
+ * or pyramids the call only enqueues, with host images it waits.  info and view_info may be NULL.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, views or seen; the box rules of
+ * revo_map_distance_field; n outside 1 .. 64; the view rules of revo_map_carve_eval; radius outside 0 .. 3; accumulate above
+ * 1; a margin that is not finite or negative; a flag outside 0 / 1; a misaligned device pointer. */
+int revo_map_observe(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views, int device_in,
+                     const revo_map_observe_params* prm, uint8_t* seen, int device_seen, revo_map_observe_info* info,
+                     revo_map_carve_view_info* view_info);
+
+/* The distance field with unseen space as an obstacle.  A cell is SOLID as in revo_map_distance_field; it is KNOWN if it is
+ * solid, or (seen[c] & 0x7F) >= max(min_views, 1), or seen[c] & 0x80; otherwise it is UNKNOWN.  d2 is
+ * revo_map_distance_field's definition over the obstacle set solid + unknown: the exact squared distance in cells to the
+ * nearest such cell inside the box, REVO_DF_NONE only if the set is empty, clamp as there.  revo_map_plan over this field
+ * keeps the clearance from unseen space too, and a goal in unseen space counts in seeds_blocked. */
+typedef struct revo_map_known_info {  /* 64 bytes; the first five words are revo_map_df_info's */
+  uint64_t cells, solid, outside, below;
+  uint64_t max_d2;
+  uint64_t unknown;         /* cells of the box that are not known                          */
+  uint64_t known_free;      /* cells - solid - unknown                                      */
+  uint64_t reserved;        /* zero */
+} revo_map_known_info;
+/* seen: the box's seen volume, n[0]*n[1]*n[2] bytes (device_seen: where it lives; a host volume is uploaded).  d2, device_out
+ * and info as revo_map_distance_field's.  The call only enqueues when both flags are 1 and waits otherwise.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: revo_map_distance_field's rules; NULL seen; a
+ * flag outside 0 / 1; a device seen that is not 16-byte aligned. */
+int revo_map_known_field(revo_map* m, const revo_map_df_box* box, uint32_t min_count, uint32_t clamp, const uint8_t* seen,
+                         int device_seen, uint32_t min_views, uint32_t* d2, int device_out, revo_map_known_info* info);
+
+/* Where known space ends.  A frontier cell is not solid, has (seen[c] & 0x7F) >= max(min_views, 1), and at least one of its six
+ * face neighbours INSIDE the box is unknown as defined above (cells at the box's faces have fewer neighbours: the outside of
+ * the box is not unknown).  The records are revo_map_plan_seed: the absolute voxel index and cost0 = 0; revo_map_plan takes
+ * them as they are.  *n_cells = the number of frontier cells.  device_out = 0: host records in ascending order of the cell's
+ * place in the box (x, then y, then z).  device_out = 1: device memory, 16-byte aligned, unspecified order.  cells == NULL:
+ * count only (cap is ignored).  REVO_ERR_CAPACITY with nothing written when cap < *n_cells.  A counting launch runs first and
+ * a second one writes; the call waits.  REVO_ERR_INVALID_ARG, with nothing written: NULL m, box, seen or n_cells; the box
+ * rules; a flag outside 0 / 1; a misaligned device pointer (16 bytes). */
+int revo_map_frontiers(revo_map* m, const revo_map_df_box* box, uint32_t min_count, const uint8_t* seen, int device_seen,
+                       uint32_t min_views, revo_map_plan_seed* cells, size_t cap, size_t* n_cells, int device_out);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

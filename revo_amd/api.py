@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -568,8 +568,9 @@ class VoxelMap:
             raise
 
     # -- free-space carving (revo_map_carve_eval / revo_map_carve)
-    def _carve(self, fn, views, radius, min_views, min_count, max_count, margin, margin_rel, device, records=True):
-        from . import mapfile
+    @staticmethod
+    def _carve_views(views):
+        """-> (the revo_map_carve_view array of a carve or observe call, device_in, what keeps the images alive)."""
         views = list(views)
         n = len(views)
         if not 1 <= n <= 64:
@@ -602,7 +603,12 @@ class VoxelMap:
             v.T_w_c[:] = _cm4(T).tolist()
         if len(set(on_device)) > 1:
             raise ValueError("the raw depth images of one carve are all host arrays or all device tensors")
-        device_in = 1 if on_device and on_device[0] else 0
+        return cv, 1 if on_device and on_device[0] else 0, keep
+
+    def _carve(self, fn, views, radius, min_views, min_count, max_count, margin, margin_rel, device, records=True):
+        from . import mapfile
+        cv, device_in, keep = self._carve_views(views)
+        n = len(cv)
         prm = MapCarveParams(int(radius), int(min_views), int(min_count), int(max_count),
                              float(self.voxel if margin is None else margin), float(margin_rel))
         L = _lib.lib()
@@ -625,10 +631,13 @@ class VoxelMap:
                      0, C.byref(info), vinfo))
             rec = rec[:n_rec.value]
         del keep
+        return rec, {k: int(getattr(info, k)) for k in mapfile.CARVE_INFO_KEYS}, self._view_counts(vinfo)
+
+    @staticmethod
+    def _view_counts(vinfo):
         names = (("outside", "outside"), ("unknown", "unknown"), ("free", "free_space"), ("confirmed", "confirmed"),
                  ("occluded", "occluded"), ("edge", "edge"))
-        return (rec, {k: int(getattr(info, k)) for k in mapfile.CARVE_INFO_KEYS},
-                [{name: int(getattr(vi, field)) for name, field in names} for vi in vinfo])
+        return [{name: int(getattr(vi, field)) for name, field in names} for vi in vinfo]
 
     def carve_eval(self, views, radius=1, min_views=1, min_count=1, max_count=0, margin=None, margin_rel=0.0, device=False, records=True):
         """What carve() would remove; the map is untouched.  views: 1 .. 64 of (pyr, T_w_c) -- a pyramid of this map's context:
@@ -840,16 +849,138 @@ class VoxelMap:
         from . import mapfile
         return {k: int(getattr(i, k)) for k in mapfile.DF_INFO_KEYS}
 
-    def distance_field(self, lo=None, n=None, pad=8, min_count=1, clamp=0):
+    def distance_field(self, lo=None, n=None, pad=8, min_count=1, clamp=0, seen=None, min_views=1):
         """The exact squared Euclidean distance, in cells, from every cell of a box of voxel indices to the nearest voxel with
         count >= min_count inside the box (revo_map_distance_field) -> DistanceField.  lo, n: the box's first voxel
         index and its cells (1 .. 1024) per axis, at most 2^27 cells; by default the map's bounds grown by `pad` cells.  Voxels
-        outside the box are not seen, so pad by the distance that matters.  clamp > 0: values are min(value, clamp)."""
+        outside the box are not seen, so pad by the distance that matters.  clamp > 0: values are min(value, clamp).
+        seen: a SeenVolume -- the known field (revo_map_known_field) over its box: every cell that is neither solid
+        nor known (>= min_views free votes, or the surface bit) is an obstacle too; lo, n and pad are then not given."""
+        if seen is not None:
+            return self._known_field(seen, min_views, lo, n, min_count, clamp)
         box = self._df_box(lo, n, pad, min_count)
         d2 = np.empty(tuple(box.n), np.uint32)
         info = MapDfInfo()
         check(_lib.lib().revo_map_distance_field(self._h, C.byref(box), int(min_count), int(clamp), d2.ctypes.data_as(vp), 0, C.byref(info)))
         return DistanceField(d2, np.array(list(box.lo), np.int32), self.voxel, self._df_info(info), self, clamp=int(clamp))
+
+    def _seen_box(self, seen, lo=None, n=None):
+        if lo is not None or n is not None:
+            raise ValueError("a seen volume brings its own box: lo and n are not given with it")
+        if np.float32(seen.voxel).tobytes() != np.float32(self.voxel).tobytes():
+            raise ValueError("the seen volume was observed at voxels of %g m, the map has %g m" % (seen.voxel, self.voxel))
+        vol = np.ascontiguousarray(seen.seen, np.uint8)
+        return self._df_box(seen.lo, vol.shape, 0, 1), vol
+
+    def _known_field(self, seen, min_views, lo, n, min_count, clamp):
+        from . import mapfile
+        box, vol = self._seen_box(seen, lo, n)
+        d2 = np.empty(tuple(box.n), np.uint32)
+        info = MapKnownInfo()
+        check(_lib.lib().revo_map_known_field(self._h, C.byref(box), int(min_count), int(clamp), vol.ctypes.data_as(vp), 0, int(min_views),
+                                              d2.ctypes.data_as(vp), 0, C.byref(info)))
+        f = DistanceField(d2, np.array(list(box.lo), np.int32), self.voxel, {k: int(getattr(info, k)) for k in mapfile.KNOWN_INFO_KEYS}, self,
+                          clamp=int(clamp))
+        f.known, f.min_views = True, max(1, int(min_views))
+        return f
+
+    def known_field_into(self, d_d2, d_seen, lo, n, min_count=1, clamp=0, min_views=1, d_info=None, wait=True):
+        """The known field between torch device tensors: d_seen the seen volume (uint8 of the box's shape n), d_d2 and d_info
+        as distance_field_into takes them (d_info: 64 bytes, revo_map_known_info)."""
+        box = self._df_box(lo, n, 0, 1)
+        if tuple(d_d2.shape) != tuple(box.n) or d_d2.element_size() != 4 or d_d2.is_floating_point():
+            raise ValueError("d_d2 must be a 32-bit integer tensor of the box's shape")
+        if tuple(d_seen.shape) != tuple(box.n) or str(d_seen.dtype) != "torch.uint8":
+            raise ValueError("d_seen must be a uint8 tensor of the box's shape")
+        for t_ in (d_d2, d_seen, d_info):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("tensors must be contiguous device tensors")
+        if d_info is not None and d_info.numel() * d_info.element_size() != 64:
+            raise ValueError("d_info needs 64 bytes")
+        import torch
+        torch.cuda.current_stream(d_d2.device).synchronize()  # the volume is written, the outputs' earlier use is over
+        check(_lib.lib().revo_map_known_field(self._h, C.byref(box), int(min_count), int(clamp), vp(d_seen.data_ptr()), 1, int(min_views),
+                                              vp(d_d2.data_ptr()), 1, vp(d_info.data_ptr()) if d_info is not None else None))
+        if wait:
+            self.sync()
+
+    # -- known space (revo_map_observe / revo_map_frontiers, DESIGN 24)
+    def observe(self, views, lo=None, n=None, pad=0, radius=1, margin=None, margin_rel=0.0, into=None):
+        """What the views have looked at -> SeenVolume: one byte per cell of a box of voxel indices -- the views that look
+        through the cell's centre (free votes, at most 127) and, in bit 7, whether one measured a surface there
+        (revo_map_observe).  views, radius, margin, margin_rel: as carve_eval takes them; the class of a cell's
+        centre in a view is carve_eval's class of that point.  lo, n: the box (by default the map's bounds grown by `pad`
+        cells).  into: a SeenVolume to accumulate into (votes add and saturate, the surface bit stays); its box is the
+        call's, so lo and n are not given.  The map's voxels play no part."""
+        from . import mapfile
+        cv, device_in, keep = self._carve_views(views)
+        if into is not None:
+            box, vol = self._seen_box(into, lo, n)
+            vol = vol.copy()
+        else:
+            box = self._df_box(lo, n, pad, 1)
+            vol = np.empty(tuple(box.n), np.uint8)
+        prm = MapObserveParams(int(radius), 0 if into is None else 1, float(self.voxel if margin is None else margin), float(margin_rel))
+        info, vinfo = MapObserveInfo(), (MapCarveViewInfo * len(cv))()
+        check(_lib.lib().revo_map_observe(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vol.ctypes.data_as(vp), 0, C.byref(info),
+                                          C.cast(vinfo, vp)))
+        del keep
+        return SeenVolume(vol, np.array(list(box.lo), np.int32), self.voxel, {k: int(getattr(info, k)) for k in mapfile.SEEN_INFO_KEYS},
+                          self._view_counts(vinfo))
+
+    def observe_into(self, d_seen, views, lo, radius=1, margin=None, margin_rel=0.0, accumulate=False, d_info=None, d_view_info=None, wait=True):
+        """observe() into a torch device tensor: d_seen uint8 of the box's shape (its cells are the box's n), d_info None or 64
+        bytes (revo_map_observe_info), d_view_info None or 32 bytes per view (revo_map_carve_view_info); contiguous, 16-byte
+        aligned, on the map's device.  accumulate: d_seen is read and updated.  With device or pyramid views the call is only
+        enqueued on the context's tracker stream: wait=False returns at once (sync() orders later reads)."""
+        cv, device_in, keep = self._carve_views(views)
+        if d_seen.dim() != 3 or str(d_seen.dtype) != "torch.uint8":
+            raise ValueError("d_seen must be a 3-D uint8 tensor")
+        box = self._df_box(lo, tuple(d_seen.shape), 0, 1)
+        for t_, size in ((d_seen, None), (d_info, 64), (d_view_info, 32 * len(cv))):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("output tensors must be contiguous device tensors")
+            if t_ is not None and size is not None and t_.numel() * t_.element_size() != size:
+                raise ValueError("d_info needs 64 bytes and d_view_info 32 bytes per view")
+        prm = MapObserveParams(int(radius), 1 if accumulate else 0, float(self.voxel if margin is None else margin), float(margin_rel))
+        import torch
+        torch.cuda.current_stream(d_seen.device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
+        check(_lib.lib().revo_map_observe(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vp(d_seen.data_ptr()), 1,
+                                          vp(d_info.data_ptr()) if d_info is not None else None,
+                                          vp(d_view_info.data_ptr()) if d_view_info is not None else None))
+        if wait:
+            self.sync()
+        del keep
+
+    def frontiers(self, seen, min_views=1, min_count=1):
+        """Where known space ends -> [k, 3] int32 voxel indices in ascending order of the cell's place in the box: the cells
+        of a SeenVolume that are not solid, have >= min_views free votes and have a face neighbour inside the box that is
+        neither solid nor known (revo_map_frontiers).  DistanceField.plan takes them as goals."""
+        box, vol = self._seen_box(seen)
+        L, k = _lib.lib(), C.c_size_t()
+        args = (self._h, C.byref(box), int(min_count), vol.ctypes.data_as(vp), 0, int(min_views))
+        check(L.revo_map_frontiers(*args, None, 0, C.byref(k), 0))
+        rec = np.zeros(k.value, np.dtype([("cell", "<i4", (3,)), ("cost0", "<u4")]))
+        if k.value:
+            check(L.revo_map_frontiers(*args, rec.ctypes.data_as(vp), k.value, C.byref(k), 0))
+        return rec["cell"][:k.value].copy()
+
+    def frontiers_into(self, d_cells, d_seen, lo, min_views=1, min_count=1):
+        """frontiers() between torch device tensors: d_seen the seen volume (3-D uint8), d_cells room for 16-byte records
+        (revo_map_plan_seed: the cell, cost0 = 0) or None to count only -> the number of frontier cells; the records come in
+        unspecified order.  RevoError (REVO_ERR_CAPACITY), nothing written, when d_cells holds fewer."""
+        if d_seen.dim() != 3 or str(d_seen.dtype) != "torch.uint8" or not (d_seen.is_contiguous() and d_seen.is_cuda):
+            raise ValueError("d_seen must be a contiguous 3-D uint8 device tensor")
+        if d_cells is not None and not (d_cells.is_contiguous() and d_cells.is_cuda):
+            raise ValueError("d_cells must be a contiguous device tensor")
+        box = self._df_box(lo, tuple(d_seen.shape), 0, 1)
+        import torch
+        torch.cuda.current_stream(d_seen.device).synchronize()
+        k = C.c_size_t()
+        cap = 0 if d_cells is None else d_cells.numel() * d_cells.element_size() // 16
+        check(_lib.lib().revo_map_frontiers(self._h, C.byref(box), int(min_count), vp(d_seen.data_ptr()), 1, int(min_views),
+                                            vp(d_cells.data_ptr()) if d_cells is not None else None, cap, C.byref(k), 1))
+        return int(k.value)
 
     def distance_field_into(self, d_d2, lo, n, min_count=1, clamp=0, d_info=None, wait=True):
         """distance_field() into a torch device tensor: d_d2 of shape n with 32-bit integers, d_info None or a 64-byte tensor
@@ -1115,6 +1246,7 @@ class DistanceField:
         self.voxel = float(np.float32(voxel))
         self.info = info
         self._map = map
+        self.known, self.min_views = False, None  # a known field (VoxelMap.distance_field(seen=...)) says so, and with which votes
 
     def metres(self):
         """[n0, n1, n2] float32: sqrt(d2) * voxel, +inf where there is no voxel."""
@@ -1193,6 +1325,61 @@ class DistanceField:
     def load(cls, path):
         from . import mapfile
         return cls(*mapfile.read_field(path))
+
+
+class SeenVolume:
+    """What has been looked at, over a box of voxel indices (VoxelMap.observe, `mapfile observe`): seen [n0, n1, n2]
+    uint8 -- the low seven bits the views that looked through the cell's centre (free votes, at most 127), bit 7 whether a view
+    measured a surface there --, lo the box's first voxel index, n its cells per axis, voxel the map's edge in metres, info the
+    last call's counters (mapfile.SEEN_INFO_KEYS) and view_info its per-view class counts (None for a loaded volume)."""
+
+    def __init__(self, seen, lo, voxel, info=None, view_info=None):
+        seen = np.asarray(seen)
+        if seen.dtype != np.uint8 or seen.ndim != 3:
+            raise ValueError("a seen volume is a 3-D uint8 array")
+        self.seen = seen
+        self.lo = np.asarray(lo, np.int32).reshape(3)
+        self.n = np.asarray(seen.shape, np.int32)
+        self.voxel = float(np.float32(voxel))
+        self.info = info
+        self.view_info = view_info
+
+    def free(self, min_views=1):
+        """[n0, n1, n2] bool: the cells with at least min_views free votes."""
+        from . import mapfile
+        return mapfile.seen_free(self.seen, min_views)
+
+    def known(self, solid=None, min_views=1):
+        """[n0, n1, n2] bool: the cells that are free or carry the surface bit -- or are solid, where `solid` (a bool volume
+        of the box, mapfile.solid_cells) says so."""
+        from . import mapfile
+        return mapfile.seen_known(self.seen, min_views, solid)
+
+    def save(self, path):
+        """The .npz `python -m revo_amd.mapfile observe` writes: seen, lo, n, voxel."""
+        from . import mapfile
+        return mapfile.write_seen(path, self.seen, self.lo, self.voxel)
+
+    @classmethod
+    def load(cls, path):
+        from . import mapfile
+        return cls(*mapfile.read_seen(path))
+
+
+def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
+    """The whole route from mapping to exploration on the map's device: the known field of `seen` (a SeenVolume), its
+    frontiers, the cost-to-go with the frontiers as goals at the clearance (metres), and the path from `start` (a voxel index,
+    or metres) down to the nearest frontier -> dict: field (DistanceField), frontiers [k, 3], cost (CostField), path
+    (cells, status, cost).  ValueError when the volume has no frontier cell, or when the clearance is above one voxel edge: a
+    frontier cell touches unseen space, which the known field counts as an obstacle, so none keeps a larger clearance."""
+    field = m.distance_field(seen=seen, min_views=min_views, min_count=min_count)
+    fr = m.frontiers(seen, min_views, min_count)
+    if len(fr) == 0:
+        raise ValueError("the seen volume has no frontier cell")
+    cost = field.plan(fr, clearance=clearance)
+    if cost.info["seeds_used"] == 0:  # a frontier cell touches unseen space: d2 = 1 in the known field
+        raise ValueError("no frontier cell keeps the clearance: unseen space counts against it, so explore needs r2 = 1 (at most one voxel edge)")
+    return {"field": field, "frontiers": fr, "cost": cost, "path": cost.path(np.asarray(start).reshape(1, 3), max_len)[0]}
 
 
 class CostField:
@@ -1456,6 +1643,17 @@ class MapWindow:
 
     def cast_rays(self, *args, **kw):
         return self.map.cast_rays(*args, **kw)
+
+    def observe(self, *args, **kw):
+        """The inner map's observe: what views have looked at, over the voxels the window holds now."""
+        return self.map.observe(*args, **kw)
+
+    def distance_field(self, *args, **kw):
+        """The inner map's distance field (seen=: the known field)."""
+        return self.map.distance_field(*args, **kw)
+
+    def frontiers(self, *args, **kw):
+        return self.map.frontiers(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

@@ -2,7 +2,6 @@
 // revo_map_subtract_posed (a map under a rigid pose), revo_map_carve_eval and revo_map_carve (free-space carving).
 // Contracts: include/revo_hip.h; DESIGN 18 and 19.
 #include "revo_map_impl.h"
-#include "revo_carve_host.h"
 
 // ------------------------------------------------------------------------------------------- maps under a pose (18) --
 struct MapPose { float r00, r01, r02, r10, r11, r12, r20, r21, r22, tx, ty, tz, voxel; };  // r_ij: row i, column j; the destination edge
@@ -203,10 +202,6 @@ extern "C" int revo_map_subtract_posed(revo_map* dst, revo_map* src, const float
 
 // ---------------------------------------------------------------------------------------------- free-space carving (19) --
 // revo_map_carve_eval / revo_map_carve (contract: include/revo_hip.h).
-struct MapCarveView {  // one view of a launch, in device memory
-  CarveView v;
-  const float* depth;
-};
 struct MapCarveK {
   const u64* keys; const MapVal* vals; unsigned cap;  // the map's table
   const MapCarveView* views; int n;
@@ -217,40 +212,6 @@ struct MapCarveK {
   u64* info;                          // one 64-byte line: revo_map_carve_info's four counters
   unsigned* vinfo;                    // 8 words per view: revo_map_carve_view_info
 };
-enum { CARVE_OUTSIDE = 0, CARVE_UNKNOWN = 1, CARVE_FREE = 2, CARVE_CONFIRMED = 3, CARVE_OCCLUDED = 4, CARVE_EDGE = 5, CARVE_CLASSES = 6 };
-#define CARVE_MAX_VIEWS 64
-
-// The class of the point p in one view: the one text of the contract's rule.  Every read of the depth image lies inside a
-// window that has been tested against the image size first, and |u|, |v| < 2^20 bounds the integers the test is made on.
-__device__ __forceinline__ int map_carve_class(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel) {
-  const CarveView& c = vw.v;
-  const float x = ((c.Rc[0] * px + c.Rc[1] * py) + c.Rc[2] * pz) + c.tc[0];
-  const float y = ((c.Rc[3] * px + c.Rc[4] * py) + c.Rc[5] * pz) + c.tc[1];
-  const float z = ((c.Rc[6] * px + c.Rc[7] * py) + c.Rc[8] * pz) + c.tc[2];
-  if (!isfinite(x) || !isfinite(y) || !map_depth_ok(z, c.zmin, c.zmax)) return CARVE_OUTSIDE;
-  const float u = __fdiv_rn(c.fx * x, z) + c.cx;
-  const float v = __fdiv_rn(c.fy * y, z) + c.cy;
-  if (!(fabsf(u) < 1048576.0f) || !(fabsf(v) < 1048576.0f)) return CARVE_OUTSIDE;  // NaN / inf fail the comparison
-  const int iu = (int)floorf(u + 0.5f), iv = (int)floorf(v + 0.5f);
-  if (iu - r < 0 || iu + r > c.w - 1 || iv - r < 0 || iv + r > c.h - 1) return CARVE_OUTSIDE;
-  bool usable = true;
-  float dmin = INFINITY;
-  for (int dy = -r; dy <= r; ++dy) {
-    const float* row = vw.depth + (size_t)(iv + dy) * c.w + iu;
-    for (int dx = -r; dx <= r; ++dx) {
-      const float d = row[dx];
-      usable = usable && map_depth_ok(d, c.zmin, c.zmax);
-      dmin = fminf(dmin, d);  // only looked at when every depth is usable
-    }
-  }
-  if (!usable) return CARVE_UNKNOWN;
-  if (z < dmin - (margin + margin_rel * dmin)) return CARVE_FREE;
-  const float dc = vw.depth[(size_t)iv * c.w + iu];
-  const float mc = margin + margin_rel * dc;
-  if (fabsf(z - dc) <= mc) return CARVE_CONFIRMED;
-  return z > dc + mc ? CARVE_OCCLUDED : CARVE_EDGE;
-}
-
 // One thread per slot of the table: the value as four 16-byte loads, the point once, then the views one after another with
 // the votes in a register.  Per view the classes of a wave are counted by ballots into LDS; the carved records are compacted
 // as k_map_export compacts (LDS counter, one global atomic per block); every counter takes one global atomic per block.
@@ -347,34 +308,9 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
   if (device_out) TRY(map_check_aligned((uintptr_t)records, 16, "the device output is"));
   revo_map_carve_params pp;
   if (const char* why = carve_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_carve: ") + why);
-  const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
   std::vector<MapCarveView> hv(n);
   size_t up_bytes = 0;
-  for (int i = 0; i < n; ++i) {
-    const std::string at = "view " + std::to_string(i) + ": ";
-    if (const char* why = carve_view_check(&views[i], cam, m->g.w, m->g.h, &hv[i].v)) return fail(REVO_ERR_INVALID_ARG, at + why);
-    hv[i].depth = views[i].depth;
-    if (views[i].depth) {
-      if (device_in) TRY(map_check_aligned((uintptr_t)views[i].depth, 4, at + "the device depth image is"));
-      if (!device_in) up_bytes += ((size_t)hv[i].v.w * hv[i].v.h * sizeof(float) + 255) & ~(size_t)255;
-    }
-  }
-  for (int i = 0; i < n; ++i) {  // every pyramid's context and kind, before any of them orders a stream
-    if (!views[i].kf) continue;
-    const revo_ctx* pc = nullptr;
-    int batch_view = 0;
-    TRY(revo_map_source_kind_(views[i].kf, &pc, &batch_view));
-    const std::string at = "view " + std::to_string(i) + ": ";
-    if (pc != m->ctx) return fail(REVO_ERR_INVALID_ARG, at + "the pyramid belongs to another context than the map");
-    if (batch_view)
-      return fail(REVO_ERR_INVALID_ARG, at + "a batch view is not a keyframe the map calls take (pass its depth plane as a raw image)");
-  }
-  for (int i = 0; i < n; ++i) {  // nothing is refused from here on: the tracker stream is ordered behind the pyramids' builds
-    if (!views[i].kf) continue;
-    MapSource src;
-    TRY(revo_map_source_(const_cast<revo_pyr*>(views[i].kf), &src));
-    hv[i].depth = src.depth;
-  }
+  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes));
   MapStats st;  // waits for the map: its table is complete
   TRY(map_read_stats(m, &st));
   hipStream_t s = (hipStream_t)m->g.stream;
@@ -383,14 +319,7 @@ static int carve_apply(revo_map* m, int n, const revo_map_carve_view* views, int
   TRY(r.buf.alloc(o_views + sizeof(MapCarveView) * n));
   if (up_bytes) {
     TRY(r.images.alloc(up_bytes));
-    size_t o = 0;
-    for (int i = 0; i < n; ++i) {
-      if (!views[i].depth) continue;
-      const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * sizeof(float);
-      HIPCHECK(hipMemcpyAsync(r.images.p + o, views[i].depth, bytes, hipMemcpyHostToDevice, s));
-      hv[i].depth = (const float*)(r.images.p + o);
-      o += (bytes + 255) & ~(size_t)255;
-    }
+    TRY(map_views_upload(n, views, hv.data(), r.images.p, s));
   }
   HIPCHECK(hipMemcpyAsync(r.buf.p + o_views, hv.data(), sizeof(MapCarveView) * n, hipMemcpyHostToDevice, s));
   MapCarveK a{};

@@ -7,6 +7,7 @@
 // order-free), pass z turns every z-line's bits into dz^2, passes y and x are the min-plus step d(i) = min_j (i - j)^2 + g(j)
 // along their axis, and the last one writes the contract's values (clamp, REVO_DF_NONE) and feeds max_d2.
 #include "revo_map_impl.h"
+#include "revo_seen_host.h"
 
 #include <climits>
 
@@ -16,13 +17,18 @@
 #define DF_MAX_POINTS (1ull << 24)
 #define DF_TILE_WORDS 8192  // the LDS tile of a min-plus block: line length x strip width <= 8192 words (32 KB)
 
-// info words: cells, solid, outside, below, max_d2 (revo_map_df_info)
-enum { DF_CELLS = 0, DF_SOLID = 1, DF_OUTSIDE = 2, DF_BELOW = 3, DF_MAXD2 = 4 };
+// info words: cells, solid, outside, below, max_d2 (revo_map_df_info), then unknown, known_free (revo_map_known_info)
+enum { DF_CELLS = 0, DF_SOLID = 1, DF_OUTSIDE = 2, DF_BELOW = 3, DF_MAXD2 = 4, DF_UNKNOWN = 5, DF_KNOWN_FREE = 6 };
 
 static_assert(sizeof(revo_map_df_box) == 24 && offsetof(revo_map_df_box, n) == 12, "the box is six 32-bit words");
 static_assert(sizeof(revo_map_df_info) == 64 && offsetof(revo_map_df_info, cells) == 8 * DF_CELLS && offsetof(revo_map_df_info, solid) == 8 * DF_SOLID &&
               offsetof(revo_map_df_info, outside) == 8 * DF_OUTSIDE && offsetof(revo_map_df_info, below) == 8 * DF_BELOW &&
               offsetof(revo_map_df_info, max_d2) == 8 * DF_MAXD2 && offsetof(revo_map_df_info, reserved) == 40, "the info record is the kernels' counter line");
+static_assert(sizeof(revo_map_known_info) == 64 && offsetof(revo_map_known_info, cells) == 8 * DF_CELLS && offsetof(revo_map_known_info, solid) == 8 * DF_SOLID &&
+              offsetof(revo_map_known_info, outside) == 8 * DF_OUTSIDE && offsetof(revo_map_known_info, below) == 8 * DF_BELOW &&
+              offsetof(revo_map_known_info, max_d2) == 8 * DF_MAXD2 && offsetof(revo_map_known_info, unknown) == 8 * DF_UNKNOWN &&
+              offsetof(revo_map_known_info, known_free) == 8 * DF_KNOWN_FREE && offsetof(revo_map_known_info, reserved) == 56,
+              "the known field's info record is the same line, two words longer");
 static_assert(sizeof(revo_map_df_sample_t) == 16 && offsetof(revo_map_df_sample_t, grad) == 4, "a sample is one 16-byte word");
 static_assert(REVO_DF_NONE == 0xffffffffu, "REVO_DF_NONE is all ones");
 
@@ -62,6 +68,40 @@ __global__ void __launch_bounds__(256) k_df_occupancy(const u64* __restrict__ ke
   __syncthreads();
   if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(&info[DF_SOLID + threadIdx.x], (u64)s_cnt[threadIdx.x]);
   if (blockIdx.x == 0 && threadIdx.x == 3) info[DF_CELLS] = (u64)box.n[0] * box.n[1] * box.n[2];
+}
+
+// revo_map_known_field: between k_df_occupancy and k_df_pass_z, the unknown cells join the bit volume.  One lane per 32-cell
+// word: its solid bits, the (up to) 32 bytes of `seen` behind them, and the bits of the cells that are neither solid nor known
+// ORed in (every word has one owner: a plain store).  unknown and known_free are counted by the wave, then one global atomic
+// per block and counter, on the line k_df_occupancy and the passes write.
+__global__ void __launch_bounds__(256) k_df_unknown(const uint8_t* __restrict__ seen, const revo_map_df_box box, unsigned wz, unsigned min_views,
+                                                    unsigned* bits, u64* info) {
+  __shared__ unsigned s_cnt[2];  // unknown, known_free
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned words = (unsigned)box.n[0] * (unsigned)box.n[1] * wz;
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  unsigned n_unknown = 0, n_free = 0;
+  if (i < words) {
+    const unsigned line = i / wz, w = i - line * wz;
+    const unsigned nz = (unsigned)box.n[2], z0 = w * 32, len = min(32u, nz - z0);
+    const uint8_t* row = seen + (size_t)line * nz + z0;
+    const unsigned solid = bits[i];
+    unsigned unknown = 0;
+    for (unsigned k = 0; k < len; ++k)
+      unknown |= (seen_is_unknown((solid >> k) & 1u, row[k], min_views) ? 1u : 0u) << k;
+    if (unknown) bits[i] = solid | unknown;
+    n_unknown = (unsigned)__popc(unknown);
+    n_free = len - (unsigned)__popc(solid) - n_unknown;
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) { n_unknown += __shfl_down(n_unknown, off, 64); n_free += __shfl_down(n_free, off, 64); }
+  if ((threadIdx.x & 63) == 0) {
+    if (n_unknown) atomicAdd(&s_cnt[0], n_unknown);
+    if (n_free) atomicAdd(&s_cnt[1], n_free);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&info[DF_UNKNOWN + threadIdx.x], (u64)s_cnt[threadIdx.x]);
 }
 
 // The same scan for revo_map_bounds: b[0..2] the smallest, b[3..5] the largest index per axis, cnt the solid voxels.  A wave
@@ -234,7 +274,7 @@ __global__ void __launch_bounds__(256) k_df_sample(const DfSampleK a, const unsi
 
 // -------------------------------------------------------------------------------------------------------- entry points --
 // the box rules of DESIGN 21; nullptr if the box keeps them
-static const char* df_box_check(const revo_map_df_box* box, size_t* cells) {
+const char* map_df_box_check(const revo_map_df_box* box, size_t* cells) {
   size_t n = 1;
   for (int k = 0; k < 3; ++k) {
     if (box->n[k] < 1 || box->n[k] > DF_MAX_N) return "a box size must be 1 .. 1024 cells";
@@ -255,31 +295,44 @@ static void df_launch_pass(hipStream_t s, unsigned* d2, unsigned outer, int L, u
   hipLaunchKernelGGL(k_df_pass<LAST>, dim3(outer * strips), dim3(256), sizeof(unsigned) * ((size_t)L << sh), s, d2, L, inner, sh, strips, clamp, info);
 }
 
-extern "C" int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, uint32_t min_count, uint32_t clamp, uint32_t* d2, int device_out,
-                                       revo_map_df_info* info) {
-  if (!m || !box || !d2) return fail(REVO_ERR_INVALID_ARG, "null argument");
-  size_t cells = 0;
-  if (const char* why = df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_distance_field: ") + why);
-  TRY(map_check_side(device_out, "device_out"));
-  if (device_out) TRY(map_check_aligned((uintptr_t)d2 | (uintptr_t)info, 16, "a device output is"));
-  HIPCHECK(hipSetDevice(m->g.device));
-  hipStream_t s = (hipStream_t)m->g.stream;
-  const revo_map_df_box b = *box;
-  const unsigned wz = (unsigned)(b.n[2] + 31) / 32;
-  const unsigned lines = (unsigned)b.n[0] * (unsigned)b.n[1];
-  const size_t bit_bytes = sizeof(unsigned) * (size_t)lines * wz;
+// The bit volume of the box's solid voxels on stream s, in m->dfbits, with k_df_occupancy's counters in `info` (NULL: the map's
+// own line, m->dfcnt).  For the units that ask "is this cell solid" (revo_map_frontiers).
+int map_df_solid_bits(revo_map* m, const revo_map_df_box* box, uint32_t min_count, hipStream_t s, const unsigned** bits, unsigned* wz, u64* info) {
+  const unsigned w = (unsigned)(box->n[2] + 31) / 32;
+  const size_t bit_bytes = sizeof(unsigned) * (size_t)box->n[0] * (size_t)box->n[1] * w;
   TRY(m->dfbits.reserve(bit_bytes, s));
   TRY(m->dfcnt.reserve(128, s));
+  if (!info) info = (u64*)m->dfcnt.p;
+  HIPCHECK(hipMemsetAsync(m->dfbits.p, 0, bit_bytes, s));
+  HIPCHECK(hipMemsetAsync(info, 0, sizeof(revo_map_df_info), s));
+  hipLaunchKernelGGL(k_df_occupancy, dim3((unsigned)std::max<size_t>((m->cap + 255) / 256, 1)), dim3(256), 0, s, m->d_keys, m->d_vals,
+                     (unsigned)m->cap, (u64)std::max<uint32_t>(min_count, 1), *box, w, (unsigned*)m->dfbits.p, info);
+  HIPCHECK(hipGetLastError());
+  *bits = (const unsigned*)m->dfbits.p;
+  *wz = w;
+  return REVO_OK;
+}
+
+// The field of the box over the solid voxels and, with d_seen (the box's seen volume in device memory), the unknown cells
+// too: the body of revo_map_distance_field and revo_map_known_field behind their argument checks.
+static int df_run(revo_map* m, const revo_map_df_box* box, size_t cells, uint32_t min_count, uint32_t clamp, const uint8_t* d_seen,
+                  uint32_t min_views, uint32_t* d2, int device_out, void* info, bool wait) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  const revo_map_df_box b = *box;
+  const unsigned lines = (unsigned)b.n[0] * (unsigned)b.n[1];
+  TRY(m->dfbits.reserve(sizeof(unsigned) * (size_t)lines * ((unsigned)(b.n[2] + 31) / 32), s));  // every allocation before the timed span
+  TRY(m->dfcnt.reserve(128, s));
   TRY(m->dfout.reserve(device_out ? 0 : sizeof(unsigned) * cells, s));
-  unsigned* bits = (unsigned*)m->dfbits.p;
   unsigned* d_out = device_out ? d2 : (unsigned*)m->dfout.p;
   u64* d_info = device_out && info ? (u64*)info : (u64*)m->dfcnt.p;
   TRY(m->df_time.begin(s));
-  HIPCHECK(hipMemsetAsync(bits, 0, bit_bytes, s));
-  HIPCHECK(hipMemsetAsync(d_info, 0, sizeof(revo_map_df_info), s));
-  hipLaunchKernelGGL(k_df_occupancy, dim3((unsigned)std::max<size_t>((m->cap + 255) / 256, 1)), dim3(256), 0, s, m->d_keys, m->d_vals,
-                     (unsigned)m->cap, (u64)std::max<uint32_t>(min_count, 1), b, wz, bits, d_info);
-  HIPCHECK(hipGetLastError());
+  const unsigned* bits = nullptr;
+  unsigned wz = 0;
+  TRY(map_df_solid_bits(m, box, min_count, s, &bits, &wz, d_info));
+  if (d_seen) {
+    hipLaunchKernelGGL(k_df_unknown, dim3((lines * wz + 255) / 256), dim3(256), 0, s, d_seen, b, wz, min_views, (unsigned*)m->dfbits.p, d_info);
+    HIPCHECK(hipGetLastError());
+  }
   hipLaunchKernelGGL(k_df_pass_z, dim3(std::min(lines / 4 + 1, 8192u)), dim3(256), 0, s, bits, lines, b.n[2], wz, d_out);
   HIPCHECK(hipGetLastError());
   df_launch_pass<false>(s, d_out, (unsigned)b.n[0], b.n[1], (unsigned)b.n[2], 0, d_info);
@@ -287,11 +340,43 @@ extern "C" int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, 
   df_launch_pass<true>(s, d_out, 1, b.n[0], (unsigned)b.n[1] * (unsigned)b.n[2], clamp, d_info);
   HIPCHECK(hipGetLastError());
   TRY(m->df_time.end(s));
-  if (device_out) return REVO_OK;
-  HIPCHECK(hipMemcpyAsync(d2, d_out, sizeof(unsigned) * cells, hipMemcpyDeviceToHost, s));
-  if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_df_info), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
+  if (!device_out) {
+    HIPCHECK(hipMemcpyAsync(d2, d_out, sizeof(unsigned) * cells, hipMemcpyDeviceToHost, s));
+    if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_df_info), hipMemcpyDeviceToHost, s));
+  }
+  if (wait) HIPCHECK(hipStreamSynchronize(s));
   return REVO_OK;
+}
+
+extern "C" int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, uint32_t min_count, uint32_t clamp, uint32_t* d2, int device_out,
+                                       revo_map_df_info* info) {
+  if (!m || !box || !d2) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  size_t cells = 0;
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_distance_field: ") + why);
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)d2 | (uintptr_t)info, 16, "a device output is"));
+  HIPCHECK(hipSetDevice(m->g.device));
+  return df_run(m, box, cells, min_count, clamp, nullptr, 0, d2, device_out, info, !device_out);
+}
+
+extern "C" int revo_map_known_field(revo_map* m, const revo_map_df_box* box, uint32_t min_count, uint32_t clamp, const uint8_t* seen,
+                                    int device_seen, uint32_t min_views, uint32_t* d2, int device_out, revo_map_known_info* info) {
+  if (!m || !box || !d2 || !seen) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  size_t cells = 0;
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_known_field: ") + why);
+  TRY(map_check_side(device_seen, "device_seen"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_seen) TRY(map_check_aligned((uintptr_t)seen, 16, "the device seen volume is"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)d2 | (uintptr_t)info, 16, "a device output is"));
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  const uint8_t* d_seen = seen;
+  if (!device_seen) {
+    TRY(m->seenvol.reserve(cells, s));
+    HIPCHECK(hipMemcpyAsync(m->seenvol.p, seen, cells, hipMemcpyHostToDevice, s));
+    d_seen = (const uint8_t*)m->seenvol.p;
+  }
+  return df_run(m, box, cells, min_count, clamp, d_seen, min_views, d2, device_out, info, !device_out || !device_seen);
 }
 
 extern "C" int revo_map_distance_field_last_ms(revo_map* m, float* ms) {
@@ -326,7 +411,7 @@ extern "C" int revo_map_df_sample(revo_map* m, const revo_map_df_box* box, const
   if (!m || !box || !d2 || !xyz || !out) return fail(REVO_ERR_INVALID_ARG, "null argument");
   if (n < 1 || n > DF_MAX_POINTS) return fail(REVO_ERR_INVALID_ARG, "revo_map_df_sample: n must be 1 .. 2^24 points");
   size_t cells = 0;
-  if (const char* why = df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_df_sample: ") + why);
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_df_sample: ") + why);
   TRY(map_check_side(device_field, "device_field"));
   TRY(map_check_side(device_in, "device_in"));
   TRY(map_check_side(device_out, "device_out"));

@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -17,6 +17,7 @@
 #include "revo_internal.h"
 #include "revo_map.h"
 #include "revo_pose_host.h"
+#include "revo_carve_host.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -152,6 +153,46 @@ __device__ __forceinline__ u64 map_colour_bgr(u64 n, u64 sb, u64 sg, u64 sr) {
   return map_channel(sb, n) | (map_channel(sg, n) << 8) | (map_channel(sr, n) << 16);
 }
 
+// The per-view rule of DESIGN 19, for every unit that classifies a point in a view (revo_map_edit.hip: a voxel's mean;
+// revo_map_seen.hip: a cell's centre): one text, so both compile the same arithmetic.
+struct MapCarveView {  // one view of a launch, in device memory
+  CarveView v;
+  const float* depth;
+};
+enum { CARVE_OUTSIDE = 0, CARVE_UNKNOWN = 1, CARVE_FREE = 2, CARVE_CONFIRMED = 3, CARVE_OCCLUDED = 4, CARVE_EDGE = 5, CARVE_CLASSES = 6 };
+#define CARVE_MAX_VIEWS 64
+
+// The class of the point p in one view: the one text of the contract's rule.  Every read of the depth image lies inside a
+// window that has been tested against the image size first, and |u|, |v| < 2^20 bounds the integers the test is made on.
+__device__ __forceinline__ int map_carve_class(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel) {
+  const CarveView& c = vw.v;
+  const float x = ((c.Rc[0] * px + c.Rc[1] * py) + c.Rc[2] * pz) + c.tc[0];
+  const float y = ((c.Rc[3] * px + c.Rc[4] * py) + c.Rc[5] * pz) + c.tc[1];
+  const float z = ((c.Rc[6] * px + c.Rc[7] * py) + c.Rc[8] * pz) + c.tc[2];
+  if (!isfinite(x) || !isfinite(y) || !map_depth_ok(z, c.zmin, c.zmax)) return CARVE_OUTSIDE;
+  const float u = __fdiv_rn(c.fx * x, z) + c.cx;
+  const float v = __fdiv_rn(c.fy * y, z) + c.cy;
+  if (!(fabsf(u) < 1048576.0f) || !(fabsf(v) < 1048576.0f)) return CARVE_OUTSIDE;  // NaN / inf fail the comparison
+  const int iu = (int)floorf(u + 0.5f), iv = (int)floorf(v + 0.5f);
+  if (iu - r < 0 || iu + r > c.w - 1 || iv - r < 0 || iv + r > c.h - 1) return CARVE_OUTSIDE;
+  bool usable = true;
+  float dmin = INFINITY;
+  for (int dy = -r; dy <= r; ++dy) {
+    const float* row = vw.depth + (size_t)(iv + dy) * c.w + iu;
+    for (int dx = -r; dx <= r; ++dx) {
+      const float d = row[dx];
+      usable = usable && map_depth_ok(d, c.zmin, c.zmax);
+      dmin = fminf(dmin, d);  // only looked at when every depth is usable
+    }
+  }
+  if (!usable) return CARVE_UNKNOWN;
+  if (z < dmin - (margin + margin_rel * dmin)) return CARVE_FREE;
+  const float dc = vw.depth[(size_t)iv * c.w + iu];
+  const float mc = margin + margin_rel * dc;
+  if (fabsf(z - dc) <= mc) return CARVE_CONFIRMED;
+  return z > dc + mc ? CARVE_OCCLUDED : CARVE_EDGE;
+}
+
 // Block compaction in arrival order.  s_n (LDS) is zero behind the kernel's first barrier; every selected thread draws its
 // place in the block; behind a barrier thread 0 draws the block's base from `counter` (an unsigned total, or the u64 word of
 // an info line) with one global atomic; behind another barrier s_base + place is the thread's output index.  The pair leaves
@@ -244,7 +285,58 @@ struct revo_map {
   OwnedEvent plan_ev;
   EventTimer plan_time;
   uint32_t plan_rounds = 0;
+  // revo_map_observe / revo_map_known_field / revo_map_frontiers (revo_map_seen.hip, revo_map_field.hip): the views of a
+  // call, its counter lines, and the device copy of a host seen volume (in or out)
+  HostRows<MapCarveView> seen_views;
+  DevBuf seencnt, seenvol;
 };
+
+// The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every
+// pyramid's context and kind before any of them orders a stream, then the pyramids' depth planes (the tracker stream is
+// ordered behind their builds; nothing is refused from there on).  hv[i].depth stays the caller's pointer for a raw image;
+// *up_bytes: what the call's host images need in one upload, each rounded up to 256 bytes.
+inline int map_views_prepare(revo_map* m, int n, const revo_map_carve_view* views, int device_in, MapCarveView* hv, size_t* up_bytes) {
+  const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
+  *up_bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    const std::string at = "view " + std::to_string(i) + ": ";
+    if (const char* why = carve_view_check(&views[i], cam, m->g.w, m->g.h, &hv[i].v)) return fail(REVO_ERR_INVALID_ARG, at + why);
+    hv[i].depth = views[i].depth;
+    if (views[i].depth) {
+      if (device_in) TRY(map_check_aligned((uintptr_t)views[i].depth, 4, at + "the device depth image is"));
+      if (!device_in) *up_bytes += ((size_t)hv[i].v.w * hv[i].v.h * sizeof(float) + 255) & ~(size_t)255;
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!views[i].kf) continue;
+    const revo_ctx* pc = nullptr;
+    int batch_view = 0;
+    TRY(revo_map_source_kind_(views[i].kf, &pc, &batch_view));
+    const std::string at = "view " + std::to_string(i) + ": ";
+    if (pc != m->ctx) return fail(REVO_ERR_INVALID_ARG, at + "the pyramid belongs to another context than the map");
+    if (batch_view)
+      return fail(REVO_ERR_INVALID_ARG, at + "a batch view is not a keyframe the map calls take (pass its depth plane as a raw image)");
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!views[i].kf) continue;
+    MapSource src;
+    TRY(revo_map_source_(const_cast<revo_pyr*>(views[i].kf), &src));
+    hv[i].depth = src.depth;
+  }
+  return REVO_OK;
+}
+// The host images of the call into `images` (room for up_bytes) on stream s; hv[i].depth then names the device copy.
+inline int map_views_upload(int n, const revo_map_carve_view* views, MapCarveView* hv, char* images, hipStream_t s) {
+  size_t o = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!views[i].depth) continue;
+    const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * sizeof(float);
+    HIPCHECK(hipMemcpyAsync(images + o, views[i].depth, bytes, hipMemcpyHostToDevice, s));
+    hv[i].depth = (const float*)(images + o);
+    o += (bytes + 255) & ~(size_t)255;
+  }
+  return REVO_OK;
+}
 
 // revo_map.hip, for the other units.  map_read_stats waits for the map's stream; map_grow(live_only) is the compaction an
 // accepted subtraction ends with; map_merge_core / map_subtract_core: one merge into (subtraction from) m of the input `a` names.
@@ -253,6 +345,12 @@ int map_grow(revo_map* m, size_t newcap, bool live_only = false);
 int map_read_stats(revo_map* m, MapStats* out);
 int map_merge_core(revo_map* m, MapMergeK a, int src_kind, size_t bound, bool trusted, int keyframes);
 int map_subtract_core(revo_map* m, MapMergeK a, int src_kind, u64 dropped, u64 keyframes);
+
+// revo_map_field.hip, for revo_map_seen.hip: the box rules of DESIGN 21 (NULL if the box keeps them; *cells: its cells), and the
+// bit volume of the box's solid voxels (z-major, wz 32-bit words per z-line) enqueued on stream s into m->dfbits, with
+// k_df_occupancy's counters in `info` (NULL: m->dfcnt's line).
+const char* map_df_box_check(const revo_map_df_box* box, size_t* cells);
+int map_df_solid_bits(revo_map* m, const revo_map_df_box* box, uint32_t min_count, hipStream_t s, const unsigned** bits, unsigned* wz, u64* info = nullptr);
 
 // Room in m's table for `bound` more keys at a load <= 0.5 (the checked path inserts every new key before it decides: what
 // the map may hold + all of them); *ub: the bound of the voxels it holds now.  what: "batch", "merge".

@@ -27,6 +27,15 @@ Equal maps give equal files.
                                                         map A's distance field (revo_map_distance_field), without a GPU:
                                                         the squared distance in cells to the nearest voxel, over the map's bounds
                                                         grown by N cells (default 8); OUT.npz holds d2, lo, n, voxel
+    python -m revo_amd.mapfile observe A --views DIR -o SEEN.npz [--pad N] [--radius N] [--margin M] [--margin-rel F]
+                                                        [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S]
+                                                        what the views of DIR have looked at (revo_map_observe), without
+                                                        a GPU: one byte per cell of A's bounds grown by N cells (default 0), free
+                                                        votes and the surface bit; SEEN.npz holds seen, lo, n, voxel
+    python -m revo_amd.mapfile frontiers A --seen SEEN.npz -o CELLS.txt [--min-count N] [--min-views K]
+                                                        the free cells next to unseen space (revo_map_frontiers), one voxel index
+                                                        per line; `esdf` and `plan` take --seen SEEN.npz [--min-views K] too: the
+                                                        field then treats unseen space as an obstacle (revo_map_known_field)
     python -m revo_amd.mapfile df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt
                                                         map SRC's points registered against map DST's distance field
                                                         (revo_map_df_align), without a GPU: the pose SRC's frame ->
@@ -322,15 +331,9 @@ def carve_classes(p, view, radius, margin, margin_rel):
     return cls
 
 
-def carve_records(records, voxel, views, radius=1, min_views=1, min_count=1, max_count=0, margin=None, margin_rel=0.0):
-    """Free-space carving without a GPU: revo_map_carve_eval's contract (DESIGN 19) in vectorised numpy.  views: a list of
-    (depth [h, w] float32, T_w_c, (fx, fy, cx, cy, zmin, zmax)).  Per voxel with count >= max(min_count, 1) (and <= max_count
-    unless that is 0) and per view its class; a voxel that is `free` in at least max(min_views, 1) views is carved.  margin
-    None: the voxel edge.  -> (the carved voxels' records in ascending key order -- subtract_records(records, them) is the carved
-    map --, info dict of CARVE_INFO_KEYS, one dict of CARVE_CLASSES counts per view).  ValueError as the library's
-    REVO_ERR_INVALID_ARG."""
-    rec = as_records(records)
-    check_records(rec)
+def carve_rule_args(voxel, views, radius, margin, margin_rel):
+    """What the per-view rule runs with, checked as revo_map_carve_eval and revo_map_observe check it -> (checked views,
+    radius, margin, margin_rel).  margin None: the voxel edge."""
     if not 0 <= int(radius) <= 3:
         raise ValueError("radius must be 0 .. 3")
     margin = np.float32(voxel if margin is None else margin)
@@ -340,7 +343,19 @@ def carve_records(records, voxel, views, radius=1, min_views=1, min_count=1, max
     views = list(views)
     if not 1 <= len(views) <= 64:
         raise ValueError("a carve takes 1 .. 64 views")
-    views = [carve_view(*v) for v in views]
+    return [carve_view(*v) for v in views], int(radius), margin, margin_rel
+
+
+def carve_records(records, voxel, views, radius=1, min_views=1, min_count=1, max_count=0, margin=None, margin_rel=0.0):
+    """Free-space carving without a GPU: revo_map_carve_eval's contract (DESIGN 19) in vectorised numpy.  views: a list of
+    (depth [h, w] float32, T_w_c, (fx, fy, cx, cy, zmin, zmax)).  Per voxel with count >= max(min_count, 1) (and <= max_count
+    unless that is 0) and per view its class; a voxel that is `free` in at least max(min_views, 1) views is carved.  margin
+    None: the voxel edge.  -> (the carved voxels' records in ascending key order -- subtract_records(records, them) is the carved
+    map --, info dict of CARVE_INFO_KEYS, one dict of CARVE_CLASSES counts per view).  ValueError as the library's
+    REVO_ERR_INVALID_ARG."""
+    rec = as_records(records)
+    check_records(rec)
+    views, radius, margin, margin_rel = carve_rule_args(voxel, views, radius, margin, margin_rel)
     sel = rec["count"] >= np.uint64(max(1, int(min_count)))
     if int(max_count):
         sel &= rec["count"] <= np.uint64(int(max_count))
@@ -358,14 +373,11 @@ def carve_records(records, voxel, views, radius=1, min_views=1, min_count=1, max
     return gone.copy(), info, counts
 
 
-def carve_file(path, views_dir, camera, zrange, depth_scale=5000.0, **params):
-    """(header, records, removed header, removed records, info) of the file's map carved with the views of a `run_tum
-    --map-views` folder: depth/*.png (16-bit, metres x depth_scale), associate.txt and poses.txt (the pose of each depth
-    image by time stamp).  camera (fx, fy, cx, cy) and zrange (zmin, zmax) say how the views were taken.  The removed voxels
-    carry no dropped points and no keyframes, so the two headers add up to the file's."""
+def read_views(views_dir, camera, zrange, depth_scale=5000.0):
+    """The views of a `run_tum --map-views` folder as carve_records and observe_records take them: depth/*.png (16-bit, metres
+    x depth_scale), associate.txt and poses.txt (the pose of each depth image by time stamp)."""
     import os
     from . import tum
-    header, rec = read(path)
     rows = tum.read_associate(os.path.join(views_dir, "associate.txt"))
     poses = {round(ts, 6): T for ts, T in tum.read_poses(os.path.join(views_dir, "poses.txt"))}
     views = []
@@ -377,6 +389,16 @@ def carve_file(path, views_dir, camera, zrange, depth_scale=5000.0, **params):
         views.append((raw.astype(np.float32) / np.float32(depth_scale), T, tuple(camera) + tuple(zrange)))
     if not views:
         raise ValueError("%s holds no views" % views_dir)
+    return views
+
+
+def carve_file(path, views_dir, camera, zrange, depth_scale=5000.0, **params):
+    """(header, records, removed header, removed records, info) of the file's map carved with the views of a `run_tum
+    --map-views` folder: depth/*.png (16-bit, metres x depth_scale), associate.txt and poses.txt (the pose of each depth
+    image by time stamp).  camera (fx, fy, cx, cy) and zrange (zmin, zmax) say how the views were taken.  The removed voxels
+    carry no dropped points and no keyframes, so the two headers add up to the file's."""
+    header, rec = read(path)
+    views = read_views(views_dir, camera, zrange, depth_scale)
     gone = np.zeros(0, RAW_DTYPE)
     info = dict.fromkeys(CARVE_INFO_KEYS, 0)
     if int(params.get("min_views", 1)) <= 1:  # 64 views per carve; with min_views 1 carving in parts is carving at once
@@ -661,23 +683,185 @@ def distance_field_records(records, lo, n, min_count=1, clamp=0):
     seen), DF_NONE when the box holds none; with clamp > 0 every other value is min(value, clamp).  Written as the three
     min-plus passes z, y, x over exact integers."""
     lo, n = check_box(lo, n)
+    mask, info = solid_cells(records, lo, n, min_count)
+    d2, info["max_d2"] = _field_of(mask, clamp)
+    return d2, info
+
+
+def solid_cells(records, lo, n, min_count=1):
+    """(bool [n0, n1, n2]: the cells of the box that hold a voxel with count >= max(min_count, 1); the counters cells, solid,
+    outside, below of DF_INFO_KEYS)."""
     rec = as_records(records)
     solid = rec["count"] >= np.uint64(max(1, int(min_count)))
     k = key_axes(rec["key"][solid]) - lo
     inside = np.all((k >= 0) & (k < n), axis=1)
     k = k[inside]
-    g = np.full(tuple(int(x) for x in n), _DF_INF, np.int32)
-    g[k[:, 0], k[:, 1], k[:, 2]] = 0
+    mask = np.zeros(tuple(int(x) for x in n), bool)
+    mask[k[:, 0], k[:, 1], k[:, 2]] = True
+    return mask, {"cells": int(mask.size), "solid": int(inside.sum()), "outside": int(solid.sum() - inside.sum()), "below": int((~solid).sum())}
+
+
+def _field_of(obstacles, clamp):
+    """(d2, max_d2) of revo_map_distance_field's definition over a bool volume of obstacle cells."""
+    g = np.where(obstacles, np.int32(0), _DF_INF)
     for axis in (2, 1, 0):
         g = _min_plus(g, axis)
     none = g >= _DF_INF
     g = g.astype(np.uint32)
     if int(clamp) > 0:
         g = np.minimum(g, np.uint32(min(int(clamp), 0xFFFFFFFF)))
-    d2 = np.where(none, DF_NONE, g)
-    info = {"cells": int(d2.size), "solid": int(inside.sum()), "outside": int(solid.sum() - inside.sum()), "below": int((~solid).sum()),
-            "max_d2": int(g[~none].max()) if (~none).any() else 0}
+    return np.where(none, DF_NONE, g), int(g[~none].max()) if (~none).any() else 0
+
+
+SEEN_INFO_KEYS = ("cells", "cells_free", "cells_surface", "votes", "newly_known")
+KNOWN_INFO_KEYS = DF_INFO_KEYS + ("unknown", "known_free")
+SEEN_VOTES, SEEN_SURFACE = np.uint8(0x7F), np.uint8(0x80)
+
+
+def seen_centres(lo, n, voxel):
+    """[cells, 3] float32: the centres of the box's cells in the volume's order (z fastest), ((float32)(lo + a) + 0.5) * voxel
+    with the product rounded once."""
+    ax = [(np.arange(int(lo[i]), int(lo[i]) + int(n[i])).astype(np.float32) + np.float32(0.5)) * np.float32(voxel) for i in range(3)]
+    return np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+
+
+def seen_update(seen_in, f, s):
+    """The byte rule of revo_map_observe: ((in | s << 7) & 0x80) | min(127, (in & 0x7F) + f), elementwise -> uint8."""
+    b = np.asarray(seen_in, np.uint8).astype(np.int64)
+    return (((b | (np.asarray(s, np.int64) << 7)) & 0x80) | np.minimum(127, (b & 0x7F) + np.asarray(f, np.int64))).astype(np.uint8)
+
+
+def observe_records(voxel, lo, n, views, radius=1, margin=None, margin_rel=0.0, seen=None, chunk=1 << 20):
+    """The seen volume without a GPU: revo_map_observe's contract in vectorised numpy, through carve_classes -- the
+    class rule carve_records uses.  views: as carve_records takes them; seen: a uint8 [n0, n1, n2] volume to accumulate into
+    (it is not changed), None for a fresh one.  -> (seen uint8 [n0, n1, n2], info dict of SEEN_INFO_KEYS, one dict of
+    CARVE_CLASSES counts per view).  ValueError as the library's REVO_ERR_INVALID_ARG."""
+    lo, n = check_box(lo, n)
+    views, radius, margin, margin_rel = carve_rule_args(voxel, views, radius, margin, margin_rel)
+    shape = tuple(int(x) for x in n)
+    if seen is None:
+        before = np.zeros(shape, np.uint8)
+    else:
+        before = np.asarray(seen)
+        if before.dtype != np.uint8 or before.shape != shape:
+            raise ValueError("the volume to accumulate into is a uint8 array of the box's shape")
+    p = seen_centres(lo, n, voxel)
+    f, s = np.zeros(len(p), np.int64), np.zeros(len(p), np.int64)
+    counts = [dict.fromkeys(CARVE_CLASSES, 0) for _ in views]
+    for a in range(0, len(p), int(chunk)):
+        for vw, cnt in zip(views, counts):
+            cls = carve_classes(p[a:a + chunk], vw, radius, margin, margin_rel)
+            f[a:a + chunk] += cls == 2
+            s[a:a + chunk] |= cls == 3
+            for i, name in enumerate(CARVE_CLASSES):
+                cnt[name] += int((cls == i).sum())
+    out = seen_update(before.reshape(-1), f, s).reshape(shape)
+    info = {"cells": int(out.size), "cells_free": int(((out & SEEN_VOTES) != 0).sum()), "cells_surface": int(((out & SEEN_SURFACE) != 0).sum()),
+            "votes": int(f.sum()), "newly_known": int(((before == 0) & (out != 0)).sum())}
+    return out, info, counts
+
+
+def seen_free(seen, min_views=1):
+    """bool: the cells with at least max(min_views, 1) free votes."""
+    return (np.asarray(seen, np.uint8) & SEEN_VOTES) >= max(1, int(min_views))
+
+
+def seen_known(seen, min_views=1, solid=None):
+    """bool: the known cells -- free, with the surface bit, or (solid: a bool volume) solid."""
+    k = seen_free(seen, min_views) | ((np.asarray(seen, np.uint8) & SEEN_SURFACE) != 0)
+    return k if solid is None else k | np.asarray(solid, bool)
+
+
+def _seen_volume(seen, n):
+    seen = np.asarray(seen)
+    if seen.dtype != np.uint8 or seen.shape != tuple(int(x) for x in n):
+        raise ValueError("the seen volume is a uint8 array of the box's shape")
+    return seen
+
+
+def known_field_records(records, lo, n, seen, min_count=1, clamp=0, min_views=1):
+    """revo_map_known_field restated: distance_field_records over the obstacle set solid + unknown -> (d2 uint32 [n0, n1, n2],
+    info dict of KNOWN_INFO_KEYS)."""
+    lo, n = check_box(lo, n)
+    seen = _seen_volume(seen, n)
+    solid, info = solid_cells(records, lo, n, min_count)
+    unknown = ~seen_known(seen, min_views, solid)
+    d2, info["max_d2"] = _field_of(solid | unknown, clamp)
+    info["unknown"] = int(unknown.sum())
+    info["known_free"] = info["cells"] - info["solid"] - info["unknown"]
     return d2, info
+
+
+def frontier_records(records, lo, n, seen, min_count=1, min_views=1):
+    """revo_map_frontiers restated: [k, 3] int32 absolute voxel indices, in ascending order of the cell's place in the box, of
+    the cells that are not solid, have >= max(min_views, 1) free votes and have a face neighbour inside the box that is unknown."""
+    lo, n = check_box(lo, n)
+    seen = _seen_volume(seen, n)
+    solid, _ = solid_cells(records, lo, n, min_count)
+    unknown = ~seen_known(seen, min_views, solid)
+    near = np.zeros(unknown.shape, bool)
+    for axis in range(3):
+        a, b = [slice(None)] * 3, [slice(None)] * 3
+        a[axis], b[axis] = slice(1, None), slice(None, -1)
+        near[tuple(a)] |= unknown[tuple(b)]
+        near[tuple(b)] |= unknown[tuple(a)]
+    cells = np.argwhere(~solid & seen_free(seen, min_views) & near)
+    return (cells + lo).astype(np.int32).reshape(-1, 3)
+
+
+def explore_records(records, lo, n, voxel, seen, start, clearance, min_count=1, min_views=1, max_len=4096):
+    """The whole route without a GPU: the known field, the frontiers, the cost-to-go with the frontiers as goals at the
+    clearance (metres), and the path from `start` (a voxel index) -> (d2, frontiers, cost, plan info, (cells, status, cost))."""
+    d2, _ = known_field_records(records, lo, n, seen, min_count, 0, min_views)
+    fr = frontier_records(records, lo, n, seen, min_count, min_views)
+    if len(fr) == 0:
+        raise ValueError("the seen volume has no frontier cell")
+    cost, info = plan_records(d2, lo, n, plan_seeds(fr), plan_r2(clearance, voxel))
+    if info["seeds_used"] == 0:  # a frontier cell touches unseen space: d2 = 1 in the known field
+        raise ValueError("no frontier cell keeps the clearance: unseen space counts against it, so the route needs r2 = 1 (at most one voxel edge)")
+    return d2, fr, cost, info, plan_paths(cost, lo, n, np.asarray(start, np.int64).reshape(1, 3), max_len)[0]
+
+
+def write_seen(path, seen, lo, voxel):
+    """The .npz of a seen volume: seen (uint8 [n0, n1, n2]), lo, n (int32 [3]), voxel (float32)."""
+    seen = np.ascontiguousarray(seen, np.uint8)
+    with open(path, "wb") as f:
+        np.savez(f, seen=seen, lo=np.asarray(lo, np.int32).reshape(3), n=np.asarray(seen.shape, np.int32), voxel=np.float32(voxel))
+    return path
+
+
+def read_seen(path):
+    """(seen, lo, voxel) of a file write_seen wrote; ValueError if its arrays do not fit together."""
+    with np.load(path) as z:
+        if not all(k in z.files for k in ("seen", "lo", "n", "voxel")):
+            raise ValueError("%s is not a seen-volume file (seen, lo, n, voxel)" % path)
+        seen, lo, n, voxel = z["seen"], z["lo"], z["n"], z["voxel"]
+    if seen.dtype != np.uint8 or seen.ndim != 3 or lo.shape != (3,) or list(seen.shape) != [int(x) for x in n]:
+        raise ValueError("%s: a seen volume is a 3-D uint8 array of the shape its n states" % path)
+    check_box(lo, n)
+    return seen, lo.astype(np.int32), float(np.float32(voxel))
+
+
+def _seen_for(path, voxel):
+    """The seen volume of a file for a map of edge `voxel`."""
+    seen, lo, v = read_seen(path)
+    if np.float32(v).tobytes() != np.float32(voxel).tobytes():
+        raise ValueError("%s was observed at voxels of %g m, the map has %g m" % (path, v, voxel))
+    return seen, lo, np.asarray(seen.shape, np.int64)
+
+
+def observe_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, **params):
+    """(seen, lo, voxel, info) of the views of a `run_tum --map-views` folder over the bounds of the file's map grown by `pad`
+    cells; more than 64 views accumulate in parts of 64."""
+    header, rec = read(path)
+    views = read_views(views_dir, camera, zrange, depth_scale)
+    lo, hi, _ = bounds_records(rec)
+    lo, n = padded_box(lo, hi, pad)
+    seen, info = None, None
+    for i in range(0, len(views), 64):
+        seen, part, _ = observe_records(header["voxel"], lo, n, views[i:i + 64], seen=seen, **params)
+        info = part if info is None else dict(part, votes=info["votes"] + part["votes"], newly_known=info["newly_known"] + part["newly_known"])
+    return seen, lo.astype(np.int32), header["voxel"], info
 
 
 def df_sample(d2, lo, voxel, points):
@@ -1092,16 +1276,21 @@ def read_cost(path):
     return cost, lo.astype(np.int32), float(np.float32(voxel)), int(r2)
 
 
-def plan_file(path, goals, starts, clearance, pad=None, max_len=1 << 20, min_count=1):
+def plan_file(path, goals, starts, clearance, pad=None, max_len=1 << 20, min_count=1, seen=None, min_views=1):
     """Plans through the file's map: the distance field over its bounds grown by `pad` cells (by default the clearance in
     cells plus 2), the cost field from `goals` at the clearance (metres), and the paths from `starts` (both voxel indices)
-    -> (cost, lo, voxel, r2, info, paths)."""
+    -> (cost, lo, voxel, r2, info, paths).  With seen (a write_seen file) the field is the known field over that volume's
+    box: the way keeps the clearance from unseen space too."""
     header, rec = read(path)
     voxel = header["voxel"]
     r2 = plan_r2(clearance, voxel)
-    lo, hi, _ = bounds_records(rec, min_count)
-    lo, n = padded_box(lo, hi, int(np.ceil(np.sqrt(r2))) + 2 if pad is None else pad)
-    d2, _ = distance_field_records(rec, lo, n, min_count)
+    if seen is not None:
+        vol, lo, n = _seen_for(seen, voxel)
+        d2, _ = known_field_records(rec, lo, n, vol, min_count, 0, min_views)
+    else:
+        lo, hi, _ = bounds_records(rec, min_count)
+        lo, n = padded_box(lo, hi, int(np.ceil(np.sqrt(r2))) + 2 if pad is None else pad)
+        d2, _ = distance_field_records(rec, lo, n, min_count)
     cost, info = plan_records(d2, lo, n, goals, r2)
     return cost, lo.astype(np.int32), voxel, r2, info, plan_paths(cost, lo, n, starts, max_len)
 
@@ -1126,9 +1315,14 @@ def read_field(path):
     return d2, lo.astype(np.int32), float(np.float32(voxel))
 
 
-def esdf_file(path, pad=8, min_count=1, clamp=0):
-    """(d2, lo, voxel, info) of the file's map over its bounds grown by `pad` cells."""
+def esdf_file(path, pad=8, min_count=1, clamp=0, seen=None, min_views=1):
+    """(d2, lo, voxel, info) of the file's map over its bounds grown by `pad` cells; with seen (a write_seen file) the known
+    field over that volume's box."""
     header, rec = read(path)
+    if seen is not None:
+        vol, lo, n = _seen_for(seen, header["voxel"])
+        d2, info = known_field_records(rec, lo, n, vol, min_count, clamp, min_views)
+        return d2, lo.astype(np.int32), header["voxel"], info
     lo, hi, _ = bounds_records(rec, min_count)
     lo, n = padded_box(lo, hi, pad)
     d2, info = distance_field_records(rec, lo, n, min_count, clamp)
@@ -1270,8 +1464,47 @@ def main(argv=None):
                 print("%s: %d voxels (%s carved with the views of %s: %d voxels, %d points removed)"
                       % (val["-o"][0], len(rec), pos[0], val["--views"][0], len(gone), int(gone["count"].sum(dtype=np.uint64))))
                 return 0
+        if cmd == "observe" and "-o" in args and "--views" in args:
+            opt = {"-o": 1, "--views": 1, "--pad": 1, "--radius": 1, "--margin": 1, "--margin-rel": 1, "--camera": 4, "--zrange": 2, "--depth-scale": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1:
+                params = {name: conv(val[o][0]) for o, name, conv in (("--radius", "radius", int), ("--margin", "margin", float),
+                                                                       ("--margin-rel", "margin_rel", float), ("--pad", "pad", int)) if o in val}
+                camera = [float(x) for x in val.get("--camera", (525.0, 525.0, 319.5, 239.5))]  # the TUM default camera
+                zrange = [float(x) for x in val.get("--zrange", (0.1, 5.2))]
+                seen, lo, voxel, info = observe_file(pos[0], val["--views"][0], camera, zrange, float(val.get("--depth-scale", [5000.0])[0]), **params)
+                write_seen(val["-o"][0], seen, lo, voxel)
+                print("%s: %d x %d x %d cells from %s (the views of %s over %s): %d free, %d with a surface"
+                      % ((val["-o"][0],) + seen.shape + (lo.tolist(), val["--views"][0], pos[0], info["cells_free"], info["cells_surface"])))
+                return 0
+        if cmd == "frontiers" and "-o" in args and "--seen" in args:
+            opt = {"-o": None, "--seen": None, "--min-count": "1", "--min-views": "1"}
+            pos, i = [], 0
+            while i < len(args):
+                if args[i] in opt and i + 1 < len(args):
+                    opt[args[i]] = args[i + 1]
+                    i += 2
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1 and opt["-o"] is not None and opt["--seen"] is not None:
+                header, rec = read(pos[0])
+                vol, lo, n = _seen_for(opt["--seen"], header["voxel"])
+                cells = frontier_records(rec, lo, n, vol, int(opt["--min-count"]), int(opt["--min-views"]))
+                with open(opt["-o"], "w") as f:
+                    f.write("".join("%d %d %d\n" % tuple(c) for c in cells.tolist()))
+                print("%s: %d frontier cells of %s seen through %s" % (opt["-o"], len(cells), pos[0], opt["--seen"]))
+                return 0
         if cmd == "esdf" and "-o" in args:
-            opt = {"-o": None, "--pad": "8", "--min-count": "1", "--clamp": "0"}
+            opt = {"-o": None, "--pad": "8", "--min-count": "1", "--clamp": "0", "--seen": None, "--min-views": "1"}
             pos, i = [], 0
             while i < len(args):
                 if args[i] in opt and i + 1 < len(args):
@@ -1281,10 +1514,12 @@ def main(argv=None):
                     pos.append(args[i])
                     i += 1
             if len(pos) == 1 and opt["-o"] is not None:
-                d2, lo, voxel, info = esdf_file(pos[0], int(opt["--pad"]), int(opt["--min-count"]), int(opt["--clamp"]))
+                d2, lo, voxel, info = esdf_file(pos[0], int(opt["--pad"]), int(opt["--min-count"]), int(opt["--clamp"]), opt["--seen"],
+                                                int(opt["--min-views"]))
                 write_field(opt["-o"], d2, lo, voxel)
-                print("%s: %d x %d x %d cells from %s (%s), %d voxels in the box, largest d2 %d"
-                      % ((opt["-o"],) + d2.shape + (lo.tolist(), pos[0], info["solid"], info["max_d2"])))
+                print("%s: %d x %d x %d cells from %s (%s), %d voxels in the box%s, largest d2 %d"
+                      % ((opt["-o"],) + d2.shape + (lo.tolist(), pos[0], info["solid"],
+                                                    ", %d unknown cells" % info["unknown"] if "unknown" in info else "", info["max_d2"])))
                 return 0
         if cmd == "df-align" and "-o" in args:
             opt = {"-o": None, "--init": None, "--max-dist": None, "--pad": None}
@@ -1307,7 +1542,7 @@ def main(argv=None):
                          float(np.sqrt(rec["S"][27] / max(int(rec["matched"]), 1)))))
                 return 0 if status != ALIGN_LOST else 1
         if cmd == "plan" and "-o" in args:
-            opt = {"-o": 1, "--goal": 3, "--start": 3, "--clearance": 1, "--pad": 1, "--cost": 1}
+            opt = {"-o": 1, "--goal": 3, "--start": 3, "--clearance": 1, "--pad": 1, "--cost": 1, "--seen": 1, "--min-views": 1}
             val, pos, i = {}, [], 0
             while i < len(args):
                 k = opt.get(args[i])
@@ -1321,7 +1556,9 @@ def main(argv=None):
                 goals = [[int(x) for x in g] for g in val["--goal"]]
                 starts = [[int(x) for x in s] for s in val["--start"]]
                 cost, lo, voxel, r2, info, paths = plan_file(pos[0], goals, starts, float(val["--clearance"][-1][0]),
-                                                             None if "--pad" not in val else int(val["--pad"][-1][0]))
+                                                             None if "--pad" not in val else int(val["--pad"][-1][0]),
+                                                             seen=val["--seen"][-1][0] if "--seen" in val else None,
+                                                             min_views=int(val.get("--min-views", [["1"]])[-1][0]))
                 if "--cost" in val:
                     write_cost(val["--cost"][-1][0], cost, lo, voxel, r2)
                 if info["seeds_used"] == 0:
@@ -1352,8 +1589,11 @@ def main(argv=None):
     print("usage: python -m revo_amd.mapfile info FILE... | merge OUT FILE... | subtract A B -o OUT | coarsen A SHIFT -o OUT | "
           "transform A POSE.txt -o OUT [--voxel V] [--min-count N] | carve A --views DIR -o OUT [--removed R] [--radius N] [--margin M] "
           "[--margin-rel F] [--min-views K] [--min-count N] [--max-count N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
-          "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] | df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt | "
-          "plan A --goal X Y Z [--goal ...] --start X Y Z [--start ...] --clearance M [--pad N] -o PATH.txt [--cost OUT.npz] | "
+          "observe A --views DIR -o SEEN.npz [--pad N] [--radius N] [--margin M] [--margin-rel F] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] "
+          "[--depth-scale S] | frontiers A --seen SEEN.npz -o CELLS.txt [--min-count N] [--min-views K] | "
+          "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] [--seen SEEN.npz] [--min-views K] | df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt | "
+          "plan A --goal X Y Z [--goal ...] --start X Y Z [--start ...] --clearance M [--pad N] [--seen SEEN.npz] [--min-views K] -o PATH.txt "
+          "[--cost OUT.npz] | "
           "ply FILE [OUT.ply]")
     return 2
 

@@ -341,6 +341,24 @@ class MapPlanPath(C.Structure):
 assert (C.sizeof(MapPlanSeed), C.sizeof(MapPlanInfo), C.sizeof(MapPlanPath)) == (16, 64, 16)
 
 
+class MapObserveParams(C.Structure):
+    """revo_map_observe_params (include/revo_hip.h), 16 bytes: the pixel window, whether the call accumulates, the margins."""
+    _fields_ = [("radius", C.c_int32), ("accumulate", C.c_uint32), ("margin", C.c_float), ("margin_rel", C.c_float)]
+
+
+class MapObserveInfo(C.Structure):
+    """revo_map_observe_info (include/revo_hip.h), 64 bytes: integer sums of an observe call."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "cells_free", "cells_surface", "votes", "newly_known")] + [("reserved", C.c_uint64 * 3)]
+
+
+class MapKnownInfo(C.Structure):
+    """revo_map_known_info (include/revo_hip.h), 64 bytes: revo_map_df_info's five words, then unknown and known_free."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "solid", "outside", "below", "max_d2", "unknown", "known_free", "reserved")]
+
+
+assert (C.sizeof(MapObserveParams), C.sizeof(MapObserveInfo), C.sizeof(MapKnownInfo)) == (16, 64, 64)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
