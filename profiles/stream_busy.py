@@ -11,7 +11,7 @@ cols = [r[1] for r in db.execute("pragma table_info(kernels)")]
 sid = "stream_id" if "stream_id" in cols else "queue_id"
 rows = list(db.execute("select name, start, end, %s from kernels order by start" % sid))
 short = lambda n: n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-trk = [i for i, r in enumerate(rows) if "k_track<false>" in r[0]]
+trk = [i for i, r in enumerate(rows) if "k_track<false" in r[0]]  # k_track<false> until round 6, k_track<false, false> since
 first = int(sys.argv[2]) if len(sys.argv) > 2 else 14
 count = int(sys.argv[3]) if len(sys.argv) > 3 else 30
 t_idx = trk[first:first + count]

@@ -16,6 +16,7 @@
 // Exactness: every integer stage is bit-exact by construction; float stages
 // keep the reference's operation order and are compiled with -ffp-contract=off.
 #include "revo_dev.h"
+#include "revo_nms_px.h"
 #include <type_traits>
 
 namespace {
@@ -248,35 +249,12 @@ __device__ __forceinline__ uint32_t as_u32(s2v v) { return __builtin_bit_cast(ui
 // two bytes of the 8-byte value {hi:lo} zero-extended into the halves of a dword (v_perm_b32, selector 0x0c = 0x00)
 #define PAIR(hi, lo, sel) as_s2(__builtin_amdgcn_perm((hi), (lo), (sel)))
 
-// NMS of one pixel (cv::Canny): its 3x3 neighbourhood of |grad|^2 by value, its own gradient; sets bit k of cand / strong
-__device__ __forceinline__ void nms_px(int k, int aL, int aM, int aR, int bL, int m, int bR, int cL, int cM, int cR, uint32_t dxy,
-                                       int low, int high, uint32_t& cb, uint32_t& sb) {
-  const int TG22 = 13573;  // (int)(0.41421356...*(1<<15) + 0.5)
-  const s2v v = as_s2(dxy);
-  const s2v z = {0, 0};
-  const uint32_t ab = as_u32(__builtin_elementwise_max(v, z - v));  // |dx| | |dy| << 16
-  const int ax = (int)(ab & 0xffffu);
-  const int ay15 = (int)((ab >> 1) & 0x7fff8000u);                  // |dy| << 15
-  const int t22 = ax * TG22;
-  const bool horiz = ay15 < t22;
-  const bool vert = ay15 > t22 + (ax << 16);
-  const bool neg = (int)(dxy ^ (dxy << 16)) < 0;                    // sign(dx) != sign(dy)
-  const int diag_a = neg ? aR : aL;
-  const int diag_b = neg ? cL : cR;
-  const int a = horiz ? bL : (vert ? aM : diag_a);
-  const int b = horiz ? bR : (vert ? cM : diag_b);
-  const bool ge = horiz || vert;                                    // m > a && m >= b on the axes, m > both on the diagonals
-  const bool is_max = (m > a) & (ge ? (m >= b) : (m > b));
-  const bool c = (m > low) & is_max;
-  cb |= c ? (1u << k) : 0u;
-  sb |= (c & (m > high)) ? (1u << k) : 0u;
-}
 #define NMS_R 6
 
-// FOUR pixels per thread (columns -1 .. 4 in flight; an 8-pixel form of the same kernel, columns -1 .. 8, existed until round 4): ~60 registers instead of
-// 104.  It runs ~14 % more instructions (the halo columns are shared by fewer outputs), but the build shares every CU
-// with two resident tracker workgroups (2 x 168 VGPRs per SIMD lane slot): 176 registers are left, i.e. ONE wave per SIMD
-// of the 8-pixel kernel (42 us alone, 82-89 us in the pipelined step) against two or three of this one.
+// FOUR pixels per thread (columns -1 .. 4 in flight; an 8-pixel form of the same kernel, columns -1 .. 8, existed until round 4): 62 registers instead of
+// 104.  It runs ~14 % more instructions (the halo columns are shared by fewer outputs), but the build shares every SIMD
+// with two resident tracker waves (160 VGPRs allocated each): 192 registers are left, i.e. ONE wave per SIMD of the 8-pixel
+// kernel (42 us alone, 82-89 us in the pipelined step) against THREE of this one (<= 64 registers; two at 65-72).
 struct HRow4 { s2v d[3], s[3]; };  // column pairs (-1,0) (1,2) (3,4)
 __device__ __forceinline__ HRow4 hrow4(uint32_t prev, uint32_t m0, uint32_t next) {  // prev = g[-4..-1], m0 = g[0..3], next = g[4..7]
   const s2v E0 = PAIR(0u, prev, 0x0c030c02u), E1 = PAIR(0u, m0, 0x0c010c00u), E2 = PAIR(0u, m0, 0x0c030c02u), E3 = PAIR(0u, next, 0x0c010c00u);
@@ -288,7 +266,7 @@ __device__ __forceinline__ HRow4 hrow4(uint32_t prev, uint32_t m0, uint32_t next
 }
 struct MRow4 { int v0, v1, v2, v3, v4, v5; };   // |grad|^2 of columns -1..4
 struct DRow4 { uint32_t v0, v1, v2, v3; };      // (dx | dy << 16) of columns 0..3
-__device__ __forceinline__ void mag_row4(const HRow4& a, const HRow4& b, const HRow4& c, uint32_t cm_left, uint32_t cm_right, bool valid,
+__device__ __forceinline__ void mag_row4(const HRow4& a, const HRow4& b, const HRow4& c, bool has_left, bool has_right, bool valid,
                                          MRow4& m, DRow4& dxy) {
   uint32_t lo[3], hi[3];
 #pragma unroll
@@ -298,26 +276,32 @@ __device__ __forceinline__ void mag_row4(const HRow4& a, const HRow4& b, const H
     lo[k] = __builtin_amdgcn_perm(as_u32(dy), as_u32(dx), 0x05040100u);
     hi[k] = __builtin_amdgcn_perm(as_u32(dy), as_u32(dx), 0x07060302u);
   }
-  const uint32_t rv = valid ? ~0u : 0u;
-#define MAG2(x) __builtin_amdgcn_sdot2(as_s2(x), as_s2(x), 0, false)
-  m.v0 = MAG2(lo[0]) & (int)(cm_left & rv);
-  m.v1 = MAG2(hi[0]) & (int)rv;
-  m.v2 = MAG2(lo[1]) & (int)rv;
-  m.v3 = MAG2(hi[1]) & (int)rv;
-  m.v4 = MAG2(lo[2]) & (int)rv;
-  m.v5 = MAG2(hi[2]) & (int)(cm_right & rv);
+  // a magnitude outside the image (row, or the halo column at the row's end) is 0: one select each, the conditions are lane masks
+  const bool vl = valid && has_left, vr = valid && has_right;
+  // clamp = true selects the three-operand v_dot2_i32_i16 (the two-operand form accumulates into its destination and costs a
+  // v_mov 0 each); the sum is at most 2 * 1020^2, so the clamp never acts
+#define MAG2(x) __builtin_amdgcn_sdot2(as_s2(x), as_s2(x), 0, true)
+  m.v0 = vl ? MAG2(lo[0]) : 0;
+  m.v1 = valid ? MAG2(hi[0]) : 0;
+  m.v2 = valid ? MAG2(lo[1]) : 0;
+  m.v3 = valid ? MAG2(hi[1]) : 0;
+  m.v4 = valid ? MAG2(lo[2]) : 0;
+  m.v5 = vr ? MAG2(hi[2]) : 0;
 #undef MAG2
   dxy.v0 = hi[0]; dxy.v1 = lo[1]; dxy.v2 = hi[1]; dxy.v3 = lo[2];
 }
-__device__ __forceinline__ void nms_row4(const MRow4& A, const MRow4& B, const MRow4& C, const DRow4& d, int low, int high,
-                                         uint32_t* cand, uint32_t* strong) {
-  uint32_t cb = 0, sb = 0;
-  nms_px(0, A.v0, A.v1, A.v2, B.v0, B.v1, B.v2, C.v0, C.v1, C.v2, d.v0, low, high, cb, sb);
-  nms_px(1, A.v1, A.v2, A.v3, B.v1, B.v2, B.v3, C.v1, C.v2, C.v3, d.v1, low, high, cb, sb);
-  nms_px(2, A.v2, A.v3, A.v4, B.v2, B.v3, B.v4, C.v2, C.v3, C.v4, d.v2, low, high, cb, sb);
-  nms_px(3, A.v3, A.v4, A.v5, B.v3, B.v4, B.v5, C.v3, C.v4, C.v5, d.v3, low, high, cb, sb);
-  *cand = cb;
-  *strong = sb;
+// NMS of the row's four pixels (revo_nms_px.h, threshold form): rows A, B, C of |grad|^2, B1 / C1 = B - 1 / C - 1 where a pixel
+// needs them (bR - 1 of pixel k is B1[k + 2], cM - 1 is C1[k + 1]); pixel 3 is pushed first, so bit k is pixel k
+struct MRow4m1 { int v1, v2, v3, v4, v5; };     // |grad|^2 - 1 of columns 0..4
+__device__ __forceinline__ MRow4m1 minus1_row4(const MRow4& m) { return {m.v1 - 1, m.v2 - 1, m.v3 - 1, m.v4 - 1, m.v5 - 1}; }
+__device__ __forceinline__ void nms_row4(const MRow4& A, const MRow4& B, const MRow4m1& B1, const MRow4& C, const MRow4m1& C1, const DRow4& d,
+                                         int low, int low_high, uint32_t* cand, uint32_t* strong) {
+  const NmsOut p3 = nms_px_thr(A.v3, A.v4, A.v5, B.v3, B.v4, B1.v5, C.v3, C1.v4, C.v5, d.v3, low, low_high);
+  const NmsOut p2 = nms_px_thr(A.v2, A.v3, A.v4, B.v2, B.v3, B1.v4, C.v2, C1.v3, C.v4, d.v2, low, low_high);
+  const NmsOut p1 = nms_px_thr(A.v1, A.v2, A.v3, B.v1, B.v2, B1.v3, C.v1, C1.v2, C.v3, d.v1, low, low_high);
+  const NmsOut p0 = nms_px_thr(A.v0, A.v1, A.v2, B.v0, B.v1, B1.v2, C.v0, C1.v1, C.v2, d.v0, low, low_high);
+  *cand = nms_push(nms_push(nms_push(p3.cand >> 31, p2.cand), p1.cand), p0.cand);
+  *strong = nms_push(nms_push(nms_push(p3.strong >> 31, p2.strong), p1.strong), p0.strong);
 }
 __global__ void __launch_bounds__(256) k_canny_nms4(PyrGeom g, FramePlanes pl) {
   BUILD_PRIO();
@@ -340,21 +324,21 @@ __global__ void __launch_bounds__(256) k_canny_nms4(PyrGeom g, FramePlanes pl) {
   const bool has_prev = x > 0, has_next = x + 4 < w;
   const int xo = active ? x : 0;
   const int o_prev = (active && has_prev) ? xo - 4 : xo, o_next = (active && has_next) ? xo + 4 : xo;
-  const uint32_t cm_left = (active && has_prev) ? ~0u : 0u, cm_right = (active && has_next) ? ~0u : 0u;
   struct Raw { uint32_t prev, m0, next; };
   auto load_raw = [&](int r) -> Raw {
-    const int rr = clampi(r, 0, h - 1);  // BORDER_REPLICATE
-    const uint8_t* row = gray + (size_t)rr * w;
+    // BORDER_REPLICATE.  The level's plane is a wave-uniform base; a 32-bit byte offset per lane (a level has < 2^24 rows and
+    // columns and < 2^32 pixels) keeps three offsets in registers instead of three pointers and needs one mad per load
+    const uint32_t rr = (uint32_t)clampi(r, 0, h - 1);
     Raw q;
-    q.m0 = *reinterpret_cast<const uint32_t*>(row + xo);
-    q.prev = *reinterpret_cast<const uint32_t*>(row + o_prev);
-    q.next = *reinterpret_cast<const uint32_t*>(row + o_next);
+    q.m0 = *reinterpret_cast<const uint32_t*>(gray + (__umul24(rr, (uint32_t)w) + (uint32_t)xo));
+    q.prev = *reinterpret_cast<const uint32_t*>(gray + (__umul24(rr, (uint32_t)w) + (uint32_t)o_prev));
+    q.next = *reinterpret_cast<const uint32_t*>(gray + (__umul24(rr, (uint32_t)w) + (uint32_t)o_next));
     return q;
   };
+  // BORDER_REPLICATE at the row's ends: one byte permute takes the neighbour word, or the edge pixel four times
+  const uint32_t sel_prev = has_prev ? 0x03020100u : 0x04040404u, sel_next = has_next ? 0x03020100u : 0x07070707u;
   auto make_hrow = [&](Raw q) -> HRow4 {
-    if (!has_prev) q.prev = (q.m0 & 0xffu) * 0x01010101u;
-    if (!has_next) q.next = (q.m0 >> 24) * 0x01010101u;
-    return hrow4(q.prev, q.m0, q.next);
+    return hrow4(__builtin_amdgcn_perm(q.m0, q.prev, sel_prev), q.m0, __builtin_amdgcn_perm(q.m0, q.next, sel_next));
   };
   HRow4 H0, H1, H2;
   MRow4 M0, M1, M2;
@@ -362,13 +346,15 @@ __global__ void __launch_bounds__(256) k_canny_nms4(PyrGeom g, FramePlanes pl) {
   {
     const Raw r0 = load_raw(y0 - 2), r1 = load_raw(y0 - 1), r2 = load_raw(y0), r3 = load_raw(y0 + 1);
     H0 = make_hrow(r0); H1 = make_hrow(r1); H2 = make_hrow(r2);
-    mag_row4(H0, H1, H2, cm_left, cm_right, active && y0 - 1 >= 0, M0, D0);   // magnitude row y0 - 1
+    mag_row4(H0, H1, H2, has_prev, has_next, active && y0 - 1 >= 0, M0, D0);   // magnitude row y0 - 1
     H0 = make_hrow(r3);
   }
   Raw ahead = load_raw(y0 + 2);
-  mag_row4(H1, H2, H0, cm_left, cm_right, active, M1, D1);                    // magnitude row y0
-  uint2* out = pl.cs[l] + ((size_t)f * h + y0) * lv.wpr + (xg >> 3);
+  mag_row4(H1, H2, H0, has_prev, has_next, active, M1, D1);                    // magnitude row y0
+  uint2* out = pl.cs[l] + (size_t)f * h * lv.wpr;                             // wave-uniform; the lane's word is a 32-bit index
+  const uint32_t ow = (uint32_t)y0 * (uint32_t)lv.wpr + (uint32_t)(xg >> 3);
   const int sh = 4 * (threadIdx.x & 7);
+  const int low_high = max(g.canny_low, g.canny_high);
   auto emit = [&](int i, uint32_t cb, uint32_t sb) {
     // eight threads' nibbles -> one word (DPP: two quad permutes, then the other quad through row_half_mirror)
     uint32_t cw = cb << sh, sw = sb << sh;
@@ -378,15 +364,15 @@ __global__ void __launch_bounds__(256) k_canny_nms4(PyrGeom g, FramePlanes pl) {
     sw |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sw, 0x4E, 0xf, 0xf, true);
     cw |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cw, 0x141, 0xf, 0xf, true);  // row_half_mirror: lane i <-> 7 - i
     sw |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sw, 0x141, 0xf, 0xf, true);
-    if ((threadIdx.x & 7) == 0 && y0 + i < h) out[(size_t)i * lv.wpr] = make_uint2(cw, sw);
+    if ((threadIdx.x & 7) == 0 && y0 + i < h) out[ow + (uint32_t)(i * lv.wpr)] = make_uint2(cw, sw);
   };
 #define NMS_STEP4(i, Ha, Hb, Hc, Ma, Mb, Mc, Db, Dc)                                  \
   {                                                                                   \
     Hc = make_hrow(ahead);                                                            \
     if ((i) < NMS_R - 1) ahead = load_raw(y0 + (i) + 3);                              \
-    mag_row4(Ha, Hb, Hc, cm_left, cm_right, active && y0 + (i) + 1 < h, Mc, Dc);      \
+    mag_row4(Ha, Hb, Hc, has_prev, has_next, active && y0 + (i) + 1 < h, Mc, Dc);      \
     uint32_t cb, sb;                                                                  \
-    nms_row4(Ma, Mb, Mc, Db, g.canny_low, g.canny_high, &cb, &sb);                    \
+    nms_row4(Ma, Mb, minus1_row4(Mb), Mc, minus1_row4(Mc), Db, g.canny_low, low_high, &cb, &sb); \
     emit((i), cb, sb);                                                                \
   }
   NMS_STEP4(0, H2, H0, H1, M0, M1, M2, D1, D2)
