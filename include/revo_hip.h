@@ -1416,6 +1416,64 @@ int revo_map_known_field(revo_map* m, const revo_map_df_box* box, uint32_t min_c
 int revo_map_frontiers(revo_map* m, const revo_map_df_box* box, uint32_t min_count, const uint8_t* seen, int device_seen,
                        uint32_t min_views, revo_map_plan_seed* cells, size_t cap, size_t* n_cells, int device_out);
 
+/* ---- what a view would add: the unknown space candidate poses would reveal --------------------------------
+ * A read-only, batched question to the map and a seen volume: for each of n_poses camera poses, how many cells that are
+ * unknown now would one depth view from there make known?  Nothing is observed and nothing is written but the records.  Every
+ * value is an integer decided by float32 arithmetic with one definition, so a pose's record is a pure function of the map, the
+ * seen volume, the camera and that pose -- the same bytes on every run, whatever the launch.
+ *
+ * The predicted view.  cam gives the size, the intrinsics, the depth range and min_count with revo_map_raycast's rules and
+ * its all-zero defaults; cam's own T_w_c and splat_max are not read.  The predicted depth image of pose i (16 floats,
+ * column-major camera -> world, revo_map_carve_eval's pose rules: finite, rotation orthogonal) is exactly the depth output
+ * of revo_map_raycast for cam with that pose and max_steps: the hit voxel's z, 0 for a ray that hits nothing.  With
+ * miss_depth != 0 every 0 of the image (a miss) is then replaced by miss_depth: free space is taken as seen up to there.
+ * The cells.  A cell's centre p is revo_map_observe's; its class in the predicted view is revo_map_carve_eval's class of p
+ * in a raw view with cam's size, intrinsics and range, the pose and the predicted image, with radius, margin and margin_rel
+ * read exactly as there.  A cell is UNKNOWN exactly as in revo_map_known_field: not solid at cam's min_count,
+ * (seen[c] & 0x7F) < max(min_views, 1), and bit 7 clear.
+ * Exact properties: the record of a pose does not depend on the other poses of the call, on their order, or on how the call
+ * is split into launches; seen and the map are not written; with min_views = 1 the cells counted by unknown_free +
+ * unknown_surface are exactly the unknown cells whose byte changes under revo_map_observe(accumulate = 1) with the predicted
+ * image (its misses replaced when miss_depth != 0) as a raw view. */
+typedef struct revo_map_gain_params {  /* 32 bytes; NULL: 1, 1, the map's voxel edge, 0, 0, 4096 */
+  int32_t radius;        /* 0 .. 3: half width of the pixel window, as revo_map_observe_params'                    */
+  uint32_t min_views;    /* free votes that make a cell known; 0 counts as 1                                        */
+  float margin;          /* metres, finite, >= 0                                                                    */
+  float margin_rel;      /* per metre of depth, finite, >= 0                                                        */
+  float miss_depth;      /* 0: a miss stays a depth hole; else zmin < miss_depth < zmax, the depth a miss is read as */
+  uint32_t max_steps;    /* 1 .. 2^20: the cells a ray examines at most, as revo_map_ray_params'                    */
+  uint32_t reserved[2];  /* zero */
+} revo_map_gain_params;
+typedef struct revo_map_gain {         /* 32 bytes per pose; the three cell counts are over the UNKNOWN cells of the box */
+  uint32_t unknown_free;     /* unknown cells whose class is FREE                                   */
+  uint32_t unknown_surface;  /* unknown cells whose class is CONFIRMED                              */
+  uint32_t unknown_inside;   /* unknown cells whose class is not OUTSIDE                            */
+  uint32_t hits;             /* hit pixels of the predicted view, before miss_depth is applied      */
+  uint32_t reserved[4];      /* zero */
+} revo_map_gain;
+typedef struct revo_map_gain_info {    /* 64 bytes, little-endian, no padding: integer sums, so order-free */
+  uint64_t poses;            /* n_poses                                                             */
+  uint64_t cells;            /* n[0]*n[1]*n[2]                                                      */
+  uint64_t unknown;          /* unknown cells of the box                                            */
+  uint64_t unknown_free, unknown_surface, unknown_inside;  /* the sums of the per-pose counts      */
+  uint64_t rays;             /* rays cast: width*height per pose that keeps the pose rules          */
+  uint64_t ray_hits;         /* the sum of the per-pose hits                                        */
+} revo_map_gain_info;
+/* seen: the box's seen volume (device_seen: where it lives; a host volume is uploaded).  T_w_c_n16: n_poses (1 .. 4096)
+ * poses (device_in: where they live).  out: n_poses records, info: NULL or the call's record (device_out: where both live).
+ * Device pointers are 16-byte aligned.  Runs on the context's tracker stream; the call only enqueues when all three flags are
+ * 1 and waits otherwise.  Poses in host memory are checked; poses in device memory are not: one that breaks the pose rules
+ * gives an all-zero record, casts no ray and is no error, as revo_map_cast_rays treats a bad ray.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, seen, cam, poses or out; the box
+ * rules of revo_map_distance_field; the view rules of revo_map_raycast on cam; n_poses outside 1 .. 4096; a host pose that is
+ * not finite or whose rotation is not orthogonal; radius outside 0 .. 3; a margin that is not finite or negative; a
+ * miss_depth that is neither 0 nor inside (zmin, zmax); max_steps outside 1 .. 2^20; a reserved word that is not 0; a flag
+ * outside 0 / 1; a misaligned device pointer. */
+int revo_map_view_gain(revo_map* m, const revo_map_df_box* box, const uint8_t* seen, int device_seen,
+                       const revo_map_view* cam, size_t n_poses, const float* T_w_c_n16, int device_in,
+                       const revo_map_gain_params* prm, revo_map_gain* out, int device_out,
+                       revo_map_gain_info* info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -982,6 +982,83 @@ class VoxelMap:
                                             vp(d_cells.data_ptr()) if d_cells is not None else None, cap, C.byref(k), 1))
         return int(k.value)
 
+    # -- what a view would add (revo_map_view_gain)
+    def _gain_camera(self, camera, size, zrange, min_count):
+        """-> MapView without a pose.  camera None: the context's level-0 camera, size and depth range (size and zrange are then
+        not given); else an api.Camera or (fx, fy, cx, cy) with size (width, height) -- the Camera's own by default -- and
+        zrange (zmin, zmax) or None = the context's range."""
+        s = self.cameraPyr.settings
+        v = MapView()
+        if camera is None:
+            if size is not None or zrange is not None:
+                raise ValueError("size and zrange go with a camera: without one the context's camera, size and range are used")
+            v.width, v.height = int(s.width), int(s.height)
+        else:
+            if isinstance(camera, Camera):
+                size = (camera.width, camera.height) if size is None else size
+                camera = (camera.fx, camera.fy, camera.cx, camera.cy)
+            if len(camera) != 4 or size is None:
+                raise ValueError("a camera is (fx, fy, cx, cy) with a size (width, height)")
+            zmin, zmax = zrange if zrange is not None else (s.depth_min, s.depth_max)
+            v.width, v.height = int(size[0]), int(size[1])
+            v.fx, v.fy, v.cx, v.cy, v.zmin, v.zmax = [float(x) for x in tuple(camera) + (zmin, zmax)]
+        v.T_w_c[:] = _cm4(np.eye(4, dtype=np.float32)).tolist()
+        v.min_count = int(min_count)
+        return v
+
+    def _gain_params(self, min_views, radius, margin, margin_rel, miss_depth, max_steps):
+        return MapGainParams(int(radius), int(min_views), float(self.voxel if margin is None else margin), float(margin_rel), float(miss_depth),
+                             int(max_steps))
+
+    def view_gain(self, seen, poses, camera=None, size=None, min_views=1, radius=1, margin=None, margin_rel=0.0, miss_depth=0.0, min_count=1,
+                  max_steps=4096, zrange=None):
+        """What a depth view from each of `poses` (one 4x4 camera -> world pose, or 1 .. 4096 of them) would add to `seen` (a
+        SeenVolume; its box is the call's) -> mapfile.GainRecords: per pose unknown_free, unknown_surface, unknown_inside -- the
+        cells that are unknown now (not solid, fewer than min_views free votes, no surface bit) and would be seen free, on a
+        surface, or lie inside the view at all -- and hits, the pixels of the predicted depth image that show a voxel; `.info`
+        holds the call's sums (mapfile.GAIN_INFO_KEYS).  The predicted image is raycast()'s from that pose, the class of a cell
+        observe()'s; nothing is observed or written (revo_map_view_gain).  camera, size, zrange: see _gain_camera.
+        miss_depth 0: a ray that hits nothing leaves a depth hole, as a sensor would; else the depth such a pixel is read as
+        (free space seen up to there)."""
+        from . import mapfile
+        box, vol = self._seen_box(seen)
+        T = mapfile.gain_poses(poses)
+        cm = np.ascontiguousarray(T.transpose(0, 2, 1))
+        cam = self._gain_camera(camera, size, zrange, min_count)
+        prm = self._gain_params(min_views, radius, margin, margin_rel, miss_depth, max_steps)
+        out = np.zeros(len(T), mapfile.GAIN_DTYPE)
+        info = MapGainInfo()
+        check(_lib.lib().revo_map_view_gain(self._h, C.byref(box), vol.ctypes.data_as(vp), 0, C.byref(cam), len(T), cm.ctypes.data_as(vp), 0,
+                                            C.byref(prm), out.ctypes.data_as(vp), 0, C.byref(info)))
+        return mapfile.gain_result(out, {k: int(getattr(info, k)) for k in mapfile.GAIN_INFO_KEYS})
+
+    def view_gain_into(self, d_out, d_seen, lo, d_poses, camera=None, size=None, min_views=1, radius=1, margin=None, margin_rel=0.0, miss_depth=0.0,
+                       min_count=1, max_steps=4096, zrange=None, d_info=None, wait=True):
+        """view_gain() between torch device tensors: d_seen the seen volume (3-D uint8; its shape is the box's n), d_poses
+        [k, 16] or [k, 4, 4] float32 with every pose COLUMN-major (a row-major pose transposed), d_out 32 bytes per pose
+        (revo_map_gain), d_info None or 64 bytes (revo_map_gain_info); contiguous, 16-byte aligned, on the map's device.  Poses
+        in device memory are not checked: one that is not finite or not orthogonal gets an all-zero record.  The call is only
+        enqueued on the context's tracker stream: wait=False returns at once (sync() orders later reads)."""
+        if d_seen.dim() != 3 or str(d_seen.dtype) != "torch.uint8":
+            raise ValueError("d_seen must be a 3-D uint8 tensor")
+        if str(d_poses.dtype) != "torch.float32" or d_poses.numel() % 16 or d_poses.numel() == 0:
+            raise ValueError("d_poses must hold 16 float32 numbers per pose")
+        k = d_poses.numel() // 16
+        for t_, size_ in ((d_seen, None), (d_poses, None), (d_out, 32 * k), (d_info, 64)):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("tensors must be contiguous device tensors")
+            if t_ is not None and size_ is not None and t_.numel() * t_.element_size() != size_:
+                raise ValueError("d_out needs 32 bytes per pose and d_info 64 bytes")
+        box = self._df_box(lo, tuple(d_seen.shape), 0, 1)
+        cam = self._gain_camera(camera, size, zrange, min_count)
+        prm = self._gain_params(min_views, radius, margin, margin_rel, miss_depth, max_steps)
+        import torch
+        torch.cuda.current_stream(d_out.device).synchronize()  # the inputs are written, the outputs' earlier use is over
+        check(_lib.lib().revo_map_view_gain(self._h, C.byref(box), vp(d_seen.data_ptr()), 1, C.byref(cam), k, vp(d_poses.data_ptr()), 1, C.byref(prm),
+                                            vp(d_out.data_ptr()), 1, vp(d_info.data_ptr()) if d_info is not None else None))
+        if wait:
+            self.sync()
+
     def distance_field_into(self, d_d2, lo, n, min_count=1, clamp=0, d_info=None, wait=True):
         """distance_field() into a torch device tensor: d_d2 of shape n with 32-bit integers, d_info None or a 64-byte tensor
         (revo_map_df_info); contiguous, 16-byte aligned, on the map's device.  Enqueued on the context's tracker stream: wait=True
@@ -1382,6 +1459,32 @@ def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
     return {"field": field, "frontiers": fr, "cost": cost, "path": cost.path(np.asarray(start).reshape(1, 3), max_len)[0]}
 
 
+def next_view(m, seen, start, clearance, camera=None, size=None, headings=8, up=(0, -1, 0), stride=4, max_candidates=1024, weight=1.0,
+              min_count=1, max_len=4096, **gain_params):
+    """Where to look next, on the map's device: the known field of `seen` (a SeenVolume), the cost-to-go from
+    `start` (a voxel index, or metres) at the clearance (metres), the reachable cells on the lattice of absolute indices that
+    are multiples of `stride` (ascending cell order, at most max_candidates // headings), `headings` yaws about `up` at each
+    (mapfile.next_view_poses), their view gain (gain_params: VoxelMap.view_gain's min_views, radius, margin, margin_rel,
+    miss_depth, max_steps, zrange) and the score unknown_free / (1 + weight * metres of the way), ties to the lowest index
+    -> dict: pose (4x4), cell, heading, record, index, scores, poses, cells, gain, field, cost (CostField), path ((cells,
+    status, cost) from the position back to `start`).  ValueError when no candidate position is reachable."""
+    from . import mapfile
+    field = m.distance_field(seen=seen, min_views=gain_params.get("min_views", 1), min_count=min_count)
+    st = np.asarray(start)
+    cost = field.plan(st.reshape(1, 3) if st.dtype.kind == "f" else st.astype(np.int64).reshape(1, 3), clearance=clearance)
+    cells = mapfile.next_view_candidates(cost.cost, cost.lo, stride, headings, max_candidates)
+    if len(cells) == 0:
+        raise ValueError("no candidate position is reachable from the start (%d seeds used, %d cells reachable)"
+                         % (cost.info["seeds_used"], cost.info["reachable"]))
+    poses = mapfile.next_view_poses(cells, m.voxel, headings, up)
+    gain = m.view_gain(seen, poses, camera, size, min_count=min_count, **gain_params)
+    at = tuple((cells - cost.lo.astype(np.int64)).T)
+    scores, best = mapfile.next_view_choice(gain, cost.cost[at], m.voxel, headings, weight)
+    cell = cells[best // int(headings)]
+    return {"pose": poses[best], "cell": cell.astype(np.int32), "heading": best % int(headings), "record": gain[best], "index": best, "scores": scores,
+            "poses": poses, "cells": cells.astype(np.int32), "gain": gain, "field": field, "cost": cost, "path": cost.path(cell.reshape(1, 3), max_len)[0]}
+
+
 class CostField:
     """A cost-to-go field over a box of voxel indices (DistanceField.plan, `mapfile plan --cost`): cost [n0, n1, n2]
     uint32, the cheapest way to a goal over free cells in units of a third of a voxel edge per straight step (3, 4, 5 for a
@@ -1654,6 +1757,13 @@ class MapWindow:
 
     def frontiers(self, *args, **kw):
         return self.map.frontiers(*args, **kw)
+
+    def view_gain(self, *args, **kw):
+        """The inner map's view_gain: what candidate views would add, over the voxels the window holds now."""
+        return self.map.view_gain(*args, **kw)
+
+    def view_gain_into(self, *args, **kw):
+        return self.map.view_gain_into(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -18,6 +18,7 @@
 #include "revo_map.h"
 #include "revo_pose_host.h"
 #include "revo_carve_host.h"
+#include "revo_ray_host.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull  // no packed key reaches bit 63
 #define MAP_SHARDS 16                    // per-map batch counters, one 128-B line each (one global atomic per block and counter)
@@ -241,7 +242,20 @@ struct revo_map_stage {
   int upload(int nd, int nc, hipStream_t s) { if (nd) TRY(desc.upload(nd, s, false)); return com.upload(nc, s); }
 };
 struct MapViewK;    // revo_map_view.hip: one view of a render launch
-struct MapRayView;  // revo_map_view.hip: one view of a raycast launch
+// revo_map_raycast's launch records, for revo_map_view.hip, which launches them, and revo_map_gain.hip, which fills views
+// of its own on the device.
+struct MapRayK {  // what every ray of a launch shares
+  const u64* keys; const MapVal* vals; unsigned mask;  // the map's table
+  const u64* bkeys; unsigned bmask;                    // the keys of the occupied 8 x 8 x 8 blocks (NULL: every cell is looked up)
+  u64 min_count;                                       // >= 1
+  unsigned max_steps;
+  float voxel;
+  u64* info;                                           // one 64-byte line: revo_map_ray_info's counters
+};
+struct MapRayView {  // one view of a launch, in device memory
+  RayView v;
+  float* depth; uint8_t* bgr; u64* key; unsigned* hits;  // bgr, key: NULL when not asked for
+};
 struct MapDfPose;   // revo_map_df_align.hip: one pose of a registration launch
 
 struct revo_map {
@@ -289,6 +303,9 @@ struct revo_map {
   // call, its counter lines, and the device copy of a host seen volume (in or out)
   HostRows<MapCarveView> seen_views;
   DevBuf seencnt, seenvol;
+  // revo_map_view_gain (revo_map_gain.hip): the predicted depth images of a launch's poses, the poses' descriptors (ray views
+  // and gain poses), the counter lines, and the device records of a host-output call
+  DevBuf gaindepth, gaindesc, gaincnt, gainout;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every
@@ -351,6 +368,12 @@ int map_subtract_core(revo_map* m, MapMergeK a, int src_kind, u64 dropped, u64 k
 // k_df_occupancy's counters in `info` (NULL: m->dfcnt's line).
 const char* map_df_box_check(const revo_map_df_box* box, size_t* cells);
 int map_df_solid_bits(revo_map* m, const revo_map_df_box* box, uint32_t min_count, hipStream_t s, const unsigned** bits, unsigned* wz, u64* info = nullptr);
+
+// revo_map_view.hip, for revo_map_gain.hip: revo_map_raycast's march over views that are in device memory already.  map_ray_open
+// reserves and builds the block table of the map as it is on the stream, clears the info line d_info and fills *a;
+// map_ray_views enqueues k_map_raycast over n (1 .. 64) views whose largest image takes max_blocks blocks.
+int map_ray_open(revo_map* m, MapRayK* a, uint32_t min_count, uint32_t max_steps, u64* d_info);
+int map_ray_views(revo_map* m, const MapRayK& a, int n, const MapRayView* d_views, int max_blocks);
 
 // Room in m's table for `bound` more keys at a load <= 0.5 (the checked path inserts every new key before it decides: what
 // the map may hold + all of them); *ub: the bound of the voxels it holds now.  what: "batch", "merge".

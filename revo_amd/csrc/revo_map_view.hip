@@ -177,18 +177,6 @@ extern "C" int revo_map_render_last_ms(revo_map* m, float* ms) {
 }
 // --------------------------------------------------------------------------------------------- rays through the map (20) --
 // revo_map_raycast / revo_map_cast_rays (contract: include/revo_hip.h).
-struct MapRayK {  // what every ray of a launch shares
-  const u64* keys; const MapVal* vals; unsigned mask;  // the map's table
-  const u64* bkeys; unsigned bmask;                    // the keys of the occupied 8 x 8 x 8 blocks (NULL: every cell is looked up)
-  u64 min_count;                                       // >= 1
-  unsigned max_steps;
-  float voxel;
-  u64* info;                                           // one 64-byte line: revo_map_ray_info's counters
-};
-struct MapRayView {  // one view of a launch, in device memory
-  RayView v;
-  float* depth; uint8_t* bgr; u64* key; unsigned* hits;  // bgr, key: NULL when not asked for
-};
 struct MapRayOut { u64 key; float s; unsigned cells; float z; unsigned bgr; };  // z, bgr (B | G << 8 | R << 16): view rays only
 enum { RAY_HIT = 0, RAY_RANGE = 1, RAY_OUTSIDE = 2, RAY_EXHAUSTED = 3, RAY_STATUSES = 4 };
 
@@ -396,6 +384,19 @@ static int ray_begin(revo_map* m, MapRayK* a, u64 min_count, unsigned max_steps,
   HIPCHECK(hipMemsetAsync(d_info, 0, sizeof(revo_map_ray_info), s));
   if (n_hits) HIPCHECK(hipMemsetAsync(d_hits, 0, sizeof(unsigned) * n_hits, s));
   return REVO_OK;
+}
+
+// For revo_map_gain.hip (declared in revo_map_impl.h): the same block table, march and counters over views the caller has
+// written to device memory.
+int map_ray_open(revo_map* m, MapRayK* a, uint32_t min_count, uint32_t max_steps, u64* d_info) {
+  TRY(m->bkeys.reserve(sizeof(u64) * m->cap, (hipStream_t)m->g.stream));
+  return ray_begin(m, a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0);
+}
+int map_ray_views(revo_map* m, const MapRayK& a, int n, const MapRayView* d_views, int max_blocks) {
+  hipStream_t s = (hipStream_t)m->g.stream;
+  hipLaunchKernelGGL(k_map_raycast, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), 0, s, a, d_views);
+  HIPCHECK(hipGetLastError());
+  return m->ray_time.end(s);
 }
 
 extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, const revo_map_ray_params* prm, float* const* depth,

@@ -36,6 +36,17 @@ Equal maps give equal files.
                                                         the free cells next to unseen space (revo_map_frontiers), one voxel index
                                                         per line; `esdf` and `plan` take --seen SEEN.npz [--min-views K] too: the
                                                         field then treats unseen space as an obstacle (revo_map_known_field)
+    python -m revo_amd.mapfile gain A --seen SEEN.npz --poses POSES.txt --camera FX FY CX CY --size W H [--zrange ZMIN ZMAX]
+                                                        [--radius N] [--margin M] [--margin-rel F] [--min-views K] [--min-count N]
+                                                        [--miss-depth D] [--max-steps N] -o GAIN.txt
+                                                        what a view from each pose of POSES.txt (one row-major 4x4 or 3x4 per line)
+                                                        would add to SEEN.npz (revo_map_view_gain), without a GPU: per
+                                                        pose the unknown cells it would see free, on a surface, inside the view,
+                                                        and the hit pixels of the predicted depth image
+    python -m revo_amd.mapfile next-view A --seen SEEN.npz --start X Y Z --clearance M --camera FX FY CX CY --size W H
+                                                        [--headings N] [--stride N] [--max-candidates N] [--weight W] [--up X Y Z]
+                                                        [the options of gain] -o POSE.txt
+                                                        the reachable pose that would reveal most per metre of the way there
     python -m revo_amd.mapfile df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt
                                                         map SRC's points registered against map DST's distance field
                                                         (revo_map_df_align), without a GPU: the pose SRC's frame ->
@@ -822,6 +833,173 @@ def explore_records(records, lo, n, voxel, seen, start, clearance, min_count=1, 
     return d2, fr, cost, info, plan_paths(cost, lo, n, np.asarray(start, np.int64).reshape(1, 3), max_len)[0]
 
 
+GAIN_DTYPE = np.dtype([("unknown_free", "<u4"), ("unknown_surface", "<u4"), ("unknown_inside", "<u4"), ("hits", "<u4"), ("reserved", "<u4", (4,))])
+GAIN_INFO_KEYS = ("poses", "cells", "unknown", "unknown_free", "unknown_surface", "unknown_inside", "rays", "ray_hits")
+GAIN_MAX_POSES = 4096
+assert GAIN_DTYPE.itemsize == 32
+
+
+class GainRecords(np.ndarray):
+    """The per-pose records of a view-gain call (GAIN_DTYPE) with the call's counters in `.info` (GAIN_INFO_KEYS)."""
+    info = None
+
+    def __array_finalize__(self, obj):
+        self.info = getattr(obj, "info", None)
+
+
+def gain_result(records, info):
+    out = np.ascontiguousarray(records, GAIN_DTYPE).view(GainRecords)
+    out.info = dict(info)
+    return out
+
+
+def gain_poses(poses):
+    """[k, 4, 4] float32 of one pose or 1 .. 4096 poses given as 4x4 or 3x4 matrices; no rule of a pose is checked here."""
+    T = np.asarray(poses, np.float32)
+    if T.ndim == 2:
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] not in ((4, 4), (3, 4)) or not 1 <= len(T) <= GAIN_MAX_POSES:
+        raise ValueError("view gain takes 1 .. 4096 poses, 4x4 or 3x4 each")
+    if T.shape[1] == 3:
+        T = np.concatenate([T, np.broadcast_to(np.float32([0, 0, 0, 1]), (len(T), 1, 4))], 1)
+    return np.ascontiguousarray(T)
+
+
+def gain_pose_ok(T):
+    """revo_map_carve_eval's pose rules: finite, rotation orthogonal."""
+    return bool(np.all(np.isfinite(T))) and pose_is_orthogonal(T[:3, :3])
+
+
+def gain_records(records, voxel, lo, n, seen, view, poses, radius=1, min_views=1, margin=None, margin_rel=0.0, miss_depth=0.0,
+                 min_count=1, max_steps=4096, device_poses=False):
+    """What each of `poses` would add to a seen volume, without a GPU: revo_map_view_gain's contract in vectorised
+    numpy, through raycast_records (the predicted depth image), carve_classes (a centre's class in it) and seen_known (which
+    cells are unknown).  view: ((fx, fy, cx, cy, zmin, zmax), (width, height)); poses: what gain_poses takes.  -> GainRecords:
+    GAIN_DTYPE per pose, and .info.  device_poses: a pose that breaks the pose rules gives an all-zero record, as the library
+    treats poses in device memory; otherwise it is a ValueError, like every REVO_ERR_INVALID_ARG of the library."""
+    lo, n = check_box(lo, n)
+    seen = _seen_volume(seen, n)
+    rec, v = _ray_args(records, voxel, min_count, max_steps)
+    k, size = view
+    T = gain_poses(poses)
+    cam = ray_view(np.eye(4, dtype=np.float32), k, size)
+    k = cam[4]
+    if not 0 <= int(radius) <= 3:
+        raise ValueError("radius must be 0 .. 3")
+    margin, margin_rel, miss = np.float32(v if margin is None else margin), np.float32(margin_rel), np.float32(miss_depth)
+    if not (np.isfinite(margin) and margin >= 0 and np.isfinite(margin_rel) and margin_rel >= 0):
+        raise ValueError("margin and margin_rel must be finite and >= 0")
+    if miss != 0 and not (miss > k[4] and miss < k[5]):
+        raise ValueError("miss_depth must be 0 or inside (zmin, zmax)")
+    good = [gain_pose_ok(M) for M in T]
+    if not device_poses and not all(good):
+        raise ValueError("pose %d is not finite or its rotation is not orthogonal" % good.index(False))
+    solid, _ = solid_cells(rec, lo, n, 1)
+    unknown = ~seen_known(seen, min_views, solid)
+    p = seen_centres(lo, n, v)[unknown.reshape(-1)]
+    out = np.zeros(len(T), GAIN_DTYPE)
+    info = dict.fromkeys(GAIN_INFO_KEYS, 0)
+    info.update(poses=len(T), cells=int(unknown.size), unknown=int(unknown.sum()))
+    idx = [i for i, g in enumerate(good) if g]
+    for a in range(0, len(idx), 64):
+        part = idx[a:a + 64]
+        cast = raycast_records(rec, v, [(T[i], k, size) for i in part], 1, max_steps)
+        info["rays"] += cast["info"]["rays"]
+        for i, D, hits in zip(part, cast["depth"], cast["hits"]):
+            if miss != 0:
+                D = np.where(D == 0, miss, D)
+            cls = carve_classes(p, carve_view(D, T[i], k), int(radius), margin, margin_rel)
+            out[i] = (int((cls == 2).sum()), int((cls == 3).sum()), int((cls != 0).sum()), hits, (0, 0, 0, 0))
+    for name, field in (("unknown_free", "unknown_free"), ("unknown_surface", "unknown_surface"), ("unknown_inside", "unknown_inside"), ("ray_hits", "hits")):
+        info[name] = int(out[field].sum(dtype=np.uint64))
+    return gain_result(out, info)
+
+
+def next_view_poses(cells, voxel, headings=8, up=(0.0, -1.0, 0.0)):
+    """[len(cells) * headings, 4, 4] float32 camera -> world poses: at the centre of every cell (absolute voxel indices), `headings`
+    yaws 2 pi j / headings about `up`.  The camera looks along its +z with its image's y axis pointing against `up`; yaw 0 looks
+    along the world's +z made perpendicular to `up` (the world's +x where `up` is within 0.1 of the z axis).  Computed in
+    float64 and rounded once."""
+    cells = np.asarray(cells, np.int64).reshape(-1, 3)
+    headings = int(headings)
+    u = np.asarray(up, np.float64).reshape(3)
+    if headings < 1 or not np.all(np.isfinite(u)) or not np.linalg.norm(u) > 0:
+        raise ValueError("headings must be >= 1 and up a finite direction")
+    u = u / np.linalg.norm(u)
+    ref = np.array([0.0, 0.0, 1.0]) if abs(u[2]) < 0.9 else np.array([1.0, 0.0, 0.0])
+    f0 = ref - ref.dot(u) * u
+    f0 /= np.linalg.norm(f0)
+    s0 = np.cross(u, f0)
+    T = np.zeros((len(cells), headings, 4, 4), np.float64)
+    for j in range(headings):
+        th = 2.0 * np.pi * j / headings
+        z = np.cos(th) * f0 + np.sin(th) * s0
+        y = -u
+        T[:, j, :3, 0], T[:, j, :3, 1], T[:, j, :3, 2] = np.cross(y, z), y, z
+    T[:, :, :3, 3] = (((cells.astype(np.float32) + np.float32(0.5)) * np.float32(voxel)).astype(np.float64))[:, None, :]
+    T[:, :, 3, 3] = 1.0
+    return T.reshape(-1, 4, 4).astype(np.float32)
+
+
+def next_view_candidates(cost, lo, stride=4, headings=8, max_candidates=1024):
+    """[k, 3] int64 absolute voxel indices: the reachable cells of a cost field (cost != PLAN_NONE) whose absolute index is a
+    multiple of `stride` on every axis, in ascending order of the cell's place in the box, at most max_candidates // headings."""
+    stride, headings = int(stride), int(headings)
+    if stride < 1 or headings < 1 or int(max_candidates) < headings:
+        raise ValueError("stride and headings must be >= 1 and max_candidates at least one position's headings")
+    lo = np.asarray(lo, np.int64).reshape(3)
+    c = np.argwhere(np.asarray(cost) != PLAN_NONE) + lo
+    c = c[np.all(c % stride == 0, axis=1)]
+    return c[:int(max_candidates) // headings]
+
+
+def next_view_choice(gain, cost_at, voxel, headings, weight=1.0):
+    """(scores float64 [poses], best index): unknown_free / (1 + weight * metres) with metres = cost * voxel / 3 of the pose's
+    position; the best is the first of the largest."""
+    metres = np.repeat(np.asarray(cost_at, np.float64), int(headings)) * float(np.float32(voxel)) / 3.0
+    scores = np.asarray(gain["unknown_free"], np.float64) / (1.0 + float(weight) * metres)
+    return scores, int(np.argmax(scores))
+
+
+def next_view_records(records, voxel, lo, n, seen, start, clearance, view, headings=8, up=(0.0, -1.0, 0.0), stride=4, max_candidates=1024,
+                      weight=1.0, min_count=1, max_len=4096, **gain_params):
+    """Where to look next, without a GPU: the known field of `seen`, the cost-to-go from `start` (a voxel index; the
+    plan with `start` as its only seed) at the clearance (metres), the candidate positions next_view_candidates picks from it,
+    `headings` yaws at each, their view gain, and the best score -> dict: pose (4x4), cell, heading, record, index, scores,
+    poses, cells, gain (GainRecords), cost, path ((cells, status, cost) from the position back to `start`).  ValueError when no
+    candidate is reachable."""
+    lo, n = check_box(lo, n)
+    min_views = gain_params.get("min_views", 1)
+    d2, _ = known_field_records(records, lo, n, seen, min_count, 0, min_views)
+    cost, pinfo = plan_records(d2, lo, n, plan_seeds(np.asarray(start, np.int64).reshape(1, 3)), plan_r2(clearance, voxel))
+    cells = next_view_candidates(cost, lo, stride, headings, max_candidates)
+    if len(cells) == 0:
+        raise ValueError("no candidate position is reachable from the start (%d seeds used, %d cells reachable)" % (pinfo["seeds_used"], pinfo["reachable"]))
+    poses = next_view_poses(cells, voxel, headings, up)
+    gain = gain_records(records, voxel, lo, n, seen, view, poses, min_count=min_count, **gain_params)
+    at = tuple((cells - lo).T)
+    scores, best = next_view_choice(gain, cost[at], voxel, headings, weight)
+    cell = cells[best // int(headings)]
+    return {"pose": poses[best], "cell": cell.astype(np.int32), "heading": best % int(headings), "record": gain[best], "index": best, "scores": scores,
+            "poses": poses, "cells": cells.astype(np.int32), "gain": gain, "cost": cost, "path": plan_paths(cost, lo, n, cell.reshape(1, 3), max_len)[0]}
+
+
+def read_poses(path):
+    """[k, 4, 4] float32: one pose per line of a text file, 16 or 12 numbers each (a row-major 4x4 or 3x4); '#' starts a comment."""
+    out = []
+    with open(path) as f:
+        for ln in f:
+            a = [float(x) for x in ln.split("#")[0].replace(",", " ").split()]
+            if not a:
+                continue
+            if len(a) not in (12, 16):
+                raise ValueError("%s: a line holds %d numbers; a pose is 16 (4x4) or 12 (3x4), row-major" % (path, len(a)))
+            out.append(_pose_matrix(np.float32(a).reshape(-1, 4)))
+    if not out:
+        raise ValueError("%s holds no pose" % path)
+    return np.stack(out)
+
+
 def write_seen(path, seen, lo, voxel):
     """The .npz of a seen volume: seen (uint8 [n0, n1, n2]), lo, n (int32 [3]), voxel (float32)."""
     seen = np.ascontiguousarray(seen, np.uint8)
@@ -1576,6 +1754,49 @@ def main(argv=None):
                       % ((val["-o"][-1][0], len(paths), ", ".join(PLAN_STATUS[st] for _, st, _ in paths)) + cost.shape
                          + (r2, info["free"], info["reachable"], info["max_cost"])))
                 return 0
+        if cmd in ("gain", "next-view") and "-o" in args and "--seen" in args:
+            opt = {"-o": 1, "--seen": 1, "--poses": 1, "--camera": 4, "--size": 2, "--zrange": 2, "--radius": 1, "--margin": 1, "--margin-rel": 1,
+                   "--min-views": 1, "--min-count": 1, "--miss-depth": 1, "--max-steps": 1, "--start": 3, "--clearance": 1, "--headings": 1,
+                   "--stride": 1, "--max-candidates": 1, "--weight": 1, "--up": 3}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            need = ("--poses",) if cmd == "gain" else ("--start", "--clearance")
+            if len(pos) == 1 and all(k in val for k in need + ("--camera", "--size")):
+                params = {name: conv(val[o][0]) for o, name, conv in (("--radius", "radius", int), ("--margin", "margin", float),
+                                                                       ("--margin-rel", "margin_rel", float), ("--min-views", "min_views", int),
+                                                                       ("--min-count", "min_count", int), ("--miss-depth", "miss_depth", float),
+                                                                       ("--max-steps", "max_steps", int)) if o in val}
+                view = ([float(x) for x in val["--camera"]] + [float(x) for x in val.get("--zrange", (0.1, 5.2))], [int(x) for x in val["--size"]])
+                header, rec = read(pos[0])
+                vol, lo, n = _seen_for(val["--seen"][0], header["voxel"])
+                if cmd == "gain":
+                    g = gain_records(rec, header["voxel"], lo, n, vol, view, read_poses(val["--poses"][0]), **params)
+                    with open(val["-o"][0], "w") as f:
+                        f.write("# unknown_free unknown_surface unknown_inside hits\n")
+                        f.write("".join("%d %d %d %d\n" % (r["unknown_free"], r["unknown_surface"], r["unknown_inside"], r["hits"]) for r in g))
+                    print("%s: %d poses over %d unknown of %d cells: %d free, %d surface, %d inside the views; %d of %d rays hit"
+                          % (val["-o"][0], len(g), g.info["unknown"], g.info["cells"], g.info["unknown_free"], g.info["unknown_surface"],
+                             g.info["unknown_inside"], g.info["ray_hits"], g.info["rays"]))
+                    return 0
+                extra = {name: conv(val[o][0]) for o, name, conv in (("--headings", "headings", int), ("--stride", "stride", int),
+                                                                      ("--max-candidates", "max_candidates", int), ("--weight", "weight", float)) if o in val}
+                if "--up" in val:
+                    extra["up"] = [float(x) for x in val["--up"]]
+                r = next_view_records(rec, header["voxel"], lo, n, vol, [int(x) for x in val["--start"]], float(val["--clearance"][0]), view,
+                                      **extra, **params)
+                with open(val["-o"][0], "w") as f:
+                    f.write("".join(" ".join("%.9g" % x for x in row) + "\n" for row in r["pose"]))
+                print("%s: the best of %d poses at %d positions: cell %s heading %d, %d unknown cells seen free, score %.6g, %d cells from the start"
+                      % (val["-o"][0], len(r["poses"]), len(r["cells"]), r["cell"].tolist(), r["heading"], int(r["record"]["unknown_free"]),
+                         r["scores"][r["index"]], len(r["path"][0])))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -1594,6 +1815,10 @@ def main(argv=None):
           "esdf A -o OUT.npz [--pad N] [--min-count N] [--clamp D2] [--seen SEEN.npz] [--min-views K] | df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt | "
           "plan A --goal X Y Z [--goal ...] --start X Y Z [--start ...] --clearance M [--pad N] [--seen SEEN.npz] [--min-views K] -o PATH.txt "
           "[--cost OUT.npz] | "
+          "gain A --seen SEEN.npz --poses POSES.txt --camera FX FY CX CY --size W H [--zrange ZMIN ZMAX] [--radius N] [--margin M] [--margin-rel F] "
+          "[--min-views K] [--min-count N] [--miss-depth D] [--max-steps N] -o GAIN.txt | "
+          "next-view A --seen SEEN.npz --start X Y Z --clearance M --camera FX FY CX CY --size W H [--headings N] [--stride N] [--max-candidates N] "
+          "[--weight W] [--up X Y Z] [the options of gain] -o POSE.txt | "
           "ply FILE [OUT.ply]")
     return 2
 

@@ -359,6 +359,27 @@ class MapKnownInfo(C.Structure):
 assert (C.sizeof(MapObserveParams), C.sizeof(MapObserveInfo), C.sizeof(MapKnownInfo)) == (16, 64, 64)
 
 
+class MapGainParams(C.Structure):
+    """revo_map_gain_params (include/revo_hip.h), 32 bytes: the pixel window, the votes that make a cell known, the margins, the
+    depth a miss pixel is read as (0: a hole) and the cells a ray examines at most."""
+    _fields_ = [("radius", C.c_int32), ("min_views", C.c_uint32), ("margin", C.c_float), ("margin_rel", C.c_float),
+                ("miss_depth", C.c_float), ("max_steps", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class MapGain(C.Structure):
+    """revo_map_gain (include/revo_hip.h), 32 bytes per pose: the unknown cells of the box by their class in the predicted view,
+    and the view's hit pixels."""
+    _fields_ = [(k, C.c_uint32) for k in ("unknown_free", "unknown_surface", "unknown_inside", "hits")] + [("reserved", C.c_uint32 * 4)]
+
+
+class MapGainInfo(C.Structure):
+    """revo_map_gain_info (include/revo_hip.h), 64 bytes: integer sums of a view_gain call."""
+    _fields_ = [(k, C.c_uint64) for k in ("poses", "cells", "unknown", "unknown_free", "unknown_surface", "unknown_inside", "rays", "ray_hits")]
+
+
+assert (C.sizeof(MapGainParams), C.sizeof(MapGain), C.sizeof(MapGainInfo)) == (32, 32, 64)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
