@@ -561,45 +561,37 @@ template <int NE, bool EXACT>
 __device__ __forceinline__ void fused_point(const f4v p, gf32p dtm, const float* R0, const float* T0, const float (*R)[9],
                                             const float (*T)[3], const Cam& c, float edist, bool filt, float huber, float* acc,
                                             double* ed) {
-  const PtState s0 = project_point(p, R0, T0, c, true);
+  const PtState s0 = project_point(p.x, p.y, p.z, R0, T0, c, true);
   PtState s[NE];
 #pragma unroll
-  for (int j = 0; j < NE; ++j) s[j] = project_point(p, R[j], T[j], c, true);
+  for (int j = 0; j < NE; ++j) s[j] = project_point(p.x, p.y, p.z, R[j], T[j], c, true);
   const DtPatch q = load_patch(dtm, c.w, s0.ix, s0.iy);
-  float g00[NE], g10[NE], g01[NE], g11[NE];
-  int ddx[NE], ddy[NE];
+  tpx_f2 g0[NE], g1[NE];  // the retry's samples (d00, d10), (d01, d11) where they have to be gathered
   bool hit[NE];
 #pragma unroll
   for (int j = 0; j < NE; ++j) {
-    ddx[j] = s[j].ix - s0.ix;
-    ddy[j] = s[j].iy - s0.iy;
-    hit[j] = (ddy[j] == 0 && ddx[j] >= -1 && ddx[j] <= 1) || (ddx[j] == 0 && (ddy[j] == 1 || ddy[j] == -1));
-    g00[j] = g10[j] = g01[j] = g11[j] = 0.0f;
+    hit[j] = retry_in_patch(s[j].ix, s[j].iy, s0.ix, s0.iy);
+    g0[j] = g1[j] = tpx_any();
     if (!hit[j]) {
       gf32p t = dtm + s[j].iy * c.w + s[j].ix;
-      g00[j] = t[0]; g10[j] = t[1]; g01[j] = t[c.w]; g11[j] = t[c.w + 1];
+      g0[j] = tpx_mk(t[0], t[1]); g1[j] = tpx_mk(t[c.w], t[c.w + 1]);
     }
   }
+  // picked out of the patch BEFORE candidate 0's long evaluation: the 12 samples and the retries' pixels end here, and what
+  // stays live across it is four samples per retry (and the four the gather brings)
+  tpx_f2 D0[NE], D1[NE];
+#pragma unroll
+  for (int j = 0; j < NE; ++j) retry_pick(q, s[j].ix, s[j].iy, s0.ix, s0.iy, D0[j], D1[j]);
+  __builtin_amdgcn_sched_barrier(0);
   accumulate_point<EXACT>(s0, q, c.fx, c.fy, edist, filt, huber, acc, ed);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int j = 0; j < NE; ++j) { D0[j] = tpx_sel(hit[j], D0[j], g0[j]); D1[j] = tpx_sel(hit[j], D1[j], g1[j]); }
 #pragma unroll
   for (int j = 0; j < NE; ++j) {
-    float d00 = g00[j], d10 = g10[j], d01 = g01[j], d11 = g11[j];
-    if (hit[j]) {
-      const bool same_row = ddy[j] == 0, up = ddy[j] < 0, left = ddx[j] < 0, mid = ddx[j] == 0;
-      // rows iy0 / iy0+1 shifted by ddx, or rows iy0-1 / iy0, or rows iy0+1 / iy0+2 (ddx == 0)
-      d00 = same_row ? (left ? q.b0 : (mid ? q.b1 : q.b2)) : (up ? q.a0 : q.c1);
-      d10 = same_row ? (left ? q.b1 : (mid ? q.b2 : q.b3)) : (up ? q.a1 : q.c2);
-      d01 = same_row ? (left ? q.c0 : (mid ? q.c1 : q.c2)) : (up ? q.b1 : q.d0);
-      d11 = same_row ? (left ? q.c1 : (mid ? q.c2 : q.c3)) : (up ? q.b2 : q.d1);
-    }
-    const float dxdy = s[j].dx * s[j].dy;
-    const float w11 = dxdy, w01 = s[j].dy - dxdy, w10 = s[j].dx - dxdy, w00 = ((1.0f - s[j].dx) - s[j].dy) + dxdy;
-    float res = ((w11 * d11 + w01 * d01) + w10 * d10) + w00 * d00;
-    const bool good = s[j].valid && !(res > edist && filt);
-    if (!good) res = 0.0f;
-    const float wr = (res <= huber) ? 1.0f : revo_div(huber, res);
-    if constexpr (EXACT) accumulate_error_x<false>(res, wr, good, ed, 2 + j, acc + 1 + j);
-    else accumulate_error<false>(res, wr, good, ed + 2 + j, acc + CSLOT + 1 + j);
+    const RetryTerm t = retry_term(s[j], D0[j], D1[j], edist, filt, huber);
+    if constexpr (EXACT) accumulate_error_x<false>(t.res, t.wr, t.good, ed, 2 + j, acc + 1 + j);
+    else accumulate_error<false>(t.res, t.wr, t.good, ed + 2 + j, acc + CSLOT + 1 + j);
   }
 }
 

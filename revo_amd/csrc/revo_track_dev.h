@@ -6,6 +6,7 @@
 #pragma once
 #include "revo_dev.h"
 #include "revo_div.h"
+#include "revo_track_px.h"  // the per-point arithmetic in register pairs: projection, patch terms, Jacobian, normal-equation updates
 
 #define CSLOT 27  // float slots: 0..26 normal equations (21 + 6), CSLOT + j = good-point count of candidate j
 #define XERR 27   // exact-sums layout: double-double slots 0..26 = normal equations, XERR + k = error slot k (DSLOT below)
@@ -107,8 +108,6 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 typedef const float __attribute__((address_space(1)))* gf32p;
 typedef const f4v __attribute__((address_space(1)))* gf4p;
 
-// 12 DT samples around (ix,iy): rows iy-1 (2), iy (4), iy+1 (4), iy+2 (2)
-struct DtPatch { float a0, a1, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1; };
 // 4-byte aligned vector types: the middle rows of the patch are ONE dwordx4 gather each (global loads only need
 // dword alignment) -- a gather instruction costs the vector L1 one tag lookup per distinct cache line among the 64
 // lanes, whatever its width, and that lookup rate is part of what bounds the evaluation of the fine levels
@@ -118,37 +117,16 @@ typedef const f4u __attribute__((address_space(1)))* gf4up;
 typedef const f2u __attribute__((address_space(1)))* gf2up;
 __device__ __forceinline__ DtPatch load_patch(gf32p dt, int w, int ix, int iy) {
   gf32p p = dt + iy * w + ix;
-  DtPatch q;
+  DtPatch q;  // rows iy-1 (2), iy (4), iy+1 (4), iy+2 (2): the register pairs of revo_track_px.h, as the loads deliver them
   const f2u a = *(gf2up)(p - w);
   const f4u b = *(gf4up)(p - 1);
   const f4u c = *(gf4up)(p + w - 1);
   const f2u d = *(gf2up)(p + 2 * w);
-  q.a0 = a.x; q.a1 = a.y;
-  q.b0 = b.x; q.b1 = b.y; q.b2 = b.z; q.b3 = b.w;
-  q.c0 = c.x; q.c1 = c.y; q.c2 = c.z; q.c3 = c.w;
-  q.d0 = d.x; q.d1 = d.y;
+  q.a = tpx_mk(a.x, a.y);
+  q.b01 = tpx_mk(b.x, b.y); q.b23 = tpx_mk(b.z, b.w);
+  q.c01 = tpx_mk(c.x, c.y); q.c23 = tpx_mk(c.z, c.w);
+  q.d = tpx_mk(d.x, d.y);
   return q;
-}
-
-struct PtState { float X, Y, Z, rz, dx, dy; int ix, iy; bool valid; };  // rz: refined 1/Z (revo_div.h)
-struct Cam { float fx, fy, cx, cy, wlim, hlim; int w, h; };
-
-__device__ __forceinline__ PtState project_point(const f4v p, const float* R, const float* T, const Cam& c, bool in_range) {
-  PtState s;
-  s.X = ((R[0] * p.x + R[3] * p.y) + R[6] * p.z) + T[0];
-  s.Y = ((R[1] * p.x + R[4] * p.y) + R[7] * p.z) + T[1];
-  s.Z = ((R[2] * p.x + R[5] * p.y) + R[8] * p.z) + T[2];
-  // X/Z and Y/Z, correctly rounded, off ONE refined reciprocal (revo_div.h: the same bits as two IEEE divisions)
-  s.rz = revo_recip_refined(s.Z);
-  const float u = revo_div_with(s.X, s.Z, s.rz) * c.fx + c.cx;
-  const float v = revo_div_with(s.Y, s.Z, s.rz) * c.fy + c.cy;
-  s.valid = in_range && (u > 1.0f && v > 1.0f && u < c.wlim && v < c.hlim);  // optimizer.cpp:100 (NaN-safe form)
-  s.ix = s.valid ? (int)u : 1;
-  s.iy = s.valid ? (int)v : 1;
-  s.dx = u - (float)s.ix;
-  s.dy = v - (float)s.iy;
-  if (!s.valid) { s.X = 0.0f; s.Y = 0.0f; s.Z = 1.0f; s.rz = 1.0f; s.dx = 0.0f; s.dy = 0.0f; }
-  return s;
 }
 
 // The candidate's error terms.  The LM's accept / stop decisions compare exactly these sums (optimizer.cpp:129-133,273-278:
@@ -183,7 +161,7 @@ __device__ __forceinline__ void accumulate_error_x(float res, float wr, bool goo
 // xd[k] / xd[32 + k]: head / tail of slot k (0..20: A, upper triangle; 21..26: sum v[a]*(r*w), b = its negation).
 __device__ __forceinline__ void accumulate_terms_x(const PtState& s, float gx, float gy, float res, float wr, bool good, float* cnt,
                                                    double* xd) {
-  const float px = s.X, py = s.Y;
+  const float px = s.XY.x, py = s.XY.y;
   const float z = revo_div_with(1.0f, s.Z, s.rz);  // 1.0f / pz
   const float zs = revo_div(1.0f, s.Z * s.Z);      // 1.0f / (pz*pz)
   float v[6];
@@ -207,57 +185,24 @@ __device__ __forceinline__ void accumulate_terms_x(const PtState& s, float gx, f
 }
 
 // calcErrorAndBuffers' interpolation + filter + Huber (optimizer.cpp:106-133, optimizer.h:156-185)
-// fused with calculateWarpUpdate's Jacobian (optimizer.cpp:218-228) and LGS6::update.
+// fused with calculateWarpUpdate's Jacobian (optimizer.cpp:218-228) and LGS6::update (revo_track_px.h).
 // EXACT: acc = the KMAX good counts, ed = the 32 double-double slots (heads, then tails).
 template <bool EXACT>
 __device__ __forceinline__ void accumulate_point(const PtState& s, const DtPatch& q, float fx, float fy, float edist, bool filt,
                                                  float huber, float* acc, double* ed) {
-  // the reference's table entries at the four corners: (0.5(prev-next), 0.5(up-down), dt)
-  const float gx00 = 0.5f * (q.b0 - q.b2), gy00 = 0.5f * (q.a0 - q.c1), d00 = q.b1;
-  const float gx10 = 0.5f * (q.b1 - q.b3), gy10 = 0.5f * (q.a1 - q.c2), d10 = q.b2;
-  const float gx01 = 0.5f * (q.c0 - q.c2), gy01 = 0.5f * (q.b1 - q.d0), d01 = q.c1;
-  const float gx11 = 0.5f * (q.c1 - q.c3), gy11 = 0.5f * (q.b2 - q.d1), d11 = q.c2;
-  const float dxdy = s.dx * s.dy;
-  const float w11 = dxdy, w01 = s.dy - dxdy, w10 = s.dx - dxdy, w00 = ((1.0f - s.dx) - s.dy) + dxdy;
-  float r0 = ((w11 * gx11 + w01 * gx01) + w10 * gx10) + w00 * gx00;
-  float r1 = ((w11 * gy11 + w01 * gy01) + w10 * gy10) + w00 * gy00;
-  float res = ((w11 * d11 + w01 * d01) + w10 * d10) + w00 * d00;
-  const bool good = s.valid && !(res > edist && filt);  // optimizer.cpp:108
-  if (!good) { r0 = 0.0f; r1 = 0.0f; res = 0.0f; }
-  const float wr = (res <= huber) ? 1.0f : revo_div(huber, res);
-  const float gx = fx * r0, gy = fy * r1;
+  const PtTerm t = point_term(s, q, fx, fy, edist, filt, huber);
   if constexpr (EXACT) {
-    accumulate_terms_x(s, gx, gy, res, wr, good, acc, ed);
+    accumulate_terms_x(s, t.G.x, t.G.y, t.res, t.wr, t.good, acc, ed);
     return;
   }
-  const float z = revo_div_with(1.0f, s.Z, s.rz);
-  const float zs = z * z;  // reference: 1/(pz*pz), optimizer.cpp:213; differs by <= 1 ulp
-  float jv[6];
-  jv[0] = z * gx;
-  jv[1] = z * gy;
-  jv[2] = (-s.X * zs) * gx + (-s.Y * zs) * gy;
-  jv[3] = (-s.X * s.Y * zs) * gx + (-(1.0f + s.Y * s.Y * zs)) * gy;
-  jv[4] = (1.0f + s.X * s.X * zs) * gx + (s.X * s.Y * zs) * gy;
-  jv[5] = (-s.Y * z) * gx + (s.X * z) * gy;
-  float wv[6];
-#pragma unroll
-  for (int a = 0; a < 6; ++a) wv[a] = wr * jv[a];
-  {
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int c = a; c < 6; ++c) { acc[k] = fmaf(wv[a], jv[c], acc[k]); ++k; }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; ++a) acc[21 + a] = fmaf(wv[a], res, acc[21 + a]);
-  accumulate_error<true>(res, wr, good, ed, acc + CSLOT);
+  accumulate_normal(jacobian(s, t.G), t.wr, t.res, acc);
+  accumulate_error<true>(t.res, t.wr, t.good, ed, acc + CSLOT);
 }
 
 template <bool EXACT>
 __device__ __forceinline__ void full_point(const f4v p, gf32p dtm, const float* R, const float* T, const Cam& c, float edist,
                                            bool filt, float huber, float* acc, double* ed) {
-  const PtState s = project_point(p, R, T, c, true);
+  const PtState s = project_point(p.x, p.y, p.z, R, T, c, true);
   const DtPatch q = load_patch(dtm, c.w, s.ix, s.iy);
   accumulate_point<EXACT>(s, q, c.fx, c.fy, edist, filt, huber, acc, ed);
 }
