@@ -1474,6 +1474,93 @@ int revo_map_view_gain(revo_map* m, const revo_map_df_box* box, const uint8_t* s
                        const revo_map_gain_params* prm, revo_map_gain* out, int device_out,
                        revo_map_gain_info* info);
 
+/* ---- a surface: the TSDF volume fused from depth views, and the mesh of its zero level set -----------------
+ * The volume is one 8-byte cell per cell of a distance-field box (revo_map_df_box with its rules, z fastest, at most 2^27
+ * cells): the integer sum of the views' truncated signed distances in units of trunc / 1024, and how many views gave one.
+ * Every value is an integer decided by float32 arithmetic with one definition and the sums are integer sums, so the volume
+ * is a pure function of the inputs -- the same bytes on every run, whatever the launch and whatever the order of the views.
+ *
+ * The cell's point p is revo_map_observe's centre.  Per view, the class of p is revo_map_carve_eval's class at radius 0 with
+ * margin = trunc and margin_rel = 0, read exactly as there.  With dc the centre pixel's depth D[iv, iu] and z the camera-space
+ * depth of p that the class rule computes:
+ *   FREE       q = 1024                                                  (in front of the surface by more than trunc)
+ *   CONFIRMED  q = (int32_t)rintf(((dc - z) / trunc) * 1024.0f), a difference, a quotient, a product and the rounding to the
+ *              nearest integer (ties to even), each on its own; |z - dc| <= trunc holds, so |q| <= 1024 without a clamp
+ *   every other class: no update.
+ * An update is sum += q, weight += 1, the views taken in their order.  A cell whose weight has reached 2^20 takes no further
+ * update; a dropped update is counted in saturated.  So |sum| <= 2^30.
+ * Exact properties: while saturated == 0 the order of the views cannot show; revo_map_tsdf_fuse with views A followed by an
+ * accumulating call with views B leaves the bytes of one call with A and B together; a call that does not accumulate does not
+ * read the volume; for at most 127 views weight > 0 holds exactly where revo_map_observe with radius 0, margin = trunc and
+ * margin_rel = 0 leaves a byte other than 0, and view_info equals that call's view_info. */
+typedef struct revo_map_tsdf_cell {      /* 8 bytes */
+  int32_t sum;           /* the sum of q over the cell's updates, in units of trunc / 1024                 */
+  uint32_t weight;       /* the updates, at most 2^20                                                       */
+} revo_map_tsdf_cell;
+typedef struct revo_map_tsdf_params {    /* 16 bytes; NULL: 4 x the map's voxel edge, 0 */
+  float trunc;           /* metres, finite, > 0                                                             */
+  uint32_t accumulate;   /* 0: the volume is written; 1: it is read and updated                             */
+  uint32_t reserved[2];  /* zero */
+} revo_map_tsdf_params;
+typedef struct revo_map_tsdf_info {      /* 64 bytes, little-endian, no padding: integer sums, so order-free */
+  uint64_t cells;           /* n[0]*n[1]*n[2]                                               */
+  uint64_t updates;         /* the updates of this call                                     */
+  uint64_t cells_weighted;  /* cells with weight > 0 after the call                         */
+  uint64_t cells_inside;    /* of those, the cells with sum < 0                             */
+  uint64_t saturated;       /* the updates of this call that a full weight dropped          */
+  uint64_t reserved[3];     /* zero */
+} revo_map_tsdf_info;
+/* The volume of `box` from n views (1 .. 64; revo_map_carve_view with every rule of revo_map_carve_eval, device_in as there;
+ * every pyramid and image is checked before anything is enqueued, host images are uploaded to one temporary buffer).  Runs on
+ * the context's tracker stream, for a pyramid view behind that pyramid's build.  The map gives the context, the stream and the
+ * voxel edge and is not changed.
+ * device_tsdf = 0: tsdf, info and view_info (n records: the cells of the box by class, summing to cells) are host pointers and
+ * the call waits.  device_tsdf = 1: all three are device pointers of the map's device, 16-byte aligned; with device images or
+ * pyramids the call only enqueues, with host images it waits.  info and view_info may be NULL.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, views or tsdf; the box rules of
+ * revo_map_distance_field; n outside 1 .. 64; the view rules of revo_map_carve_eval; a trunc that is not finite or not > 0;
+ * accumulate above 1; a reserved word that is not 0; a flag outside 0 / 1; a misaligned device pointer. */
+int revo_map_tsdf_fuse(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views, int device_in,
+                       const revo_map_tsdf_params* prm, revo_map_tsdf_cell* tsdf, int device_tsdf, revo_map_tsdf_info* info,
+                       revo_map_carve_view_info* view_info);
+
+/* The mesh of the volume's zero level set, in one canonical order: a pure function of the volume's bytes, the box, the voxel
+ * edge and min_weight.  All decisions are integer.
+ * A cell is VALID when weight >= max(min_weight, 1) and INSIDE when it is valid and sum < 0 (sum >= 0 is outside).  A cube at
+ * the cell c has the corners c + {0,1}^3, all inside the box (a box with an axis of 1 has no cube); it is ACTIVE when all eight
+ * corners are valid.  An active cube is split into the six tetrahedra of the Kuhn triangulation, one per permutation pi of
+ * (x, y, z) in lexicographic order (xyz, xzy, yxz, yzx, zxy, zyx): v0 = c, v1 = v0 + e_pi(0), v2 = v1 + e_pi(1), v3 = c + (1,1,1).
+ * Face diagonals agree between neighbouring cubes, so the mesh is watertight inside the active region.
+ * Vertices sit on lattice edges.  An edge is (cell, type), type = dx + 2 dy + 4 dz - 1 in 0 .. 6, from the cell to cell +
+ * (dx, dy, dz).  It carries a vertex when its end points differ in INSIDE and it is an edge of a tetrahedron of at least one
+ * active cube (an axis edge belongs to four cubes, a face diagonal to two, the body diagonal to one).  With (s0, w0) the cell
+ * at the lower end and (s1, w1) at the upper: n0 = (int64)s0*w1, n1 = (int64)s1*w0 (both below 2^51 in size),
+ * a = (float)((double)n0 / (double)(n0 - n1)), and per axis pos_i = (((float)(lo_i + c_i) + 0.5f) + (d_i ? a : 0.0f)) * voxel,
+ * every operation rounded on its own.  Vertices are listed in ascending order of (the cell's place in the box, type).
+ * Triangles are listed in ascending order of (the cube's place, tetrahedron, k), three vertex indices each.  By how many of
+ * v0 .. v3 are inside: 0 or 4: none.  1 or 3, with a the lone corner and b < c < d the others: (ab, ac, ad).  2, with a < b
+ * inside and c < d outside: (ac, ad, bd) and (ac, bd, bc).  The triangles of a case are listed as written or all with their last
+ * two vertices swapped, whichever makes the normal point from the inside corners to the outside corners (decided at the edge
+ * midpoints in exact arithmetic).  With the case code = sum over the inside v_i of 2^i, they are swapped when bit `code` is
+ * set in 0x4D24 for the tetrahedra xyz, yzx, zxy and in 0x32DA for xzy, yxz, zyx.
+ * info: cells; valid; inside; cubes = (n[0]-1)(n[1]-1)(n[2]-1); cubes_active; vertices; triangles. */
+typedef struct revo_map_mesh_info {      /* 64 bytes, little-endian, no padding */
+  uint64_t cells, valid, inside, cubes, cubes_active, vertices, triangles;
+  uint64_t reserved;        /* zero */
+} revo_map_mesh_info;
+/* tsdf: the box's volume (device_tsdf: where it lives; a host volume is uploaded).  vertices: room for cap_vertices vertices of
+ * 3 floats, triangles: room for cap_triangles triangles of 3 indices (device_out: where both live).  n_vertices, n_triangles
+ * and info (may be NULL) are host pointers.  A counting pass runs first and the call waits for it: REVO_ERR_CAPACITY, with
+ * nothing written but the two counts and info, when an output that is not NULL holds fewer than there are.  vertices and
+ * triangles both NULL: count only (the caps are ignored); one of them NULL: only the other is written.  The order is the
+ * canonical one for host and device outputs alike.  Runs on the context's tracker stream; the map gives the context, the
+ * stream and the voxel edge and is not changed.
+ * REVO_ERR_INVALID_ARG, with nothing written: NULL m, box, tsdf, n_vertices or n_triangles; the box rules; a flag outside
+ * 0 / 1; a device pointer that is not 16-byte aligned. */
+int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, int device_tsdf, uint32_t min_weight,
+                       float* vertices, size_t cap_vertices, uint32_t* triangles, size_t cap_triangles, size_t* n_vertices,
+                       size_t* n_triangles, int device_out, revo_map_mesh_info* info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -182,6 +182,9 @@ def lib():
     L.revo_map_known_field.argtypes = [vp, C.POINTER(MapDfBox), C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint32, vp, C.c_int, vp]
     L.revo_map_frontiers.argtypes = [vp, C.POINTER(MapDfBox), C.c_uint32, vp, C.c_int, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.revo_map_view_gain.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.POINTER(MapView), C.c_size_t, vp, C.c_int, C.POINTER(MapGainParams), vp, C.c_int, vp]
+    L.revo_map_tsdf_fuse.argtypes = [vp, C.POINTER(MapDfBox), C.c_int, C.POINTER(MapCarveView), C.c_int, C.POINTER(MapTsdfParams), vp, C.c_int, vp, vp]
+    L.revo_map_tsdf_mesh.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_size_t), C.c_int, vp]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

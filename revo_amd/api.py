@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapMeshInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -952,6 +952,102 @@ class VoxelMap:
             self.sync()
         del keep
 
+    # -- a surface (revo_map_tsdf_fuse / revo_map_tsdf_mesh)
+    def _tsdf_box(self, vol, lo=None, n=None):
+        if lo is not None or n is not None:
+            raise ValueError("a TSDF volume brings its own box: lo and n are not given with it")
+        if np.float32(vol.voxel).tobytes() != np.float32(self.voxel).tobytes():
+            raise ValueError("the TSDF volume was fused at voxels of %g m, the map has %g m" % (vol.voxel, self.voxel))
+        cells = np.ascontiguousarray(vol.cells)
+        return self._df_box(vol.lo, cells.shape, 0, 1), cells
+
+    def fuse(self, views, lo=None, n=None, pad=8, trunc=None, into=None):
+        """The views fused into a truncated signed distance volume -> TsdfVolume: per cell of a box of voxel indices the integer
+        sum of the views' signed distances to the surface they measured, in units of trunc / 1024, and the number of views that
+        gave one (revo_map_tsdf_fuse).  views: as carve_eval and observe take them; the class of a cell's centre in a
+        view is carve_eval's at radius 0 with margin = trunc.  lo, n: the box (by default the map's bounds grown by `pad` cells).
+        trunc: metres (default 4 voxel edges).  into: a TsdfVolume to accumulate into (it is not changed); its box and trunc are
+        the call's, so lo, n and trunc are not given.  The map's voxels play no part."""
+        from . import mapfile
+        cv, device_in, keep = self._carve_views(views)
+        if into is not None:
+            if trunc is not None and np.float32(trunc).tobytes() != np.float32(into.trunc).tobytes():
+                raise ValueError("a TSDF volume brings its own trunc")
+            box, vol = self._tsdf_box(into, lo, n)
+            vol, trunc = vol.copy(), into.trunc
+        else:
+            box = self._df_box(lo, n, pad, 1)
+            vol = np.empty(tuple(box.n), mapfile.TSDF_CELL_DTYPE)
+        trunc = float(mapfile.tsdf_trunc(self.voxel, trunc))
+        prm = MapTsdfParams(trunc, 0 if into is None else 1)
+        info, vinfo = MapTsdfInfo(), (MapCarveViewInfo * len(cv))()
+        check(_lib.lib().revo_map_tsdf_fuse(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vol.ctypes.data_as(vp), 0, C.byref(info),
+                                            C.cast(vinfo, vp)))
+        del keep
+        return TsdfVolume(vol, np.array(list(box.lo), np.int32), self.voxel, trunc, {k: int(getattr(info, k)) for k in mapfile.TSDF_INFO_KEYS},
+                          self._view_counts(vinfo), self)
+
+    def fuse_into(self, d_tsdf, views, lo, trunc=None, accumulate=False, d_info=None, d_view_info=None, wait=True):
+        """fuse() into a torch device tensor: d_tsdf int32 [n0, n1, n2, 2] (sum, weight; the box's cells are its first three
+        sizes), d_info None or 64 bytes (revo_map_tsdf_info), d_view_info None or 32 bytes per view; contiguous, 16-byte aligned,
+        on the map's device.  accumulate: d_tsdf is read and updated.  With device or pyramid views the call is only enqueued on
+        the context's tracker stream: wait=False returns at once (sync() orders later reads)."""
+        from . import mapfile
+        cv, device_in, keep = self._carve_views(views)
+        if d_tsdf.dim() != 4 or d_tsdf.shape[3] != 2 or str(d_tsdf.dtype) != "torch.int32":
+            raise ValueError("d_tsdf must be an int32 tensor [n0, n1, n2, 2]")
+        box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
+        for t_, size in ((d_tsdf, None), (d_info, 64), (d_view_info, 32 * len(cv))):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("output tensors must be contiguous device tensors")
+            if t_ is not None and size is not None and t_.numel() * t_.element_size() != size:
+                raise ValueError("d_info needs 64 bytes and d_view_info 32 bytes per view")
+        prm = MapTsdfParams(float(mapfile.tsdf_trunc(self.voxel, trunc)), 1 if accumulate else 0)
+        import torch
+        torch.cuda.current_stream(d_tsdf.device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
+        check(_lib.lib().revo_map_tsdf_fuse(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vp(d_tsdf.data_ptr()), 1,
+                                            vp(d_info.data_ptr()) if d_info is not None else None,
+                                            vp(d_view_info.data_ptr()) if d_view_info is not None else None))
+        if wait:
+            self.sync()
+        del keep
+
+    def mesh(self, tsdf, min_weight=1):
+        """The mesh of a TsdfVolume's zero level set -> mapfile.Mesh: vertices, triangles and the call's counts, in the contract's
+        canonical order (revo_map_tsdf_mesh).  A cell counts when its weight >= max(min_weight, 1)."""
+        from . import mapfile
+        box, cells = self._tsdf_box(tsdf)
+        L, nv, nt, info = _lib.lib(), C.c_size_t(), C.c_size_t(), MapMeshInfo()
+        args = (self._h, C.byref(box), cells.ctypes.data_as(vp), 0, int(min_weight))
+        check(L.revo_map_tsdf_mesh(*args, None, 0, None, 0, C.byref(nv), C.byref(nt), 0, C.byref(info)))
+        v, t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.uint32)
+        if nv.value or nt.value:
+            check(L.revo_map_tsdf_mesh(*args, v.ctypes.data_as(vp), nv.value, t.ctypes.data_as(vp), nt.value, C.byref(nv), C.byref(nt), 0, C.byref(info)))
+        return mapfile.Mesh(v, t, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS})
+
+    def mesh_into(self, d_vertices, d_triangles, d_tsdf, lo, min_weight=1):
+        """mesh() between torch device tensors: d_tsdf int32 [n0, n1, n2, 2] as fuse_into leaves it, d_vertices float32 [cap, 3],
+        d_triangles int32 [cap, 3]; contiguous, 16-byte aligned, on the map's device.  -> (vertices, triangles, info dict): the
+        counts; RevoError (REVO_ERR_CAPACITY), with nothing written, when a tensor holds fewer.  Both None: count only.  The call
+        waits for the map's stream first, so a fuse_into(wait=False) before it needs no sync()."""
+        from . import mapfile
+        if d_tsdf.dim() != 4 or d_tsdf.shape[3] != 2 or str(d_tsdf.dtype) != "torch.int32":
+            raise ValueError("d_tsdf must be an int32 tensor [n0, n1, n2, 2]")
+        box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
+        for t_, dt in ((d_vertices, "torch.float32"), (d_triangles, "torch.int32")):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda and t_.dim() == 2 and t_.shape[1] == 3 and str(t_.dtype) == dt):
+                raise ValueError("d_vertices is a float32 and d_triangles an int32 contiguous device tensor [cap, 3]")
+        if not (d_tsdf.is_contiguous() and d_tsdf.is_cuda):
+            raise ValueError("d_tsdf must be a contiguous device tensor")
+        import torch
+        torch.cuda.current_stream(d_tsdf.device).synchronize()
+        nv, nt, info = C.c_size_t(), C.c_size_t(), MapMeshInfo()
+        check(_lib.lib().revo_map_tsdf_mesh(self._h, C.byref(box), vp(d_tsdf.data_ptr()), 1, int(min_weight),
+                                            vp(d_vertices.data_ptr()) if d_vertices is not None else None, len(d_vertices) if d_vertices is not None else 0,
+                                            vp(d_triangles.data_ptr()) if d_triangles is not None else None, len(d_triangles) if d_triangles is not None else 0,
+                                            C.byref(nv), C.byref(nt), 1, C.byref(info)))
+        return nv.value, nt.value, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS}
+
     def frontiers(self, seen, min_views=1, min_count=1):
         """Where known space ends -> [k, 3] int32 voxel indices in ascending order of the cell's place in the box: the cells
         of a SeenVolume that are not solid, have >= min_views free votes and have a face neighbour inside the box that is
@@ -1443,6 +1539,53 @@ class SeenVolume:
         return cls(*mapfile.read_seen(path))
 
 
+class TsdfVolume:
+    """Depth views fused into a truncated signed distance volume over a box of voxel indices (VoxelMap.fuse, `mapfile tsdf`;
+    DESIGN 26): cells [n0, n1, n2] of (sum int32, weight uint32) -- the integer sum of the views' signed distances in units of
+    trunc / 1024 and the views that gave one --, lo the box's first voxel index, n its cells per axis, voxel the map's edge and
+    trunc the truncation distance in metres, info the last call's counters (mapfile.TSDF_INFO_KEYS) and view_info its per-view
+    class counts (None for a loaded volume)."""
+
+    def __init__(self, cells, lo, voxel, trunc, info=None, view_info=None, map=None):
+        from . import mapfile
+        cells = np.asarray(cells)
+        if cells.dtype != mapfile.TSDF_CELL_DTYPE or cells.ndim != 3:
+            raise ValueError("a TSDF volume is a 3-D array of (sum int32, weight uint32) cells")
+        self.cells = cells
+        self.lo = np.asarray(lo, np.int32).reshape(3)
+        self.n = np.asarray(cells.shape, np.int32)
+        self.voxel = float(np.float32(voxel))
+        self.trunc = float(mapfile.tsdf_trunc(voxel, trunc))
+        self.info = info
+        self.view_info = view_info
+        self._map = map
+
+    def sdf(self):
+        """[n0, n1, n2] float64 metres: sum / weight * trunc / 1024 (positive in front of the surface), NaN where no view gave
+        a distance."""
+        from . import mapfile
+        return mapfile.tsdf_sdf(self.cells, self.trunc)
+
+    def mesh(self, min_weight=1, map=None):
+        """The mesh of the zero level set -> mapfile.Mesh, on the device of the map the volume was fused with (or `map`); a
+        loaded volume without one is meshed by mapfile.mesh_records, which gives the same bytes."""
+        from . import mapfile
+        m = map if map is not None else self._map
+        if m is None:
+            return mapfile.mesh_records(self.cells, self.lo, self.voxel, min_weight)
+        return m.mesh(self, min_weight)
+
+    def save(self, path):
+        """The .npz `python -m revo_amd.mapfile tsdf` writes: sum, weight, lo, n, voxel, trunc."""
+        from . import mapfile
+        return mapfile.write_tsdf(path, self.cells, self.lo, self.voxel, self.trunc)
+
+    @classmethod
+    def load(cls, path):
+        from . import mapfile
+        return cls(*mapfile.read_tsdf(path))
+
+
 def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
     """The whole route from mapping to exploration on the map's device: the known field of `seen` (a SeenVolume), its
     frontiers, the cost-to-go with the frontiers as goals at the clearance (metres), and the path from `start` (a voxel index,
@@ -1764,6 +1907,19 @@ class MapWindow:
 
     def view_gain_into(self, *args, **kw):
         return self.map.view_gain_into(*args, **kw)
+
+    def fuse(self, *args, **kw):
+        """The inner map's fuse: depth views into a TSDF volume, by default over the voxels the window holds now."""
+        return self.map.fuse(*args, **kw)
+
+    def fuse_into(self, *args, **kw):
+        return self.map.fuse_into(*args, **kw)
+
+    def mesh(self, *args, **kw):
+        return self.map.mesh(*args, **kw)
+
+    def mesh_into(self, *args, **kw):
+        return self.map.mesh_into(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

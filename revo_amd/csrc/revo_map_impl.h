@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -165,11 +165,16 @@ enum { CARVE_OUTSIDE = 0, CARVE_UNKNOWN = 1, CARVE_FREE = 2, CARVE_CONFIRMED = 3
 
 // The class of the point p in one view: the one text of the contract's rule.  Every read of the depth image lies inside a
 // window that has been tested against the image size first, and |u|, |v| < 2^20 bounds the integers the test is made on.
-__device__ __forceinline__ int map_carve_class(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel) {
+// ZD: the camera-space depth z and (for a CONFIRMED point) the centre pixel's depth dc go out as well -- map_carve_class_zd, for
+// revo_map_tsdf.hip; without it the two pointers are not looked at and the function is what it was.
+template <bool ZD>
+__device__ __forceinline__ int map_carve_class_t(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel,
+                                                 float* z_out, float* dc_out) {
   const CarveView& c = vw.v;
   const float x = ((c.Rc[0] * px + c.Rc[1] * py) + c.Rc[2] * pz) + c.tc[0];
   const float y = ((c.Rc[3] * px + c.Rc[4] * py) + c.Rc[5] * pz) + c.tc[1];
   const float z = ((c.Rc[6] * px + c.Rc[7] * py) + c.Rc[8] * pz) + c.tc[2];
+  if (ZD) *z_out = z;
   if (!isfinite(x) || !isfinite(y) || !map_depth_ok(z, c.zmin, c.zmax)) return CARVE_OUTSIDE;
   const float u = __fdiv_rn(c.fx * x, z) + c.cx;
   const float v = __fdiv_rn(c.fy * y, z) + c.cy;
@@ -190,8 +195,18 @@ __device__ __forceinline__ int map_carve_class(float px, float py, float pz, con
   if (z < dmin - (margin + margin_rel * dmin)) return CARVE_FREE;
   const float dc = vw.depth[(size_t)iv * c.w + iu];
   const float mc = margin + margin_rel * dc;
+  if (ZD) *dc_out = dc;
   if (fabsf(z - dc) <= mc) return CARVE_CONFIRMED;
   return z > dc + mc ? CARVE_OCCLUDED : CARVE_EDGE;
+}
+__device__ __forceinline__ int map_carve_class(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel) {
+  return map_carve_class_t<false>(px, py, pz, vw, r, margin, margin_rel, nullptr, nullptr);
+}
+// The same text, and beside the class the depths it was decided on: *z for every class (the camera-space depth), *dc where the
+// class is CONFIRMED, OCCLUDED or EDGE (the centre pixel's depth).
+__device__ __forceinline__ int map_carve_class_zd(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel,
+                                                  float* z, float* dc) {
+  return map_carve_class_t<true>(px, py, pz, vw, r, margin, margin_rel, z, dc);
 }
 
 // Block compaction in arrival order.  s_n (LDS) is zero behind the kernel's first barrier; every selected thread draws its
@@ -306,6 +321,10 @@ struct revo_map {
   // revo_map_view_gain (revo_map_gain.hip): the predicted depth images of a launch's poses, the poses' descriptors (ray views
   // and gain poses), the counter lines, and the device records of a host-output call
   DevBuf gaindepth, gaindesc, gaincnt, gainout;
+  // revo_map_tsdf_fuse / revo_map_tsdf_mesh (revo_map_tsdf.hip): the views of a call, its counter lines, the device copy of a host
+  // volume (in or out), and the mesh's scratch: a byte and a word per cell, the block totals, the device outputs of a host call
+  HostRows<MapCarveView> tsdf_views;
+  DevBuf tsdfcnt, tsdfvol, meshwork, meshout;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every

@@ -1,0 +1,477 @@
+// revo_map_tsdf.hip -- a surface: revo_map_tsdf_fuse, the truncated signed distance volume of a box of voxel indices
+// fused from depth views with integer sums, and revo_map_tsdf_mesh, the mesh of its zero level set over the Kuhn tetrahedra of
+// the cells' cubes, in one canonical order.  Contracts: include/revo_hip.h.  Every value is an integer that float32 arithmetic
+// with one definition decides, or (a vertex) a float that one chain of separately rounded operations gives.
+#include "revo_map_impl.h"
+#include "revo_seen_host.h"  // a cell's point is the seen volume's
+#include "revo_tsdf_host.h"
+
+#define TSDF_RUN 4  // consecutive cells of a thread: two 16-byte words of the volume
+
+struct TsdfFuseK {
+  const MapCarveView* views; int n;
+  unsigned accumulate;
+  float trunc, voxel;
+  revo_map_df_box box;
+  unsigned cells;
+  int2* tsdf;         // 16-byte aligned: thread t owns the cells 4 t .. 4 t + 3
+  u64* info;          // one 64-byte line: revo_map_tsdf_info
+  unsigned* vinfo;    // 8 words per view: revo_map_carve_view_info
+};
+enum { TF_CELLS = 0, TF_UPDATES = 1, TF_WEIGHTED = 2, TF_INSIDE = 3, TF_SATURATED = 4 };
+
+static_assert(sizeof(revo_map_tsdf_cell) == 8 && offsetof(revo_map_tsdf_cell, weight) == 4 && sizeof(int2) == 8, "a cell is one 8-byte word");
+static_assert(sizeof(revo_map_tsdf_params) == 16 && offsetof(revo_map_tsdf_params, accumulate) == 4 && offsetof(revo_map_tsdf_params, reserved) == 8,
+              "the parameter record is the documented layout");
+static_assert(sizeof(revo_map_tsdf_info) == 64 && offsetof(revo_map_tsdf_info, cells) == 8 * TF_CELLS &&
+              offsetof(revo_map_tsdf_info, updates) == 8 * TF_UPDATES && offsetof(revo_map_tsdf_info, cells_weighted) == 8 * TF_WEIGHTED &&
+              offsetof(revo_map_tsdf_info, cells_inside) == 8 * TF_INSIDE && offsetof(revo_map_tsdf_info, saturated) == 8 * TF_SATURATED &&
+              offsetof(revo_map_tsdf_info, reserved) == 40, "the info record is the kernel's counter line");
+
+__device__ __forceinline__ unsigned tsdf_wave_sum(unsigned v) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;  // lane 0 holds the wave's sum
+}
+
+// One thread per run of TSDF_RUN cells that follow each other in memory (z fastest; consecutive lanes take consecutive runs: a
+// wave's projections fall on neighbouring pixels, as in k_map_observe).  The views are read through uniform addresses one after
+// another; a cell's sum and weight stay in registers from the one read (when accumulating) to the one write: two 16-byte words
+// for a whole run, 8-byte words for the tail of a volume whose cells are no multiple of four.  Per view the classes of a wave
+// are counted by ballots into LDS; every counter takes one global atomic per block.  No atomic touches a cell.
+__global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
+  __shared__ unsigned s_cls[CARVE_MAX_VIEWS * CARVE_CLASSES];
+  __shared__ unsigned s_cnt[4];  // updates, weighted, inside, saturated
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256) s_cls[k] = 0;
+  if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const size_t c0 = (size_t)(blockIdx.x * 256u + threadIdx.x) * TSDF_RUN;  // the first cell of the run
+  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
+  bool valid[TSDF_RUN];
+  float px[TSDF_RUN], py[TSDF_RUN], pz[TSDF_RUN];
+  int sum[TSDF_RUN];
+  unsigned weight[TSDF_RUN];
+#pragma unroll
+  for (int j = 0; j < TSDF_RUN; ++j) {
+    const size_t c = c0 + j;
+    valid[j] = c < a.cells;
+    const unsigned cc = valid[j] ? (unsigned)c : 0u;
+    const unsigned line = cc / nz, iz = cc - line * nz;
+    const unsigned ix = line / ny, iy = line - ix * ny;
+    px[j] = seen_centre(a.box.lo[0], (int)ix, a.voxel);
+    py[j] = seen_centre(a.box.lo[1], (int)iy, a.voxel);
+    pz[j] = seen_centre(a.box.lo[2], (int)iz, a.voxel);
+    sum[j] = 0;
+    weight[j] = 0u;
+  }
+  const bool whole = valid[TSDF_RUN - 1];  // the four cells exist, and tsdf + c0 is 16-byte aligned
+  if (a.accumulate) {
+    if (whole) {
+      const int4 lo = *(const int4*)(a.tsdf + c0), hi = *(const int4*)(a.tsdf + c0 + 2);
+      sum[0] = lo.x; weight[0] = (unsigned)lo.y; sum[1] = lo.z; weight[1] = (unsigned)lo.w;
+      sum[2] = hi.x; weight[2] = (unsigned)hi.y; sum[3] = hi.z; weight[3] = (unsigned)hi.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < TSDF_RUN; ++j)
+        if (valid[j]) { const int2 v = a.tsdf[c0 + j]; sum[j] = v.x; weight[j] = (unsigned)v.y; }
+    }
+  }
+  unsigned n_upd = 0, n_sat = 0;
+  for (int vi = 0; vi < a.n; ++vi) {  // uniform: the ballots see whole waves
+    int cls[TSDF_RUN];
+#pragma unroll
+    for (int j = 0; j < TSDF_RUN; ++j) {
+      float z = 0.0f, dc = 0.0f;
+      cls[j] = valid[j] ? map_carve_class_zd(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
+      if (cls[j] == CARVE_FREE || cls[j] == CARVE_CONFIRMED) {
+        const int q = cls[j] == CARVE_FREE ? TSDF_Q_ONE : tsdf_quantum(dc, z, a.trunc);
+        const unsigned dropped = tsdf_update(sum[j], weight[j], q);
+        n_sat += dropped;
+        n_upd += 1u - dropped;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < CARVE_CLASSES; ++k) {
+      unsigned cnt = 0;
+#pragma unroll
+      for (int j = 0; j < TSDF_RUN; ++j) cnt += (unsigned)__popcll(__ballot(cls[j] == k));
+      if (lane == 0 && cnt) atomicAdd(&s_cls[vi * CARVE_CLASSES + k], cnt);
+    }
+  }
+  unsigned n_weighted = 0, n_inside = 0;
+#pragma unroll
+  for (int j = 0; j < TSDF_RUN; ++j)
+    if (valid[j]) {
+      n_weighted += weight[j] > 0u;
+      n_inside += weight[j] > 0u && sum[j] < 0;
+    }
+  if (whole) {
+    *(int4*)(a.tsdf + c0) = make_int4(sum[0], (int)weight[0], sum[1], (int)weight[1]);
+    *(int4*)(a.tsdf + c0 + 2) = make_int4(sum[2], (int)weight[2], sum[3], (int)weight[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < TSDF_RUN; ++j)
+      if (valid[j]) a.tsdf[c0 + j] = make_int2(sum[j], (int)weight[j]);
+  }
+  n_upd = tsdf_wave_sum(n_upd); n_weighted = tsdf_wave_sum(n_weighted); n_inside = tsdf_wave_sum(n_inside); n_sat = tsdf_wave_sum(n_sat);
+  if (lane == 0) {  // a block's updates: at most 256 * 4 * 64
+    if (n_upd) atomicAdd(&s_cnt[0], n_upd);
+    if (n_weighted) atomicAdd(&s_cnt[1], n_weighted);
+    if (n_inside) atomicAdd(&s_cnt[2], n_inside);
+    if (n_sat) atomicAdd(&s_cnt[3], n_sat);
+  }
+  __syncthreads();
+  if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&a.info[TF_UPDATES + threadIdx.x], (u64)s_cnt[threadIdx.x]);
+  if (blockIdx.x == 0 && threadIdx.x == 4) a.info[TF_CELLS] = (u64)a.cells;
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256)
+    if (s_cls[k]) atomicAdd(&a.vinfo[(k / CARVE_CLASSES) * 8 + k % CARVE_CLASSES], s_cls[k]);
+}
+
+extern "C" int revo_map_tsdf_fuse(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views, int device_in,
+                                  const revo_map_tsdf_params* prm, revo_map_tsdf_cell* tsdf, int device_tsdf, revo_map_tsdf_info* info,
+                                  revo_map_carve_view_info* view_info) {
+  if (!m || !box || !views || !tsdf) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  size_t cells = 0;
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_tsdf_fuse: ") + why);
+  if (n < 1 || n > CARVE_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, "revo_map_tsdf_fuse: n must be 1 .. 64 views");
+  TRY(map_check_side(device_in, "device_in"));
+  TRY(map_check_side(device_tsdf, "device_tsdf"));
+  if (device_tsdf) TRY(map_check_aligned((uintptr_t)tsdf | (uintptr_t)info | (uintptr_t)view_info, 16, "a device output is"));
+  revo_map_tsdf_params pp;
+  if (const char* why = tsdf_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_tsdf_fuse: ") + why);
+  std::vector<MapCarveView> hv(n);
+  size_t up_bytes = 0;
+  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes));
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  const size_t vinfo_bytes = sizeof(revo_map_carve_view_info) * (size_t)n, vol_bytes = sizeof(revo_map_tsdf_cell) * cells;
+  TRY(m->tsdf_views.reserve(n, s));  // waits until the previous call's upload has read the pinned rows
+  TRY(m->tsdfcnt.reserve(256 + sizeof(revo_map_carve_view_info) * CARVE_MAX_VIEWS, s));
+  TRY(m->tsdfvol.reserve(device_tsdf ? 0 : vol_bytes, s));
+  DevScratch images;  // host depth images of the call, uploaded; freed behind the wait below
+  if (up_bytes) {
+    TRY(images.alloc(up_bytes));
+    TRY(map_views_upload(n, views, hv.data(), images.p, s));
+  }
+  memcpy(m->tsdf_views.h, hv.data(), sizeof(MapCarveView) * n);
+  TRY(m->tsdf_views.upload(n, s));
+  TsdfFuseK a{};
+  a.views = m->tsdf_views.d; a.n = n;
+  a.accumulate = pp.accumulate;
+  a.trunc = pp.trunc; a.voxel = m->voxel;
+  a.box = *box;
+  a.cells = (unsigned)cells;
+  a.tsdf = device_tsdf ? (int2*)tsdf : (int2*)m->tsdfvol.p;
+  a.info = device_tsdf && info ? (u64*)info : (u64*)m->tsdfcnt.p;
+  a.vinfo = device_tsdf && view_info ? (unsigned*)view_info : (unsigned*)(m->tsdfcnt.p + 256);
+  if (!device_tsdf && pp.accumulate) HIPCHECK(hipMemcpyAsync(a.tsdf, tsdf, vol_bytes, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemsetAsync(a.info, 0, sizeof(revo_map_tsdf_info), s));
+  HIPCHECK(hipMemsetAsync(a.vinfo, 0, vinfo_bytes, s));
+  const size_t runs = (cells + TSDF_RUN - 1) / TSDF_RUN;
+  hipLaunchKernelGGL(k_tsdf_fuse, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, s, a);
+  HIPCHECK(hipGetLastError());
+  if (!device_tsdf) {
+    HIPCHECK(hipMemcpyAsync(tsdf, a.tsdf, vol_bytes, hipMemcpyDeviceToHost, s));
+    if (info) HIPCHECK(hipMemcpyAsync(info, a.info, sizeof(revo_map_tsdf_info), hipMemcpyDeviceToHost, s));
+    if (view_info) HIPCHECK(hipMemcpyAsync(view_info, a.vinfo, vinfo_bytes, hipMemcpyDeviceToHost, s));
+  }
+  if (!device_tsdf || up_bytes) HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- the mesh --
+// The scratch of a call, all in m->meshwork: a byte per cell (bit 0 valid, bit 1 inside), a word per cell (below), a pair of
+// totals per block of 256 cells -- after the scan the vertices and triangles before the block --, and the counter line.
+// A cell's word: bits 0 .. 6 the types of the edges at the cell that carry a vertex, bit 7 the cell's cube is active, bits
+// 8 .. 18 the vertices of the block before the cell (< 7 * 256), bits 19 .. 30 the triangles of the block before it (< 12 * 256).
+enum { MI_CELLS = 0, MI_VALID = 1, MI_INSIDE = 2, MI_CUBES = 3, MI_ACTIVE = 4, MI_VERTICES = 5, MI_TRIANGLES = 6 };
+static_assert(sizeof(revo_map_mesh_info) == 64 && offsetof(revo_map_mesh_info, valid) == 8 * MI_VALID && offsetof(revo_map_mesh_info, inside) == 8 * MI_INSIDE &&
+              offsetof(revo_map_mesh_info, cubes_active) == 8 * MI_ACTIVE && offsetof(revo_map_mesh_info, vertices) == 8 * MI_VERTICES &&
+              offsetof(revo_map_mesh_info, triangles) == 8 * MI_TRIANGLES && offsetof(revo_map_mesh_info, reserved) == 56, "the info record is the counter line");
+#define MESH_ACTIVE 0x80u
+#define MESH_VLOCAL(w) (((w) >> 8) & 0x7ffu)
+#define MESH_TLOCAL(w) (((w) >> 19) & 0xfffu)
+
+struct MeshK {
+  const int2* tsdf;
+  revo_map_df_box box;
+  unsigned cells, min_weight, blocks;
+  float voxel;
+  uint8_t* flags;
+  unsigned* words;
+  uint2* totals;   // per block: vertices, triangles; exclusive prefixes behind k_mesh_scan
+  u64* info;
+  float* vertices;
+  unsigned* triangles;
+};
+
+// The exclusive prefix of v over the block's threads and the block's total; s_w: one word per wave.
+template <int WAVES>
+__device__ __forceinline__ unsigned mesh_block_scan(unsigned v, unsigned* s_w, unsigned* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned t = __shfl_up(inc, off, 64);
+    if (lane >= off) inc += t;
+  }
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  unsigned base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    const unsigned x = s_w[w];
+    base += w < wave ? x : 0u;
+    tot += x;
+  }
+  __syncthreads();  // s_w may be written again
+  *total = tot;
+  return base + inc - v;
+}
+
+// One thread per cell: what the cell says, as a byte.
+__global__ void __launch_bounds__(256) k_mesh_flags(const MeshK a) {
+  __shared__ unsigned s_cnt[2];
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned c = blockIdx.x * 256u + threadIdx.x;
+  bool valid = false, inside = false;
+  if (c < a.cells) {
+    const int2 v = a.tsdf[c];
+    valid = tsdf_valid((unsigned)v.y, a.min_weight);
+    inside = tsdf_inside(v.x, (unsigned)v.y, a.min_weight);
+    a.flags[c] = (uint8_t)((valid ? 1u : 0u) | (inside ? 2u : 0u));
+  }
+  const unsigned nv = (unsigned)__popcll(__ballot(valid)), ni = (unsigned)__popcll(__ballot(inside));
+  if ((threadIdx.x & 63) == 0) {
+    if (nv) atomicAdd(&s_cnt[0], nv);
+    if (ni) atomicAdd(&s_cnt[1], ni);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&a.info[MI_VALID + threadIdx.x], (u64)s_cnt[threadIdx.x]);
+}
+
+// the bit of the neighbour at the offset (dx, dy, dz), each in -1 .. 1, in a cell's 27-neighbourhood masks
+__device__ __forceinline__ constexpr unsigned mesh_nb_bit(int dx, int dy, int dz) { return 1u << ((dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)); }
+// the neighbourhood bits of the corners of the cube at cell - o (o: a corner number)
+__device__ __forceinline__ constexpr unsigned mesh_cube_bits(unsigned o) {
+  unsigned m = 0;
+  for (unsigned e = 0; e < 8; ++e) m |= mesh_nb_bit((int)(e & 1) - (int)(o & 1), (int)((e >> 1) & 1) - (int)((o >> 1) & 1), (int)((e >> 2) & 1) - (int)((o >> 2) & 1));
+  return m;
+}
+__device__ __forceinline__ constexpr unsigned mesh_corner_bit(unsigned v) { return mesh_nb_bit((int)(v & 1), (int)((v >> 1) & 1), (int)((v >> 2) & 1)); }
+// the case code of the tetrahedron k of the cube whose corners' inside flags are the bits of `in8` (bit v: corner v)
+__device__ __forceinline__ unsigned mesh_tetra_code(unsigned in8, int k) {
+  const unsigned v12 = tsdf_tetra_v12(k);
+  return (in8 & 1u) | (((in8 >> (v12 & 7u)) & 1u) << 1) | (((in8 >> (v12 >> 4)) & 1u) << 2) | (((in8 >> 7) & 1u) << 3);
+}
+
+// One thread per cell.  The bytes of the cell's 27-neighbourhood (0 outside the box) go into two masks; from them the eight
+// cubes the cell is a corner of are active or not, an edge at the cell carries a vertex or not, and the cell's own cube has its
+// triangles counted.  The block's prefix sums go into the cell's word, its totals into the block's pair.
+__global__ void __launch_bounds__(256) k_mesh_count(const MeshK a) {
+  __shared__ unsigned s_w[4];
+  const unsigned c = blockIdx.x * 256u + threadIdx.x;
+  const int nx = a.box.n[0], ny = a.box.n[1], nz = a.box.n[2];
+  unsigned mask = 0, active = 0, ntri = 0;
+  if (c < a.cells) {
+    const unsigned line = c / (unsigned)nz;
+    const int iz = (int)(c - line * (unsigned)nz), ix = (int)(line / (unsigned)ny), iy = (int)(line - (unsigned)ix * (unsigned)ny);
+    unsigned vmask = 0, imask = 0;
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx)
+#pragma unroll
+      for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dz = -1; dz <= 1; ++dz) {
+          const int x = ix + dx, y = iy + dy, z = iz + dz;
+          if (x >= 0 && x < nx && y >= 0 && y < ny && z >= 0 && z < nz) {
+            const unsigned f = a.flags[((size_t)x * ny + y) * nz + z];
+            vmask |= (f & 1u) ? mesh_nb_bit(dx, dy, dz) : 0u;
+            imask |= (f & 2u) ? mesh_nb_bit(dx, dy, dz) : 0u;
+          }
+        }
+    unsigned cubes = 0;  // bit o: the cube at cell - o is active
+#pragma unroll
+    for (unsigned o = 0; o < 8; ++o) cubes |= (vmask & mesh_cube_bits(o)) == mesh_cube_bits(o) ? 1u << o : 0u;
+    const bool in0 = (imask & mesh_corner_bit(0)) != 0;
+#pragma unroll
+    for (unsigned t = 0; t < 7; ++t) {
+      unsigned owners = 0;
+#pragma unroll
+      for (unsigned o = 0; o < 8; ++o) owners |= tsdf_edge_in_cube(t, o) ? 1u << o : 0u;
+      const bool in1 = (imask & mesh_corner_bit(t + 1u)) != 0;
+      mask |= (in0 != in1 && (cubes & owners)) ? 1u << t : 0u;
+    }
+    active = cubes & 1u;
+    if (active) {
+      unsigned in8 = 0;
+#pragma unroll
+      for (unsigned v = 0; v < 8; ++v) in8 |= (imask & mesh_corner_bit(v)) ? 1u << v : 0u;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) ntri += (unsigned)tsdf_case_count(mesh_tetra_code(in8, k));
+    }
+  }
+  unsigned vtot = 0, ttot = 0;
+  const unsigned vloc = mesh_block_scan<4>((unsigned)__popc(mask), s_w, &vtot);
+  const unsigned tloc = mesh_block_scan<4>(ntri, s_w, &ttot);
+  if (c < a.cells) a.words[c] = mask | (active ? MESH_ACTIVE : 0u) | (vloc << 8) | (tloc << 19);
+  if (threadIdx.x == 0) a.totals[blockIdx.x] = make_uint2(vtot, ttot);
+  const unsigned na = (unsigned)__popcll(__ballot(active != 0u));
+  if ((threadIdx.x & 63) == 0 && na) atomicAdd(&a.info[MI_ACTIVE], (u64)na);
+}
+
+// One block: the exclusive prefix sums of the blocks' totals in place, 1024 at a time behind a running carry, and the two sums
+// (at most 7 * 2^27 vertices and 12 * 2^27 triangles: they fit 32 bits) into the counter line.
+__global__ void __launch_bounds__(1024) k_mesh_scan(const MeshK a) {
+  __shared__ unsigned s_w[16];
+  unsigned vcarry = 0, tcarry = 0;
+  for (unsigned base = 0; base < a.blocks; base += 1024u) {
+    const unsigned i = base + threadIdx.x;
+    const uint2 t = i < a.blocks ? a.totals[i] : make_uint2(0u, 0u);
+    unsigned vtot = 0, ttot = 0;
+    const unsigned vex = mesh_block_scan<16>(t.x, s_w, &vtot);
+    const unsigned tex = mesh_block_scan<16>(t.y, s_w, &ttot);
+    if (i < a.blocks) a.totals[i] = make_uint2(vcarry + vex, tcarry + tex);
+    vcarry += vtot;
+    tcarry += ttot;
+  }
+  if (threadIdx.x == 0) { a.info[MI_VERTICES] = (u64)vcarry; a.info[MI_TRIANGLES] = (u64)tcarry; }
+}
+
+// One thread per cell: the vertices of the cell's edges, in the order of their types, at the cell's place in the list.
+__global__ void __launch_bounds__(256) k_mesh_vertices(const MeshK a) {
+  const unsigned c = blockIdx.x * 256u + threadIdx.x;
+  if (c >= a.cells) return;
+  const unsigned w = a.words[c], mask = w & 0x7fu;
+  if (!mask) return;
+  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
+  const unsigned line = c / nz, iz = c - line * nz, ix = line / ny, iy = line - ix * ny;
+  size_t at = (size_t)a.totals[blockIdx.x].x + MESH_VLOCAL(w);
+  const int2 lo = a.tsdf[c];
+#pragma unroll
+  for (unsigned t = 0; t < 7; ++t) {
+    if (!((mask >> t) & 1u)) continue;
+    const unsigned d = t + 1u;  // the edge's end: inside the box, since an active cube holds the edge
+    const int2 hi = a.tsdf[(size_t)c + ((d & 1u) ? (size_t)ny * nz : 0) + ((d & 2u) ? nz : 0u) + ((d & 4u) ? 1u : 0u)];
+    const float al = tsdf_edge_alpha(lo.x, (unsigned)lo.y, hi.x, (unsigned)hi.y);
+    float* out = a.vertices + 3 * at;
+    out[0] = tsdf_vertex_axis(a.box.lo[0], (int)ix, (d & 1u) != 0, al, a.voxel);
+    out[1] = tsdf_vertex_axis(a.box.lo[1], (int)iy, (d & 2u) != 0, al, a.voxel);
+    out[2] = tsdf_vertex_axis(a.box.lo[2], (int)iz, (d & 4u) != 0, al, a.voxel);
+    ++at;
+  }
+}
+
+// the corner number of v_i of the tetrahedron whose v1, v2 are packed in v12
+__device__ __forceinline__ unsigned mesh_corner(unsigned v12, unsigned i) { return i == 0u ? 0u : i == 1u ? (v12 & 7u) : i == 2u ? (v12 >> 4) : 7u; }
+// The index of the vertex on the edge between the corners lo and hi (lo's bits among hi's) of the cube at the cell c: the base of
+// lo's cell and the edges of lower type that carry a vertex there.
+__device__ __forceinline__ unsigned mesh_vertex_index(const MeshK& a, unsigned c, unsigned lo, unsigned hi) {
+  const unsigned nz = (unsigned)a.box.n[2], nyz = (unsigned)a.box.n[1] * nz;
+  const unsigned e = c + ((lo & 1u) ? nyz : 0u) + ((lo & 2u) ? nz : 0u) + ((lo & 4u) ? 1u : 0u);
+  const unsigned w = a.words[e];
+  return a.totals[e >> 8].x + MESH_VLOCAL(w) + (unsigned)__popc(w & 0x7fu & ((1u << tsdf_edge_type(lo, hi)) - 1u));
+}
+
+// One thread per cell: the triangles of the cell's cube when it is active, tetrahedron by tetrahedron, at the cube's place in the
+// list.  A vertex index is looked up from the word and the block's base of the cell at the edge's lower end.
+__global__ void __launch_bounds__(256) k_mesh_triangles(const MeshK a) {
+  const unsigned c = blockIdx.x * 256u + threadIdx.x;
+  if (c >= a.cells) return;
+  const unsigned w = a.words[c];
+  if (!(w & MESH_ACTIVE)) return;
+  const unsigned nz = (unsigned)a.box.n[2], nyz = (unsigned)a.box.n[1] * nz;
+  unsigned in8 = 0;
+#pragma unroll
+  for (unsigned v = 0; v < 8; ++v)  // an active cube's corners are inside the box
+    in8 |= (a.flags[(size_t)c + ((v & 1u) ? nyz : 0u) + ((v & 2u) ? nz : 0u) + ((v & 4u) ? 1u : 0u)] & 2u) ? 1u << v : 0u;
+  if (in8 == 0u || in8 == 0xffu) return;
+  size_t at = (size_t)a.totals[blockIdx.x].y + MESH_TLOCAL(w);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const unsigned code = mesh_tetra_code(in8, k), v12 = tsdf_tetra_v12(k);
+    const int cnt = tsdf_case_count(code);
+    const bool swap = (tsdf_swap_word(k) >> code) & 1u;
+    for (int j = 0; j < cnt; ++j) {
+      const unsigned tri = tsdf_case_triangle(code, j);
+      unsigned idx0 = 0, idx1 = 0, idx2 = 0;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const unsigned e = (tri >> (4 * q)) & 15u;
+        const unsigned id = mesh_vertex_index(a, c, mesh_corner(v12, e & 3u), mesh_corner(v12, e >> 2));
+        if (q == 0) idx0 = id; else if (q == 1) idx1 = id; else idx2 = id;
+      }
+      unsigned* out = a.triangles + 3 * at;
+      out[0] = idx0;
+      out[1] = swap ? idx2 : idx1;
+      out[2] = swap ? idx1 : idx2;
+      ++at;
+    }
+  }
+}
+
+extern "C" int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, int device_tsdf, uint32_t min_weight,
+                                  float* vertices, size_t cap_vertices, uint32_t* triangles, size_t cap_triangles, size_t* n_vertices,
+                                  size_t* n_triangles, int device_out, revo_map_mesh_info* info) {
+  if (!m || !box || !tsdf || !n_vertices || !n_triangles) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  size_t cells = 0;
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_tsdf_mesh: ") + why);
+  TRY(map_check_side(device_tsdf, "device_tsdf"));
+  TRY(map_check_side(device_out, "device_out"));
+  if (device_tsdf) TRY(map_check_aligned((uintptr_t)tsdf, 16, "the device volume is"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)vertices | (uintptr_t)triangles, 16, "a device output is"));
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  const size_t vol_bytes = sizeof(revo_map_tsdf_cell) * cells, blocks = (cells + 255) / 256;
+  // the scratch: counter line | totals | words | flags
+  const size_t off_totals = 256, off_words = off_totals + ((sizeof(uint2) * blocks + 255) & ~(size_t)255);
+  const size_t off_flags = off_words + ((sizeof(unsigned) * cells + 255) & ~(size_t)255);
+  TRY(m->meshwork.reserve(off_flags + cells, s));
+  TRY(m->tsdfvol.reserve(device_tsdf ? 0 : vol_bytes, s));
+  if (!device_tsdf) HIPCHECK(hipMemcpyAsync(m->tsdfvol.p, tsdf, vol_bytes, hipMemcpyHostToDevice, s));
+  MeshK a{};
+  a.tsdf = device_tsdf ? (const int2*)tsdf : (const int2*)m->tsdfvol.p;
+  a.box = *box;
+  a.cells = (unsigned)cells; a.min_weight = min_weight; a.blocks = (unsigned)blocks;
+  a.voxel = m->voxel;
+  a.info = (u64*)m->meshwork.p;
+  a.totals = (uint2*)(m->meshwork.p + off_totals);
+  a.words = (unsigned*)(m->meshwork.p + off_words);
+  a.flags = (uint8_t*)(m->meshwork.p + off_flags);
+  const dim3 grid((unsigned)blocks);
+  HIPCHECK(hipMemsetAsync(a.info, 0, 64, s));
+  hipLaunchKernelGGL(k_mesh_flags, grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_mesh_count, grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, s, a);
+  HIPCHECK(hipGetLastError());
+  u64 line[8];
+  HIPCHECK(hipMemcpyAsync(line, a.info, sizeof(line), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  line[MI_CELLS] = cells;
+  line[MI_CUBES] = (u64)(box->n[0] - 1) * (u64)(box->n[1] - 1) * (u64)(box->n[2] - 1);
+  line[7] = 0;
+  const size_t nv = (size_t)line[MI_VERTICES], nt = (size_t)line[MI_TRIANGLES];
+  *n_vertices = nv;
+  *n_triangles = nt;
+  if (info) memcpy(info, line, sizeof(line));
+  if (!vertices && !triangles) return REVO_OK;
+  if ((vertices && cap_vertices < nv) || (triangles && cap_triangles < nt))
+    return fail(REVO_ERR_CAPACITY, "tsdf mesh: an output holds fewer vertices or triangles than the mesh has");
+  const size_t vbytes = (12 * nv + 255) & ~(size_t)255;
+  if (!device_out) TRY(m->meshout.reserve(vbytes + 12 * nt, s));
+  a.vertices = device_out ? vertices : (float*)m->meshout.p;
+  a.triangles = device_out ? triangles : (unsigned*)(m->meshout.p + vbytes);
+  if (vertices && nv) {
+    hipLaunchKernelGGL(k_mesh_vertices, grid, dim3(256), 0, s, a);
+    if (!device_out) HIPCHECK(hipMemcpyAsync(vertices, a.vertices, 12 * nv, hipMemcpyDeviceToHost, s));
+  }
+  if (triangles && nt) {
+    hipLaunchKernelGGL(k_mesh_triangles, grid, dim3(256), 0, s, a);
+    if (!device_out) HIPCHECK(hipMemcpyAsync(triangles, a.triangles, 12 * nt, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));
+  return REVO_OK;
+}

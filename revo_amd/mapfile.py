@@ -47,6 +47,13 @@ Equal maps give equal files.
                                                         [--headings N] [--stride N] [--max-candidates N] [--weight W] [--up X Y Z]
                                                         [the options of gain] -o POSE.txt
                                                         the reachable pose that would reveal most per metre of the way there
+    python -m revo_amd.mapfile tsdf A --views DIR [--trunc M] [--pad N] -o TSDF.npz
+                                                        [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S]
+                                                        the views of DIR fused into a truncated signed distance volume over A's
+                                                        bounds grown by N cells (revo_map_tsdf_fuse, DESIGN 26), without a GPU;
+                                                        TSDF.npz holds sum, weight, lo, n, voxel, trunc
+    python -m revo_amd.mapfile mesh TSDF.npz [--min-weight K] -o MESH.ply
+                                                        the mesh of the volume's zero level set (revo_map_tsdf_mesh), binary PLY
     python -m revo_amd.mapfile df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt
                                                         map SRC's points registered against map DST's distance field
                                                         (revo_map_df_align), without a GPU: the pose SRC's frame ->
@@ -305,9 +312,10 @@ def carve_view(depth, T_w_c, intrinsics):
     return D, Rc, tc, k
 
 
-def carve_classes(p, view, radius, margin, margin_rel):
+def carve_classes(p, view, radius, margin, margin_rel, depths=False):
     """The class (index into CARVE_CLASSES) of every point p [N, 3] float32 in one checked view (carve_view): revo_map_carve's
-    rule (include/revo_hip.h), float32 operation by operation."""
+    rule (include/revo_hip.h), float32 operation by operation.  depths: -> (class, z, dc), the camera-space depth of
+    every point and the centre pixel's depth (NaN where the class is outside) the classes were decided on."""
     D, Rc, tc, k = view
     f32 = np.float32
     fx, fy, cx, cy, zmin, zmax = (f32(x) for x in k)
@@ -325,6 +333,7 @@ def carve_classes(p, view, radius, margin, margin_rel):
         iv = np.floor(np.where(ok, v, f32(0)) + f32(0.5)).astype(np.int64)
         ok &= (iu - r >= 0) & (iu + r <= w - 1) & (iv - r >= 0) & (iv + r <= h - 1)
         j = np.nonzero(ok)[0]
+        z_all = z
         iu, iv, z = iu[j], iv[j], z[j]
         usable = np.ones(len(j), bool)
         dmin = np.full(len(j), np.inf, f32)
@@ -339,6 +348,10 @@ def carve_classes(p, view, radius, margin, margin_rel):
         c = np.where(z < dmin - (margin + margin_rel * dmin), 2,
                      np.where(np.abs(z - dc) <= mc, 3, np.where(z > dc + mc, 4, 5)))
     cls[j] = np.where(usable, c, 1)
+    if depths:
+        dc_all = np.full(len(p), np.nan, f32)
+        dc_all[j] = dc
+        return cls, z_all.astype(f32), dc_all
     return cls
 
 
@@ -1040,6 +1053,219 @@ def observe_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, **p
         seen, part, _ = observe_records(header["voxel"], lo, n, views[i:i + 64], seen=seen, **params)
         info = part if info is None else dict(part, votes=info["votes"] + part["votes"], newly_known=info["newly_known"] + part["newly_known"])
     return seen, lo.astype(np.int32), header["voxel"], info
+
+
+TSDF_CELL_DTYPE = np.dtype([("sum", "<i4"), ("weight", "<u4")])  # revo_map_tsdf_cell
+TSDF_INFO_KEYS = ("cells", "updates", "cells_weighted", "cells_inside", "saturated")
+MESH_INFO_KEYS = ("cells", "valid", "inside", "cubes", "cubes_active", "vertices", "triangles")
+TSDF_W_MAX = 1 << 20
+# the Kuhn tetrahedra of a cube: the corner numbers (dx + 2 dy + 4 dz) of v0 .. v3, per permutation of (x, y, z) in lexicographic order
+TSDF_TETRA = ((0, 1, 3, 7), (0, 1, 5, 7), (0, 2, 3, 7), (0, 2, 6, 7), (0, 4, 5, 7), (0, 4, 6, 7))
+# bit `case` (bit i of the case: v_i inside): the case's triangles are listed with their last two vertices swapped
+TSDF_SWAP = (0x4D24, 0x32DA, 0x32DA, 0x4D24, 0x4D24, 0x32DA)
+
+
+def tsdf_trunc(voxel, trunc=None):
+    """The truncation distance a fuse runs with, checked as revo_map_tsdf_fuse checks it (None: 4 x the voxel edge) -> float32."""
+    t = np.float32(4.0) * np.float32(voxel) if trunc is None else np.float32(trunc)
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError("trunc must be finite and > 0")
+    return t
+
+
+def _tsdf_volume(cells, n=None):
+    cells = np.asarray(cells)
+    if cells.dtype != TSDF_CELL_DTYPE or cells.ndim != 3 or (n is not None and cells.shape != tuple(int(x) for x in n)):
+        raise ValueError("a TSDF volume is a 3-D array of (sum int32, weight uint32) cells of the box's shape")
+    return cells
+
+
+def tsdf_records(voxel, lo, n, views, trunc=None, tsdf=None, chunk=1 << 20):
+    """The TSDF volume without a GPU: revo_map_tsdf_fuse's contract in vectorised numpy, through carve_classes at
+    radius 0 with margin = trunc.  views: as carve_records takes them; tsdf: a volume to accumulate into (it is not changed),
+    None for a fresh one.  -> (cells TSDF_CELL_DTYPE [n0, n1, n2], info dict of TSDF_INFO_KEYS, one dict of CARVE_CLASSES counts
+    per view).  ValueError as the library's REVO_ERR_INVALID_ARG."""
+    lo, n = check_box(lo, n)
+    trunc = tsdf_trunc(voxel, trunc)
+    views, _, _, _ = carve_rule_args(voxel, views, 0, trunc, 0.0)
+    shape = tuple(int(x) for x in n)
+    before = np.zeros(shape, TSDF_CELL_DTYPE) if tsdf is None else _tsdf_volume(tsdf, n)
+    p = seen_centres(lo, n, voxel)
+    s = before["sum"].reshape(-1).astype(np.int64)
+    w = before["weight"].reshape(-1).astype(np.int64)
+    counts = [dict.fromkeys(CARVE_CLASSES, 0) for _ in views]
+    updates = saturated = 0
+    for a in range(0, len(p), int(chunk)):
+        sl = slice(a, a + int(chunk))
+        for vw, cnt in zip(views, counts):  # in their order: a full weight drops the later ones
+            cls, z, dc = carve_classes(p[sl], vw, 0, trunc, np.float32(0), depths=True)
+            with np.errstate(all="ignore"):
+                q = np.rint(((dc - z) / trunc) * np.float32(1024))
+            q = np.where(cls == 2, 1024, np.where(cls == 3, q, 0)).astype(np.int64)
+            hit = (cls == 2) | (cls == 3)
+            full = w[sl] >= TSDF_W_MAX
+            take = hit & ~full
+            s[sl] += np.where(take, q, 0)
+            w[sl] += take
+            updates += int(take.sum())
+            saturated += int((hit & full).sum())
+            for i, name in enumerate(CARVE_CLASSES):
+                cnt[name] += int((cls == i).sum())
+    out = np.zeros(shape, TSDF_CELL_DTYPE)
+    out["sum"], out["weight"] = s.reshape(shape), w.reshape(shape)
+    info = {"cells": int(out.size), "updates": updates, "cells_weighted": int((w > 0).sum()), "cells_inside": int(((w > 0) & (s < 0)).sum()),
+            "saturated": saturated}
+    return out, info, counts
+
+
+def tsdf_sdf(cells, trunc):
+    """The signed distance in metres, float64 [n0, n1, n2]: sum / weight * trunc / 1024, NaN where the weight is 0."""
+    cells = _tsdf_volume(cells)
+    with np.errstate(all="ignore"):
+        return np.where(cells["weight"] > 0, cells["sum"].astype(np.float64) / cells["weight"] * float(np.float32(trunc)) / 1024.0, np.nan)
+
+
+class Mesh:
+    """A triangle mesh (revo_map_tsdf_mesh, mesh_records): vertices [V, 3] float32 metres, triangles [T, 3] uint32 vertex
+    indices, both in the contract's canonical order; info: the call's counts (MESH_INFO_KEYS), None for a loaded mesh."""
+
+    def __init__(self, vertices, triangles, info=None):
+        self.vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
+        self.triangles = np.asarray(triangles, np.uint32).reshape(-1, 3)
+        self.info = info
+
+    def save_ply(self, path):
+        from . import ply
+        return ply.write_mesh_ply(path, self.vertices, self.triangles)
+
+    @classmethod
+    def load_ply(cls, path):
+        from . import ply
+        return cls(*ply.read_mesh_ply(path))
+
+
+def _tsdf_case_triangles(case):
+    """The triangles of a case (bit i: v_i inside) as edges (i, j), i < j, before the swap."""
+    ins = [i for i in range(4) if (case >> i) & 1]
+    out = [i for i in range(4) if not (case >> i) & 1]
+    e = lambda a, b: (min(a, b), max(a, b))  # noqa: E731
+    if len(ins) in (0, 4):
+        return []
+    if len(ins) in (1, 3):
+        a = ins[0] if len(ins) == 1 else out[0]
+        b, c, d = [i for i in range(4) if i != a]
+        return [(e(a, b), e(a, c), e(a, d))]
+    (a, b), (c, d) = ins, out
+    return [(e(a, c), e(a, d), e(b, d)), (e(a, c), e(b, d), e(b, c))]
+
+
+def mesh_records(cells, lo, voxel, min_weight=1):
+    """The mesh of a TSDF volume without a GPU: revo_map_tsdf_mesh's contract in vectorised numpy -> Mesh."""
+    cells = _tsdf_volume(cells)
+    n = np.asarray(cells.shape, np.int64)
+    lo, _ = check_box(lo, n)
+    f32 = np.float32
+    voxel = f32(voxel)
+    mw = max(1, int(min_weight))
+    s, w = cells["sum"].astype(np.int64), cells["weight"].astype(np.int64)
+    valid = w >= mw
+    inside = valid & (s < 0)
+    info = dict.fromkeys(MESH_INFO_KEYS, 0)
+    info.update(cells=int(cells.size), valid=int(valid.sum()), inside=int(inside.sum()), cubes=int(np.prod(n - 1)))
+    off = lambda v: (v & 1, (v >> 1) & 1, (v >> 2) & 1)  # noqa: E731
+
+    def shifted(a, d, fill=False):
+        """a[c + d] where that is inside the box, `fill` elsewhere (d: an offset of -1 .. 1 per axis)."""
+        out = np.full(a.shape, fill, a.dtype)
+        src = tuple(slice(max(0, d[i]), a.shape[i] + min(0, d[i])) for i in range(3))
+        dst = tuple(slice(max(0, -d[i]), a.shape[i] + min(0, -d[i])) for i in range(3))
+        out[dst] = a[src]
+        return out
+
+    active = np.ones(cells.shape, bool)
+    for v in range(8):
+        active &= shifted(valid, off(v))
+    info["cubes_active"] = int(active.sum())
+    # the edges that carry a vertex: bit per type, in the order (cell, type)
+    carries = np.zeros(cells.shape + (7,), bool)
+    for t in range(7):
+        d = t + 1
+        owner = np.zeros(cells.shape, bool)
+        for o in range(8):
+            if not (o & d):
+                owner |= shifted(active, tuple(-x for x in off(o)))
+        carries[..., t] = (inside != shifted(inside, off(d))) & owner
+    flat = carries.reshape(-1, 7)
+    cell_i, type_i = np.nonzero(flat)
+    index = np.cumsum(flat.reshape(-1)).reshape(-1, 7) - 1  # the vertex of (cell, type), where it has one
+    ix, iy, iz = np.unravel_index(cell_i, cells.shape)
+    d = type_i + 1
+    dx, dy, dz = d & 1, (d >> 1) & 1, (d >> 2) & 1
+    n0 = s[ix, iy, iz] * w[ix + dx, iy + dy, iz + dz]
+    n1 = s[ix + dx, iy + dy, iz + dz] * w[ix, iy, iz]
+    a = (n0.astype(np.float64) / (n0 - n1).astype(np.float64)).astype(f32)
+    vertices = np.empty((len(cell_i), 3), f32)
+    for axis, (c, along) in enumerate(((ix, dx), (iy, dy), (iz, dz))):
+        vertices[:, axis] = (((int(lo[axis]) + c).astype(f32) + f32(0.5)) + np.where(along == 1, a, f32(0))) * voxel
+    # the triangles: per active cube (ascending place), tetrahedron and k
+    cubes = np.nonzero(active.reshape(-1))[0]
+    cx, cy, cz = np.unravel_index(cubes, cells.shape)
+    place = lambda v: ((cx + off(v)[0]) * int(n[1]) + cy + off(v)[1]) * int(n[2]) + cz + off(v)[2]  # noqa: E731
+    tri = np.zeros((len(cubes), 6, 2, 3), np.int64)
+    have = np.zeros((len(cubes), 6, 2), bool)
+    corner_in = [inside.reshape(-1)[place(v)] for v in range(8)]
+    for k, tc in enumerate(TSDF_TETRA):
+        case = sum(corner_in[tc[i]].astype(np.int64) << i for i in range(4))
+        for code in range(1, 15):
+            sel = np.nonzero(case == code)[0]
+            if not len(sel):
+                continue
+            for j, t3 in enumerate(_tsdf_case_triangles(code)):
+                if (TSDF_SWAP[k] >> code) & 1:
+                    t3 = (t3[0], t3[2], t3[1])
+                for q, (i0, i1) in enumerate(t3):
+                    tri[sel, k, j, q] = index[place(tc[i0])[sel], (tc[i0] ^ tc[i1]) - 1]
+                have[sel, k, j] = True
+    triangles = tri[have].astype(np.uint32).reshape(-1, 3)
+    info["vertices"], info["triangles"] = len(vertices), len(triangles)
+    return Mesh(vertices, triangles, info)
+
+
+def write_tsdf(path, cells, lo, voxel, trunc):
+    """The .npz of a TSDF volume: sum (int32 [n0, n1, n2]), weight (uint32), lo, n (int32 [3]), voxel, trunc (float32)."""
+    cells = _tsdf_volume(cells)
+    with open(path, "wb") as f:
+        np.savez(f, sum=np.ascontiguousarray(cells["sum"]), weight=np.ascontiguousarray(cells["weight"]), lo=np.asarray(lo, np.int32).reshape(3),
+                 n=np.asarray(cells.shape, np.int32), voxel=np.float32(voxel), trunc=np.float32(trunc))
+    return path
+
+
+def read_tsdf(path):
+    """(cells, lo, voxel, trunc) of a file write_tsdf wrote; ValueError if its arrays do not fit together."""
+    with np.load(path) as z:
+        if not all(k in z.files for k in ("sum", "weight", "lo", "n", "voxel", "trunc")):
+            raise ValueError("%s is not a TSDF file (sum, weight, lo, n, voxel, trunc)" % path)
+        s, w, lo, n, voxel, trunc = (z[k] for k in ("sum", "weight", "lo", "n", "voxel", "trunc"))
+    if s.dtype != np.int32 or w.dtype != np.uint32 or s.ndim != 3 or s.shape != w.shape or lo.shape != (3,) or list(s.shape) != [int(x) for x in n]:
+        raise ValueError("%s: a TSDF volume is an int32 sum and a uint32 weight of the shape its n states" % path)
+    check_box(lo, n)
+    cells = np.zeros(s.shape, TSDF_CELL_DTYPE)
+    cells["sum"], cells["weight"] = s, w
+    return cells, lo.astype(np.int32), float(np.float32(voxel)), float(tsdf_trunc(voxel, trunc))
+
+
+def tsdf_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, trunc=None):
+    """(cells, lo, voxel, trunc, info) of the views of a `run_tum --map-views` folder over the bounds of the file's map grown by
+    `pad` cells; more than 64 views accumulate in parts of 64."""
+    header, rec = read(path)
+    views = read_views(views_dir, camera, zrange, depth_scale)
+    lo, hi, _ = bounds_records(rec)
+    lo, n = padded_box(lo, hi, pad)
+    cells, info = None, None
+    for i in range(0, len(views), 64):
+        cells, part, _ = tsdf_records(header["voxel"], lo, n, views[i:i + 64], trunc, tsdf=cells)
+        info = part if info is None else dict(part, updates=info["updates"] + part["updates"], saturated=info["saturated"] + part["saturated"])
+    return cells, lo.astype(np.int32), header["voxel"], float(tsdf_trunc(header["voxel"], trunc)), info
 
 
 def df_sample(d2, lo, voxel, points):
@@ -1797,6 +2023,33 @@ def main(argv=None):
                       % (val["-o"][0], len(r["poses"]), len(r["cells"]), r["cell"].tolist(), r["heading"], int(r["record"]["unknown_free"]),
                          r["scores"][r["index"]], len(r["path"][0])))
                 return 0
+        if cmd in ("tsdf", "mesh") and "-o" in args:
+            opt = {"-o": 1, "--views": 1, "--pad": 1, "--trunc": 1, "--camera": 4, "--zrange": 2, "--depth-scale": 1, "--min-weight": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if cmd == "tsdf" and len(pos) == 1 and "--views" in val:
+                camera = [float(x) for x in val.get("--camera", (525.0, 525.0, 319.5, 239.5))]  # the TUM default camera
+                zrange = [float(x) for x in val.get("--zrange", (0.1, 5.2))]
+                cells, lo, voxel, trunc, info = tsdf_file(pos[0], val["--views"][0], camera, zrange, float(val.get("--depth-scale", [5000.0])[0]),
+                                                          int(val.get("--pad", [0])[0]), float(val["--trunc"][0]) if "--trunc" in val else None)
+                write_tsdf(val["-o"][0], cells, lo, voxel, trunc)
+                print("%s: %d x %d x %d cells from %s (the views of %s over %s), trunc %g m: %d with a weight, %d inside"
+                      % ((val["-o"][0],) + cells.shape + (lo.tolist(), val["--views"][0], pos[0], trunc, info["cells_weighted"], info["cells_inside"])))
+                return 0
+            if cmd == "mesh" and len(pos) == 1:
+                cells, lo, voxel, _ = read_tsdf(pos[0])
+                m = mesh_records(cells, lo, voxel, int(val.get("--min-weight", [1])[0]))
+                m.save_ply(val["-o"][0])
+                print("%s: %d vertices, %d triangles from %d active cubes of %s" % (val["-o"][0], len(m.vertices), len(m.triangles),
+                                                                                   m.info["cubes_active"], pos[0]))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -1819,6 +2072,8 @@ def main(argv=None):
           "[--min-views K] [--min-count N] [--miss-depth D] [--max-steps N] -o GAIN.txt | "
           "next-view A --seen SEEN.npz --start X Y Z --clearance M --camera FX FY CX CY --size W H [--headings N] [--stride N] [--max-candidates N] "
           "[--weight W] [--up X Y Z] [the options of gain] -o POSE.txt | "
+          "tsdf A --views DIR -o TSDF.npz [--trunc M] [--pad N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
+          "mesh TSDF.npz -o MESH.ply [--min-weight K] | "
           "ply FILE [OUT.ply]")
     return 2
 

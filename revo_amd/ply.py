@@ -159,6 +159,48 @@ def read_voxel_ply(path):
     return (np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["red"], v["green"], v["blue"]], 1), v["count"].copy())
 
 
+MESH_PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<u4", (3,))])  # 13 bytes per face, packed
+
+
+def mesh_ply_header(nv, nf):
+    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "element face %d\nproperty list uchar uint vertex_indices\nend_header\n" % (nv, nf)).encode("ascii")
+
+
+def write_mesh_ply(path, vertices, triangles):
+    """A triangle mesh (mapfile.Mesh) as binary little-endian PLY: `vertex` elements x y z float32 and `face` elements, each a
+    list of three uint32 vertex indices, both in the order given."""
+    v = np.ascontiguousarray(np.asarray(vertices, "<f4").reshape(-1, 3))
+    t = np.asarray(triangles, np.uint32).reshape(-1, 3)
+    if len(t) and int(t.max()) >= len(v):
+        raise ValueError("a triangle names a vertex the mesh does not have")
+    f = np.empty(len(t), MESH_PLY_FACE_DTYPE)
+    f["n"], f["v"] = 3, t
+    with open(path, "wb") as out:
+        out.write(mesh_ply_header(len(v), len(t)))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+    return path
+
+
+def read_mesh_ply(path):
+    """Reader for write_mesh_ply's files -> (vertices V x 3 float32, triangles T x 3 uint32)."""
+    data = open(path, "rb").read()
+    if b"end_header\n" not in data:
+        raise ValueError("not a mesh PLY")
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    count = {l.split()[1]: int(l.split()[2]) for l in data[:end].decode("ascii", "replace").split("\n") if l.startswith("element ")}
+    nv, nf = count.get("vertex", 0), count.get("face", 0)
+    if data[:end] != mesh_ply_header(nv, nf) or len(data) != end + 12 * nv + 13 * nf:
+        raise ValueError("not a mesh PLY")
+    v = np.frombuffer(data, "<f4", count=3 * nv, offset=end).reshape(nv, 3).copy()
+    f = np.frombuffer(data, MESH_PLY_FACE_DTYPE, count=nf, offset=end + 12 * nv)
+    if nf and not np.all(f["n"] == 3):
+        raise ValueError("not a triangle mesh")
+    return v, f["v"].astype(np.uint32).reshape(nf, 3)
+
+
 def read_ply_vertices(path):
     """Minimal reader for the files above (tests): -> (V x 6 float array, list of edge tuples)."""
     with open(path) as f:

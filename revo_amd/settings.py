@@ -380,6 +380,29 @@ class MapGainInfo(C.Structure):
 assert (C.sizeof(MapGainParams), C.sizeof(MapGain), C.sizeof(MapGainInfo)) == (32, 32, 64)
 
 
+class MapTsdfCell(C.Structure):
+    """revo_map_tsdf_cell (include/revo_hip.h), 8 bytes: the integer sum of a cell's truncated distances and its updates."""
+    _fields_ = [("sum", C.c_int32), ("weight", C.c_uint32)]
+
+
+class MapTsdfParams(C.Structure):
+    """revo_map_tsdf_params (include/revo_hip.h), 16 bytes: the truncation distance in metres and whether the call accumulates."""
+    _fields_ = [("trunc", C.c_float), ("accumulate", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class MapTsdfInfo(C.Structure):
+    """revo_map_tsdf_info (include/revo_hip.h), 64 bytes: integer sums of a fuse call."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "updates", "cells_weighted", "cells_inside", "saturated")] + [("reserved", C.c_uint64 * 3)]
+
+
+class MapMeshInfo(C.Structure):
+    """revo_map_mesh_info (include/revo_hip.h), 64 bytes: the counts of a mesh call."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "valid", "inside", "cubes", "cubes_active", "vertices", "triangles", "reserved")]
+
+
+assert (C.sizeof(MapTsdfCell), C.sizeof(MapTsdfParams), C.sizeof(MapTsdfInfo), C.sizeof(MapMeshInfo)) == (8, 16, 64, 64)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [
