@@ -1561,6 +1561,59 @@ int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const revo_map_t
                        float* vertices, size_t cap_vertices, uint32_t* triangles, size_t cap_triangles, size_t* n_vertices,
                        size_t* n_triangles, int device_out, revo_map_mesh_info* info);
 
+/* ---- colour and normals on the surface ---------------------------------------------------------------------
+ * The colour volume: one 16-byte cell per cell of the TSDF volume's box, with its layout and alignment rules (z fastest, the
+ * same place per cell).  A view's colour image is h x w x 3 bytes, B, G, R, rows packed; for a pyramid view it is the
+ * pyramid's level-0 BGR plane.  For a cell and a view a colour update takes place exactly when the cell's TSDF update takes
+ * place (the TSDF weight was below 2^20, so the update was not dropped) and the class is CONFIRMED:
+ *   sum_c += BGR[iv, iu][c] for c = B, G, R;  weight += 1,   (iu, iv) the centre pixel the class rule computed.
+ * FREE updates the TSDF cell only.  So color.weight <= tsdf.weight <= 2^20, every sum_c <= 255 * 2^20, nothing overflows.
+ * Exact properties: the tsdf bytes, info and view_info equal revo_map_tsdf_fuse's on the same arguments; while nothing
+ * saturates the order of the views cannot show in either volume; views A and then an accumulating call with views B leave the
+ * bytes of one call with A and B, in both volumes; a call that does not accumulate reads neither volume; for volumes fused
+ * only through this entry point color.weight > 0 holds in every cell with tsdf.sum < 0 (a negative sum needs a CONFIRMED
+ * update). */
+typedef struct revo_map_tsdf_color {       /* 16 bytes */
+  uint32_t sum_b, sum_g, sum_r;  /* the sums of the centre pixels' bytes over the cell's colour updates   */
+  uint32_t weight;               /* the colour updates, at most the TSDF cell's weight                    */
+} revo_map_tsdf_color;
+typedef struct revo_map_tsdf_color_info {  /* 32 bytes, little-endian, no padding */
+  uint64_t color_updates;   /* the colour updates of this call                              */
+  uint64_t cells_colored;   /* cells with color.weight > 0 after the call                   */
+  uint64_t reserved[2];     /* zero */
+} revo_map_tsdf_color_info;
+/* revo_map_tsdf_fuse with the colour volume fused in the same pass.  bgr: n pointers (a host array); bgr[i] is NULL for a
+ * pyramid view and the colour image of a raw view, on the side of the depth images (device_in).  color and color_info live where
+ * tsdf and info live (device_tsdf); color_info may be NULL.  Every other rule is revo_map_tsdf_fuse's: everything is checked
+ * before anything is enqueued, host images (depth and colour) are uploaded to one temporary buffer, the call only enqueues when
+ * everything is on the device, device pointers are 16-byte aligned.
+ * REVO_ERR_INVALID_ARG, with nothing written, as revo_map_tsdf_fuse and also for a NULL bgr or color and a bgr[i] that does not
+ * match its view's kind. */
+int revo_map_tsdf_fuse_color(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views,
+                             const uint8_t* const* bgr, int device_in, const revo_map_tsdf_params* prm,
+                             revo_map_tsdf_cell* tsdf, revo_map_tsdf_color* color, int device_tsdf,
+                             revo_map_tsdf_info* info, revo_map_tsdf_color_info* color_info,
+                             revo_map_carve_view_info* view_info);
+
+/* revo_map_tsdf_mesh with two arrays per vertex, each a pure function of the two volumes' bytes, the box, the voxel edge and
+ * min_weight.  Vertices and triangles are byte for byte revo_map_tsdf_mesh's, in its order; the counting, capacity and NULL
+ * rules are its rules (normals and colors hold cap_vertices entries; each may be NULL and is then not written; all four
+ * outputs NULL: count only).  color may be NULL when colors is NULL; colors != NULL with color == NULL is an argument error.
+ * The vertex sits on the edge from the cell c0 to c1 with the parameter a.  Every float32 operation is rounded on its own.
+ * Normal (3 floats): f(c) = (float)sum / (float)weight.  The gradient at a cell, per axis i, with VALID as the mesh defines it
+ * and a cell outside the box not valid: both c +- e_i valid: (f(c+e_i) - f(c-e_i)) * 0.5f; only c+e_i: f(c+e_i) - f(c); only
+ * c-e_i: f(c) - f(c-e_i); neither: 0.0f.  g_i = g0_i + a * (g1_i - g0_i); l2 = (g_x*g_x + g_y*g_y) + g_z*g_z;
+ * n_i = g_i / sqrtf(l2), square root and division correctly rounded; (0, 0, 0) when l2 is 0 or not finite.  The field is
+ * positive outside, so the normal points from inside to outside, as the triangles' normals do.
+ * Colour (4 bytes B, G, R, k): k is the number of the edge's end cells with color.weight > 0.  Per channel
+ * m(c) = (float)sum_c / (float)weight; k = 2: v = m0 + a * (m1 - m0); k = 1: the coloured end's m; k = 0: v = 0; the byte is
+ * (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 255.0f)). */
+int revo_map_tsdf_mesh_attr(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf,
+                            const revo_map_tsdf_color* color, int device_tsdf, uint32_t min_weight,
+                            float* vertices, float* normals, uint8_t* colors, size_t cap_vertices,
+                            uint32_t* triangles, size_t cap_triangles, size_t* n_vertices, size_t* n_triangles,
+                            int device_out, revo_map_mesh_info* info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

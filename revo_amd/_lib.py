@@ -185,6 +185,10 @@ def lib():
     L.revo_map_tsdf_fuse.argtypes = [vp, C.POINTER(MapDfBox), C.c_int, C.POINTER(MapCarveView), C.c_int, C.POINTER(MapTsdfParams), vp, C.c_int, vp, vp]
     L.revo_map_tsdf_mesh.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t),
                                      C.POINTER(C.c_size_t), C.c_int, vp]
+    L.revo_map_tsdf_fuse_color.argtypes = [vp, C.POINTER(MapDfBox), C.c_int, C.POINTER(MapCarveView), vp, C.c_int, C.POINTER(MapTsdfParams), vp, vp,
+                                           C.c_int, vp, vp, vp]
+    L.revo_map_tsdf_mesh_attr.argtypes = [vp, C.POINTER(MapDfBox), vp, vp, C.c_int, C.c_uint32, vp, vp, vp, C.c_size_t, vp, C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int, vp]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

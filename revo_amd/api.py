@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapMeshInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -961,91 +961,186 @@ class VoxelMap:
         cells = np.ascontiguousarray(vol.cells)
         return self._df_box(vol.lo, cells.shape, 0, 1), cells
 
-    def fuse(self, views, lo=None, n=None, pad=8, trunc=None, into=None):
+    def _color_views(self, views):
+        """The views of a colour fuse -> (_carve_views' three results, the bgr pointer array of revo_map_tsdf_fuse_color, what
+        keeps the colour images alive).  A raw view is (depth, T, intrinsics-or-None, bgr), a pyramid view brings its own."""
+        views = list(views)
+        for v in views:
+            if not isinstance(v[0], ImgPyramidRGBD) and (len(v) < 4 or v[3] is None):
+                raise ValueError("with color=True a raw view is (depth, T, intrinsics or None, bgr)")
+        cv, device_in, keep = self._carve_views([v[:3] for v in views])
+        ptrs, keep_c = (C.c_void_p * len(views))(), []
+        for i, v in enumerate(views):
+            if isinstance(v[0], ImgPyramidRGBD):
+                continue
+            im, shape = v[3], (int(cv[i].height), int(cv[i].width), 3)
+            if device_in:
+                if not (hasattr(im, "data_ptr") and im.is_cuda and im.is_contiguous() and str(im.dtype) == "torch.uint8" and tuple(im.shape) == shape):
+                    raise ValueError("the colour image of a device depth image is a contiguous [h, w, 3] uint8 device tensor")
+                import torch
+                torch.cuda.current_stream(im.device).synchronize()
+                ptrs[i] = im.data_ptr()
+            else:
+                if hasattr(im, "data_ptr"):
+                    raise ValueError("the colour image of a host depth image is a host array")
+                im = np.asarray(im)
+                if im.dtype != np.uint8 or im.shape != shape:
+                    raise ValueError("a colour image is an [h, w, 3] uint8 array of the depth image's size")
+                im = np.ascontiguousarray(im)
+                ptrs[i] = im.ctypes.data
+            keep_c.append(im)
+        return cv, device_in, keep, ptrs, keep_c
+
+    def fuse(self, views, lo=None, n=None, pad=8, trunc=None, into=None, color=False):
         """The views fused into a truncated signed distance volume -> TsdfVolume: per cell of a box of voxel indices the integer
         sum of the views' signed distances to the surface they measured, in units of trunc / 1024, and the number of views that
         gave one (revo_map_tsdf_fuse).  views: as carve_eval and observe take them; the class of a cell's centre in a
         view is carve_eval's at radius 0 with margin = trunc.  lo, n: the box (by default the map's bounds grown by `pad` cells).
         trunc: metres (default 4 voxel edges).  into: a TsdfVolume to accumulate into (it is not changed); its box and trunc are
-        the call's, so lo, n and trunc are not given.  The map's voxels play no part."""
+        the call's, so lo, n and trunc are not given.  The map's voxels play no part.
+        color: the colour volume is fused in the same pass (revo_map_tsdf_fuse_color): a raw view is (depth, T,
+        intrinsics or None, bgr) with bgr an [h, w, 3] uint8 array (a device tensor beside a device depth image), a pyramid view
+        brings its level-0 colour plane.  The result has .color and .color_info; `into` must then carry a colour volume, and
+        must not without color."""
         from . import mapfile
-        cv, device_in, keep = self._carve_views(views)
+        if into is not None and (into.color is not None) != bool(color):
+            raise ValueError("a volume with colour is accumulated into with color=True, one without it with color=False")
+        if color:
+            cv, device_in, keep, bgr, keep_c = self._color_views(views)
+        else:
+            cv, device_in, keep = self._carve_views(views)
         if into is not None:
             if trunc is not None and np.float32(trunc).tobytes() != np.float32(into.trunc).tobytes():
                 raise ValueError("a TSDF volume brings its own trunc")
             box, vol = self._tsdf_box(into, lo, n)
             vol, trunc = vol.copy(), into.trunc
+            col = np.ascontiguousarray(into.color).copy() if color else None
         else:
             box = self._df_box(lo, n, pad, 1)
             vol = np.empty(tuple(box.n), mapfile.TSDF_CELL_DTYPE)
+            col = np.empty(tuple(box.n), mapfile.TSDF_COLOR_DTYPE) if color else None
         trunc = float(mapfile.tsdf_trunc(self.voxel, trunc))
         prm = MapTsdfParams(trunc, 0 if into is None else 1)
-        info, vinfo = MapTsdfInfo(), (MapCarveViewInfo * len(cv))()
-        check(_lib.lib().revo_map_tsdf_fuse(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vol.ctypes.data_as(vp), 0, C.byref(info),
-                                            C.cast(vinfo, vp)))
+        info, vinfo, cinfo = MapTsdfInfo(), (MapCarveViewInfo * len(cv))(), MapTsdfColorInfo()
+        if color:
+            check(_lib.lib().revo_map_tsdf_fuse_color(self._h, C.byref(box), len(cv), cv, C.cast(bgr, vp), device_in, C.byref(prm),
+                                                      vol.ctypes.data_as(vp), col.ctypes.data_as(vp), 0, C.byref(info), C.byref(cinfo), C.cast(vinfo, vp)))
+            del keep_c
+        else:
+            check(_lib.lib().revo_map_tsdf_fuse(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vol.ctypes.data_as(vp), 0, C.byref(info),
+                                                C.cast(vinfo, vp)))
         del keep
         return TsdfVolume(vol, np.array(list(box.lo), np.int32), self.voxel, trunc, {k: int(getattr(info, k)) for k in mapfile.TSDF_INFO_KEYS},
-                          self._view_counts(vinfo), self)
+                          self._view_counts(vinfo), self, color=col,
+                          color_info={k: int(getattr(cinfo, k)) for k in mapfile.TSDF_COLOR_INFO_KEYS} if color else None)
 
-    def fuse_into(self, d_tsdf, views, lo, trunc=None, accumulate=False, d_info=None, d_view_info=None, wait=True):
+    def fuse_into(self, d_tsdf, views, lo, trunc=None, accumulate=False, d_info=None, d_view_info=None, wait=True, d_color=None, d_color_info=None):
         """fuse() into a torch device tensor: d_tsdf int32 [n0, n1, n2, 2] (sum, weight; the box's cells are its first three
         sizes), d_info None or 64 bytes (revo_map_tsdf_info), d_view_info None or 32 bytes per view; contiguous, 16-byte aligned,
         on the map's device.  accumulate: d_tsdf is read and updated.  With device or pyramid views the call is only enqueued on
-        the context's tracker stream: wait=False returns at once (sync() orders later reads)."""
+        the context's tracker stream: wait=False returns at once (sync() orders later reads).
+        d_color: int32 [n0, n1, n2, 4] (sum_b, sum_g, sum_r, weight) -- the colour volume is fused in the same pass, the views are
+        those of fuse(color=True); d_color_info: None or 32 bytes (revo_map_tsdf_color_info)."""
         from . import mapfile
-        cv, device_in, keep = self._carve_views(views)
+        if d_color is not None:
+            cv, device_in, keep, bgr, keep_c = self._color_views(views)
+        else:
+            if d_color_info is not None:
+                raise ValueError("d_color_info goes with d_color")
+            cv, device_in, keep = self._carve_views(views)
         if d_tsdf.dim() != 4 or d_tsdf.shape[3] != 2 or str(d_tsdf.dtype) != "torch.int32":
             raise ValueError("d_tsdf must be an int32 tensor [n0, n1, n2, 2]")
+        if d_color is not None and (tuple(d_color.shape) != tuple(d_tsdf.shape[:3]) + (4,) or str(d_color.dtype) != "torch.int32"):
+            raise ValueError("d_color must be an int32 tensor [n0, n1, n2, 4] over d_tsdf's box")
         box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
-        for t_, size in ((d_tsdf, None), (d_info, 64), (d_view_info, 32 * len(cv))):
+        for t_, size in ((d_tsdf, None), (d_info, 64), (d_view_info, 32 * len(cv)), (d_color, None), (d_color_info, 32)):
             if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
                 raise ValueError("output tensors must be contiguous device tensors")
             if t_ is not None and size is not None and t_.numel() * t_.element_size() != size:
-                raise ValueError("d_info needs 64 bytes and d_view_info 32 bytes per view")
+                raise ValueError("d_info needs 64 bytes, d_view_info 32 bytes per view and d_color_info 32 bytes")
         prm = MapTsdfParams(float(mapfile.tsdf_trunc(self.voxel, trunc)), 1 if accumulate else 0)
         import torch
         torch.cuda.current_stream(d_tsdf.device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
-        check(_lib.lib().revo_map_tsdf_fuse(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), vp(d_tsdf.data_ptr()), 1,
-                                            vp(d_info.data_ptr()) if d_info is not None else None,
-                                            vp(d_view_info.data_ptr()) if d_view_info is not None else None))
+        ptr = lambda t_: vp(t_.data_ptr()) if t_ is not None else None  # noqa: E731
+        if d_color is not None:
+            check(_lib.lib().revo_map_tsdf_fuse_color(self._h, C.byref(box), len(cv), cv, C.cast(bgr, vp), device_in, C.byref(prm), ptr(d_tsdf),
+                                                      ptr(d_color), 1, ptr(d_info), ptr(d_color_info), ptr(d_view_info)))
+        else:
+            check(_lib.lib().revo_map_tsdf_fuse(self._h, C.byref(box), len(cv), cv, device_in, C.byref(prm), ptr(d_tsdf), 1, ptr(d_info), ptr(d_view_info)))
         if wait:
             self.sync()
         del keep
 
-    def mesh(self, tsdf, min_weight=1):
+    def mesh(self, tsdf, min_weight=1, normals=False, colors=False):
         """The mesh of a TsdfVolume's zero level set -> mapfile.Mesh: vertices, triangles and the call's counts, in the contract's
-        canonical order (revo_map_tsdf_mesh).  A cell counts when its weight >= max(min_weight, 1)."""
+        canonical order (revo_map_tsdf_mesh).  A cell counts when its weight >= max(min_weight, 1).
+        normals, colors: the mesh carries per-vertex unit normals and B, G, R, k bytes (revo_map_tsdf_mesh_attr, DESIGN 27);
+        colours need a volume fused with color=True."""
         from . import mapfile
         box, cells = self._tsdf_box(tsdf)
         L, nv, nt, info = _lib.lib(), C.c_size_t(), C.c_size_t(), MapMeshInfo()
-        args = (self._h, C.byref(box), cells.ctypes.data_as(vp), 0, int(min_weight))
-        check(L.revo_map_tsdf_mesh(*args, None, 0, None, 0, C.byref(nv), C.byref(nt), 0, C.byref(info)))
+        if not (normals or colors):
+            args = (self._h, C.byref(box), cells.ctypes.data_as(vp), 0, int(min_weight))
+            check(L.revo_map_tsdf_mesh(*args, None, 0, None, 0, C.byref(nv), C.byref(nt), 0, C.byref(info)))
+            v, t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.uint32)
+            if nv.value or nt.value:
+                check(L.revo_map_tsdf_mesh(*args, v.ctypes.data_as(vp), nv.value, t.ctypes.data_as(vp), nt.value, C.byref(nv), C.byref(nt), 0, C.byref(info)))
+            return mapfile.Mesh(v, t, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS})
+        if colors and tsdf.color is None:
+            raise ValueError("the volume has no colour: fuse it with color=True")
+        col = np.ascontiguousarray(tsdf.color) if colors else None
+        args = (self._h, C.byref(box), cells.ctypes.data_as(vp), col.ctypes.data_as(vp) if colors else None, 0, int(min_weight))
+        check(L.revo_map_tsdf_mesh_attr(*args, None, None, None, 0, None, 0, C.byref(nv), C.byref(nt), 0, C.byref(info)))
         v, t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.uint32)
+        nrm = np.zeros((nv.value, 3), np.float32) if normals else None
+        rgb = np.zeros((nv.value, 4), np.uint8) if colors else None
         if nv.value or nt.value:
-            check(L.revo_map_tsdf_mesh(*args, v.ctypes.data_as(vp), nv.value, t.ctypes.data_as(vp), nt.value, C.byref(nv), C.byref(nt), 0, C.byref(info)))
-        return mapfile.Mesh(v, t, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS})
+            check(L.revo_map_tsdf_mesh_attr(*args, v.ctypes.data_as(vp), nrm.ctypes.data_as(vp) if normals else None,
+                                            rgb.ctypes.data_as(vp) if colors else None, nv.value, t.ctypes.data_as(vp), nt.value,
+                                            C.byref(nv), C.byref(nt), 0, C.byref(info)))
+        return mapfile.Mesh(v, t, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS}, nrm, rgb)
 
-    def mesh_into(self, d_vertices, d_triangles, d_tsdf, lo, min_weight=1):
+    def mesh_into(self, d_vertices, d_triangles, d_tsdf, lo, min_weight=1, d_normals=None, d_colors=None, d_color=None):
         """mesh() between torch device tensors: d_tsdf int32 [n0, n1, n2, 2] as fuse_into leaves it, d_vertices float32 [cap, 3],
         d_triangles int32 [cap, 3]; contiguous, 16-byte aligned, on the map's device.  -> (vertices, triangles, info dict): the
         counts; RevoError (REVO_ERR_CAPACITY), with nothing written, when a tensor holds fewer.  Both None: count only.  The call
-        waits for the map's stream first, so a fuse_into(wait=False) before it needs no sync()."""
+        waits for the map's stream first, so a fuse_into(wait=False) before it needs no sync().
+        d_normals float32 [cap, 3], d_colors uint8 [cap, 4] (both of d_vertices' capacity) and d_color, the colour volume int32
+        [n0, n1, n2, 4]: the vertices' attributes (revo_map_tsdf_mesh_attr); d_colors needs d_color."""
         from . import mapfile
         if d_tsdf.dim() != 4 or d_tsdf.shape[3] != 2 or str(d_tsdf.dtype) != "torch.int32":
             raise ValueError("d_tsdf must be an int32 tensor [n0, n1, n2, 2]")
         box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
-        for t_, dt in ((d_vertices, "torch.float32"), (d_triangles, "torch.int32")):
+        for t_, dt in ((d_vertices, "torch.float32"), (d_triangles, "torch.int32"), (d_normals, "torch.float32")):
             if t_ is not None and not (t_.is_contiguous() and t_.is_cuda and t_.dim() == 2 and t_.shape[1] == 3 and str(t_.dtype) == dt):
-                raise ValueError("d_vertices is a float32 and d_triangles an int32 contiguous device tensor [cap, 3]")
+                raise ValueError("d_vertices and d_normals are float32 and d_triangles an int32 contiguous device tensor [cap, 3]")
+        if d_colors is not None and not (d_colors.is_contiguous() and d_colors.is_cuda and d_colors.dim() == 2 and d_colors.shape[1] == 4
+                                         and str(d_colors.dtype) == "torch.uint8"):
+            raise ValueError("d_colors is a uint8 contiguous device tensor [cap, 4]")
+        if d_colors is not None and d_color is None:
+            raise ValueError("d_colors needs the colour volume d_color")
+        if d_color is not None and not (tuple(d_color.shape) == tuple(d_tsdf.shape[:3]) + (4,) and str(d_color.dtype) == "torch.int32"
+                                        and d_color.is_contiguous() and d_color.is_cuda):
+            raise ValueError("d_color must be a contiguous int32 device tensor [n0, n1, n2, 4] over d_tsdf's box")
         if not (d_tsdf.is_contiguous() and d_tsdf.is_cuda):
             raise ValueError("d_tsdf must be a contiguous device tensor")
+        caps = {len(t_) for t_ in (d_vertices, d_normals, d_colors) if t_ is not None}
+        if len(caps) > 1:
+            raise ValueError("d_vertices, d_normals and d_colors hold the same number of vertices")
         import torch
         torch.cuda.current_stream(d_tsdf.device).synchronize()
         nv, nt, info = C.c_size_t(), C.c_size_t(), MapMeshInfo()
-        check(_lib.lib().revo_map_tsdf_mesh(self._h, C.byref(box), vp(d_tsdf.data_ptr()), 1, int(min_weight),
-                                            vp(d_vertices.data_ptr()) if d_vertices is not None else None, len(d_vertices) if d_vertices is not None else 0,
-                                            vp(d_triangles.data_ptr()) if d_triangles is not None else None, len(d_triangles) if d_triangles is not None else 0,
-                                            C.byref(nv), C.byref(nt), 1, C.byref(info)))
+        ptr = lambda t_: vp(t_.data_ptr()) if t_ is not None else None  # noqa: E731
+        if d_normals is None and d_colors is None:
+            check(_lib.lib().revo_map_tsdf_mesh(self._h, C.byref(box), vp(d_tsdf.data_ptr()), 1, int(min_weight),
+                                                ptr(d_vertices), len(d_vertices) if d_vertices is not None else 0,
+                                                ptr(d_triangles), len(d_triangles) if d_triangles is not None else 0,
+                                                C.byref(nv), C.byref(nt), 1, C.byref(info)))
+        else:
+            check(_lib.lib().revo_map_tsdf_mesh_attr(self._h, C.byref(box), vp(d_tsdf.data_ptr()), ptr(d_color), 1, int(min_weight),
+                                                     ptr(d_vertices), ptr(d_normals), ptr(d_colors), caps.pop(),
+                                                     ptr(d_triangles), len(d_triangles) if d_triangles is not None else 0,
+                                                     C.byref(nv), C.byref(nt), 1, C.byref(info)))
         return nv.value, nt.value, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS}
 
     def frontiers(self, seen, min_views=1, min_count=1):
@@ -1546,11 +1641,17 @@ class TsdfVolume:
     trunc the truncation distance in metres, info the last call's counters (mapfile.TSDF_INFO_KEYS) and view_info its per-view
     class counts (None for a loaded volume)."""
 
-    def __init__(self, cells, lo, voxel, trunc, info=None, view_info=None, map=None):
+    def __init__(self, cells, lo, voxel, trunc, info=None, view_info=None, map=None, color=None, color_info=None):
         from . import mapfile
         cells = np.asarray(cells)
         if cells.dtype != mapfile.TSDF_CELL_DTYPE or cells.ndim != 3:
             raise ValueError("a TSDF volume is a 3-D array of (sum int32, weight uint32) cells")
+        if color is not None:
+            color = np.asarray(color)
+            if color.dtype != mapfile.TSDF_COLOR_DTYPE or color.shape != cells.shape:
+                raise ValueError("a colour volume is an array of (sum_b, sum_g, sum_r, weight uint32) cells of the TSDF volume's shape")
+        self.color = color            # mapfile.TSDF_COLOR_DTYPE [n0, n1, n2], or None: fused without colour (DESIGN 27)
+        self.color_info = color_info  # the last call's colour counters (mapfile.TSDF_COLOR_INFO_KEYS)
         self.cells = cells
         self.lo = np.asarray(lo, np.int32).reshape(3)
         self.n = np.asarray(cells.shape, np.int32)
@@ -1566,24 +1667,101 @@ class TsdfVolume:
         from . import mapfile
         return mapfile.tsdf_sdf(self.cells, self.trunc)
 
-    def mesh(self, min_weight=1, map=None):
+    def mesh(self, min_weight=1, normals=False, colors=False, map=None):
         """The mesh of the zero level set -> mapfile.Mesh, on the device of the map the volume was fused with (or `map`); a
-        loaded volume without one is meshed by mapfile.mesh_records, which gives the same bytes."""
+        loaded volume without one is meshed by mapfile.mesh_records, which gives the same bytes.  normals, colors: with the
+        vertices' attributes (VoxelMap.mesh; mapfile.mesh_attr_records without a map)."""
         from . import mapfile
         m = map if map is not None else self._map
+        if colors and self.color is None:
+            raise ValueError("the volume has no colour: fuse it with color=True")
         if m is None:
-            return mapfile.mesh_records(self.cells, self.lo, self.voxel, min_weight)
-        return m.mesh(self, min_weight)
+            if not (normals or colors):
+                return mapfile.mesh_records(self.cells, self.lo, self.voxel, min_weight)
+            out = mapfile.mesh_attr_records(self.cells, self.color if colors else None, self.lo, self.voxel, min_weight)
+            if not normals:
+                out.normals = None
+            return out
+        return m.mesh(self, min_weight, normals, colors)
 
     def save(self, path):
-        """The .npz `python -m revo_amd.mapfile tsdf` writes: sum, weight, lo, n, voxel, trunc."""
+        """The .npz `python -m revo_amd.mapfile tsdf` writes: sum, weight, lo, n, voxel, trunc, and with a colour volume
+        color_sum and color_weight."""
         from . import mapfile
-        return mapfile.write_tsdf(path, self.cells, self.lo, self.voxel, self.trunc)
+        return mapfile.write_tsdf(path, self.cells, self.lo, self.voxel, self.trunc, self.color)
 
     @classmethod
     def load(cls, path):
         from . import mapfile
-        return cls(*mapfile.read_tsdf(path))
+        cells, lo, voxel, trunc, color = mapfile.read_tsdf(path, color=True)
+        return cls(cells, lo, voxel, trunc, color=color)
+
+
+class SurfaceVolume:
+    """The surface of a running sequence: the two device volumes of a box that is decided before the run and does not
+    move, cleared on creation.  integrate(view) is one accumulating fuse call, enqueued only; volume() downloads a TsdfVolume;
+    mesh() meshes on the device.  vo.REVO(surface=) feeds it every keyframe.  lo, n: the box in voxel indices of the map's world
+    frame; trunc: metres (default 4 voxel edges); color=False keeps the TSDF volume alone."""
+
+    def __init__(self, map, lo, n, trunc=None, color=True):
+        import torch
+        from . import mapfile
+        self.map = map
+        box = map._df_box(lo, n, 0, 1)
+        self.lo = np.array(list(box.lo), np.int32)
+        self.n = np.array(list(box.n), np.int32)
+        self.trunc = float(mapfile.tsdf_trunc(map.voxel, trunc))
+        dev = torch.device("cuda", map.cameraPyr.device)
+        shape = tuple(int(x) for x in self.n)
+        self.d_tsdf = torch.zeros(shape + (2,), dtype=torch.int32, device=dev)
+        self.d_color = torch.zeros(shape + (4,), dtype=torch.int32, device=dev) if color else None
+        self.views = 0
+        self._vinfo = []  # one [8] int32 device tensor per integrated view: revo_map_carve_view_info
+
+    def integrate(self, view):
+        """One view -- (pyramid, T_w_c), or a raw view as VoxelMap.fuse takes it with device images -- fused into the volumes:
+        one accumulating call on the map's stream, which returns at once."""
+        import torch
+        vi = torch.zeros(8, dtype=torch.int32, device=self.d_tsdf.device)
+        self.map.fuse_into(self.d_tsdf, [view], self.lo, self.trunc, accumulate=True, d_view_info=vi, wait=False, d_color=self.d_color)
+        self._vinfo.append(vi)
+        self.views += 1
+
+    def view_counts(self):
+        """Per integrated view the cells of the box by class (mapfile.CARVE_CLASSES); waits for the map's stream."""
+        import torch
+        from . import mapfile
+        self.map.sync()
+        if not self._vinfo:
+            return []
+        rows = torch.stack(self._vinfo).cpu().numpy().view(np.uint32)
+        return [{name: int(r[i]) for i, name in enumerate(mapfile.CARVE_CLASSES)} for r in rows]
+
+    def volume(self):
+        """The volumes as they stand -> TsdfVolume (with .color unless created with color=False); waits for the map's stream."""
+        from . import mapfile
+        self.map.sync()
+        cells = np.ascontiguousarray(self.d_tsdf.cpu().numpy()).view(mapfile.TSDF_CELL_DTYPE)[..., 0]
+        col = None if self.d_color is None else np.ascontiguousarray(self.d_color.cpu().numpy()).view(mapfile.TSDF_COLOR_DTYPE)[..., 0]
+        return TsdfVolume(cells, self.lo, self.map.voxel, self.trunc, map=self.map, color=col)
+
+    def mesh(self, min_weight=1, normals=True, colors=True):
+        """The mesh of the volumes as they stand, on the device -> mapfile.Mesh.  colors needs color=True at creation."""
+        import torch
+        from . import mapfile
+        if colors and self.d_color is None:
+            raise ValueError("the surface was created without colour")
+        nv, nt, _ = self.map.mesh_into(None, None, self.d_tsdf, self.lo, min_weight)
+        dev = self.d_tsdf.device
+        d_v = torch.zeros((max(nv, 1), 3), dtype=torch.float32, device=dev)
+        d_t = torch.zeros((max(nt, 1), 3), dtype=torch.int32, device=dev)
+        d_n = torch.zeros((max(nv, 1), 3), dtype=torch.float32, device=dev) if normals else None
+        d_c = torch.zeros((max(nv, 1), 4), dtype=torch.uint8, device=dev) if colors else None
+        nv, nt, info = self.map.mesh_into(d_v, d_t, self.d_tsdf, self.lo, min_weight, d_normals=d_n, d_colors=d_c,
+                                          d_color=self.d_color if colors else None)
+        self.map.sync()
+        return mapfile.Mesh(d_v[:nv].cpu().numpy(), d_t[:nt].cpu().numpy().view(np.uint32), info,
+                            d_n[:nv].cpu().numpy() if normals else None, d_c[:nv].cpu().numpy() if colors else None)
 
 
 def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):

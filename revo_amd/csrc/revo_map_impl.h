@@ -167,9 +167,11 @@ enum { CARVE_OUTSIDE = 0, CARVE_UNKNOWN = 1, CARVE_FREE = 2, CARVE_CONFIRMED = 3
 // window that has been tested against the image size first, and |u|, |v| < 2^20 bounds the integers the test is made on.
 // ZD: the camera-space depth z and (for a CONFIRMED point) the centre pixel's depth dc go out as well -- map_carve_class_zd, for
 // revo_map_tsdf.hip; without it the two pointers are not looked at and the function is what it was.
-template <bool ZD>
+// PIX: for a CONFIRMED, OCCLUDED or EDGE point the centre pixel's place iv * w + iu goes out too -- map_carve_class_zdp, for the
+// colour of revo_map_tsdf_fuse_color.
+template <bool ZD, bool PIX = false>
 __device__ __forceinline__ int map_carve_class_t(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel,
-                                                 float* z_out, float* dc_out) {
+                                                 float* z_out, float* dc_out, unsigned* pix_out = nullptr) {
   const CarveView& c = vw.v;
   const float x = ((c.Rc[0] * px + c.Rc[1] * py) + c.Rc[2] * pz) + c.tc[0];
   const float y = ((c.Rc[3] * px + c.Rc[4] * py) + c.Rc[5] * pz) + c.tc[1];
@@ -196,6 +198,7 @@ __device__ __forceinline__ int map_carve_class_t(float px, float py, float pz, c
   const float dc = vw.depth[(size_t)iv * c.w + iu];
   const float mc = margin + margin_rel * dc;
   if (ZD) *dc_out = dc;
+  if (PIX) *pix_out = (unsigned)iv * (unsigned)c.w + (unsigned)iu;
   if (fabsf(z - dc) <= mc) return CARVE_CONFIRMED;
   return z > dc + mc ? CARVE_OCCLUDED : CARVE_EDGE;
 }
@@ -207,6 +210,10 @@ __device__ __forceinline__ int map_carve_class(float px, float py, float pz, con
 __device__ __forceinline__ int map_carve_class_zd(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel,
                                                   float* z, float* dc) {
   return map_carve_class_t<true>(px, py, pz, vw, r, margin, margin_rel, z, dc);
+}
+__device__ __forceinline__ int map_carve_class_zdp(float px, float py, float pz, const MapCarveView& vw, int r, float margin, float margin_rel,
+                                                   float* z, float* dc, unsigned* pix) {
+  return map_carve_class_t<true, true>(px, py, pz, vw, r, margin, margin_rel, z, dc, pix);
 }
 
 // Block compaction in arrival order.  s_n (LDS) is zero behind the kernel's first barrier; every selected thread draws its
@@ -325,13 +332,18 @@ struct revo_map {
   // volume (in or out), and the mesh's scratch: a byte and a word per cell, the block totals, the device outputs of a host call
   HostRows<MapCarveView> tsdf_views;
   DevBuf tsdfcnt, tsdfvol, meshwork, meshout;
+  // revo_map_tsdf_fuse_color / revo_map_tsdf_mesh_attr: the views' colour images, the device copy of a host colour volume
+  HostRows<const uint8_t*> tsdf_bgr;
+  DevBuf tsdfcol;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every
 // pyramid's context and kind before any of them orders a stream, then the pyramids' depth planes (the tracker stream is
 // ordered behind their builds; nothing is refused from there on).  hv[i].depth stays the caller's pointer for a raw image;
 // *up_bytes: what the call's host images need in one upload, each rounded up to 256 bytes.
-inline int map_views_prepare(revo_map* m, int n, const revo_map_carve_view* views, int device_in, MapCarveView* hv, size_t* up_bytes) {
+// bgr (revo_map_tsdf_fuse_color): where a pyramid view's level-0 colour plane goes, the other entries are left alone.
+inline int map_views_prepare(revo_map* m, int n, const revo_map_carve_view* views, int device_in, MapCarveView* hv, size_t* up_bytes,
+                             const uint8_t** bgr = nullptr) {
   const CarveCam cam{m->g.fx, m->g.fy, m->g.cx, m->g.cy, m->g.dmin, m->g.dmax};
   *up_bytes = 0;
   for (int i = 0; i < n; ++i) {
@@ -358,6 +370,7 @@ inline int map_views_prepare(revo_map* m, int n, const revo_map_carve_view* view
     MapSource src;
     TRY(revo_map_source_(const_cast<revo_pyr*>(views[i].kf), &src));
     hv[i].depth = src.depth;
+    if (bgr) bgr[i] = src.bgr;
   }
   return REVO_OK;
 }

@@ -1,7 +1,9 @@
 // revo_map_tsdf.hip -- a surface: revo_map_tsdf_fuse, the truncated signed distance volume of a box of voxel indices
 // fused from depth views with integer sums, and revo_map_tsdf_mesh, the mesh of its zero level set over the Kuhn tetrahedra of
-// the cells' cubes, in one canonical order.  Contracts: include/revo_hip.h.  Every value is an integer that float32 arithmetic
-// with one definition decides, or (a vertex) a float that one chain of separately rounded operations gives.
+// the cells' cubes, in one canonical order; with them revo_map_tsdf_fuse_color, the colour volume fused in the same
+// pass, and revo_map_tsdf_mesh_attr, the mesh with a normal and a colour per vertex.  Contracts: include/revo_hip.h.  Every value
+// is an integer that float32 arithmetic with one definition decides, or (a vertex, a normal) a float that one chain of separately
+// rounded operations gives.
 #include "revo_map_impl.h"
 #include "revo_seen_host.h"  // a cell's point is the seen volume's
 #include "revo_tsdf_host.h"
@@ -18,6 +20,11 @@ struct TsdfFuseK {
   u64* info;          // one 64-byte line: revo_map_tsdf_info
   unsigned* vinfo;    // 8 words per view: revo_map_carve_view_info
 };
+struct TsdfColorK {     // what k_tsdf_fuse<true> takes beside TsdfFuseK
+  const uint8_t* const* bgr;  // per view: h x w x 3 bytes
+  uint4* color;               // 16-byte aligned: sum_b, sum_g, sum_r, weight per cell
+  u64* info;                  // half a line: revo_map_tsdf_color_info
+};
 enum { TF_CELLS = 0, TF_UPDATES = 1, TF_WEIGHTED = 2, TF_INSIDE = 3, TF_SATURATED = 4 };
 
 static_assert(sizeof(revo_map_tsdf_cell) == 8 && offsetof(revo_map_tsdf_cell, weight) == 4 && sizeof(int2) == 8, "a cell is one 8-byte word");
@@ -27,6 +34,10 @@ static_assert(sizeof(revo_map_tsdf_info) == 64 && offsetof(revo_map_tsdf_info, c
               offsetof(revo_map_tsdf_info, updates) == 8 * TF_UPDATES && offsetof(revo_map_tsdf_info, cells_weighted) == 8 * TF_WEIGHTED &&
               offsetof(revo_map_tsdf_info, cells_inside) == 8 * TF_INSIDE && offsetof(revo_map_tsdf_info, saturated) == 8 * TF_SATURATED &&
               offsetof(revo_map_tsdf_info, reserved) == 40, "the info record is the kernel's counter line");
+static_assert(sizeof(revo_map_tsdf_color) == 16 && offsetof(revo_map_tsdf_color, sum_g) == 4 && offsetof(revo_map_tsdf_color, sum_r) == 8 &&
+              offsetof(revo_map_tsdf_color, weight) == 12 && sizeof(uint4) == 16, "a colour cell is one 16-byte word");
+static_assert(sizeof(revo_map_tsdf_color_info) == 32 && offsetof(revo_map_tsdf_color_info, cells_colored) == 8 &&
+              offsetof(revo_map_tsdf_color_info, reserved) == 16, "the colour info record is the kernel's two counters");
 
 __device__ __forceinline__ unsigned tsdf_wave_sum(unsigned v) {
 #pragma unroll
@@ -39,11 +50,17 @@ __device__ __forceinline__ unsigned tsdf_wave_sum(unsigned v) {
 // another; a cell's sum and weight stay in registers from the one read (when accumulating) to the one write: two 16-byte words
 // for a whole run, 8-byte words for the tail of a volume whose cells are no multiple of four.  Per view the classes of a wave
 // are counted by ballots into LDS; every counter takes one global atomic per block.  No atomic touches a cell.
-__global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
+// COLOR (revo_map_tsdf_fuse_color): the run's four colour cells stay in registers the same way, one 16-byte word each; a view's
+// three colour bytes are read where its update of a cell is a CONFIRMED one that was not dropped.  Without it `col` is not
+// looked at and the kernel is what it was.
+template <bool COLOR>
+__global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a, const TsdfColorK col) {
   __shared__ unsigned s_cls[CARVE_MAX_VIEWS * CARVE_CLASSES];
   __shared__ unsigned s_cnt[4];  // updates, weighted, inside, saturated
+  __shared__ unsigned s_col[2];  // colour updates, cells coloured
   for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256) s_cls[k] = 0;
   if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+  if (COLOR && threadIdx.x < 2) s_col[threadIdx.x] = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const size_t c0 = (size_t)(blockIdx.x * 256u + threadIdx.x) * TSDF_RUN;  // the first cell of the run
@@ -52,6 +69,7 @@ __global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
   float px[TSDF_RUN], py[TSDF_RUN], pz[TSDF_RUN];
   int sum[TSDF_RUN];
   unsigned weight[TSDF_RUN];
+  uint4 rgb[TSDF_RUN];  // COLOR: the colour cells
 #pragma unroll
   for (int j = 0; j < TSDF_RUN; ++j) {
     const size_t c = c0 + j;
@@ -64,6 +82,7 @@ __global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
     pz[j] = seen_centre(a.box.lo[2], (int)iz, a.voxel);
     sum[j] = 0;
     weight[j] = 0u;
+    if (COLOR) rgb[j] = make_uint4(0u, 0u, 0u, 0u);
   }
   const bool whole = valid[TSDF_RUN - 1];  // the four cells exist, and tsdf + c0 is 16-byte aligned
   if (a.accumulate) {
@@ -76,19 +95,27 @@ __global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
       for (int j = 0; j < TSDF_RUN; ++j)
         if (valid[j]) { const int2 v = a.tsdf[c0 + j]; sum[j] = v.x; weight[j] = (unsigned)v.y; }
     }
+    if (COLOR) {
+#pragma unroll
+      for (int j = 0; j < TSDF_RUN; ++j)
+        if (valid[j]) rgb[j] = col.color[c0 + j];
+    }
   }
-  unsigned n_upd = 0, n_sat = 0;
+  unsigned n_upd = 0, n_sat = 0, n_cupd = 0;
   for (int vi = 0; vi < a.n; ++vi) {  // uniform: the ballots see whole waves
     int cls[TSDF_RUN];
 #pragma unroll
     for (int j = 0; j < TSDF_RUN; ++j) {
       float z = 0.0f, dc = 0.0f;
-      cls[j] = valid[j] ? map_carve_class_zd(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
+      unsigned pix = 0u;
+      if (COLOR) cls[j] = valid[j] ? map_carve_class_zdp(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
+      else cls[j] = valid[j] ? map_carve_class_zd(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
       if (cls[j] == CARVE_FREE || cls[j] == CARVE_CONFIRMED) {
         const int q = cls[j] == CARVE_FREE ? TSDF_Q_ONE : tsdf_quantum(dc, z, a.trunc);
         const unsigned dropped = tsdf_update(sum[j], weight[j], q);
         n_sat += dropped;
         n_upd += 1u - dropped;
+        if (COLOR) n_cupd += tsdf_color_update(rgb[j].x, rgb[j].y, rgb[j].z, rgb[j].w, cls[j] == CARVE_CONFIRMED, dropped, col.bgr[vi] + (size_t)pix * 3);
       }
     }
 #pragma unroll
@@ -114,6 +141,20 @@ __global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
     for (int j = 0; j < TSDF_RUN; ++j)
       if (valid[j]) a.tsdf[c0 + j] = make_int2(sum[j], (int)weight[j]);
   }
+  if (COLOR) {
+    unsigned n_col = 0;
+#pragma unroll
+    for (int j = 0; j < TSDF_RUN; ++j)
+      if (valid[j]) {
+        col.color[c0 + j] = rgb[j];
+        n_col += rgb[j].w > 0u;
+      }
+    n_cupd = tsdf_wave_sum(n_cupd); n_col = tsdf_wave_sum(n_col);
+    if (lane == 0) {
+      if (n_cupd) atomicAdd(&s_col[0], n_cupd);
+      if (n_col) atomicAdd(&s_col[1], n_col);
+    }
+  }
   n_upd = tsdf_wave_sum(n_upd); n_weighted = tsdf_wave_sum(n_weighted); n_inside = tsdf_wave_sum(n_inside); n_sat = tsdf_wave_sum(n_sat);
   if (lane == 0) {  // a block's updates: at most 256 * 4 * 64
     if (n_upd) atomicAdd(&s_cnt[0], n_upd);
@@ -124,35 +165,62 @@ __global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a) {
   __syncthreads();
   if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&a.info[TF_UPDATES + threadIdx.x], (u64)s_cnt[threadIdx.x]);
   if (blockIdx.x == 0 && threadIdx.x == 4) a.info[TF_CELLS] = (u64)a.cells;
+  if (COLOR && threadIdx.x >= 8 && threadIdx.x < 10 && s_col[threadIdx.x - 8]) atomicAdd(&col.info[threadIdx.x - 8], (u64)s_col[threadIdx.x - 8]);
   for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256)
     if (s_cls[k]) atomicAdd(&a.vinfo[(k / CARVE_CLASSES) * 8 + k % CARVE_CLASSES], s_cls[k]);
 }
 
-extern "C" int revo_map_tsdf_fuse(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views, int device_in,
-                                  const revo_map_tsdf_params* prm, revo_map_tsdf_cell* tsdf, int device_tsdf, revo_map_tsdf_info* info,
-                                  revo_map_carve_view_info* view_info) {
-  if (!m || !box || !views || !tsdf) return fail(REVO_ERR_INVALID_ARG, "null argument");
+// Both fuse calls.  name: the entry point's, for its messages.  with_color: revo_map_tsdf_fuse_color -- bgr, color and cinfo are
+// looked at and k_tsdf_fuse<true> runs.
+static int tsdf_fuse_core(const char* name, bool with_color, revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views,
+                          const uint8_t* const* bgr, int device_in, const revo_map_tsdf_params* prm, revo_map_tsdf_cell* tsdf,
+                          revo_map_tsdf_color* color, int device_tsdf, revo_map_tsdf_info* info, revo_map_tsdf_color_info* cinfo,
+                          revo_map_carve_view_info* view_info) {
+  if (!m || !box || !views || !tsdf || (with_color && (!bgr || !color))) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  const std::string who = std::string(name) + ": ";
   size_t cells = 0;
-  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_tsdf_fuse: ") + why);
-  if (n < 1 || n > CARVE_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, "revo_map_tsdf_fuse: n must be 1 .. 64 views");
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, who + why);
+  if (n < 1 || n > CARVE_MAX_VIEWS) return fail(REVO_ERR_INVALID_ARG, who + "n must be 1 .. 64 views");
   TRY(map_check_side(device_in, "device_in"));
   TRY(map_check_side(device_tsdf, "device_tsdf"));
   if (device_tsdf) TRY(map_check_aligned((uintptr_t)tsdf | (uintptr_t)info | (uintptr_t)view_info, 16, "a device output is"));
+  if (device_tsdf && with_color) TRY(map_check_aligned((uintptr_t)color | (uintptr_t)cinfo, 16, "a device output is"));
   revo_map_tsdf_params pp;
-  if (const char* why = tsdf_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_tsdf_fuse: ") + why);
+  if (const char* why = tsdf_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, who + why);
+  std::vector<const uint8_t*> hb(n, nullptr);  // the views' colour images as the kernel reads them
+  if (with_color)
+    for (int i = 0; i < n; ++i) {
+      if (const char* why = tsdf_bgr_check(&views[i], bgr[i])) return fail(REVO_ERR_INVALID_ARG, who + "view " + std::to_string(i) + ": " + why);
+      hb[i] = bgr[i];
+    }
   std::vector<MapCarveView> hv(n);
   size_t up_bytes = 0;
-  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes));
+  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes, with_color ? hb.data() : nullptr));
+  size_t up_bgr = 0;  // the host colour images behind the depth images in the one upload, each rounded up to 256 bytes
+  if (with_color && !device_in)
+    for (int i = 0; i < n; ++i)
+      if (bgr[i]) up_bgr += ((size_t)hv[i].v.w * hv[i].v.h * 3 + 255) & ~(size_t)255;
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t vinfo_bytes = sizeof(revo_map_carve_view_info) * (size_t)n, vol_bytes = sizeof(revo_map_tsdf_cell) * cells;
+  const size_t col_bytes = sizeof(revo_map_tsdf_color) * cells;
   TRY(m->tsdf_views.reserve(n, s));  // waits until the previous call's upload has read the pinned rows
+  if (with_color) TRY(m->tsdf_bgr.reserve(n, s));
   TRY(m->tsdfcnt.reserve(256 + sizeof(revo_map_carve_view_info) * CARVE_MAX_VIEWS, s));
   TRY(m->tsdfvol.reserve(device_tsdf ? 0 : vol_bytes, s));
-  DevScratch images;  // host depth images of the call, uploaded; freed behind the wait below
-  if (up_bytes) {
-    TRY(images.alloc(up_bytes));
+  if (with_color) TRY(m->tsdfcol.reserve(device_tsdf ? 0 : col_bytes, s));
+  DevScratch images;  // host images of the call, uploaded; freed behind the wait below
+  if (up_bytes + up_bgr) {
+    TRY(images.alloc(up_bytes + up_bgr));
     TRY(map_views_upload(n, views, hv.data(), images.p, s));
+    size_t o = up_bytes;
+    for (int i = 0; up_bgr && i < n; ++i) {
+      if (!bgr[i]) continue;
+      const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * 3;
+      HIPCHECK(hipMemcpyAsync(images.p + o, bgr[i], bytes, hipMemcpyHostToDevice, s));
+      hb[i] = (const uint8_t*)(images.p + o);
+      o += (bytes + 255) & ~(size_t)255;
+    }
   }
   memcpy(m->tsdf_views.h, hv.data(), sizeof(MapCarveView) * n);
   TRY(m->tsdf_views.upload(n, s));
@@ -165,19 +233,49 @@ extern "C" int revo_map_tsdf_fuse(revo_map* m, const revo_map_df_box* box, int n
   a.tsdf = device_tsdf ? (int2*)tsdf : (int2*)m->tsdfvol.p;
   a.info = device_tsdf && info ? (u64*)info : (u64*)m->tsdfcnt.p;
   a.vinfo = device_tsdf && view_info ? (unsigned*)view_info : (unsigned*)(m->tsdfcnt.p + 256);
+  TsdfColorK col{};
+  if (with_color) {
+    memcpy(m->tsdf_bgr.h, hb.data(), sizeof(const uint8_t*) * n);
+    TRY(m->tsdf_bgr.upload(n, s));
+    col.bgr = m->tsdf_bgr.d;
+    col.color = device_tsdf ? (uint4*)color : (uint4*)m->tsdfcol.p;
+    col.info = device_tsdf && cinfo ? (u64*)cinfo : (u64*)(m->tsdfcnt.p + 64);
+    if (!device_tsdf && pp.accumulate) HIPCHECK(hipMemcpyAsync(col.color, color, col_bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(col.info, 0, sizeof(revo_map_tsdf_color_info), s));
+  }
   if (!device_tsdf && pp.accumulate) HIPCHECK(hipMemcpyAsync(a.tsdf, tsdf, vol_bytes, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemsetAsync(a.info, 0, sizeof(revo_map_tsdf_info), s));
   HIPCHECK(hipMemsetAsync(a.vinfo, 0, vinfo_bytes, s));
   const size_t runs = (cells + TSDF_RUN - 1) / TSDF_RUN;
-  hipLaunchKernelGGL(k_tsdf_fuse, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, s, a);
+  const dim3 grid((unsigned)((runs + 255) / 256));
+  if (with_color) hipLaunchKernelGGL(k_tsdf_fuse<true>, grid, dim3(256), 0, s, a, col);
+  else hipLaunchKernelGGL(k_tsdf_fuse<false>, grid, dim3(256), 0, s, a, col);
   HIPCHECK(hipGetLastError());
   if (!device_tsdf) {
     HIPCHECK(hipMemcpyAsync(tsdf, a.tsdf, vol_bytes, hipMemcpyDeviceToHost, s));
     if (info) HIPCHECK(hipMemcpyAsync(info, a.info, sizeof(revo_map_tsdf_info), hipMemcpyDeviceToHost, s));
     if (view_info) HIPCHECK(hipMemcpyAsync(view_info, a.vinfo, vinfo_bytes, hipMemcpyDeviceToHost, s));
+    if (with_color) {
+      HIPCHECK(hipMemcpyAsync(color, col.color, col_bytes, hipMemcpyDeviceToHost, s));
+      if (cinfo) HIPCHECK(hipMemcpyAsync(cinfo, col.info, sizeof(revo_map_tsdf_color_info), hipMemcpyDeviceToHost, s));
+    }
   }
-  if (!device_tsdf || up_bytes) HIPCHECK(hipStreamSynchronize(s));
+  if (!device_tsdf || up_bytes + up_bgr) HIPCHECK(hipStreamSynchronize(s));
   return REVO_OK;
+}
+
+extern "C" int revo_map_tsdf_fuse(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views, int device_in,
+                                  const revo_map_tsdf_params* prm, revo_map_tsdf_cell* tsdf, int device_tsdf, revo_map_tsdf_info* info,
+                                  revo_map_carve_view_info* view_info) {
+  return tsdf_fuse_core("revo_map_tsdf_fuse", false, m, box, n, views, nullptr, device_in, prm, tsdf, nullptr, device_tsdf, info, nullptr, view_info);
+}
+
+extern "C" int revo_map_tsdf_fuse_color(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views,
+                                        const uint8_t* const* bgr, int device_in, const revo_map_tsdf_params* prm,
+                                        revo_map_tsdf_cell* tsdf, revo_map_tsdf_color* color, int device_tsdf, revo_map_tsdf_info* info,
+                                        revo_map_tsdf_color_info* color_info, revo_map_carve_view_info* view_info) {
+  return tsdf_fuse_core("revo_map_tsdf_fuse_color", true, m, box, n, views, bgr, device_in, prm, tsdf, color, device_tsdf, info, color_info,
+                        view_info);
 }
 
 // ----------------------------------------------------------------------------------------------------------------- the mesh --
@@ -364,6 +462,74 @@ __global__ void __launch_bounds__(256) k_mesh_vertices(const MeshK a) {
   }
 }
 
+struct MeshAttrK {  // what k_mesh_attr takes beside MeshK
+  const uint4* color;  // NULL: no colours
+  float* normals;      // 3 floats per vertex, or NULL
+  uint8_t* colors;     // 4 bytes per vertex, or NULL
+};
+
+// The field at the cell (x, y, z) and whether the cell is valid; a cell outside the box is not, and is not read.
+__device__ __forceinline__ bool mesh_field(const MeshK& a, int x, int y, int z, float* f) {
+  *f = 0.0f;
+  if (x < 0 || x >= a.box.n[0] || y < 0 || y >= a.box.n[1] || z < 0 || z >= a.box.n[2]) return false;
+  const int2 v = a.tsdf[((size_t)x * (unsigned)a.box.n[1] + (unsigned)y) * (unsigned)a.box.n[2] + (unsigned)z];
+  if (!tsdf_valid((unsigned)v.y, a.min_weight)) return false;
+  *f = tsdf_field(v.x, (unsigned)v.y);
+  return true;
+}
+// The gradient at the valid cell (x, y, z) whose field is fc.
+__device__ __forceinline__ void mesh_gradient(const MeshK& a, int x, int y, int z, float fc, float* gx, float* gy, float* gz) {
+  float fm = 0.0f, fp = 0.0f;
+  bool vm = mesh_field(a, x - 1, y, z, &fm), vp = mesh_field(a, x + 1, y, z, &fp);
+  *gx = tsdf_grad_axis(vm, fm, fc, vp, fp);
+  vm = mesh_field(a, x, y - 1, z, &fm); vp = mesh_field(a, x, y + 1, z, &fp);
+  *gy = tsdf_grad_axis(vm, fm, fc, vp, fp);
+  vm = mesh_field(a, x, y, z - 1, &fm); vp = mesh_field(a, x, y, z + 1, &fp);
+  *gz = tsdf_grad_axis(vm, fm, fc, vp, fp);
+}
+
+// One thread per cell, as k_mesh_vertices: the normals and colours of the vertices of the cell's edges, in the order of their
+// types, at the cell's place in the list.  The neighbourhoods of the edge's two ends are read from the volume directly.
+__global__ void __launch_bounds__(256) k_mesh_attr(const MeshK a, const MeshAttrK b) {
+  const unsigned c = blockIdx.x * 256u + threadIdx.x;
+  if (c >= a.cells) return;
+  const unsigned w = a.words[c], mask = w & 0x7fu;
+  if (!mask) return;
+  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
+  const unsigned line = c / nz, iz = c - line * nz, ix = line / ny, iy = line - ix * ny;
+  size_t at = (size_t)a.totals[blockIdx.x].x + MESH_VLOCAL(w);
+  const int2 lo = a.tsdf[c];
+  float g0x = 0.0f, g0y = 0.0f, g0z = 0.0f;
+  if (b.normals) mesh_gradient(a, (int)ix, (int)iy, (int)iz, tsdf_field(lo.x, (unsigned)lo.y), &g0x, &g0y, &g0z);
+  uint4 c0 = make_uint4(0u, 0u, 0u, 0u);
+  if (b.colors) c0 = b.color[c];
+#pragma unroll
+  for (unsigned t = 0; t < 7; ++t) {
+    if (!((mask >> t) & 1u)) continue;
+    const unsigned d = t + 1u;  // the edge's end: inside the box and valid, since an active cube holds the edge
+    const size_t e = (size_t)c + ((d & 1u) ? (size_t)ny * nz : 0) + ((d & 2u) ? nz : 0u) + ((d & 4u) ? 1u : 0u);
+    const int2 hi = a.tsdf[e];
+    const float al = tsdf_edge_alpha(lo.x, (unsigned)lo.y, hi.x, (unsigned)hi.y);
+    if (b.normals) {
+      float g1x, g1y, g1z, nx, nyv, nzv;
+      mesh_gradient(a, (int)(ix + (d & 1u)), (int)(iy + ((d >> 1) & 1u)), (int)(iz + ((d >> 2) & 1u)), tsdf_field(hi.x, (unsigned)hi.y), &g1x, &g1y, &g1z);
+      tsdf_normal(tsdf_lerp(g0x, g1x, al), tsdf_lerp(g0y, g1y, al), tsdf_lerp(g0z, g1z, al), &nx, &nyv, &nzv);
+      float* out = b.normals + 3 * at;
+      out[0] = nx; out[1] = nyv; out[2] = nzv;
+    }
+    if (b.colors) {
+      const uint4 c1 = b.color[e];
+      uchar4 px;
+      px.x = tsdf_color_byte(c0.x, c0.w, c1.x, c1.w, al);
+      px.y = tsdf_color_byte(c0.y, c0.w, c1.y, c1.w, al);
+      px.z = tsdf_color_byte(c0.z, c0.w, c1.z, c1.w, al);
+      px.w = (uint8_t)tsdf_color_k(c0.w, c1.w);
+      ((uchar4*)b.colors)[at] = px;
+    }
+    ++at;
+  }
+}
+
 // the corner number of v_i of the tetrahedron whose v1, v2 are packed in v12
 __device__ __forceinline__ unsigned mesh_corner(unsigned v12, unsigned i) { return i == 0u ? 0u : i == 1u ? (v12 & 7u) : i == 2u ? (v12 >> 4) : 7u; }
 // The index of the vertex on the edge between the corners lo and hi (lo's bits among hi's) of the cube at the cell c: the base of
@@ -412,16 +578,19 @@ __global__ void __launch_bounds__(256) k_mesh_triangles(const MeshK a) {
   }
 }
 
-extern "C" int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, int device_tsdf, uint32_t min_weight,
-                                  float* vertices, size_t cap_vertices, uint32_t* triangles, size_t cap_triangles, size_t* n_vertices,
-                                  size_t* n_triangles, int device_out, revo_map_mesh_info* info) {
+// Both mesh calls.  name: the entry point's, for its messages; revo_map_tsdf_mesh passes no colour volume, normals or colours.
+static int tsdf_mesh_core(const char* name, revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, const revo_map_tsdf_color* color,
+                          int device_tsdf, uint32_t min_weight, float* vertices, float* normals, uint8_t* colors, size_t cap_vertices,
+                          uint32_t* triangles, size_t cap_triangles, size_t* n_vertices, size_t* n_triangles, int device_out,
+                          revo_map_mesh_info* info) {
   if (!m || !box || !tsdf || !n_vertices || !n_triangles) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (colors && !color) return fail(REVO_ERR_INVALID_ARG, std::string(name) + ": colours need the colour volume");
   size_t cells = 0;
-  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string("revo_map_tsdf_mesh: ") + why);
+  if (const char* why = map_df_box_check(box, &cells)) return fail(REVO_ERR_INVALID_ARG, std::string(name) + ": " + why);
   TRY(map_check_side(device_tsdf, "device_tsdf"));
   TRY(map_check_side(device_out, "device_out"));
-  if (device_tsdf) TRY(map_check_aligned((uintptr_t)tsdf, 16, "the device volume is"));
-  if (device_out) TRY(map_check_aligned((uintptr_t)vertices | (uintptr_t)triangles, 16, "a device output is"));
+  if (device_tsdf) TRY(map_check_aligned((uintptr_t)tsdf | (uintptr_t)color, 16, "the device volume is"));
+  if (device_out) TRY(map_check_aligned((uintptr_t)vertices | (uintptr_t)triangles | (uintptr_t)normals | (uintptr_t)colors, 16, "a device output is"));
   HIPCHECK(hipSetDevice(m->g.device));
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t vol_bytes = sizeof(revo_map_tsdf_cell) * cells, blocks = (cells + 255) / 256;
@@ -431,6 +600,13 @@ extern "C" int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const
   TRY(m->meshwork.reserve(off_flags + cells, s));
   TRY(m->tsdfvol.reserve(device_tsdf ? 0 : vol_bytes, s));
   if (!device_tsdf) HIPCHECK(hipMemcpyAsync(m->tsdfvol.p, tsdf, vol_bytes, hipMemcpyHostToDevice, s));
+  MeshAttrK b{};
+  if (colors) {  // the colour volume is only read for them
+    const size_t col_bytes = sizeof(revo_map_tsdf_color) * cells;
+    TRY(m->tsdfcol.reserve(device_tsdf ? 0 : col_bytes, s));
+    if (!device_tsdf) HIPCHECK(hipMemcpyAsync(m->tsdfcol.p, color, col_bytes, hipMemcpyHostToDevice, s));
+    b.color = device_tsdf ? (const uint4*)color : (const uint4*)m->tsdfcol.p;
+  }
   MeshK a{};
   a.tsdf = device_tsdf ? (const int2*)tsdf : (const int2*)m->tsdfvol.p;
   a.box = *box;
@@ -456,13 +632,21 @@ extern "C" int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const
   *n_vertices = nv;
   *n_triangles = nt;
   if (info) memcpy(info, line, sizeof(line));
-  if (!vertices && !triangles) return REVO_OK;
-  if ((vertices && cap_vertices < nv) || (triangles && cap_triangles < nt))
+  if (!vertices && !triangles && !normals && !colors) return REVO_OK;
+  if (((vertices || normals || colors) && cap_vertices < nv) || (triangles && cap_triangles < nt))
     return fail(REVO_ERR_CAPACITY, "tsdf mesh: an output holds fewer vertices or triangles than the mesh has");
-  const size_t vbytes = (12 * nv + 255) & ~(size_t)255;
-  if (!device_out) TRY(m->meshout.reserve(vbytes + 12 * nt, s));
+  // a host call's device outputs: vertices | triangles | normals | colours
+  const size_t vbytes = (12 * nv + 255) & ~(size_t)255, tbytes = (12 * nt + 255) & ~(size_t)255;
+  if (!device_out) TRY(m->meshout.reserve(vbytes + tbytes + (normals ? vbytes : 0) + (colors ? 4 * nv : 0), s));
   a.vertices = device_out ? vertices : (float*)m->meshout.p;
   a.triangles = device_out ? triangles : (unsigned*)(m->meshout.p + vbytes);
+  b.normals = !normals ? nullptr : device_out ? normals : (float*)(m->meshout.p + vbytes + tbytes);
+  b.colors = !colors ? nullptr : device_out ? colors : (uint8_t*)(m->meshout.p + vbytes + tbytes + (normals ? vbytes : 0));
+  if ((normals || colors) && nv) {
+    hipLaunchKernelGGL(k_mesh_attr, grid, dim3(256), 0, s, a, b);
+    if (!device_out && normals) HIPCHECK(hipMemcpyAsync(normals, b.normals, 12 * nv, hipMemcpyDeviceToHost, s));
+    if (!device_out && colors) HIPCHECK(hipMemcpyAsync(colors, b.colors, 4 * nv, hipMemcpyDeviceToHost, s));
+  }
   if (vertices && nv) {
     hipLaunchKernelGGL(k_mesh_vertices, grid, dim3(256), 0, s, a);
     if (!device_out) HIPCHECK(hipMemcpyAsync(vertices, a.vertices, 12 * nv, hipMemcpyDeviceToHost, s));
@@ -474,4 +658,19 @@ extern "C" int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(s));
   return REVO_OK;
+}
+
+extern "C" int revo_map_tsdf_mesh(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, int device_tsdf, uint32_t min_weight,
+                                  float* vertices, size_t cap_vertices, uint32_t* triangles, size_t cap_triangles, size_t* n_vertices,
+                                  size_t* n_triangles, int device_out, revo_map_mesh_info* info) {
+  return tsdf_mesh_core("revo_map_tsdf_mesh", m, box, tsdf, nullptr, device_tsdf, min_weight, vertices, nullptr, nullptr, cap_vertices, triangles,
+                        cap_triangles, n_vertices, n_triangles, device_out, info);
+}
+
+extern "C" int revo_map_tsdf_mesh_attr(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, const revo_map_tsdf_color* color,
+                                       int device_tsdf, uint32_t min_weight, float* vertices, float* normals, uint8_t* colors, size_t cap_vertices,
+                                       uint32_t* triangles, size_t cap_triangles, size_t* n_vertices, size_t* n_triangles, int device_out,
+                                       revo_map_mesh_info* info) {
+  return tsdf_mesh_core("revo_map_tsdf_mesh_attr", m, box, tsdf, color, device_tsdf, min_weight, vertices, normals, colors, cap_vertices, triangles,
+                        cap_triangles, n_vertices, n_triangles, device_out, info);
 }

@@ -1,7 +1,8 @@
 // revo_tsdf_host.h -- the arithmetic of the TSDF volume and its mesh (include/revo_hip.h) that host and device code
 // share, each rule written once: the parameters a call runs with, a view's update of a cell, what a cell says (valid, inside),
 // the Kuhn tetrahedra of a cube, the cubes an edge belongs to, a tetrahedron's triangles and a vertex's place on its edge.
-// Plain C++: revo_map_tsdf.hip compiles it for both sides, tests/cpp/tsdf_host.cpp for the host alone.  Internal.
+// DESIGN 27 added the colour update that goes with a TSDF update, the colour image a view needs, and a vertex's normal and colour.
+// Plain C++: revo_map_tsdf.hip compiles it for both sides, tests/cpp/tsdf_host.cpp and surface_host.cpp for the host alone.  Internal.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -45,6 +46,26 @@ TSDF_HD unsigned tsdf_update(int32_t& sum, uint32_t& weight, int32_t q) {
   sum += q;
   weight += 1u;
   return 0u;
+}
+
+// The colour image that goes with a view (revo_map_tsdf_fuse_color): a pyramid view brings its own level-0 BGR plane,
+// a raw view needs one.  Why the pair is refused, or NULL.
+inline const char* tsdf_bgr_check(const revo_map_carve_view* v, const uint8_t* bgr) {
+  if (v->kf && bgr) return "a pyramid view brings its own colour image: bgr must be NULL";
+  if (!v->kf && !bgr) return "a raw view needs a colour image";
+  return nullptr;
+}
+
+// The colour update that goes with one TSDF update of a cell: it takes place when the view's class is CONFIRMED and the TSDF
+// update was not dropped (dropped: tsdf_update's result), so the colour weight never passes the TSDF weight.  px: the centre
+// pixel's three bytes B, G, R.  Returns 1 when it took place.
+TSDF_HD unsigned tsdf_color_update(uint32_t& sb, uint32_t& sg, uint32_t& sr, uint32_t& cw, bool confirmed, unsigned dropped, const uint8_t* px) {
+  if (!confirmed || dropped) return 0u;
+  sb += px[0];
+  sg += px[1];
+  sr += px[2];
+  cw += 1u;
+  return 1u;
 }
 
 // What a cell says.  min_weight 0 counts as 1.
@@ -114,4 +135,58 @@ TSDF_HD float tsdf_edge_alpha(int32_t s0, uint32_t w0, int32_t s1, uint32_t w1) 
 // One coordinate of a vertex: the cell's centre (revo_map_observe's), plus a along the axes the edge runs along.
 TSDF_HD float tsdf_vertex_axis(int lo, int c, bool along, float a, float voxel) {
   return (((float)(lo + c) + 0.5f) + (along ? a : 0.0f)) * voxel;
+}
+
+// ---- the attributes of a vertex (revo_map_tsdf_mesh_attr): every float32 operation rounded on its own ----
+TSDF_HD float tsdf_div(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __fdiv_rn(a, b);
+#else
+  return a / b;
+#endif
+}
+// (sqrtf, not __fsqrt_rn: without OCML's rounded operations that one is the hardware's approximate square root; sqrtf is
+// correctly rounded under the compiler's default -fhip-fp32-correctly-rounded-divide-sqrt)
+TSDF_HD float tsdf_sqrt(float a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return sqrtf(a);
+#else
+  return std::sqrt(a);
+#endif
+}
+// The field at a cell with weight > 0, in units of trunc / 1024; a colour channel's mean is the same quotient of a uint32 sum.
+TSDF_HD float tsdf_field(int32_t sum, uint32_t weight) { return tsdf_div((float)sum, (float)weight); }
+TSDF_HD float tsdf_channel(uint32_t sum, uint32_t weight) { return tsdf_div((float)sum, (float)weight); }
+// One axis of the gradient at a cell: fc the cell's field, (vm, fm) and (vp, fp) whether the neighbours c - e and c + e are
+// valid (a cell outside the box is not) and their fields.
+TSDF_HD float tsdf_grad_axis(bool vm, float fm, float fc, bool vp, float fp) {
+  if (vm && vp) return (fp - fm) * 0.5f;
+  if (vp) return fp - fc;
+  if (vm) return fc - fm;
+  return 0.0f;
+}
+// Between the edge's two ends: x0 at the lower, x1 at the upper, a the vertex's place.
+TSDF_HD float tsdf_lerp(float x0, float x1, float a) { return x0 + a * (x1 - x0); }
+// The unit normal of a gradient; (0, 0, 0) when its squared length is 0 or not finite.
+TSDF_HD void tsdf_normal(float gx, float gy, float gz, float* nx, float* ny, float* nz) {
+  const float l2 = (gx * gx + gy * gy) + gz * gz;
+  if (!(l2 > 0.0f) || !std::isfinite(l2)) { *nx = 0.0f; *ny = 0.0f; *nz = 0.0f; return; }
+  const float l = tsdf_sqrt(l2);
+  *nx = tsdf_div(gx, l);
+  *ny = tsdf_div(gy, l);
+  *nz = tsdf_div(gz, l);
+}
+// How many of an edge's two end cells carry a colour.
+TSDF_HD unsigned tsdf_color_k(uint32_t cw0, uint32_t cw1) { return (cw0 > 0u ? 1u : 0u) + (cw1 > 0u ? 1u : 0u); }
+// One channel's byte of a vertex: (s0, cw0) the lower end's sum and colour weight, (s1, cw1) the upper end's.
+TSDF_HD uint8_t tsdf_color_byte(uint32_t s0, uint32_t cw0, uint32_t s1, uint32_t cw1, float a) {
+  float v = 0.0f;
+  if (cw0 > 0u && cw1 > 0u) v = tsdf_lerp(tsdf_channel(s0, cw0), tsdf_channel(s1, cw1), a);
+  else if (cw0 > 0u) v = tsdf_channel(s0, cw0);
+  else if (cw1 > 0u) v = tsdf_channel(s1, cw1);
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 255.0f));
+#else
+  return (uint8_t)std::nearbyint(std::fmin(std::fmax(v, 0.0f), 255.0f));  // the default rounding mode: ties to even
+#endif
 }

@@ -47,12 +47,12 @@ Equal maps give equal files.
                                                         [--headings N] [--stride N] [--max-candidates N] [--weight W] [--up X Y Z]
                                                         [the options of gain] -o POSE.txt
                                                         the reachable pose that would reveal most per metre of the way there
-    python -m revo_amd.mapfile tsdf A --views DIR [--trunc M] [--pad N] -o TSDF.npz
+    python -m revo_amd.mapfile tsdf A --views DIR [--color] [--trunc M] [--pad N] -o TSDF.npz
                                                         [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S]
                                                         the views of DIR fused into a truncated signed distance volume over A's
                                                         bounds grown by N cells (revo_map_tsdf_fuse, DESIGN 26), without a GPU;
                                                         TSDF.npz holds sum, weight, lo, n, voxel, trunc
-    python -m revo_amd.mapfile mesh TSDF.npz [--min-weight K] -o MESH.ply
+    python -m revo_amd.mapfile mesh TSDF.npz [--min-weight K] [--normals] [--colors] -o MESH.ply
                                                         the mesh of the volume's zero level set (revo_map_tsdf_mesh), binary PLY
     python -m revo_amd.mapfile df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt
                                                         map SRC's points registered against map DST's distance field
@@ -312,10 +312,11 @@ def carve_view(depth, T_w_c, intrinsics):
     return D, Rc, tc, k
 
 
-def carve_classes(p, view, radius, margin, margin_rel, depths=False):
+def carve_classes(p, view, radius, margin, margin_rel, depths=False, pixels=False):
     """The class (index into CARVE_CLASSES) of every point p [N, 3] float32 in one checked view (carve_view): revo_map_carve's
     rule (include/revo_hip.h), float32 operation by operation.  depths: -> (class, z, dc), the camera-space depth of
-    every point and the centre pixel's depth (NaN where the class is outside) the classes were decided on."""
+    every point and the centre pixel's depth (NaN where the class is outside) the classes were decided on.  pixels (with depths):
+    -> (class, z, dc, pix), pix the centre pixel's place iv * w + iu (-1 where the class is outside)."""
     D, Rc, tc, k = view
     f32 = np.float32
     fx, fy, cx, cy, zmin, zmax = (f32(x) for x in k)
@@ -351,6 +352,10 @@ def carve_classes(p, view, radius, margin, margin_rel, depths=False):
     if depths:
         dc_all = np.full(len(p), np.nan, f32)
         dc_all[j] = dc
+        if pixels:
+            pix_all = np.full(len(p), -1, np.int64)
+            pix_all[j] = iv * w + iu
+            return cls, z_all.astype(f32), dc_all, pix_all
         return cls, z_all.astype(f32), dc_all
     return cls
 
@@ -397,9 +402,10 @@ def carve_records(records, voxel, views, radius=1, min_views=1, min_count=1, max
     return gone.copy(), info, counts
 
 
-def read_views(views_dir, camera, zrange, depth_scale=5000.0):
+def read_views(views_dir, camera, zrange, depth_scale=5000.0, color=False):
     """The views of a `run_tum --map-views` folder as carve_records and observe_records take them: depth/*.png (16-bit, metres
-    x depth_scale), associate.txt and poses.txt (the pose of each depth image by time stamp)."""
+    x depth_scale), associate.txt and poses.txt (the pose of each depth image by time stamp).  color: each view brings the BGR
+    image of rgb/*.png as a fourth entry, as tsdf_records(bgr=) takes it."""
     import os
     from . import tum
     rows = tum.read_associate(os.path.join(views_dir, "associate.txt"))
@@ -409,8 +415,8 @@ def read_views(views_dir, camera, zrange, depth_scale=5000.0):
         T = poses.get(round(float(rgb_ts), 6), poses.get(round(float(depth_ts), 6)))
         if T is None:
             raise ValueError("%s: no pose in poses.txt for the view at %s" % (views_dir, rgb_ts))
-        raw = tum.load_frame(views_dir, rgb_file, depth_file)[1]
-        views.append((raw.astype(np.float32) / np.float32(depth_scale), T, tuple(camera) + tuple(zrange)))
+        bgr, raw = tum.load_frame(views_dir, rgb_file, depth_file)
+        views.append((raw.astype(np.float32) / np.float32(depth_scale), T, tuple(camera) + tuple(zrange)) + ((bgr,) if color else ()))
     if not views:
         raise ValueError("%s holds no views" % views_dir)
     return views
@@ -1057,6 +1063,8 @@ def observe_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, **p
 
 TSDF_CELL_DTYPE = np.dtype([("sum", "<i4"), ("weight", "<u4")])  # revo_map_tsdf_cell
 TSDF_INFO_KEYS = ("cells", "updates", "cells_weighted", "cells_inside", "saturated")
+TSDF_COLOR_DTYPE = np.dtype([("sum_b", "<u4"), ("sum_g", "<u4"), ("sum_r", "<u4"), ("weight", "<u4")])  # revo_map_tsdf_color
+TSDF_COLOR_INFO_KEYS = ("color_updates", "cells_colored")
 MESH_INFO_KEYS = ("cells", "valid", "inside", "cubes", "cubes_active", "vertices", "triangles")
 TSDF_W_MAX = 1 << 20
 # the Kuhn tetrahedra of a cube: the corner numbers (dx + 2 dy + 4 dz) of v0 .. v3, per permutation of (x, y, z) in lexicographic order
@@ -1080,16 +1088,52 @@ def _tsdf_volume(cells, n=None):
     return cells
 
 
-def tsdf_records(voxel, lo, n, views, trunc=None, tsdf=None, chunk=1 << 20):
+def _tsdf_color_volume(color, shape):
+    color = np.asarray(color)
+    if color.dtype != TSDF_COLOR_DTYPE or color.shape != tuple(int(x) for x in shape):
+        raise ValueError("a colour volume is a 3-D array of (sum_b, sum_g, sum_r, weight uint32) cells of the TSDF volume's shape")
+    return color
+
+
+def tsdf_bgr_images(views, bgr):
+    """The colour images of a fuse's checked views (carve_view), checked as revo_map_tsdf_fuse_color checks them: one [h, w, 3]
+    uint8 image per view, of the view's size."""
+    bgr = list(bgr)
+    if len(bgr) != len(views):
+        raise ValueError("a colour fuse takes one colour image per view")
+    out = []
+    for i, (vw, im) in enumerate(zip(views, bgr)):
+        if im is None:
+            raise ValueError("view %d: a raw view needs a colour image" % i)
+        im = np.asarray(im)
+        if im.dtype != np.uint8 or im.shape != vw[0].shape + (3,):
+            raise ValueError("view %d: a colour image is [h, w, 3] uint8 of the depth image's size" % i)
+        out.append(np.ascontiguousarray(im).reshape(-1, 3))
+    return out
+
+
+def tsdf_records(voxel, lo, n, views, trunc=None, tsdf=None, chunk=1 << 20, bgr=None, color=None):
     """The TSDF volume without a GPU: revo_map_tsdf_fuse's contract in vectorised numpy, through carve_classes at
     radius 0 with margin = trunc.  views: as carve_records takes them; tsdf: a volume to accumulate into (it is not changed),
     None for a fresh one.  -> (cells TSDF_CELL_DTYPE [n0, n1, n2], info dict of TSDF_INFO_KEYS, one dict of CARVE_CLASSES counts
-    per view).  ValueError as the library's REVO_ERR_INVALID_ARG."""
+    per view).  ValueError as the library's REVO_ERR_INVALID_ARG.
+    bgr: one [h, w, 3] uint8 colour image per view -- revo_map_tsdf_fuse_color's contract; color: the colour volume to
+    accumulate into beside tsdf.  -> (cells, info, counts, colour cells TSDF_COLOR_DTYPE, dict of TSDF_COLOR_INFO_KEYS)."""
     lo, n = check_box(lo, n)
     trunc = tsdf_trunc(voxel, trunc)
     views, _, _, _ = carve_rule_args(voxel, views, 0, trunc, 0.0)
     shape = tuple(int(x) for x in n)
     before = np.zeros(shape, TSDF_CELL_DTYPE) if tsdf is None else _tsdf_volume(tsdf, n)
+    if bgr is None and color is not None:
+        raise ValueError("a colour volume is accumulated into with colour images")
+    if bgr is not None:
+        images = tsdf_bgr_images(views, bgr)
+        if (tsdf is None) != (color is None):
+            raise ValueError("a colour fuse accumulates into both volumes or into none")
+        cbefore = np.zeros(shape, TSDF_COLOR_DTYPE) if color is None else _tsdf_color_volume(color, shape)
+        csum = np.stack([cbefore[k].reshape(-1).astype(np.int64) for k in ("sum_b", "sum_g", "sum_r")], 1)
+        cw = cbefore["weight"].reshape(-1).astype(np.int64)
+        color_updates = 0
     p = seen_centres(lo, n, voxel)
     s = before["sum"].reshape(-1).astype(np.int64)
     w = before["weight"].reshape(-1).astype(np.int64)
@@ -1097,8 +1141,8 @@ def tsdf_records(voxel, lo, n, views, trunc=None, tsdf=None, chunk=1 << 20):
     updates = saturated = 0
     for a in range(0, len(p), int(chunk)):
         sl = slice(a, a + int(chunk))
-        for vw, cnt in zip(views, counts):  # in their order: a full weight drops the later ones
-            cls, z, dc = carve_classes(p[sl], vw, 0, trunc, np.float32(0), depths=True)
+        for vi, (vw, cnt) in enumerate(zip(views, counts)):  # in their order: a full weight drops the later ones
+            cls, z, dc, pix = carve_classes(p[sl], vw, 0, trunc, np.float32(0), depths=True, pixels=True)
             with np.errstate(all="ignore"):
                 q = np.rint(((dc - z) / trunc) * np.float32(1024))
             q = np.where(cls == 2, 1024, np.where(cls == 3, q, 0)).astype(np.int64)
@@ -1109,12 +1153,23 @@ def tsdf_records(voxel, lo, n, views, trunc=None, tsdf=None, chunk=1 << 20):
             w[sl] += take
             updates += int(take.sum())
             saturated += int((hit & full).sum())
+            if bgr is not None:  # the colour update goes with a CONFIRMED update that took place
+                took = np.nonzero(take & (cls == 3))[0]
+                csum[sl][took] += images[vi][pix[took]]
+                cw[sl][took] += 1
+                color_updates += len(took)
             for i, name in enumerate(CARVE_CLASSES):
                 cnt[name] += int((cls == i).sum())
     out = np.zeros(shape, TSDF_CELL_DTYPE)
     out["sum"], out["weight"] = s.reshape(shape), w.reshape(shape)
     info = {"cells": int(out.size), "updates": updates, "cells_weighted": int((w > 0).sum()), "cells_inside": int(((w > 0) & (s < 0)).sum()),
             "saturated": saturated}
+    if bgr is not None:
+        cout = np.zeros(shape, TSDF_COLOR_DTYPE)
+        for k, name in enumerate(("sum_b", "sum_g", "sum_r")):
+            cout[name] = csum[:, k].reshape(shape)
+        cout["weight"] = cw.reshape(shape)
+        return out, info, counts, cout, {"color_updates": color_updates, "cells_colored": int((cw > 0).sum())}
     return out, info, counts
 
 
@@ -1127,21 +1182,28 @@ def tsdf_sdf(cells, trunc):
 
 class Mesh:
     """A triangle mesh (revo_map_tsdf_mesh, mesh_records): vertices [V, 3] float32 metres, triangles [T, 3] uint32 vertex
-    indices, both in the contract's canonical order; info: the call's counts (MESH_INFO_KEYS), None for a loaded mesh."""
+    indices, both in the contract's canonical order; info: the call's counts (MESH_INFO_KEYS), None for a loaded mesh.
+    normals: None or [V, 3] float32 unit normals, colors: None or [V, 4] uint8 B, G, R, k (revo_map_tsdf_mesh_attr)."""
 
-    def __init__(self, vertices, triangles, info=None):
+    def __init__(self, vertices, triangles, info=None, normals=None, colors=None):
         self.vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
         self.triangles = np.asarray(triangles, np.uint32).reshape(-1, 3)
         self.info = info
+        self.normals = None if normals is None else np.asarray(normals, np.float32).reshape(-1, 3)
+        self.colors = None if colors is None else np.asarray(colors, np.uint8).reshape(-1, 4)
+        for a in (self.normals, self.colors):
+            if a is not None and len(a) != len(self.vertices):
+                raise ValueError("a mesh has one normal and one colour per vertex")
 
     def save_ply(self, path):
         from . import ply
-        return ply.write_mesh_ply(path, self.vertices, self.triangles)
+        return ply.write_mesh_ply(path, self.vertices, self.triangles, self.normals, self.colors)
 
     @classmethod
     def load_ply(cls, path):
         from . import ply
-        return cls(*ply.read_mesh_ply(path))
+        v, t, normals, colors = ply.read_mesh_ply(path, attributes=True)
+        return cls(v, t, None, normals, colors)
 
 
 def _tsdf_case_triangles(case):
@@ -1159,8 +1221,9 @@ def _tsdf_case_triangles(case):
     return [(e(a, c), e(a, d), e(b, d)), (e(a, c), e(b, d), e(b, c))]
 
 
-def mesh_records(cells, lo, voxel, min_weight=1):
-    """The mesh of a TSDF volume without a GPU: revo_map_tsdf_mesh's contract in vectorised numpy -> Mesh."""
+def mesh_records(cells, lo, voxel, min_weight=1, _edges=None):
+    """The mesh of a TSDF volume without a GPU: revo_map_tsdf_mesh's contract in vectorised numpy -> Mesh.
+    _edges: a dict that takes the vertices' edges (mesh_attr_records)."""
     cells = _tsdf_volume(cells)
     n = np.asarray(cells.shape, np.int64)
     lo, _ = check_box(lo, n)
@@ -1207,6 +1270,8 @@ def mesh_records(cells, lo, voxel, min_weight=1):
     vertices = np.empty((len(cell_i), 3), f32)
     for axis, (c, along) in enumerate(((ix, dx), (iy, dy), (iz, dz))):
         vertices[:, axis] = (((int(lo[axis]) + c).astype(f32) + f32(0.5)) + np.where(along == 1, a, f32(0))) * voxel
+    if _edges is not None:
+        _edges.update(c0=(ix, iy, iz), d=(dx, dy, dz), a=a, valid=valid, shifted=shifted)
     # the triangles: per active cube (ascending place), tetrahedron and k
     cubes = np.nonzero(active.reshape(-1))[0]
     cx, cy, cz = np.unravel_index(cubes, cells.shape)
@@ -1231,17 +1296,74 @@ def mesh_records(cells, lo, voxel, min_weight=1):
     return Mesh(vertices, triangles, info)
 
 
-def write_tsdf(path, cells, lo, voxel, trunc):
-    """The .npz of a TSDF volume: sum (int32 [n0, n1, n2]), weight (uint32), lo, n (int32 [3]), voxel, trunc (float32)."""
+def mesh_attr_records(tsdf, color, lo, voxel, min_weight=1):
+    """mesh_records with the vertices' normals and colours: revo_map_tsdf_mesh_attr's contract in vectorised numpy,
+    float32 operation by operation -> Mesh.  color: the colour volume, or None (then the mesh has no colours)."""
+    f32 = np.float32
+    e = {}
+    m = mesh_records(tsdf, lo, voxel, min_weight, _edges=e)
+    cells = _tsdf_volume(tsdf)
+    valid, shifted = e["valid"], e["shifted"]
+    (ix, iy, iz), (dx, dy, dz), a = e["c0"], e["d"], e["a"]
+    with np.errstate(all="ignore"):
+        f = np.where(valid, cells["sum"].astype(f32) / cells["weight"].astype(f32), f32(0)).astype(f32)
+        grad = np.zeros(cells.shape + (3,), f32)
+        for axis in range(3):
+            dm, dp = [0, 0, 0], [0, 0, 0]
+            dm[axis], dp[axis] = -1, 1
+            vm, vp = shifted(valid, dm), shifted(valid, dp)
+            fm, fp = shifted(f, dm, f32(0)), shifted(f, dp, f32(0))
+            grad[..., axis] = np.where(vm & vp, (fp - fm) * f32(0.5), np.where(vp, fp - f, np.where(vm, f - fm, f32(0))))
+        g0, g1 = grad[ix, iy, iz], grad[ix + dx, iy + dy, iz + dz]
+        g = (g0 + a[:, None] * (g1 - g0)).astype(f32)
+        l2 = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
+        ok = np.isfinite(l2) & (l2 > 0)
+        m.normals = np.where(ok[:, None], g / np.sqrt(l2)[:, None], f32(0)).astype(f32).reshape(-1, 3)
+        if color is not None:
+            color = _tsdf_color_volume(color, cells.shape)
+            cw = color["weight"]
+            w0, w1 = cw[ix, iy, iz], cw[ix + dx, iy + dy, iz + dz]
+            out = np.zeros((len(a), 4), np.uint8)
+            for k, name in enumerate(("sum_b", "sum_g", "sum_r")):
+                mean = color[name].astype(f32) / cw.astype(f32)
+                m0, m1 = mean[ix, iy, iz], mean[ix + dx, iy + dy, iz + dz]
+                v = np.where((w0 > 0) & (w1 > 0), m0 + a * (m1 - m0), np.where(w0 > 0, m0, np.where(w1 > 0, m1, f32(0)))).astype(f32)
+                out[:, k] = np.rint(np.minimum(np.maximum(v, f32(0)), f32(255))).astype(np.uint8)
+            out[:, 3] = (w0 > 0).astype(np.uint8) + (w1 > 0).astype(np.uint8)
+            m.colors = out
+    return m
+
+
+def write_tsdf(path, cells, lo, voxel, trunc, color=None):
+    """The .npz of a TSDF volume: sum (int32 [n0, n1, n2]), weight (uint32), lo, n (int32 [3]), voxel, trunc (float32); with a
+    colour volume also color_sum (uint32 [n0, n1, n2, 3]: B, G, R) and color_weight (uint32)."""
     cells = _tsdf_volume(cells)
+    extra = {}
+    if color is not None:
+        color = _tsdf_color_volume(color, cells.shape)
+        extra = {"color_sum": np.stack([color[k] for k in ("sum_b", "sum_g", "sum_r")], -1), "color_weight": np.ascontiguousarray(color["weight"])}
     with open(path, "wb") as f:
         np.savez(f, sum=np.ascontiguousarray(cells["sum"]), weight=np.ascontiguousarray(cells["weight"]), lo=np.asarray(lo, np.int32).reshape(3),
-                 n=np.asarray(cells.shape, np.int32), voxel=np.float32(voxel), trunc=np.float32(trunc))
+                 n=np.asarray(cells.shape, np.int32), voxel=np.float32(voxel), trunc=np.float32(trunc), **extra)
     return path
 
 
-def read_tsdf(path):
-    """(cells, lo, voxel, trunc) of a file write_tsdf wrote; ValueError if its arrays do not fit together."""
+def read_tsdf(path, color=False):
+    """(cells, lo, voxel, trunc) of a file write_tsdf wrote; ValueError if its arrays do not fit together.  color: a fifth entry,
+    the file's colour volume or None."""
+    if color:
+        base = read_tsdf(path)
+        with np.load(path) as z:
+            if "color_sum" not in z.files and "color_weight" not in z.files:
+                return base + (None,)
+            if not ("color_sum" in z.files and "color_weight" in z.files):
+                raise ValueError("%s: a colour volume is color_sum and color_weight" % path)
+            cs, cw = z["color_sum"], z["color_weight"]
+        if cs.dtype != np.uint32 or cw.dtype != np.uint32 or cw.shape != base[0].shape or cs.shape != base[0].shape + (3,):
+            raise ValueError("%s: a colour volume is a uint32 color_sum [n0, n1, n2, 3] and a uint32 color_weight" % path)
+        col = np.zeros(cw.shape, TSDF_COLOR_DTYPE)
+        col["sum_b"], col["sum_g"], col["sum_r"], col["weight"] = cs[..., 0], cs[..., 1], cs[..., 2], cw
+        return base + (col,)
     with np.load(path) as z:
         if not all(k in z.files for k in ("sum", "weight", "lo", "n", "voxel", "trunc")):
             raise ValueError("%s is not a TSDF file (sum, weight, lo, n, voxel, trunc)" % path)
@@ -1254,18 +1376,28 @@ def read_tsdf(path):
     return cells, lo.astype(np.int32), float(np.float32(voxel)), float(tsdf_trunc(voxel, trunc))
 
 
-def tsdf_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, trunc=None):
+def tsdf_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, trunc=None, color=False):
     """(cells, lo, voxel, trunc, info) of the views of a `run_tum --map-views` folder over the bounds of the file's map grown by
-    `pad` cells; more than 64 views accumulate in parts of 64."""
+    `pad` cells; more than 64 views accumulate in parts of 64.  color: the folder's rgb/ images are fused too -> (cells, lo,
+    voxel, trunc, info, colour cells); info then holds TSDF_COLOR_INFO_KEYS as well."""
     header, rec = read(path)
-    views = read_views(views_dir, camera, zrange, depth_scale)
+    views = read_views(views_dir, camera, zrange, depth_scale, color=color)
     lo, hi, _ = bounds_records(rec)
     lo, n = padded_box(lo, hi, pad)
-    cells, info = None, None
+    cells, info, col = None, None, None
     for i in range(0, len(views), 64):
-        cells, part, _ = tsdf_records(header["voxel"], lo, n, views[i:i + 64], trunc, tsdf=cells)
-        info = part if info is None else dict(part, updates=info["updates"] + part["updates"], saturated=info["saturated"] + part["saturated"])
-    return cells, lo.astype(np.int32), header["voxel"], float(tsdf_trunc(header["voxel"], trunc)), info
+        part_views = views[i:i + 64]
+        if color:
+            cells, part, _, col, cpart = tsdf_records(header["voxel"], lo, n, [v[:3] for v in part_views], trunc, tsdf=cells,
+                                                       bgr=[v[3] for v in part_views], color=col)
+            part = dict(part, **cpart)
+        else:
+            cells, part, _ = tsdf_records(header["voxel"], lo, n, part_views, trunc, tsdf=cells)
+        if info is not None:
+            part = dict(part, **{k: info[k] + part[k] for k in ("updates", "saturated", "color_updates") if k in part})
+        info = part
+    out = (cells, lo.astype(np.int32), header["voxel"], float(tsdf_trunc(header["voxel"], trunc)), info)
+    return out + (col,) if color else out
 
 
 def df_sample(d2, lo, voxel, points):
@@ -2034,18 +2166,30 @@ def main(argv=None):
                 else:
                     pos.append(args[i])
                     i += 1
+            flags = {f for f in ("--color", "--normals", "--colors") if f in pos}
+            pos = [a for a in pos if a not in flags]
             if cmd == "tsdf" and len(pos) == 1 and "--views" in val:
                 camera = [float(x) for x in val.get("--camera", (525.0, 525.0, 319.5, 239.5))]  # the TUM default camera
                 zrange = [float(x) for x in val.get("--zrange", (0.1, 5.2))]
-                cells, lo, voxel, trunc, info = tsdf_file(pos[0], val["--views"][0], camera, zrange, float(val.get("--depth-scale", [5000.0])[0]),
-                                                          int(val.get("--pad", [0])[0]), float(val["--trunc"][0]) if "--trunc" in val else None)
-                write_tsdf(val["-o"][0], cells, lo, voxel, trunc)
-                print("%s: %d x %d x %d cells from %s (the views of %s over %s), trunc %g m: %d with a weight, %d inside"
-                      % ((val["-o"][0],) + cells.shape + (lo.tolist(), val["--views"][0], pos[0], trunc, info["cells_weighted"], info["cells_inside"])))
+                res = tsdf_file(pos[0], val["--views"][0], camera, zrange, float(val.get("--depth-scale", [5000.0])[0]),
+                                int(val.get("--pad", [0])[0]), float(val["--trunc"][0]) if "--trunc" in val else None, color="--color" in flags)
+                cells, lo, voxel, trunc, info = res[:5]
+                write_tsdf(val["-o"][0], cells, lo, voxel, trunc, res[5] if "--color" in flags else None)
+                print("%s: %d x %d x %d cells from %s (the views of %s over %s), trunc %g m: %d with a weight, %d inside%s"
+                      % ((val["-o"][0],) + cells.shape + (lo.tolist(), val["--views"][0], pos[0], trunc, info["cells_weighted"], info["cells_inside"],
+                                                          ", %d coloured" % info["cells_colored"] if "--color" in flags else "")))
                 return 0
             if cmd == "mesh" and len(pos) == 1:
-                cells, lo, voxel, _ = read_tsdf(pos[0])
-                m = mesh_records(cells, lo, voxel, int(val.get("--min-weight", [1])[0]))
+                cells, lo, voxel, _, col = read_tsdf(pos[0], color=True)
+                mw = int(val.get("--min-weight", [1])[0])
+                if "--colors" in flags and col is None:
+                    raise ValueError("%s holds no colour volume (mapfile tsdf --color writes one)" % pos[0])
+                if flags:
+                    m = mesh_attr_records(cells, col if "--colors" in flags else None, lo, voxel, mw)
+                    if "--normals" not in flags:
+                        m.normals = None
+                else:
+                    m = mesh_records(cells, lo, voxel, mw)
                 m.save_ply(val["-o"][0])
                 print("%s: %d vertices, %d triangles from %d active cubes of %s" % (val["-o"][0], len(m.vertices), len(m.triangles),
                                                                                    m.info["cubes_active"], pos[0]))
@@ -2072,8 +2216,8 @@ def main(argv=None):
           "[--min-views K] [--min-count N] [--miss-depth D] [--max-steps N] -o GAIN.txt | "
           "next-view A --seen SEEN.npz --start X Y Z --clearance M --camera FX FY CX CY --size W H [--headings N] [--stride N] [--max-candidates N] "
           "[--weight W] [--up X Y Z] [the options of gain] -o POSE.txt | "
-          "tsdf A --views DIR -o TSDF.npz [--trunc M] [--pad N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
-          "mesh TSDF.npz -o MESH.ply [--min-weight K] | "
+          "tsdf A --views DIR -o TSDF.npz [--color] [--trunc M] [--pad N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
+          "mesh TSDF.npz -o MESH.ply [--min-weight K] [--normals] [--colors] | "
           "ply FILE [OUT.ply]")
     return 2
 

@@ -162,43 +162,68 @@ def read_voxel_ply(path):
 MESH_PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<u4", (3,))])  # 13 bytes per face, packed
 
 
-def mesh_ply_header(nv, nf):
+def mesh_ply_header(nv, nf, normals=False, colors=False):
     return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n"
-            "property float x\nproperty float y\nproperty float z\n"
-            "element face %d\nproperty list uchar uint vertex_indices\nend_header\n" % (nv, nf)).encode("ascii")
+            "property float x\nproperty float y\nproperty float z\n%s%s"
+            "element face %d\nproperty list uchar uint vertex_indices\nend_header\n"
+            % (nv, "property float nx\nproperty float ny\nproperty float nz\n" if normals else "",
+               "property uchar red\nproperty uchar green\nproperty uchar blue\n" if colors else "", nf)).encode("ascii")
 
 
-def write_mesh_ply(path, vertices, triangles):
+def mesh_ply_vertex_dtype(normals=False, colors=False):
+    return np.dtype([("p", "<f4", (3,))] + ([("n", "<f4", (3,))] if normals else []) + ([("rgb", "u1", (3,))] if colors else []))
+
+
+def write_mesh_ply(path, vertices, triangles, normals=None, colors=None):
     """A triangle mesh (mapfile.Mesh) as binary little-endian PLY: `vertex` elements x y z float32 and `face` elements, each a
-    list of three uint32 vertex indices, both in the order given."""
+    list of three uint32 vertex indices, both in the order given.  normals ([V, 3] float32): nx ny nz behind the position;
+    colors ([V, 4] uint8 B, G, R, k): red green blue behind those (k is not written).  Without them the file is what it was."""
     v = np.ascontiguousarray(np.asarray(vertices, "<f4").reshape(-1, 3))
     t = np.asarray(triangles, np.uint32).reshape(-1, 3)
     if len(t) and int(t.max()) >= len(v):
         raise ValueError("a triangle names a vertex the mesh does not have")
+    rows = np.zeros(len(v), mesh_ply_vertex_dtype(normals is not None, colors is not None))
+    rows["p"] = v
+    if normals is not None:
+        rows["n"] = np.asarray(normals, "<f4").reshape(len(v), 3)
+    if colors is not None:
+        rows["rgb"] = np.asarray(colors, np.uint8).reshape(len(v), 4)[:, 2::-1]
     f = np.empty(len(t), MESH_PLY_FACE_DTYPE)
     f["n"], f["v"] = 3, t
     with open(path, "wb") as out:
-        out.write(mesh_ply_header(len(v), len(t)))
-        out.write(v.tobytes())
+        out.write(mesh_ply_header(len(v), len(t), normals is not None, colors is not None))
+        out.write(rows.tobytes())
         out.write(f.tobytes())
     return path
 
 
-def read_mesh_ply(path):
-    """Reader for write_mesh_ply's files -> (vertices V x 3 float32, triangles T x 3 uint32)."""
+def read_mesh_ply(path, attributes=False):
+    """Reader for write_mesh_ply's files -> (vertices V x 3 float32, triangles T x 3 uint32).  attributes: -> (vertices,
+    triangles, normals or None, colors or None); colors [V, 4] uint8 B, G, R and 255 (the file does not hold k)."""
     data = open(path, "rb").read()
     if b"end_header\n" not in data:
         raise ValueError("not a mesh PLY")
     end = data.index(b"end_header\n") + len(b"end_header\n")
-    count = {l.split()[1]: int(l.split()[2]) for l in data[:end].decode("ascii", "replace").split("\n") if l.startswith("element ")}
+    lines = data[:end].decode("ascii", "replace").split("\n")
+    count = {l.split()[1]: int(l.split()[2]) for l in lines if l.startswith("element ")}
     nv, nf = count.get("vertex", 0), count.get("face", 0)
-    if data[:end] != mesh_ply_header(nv, nf) or len(data) != end + 12 * nv + 13 * nf:
+    has_n, has_c = "property float nx" in lines, "property uchar red" in lines
+    dt = mesh_ply_vertex_dtype(has_n, has_c)
+    if data[:end] != mesh_ply_header(nv, nf, has_n, has_c) or len(data) != end + dt.itemsize * nv + 13 * nf:
         raise ValueError("not a mesh PLY")
-    v = np.frombuffer(data, "<f4", count=3 * nv, offset=end).reshape(nv, 3).copy()
-    f = np.frombuffer(data, MESH_PLY_FACE_DTYPE, count=nf, offset=end + 12 * nv)
+    rows = np.frombuffer(data, dt, count=nv, offset=end)
+    v = rows["p"].reshape(nv, 3).copy()
+    f = np.frombuffer(data, MESH_PLY_FACE_DTYPE, count=nf, offset=end + dt.itemsize * nv)
     if nf and not np.all(f["n"] == 3):
         raise ValueError("not a triangle mesh")
-    return v, f["v"].astype(np.uint32).reshape(nf, 3)
+    t = f["v"].astype(np.uint32).reshape(nf, 3)
+    if not attributes:
+        return v, t
+    colors = None
+    if has_c:
+        colors = np.full((nv, 4), 255, np.uint8)
+        colors[:, :3] = rows["rgb"].reshape(nv, 3)[:, ::-1]
+    return v, t, rows["n"].reshape(nv, 3).copy() if has_n else None, colors
 
 
 def read_ply_vertices(path):

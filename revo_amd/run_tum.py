@@ -29,6 +29,12 @@ carve): voxels the keyframe's depth image looks through -- moved obje
 map.  --map-carve-margin M sets the margin in metres (default: the voxel edge), --map-carve-views K the views a voxel must be
 free in (default 1; a keyframe is one view, so K > 1 carves nothing).  An error with --map-window and with --streams.  The pose
 file does not depend on it.
+--surface FILE.ply (with --map, sequential driver only) fuses every keyframe's depth and colour into a TSDF and a colour volume
+while the sequence runs (vo.REVO's surface, api.SurfaceVolume) and writes the mesh with per-vertex normals and colours
+at the end.  --surface-box I0 J0 K0 N0 N1 N2 is the box in voxel indices of the world frame (the first camera's frame), decided
+before the run (default -128 -128 -32 256 256 256); surfaces outside it are not there, and the keyframes that confirm no cell of
+it are counted on stderr.  --surface-trunc M: the truncation distance in metres (default 4 voxel edges); --surface-min-weight K:
+the views a cell needs.  An error with --map-window and with --streams.  The pose file does not depend on it.
 --covariances writes cov_<dataset>.txt next to the pose file, one line per pose line in the same order: the frame's time stamp,
 its keyframe's time stamp, the good-point count, sigma2 and the 21 upper-triangle entries (row-major) of the 6x6 covariance of the
 relative pose frame -> keyframe (api.pair_covariance of the level-0 settings.PairInfo at the final pose; translation 0-2,
@@ -45,7 +51,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -161,6 +167,37 @@ def main(argv=None):
         if not (np.isfinite(map_carve.get("margin", 0.0)) and map_carve.get("margin", 0.0) >= 0) or map_carve.get("min_views", 1) < 1:
             print("--map-carve-margin needs a margin >= 0 in metres, --map-carve-views a positive number of views")
             return 2
+    surface = None  # vo.REVO's surface: the coloured, shaded mesh of the keyframes' TSDF volume, written at the end of the run
+    for opt, key, k, conv in (("--surface", "file", 1, str), ("--surface-box", "box", 6, int), ("--surface-trunc", "trunc", 1, float),
+                              ("--surface-min-weight", "min_weight", 1, int)):
+        if opt in argv:
+            i = argv.index(opt)
+            try:
+                got = [conv(x) for x in argv[i + 1:i + 1 + k]]
+                if len(got) != k:
+                    raise ValueError
+            except ValueError:
+                print("%s needs %s" % (opt, {"file": "a file name", "box": "six integers: I0 J0 K0 N0 N1 N2", "trunc": "a distance in metres",
+                                             "min_weight": "a number of views"}[key]))
+                return 2
+            surface = dict(surface or {}, **{key: got[0] if k == 1 else got})
+            argv = argv[:i] + argv[i + 1 + k:]
+    if surface is not None:
+        if "file" not in surface:
+            print("--surface-box, --surface-trunc and --surface-min-weight need --surface FILE.ply")
+            return 2
+        if map_voxel is None:
+            print("--surface fuses the keyframes over the voxel map's frame: it needs --map VOXEL")
+            return 2
+        if map_window:
+            print("--surface is not supported together with --map-window: the volumes keep what the window evicts")
+            return 2
+        if "--streams" in argv:
+            print("--surface is not supported together with --streams: the surface runs on the sequential driver only (drop --streams)")
+            return 2
+        if any(x < 1 for x in surface.get("box", (0, 0, 0, 1, 1, 1))[3:]) or not surface.get("trunc", 1.0) > 0 or surface.get("min_weight", 1) < 0:
+            print("--surface-box needs N0 N1 N2 >= 1, --surface-trunc a distance > 0 in metres, --surface-min-weight a number >= 0")
+            return 2
     exact_sums = "--exact-sums" in argv  # the tracker's exact-sums mode (both drivers)
     if exact_sums:
         argv = [a for a in argv if a != "--exact-sums"]
@@ -203,8 +240,13 @@ def main(argv=None):
         vmap = api.VoxelMap(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"])) if map_voxel else None
         if map_window:
             vmap = api.MapWindow(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"]), window=map_window)
+        surf = None
+        if surface is not None:  # the box is decided here and does not move: voxel indices of the first camera's frame
+            box = surface.get("box", (-128, -128, -32, 256, 256, 256))
+            surf = api.SurfaceVolume(vmap, box[:3], box[3:], surface.get("trunc"), color=True)
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
-                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances, carve=map_carve)
+                      mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances, carve=map_carve,
+                      surface=surf)
         nd = tum.default_decoders() if decoders is None else decoders
         rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
                                   read_n_images=io["read_n_images"])
@@ -235,6 +277,8 @@ def main(argv=None):
                       % (sum(i["voxels_carved"] for i in done), sum(i["points_carved"] for i in done), len(done),
                          (" -- %d keyframes carved NOTHING: their pose's rotation had drifted past the orthogonality rule"
                           % drv.carve_skipped) if drv.carve_skipped else ""))
+            if surf is not None:
+                _save_surface(surf, drv, surface, name, len(io["datasets"]) > 1)
             if map_window:
                 with open("map_window_%s.txt" % name, "w") as f:
                     for ts, T in zip(vmap.timestamps, vmap.keyframes):
@@ -248,6 +292,21 @@ def main(argv=None):
             print("model: %d points of %d keyframes -> %s, %s" % (drawer.nPts, len(drawer.vpKfsF), out[0], out[1]))
         _report_ate(folder, drv.poses)
     return 0
+
+
+def _save_surface(surf, drv, surface, name, per_dataset):
+    """--surface FILE.ply: the mesh of the run's volumes with normals and colours (FILE with _<dataset> in front of its extension
+    when there are several data sets)."""
+    import sys
+    mesh = surf.mesh(surface.get("min_weight", 1), normals=True, colors=True)
+    out = _rvm_path(surface["file"], name, per_dataset)
+    mesh.save_ply(out)
+    print("Surface: %d vertices, %d triangles from %d keyframes over the box %s + %s -> %s"
+          % (len(mesh.vertices), len(mesh.triangles), surf.views, surf.lo.tolist(), surf.n.tolist(), out))
+    blind = sum(1 for c in surf.view_counts() if c["confirmed"] == 0)
+    if blind or drv.surface_skipped:
+        print("Surface: %d of %d keyframes confirmed no cell of the box (their surfaces lie outside it); %d were not fused for their pose's rotation"
+              % (blind, surf.views, drv.surface_skipped), file=sys.stderr)
 
 
 def _rvm_path(map_save, name, per_dataset):

@@ -403,6 +403,19 @@ class MapMeshInfo(C.Structure):
 assert (C.sizeof(MapTsdfCell), C.sizeof(MapTsdfParams), C.sizeof(MapTsdfInfo), C.sizeof(MapMeshInfo)) == (8, 16, 64, 64)
 
 
+class MapTsdfColor(C.Structure):
+    """revo_map_tsdf_color (include/revo_hip.h), 16 bytes: the sums of a cell's colour updates per channel and their number."""
+    _fields_ = [("sum_b", C.c_uint32), ("sum_g", C.c_uint32), ("sum_r", C.c_uint32), ("weight", C.c_uint32)]
+
+
+class MapTsdfColorInfo(C.Structure):
+    """revo_map_tsdf_color_info (include/revo_hip.h), 32 bytes: the colour counters of a fuse call."""
+    _fields_ = [("color_updates", C.c_uint64), ("cells_colored", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+assert (C.sizeof(MapTsdfColor), C.sizeof(MapTsdfColorInfo)) == (16, 32)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

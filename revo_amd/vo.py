@@ -22,7 +22,7 @@ from .settings import PairInfo, StreamFrame, StreamResult, TrackerSettings
 
 class REVO:
     def __init__(self, settingsPyr, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False, carve=None):
+                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False, carve=None, surface=None):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         self.camPyr = cameraPyr or api.CameraPyr(settingsPyr, device=device)
@@ -51,6 +51,19 @@ class REVO:
                 raise ValueError("carve needs a voxelMap")
             if isinstance(voxelMap, api.MapWindow):
                 raise ValueError("carve is not supported with a MapWindow: its per-keyframe records must stay subtractable")
+        # surface: an api.SurfaceVolume of voxelMap: every keyframe's pyramid is fused into its volumes at T_w_kf where
+        # the keyframe is reported to the map, after the carve and beside the integration -- one accumulating call, enqueued only.
+        # A keyframe whose pose's rotation fails the library's is_orthogonal rule is not fused and counted in surface_skipped.
+        # Off by default: nothing new is enqueued.
+        self.surface = surface
+        self.surface_skipped = 0
+        if surface is not None:
+            if voxelMap is None:
+                raise ValueError("surface needs a voxelMap")
+            if isinstance(voxelMap, api.MapWindow):
+                raise ValueError("surface is not supported with a MapWindow: the volumes keep what the window evicts")
+            if surface.map is not voxelMap:
+                raise ValueError("the surface belongs to another map than voxelMap")
         # pair_info: every reported pose comes with its level-0 settings.PairInfo (the information matrix of the relative pose
         # curr -> keyframe at the final pose) and that keyframe's time stamp: pair_infos[i] belongs to poses[i]
         self.pair_info = bool(pair_info)
@@ -112,7 +125,20 @@ class REVO:
                 if self.carve is not None:
                     self._carve_with(kfPyr, T_w_kf)
                 self.voxelMap.integrate(kfPyr, T_w_kf)
+                if self.surface is not None:
+                    self._surface_with(kfPyr, T_w_kf)
         return M, bool(kf.value)
+
+    def _surface_with(self, kfPyr, T_w_kf):
+        from . import mapfile
+        if mapfile.pose_is_orthogonal(np.asarray(T_w_kf, np.float32)[:3, :3]):
+            self.surface.integrate((kfPyr, T_w_kf))
+            return
+        self.surface_skipped += 1
+        if self.surface_skipped == 1:
+            import warnings
+            warnings.warn("REVO surface: the rotation of a keyframe pose is no longer orthogonal to 1e-5 (float32 drift); that "
+                          "keyframe is not fused -- see REVO.surface_skipped for how many", RuntimeWarning, stacklevel=3)
 
     def _carve_with(self, kfPyr, T_w_kf):
         from . import mapfile
