@@ -1614,6 +1614,77 @@ int revo_map_tsdf_mesh_attr(revo_map* m, const revo_map_df_box* box, const revo_
                             uint32_t* triangles, size_t cap_triangles, size_t* n_vertices, size_t* n_triangles,
                             int device_out, revo_map_mesh_info* info);
 
+/* ---- views of the surface: depth, normal and colour images ray-cast from the TSDF volume ---------------------
+ * One thread marches one ray alone through the fused field in steps of camera depth; a surface is the sign change between two
+ * neighbouring samples, found with sub-voxel accuracy from the trilinear interpolant.  No atomic decides an output, so a view's
+ * images are a pure function of the two volumes' bytes, the box, the voxel edge, the view and the parameters: the same bytes
+ * whatever the launch, the other views of the call, or the side the volumes live on.
+ * All arithmetic is float32 with every operation rounded on its own; a / b is the correctly rounded quotient, sqrtf too.
+ *
+ * Rays.  A view is a revo_map_view with revo_map_render's rules and all-zero defaults; splat_max and min_count are not read.
+ * Pixel (x, y) casts revo_map_raycast's ray: dcx = ((float)x - cx)/fx, dcy = ((float)y - cy)/fy,
+ * d_i = ((R_i0*dcx) + (R_i1*dcy)) + R_i2 (R the rotation of T_w_c), o = the translation of T_w_c: the parameter is camera depth.
+ * Samples.  Sample k = 0, 1, ... sits at s_k = zmin + (float)k * step, computed from the integer and never accumulated.  The
+ * march visits the samples in order, starting with "no previous sample":
+ *  1. if k == max_steps the ray is EXHAUSTED;
+ *  2. if !(s_k < zmax) the ray is a RANGE miss;
+ *  3. the sample's place in the box: g_i = o_i + s_k*d_i, u_i = g_i / voxel - ((float)lo_i + 0.5f) (cell centres sit at
+ *     integers), b_i = floorf(u_i), r_i = u_i - b_i;
+ *  4. the sample is VALID when every u_i is finite with 0 <= b_i <= n_i - 2 and all eight cells b + {0,1}^3 are valid by the
+ *     mesh's rule, weight >= max(min_weight, 1).  A box with an axis of 1 has no valid sample;
+ *  5. for a valid sample f(c) = (float)sum / (float)weight at the eight cells, written f(dx, dy, dz).  L(x0, x1, a) =
+ *     x0 + a*(x1 - x0).  A value at the eight corners is interpolated along z first, then y, then x:
+ *     T(v) = L(L(L(v000, v001, r_z), L(v010, v011, r_z), r_y), L(L(v100, v101, r_z), L(v110, v111, r_z), r_y), r_x); F = T(f).
+ *     G is the interpolant's own gradient, in field units per cell: G_x interpolates the four differences f(1,y,z) - f(0,y,z)
+ *     along z with r_z, then along y with r_y; G_y the four f(x,1,z) - f(x,0,z) along z with r_z, then along x with r_x; G_z
+ *     the four f(x,y,1) - f(x,y,0) along y with r_y, then along x with r_x;
+ *  6. the decision, from this sample and the previous one: an invalid sample forgets the previous one (a surface is never
+ *     found across unknown space); a valid sample behind a valid previous sample with Fp >= 0 and F < 0 is a HIT (inside is
+ *     F < 0, as the mesh has it); with Fp < 0 and F >= 0 it ends the ray as BACKFACE (a surface seen from behind is not
+ *     shown); otherwise the sample becomes the previous one.
+ * A hit is computed from the two samples alone: a = Fp / (Fp - F); depth = s_{k-1} + a*step; the normal is the unit vector of
+ * g_i = L(Gp_i, G_i, a) exactly as revo_map_tsdf_mesh_attr normalises (l2 = (g_x*g_x + g_y*g_y) + g_z*g_z, n_i = g_i / sqrtf(l2),
+ * (0, 0, 0) when l2 is 0 or not finite): in the world frame, pointing from inside to outside.  A sample's colour cell is its
+ * nearest corner b_i + (r_i >= 0.5f ? 1 : 0); the pixel's B, G, R are revo_map_tsdf_mesh_attr's bytes over the two samples'
+ * colour cells with a, the previous sample as the lower end; k counts the two cells with color.weight > 0, and k = 0 gives
+ * 0, 0, 0.  A miss: depth 0, normal (0, 0, 0), BGR 0. */
+typedef struct revo_map_tsdf_ray_params {  /* 16 bytes; NULL: the defaults */
+  float step;               /* metres of camera depth between samples; 0: the map's voxel edge; else finite and > 0 */
+  uint32_t min_weight;      /* the views a cell needs, as revo_map_tsdf_mesh's; 0 counts as 1 */
+  uint32_t max_steps;       /* 1 .. 2^20: the samples of a ray at most; 0: 4096 */
+  uint32_t reserved;        /* zero */
+} revo_map_tsdf_ray_params;
+#define REVO_TSDF_RAY_HIT 0u
+#define REVO_TSDF_RAY_RANGE 1u
+#define REVO_TSDF_RAY_BACKFACE 2u
+#define REVO_TSDF_RAY_EXHAUSTED 3u
+typedef struct revo_map_tsdf_ray_info {    /* 64 bytes, little-endian, no padding: integer sums over the rays of a call */
+  uint64_t rays, hits, range, backface, exhausted;  /* rays = the sum of the four statuses */
+  uint64_t samples;         /* the samples of the march above whose place was formed (step 3): k + 1 for a ray that sample k
+                               ended (HIT, BACKFACE), k for a RANGE miss at sample k, max_steps for an EXHAUSTED ray -- not the
+                               samples a kernel happened to evaluate */
+  uint64_t uncolored;       /* the hits with k = 0; 0 when color is NULL */
+  uint64_t reserved;        /* zero */
+} revo_map_tsdf_ray_info;
+/* n views (1 .. 64, sizes may differ) of the surface in the volumes of `box` (revo_map_distance_field's box rules; tsdf a
+ * revo_map_tsdf_cell and color a revo_map_tsdf_color volume with revo_map_tsdf_mesh_attr's layout; device_tsdf: where both
+ * live, a host volume is uploaded).  m gives the context, the tracker stream and the voxel edge and is not changed; its voxels
+ * play no part.  color may be NULL when bgr is NULL; it is then not read.  Two launches on the tracker stream: one over the
+ * cells that marks the 8 x 8 x 8 blocks of sample bases near an inside cell, one that marches a ray per pixel and looks a
+ * sample's eight cells up only where that can decide the ray -- the outputs are those of the march above, byte for byte.
+ * depth[i] (h x w floats) is required; normal (h x w x 3 floats per view), bgr (h x w x 3 bytes per view, B, G, R), hits (n
+ * entries: the hit pixels of each view) and info (one record for the call) may be NULL, and normal[i] / bgr[i] follow their
+ * array.  device_out = 0: host pointers, the call waits.  device_out = 1: device pointers (every output, hits and info
+ * included, 16-byte aligned); with a device volume the call only enqueues.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, tsdf, views or depth, a NULL
+ * depth[i], normal[i] or bgr[i] of a given array; the box rules; n outside 1 .. 64; revo_map_render's view rules (size, pose,
+ * intrinsics, depth range); a step that is not finite or is negative; max_steps above 2^20; a reserved word that is not 0; a
+ * flag outside 0 / 1; a misaligned device pointer (volumes included); bgr without color. */
+int revo_map_tsdf_raycast(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, const revo_map_tsdf_color* color,
+                          int device_tsdf, int n, const revo_map_view* views, const revo_map_tsdf_ray_params* prm,
+                          float* const* depth, float* const* normal, uint8_t* const* bgr, uint32_t* hits, int device_out,
+                          revo_map_tsdf_ray_info* info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -189,6 +189,8 @@ def lib():
                                            C.c_int, vp, vp, vp]
     L.revo_map_tsdf_mesh_attr.argtypes = [vp, C.POINTER(MapDfBox), vp, vp, C.c_int, C.c_uint32, vp, vp, vp, C.c_size_t, vp, C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int, vp]
+    L.revo_map_tsdf_raycast.argtypes = [vp, C.POINTER(MapDfBox), vp, vp, C.c_int, C.c_int, vp, C.POINTER(MapTsdfRayParams), vpp, vpp, vpp, vp,
+                                        C.c_int, vp]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfRayInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1143,6 +1143,93 @@ class VoxelMap:
                                                      C.byref(nv), C.byref(nt), 1, C.byref(info)))
         return nv.value, nt.value, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS}
 
+    # -- views of the surface (revo_map_tsdf_raycast)
+    def _surface_views(self, poses, camera, size, zrange):
+        """-> (MapView array, n, single) for the poses (one 4x4 camera -> world pose, or a list / (n, 4, 4) array of 1 .. 64);
+        camera, size, zrange: see _gain_camera."""
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        T = T.reshape(-1, 4, 4)
+        if not 1 <= len(T) <= 64:
+            raise ValueError("a surface ray cast takes 1 .. 64 poses")
+        cam = self._gain_camera(camera, size, zrange, 1)
+        views = (MapView * len(T))()
+        for v, M in zip(views, T):
+            C.memmove(C.byref(v), C.byref(cam), C.sizeof(MapView))
+            v.T_w_c[:] = _cm4(M).tolist()
+        return views, len(T), single
+
+    @staticmethod
+    def _tsdf_ray_params(step, min_weight, max_steps):
+        if int(min_weight) < 0 or int(max_steps) < 0:
+            raise ValueError("min_weight and max_steps are >= 0")
+        return MapTsdfRayParams(0.0 if step is None else float(step), int(min_weight), int(max_steps), 0)
+
+    def surface_raycast(self, tsdf, poses, camera=None, size=None, zrange=None, step=None, min_weight=1, max_steps=4096, normals=True, colors=True):
+        """A TsdfVolume's surface seen from camera poses (revo_map_tsdf_raycast): one ray per pixel marched through the
+        fused field in steps of `step` metres of camera depth (default: the voxel edge), the surface found between two samples
+        from the trilinear interpolant.  -> dict: depth [h, w] float32 metres (0 = no surface on the ray), normals [h, w, 3]
+        float32 unit vectors in the world frame pointing out of the surface (None with normals=False), bgr [h, w, 3] uint8 (None
+        with colors=False), hits = the pixels with a depth, info = the call's counters (mapfile.TSDF_RAY_INFO_KEYS).  A list or
+        (n, 4, 4) array of 1 .. 64 poses is ONE library call and gives lists under depth, normals, bgr and hits.  camera, size,
+        zrange: see _gain_camera.  colors needs a volume fused with color=True.  The map's voxels play no part."""
+        from . import mapfile
+        if colors and tsdf.color is None:
+            raise ValueError("the volume has no colour: fuse it with color=True, or pass colors=False")
+        box, cells = self._tsdf_box(tsdf)
+        col = np.ascontiguousarray(tsdf.color) if colors else None
+        views, n, single = self._surface_views(poses, camera, size, zrange)
+        depth = [np.empty((v.height, v.width), np.float32) for v in views]
+        nrm = [np.empty((v.height, v.width, 3), np.float32) for v in views] if normals else None
+        bgr = [np.empty((v.height, v.width, 3), np.uint8) for v in views] if colors else None
+        hits, info = np.zeros(n, np.uint32), MapTsdfRayInfo()
+        ptrs = lambda arrays: (vp * n)(*[a.ctypes.data for a in arrays]) if arrays is not None else None  # noqa: E731
+        prm = self._tsdf_ray_params(step, min_weight, max_steps)
+        check(_lib.lib().revo_map_tsdf_raycast(self._h, C.byref(box), cells.ctypes.data_as(vp), col.ctypes.data_as(vp) if colors else None, 0, n,
+                                               views, C.byref(prm), ptrs(depth), ptrs(nrm), ptrs(bgr), hits.ctypes.data_as(vp), 0, C.byref(info)))
+        pick = (lambda a: None if a is None else a[0]) if single else (lambda a: a)
+        return {"depth": pick(depth), "normals": pick(nrm), "bgr": pick(bgr), "hits": int(hits[0]) if single else [int(x) for x in hits],
+                "info": {k: int(getattr(info, k)) for k in mapfile.TSDF_RAY_INFO_KEYS}}
+
+    def surface_raycast_into(self, d_depth, d_tsdf, lo, poses, camera=None, size=None, zrange=None, step=None, min_weight=1, max_steps=4096,
+                             d_normals=None, d_bgr=None, d_color=None, d_hits=None, d_info=None, wait=True):
+        """surface_raycast() between torch device tensors: d_tsdf int32 [n0, n1, n2, 2] as fuse_into leaves it and d_color int32
+        [n0, n1, n2, 4] (needed for d_bgr), d_depth float32 [n, h, w] (or [h, w] for one pose), d_normals float32 shaped like
+        d_depth + (3,) or None, d_bgr uint8 likewise or None, d_hits None or n 32-bit entries, d_info None or 64 bytes
+        (revo_map_tsdf_ray_info); contiguous, on the map's device, every view's part 16-byte aligned.  Only enqueued on the
+        context's tracker stream: wait=True returns when it is done, wait=False at once (sync() orders later reads)."""
+        if d_tsdf.dim() != 4 or d_tsdf.shape[3] != 2 or str(d_tsdf.dtype) != "torch.int32":
+            raise ValueError("d_tsdf must be an int32 tensor [n0, n1, n2, 2]")
+        if d_color is not None and (tuple(d_color.shape) != tuple(d_tsdf.shape[:3]) + (4,) or str(d_color.dtype) != "torch.int32"):
+            raise ValueError("d_color must be an int32 tensor [n0, n1, n2, 4] over d_tsdf's box")
+        if d_bgr is not None and d_color is None:
+            raise ValueError("d_bgr needs the colour volume d_color")
+        box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
+        views, n, single = self._surface_views(poses, camera, size, zrange)
+        h, w = views[0].height, views[0].width
+        shape = (h, w) if single else (n, h, w)
+        if tuple(d_depth.shape) != shape or any(t_ is not None and tuple(t_.shape) != shape + (3,) for t_ in (d_normals, d_bgr)):
+            raise ValueError("output tensors do not match the views")
+        if str(d_depth.dtype) != "torch.float32" or (d_normals is not None and str(d_normals.dtype) != "torch.float32") or \
+                (d_bgr is not None and str(d_bgr.dtype) != "torch.uint8"):
+            raise ValueError("d_depth and d_normals must be float32 and d_bgr uint8")
+        for t_ in (d_tsdf, d_color, d_depth, d_normals, d_bgr, d_hits, d_info):
+            if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                raise ValueError("the tensors must be contiguous device tensors")
+        if d_hits is not None and (d_hits.numel() != n or d_hits.element_size() != 4):
+            raise ValueError("d_hits needs n 32-bit entries")
+        if d_info is not None and d_info.numel() * d_info.element_size() != 64:
+            raise ValueError("d_info needs 64 bytes")
+        ptrs = lambda t_, per: (vp * n)(*[t_.data_ptr() + per * h * w * i for i in range(n)]) if t_ is not None else None  # noqa: E731
+        ptr = lambda t_: vp(t_.data_ptr()) if t_ is not None else None  # noqa: E731
+        import torch
+        torch.cuda.current_stream(d_depth.device).synchronize()  # the tensors' earlier use is over before the tracker stream touches them
+        prm = self._tsdf_ray_params(step, min_weight, max_steps)
+        check(_lib.lib().revo_map_tsdf_raycast(self._h, C.byref(box), ptr(d_tsdf), ptr(d_color), 1, n, views, C.byref(prm), ptrs(d_depth, 4),
+                                               ptrs(d_normals, 12), ptrs(d_bgr, 3), ptr(d_hits), 1, ptr(d_info)))
+        if wait:
+            self.sync()
+
     def frontiers(self, seen, min_views=1, min_count=1):
         """Where known space ends -> [k, 3] int32 voxel indices in ascending order of the cell's place in the box: the cells
         of a SeenVolume that are not solid, have >= min_views free votes and have a face neighbour inside the box that is
@@ -1684,6 +1771,28 @@ class TsdfVolume:
             return out
         return m.mesh(self, min_weight, normals, colors)
 
+    def raycast(self, poses, camera=None, size=None, step=None, min_weight=1, max_steps=4096, normals=True, colors=True, zrange=None, map=None):
+        """The surface seen from camera poses -> dict of depth, normals, bgr, hits and info (VoxelMap.surface_raycast),
+        on the device of the map the volume was fused with (or `map`).  colors=True needs a colour volume; a volume without one
+        gives bgr None.  A loaded volume without a map is ray-cast by mapfile.tsdf_raycast_records, which gives the same bytes;
+        it needs a camera (fx, fy, cx, cy), a size and a zrange."""
+        from . import mapfile
+        m = map if map is not None else self._map
+        colors = bool(colors) and self.color is not None
+        if m is not None:
+            return m.surface_raycast(self, poses, camera, size, zrange, step, min_weight, max_steps, normals, colors)
+        if camera is None or size is None or zrange is None:
+            raise ValueError("without a map the camera (fx, fy, cx, cy), the size and the zrange must be given")
+        if isinstance(camera, Camera):
+            camera = (camera.fx, camera.fy, camera.cx, camera.cy)
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        views = [(M, tuple(camera) + tuple(zrange), size) for M in T.reshape(-1, 4, 4)]
+        r = mapfile.tsdf_raycast_records(self.cells, self.color if colors else None, self.lo, self.voxel, views, step, min_weight, max_steps)
+        pick = (lambda a: a[0]) if single else (lambda a: a)
+        return {"depth": pick(r["depth"]), "normals": pick(r["normals"]) if normals else None, "bgr": pick(r["bgr"]) if colors else None,
+                "hits": pick(r["hits"]), "info": r["info"]}
+
     def save(self, path):
         """The .npz `python -m revo_amd.mapfile tsdf` writes: sum, weight, lo, n, voxel, trunc, and with a colour volume
         color_sum and color_weight."""
@@ -1762,6 +1871,37 @@ class SurfaceVolume:
         self.map.sync()
         return mapfile.Mesh(d_v[:nv].cpu().numpy(), d_t[:nt].cpu().numpy().view(np.uint32), info,
                             d_n[:nv].cpu().numpy() if normals else None, d_c[:nv].cpu().numpy() if colors else None)
+
+    def raycast(self, poses, camera=None, size=None, step=None, min_weight=1, max_steps=4096, normals=True, colors=True, zrange=None, device=False):
+        """The surface as it stands seen from camera poses (VoxelMap.surface_raycast_into on the device volumes): no
+        host copy of the volumes, the call is only enqueued behind the integrations.  -> dict of depth, normals, bgr, hits and
+        info as TsdfVolume.raycast gives them; device=True: the torch device tensors themselves (depth [n, h, w] or [h, w],
+        normals, bgr, hits int32 [n], info int64 [8] in mapfile.TSDF_RAY_INFO_KEYS' order), valid behind the map's sync()."""
+        import torch
+        from . import mapfile
+        colors = bool(colors) and self.d_color is not None
+        views, n, single = self.map._surface_views(poses, camera, size, zrange)
+        h, w = views[0].height, views[0].width
+        dev = self.d_tsdf.device
+        shape = (h, w) if single else (n, h, w)
+        if not single and (h * w) % 16:  # every view's part of a stacked tensor is 16-byte aligned
+            raise ValueError("several device views at once need a pixel count that is a multiple of 16")
+        d_depth = torch.empty(shape, dtype=torch.float32, device=dev)
+        d_nrm = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if normals else None
+        d_bgr = torch.empty(shape + (3,), dtype=torch.uint8, device=dev) if colors else None
+        d_hits = torch.zeros(max(n, 4), dtype=torch.int32, device=dev)[:n]
+        d_info = torch.zeros(8, dtype=torch.int64, device=dev)
+        self.map.surface_raycast_into(d_depth, self.d_tsdf, self.lo, poses, camera, size, zrange, step, min_weight, max_steps, d_normals=d_nrm,
+                                      d_bgr=d_bgr, d_color=self.d_color if colors else None, d_hits=d_hits, d_info=d_info, wait=False)
+        if device:
+            return {"depth": d_depth, "normals": d_nrm, "bgr": d_bgr, "hits": d_hits, "info": d_info}
+        self.map.sync()
+        host = lambda t_: None if t_ is None else t_.cpu().numpy()  # noqa: E731
+        split = (lambda a: a) if single else (lambda a: None if a is None else list(a))
+        hits, info = d_hits.cpu().numpy(), d_info.cpu().numpy()
+        return {"depth": split(host(d_depth)), "normals": split(host(d_nrm)), "bgr": split(host(d_bgr)),
+                "hits": int(hits[0]) if single else [int(x) for x in hits],
+                "info": {k: int(info[i]) for i, k in enumerate(mapfile.TSDF_RAY_INFO_KEYS)}}
 
 
 def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
@@ -2098,6 +2238,13 @@ class MapWindow:
 
     def mesh_into(self, *args, **kw):
         return self.map.mesh_into(*args, **kw)
+
+    def surface_raycast(self, *args, **kw):
+        """The inner map's surface_raycast: views of a TsdfVolume's surface (the window's voxels play no part)."""
+        return self.map.surface_raycast(*args, **kw)
+
+    def surface_raycast_into(self, *args, **kw):
+        return self.map.surface_raycast_into(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

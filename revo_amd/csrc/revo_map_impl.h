@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -279,6 +279,7 @@ struct MapRayView {  // one view of a launch, in device memory
   float* depth; uint8_t* bgr; u64* key; unsigned* hits;  // bgr, key: NULL when not asked for
 };
 struct MapDfPose;   // revo_map_df_align.hip: one pose of a registration launch
+struct TsdfRayView; // revo_map_tsdf_ray.hip: one view of a surface ray cast
 
 struct revo_map {
   revo_ctx* ctx = nullptr;
@@ -335,6 +336,10 @@ struct revo_map {
   // revo_map_tsdf_fuse_color / revo_map_tsdf_mesh_attr: the views' colour images, the device copy of a host colour volume
   HostRows<const uint8_t*> tsdf_bgr;
   DevBuf tsdfcol;
+  // revo_map_tsdf_raycast (revo_map_tsdf_ray.hip): the counter lines and the block mask, the views' descriptors, the device outputs
+  // of a host-output call; a host volume goes through tsdfvol and tsdfcol
+  DevBuf tsdfraywork, tsdfrayout;
+  HostRows<TsdfRayView> tsdfray_views;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every

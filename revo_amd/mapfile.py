@@ -1400,6 +1400,153 @@ def tsdf_file(path, views_dir, camera, zrange, depth_scale=5000.0, pad=0, trunc=
     return out + (col,) if color else out
 
 
+# -------------------------------------------------------------------------------- views of the surface --
+TSDF_RAY_STATUS = ("hit", "range", "backface", "exhausted")
+TSDF_RAY_INFO_KEYS = ("rays", "hits", "range", "backface", "exhausted", "samples", "uncolored")
+TSDF_RAY_MAX_STEPS = 1 << 20
+
+
+def tsdf_ray_params(voxel, step=None, min_weight=1, max_steps=4096):
+    """The parameters a surface ray cast runs with, checked as revo_map_tsdf_raycast checks them -> (step float32, min_weight,
+    max_steps): step None or 0 is the voxel edge, min_weight 0 counts as 1, max_steps 0 is 4096."""
+    v = np.float32(voxel)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError("the voxel edge must be finite and > 0")
+    st = np.float32(0 if step is None else step)
+    if not np.isfinite(st) or st < 0:
+        raise ValueError("step must be finite and >= 0 (0: the voxel edge)")
+    if not 0 <= int(max_steps) <= TSDF_RAY_MAX_STEPS:
+        raise ValueError("max_steps must be 0 (4096) or 1 .. 2^20")
+    if not 0 <= int(min_weight) < 1 << 32:
+        raise ValueError("min_weight is a number of views >= 0")
+    return (v if st == 0 else st), max(1, int(min_weight)), int(max_steps) or 4096
+
+
+def _tsdf_ray_march(f, valid, lo, voxel, o, d, zmin, zmax, step, max_steps):
+    """The plain march of revo_map_tsdf_raycast (include/revo_hip.h) for the N rays of one view at once, float32
+    operation by operation: every ray still under way takes sample k in iteration k.  f, valid: the field and the validity of
+    the cells; o, d [N, 3] float32.  -> dict of [N] arrays: status, k (the sample that ended the ray), and for the hits a, sp
+    (the previous sample's depth), gp, g ([N, 3]: the two gradients), c0, c1 (the two colour cells' places)."""
+    f32 = np.float32
+    n = len(o)
+    nx, ny, nz = f.shape
+    ff, vv = f.reshape(-1), valid.reshape(-1)
+    last = ff.size - 1
+    out = {"status": np.full(n, 3, np.int64), "k": np.full(n, int(max_steps), np.int64), "a": np.zeros(n, f32), "sp": np.zeros(n, f32),
+           "gp": np.zeros((n, 3), f32), "g": np.zeros((n, 3), f32), "c0": np.zeros(n, np.int64), "c1": np.zeros(n, np.int64)}
+    centre = np.asarray(lo, np.int64).astype(f32) + f32(0.5)
+    top = (np.asarray(f.shape, np.int64) - 2).astype(f32)
+    offs = {(dx, dy, dz): (dx * ny + dy) * nz + dz for dx in (0, 1) for dy in (0, 1) for dz in (0, 1)}
+    L = lambda x0, x1, a: x0 + a * (x1 - x0)  # noqa: E731
+    B = lambda v00, v01, v10, v11, r0, r1: L(L(v00, v01, r0), L(v10, v11, r0), r1)  # noqa: E731
+    idx = np.arange(n)
+    pv, pF, pS, pG, pC = np.zeros(n, bool), np.zeros(n, f32), np.zeros(n, f32), np.zeros((n, 3), f32), np.zeros(n, np.int64)
+    with np.errstate(all="ignore"):
+        for k in range(int(max_steps)):
+            if not len(idx):
+                break
+            s = f32(zmin + f32(k) * step)
+            if not s < zmax:  # every ray of a view shares its samples' depths
+                out["status"][idx], out["k"][idx] = 1, k
+                break
+            g = o[idx] + s * d[idx]
+            u = g / voxel - centre
+            b = np.floor(u)
+            r = (u - b).astype(f32)
+            inbox = np.all(np.isfinite(u) & (b >= 0) & (b <= top), 1)
+            bi = np.where(inbox[:, None], b, 0).astype(np.int64)
+            c = (bi[:, 0] * ny + bi[:, 1]) * nz + bi[:, 2]
+            at = {key: np.minimum(c + off, last) for key, off in offs.items()}
+            val = inbox.copy()
+            for a_ in at.values():
+                val &= vv[a_]
+            q = {key: ff[a_] for key, a_ in at.items()}
+            rx, ry, rz = r[:, 0], r[:, 1], r[:, 2]
+            F = L(B(q[0, 0, 0], q[0, 0, 1], q[0, 1, 0], q[0, 1, 1], rz, ry), B(q[1, 0, 0], q[1, 0, 1], q[1, 1, 0], q[1, 1, 1], rz, ry), rx)
+            G = np.stack([B(q[1, 0, 0] - q[0, 0, 0], q[1, 0, 1] - q[0, 0, 1], q[1, 1, 0] - q[0, 1, 0], q[1, 1, 1] - q[0, 1, 1], rz, ry),
+                          B(q[0, 1, 0] - q[0, 0, 0], q[0, 1, 1] - q[0, 0, 1], q[1, 1, 0] - q[1, 0, 0], q[1, 1, 1] - q[1, 0, 1], rz, rx),
+                          B(q[0, 0, 1] - q[0, 0, 0], q[0, 1, 1] - q[0, 1, 0], q[1, 0, 1] - q[1, 0, 0], q[1, 1, 1] - q[1, 1, 0], ry, rx)], 1).astype(f32)
+            near = bi + (r >= f32(0.5))
+            cc = (near[:, 0] * ny + near[:, 1]) * nz + near[:, 2]
+            both = val & pv
+            hit = both & (pF >= 0) & (F < 0)
+            back = both & (pF < 0) & (F >= 0)
+            h = idx[hit]
+            out["status"][h], out["k"][h] = 0, k
+            out["a"][h] = pF[hit] / (pF[hit] - F[hit])
+            out["sp"][h], out["gp"][h], out["g"][h], out["c0"][h], out["c1"][h] = pS[hit], pG[hit], G[hit], pC[hit], cc[hit]
+            out["status"][idx[back]], out["k"][idx[back]] = 2, k
+            go = ~(hit | back)
+            idx, pv, pF, pS, pG, pC = idx[go], val[go], F[go].astype(f32), np.full(int(go.sum()), s, f32), G[go], cc[go]
+    return out
+
+
+def tsdf_raycast_records(tsdf, color, lo, voxel, views, step=None, min_weight=1, max_steps=4096):
+    """Depth, normal and colour views of a TSDF volume without a GPU: revo_map_tsdf_raycast's contract in vectorised
+    numpy.  tsdf: the volume; color: the colour volume or None (then no bgr comes back and uncolored is 0); lo: the box's first
+    voxel index; views: a list of (T_w_c, (fx, fy, cx, cy, zmin, zmax), (width, height)), 1 .. 64.  -> a dict of per-view lists
+    depth ([h, w] float32, 0 = miss), normals ([h, w, 3] float32), bgr ([h, w, 3] uint8, or None without a colour volume), hits,
+    and -- beyond what the library returns -- status ([h, w]: the index into TSDF_RAY_STATUS), samples ([h, w]: the samples the
+    ray counts) and colored ([h, w]: a hit's k), plus info: the call's TSDF_RAY_INFO_KEYS sums.  ValueError as the library's
+    REVO_ERR_INVALID_ARG."""
+    f32 = np.float32
+    cells = _tsdf_volume(tsdf)
+    lo, _ = check_box(lo, np.asarray(cells.shape, np.int64))
+    if color is not None:
+        color = _tsdf_color_volume(color, cells.shape)
+    st, mw, ms = tsdf_ray_params(voxel, step, min_weight, max_steps)
+    views = list(views)
+    if not 1 <= len(views) <= 64:
+        raise ValueError("a ray cast takes 1 .. 64 views")
+    views = [ray_view(*vw) for vw in views]
+    voxel = f32(voxel)
+    valid = cells["weight"] >= mw
+    with np.errstate(all="ignore"):
+        f = np.where(valid, cells["sum"].astype(f32) / cells["weight"].astype(f32), f32(0)).astype(f32)
+        if color is not None:
+            cw = color["weight"].reshape(-1)
+            mean = [(color[name].astype(f32) / color["weight"].astype(f32)).astype(f32).reshape(-1) for name in ("sum_b", "sum_g", "sum_r")]
+    out = {k: [] for k in ("depth", "normals", "bgr", "hits", "status", "samples", "colored")}
+    total = dict.fromkeys(TSDF_RAY_INFO_KEYS, 0)
+    for vw in views:
+        w, h = vw[5]
+        o, _, d, _ = ray_view_rays(vw)
+        m = _tsdf_ray_march(f, valid, lo, voxel, o, d, vw[4][4], vw[4][5], st, ms)
+        status, k, a = m["status"], m["k"], m["a"]
+        got = status == 0
+        samples = np.where(got | (status == 2), k + 1, k)
+        with np.errstate(all="ignore"):
+            depth = np.where(got, m["sp"] + a * st, f32(0)).astype(f32)
+            g = (m["gp"] + a[:, None] * (m["g"] - m["gp"])).astype(f32)
+            l2 = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
+            ok = got & np.isfinite(l2) & (l2 > 0)
+            normals = np.where(ok[:, None], g / np.sqrt(l2)[:, None], f32(0)).astype(f32)
+            colored = np.zeros(len(a), np.int64)
+            bgr = None
+            if color is not None:
+                w0, w1 = cw[m["c0"]], cw[m["c1"]]
+                bgr = np.zeros((len(a), 3), np.uint8)
+                for ch in range(3):
+                    m0, m1 = mean[ch][m["c0"]], mean[ch][m["c1"]]
+                    v = np.where((w0 > 0) & (w1 > 0), m0 + a * (m1 - m0), np.where(w0 > 0, m0, np.where(w1 > 0, m1, f32(0)))).astype(f32)
+                    bgr[:, ch] = np.where(got, np.rint(np.minimum(np.maximum(v, f32(0)), f32(255))), 0).astype(np.uint8)
+                colored = np.where(got, (w0 > 0).astype(np.int64) + (w1 > 0).astype(np.int64), 0)
+        out["depth"].append(depth.reshape(h, w))
+        out["normals"].append(normals.reshape(h, w, 3))
+        out["bgr"].append(None if bgr is None else bgr.reshape(h, w, 3))
+        out["hits"].append(int(got.sum()))
+        out["status"].append(status.reshape(h, w))
+        out["samples"].append(samples.reshape(h, w))
+        out["colored"].append(colored.reshape(h, w))
+        for i, name in enumerate(TSDF_RAY_STATUS):
+            total[name if name != "hit" else "hits"] += int((status == i).sum())
+        total["rays"] += len(status)
+        total["samples"] += int(samples.sum())
+        total["uncolored"] += int((got & (colored == 0)).sum()) if color is not None else 0
+    out["info"] = total
+    return out
+
+
 def df_sample(d2, lo, voxel, points):
     """revo_map_df_sample restated: a DF_SAMPLE_DTYPE array, one entry per point ([N, 3] float32 metres).  All arithmetic is
     float32, every operation rounded on its own.  dist -1: outside the box (or not finite); +inf: the cell holds DF_NONE."""
@@ -2194,6 +2341,31 @@ def main(argv=None):
                 print("%s: %d vertices, %d triangles from %d active cubes of %s" % (val["-o"][0], len(m.vertices), len(m.triangles),
                                                                                    m.info["cubes_active"], pos[0]))
                 return 0
+        if cmd == "surface-views" and "-o" in args and "--poses" in args:
+            opt = {"-o": 1, "--poses": 1, "--camera": 4, "--size": 2, "--zrange": 2, "--step": 1, "--min-weight": 1, "--max-steps": 1, "--depth-scale": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            with_normals = "--normals" in pos
+            pos = [a for a in pos if a != "--normals"]
+            if len(pos) == 1 and "--camera" in val and "--size" in val:
+                from . import api, tum
+                vol = api.TsdfVolume.load(pos[0])
+                poses = [(float(j), T) for j, T in enumerate(read_poses(val["--poses"][0]))]  # the time stamps: the poses' numbers
+                n = tum.write_surface_views(val["-o"][0], vol, poses, depth_scale=float(val.get("--depth-scale", [5000.0])[0]), batch=64,
+                                            normals=with_normals, camera=[float(x) for x in val["--camera"]], size=[int(x) for x in val["--size"]],
+                                            zrange=[float(x) for x in val.get("--zrange", (0.1, 5.2))],
+                                            step=float(val["--step"][0]) if "--step" in val else None, min_weight=int(val.get("--min-weight", [1])[0]),
+                                            max_steps=int(val.get("--max-steps", [4096])[0]))
+                print("%s: %d views of the surface in %s (%s colour%s)" % (val["-o"][0], n, pos[0], "with" if vol.color is not None else "without",
+                                                                           ", normals" if with_normals else ""))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -2218,6 +2390,8 @@ def main(argv=None):
           "[--weight W] [--up X Y Z] [the options of gain] -o POSE.txt | "
           "tsdf A --views DIR -o TSDF.npz [--color] [--trunc M] [--pad N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
           "mesh TSDF.npz -o MESH.ply [--min-weight K] [--normals] [--colors] | "
+          "surface-views TSDF.npz --poses POSES.txt --camera FX FY CX CY --size W H [--zrange ZMIN ZMAX] [--step M] [--min-weight K] [--max-steps N] "
+          "[--depth-scale S] [--normals] -o DIR | "
           "ply FILE [OUT.ply]")
     return 2
 

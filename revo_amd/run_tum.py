@@ -35,6 +35,10 @@ at the end.  --surface-box I0 J0 K0 N0 N1 N2 is the box in voxel indices of the 
 before the run (default -128 -128 -32 256 256 256); surfaces outside it are not there, and the keyframes that confirm no cell of
 it are counted on stderr.  --surface-trunc M: the truncation distance in metres (default 4 voxel edges); --surface-min-weight K:
 the views a cell needs.  An error with --map-window and with --streams.  The pose file does not depend on it.
+--surface-views DIR (with --surface) ray-casts the finished surface from the estimated pose of every keyframe, or with
+--surface-views-every K of every K-th tracked frame, on the GPU (api.SurfaceVolume.raycast, DESIGN 28: depth and colour from the
+sign change of the fused field, sub-voxel accurate and without holes) and writes the TUM-layout data set that --map-views writes
+(tum.write_surface_views: rgb/, depth/, associate.txt, poses.txt) into DIR; DIR/<dataset>/ with more than one dataset.
 --covariances writes cov_<dataset>.txt next to the pose file, one line per pose line in the same order: the frame's time stamp,
 its keyframe's time stamp, the good-point count, sigma2 and the 21 upper-triangle entries (row-major) of the 6x6 covariance of the
 relative pose frame -> keyframe (api.pair_covariance of the level-0 settings.PairInfo at the final pose; translation 0-2,
@@ -51,7 +55,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -167,6 +171,24 @@ def main(argv=None):
         if not (np.isfinite(map_carve.get("margin", 0.0)) and map_carve.get("margin", 0.0) >= 0) or map_carve.get("min_views", 1) < 1:
             print("--map-carve-margin needs a margin >= 0 in metres, --map-carve-views a positive number of views")
             return 2
+    sviews_dir, sviews_every = None, 0  # tum.write_surface_views of the finished surface: every keyframe's pose, or every K-th frame's
+    if "--surface-views-every" in argv:
+        i = argv.index("--surface-views-every")
+        sviews_every = int(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
+        if sviews_every < 1:
+            print("--surface-views-every needs a positive number of frames")
+            return 2
+    if "--surface-views" in argv:
+        i = argv.index("--surface-views")
+        sviews_dir = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+    if sviews_every and sviews_dir is None:
+        print("--surface-views-every needs --surface-views DIR")
+        return 2
+    if sviews_dir is not None and "--surface" not in argv:
+        print("--surface-views ray-casts the TSDF surface: it needs --surface FILE.ply")
+        return 2
     surface = None  # vo.REVO's surface: the coloured, shaded mesh of the keyframes' TSDF volume, written at the end of the run
     for opt, key, k, conv in (("--surface", "file", 1, str), ("--surface-box", "box", 6, int), ("--surface-trunc", "trunc", 1, float),
                               ("--surface-min-weight", "min_weight", 1, int)):
@@ -279,6 +301,9 @@ def main(argv=None):
                           % drv.carve_skipped) if drv.carve_skipped else ""))
             if surf is not None:
                 _save_surface(surf, drv, surface, name, len(io["datasets"]) > 1)
+                if sviews_dir is not None:
+                    _save_surface_views(surf, os.path.join(sviews_dir, name) if len(io["datasets"]) > 1 else sviews_dir, drv.poses,
+                                        [kf for _, kf in res], sviews_every, io["depth_scale_factor"], surface.get("min_weight", 1))
             if map_window:
                 with open("map_window_%s.txt" % name, "w") as f:
                     for ts, T in zip(vmap.timestamps, vmap.keyframes):
@@ -365,6 +390,14 @@ def _save_views(vmap, folder, poses, is_kf, every, depth_scale, raycast=False):
     sel = poses[::every] if every else [p for p, kf in zip(poses, is_kf) if kf]
     n = tum.write_map_views(folder, vmap, sel, depth_scale=depth_scale, raycast=raycast)
     print("Map views: %d views (%s%s) -> %s" % (n, ("every %d frames" % every) if every else "one per keyframe", ", ray-cast" if raycast else "", folder))
+
+
+def _save_surface_views(surf, folder, poses, is_kf, every, depth_scale, min_weight):
+    """--surface-views: the finished surface from the pose of every keyframe (every == 0) or of every `every`-th tracked frame."""
+    from . import tum
+    sel = poses[::every] if every else [p for p, kf in zip(poses, is_kf) if kf]
+    n = tum.write_surface_views(folder, surf, sel, depth_scale=depth_scale, min_weight=min_weight)
+    print("Surface views: %d views (%s) -> %s" % (n, ("every %d frames" % every) if every else "one per keyframe", folder))
 
 
 def _report_ate(folder, poses):

@@ -416,6 +416,20 @@ class MapTsdfColorInfo(C.Structure):
 assert (C.sizeof(MapTsdfColor), C.sizeof(MapTsdfColorInfo)) == (16, 32)
 
 
+class MapTsdfRayParams(C.Structure):
+    """revo_map_tsdf_ray_params (include/revo_hip.h), 16 bytes: the step in metres of camera depth (0: the voxel edge), the views a
+    cell needs (0 counts as 1) and the samples of a ray at most (0: 4096)."""
+    _fields_ = [("step", C.c_float), ("min_weight", C.c_uint32), ("max_steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MapTsdfRayInfo(C.Structure):
+    """revo_map_tsdf_ray_info (include/revo_hip.h), 64 bytes: integer sums over the rays of a surface ray cast."""
+    _fields_ = [(k, C.c_uint64) for k in ("rays", "hits", "range", "backface", "exhausted", "samples", "uncolored", "reserved")]
+
+
+assert (C.sizeof(MapTsdfRayParams), C.sizeof(MapTsdfRayInfo)) == (16, 64)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

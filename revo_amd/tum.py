@@ -430,35 +430,59 @@ def read_poses(path):
     return out
 
 
-def write_map_views(folder, vmap, poses, depth_scale=5000.0, batch=16, splat_max=4, min_count=1, raycast=False):
-    """Renders the voxel map `vmap` (api.VoxelMap.render, or with raycast=True api.VoxelMap.raycast: the ray march in place of
-    the splat, no footprint and no holes; `batch` views per library call) from `poses` [(timestamp, 4x4 camera -> world)] and writes a TUM-layout data set: rgb/<ts>.png (8-bit colour), depth/<ts>.png (16-bit: metres x
-    depth_scale, rounded to nearest, saturated at 65535, 0 = nothing there), associate.txt, and poses.txt in the pose
-    file's format (vo.tum_lines).  The views are rendered from the poses as poses.txt states them (read_poses), so the
-    folder describes itself: read_associate / load_frame / read_poses give back what was rendered.  -> number of views."""
+def write_views(folder, poses, render, depth_scale=5000.0, batch=16, what="the voxel map", normals=False):
+    """Writes views rendered from `poses` [(timestamp, 4x4 camera -> world)] as a TUM-layout data set: rgb/<ts>.png (8-bit
+    colour), depth/<ts>.png (16-bit: metres x depth_scale, rounded to nearest, saturated at 65535, 0 = nothing there),
+    associate.txt, and poses.txt in the pose file's format (vo.tum_lines).  render(list of poses) -> (depth images, bgr images)
+    or, with normals=True, (depth, bgr, normal images); the normals go to normals/<ts>.npy ([h, w, 3] float32).  The views are
+    rendered from the poses as poses.txt states them (read_poses), so the folder describes itself: read_associate / load_frame /
+    read_poses give back what was rendered.  -> number of views."""
     from PIL import Image
     from . import vo
     os.makedirs(os.path.join(folder, "rgb"), exist_ok=True)
     os.makedirs(os.path.join(folder, "depth"), exist_ok=True)
+    if normals:
+        os.makedirs(os.path.join(folder, "normals"), exist_ok=True)
     pose_file = os.path.join(folder, "poses.txt")
     with open(pose_file, "w") as f:
         f.write("".join(line + "\n" for line in vo.tum_lines(poses)))
     poses = read_poses(pose_file)
     with open(os.path.join(folder, "associate.txt"), "w") as fa:
-        fa.write("# rgb depth (views of the voxel map at the poses of poses.txt)\n")
+        fa.write("# rgb depth (views of %s at the poses of poses.txt)\n" % what)
         for i in range(0, len(poses), batch):
             part = poses[i:i + batch]
-            if raycast:
-                depth, bgr, _ = vmap.raycast([T for _, T in part], min_count=min_count)
-            else:
-                depth, bgr, _ = vmap.render([T for _, T in part], splat_max=splat_max, min_count=min_count)
-            for (ts, _), d, c in zip(part, depth, bgr):
+            out = render([T for _, T in part])
+            for j, ((ts, _), d, c) in enumerate(zip(part, out[0], out[1])):
                 name = "%.6f.png" % ts
                 Image.fromarray(np.ascontiguousarray(c[..., ::-1])).save(os.path.join(folder, "rgb", name))
                 raw = np.clip(np.rint(d.astype(np.float64) * depth_scale), 0, 65535).astype(np.uint16)
                 Image.fromarray(raw).save(os.path.join(folder, "depth", name))
+                if normals:
+                    np.save(os.path.join(folder, "normals", "%.6f.npy" % ts), np.ascontiguousarray(out[2][j], np.float32))
                 fa.write("%.6f rgb/%s %.6f depth/%s\n" % (ts, name, ts, name))
     return len(poses)
+
+
+def write_map_views(folder, vmap, poses, depth_scale=5000.0, batch=16, splat_max=4, min_count=1, raycast=False):
+    """Renders the voxel map `vmap` (api.VoxelMap.render, or with raycast=True api.VoxelMap.raycast: the ray march in place of
+    the splat, no footprint and no holes; `batch` views per library call) from `poses` [(timestamp, 4x4 camera -> world)] and
+    writes the TUM-layout data set of write_views.  -> number of views."""
+    def render(Ts):
+        if raycast:
+            return vmap.raycast(Ts, min_count=min_count)[:2]
+        return vmap.render(Ts, splat_max=splat_max, min_count=min_count)[:2]
+    return write_views(folder, poses, render, depth_scale, batch)
+
+
+def write_surface_views(folder, surface, poses, depth_scale=5000.0, batch=16, normals=False, **ray_kw):
+    """Ray-casts a surface -- anything with TsdfVolume.raycast's call: an api.TsdfVolume, an api.SurfaceVolume -- from `poses`
+    (revo_map_tsdf_raycast) and writes the TUM-layout data set of write_views; a pixel without colour is black.
+    ray_kw: raycast's camera, size, zrange, step, min_weight, max_steps.  -> number of views."""
+    def render(Ts):
+        r = surface.raycast(Ts, normals=normals, colors=True, **ray_kw)
+        bgr = r["bgr"] if r["bgr"] is not None else [np.zeros(d.shape + (3,), np.uint8) for d in r["depth"]]
+        return r["depth"], bgr, r["normals"]
+    return write_views(folder, poses, render, depth_scale, batch, what="the TSDF surface", normals=normals)
 
 
 def read_groundtruth_positions(path):
