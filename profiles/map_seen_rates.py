@@ -7,8 +7,9 @@ boxes of 64^3, 128^3 and 256^3 cells around the map's median voxel; 3 warm-up ca
   1. revo_map_observe with 1 and with 8 views (the four views twice), images and volume on the device: a host clock around
      one call and the wait for the stream; beside it the bytes the call must move -- one byte per cell out, the depth images
      in -- and what share of the 8 TB/s HBM peak moving only those would be;
-  2. revo_map_known_field beside revo_map_distance_field on the same boxes: device time through
-     revo_map_distance_field_last_ms (HIP events from the first memset to the end of the last pass), device outputs;
+  2. revo_map_known_field beside revo_map_distance_field on the same boxes, device outputs: a host clock around one call
+     and the wait for the stream for both (revo_map_distance_field_last_ms describes revo_map_distance_field alone), and
+     beside it the plain field's device time through that call;
   3. revo_map_frontiers, volume and records on the device: a host clock around the counting call and the writing call.
 
     python profiles/map_seen_rates.py [--reps 10] [--commit TEXT] [--out profiles/map_seen_rates.txt]
@@ -78,21 +79,15 @@ def main():
         m.observe_into(d, views, lo)
         volumes[name] = d
 
-    say("\n2. revo_map_known_field beside revo_map_distance_field (device time, HIP events; device outputs)")
-    say("%-14s %10s %8s %10s %12s %16s %16s" % ("box", "cells", "solid", "unknown", "known free", "plain median ms", "known median ms"))
+    say("\n2. revo_map_known_field beside revo_map_distance_field (host clock around the call and its wait; device outputs)")
+    say("%-14s %10s %8s %10s %12s %16s %16s %16s" % ("box", "cells", "solid", "unknown", "known free", "plain median ms", "known median ms", "plain device ms"))
     for name, lo, n in boxes:
         d2 = torch.empty(n, dtype=torch.int32, device="cuda")
-        plain, known = [], []
-        for r in range(3 + a.reps):
-            m.distance_field_into(d2, lo, n, wait=False)
-            t = m.last_distance_field_ms()
-            m.known_field_into(d2, volumes[name], lo, n, d_info=d_info, wait=False)
-            u = m.last_distance_field_ms()
-            if r >= 3:
-                plain.append(t)
-                known.append(u)
+        plain = clock(lambda: m.distance_field_into(d2, lo, n))[0]
+        device = m.last_distance_field_ms()
+        known = clock(lambda: m.known_field_into(d2, volumes[name], lo, n, d_info=d_info))[0]
         i = d_info.cpu().numpy()
-        say("%-14s %10d %8d %10d %12d %16.3f %16.3f" % (name, n[0] * n[1] * n[2], i[1], i[5], i[6], float(np.median(plain)), float(np.median(known))))
+        say("%-14s %10d %8d %10d %12d %16.3f %16.3f %16.3f" % (name, n[0] * n[1] * n[2], i[1], i[5], i[6], plain, known, device))
 
     say("\n3. revo_map_frontiers, volume and records on the device (host clock: the counting call, then the writing call)")
     say("%-14s %10s %12s %10s %10s" % ("box", "cells", "frontiers", "median ms", "best ms"))

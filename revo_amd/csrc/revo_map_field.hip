@@ -314,9 +314,10 @@ int map_df_solid_bits(revo_map* m, const revo_map_df_box* box, uint32_t min_coun
 }
 
 // The field of the box over the solid voxels and, with d_seen (the box's seen volume in device memory), the unknown cells
-// too: the body of revo_map_distance_field and revo_map_known_field behind their argument checks.
+// too: the body of revo_map_distance_field and revo_map_known_field behind their argument checks.  timer: the handle's df_time
+// for revo_map_distance_field, which owns it (revo_map_distance_field_last_ms describes its last call); NULL for the known field.
 static int df_run(revo_map* m, const revo_map_df_box* box, size_t cells, uint32_t min_count, uint32_t clamp, const uint8_t* d_seen,
-                  uint32_t min_views, uint32_t* d2, int device_out, void* info, bool wait) {
+                  uint32_t min_views, uint32_t* d2, int device_out, void* info, bool wait, EventTimer* timer) {
   hipStream_t s = (hipStream_t)m->g.stream;
   const revo_map_df_box b = *box;
   const unsigned lines = (unsigned)b.n[0] * (unsigned)b.n[1];
@@ -325,7 +326,7 @@ static int df_run(revo_map* m, const revo_map_df_box* box, size_t cells, uint32_
   TRY(m->dfout.reserve(device_out ? 0 : sizeof(unsigned) * cells, s));
   unsigned* d_out = device_out ? d2 : (unsigned*)m->dfout.p;
   u64* d_info = device_out && info ? (u64*)info : (u64*)m->dfcnt.p;
-  TRY(m->df_time.begin(s));
+  if (timer) TRY(timer->begin(s));
   const unsigned* bits = nullptr;
   unsigned wz = 0;
   TRY(map_df_solid_bits(m, box, min_count, s, &bits, &wz, d_info));
@@ -339,7 +340,7 @@ static int df_run(revo_map* m, const revo_map_df_box* box, size_t cells, uint32_
   HIPCHECK(hipGetLastError());
   df_launch_pass<true>(s, d_out, 1, b.n[0], (unsigned)b.n[1] * (unsigned)b.n[2], clamp, d_info);
   HIPCHECK(hipGetLastError());
-  TRY(m->df_time.end(s));
+  if (timer) TRY(timer->end(s));
   if (!device_out) {
     HIPCHECK(hipMemcpyAsync(d2, d_out, sizeof(unsigned) * cells, hipMemcpyDeviceToHost, s));
     if (info) HIPCHECK(hipMemcpyAsync(info, d_info, sizeof(revo_map_df_info), hipMemcpyDeviceToHost, s));
@@ -356,7 +357,7 @@ extern "C" int revo_map_distance_field(revo_map* m, const revo_map_df_box* box, 
   TRY(map_check_side(device_out, "device_out"));
   if (device_out) TRY(map_check_aligned((uintptr_t)d2 | (uintptr_t)info, 16, "a device output is"));
   HIPCHECK(hipSetDevice(m->g.device));
-  return df_run(m, box, cells, min_count, clamp, nullptr, 0, d2, device_out, info, !device_out);
+  return df_run(m, box, cells, min_count, clamp, nullptr, 0, d2, device_out, info, !device_out, &m->df_time);
 }
 
 extern "C" int revo_map_known_field(revo_map* m, const revo_map_df_box* box, uint32_t min_count, uint32_t clamp, const uint8_t* seen,
@@ -376,7 +377,7 @@ extern "C" int revo_map_known_field(revo_map* m, const revo_map_df_box* box, uin
     HIPCHECK(hipMemcpyAsync(m->seenvol.p, seen, cells, hipMemcpyHostToDevice, s));
     d_seen = (const uint8_t*)m->seenvol.p;
   }
-  return df_run(m, box, cells, min_count, clamp, d_seen, min_views, d2, device_out, info, !device_out || !device_seen);
+  return df_run(m, box, cells, min_count, clamp, d_seen, min_views, d2, device_out, info, !device_out || !device_seen, nullptr);
 }
 
 extern "C" int revo_map_distance_field_last_ms(revo_map* m, float* ms) {

@@ -365,13 +365,15 @@ static int ray_reserve(revo_map* m, int n_views, size_t out_bytes) {
 }
 
 // What both entry points share: the first event, the block table of the map as it is on the stream, the cleared counters.
+// timer: the handle's ray_time for revo_map_raycast and revo_map_cast_rays, which own it; NULL for the march of another feature
+// (map_ray_open), so that revo_map_raycast_last_ms keeps describing the last ray cast, or refuses where there was none.
 // REVO_MAP_RAYCAST_BLOCKS=0: no block table, every cell is looked up (the exactness test and profiles/map_raycast_rates.py).
-static int ray_begin(revo_map* m, MapRayK* a, u64 min_count, unsigned max_steps, u64* d_info, unsigned* d_hits, int n_hits) {
+static int ray_begin(revo_map* m, MapRayK* a, u64 min_count, unsigned max_steps, u64* d_info, unsigned* d_hits, int n_hits, EventTimer* timer) {
   hipStream_t s = (hipStream_t)m->g.stream;
   a->keys = m->d_keys; a->vals = m->d_vals; a->mask = (unsigned)(m->cap - 1);
   a->min_count = min_count; a->max_steps = max_steps; a->voxel = m->voxel;
   a->info = d_info;
-  TRY(m->ray_time.begin(s));
+  if (timer) TRY(timer->begin(s));
   a->bkeys = nullptr; a->bmask = 0;
   if (env_int("REVO_MAP_RAYCAST_BLOCKS", 1, 0, 1)) {
     u64* bkeys = (u64*)m->bkeys.p;
@@ -390,13 +392,13 @@ static int ray_begin(revo_map* m, MapRayK* a, u64 min_count, unsigned max_steps,
 // written to device memory.
 int map_ray_open(revo_map* m, MapRayK* a, uint32_t min_count, uint32_t max_steps, u64* d_info) {
   TRY(m->bkeys.reserve(sizeof(u64) * m->cap, (hipStream_t)m->g.stream));
-  return ray_begin(m, a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0);
+  return ray_begin(m, a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0, nullptr);
 }
 int map_ray_views(revo_map* m, const MapRayK& a, int n, const MapRayView* d_views, int max_blocks) {
   hipStream_t s = (hipStream_t)m->g.stream;
   hipLaunchKernelGGL(k_map_raycast, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), 0, s, a, d_views);
   HIPCHECK(hipGetLastError());
-  return m->ray_time.end(s);
+  return REVO_OK;
 }
 
 extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, const revo_map_ray_params* prm, float* const* depth,
@@ -448,7 +450,7 @@ extern "C" int revo_map_raycast(revo_map* m, int n, const revo_map_view* views, 
   }
   TRY(m->rviews.upload(n, s));
   MapRayK a{};
-  TRY(ray_begin(m, &a, min_count, max_steps, d_info, d_hits, n));
+  TRY(ray_begin(m, &a, min_count, max_steps, d_info, d_hits, n, &m->ray_time));
   hipLaunchKernelGGL(k_map_raycast, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), 0, s, a, m->rviews.d);
   HIPCHECK(hipGetLastError());
   TRY(m->ray_time.end(s));
@@ -489,7 +491,7 @@ extern "C" int revo_map_cast_rays(revo_map* m, size_t n, const revo_map_ray* ray
   u64* d_info = device_out && info ? (u64*)info : (u64*)m->rcnt.p;
   ulonglong2* d_out = device_out ? (ulonglong2*)out : (ulonglong2*)m->rout.p;
   MapRayK a{};
-  { const int rc = ray_begin(m, &a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0); if (rc) { (void)hipStreamSynchronize(s); return rc; } }
+  { const int rc = ray_begin(m, &a, std::max<u64>(min_count, 1), max_steps, d_info, nullptr, 0, &m->ray_time); if (rc) { (void)hipStreamSynchronize(s); return rc; } }
   hipLaunchKernelGGL(k_map_cast_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, d_rays, (unsigned)n, d_out);
   if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); return fail(REVO_ERR_HIP, "k_map_cast_rays: the launch failed"); }
   TRY(m->ray_time.end(s));
