@@ -17,6 +17,7 @@
 // keep the reference's operation order and are compiled with -ffp-contract=off.
 #include "revo_dev.h"
 #include "revo_nms_px.h"
+#include "revo_edt_px.h"
 #include <type_traits>
 
 namespace {
@@ -1999,7 +2000,6 @@ __global__ void __launch_bounds__(1024) k_pcl_scan(int* chunk, int n, int* total
 // values are small wherever there are edges.  Result sqrtf(d2) is bit-identical
 // to OpenCV's (all d2 < 2^24); no edge at all -> OpenCV's 1e15f sentinel.
 // ---------------------------------------------------------------------------
-#define EDT_INF (1 << 29)
 // 1024 threads = (columns of the strip) x (row groups); every thread owns <= 32 rows of one column and
 // keeps their edge bits in a 32-bit mask: nearest edge above/below = clz / ffs on the mask, or the
 // LDS carry (last/first edge row of the other groups).  One edge read, one g^2 write per pixel.
@@ -2066,68 +2066,50 @@ __global__ void __launch_bounds__(EDT_THREADS) k_edt_cols(PyrGeom g, FramePlanes
   }
 }
 
-// Rows: a workgroup takes whole rows worth ~EDT_ROW_PX pixels (2 rows of 640, 16 of 80: every lane has a pixel), squares the
-// vertical distances into LDS rows padded with "no edge" on both sides as far as the search can reach, and every pixel searches
-//      d2(x) = min_d  d^2 + min(g2[x - d], g2[x + d]),     four distances per trip, until d^2 >= best      (no bounds checks)
-// sqrtf of an integer-valued float in [0, 2^24): v_sqrt_f32 (within 1 ulp) and the +-1 ulp correction of the compiler's own
-// sqrtf expansion, without its scaling of tiny inputs and its inf / nan / zero classification (x = 0 falls through both
-// corrections: the residual of the lower neighbour is NaN, that of the upper one is not positive).  Same instructions on the
-// same values as sqrtf(x) for x >= 1: correctly rounded.
-__device__ __forceinline__ float sqrt_rn_int(float x) {
-  const float s = __builtin_amdgcn_sqrtf(x);
-  const unsigned si = __float_as_uint(s);
-  const float sd = __uint_as_float(si - 1u), su = __uint_as_float(si + 1u);
-  const float rd = __builtin_fmaf(-sd, s, x), ru = __builtin_fmaf(-su, s, x);
-  float r = (rd <= 0.0f) ? sd : s;
-  r = (ru > 0.0f) ? su : r;
-  return r;
-}
-__global__ void __launch_bounds__(256) k_edt_rows(PyrGeom g, FramePlanes pl, int f0, int fstride) {
-  extern __shared__ int s_g2[];
+// Rows: a workgroup of EDT_ROW_THREADS lanes takes whole rows worth ~EDT_ROW_PX pixels (2 rows of 640, 16 of 80), squares the
+// vertical distances into LDS rows padded with "no edge" on both sides as far as the search can reach, and every lane takes
+// groups of four consecutive pixels of a row (1280 px = 320 groups: one per lane at the widths 640, 320, 160, 80; a strided
+// loop serves every other width and a last block with fewer rows).  The search is revo_edt_px.h:
+//      d2(x) = min_d  d^2 + min(g2[x - d], g2[x + d]),     d = 4t .. 4t+3 of all four pixels per trip from two 16-byte LDS reads,
+// until (4t)^2 >= best of all four (no bounds checks, no per-distance addresses), then four roots and one 16-byte store.
+__global__ void __launch_bounds__(EDT_ROW_THREADS) k_edt_rows(PyrGeom g, FramePlanes pl, int f0, int fstride) {
+  extern __shared__ __attribute__((aligned(16))) int s_g2[];
   const int f = f0 + blockIdx.z * fstride;
   const int l = level_of(g, blockIdx.x, &LevelGeom::edt_block_base);
   const LevelGeom lv = g.lv[l];
   const int w = lv.w;
   const int y0 = (blockIdx.x - lv.edt_block_base) * lv.edt_rows;
   const int nr = min(lv.edt_rows, lv.h - y0);
-  const int pad = w + 4, pitch = w + 2 * pad;  // the search stops at d < w (+3 for the trip): never leaves the padding
-  const uint16_t* gd = reinterpret_cast<const uint16_t*>(pl.scratch[l]) + (size_t)f * lv.npix + (size_t)y0 * w;
-  // LDS rows: [pad "no edge"][w squared vertical distances][pad "no edge"].  Row by row, no index division (the flattened
-  // fill with its divisions was 43 % of this kernel's VALU instructions): the pads are constant 16-byte stores (widths are
-  // multiples of 4, so pad, pitch and every row start are too), the data four pixels per lane from one 8-byte load.
+  const int pad = w + 4, pitch = w + 2 * pad;  // the search stops at d < w: never leaves the padding (revo_edt_px.h)
+  // LDS rows: [pad "no edge"][w squared vertical distances][pad "no edge"]; widths are multiples of 4, so pad, pitch and every
+  // row start are 16-byte quads.  The rows of a block are contiguous in the column pass's plane: lane j takes quad j of the
+  // block = (row, quad of the row) with one 8-byte load, issued first, and stores the two pad quads of the same offset under
+  // its latency.  (The pads are one quad longer than the row: two more stores per row.)  No integer division: edt_div_small.
+  const uint2* src = reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(pl.scratch[l]) + (size_t)f * lv.npix + (size_t)y0 * w);
   const int4 inf4 = make_int4(EDT_INF, EDT_INF, EDT_INF, EDT_INF);
-  const int padq = pad >> 2, wq = w >> 2;
-  for (int r = 0; r < nr; ++r) {
-    int4* row4 = reinterpret_cast<int4*>(s_g2 + r * pitch);
-    for (int i = threadIdx.x; i < padq; i += 256) { row4[i] = inf4; row4[padq + wq + i] = inf4; }
-    const uint2* src = reinterpret_cast<const uint2*>(gd + r * w);
-    for (int i = threadIdx.x; i < wq; i += 256) {
-      const uint2 q = src[i];
-      const int d0 = (int)(q.x & 0xffffu), d1 = (int)(q.x >> 16), d2 = (int)(q.y & 0xffffu), d3 = (int)(q.y >> 16);
-      row4[padq + i] = make_int4(d0 == 0xffff ? EDT_INF : __mul24(d0, d0), d1 == 0xffff ? EDT_INF : __mul24(d1, d1),
-                                 d2 == 0xffff ? EDT_INF : __mul24(d2, d2), d3 == 0xffff ? EDT_INF : __mul24(d3, d3));
-    }
+  const int padq = pad >> 2, wq = w >> 2, pitchq = pitch >> 2;
+  int4* lds4 = reinterpret_cast<int4*>(s_g2);
+  const float inv_wq = __builtin_amdgcn_rcpf((float)wq);
+  for (int j = threadIdx.x; j < nr * wq; j += EDT_ROW_THREADS) {
+    const uint2 q = src[j];
+    const int r = edt_div_small(j, inv_wq), i = j - __mul24(r, wq);
+    int4* row4 = lds4 + __mul24(r, pitchq);
+    row4[i] = inf4;
+    row4[padq + wq + i] = inf4;
+    row4[padq + i] = make_int4(edt_g2((int)(q.x & 0xffffu)), edt_g2((int)(q.x >> 16)), edt_g2((int)(q.y & 0xffffu)), edt_g2((int)(q.y >> 16)));
   }
+  for (int j = threadIdx.x; j < 2 * nr; j += EDT_ROW_THREADS) lds4[__mul24(j >> 1, pitchq) + ((j & 1) ? padq + 2 * wq : wq)] = inf4;
   __syncthreads();
-  float* dt = pl.dt[l] + (size_t)f * lv.npix + (size_t)y0 * w;
-  // pixel p = r * w + x, p += 256 per trip: (r, x) advance by (256 / w, 256 % w) with one carry -- one division per thread
-  const int dq = 256 / w, dr = 256 - dq * w;
-  int r = threadIdx.x / w, x = threadIdx.x - r * w;
-  for (int p = threadIdx.x; p < nr * w; p += 256) {
-    const int* c = s_g2 + r * pitch + pad + x;
-    int best = c[0];
-    for (int d = 1; d < w && d * d < best; d += 4) {
-      int m = best;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int dj = d + j;
-        m = min(m, dj * dj + min(c[-dj], c[dj]));
-      }
-      best = m;
-    }
-    dt[p] = best >= EDT_INF ? sqrtf(1e15f) : sqrt_rn_int((float)best);
-    x += dr; r += dq;
-    if (x >= w) { x -= w; ++r; }
+  float4* dt4 = reinterpret_cast<float4*>(pl.dt[l] + (size_t)f * lv.npix + (size_t)y0 * w);
+  // Search: group i of the block -> quad i / nr of row i % nr.  The lanes of a wave lie interleaved over the block's rows, a
+  // compact 2-D patch of the image whose pixels need about the same number of trips (counted and measured against lanes laid
+  // along the flattened rows: profiles/edt_rows_window.txt).  The rows of a block are contiguous in the DT plane too.
+  const float inv = __builtin_amdgcn_rcpf((float)nr);
+  for (int i = threadIdx.x; i < nr * wq; i += EDT_ROW_THREADS) {
+    const int q = edt_div_small(i, inv), r = i - __mul24(q, nr);
+    int best[4];
+    edt_search4(s_g2 + __mul24(r, pitch) + pad, q, w, best);
+    dt4[__mul24(r, wq) + q] = make_float4(edt_dt(best[0]), edt_dt(best[1]), edt_dt(best[2]), edt_dt(best[3]));
   }
 }
 
@@ -2468,7 +2450,7 @@ void launch_keyframe(const PyrGeom& g, const FramePlanes& p, int f0, int fstride
   if (which & 1) hipLaunchKernelGGL(k_edt_cols, dim3(strips * count), dim3(EDT_THREADS), 0, s, g, p, f0, fstride, count);
   size_t rows_lds = 0;
   for (int l = 0; l < g.n_levels; ++l) rows_lds = std::max(rows_lds, (size_t)g.lv[l].edt_rows * (3 * g.lv[l].w + 8) * sizeof(int));
-  if (which & 2) hipLaunchKernelGGL(k_edt_rows, dim3(g.total_edt_blocks, 1, count), dim3(256), rows_lds, s, g, p, f0, fstride);
+  if (which & 2) hipLaunchKernelGGL(k_edt_rows, dim3(g.total_edt_blocks, 1, count), dim3(EDT_ROW_THREADS), rows_lds, s, g, p, f0, fstride);
 }
 
 // The float4 table is only materialised for the returnOptimizationStructure accessor: the
