@@ -1685,6 +1685,76 @@ int revo_map_tsdf_raycast(revo_map* m, const revo_map_df_box* box, const revo_ma
                           float* const* depth, float* const* normal, uint8_t* const* bgr, uint32_t* hits, int device_out,
                           revo_map_tsdf_ray_info* info);
 
+/* ---- tracking a depth frame against the surface ----------------------------------------------------------------
+ * Frame-to-model tracking: every pixel of a depth image is back-projected, moved by a candidate pose and looked up in the fused
+ * field, whose value there is the signed distance to the surface and whose interpolant's gradient is its direction.  No cloud is
+ * extracted, uploaded or searched, and no distance field is rebuilt: the TSDF is the model as it stands.
+ * All arithmetic is float32 with every operation rounded on its own; a / b is the correctly rounded quotient.  No atomic decides
+ * an output.
+ *
+ * The record of one pose.  m, box, tsdf, device_tsdf: revo_map_tsdf_raycast's volume arguments with its rules (m gives the voxel
+ * edge v, the context and the stream); trunc: the volume's truncation distance in metres.  frame: one revo_map_carve_view with
+ * every rule of revo_map_carve_eval (kf: a pyramid's level-0 depth plane with the context's camera and range; or a raw depth
+ * image with its size and either six zeros or its own intrinsics and range); its T_w_c is NOT read.  Pose: T_w_c, R column-major
+ * and t.  Per pixel (x, y) with x % stride == 0 and y % stride == 0:
+ *   D = depth[y*w + x]; the pixel is SKIPPED unless D is finite, > zmin and < zmax (the carve rule);
+ *   dcx = ((float)x - cx)/fx, dcy = ((float)y - cy)/fy;  pc = (dcx*D, dcy*D, D);
+ *   p'_i = ((R_i0*pcx + R_i1*pcy) + R_i2*pcz) + t_i;
+ *   the place: u_i = p'_i / v - ((float)lo_i + 0.5f), b_i = floorf(u_i), r_i = u_i - b_i (revo_map_tsdf_raycast's step 3 with
+ *         g_i = p'_i); the pixel is SKIPPED unless every u_i is finite with 0 <= b_i <= n_i - 2 and the eight cells b + {0,1}^3
+ *         are valid, weight >= max(min_weight, 1); then F and G are revo_map_tsdf_raycast's step 5;
+ *   kq = trunc / 1024.0f;  e = F*kq, the signed residual in metres (positive in front of the surface);
+ *   g_i = (G_i*kq) / v, dimensionless: the exact derivative of the interpolant;
+ *   the pixel is accepted iff fabsf(e) <= max_dist (inclusive), otherwise GATED (the gated count is considered - matched -
+ *         skipped).
+ * Per accepted pixel, with u = p' - centre:  a = u x g, J = (g, a) and the 28 terms S[0..20] J_i*J_j (i <= j, row by row),
+ * S[21..26] J_i*e, S[27] e*e exactly as revo_map_df_align_eval forms them.  Each S is the float nearest the exact sum of its float
+ * terms (double-double from the first addition, rounded once; DESIGN 4.1's midpoint caveat applies).  The counts are exact. */
+typedef struct revo_map_tsdf_track_info {   /* 208 bytes, little-endian, no padding holes: revo_map_df_align_info's layout */
+  float    S[28];
+  uint64_t matched;      /* accepted pixels                                                                            */
+  uint64_t considered;   /* the pixels the stride visits: ceil(w / stride) * ceil(h / stride)                          */
+  uint64_t skipped;      /* pixels without a usable depth, outside the interpolation cells, or next to an invalid cell */
+  float    centre[3], max_dist;  /* the parameters the call ran with (max_dist after its default)                      */
+  float    R[9], T[3];   /* the pose the sums were taken at (R column-major), as given                                 */
+  int32_t  flags;        /* bit0: the pose is not finite or its rotation not orthogonal (revo_map_align_eval's rule):
+                            everything else is then zero except pose, centre, max_dist                                 */
+  int32_t  reserved;     /* zero */
+} revo_map_tsdf_track_info;
+typedef struct revo_map_tsdf_track_params {  /* 32 bytes; NULL: the defaults and centre 0 */
+  float    max_dist;     /* metres; 0: trunc / 2; else finite, 0 < max_dist <= trunc */
+  uint32_t stride;       /* 1 .. 8; 0: 1 */
+  uint32_t min_weight;   /* the views a cell needs; 0 counts as 1 */
+  float    centre[3];    /* finite: the rotation centre of J */
+  uint32_t reserved[2];  /* zero */
+} revo_map_tsdf_track_params;
+
+/* One record per pose (nposes 1 .. 4096, 4x4 column-major T_w_c), all poses in ONE launch on m's context's tracker stream; for
+ * a pyramid frame behind that pyramid's build.  device_in: where a raw depth image lives (a device pointer 4-byte aligned);
+ * device_out: where out lives (a device pointer 16-byte aligned); a device volume is 16-byte aligned.  A host volume and a host
+ * image are uploaded into the handle's buffers.  The call only enqueues when volume, frame and output are all on the device (a
+ * pyramid frame is), and waits otherwise.  The map is not read or changed.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: a NULL m, box, tsdf, frame, poses or out; the box
+ * rules; revo_map_carve_eval's view rules except those of T_w_c; nposes out of range; a trunc that is not finite or not > 0; a
+ * max_dist that is not finite, negative or above trunc; a stride above 8; a centre that is not finite; a reserved word that is
+ * not 0; a flag outside 0 / 1; a misaligned device pointer. */
+int revo_map_tsdf_track_eval(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, int device_tsdf, float trunc,
+                             const revo_map_carve_view* frame, int device_in, int nposes, const float* T_w_c_n16,
+                             const revo_map_tsdf_track_params* prm, revo_map_tsdf_track_info* out, int device_out);
+
+/* Host only.  revo_map_df_align_system's arithmetic: e(x) ~ e + g.v + w.(u x g) = e + J.x, H = sum J J^T from its upper triangle
+ * S[0..20], g = S[21..26], cost = S[27].  REVO_ERR_INVALID_ARG: NULL, or flags bit0. */
+int revo_map_tsdf_track_system(const revo_map_tsdf_track_info* info, double H[36], double g[6]);
+
+/* revo_map_align's Gauss-Newton loop over revo_map_tsdf_track_eval's records: the same options, Cholesky and pivot rule, update
+ * T <- Tr(c) exp(x) Tr(-c) T, stopping rule and statuses; info_out from one more evaluation.  A host volume and a host image are
+ * uploaded once per call.  The call waits.  REVO_ERR_INVALID_ARG: as revo_map_tsdf_track_eval, a T_init that is not finite,
+ * max_iters < 1. */
+int revo_map_tsdf_track(revo_map* m, const revo_map_df_box* box, const revo_map_tsdf_cell* tsdf, int device_tsdf, float trunc,
+                        const revo_map_carve_view* frame, int device_in, const float T_init[16],
+                        const revo_map_tsdf_track_params* prm, const revo_map_align_opts* opt, float T_out[16],
+                        revo_map_tsdf_track_info* info_out, int32_t* iterations, int32_t* status);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

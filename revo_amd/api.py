@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfRayInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfTrackParams, MapTsdfRayInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1230,6 +1230,94 @@ class VoxelMap:
         if wait:
             self.sync()
 
+    # -- tracking a depth frame against the surface (revo_map_tsdf_track_eval / revo_map_tsdf_track)
+    def _surface_track_args(self, tsdf, lo, trunc, frame, max_dist, stride, min_weight, centre):
+        """(box, volume pointer, its side, the frame's MapCarveView array, its side, trunc, params, what keeps the memory alive) of a
+        tracking call.  tsdf: a numpy array of mapfile.TSDF_CELL_DTYPE cells [n0, n1, n2] or a torch int32 device tensor [n0, n1, n2, 2]
+        as fuse_into leaves it; frame: a pyramid (its level-0 depth plane, the context's camera and range) or (depth, camera[,
+        zrange]) with depth an [h, w] float32 array or device tensor, camera (fx, fy, cx, cy), an api.Camera or None (the
+        context's), zrange (zmin, zmax) or None (the context's).  centre None: the middle of the box."""
+        from . import mapfile
+        keep = []
+        if hasattr(tsdf, "data_ptr"):
+            if tsdf.dim() != 4 or tsdf.shape[3] != 2 or str(tsdf.dtype) != "torch.int32" or not (tsdf.is_contiguous() and tsdf.is_cuda):
+                raise ValueError("a device volume must be a contiguous int32 tensor [n0, n1, n2, 2]")
+            shape, tp, tdev = tuple(int(x) for x in tsdf.shape[:3]), vp(tsdf.data_ptr()), 1
+            import torch
+            torch.cuda.current_stream(tsdf.device).synchronize()  # the volume is written before the tracker stream reads it
+        else:
+            tsdf = np.ascontiguousarray(tsdf)
+            if tsdf.dtype != mapfile.TSDF_CELL_DTYPE or tsdf.ndim != 3:
+                raise ValueError("a TSDF volume is a 3-D array of (sum int32, weight uint32) cells")
+            shape, tp, tdev = tsdf.shape, tsdf.ctypes.data_as(vp), 0
+        keep.append(tsdf)
+        if isinstance(frame, ImgPyramidRGBD):
+            view = (frame, np.eye(4, dtype=np.float32))
+        else:
+            frame = tuple(frame)
+            if not 2 <= len(frame) <= 3:
+                raise ValueError("a frame is a pyramid or (depth, camera[, zrange])")
+            cam, zr = frame[1], frame[2] if len(frame) > 2 else None
+            if cam is None:
+                if zr is not None:
+                    raise ValueError("a zrange goes with a camera: without one the context's camera and range are used")
+                k = None
+            else:
+                if isinstance(cam, Camera):
+                    cam = (cam.fx, cam.fy, cam.cx, cam.cy)
+                st = self.cameraPyr.settings
+                k = tuple(cam) + (tuple(zr) if zr is not None else (st.depth_min, st.depth_max))
+            view = (frame[0], np.eye(4, dtype=np.float32), k)
+        cv, device_in, kv = self._carve_views([view])
+        keep.append(kv)
+        if int(stride) < 0 or int(min_weight) < 0:
+            raise ValueError("stride and min_weight are >= 0")
+        if centre is None:
+            centre = mapfile.tsdf_track_centre(lo, shape, self.voxel)
+        p = MapTsdfTrackParams()
+        p.max_dist, p.stride, p.min_weight = 0.0 if max_dist is None else float(max_dist), int(stride), int(min_weight)
+        p.centre[:] = [float(x) for x in np.asarray(centre, np.float32).reshape(3)]
+        return self._df_box(lo, shape, 0, 1), tp, tdev, cv, device_in, float(trunc), p, keep
+
+    def surface_track_eval(self, tsdf, lo, trunc, frame, poses, max_dist=None, stride=1, min_weight=1, centre=None, d_out=None):
+        """The tracking sums of a depth frame against the TSDF volume `tsdf` of the box at lo (fused at this map's voxel edge with the
+        truncation distance trunc) at each camera pose T_w_c (one 4x4 or [n, 4, 4], 1 .. 4096): MapTsdfTrackInfo records, all from
+        one launch (revo_map_tsdf_track_eval).  tsdf, frame, centre: see _surface_track_args.  max_dist defaults to trunc / 2.
+        d_out: a torch uint8 device tensor of n x 208 bytes takes the records instead (returns None; with a device volume and a
+        device or pyramid frame the call only enqueues: sync() orders later reads)."""
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        T = T.reshape(-1, 4, 4)
+        n = len(T)
+        flat = np.ascontiguousarray(np.concatenate([_cm4(M) for M in T]))
+        box, tp, tdev, cv, din, tr, p, keep = self._surface_track_args(tsdf, lo, trunc, frame, max_dist, stride, min_weight, centre)
+        if d_out is not None:
+            if not (d_out.is_cuda and d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= n * C.sizeof(MapTsdfTrackInfo)):
+                raise ValueError("d_out must be a contiguous device tensor of n x %d bytes" % C.sizeof(MapTsdfTrackInfo))
+            import torch
+            torch.cuda.current_stream(d_out.device).synchronize()
+            check(_lib.lib().revo_map_tsdf_track_eval(self._h, C.byref(box), tp, tdev, tr, cv, din, n, _p(flat, f32p), C.byref(p), vp(d_out.data_ptr()), 1))
+            return None
+        out = (MapTsdfTrackInfo * n)()
+        check(_lib.lib().revo_map_tsdf_track_eval(self._h, C.byref(box), tp, tdev, tr, cv, din, n, _p(flat, f32p), C.byref(p), C.cast(out, vp), 0))
+        return out[0] if single else list(out)
+
+    def surface_track(self, tsdf, lo, trunc, frame, T_init, max_dist=None, stride=1, min_weight=1, centre=None, max_iters=30, eps_t=1e-6,
+                      eps_r=1e-6, min_matched=12):
+        """Gauss-Newton of the frame's camera pose onto the surface from T_init over surface_track_eval's records
+        (revo_map_tsdf_track): align()'s loop, options and statuses.  -> dict: T (the refined T_w_c), info (the MapTsdfTrackInfo at T),
+        iterations, status, cov = sigma2 H^-1 with sigma2 = S[27] / (matched - 6), sigma2, centre."""
+        T0 = np.asarray(T_init, np.float32).reshape(4, 4)
+        box, tp, tdev, cv, din, tr, p, keep = self._surface_track_args(tsdf, lo, trunc, frame, max_dist, stride, min_weight, centre)
+        o = MapAlignOpts(int(max_iters), 0, float(eps_t), float(eps_r), int(min_matched))
+        T1 = np.zeros(16, np.float32)
+        info, it, st = MapTsdfTrackInfo(), C.c_int32(), C.c_int32()
+        check(_lib.lib().revo_map_tsdf_track(self._h, C.byref(box), tp, tdev, tr, cv, din, _p(_cm4(T0), f32p), C.byref(p), C.byref(o), _p(T1, f32p),
+                                             C.byref(info), C.byref(it), C.byref(st)))
+        cov, s2 = tsdf_track_covariance(info)
+        return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2,
+                "centre": np.array(list(p.centre), np.float32)}
+
     def frontiers(self, seen, min_views=1, min_count=1):
         """Where known space ends -> [k, 3] int32 voxel indices in ascending order of the cell's place in the box: the cells
         of a SeenVolume that are not solid, have >= min_views free votes and have a face neighbour inside the box that is
@@ -1793,6 +1881,25 @@ class TsdfVolume:
         return {"depth": pick(r["depth"]), "normals": pick(r["normals"]) if normals else None, "bgr": pick(r["bgr"]) if colors else None,
                 "hits": pick(r["hits"]), "info": r["info"]}
 
+    def track_eval(self, frame, poses, max_dist=None, stride=1, min_weight=1, centre=None, map=None):
+        """The tracking sums of a depth frame against this surface at camera poses -> MapTsdfTrackInfo records
+        (VoxelMap.surface_track_eval), on the device of the map the volume was fused with (or `map`).  frame: a pyramid
+        or (depth, camera[, zrange])."""
+        m = map if map is not None else self._map
+        if m is None:
+            raise ValueError("tracking runs on a map's device: pass map= (mapfile.tsdf_track_records is the contract on the CPU)")
+        m._tsdf_box(self)
+        return m.surface_track_eval(self.cells, self.lo, self.trunc, frame, poses, max_dist, stride, min_weight, centre)
+
+    def track(self, frame, T_init, max_dist=None, stride=1, min_weight=1, centre=None, map=None, **opts):
+        """The frame's camera pose refined against this surface from T_init (VoxelMap.surface_track) -> dict of T, info,
+        iterations, status, cov, sigma2 and centre, as align gives them.  opts: max_iters, eps_t, eps_r, min_matched."""
+        m = map if map is not None else self._map
+        if m is None:
+            raise ValueError("tracking runs on a map's device: pass map= (mapfile.tsdf_track is the contract on the CPU)")
+        m._tsdf_box(self)
+        return m.surface_track(self.cells, self.lo, self.trunc, frame, T_init, max_dist, stride, min_weight, centre, **opts)
+
     def save(self, path):
         """The .npz `python -m revo_amd.mapfile tsdf` writes: sum, weight, lo, n, voxel, trunc, and with a colour volume
         color_sum and color_weight."""
@@ -1902,6 +2009,17 @@ class SurfaceVolume:
         return {"depth": split(host(d_depth)), "normals": split(host(d_nrm)), "bgr": split(host(d_bgr)),
                 "hits": int(hits[0]) if single else [int(x) for x in hits],
                 "info": {k: int(info[i]) for i, k in enumerate(mapfile.TSDF_RAY_INFO_KEYS)}}
+
+    def track_eval(self, frame, poses, max_dist=None, stride=1, min_weight=1, centre=None, d_out=None):
+        """The tracking sums of a depth frame against the surface as it stands (VoxelMap.surface_track_eval on the device volume,
+        DESIGN 29): no host copy of the volume; with a pyramid or device frame and d_out the call is only enqueued behind the
+        integrations."""
+        return self.map.surface_track_eval(self.d_tsdf, self.lo, self.trunc, frame, poses, max_dist, stride, min_weight, centre, d_out)
+
+    def track(self, frame, T_init, max_dist=None, stride=1, min_weight=1, centre=None, **opts):
+        """The frame's camera pose refined against the surface as it stands, from T_init (VoxelMap.surface_track on the device
+        volume) -> dict of T, info, iterations, status, cov, sigma2 and centre."""
+        return self.map.surface_track(self.d_tsdf, self.lo, self.trunc, frame, T_init, max_dist, stride, min_weight, centre, **opts)
 
 
 def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
@@ -2057,6 +2175,27 @@ def df_align_covariance(info):
     if (info.flags & 1) or info.matched <= 6:
         return None, None
     H, _ = df_align_system(info)
+    s2 = float(info.S[27]) / float(info.matched - 6)
+    try:
+        X = np.linalg.inv(H)
+    except np.linalg.LinAlgError:
+        return None, None
+    return s2 * 0.5 * (X + X.T), s2
+
+
+def tsdf_track_system(info):
+    """(H [6, 6], g [6]) float64 of a MapTsdfTrackInfo: the Gauss-Newton system of revo_map_tsdf_track_system (unknowns v, w)."""
+    H, g = np.zeros(36, np.float64), np.zeros(6, np.float64)
+    check(_lib.lib().revo_map_tsdf_track_system(C.byref(info), _p(H, C.POINTER(C.c_double)), _p(g, C.POINTER(C.c_double))))
+    return H.reshape(6, 6), g
+
+
+def tsdf_track_covariance(info):
+    """(cov [6, 6] = sigma2 H^-1, sigma2 = S[27] / (matched - 6)) of a surface tracking record (one residual per pixel);
+    (None, None) without an evaluation, with too few pixels or with a singular H."""
+    if (info.flags & 1) or info.matched <= 6:
+        return None, None
+    H, _ = tsdf_track_system(info)
     s2 = float(info.S[27]) / float(info.matched - 6)
     try:
         X = np.linalg.inv(H)
@@ -2245,6 +2384,13 @@ class MapWindow:
 
     def surface_raycast_into(self, *args, **kw):
         return self.map.surface_raycast_into(*args, **kw)
+
+    def surface_track_eval(self, *args, **kw):
+        """The inner map's surface_track_eval: a depth frame against a TSDF volume (the window's voxels play no part)."""
+        return self.map.surface_track_eval(*args, **kw)
+
+    def surface_track(self, *args, **kw):
+        return self.map.surface_track(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -280,6 +280,14 @@ struct MapRayView {  // one view of a launch, in device memory
 };
 struct MapDfPose;   // revo_map_df_align.hip: one pose of a registration launch
 struct TsdfRayView; // revo_map_tsdf_ray.hip: one view of a surface ray cast
+struct TsdfTrackPose; // revo_map_tsdf_track.hip: one pose of a surface tracking launch
+// revo_map_tsdf_track_eval / revo_map_tsdf_track (revo_map_tsdf_track.hip): the poses of a launch, its tickets, counts and
+// published partials, the device copy of a host depth image, and the device records of a host-output call.  Only these two calls go
+// through them; a host volume goes through the handle's tsdfvol, which revo_map_tsdf_fuse, _mesh and _raycast use too.
+struct MapTsdfTrackScratch {
+  HostRows<TsdfTrackPose> poses;
+  DevBuf work, frame, out;
+};
 
 struct revo_map {
   revo_ctx* ctx = nullptr;
@@ -340,6 +348,8 @@ struct revo_map {
   // of a host-output call; a host volume goes through tsdfvol and tsdfcol
   DevBuf tsdfraywork, tsdfrayout;
   HostRows<TsdfRayView> tsdfray_views;
+  // revo_map_tsdf_track_eval / revo_map_tsdf_track: everything of theirs, in a type of its own
+  MapTsdfTrackScratch tsdftrk;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every

@@ -52,15 +52,27 @@ TSDF_HD uint32_t tsdf_ray_block(int nby, int nbz, int bx, int by, int bz) {
 // Sample k's depth: from the integer, never accumulated.
 TSDF_HD float tsdf_ray_s(float zmin, uint32_t k, float step) { return zmin + (float)k * step; }
 
-// One axis of a sample's place: cell centres sit at integers.
-TSDF_HD bool tsdf_ray_axis(float o, float s, float d, float voxel, int lo, int n, int* b, float* r) {
-  const float g = o + s * d;
+// One axis of a place: cell centres sit at integers.  g: the world coordinate.
+TSDF_HD bool tsdf_ray_axis_at(float g, float voxel, int lo, int n, int* b, float* r) {
   const float u = tsdf_div(g, voxel) - ((float)lo + 0.5f);
   const float f = std::floor(u);
   *r = u - f;
   const bool ok = std::isfinite(u) && f >= 0.0f && f <= (float)(n - 2);
   *b = ok ? (int)f : 0;
   return ok;
+}
+// ... of a sample: the coordinate is o + s * d.
+TSDF_HD bool tsdf_ray_axis(float o, float s, float d, float voxel, int lo, int n, int* b, float* r) {
+  return tsdf_ray_axis_at(o + s * d, voxel, lo, n, b, r);
+}
+// The place of a world point (revo_map_tsdf_track).
+TSDF_HD TsdfRayPlace tsdf_ray_place_at(const TsdfRayK& a, float gx, float gy, float gz) {
+  TsdfRayPlace p;
+  const bool okx = tsdf_ray_axis_at(gx, a.voxel, a.box.lo[0], a.box.n[0], &p.bx, &p.rx);
+  const bool oky = tsdf_ray_axis_at(gy, a.voxel, a.box.lo[1], a.box.n[1], &p.by, &p.ry);
+  const bool okz = tsdf_ray_axis_at(gz, a.voxel, a.box.lo[2], a.box.n[2], &p.bz, &p.rz);
+  p.inbox = okx && oky && okz;
+  return p;
 }
 TSDF_HD TsdfRayPlace tsdf_ray_place(const TsdfRayK& a, const TsdfRay& ray, float s) {
   TsdfRayPlace p;
@@ -78,14 +90,12 @@ TSDF_HD float tsdf_ray_bilerp(float v00, float v01, float v10, float v11, float 
 // The nearest corner of an axis; r == 0.5 goes up.
 TSDF_HD int tsdf_ray_near(int b, float r) { return b + (r >= 0.5f ? 1 : 0); }
 
-// The sample at the place p: valid when its base lies in the box and its eight cells are valid.  The corners are named f<x><y><z>.
-TSDF_HD void tsdf_ray_sample(const TsdfRayK& a, const TsdfRayPlace& p, float s, TsdfRaySample* out) {
-  out->valid = false; out->s = s; out->F = 0.0f; out->gx = 0.0f; out->gy = 0.0f; out->gz = 0.0f; out->ccell = 0u;
-  if (!p.inbox) return;
+// The sample at the place p (its base in the box) from its eight cells, named c<x><y><z>: valid when all eight are.  *out holds
+// tsdf_ray_sample's "not valid" on entry.
+TSDF_HD void tsdf_ray_sample_cells(const TsdfRayK& a, const TsdfRayPlace& p, const revo_map_tsdf_cell& c000, const revo_map_tsdf_cell& c001,
+                                   const revo_map_tsdf_cell& c010, const revo_map_tsdf_cell& c011, const revo_map_tsdf_cell& c100,
+                                   const revo_map_tsdf_cell& c101, const revo_map_tsdf_cell& c110, const revo_map_tsdf_cell& c111, TsdfRaySample* out) {
   const size_t nz = (size_t)a.box.n[2], nyz = (size_t)a.box.n[1] * nz;
-  const size_t c = (size_t)p.bx * nyz + (size_t)p.by * nz + (size_t)p.bz;
-  const revo_map_tsdf_cell c000 = a.tsdf[c], c001 = a.tsdf[c + 1], c010 = a.tsdf[c + nz], c011 = a.tsdf[c + nz + 1];
-  const revo_map_tsdf_cell c100 = a.tsdf[c + nyz], c101 = a.tsdf[c + nyz + 1], c110 = a.tsdf[c + nyz + nz], c111 = a.tsdf[c + nyz + nz + 1];
   const uint32_t mw = a.min_weight;
   if (!(tsdf_valid(c000.weight, mw) && tsdf_valid(c001.weight, mw) && tsdf_valid(c010.weight, mw) && tsdf_valid(c011.weight, mw) &&
         tsdf_valid(c100.weight, mw) && tsdf_valid(c101.weight, mw) && tsdf_valid(c110.weight, mw) && tsdf_valid(c111.weight, mw)))
@@ -102,6 +112,17 @@ TSDF_HD void tsdf_ray_sample(const TsdfRayK& a, const TsdfRayPlace& p, float s, 
   out->gy = tsdf_ray_bilerp(f010 - f000, f011 - f001, f110 - f100, f111 - f101, p.rz, p.rx);
   out->gz = tsdf_ray_bilerp(f001 - f000, f011 - f010, f101 - f100, f111 - f110, p.ry, p.rx);
   out->ccell = (uint32_t)((size_t)tsdf_ray_near(p.bx, p.rx) * nyz + (size_t)tsdf_ray_near(p.by, p.ry) * nz + (size_t)tsdf_ray_near(p.bz, p.rz));
+}
+
+// The sample at the place p: valid when its base lies in the box and its eight cells are valid.
+TSDF_HD void tsdf_ray_sample(const TsdfRayK& a, const TsdfRayPlace& p, float s, TsdfRaySample* out) {
+  out->valid = false; out->s = s; out->F = 0.0f; out->gx = 0.0f; out->gy = 0.0f; out->gz = 0.0f; out->ccell = 0u;
+  if (!p.inbox) return;
+  const size_t nz = (size_t)a.box.n[2], nyz = (size_t)a.box.n[1] * nz;
+  const size_t c = (size_t)p.bx * nyz + (size_t)p.by * nz + (size_t)p.bz;
+  const revo_map_tsdf_cell c000 = a.tsdf[c], c001 = a.tsdf[c + 1], c010 = a.tsdf[c + nz], c011 = a.tsdf[c + nz + 1];
+  const revo_map_tsdf_cell c100 = a.tsdf[c + nyz], c101 = a.tsdf[c + nyz + 1], c110 = a.tsdf[c + nyz + nz], c111 = a.tsdf[c + nyz + nz + 1];
+  tsdf_ray_sample_cells(a, p, c000, c001, c010, c011, c100, c101, c110, c111, out);
 }
 
 // What two valid samples that follow each other decide: -1 nothing, else the status that ends the ray.

@@ -1762,10 +1762,17 @@ def df_align(d2, lo, n, voxel, points, T_init=None, max_dist=None, centre=None, 
         raise ValueError("max_iters must be >= 1")
     if centre is None:
         centre = df_align_centre(p, T0)
+    evaluate = lambda T: df_align_records(d2, lo, n, voxel, p, np.array(T, np.float64).astype(F), max_dist, centre)[0]  # noqa: E731
+    return _gauss_newton(evaluate, T0, centre, max_iters, eps_t, eps_r, min_matched)
+
+
+def _gauss_newton(evaluate, T0, centre, max_iters, eps_t, eps_r, min_matched):
+    """align_loop_over of revo_align_host.h in its order of operations: Gauss-Newton in double over the records evaluate(T) gives
+    (T: 4 x 4 nested lists of doubles, rounded to float32 by evaluate) -> (T 4x4 float32, the record at T, iterations, status)."""
+    F = np.float32
     c = [float(x) for x in np.asarray(centre, F).reshape(3)]
     Cp = [[1.0, 0.0, 0.0, c[0]], [0.0, 1.0, 0.0, c[1]], [0.0, 0.0, 1.0, c[2]], [0.0, 0.0, 0.0, 1.0]]
     Cm = [[1.0, 0.0, 0.0, -c[0]], [0.0, 1.0, 0.0, -c[1]], [0.0, 0.0, 1.0, -c[2]], [0.0, 0.0, 0.0, 1.0]]
-    evaluate = lambda T: df_align_records(d2, lo, n, voxel, p, np.array(T, np.float64).astype(F), max_dist, centre)[0]  # noqa: E731
     T = [[float(x) for x in row] for row in T0]
     Tsys, status, it = T, ALIGN_ITER_LIMIT, 0
     while it < int(max_iters):
@@ -1807,6 +1814,160 @@ def df_align_files(dst_path, src_path, T_init=None, max_dist=None, pad=None, min
     lo, n = padded_box(lo, hi, pad)
     d2, _ = distance_field_records(rec, lo, n, min_count)
     return df_align(d2, lo, n, voxel, to_points(src, min_count)[0], T_init, max_dist, **opts)
+
+
+# --------------------------------------------------------------------- tracking a depth frame against the surface --
+TSDF_TRACK_DTYPE = DF_ALIGN_DTYPE   # revo_map_tsdf_track_info has revo_map_df_align_info's layout
+TSDF_TRACK_MAX_POSES = 4096
+TSDF_TRACK_CLASSES = ("skipped", "gated", "accepted")
+
+
+def tsdf_track_params(trunc, max_dist=None, stride=1, min_weight=1, centre=None):
+    """The parameters a surface tracking call runs with, checked as revo_map_tsdf_track_eval checks them -> (trunc, max_dist
+    float32, stride, min_weight, centre float32 [3]): max_dist None or 0 is trunc / 2, stride 0 is 1, min_weight 0 counts as 1,
+    centre None is the origin."""
+    F = np.float32
+    tr = F(trunc)
+    if not (np.isfinite(tr) and tr > 0):
+        raise ValueError("trunc must be finite and > 0")
+    md = F(0 if max_dist is None else max_dist)
+    if not np.isfinite(md) or md < 0 or md > tr:
+        raise ValueError("max_dist must be 0 (trunc / 2) or finite with 0 < max_dist <= trunc")
+    if not 0 <= int(stride) <= 8:
+        raise ValueError("stride must be 0 (1) or 1 .. 8")
+    if not 0 <= int(min_weight) < 1 << 32:
+        raise ValueError("min_weight is a number of views >= 0")
+    c = np.zeros(3, F) if centre is None else np.asarray(centre, F).reshape(3)
+    if not np.all(np.isfinite(c)):
+        raise ValueError("the centre is not finite")
+    return tr, (tr * F(0.5) if md == 0 else md), max(1, int(stride)), max(1, int(min_weight)), c
+
+
+def tsdf_track_centre(lo, n, voxel):
+    """The default rotation centre of TsdfVolume.track: the middle of the volume's box in metres, (lo + n / 2) * voxel in float64,
+    rounded to float32."""
+    lo, n = np.asarray(lo, np.float64).reshape(3), np.asarray(n, np.float64).reshape(3)
+    return ((lo + n / 2.0) * float(np.float32(voxel))).astype(np.float32)
+
+
+def tsdf_track_terms(cells, lo, voxel, trunc, depth, camera, zrange, T, max_dist, stride, min_weight, centre, classes=False):
+    """The per-pixel part of revo_map_tsdf_track_eval at one pose T (4x4 float32, finite, orthogonal) with checked parameters,
+    float32 with every operation rounded on its own -> (the 28 float32 term arrays of the accepted pixels, matched, considered,
+    skipped[, the class of every visited pixel, row by row: an index into TSDF_TRACK_CLASSES])."""
+    F = np.float32
+    n = np.asarray(cells.shape, np.int64)
+    lo = np.asarray(lo, np.int64).reshape(3)
+    D = np.asarray(depth, F)
+    h, w = D.shape
+    fx, fy, cx, cy = (F(x) for x in camera)
+    zmin, zmax = F(zrange[0]), F(zrange[1])
+    T = np.asarray(T, F)
+    v, c, kq = F(voxel), np.asarray(centre, F).reshape(3), F(trunc) / F(1024.0)
+    ys, xs = np.meshgrid(np.arange(0, h, stride), np.arange(0, w, stride), indexing="ij")
+    xs, ys = xs.reshape(-1), ys.reshape(-1)
+    cls = np.zeros(len(xs), np.int64)
+    L = lambda x0, x1, a: x0 + a * (x1 - x0)  # noqa: E731
+    B = lambda v00, v01, v10, v11, r0, r1: L(L(v00, v01, r0), L(v10, v11, r0), r1)  # noqa: E731
+    with np.errstate(all="ignore"):
+        d = D[ys, xs]
+        idx = np.flatnonzero(np.isfinite(d) & (d > zmin) & (d < zmax))
+        d = d[idx]
+        dcx, dcy = (xs[idx].astype(F) - cx) / fx, (ys[idx].astype(F) - cy) / fy
+        pcx, pcy, pcz = dcx * d, dcy * d, d
+        pt = np.stack([((T[i, 0] * pcx + T[i, 1] * pcy) + T[i, 2] * pcz) + T[i, 3] for i in range(3)], 1).astype(F).reshape(-1, 3)
+        u = (pt / v - (lo.astype(F) + F(0.5))).astype(F)
+        b = np.floor(u)
+        r = (u - b).astype(F)
+        inbox = np.all(np.isfinite(u) & (b >= 0) & (b <= (n - 2).astype(F)), axis=1)
+        idx, pt, r, b = idx[inbox], pt[inbox], r[inbox], b[inbox].astype(np.int64)
+        corner = {(i, j, k): cells[b[:, 0] + i, b[:, 1] + j, b[:, 2] + k] for i in (0, 1) for j in (0, 1) for k in (0, 1)}
+        valid = np.ones(len(idx), bool)
+        for q in corner.values():
+            valid &= q["weight"] >= min_weight
+        idx, pt, r = idx[valid], pt[valid], r[valid]
+        q = {key: (x["sum"][valid].astype(F) / x["weight"][valid].astype(F)).astype(F) for key, x in corner.items()}
+        rx, ry, rz = r[:, 0], r[:, 1], r[:, 2]
+        Fv = L(B(q[0, 0, 0], q[0, 0, 1], q[0, 1, 0], q[0, 1, 1], rz, ry), B(q[1, 0, 0], q[1, 0, 1], q[1, 1, 0], q[1, 1, 1], rz, ry), rx)
+        G = [B(q[1, 0, 0] - q[0, 0, 0], q[1, 0, 1] - q[0, 0, 1], q[1, 1, 0] - q[0, 1, 0], q[1, 1, 1] - q[0, 1, 1], rz, ry),
+             B(q[0, 1, 0] - q[0, 0, 0], q[0, 1, 1] - q[0, 0, 1], q[1, 1, 0] - q[1, 0, 0], q[1, 1, 1] - q[1, 0, 1], rz, rx),
+             B(q[0, 0, 1] - q[0, 0, 0], q[0, 1, 1] - q[0, 1, 0], q[1, 0, 1] - q[1, 0, 0], q[1, 1, 1] - q[1, 1, 0], ry, rx)]
+        e = Fv * kq
+        gx, gy, gz = ((a * kq) / v for a in G)
+        acc = np.abs(e) <= F(max_dist)
+        cls[idx] = np.where(acc, 2, 1)
+        pt, e, gx, gy, gz = pt[acc], e[acc], gx[acc], gy[acc], gz[acc]
+        uu = pt - c
+        ux, uy, uz = uu[:, 0], uu[:, 1], uu[:, 2]
+        J = [gx, gy, gz, uy * gz - uz * gy, uz * gx - ux * gz, ux * gy - uy * gx]
+        terms = [J[i] * J[j] for i in range(6) for j in range(i, 6)] + [J[i] * e for i in range(6)] + [e * e]
+    assert all(t.dtype == F for t in terms)
+    out = (terms, int(acc.sum()), len(xs), int(len(xs) - len(idx)))
+    return out + (cls,) if classes else out
+
+
+def tsdf_track_records(tsdf, lo, voxel, trunc, depth, camera, zrange, poses, max_dist=None, stride=1, min_weight=1, centre=None):
+    """revo_map_tsdf_track_eval restated in vectorised numpy: a TSDF_TRACK_DTYPE array, one record per pose (4x4 T_w_c,
+    or [N, 4, 4]; 1 .. 4096), of the depth image ([h, w] float32 metres, camera (fx, fy, cx, cy), zrange (zmin, zmax)) against the
+    volume tsdf of the box at lo with the edge `voxel` and the truncation distance trunc.  The sums are formed as df_align_records
+    forms them.  ValueError as the library's REVO_ERR_INVALID_ARG."""
+    F = np.float32
+    cells = _tsdf_volume(tsdf)
+    lo, _ = check_box(lo, np.asarray(cells.shape, np.int64))
+    if not (np.isfinite(F(voxel)) and F(voxel) > 0):
+        raise ValueError("the voxel edge must be finite and > 0")
+    tr, md, st, mw, c = tsdf_track_params(trunc, max_dist, stride, min_weight, centre)
+    D = np.asarray(depth, F)
+    if D.ndim != 2 or not (1 <= D.shape[0] <= 2048 and 1 <= D.shape[1] <= 2048):
+        raise ValueError("a depth image is [h, w] float32 with width and height 1 .. 2048")
+    k = [F(x) for x in tuple(camera)[:4]] + [F(x) for x in zrange]
+    if len(k) != 6 or not all(np.isfinite(x) for x in k) or not (k[0] > 0 and k[1] > 0) or not (k[4] >= 0 and k[4] < k[5]):
+        raise ValueError("the camera needs finite intrinsics with fx, fy > 0 and a depth range 0 <= zmin < zmax")
+    Ts = np.asarray(poses, F).reshape(-1, 4, 4)
+    if not 1 <= len(Ts) <= TSDF_TRACK_MAX_POSES:
+        raise ValueError("1 .. 4096 poses")
+    out = np.zeros(len(Ts), TSDF_TRACK_DTYPE)
+    for r, T in zip(out, Ts):
+        r["centre"], r["max_dist"] = c, md
+        r["R"], r["T"] = np.ascontiguousarray(T[:3, :3].T).reshape(9), T[:3, 3]  # column-major, as given (a NaN keeps its bits)
+        if not np.all(np.isfinite(T[:3, :4])) or not pose_is_orthogonal(T[:3, :3]):
+            r["flags"] = 1
+            continue
+        terms, matched, considered, skipped = tsdf_track_terms(cells, lo, voxel, tr, D, k[:4], k[4:], T, md, st, mw, c)
+        r["S"] = [sum_exact_f32(t) for t in terms]
+        r["matched"], r["considered"], r["skipped"] = matched, considered, skipped
+    return out
+
+
+def tsdf_track(tsdf, lo, voxel, trunc, depth, camera, zrange, T_init, max_dist=None, stride=1, min_weight=1, centre=None, max_iters=30,
+               eps_t=1e-6, eps_r=1e-6, min_matched=12):
+    """revo_map_tsdf_track restated: Gauss-Newton in double over tsdf_track_records' records from T_init -> (T 4x4 float32, the record
+    at T, iterations, status).  centre None: tsdf_track_centre, the middle of the box."""
+    F = np.float32
+    cells = _tsdf_volume(tsdf)
+    T0 = np.asarray(T_init, F).reshape(4, 4)
+    if not np.all(np.isfinite(T0)):
+        raise ValueError("T_init is not finite")
+    if int(max_iters) < 1:
+        raise ValueError("max_iters must be >= 1")
+    if centre is None:
+        centre = tsdf_track_centre(lo, cells.shape, voxel)
+    evaluate = lambda T: tsdf_track_records(cells, lo, voxel, trunc, depth, camera, zrange, np.array(T, np.float64).astype(F), max_dist, stride,  # noqa: E731
+                                            min_weight, centre)[0]
+    return _gauss_newton(evaluate, T0, centre, max_iters, eps_t, eps_r, min_matched)
+
+
+def tsdf_track_file(path, views_dir, camera, zrange, depth_scale=5000.0, **params):
+    """`mapfile surface-track`: every frame of a `run_tum --map-views` / `--surface-views` folder (or one `mapfile surface-views`
+    wrote) tracked against the volume of the .npz `path` from the pose poses.txt lists for it -> [(time stamp, listed pose, refined
+    pose, record, iterations, status)].  params: tsdf_track's."""
+    import os
+    from . import tum
+    cells, lo, voxel, trunc, _ = read_tsdf(path, color=True)
+    stamps = [float(r[0]) for r in tum.read_associate(os.path.join(views_dir, "associate.txt"))]
+    out = []
+    for ts, (depth, T0, _) in zip(stamps, read_views(views_dir, camera, zrange, depth_scale)):
+        out.append((ts, T0) + tsdf_track(cells, lo, voxel, trunc, depth, camera, zrange, T0, **params))
+    return out
 
 
 # ---------------------------------------------------------------------------------- planning through the map (DESIGN 23) --
@@ -2366,6 +2527,34 @@ def main(argv=None):
                 print("%s: %d views of the surface in %s (%s colour%s)" % (val["-o"][0], n, pos[0], "with" if vol.color is not None else "without",
                                                                            ", normals" if with_normals else ""))
                 return 0
+        if cmd == "surface-track" and "-o" in args and "--views" in args:
+            opt = {"-o": 1, "--views": 1, "--stride": 1, "--max-dist": 1, "--min-weight": 1, "--camera": 4, "--zrange": 2, "--depth-scale": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1:
+                from . import vo
+                params = {name: conv(val[o][0]) for o, name, conv in (("--stride", "stride", int), ("--max-dist", "max_dist", float),
+                                                                       ("--min-weight", "min_weight", int)) if o in val}
+                camera = [float(x) for x in val.get("--camera", (525.0, 525.0, 319.5, 239.5))]  # the TUM default camera
+                zrange = [float(x) for x in val.get("--zrange", (0.1, 5.2))]
+                res = tsdf_track_file(pos[0], val["--views"][0], camera, zrange, float(val.get("--depth-scale", [5000.0])[0]), **params)
+                names = ("converged", "iteration limit", "lost")
+                with open(val["-o"][0], "w") as f:
+                    f.write("# timestamp matched considered skipped iterations status\n")
+                    for ts, _, _, rec, it, status in res:
+                        f.write("# %.6f %d %d %d %d %s\n" % (ts, rec["matched"], rec["considered"], rec["skipped"], it, names[status].replace(" ", "_")))
+                    f.write("".join(line + "\n" for line in vo.tum_lines([(ts, T) for ts, _, T, _, _, _ in res])))
+                print("%s: %d frames of %s tracked against %s: %d converged, %d lost, %d matched pixels"
+                      % (val["-o"][0], len(res), val["--views"][0], pos[0], sum(r[5] == ALIGN_CONVERGED for r in res),
+                         sum(r[5] == ALIGN_LOST for r in res), sum(int(r[3]["matched"]) for r in res)))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -2392,6 +2581,8 @@ def main(argv=None):
           "mesh TSDF.npz -o MESH.ply [--min-weight K] [--normals] [--colors] | "
           "surface-views TSDF.npz --poses POSES.txt --camera FX FY CX CY --size W H [--zrange ZMIN ZMAX] [--step M] [--min-weight K] [--max-steps N] "
           "[--depth-scale S] [--normals] -o DIR | "
+          "surface-track TSDF.npz --views DIR [--stride K] [--max-dist M] [--min-weight K] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] "
+          "[--depth-scale S] -o POSES.txt | "
           "ply FILE [OUT.ply]")
     return 2
 

@@ -35,6 +35,9 @@ at the end.  --surface-box I0 J0 K0 N0 N1 N2 is the box in voxel indices of the 
 before the run (default -128 -128 -32 256 256 256); surfaces outside it are not there, and the keyframes that confirm no cell of
 it are counted on stderr.  --surface-trunc M: the truncation distance in metres (default 4 voxel edges); --surface-min-weight K:
 the views a cell needs.  An error with --map-window and with --streams.  The pose file does not depend on it.
+--surface-track (with --surface) tracks every keyframe against the surface as it stands before it is fused (vo.REVO's surface_track,
+api.SurfaceVolume.track): a keyframe whose tracking converges is fused at the refined pose; surface_poses_<dataset>.txt
+gets the poses the keyframes were fused at.  The trajectory in poses_<dataset>.txt is the tracker's, unchanged.
 --surface-views DIR (with --surface) ray-casts the finished surface from the estimated pose of every keyframe, or with
 --surface-views-every K of every K-th tracked frame, on the GPU (api.SurfaceVolume.raycast, DESIGN 28: depth and colour from the
 sign change of the fused field, sub-voxel accurate and without holes) and writes the TUM-layout data set that --map-views writes
@@ -55,7 +58,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -189,6 +192,12 @@ def main(argv=None):
     if sviews_dir is not None and "--surface" not in argv:
         print("--surface-views ray-casts the TSDF surface: it needs --surface FILE.ply")
         return 2
+    surface_track = "--surface-track" in argv  # vo.REVO's surface_track: every keyframe tracked against the surface before it is fused
+    if surface_track:
+        argv = [a for a in argv if a != "--surface-track"]
+        if "--surface" not in argv:
+            print("--surface-track tracks the keyframes against the TSDF surface: it needs --surface FILE.ply")
+            return 2
     surface = None  # vo.REVO's surface: the coloured, shaded mesh of the keyframes' TSDF volume, written at the end of the run
     for opt, key, k, conv in (("--surface", "file", 1, str), ("--surface-box", "box", 6, int), ("--surface-trunc", "trunc", 1, float),
                               ("--surface-min-weight", "min_weight", 1, int)):
@@ -268,7 +277,7 @@ def main(argv=None):
             surf = api.SurfaceVolume(vmap, box[:3], box[3:], surface.get("trunc"), color=True)
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
                       mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances, carve=map_carve,
-                      surface=surf)
+                      surface=surf, surface_track=surface_track or None)
         nd = tum.default_decoders() if decoders is None else decoders
         rows = tum.read_associate(os.path.join(folder, io["associate"]), skip_first_n_frames=io["skip_first_n_frames"],
                                   read_n_images=io["read_n_images"])
@@ -301,6 +310,8 @@ def main(argv=None):
                           % drv.carve_skipped) if drv.carve_skipped else ""))
             if surf is not None:
                 _save_surface(surf, drv, surface, name, len(io["datasets"]) > 1)
+                if surface_track:
+                    _save_surface_tracks(drv, name)
                 if sviews_dir is not None:
                     _save_surface_views(surf, os.path.join(sviews_dir, name) if len(io["datasets"]) > 1 else sviews_dir, drv.poses,
                                         [kf for _, kf in res], sviews_every, io["depth_scale_factor"], surface.get("min_weight", 1))
@@ -332,6 +343,20 @@ def _save_surface(surf, drv, surface, name, per_dataset):
     if blind or drv.surface_skipped:
         print("Surface: %d of %d keyframes confirmed no cell of the box (their surfaces lie outside it); %d were not fused for their pose's rotation"
               % (blind, surf.views, drv.surface_skipped), file=sys.stderr)
+
+
+def _save_surface_tracks(drv, name):
+    """--surface-track: surface_poses_<dataset>.txt beside the pose file -- every keyframe's pose as it was fused into the surface, in
+    the pose file's format, behind one comment line per keyframe with its matched pixels and the tracking's status."""
+    from . import vo
+    names = ("converged", "iteration_limit", "lost")
+    with open("surface_poses_%s.txt" % name, "w") as f:
+        f.write("# timestamp matched considered status (lost, iteration_limit: fused at the tracker's pose)\n")
+        for ts, _, _, info, status in drv.surface_tracks:
+            f.write("# %.6f %d %d %s\n" % (ts, info.matched if info is not None else 0, info.considered if info is not None else 0, names[status]))
+        f.write("".join(line + "\n" for line in vo.tum_lines([(ts, T) for ts, _, T, _, _ in drv.surface_tracks])))
+    print("Surface track: %d of %d keyframes refined against the surface -> surface_poses_%s.txt"
+          % (sum(1 for t in drv.surface_tracks if t[4] == 0), len(drv.surface_tracks), name))
 
 
 def _rvm_path(map_save, name, per_dataset):

@@ -430,6 +430,22 @@ class MapTsdfRayInfo(C.Structure):
 assert (C.sizeof(MapTsdfRayParams), C.sizeof(MapTsdfRayInfo)) == (16, 64)
 
 
+class MapTsdfTrackParams(C.Structure):
+    """revo_map_tsdf_track_params (include/revo_hip.h), 32 bytes: the gate in metres (0: trunc / 2), the pixel stride (0: 1, at most
+    8), the views a cell needs (0 counts as 1) and the rotation centre."""
+    _fields_ = [("max_dist", C.c_float), ("stride", C.c_uint32), ("min_weight", C.c_uint32), ("centre", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class MapTsdfTrackInfo(C.Structure):
+    """revo_map_tsdf_track_info (include/revo_hip.h), 208 bytes, MapDfAlignInfo's layout: the 28 sums of tracking a depth frame against
+    the TSDF surface at a pose (the upper triangle of sum J J^T, sum J e, sum e e with J = (g, u x g), g the interpolant's gradient), the
+    exact counts and the inputs.  The gated pixels are considered - matched - skipped."""
+    _fields_ = list(MapDfAlignInfo._fields_)
+
+
+assert (C.sizeof(MapTsdfTrackParams), C.sizeof(MapTsdfTrackInfo)) == (32, 208)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

@@ -22,7 +22,7 @@ from .settings import PairInfo, StreamFrame, StreamResult, TrackerSettings
 
 class REVO:
     def __init__(self, settingsPyr, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False, carve=None, surface=None):
+                 mapDrawer=None, generate_dense_pcl=False, voxelMap=None, pair_info=False, carve=None, surface=None, surface_track=None):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         self.camPyr = cameraPyr or api.CameraPyr(settingsPyr, device=device)
@@ -64,6 +64,17 @@ class REVO:
                 raise ValueError("surface is not supported with a MapWindow: the volumes keep what the window evicts")
             if surface.map is not voxelMap:
                 raise ValueError("the surface belongs to another map than voxelMap")
+        # surface_track: True or a dict of api.SurfaceVolume.track's parameters (max_dist, stride, min_weight, centre, max_iters, eps_t,
+        # eps_r, min_matched): frame-to-model tracking.  Every keyframe is tracked against the surface as it stands, from
+        # its T_w_kf, before it is fused; where that converges the keyframe is fused at the refined pose, otherwise at T_w_kf (the
+        # first keyframes meet an empty volume: LOST, nothing changes).  surface_tracks[i]: (keyframe time stamp, T_w_kf, the pose it
+        # was fused at, the MapTsdfTrackInfo at the loop's last pose or None, status); a keyframe whose rotation fails the is_orthogonal
+        # rule is not tracked (info None, LOST).  The reported trajectory, the voxel map's integration and the carve keep T_w_kf.  Off
+        # by default: nothing new is enqueued.
+        self.surface_track = None if surface_track is None or surface_track is False else ({} if surface_track is True else dict(surface_track))
+        self.surface_tracks = []
+        if self.surface_track is not None and surface is None:
+            raise ValueError("surface_track needs a surface")
         # pair_info: every reported pose comes with its level-0 settings.PairInfo (the information matrix of the relative pose
         # curr -> keyframe at the final pose) and that keyframe's time stamp: pair_infos[i] belongs to poses[i]
         self.pair_info = bool(pair_info)
@@ -126,8 +137,21 @@ class REVO:
                     self._carve_with(kfPyr, T_w_kf)
                 self.voxelMap.integrate(kfPyr, T_w_kf)
                 if self.surface is not None:
-                    self._surface_with(kfPyr, T_w_kf)
+                    self._surface_with(kfPyr, T_w_kf if self.surface_track is None else self._surface_track_with(kfPyr, T_w_kf))
         return M, bool(kf.value)
+
+    def _surface_track_with(self, kfPyr, T_w_kf):
+        """The keyframe tracked against the surface as it stands -> the pose to fuse it at."""
+        from . import mapfile
+        T0 = np.asarray(T_w_kf, np.float32)
+        info, status, T = None, mapfile.ALIGN_LOST, T0
+        if mapfile.pose_is_orthogonal(T0[:3, :3]):
+            r = self.surface.track(kfPyr, T0, **self.surface_track)
+            info, status = r["info"], r["status"]
+            if status == mapfile.ALIGN_CONVERGED:
+                T = r["T"]
+        self.surface_tracks.append((kfPyr.returnTimestamp(), T0, T, info, status))
+        return T
 
     def _surface_with(self, kfPyr, T_w_kf):
         from . import mapfile
