@@ -416,6 +416,17 @@ __device__ __forceinline__ uint32_t run_fill(uint32_t C, uint32_t S) {  // S sub
   const uint32_t dn = __builtin_bitreverse32(((rC + rS) ^ rC) & rC);
   return up | dn | S;
 }
+// generateDistHistogram's count of a tile that spans more than three bitmap words (patches of 67 pixels and more, depending on
+// where in a word the tile starts): `patch` rows of words 0 .. last from `row`, the first masked by ma, the last by mb.  The
+// tiles of the reference's patch sizes (20, 10, 5) span at most two words and never come here.
+__device__ __forceinline__ int hist_wide_tile(const uint32_t* row, int pitch, int patch, int last, uint32_t ma, uint32_t mb) {
+  int cnt = 0;
+  for (int y = 0; y < patch; ++y, row += pitch) {
+    cnt += __popc(row[0] & ma) + __popc(row[last] & mb);
+    for (int k = 1; k < last; ++k) cnt += __popc(row[k]);
+  }
+  return cnt;
+}
 
 // (-DREVO_HYST_PROFILE: thread 0's clock after every phase, one printf per level-0 frame at the end.  The printf of workgroups
 // that finish early disturbs the LATE phases of the ones still running -- device printf is a host call -- so only the phases of
@@ -828,12 +839,14 @@ __device__ __forceinline__ void hyst_level(const PyrGeom& g, const FramePlanes& 
         ty += (ty + 1) * lv.hist_w <= t ? 1 : (ty * lv.hist_w > t ? -1 : 0);
         const int tx = t - ty * lv.hist_w;
         const int xa = tx * lv.patch, xb = xa + lv.patch;  // [xa, xb)
-        const int wa = xa >> 5, wb = (xb - 1) >> 5;        // patch <= 64: at most 3 words
+        const int wa = xa >> 5, wb = (xb - 1) >> 5;        // at most 3 words up to patch 66; beyond: hist_wide_tile
         const uint32_t ma = ~0u << (xa & 31), mb = (xb & 31) ? ~0u >> (32 - (xb & 31)) : ~0u;
         const uint32_t m0 = wa == wb ? ma & mb : ma, m1 = wb > wa + 1 ? ~0u : (wb > wa ? mb : 0u), m2 = wb > wa + 1 ? mb : 0u;
         const int o1 = wb > wa ? 1 : 0, o2 = wb > wa + 1 ? 2 : 0;
         const uint32_t* row = E + (ty * lv.patch + 1) * pitch + wa;
         int cnt = 0;
+        if (wb - wa > 2) cnt = hist_wide_tile(row, pitch, lv.patch, wb - wa, ma, mb);
+        else
         for (int y = 0; y < lv.patch; ++y, row += pitch) cnt += __popc(row[0] & m0) + __popc(row[o1] & m1) + __popc(row[o2] & m2);
         const uint8_t v = (uint8_t)(cnt & 255);
         pl.hist[l][(size_t)f * ntiles + t] = v;
@@ -1368,6 +1381,8 @@ __global__ void __launch_bounds__(HO_THREADS) k_hyst_out(PyrGeom g, FramePlanes 
       const int o1 = wb > wa ? 1 : 0, o2 = wb > wa + 1 ? 2 : 0;
       const uint32_t* row = E + (ty * lv.patch - br.R0) * pitch + wa;
       int cnt = 0;
+      if (wb - wa > 2) cnt = hist_wide_tile(row, pitch, lv.patch, wb - wa, ma, mb);
+      else
       for (int y = 0; y < lv.patch; ++y, row += pitch) cnt += __popc(row[0] & m0) + __popc(row[o1] & m1) + __popc(row[o2] & m2);
       const uint8_t v = (uint8_t)(cnt & 255);
       pl.hist[l][(size_t)f * lv.hist_w * lv.hist_h + (size_t)ty * lv.hist_w + tx] = v;
