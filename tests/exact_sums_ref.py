@@ -87,23 +87,30 @@ def point_terms(ref_table, pts, cam, R, T, edge_distance, use_edge_filter, huber
     return np.array(terms, np.float32).reshape(27, n_good), sw, r2, n_good, len(p) - n_good
 
 
-def eval_cost(ref_dt, pts, cam, R, T, edge_distance, use_edge_filter):
-    """TrackerNew::evalCostFunction (tracker.cpp:357-393) at a pose: the keyframe's distance transform [h, w] read at the FLOOR of
-    every projection (fx*X)/Z + cx, (fy*Y)/Z + cy that lies in 0 <= u < w, 0 <= v < h, filtered like the residual, summed in
-    float64 (exact for these terms whatever the order) and rounded to float once."""
+def cost_terms(ref_dt, pts, cam, R, T, edge_distance, use_edge_filter):
+    """TrackerNew::evalCostFunction's per-point terms (tracker.cpp:371-389) at a pose, one per point of pts: the keyframe's
+    distance transform [h, w] read at the FLOOR of the projection (fx*X)/Z + cx, (fy*Y)/Z + cy where that lies in 0 <= u < w,
+    0 <= v < h and the edge filter keeps it, else 0."""
     fx, fy, cx, cy = (f32(c) for c in cam[:4])
     w, h = int(cam[4]), int(cam[5])
     R = np.asarray(R, np.float32).reshape(3, 3)
     T = np.asarray(T, np.float32).reshape(3)
     p = np.asarray(pts, np.float32)
     W = [((R[r, 0] * p[:, 0] + R[r, 1] * p[:, 1]) + R[r, 2] * p[:, 2]) + T[r] for r in range(3)]
+    out = np.zeros(len(p), np.float32)
     with np.errstate(all="ignore"):
         u = (fx * W[0]) / W[2] + cx
         v = (fy * W[1]) / W[2] + cy
         inside = (u >= 0) & (u < f32(w)) & (v >= 0) & (v < f32(h))
         r = np.asarray(ref_dt, np.float32)[np.floor(v[inside]).astype(np.int64), np.floor(u[inside]).astype(np.int64)]
-    keep = ~((r > f32(edge_distance)) & bool(use_edge_filter))
-    return f32(r[keep].astype(np.float64).sum())
+    out[inside] = np.where((r > f32(edge_distance)) & bool(use_edge_filter), f32(0), r)
+    return out
+
+
+def eval_cost(ref_dt, pts, cam, R, T, edge_distance, use_edge_filter):
+    """TrackerNew::evalCostFunction (tracker.cpp:357-393) at a pose: cost_terms summed in float64 (exact for these terms
+    whatever the order) and rounded to float once."""
+    return f32(cost_terms(ref_dt, pts, cam, R, T, edge_distance, use_edge_filter).astype(np.float64).sum())
 
 
 def exact_eval(ref_table, pts, cam, R, T, edge_distance, use_edge_filter, huber):
