@@ -1755,6 +1755,78 @@ int revo_map_tsdf_track(revo_map* m, const revo_map_df_box* box, const revo_map_
                         const revo_map_tsdf_track_params* prm, const revo_map_align_opts* opt, float T_out[16],
                         revo_map_tsdf_track_info* info_out, int32_t* iterations, int32_t* status);
 
+/* ---- a box that follows the camera: exact shift, spill and refill of the surface volumes -----------------------
+ * revo_map_tsdf_fuse, _mesh, _raycast and _track take (box, volume) per call; these two calls move the box.  Everything is an
+ * integer that leaves the handle and comes back without loss, in ascending key order, and every output is a pure function of
+ * the input bytes.
+ *
+ * The record of one cell that has left a box: the cell's voxel index as the voxel map's packed key (21 bits per axis biased by
+ * 2^20, x highest: revo_map_voxel_raw's key, so ascending keys are ascending places in any box) and the bytes of its two cells;
+ * the four colour words are zero without a colour volume.
+ * A cell is EMPTY when every byte of its revo_map_tsdf_cell is zero and, with a colour volume, every byte of its
+ * revo_map_tsdf_color too (a cell with weight 0 and sum != 0 is not EMPTY).
+ * A cell FITS when, decided in 64 bits, weight <= 2^20, |sum| <= 2^30, colour weight <= 2^20 and each colour sum <= 255 * 2^20:
+ * what any sequence of fuse calls can leave.
+ * Exact properties: (a) revo_map_tsdf_shift by d, then by -d, then revo_map_tsdf_refill of the first shift's records restores the
+ * bytes of both volumes, for any bytes that FIT; (b) for d1, d2 with no opposite signs on any axis, a shift by d1 followed by one
+ * by d2 leaves the destination bytes of one shift by d1 + d2, and the two record lists merged by key are that shift's list;
+ * (c) no other call's bytes change. */
+typedef struct revo_map_tsdf_record {      /* 32 bytes, little-endian, no padding */
+  uint64_t key;                            /* the cell's voxel index, packed                  */
+  int32_t  sum;                            /* revo_map_tsdf_cell                              */
+  uint32_t weight;
+  uint32_t sum_b, sum_g, sum_r;            /* revo_map_tsdf_color; zero without a colour volume */
+  uint32_t color_weight;
+} revo_map_tsdf_record;
+typedef struct revo_map_tsdf_shift_info {  /* 64 bytes, little-endian, no padding */
+  uint64_t cells;        /* n[0]*n[1]*n[2]                                                       */
+  uint64_t staying;      /* source cells that lie in the destination box                         */
+  uint64_t leaving;      /* cells - staying                                                      */
+  uint64_t records;      /* leaving cells that are not EMPTY                                     */
+  uint64_t dropped;      /* of those, the cells a move without records discarded                 */
+  uint64_t reserved[3];  /* zero */
+} revo_map_tsdf_shift_info;
+/* The volumes of the box (box->lo, box->n) moved out of place into the volumes of the box (box->lo + delta, box->n): the
+ * destination cell c' receives the bytes of the source cell c' + delta when that cell lies in the source box (it is STAYING) and
+ * zero bytes otherwise; every other source cell is LEAVING, and every leaving cell that is not EMPTY gives one record, in
+ * ascending key order, the same bytes for host and device outputs (the order comes from a scan over the leaving cells in place
+ * order, never from arrival).  src_color and dst_color: both NULL (the TSDF volume alone) or both given.  device_tsdf: where the
+ * four volumes live; device_out: where records lives.  Host volumes are uploaded into the handle's buffers, the result is
+ * downloaded and the call waits.  Runs on the context's tracker stream; the map gives the context and the stream and is not changed.
+ *   records and n_records given: move and emit.  A counting pass runs first and the call waits for it; when cap_records is below
+ *       the count the call returns REVO_ERR_CAPACITY with nothing written but *n_records and info (the destination is untouched).
+ *   records NULL, n_records given: count only; the destination is not written (dst_tsdf must still be given).  The call waits.
+ *   both NULL: move and drop; the leaving cells are discarded and info->dropped counts those that were not EMPTY.  With device
+ *       volumes the call only enqueues.
+ * info (may be NULL) is a host pointer whenever the call waits; in the one case that only enqueues (move and drop with device
+ * volumes) it is a device pointer, 16-byte aligned.  delta = 0 is a copy without a record; |delta_i| >= n_i on any axis leaves a
+ * destination of zeros and every source cell leaving.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, delta, src_tsdf or dst_tsdf; exactly
+ * one of the colour volumes NULL; the box rules of revo_map_distance_field for the source or for the destination box (a
+ * destination that leaves the index range included); source and destination byte ranges that overlap (an in-place shift is not
+ * offered); records with a NULL n_records; a flag outside 0 / 1; a misaligned device pointer (16 bytes). */
+int revo_map_tsdf_shift(revo_map* m, const revo_map_df_box* box, const int32_t delta[3], const revo_map_tsdf_cell* src_tsdf,
+                        const revo_map_tsdf_color* src_color, revo_map_tsdf_cell* dst_tsdf, revo_map_tsdf_color* dst_color,
+                        int device_tsdf, revo_map_tsdf_record* records, size_t cap_records, size_t* n_records, int device_out,
+                        revo_map_tsdf_shift_info* info);
+
+typedef struct revo_map_tsdf_refill_info {  /* 32 bytes, little-endian, no padding */
+  uint64_t records;      /* n                                            */
+  uint64_t applied;      /* records whose key lies inside the box        */
+  uint64_t outside;      /* records - applied: ignored                   */
+  uint64_t reserved;     /* zero */
+} revo_map_tsdf_refill_info;
+/* Every record (n of them, device_in: where they live; n = 0 is valid and changes nothing) whose key lies inside the box is added
+ * to its cell: sum += sum, weight += weight, and with a colour volume the four colour words likewise.  Records outside the box
+ * are ignored and counted.  The records must be in strictly ascending key order, so keys are unique and no atomic touches a cell.
+ * All or nothing, as revo_map_subtract_raw is: a check pass runs first and the call waits for it, then the apply pass is enqueued
+ * (a host volume is uploaded, updated, downloaded and the call waits again).  info (may be NULL) is a host pointer.
+ * REVO_ERR_INVALID_ARG, with no byte of either volume changed: NULL m, box or tsdf, NULL records with n > 0, n above 2^30; the box
+ * rules; a flag outside 0 / 1; a misaligned device pointer (16 bytes); a key that is not ascending or has bit 63 set; a record
+ * with a colour word that is not zero when color is NULL; a record inside the box whose cell would not FIT afterwards. */
+int revo_map_tsdf_refill(revo_map* m, const revo_map_df_box* box, revo_map_tsdf_cell* tsdf, revo_map_tsdf_color* color, int device_tsdf,
+                         size_t n, const revo_map_tsdf_record* records, int device_in, revo_map_tsdf_refill_info* info);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

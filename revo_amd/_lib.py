@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -196,6 +196,8 @@ def lib():
     L.revo_map_tsdf_track_system.argtypes = [C.POINTER(MapTsdfTrackInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.revo_map_tsdf_track.argtypes = [vp, C.POINTER(MapDfBox), vp, C.c_int, C.c_float, C.POINTER(MapCarveView), C.c_int, f32p,
                                       C.POINTER(MapTsdfTrackParams), C.POINTER(MapAlignOpts), f32p, C.POINTER(MapTsdfTrackInfo), i32p, i32p]
+    L.revo_map_tsdf_shift.argtypes = [vp, C.POINTER(MapDfBox), i32p, vp, vp, vp, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, vp]
+    L.revo_map_tsdf_refill.argtypes = [vp, C.POINTER(MapDfBox), vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.POINTER(MapTsdfRefillInfo)]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfTrackParams, MapTsdfRayInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfTrackParams, MapTsdfRayInfo,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1143,6 +1143,120 @@ class VoxelMap:
                                                      C.byref(nv), C.byref(nt), 1, C.byref(info)))
         return nv.value, nt.value, {k: int(getattr(info, k)) for k in mapfile.MESH_INFO_KEYS}
 
+    @staticmethod
+    def _surface_tensors(d_tsdf, d_color, what):
+        if d_tsdf.dim() != 4 or d_tsdf.shape[3] != 2 or str(d_tsdf.dtype) != "torch.int32" or not (d_tsdf.is_contiguous() and d_tsdf.is_cuda):
+            raise ValueError("%s must be a contiguous int32 device tensor [n0, n1, n2, 2]" % what)
+        if d_color is not None and not (tuple(d_color.shape) == tuple(d_tsdf.shape[:3]) + (4,) and str(d_color.dtype) == "torch.int32"
+                                        and d_color.is_contiguous() and d_color.is_cuda):
+            raise ValueError("%s's colour volume must be a contiguous int32 device tensor [n0, n1, n2, 4] over its box" % what)
+
+    def shift_into(self, d_dst, d_src, lo, delta, d_dst_color=None, d_src_color=None, d_records=None, count_only=False, d_info=None):
+        """The surface volumes of the box at lo moved into the volumes of the box at lo + delta, between torch device tensors
+        (revo_map_tsdf_shift): d_src, d_dst int32 [n0, n1, n2, 2], the colour volumes int32 [n0, n1, n2, 4] (both or
+        neither); the move is out of place.  A cell that lies in both boxes keeps its bytes, an entering cell is zero, and
+        d_records: a contiguous device tensor of 32 bytes per record -- the leaving cells that are not EMPTY are written to it as
+              mapfile.TSDF_RECORD_DTYPE in ascending key order -> (records, info dict of mapfile.TSDF_SHIFT_INFO_KEYS); RevoError
+              (REVO_ERR_CAPACITY), with d_dst untouched, when it holds fewer.  The call waits for the count.
+        count_only: -> (records, info) without writing d_dst.
+        neither: the leaving cells are dropped and the call is only enqueued (sync() orders later reads); d_info: None or 64 bytes
+              on the device, revo_map_tsdf_shift_info with `dropped`.  -> None.
+        The move (and the emit pass) run on the map's stream behind the call: every tensor given must stay alive, and unwritten by
+        other streams, until the map's sync() -- torch's allocator does not know that stream."""
+        from . import mapfile
+        import torch
+        self._surface_tensors(d_src, d_src_color, "d_src")
+        self._surface_tensors(d_dst, d_dst_color, "d_dst")
+        if tuple(d_src.shape) != tuple(d_dst.shape):
+            raise ValueError("d_src and d_dst are volumes of boxes of one size")
+        if count_only and d_records is not None:
+            raise ValueError("count_only writes no records")
+        box = self._df_box(lo, tuple(d_src.shape[:3]), 0, 1)
+        dl = (C.c_int32 * 3)(*[int(x) for x in np.asarray(delta, np.int64).reshape(3)])
+        cap = 0
+        if d_records is not None:
+            if not (d_records.is_cuda and d_records.is_contiguous()):
+                raise ValueError("d_records must be a contiguous device tensor")
+            cap = d_records.numel() * d_records.element_size() // 32
+        drop = d_records is None and not count_only
+        if d_info is not None and not (drop and d_info.is_cuda and d_info.is_contiguous() and d_info.numel() * d_info.element_size() == 64):
+            raise ValueError("d_info is 64 bytes on the device and goes with a move that drops the leaving cells")
+        torch.cuda.current_stream(d_src.device).synchronize()  # the tensors' earlier use is over before the tracker stream touches them
+        ptr = lambda t_: vp(t_.data_ptr()) if t_ is not None else None  # noqa: E731
+        n, info = C.c_size_t(), MapTsdfShiftInfo()
+        check(_lib.lib().revo_map_tsdf_shift(self._h, C.byref(box), dl, ptr(d_src), ptr(d_src_color), ptr(d_dst), ptr(d_dst_color), 1,
+                                             ptr(d_records), cap, None if drop else C.byref(n), 1,
+                                             ptr(d_info) if drop else C.cast(C.byref(info), vp)))
+        if drop:
+            return None
+        return n.value, {k: int(getattr(info, k)) for k in mapfile.TSDF_SHIFT_INFO_KEYS}
+
+    def refill_into(self, d_tsdf, lo, d_records, n=None, d_color=None):
+        """Records added back into the cells of the box at lo, between torch device tensors (revo_map_tsdf_refill):
+        d_records a contiguous device tensor of 32 bytes per record (mapfile.TSDF_RECORD_DTYPE, strictly ascending keys), n how
+        many of them (default: all it holds).  Records outside the box are ignored.  All or nothing: RevoError
+        (REVO_ERR_INVALID_ARG), with both volumes unchanged, when the keys are out of order, a record carries colour without
+        d_color, or a cell would pass the sums a fuse can reach.  The call waits for its check and enqueues the update on the map's
+        stream: d_records (and the volumes) must stay alive until the map's sync() -- torch's allocator does not know that stream,
+        and a tensor dropped earlier may be handed out again while the update still reads it.
+        -> info dict of mapfile.TSDF_REFILL_INFO_KEYS."""
+        from . import mapfile
+        import torch
+        self._surface_tensors(d_tsdf, d_color, "d_tsdf")
+        box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
+        if d_records is None:
+            n = 0
+        else:
+            if not (d_records.is_cuda and d_records.is_contiguous()):
+                raise ValueError("d_records must be a contiguous device tensor")
+            cap = d_records.numel() * d_records.element_size() // 32
+            n = cap if n is None else int(n)
+            if n < 0 or n > cap:
+                raise ValueError("d_records holds %d records, not %d" % (cap, n))
+        torch.cuda.current_stream(d_tsdf.device).synchronize()
+        info = MapTsdfRefillInfo()
+        check(_lib.lib().revo_map_tsdf_refill(self._h, C.byref(box), vp(d_tsdf.data_ptr()), vp(d_color.data_ptr()) if d_color is not None else None, 1,
+                                              n, vp(d_records.data_ptr()) if n else None, 1, C.byref(info)))
+        return {k: int(getattr(info, k)) for k in mapfile.TSDF_REFILL_INFO_KEYS}
+
+    def surface_shift(self, cells, lo, delta, color=None, records=True):
+        """revo_map_tsdf_shift on host volumes (numpy, mapfile's dtypes): -> (cells2, color2, records, info) as
+        mapfile.tsdf_shift_records gives them; records=False drops the leaving cells (records is None, info counts `dropped`)."""
+        from . import mapfile
+        cells = np.ascontiguousarray(mapfile._tsdf_volume(cells))
+        color = None if color is None else np.ascontiguousarray(mapfile._tsdf_color_volume(color, cells.shape))
+        box = self._df_box(lo, cells.shape, 0, 1)
+        dl = (C.c_int32 * 3)(*[int(x) for x in np.asarray(delta, np.int64).reshape(3)])
+        out = np.zeros(cells.shape, mapfile.TSDF_CELL_DTYPE)
+        cout = None if color is None else np.zeros(cells.shape, mapfile.TSDF_COLOR_DTYPE)
+        hp = lambda a: a.ctypes.data_as(vp) if a is not None else None  # noqa: E731
+        L, n, info = _lib.lib(), C.c_size_t(), MapTsdfShiftInfo()
+        args = (self._h, C.byref(box), dl, hp(cells), hp(color), hp(out), hp(cout), 0)
+        rec = None
+        if records:
+            check(L.revo_map_tsdf_shift(*args, None, 0, C.byref(n), 0, C.cast(C.byref(info), vp)))
+            rec = np.zeros(n.value, mapfile.TSDF_RECORD_DTYPE)
+            if n.value:
+                check(L.revo_map_tsdf_shift(*args, rec.ctypes.data_as(vp), n.value, C.byref(n), 0, C.cast(C.byref(info), vp)))
+            else:  # nothing to emit: the move alone
+                check(L.revo_map_tsdf_shift(*args, None, 0, None, 0, C.cast(C.byref(info), vp)))
+        else:
+            check(L.revo_map_tsdf_shift(*args, None, 0, None, 0, C.cast(C.byref(info), vp)))
+        return out, cout, rec, {k: int(getattr(info, k)) for k in mapfile.TSDF_SHIFT_INFO_KEYS}
+
+    def surface_refill(self, cells, lo, records, color=None):
+        """revo_map_tsdf_refill on host volumes and records (numpy): -> (cells2, color2, info) as mapfile.tsdf_refill_records gives
+        them; the inputs are not changed.  RevoError (REVO_ERR_INVALID_ARG) where that one raises ValueError."""
+        from . import mapfile
+        out = np.array(mapfile._tsdf_volume(cells), copy=True, order="C")
+        cout = None if color is None else np.array(mapfile._tsdf_color_volume(color, out.shape), copy=True, order="C")
+        rec = np.ascontiguousarray(mapfile.tsdf_record_array(records))
+        box = self._df_box(lo, out.shape, 0, 1)
+        info = MapTsdfRefillInfo()
+        check(_lib.lib().revo_map_tsdf_refill(self._h, C.byref(box), out.ctypes.data_as(vp), cout.ctypes.data_as(vp) if cout is not None else None, 0,
+                                              len(rec), rec.ctypes.data_as(vp) if len(rec) else None, 0, C.byref(info)))
+        return out, cout, {k: int(getattr(info, k)) for k in mapfile.TSDF_REFILL_INFO_KEYS}
+
     # -- views of the surface (revo_map_tsdf_raycast, DESIGN 28)
     def _surface_views(self, poses, camera, size, zrange):
         """-> (MapView array, n, single) for the poses (one 4x4 camera -> world pose, or a list / (n, 4, 4) array of 1 .. 64);
@@ -1914,10 +2028,11 @@ class TsdfVolume:
 
 
 class SurfaceVolume:
-    """The surface of a running sequence: the two device volumes of a box that is decided before the run and does not
-    move, cleared on creation.  integrate(view) is one accumulating fuse call, enqueued only; volume() downloads a TsdfVolume;
+    """The surface of a running sequence: the two device volumes of a box that is decided before the run, cleared on
+    creation.  integrate(view) is one accumulating fuse call, enqueued only; volume() downloads a TsdfVolume;
     mesh() meshes on the device.  vo.REVO(surface=) feeds it every keyframe.  lo, n: the box in voxel indices of the map's world
-    frame; trunc: metres (default 4 voxel edges); color=False keeps the TSDF volume alone."""
+    frame; trunc: metres (default 4 voxel edges); color=False keeps the TSDF volume alone.  The box moves only when shift() is
+    called; FollowingSurface calls it as the camera goes."""
 
     def __init__(self, map, lo, n, trunc=None, color=True):
         import torch
@@ -2020,6 +2135,154 @@ class SurfaceVolume:
         """The frame's camera pose refined against the surface as it stands, from T_init (VoxelMap.surface_track on the device
         volume) -> dict of T, info, iterations, status, cov, sigma2 and centre."""
         return self.map.surface_track(self.d_tsdf, self.lo, self.trunc, frame, T_init, max_dist, stride, min_weight, centre, **opts)
+
+    def shift(self, delta, spill=True):
+        """The box moved by delta cells (VoxelMap.shift_into): the volumes are moved out of place into a second pair of
+        device volumes, allocated at the first shift, and the pairs are swapped; lo += delta.  spill=True -> the cells that left and
+        were not EMPTY, as mapfile.TSDF_RECORD_DTYPE in ascending key order (the call waits for them); spill=False drops them, is
+        only enqueued and returns None.  shift_info: the last shift's counters (None after a dropping one).
+        The records go through a device buffer that is kept and only grows: a shift emits straight into it (one counting pass); only
+        when it holds fewer records than leave (REVO_ERR_CAPACITY, nothing moved) is the shift counted, the buffer grown to that
+        count and the shift made again."""
+        import torch
+        from . import mapfile
+        d = np.asarray(delta, np.int64).reshape(3)
+        mapfile.check_box(self.lo.astype(np.int64) + d, self.n)
+        if getattr(self, "_alt", None) is None:
+            self._alt = (torch.empty_like(self.d_tsdf), None if self.d_color is None else torch.empty_like(self.d_color))
+        a_t, a_c = self._alt
+        rec, info = None, None
+        if spill:
+            args = (a_t, self.d_tsdf, self.lo, d, a_c, self.d_color)
+            done = False
+            if getattr(self, "_spill", None) is not None:
+                try:
+                    n, info = self.map.shift_into(*args, d_records=self._spill)
+                    done = True
+                except RevoError as e:
+                    if e.code != -5:  # REVO_ERR_CAPACITY: nothing was moved
+                        raise
+            if not done:
+                n, info = self.map.shift_into(*args, count_only=True)
+                self._spill = torch.empty(32 * max(n, 1), dtype=torch.uint8, device=self.d_tsdf.device)
+                n, info = self.map.shift_into(*args, d_records=self._spill)
+            self.map.sync()
+            rec = self._spill[:32 * n].cpu().numpy().view(mapfile.TSDF_RECORD_DTYPE).copy()
+        else:
+            self.map.shift_into(a_t, self.d_tsdf, self.lo, d, a_c, self.d_color)
+        self._alt = (self.d_tsdf, self.d_color)
+        self.d_tsdf, self.d_color = a_t, a_c
+        self.lo = (self.lo.astype(np.int64) + d).astype(np.int32)
+        self.shift_info = info
+        return rec
+
+    def refill(self, records):
+        """Records (mapfile.TSDF_RECORD_DTYPE, strictly ascending keys) added back into the cells of the box as it stands
+        (VoxelMap.refill_into): all or nothing -> the dict of mapfile.TSDF_REFILL_INFO_KEYS.  Waits for the map's stream: the
+        update reads a device copy of the records that this call owns and lets go of."""
+        import torch
+        from . import mapfile
+        rec = np.ascontiguousarray(mapfile.tsdf_record_array(records))
+        if len(rec) == 0:
+            return {"records": 0, "applied": 0, "outside": 0}
+        d_rec = torch.from_numpy(rec.view(np.uint8).copy()).to(self.d_tsdf.device)
+        try:
+            return self.map.refill_into(self.d_tsdf, self.lo, d_rec, len(rec), self.d_color)
+        finally:
+            self.map.sync()  # d_rec goes back to torch's allocator only behind the update that reads it
+
+
+class FollowingSurface(SurfaceVolume):
+    """A SurfaceVolume whose box follows the camera: n cells per axis, placed by mapfile.follow_lo -- centred `ahead`
+    metres (default n[2] * voxel / 2) along the camera's z axis and snapped to multiples of `step` cells.  follow(T_w_c) moves the
+    box when the policy's answer differs from lo: the cells that leave go to `store` (a mapfile.SurfaceStore, by default a fresh
+    one), the store's records inside the new box come back into it.  integrate(view) follows the view's pose and then fuses, so
+    vo.REVO(surface=FollowingSurface(...)) works as with a SurfaceVolume.  shifts: how often the box has moved.  Until the first
+    follow the box sits where the identity pose puts it; the first follow places it without a move, since nothing is fused yet.
+    assemble() is the whole surface, mesh() its mesh.  MultiREVO, an in-place shift and a pyramid of volumes are not part of it."""
+
+    def __init__(self, map, n, trunc=None, color=True, step=16, ahead=None, store=None):
+        from . import mapfile
+        n = np.asarray(n, np.int64).reshape(3)
+        self.step = int(step)
+        self.ahead = float(n[2]) * float(map.voxel) / 2.0 if ahead is None else float(ahead)
+        super().__init__(map, mapfile.follow_lo(np.eye(4, dtype=np.float32), n, map.voxel, self.ahead, self.step), n, trunc, color)
+        self.store = store if store is not None else mapfile.SurfaceStore(voxel=map.voxel, trunc=self.trunc)
+        self.store.check(map.voxel, self.trunc)  # a given store must be of this voxel edge and truncation
+        if self.store.voxel is None:
+            self.store.voxel = float(np.float32(map.voxel))
+        if self.store.trunc is None:
+            self.store.trunc = self.trunc
+        self.shifts = 0
+        self._placed = False
+
+    def _take_back(self):
+        """The store's records inside the box, into the box.  All or nothing: a refill that is refused (a store of the caller's whose
+        records do not FIT on top of the box, or hold colour the surface has no volume for) leaves them in the store."""
+        back = self.store.take(self.lo, self.n)
+        if len(back) == 0:
+            return
+        try:
+            if self.d_color is None and any(np.any(back[k] != 0) for k in ("sum_b", "sum_g", "sum_r", "color_weight")):
+                raise ValueError("the store holds colour and the surface was created without colour")
+            super().refill(back)
+        except Exception:
+            self.store.add(back)
+            raise
+
+    def follow(self, T_w_c):
+        """The box goes where mapfile.follow_lo puts it for the pose -> True when it moved."""
+        from . import mapfile
+        lo = mapfile.follow_lo(T_w_c, self.n, self.map.voxel, self.ahead, self.step)
+        if not self._placed:
+            self._placed = True
+            self.lo = lo.astype(np.int32)
+            self._take_back()
+            return False
+        d = lo - self.lo.astype(np.int64)
+        if not d.any():
+            return False
+        self.store.add(self.shift(d, spill=True))
+        self._take_back()
+        self.shifts += 1
+        return True
+
+    def refill(self, records):
+        self._placed = True
+        return super().refill(records)
+
+    def integrate(self, view):
+        """follow(the view's pose), then SurfaceVolume.integrate."""
+        self.follow(view[1])
+        super().integrate(view)
+
+    def assemble(self, lo=None, n=None):
+        """The store plus the box as it stands -> TsdfVolume over the box (lo, n), by default the bounds of both; ValueError with a
+        message when that is more than one volume holds (an axis above 1024 cells or more than 2^27 cells).  Nothing is changed."""
+        from . import mapfile
+        cur = self.volume()
+        b = self.store.bounds()
+        b_lo = self.lo.astype(np.int64) if b is None else np.minimum(b[0], self.lo)
+        b_hi = self.lo.astype(np.int64) + self.n if b is None else np.maximum(b[0] + b[1], self.lo.astype(np.int64) + self.n)
+        lo, n = mapfile.surface_assemble_box((b_lo, b_hi - b_lo), lo, n)
+        cells, color = self.store.volume(lo, n)
+        a = np.maximum(lo, self.lo)                      # the part of the current box inside (lo, n)
+        e = np.minimum(lo + n, self.lo.astype(np.int64) + self.n)
+        if np.all(e > a):
+            dst = tuple(slice(int(a[k] - lo[k]), int(e[k] - lo[k])) for k in range(3))
+            src = tuple(slice(int(a[k] - self.lo[k]), int(e[k] - self.lo[k])) for k in range(3))
+            for k in ("sum", "weight"):
+                cells[k][dst] += cur.cells[k][src]
+            if cur.color is not None:
+                for k in ("sum_b", "sum_g", "sum_r", "weight"):
+                    color[k][dst] += cur.color[k][src]
+        return TsdfVolume(cells, lo.astype(np.int32), self.map.voxel, self.trunc, map=self.map, color=color if self.d_color is not None else None)
+
+    def mesh(self, min_weight=1, normals=True, colors=True):
+        """The mesh of assemble() -> mapfile.Mesh; ValueError as assemble() when the surface does not fit one volume."""
+        if colors and self.d_color is None:
+            raise ValueError("the surface was created without colour")
+        return self.assemble().mesh(min_weight, normals, colors)
 
 
 def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
@@ -2391,6 +2654,19 @@ class MapWindow:
 
     def surface_track(self, *args, **kw):
         return self.map.surface_track(*args, **kw)
+
+    def shift_into(self, *args, **kw):
+        """The inner map's shift_into: surface volumes moved with their box (the window's voxels play no part)."""
+        return self.map.shift_into(*args, **kw)
+
+    def refill_into(self, *args, **kw):
+        return self.map.refill_into(*args, **kw)
+
+    def surface_shift(self, *args, **kw):
+        return self.map.surface_shift(*args, **kw)
+
+    def surface_refill(self, *args, **kw):
+        return self.map.surface_refill(*args, **kw)
 
     def carve(self, *args, **kw):
         """Not supported: the window evicts a keyframe by subtracting the records it kept of it, and a carved voxel has lost

@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip, revo_map_tsdf_follow.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -289,6 +289,13 @@ struct MapTsdfTrackScratch {
   DevBuf work, frame, out;
 };
 
+// revo_map_tsdf_shift / revo_map_tsdf_refill (revo_map_tsdf_follow.hip): the counter line and the block totals of the
+// leaving cells, the device copy of a host destination (both volumes) and the device records of a host-side record list.  Only
+// these two calls go through them; a host source volume goes through the handle's tsdfvol and tsdfcol.
+struct MapTsdfFollowScratch {
+  DevBuf work, dst, dstcol, recs;
+};
+
 struct revo_map {
   revo_ctx* ctx = nullptr;
   MapCtxGeom g{};
@@ -350,6 +357,8 @@ struct revo_map {
   HostRows<TsdfRayView> tsdfray_views;
   // revo_map_tsdf_track_eval / revo_map_tsdf_track: everything of theirs, in a type of its own
   MapTsdfTrackScratch tsdftrk;
+  // revo_map_tsdf_shift / revo_map_tsdf_refill: everything of theirs, in a type of its own
+  MapTsdfFollowScratch tsdffol;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every

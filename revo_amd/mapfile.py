@@ -1970,6 +1970,276 @@ def tsdf_track_file(path, views_dir, camera, zrange, depth_scale=5000.0, **param
     return out
 
 
+# ----------------------------------------------------------------------------- a box that follows the camera --
+TSDF_RECORD_DTYPE = np.dtype([("key", "<u8"), ("sum", "<i4"), ("weight", "<u4"), ("sum_b", "<u4"), ("sum_g", "<u4"), ("sum_r", "<u4"),
+                              ("color_weight", "<u4")])  # revo_map_tsdf_record
+TSDF_SHIFT_INFO_KEYS = ("cells", "staying", "leaving", "records", "dropped")
+TSDF_REFILL_INFO_KEYS = ("records", "applied", "outside")
+TSDF_SUM_MAX = 1 << 30          # |sum| of a cell that FITS
+TSDF_COLOR_MAX = 255 << 20      # a colour sum of a cell that FITS
+SURFACE_ASSEMBLE_MAX_N = DF_MAX_N
+SURFACE_ASSEMBLE_MAX_CELLS = DF_MAX_CELLS
+_RECORD_COLOR = (("sum_b", "sum_b"), ("sum_g", "sum_g"), ("sum_r", "sum_r"), ("color_weight", "weight"))  # record field, colour cell field
+
+
+def pack_keys(idx):
+    """The packed keys (uint64) of [N, 3] voxel indices, each in [-2^20, 2^20 - 1]: 21 bits per axis biased by 2^20, x highest."""
+    k = (np.asarray(idx, np.int64).reshape(-1, 3) + (1 << 20)).astype(np.uint64)
+    return (k[:, 0] << np.uint64(42)) | (k[:, 1] << np.uint64(21)) | k[:, 2]
+
+
+def tsdf_record_array(records):
+    """records as a 1-D TSDF_RECORD_DTYPE array (an array of that dtype, or bytes of whole records)."""
+    if isinstance(records, (bytes, bytearray, memoryview)):
+        records = np.frombuffer(bytes(records), TSDF_RECORD_DTYPE)
+    rec = np.asarray(records)
+    if rec.dtype != TSDF_RECORD_DTYPE or rec.ndim != 1:
+        raise ValueError("surface records are a 1-D array of TSDF_RECORD_DTYPE")
+    return rec
+
+
+def _tsdf_cells_nonempty(cells, color):
+    ne = (cells["sum"] != 0) | (cells["weight"] != 0)
+    if color is not None:
+        for k in ("sum_b", "sum_g", "sum_r", "weight"):
+            ne |= color[k] != 0
+    return ne
+
+
+def _tsdf_cells_to_records(idx, cells, color):
+    """The records of the cells at the voxel indices idx [N, 3] (cells, color: [N] arrays; color may be None), in key order."""
+    rec = np.zeros(len(cells), TSDF_RECORD_DTYPE)
+    rec["key"] = pack_keys(idx)
+    rec["sum"], rec["weight"] = cells["sum"], cells["weight"]
+    if color is not None:
+        for rk, ck in _RECORD_COLOR:
+            rec[rk] = color[ck]
+    return rec[np.argsort(rec["key"], kind="stable")]
+
+
+def tsdf_volume_records(cells, color, lo):
+    """Every cell of the box (lo, cells.shape) that is not EMPTY, as TSDF_RECORD_DTYPE in ascending key order."""
+    cells = _tsdf_volume(cells)
+    if color is not None:
+        color = _tsdf_color_volume(color, cells.shape)
+    lo, _ = check_box(lo, cells.shape)
+    mask = _tsdf_cells_nonempty(cells, color)
+    return _tsdf_cells_to_records(np.argwhere(mask) + lo, cells[mask], None if color is None else color[mask])
+
+
+def tsdf_shift_records(cells, color, lo, delta):
+    """revo_map_tsdf_shift's contract in numpy: the volumes of the box (lo, cells.shape) moved into the volumes of the box
+    (lo + delta, same shape).  color: the colour volume or None.  -> (cells2, color2, records, info): the destination volumes (an
+    entering cell is zero), the leaving cells that are not EMPTY as TSDF_RECORD_DTYPE in ascending key order, and the dict of
+    TSDF_SHIFT_INFO_KEYS (dropped is 0: the records are returned).  ValueError as the library's REVO_ERR_INVALID_ARG."""
+    cells = _tsdf_volume(cells)
+    if color is not None:
+        color = _tsdf_color_volume(color, cells.shape)
+    lo, n = check_box(lo, cells.shape)
+    d = np.asarray(delta, np.int64).reshape(3)
+    check_box(lo + d, n)
+    out = np.zeros(cells.shape, TSDF_CELL_DTYPE)
+    cout = None if color is None else np.zeros(cells.shape, TSDF_COLOR_DTYPE)
+    leaving = np.ones(cells.shape, bool)
+    if np.all(np.abs(d) < n):
+        src = tuple(slice(int(max(0, d[k])), int(min(n[k], n[k] + d[k]))) for k in range(3))
+        dst = tuple(slice(int(max(0, -d[k])), int(min(n[k], n[k] - d[k]))) for k in range(3))
+        out[dst] = cells[src]
+        if color is not None:
+            cout[dst] = color[src]
+        leaving[src] = False
+    mask = leaving & _tsdf_cells_nonempty(cells, color)
+    idx = np.argwhere(mask) + lo
+    rec = _tsdf_cells_to_records(idx, cells[mask], None if color is None else color[mask])
+    total = int(cells.size)
+    n_leaving = int(leaving.sum())
+    info = {"cells": total, "staying": total - n_leaving, "leaving": n_leaving, "records": len(rec), "dropped": 0}
+    return out, cout, rec, info
+
+
+def tsdf_refill_records(cells, color, lo, records):
+    """revo_map_tsdf_refill's contract in numpy: every record whose key lies inside the box (lo, cells.shape) added to its cell.
+    -> (cells2, color2, info dict of TSDF_REFILL_INFO_KEYS); the inputs are not changed.  ValueError where the library refuses: keys
+    that are not strictly ascending (or with bit 63 set), colour words without a colour volume, a cell that would not FIT."""
+    cells = _tsdf_volume(cells)
+    if color is not None:
+        color = _tsdf_color_volume(color, cells.shape)
+    lo, n = check_box(lo, cells.shape)
+    rec = tsdf_record_array(records)
+    key = rec["key"]
+    if np.any(key >> np.uint64(63)) or np.any(key[1:] <= key[:-1]):
+        raise ValueError("surface records must be in strictly ascending key order")
+    if color is None and any(np.any(rec[rk] != 0) for rk, _ in _RECORD_COLOR):
+        raise ValueError("a record carries colour words and there is no colour volume")
+    c = key_axes(key) - lo
+    inside = np.all((c >= 0) & (c < n), axis=1)
+    ci = tuple(c[inside].T)
+    r = rec[inside]
+    s = cells["sum"][ci].astype(np.int64) + r["sum"].astype(np.int64)
+    w = cells["weight"][ci].astype(np.int64) + r["weight"].astype(np.int64)
+    bad = (np.abs(s) > TSDF_SUM_MAX) | (w > TSDF_W_MAX)
+    cs = {}
+    if color is not None:
+        for rk, ck in _RECORD_COLOR:
+            cs[ck] = color[ck][ci].astype(np.int64) + r[rk].astype(np.int64)
+            bad |= cs[ck] > (TSDF_W_MAX if ck == "weight" else TSDF_COLOR_MAX)
+    if np.any(bad):
+        raise ValueError("a cell would pass the sums a fuse can reach")
+    out = cells.copy()
+    out["sum"][ci] = s.astype(np.int32)
+    out["weight"][ci] = w.astype(np.uint32)
+    cout = None
+    if color is not None:
+        cout = color.copy()
+        for ck, v in cs.items():
+            cout[ck][ci] = v.astype(np.uint32)
+    return out, cout, {"records": len(rec), "applied": int(inside.sum()), "outside": int(len(rec) - inside.sum())}
+
+
+def follow_lo(T_w_c, n, voxel, ahead, step):
+    """The following policy, one pure function: the first voxel index of the box of n cells that a camera at T_w_c (4x4,
+    the float32 pose; computed in float64) should be in -- centred `ahead` metres along the camera's z axis, snapped down to a
+    multiple of `step` cells per axis, and clamped so the box stays inside the index range [-2^20, 2^20 - 1]."""
+    T = np.asarray(np.asarray(T_w_c, np.float32).reshape(4, 4), np.float64)
+    n = np.asarray(n, np.int64).reshape(3)
+    step = int(step)
+    if step < 1:
+        raise ValueError("step must be >= 1 cell")
+    if not np.all(np.isfinite(T)):
+        raise ValueError("the pose is not finite")
+    v = float(np.float32(voxel))
+    p = T[:3, 3] + float(ahead) * T[:3, 2]
+    want = np.floor(p / v).astype(np.int64) - n // 2
+    lo = step * np.floor_divide(want, step)
+    return np.clip(lo, -(1 << 20), (1 << 20) - n).astype(np.int64)
+
+
+class SurfaceStore:
+    """Everything that has left a following surface's box: TSDF_RECORD_DTYPE records, sparse, in ascending key order
+    with unique keys.  voxel, trunc: what the records were fused with (None until known); they travel with save / load."""
+
+    def __init__(self, records=None, voxel=None, trunc=None):
+        self.records = np.zeros(0, TSDF_RECORD_DTYPE)
+        self.voxel = None if voxel is None else float(np.float32(voxel))
+        self.trunc = None if trunc is None else float(np.float32(trunc))
+        if records is not None:
+            self.add(records)
+
+    def __len__(self):
+        return len(self.records)
+
+    def add(self, records):
+        """Records into the store; records with equal keys (in the store or among themselves) are summed field by field.  All or
+        nothing: ValueError, with the store unchanged, when a key has bit 63 set or a summed cell would not FIT."""
+        rec = tsdf_record_array(records)
+        if len(rec) == 0:
+            return
+        if np.any(rec["key"] >> np.uint64(63)):
+            raise ValueError("a surface record's key has bit 63 set")
+        both = np.concatenate([self.records, rec])
+        keys, inv = np.unique(both["key"], return_inverse=True)
+        out = np.zeros(len(keys), TSDF_RECORD_DTYPE)
+        out["key"] = keys
+        for k in TSDF_RECORD_DTYPE.names[1:]:
+            acc = np.zeros(len(keys), np.int64)
+            np.add.at(acc, inv, both[k].astype(np.int64))
+            limit = TSDF_SUM_MAX if k == "sum" else TSDF_W_MAX if k in ("weight", "color_weight") else TSDF_COLOR_MAX
+            if np.any(np.abs(acc) > limit):
+                raise ValueError("a cell of the store would pass the sums a fuse can reach")
+            out[k] = acc.astype(TSDF_RECORD_DTYPE[k])
+        self.records = out
+
+    def _inside(self, lo, n):
+        lo, n = check_box(lo, n)
+        c = key_axes(self.records["key"]) - lo
+        return np.all((c >= 0) & (c < n), axis=1)
+
+    def take(self, lo, n):
+        """The records inside the box (lo, n), in key order; they leave the store."""
+        inside = self._inside(lo, n)
+        out = self.records[inside]
+        self.records = self.records[~inside]
+        return out
+
+    def bounds(self):
+        """(lo [3], n [3]) int64 of the smallest box that holds every record, or None for an empty store."""
+        if len(self.records) == 0:
+            return None
+        k = key_axes(self.records["key"])
+        return k.min(0), k.max(0) - k.min(0) + 1
+
+    def check(self, voxel=None, trunc=None):
+        """ValueError when the store's voxel edge or truncation distance is known, given, and another."""
+        for mine, given, name in ((self.voxel, voxel, "voxel edge"), (self.trunc, trunc, "truncation distance")):
+            if mine is not None and given is not None and np.float32(mine) != np.float32(given):
+                raise ValueError("the store's %s is %g, not %g" % (name, mine, given))
+
+    def volume(self, lo, n, voxel=None, trunc=None):
+        """(cells, color) dense over the box (lo, n): the store's records inside it, zeros elsewhere; the store keeps them.  voxel,
+        trunc: checked against the store's where both are known (check)."""
+        self.check(voxel, trunc)
+        lo, n = check_box(lo, n)
+        shape = tuple(int(x) for x in n)
+        cells, color = np.zeros(shape, TSDF_CELL_DTYPE), np.zeros(shape, TSDF_COLOR_DTYPE)
+        inside = self._inside(lo, n)
+        r = self.records[inside]
+        ci = tuple((key_axes(r["key"]) - lo).T)
+        cells["sum"][ci], cells["weight"][ci] = r["sum"], r["weight"]
+        for rk, ck in _RECORD_COLOR:
+            color[ck][ci] = r[rk]
+        return cells, color
+
+    def save(self, path):
+        """The .npz of a store: records (TSDF_RECORD_DTYPE), voxel and trunc (float32; NaN when not known)."""
+        with open(path, "wb") as f:
+            np.savez(f, records=self.records, voxel=np.float32(np.nan if self.voxel is None else self.voxel),
+                     trunc=np.float32(np.nan if self.trunc is None else self.trunc))
+        return path
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            if not all(k in z.files for k in ("records", "voxel", "trunc")):
+                raise ValueError("%s is not a surface store (records, voxel, trunc)" % path)
+            rec, voxel, trunc = z["records"], float(z["voxel"]), float(z["trunc"])
+        if rec.dtype != TSDF_RECORD_DTYPE or rec.ndim != 1:
+            raise ValueError("%s: the records are not TSDF_RECORD_DTYPE" % path)
+        if np.any(rec["key"] >> np.uint64(63)) or np.any(rec["key"][1:] <= rec["key"][:-1]):
+            raise ValueError("%s: the records are not in strictly ascending key order" % path)
+        s = cls(None, None if np.isnan(voxel) else voxel, None if np.isnan(trunc) else trunc)
+        s.records = rec
+        return s
+
+
+def surface_assemble_box(bounds, lo=None, n=None):
+    """The box a store (and what goes with it) is assembled over: (lo, n) as given, or the bounds; ValueError with a message when
+    there is nothing to assemble or the box is larger than a volume may be (1024 cells per axis, 2^27 cells)."""
+    if (lo is None) != (n is None):
+        raise ValueError("give both lo and n, or neither (the store's bounds)")
+    if lo is None:
+        if bounds is None:
+            raise ValueError("the store is empty: there is no surface to assemble")
+        lo, n = bounds
+    lo, n = np.asarray(lo, np.int64).reshape(3), np.asarray(n, np.int64).reshape(3)
+    if np.any(n > SURFACE_ASSEMBLE_MAX_N):
+        raise ValueError("the surface spans %s cells: an axis of more than %d cells does not fit one volume (give a smaller box; the "
+                         "store keeps everything)" % (n.tolist(), SURFACE_ASSEMBLE_MAX_N))
+    if np.all(n >= 1) and int(n[0]) * int(n[1]) * int(n[2]) > SURFACE_ASSEMBLE_MAX_CELLS:
+        raise ValueError("the surface spans %s cells: more than 2^27 cells do not fit one volume (give a smaller box; the store keeps "
+                         "everything)" % (n.tolist(),))
+    return check_box(lo, n)
+
+
+def surface_assemble_file(path, box=None):
+    """`mapfile surface-assemble`: (cells, color, lo, voxel, trunc) of the store file `path` over box = (lo, n), by default its bounds."""
+    store = SurfaceStore.load(path)
+    if store.voxel is None or store.trunc is None:
+        raise ValueError("%s does not state its voxel edge and truncation distance" % path)
+    lo, n = surface_assemble_box(store.bounds(), *(box if box is not None else (None, None)))
+    cells, color = store.volume(lo, n)
+    return cells, color, lo.astype(np.int32), store.voxel, store.trunc
+
+
 # ---------------------------------------------------------------------------------- planning through the map (DESIGN 23) --
 PLAN_NONE = np.uint32(0xFFFFFFFF)
 PLAN_INFO_KEYS = ("cells", "free", "reachable", "max_cost", "seeds_used", "seeds_outside", "seeds_blocked")
@@ -2555,6 +2825,27 @@ def main(argv=None):
                       % (val["-o"][0], len(res), val["--views"][0], pos[0], sum(r[5] == ALIGN_CONVERGED for r in res),
                          sum(r[5] == ALIGN_LOST for r in res), sum(int(r[3]["matched"]) for r in res)))
                 return 0
+        if cmd == "surface-assemble" and "-o" in args:
+            opt = {"-o": 1, "--box": 6}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1:
+                box = None
+                if "--box" in val:
+                    b = [int(x) for x in val["--box"]]
+                    box = (b[:3], b[3:])
+                cells, color, lo, voxel, trunc = surface_assemble_file(pos[0], box)
+                write_tsdf(val["-o"][0], cells, lo, voxel, trunc, color)
+                print("%s: %d x %d x %d cells from %s of the store %s: %d with a weight"
+                      % ((val["-o"][0],) + cells.shape + (lo.tolist(), pos[0], int((cells["weight"] > 0).sum()))))
+                return 0
         if cmd == "ply" and len(args) in (1, 2):
             from . import ply
             out = args[1] if len(args) == 2 else (args[0][:-4] if args[0].endswith(".rvm") else args[0]) + ".ply"
@@ -2583,6 +2874,7 @@ def main(argv=None):
           "[--depth-scale S] [--normals] -o DIR | "
           "surface-track TSDF.npz --views DIR [--stride K] [--max-dist M] [--min-weight K] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] "
           "[--depth-scale S] -o POSES.txt | "
+          "surface-assemble STORE.npz [--box I0 J0 K0 N0 N1 N2] -o TSDF.npz | "
           "ply FILE [OUT.ply]")
     return 2
 

@@ -38,6 +38,13 @@ the views a cell needs.  An error with --map-window and with --streams.  The pos
 --surface-track (with --surface) tracks every keyframe against the surface as it stands before it is fused (vo.REVO's surface_track,
 api.SurfaceVolume.track): a keyframe whose tracking converges is fused at the refined pose; surface_poses_<dataset>.txt
 gets the poses the keyframes were fused at.  The trajectory in poses_<dataset>.txt is the tracker's, unchanged.
+--surface-follow (with --surface) lets the box follow the camera (api.FollowingSurface): a box of --surface-follow-size
+N0 N1 N2 cells (default 256 256 256) centred ahead of the camera and snapped to multiples of --surface-follow-step K cells (default
+16); the cells that leave it are kept in a sparse store and come back when the camera returns.  The mesh written at the end is that
+of the whole surface, store and box together; where that spans more than one volume holds (1024 cells on an axis, 2^27 cells) a
+message says so and the store is written instead (--surface-store FILE.npz, default FILE.npz beside the mesh; `python -m
+revo_amd.mapfile surface-assemble` cuts boxes out of it).  --surface-store FILE.npz writes the store in any case.  An error with
+--surface-box and with --surface-views.  MultiREVO, an in-place shift and a pyramid of volumes are not part of it.
 --surface-views DIR (with --surface) ray-casts the finished surface from the estimated pose of every keyframe, or with
 --surface-views-every K of every K-th tracked frame, on the GPU (api.SurfaceVolume.raycast, DESIGN 28: depth and colour from the
 sign change of the fused field, sub-voxel accurate and without holes) and writes the TUM-layout data set that --map-views writes
@@ -58,7 +65,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -198,6 +205,33 @@ def main(argv=None):
         if "--surface" not in argv:
             print("--surface-track tracks the keyframes against the TSDF surface: it needs --surface FILE.ply")
             return 2
+    follow = None  # api.FollowingSurface instead of a fixed box: {"size": [n0, n1, n2], "step": k, "store": file or None}
+    if "--surface-follow" in argv:
+        argv = [a for a in argv if a != "--surface-follow"]
+        follow = {}
+        for other, why in (("--surface-box", "the box follows the camera, so there is no box to give (see --surface-follow-size)"),
+                           ("--surface-views", "the views are cast from one volume, and a following surface is a box and a store")):
+            if other in argv or (other == "--surface-views" and sviews_dir is not None):
+                print("--surface-follow is not supported together with %s: %s" % (other, why))
+                return 2
+        if "--surface" not in argv:
+            print("--surface-follow moves the TSDF surface's box: it needs --surface FILE.ply")
+            return 2
+    for opt, key, k, conv in (("--surface-follow-size", "size", 3, int), ("--surface-follow-step", "step", 1, int), ("--surface-store", "store", 1, str)):
+        if opt in argv:
+            i = argv.index(opt)
+            try:
+                got = [conv(x) for x in argv[i + 1:i + 1 + k]]
+                if len(got) != k or (conv is int and min(got) < 1):
+                    raise ValueError
+            except ValueError:
+                print("%s needs %s" % (opt, {"size": "three cell counts >= 1: N0 N1 N2", "step": "a number of cells >= 1", "store": "a file name"}[key]))
+                return 2
+            if follow is None:
+                print("%s needs --surface-follow" % opt)
+                return 2
+            follow[key] = got[0] if k == 1 else got
+            argv = argv[:i] + argv[i + 1 + k:]
     surface = None  # vo.REVO's surface: the coloured, shaded mesh of the keyframes' TSDF volume, written at the end of the run
     for opt, key, k, conv in (("--surface", "file", 1, str), ("--surface-box", "box", 6, int), ("--surface-trunc", "trunc", 1, float),
                               ("--surface-min-weight", "min_weight", 1, int)):
@@ -272,9 +306,12 @@ def main(argv=None):
         if map_window:
             vmap = api.MapWindow(cam, map_voxel, dense=bool(sysd["do_generate_dense_pcl"]), window=map_window)
         surf = None
-        if surface is not None:  # the box is decided here and does not move: voxel indices of the first camera's frame
-            box = surface.get("box", (-128, -128, -32, 256, 256, 256))
-            surf = api.SurfaceVolume(vmap, box[:3], box[3:], surface.get("trunc"), color=True)
+        if surface is not None:
+            if follow is not None:  # the box goes with the camera; what leaves it is kept in surf.store
+                surf = api.FollowingSurface(vmap, follow.get("size", (256, 256, 256)), surface.get("trunc"), color=True, step=follow.get("step", 16))
+            else:  # the box is decided here and does not move: voxel indices of the first camera's frame
+                box = surface.get("box", (-128, -128, -32, 256, 256, 256))
+                surf = api.SurfaceVolume(vmap, box[:3], box[3:], surface.get("trunc"), color=True)
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
                       mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances, carve=map_carve,
                       surface=surf, surface_track=surface_track or None)
@@ -309,7 +346,10 @@ def main(argv=None):
                          (" -- %d keyframes carved NOTHING: their pose's rotation had drifted past the orthogonality rule"
                           % drv.carve_skipped) if drv.carve_skipped else ""))
             if surf is not None:
-                _save_surface(surf, drv, surface, name, len(io["datasets"]) > 1)
+                if follow is not None:
+                    _save_following_surface(surf, drv, surface, follow, name, len(io["datasets"]) > 1)
+                else:
+                    _save_surface(surf, drv, surface, name, len(io["datasets"]) > 1)
                 if surface_track:
                     _save_surface_tracks(drv, name)
                 if sviews_dir is not None:
@@ -343,6 +383,31 @@ def _save_surface(surf, drv, surface, name, per_dataset):
     if blind or drv.surface_skipped:
         print("Surface: %d of %d keyframes confirmed no cell of the box (their surfaces lie outside it); %d were not fused for their pose's rotation"
               % (blind, surf.views, drv.surface_skipped), file=sys.stderr)
+
+
+def _save_following_surface(surf, drv, surface, follow, name, per_dataset):
+    """--surface-follow: the mesh of the whole surface (store and box), or a message and the store when it does not fit one volume;
+    --surface-store: the store as well, what the box holds at the end included."""
+    import sys
+    from . import mapfile
+    out = _rvm_path(surface["file"], name, per_dataset)
+    store_out = _rvm_path(follow["store"], name, per_dataset) if follow.get("store") else None
+    try:
+        mesh = surf.mesh(surface.get("min_weight", 1), normals=True, colors=True)
+        mesh.save_ply(out)
+        print("Surface: %d vertices, %d triangles from %d keyframes; the box %s + %s moved %d times, %d cells in the store -> %s"
+              % (len(mesh.vertices), len(mesh.triangles), surf.views, surf.lo.tolist(), surf.n.tolist(), surf.shifts, len(surf.store), out))
+    except ValueError as e:
+        store_out = store_out or os.path.splitext(out)[0] + ".npz"
+        print("Surface: no mesh written -- %s" % e, file=sys.stderr)
+    if store_out is not None:
+        whole = mapfile.SurfaceStore(surf.store.records, surf.store.voxel, surf.store.trunc)
+        cur = surf.volume()
+        whole.add(mapfile.tsdf_volume_records(cur.cells, cur.color, cur.lo))
+        whole.save(store_out)
+        print("Surface store: %d cells -> %s (python -m revo_amd.mapfile surface-assemble cuts volumes out of it)" % (len(whole), store_out))
+    if drv.surface_skipped:
+        print("Surface: %d keyframes were not fused for their pose's rotation" % drv.surface_skipped, file=sys.stderr)
 
 
 def _save_surface_tracks(drv, name):

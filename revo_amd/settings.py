@@ -446,6 +446,26 @@ class MapTsdfTrackInfo(C.Structure):
 assert (C.sizeof(MapTsdfTrackParams), C.sizeof(MapTsdfTrackInfo)) == (32, 208)
 
 
+class MapTsdfRecord(C.Structure):
+    """revo_map_tsdf_record (include/revo_hip.h), 32 bytes: a cell that has left the surface volume's box -- its voxel index as the
+    map's packed key and the bytes of its TSDF and colour cells (mapfile.TSDF_RECORD_DTYPE)."""
+    _fields_ = [("key", C.c_uint64), ("sum", C.c_int32), ("weight", C.c_uint32), ("sum_b", C.c_uint32), ("sum_g", C.c_uint32),
+                ("sum_r", C.c_uint32), ("color_weight", C.c_uint32)]
+
+
+class MapTsdfShiftInfo(C.Structure):
+    """revo_map_tsdf_shift_info (include/revo_hip.h), 64 bytes: the cells of a shift by what became of them."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "staying", "leaving", "records", "dropped")] + [("reserved", C.c_uint64 * 3)]
+
+
+class MapTsdfRefillInfo(C.Structure):
+    """revo_map_tsdf_refill_info (include/revo_hip.h), 32 bytes: the records of a refill by what became of them."""
+    _fields_ = [(k, C.c_uint64) for k in ("records", "applied", "outside", "reserved")]
+
+
+assert (C.sizeof(MapTsdfRecord), C.sizeof(MapTsdfShiftInfo), C.sizeof(MapTsdfRefillInfo)) == (32, 64, 32)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

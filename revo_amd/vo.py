@@ -70,7 +70,8 @@ class REVO:
         # first keyframes meet an empty volume: LOST, nothing changes).  surface_tracks[i]: (keyframe time stamp, T_w_kf, the pose it
         # was fused at, the MapTsdfTrackInfo at the loop's last pose or None, status); a keyframe whose rotation fails the is_orthogonal
         # rule is not tracked (info None, LOST).  The reported trajectory, the voxel map's integration and the carve keep T_w_kf.  Off
-        # by default: nothing new is enqueued.
+        # by default: nothing new is enqueued.  With an api.FollowingSurface the box follows the keyframe's pose before it is
+        # tracked (and, as always, before it is fused); any other surface is not asked to move.
         self.surface_track = None if surface_track is None or surface_track is False else ({} if surface_track is True else dict(surface_track))
         self.surface_tracks = []
         if self.surface_track is not None and surface is None:
@@ -146,6 +147,9 @@ class REVO:
         T0 = np.asarray(T_w_kf, np.float32)
         info, status, T = None, mapfile.ALIGN_LOST, T0
         if mapfile.pose_is_orthogonal(T0[:3, :3]):
+            follow = getattr(self.surface, "follow", None)
+            if follow is not None:  # an api.FollowingSurface: the box goes where the keyframe looks before it is tracked
+                follow(T0)
             r = self.surface.track(kfPyr, T0, **self.surface_track)
             info, status = r["info"], r["status"]
             if status == mapfile.ALIGN_CONVERGED:
