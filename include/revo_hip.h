@@ -305,7 +305,12 @@ int revo_batch_track(revo_batch* b, const uint8_t* d_bgr, const float* d_depth,
  * the depth-validity bits and the edge lists of the keyframe-role frames (even) only when somebody asks for them: any
  * accessor or single-pair / vote call on an even view of revo_batch_frame.  The same kernels run on the same inputs
  * either way: every plane, list and record is bit-identical to an eager build's.  That late work reads the edge maps and
- * level 0 of the depth pyramid, so the next revo_batch_build* of the batch is ordered behind it by the library. */
+ * level 0 of the depth pyramid, so the next revo_batch_build* of the batch is ordered behind it by the library.
+ * The BYTE edge planes of such a batch (REVO_PLANE_EDGES, REVO_PLANE_EDGES_ORIG: edgesPyr / edgesOrigPyr) are produced on
+ * first access as well: the build ends at the edge bitmaps, which are all the tracker's inputs are made from, and the first
+ * accessor, vote, reference-ordered edge list or map call that reads a byte plane through a view of revo_batch_frame expands
+ * them for all frames of the batch (one streaming kernel, behind fill-in).  revo_batch_sync does not.  Same bytes as an
+ * eager build's. */
 int revo_batch_build(revo_batch* b, const uint8_t* d_bgr, const float* d_depth,
                      void* stream);
 /* revo_batch_build without the copy of the depth input: level 0 of the depth pyramid IS d_depth (the reference's

@@ -18,6 +18,7 @@ extern "C" int revo_batch_create(revo_ctx* c, int n_pairs, revo_batch** out) {
   TRY(b->ev0.create(hipEventDefault)); TRY(b->ev1.create(hipEventDefault));
   TRY(b->descs.create());
   TRY(b->trk.create());
+  b->fs->trk_mark = &b->trk;
   b->cluster = pick_cluster(c, n_pairs);
   b->defer = env_defer();
   TRY(b->d_mail.alloc(mail_bytes(n_pairs, b->cluster) / sizeof(unsigned long long)));
@@ -61,6 +62,7 @@ static int enqueue_batch_tail(revo_batch* b, hipStream_t s) {
     std::lock_guard<std::mutex> lk(b->fs->edt_mu);
     b->fs->edt_pending = true; b->fs->edt_count = b->n_pairs;
     b->fs->ref_lists_pending = true;
+    b->fs->edge_bytes_pending = true;  // (the build ended at the edge bitmaps: ensure_edge_bytes)
   } else {
     launch_tile_points(g, b->fs->p, b->fs->B, s);
     launch_keyframe(g, b->fs->p, 0, 2, b->n_pairs, s);
@@ -79,7 +81,10 @@ static int batch_build(revo_batch* b, const uint8_t* d_bgr, const float* d_depth
   // (last_results stays: a caller that pipelines track_only(k) -> build(k) -> sync still gets the flag-8 check of launch k;
   // the result buffer must stay valid until revo_batch_sync or the next revo_batch_track_only)
   TRY(wait_edt_before_rebuild(b->fs.get(), s));  // the previous build's deferred EDT still reads these planes
-  TRY(batch_wait_tracker(b, s));                 // ... and its tracker grid still reads lists and DT planes
+  // ... and its tracker grid still reads lists, counts and DT planes (PairDesc).  A build that defers writes none of them: gray,
+  // depth level 0, the Canny words, hist / hist_nz and the hysteresis scratch are all its kernels touch, and run_pending_edt
+  // waits for the grid on the stream that does write them -- the build stream, the step's critical chain, does not
+  if (!b->defer) TRY(batch_wait_tracker(b, s));
   // (Measured and not kept: the two halves of the batch as two concurrent kernel chains -- 78.4 k -> 70.5 k frames/s.)
   enqueue_build(b->ctx, b->fs.get(), d_bgr, d_depth, d_depth_u16, alpha, s, borrow, false, 0, -1, b->defer);
   TRY(enqueue_batch_tail(b, s));
@@ -264,6 +269,8 @@ extern "C" int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, con
   PyrGeom g = c->geom;
   g.frame0 = 0;
   FrameSet* fs = b->fs.get();
+  g.edge_bytes_lazy = b->defer ? 1 : 0;  // the kernels as the batch's own builds launch them
+  fs->lazy_edge_bytes = b->defer;
   const int B = fs->B, L = g.n_levels;
   fs->p.depth[0] = const_cast<float*>(d_depth);
   struct Stage { const char* name; int a, w; };
@@ -323,6 +330,7 @@ extern "C" int revo_batch_profile_build(revo_batch* b, const uint8_t* d_bgr, con
     std::lock_guard<std::mutex> lk(fs->edt_mu);
     fs->edt_pending = false;
     fs->ref_lists_pending = false;  // (every kernel above ran over all B frames)
+    fs->edge_bytes_pending = b->defer;
     TRY(fs->edt.record(s));
     fs->ref.recorded = false;       // `edt` covers the even frames' lists too
   }

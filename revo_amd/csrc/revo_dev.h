@@ -44,6 +44,8 @@ struct PyrGeom {
   int hyst_heavy_runs; // MIXED hysteresis (levels that fit one workgroup): a level-0 frame with at least this many weak runs takes the
                        // banded path, several workgroups, inside the same launch (REVO_HYST_HEAVY_RUNS; 0 = off: one workgroup per frame)
   int total_tiles;     // 32 x 32-pixel tiles of all levels (wpr x nchunk per level): the tracker's tile-ordered edge list
+  int edge_bytes_lazy; // per launch: 1 = the set's byte edge planes are produced on first access (ensure_edge_bytes): the hysteresis
+                       // ends at the bitmaps (cs[].y; cs[].x keeps the one from before fill-in), k_fill and k_edt_cols work on bits alone
   int pts_staged;      // per launch: 1 = the depths of the edge pixels of levels < n_levels - 1 were staged by the depth half of
                        // k_pyrdown (k_edge_prefix in front of it): k_pts_tiles reads them from FramePlanes::stage, not from the depth planes
   float depth_min, depth_max;
@@ -58,8 +60,9 @@ struct PyrGeom {
 struct FramePlanes {
   uint8_t* gray[REVO_L];
   float* depth[REVO_L];
-  uint2* cs[REVO_L];           // Canny bitmaps: per row and 32 pixels {candidate bits, strong bits} (frame stride h*wpr)
-  uint8_t* edges[REVO_L];      // edgesPyr     {0,255}
+  uint2* cs[REVO_L];           // Canny bitmaps: per row and 32 pixels {candidate bits, strong bits} (frame stride h*wpr); behind the
+                               // hysteresis .y is the EDGE bitmap (k_fill adds to it), and in a lazy set .x the one from before fill-in
+  uint8_t* edges[REVO_L];      // edgesPyr     {0,255}; a lazy set (PyrGeom::edge_bytes_lazy) gets both planes from ensure_edge_bytes
   uint8_t* edges_orig[REVO_L]; // edgesOrigPyr {0,255}: written only for levels with has_orig (elsewhere it IS edges)
   int* scratch[REVO_L];        // CCL parent keys during the build; column g^2 during makeKeyframe
   float4* pts[REVO_L];         // edges3DPyr: (X,Y,Z,1), capacity npix per frame -- the reference's order, built on demand
@@ -151,6 +154,7 @@ void launch_edge_prefix(const PyrGeom& g, const FramePlanes& p, int B, hipStream
 void launch_canny_nms(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s);
 void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s);
 void launch_fill(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s);
+void launch_edge_bytes(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s);   // edges / edges_orig of a lazy set, all levels
 void launch_compact(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s);      // reference-ordered list (accessor)
 // tile-ordered list + npts (hot path); which: bit 0 = k_tile_count, bit 1 = k_pts_tiles (the stage profiler times them apart)
 void launch_tile_points(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s, int which = 3);

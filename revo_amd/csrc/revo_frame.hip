@@ -172,7 +172,7 @@ extern "C" int revo_pyramid_make_keyframe(revo_pyr* p) {
   if (!p) return fail(REVO_ERR_INVALID_ARG, "null pyramid");
   HIPCHECK(hipSetDevice(p->ctx->device));
   TRY(wait_ready(p->ctx, p));
-  if (!p->dt_ready) launch_keyframe(p->ctx->geom, p->fs->p, p->frame, 1, 1, p->ctx->stream);
+  if (!p->dt_ready) launch_keyframe(geom_of_set(p->ctx, p->fs), p->fs->p, p->frame, 1, 1, p->ctx->stream);
   HIPCHECK(hipGetLastError());
   p->dt_ready = false;  // (a second makeKeyframe computes again, like the reference)
   p->is_kf = true;
@@ -187,7 +187,7 @@ extern "C" int revo_pyramid_prepare_keyframe_(revo_pyr* p) {
   if (!p->owns_fs || p->is_kf || p->dt_ready) return REVO_OK;
   HIPCHECK(hipSetDevice(p->ctx->device));
   TRY(wait_ready(p->ctx, p));
-  launch_keyframe(p->ctx->geom, p->fs->p, p->frame, 1, 1, p->ctx->stream);
+  launch_keyframe(geom_of_set(p->ctx, p->fs), p->fs->p, p->frame, 1, 1, p->ctx->stream);
   HIPCHECK(hipGetLastError());
   p->dt_ready = true;
   return REVO_OK;
@@ -204,6 +204,8 @@ extern "C" int revo_pyramid_read(revo_pyr* p, revo_plane what, int lvl, void* ds
   const FramePlanes& P = p->fs->p;
   const size_t f = (size_t)p->frame;
   TRY(wait_ready(c, p));
+  // the byte edge planes themselves, and the reference-ordered walk that reads them (k_compact_walk)
+  if (what == REVO_PLANE_EDGES || what == REVO_PLANE_EDGES_ORIG || what == REVO_PLANE_EDGES3D) TRY(ensure_edge_bytes(c, p->fs, c->stream));
   HIPCHECK(hipStreamSynchronize(c->stream));
   const void* src = nullptr;
   size_t n = v.npix, esz = 1;
@@ -266,6 +268,7 @@ extern "C" int revo_pyramid_colored_pcl(revo_pyr* p, int lvl, int dense, float* 
   if (!(p->owns_fs || p->has_colour) || !p->fs->d_bgr)
     return fail(REVO_ERR_INVALID_ARG, "batch views keep no colour image (rgbFullSize): use revo_pyramid_create");
   TRY(wait_ready(c, p));
+  TRY(ensure_edge_bytes(c, p->fs, c->stream));  // k_pcl_walk reads edges[lvl]
   std::lock_guard<std::mutex> lk(c->mu);
   const PyrGeom& g = c->geom;
   const size_t n0 = g.lv[0].npix, slots = (size_t)g.lv[0].w * g.lv[0].nchunk;
@@ -311,6 +314,7 @@ extern "C" int revo_map_source_(revo_pyr* p, MapSource* out) {
   if (!(p->owns_fs || p->has_colour) || !p->fs->d_bgr)
     return fail(REVO_ERR_INVALID_ARG, "batch views keep no colour image (rgbFullSize): use revo_pyramid_create");
   TRY(wait_ready(c, p));
+  TRY(ensure_edge_bytes(c, p->fs, c->stream));  // the cloud fuse reads edges[0]
   const size_t n0 = c->geom.lv[0].npix, f = (size_t)p->frame;
   out->ctx = c;
   out->depth = p->fs->p.depth[0] + f * n0;

@@ -334,7 +334,7 @@ int frameset_create(revo_ctx* c, int B, bool with_staging, FrameSet** out, bool 
     TRY(fs->h_bgr.alloc((size_t)g.lv[0].npix * 3 * B));
     TRY(fs->h_depth.alloc((size_t)g.lv[0].npix * B));
   }
-  for (StreamMark* m : {&fs->ready, &fs->free_trk, &fs->free_vote, &fs->edt, &fs->ref}) TRY(m->create());
+  for (StreamMark* m : {&fs->ready, &fs->free_trk, &fs->free_vote, &fs->edt, &fs->ref, &fs->ebytes}) TRY(m->create());
   // counts start at zero so an accessor on a not-yet-built pyramid is well defined
   hipMemsetAsync(fs->p.npts, 0, sizeof(int) * REVO_L * B, c->stream);
   HIPCHECK(hipStreamSynchronize(c->stream));
@@ -352,6 +352,9 @@ void enqueue_build(revo_ctx* c, FrameSet* fs, const uint8_t* d_bgr, const float*
   PyrGeom g = c->geom;
   g.frame0 = frame0;
   const int B = nframes < 0 ? fs->B : nframes;
+  // a batch that defers the end of its build also leaves the byte edge planes to their first reader (ensure_edge_bytes)
+  g.edge_bytes_lazy = gray_only ? 1 : 0;
+  fs->lazy_edge_bytes = gray_only;
   fs->p.depth[0] = (borrow_depth && d_depth_f32) ? const_cast<float*>(d_depth_f32) : fs->own_depth0;
   launch_gray_depth(g, fs->p, d_bgr, d_depth_f32, d_depth_u16, alpha, B, s);
   // gray_only (batches that defer): the depth half of the pyramid is left to the first consumer with the edge lists
@@ -537,10 +540,13 @@ int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s, bool need_ref_list
   } else {
     TRY(fs->ready.wait(s));
     behind_build = true;
+    // the set's previous tracker grid still reads the lists, counts and DT planes written below (the build stream, which
+    // writes none of them, does not wait for it)
+    if (fs->trk_mark) TRY(fs->trk_mark->wait_elsewhere(s));
     // (the edge lists and the EDT do not depend on each other; running the EDT first -- next to the memory-bound first kernels of
     // the following build instead of its VALU-bound NMS -- was measured equal: profiles/r04_ab_aux_order.txt)
     enqueue_list_side(c, fs, 1, 2, fs->edt_count, s);  // frame 2i + 1 is pair i's current frame: the only lists a grid reads
-    launch_keyframe(c->geom, fs->p, 0, 2, fs->edt_count, s);
+    launch_keyframe(geom_of_set(c, fs), fs->p, 0, 2, fs->edt_count, s);  // (a lazy set: the column pass reads bitmaps at every width)
     HIPCHECK(hipGetLastError());
     TRY(fs->edt.record(s));
     fs->edt_pending = false;
@@ -559,7 +565,18 @@ int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s, bool need_ref_list
 int wait_edt_before_rebuild(FrameSet* fs, hipStream_t s) {
   std::lock_guard<std::mutex> lk(fs->edt_mu);
   TRY(fs->edt.wait_elsewhere(s));
-  return fs->ref.wait_elsewhere(s);
+  TRY(fs->ref.wait_elsewhere(s));
+  return fs->ebytes.wait_elsewhere(s);  // an expansion of the byte edge planes that was started still reads the bitmaps
+}
+int ensure_edge_bytes(revo_ctx* c, FrameSet* fs, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(fs->edt_mu);
+  if (!fs->edge_bytes_pending) return fs->ebytes.wait_elsewhere(s);  // written by the build, or expanded by an earlier reader
+  TRY(fs->ready.wait(s));  // behind fill-in
+  launch_edge_bytes(c->geom, fs->p, fs->B, s);
+  HIPCHECK(hipGetLastError());
+  TRY(fs->ebytes.record(s));
+  fs->edge_bytes_pending = false;
+  return REVO_OK;
 }
 // Waits for an event by POLLING it (the in-place frame upload, ~50-100 us): the IO thread gets its answer a few microseconds after the
 // copy has finished instead of after hipEventSynchronize's park-and-wake; the sequential stream runs 1-3 % faster with it

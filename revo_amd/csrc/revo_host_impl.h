@@ -49,6 +49,16 @@ struct FrameSet {
   // mark discipline as the EDT: set by every batch build, cleared by whoever runs the work, `ref` for consumers on other streams
   std::atomic<bool> ref_lists_pending{false};
   StreamMark ref;
+  // ... and the BYTE edge planes (edges / edges_orig) of a batch that defers: its hot path reads the edge bitmaps alone, so the
+  // build ends at them (PyrGeom::edge_bytes_lazy) and ensure_edge_bytes expands them for whoever reads a byte plane through a
+  // view.  Same lock, same mark discipline; `lazy_edge_bytes` says how the LAST build left the set (its bitmaps in cs[] are then
+  // also what the deferred EDT reads at every width)
+  bool lazy_edge_bytes = false;
+  std::atomic<bool> edge_bytes_pending{false};
+  StreamMark ebytes;
+  // (batches) the batch's last tracker grid: the deferred work rewrites what it reads (lists, counts, DT planes), on whatever
+  // stream runs it -- run_pending_edt orders itself behind this mark.  The build stream writes none of those planes.
+  const StreamMark* trk_mark = nullptr;
   StreamMark free_trk;   // recorded on the tracker stream when the set goes back to the pool
   StreamMark free_vote;  // ... and on the vote stream (the quality vote and the cloud copy read the set there)
   OwnedEvent h2d;        // (single-frame API) the copy out of page-locked caller rows has finished; made on first use
@@ -206,6 +216,15 @@ void enqueue_build(revo_ctx* c, FrameSet* fs, const uint8_t* d_bgr, const float*
                    int nframes = -1, bool gray_only = false);
 int run_pending_edt(revo_ctx* c, FrameSet* fs, hipStream_t s, bool need_ref_lists = false);
 int wait_edt_before_rebuild(FrameSet* fs, hipStream_t s);
+// THE place where the byte edge planes of a lazily built set come into being: every reader of edges / edges_orig through a view
+// calls it on its stream first (a no-op for sets whose build wrote them).  Behind the set's "built" event, i.e. behind fill-in.
+int ensure_edge_bytes(revo_ctx* c, FrameSet* fs, hipStream_t s);
+// the context's geometry for kernels that read a set's edges (the EDT's column pass): a lazily built set has its bitmaps only
+inline PyrGeom geom_of_set(const revo_ctx* c, const FrameSet* fs) {
+  PyrGeom g = c->geom;
+  g.edge_bytes_lazy = fs->lazy_edge_bytes ? 1 : 0;
+  return g;
+}
 // revo_single.hip
 int decode_track(const revo_pair_result& r, float R[9], float T[3], float* err, int* status, revo_residual_info* info, int32_t* iters);
 // A past-cloud buffer for at least `need` points out of `pool`: recycled if one is large enough (no hipMalloc per frame in

@@ -234,6 +234,7 @@ extern "C" int revo_mdev_vote_(revo_mdev* m, int n, MultiVote* votes) {
     if (past.empty() || !m->ts.check_tracking_results) continue;  // nothing to vote on (tracker.cpp:121)
     FrameSet* fs = (FrameSet*)v.set;
     TRY(fs->ready.wait_elsewhere(vs));
+    TRY(ensure_edge_bytes(c, fs, vs));  // (these sets are built with their byte planes: the choke point of every byte reader)
     VoteDesc& d = m->vdesc.h[nv];
     memset(&d, 0, sizeof(d));
     float inv[16];
@@ -319,6 +320,7 @@ extern "C" int revo_mdev_promote_(revo_mdev* m, int n, const MultiFrame* f) {
   for (int i = 0; i < n; ++i) {
     FrameSet* src = (FrameSet*)f[i].set;
     TRY(src->ready.wait_elsewhere(s));
+    TRY(ensure_edge_bytes(c, src, s));  // the copies below take edges / edges_orig (these sets are built with them)
     const size_t sf = (size_t)f[i].frame, df = (size_t)f[i].stream;
     const FramePlanes& a = src->p;
     const FramePlanes& b = m->kf->p;

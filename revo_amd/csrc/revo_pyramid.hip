@@ -18,6 +18,7 @@
 #include "revo_dev.h"
 #include "revo_nms_px.h"
 #include "revo_edt_px.h"
+#include "revo_edge_bits.h"
 #include <type_traits>
 
 namespace {
@@ -442,7 +443,8 @@ __device__ __forceinline__ int hist_wide_tile(const uint32_t* row, int pitch, in
 // E lives in the (level, frame)'s scratch plane in HBM / L2 -- same layout, same code; the workgroup's own stores are visible
 // to its own loads after a barrier.  This is the exact last resort of the banded path on very large levels (a band whose runs
 // exceed its label space): slow, correct, rare.
-template <bool C_IN_LDS, bool E_GLOBAL = false>
+// LAZY: the set's byte edge planes are produced on first access (PyrGeom::edge_bytes_lazy): the level ends at its bitmaps.
+template <bool C_IN_LDS, bool E_GLOBAL = false, bool LAZY = false>
 __device__ __forceinline__ void hyst_level(const PyrGeom& g, const FramePlanes& pl, const int l, const int f, uint32_t* s_mem) {
   static_assert(!(C_IN_LDS && E_GLOBAL), "the candidate bitmap is in LDS only when the edge bitmap is");
 #ifdef REVO_HYST_PROFILE
@@ -793,12 +795,13 @@ __device__ __forceinline__ void hyst_level(const PyrGeom& g, const FramePlanes& 
   }
   __syncthreads();
   HP(5);
-  // edgesPyr / edgesOrigPyr: 16 pixels per store
+  // edgesPyr / edgesOrigPyr: 16 pixels per store.  Not for a set whose byte planes are produced on first access
+  // (g.edge_bytes_lazy, DESIGN 3.0 "Byte edge planes on first access"): the bitmaps below are all its hot path reads.
   uint8_t* edges = pl.edges[l] + (size_t)f * lv.npix;
   uint8_t* orig = lv.has_orig ? pl.edges_orig[l] + (size_t)f * lv.npix : nullptr;
   const bool rows16 = (w & 15) == 0;  // then a group of 16 pixels lies in one row and one half of a bitmap word
   const float inv_w = 1.0f / (float)w;
-  for (int i = tid; i < lv.npix / 16; i += HYST_THREADS) {
+  for (int i = tid; i < (LAZY ? 0 : lv.npix / 16); i += HYST_THREADS) {
     const int p = i * 16;
     int y = (int)(((float)p + 0.5f) * inv_w);  // p / w without the integer division ...
     y += (y + 1) * w <= p ? 1 : (y * w > p ? -1 : 0);  // ... and exact whatever the rounding did
@@ -822,9 +825,12 @@ __device__ __forceinline__ void hyst_level(const PyrGeom& g, const FramePlanes& 
     if (orig) *reinterpret_cast<uint4*>(orig + p) = v;
   }
   // the edge bitmap itself replaces the strong words (cs[].y): the edge-list count pass reads 32 pixels per load from it
+  // (lazy byte planes: the candidate word is dead from here on -- every sweep above has ended, and the flagged relaunch only
+  // runs for pairs whose words no kernel has rewritten -- so it keeps the bitmap from BEFORE fill-in, which is edgesOrigPyr)
   {
     uint2* csw = pl.cs[l] + (size_t)f * h * wpr;
-    for (int i = tid; i < nwords; i += HYST_THREADS) csw[i].y = E[pitch + i];
+    if (LAZY) for (int i = tid; i < nwords; i += HYST_THREADS) { const uint32_t e = E[pitch + i]; csw[i] = make_uint2(e, e); }
+    else for (int i = tid; i < nwords; i += HYST_THREADS) csw[i].y = E[pitch + i];
   }
   HP(6);
   // histPyr[l] and the number of non-empty tiles (imgpyramidrgbd.cpp:146-172)
@@ -874,7 +880,7 @@ __device__ __forceinline__ void hyst_level(const PyrGeom& g, const FramePlanes& 
 // (Measured in round 4 and not kept, profiles/r04_ab_hyst_grouping_priority.txt: two workgroups per frame -- level 0 / the
 // other levels one after the other -- so that the launch asks for 128 whole-LDS CUs instead of 256: 84.4 k against 87.2 k
 // frames/s; a 512-thread, 144 KB variant that fits next to a tracker workgroup: 72 k, the kernel alone is 35 % slower.)
-template <bool C_IN_LDS, bool E_GLOBAL = false>
+template <bool C_IN_LDS, bool E_GLOBAL = false, bool LAZY = false>
 __global__ void __launch_bounds__(HYST_THREADS) k_hyst(PyrGeom g, FramePlanes pl, int only_flagged, int n_frames) {
   BUILD_PRIO();
   extern __shared__ uint32_t s_mem[];
@@ -892,7 +898,7 @@ __global__ void __launch_bounds__(HYST_THREADS) k_hyst(PyrGeom g, FramePlanes pl
     const int l = item / n_frames;
     const int f = g.frame0 + item % n_frames;
     if (only_flagged && !pl.need_full[f * REVO_L + l]) continue;
-    hyst_level<C_IN_LDS, E_GLOBAL>(g, pl, l, f, s_mem);
+    hyst_level<C_IN_LDS, E_GLOBAL, LAZY>(g, pl, l, f, s_mem);
     __syncthreads();
   }
 }
@@ -1179,6 +1185,7 @@ __device__ __forceinline__ bool hyst_frame_is_heavy(const PyrGeom& g, const Fram
   for (int k = 0; k < HYST_THREADS / 64; ++k) total += s_cnt[k];
   return total >= g.hyst_heavy_runs;
 }
+template <bool LAZY>
 __global__ void __launch_bounds__(HYST_THREADS) k_hyst_mixed(PyrGeom g, FramePlanes pl, int n_frames) {
   static_assert(HB_THREADS == HYST_THREADS, "one workgroup shape for both paths");
   extern __shared__ uint32_t s_mem[];
@@ -1197,7 +1204,7 @@ __global__ void __launch_bounds__(HYST_THREADS) k_hyst_mixed(PyrGeom g, FramePla
     if (threadIdx.x == 0) pl.hyst_heavy[f] = heavy ? 1 : 0;
     if (heavy) return;
   }
-  hyst_level<true>(g, pl, l, f, s_mem);
+  hyst_level<true, false, LAZY>(g, pl, l, f, s_mem);
 }
 
 // S: flags across the seams of one (level, frame).  One sweep over the seams lists the touching (run above, run below) pairs
@@ -1306,6 +1313,7 @@ __global__ void __launch_bounds__(HS_THREADS) k_hyst_seam(PyrGeom g, FramePlanes
 
 // P: promotions that came across a seam, then the band's outputs
 #define HO_THREADS 512
+template <bool LAZY>
 __global__ void __launch_bounds__(HO_THREADS) k_hyst_out(PyrGeom g, FramePlanes pl, int mixed) {
   extern __shared__ uint32_t s_mem[];
   const int nB = gridDim.x / (mixed ? g.lv[0].nbands : g.total_bands);  // mixed: the bands of level 0 only (they come first)
@@ -1335,12 +1343,12 @@ __global__ void __launch_bounds__(HO_THREADS) k_hyst_out(PyrGeom g, FramePlanes 
     }
     __syncthreads();
   }
-  // edgesPyr / edgesOrigPyr: 16 pixels per store (band heights are multiples of 4 rows, widths of 4 pixels)
+  // edgesPyr / edgesOrigPyr: 16 pixels per store (band heights are multiples of 4 rows, widths of 4 pixels); not for lazy byte planes
   uint8_t* edges = pl.edges[l] + (size_t)f * lv.npix + (size_t)br.R0 * w;
   uint8_t* orig = lv.has_orig ? pl.edges_orig[l] + (size_t)f * lv.npix + (size_t)br.R0 * w : nullptr;
   const bool rows16 = (w & 15) == 0;
   const float inv_w = 1.0f / (float)w;
-  for (int i = tid; i < hb * w / 16; i += HO_THREADS) {
+  for (int i = tid; i < (LAZY ? 0 : hb * w / 16); i += HO_THREADS) {
     const int p = i * 16;
     int y = (int)(((float)p + 0.5f) * inv_w);
     y += (y + 1) * w <= p ? 1 : (y * w > p ? -1 : 0);
@@ -1364,8 +1372,9 @@ __global__ void __launch_bounds__(HO_THREADS) k_hyst_out(PyrGeom g, FramePlanes 
     if (orig) *reinterpret_cast<uint4*>(orig + p) = v;
   }
   {
-    uint2* csw = pl.cs[l] + ((size_t)f * h + br.R0) * wpr;
-    for (int i = tid; i < nwb; i += HO_THREADS) csw[i].y = E[i];
+    uint2* csw = pl.cs[l] + ((size_t)f * h + br.R0) * wpr;  // (lazy byte planes: both words, as in hyst_level -- the seam pass is over)
+    if (LAZY) for (int i = tid; i < nwb; i += HO_THREADS) csw[i] = make_uint2(E[i], E[i]);
+    else for (int i = tid; i < nwb; i += HO_THREADS) csw[i].y = E[i];
   }
   // the band's histogram tiles (band heights are multiples of the patch size; imgpyramidrgbd.cpp:146-172)
   if (lv.patch > 0) {
@@ -1406,27 +1415,52 @@ __global__ void __launch_bounds__(1024) k_fill(PyrGeom g, FramePlanes pl, int on
   for (int l = la; l < lb; ++l) {
     const LevelGeom lv = g.lv[l], lf = g.lv[l - 1];
     if (!(g.use_edge_hist && lv.patch > 0 && lf.patch > 0)) continue;
-    const float frac = (float)pl.hist_nz[f * REVO_L + l] / (float)(lv.hist_w * lv.hist_h);
-    if (frac < g.n_percentage) {
-      const uint8_t* top = pl.edges[l - 1] + (size_t)f * lf.npix;
-      uint8_t* mod = pl.edges[l] + (size_t)f * lv.npix;
+    if (fill_gate_open(pl.hist_nz[f * REVO_L + l], lv.hist_w, lv.hist_h, g.n_percentage)) {
+      // the finer level's edge bitmap (k_hyst left it in cs[].y, this kernel added level l - 1's own fill-in to it): the bit IS
+      // top[yy * w + xx] > 0, and a set whose byte planes are produced on first access has nothing else
+      const uint2* top = pl.cs[l - 1] + (size_t)f * lf.h * lf.wpr;
+      uint2* modw = pl.cs[l] + (size_t)f * lv.h * lv.wpr;
+      uint8_t* mod = g.edge_bytes_lazy ? nullptr : pl.edges[l] + (size_t)f * lv.npix;
       const uint8_t* hist = pl.hist[l] + (size_t)f * lv.hist_w * lv.hist_h;
       const double thr = g.fill_thr[l];
       // finer pixel (yy,xx) odd,odd <-> coarse pixel (yy/2, xx/2)
       const int cw = lf.w / 2, ch = lf.h / 2;
       for (int i = blockIdx.x * 1024 + threadIdx.x; i < cw * ch; i += gridDim.x * 1024) {
         const int y = i / cw, x = i % cw;
-        const int yy = 2 * y + 1, xx = 2 * x + 1;
-        const int ty = yy / lf.patch, tx = xx / lf.patch;
-        if (ty >= lv.hist_h || tx >= lv.hist_w) continue;
-        if ((double)hist[(size_t)ty * lv.hist_w + tx] < thr && top[(size_t)yy * lf.w + xx] > 0) {
-          mod[(size_t)y * lv.w + x] = 255;
-          // ... and in the level's edge bitmap (k_hyst left it in cs[].y), which the edge-list count pass reads
-          atomicOr(&(pl.cs[l] + (size_t)f * lv.h * lv.wpr)[(size_t)y * lv.wpr + (x >> 5)].y, 1u << (x & 31));
+        if (fill_in_pixel(y, x, lf.patch, lv.hist_w, lv.hist_h, hist, thr, [&](int yy, int xx) {
+              return edge_bit([&](int k) { return top[k].y; }, lf.wpr, yy, xx); })) {
+          if (mod) mod[(size_t)y * lv.w + x] = 255;
+          // ... and in the level's edge bitmap, which the edge-list count pass, the next level and the EDT read
+          atomicOr(&modw[(size_t)y * lv.wpr + (x >> 5)].y, 1u << (x & 31));
         }
       }
     }
     __syncthreads();
+  }
+}
+
+// The byte planes of a set that was built without them (g.edge_bytes_lazy; ensure_edge_bytes, revo_host.hip): edgesPyr out of
+// the edge bitmap cs[].y (hysteresis + fill-in) and, where fillInEdges may change the level, edgesOrigPyr out of the bitmap from
+// before fill-in, which the hysteresis left in cs[].x.  All levels, all frames (blockIdx.y); a lane expands 16 pixels -- at
+// most four words of one or two rows -- into one 16-byte store per plane.  Streaming, no LDS: the bytes k_hyst / k_hyst_out
+// would have written, bit for bit (revo_edge_bits.h is what both run).
+__global__ void __launch_bounds__(256) k_edge_bytes(PyrGeom g, FramePlanes pl) {
+  const int P = (blockIdx.x * 256 + threadIdx.x) * 16;  // first pixel of the group in the concatenation of the levels
+  if (P >= g.total_pix) return;                         // (every level has a multiple of 16 pixels: build_geom)
+  const int f = g.frame0 + blockIdx.y;
+  const int l = level_of(g, P, &LevelGeom::pix_base);
+  const LevelGeom& lv = g.lv[l];
+  const int p = P - lv.pix_base;
+  int y = (int)(((float)p + 0.5f) * (1.0f / (float)lv.w));      // p / w without the integer division ...
+  y += (y + 1) * lv.w <= p ? 1 : (y * lv.w > p ? -1 : 0);       // ... and exact whatever the rounding did
+  const int x = p - y * lv.w;
+  const uint2* csw = pl.cs[l] + (size_t)f * lv.h * lv.wpr;
+  uint32_t o[4];
+  edge_bytes16([&](int k) { return csw[k].y; }, lv.w, lv.wpr, y, x, o);
+  *reinterpret_cast<uint4*>(pl.edges[l] + (size_t)f * lv.npix + p) = make_uint4(o[0], o[1], o[2], o[3]);
+  if (lv.has_orig) {
+    edge_bytes16([&](int k) { return csw[k].x; }, lv.w, lv.wpr, y, x, o);
+    *reinterpret_cast<uint4*>(pl.edges_orig[l] + (size_t)f * lv.npix + p) = make_uint4(o[0], o[1], o[2], o[3]);
   }
 }
 
@@ -2042,16 +2076,20 @@ __global__ void __launch_bounds__(EDT_THREADS) k_edt_cols(PyrGeom g, FramePlanes
   const bool in = x < lv.w;
   const uint8_t* edges = pl.edges[l] + (size_t)f * lv.npix;
   unsigned em = 0;
-  if ((lv.w & 31) == 0 && (ncols & 31) == 0) {
+  const uint2* csw = pl.cs[l] + (size_t)f * lv.h * lv.wpr;
+  if (((lv.w & 31) == 0 || g.edge_bytes_lazy) && (ncols & 31) == 0) {
     // the level's edge bitmap (k_hyst / k_fill left it in cs[].y) as 32 x 32 bit tiles: lane r of a half-wave loads
-    // the word of row yb + r, the transpose hands every column its rows -- one load instead of 32 byte loads
-    const uint2* csw = pl.cs[l] + (size_t)f * lv.h * lv.wpr;
+    // the word of row yb + r, the transpose hands every column its rows -- one load instead of 32 byte loads.  A width that
+    // is no multiple of 32 ends in a partial word per row: the words beyond it are not loaded (wc < wpr) and the columns
+    // beyond w are dropped (!in).  Sets with live byte planes keep the byte loop at those widths, as before.
     const int r = threadIdx.x & 31;
     const int wc = (sidx * ncols + (col & ~31)) >> 5;
     uint32_t v = 0;
     if (yb + r < ye && wc < lv.wpr) v = csw[(size_t)(yb + r) * lv.wpr + wc].y;
     em = tile_transpose32(v, r);
     if (!in) em = 0;
+  } else if (in && g.edge_bytes_lazy) {  // 16-column strips (heights above 1024) of a set without byte planes: bit by bit
+    for (int y = yb; y < ye; ++y) em |= ((csw[(size_t)y * lv.wpr + (x >> 5)].y >> (x & 31)) & 1u) << (y - yb);
   } else if (in) {
 #pragma unroll 8
     for (int y = yb; y < ye; ++y) em |= (edges[(size_t)y * lv.w + x] ? 1u : 0u) << (y - yb);
@@ -2336,7 +2374,8 @@ void launch_canny_nms(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t
 }
 
 // hysteresis + edge planes + tile histograms: one workgroup per (level, frame)
-void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
+template <bool LAZY>
+static void launch_hyst_t(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
   size_t e_bytes = 0, ec_bytes = 0;
   for (int l = 0; l < g.n_levels; ++l) {
     const size_t nw = (size_t)g.lv[l].h * g.lv[l].wpr;
@@ -2346,8 +2385,8 @@ void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
   }
   static bool attr_set = false;
   if (!attr_set) {  // more than the default 64 KB of dynamic LDS
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst<true>), hipFuncAttributeMaxDynamicSharedMemorySize, REVO_HYST_LDS_MAX);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst<false>), hipFuncAttributeMaxDynamicSharedMemorySize, REVO_HYST_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst<true, false, LAZY>), hipFuncAttributeMaxDynamicSharedMemorySize, REVO_HYST_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst<false, false, LAZY>), hipFuncAttributeMaxDynamicSharedMemorySize, REVO_HYST_LDS_MAX);
     attr_set = true;
   }
   // Banded (several workgroups per level and frame) when a level does not fit the single-workgroup union-find -- 1280x960
@@ -2362,7 +2401,7 @@ void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
     static bool attr2 = false;
     if (!attr2) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_band), hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS_WORDS * 4);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_out), hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS_WORDS * 4);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_out<LAZY>), hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS_WORDS * 4);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_seam), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       (void)hipGetLastError();  // (a refused attribute must not surface as the error of the next launch check)
       attr2 = true;
@@ -2376,7 +2415,7 @@ void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
     }
     hipLaunchKernelGGL(k_hyst_band, dim3(g.total_bands * B), dim3(HB_THREADS), HB_LDS_WORDS * 4, s, g, p);
     if (g.any_banded) hipLaunchKernelGGL(k_hyst_seam, dim3(g.n_levels * B), dim3(HS_THREADS), seam_lds, s, g, p, 0);
-    hipLaunchKernelGGL(k_hyst_out, dim3(g.total_bands * B), dim3(HO_THREADS), out_lds, s, g, p, 0);
+    hipLaunchKernelGGL(k_hyst_out<LAZY>, dim3(g.total_bands * B), dim3(HO_THREADS), out_lds, s, g, p, 0);
   }
   // MIXED: every level fits one workgroup, level 0 has several bands, the knob is on: heavy level-0 frames through the bands,
   // everything else through one workgroup, in one launch; then the seam and output passes of the heavy frames and the sweep for
@@ -2385,8 +2424,8 @@ void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
   if (mixed) {
     static bool attr3 = false;
     if (!attr3) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_mixed), hipFuncAttributeMaxDynamicSharedMemorySize, REVO_HYST_LDS_MAX);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_out), hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS_WORDS * 4);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_mixed<LAZY>), hipFuncAttributeMaxDynamicSharedMemorySize, REVO_HYST_LDS_MAX);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_out<LAZY>), hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS_WORDS * 4);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyst_seam), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       (void)hipGetLastError();
       attr3 = true;
@@ -2394,19 +2433,24 @@ void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
     const LevelGeom& l0 = g.lv[0];
     const size_t seam_lds = std::max<size_t>(4, (size_t)l0.nbands * (size_t)(HB_LDS_WORDS / 2 / 32 + 64) * 4);
     const size_t out_lds = std::max<size_t>(4, (size_t)l0.band_rows * l0.wpr * 4);
-    hipLaunchKernelGGL(k_hyst_mixed, dim3((l0.nbands + g.n_levels) * B), dim3(HYST_THREADS), REVO_HYST_LDS_MAX, s, g, p, B);
+    hipLaunchKernelGGL(k_hyst_mixed<LAZY>, dim3((l0.nbands + g.n_levels) * B), dim3(HYST_THREADS), REVO_HYST_LDS_MAX, s, g, p, B);
     hipLaunchKernelGGL(k_hyst_seam, dim3(B), dim3(HS_THREADS), seam_lds, s, g, p, 1);
-    hipLaunchKernelGGL(k_hyst_out, dim3(l0.nbands * B), dim3(HO_THREADS), out_lds, s, g, p, 1);
-    hipLaunchKernelGGL(k_hyst<true>, dim3(std::min(32, g.n_levels * B)), dim3(HYST_THREADS), REVO_HYST_LDS_MAX, s, g, p, 1, B);
+    hipLaunchKernelGGL(k_hyst_out<LAZY>, dim3(l0.nbands * B), dim3(HO_THREADS), out_lds, s, g, p, 1);
+    hipLaunchKernelGGL((k_hyst<true, false, LAZY>), dim3(std::min(32, g.n_levels * B)), dim3(HYST_THREADS), REVO_HYST_LDS_MAX, s, g, p, 1, B);
     return;
   }
   const int n_wg = only_flagged ? std::min(32, g.n_levels * B) : g.n_levels * B;
   if (ec_bytes + 4096 <= REVO_HYST_LDS_MAX)  // candidate bitmap + union-find labels in LDS: all of it (one workgroup per CU anyway)
-    hipLaunchKernelGGL(k_hyst<true>, dim3(n_wg), dim3(HYST_THREADS), REVO_HYST_LDS_MAX, s, g, p, only_flagged, B);
+    hipLaunchKernelGGL((k_hyst<true, false, LAZY>), dim3(n_wg), dim3(HYST_THREADS), REVO_HYST_LDS_MAX, s, g, p, only_flagged, B);
   else if (e_bytes <= REVO_HYST_LDS_MAX)  // big levels: only the edge bitmap lives in LDS, the (constant) candidate words are re-read through L1/L2
-    hipLaunchKernelGGL(k_hyst<false>, dim3(n_wg), dim3(HYST_THREADS), e_bytes, s, g, p, only_flagged, B);
+    hipLaunchKernelGGL((k_hyst<false, false, LAZY>), dim3(n_wg), dim3(HYST_THREADS), e_bytes, s, g, p, only_flagged, B);
   else  // very big levels (beyond ~1280 x 990): the edge bitmap in the scratch plane -- the last resort behind the bands
-    hipLaunchKernelGGL((k_hyst<false, true>), dim3(n_wg), dim3(HYST_THREADS), 16, s, g, p, only_flagged, B);
+    hipLaunchKernelGGL((k_hyst<false, true, LAZY>), dim3(n_wg), dim3(HYST_THREADS), 16, s, g, p, only_flagged, B);
+}
+
+void launch_hyst(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
+  if (g.edge_bytes_lazy) launch_hyst_t<true>(g, p, B, s);  // the same bodies without the byte planes' output phase
+  else launch_hyst_t<false>(g, p, B, s);
 }
 
 void launch_fill(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
@@ -2422,6 +2466,10 @@ void launch_fill(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
     const int n = (g.lv[l - 1].w / 2) * (g.lv[l - 1].h / 2);
     hipLaunchKernelGGL(k_fill, dim3(std::min(64, (n + 1023) / 1024), 1, B), dim3(1024), 0, s, g, p, l);
   }
+}
+
+void launch_edge_bytes(const PyrGeom& g, const FramePlanes& p, int B, hipStream_t s) {
+  hipLaunchKernelGGL(k_edge_bytes, dim3((g.total_pix / 16 + 255) / 256, B), dim3(256), 0, s, g, p);
 }
 
 // the hot path's edge list: tile-ordered, for the tracker (the reference-ordered list is launch_compact, on demand)

@@ -162,6 +162,7 @@ static int assess_launch(revo_ctx* c, const float T_w_curr[16], const revo_pyr* 
   if (hl < 0 || hl >= c->geom.n_levels) return fail(REVO_ERR_LEVEL, "histogram_level outside the pyramid");
   hipStream_t vs = c->vote_stream;
   TRY(wait_ready_on(c, curr, vs));
+  TRY(ensure_edge_bytes(c, curr->fs, vs));  // k_vote_hist reads edges / edges_orig of the histogram level
   float inv[16];
   mat4_inverse(T_w_curr, inv);
   int nframes = 0;
