@@ -1832,6 +1832,116 @@ typedef struct revo_map_tsdf_refill_info {  /* 32 bytes, little-endian, no paddi
 int revo_map_tsdf_refill(revo_map* m, const revo_map_df_box* box, revo_map_tsdf_cell* tsdf, revo_map_tsdf_color* color, int device_tsdf,
                          size_t n, const revo_map_tsdf_record* records, int device_in, revo_map_tsdf_refill_info* info);
 
+/* ---- surfaces for many sequences at once: batched fuse and track -------------------------------------------------
+ * revo_map_tsdf_fuse* and revo_map_tsdf_track* are one volume per call.  These calls take a list of jobs, each with its own
+ * volume, box, view or frame and voxel edge, and run all of them in one launch (the Gauss-Newton loop: one launch, one copy and
+ * one wait per round for all jobs together).  Every output has an exact specification, the single calls: a job's bytes are the
+ * bytes the single call leaves for that job alone.  Everything lives in device memory of m's device; m gives the context, the
+ * tracker stream and the scratch, a job's own map (of m's context; NULL: m) gives the job's voxel edge.
+ *
+ * One fuse job: the view is fused into the job's volumes as revo_map_tsdf_fuse_color (color given) or revo_map_tsdf_fuse (color
+ * NULL) does with n = 1, accumulate = 1, device_in = 1 and device_tsdf = 1: the volumes are read and updated. */
+typedef struct revo_map_tsdf_fuse_job {  /* 200 bytes, no padding holes */
+  revo_map* map;                         /* gives the voxel edge; of m's context; NULL: m                                   */
+  revo_map_df_box box;                   /* the box rules of revo_map_distance_field                                          */
+  float trunc;                           /* metres; 0: 4 x the job's voxel edge; else finite and > 0                          */
+  uint32_t reserved;                     /* zero                                                                              */
+  revo_map_tsdf_cell* tsdf;              /* device, 16-byte aligned: n[0]*n[1]*n[2] cells                                     */
+  revo_map_tsdf_color* color;            /* device, 16-byte aligned, or NULL: no colour is fused                              */
+  revo_map_carve_view view;              /* kf, or a raw depth image in device memory (4-byte aligned); every view rule of    */
+                                         /* revo_map_carve_eval                                                               */
+  const uint8_t* bgr;                    /* with color: NULL for a pyramid view, the device colour image of a raw view;       */
+                                         /* without color: NULL                                                               */
+  revo_map_tsdf_info* info;              /* device, 16-byte aligned, or NULL                                                  */
+  revo_map_tsdf_color_info* color_info;  /* device, 16-byte aligned, or NULL; NULL without color                              */
+  revo_map_carve_view_info* view_info;   /* device, 16-byte aligned, or NULL: one record                                      */
+} revo_map_tsdf_fuse_job;
+/* n_jobs (1 .. 1024) fuse jobs in ONE launch on m's context's tracker stream, for a pyramid view behind that pyramid's build.
+ * The call only enqueues.  After it every job's volumes and records hold exactly the bytes the single call leaves (above); the
+ * order of the jobs cannot show.  No atomic touches a cell, so two jobs must not share one.
+ * REVO_ERR_INVALID_ARG, the call refused as a whole before anything is enqueued and with no byte written: NULL m or jobs; n_jobs
+ * outside 1 .. 1024; in any job: a map of another context, a NULL tsdf, a box, view, bgr, trunc or alignment rule of the single
+ * call broken, a reserved word that is not 0, bgr or color_info given without color, a volume or an image that is not in device
+ * memory of m's device; two volumes (TSDF or colour, of any two jobs) whose byte ranges overlap. */
+int revo_map_tsdf_fuse_many(revo_map* m, int n_jobs, const revo_map_tsdf_fuse_job* jobs);
+
+/* One track job: revo_map_tsdf_track_eval's arguments for one volume and one frame (device_tsdf = 1, device_in = 1). */
+typedef struct revo_map_tsdf_track_job {  /* 200 bytes, no padding holes */
+  revo_map* map;                          /* gives the voxel edge; of m's context; NULL: m                                    */
+  revo_map_df_box box;
+  float trunc;                            /* the volume's truncation distance in metres: finite and > 0                       */
+  int32_t n_poses;                        /* revo_map_tsdf_track_eval_many: the job's poses, >= 1; revo_map_tsdf_track_many: the job's own */
+                                          /* max_iters, 0: the options'                                                       */
+  const revo_map_tsdf_cell* tsdf;         /* device, 16-byte aligned                                                          */
+  revo_map_carve_view frame;              /* kf, or a raw depth image in device memory; its T_w_c is not read                 */
+  revo_map_tsdf_track_params prm;         /* all zero: the defaults and centre 0                                              */
+  const float* poses;                     /* host: n_poses 4x4 column-major T_w_c (eval_many), or the 16 floats of T_init (track_many) */
+} revo_map_tsdf_track_job;
+/* The records of all jobs, job after job (job j's records start behind those of the jobs before it), from ONE launch for all
+ * poses of all jobs: at most 4096 poses in total.  A job's records are the bytes revo_map_tsdf_track_eval gives for that job
+ * alone, the flags-bit-0 record of a pose that is not finite or not orthogonal included.  Frames may differ in size and stride.
+ * out: device memory 16-byte aligned (device_out = 1, the call only enqueues) or host memory (0, the call waits).
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, jobs or out; n_jobs outside 1 .. 1024; in
+ * any job every rule of revo_map_tsdf_track_eval, n_poses < 1, NULL poses, a map of another context, a volume or an image that is
+ * not in device memory of m's device; more than 4096 poses in total; device_out outside 0 / 1; a misaligned device output. */
+int revo_map_tsdf_track_eval_many(revo_map* m, int n_jobs, const revo_map_tsdf_track_job* jobs, revo_map_tsdf_track_info* out,
+                                  int device_out);
+
+typedef struct revo_map_tsdf_track_result {  /* 288 bytes, no padding holes */
+  float T[16];                     /* revo_map_tsdf_track's T_out                                  */
+  revo_map_tsdf_track_info info;   /* ... info_out                                                 */
+  int32_t iterations, status;      /* ... iterations and status                                    */
+  int32_t evaluations;             /* the records the job's loop took: iterations + 1, or + 2 for REVO_ALIGN_LOST */
+  int32_t reserved;                /* zero */
+} revo_map_tsdf_track_result;
+/* revo_map_tsdf_track's Gauss-Newton loop for all jobs (1 .. 1024) in lockstep from each job's T_init (poses); opt: one set of
+ * options for all jobs (NULL: revo_map_tsdf_track's defaults; a job's n_poses > 0 is that job's max_iters instead).  A round evaluates, in one launch, the current pose of every job
+ * that still needs an evaluation (the closing evaluation that gives info counts as one), copies those records once, waits once
+ * and advances each job on the host.  Per job T, info, iterations and status are exactly revo_map_tsdf_track's for that job
+ * alone.  *rounds (may be NULL): the rounds taken, which is the largest `evaluations` of any job.  results: host memory, n_jobs
+ * records.  The call waits.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: as revo_map_tsdf_track_eval_many without the
+ * output's rules; NULL results; a T_init that is not finite; max_iters < 1; a job's n_poses < 0. */
+int revo_map_tsdf_track_many(revo_map* m, int n_jobs, const revo_map_tsdf_track_job* jobs, const revo_map_align_opts* opt,
+                             revo_map_tsdf_track_result* results, int32_t* rounds);
+
+/* A surface for a stream of revo_vo_multi: the caller-owned device volumes of a box, fused from every keyframe the stream
+ * promotes from now on, in the step, right behind the batched map integration of the step's promoted keyframes. */
+typedef struct revo_vo_multi_surface {  /* 120 bytes, no padding holes */
+  revo_map* map;                        /* gives the voxel edge; of the handle's context                            */
+  revo_map_df_box box;
+  float trunc;                          /* metres; 0: 4 voxel edges                                                 */
+  int32_t track;                        /* 0 / 1: each keyframe is tracked against the surface before it is fused   */
+  revo_map_tsdf_cell* tsdf;             /* device, 16-byte aligned; they outlive the attachment                     */
+  revo_map_tsdf_color* color;           /* or NULL                                                                  */
+  revo_map_tsdf_track_params track_prm; /* read with track                                                          */
+  revo_map_align_opts track_opts;       /* read with track; max_iters 0: revo_map_tsdf_track's defaults             */
+} revo_vo_multi_surface;
+typedef struct revo_vo_multi_surface_report {  /* 408 bytes, no padding holes: a stream's last keyframe */
+  double timestamp;
+  float T_w_kf[16];                     /* the keyframe's pose as the tracker has it: the trajectory's and the map's    */
+  float T_fused[16];                    /* the pose it was fused at: the refined pose of a CONVERGED track, else T_w_kf */
+  revo_map_tsdf_track_info track;       /* with tracked: revo_map_tsdf_track's info_out; else zero                      */
+  int32_t iterations, status;           /* revo_map_tsdf_track's; REVO_ALIGN_LOST without a track                       */
+  int32_t tracked;                      /* 1: the loop ran (track on and T_w_kf passes the orthogonality rule)          */
+  int32_t fused;                        /* 1: the keyframe was fused; 0: T_fused fails the rule (or the call failed)    */
+  revo_map_carve_view_info view_info;   /* of the fuse; zero when not fused                                             */
+  uint64_t keyframes_fused, keyframes_skipped;  /* running counts since the surface was attached                        */
+} revo_vo_multi_surface_report;
+/* s == NULL detaches; revo_vo_multi_reset detaches.  In revo_vo_multi_step every promoted keyframe whose stream has a surface is
+ * handled as the sequential driver handles it: with track, one revo_map_tsdf_track_many over those keyframes against their
+ * volumes as they stand, from T_w_kf (a T_w_kf that fails revo_map_align_eval's orthogonality rule is not tracked); the fuse pose
+ * is the refined pose where the status is REVO_ALIGN_CONVERGED and T_w_kf otherwise; a keyframe whose fuse pose fails the rule is
+ * not fused and is counted; then one revo_map_tsdf_fuse_many over the rest.  A step never fails for a surface, as it never fails
+ * for a map; the reported trajectory and the map integration keep T_w_kf.  Without a surface on any promoted stream nothing is
+ * enqueued.
+ * REVO_ERR_INVALID_ARG: a stream out of range; a map of another context or NULL; the box, trunc, alignment or parameter rules of
+ * revo_map_tsdf_fuse_many and revo_map_tsdf_track_many; track outside 0 / 1; volumes that are not in device memory. */
+int revo_vo_multi_attach_surface(revo_vo_multi* mv, int stream, const revo_vo_multi_surface* s);
+/* The report of the stream's last keyframe since the surface was attached; waits for that step's fuse.
+ * REVO_ERR_INVALID_ARG: a bad stream or NULL out, no surface attached, or no keyframe since it was. */
+int revo_vo_multi_surface_last(revo_vo_multi* mv, int stream, revo_vo_multi_surface_report* out);
+
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end
  * (iowrapperRGBD.cpp:257-333) for the multi-stream driver.  Inflate (zlib, RFC 1950/1951: stored, fixed and dynamic blocks,

@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -198,6 +198,11 @@ def lib():
                                       C.POINTER(MapTsdfTrackParams), C.POINTER(MapAlignOpts), f32p, C.POINTER(MapTsdfTrackInfo), i32p, i32p]
     L.revo_map_tsdf_shift.argtypes = [vp, C.POINTER(MapDfBox), i32p, vp, vp, vp, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, vp]
     L.revo_map_tsdf_refill.argtypes = [vp, C.POINTER(MapDfBox), vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.POINTER(MapTsdfRefillInfo)]
+    L.revo_map_tsdf_fuse_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfFuseJob)]
+    L.revo_map_tsdf_track_eval_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfTrackJob), vp, C.c_int]
+    L.revo_vo_multi_attach_surface.argtypes = [vp, C.c_int, C.POINTER(MultiSurface)]
+    L.revo_vo_multi_surface_last.argtypes = [vp, C.c_int, C.POINTER(MultiSurfaceReport)]
+    L.revo_map_tsdf_track_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfTrackJob), C.POINTER(MapAlignOpts), C.POINTER(MapTsdfTrackResult), i32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]
     L.revo_png_decoder_destroy.argtypes = [vp]

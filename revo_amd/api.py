@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfTrackParams, MapTsdfRayInfo,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1432,6 +1432,130 @@ class VoxelMap:
         return {"T": T1.reshape(4, 4).T.copy(), "info": info, "iterations": it.value, "status": st.value, "cov": cov, "sigma2": s2,
                 "centre": np.array(list(p.centre), np.float32)}
 
+    # -- surfaces for many sequences at once (revo_map_tsdf_fuse_many / _track_eval_many / _track_many)
+    def _job_map(self, job):
+        m = job.get("map")
+        m = self if m is None else (m.map if isinstance(m, MapWindow) else m)
+        if not isinstance(m, VoxelMap):
+            raise ValueError("a job's map is a VoxelMap (or a MapWindow) of this map's context")
+        return m
+
+    def _fuse_jobs(self, jobs):
+        """-> (the revo_map_tsdf_fuse_job array of fuse_many_into's jobs, how many, what keeps the memory alive)."""
+        import torch
+        from . import mapfile
+        jobs = list(jobs)
+        arr = (MapTsdfFuseJob * max(len(jobs), 1))()
+        keep = []
+        for j, job in zip(arr, jobs):
+            m = self._job_map(job)
+            d_tsdf, d_color = job["d_tsdf"], job.get("d_color")
+            self._surface_tensors(d_tsdf, d_color, "d_tsdf")
+            view = tuple(job["view"])
+            if d_color is not None:
+                cv, device_in, kv, bgr, kc_ = m._color_views([view])
+                j.bgr = bgr[0]
+                keep.append(kc_)
+            else:
+                cv, device_in, kv = m._carve_views([view])
+            if not isinstance(view[0], ImgPyramidRGBD) and not device_in:
+                raise ValueError("the images of a batched fuse are device tensors")
+            keep.append(kv)
+            j.map = m._h
+            j.box = m._df_box(job["lo"], tuple(d_tsdf.shape[:3]), 0, 1)
+            j.trunc = float(mapfile.tsdf_trunc(m.voxel, job.get("trunc")))
+            j.tsdf = d_tsdf.data_ptr()
+            j.color = d_color.data_ptr() if d_color is not None else None
+            C.memmove(C.byref(j.view), C.byref(cv[0]), C.sizeof(MapCarveView))
+            for key, field, size in (("d_info", "info", 64), ("d_color_info", "color_info", 32), ("d_view_info", "view_info", 32)):
+                t_ = job.get(key)
+                if t_ is None:
+                    continue
+                if not (t_.is_contiguous() and t_.is_cuda and t_.numel() * t_.element_size() == size):
+                    raise ValueError("d_info needs 64 bytes, d_view_info and d_color_info 32 bytes each, contiguous on the device")
+                setattr(j, field, t_.data_ptr())
+            keep.append(job)
+        if jobs:
+            torch.cuda.current_stream(jobs[0]["d_tsdf"].device).synchronize()  # the tensors' earlier use is over before the tracker stream writes
+        return arr, len(jobs), keep
+
+    def fuse_many_into(self, jobs, wait=True):
+        """Many (volume, view) fuses in one launch (revo_map_tsdf_fuse_many): every job's volumes hold afterwards what
+        fuse_into(..., accumulate=True) leaves for that job alone.  A job is a dict: d_tsdf (int32 device tensor [n0, n1, n2, 2]), lo,
+        view (as fuse_into takes one: a pyramid view, or a raw view with device images -- (depth, T, intrinsics or None[, bgr])), and
+        optionally trunc, d_color (int32 [n0, n1, n2, 4]), map (the VoxelMap that gives the job's voxel edge; default: this one),
+        d_info (64 bytes), d_color_info (32 bytes), d_view_info (32 bytes).  1 .. 1024 jobs, everything on the device; the call is
+        only enqueued on the context's tracker stream: wait=False returns at once."""
+        arr, n, keep = self._fuse_jobs(jobs)
+        check(_lib.lib().revo_map_tsdf_fuse_many(self._h, n, arr))
+        if wait:
+            self.sync()
+        del keep
+
+    def _track_jobs(self, jobs, with_poses):
+        """-> (the revo_map_tsdf_track_job array of a batched tracking call, the poses per job, what keeps the memory alive).  A job is a
+        dict: tsdf (int32 device tensor), lo, trunc, frame (a pyramid or (device depth, camera[, zrange])), poses (with_poses: one 4x4 or
+        [n, 4, 4]) or T_init, and optionally max_dist, stride, min_weight, centre, map and (the loop) max_iters, the job's own limit."""
+        jobs = list(jobs)
+        arr = (MapTsdfTrackJob * max(len(jobs), 1))()
+        keep, counts = [], []
+        for j, job in zip(arr, jobs):
+            m = self._job_map(job)
+            box, tp, tdev, cv, din, tr, p, kp = m._surface_track_args(job["tsdf"], job["lo"], job["trunc"], job["frame"], job.get("max_dist"),
+                                                                      job.get("stride", 1), job.get("min_weight", 1), job.get("centre"))
+            if not tdev or (not isinstance(job["frame"], ImgPyramidRGBD) and not din):
+                raise ValueError("the volumes and images of a batched tracking call are device tensors")
+            T = np.asarray(job["poses"] if with_poses else job["T_init"], np.float32).reshape(-1, 4, 4)
+            if not with_poses and len(T) != 1:
+                raise ValueError("T_init is one 4x4 pose")
+            flat = np.ascontiguousarray(np.concatenate([_cm4(M) for M in T]) if len(T) else np.zeros(0, np.float32))
+            keep += [kp, flat]
+            counts.append(len(T))
+            j.map, j.box, j.trunc, j.n_poses, j.tsdf = m._h, box, tr, len(T) if with_poses else int(job.get("max_iters") or 0), tp
+            C.memmove(C.byref(j.frame), C.byref(cv[0]), C.sizeof(MapCarveView))
+            j.prm = p
+            j.poses = flat.ctypes.data
+        return arr, len(jobs), counts, keep
+
+    def surface_track_eval_many(self, jobs, d_out=None):
+        """The tracking sums of many (volume, frame) jobs, all poses of all jobs in one launch (revo_map_tsdf_track_eval_many; at most 4096
+        poses in total): per job the MapTsdfTrackInfo records surface_track_eval gives for it alone -> a list of lists.  jobs: see
+        _track_jobs.  d_out: a torch uint8 device tensor of (all poses) x 208 bytes takes the records, job after job, instead
+        (returns None; the call only enqueues)."""
+        arr, n, counts, keep = self._track_jobs(jobs, True)
+        total = sum(counts)
+        if d_out is not None:
+            if not (d_out.is_cuda and d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= total * C.sizeof(MapTsdfTrackInfo)):
+                raise ValueError("d_out must be a contiguous device tensor of (all poses) x %d bytes" % C.sizeof(MapTsdfTrackInfo))
+            import torch
+            torch.cuda.current_stream(d_out.device).synchronize()
+            check(_lib.lib().revo_map_tsdf_track_eval_many(self._h, n, arr, vp(d_out.data_ptr()), 1))
+            return None
+        out = (MapTsdfTrackInfo * max(total, 1))()
+        check(_lib.lib().revo_map_tsdf_track_eval_many(self._h, n, arr, C.cast(out, vp), 0))
+        del keep
+        recs, at = [], 0
+        for c in counts:
+            recs.append([out[at + i] for i in range(c)])
+            at += c
+        return recs
+
+    def surface_track_many(self, jobs, max_iters=30, eps_t=1e-6, eps_r=1e-6, min_matched=12):
+        """surface_track's Gauss-Newton loop for many (volume, frame, T_init) jobs in lockstep (revo_map_tsdf_track_many): one launch, one
+        copy and one wait per round for all jobs.  -> (a list of dicts as surface_track gives them, plus `evaluations`; rounds)."""
+        arr, n, _, keep = self._track_jobs(jobs, False)
+        o = MapAlignOpts(int(max_iters), 0, float(eps_t), float(eps_r), int(min_matched))
+        res, rounds = (MapTsdfTrackResult * max(n, 1))(), C.c_int32()
+        check(_lib.lib().revo_map_tsdf_track_many(self._h, n, arr, C.byref(o), res, C.byref(rounds)))
+        del keep
+        out = []
+        for j, r in zip(arr, res):
+            info = MapTsdfTrackInfo.from_buffer_copy(bytes(r.info))
+            cov, s2 = tsdf_track_covariance(info)
+            out.append({"T": np.array(list(r.T), np.float32).reshape(4, 4).T.copy(), "info": info, "iterations": int(r.iterations), "status": int(r.status),
+                        "cov": cov, "sigma2": s2, "centre": np.array(list(j.prm.centre), np.float32), "evaluations": int(r.evaluations)})
+        return out, int(rounds.value)
+
     def frontiers(self, seen, min_views=1, min_count=1):
         """Where known space ends -> [k, 3] int32 voxel indices in ascending order of the cell's place in the box: the cells
         of a SeenVolume that are not solid, have >= min_views free votes and have a face neighbour inside the box that is
@@ -2285,6 +2409,35 @@ class FollowingSurface(SurfaceVolume):
         return self.assemble().mesh(min_weight, normals, colors)
 
 
+def fuse_surfaces(pairs, wait=False):
+    """[(SurfaceVolume, view), ...] -- one view into each surface of as many running sequences, all in one launch
+    (VoxelMap.fuse_many_into): each volume afterwards holds what its own integrate(view) leaves, and its `views` and
+    per-view counts go on as there.  The surfaces' maps share one context; the volumes are distinct."""
+    import torch
+    pairs = list(pairs)
+    if not pairs:
+        return
+    jobs = []
+    for surf, view in pairs:
+        vi = torch.zeros(8, dtype=torch.int32, device=surf.d_tsdf.device)
+        jobs.append(dict(map=surf.map, d_tsdf=surf.d_tsdf, d_color=surf.d_color, lo=surf.lo, trunc=surf.trunc, view=view, d_view_info=vi))
+    pairs[0][0].map.fuse_many_into(jobs, wait=wait)
+    for (surf, _), job in zip(pairs, jobs):
+        surf._vinfo.append(job["d_view_info"])
+        surf.views += 1
+
+
+def track_surfaces(triples, max_dist=None, stride=1, min_weight=1, centre=None, **opts):
+    """[(SurfaceVolume, frame, T_init), ...] -- each frame's camera pose refined against its own surface as it stands, all loops in
+    lockstep (VoxelMap.surface_track_many) -> (a list of dicts as SurfaceVolume.track gives them, rounds)."""
+    triples = list(triples)
+    if not triples:
+        return [], 0
+    jobs = [dict(map=s.map, tsdf=s.d_tsdf, lo=s.lo, trunc=s.trunc, frame=f, T_init=T, max_dist=max_dist, stride=stride, min_weight=min_weight, centre=centre)
+            for s, f, T in triples]
+    return triples[0][0].map.surface_track_many(jobs, **opts)
+
+
 def explore(m, seen, start, clearance, min_views=1, min_count=1, max_len=4096):
     """The whole route from mapping to exploration on the map's device: the known field of `seen` (a SeenVolume), its
     frontiers, the cost-to-go with the frontiers as goals at the clearance (metres), and the path from `start` (a voxel index,
@@ -2654,6 +2807,16 @@ class MapWindow:
 
     def surface_track(self, *args, **kw):
         return self.map.surface_track(*args, **kw)
+
+    def fuse_many_into(self, *args, **kw):
+        """The inner map's batched surface calls: the window's voxels play no part."""
+        return self.map.fuse_many_into(*args, **kw)
+
+    def surface_track_eval_many(self, *args, **kw):
+        return self.map.surface_track_eval_many(*args, **kw)
+
+    def surface_track_many(self, *args, **kw):
+        return self.map.surface_track_many(*args, **kw)
 
     def shift_into(self, *args, **kw):
         """The inner map's shift_into: surface volumes moved with their box (the window's voxels play no part)."""

@@ -162,6 +162,72 @@ inline int align_loop_over(const float T_init[16], const float centre[3], const 
   return 0;
 }
 
+// align_loop_over turned inside out, for a caller that evaluates many loops' poses together (revo_map_tsdf_track_many):
+// the same state (T, Tsys, it, status), the same arithmetic in the same order, but the caller feeds it one record at a time.
+//   begin(T_init, centre, o);  while (s.wants()) { evaluate a record at s.pose(); s.feed(record, fill); }
+// then pose() is T_out, rec the closing record, it and st the iterations and the status.  The records it asks for are
+// align_loop_over's evaluations, one for one: `evals` of them, it + 1, or it + 2 when the status is LOST.
+// tests/cpp/align_stepper_host.cpp holds the two against each other.
+template <class Rec>
+struct AlignStepper {
+  double T[16], Tsys[16], Cp[16], Cm[16];
+  revo_map_align_opts o;
+  int it, st, evals;
+  int phase;  // 0: the next record is an iteration's; 1: the next record is the closing one; 2: done
+  float Tf[16];
+  Rec rec;
+
+  void begin(const float T_init[16], const float centre[3], const revo_map_align_opts& opts) {
+    for (int r = 0; r < 4; ++r)
+      for (int col = 0; col < 4; ++col) T[4 * r + col] = (double)T_init[4 * col + r];
+    memcpy(Tsys, T, sizeof(T));
+    const double cx = centre[0], cy = centre[1], cz = centre[2];
+    const double cp[16] = {1, 0, 0, cx, 0, 1, 0, cy, 0, 0, 1, cz, 0, 0, 0, 1}, cm[16] = {1, 0, 0, -cx, 0, 1, 0, -cy, 0, 0, 1, -cz, 0, 0, 0, 1};
+    memcpy(Cp, cp, sizeof(cp));
+    memcpy(Cm, cm, sizeof(cm));
+    o = opts;
+    st = REVO_ALIGN_ITER_LIMIT; it = 0; evals = 0;
+    phase = it < o.max_iters ? 0 : 1;
+    to_float();
+  }
+  bool wants() const { return phase != 2; }
+  const float* pose() const { return Tf; }  // column-major: where the next record is wanted; T_out once nothing is
+  template <class Fill>
+  void feed(const Rec& r, Fill&& fill) {
+    rec = r;
+    ++evals;
+    if (phase == 1) { phase = 2; return; }
+    double H[36], g[6], x[6];
+    bool have = !(rec.flags & 1) && rec.matched >= o.min_matched;
+    if (have) { fill(&rec, H, g); have = align_solve(H, g, x); }
+    if (!have) {
+      st = REVO_ALIGN_LOST;
+      memcpy(T, Tsys, sizeof(T));
+      phase = 1;
+      to_float();
+      return;
+    }
+    ++it;
+    memcpy(Tsys, T, sizeof(T));
+    double E[16], M[16];
+    se3_exp_d(x, E);
+    mat4_mul(Cp, E, M);
+    mat4_mul(M, Cm, M);
+    mat4_mul(M, T, T);
+    double mv = 0.0, mw = 0.0;
+    for (int i = 0; i < 3; ++i) { mv = std::max(mv, std::fabs(x[i])); mw = std::max(mw, std::fabs(x[3 + i])); }
+    if (mv < o.eps_t && mw < o.eps_r) { st = REVO_ALIGN_CONVERGED; phase = 1; }
+    else if (!(it < o.max_iters)) phase = 1;
+    to_float();
+  }
+
+ private:
+  void to_float() {
+    for (int r = 0; r < 4; ++r)
+      for (int col = 0; col < 4; ++col) Tf[4 * col + r] = (float)T[4 * r + col];
+  }
+};
+
 // revo_map_align's loop: point-to-point records
 template <class Eval>
 inline int align_loop(const float T_init[16], const float centre[3], const revo_map_align_opts& o, Eval&& eval, float T_out[16],

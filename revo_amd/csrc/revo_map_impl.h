@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip, revo_map_tsdf_follow.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip, revo_map_tsdf_follow.hip, revo_map_tsdf_many.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.
@@ -296,6 +296,19 @@ struct MapTsdfFollowScratch {
   DevBuf work, dst, dstcol, recs;
 };
 
+// revo_map_tsdf_fuse_many / revo_map_tsdf_track_eval_many / revo_map_tsdf_track_many (revo_map_tsdf_many.hip): the job
+// tables of a launch and its pose rows, the fuse's counter lines and tickets, the tracker's tickets, counts and published
+// partials, and the device records of a host-output call.  Only these three calls go through them.
+struct TsdfManyFuseJob;   // revo_map_tsdf_many.hip: one job of a batched fuse
+struct TsdfManyTrackJob;  // ... one job of a batched tracking launch
+struct TsdfManyPose;      // ... one pose of it, with its job
+struct MapTsdfManyScratch {
+  HostRows<TsdfManyFuseJob> fuse_jobs;
+  HostRows<TsdfManyTrackJob> track_jobs;
+  HostRows<TsdfManyPose> poses;
+  DevBuf fuse_work, track_work, out;
+};
+
 struct revo_map {
   revo_ctx* ctx = nullptr;
   MapCtxGeom g{};
@@ -359,6 +372,8 @@ struct revo_map {
   MapTsdfTrackScratch tsdftrk;
   // revo_map_tsdf_shift / revo_map_tsdf_refill: everything of theirs, in a type of its own
   MapTsdfFollowScratch tsdffol;
+  // revo_map_tsdf_fuse_many / revo_map_tsdf_track_eval_many / revo_map_tsdf_track_many: everything of theirs, in a type of its own
+  MapTsdfManyScratch tsdfmany;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every

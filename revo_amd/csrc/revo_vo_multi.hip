@@ -15,6 +15,7 @@
 #include "revo_mat4.h"
 #include "revo_multi.h"
 #include "revo_map.h"
+#include "revo_pose_host.h"
 
 namespace {
 struct Ref { void* set; int frame; double ts; };  // a frame of a step set
@@ -42,6 +43,18 @@ struct Stream {
   revo_pair_info info{};
   double info_kf_ts = 0.0;
 };
+// revo_vo_multi_attach_surface's per-stream state: the attachment, the last keyframe's report and the device record its fuse writes
+struct Surface {
+  bool on = false, has_last = false;
+  revo_vo_multi_surface s{};
+  revo_vo_multi_surface_report last{};
+  revo_map_carve_view_info* d_vinfo = nullptr;  // device, 32 bytes: the view info of the last fuse
+};
+static_assert(sizeof(revo_vo_multi_surface) == 120 && offsetof(revo_vo_multi_surface, trunc) == 32 && offsetof(revo_vo_multi_surface, tsdf) == 40 &&
+              offsetof(revo_vo_multi_surface, track_prm) == 56 && offsetof(revo_vo_multi_surface, track_opts) == 88, "the surface record is the documented layout");
+static_assert(sizeof(revo_vo_multi_surface_report) == 408 && offsetof(revo_vo_multi_surface_report, T_fused) == 72 && offsetof(revo_vo_multi_surface_report, track) == 136 &&
+              offsetof(revo_vo_multi_surface_report, iterations) == 344 && offsetof(revo_vo_multi_surface_report, view_info) == 360 &&
+              offsetof(revo_vo_multi_surface_report, keyframes_fused) == 392, "the report is the documented layout");
 }  // namespace
 
 struct revo_vo_multi {
@@ -53,6 +66,8 @@ struct revo_vo_multi {
   std::vector<revo_map*> maps;              // per stream: the voxel map its promoted keyframes go into (revo_vo_multi_attach_map)
   revo_map_stage* map_stage = nullptr;      // descriptors of the step's batched map integration
   bool pair_info = false;                   // revo_vo_multi_set_pair_info
+  std::vector<Surface> surf;                // per stream: the surface its promoted keyframes are fused into (revo_vo_multi_attach_surface)
+  int n_surf = 0;                           // how many streams have one
 };
 
 static void ref_add(revo_vo_multi* m, void* set) {
@@ -82,20 +97,38 @@ extern "C" int revo_vo_multi_create(revo_ctx* ctx, int n_streams, int max_queue,
   m->max_queue = max_queue;
   m->st.resize(n_streams);
   m->maps.assign(n_streams, nullptr);
+  m->surf.resize(n_streams);
   *out = m;
   return REVO_OK;
 }
 
 extern "C" void revo_vo_multi_destroy(revo_vo_multi* m) {
   if (!m) return;
-  for (int s = 0; s < m->S; ++s) revo_map_note_attach_(m->maps[s], m, s, 0);
+  for (int s = 0; s < m->S; ++s) {
+    revo_map_note_attach_(m->maps[s], m, s, 0);
+    if (m->surf[s].on) revo_map_note_attach_(m->surf[s].s.map, m, s, 0);
+  }
   revo_mdev_destroy_(m->dev);  // (synchronises the context's streams; the step sets go with it)
+  for (Surface& f : m->surf) (void)hipFree(f.d_vinfo);
   revo_map_stage_destroy_(m->map_stage);
   revo_ctx_release_(m->ctx);
   delete m;
 }
 
 static bool stream_ok(const revo_vo_multi* m, int s) { return m && s >= 0 && s < m->S; }
+
+// A map knows the streams that hold it, as a voxel map or through a surface: told again whenever either changes.
+static void renote(revo_vo_multi* m, int s, revo_map* map) {
+  revo_map_note_attach_(map, m, s, (m->maps[s] == map || (m->surf[s].on && m->surf[s].s.map == map)) ? 1 : 0);
+}
+static void surface_detach(revo_vo_multi* m, int s) {
+  Surface& f = m->surf[s];
+  if (!f.on) return;
+  revo_map* old = f.s.map;
+  f.on = false; f.has_last = false;
+  --m->n_surf;
+  renote(m, s, old);
+}
 
 extern "C" int revo_vo_multi_pending(const revo_vo_multi* m, int s) {
   if (!stream_ok(m, s)) return -1;
@@ -135,6 +168,7 @@ extern "C" int revo_vo_multi_reset(revo_vo_multi* m, int s) {
   x = Stream();
   revo_map_note_attach_(m->maps[s], m, s, 0);  // the next sequence starts without a map
   m->maps[s] = nullptr;
+  surface_detach(m, s);                        // ... and without a surface
   return REVO_OK;
 }
 
@@ -147,14 +181,156 @@ extern "C" int revo_vo_multi_attach_map(revo_vo_multi* m, int s, revo_map* map) 
     const int rc = revo_map_stage_create_(&m->map_stage);
     if (rc) return rc;
   }
-  revo_map_note_attach_(m->maps[s], m, s, 0);
+  revo_map* old = m->maps[s];
   m->maps[s] = map;
-  revo_map_note_attach_(map, m, s, 1);
+  renote(m, s, old);
+  renote(m, s, map);
   return REVO_OK;
 }
-// revo_map_destroy of an attached map
+// revo_map_destroy of an attached map: the stream's surface on that map goes with it
 extern "C" void revo_vo_multi_forget_map_(revo_vo_multi* m, int s, revo_map* map) {
-  if (stream_ok(m, s) && m->maps[s] == map) m->maps[s] = nullptr;
+  if (!stream_ok(m, s)) return;
+  if (m->maps[s] == map) m->maps[s] = nullptr;
+  if (m->surf[s].on && m->surf[s].s.map == map) { m->surf[s].on = false; m->surf[s].has_last = false; --m->n_surf; }
+}
+
+extern "C" int revo_vo_multi_attach_surface(revo_vo_multi* m, int s, const revo_vo_multi_surface* in) {
+  if (!stream_ok(m, s)) return fail(REVO_ERR_INVALID_ARG, "stream out of range");
+  if (!in) { surface_detach(m, s); return REVO_OK; }
+  if (!in->map || revo_map_ctx_(in->map) != m->ctx) return fail(REVO_ERR_INVALID_ARG, "the surface's map is NULL or belongs to another context than the handle");
+  if (in->track != 0 && in->track != 1) return fail(REVO_ERR_INVALID_ARG, "track must be 0 or 1");
+  MapCtxGeom g;
+  const int rc = revo_map_ctx_geom_(m->ctx, &g);
+  if (rc) return rc;
+  if (!in->tsdf || !on_device(in->tsdf, g.device) || (in->color && !on_device(in->color, g.device)))
+    return fail(REVO_ERR_INVALID_ARG, "the surface's volumes must be in device memory of the handle's device");
+  if (((uintptr_t)in->tsdf | (uintptr_t)in->color) & 15) return fail(REVO_ERR_INVALID_ARG, "the surface's volumes are not 16-byte aligned");
+  for (int k = 0; k < 3; ++k)
+    if (in->box.n[k] < 1 || in->box.n[k] > 1024 || in->box.lo[k] < -(1 << 20) || (long long)in->box.lo[k] + in->box.n[k] - 1 > (1 << 20) - 1)
+      return fail(REVO_ERR_INVALID_ARG, "the surface's box breaks the box rules");
+  if ((size_t)in->box.n[0] * (size_t)in->box.n[1] * (size_t)in->box.n[2] > ((size_t)1 << 27)) return fail(REVO_ERR_INVALID_ARG, "the surface's box holds more than 2^27 cells");
+  if (!std::isfinite(in->trunc) || in->trunc < 0.0f) return fail(REVO_ERR_INVALID_ARG, "the surface's trunc must be 0 or finite and > 0");
+  if (in->track && in->track_opts.max_iters < 0) return fail(REVO_ERR_INVALID_ARG, "max_iters must be >= 0");
+  Surface& f = m->surf[s];
+  if (!f.d_vinfo) HIPCHECK(hipMalloc((void**)&f.d_vinfo, sizeof(revo_map_carve_view_info)));
+  surface_detach(m, s);
+  f.s = *in;
+  if (f.s.trunc == 0.0f) {  // the default, resolved once: the tracking jobs need the number
+    float voxel = 0.0f;
+    const int rv = revo_map_voxel_size(in->map, &voxel, nullptr);
+    if (rv) return rv;
+    f.s.trunc = 4.0f * voxel;
+  }
+  f.on = true; f.has_last = false;
+  memset(&f.last, 0, sizeof(f.last));
+  ++m->n_surf;
+  renote(m, s, in->map);
+  return REVO_OK;
+}
+
+extern "C" int revo_vo_multi_surface_last(revo_vo_multi* m, int s, revo_vo_multi_surface_report* out) {
+  if (!stream_ok(m, s) || !out) return fail(REVO_ERR_INVALID_ARG, "bad argument");
+  Surface& f = m->surf[s];
+  if (!f.on || !f.has_last) return fail(REVO_ERR_INVALID_ARG, "no surface report: no surface is attached or the stream has promoted no keyframe since");
+  if (f.last.fused) {  // the record of that step's fuse, behind it on the tracker stream
+    MapCtxGeom g;
+    const int rc = revo_map_ctx_geom_(m->ctx, &g);
+    if (rc) return rc;
+    HIPCHECK(hipStreamSynchronize((hipStream_t)g.stream));
+    HIPCHECK(hipMemcpy(&f.last.view_info, f.d_vinfo, sizeof(f.last.view_info), hipMemcpyDeviceToHost));
+  }
+  *out = f.last;
+  return REVO_OK;
+}
+
+// The promoted keyframes of a step whose streams have a surface, as the sequential driver handles each (vo.REVO): tracked against
+// the surface as it stands, all loops in lockstep; then fused, all in one launch, at the refined pose where the loop converged and
+// at T_w_kf otherwise.  Nothing here fails the step: a call that is refused leaves its keyframes unfused and counted.
+static void surfaces_step(revo_vo_multi* m, const std::vector<MultiFrame>& promote) {
+  if (!m->n_surf) return;
+  std::vector<int> on;  // indices into promote
+  for (size_t i = 0; i < promote.size(); ++i)
+    if (m->surf[promote[i].stream].on) on.push_back((int)i);
+  if (on.empty()) return;
+  for (int i : on) {
+    const MultiFrame& p = promote[i];
+    Surface& f = m->surf[p.stream];
+    revo_vo_multi_surface_report& r = f.last;
+    const uint64_t fused = r.keyframes_fused, skipped = r.keyframes_skipped;
+    memset(&r, 0, sizeof(r));
+    r.keyframes_fused = fused; r.keyframes_skipped = skipped;
+    r.timestamp = p.ts;
+    memcpy(r.T_w_kf, p.T_w, sizeof(r.T_w_kf));
+    memcpy(r.T_fused, p.T_w, sizeof(r.T_fused));
+    r.status = REVO_ALIGN_LOST;
+    f.has_last = true;
+  }
+  // the loops, one call per set of options (one, unless the streams were given different ones)
+  std::vector<int> todo;
+  for (int i : on) {
+    const Surface& f = m->surf[promote[i].stream];
+    if (f.s.track && pose_is_finite(promote[i].T_w) && pose_is_orthogonal(promote[i].T_w)) todo.push_back(i);
+  }
+  auto opts_of = [](const Surface& f) {
+    revo_map_align_opts o = f.s.track_opts;
+    if (o.max_iters == 0) o = revo_map_align_opts{30, 0, 1e-6, 1e-6, 12};
+    return o;
+  };
+  while (!todo.empty()) {
+    const revo_map_align_opts o = opts_of(m->surf[promote[todo[0]].stream]);
+    std::vector<int> now, later;
+    for (int i : todo) {
+      const revo_map_align_opts oi = opts_of(m->surf[promote[i].stream]);
+      (oi.max_iters == o.max_iters && oi.eps_t == o.eps_t && oi.eps_r == o.eps_r && oi.min_matched == o.min_matched ? now : later).push_back(i);
+    }
+    std::vector<revo_map_tsdf_track_job> jobs(now.size());
+    std::vector<revo_map_tsdf_track_result> res(now.size());
+    for (size_t k = 0; k < now.size(); ++k) {
+      const MultiFrame& p = promote[now[k]];
+      const Surface& f = m->surf[p.stream];
+      revo_map_tsdf_track_job& j = jobs[k];
+      memset(&j, 0, sizeof(j));
+      j.map = f.s.map; j.box = f.s.box;
+      j.trunc = f.s.trunc;
+      j.tsdf = f.s.tsdf;
+      j.frame.kf = revo_mdev_keyframe_(m->dev, p.stream);
+      j.prm = f.s.track_prm;
+      j.poses = p.T_w;
+    }
+    if (revo_map_tsdf_track_many(jobs[0].map, (int)jobs.size(), jobs.data(), &o, res.data(), nullptr) == REVO_OK)
+      for (size_t k = 0; k < now.size(); ++k) {
+        revo_vo_multi_surface_report& r = m->surf[promote[now[k]].stream].last;
+        r.track = res[k].info;
+        r.iterations = res[k].iterations; r.status = res[k].status;
+        r.tracked = 1;
+        if (r.status == REVO_ALIGN_CONVERGED) memcpy(r.T_fused, res[k].T, sizeof(r.T_fused));
+      }
+    todo.swap(later);
+  }
+  // the fuse
+  std::vector<revo_map_tsdf_fuse_job> jobs;
+  std::vector<int> who;
+  for (int i : on) {
+    const MultiFrame& p = promote[i];
+    Surface& f = m->surf[p.stream];
+    if (!pose_is_finite(f.last.T_fused) || !pose_is_orthogonal(f.last.T_fused)) { ++f.last.keyframes_skipped; continue; }
+    revo_map_tsdf_fuse_job j;
+    memset(&j, 0, sizeof(j));
+    j.map = f.s.map; j.box = f.s.box;
+    j.trunc = f.s.trunc;
+    j.tsdf = f.s.tsdf; j.color = f.s.color;
+    j.view.kf = revo_mdev_keyframe_(m->dev, p.stream);
+    memcpy(j.view.T_w_c, f.last.T_fused, sizeof(j.view.T_w_c));
+    j.view_info = f.d_vinfo;
+    jobs.push_back(j);
+    who.push_back(p.stream);
+  }
+  if (jobs.empty()) return;
+  const bool ok = revo_map_tsdf_fuse_many(jobs[0].map, (int)jobs.size(), jobs.data()) == REVO_OK;
+  for (int s : who) {
+    revo_vo_multi_surface_report& r = m->surf[s].last;
+    if (ok) { r.fused = 1; ++r.keyframes_fused; } else ++r.keyframes_skipped;
+  }
 }
 
 static int submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16, double depth_scale_factor,
@@ -346,6 +522,7 @@ extern "C" int revo_vo_multi_step(revo_vo_multi* m, revo_stream_result* out, int
     if (!maps.empty() && (rc = revo_map_integrate_views_(m->map_stage, (int)maps.size(), maps.data(), kfs.data(), T.data())))
       return rc;
   }
+  surfaces_step(m, promote);  // the surfaces of the promoted streams: tracked and fused right behind the map integration
   if ((rc = revo_mdev_add_clouds_(m->dev, (int)clouds.size(), clouds.data()))) return rc;
   // results come out in stream order
   std::vector<revo_stream_result> tmp(out, out + n_res);

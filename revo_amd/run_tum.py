@@ -45,6 +45,11 @@ of the whole surface, store and box together; where that spans more than one vol
 message says so and the store is written instead (--surface-store FILE.npz, default FILE.npz beside the mesh; `python -m
 revo_amd.mapfile surface-assemble` cuts boxes out of it).  --surface-store FILE.npz writes the store in any case.  An error with
 --surface-box and with --surface-views.  MultiREVO, an in-place shift and a pyramid of volumes are not part of it.
+--streams-surface FILE.ply (with --streams and --map) gives every dataset of a multi-stream run its own surface on its map
+(vo.MultiREVO's surface): the keyframes a step promotes are fused, all streams in one launch, into volumes of
+--surface-box (the sequential default), with --surface-trunc and --surface-min-weight as --surface takes them; FILE_<dataset>.ply is
+written per dataset, the sequential run's bytes.  --streams-surface-track tracks every keyframe against its stream's surface first,
+all loops in lockstep, and writes surface_poses_<dataset>.txt as --surface-track does.  An error without --streams or --map.
 --surface-views DIR (with --surface) ray-casts the finished surface from the estimated pose of every keyframe, or with
 --surface-views-every K of every K-th tracked frame, on the GPU (api.SurfaceVolume.raycast, DESIGN 28: depth and colour from the
 sign change of the fused field, sub-voxel accurate and without holes) and writes the TUM-layout data set that --map-views writes
@@ -65,7 +70,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -232,6 +237,26 @@ def main(argv=None):
                 return 2
             follow[key] = got[0] if k == 1 else got
             argv = argv[:i] + argv[i + 1 + k:]
+    ssurface = None  # vo.MultiREVO's surfaces: one SurfaceVolume per dataset, its mesh written at the end of the run
+    ssurface_track = "--streams-surface-track" in argv
+    if ssurface_track:
+        argv = [a for a in argv if a != "--streams-surface-track"]
+        if "--streams-surface" not in argv:
+            print("--streams-surface-track tracks the keyframes against their stream's TSDF surface: it needs --streams-surface FILE.ply")
+            return 2
+    if "--streams-surface" in argv:
+        i = argv.index("--streams-surface")
+        if i + 1 >= len(argv) or argv[i + 1].startswith("--"):
+            print("--streams-surface needs a file name")
+            return 2
+        ssurface = {"file": argv[i + 1]}
+        argv = argv[:i] + argv[i + 2:]
+        if "--streams" not in argv:
+            print("--streams-surface gives every dataset of a multi-stream run its surface: it needs --streams N (the sequential driver has --surface)")
+            return 2
+        if map_voxel is None:
+            print("--streams-surface fuses the keyframes over each dataset's voxel map: it needs --map VOXEL")
+            return 2
     surface = None  # vo.REVO's surface: the coloured, shaded mesh of the keyframes' TSDF volume, written at the end of the run
     for opt, key, k, conv in (("--surface", "file", 1, str), ("--surface-box", "box", 6, int), ("--surface-trunc", "trunc", 1, float),
                               ("--surface-min-weight", "min_weight", 1, int)):
@@ -247,6 +272,12 @@ def main(argv=None):
                 return 2
             surface = dict(surface or {}, **{key: got[0] if k == 1 else got})
             argv = argv[:i] + argv[i + 1 + k:]
+    if ssurface is not None and surface is not None and "file" not in surface:  # the box, trunc and min-weight of --streams-surface
+        if any(x < 1 for x in surface.get("box", (0, 0, 0, 1, 1, 1))[3:]) or not surface.get("trunc", 1.0) > 0 or surface.get("min_weight", 1) < 0:
+            print("--surface-box needs N0 N1 N2 >= 1, --surface-trunc a distance > 0 in metres, --surface-min-weight a number >= 0")
+            return 2
+        ssurface.update(surface)
+        surface = None
     if surface is not None:
         if "file" not in surface:
             print("--surface-box, --surface-trunc and --surface-min-weight need --surface FILE.ply")
@@ -297,7 +328,7 @@ def main(argv=None):
     trk_settings.optimizerSettings = OptimizerSettings(use_edge_filter=use_edge_filter)
     if streams:
         return _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode, exact_sums, map_voxel,
-                            views_dir, views_every, map_save, covariances, views_raycast, esdf)
+                            views_dir, views_every, map_save, covariances, views_raycast, esdf, ssurface, ssurface_track)
     for ds in io["datasets"]:
         folder = os.path.join(io["main_folder"], ds)
         cam = api.CameraPyr(pyr_settings, device=device, exact_sums=exact_sums)
@@ -507,8 +538,10 @@ def _report_ate(folder, poses):
 
 
 def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders, gpu_decode=False, exact_sums=False,
-                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False, views_raycast=False, esdf=None):
-    """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop."""
+                 map_voxel=None, views_dir=None, views_every=0, map_save=None, covariances=False, views_raycast=False, esdf=None,
+                 ssurface=None, ssurface_track=False):
+    """The Datasets list `streams` at a time through one vo.MultiREVO: same poses_<dataset>.txt files as the sequential loop.
+    ssurface (--streams-surface): every dataset gets a surface on its map, the sequential --surface's box, trunc and files."""
     from . import tum, vo
     names = [os.path.basename(os.path.normpath(ds)) or "dataset" for ds in io["datasets"]]
     folders = [os.path.join(io["main_folder"], ds) for ds in io["datasets"]]
@@ -537,9 +570,13 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
                                 skip_first_n_frames=io["skip_first_n_frames"], read_n_images=io["read_n_images"]):
                 yield f
 
+    surface = None
+    if ssurface is not None:  # the box is decided here and does not move: voxel indices of each dataset's first camera frame
+        box = ssurface.get("box", (-128, -128, -32, 256, 256, 256))
+        surface = dict(lo=box[:3], n=box[3:], trunc=ssurface.get("trunc"), color=True)
     drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"],
                        exact_sums=exact_sums, map_voxel=map_voxel, map_dense=bool(sysd["do_generate_dense_pcl"]),
-                       pair_info=covariances)
+                       pair_info=covariances, surface=surface, surface_track=True if ssurface_track else None)
     t0 = time.perf_counter()
     try:
         res = drv.run([frames(f) for f in folders])
@@ -559,6 +596,10 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
         if r.map is not None:
             _save_map(r.map, name, _rvm_path(map_save, name, True))
             _save_esdf(r.map, esdf, name, True)
+            if r.surface is not None:
+                _save_surface(r.surface, r, ssurface, name, True)
+                if ssurface_track:
+                    _save_surface_tracks(r, name)
             if views_dir is not None:
                 _save_views(r.map, os.path.join(views_dir, name), r.poses, [kf for _, kf in r], views_every,
                             io["depth_scale_factor"], views_raycast)

@@ -466,6 +466,50 @@ class MapTsdfRefillInfo(C.Structure):
 assert (C.sizeof(MapTsdfRecord), C.sizeof(MapTsdfShiftInfo), C.sizeof(MapTsdfRefillInfo)) == (32, 64, 32)
 
 
+class MapTsdfFuseJob(C.Structure):
+    """revo_map_tsdf_fuse_job (include/revo_hip.h), 200 bytes: one (volume, view) of revo_map_tsdf_fuse_many -- the map that gives the
+    voxel edge (NULL: the call's), the box, trunc (0: 4 voxel edges), the device volumes (color may be NULL), the view, a raw view's
+    device colour image and the job's optional device records."""
+    _fields_ = [("map", C.c_void_p), ("box", MapDfBox), ("trunc", C.c_float), ("reserved", C.c_uint32), ("tsdf", C.c_void_p), ("color", C.c_void_p),
+                ("view", MapCarveView), ("bgr", C.c_void_p), ("info", C.c_void_p), ("color_info", C.c_void_p), ("view_info", C.c_void_p)]
+
+
+class MapTsdfTrackJob(C.Structure):
+    """revo_map_tsdf_track_job (include/revo_hip.h), 200 bytes: one (volume, frame) of revo_map_tsdf_track_eval_many and
+    revo_map_tsdf_track_many -- the map that gives the voxel edge, the box, the volume's trunc, the poses of the evaluation, the device
+    volume, the frame, the parameters and the host poses (the evaluation's n_poses 4x4, or the loop's T_init)."""
+    _fields_ = [("map", C.c_void_p), ("box", MapDfBox), ("trunc", C.c_float), ("n_poses", C.c_int32), ("tsdf", C.c_void_p), ("frame", MapCarveView),
+                ("prm", MapTsdfTrackParams), ("poses", C.c_void_p)]
+
+
+class MapTsdfTrackResult(C.Structure):
+    """revo_map_tsdf_track_result (include/revo_hip.h), 288 bytes: what revo_map_tsdf_track gives for one job of revo_map_tsdf_track_many,
+    and the records its loop took."""
+    _fields_ = [("T", C.c_float * 16), ("info", MapTsdfTrackInfo), ("iterations", C.c_int32), ("status", C.c_int32), ("evaluations", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+assert (C.sizeof(MapTsdfFuseJob), C.sizeof(MapTsdfTrackJob), C.sizeof(MapTsdfTrackResult)) == (200, 200, 288)
+
+
+class MultiSurface(C.Structure):
+    """revo_vo_multi_surface (include/revo_hip.h), 120 bytes: the surface of one stream of revo_vo_multi -- the map that gives the voxel
+    edge, the box, trunc (0: 4 voxel edges), whether each keyframe is tracked before it is fused, the caller-owned device volumes
+    (color may be NULL), and the tracking parameters and options."""
+    _fields_ = [("map", C.c_void_p), ("box", MapDfBox), ("trunc", C.c_float), ("track", C.c_int32), ("tsdf", C.c_void_p), ("color", C.c_void_p),
+                ("track_prm", MapTsdfTrackParams), ("track_opts", MapAlignOpts)]
+
+
+class MultiSurfaceReport(C.Structure):
+    """revo_vo_multi_surface_report (include/revo_hip.h), 408 bytes: a stream's last keyframe as its surface saw it."""
+    _fields_ = [("timestamp", C.c_double), ("T_w_kf", C.c_float * 16), ("T_fused", C.c_float * 16), ("track", MapTsdfTrackInfo), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("tracked", C.c_int32), ("fused", C.c_int32), ("view_info", MapCarveViewInfo), ("keyframes_fused", C.c_uint64),
+                ("keyframes_skipped", C.c_uint64)]
+
+
+assert (C.sizeof(MultiSurface), C.sizeof(MultiSurfaceReport)) == (120, 408)
+
+
 class PairIn(C.Structure):
     """revo_pair_in (include/revo_hip.h): one frame-pair in host memory."""
     _fields_ = [

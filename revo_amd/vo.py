@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib, api
 from ._lib import check, f32p, u16p, u8p, vp
-from .settings import PairInfo, StreamFrame, StreamResult, TrackerSettings
+from .settings import MapTsdfTrackInfo, MultiSurface, MultiSurfaceReport, PairInfo, StreamFrame, StreamResult, TrackerSettings
 
 
 class REVO:
@@ -264,13 +264,18 @@ def tum_lines(poses):
 
 class SequenceResult(list):
     """One sequence of MultiREVO.run: [(4x4 pose, new_keyframe)] in frame order, `poses` [(timestamp, 4x4)], tum_lines(),
-    and `map`: its api.VoxelMap (MultiREVO(map_voxel=...)) or None."""
+    `map`: its api.VoxelMap (MultiREVO(map_voxel=...)) or None, and `surface`, `surface_tracks`, `surface_skipped`: its
+    api.SurfaceVolume (MultiREVO(surface=...)) with what REVO.surface_tracks and REVO.surface_skipped hold for the sequence."""
 
     def __init__(self):
         super().__init__()
         self.poses = []
         self.pair_infos = []  # MultiREVO(pair_info=True): (PairInfo, keyframe timestamp) per pose
         self.map = None
+        # MultiREVO(surface=...): the sequence's api.SurfaceVolume, REVO.surface_tracks' tuples (surface_track) and the keyframes not fused
+        self.surface = None
+        self.surface_tracks = []
+        self.surface_skipped = 0
 
     def tum_lines(self):
         return tum_lines(self.poses)
@@ -291,9 +296,11 @@ class MultiREVO:
 
     map_voxel, map_dense, map_max_voxels = None, False, 1 << 24  # run()'s per-sequence maps: off unless __init__ sets them
     pair_info = False  # run() collects each pose's PairInfo: off unless __init__ sets it
+    surface, surface_track = None, None  # run()'s per-sequence surfaces: off unless __init__ sets them
 
     def __init__(self, settingsPyr, n_streams, settingsTracker=None, device=0, cameraPyr=None, depth_scale_factor=None,
-                 max_queue=2, exact_sums=False, map_voxel=None, map_dense=False, map_max_voxels=1 << 24, pair_info=False):
+                 max_queue=2, exact_sums=False, map_voxel=None, map_dense=False, map_max_voxels=1 << 24, pair_info=False, surface=None,
+                 surface_track=None):
         self.settingsPyr = settingsPyr
         self.settingsTracker = settingsTracker or TrackerSettings()
         if cameraPyr is None:
@@ -320,6 +327,15 @@ class MultiREVO:
         self.map_dense = bool(map_dense)
         self.map_max_voxels = int(map_max_voxels)
         self._maps = [None] * self.n_streams
+        # run(): one api.SurfaceVolume per sequence on its map (surface: dict(lo=, n=[, trunc=, color=])), fed by the step's batched
+        # track and fuse of the keyframes its stream promotes; surface_track: None | True | dict, as REVO takes it
+        if surface is not None and map_voxel is None:
+            raise ValueError("surface= needs map_voxel: a sequence's surface lives on its map")
+        if surface_track is not None and surface_track is not False and surface is None:
+            raise ValueError("surface_track needs a surface")
+        self.surface = dict(surface) if surface is not None else None
+        self.surface_track = surface_track
+        self._surfaces = [None] * self.n_streams  # per stream: (SurfaceVolume, the log its reports go to, keyframes seen, tracking)
         # pair_info: one information launch per step for all streams; last_pair_info(stream) belongs to the stream's last reported pose
         self.pair_info = bool(pair_info)
         if self.pair_info:
@@ -335,6 +351,79 @@ class MultiREVO:
         """Every keyframe `stream` promotes from now on is integrated into voxelMap (None detaches); reset() detaches."""
         check(_lib.lib().revo_vo_multi_attach_map(self._h, int(stream), voxelMap._h if voxelMap is not None else None))
         self._maps[int(stream)] = voxelMap
+
+    def attach_surface(self, stream, surface, track=None, log=None):
+        """Every keyframe `stream` promotes from now on is fused into `surface` (an api.SurfaceVolume on a map of this handle's
+        context; None detaches; reset() detaches), in the step's one batched launch, as REVO(surface=) does it for one sequence.
+        track: None | True | dict of SurfaceVolume.track's options (REVO's surface_track) -- the keyframe is tracked against the
+        surface as it stands first, all streams' loops in lockstep, and fused at the refined pose where the loop converged.
+        log: the object whose surface_tracks (REVO.surface_tracks' tuples) and surface_skipped are kept current (default: the
+        surface itself gets both attributes).  The surface's `views` and per-view counts are kept current too."""
+        from . import mapfile
+        s = int(stream)
+        if surface is None:
+            check(_lib.lib().revo_vo_multi_attach_surface(self._h, s, None))
+            self._surfaces[s] = None
+            return
+        if track is False:
+            track = None
+        opts = {} if track is None or track is True else dict(track)
+        rec = MultiSurface()
+        rec.map = surface.map._h
+        rec.box = surface.map._df_box(surface.lo, tuple(int(x) for x in surface.n), 0, 1)
+        rec.trunc = float(surface.trunc)
+        rec.track = 0 if track is None else 1
+        rec.tsdf = surface.d_tsdf.data_ptr()
+        rec.color = surface.d_color.data_ptr() if surface.d_color is not None else None
+        if track is not None:
+            known = ("max_dist", "stride", "min_weight", "centre", "max_iters", "eps_t", "eps_r", "min_matched")
+            if set(opts) - set(known):
+                raise ValueError("surface_track takes %s" % ", ".join(known))
+            centre = opts.get("centre")
+            if centre is None:
+                centre = mapfile.tsdf_track_centre(surface.lo, tuple(int(x) for x in surface.n), surface.map.voxel)
+            p = rec.track_prm
+            p.max_dist = 0.0 if opts.get("max_dist") is None else float(opts["max_dist"])
+            p.stride, p.min_weight = int(opts.get("stride", 1)), int(opts.get("min_weight", 1))
+            p.centre[:] = [float(x) for x in np.asarray(centre, np.float32).reshape(3)]
+            o = rec.track_opts
+            o.max_iters, o.eps_t, o.eps_r = int(opts.get("max_iters", 30)), float(opts.get("eps_t", 1e-6)), float(opts.get("eps_r", 1e-6))
+            o.min_matched = int(opts.get("min_matched", 12))
+        import torch
+        torch.cuda.current_stream(surface.d_tsdf.device).synchronize()  # the volumes' earlier use is over before the tracker stream writes
+        check(_lib.lib().revo_vo_multi_attach_surface(self._h, s, C.byref(rec)))
+        log = surface if log is None else log
+        log.surface_tracks, log.surface_skipped = [], 0
+        self._surfaces[s] = [surface, log, self.nKeyFrames(s), track is not None]
+
+    def surface_last(self, stream):
+        """The MultiSurfaceReport of the stream's last keyframe since its surface was attached; waits for that step's fuse."""
+        rep = MultiSurfaceReport()
+        check(_lib.lib().revo_vo_multi_surface_last(self._h, int(stream), C.byref(rep)))
+        return rep
+
+    def _poll_surfaces(self):
+        """Behind a step: the report of every stream that promoted a keyframe in it goes to the stream's log and surface."""
+        for s, att in enumerate(self._surfaces):
+            if att is None:
+                continue
+            n = self.nKeyFrames(s)
+            if n == att[2]:
+                continue
+            att[2] = n
+            surface, log, _, tracking = att
+            rep = self.surface_last(s)
+            as44 = lambda a: np.array(list(a), np.float32).reshape(4, 4).T.copy()  # noqa: E731
+            if tracking:
+                info = MapTsdfTrackInfo.from_buffer_copy(bytes(rep.track)) if rep.tracked else None
+                log.surface_tracks.append((float(rep.timestamp), as44(rep.T_w_kf), as44(rep.T_fused), info, int(rep.status)))
+            log.surface_skipped = int(rep.keyframes_skipped)
+            if rep.fused:
+                import torch
+                vi = rep.view_info
+                row = [vi.outside, vi.unknown, vi.free_space, vi.confirmed, vi.occluded, vi.edge, 0, 0]
+                surface._vinfo.append(torch.tensor(np.array(row, np.uint32).view(np.int32), dtype=torch.int32, device=surface.d_tsdf.device))
+                surface.views += 1
 
     def __del__(self):
         try:
@@ -399,6 +488,8 @@ class MultiREVO:
     def step(self):
         n = C.c_int()
         check(_lib.lib().revo_vo_multi_step(self._h, self._out, C.byref(n)))
+        if any(a is not None for a in self._surfaces):
+            self._poll_surfaces()
         res = []
         for r in self._out[:n.value]:
             M = np.ctypeslib.as_array(r.pose).reshape(4, 4).T.copy()
@@ -411,6 +502,7 @@ class MultiREVO:
     def reset(self, stream):
         check(_lib.lib().revo_vo_multi_reset(self._h, int(stream)))
         self._maps[int(stream)] = None
+        self._surfaces[int(stream)] = None
 
     def nKeyFrames(self, stream):
         return _lib.lib().revo_vo_multi_num_keyframes(self._h, int(stream))
@@ -448,6 +540,9 @@ class MultiREVO:
                         out[nxt].map = api.VoxelMap(self.camPyr, self.map_voxel, dense=self.map_dense,
                                                     max_voxels=self.map_max_voxels)
                         self.attach_map(s, out[nxt].map)
+                        if self.surface is not None:
+                            out[nxt].surface = api.SurfaceVolume(out[nxt].map, **self.surface)
+                            self.attach_surface(s, out[nxt].surface, self.surface_track, log=out[nxt])
                     nxt += 1
 
         def feed():  # one submit: the next frame of every stream with room in its queue
