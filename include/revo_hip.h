@@ -1832,6 +1832,56 @@ typedef struct revo_map_tsdf_refill_info {  /* 32 bytes, little-endian, no paddi
 int revo_map_tsdf_refill(revo_map* m, const revo_map_df_box* box, revo_map_tsdf_cell* tsdf, revo_map_tsdf_color* color, int device_tsdf,
                          size_t n, const revo_map_tsdf_record* records, int device_in, revo_map_tsdf_refill_info* info);
 
+/* ---- views taken out of the surface again: the exact inverse of the fuse ----------------------------------------
+ * A cell is sum += q, weight += 1 with q an integer that is a pure function of the cell, the view and trunc, and colour is the
+ * same with the centre pixel's bytes; so a view that was fused can be taken out again exactly, as revo_map_subtract_raw takes
+ * out what revo_map_merge_raw put in.
+ * Per cell and view the class, the centre pixel and q are exactly revo_map_tsdf_fuse's (FREE: q = 1024; CONFIRMED: its rounded
+ * quotient; every other class: no update).  An update is sum -= q, weight -= 1; for a CONFIRMED update with a colour volume the
+ * three colour sums lose the centre pixel's bytes and color.weight -= 1.
+ * The call is all or nothing.  Per cell let k be the views of this call that update the cell and kc the CONFIRMED ones among
+ * them, Q the sum of their q and B, G, R the sums of their pixels' bytes.  A cell with k == 0 is not looked at.  A cell with
+ * k > 0 FITS when, decided in 64-bit integers,
+ *   weight < 2^20                      (a full cell may have dropped updates: its history cannot be inverted)
+ *   weight >= k                        (no more views leave than came)
+ *   |sum - Q| <= 1024 * (weight - k)   (an emptied cell has sum 0; the cell stays a state a fuse can reach)
+ * and with a colour volume
+ *   color.weight >= kc,  sum_c >= C for c = B, G, R               (nothing goes below zero)
+ *   color.weight - kc <= weight - k                               (the colour weight never passes the TSDF weight)
+ *   sum_c - C <= 255 * (color.weight - kc) for c = B, G, R        (an emptied colour cell has sums 0).
+ * If any cell does not fit the call returns REVO_ERR_INVALID_ARG and no byte of either volume has changed, in host or device
+ * memory; info->misfits is the number of such cells, updates and color_updates are 0 and the other counters describe the
+ * volumes as they stand.  Otherwise every update is applied.
+ * Exact properties: while nothing saturated, fusing the views A and B in any order and any split into accumulating calls and
+ * then taking out B in any split leaves the bytes of fusing A alone, in both volumes; taking out everything leaves all-zero
+ * volumes; taking out B1 and then B2 equals taking out B1 and B2 in one call when each step fits; a host volume and a device
+ * volume give the same bytes; a pyramid view and the raw view of its level-0 planes give the same bytes; view_info is byte for
+ * byte revo_map_tsdf_fuse's for the same views, refused or not. */
+typedef struct revo_map_tsdf_unfuse_info {  /* 64 bytes, little-endian, no padding */
+  uint64_t cells;           /* n[0]*n[1]*n[2]                                                */
+  uint64_t updates;         /* the updates taken out                                         */
+  uint64_t cells_weighted;  /* cells with weight > 0 after the call                          */
+  uint64_t cells_inside;    /* of those, the cells with sum < 0                              */
+  uint64_t misfits;         /* cells with k > 0 that do not FIT: the call changed nothing    */
+  uint64_t color_updates;   /* the colour updates taken out                                  */
+  uint64_t cells_colored;   /* cells with color.weight > 0 after the call; 0 without color   */
+  uint64_t reserved;        /* zero */
+} revo_map_tsdf_unfuse_info;
+/* n views (1 .. 64) taken out of the volumes of `box`.  The view, box, side and alignment rules are revo_map_tsdf_fuse_color's:
+ * bgr[i] is NULL for a pyramid view and the colour image of a raw view, on the side of the depth images (device_in); tsdf, color
+ * and view_info (n records, may be NULL) live where device_tsdf says, device pointers 16-byte aligned.  color may be NULL: bgr
+ * must then be NULL too and the colour volume is not touched.  trunc: the distance the views were fused with; 0 means 4 x the
+ * map's voxel edge.  info (may be NULL) is a host pointer.  A check pass that writes nothing to the volumes runs first and the
+ * call waits for its verdict; then the apply pass is enqueued, and the call waits again for a host volume or a given info.
+ * Runs on the context's tracker stream, for a pyramid view behind that pyramid's build.
+ * REVO_ERR_INVALID_ARG, before anything is enqueued and with nothing written: NULL m, box, views or tsdf; color without bgr or
+ * bgr without color; the box rules; n outside 1 .. 64; the view rules; a bgr[i] that does not match its view's kind; a trunc that
+ * is not 0 and not finite and > 0; a flag outside 0 / 1; a misaligned device pointer. */
+int revo_map_tsdf_unfuse(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views,
+                         const uint8_t* const* bgr, int device_in, float trunc,
+                         revo_map_tsdf_cell* tsdf, revo_map_tsdf_color* color, int device_tsdf,
+                         revo_map_tsdf_unfuse_info* info, revo_map_carve_view_info* view_info);
+
 /* ---- surfaces for many sequences at once: batched fuse and track -------------------------------------------------
  * revo_map_tsdf_fuse* and revo_map_tsdf_track* are one volume per call.  These calls take a list of jobs, each with its own
  * volume, box, view or frame and voxel edge, and run all of them in one launch (the Gauss-Newton loop: one launch, one copy and

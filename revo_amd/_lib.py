@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -198,6 +198,8 @@ def lib():
                                       C.POINTER(MapTsdfTrackParams), C.POINTER(MapAlignOpts), f32p, C.POINTER(MapTsdfTrackInfo), i32p, i32p]
     L.revo_map_tsdf_shift.argtypes = [vp, C.POINTER(MapDfBox), i32p, vp, vp, vp, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, vp]
     L.revo_map_tsdf_refill.argtypes = [vp, C.POINTER(MapDfBox), vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.POINTER(MapTsdfRefillInfo)]
+    L.revo_map_tsdf_unfuse.argtypes = [vp, C.POINTER(MapDfBox), C.c_int, C.POINTER(MapCarveView), vp, C.c_int, C.c_float, vp, vp, C.c_int,
+                                       C.POINTER(MapTsdfUnfuseInfo), vp]
     L.revo_map_tsdf_fuse_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfFuseJob)]
     L.revo_map_tsdf_track_eval_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfTrackJob), vp, C.c_int]
     L.revo_vo_multi_attach_surface.argtypes = [vp, C.c_int, C.POINTER(MultiSurface)]

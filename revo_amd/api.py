@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1070,6 +1070,73 @@ class VoxelMap:
         if wait:
             self.sync()
         del keep
+
+    # -- views taken out of a surface again (revo_map_tsdf_unfuse)
+    @staticmethod
+    def _check_unfuse(rc, info):
+        """check(rc); a refusal's RevoError carries misfits and info (the dict of mapfile.TSDF_UNFUSE_INFO_KEYS; None when the call
+        was given no info record)."""
+        from . import mapfile
+        as_dict = lambda: None if info is None else {k: int(getattr(info, k)) for k in mapfile.TSDF_UNFUSE_INFO_KEYS}  # noqa: E731
+        try:
+            check(rc)
+        except RevoError as e:
+            e.info = as_dict()
+            e.misfits = None if info is None else e.info["misfits"]
+            raise
+        return as_dict()
+
+    def unfuse(self, volume, views):
+        """Views taken out of a TsdfVolume again -> a new TsdfVolume (revo_map_tsdf_unfuse): the exact inverse of
+        fuse(into=), with the volume's box and trunc.  views: as fuse takes them, with the colour images of fuse(color=True) when
+        the volume has colour.  All or nothing: RevoError (REVO_ERR_INVALID_ARG) carrying .misfits when a cell would not fit -- a
+        view that is not in the volume, a full weight, sums no fuse can reach; the volume is not changed either way.  The
+        result's info is the dict of mapfile.TSDF_UNFUSE_INFO_KEYS."""
+        from . import mapfile
+        color = volume.color is not None
+        if color:
+            cv, device_in, keep, bgr, keep_c = self._color_views(views)
+        else:
+            cv, device_in, keep = self._carve_views(views)
+            bgr, keep_c = None, None
+        box, vol = self._tsdf_box(volume)
+        vol = vol.copy()
+        col = np.ascontiguousarray(volume.color).copy() if color else None
+        info, vinfo = MapTsdfUnfuseInfo(), (MapCarveViewInfo * len(cv))()
+        out = self._check_unfuse(_lib.lib().revo_map_tsdf_unfuse(self._h, C.byref(box), len(cv), cv, C.cast(bgr, vp) if color else None, device_in,
+                                                                 float(volume.trunc), vol.ctypes.data_as(vp), col.ctypes.data_as(vp) if color else None, 0,
+                                                                 C.byref(info), C.cast(vinfo, vp)), info)
+        del keep, keep_c
+        return TsdfVolume(vol, np.array(list(box.lo), np.int32), self.voxel, volume.trunc, out, self._view_counts(vinfo), self, color=col)
+
+    def unfuse_into(self, d_tsdf, views, lo, trunc=None, d_color=None, d_view_info=None, wait=True):
+        """unfuse() between torch device tensors: d_tsdf int32 [n0, n1, n2, 2] and d_color int32 [n0, n1, n2, 4] or None (then the
+        views carry no colour images and no colour volume is touched), as fuse_into takes them; trunc: what the views were fused
+        with (default 4 voxel edges); d_view_info: None or 32 bytes per view.  The call waits for its check pass; all or nothing:
+        RevoError carrying .misfits and .info, with no byte of the volumes changed.  wait=True -> the info dict of
+        mapfile.TSDF_UNFUSE_INFO_KEYS; wait=False -> None, the apply pass only enqueued on the map's stream (sync() orders later
+        reads; the images must stay alive until then)."""
+        from . import mapfile
+        import torch
+        if d_color is not None:
+            cv, device_in, keep, bgr, keep_c = self._color_views(views)
+        else:
+            cv, device_in, keep = self._carve_views(views)
+            bgr, keep_c = None, None
+        self._surface_tensors(d_tsdf, d_color, "d_tsdf")
+        if d_view_info is not None and not (d_view_info.is_cuda and d_view_info.is_contiguous() and
+                                            d_view_info.numel() * d_view_info.element_size() == 32 * len(cv)):
+            raise ValueError("d_view_info needs 32 bytes per view on the device")
+        box = self._df_box(lo, tuple(d_tsdf.shape[:3]), 0, 1)
+        tr = float(mapfile.tsdf_trunc(self.voxel, None if trunc is None or trunc == 0 else trunc))
+        torch.cuda.current_stream(d_tsdf.device).synchronize()  # the tensors' earlier use is over before the tracker stream touches them
+        info = MapTsdfUnfuseInfo()
+        out = self._check_unfuse(_lib.lib().revo_map_tsdf_unfuse(self._h, C.byref(box), len(cv), cv, C.cast(bgr, vp) if d_color is not None else None,
+                                                                 device_in, tr, vp(d_tsdf.data_ptr()), vp(d_color.data_ptr()) if d_color is not None else None,
+                                                                 1, C.byref(info) if wait else None,
+                                                                 vp(d_view_info.data_ptr()) if d_view_info is not None else None), info if wait else None)
+        del keep, keep_c
+        return out
 
     def mesh(self, tsdf, min_weight=1, normals=False, colors=False):
         """The mesh of a TsdfVolume's zero level set -> mapfile.Mesh: vertices, triangles and the call's counts, in the contract's
@@ -2138,6 +2205,20 @@ class TsdfVolume:
         m._tsdf_box(self)
         return m.surface_track(self.cells, self.lo, self.trunc, frame, T_init, max_dist, stride, min_weight, centre, **opts)
 
+    def unfuse(self, views, map=None):
+        """Views taken out of the volume again -> a new TsdfVolume (VoxelMap.unfuse), on the device of the map the
+        volume was fused with (or `map`); a loaded volume without one goes through mapfile.tsdf_unfuse_records, which gives the
+        same bytes and raises mapfile.TsdfUnfuseRefused where the map raises RevoError.  A volume with colour takes raw views as
+        (depth, T, intrinsics, bgr)."""
+        from . import mapfile
+        m = map if map is not None else self._map
+        if m is not None:
+            return m.unfuse(self, views)
+        views = list(views)
+        bgr = [v[3] for v in views] if self.color is not None else None
+        cells, col, info, counts = mapfile.tsdf_unfuse_records(self.cells, self.color, self.lo, self.voxel, [tuple(v[:3]) for v in views], self.trunc, bgr=bgr)
+        return TsdfVolume(cells, self.lo, self.voxel, self.trunc, info, counts, color=col)
+
     def save(self, path):
         """The .npz `python -m revo_amd.mapfile tsdf` writes: sum, weight, lo, n, voxel, trunc, and with a colour volume
         color_sum and color_weight."""
@@ -2172,21 +2253,31 @@ class SurfaceVolume:
         self.d_color = torch.zeros(shape + (4,), dtype=torch.int32, device=dev) if color else None
         self.views = 0
         self._vinfo = []  # one [8] int32 device tensor per integrated view: revo_map_carve_view_info
+        self._pending = []  # the device images of raw views whose fuse is enqueued and not yet waited for
 
     def integrate(self, view):
         """One view -- (pyramid, T_w_c), or a raw view as VoxelMap.fuse takes it with device images -- fused into the volumes:
-        one accumulating call on the map's stream, which returns at once."""
+        one accumulating call on the map's stream, which returns at once.  The call is only enqueued and torch's allocator does not
+        know the map's stream, so a raw view's device images are kept referenced here until that stream has been waited for
+        (volume(), view_counts(), or after 64 such views a wait of its own): the caller may drop them at once."""
         import torch
         vi = torch.zeros(8, dtype=torch.int32, device=self.d_tsdf.device)
         self.map.fuse_into(self.d_tsdf, [view], self.lo, self.trunc, accumulate=True, d_view_info=vi, wait=False, d_color=self.d_color)
         self._vinfo.append(vi)
         self.views += 1
+        images = [x for x in view if hasattr(x, "data_ptr")]
+        if images:
+            if len(self._pending) >= 64:
+                self.map.sync()
+                self._pending.clear()
+            self._pending.append(images)
 
     def view_counts(self):
         """Per integrated view the cells of the box by class (mapfile.CARVE_CLASSES); waits for the map's stream."""
         import torch
         from . import mapfile
         self.map.sync()
+        self._pending.clear()
         if not self._vinfo:
             return []
         rows = torch.stack(self._vinfo).cpu().numpy().view(np.uint32)
@@ -2196,6 +2287,7 @@ class SurfaceVolume:
         """The volumes as they stand -> TsdfVolume (with .color unless created with color=False); waits for the map's stream."""
         from . import mapfile
         self.map.sync()
+        self._pending.clear()
         cells = np.ascontiguousarray(self.d_tsdf.cpu().numpy()).view(mapfile.TSDF_CELL_DTYPE)[..., 0]
         col = None if self.d_color is None else np.ascontiguousarray(self.d_color.cpu().numpy()).view(mapfile.TSDF_COLOR_DTYPE)[..., 0]
         return TsdfVolume(cells, self.lo, self.map.voxel, self.trunc, map=self.map, color=col)
@@ -2315,6 +2407,145 @@ class SurfaceVolume:
         finally:
             self.map.sync()  # d_rec goes back to torch's allocator only behind the update that reads it
 
+    def remove(self, view, index=None):
+        """One view that was integrated taken out of the volumes again (VoxelMap.unfuse_into): one unfuse call, which
+        waits for its check pass.  view: as integrate takes it, at the pose it was integrated with.  All or nothing: RevoError
+        carrying .misfits, with the volumes unchanged, when the view is not in them (or a weight is full).  `views` and the
+        per-view counts are kept current: index says which integrated view it was (its place in view_counts()); by default the
+        first one whose class counts are this view's (rows with equal counts are interchangeable).  A view that fits the volumes
+        and was not integrated through this object has no such row: RuntimeError behind the unfuse, with `views` and the counts
+        unchanged.  -> the info dict of mapfile.TSDF_UNFUSE_INFO_KEYS."""
+        import torch
+        vi = torch.zeros(8, dtype=torch.int32, device=self.d_tsdf.device)
+        info = self.map.unfuse_into(self.d_tsdf, [view], self.lo, self.trunc, d_color=self.d_color, d_view_info=vi)
+        if index is None:
+            same = (torch.stack(self._vinfo) == vi).all(dim=1).nonzero() if self._vinfo else []
+            index = int(same[0]) if len(same) else None
+        if index is None or not 0 <= index < len(self._vinfo):
+            raise RuntimeError("the view has been taken out of the volumes, but no integrated view of this surface has its class counts "
+                               "(or its index): views and view_counts() are left as they were")
+        del self._vinfo[index]
+        self.views -= 1
+        return info
+
+    def repose(self, view, T_old, T_new, index=None):
+        """A view that was integrated at the pose T_old moved to T_new: one unfuse at T_old, then one fuse at T_new.
+        view: as integrate takes it; its own pose entry is not looked at.  -> the unfuse's info dict; when the unfuse is refused
+        nothing is fused, the volumes are unchanged and the dict is the refusal's (misfits > 0)."""
+        view = tuple(view)
+        at = lambda T: (view[0], np.asarray(T, np.float32).reshape(4, 4)) + view[2:]  # noqa: E731
+        try:
+            info = self.remove(at(T_old), index)
+        except RevoError as e:
+            if getattr(e, "misfits", None):
+                return e.info
+            raise
+        self.integrate(at(T_new))
+        return info
+
+
+class SurfaceWindow(SurfaceVolume):
+    """A surface that holds exactly the last `window` integrated views: the bounded surface of a long run, beside MapWindow's
+    bounded map.  Its volumes are byte for byte those of a fresh SurfaceVolume fused from those views alone.
+    integrate(view) fuses the view and then takes the oldest one out again (SurfaceVolume.remove: one unfuse call, which waits for
+    its check pass).  vo.REVO(voxelMap=MapWindow(...), surface=SurfaceWindow(...)) feeds it every keyframe.
+
+    What it keeps to name a view again: a pyramid it may keep (one the caller owns) is kept as it is, as MapWindow keeps its
+    keyframes; the driver's keyframe pyramid is only borrowed until the next frame, so of it -- and of a raw device view -- device
+    copies of the depth and the colour image are kept: window x (4 + 3) bytes per pixel.  A borrowed pyramid's colour plane cannot
+    be read back, so integrate takes the frame's colour image beside it (bgr=, the image the pyramid was built from; the driver
+    passes it)."""
+
+    def __init__(self, map, lo, n, window=1, trunc=None, color=True):
+        import collections
+        if int(window) < 1:
+            raise ValueError("window must be >= 1 view")
+        self._held = collections.deque()  # the views as they can be named again, oldest first
+        super().__init__(map, lo, n, trunc, color)
+        self.window = int(window)
+
+    def _keepable(self, view, bgr):
+        """The view in a form that stays valid while the window holds it."""
+        import torch
+        src = view[0]
+        dev = self.d_tsdf.device
+        if isinstance(src, ImgPyramidRGBD):
+            if src._owned:
+                return (src, np.array(view[1], np.float32).reshape(4, 4)) + tuple(view[2:])
+            if self.d_color is not None and bgr is None:
+                raise ValueError("a borrowed pyramid's colour plane cannot be read back: pass the frame's colour image as bgr=")
+            depth = torch.from_numpy(src.returnDepth(0)).to(dev)
+            T = np.array(view[1], np.float32).reshape(4, 4)
+            if self.d_color is None:
+                return (depth, T, None)
+            im = np.ascontiguousarray(bgr, np.uint8)
+            if im.shape != tuple(depth.shape) + (3,):
+                raise ValueError("bgr is the [h, w, 3] uint8 image the pyramid was built from")
+            return (depth, T, None, torch.from_numpy(im).to(dev))
+        if not hasattr(src, "data_ptr"):
+            raise ValueError("a raw view of a surface has device images")
+        held = (src.clone(), np.array(view[1], np.float32).reshape(4, 4), view[2] if len(view) > 2 else None)
+        return held + (view[3].clone(),) if self.d_color is not None and len(view) > 3 and view[3] is not None else held
+
+    def held_views(self):
+        """The views the window holds (`views` is their number, as SurfaceVolume's), oldest first, as they can be named again:
+        (pyramid or device depth, T_w_c, intrinsics or None[, device bgr])."""
+        return list(self._held)
+
+    def _place(self, view):
+        i = int(view) if isinstance(view, (int, np.integer)) else next((j for j, h in enumerate(self._held) if h is view), None)
+        if i is None or not 0 <= i < len(self._held):
+            raise ValueError("the window names a view it holds by the entry of held_views() or by its place in it")
+        return i
+
+    def integrate(self, view, bgr=None):
+        """The view fused, and once more than `window` views are held the oldest one taken out again.  bgr: the colour image of a
+        borrowed pyramid (see the class).  When that unfuse is refused (a cell of the oldest view has reached the full weight
+        2^20, so its history cannot be inverted) the RevoError goes to the caller with the new view fused and held: the window then
+        holds window + 1 views, every one of them in the volumes and in held_views(), and the next integrate tries the eviction again."""
+        held = self._keepable(view, bgr)
+        super().integrate(held)
+        self._held.append(held)
+        while len(self._held) > self.window:
+            self.remove(0)
+
+    def remove(self, view, index=None):
+        """A view the window holds (an entry of held_views(), or its place in it) taken out of the volumes and of the window."""
+        i = self._place(view)
+        info = super().remove(self._held[i], i)
+        del self._held[i]
+        return info
+
+    def repose(self, view, T_old, T_new, index=None):
+        """SurfaceVolume.repose of a view the window holds (an entry of held_views(), or its place in it): it keeps its place in the
+        window, at the new pose."""
+        i = self._place(view)
+        old = self._held[i]
+        new = (old[0], np.asarray(T_new, np.float32).reshape(4, 4)) + tuple(old[2:])
+        try:
+            info = SurfaceVolume.remove(self, (old[0], np.asarray(T_old, np.float32).reshape(4, 4)) + tuple(old[2:]), i)
+        except RevoError as e:
+            if getattr(e, "misfits", None):
+                return e.info
+            raise
+        SurfaceVolume.integrate(self, new)
+        self._vinfo.insert(i, self._vinfo.pop())  # the per-view counts keep the window's order
+        self._held[i] = new
+        return info
+
+    def clear(self):
+        """An empty window over zero volumes."""
+        self.map.sync()
+        self.d_tsdf.zero_()
+        if self.d_color is not None:
+            self.d_color.zero_()
+        import torch
+        torch.cuda.current_stream(self.d_tsdf.device).synchronize()
+        self._held.clear()
+        self._vinfo.clear()
+        self._pending.clear()
+        self.views = 0
+
 
 class FollowingSurface(SurfaceVolume):
     """A SurfaceVolume whose box follows the camera: n cells per axis, placed by mapfile.follow_lo -- centred `ahead`
@@ -2379,6 +2610,13 @@ class FollowingSurface(SurfaceVolume):
         """follow(the view's pose), then SurfaceVolume.integrate."""
         self.follow(view[1])
         super().integrate(view)
+
+    def remove(self, view, index=None):
+        """Not supported: cells the view updated may have left the box for the store, where no view can be taken out of them."""
+        raise NotImplementedError("a FollowingSurface cannot unfuse: cells of the view may lie in its store")
+
+    def repose(self, view, T_old, T_new, index=None):
+        raise NotImplementedError("a FollowingSurface cannot unfuse: cells of the view may lie in its store")
 
     def assemble(self, lo=None, n=None):
         """The store plus the box as it stands -> TsdfVolume over the box (lo, n), by default the bounds of both; ValueError with a
@@ -2787,6 +3025,13 @@ class MapWindow:
 
     def fuse_into(self, *args, **kw):
         return self.map.fuse_into(*args, **kw)
+
+    def unfuse(self, *args, **kw):
+        """The inner map's unfuse: views taken out of a TsdfVolume again (the window's voxels play no part)."""
+        return self.map.unfuse(*args, **kw)
+
+    def unfuse_into(self, *args, **kw):
+        return self.map.unfuse_into(*args, **kw)
 
     def mesh(self, *args, **kw):
         return self.map.mesh(*args, **kw)

@@ -1,5 +1,5 @@
 // revo_map_impl.h -- what the voxel map's translation units (revo_map.hip, revo_map_view.hip, revo_map_align.hip,
-// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip, revo_map_tsdf_follow.hip, revo_map_tsdf_many.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
+// revo_map_edit.hip, revo_map_field.hip, revo_map_df_align.hip, revo_map_plan.hip, revo_map_seen.hip, revo_map_gain.hip, revo_map_tsdf.hip, revo_map_tsdf_ray.hip, revo_map_tsdf_track.hip, revo_map_tsdf_follow.hip, revo_map_tsdf_many.hip, revo_map_tsdf_unfuse.hip) share: the table's device vocabulary (key, record, mean, compaction -- each contract written once), the
 // map handle with the host pieces every entry point uses, and the host functions that cross units.  Internal: only the map's
 // units include it.  The owners of device resources it is written with (DevBuf, DevScratch, HostRows, EventTimer, TRY) are the
 // library's, of revo_internal.h.

@@ -2,6 +2,7 @@
 // share, each rule written once: the parameters a call runs with, a view's update of a cell, what a cell says (valid, inside),
 // the Kuhn tetrahedra of a cube, the cubes an edge belongs to, a tetrahedron's triangles and a vertex's place on its edge.
 // DESIGN 27 added the colour update that goes with a TSDF update, the colour image a view needs, and a vertex's normal and colour.
+// DESIGN 32 added the down-date of a cell and its FIT test (revo_map_tsdf_unfuse.hip, tests/cpp/tsdf_unfuse_host.cpp).
 // Plain C++: revo_map_tsdf.hip compiles it for both sides, tests/cpp/tsdf_host.cpp and surface_host.cpp for the host alone.  Internal.
 #pragma once
 #include <cmath>
@@ -66,6 +67,58 @@ TSDF_HD unsigned tsdf_color_update(uint32_t& sb, uint32_t& sg, uint32_t& sr, uin
   sr += px[2];
   cw += 1u;
   return 1u;
+}
+
+// ---- views taken out again (revo_map_tsdf_unfuse): the down-date of a cell and the FIT test, one text for the
+// kernel, the host restatement and tests/cpp/tsdf_unfuse_host.cpp ----
+// The truncation distance an unfuse runs with (0: 4 x the voxel edge), or why it is refused.
+inline const char* tsdf_unfuse_trunc(float trunc, float voxel, float* out) {
+  *out = trunc == 0.0f ? 4.0f * voxel : trunc;
+  if (!std::isfinite(*out) || !(*out > 0.0f)) return "trunc must be 0 (4 x the voxel edge) or finite and > 0";
+  return nullptr;
+}
+// What the views of one call take from one cell: k updates, kc of them CONFIRMED, their quanta and their pixels' bytes.  At most
+// 64 views: |q| <= 2^16 and every colour total is below 2^14.
+struct TsdfDown {
+  uint32_t k, kc;
+  int32_t q;
+  uint32_t b, g, r;
+};
+// One view's update of the cell joins the totals.  px: the centre pixel's three bytes B, G, R of a CONFIRMED update when there
+// is a colour volume, else NULL.
+TSDF_HD void tsdf_down_add(TsdfDown& d, bool confirmed, int32_t q, const uint8_t* px) {
+  d.k += 1u;
+  d.q += q;
+  if (!confirmed) return;
+  d.kc += 1u;
+  if (px) { d.b += px[0]; d.g += px[1]; d.r += px[2]; }
+}
+// Whether a TSDF cell with d.k > 0 FITS: its weight is not full, no more views leave than came, and what is left is a state a
+// fuse can reach (an emptied cell has sum 0).  64-bit integers throughout.
+TSDF_HD bool tsdf_down_fits(int32_t sum, uint32_t weight, const TsdfDown& d) {
+  if (weight >= TSDF_W_MAX) return false;
+  const int64_t w = (int64_t)weight - (int64_t)d.k, s = (int64_t)sum - (int64_t)d.q;
+  if (w < 0) return false;
+  return (s < 0 ? -s : s) <= (int64_t)TSDF_Q_ONE * w;
+}
+// Whether the cell's colour cell FITS beside it: nothing goes below zero, the colour weight stays within the TSDF weight and
+// every sum within 255 x the colour weight.
+TSDF_HD bool tsdf_down_color_fits(uint32_t weight, uint32_t sb, uint32_t sg, uint32_t sr, uint32_t cw, const TsdfDown& d) {
+  const int64_t w = (int64_t)weight - (int64_t)d.k, c = (int64_t)cw - (int64_t)d.kc;
+  const int64_t b = (int64_t)sb - (int64_t)d.b, g = (int64_t)sg - (int64_t)d.g, r = (int64_t)sr - (int64_t)d.r;
+  if (c < 0 || b < 0 || g < 0 || r < 0) return false;
+  return c <= w && b <= 255 * c && g <= 255 * c && r <= 255 * c;
+}
+// The down-date of a cell that FITS.
+TSDF_HD void tsdf_down_apply(int32_t& sum, uint32_t& weight, const TsdfDown& d) {
+  sum -= d.q;
+  weight -= d.k;
+}
+TSDF_HD void tsdf_down_color_apply(uint32_t& sb, uint32_t& sg, uint32_t& sr, uint32_t& cw, const TsdfDown& d) {
+  sb -= d.b;
+  sg -= d.g;
+  sr -= d.r;
+  cw -= d.kc;
 }
 
 // What a cell says.  min_weight 0 counts as 1.

@@ -52,6 +52,11 @@ Equal maps give equal files.
                                                         the views of DIR fused into a truncated signed distance volume over A's
                                                         bounds grown by N cells (revo_map_tsdf_fuse, DESIGN 26), without a GPU;
                                                         TSDF.npz holds sum, weight, lo, n, voxel, trunc
+    python -m revo_amd.mapfile tsdf-unfuse TSDF.npz --views DIR [--only I,J,...] -o OUT.npz
+                                                        [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S]
+                                                        views of DIR (all, or those with the indices I, J, ...) taken out of
+                                                        the volume again (revo_map_tsdf_unfuse), without a GPU: all or
+                                                        nothing; a volume with colour takes DIR's rgb/ images too
     python -m revo_amd.mapfile mesh TSDF.npz [--min-weight K] [--normals] [--colors] -o MESH.ply
                                                         the mesh of the volume's zero level set (revo_map_tsdf_mesh), binary PLY
     python -m revo_amd.mapfile df-align DST SRC [--init POSE.txt] [--max-dist M] [--pad N] -o POSE.txt
@@ -1171,6 +1176,108 @@ def tsdf_records(voxel, lo, n, views, trunc=None, tsdf=None, chunk=1 << 20, bgr=
         cout["weight"] = cw.reshape(shape)
         return out, info, counts, cout, {"color_updates": color_updates, "cells_colored": int((cw > 0).sum())}
     return out, info, counts
+
+
+TSDF_UNFUSE_INFO_KEYS = ("cells", "updates", "cells_weighted", "cells_inside", "misfits", "color_updates", "cells_colored")
+
+
+class TsdfUnfuseRefused(ValueError):
+    """An unfuse that was refused (the library's REVO_ERR_INVALID_ARG for cells that do not FIT): nothing was changed.  misfits:
+    how many cells; info: the dict of TSDF_UNFUSE_INFO_KEYS, the volumes as they stand."""
+
+    def __init__(self, misfits, info=None):
+        super().__init__("%d cells do not fit: a view that is not in them, a full weight, or sums no fuse can reach" % misfits)
+        self.misfits = int(misfits)
+        self.info = info
+
+
+def tsdf_unfuse_records(cells, color, lo, voxel, views, trunc=None, bgr=None, chunk=1 << 20):
+    """Views taken out of a TSDF volume again without a GPU: revo_map_tsdf_unfuse's contract per cell, from
+    tsdf_records' pieces (carve_classes at radius 0 with margin = trunc, the same quantum).  cells: the volume of the box at lo;
+    color: its colour volume or None (bgr: one image per view, given exactly with a colour volume); trunc: what the views were
+    fused with (None or 0: 4 x the voxel edge).  All or nothing: -> (cells', color', info dict of TSDF_UNFUSE_INFO_KEYS, one dict of
+    CARVE_CLASSES counts per view), the inputs unchanged; TsdfUnfuseRefused, carrying `misfits`, when a cell does not FIT;
+    ValueError as the library's other REVO_ERR_INVALID_ARG."""
+    cells = _tsdf_volume(cells)
+    lo, n = check_box(lo, cells.shape)
+    trunc = tsdf_trunc(voxel, None if trunc is None or trunc == 0 else trunc)
+    views, _, _, _ = carve_rule_args(voxel, views, 0, trunc, 0.0)
+    if (color is None) != (bgr is None):
+        raise ValueError("a colour volume is unfused with colour images, and only with them")
+    if color is not None:
+        color = _tsdf_color_volume(color, cells.shape)
+        images = tsdf_bgr_images(views, bgr)
+        cs = np.stack([color[k].reshape(-1).astype(np.int64) for k in ("sum_b", "sum_g", "sum_r")], 1)
+        cw = color["weight"].reshape(-1).astype(np.int64)
+    p = seen_centres(lo, n, voxel)
+    s = cells["sum"].reshape(-1).astype(np.int64)
+    w = cells["weight"].reshape(-1).astype(np.int64)
+    k, kc, Q = np.zeros(len(p), np.int64), np.zeros(len(p), np.int64), np.zeros(len(p), np.int64)
+    C3 = np.zeros((len(p), 3), np.int64)
+    counts = [dict.fromkeys(CARVE_CLASSES, 0) for _ in views]
+    for a in range(0, len(p), int(chunk)):
+        sl = slice(a, a + int(chunk))
+        for vi, (vw, cnt) in enumerate(zip(views, counts)):
+            cls, z, dc, pix = carve_classes(p[sl], vw, 0, trunc, np.float32(0), depths=True, pixels=True)
+            with np.errstate(all="ignore"):
+                q = np.rint(((dc - z) / trunc) * np.float32(1024))
+            Q[sl] += np.where(cls == 2, 1024, np.where(cls == 3, q, 0)).astype(np.int64)
+            k[sl] += (cls == 2) | (cls == 3)
+            kc[sl] += cls == 3
+            if color is not None:
+                took = np.nonzero(cls == 3)[0]
+                C3[sl][took] += images[vi][pix[took]]
+            for i, name in enumerate(CARVE_CLASSES):
+                cnt[name] += int((cls == i).sum())
+    w1, s1 = w - k, s - Q
+    fits = (w < TSDF_W_MAX) & (w1 >= 0) & (np.abs(s1) <= 1024 * w1)
+    if color is not None:
+        c1, cs1 = cw - kc, cs - C3
+        fits &= (c1 >= 0) & np.all(cs1 >= 0, axis=1) & (c1 <= w1) & np.all(cs1 <= 255 * c1[:, None], axis=1)
+    hit = k > 0
+    misfits = int((hit & ~fits).sum())
+    if misfits:
+        info = {"cells": int(cells.size), "updates": 0, "cells_weighted": int((w > 0).sum()), "cells_inside": int(((w > 0) & (s < 0)).sum()),
+                "misfits": misfits, "color_updates": 0, "cells_colored": 0 if color is None else int((cw > 0).sum())}
+        raise TsdfUnfuseRefused(misfits, info)
+    w1, s1 = np.where(hit, w1, w), np.where(hit, s1, s)
+    out = np.zeros(cells.shape, TSDF_CELL_DTYPE)
+    out["sum"], out["weight"] = s1.reshape(cells.shape), w1.reshape(cells.shape)
+    info = {"cells": int(cells.size), "updates": int(k.sum()), "cells_weighted": int((w1 > 0).sum()), "cells_inside": int(((w1 > 0) & (s1 < 0)).sum()),
+            "misfits": 0, "color_updates": 0, "cells_colored": 0}
+    cout = None
+    if color is not None:
+        c1, cs1 = np.where(hit, c1, cw), np.where(hit[:, None], cs1, cs)
+        cout = np.zeros(cells.shape, TSDF_COLOR_DTYPE)
+        for i, name in enumerate(("sum_b", "sum_g", "sum_r")):
+            cout[name] = cs1[:, i].reshape(cells.shape)
+        cout["weight"] = c1.reshape(cells.shape)
+        info["color_updates"], info["cells_colored"] = int(kc.sum()), int((c1 > 0).sum())
+    return out, cout, info, counts
+
+
+def tsdf_unfuse_file(path, views_dir, camera, zrange, depth_scale=5000.0, only=None):
+    """(cells, lo, voxel, trunc, info, colour cells or None) of a saved volume with views of a `run_tum --map-views` /
+    `--surface-views` folder taken out again (only: the indices of the views to take, default all; more than 64 go in parts of
+    64, each part all or nothing).  A volume with colour takes the folder's rgb/ images too."""
+    cells, lo, voxel, trunc, col = read_tsdf(path, color=True)
+    views = read_views(views_dir, camera, zrange, depth_scale, color=col is not None)
+    if only is not None:
+        bad = [i for i in only if not 0 <= int(i) < len(views)]
+        if bad:
+            raise ValueError("the folder holds %d views: there is no view %s" % (len(views), ", ".join(str(i) for i in bad)))
+        views = [views[int(i)] for i in only]
+    if not views:
+        raise ValueError("no view to take out")
+    info = None
+    for i in range(0, len(views), 64):
+        part = views[i:i + 64]
+        cells, col, pinfo, _ = tsdf_unfuse_records(cells, col, lo, voxel, [v[:3] for v in part], trunc,
+                                                   bgr=[v[3] for v in part] if col is not None else None)
+        if info is not None:
+            pinfo = dict(pinfo, **{k: info[k] + pinfo[k] for k in ("updates", "color_updates")})
+        info = pinfo
+    return cells, lo, voxel, trunc, info, col
 
 
 def tsdf_sdf(cells, trunc):
@@ -2825,6 +2932,32 @@ def main(argv=None):
                       % (val["-o"][0], len(res), val["--views"][0], pos[0], sum(r[5] == ALIGN_CONVERGED for r in res),
                          sum(r[5] == ALIGN_LOST for r in res), sum(int(r[3]["matched"]) for r in res)))
                 return 0
+        if cmd == "tsdf-unfuse" and "-o" in args and "--views" in args:
+            opt = {"-o": 1, "--views": 1, "--only": 1, "--camera": 4, "--zrange": 2, "--depth-scale": 1}
+            val, pos, i = {}, [], 0
+            while i < len(args):
+                k = opt.get(args[i])
+                if k and len(args[i + 1:i + 1 + k]) == k:
+                    val[args[i]] = args[i + 1:i + 1 + k]
+                    i += 1 + k
+                else:
+                    pos.append(args[i])
+                    i += 1
+            if len(pos) == 1:
+                only = [int(x) for x in val["--only"][0].split(",")] if "--only" in val else None
+                camera = [float(x) for x in val.get("--camera", (525.0, 525.0, 319.5, 239.5))]  # the TUM default camera
+                zrange = [float(x) for x in val.get("--zrange", (0.1, 5.2))]
+                try:
+                    cells, lo, voxel, trunc, info, col = tsdf_unfuse_file(pos[0], val["--views"][0], camera, zrange,
+                                                                          float(val.get("--depth-scale", [5000.0])[0]), only)
+                except TsdfUnfuseRefused as e:
+                    print("%s: refused, nothing written: %s" % (pos[0], e))
+                    return 1
+                write_tsdf(val["-o"][0], cells, lo, voxel, trunc, col)
+                print("%s: %d updates%s of %s taken out of %s: %d cells weighted, %d inside"
+                      % (val["-o"][0], info["updates"], " and %d colour updates" % info["color_updates"] if col is not None else "",
+                         val["--views"][0], pos[0], info["cells_weighted"], info["cells_inside"]))
+                return 0
         if cmd == "surface-assemble" and "-o" in args:
             opt = {"-o": 1, "--box": 6}
             val, pos, i = {}, [], 0
@@ -2868,6 +3001,7 @@ def main(argv=None):
           "[--min-views K] [--min-count N] [--miss-depth D] [--max-steps N] -o GAIN.txt | "
           "next-view A --seen SEEN.npz --start X Y Z --clearance M --camera FX FY CX CY --size W H [--headings N] [--stride N] [--max-candidates N] "
           "[--weight W] [--up X Y Z] [the options of gain] -o POSE.txt | "
+          "tsdf-unfuse TSDF.npz --views DIR [--only I,J,...] -o OUT.npz [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
           "tsdf A --views DIR -o TSDF.npz [--color] [--trunc M] [--pad N] [--camera FX FY CX CY] [--zrange ZMIN ZMAX] [--depth-scale S] | "
           "mesh TSDF.npz -o MESH.ply [--min-weight K] [--normals] [--colors] | "
           "surface-views TSDF.npz --poses POSES.txt --camera FX FY CX CY --size W H [--zrange ZMIN ZMAX] [--step M] [--min-weight K] [--max-steps N] "

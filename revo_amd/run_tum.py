@@ -34,7 +34,11 @@ while the sequence runs (vo.REVO's surface, api.SurfaceVolume) and wr
 at the end.  --surface-box I0 J0 K0 N0 N1 N2 is the box in voxel indices of the world frame (the first camera's frame), decided
 before the run (default -128 -128 -32 256 256 256); surfaces outside it are not there, and the keyframes that confirm no cell of
 it are counted on stderr.  --surface-trunc M: the truncation distance in metres (default 4 voxel edges); --surface-min-weight K:
-the views a cell needs.  An error with --map-window and with --streams.  The pose file does not depend on it.
+the views a cell needs.  An error with --map-window (unless --surface-window bounds the surface too) and with --streams.  The pose
+file does not depend on it.
+--surface-window N (with --surface) keeps only the last N keyframes in the surface (api.SurfaceWindow): each older keyframe
+is taken out of the volumes again, exactly, when it leaves the window, so the mesh written at the end is that of the last N keyframes.
+With it --surface is allowed together with --map-window.  An error with --surface-follow and with --streams.
 --surface-track (with --surface) tracks every keyframe against the surface as it stands before it is fused (vo.REVO's surface_track,
 api.SurfaceVolume.track): a keyframe whose tracking converges is fused at the refined pose; surface_poses_<dataset>.txt
 gets the poses the keyframes were fused at.  The trajectory in poses_<dataset>.txt is the tracker's, unchanged.
@@ -70,7 +74,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-window N] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -237,6 +241,28 @@ def main(argv=None):
                 return 2
             follow[key] = got[0] if k == 1 else got
             argv = argv[:i] + argv[i + 1 + k:]
+    surface_window = 0  # api.SurfaceWindow: the surface holds the last N keyframes only
+    if "--surface-window" in argv:
+        i = argv.index("--surface-window")
+        try:
+            surface_window = int(argv[i + 1])
+        except (IndexError, ValueError):
+            surface_window = 0
+        argv = argv[:i] + argv[i + 2:]
+        if surface_window < 1:
+            print("--surface-window needs a positive number of keyframes")
+            return 2
+        if "--surface" not in argv:
+            print("--surface-window bounds the TSDF surface: it needs --surface FILE.ply")
+            return 2
+        if follow is not None:
+            print("--surface-window is not supported together with --surface-follow: a following surface's cells may lie in its store, "
+                  "where no view can be taken out of them")
+            return 2
+        if "--streams" in argv:
+            print("--surface-window is not supported together with --streams: the windowed surface runs on the sequential driver only "
+                  "(drop --streams)")
+            return 2
     ssurface = None  # vo.MultiREVO's surfaces: one SurfaceVolume per dataset, its mesh written at the end of the run
     ssurface_track = "--streams-surface-track" in argv
     if ssurface_track:
@@ -285,7 +311,7 @@ def main(argv=None):
         if map_voxel is None:
             print("--surface fuses the keyframes over the voxel map's frame: it needs --map VOXEL")
             return 2
-        if map_window:
+        if map_window and not surface_window:
             print("--surface is not supported together with --map-window: the volumes keep what the window evicts")
             return 2
         if "--streams" in argv:
@@ -342,7 +368,10 @@ def main(argv=None):
                 surf = api.FollowingSurface(vmap, follow.get("size", (256, 256, 256)), surface.get("trunc"), color=True, step=follow.get("step", 16))
             else:  # the box is decided here and does not move: voxel indices of the first camera's frame
                 box = surface.get("box", (-128, -128, -32, 256, 256, 256))
-                surf = api.SurfaceVolume(vmap, box[:3], box[3:], surface.get("trunc"), color=True)
+                if surface_window:
+                    surf = api.SurfaceWindow(vmap, box[:3], box[3:], window=surface_window, trunc=surface.get("trunc"), color=True)
+                else:
+                    surf = api.SurfaceVolume(vmap, box[:3], box[3:], surface.get("trunc"), color=True)
         drv = vo.REVO(pyr_settings, trk_settings, cameraPyr=cam, depth_scale_factor=io["depth_scale_factor"],
                       mapDrawer=drawer, generate_dense_pcl=sysd["do_generate_dense_pcl"], voxelMap=vmap, pair_info=covariances, carve=map_carve,
                       surface=surf, surface_track=surface_track or None)

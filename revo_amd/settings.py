@@ -466,6 +466,15 @@ class MapTsdfRefillInfo(C.Structure):
 assert (C.sizeof(MapTsdfRecord), C.sizeof(MapTsdfShiftInfo), C.sizeof(MapTsdfRefillInfo)) == (32, 64, 32)
 
 
+class MapTsdfUnfuseInfo(C.Structure):
+    """revo_map_tsdf_unfuse_info (include/revo_hip.h), 64 bytes: what an unfuse took out and what is left; misfits > 0: it was
+    refused and changed nothing."""
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "updates", "cells_weighted", "cells_inside", "misfits", "color_updates", "cells_colored", "reserved")]
+
+
+assert C.sizeof(MapTsdfUnfuseInfo) == 64
+
+
 class MapTsdfFuseJob(C.Structure):
     """revo_map_tsdf_fuse_job (include/revo_hip.h), 200 bytes: one (volume, view) of revo_map_tsdf_fuse_many -- the map that gives the
     voxel edge (NULL: the call's), the box, trunc (0: 4 voxel edges), the device volumes (color may be NULL), the view, a raw view's

@@ -12,6 +12,7 @@ independent sequences at once (one tracker grid per step for all of them), api.B
 throughput mode.
 """
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -60,7 +61,7 @@ class REVO:
         if surface is not None:
             if voxelMap is None:
                 raise ValueError("surface needs a voxelMap")
-            if isinstance(voxelMap, api.MapWindow):
+            if isinstance(voxelMap, api.MapWindow) and not isinstance(surface, api.SurfaceWindow):
                 raise ValueError("surface is not supported with a MapWindow: the volumes keep what the window evicts")
             if surface.map is not voxelMap:
                 raise ValueError("the surface belongs to another map than voxelMap")
@@ -72,6 +73,12 @@ class REVO:
         # rule is not tracked (info None, LOST).  The reported trajectory, the voxel map's integration and the carve keep T_w_kf.  Off
         # by default: nothing new is enqueued.  With an api.FollowingSurface the box follows the keyframe's pose before it is
         # tracked (and, as always, before it is fused); any other surface is not asked to move.
+        # an api.SurfaceWindow names a keyframe again when it leaves the window, and the driver's keyframe pyramid is only
+        # borrowed: the window keeps device copies of its images, and the colour image is the submitted frame's, kept here by time
+        # stamp from submit until the frame after it has been tracked.  Nothing is kept for any other surface.
+        # run(io_thread=True) submits on a producer thread while track_next reads and prunes here: both sides hold _window_lock.
+        self._window_bgr = {} if isinstance(surface, api.SurfaceWindow) and surface.d_color is not None else None
+        self._window_lock = threading.Lock()
         self.surface_track = None if surface_track is None or surface_track is False else ({} if surface_track is True else dict(surface_track))
         self.surface_tracks = []
         if self.surface_track is not None and surface is None:
@@ -104,6 +111,10 @@ class REVO:
     def submit(self, bgr, depth, timestamp):
         """IOWrapperRGBD::generateImgPyramidFromFiles: build the pyramid, push it to the queue."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
+        if self._window_bgr is not None:
+            held = bgr.copy()
+            with self._window_lock:
+                self._window_bgr[float(timestamp)] = held
         if self.depth_scale_factor is not None and np.asarray(depth).dtype == np.uint16:
             # iowrapperRGBD.cpp:326-327 (depth.convertTo(CV_32FC1, 1/scale)) runs inside the device build
             raw = np.ascontiguousarray(depth, np.uint16)
@@ -139,6 +150,10 @@ class REVO:
                 self.voxelMap.integrate(kfPyr, T_w_kf)
                 if self.surface is not None:
                     self._surface_with(kfPyr, T_w_kf if self.surface_track is None else self._surface_track_with(kfPyr, T_w_kf))
+        if self._window_bgr is not None and len(self.poses) > 1:  # a keyframe is the frame just tracked or the one before it
+            with self._window_lock:
+                for t in [t for t in self._window_bgr if t < self.poses[-2][0]]:
+                    del self._window_bgr[t]
         return M, bool(kf.value)
 
     def _surface_track_with(self, kfPyr, T_w_kf):
@@ -160,7 +175,12 @@ class REVO:
     def _surface_with(self, kfPyr, T_w_kf):
         from . import mapfile
         if mapfile.pose_is_orthogonal(np.asarray(T_w_kf, np.float32)[:3, :3]):
-            self.surface.integrate((kfPyr, T_w_kf))
+            if self._window_bgr is not None:
+                with self._window_lock:
+                    bgr = self._window_bgr[float(kfPyr.returnTimestamp())]
+                self.surface.integrate((kfPyr, T_w_kf), bgr=bgr)
+            else:
+                self.surface.integrate((kfPyr, T_w_kf))
             return
         self.surface_skipped += 1
         if self.surface_skipped == 1:
@@ -214,7 +234,6 @@ class REVO:
                 out.append(self.track_next())
             out.append(self.track_next())
             return out
-        import threading
         L = _lib.lib()
         check(L.revo_vo_set_max_queue(self._h, int(max_queue)))  # bounded queue inside the library, stream open
         state = {"err": None}
