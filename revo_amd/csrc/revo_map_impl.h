@@ -440,6 +440,21 @@ int map_subtract_core(revo_map* m, MapMergeK a, int src_kind, u64 dropped, u64 k
 const char* map_df_box_check(const revo_map_df_box* box, size_t* cells);
 int map_df_solid_bits(revo_map* m, const revo_map_df_box* box, uint32_t min_count, hipStream_t s, const unsigned** bits, unsigned* wz, u64* info = nullptr);
 
+// revo_map_tsdf.hip, for revo_map_tsdf_unfuse.hip: the views of a TSDF call (revo_map_tsdf_fuse[_color], revo_map_tsdf_unfuse) on
+// the device, behind the call's own argument checks.  bgr: the views' colour images, NULL for a call without colour; who: the
+// entry point's prefix for the messages; cells: the box's.  In stream order: the reserves of the handle's rows, counter lines and
+// host-volume copies (the rows' wait until the previous call's upload has read the pinned rows), one upload of the host images
+// -- depth images, then colour images, each rounded up to 256 bytes --, then the view rows and the colour row.  The caller's
+// copies, memsets and launch follow.
+struct MapTsdfViews {
+  DevScratch images;  // the host images of the call, uploaded; freed with this record, behind the caller's last wait
+  const MapCarveView* views = nullptr;
+  const uint8_t* const* bgr = nullptr;  // one pointer per view; NULL without colour
+  bool uploaded = false;                // host images were: the caller waits for the stream before it returns
+};
+int map_tsdf_views_begin(revo_map* m, const std::string& who, size_t cells, int n, const revo_map_carve_view* views, const uint8_t* const* bgr,
+                         int device_in, int device_tsdf, MapTsdfViews* out);
+
 // revo_map_view.hip, for revo_map_gain.hip: revo_map_raycast's march over views that are in device memory already.  map_ray_open
 // reserves and builds the block table of the map as it is on the stream, clears the info line d_info and fills *a;
 // map_ray_views enqueues k_map_raycast over n (1 .. 64) views whose largest image takes max_blocks blocks.

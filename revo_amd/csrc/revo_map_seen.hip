@@ -3,9 +3,8 @@
 // revo_map_known_field, the distance field over solid + unseen cells, lives with the field's passes in revo_map_field.hip.
 // Contracts: include/revo_hip.h.  Every value is an integer that float32 arithmetic with one definition decides.
 #include "revo_map_impl.h"
+#include "revo_cell_run.h"
 #include "revo_seen_host.h"
-
-#define SEEN_RUN 4  // consecutive cells of a thread: one 32-bit word of the volume
 
 struct MapObserveK {
   const MapCarveView* views; int n;
@@ -26,99 +25,68 @@ static_assert(sizeof(revo_map_observe_info) == 64 && offsetof(revo_map_observe_i
               offsetof(revo_map_observe_info, votes) == 8 * OBS_VOTES && offsetof(revo_map_observe_info, newly_known) == 8 * OBS_NEW &&
               offsetof(revo_map_observe_info, reserved) == 40, "the info record is the kernel's counter line");
 
-__device__ __forceinline__ unsigned seen_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // lane 0 holds the wave's sum
-}
-
-// One thread per 32-bit word of the volume: SEEN_RUN cells that follow each other in memory (z fastest, so mostly along z,
-// whatever n[2] is and wherever a z-line starts; consecutive lanes take consecutive runs: a wave's projections fall on
-// neighbouring pixels).  The views are read through uniform addresses one after another; a cell's votes and surface bit
-// stay in two packed registers (a byte per cell: f <= 64 cannot carry).  A word inside the volume is read (when accumulating)
-// and written as one word, the tail of a volume whose cells are no multiple of four byte by byte.  Per view the classes of a
-// wave are counted by ballots into LDS; every counter takes one global atomic per block.  No atomic touches a cell.
-__global__ void __launch_bounds__(256) k_map_observe(const MapObserveK a) {
+// One thread per 32-bit word of the volume, over the walk of revo_cell_run.h: CELL_RUN cells that follow each other in memory (z
+// fastest, so mostly along z, whatever n[2] is and wherever a z-line starts).  The views are read through uniform addresses one
+// after another; a cell's votes and surface bit stay in two packed registers (a byte per cell: f <= 64 cannot carry).  A word
+// inside the volume is read (when accumulating) and written as one word, the tail of a volume whose cells are no multiple of
+// four byte by byte.  Per view the classes of a wave are counted by ballots into LDS; every counter takes one global atomic per
+// block.  No atomic touches a cell.
+__global__ void __launch_bounds__(CELL_RUN_THREADS) k_map_observe(const MapObserveK a) {
   __shared__ unsigned s_cls[CARVE_MAX_VIEWS * CARVE_CLASSES];
   __shared__ unsigned s_cnt[4];  // free, surface, votes, newly known
-  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256) s_cls[k] = 0;
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += CELL_RUN_THREADS) s_cls[k] = 0;
   if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const size_t c0 = (size_t)(blockIdx.x * 256u + threadIdx.x) * SEEN_RUN;  // the first cell of the run
-  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
-  bool valid[SEEN_RUN];
-  float px[SEEN_RUN], py[SEEN_RUN], pz[SEEN_RUN];
+  CellRun r;  // whole: seen + c0 is 4-byte aligned
+  const size_t c0 = cell_run_first(blockIdx.x);
 #pragma unroll
-  for (int j = 0; j < SEEN_RUN; ++j) {
-    const size_t c = c0 + j;
-    valid[j] = c < a.cells;
-    const unsigned cc = valid[j] ? (unsigned)c : 0u;
-    const unsigned line = cc / nz, iz = cc - line * nz;
-    const unsigned ix = line / ny, iy = line - ix * ny;
-    px[j] = seen_centre(a.box.lo[0], (int)ix, a.voxel);
-    py[j] = seen_centre(a.box.lo[1], (int)iy, a.voxel);
-    pz[j] = seen_centre(a.box.lo[2], (int)iz, a.voxel);
-  }
+  for (int j = 0; j < CELL_RUN; ++j) cell_run_cell(c0, j, a.box, a.cells, a.voxel, r);
   unsigned votes = 0, surface = 0;  // byte j: the run's cell j
   for (int vi = 0; vi < a.n; ++vi) {  // uniform: the ballots see whole waves
-    int cls[SEEN_RUN];
+    int cls[CELL_RUN];
 #pragma unroll
-    for (int j = 0; j < SEEN_RUN; ++j) {
-      cls[j] = valid[j] ? map_carve_class(px[j], py[j], pz[j], a.views[vi], a.radius, a.margin, a.margin_rel) : -1;
+    for (int j = 0; j < CELL_RUN; ++j) {
+      cls[j] = r.valid[j] ? map_carve_class(r.px[j], r.py[j], r.pz[j], a.views[vi], a.radius, a.margin, a.margin_rel) : -1;
       votes += (cls[j] == CARVE_FREE ? 1u : 0u) << (8 * j);
       surface |= (cls[j] == CARVE_CONFIRMED ? SEEN_SURFACE : 0u) << (8 * j);
     }
-#pragma unroll
-    for (int k = 0; k < CARVE_CLASSES; ++k) {
-      unsigned cnt = 0;
-#pragma unroll
-      for (int j = 0; j < SEEN_RUN; ++j) cnt += (unsigned)__popcll(__ballot(cls[j] == k));
-      if (lane == 0 && cnt) atomicAdd(&s_cls[vi * CARVE_CLASSES + k], cnt);
-    }
+    cell_run_count_classes(cls, s_cls + vi * CARVE_CLASSES);
   }
-  const bool whole = valid[SEEN_RUN - 1];  // the four cells exist, and seen + c0 is 4-byte aligned
   unsigned in = 0;
   if (a.accumulate) {
-    if (whole) {
+    if (cell_run_whole(r)) {
       in = *(const unsigned*)(a.seen + c0);
     } else {
 #pragma unroll
-      for (int j = 0; j < SEEN_RUN; ++j)
-        if (valid[j]) in |= (unsigned)a.seen[c0 + j] << (8 * j);
+      for (int j = 0; j < CELL_RUN; ++j)
+        if (r.valid[j]) in |= (unsigned)a.seen[c0 + j] << (8 * j);
     }
   }
   unsigned out = 0, n_free = 0, n_surface = 0, n_votes = 0, n_new = 0;
 #pragma unroll
-  for (int j = 0; j < SEEN_RUN; ++j) {
+  for (int j = 0; j < CELL_RUN; ++j) {
     const unsigned f = (votes >> (8 * j)) & 0xffu, b_in = (in >> (8 * j)) & 0xffu;
     const unsigned b = seen_byte((uint8_t)b_in, f, (surface >> (8 * j + 7)) & 1u);
     out |= b << (8 * j);
-    if (valid[j]) {
+    if (r.valid[j]) {
       n_free += (b & SEEN_VOTES) != 0;
       n_surface += (b & SEEN_SURFACE) != 0;
       n_votes += f;
       n_new += b_in == 0 && b != 0;
     }
   }
-  if (whole) {
+  if (cell_run_whole(r)) {
     *(unsigned*)(a.seen + c0) = out;
   } else {
 #pragma unroll
-    for (int j = 0; j < SEEN_RUN; ++j)
-      if (valid[j]) a.seen[c0 + j] = (uint8_t)(out >> (8 * j));
+    for (int j = 0; j < CELL_RUN; ++j)
+      if (r.valid[j]) a.seen[c0 + j] = (uint8_t)(out >> (8 * j));
   }
-  n_free = seen_wave_sum(n_free); n_surface = seen_wave_sum(n_surface); n_votes = seen_wave_sum(n_votes); n_new = seen_wave_sum(n_new);
-  if (lane == 0) {  // a block's votes: at most 256 * 4 * 64
-    if (n_free) atomicAdd(&s_cnt[0], n_free);
-    if (n_surface) atomicAdd(&s_cnt[1], n_surface);
-    if (n_votes) atomicAdd(&s_cnt[2], n_votes);
-    if (n_new) atomicAdd(&s_cnt[3], n_new);
-  }
+  cell_run_tally(s_cnt, n_free, n_surface, n_votes, n_new);  // a block's votes: at most 256 * 4 * 64
   __syncthreads();
   if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&a.info[OBS_FREE + threadIdx.x], (u64)s_cnt[threadIdx.x]);
   if (blockIdx.x == 0 && threadIdx.x == 4) a.info[OBS_CELLS] = (u64)a.cells;
-  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256)
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += CELL_RUN_THREADS)
     if (s_cls[k]) atomicAdd(&a.vinfo[(k / CARVE_CLASSES) * 8 + k % CARVE_CLASSES], s_cls[k]);
 }
 
@@ -162,8 +130,7 @@ extern "C" int revo_map_observe(revo_map* m, const revo_map_df_box* box, int n, 
   if (!device_seen && pp.accumulate) HIPCHECK(hipMemcpyAsync(a.seen, seen, cells, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemsetAsync(a.info, 0, sizeof(revo_map_observe_info), s));
   HIPCHECK(hipMemsetAsync(a.vinfo, 0, vinfo_bytes, s));
-  const size_t words = (cells + SEEN_RUN - 1) / SEEN_RUN;
-  hipLaunchKernelGGL(k_map_observe, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_map_observe, dim3(cell_run_blocks(cells)), dim3(CELL_RUN_THREADS), 0, s, a);
   HIPCHECK(hipGetLastError());
   if (!device_seen) {
     HIPCHECK(hipMemcpyAsync(seen, a.seen, cells, hipMemcpyDeviceToHost, s));

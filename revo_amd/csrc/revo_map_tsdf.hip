@@ -5,10 +5,8 @@
 // is an integer that float32 arithmetic with one definition decides, or (a vertex, a normal) a float that one chain of separately
 // rounded operations gives.
 #include "revo_map_impl.h"
-#include "revo_seen_host.h"  // a cell's point is the seen volume's
+#include "revo_cell_run.h"
 #include "revo_tsdf_host.h"
-
-#define TSDF_RUN 4  // consecutive cells of a thread: two 16-byte words of the volume
 
 struct TsdfFuseK {
   const MapCarveView* views; int n;
@@ -39,77 +37,47 @@ static_assert(sizeof(revo_map_tsdf_color) == 16 && offsetof(revo_map_tsdf_color,
 static_assert(sizeof(revo_map_tsdf_color_info) == 32 && offsetof(revo_map_tsdf_color_info, cells_colored) == 8 &&
               offsetof(revo_map_tsdf_color_info, reserved) == 16, "the colour info record is the kernel's two counters");
 
-__device__ __forceinline__ unsigned tsdf_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // lane 0 holds the wave's sum
-}
-
-// One thread per run of TSDF_RUN cells that follow each other in memory (z fastest; consecutive lanes take consecutive runs: a
-// wave's projections fall on neighbouring pixels, as in k_map_observe).  The views are read through uniform addresses one after
-// another; a cell's sum and weight stay in registers from the one read (when accumulating) to the one write: two 16-byte words
-// for a whole run, 8-byte words for the tail of a volume whose cells are no multiple of four.  Per view the classes of a wave
-// are counted by ballots into LDS; every counter takes one global atomic per block.  No atomic touches a cell.
+// The walk is revo_cell_run.h's: one thread per run of CELL_RUN cells that follow each other in memory.  The views are read through
+// uniform addresses one after another; a cell's sum and weight stay in registers from the one read (when accumulating) to the one
+// write.  Per view the classes of a wave are counted by ballots into LDS; every counter takes one global atomic per block.  No
+// atomic touches a cell.
 // COLOR (revo_map_tsdf_fuse_color): the run's four colour cells stay in registers the same way, one 16-byte word each; a view's
 // three colour bytes are read where its update of a cell is a CONFIRMED one that was not dropped.  Without it `col` is not
 // looked at and the kernel is what it was.
 template <bool COLOR>
-__global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a, const TsdfColorK col) {
+__global__ void __launch_bounds__(CELL_RUN_THREADS) k_tsdf_fuse(const TsdfFuseK a, const TsdfColorK col) {
   __shared__ unsigned s_cls[CARVE_MAX_VIEWS * CARVE_CLASSES];
   __shared__ unsigned s_cnt[4];  // updates, weighted, inside, saturated
   __shared__ unsigned s_col[2];  // colour updates, cells coloured
-  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256) s_cls[k] = 0;
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += CELL_RUN_THREADS) s_cls[k] = 0;
   if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
   if (COLOR && threadIdx.x < 2) s_col[threadIdx.x] = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const size_t c0 = (size_t)(blockIdx.x * 256u + threadIdx.x) * TSDF_RUN;  // the first cell of the run
-  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
-  bool valid[TSDF_RUN];
-  float px[TSDF_RUN], py[TSDF_RUN], pz[TSDF_RUN];
-  int sum[TSDF_RUN];
-  unsigned weight[TSDF_RUN];
-  uint4 rgb[TSDF_RUN];  // COLOR: the colour cells
+  CellRun r;
+  const size_t c0 = cell_run_first(blockIdx.x);
+  int sum[CELL_RUN];
+  unsigned weight[CELL_RUN];
+  uint4 rgb[CELL_RUN];  // COLOR: the colour cells
 #pragma unroll
-  for (int j = 0; j < TSDF_RUN; ++j) {
-    const size_t c = c0 + j;
-    valid[j] = c < a.cells;
-    const unsigned cc = valid[j] ? (unsigned)c : 0u;
-    const unsigned line = cc / nz, iz = cc - line * nz;
-    const unsigned ix = line / ny, iy = line - ix * ny;
-    px[j] = seen_centre(a.box.lo[0], (int)ix, a.voxel);
-    py[j] = seen_centre(a.box.lo[1], (int)iy, a.voxel);
-    pz[j] = seen_centre(a.box.lo[2], (int)iz, a.voxel);
+  for (int j = 0; j < CELL_RUN; ++j) {
+    cell_run_cell(c0, j, a.box, a.cells, a.voxel, r);
     sum[j] = 0;
     weight[j] = 0u;
     if (COLOR) rgb[j] = make_uint4(0u, 0u, 0u, 0u);
   }
-  const bool whole = valid[TSDF_RUN - 1];  // the four cells exist, and tsdf + c0 is 16-byte aligned
   if (a.accumulate) {
-    if (whole) {
-      const int4 lo = *(const int4*)(a.tsdf + c0), hi = *(const int4*)(a.tsdf + c0 + 2);
-      sum[0] = lo.x; weight[0] = (unsigned)lo.y; sum[1] = lo.z; weight[1] = (unsigned)lo.w;
-      sum[2] = hi.x; weight[2] = (unsigned)hi.y; sum[3] = hi.z; weight[3] = (unsigned)hi.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < TSDF_RUN; ++j)
-        if (valid[j]) { const int2 v = a.tsdf[c0 + j]; sum[j] = v.x; weight[j] = (unsigned)v.y; }
-    }
-    if (COLOR) {
-#pragma unroll
-      for (int j = 0; j < TSDF_RUN; ++j)
-        if (valid[j]) rgb[j] = col.color[c0 + j];
-    }
+    cell_run_load(a.tsdf, c0, r, sum, weight);
+    cell_run_load_color<COLOR>(col.color, c0, r, rgb);
   }
   unsigned n_upd = 0, n_sat = 0, n_cupd = 0;
   for (int vi = 0; vi < a.n; ++vi) {  // uniform: the ballots see whole waves
-    int cls[TSDF_RUN];
+    int cls[CELL_RUN];
 #pragma unroll
-    for (int j = 0; j < TSDF_RUN; ++j) {
+    for (int j = 0; j < CELL_RUN; ++j) {
       float z = 0.0f, dc = 0.0f;
       unsigned pix = 0u;
-      if (COLOR) cls[j] = valid[j] ? map_carve_class_zdp(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
-      else cls[j] = valid[j] ? map_carve_class_zd(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
+      if (COLOR) cls[j] = r.valid[j] ? map_carve_class_zdp(r.px[j], r.py[j], r.pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
+      else cls[j] = r.valid[j] ? map_carve_class_zd(r.px[j], r.py[j], r.pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
       if (cls[j] == CARVE_FREE || cls[j] == CARVE_CONFIRMED) {
         const int q = cls[j] == CARVE_FREE ? TSDF_Q_ONE : tsdf_quantum(dc, z, a.trunc);
         const unsigned dropped = tsdf_update(sum[j], weight[j], q);
@@ -118,56 +86,76 @@ __global__ void __launch_bounds__(256) k_tsdf_fuse(const TsdfFuseK a, const Tsdf
         if (COLOR) n_cupd += tsdf_color_update(rgb[j].x, rgb[j].y, rgb[j].z, rgb[j].w, cls[j] == CARVE_CONFIRMED, dropped, col.bgr[vi] + (size_t)pix * 3);
       }
     }
-#pragma unroll
-    for (int k = 0; k < CARVE_CLASSES; ++k) {
-      unsigned cnt = 0;
-#pragma unroll
-      for (int j = 0; j < TSDF_RUN; ++j) cnt += (unsigned)__popcll(__ballot(cls[j] == k));
-      if (lane == 0 && cnt) atomicAdd(&s_cls[vi * CARVE_CLASSES + k], cnt);
-    }
+    cell_run_count_classes(cls, s_cls + vi * CARVE_CLASSES);
   }
-  unsigned n_weighted = 0, n_inside = 0;
+  unsigned n_weighted = 0, n_inside = 0, n_col = 0;
 #pragma unroll
-  for (int j = 0; j < TSDF_RUN; ++j)
-    if (valid[j]) {
+  for (int j = 0; j < CELL_RUN; ++j)
+    if (r.valid[j]) {
       n_weighted += weight[j] > 0u;
       n_inside += weight[j] > 0u && sum[j] < 0;
     }
-  if (whole) {
-    *(int4*)(a.tsdf + c0) = make_int4(sum[0], (int)weight[0], sum[1], (int)weight[1]);
-    *(int4*)(a.tsdf + c0 + 2) = make_int4(sum[2], (int)weight[2], sum[3], (int)weight[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < TSDF_RUN; ++j)
-      if (valid[j]) a.tsdf[c0 + j] = make_int2(sum[j], (int)weight[j]);
-  }
+  cell_run_store(a.tsdf, c0, r, sum, weight);
+  cell_run_store_color<COLOR>(col.color, c0, r, rgb);
   if (COLOR) {
-    unsigned n_col = 0;
 #pragma unroll
-    for (int j = 0; j < TSDF_RUN; ++j)
-      if (valid[j]) {
-        col.color[c0 + j] = rgb[j];
-        n_col += rgb[j].w > 0u;
-      }
-    n_cupd = tsdf_wave_sum(n_cupd); n_col = tsdf_wave_sum(n_col);
-    if (lane == 0) {
-      if (n_cupd) atomicAdd(&s_col[0], n_cupd);
-      if (n_col) atomicAdd(&s_col[1], n_col);
-    }
+    for (int j = 0; j < CELL_RUN; ++j) n_col += r.valid[j] && rgb[j].w > 0u;
   }
-  n_upd = tsdf_wave_sum(n_upd); n_weighted = tsdf_wave_sum(n_weighted); n_inside = tsdf_wave_sum(n_inside); n_sat = tsdf_wave_sum(n_sat);
-  if (lane == 0) {  // a block's updates: at most 256 * 4 * 64
-    if (n_upd) atomicAdd(&s_cnt[0], n_upd);
-    if (n_weighted) atomicAdd(&s_cnt[1], n_weighted);
-    if (n_inside) atomicAdd(&s_cnt[2], n_inside);
-    if (n_sat) atomicAdd(&s_cnt[3], n_sat);
-  }
+  if (COLOR) cell_run_tally(s_col, n_cupd, n_col);
+  cell_run_tally(s_cnt, n_upd, n_weighted, n_inside, n_sat);  // a block's updates: at most 256 * 4 * 64
   __syncthreads();
   if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&a.info[TF_UPDATES + threadIdx.x], (u64)s_cnt[threadIdx.x]);
   if (blockIdx.x == 0 && threadIdx.x == 4) a.info[TF_CELLS] = (u64)a.cells;
   if (COLOR && threadIdx.x >= 8 && threadIdx.x < 10 && s_col[threadIdx.x - 8]) atomicAdd(&col.info[threadIdx.x - 8], (u64)s_col[threadIdx.x - 8]);
-  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256)
+  for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += CELL_RUN_THREADS)
     if (s_cls[k]) atomicAdd(&a.vinfo[(k / CARVE_CLASSES) * 8 + k % CARVE_CLASSES], s_cls[k]);
+}
+
+int map_tsdf_views_begin(revo_map* m, const std::string& who, size_t cells, int n, const revo_map_carve_view* views, const uint8_t* const* bgr,
+                         int device_in, int device_tsdf, MapTsdfViews* out) {
+  const bool with_color = bgr != nullptr;
+  std::vector<const uint8_t*> hb(n, nullptr);  // the views' colour images as the kernel reads them
+  if (with_color)
+    for (int i = 0; i < n; ++i) {
+      if (const char* why = tsdf_bgr_check(&views[i], bgr[i])) return fail(REVO_ERR_INVALID_ARG, who + "view " + std::to_string(i) + ": " + why);
+      hb[i] = bgr[i];
+    }
+  std::vector<MapCarveView> hv(n);
+  size_t up_bytes = 0;
+  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes, with_color ? hb.data() : nullptr));
+  size_t up_bgr = 0;  // the host colour images behind the depth images in the one upload
+  if (with_color && !device_in)
+    for (int i = 0; i < n; ++i)
+      if (bgr[i]) up_bgr += ((size_t)hv[i].v.w * hv[i].v.h * 3 + 255) & ~(size_t)255;
+  HIPCHECK(hipSetDevice(m->g.device));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  TRY(m->tsdf_views.reserve(n, s));  // waits until the previous call's upload has read the pinned rows
+  if (with_color) TRY(m->tsdf_bgr.reserve(n, s));
+  TRY(m->tsdfcnt.reserve(256 + sizeof(revo_map_carve_view_info) * CARVE_MAX_VIEWS, s));
+  TRY(m->tsdfvol.reserve(device_tsdf ? 0 : sizeof(revo_map_tsdf_cell) * cells, s));
+  if (with_color) TRY(m->tsdfcol.reserve(device_tsdf ? 0 : sizeof(revo_map_tsdf_color) * cells, s));
+  out->uploaded = up_bytes + up_bgr != 0;
+  if (out->uploaded) {
+    TRY(out->images.alloc(up_bytes + up_bgr));
+    TRY(map_views_upload(n, views, hv.data(), out->images.p, s));
+    size_t o = up_bytes;
+    for (int i = 0; up_bgr && i < n; ++i) {
+      if (!bgr[i]) continue;
+      const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * 3;
+      HIPCHECK(hipMemcpyAsync(out->images.p + o, bgr[i], bytes, hipMemcpyHostToDevice, s));
+      hb[i] = (const uint8_t*)(out->images.p + o);
+      o += (bytes + 255) & ~(size_t)255;
+    }
+  }
+  memcpy(m->tsdf_views.h, hv.data(), sizeof(MapCarveView) * n);
+  TRY(m->tsdf_views.upload(n, s));
+  out->views = m->tsdf_views.d;
+  if (with_color) {
+    memcpy(m->tsdf_bgr.h, hb.data(), sizeof(const uint8_t*) * n);
+    TRY(m->tsdf_bgr.upload(n, s));
+    out->bgr = m->tsdf_bgr.d;
+  }
+  return REVO_OK;
 }
 
 // Both fuse calls.  name: the entry point's, for its messages.  with_color: revo_map_tsdf_fuse_color -- bgr, color and cinfo are
@@ -187,45 +175,13 @@ static int tsdf_fuse_core(const char* name, bool with_color, revo_map* m, const 
   if (device_tsdf && with_color) TRY(map_check_aligned((uintptr_t)color | (uintptr_t)cinfo, 16, "a device output is"));
   revo_map_tsdf_params pp;
   if (const char* why = tsdf_params_check(prm, m->voxel, &pp)) return fail(REVO_ERR_INVALID_ARG, who + why);
-  std::vector<const uint8_t*> hb(n, nullptr);  // the views' colour images as the kernel reads them
-  if (with_color)
-    for (int i = 0; i < n; ++i) {
-      if (const char* why = tsdf_bgr_check(&views[i], bgr[i])) return fail(REVO_ERR_INVALID_ARG, who + "view " + std::to_string(i) + ": " + why);
-      hb[i] = bgr[i];
-    }
-  std::vector<MapCarveView> hv(n);
-  size_t up_bytes = 0;
-  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes, with_color ? hb.data() : nullptr));
-  size_t up_bgr = 0;  // the host colour images behind the depth images in the one upload, each rounded up to 256 bytes
-  if (with_color && !device_in)
-    for (int i = 0; i < n; ++i)
-      if (bgr[i]) up_bgr += ((size_t)hv[i].v.w * hv[i].v.h * 3 + 255) & ~(size_t)255;
-  HIPCHECK(hipSetDevice(m->g.device));
+  MapTsdfViews v;
+  TRY(map_tsdf_views_begin(m, who, cells, n, views, with_color ? bgr : nullptr, device_in, device_tsdf, &v));
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t vinfo_bytes = sizeof(revo_map_carve_view_info) * (size_t)n, vol_bytes = sizeof(revo_map_tsdf_cell) * cells;
   const size_t col_bytes = sizeof(revo_map_tsdf_color) * cells;
-  TRY(m->tsdf_views.reserve(n, s));  // waits until the previous call's upload has read the pinned rows
-  if (with_color) TRY(m->tsdf_bgr.reserve(n, s));
-  TRY(m->tsdfcnt.reserve(256 + sizeof(revo_map_carve_view_info) * CARVE_MAX_VIEWS, s));
-  TRY(m->tsdfvol.reserve(device_tsdf ? 0 : vol_bytes, s));
-  if (with_color) TRY(m->tsdfcol.reserve(device_tsdf ? 0 : col_bytes, s));
-  DevScratch images;  // host images of the call, uploaded; freed behind the wait below
-  if (up_bytes + up_bgr) {
-    TRY(images.alloc(up_bytes + up_bgr));
-    TRY(map_views_upload(n, views, hv.data(), images.p, s));
-    size_t o = up_bytes;
-    for (int i = 0; up_bgr && i < n; ++i) {
-      if (!bgr[i]) continue;
-      const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * 3;
-      HIPCHECK(hipMemcpyAsync(images.p + o, bgr[i], bytes, hipMemcpyHostToDevice, s));
-      hb[i] = (const uint8_t*)(images.p + o);
-      o += (bytes + 255) & ~(size_t)255;
-    }
-  }
-  memcpy(m->tsdf_views.h, hv.data(), sizeof(MapCarveView) * n);
-  TRY(m->tsdf_views.upload(n, s));
   TsdfFuseK a{};
-  a.views = m->tsdf_views.d; a.n = n;
+  a.views = v.views; a.n = n;
   a.accumulate = pp.accumulate;
   a.trunc = pp.trunc; a.voxel = m->voxel;
   a.box = *box;
@@ -235,9 +191,7 @@ static int tsdf_fuse_core(const char* name, bool with_color, revo_map* m, const 
   a.vinfo = device_tsdf && view_info ? (unsigned*)view_info : (unsigned*)(m->tsdfcnt.p + 256);
   TsdfColorK col{};
   if (with_color) {
-    memcpy(m->tsdf_bgr.h, hb.data(), sizeof(const uint8_t*) * n);
-    TRY(m->tsdf_bgr.upload(n, s));
-    col.bgr = m->tsdf_bgr.d;
+    col.bgr = v.bgr;
     col.color = device_tsdf ? (uint4*)color : (uint4*)m->tsdfcol.p;
     col.info = device_tsdf && cinfo ? (u64*)cinfo : (u64*)(m->tsdfcnt.p + 64);
     if (!device_tsdf && pp.accumulate) HIPCHECK(hipMemcpyAsync(col.color, color, col_bytes, hipMemcpyHostToDevice, s));
@@ -246,10 +200,9 @@ static int tsdf_fuse_core(const char* name, bool with_color, revo_map* m, const 
   if (!device_tsdf && pp.accumulate) HIPCHECK(hipMemcpyAsync(a.tsdf, tsdf, vol_bytes, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemsetAsync(a.info, 0, sizeof(revo_map_tsdf_info), s));
   HIPCHECK(hipMemsetAsync(a.vinfo, 0, vinfo_bytes, s));
-  const size_t runs = (cells + TSDF_RUN - 1) / TSDF_RUN;
-  const dim3 grid((unsigned)((runs + 255) / 256));
-  if (with_color) hipLaunchKernelGGL(k_tsdf_fuse<true>, grid, dim3(256), 0, s, a, col);
-  else hipLaunchKernelGGL(k_tsdf_fuse<false>, grid, dim3(256), 0, s, a, col);
+  const dim3 grid(cell_run_blocks(cells));
+  if (with_color) hipLaunchKernelGGL(k_tsdf_fuse<true>, grid, dim3(CELL_RUN_THREADS), 0, s, a, col);
+  else hipLaunchKernelGGL(k_tsdf_fuse<false>, grid, dim3(CELL_RUN_THREADS), 0, s, a, col);
   HIPCHECK(hipGetLastError());
   if (!device_tsdf) {
     HIPCHECK(hipMemcpyAsync(tsdf, a.tsdf, vol_bytes, hipMemcpyDeviceToHost, s));
@@ -260,7 +213,7 @@ static int tsdf_fuse_core(const char* name, bool with_color, revo_map* m, const 
       if (cinfo) HIPCHECK(hipMemcpyAsync(cinfo, col.info, sizeof(revo_map_tsdf_color_info), hipMemcpyDeviceToHost, s));
     }
   }
-  if (!device_tsdf || up_bytes + up_bgr) HIPCHECK(hipStreamSynchronize(s));
+  if (!device_tsdf || v.uploaded) HIPCHECK(hipStreamSynchronize(s));
   return REVO_OK;
 }
 

@@ -6,7 +6,7 @@
 #include "revo_map_impl.h"
 #include "revo_track_dev.h"
 #include "revo_align_host.h"
-#include "revo_seen_host.h"  // a cell's point is the seen volume's
+#include "revo_cell_run.h"
 #include "revo_tsdf_host.h"
 #include "revo_tsdf_track_host.h"
 #include "revo_tsdf_many_host.h"
@@ -50,63 +50,32 @@ struct TsdfManyFuseK {
   unsigned* lines;    // TSDF_MANY_STRIDE words per job, zero before the launch: the counters (TSDF_MANY_LINE words) and the job's ticket
 };
 
-__device__ __forceinline__ unsigned tmy_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // lane 0 holds the wave's sum
-}
-
-// One block of one job: k_tsdf_fuse's body for one view into a volume that is read and updated -- one thread per run of four
-// cells that follow each other in memory, the run's sums and weights in registers from the one read to the one write (two
-// 16-byte words; 8-byte words for the tail of a volume whose cells are no multiple of four), the colour cells in four more.  The
-// classes of a wave are counted by ballots into LDS.  blk: the block's number within the job.
+// One block of one job: k_tsdf_fuse's body for one view into a volume that is read and updated, over the same walk
+// (revo_cell_run.h).  The classes of a wave are counted by ballots into LDS.  blk: the block's number within the job.
 template <bool COLOR>
 __device__ __forceinline__ void tmy_fuse_block(const TsdfManyFuseJob& a, unsigned blk, unsigned* s_cls, unsigned* s_cnt, unsigned* s_col) {
-  const int lane = threadIdx.x & 63;
-  const size_t c0 = (size_t)(blk * 256u + threadIdx.x) * TSDF_MANY_RUN;  // the first cell of the run
-  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
-  bool valid[TSDF_MANY_RUN];
-  float px[TSDF_MANY_RUN], py[TSDF_MANY_RUN], pz[TSDF_MANY_RUN];
-  int sum[TSDF_MANY_RUN];
-  unsigned weight[TSDF_MANY_RUN];
-  uint4 rgb[TSDF_MANY_RUN];  // COLOR: the colour cells
+  CellRun r;
+  const size_t c0 = cell_run_first(blk);
+  int sum[CELL_RUN];
+  unsigned weight[CELL_RUN];
+  uint4 rgb[CELL_RUN];  // COLOR: the colour cells
 #pragma unroll
-  for (int j = 0; j < TSDF_MANY_RUN; ++j) {
-    const size_t c = c0 + j;
-    valid[j] = c < a.cells;
-    const unsigned cc = valid[j] ? (unsigned)c : 0u;
-    const unsigned line = cc / nz, iz = cc - line * nz;
-    const unsigned ix = line / ny, iy = line - ix * ny;
-    px[j] = seen_centre(a.box.lo[0], (int)ix, a.voxel);
-    py[j] = seen_centre(a.box.lo[1], (int)iy, a.voxel);
-    pz[j] = seen_centre(a.box.lo[2], (int)iz, a.voxel);
+  for (int j = 0; j < CELL_RUN; ++j) {
+    cell_run_cell(c0, j, a.box, a.cells, a.voxel, r);
     sum[j] = 0;
     weight[j] = 0u;
     if (COLOR) rgb[j] = make_uint4(0u, 0u, 0u, 0u);
   }
-  const bool whole = valid[TSDF_MANY_RUN - 1];  // the four cells exist, and tsdf + c0 is 16-byte aligned
-  if (whole) {
-    const int4 lo = *(const int4*)(a.tsdf + c0), hi = *(const int4*)(a.tsdf + c0 + 2);
-    sum[0] = lo.x; weight[0] = (unsigned)lo.y; sum[1] = lo.z; weight[1] = (unsigned)lo.w;
-    sum[2] = hi.x; weight[2] = (unsigned)hi.y; sum[3] = hi.z; weight[3] = (unsigned)hi.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < TSDF_MANY_RUN; ++j)
-      if (valid[j]) { const int2 v = a.tsdf[c0 + j]; sum[j] = v.x; weight[j] = (unsigned)v.y; }
-  }
-  if (COLOR) {
-#pragma unroll
-    for (int j = 0; j < TSDF_MANY_RUN; ++j)
-      if (valid[j]) rgb[j] = a.color[c0 + j];
-  }
+  cell_run_load(a.tsdf, c0, r, sum, weight);
+  cell_run_load_color<COLOR>(a.color, c0, r, rgb);
   unsigned n_upd = 0, n_sat = 0, n_cupd = 0;
-  int cls[TSDF_MANY_RUN];
+  int cls[CELL_RUN];
 #pragma unroll
-  for (int j = 0; j < TSDF_MANY_RUN; ++j) {
+  for (int j = 0; j < CELL_RUN; ++j) {
     float z = 0.0f, dc = 0.0f;
     unsigned pix = 0u;
-    if (COLOR) cls[j] = valid[j] ? map_carve_class_zdp(px[j], py[j], pz[j], a.view, 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
-    else cls[j] = valid[j] ? map_carve_class_zd(px[j], py[j], pz[j], a.view, 0, a.trunc, 0.0f, &z, &dc) : -1;
+    if (COLOR) cls[j] = r.valid[j] ? map_carve_class_zdp(r.px[j], r.py[j], r.pz[j], a.view, 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
+    else cls[j] = r.valid[j] ? map_carve_class_zd(r.px[j], r.py[j], r.pz[j], a.view, 0, a.trunc, 0.0f, &z, &dc) : -1;
     if (cls[j] == CARVE_FREE || cls[j] == CARVE_CONFIRMED) {
       const int q = cls[j] == CARVE_FREE ? TSDF_Q_ONE : tsdf_quantum(dc, z, a.trunc);
       const unsigned dropped = tsdf_update(sum[j], weight[j], q);
@@ -115,49 +84,22 @@ __device__ __forceinline__ void tmy_fuse_block(const TsdfManyFuseJob& a, unsigne
       if (COLOR) n_cupd += tsdf_color_update(rgb[j].x, rgb[j].y, rgb[j].z, rgb[j].w, cls[j] == CARVE_CONFIRMED, dropped, a.bgr + (size_t)pix * 3);
     }
   }
+  cell_run_count_classes(cls, s_cls);  // uniform: the ballots see whole waves
+  unsigned n_weighted = 0, n_inside = 0, n_col = 0;
 #pragma unroll
-  for (int k = 0; k < CARVE_CLASSES; ++k) {  // uniform: the ballots see whole waves
-    unsigned cnt = 0;
-#pragma unroll
-    for (int j = 0; j < TSDF_MANY_RUN; ++j) cnt += (unsigned)__popcll(__ballot(cls[j] == k));
-    if (lane == 0 && cnt) atomicAdd(&s_cls[k], cnt);
-  }
-  unsigned n_weighted = 0, n_inside = 0;
-#pragma unroll
-  for (int j = 0; j < TSDF_MANY_RUN; ++j)
-    if (valid[j]) {
+  for (int j = 0; j < CELL_RUN; ++j)
+    if (r.valid[j]) {
       n_weighted += weight[j] > 0u;
       n_inside += weight[j] > 0u && sum[j] < 0;
     }
-  if (whole) {
-    *(int4*)(a.tsdf + c0) = make_int4(sum[0], (int)weight[0], sum[1], (int)weight[1]);
-    *(int4*)(a.tsdf + c0 + 2) = make_int4(sum[2], (int)weight[2], sum[3], (int)weight[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < TSDF_MANY_RUN; ++j)
-      if (valid[j]) a.tsdf[c0 + j] = make_int2(sum[j], (int)weight[j]);
-  }
+  cell_run_store(a.tsdf, c0, r, sum, weight);
+  cell_run_store_color<COLOR>(a.color, c0, r, rgb);
   if (COLOR) {
-    unsigned n_col = 0;
 #pragma unroll
-    for (int j = 0; j < TSDF_MANY_RUN; ++j)
-      if (valid[j]) {
-        a.color[c0 + j] = rgb[j];
-        n_col += rgb[j].w > 0u;
-      }
-    n_cupd = tmy_wave_sum(n_cupd); n_col = tmy_wave_sum(n_col);
-    if (lane == 0) {
-      if (n_cupd) atomicAdd(&s_col[0], n_cupd);
-      if (n_col) atomicAdd(&s_col[1], n_col);
-    }
+    for (int j = 0; j < CELL_RUN; ++j) n_col += r.valid[j] && rgb[j].w > 0u;
   }
-  n_upd = tmy_wave_sum(n_upd); n_weighted = tmy_wave_sum(n_weighted); n_inside = tmy_wave_sum(n_inside); n_sat = tmy_wave_sum(n_sat);
-  if (lane == 0) {  // a block's updates: at most 256 * 4
-    if (n_upd) atomicAdd(&s_cnt[0], n_upd);
-    if (n_weighted) atomicAdd(&s_cnt[1], n_weighted);
-    if (n_inside) atomicAdd(&s_cnt[2], n_inside);
-    if (n_sat) atomicAdd(&s_cnt[3], n_sat);
-  }
+  if (COLOR) cell_run_tally(s_col, n_cupd, n_col);
+  cell_run_tally(s_cnt, n_upd, n_weighted, n_inside, n_sat);  // a block's updates: at most 256 * 4
 }
 
 // Grid: the blocks of all jobs, job after job (tsdf_many_find).  A block past the last job's returns before any barrier.  A

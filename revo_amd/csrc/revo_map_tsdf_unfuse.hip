@@ -3,10 +3,8 @@
 // a call's views, the FIT test, the down-date): revo_tsdf_host.h.  Every value is an integer; the classes and quanta are the fuse's,
 // through the same map_carve_class_zd[p] and tsdf_quantum.
 #include "revo_map_impl.h"
-#include "revo_seen_host.h"  // a cell's point is the seen volume's
+#include "revo_cell_run.h"
 #include "revo_tsdf_host.h"
-
-#define UNFUSE_RUN 4  // consecutive cells of a thread: two 16-byte words of the volume, as k_tsdf_fuse's TSDF_RUN
 
 enum { UI_CELLS = 0, UI_UPDATES = 1, UI_WEIGHTED = 2, UI_INSIDE = 3, UI_MISFITS = 4, UI_CUPDATES = 5, UI_COLORED = 6 };
 
@@ -29,95 +27,57 @@ struct TsdfUnfuseK {
   unsigned* vinfo;            // the check pass: 8 words per view, revo_map_carve_view_info
 };
 
-__device__ __forceinline__ unsigned unfuse_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // lane 0 holds the wave's sum
-}
-
-// Both passes, k_tsdf_fuse's layout: one thread per run of UNFUSE_RUN cells that follow each other in memory (z fastest), the views
-// read through uniform addresses one after another, the run's cells in registers from one read -- two 16-byte words for a whole
-// run, 8-byte words for the tail of a volume whose cells are no multiple of four, one 16-byte word per colour cell.  Per cell the
-// views' updates are summed into a TsdfDown; behind the views the cell is tested (the check pass) or down-dated (the apply pass).
+// Both passes over k_tsdf_fuse's walk (revo_cell_run.h): one thread per run of CELL_RUN cells, the views read through uniform
+// addresses one after another, the run's cells in registers from one read.  Per cell the views' updates are summed into a
+// TsdfDown; behind the views the cell is tested (the check pass) or down-dated (the apply pass).
 // The check pass (APPLY false) writes nothing to the volumes: it counts the cells that do not FIT, the volumes' cells as they
 // stand, and per view the classes of a wave by ballots into LDS.  The apply pass runs only behind a check that found no misfit,
 // writes every cell of a run once and counts what it took out and what is left.  Every counter takes one global atomic per block;
 // no atomic touches a cell.
 template <bool COLOR, bool APPLY>
-__global__ void __launch_bounds__(256) k_tsdf_unfuse(const TsdfUnfuseK a) {
+__global__ void __launch_bounds__(CELL_RUN_THREADS) k_tsdf_unfuse(const TsdfUnfuseK a) {
   __shared__ unsigned s_cls[APPLY ? 1 : CARVE_MAX_VIEWS * CARVE_CLASSES];
   __shared__ unsigned s_cnt[8];  // UI_*
   if (!APPLY)
-    for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256) s_cls[k] = 0;
+    for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += CELL_RUN_THREADS) s_cls[k] = 0;
   if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const size_t c0 = (size_t)(blockIdx.x * 256u + threadIdx.x) * UNFUSE_RUN;  // the first cell of the run
-  const unsigned ny = (unsigned)a.box.n[1], nz = (unsigned)a.box.n[2];
-  bool valid[UNFUSE_RUN];
-  float px[UNFUSE_RUN], py[UNFUSE_RUN], pz[UNFUSE_RUN];
-  int sum[UNFUSE_RUN];
-  unsigned weight[UNFUSE_RUN];
-  uint4 rgb[UNFUSE_RUN];  // COLOR: the colour cells
-  TsdfDown down[UNFUSE_RUN];
+  CellRun r;
+  const size_t c0 = cell_run_first(blockIdx.x);
+  int sum[CELL_RUN];
+  unsigned weight[CELL_RUN];
+  uint4 rgb[CELL_RUN];  // COLOR: the colour cells
+  TsdfDown down[CELL_RUN];
 #pragma unroll
-  for (int j = 0; j < UNFUSE_RUN; ++j) {
-    const size_t c = c0 + j;
-    valid[j] = c < a.cells;
-    const unsigned cc = valid[j] ? (unsigned)c : 0u;
-    const unsigned line = cc / nz, iz = cc - line * nz;
-    const unsigned ix = line / ny, iy = line - ix * ny;
-    px[j] = seen_centre(a.box.lo[0], (int)ix, a.voxel);
-    py[j] = seen_centre(a.box.lo[1], (int)iy, a.voxel);
-    pz[j] = seen_centre(a.box.lo[2], (int)iz, a.voxel);
+  for (int j = 0; j < CELL_RUN; ++j) {
+    cell_run_cell(c0, j, a.box, a.cells, a.voxel, r);
     sum[j] = 0;
     weight[j] = 0u;
     rgb[j] = make_uint4(0u, 0u, 0u, 0u);
     down[j] = TsdfDown{0u, 0u, 0, 0u, 0u, 0u};
   }
-  const bool whole = valid[UNFUSE_RUN - 1];  // the four cells exist, and tsdf + c0 is 16-byte aligned
-  if (whole) {
-    const int4 lo = *(const int4*)(a.tsdf + c0), hi = *(const int4*)(a.tsdf + c0 + 2);
-    sum[0] = lo.x; weight[0] = (unsigned)lo.y; sum[1] = lo.z; weight[1] = (unsigned)lo.w;
-    sum[2] = hi.x; weight[2] = (unsigned)hi.y; sum[3] = hi.z; weight[3] = (unsigned)hi.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < UNFUSE_RUN; ++j)
-      if (valid[j]) { const int2 v = a.tsdf[c0 + j]; sum[j] = v.x; weight[j] = (unsigned)v.y; }
-  }
-  if (COLOR) {
-#pragma unroll
-    for (int j = 0; j < UNFUSE_RUN; ++j)
-      if (valid[j]) rgb[j] = a.color[c0 + j];
-  }
+  cell_run_load(a.tsdf, c0, r, sum, weight);
+  cell_run_load_color<COLOR>(a.color, c0, r, rgb);
   for (int vi = 0; vi < a.n; ++vi) {  // uniform: the ballots see whole waves
-    int cls[UNFUSE_RUN];
+    int cls[CELL_RUN];
 #pragma unroll
-    for (int j = 0; j < UNFUSE_RUN; ++j) {
+    for (int j = 0; j < CELL_RUN; ++j) {
       float z = 0.0f, dc = 0.0f;
       unsigned pix = 0u;
-      if (COLOR) cls[j] = valid[j] ? map_carve_class_zdp(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
-      else cls[j] = valid[j] ? map_carve_class_zd(px[j], py[j], pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
+      if (COLOR) cls[j] = r.valid[j] ? map_carve_class_zdp(r.px[j], r.py[j], r.pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
+      else cls[j] = r.valid[j] ? map_carve_class_zd(r.px[j], r.py[j], r.pz[j], a.views[vi], 0, a.trunc, 0.0f, &z, &dc) : -1;
       if (cls[j] == CARVE_FREE || cls[j] == CARVE_CONFIRMED) {
         const bool confirmed = cls[j] == CARVE_CONFIRMED;
         const int q = confirmed ? tsdf_quantum(dc, z, a.trunc) : TSDF_Q_ONE;
         tsdf_down_add(down[j], confirmed, q, COLOR && confirmed ? a.bgr[vi] + (size_t)pix * 3 : nullptr);
       }
     }
-    if (!APPLY) {
-#pragma unroll
-      for (int k = 0; k < CARVE_CLASSES; ++k) {
-        unsigned cnt = 0;
-#pragma unroll
-        for (int j = 0; j < UNFUSE_RUN; ++j) cnt += (unsigned)__popcll(__ballot(cls[j] == k));
-        if (lane == 0 && cnt) atomicAdd(&s_cls[vi * CARVE_CLASSES + k], cnt);
-      }
-    }
+    if (!APPLY) cell_run_count_classes(cls, s_cls + vi * CARVE_CLASSES);
   }
   unsigned n_upd = 0, n_cupd = 0, n_misfit = 0, n_weighted = 0, n_inside = 0, n_col = 0;
 #pragma unroll
-  for (int j = 0; j < UNFUSE_RUN; ++j) {
-    if (!valid[j]) continue;
+  for (int j = 0; j < CELL_RUN; ++j) {
+    if (!r.valid[j]) continue;
     if (down[j].k) {
       if (APPLY) {
         tsdf_down_apply(sum[j], weight[j], down[j]);
@@ -137,45 +97,25 @@ __global__ void __launch_bounds__(256) k_tsdf_unfuse(const TsdfUnfuseK a) {
     if (COLOR) n_col += rgb[j].w > 0u;
   }
   if (APPLY) {
-    if (whole) {
-      *(int4*)(a.tsdf + c0) = make_int4(sum[0], (int)weight[0], sum[1], (int)weight[1]);
-      *(int4*)(a.tsdf + c0 + 2) = make_int4(sum[2], (int)weight[2], sum[3], (int)weight[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < UNFUSE_RUN; ++j)
-        if (valid[j]) a.tsdf[c0 + j] = make_int2(sum[j], (int)weight[j]);
-    }
-    if (COLOR) {
-#pragma unroll
-      for (int j = 0; j < UNFUSE_RUN; ++j)
-        if (valid[j]) a.color[c0 + j] = rgb[j];
-    }
+    cell_run_store(a.tsdf, c0, r, sum, weight);
+    cell_run_store_color<COLOR>(a.color, c0, r, rgb);
   }
-  n_upd = unfuse_wave_sum(n_upd); n_weighted = unfuse_wave_sum(n_weighted); n_inside = unfuse_wave_sum(n_inside);
-  n_misfit = unfuse_wave_sum(n_misfit);
-  if (COLOR) { n_cupd = unfuse_wave_sum(n_cupd); n_col = unfuse_wave_sum(n_col); }
-  if (lane == 0) {  // a block's updates: at most 256 * 4 * 64
-    if (n_upd) atomicAdd(&s_cnt[UI_UPDATES], n_upd);
-    if (n_weighted) atomicAdd(&s_cnt[UI_WEIGHTED], n_weighted);
-    if (n_inside) atomicAdd(&s_cnt[UI_INSIDE], n_inside);
-    if (n_misfit) atomicAdd(&s_cnt[UI_MISFITS], n_misfit);
-    if (n_cupd) atomicAdd(&s_cnt[UI_CUPDATES], n_cupd);
-    if (n_col) atomicAdd(&s_cnt[UI_COLORED], n_col);
-  }
+  // a block's updates: at most 256 * 4 * 64.  The counters in UI_*'s order, from UI_UPDATES on
+  if (COLOR) cell_run_tally(s_cnt + UI_UPDATES, n_upd, n_weighted, n_inside, n_misfit, n_cupd, n_col);
+  else cell_run_tally(s_cnt + UI_UPDATES, n_upd, n_weighted, n_inside, n_misfit);
   __syncthreads();
   if (threadIdx.x >= UI_UPDATES && threadIdx.x <= UI_COLORED && s_cnt[threadIdx.x]) atomicAdd(&a.line[threadIdx.x], (u64)s_cnt[threadIdx.x]);
   if (blockIdx.x == 0 && threadIdx.x == 8) a.line[UI_CELLS] = (u64)a.cells;
   if (!APPLY)
-    for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += 256)
+    for (int k = threadIdx.x; k < a.n * CARVE_CLASSES; k += CELL_RUN_THREADS)
       if (s_cls[k]) atomicAdd(&a.vinfo[(k / CARVE_CLASSES) * 8 + k % CARVE_CLASSES], s_cls[k]);
 }
 
 template <bool APPLY>
 static void unfuse_launch(bool with_color, const TsdfUnfuseK& a, hipStream_t s) {
-  const size_t runs = ((size_t)a.cells + UNFUSE_RUN - 1) / UNFUSE_RUN;
-  const dim3 grid((unsigned)((runs + 255) / 256));
-  if (with_color) hipLaunchKernelGGL((k_tsdf_unfuse<true, APPLY>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_tsdf_unfuse<false, APPLY>), grid, dim3(256), 0, s, a);
+  const dim3 grid(cell_run_blocks(a.cells));
+  if (with_color) hipLaunchKernelGGL((k_tsdf_unfuse<true, APPLY>), grid, dim3(CELL_RUN_THREADS), 0, s, a);
+  else hipLaunchKernelGGL((k_tsdf_unfuse<false, APPLY>), grid, dim3(CELL_RUN_THREADS), 0, s, a);
 }
 
 extern "C" int revo_map_tsdf_unfuse(revo_map* m, const revo_map_df_box* box, int n, const revo_map_carve_view* views,
@@ -194,45 +134,13 @@ extern "C" int revo_map_tsdf_unfuse(revo_map* m, const revo_map_df_box* box, int
   if (device_tsdf) TRY(map_check_aligned((uintptr_t)tsdf | (uintptr_t)color | (uintptr_t)view_info, 16, "a device output is"));
   float tr = 0.0f;
   if (const char* why = tsdf_unfuse_trunc(trunc, m->voxel, &tr)) return fail(REVO_ERR_INVALID_ARG, who + why);
-  std::vector<const uint8_t*> hb(n, nullptr);  // the views' colour images as the kernel reads them
-  if (with_color)
-    for (int i = 0; i < n; ++i) {
-      if (const char* why = tsdf_bgr_check(&views[i], bgr[i])) return fail(REVO_ERR_INVALID_ARG, who + "view " + std::to_string(i) + ": " + why);
-      hb[i] = bgr[i];
-    }
-  std::vector<MapCarveView> hv(n);
-  size_t up_bytes = 0;
-  TRY(map_views_prepare(m, n, views, device_in, hv.data(), &up_bytes, with_color ? hb.data() : nullptr));
-  size_t up_bgr = 0;  // the host colour images behind the depth images in the one upload, each rounded up to 256 bytes
-  if (with_color && !device_in)
-    for (int i = 0; i < n; ++i)
-      if (bgr[i]) up_bgr += ((size_t)hv[i].v.w * hv[i].v.h * 3 + 255) & ~(size_t)255;
-  HIPCHECK(hipSetDevice(m->g.device));
+  MapTsdfViews v;
+  TRY(map_tsdf_views_begin(m, who, cells, n, views, bgr, device_in, device_tsdf, &v));
   hipStream_t s = (hipStream_t)m->g.stream;
   const size_t vinfo_bytes = sizeof(revo_map_carve_view_info) * (size_t)n, vol_bytes = sizeof(revo_map_tsdf_cell) * cells;
   const size_t col_bytes = sizeof(revo_map_tsdf_color) * cells;
-  TRY(m->tsdf_views.reserve(n, s));  // waits until the previous call's upload has read the pinned rows
-  if (with_color) TRY(m->tsdf_bgr.reserve(n, s));
-  TRY(m->tsdfcnt.reserve(256 + sizeof(revo_map_carve_view_info) * CARVE_MAX_VIEWS, s));
-  TRY(m->tsdfvol.reserve(device_tsdf ? 0 : vol_bytes, s));
-  if (with_color) TRY(m->tsdfcol.reserve(device_tsdf ? 0 : col_bytes, s));
-  DevScratch images;  // host images of the call, uploaded; freed behind the waits below
-  if (up_bytes + up_bgr) {
-    TRY(images.alloc(up_bytes + up_bgr));
-    TRY(map_views_upload(n, views, hv.data(), images.p, s));
-    size_t o = up_bytes;
-    for (int i = 0; up_bgr && i < n; ++i) {
-      if (!bgr[i]) continue;
-      const size_t bytes = (size_t)hv[i].v.w * hv[i].v.h * 3;
-      HIPCHECK(hipMemcpyAsync(images.p + o, bgr[i], bytes, hipMemcpyHostToDevice, s));
-      hb[i] = (const uint8_t*)(images.p + o);
-      o += (bytes + 255) & ~(size_t)255;
-    }
-  }
-  memcpy(m->tsdf_views.h, hv.data(), sizeof(MapCarveView) * n);
-  TRY(m->tsdf_views.upload(n, s));
   TsdfUnfuseK a{};
-  a.views = m->tsdf_views.d; a.n = n;
+  a.views = v.views; a.n = n;
   a.trunc = tr; a.voxel = m->voxel;
   a.box = *box;
   a.cells = (unsigned)cells;
@@ -240,9 +148,7 @@ extern "C" int revo_map_tsdf_unfuse(revo_map* m, const revo_map_df_box* box, int
   a.line = (u64*)m->tsdfcnt.p;  // the check's line; the apply's is the next one
   a.vinfo = device_tsdf && view_info ? (unsigned*)view_info : (unsigned*)(m->tsdfcnt.p + 256);
   if (with_color) {
-    memcpy(m->tsdf_bgr.h, hb.data(), sizeof(const uint8_t*) * n);
-    TRY(m->tsdf_bgr.upload(n, s));
-    a.bgr = m->tsdf_bgr.d;
+    a.bgr = v.bgr;
     a.color = device_tsdf ? (uint4*)color : (uint4*)m->tsdfcol.p;
     if (!device_tsdf) HIPCHECK(hipMemcpyAsync(a.color, color, col_bytes, hipMemcpyHostToDevice, s));
   }
@@ -269,7 +175,7 @@ extern "C" int revo_map_tsdf_unfuse(revo_map* m, const revo_map_df_box* box, int
     if (with_color) HIPCHECK(hipMemcpyAsync(color, a.color, col_bytes, hipMemcpyDeviceToHost, s));
   }
   if (info) HIPCHECK(hipMemcpyAsync(line, a.line, sizeof(line), hipMemcpyDeviceToHost, s));
-  if (!device_tsdf || info || up_bytes + up_bgr) HIPCHECK(hipStreamSynchronize(s));
+  if (!device_tsdf || info || v.uploaded) HIPCHECK(hipStreamSynchronize(s));
   if (info) {
     line[7] = 0;
     memcpy(info, line, sizeof(line));

@@ -10,11 +10,11 @@
 #include <utility>
 #include <vector>
 
+#include "revo_cell_run.h"
 #include "revo_tsdf_host.h"
 
 #define TSDF_MANY_MAX_JOBS 1024
-#define TSDF_MANY_RUN 4          // k_tsdf_fuse's: consecutive cells of a thread
-#define TSDF_MANY_THREADS 256    // ... and threads of a block
+#define TSDF_MANY_THREADS CELL_RUN_THREADS  // k_tsdf_fuse's block
 // A job's counter line in the launch's scratch, 32 words: revo_map_tsdf_info | revo_map_tsdf_color_info | revo_map_carve_view_info.
 #define TSDF_MANY_LINE 32
 #define TSDF_MANY_STRIDE 64      // words from one job's line to the next: the line, the job's ticket, and room to 256 bytes
@@ -23,10 +23,7 @@
 #define TSDF_MANY_LINE_VINFO 24
 
 // The blocks a job of `cells` cells takes: k_tsdf_fuse's grid for that box.
-TSDF_HD unsigned tsdf_many_blocks(size_t cells) {
-  const size_t runs = (cells + TSDF_MANY_RUN - 1) / TSDF_MANY_RUN;
-  return (unsigned)((runs + TSDF_MANY_THREADS - 1) / TSDF_MANY_THREADS);
-}
+TSDF_HD unsigned tsdf_many_blocks(size_t cells) { return cell_run_blocks(cells); }
 
 // The jobs take the launch's blocks one after another: job j the blocks first(j) .. first(j) + blocks(j) - 1, first(0) = 0, every
 // job at least one.  The job of `block` (< the total) is the last one whose first block is not behind it: a bisection over the

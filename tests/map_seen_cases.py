@@ -131,8 +131,9 @@ def spec(name):
 
 
 def z_boxes():
-    """Boxes whose z-lines start at every alignment of the volume's words, and the cell counts around a block."""
-    out = [((-1, -1, 6), (3, 3, nz)) for nz in (1, 3, 4, 5, 31, 32, 33, 65)]
+    """Boxes whose z-lines start at every alignment of the volume's words, the cell counts around a block, and 1035 cells: a full
+    block of 1024, then a second block with a tail word of three cells."""
+    out = [((-1, -1, 6), (3, 3, nz)) for nz in (1, 3, 4, 5, 31, 32, 33, 65, 115)]
     return out + [((-1, -2, 4), (3, 5, 17)), ((-2, -4, 5), (4, 8, 8)), ((-128, 0, 8), (257, 1, 1))]
 
 

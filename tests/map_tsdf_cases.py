@@ -60,6 +60,9 @@ def fuse_cases():
     c["64 views"] = dict(lo=LO, n=N, views=sc.views64(), trunc=None)
     for nz in (1, 3, 4, 5, 33):  # runs of four cells against z-lines of every length: n[0] * n[1] = 9
         c["3x3x%d" % nz] = dict(lo=(-1, -1, 6), n=(3, 3, nz), views=sc.z_views(), trunc=None)
+    # 1035 cells: a full block of 1024, then a second block of two whole runs and a tail run of three cells -- the smallest box at
+    # which a wrong block offset, or a wrong tail in a block that is not the first, shows
+    c["3x3x115"] = dict(lo=(-1, -1, 6), n=(3, 3, 115), views=sc.z_views(), trunc=None)
     return c
 
 
