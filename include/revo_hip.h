@@ -1915,6 +1915,48 @@ typedef struct revo_map_tsdf_fuse_job {  /* 200 bytes, no padding holes */
  * memory of m's device; two volumes (TSDF or colour, of any two jobs) whose byte ranges overlap. */
 int revo_map_tsdf_fuse_many(revo_map* m, int n_jobs, const revo_map_tsdf_fuse_job* jobs);
 
+/* One unfuse job: ONE view taken out of the job's volumes as revo_map_tsdf_unfuse does with n = 1, device_in = 1 and
+ * device_tsdf = 1.  The members are revo_map_tsdf_fuse_job's with the unfuse's meaning; several views of one volume stay the
+ * single call's business. */
+typedef struct revo_map_tsdf_unfuse_job {  /* 192 bytes, no padding holes */
+  revo_map* map;                         /* offset   0: gives the voxel edge; of m's context; NULL: m                        */
+  revo_map_df_box box;                   /* offset   8: the box rules of revo_map_distance_field                             */
+  float trunc;                           /* offset  32: what the view was fused with; 0: 4 x the job's voxel edge            */
+  uint32_t reserved;                     /* offset  36: zero                                                                 */
+  revo_map_tsdf_cell* tsdf;              /* offset  40: device, 16-byte aligned                                              */
+  revo_map_tsdf_color* color;            /* offset  48: device, 16-byte aligned, or NULL: the colour volume is not touched   */
+  revo_map_carve_view view;              /* offset  56: kf, or a raw depth image in device memory (4-byte aligned)           */
+  const uint8_t* bgr;                    /* offset 168: with color: NULL for a pyramid view, the device colour image of a    */
+                                         /*             raw view; without color: NULL                                        */
+  revo_map_tsdf_unfuse_info* info;       /* offset 176: device, 16-byte aligned, or NULL                                     */
+  revo_map_carve_view_info* view_info;   /* offset 184: device, 16-byte aligned, or NULL: one record                         */
+} revo_map_tsdf_unfuse_job;
+typedef struct revo_map_tsdf_unfuse_result {  /* 80 bytes, no padding holes */
+  revo_map_tsdf_unfuse_info info;        /* offset  0: the job's info, as the single call gives it (refused or not)          */
+  int32_t status;                        /* offset 64: REVO_OK, or REVO_ERR_INVALID_ARG: the job had a misfit and changed    */
+                                         /*            nothing, the single call's code for a refusal                         */
+  int32_t reserved[3];                   /* offset 68: zero                                                                  */
+} revo_map_tsdf_unfuse_result;
+/* n_jobs (1 .. 1024) unfuse jobs in TWO launches on m's context's tracker stream (a check pass and an apply pass over all jobs),
+ * for a pyramid view behind that pyramid's build.  The verdict stays on the device: the apply pass reads each job's misfit count
+ * where the check pass left it, and the blocks of a refused job return at once; there is no host wait between the passes.
+ * Per job, the single call:
+ *   a job whose cells all FIT leaves the volumes, info and view_info that revo_map_tsdf_unfuse leaves for that job alone;
+ *   a job with a misfit changes no byte of its volumes; its info is the single call's refused info (misfits counted, updates and
+ *   color_updates 0, the other counters describing the volumes as they stand) and its view_info is still the fuse's;
+ *   every other job of the call is applied all the same; neither the order of the jobs nor the other jobs show in a job's bytes.
+ * results (may be NULL): n_jobs records, in device memory 16-byte aligned (device_out = 1; status is written by the kernel) or in
+ * host memory (device_out = 0).  With results == NULL or device_out = 1 the call only enqueues; with host results it waits once,
+ * at the end.  The return value is REVO_OK whenever the argument rules hold, even if jobs were refused: a refusal is a per-job
+ * result, not a failed call.  No atomic touches a cell, so two jobs must not share a volume.
+ * REVO_ERR_INVALID_ARG, the call refused as a whole before anything is enqueued and with no byte written: NULL m or jobs; n_jobs
+ * outside 1 .. 1024; in any job: a map of another context, a NULL tsdf, a box, view, bgr, trunc or alignment rule of the single
+ * call broken, a reserved word that is not 0, bgr given without color, a volume, an image or a record that is not in device
+ * memory of m's device; two volumes (TSDF or colour, of any two jobs) whose byte ranges overlap; device_out outside 0 / 1; device
+ * results that are misaligned or not in device memory of m's device. */
+int revo_map_tsdf_unfuse_many(revo_map* m, int n_jobs, const revo_map_tsdf_unfuse_job* jobs,
+                              revo_map_tsdf_unfuse_result* results, int device_out);
+
 /* One track job: revo_map_tsdf_track_eval's arguments for one volume and one frame (device_tsdf = 1, device_in = 1). */
 typedef struct revo_map_tsdf_track_job {  /* 200 bytes, no padding holes */
   revo_map* map;                          /* gives the voxel edge; of m's context; NULL: m                                    */
@@ -1991,6 +2033,36 @@ int revo_vo_multi_attach_surface(revo_vo_multi* mv, int stream, const revo_vo_mu
 /* The report of the stream's last keyframe since the surface was attached; waits for that step's fuse.
  * REVO_ERR_INVALID_ARG: a bad stream or NULL out, no surface attached, or no keyframe since it was. */
 int revo_vo_multi_surface_last(revo_vo_multi* mv, int stream, revo_vo_multi_surface_report* out);
+
+/* A bounded surface for a stream: with window = N (1 .. 1024) the stream's volumes hold its last N fused keyframes;
+ * 0, the default of every attachment, switches the window off and the surface only grows.  Valid after
+ * revo_vo_multi_attach_surface; setting it (also to the value it has) starts an empty window: views held so far are forgotten and
+ * stay in the volumes.  With a window the step does two more things behind its revo_map_tsdf_fuse_many:
+ *   keep   for every keyframe it fused, what names the view again -- device copies of the keyframe slot's level-0 depth plane and
+ *          colour image ((4 + 3) bytes per pixel; no colour image without a colour volume) and T_fused -- enqueued on the tracker
+ *          stream where the fuse is; a window's N + 1 slots are allocated when first used.  A keyframe that was skipped is not held;
+ *   evict  for every stream that now holds more than its window, the oldest view is taken out with ONE
+ *          revo_map_tsdf_unfuse_many over all such streams, as the raw view of the kept copies (which gives the bytes of the
+ *          pyramid view it was fused as); each job's info goes to a device record of its stream, and nothing waits.
+ * A step still never fails for a surface.  The host rotates the window without knowing the device's verdict: an eviction the
+ * device refuses FORGETS the view and leaves it in the volumes.  That can happen only for volumes that were attached pre-filled
+ * (so that a cell's state is one no fuse of the held views reaches) or that hold a cell at the full weight 2^20;
+ * revo_vo_multi_surface_window_last reports it.  With track = 1 keyframes are tracked against the windowed surface as it stands.
+ * Detaching the surface, revo_vo_multi_reset and revo_vo_multi_destroy free the window.
+ * REVO_ERR_INVALID_ARG: a stream out of range; no surface attached; window outside 0 .. 1024. */
+int revo_vo_multi_surface_window(revo_vo_multi* mv, int stream, int window);
+typedef struct revo_vo_multi_surface_window_report {  /* 104 bytes, no padding holes */
+  int32_t window;                       /* offset  0: the window's size                                                     */
+  int32_t held;                         /* offset  4: the views held, <= window                                             */
+  uint64_t evictions;                   /* offset  8: the views that have left the window since it was set                  */
+  double evicted_timestamp;             /* offset 16: the keyframe time stamp of the last one; 0 without an eviction        */
+  revo_map_tsdf_unfuse_result evicted;  /* offset 24: its info as revo_map_tsdf_unfuse_many left it on the device, and its  */
+                                        /*            status by that call's rule: REVO_ERR_INVALID_ARG when misfits != 0,   */
+                                        /*            the view then stayed in the volumes; zero without an eviction         */
+} revo_vo_multi_surface_window_report;
+/* The stream's window as it stands; waits for the step's work on the tracker stream when there has been an eviction.
+ * REVO_ERR_INVALID_ARG: a bad stream or NULL out, no surface attached, or no window set. */
+int revo_vo_multi_surface_window_last(revo_vo_multi* mv, int stream, revo_vo_multi_surface_window_report* out);
 
 /* ---------------------------------------------------------------------------
  * PNG decoding on the device: replaces the cv::imread(IMREAD_COLOR) / cv::imread(IMREAD_UNCHANGED) of the TUM front-end

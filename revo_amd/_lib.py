@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MapTsdfUnfuseJob, MultiSurfaceWindowReport, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -201,9 +201,12 @@ def lib():
     L.revo_map_tsdf_unfuse.argtypes = [vp, C.POINTER(MapDfBox), C.c_int, C.POINTER(MapCarveView), vp, C.c_int, C.c_float, vp, vp, C.c_int,
                                        C.POINTER(MapTsdfUnfuseInfo), vp]
     L.revo_map_tsdf_fuse_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfFuseJob)]
+    L.revo_map_tsdf_unfuse_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfUnfuseJob), vp, C.c_int]
     L.revo_map_tsdf_track_eval_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfTrackJob), vp, C.c_int]
     L.revo_vo_multi_attach_surface.argtypes = [vp, C.c_int, C.POINTER(MultiSurface)]
     L.revo_vo_multi_surface_last.argtypes = [vp, C.c_int, C.POINTER(MultiSurfaceReport)]
+    L.revo_vo_multi_surface_window.argtypes = [vp, C.c_int, C.c_int]
+    L.revo_vo_multi_surface_window_last.argtypes = [vp, C.c_int, C.POINTER(MultiSurfaceWindowReport)]
     L.revo_map_tsdf_track_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfTrackJob), C.POINTER(MapAlignOpts), C.POINTER(MapTsdfTrackResult), i32p]
     L.revo_png_probe.argtypes = [C.c_char_p, C.c_size_t, vp]
     L.revo_png_decoder_create.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, vpp]

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfUnfuseJob, MapTsdfUnfuseResult, MapTsdfTrackJob, MapTsdfTrackResult,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1559,6 +1559,39 @@ class VoxelMap:
             self.sync()
         del keep
 
+    def unfuse_many_into(self, jobs, wait=True, d_results=None):
+        """Many (volume, view) unfuses in a check and an apply launch (revo_map_tsdf_unfuse_many): per job what
+        unfuse_into(d_tsdf, [view], ...) does for that job alone, except that a refusal is the job's result and not an error --
+        a job with a misfit changes nothing, every other job is applied.  A job is a dict as fuse_many_into takes it, without
+        d_color_info; trunc is what the view was fused with; d_info is 64 bytes of revo_map_tsdf_unfuse_info.  The verdict stays
+        on the device: nothing waits between the passes.
+        wait=True -> a list of (info dict of mapfile.TSDF_UNFUSE_INFO_KEYS, status) per job, status 0 or -1 (REVO_ERR_INVALID_ARG,
+        refused), from host results: the call's one wait.  wait=False -> None, the call only enqueued; d_results (a contiguous
+        device tensor of 80 bytes per job, revo_map_tsdf_unfuse_result) then takes the records, status included."""
+        import torch
+        from . import mapfile
+        jobs = list(jobs)
+        fj, n, keep = self._fuse_jobs(jobs)
+        arr = (MapTsdfUnfuseJob * max(n, 1))()
+        for j, f, job in zip(arr, fj, jobs):
+            if job.get("d_color_info") is not None:
+                raise ValueError("an unfuse job has no d_color_info: its info holds the colour counters")
+            for name, _t in MapTsdfUnfuseJob._fields_:
+                setattr(j, name, getattr(f, name))
+        if d_results is not None:
+            if wait:
+                raise ValueError("d_results goes with wait=False: wait=True returns the host results")
+            if not (d_results.is_cuda and d_results.is_contiguous() and d_results.numel() * d_results.element_size() == 80 * n):
+                raise ValueError("d_results needs 80 bytes per job, contiguous on the device")
+            torch.cuda.current_stream(d_results.device).synchronize()
+        res = (MapTsdfUnfuseResult * max(n, 1))() if wait else None
+        check(_lib.lib().revo_map_tsdf_unfuse_many(self._h, n, arr, C.cast(res, vp) if wait else (vp(d_results.data_ptr()) if d_results is not None else None),
+                                                   0 if wait else 1))
+        del keep
+        if not wait:
+            return None
+        return [({k: int(getattr(r.info, k)) for k in mapfile.TSDF_UNFUSE_INFO_KEYS}, int(r.status)) for r in res[:n]]
+
     def _track_jobs(self, jobs, with_poses):
         """-> (the revo_map_tsdf_track_job array of a batched tracking call, the poses per job, what keeps the memory alive).  A job is a
         dict: tsdf (int32 device tensor), lo, trunc, frame (a pyramid or (device depth, camera[, zrange])), poses (with_poses: one 4x4 or
@@ -2650,19 +2683,152 @@ class FollowingSurface(SurfaceVolume):
 def fuse_surfaces(pairs, wait=False):
     """[(SurfaceVolume, view), ...] -- one view into each surface of as many running sequences, all in one launch
     (VoxelMap.fuse_many_into): each volume afterwards holds what its own integrate(view) leaves, and its `views` and
-    per-view counts go on as there.  The surfaces' maps share one context; the volumes are distinct."""
+    per-view counts go on as there.  The surfaces' maps share one context; the volumes are distinct.
+    A SurfaceWindow entry ((window, view) or (window, view, bgr), as its integrate takes them) is honoured as its integrate honours
+    it: the view is made keepable and held, and behind the one fuse every window that now holds more than `window`
+    views has its oldest one taken out, all in one batched unfuse with host results (unfuse_surfaces).  A refused eviction keeps
+    integrate's rule: that window holds window + 1 views, and a RevoError (.refused: [(window, info), ...]) is raised after every
+    job of the call has been handled."""
     import torch
-    pairs = list(pairs)
+    pairs = [tuple(p) for p in pairs]
     if not pairs:
         return
-    jobs = []
-    for surf, view in pairs:
+    jobs, windows = [], []
+    for surf, view, *rest in pairs:
+        if isinstance(surf, SurfaceWindow):  # the view as the window can name it again, held from here on
+            view = surf._keepable(view, rest[0] if rest else None)
+            windows.append((surf, view))
         vi = torch.zeros(8, dtype=torch.int32, device=surf.d_tsdf.device)
         jobs.append(dict(map=surf.map, d_tsdf=surf.d_tsdf, d_color=surf.d_color, lo=surf.lo, trunc=surf.trunc, view=view, d_view_info=vi))
     pairs[0][0].map.fuse_many_into(jobs, wait=wait)
-    for (surf, _), job in zip(pairs, jobs):
+    for (surf, *_), job in zip(pairs, jobs):
         surf._vinfo.append(job["d_view_info"])
         surf.views += 1
+    for surf, held in windows:
+        surf._held.append(held)
+    # the evictions: one batched unfuse with host results per round over every window that holds more than `window` views
+    over, refused = [w for w, _ in windows], []
+    while True:
+        over = [w for w in over if len(w._held) > w.window]
+        if not over:
+            break
+        res = unfuse_surfaces([(w, 0) for w in over])
+        for w, (info, status) in zip(list(over), res):
+            if status:
+                refused.append((w, info))
+                over.remove(w)
+    if refused:
+        e = RevoError(-1, "%d evictions were refused (a cell of the oldest view has reached the full weight): those windows hold window + 1 views"
+                      % len(refused))
+        e.refused, e.info, e.misfits = refused, refused[0][1], refused[0][1]["misfits"]
+        raise e
+
+
+def _unfuse_jobs(entries):
+    """-> (the jobs of one unfuse_many_into, the place of each view in its window or None) for [(surface, view), ...]."""
+    import torch
+    jobs, places = [], []
+    for surf, view in entries:
+        if isinstance(surf, FollowingSurface):
+            raise NotImplementedError("a FollowingSurface cannot unfuse: cells of the view may lie in its store")
+        place = surf._place(view) if isinstance(surf, SurfaceWindow) else None
+        if place is not None:
+            view = surf._held[place]
+        vi = torch.zeros(8, dtype=torch.int32, device=surf.d_tsdf.device)
+        jobs.append(dict(map=surf.map, d_tsdf=surf.d_tsdf, d_color=surf.d_color, lo=surf.lo, trunc=surf.trunc, view=view, d_view_info=vi))
+        places.append(place)
+    return jobs, places
+
+
+def _unfuse_rows(surf, place, vi):
+    """The applied unfuse of one view in the surface's books, as SurfaceVolume.remove keeps them -> False when no integrated view
+    of the surface has the view's class counts."""
+    import torch
+    index = place
+    if index is None:
+        same = (torch.stack(surf._vinfo) == vi).all(dim=1).nonzero() if surf._vinfo else []
+        index = int(same[0]) if len(same) else None
+    if index is None or not 0 <= index < len(surf._vinfo):
+        return False
+    del surf._vinfo[index]
+    surf.views -= 1
+    if place is not None:
+        del surf._held[place]
+    return True
+
+
+def unfuse_surfaces(pairs):
+    """[(SurfaceVolume, view), ...] -- one view out of each surface again, all in one batched call (VoxelMap.unfuse_many_into,
+    DESIGN 33): per surface what its own remove(view) does, except that a refusal is that job's result and raises nothing.  A
+    SurfaceWindow names its view as its remove does (an entry of held_views() or its place).  `views` and the per-view counts are
+    kept current for the applied jobs only.  -> [(info dict of mapfile.TSDF_UNFUSE_INFO_KEYS, status), ...], status 0 or -1 (refused:
+    the surface is unchanged).  RuntimeError as SurfaceVolume.remove's, behind the call, for an applied view no row of its
+    surface matches."""
+    pairs = [tuple(p) for p in pairs]
+    if not pairs:
+        return []
+    jobs, places = _unfuse_jobs(pairs)
+    res = pairs[0][0].map.unfuse_many_into(jobs, wait=True)
+    lost = 0
+    for (surf, _), place, job, (_info, status) in zip(pairs, places, jobs, res):
+        if status == 0 and not _unfuse_rows(surf, place, job["d_view_info"]):
+            lost += 1
+    if lost:
+        raise RuntimeError("%d views have been taken out of their volumes, but no integrated view of their surfaces has their class counts: "
+                           "views and view_counts() are left as they were" % lost)
+    return res
+
+
+def repose_surfaces(quads):
+    """[(SurfaceVolume, view, T_old, T_new), ...] -- the keyframes of many streams corrected after a loop closure: one batched
+    unfuse at the old poses, then one batched fuse at the new ones over the jobs that fitted.  Per surface what its own
+    repose does: a refused job is not fused and its surface is unchanged; a window's view keeps its place.
+    -> [(the unfuse's info dict, status), ...]."""
+    quads = [tuple(q) for q in quads]
+    if not quads:
+        return []
+    pose = lambda T: np.asarray(T, np.float32).reshape(4, 4)  # noqa: E731
+    olds = []
+    for surf, view, T_old, _ in quads:
+        if isinstance(surf, SurfaceWindow):
+            olds.append((surf, surf._place(view)))
+        else:
+            view = tuple(view)
+            olds.append((surf, (view[0], pose(T_old)) + view[2:]))
+    jobs, places = _unfuse_jobs(olds)
+    for job, place, (surf, _, T_old, _) in zip(jobs, places, quads):
+        if place is not None:
+            job["view"] = (job["view"][0], pose(T_old)) + tuple(job["view"][2:])
+    res = quads[0][0].map.unfuse_many_into(jobs, wait=True)
+    again, lost = [], 0
+    for (surf, _, _, T_new), place, job, (_info, status) in zip(quads, places, jobs, res):
+        if status:
+            continue
+        new = (job["view"][0], pose(T_new)) + tuple(job["view"][2:])
+        held = list(surf._held) if place is not None else None
+        if not _unfuse_rows(surf, place, job["d_view_info"]):
+            lost += 1
+            continue
+        again.append((surf, place, new, held))
+    if again:
+        import torch
+        fj = []
+        for surf, place, new, _ in again:
+            vi = torch.zeros(8, dtype=torch.int32, device=surf.d_tsdf.device)
+            fj.append(dict(map=surf.map, d_tsdf=surf.d_tsdf, d_color=surf.d_color, lo=surf.lo, trunc=surf.trunc, view=new, d_view_info=vi))
+        again[0][0].map.fuse_many_into(fj, wait=True)
+        for (surf, place, new, held), job in zip(again, fj):
+            surf.views += 1
+            if place is None:
+                surf._vinfo.append(job["d_view_info"])
+            else:  # the per-view counts and the held views keep the window's order
+                surf._vinfo.insert(place, job["d_view_info"])
+                held[place] = new
+                surf._held.clear()
+                surf._held.extend(held)
+    if lost:
+        raise RuntimeError("%d views have been taken out of their volumes, but no integrated view of their surfaces has their class counts" % lost)
+    return res
 
 
 def track_surfaces(triples, max_dist=None, stride=1, min_weight=1, centre=None, **opts):
@@ -3056,6 +3222,10 @@ class MapWindow:
     def fuse_many_into(self, *args, **kw):
         """The inner map's batched surface calls: the window's voxels play no part."""
         return self.map.fuse_many_into(*args, **kw)
+
+    def unfuse_many_into(self, *args, **kw):
+        """The inner map's unfuse_many_into (the window's voxels play no part)."""
+        return self.map.unfuse_many_into(*args, **kw)
 
     def surface_track_eval_many(self, *args, **kw):
         return self.map.surface_track_eval_many(*args, **kw)

@@ -1,4 +1,4 @@
-// revo_cell_run.h -- the walk over a box's cells that k_tsdf_fuse, k_tsdf_fuse_many, k_tsdf_unfuse and k_map_observe share, each
+// revo_cell_run.h -- the walk over a box's cells that k_tsdf_fuse, k_tsdf_fuse_many, k_tsdf_unfuse, k_tsdf_unfuse_many and k_map_observe share, each
 // piece written once: how the cells are dealt out to blocks and threads, where a thread's cells lie and which of them exist, how
 // a run of TSDF and colour cells is read and written, and how a block counts -- a view's classes by ballots, a thread's own counts
 // by a wave sum -- into LDS.  The batched fuse equals the single one and the unfuse inverts the fuse byte for byte because they

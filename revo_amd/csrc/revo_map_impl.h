@@ -296,17 +296,22 @@ struct MapTsdfFollowScratch {
   DevBuf work, dst, dstcol, recs;
 };
 
-// revo_map_tsdf_fuse_many / revo_map_tsdf_track_eval_many / revo_map_tsdf_track_many (revo_map_tsdf_many.hip): the job
+// revo_map_tsdf_fuse_many / revo_map_tsdf_track_eval_many / revo_map_tsdf_track_many / revo_map_tsdf_unfuse_many (revo_map_tsdf_many.hip): the job
 // tables of a launch and its pose rows, the fuse's counter lines and tickets, the tracker's tickets, counts and published
-// partials, and the device records of a host-output call.  Only these three calls go through them.
+// partials, and the device records of a host-output call.  Only these four calls go through them.
 struct TsdfManyFuseJob;   // revo_map_tsdf_many.hip: one job of a batched fuse
 struct TsdfManyTrackJob;  // ... one job of a batched tracking launch
 struct TsdfManyPose;      // ... one pose of it, with its job
+struct TsdfManyUnfuseJob; // ... one job of a batched unfuse
 struct MapTsdfManyScratch {
   HostRows<TsdfManyFuseJob> fuse_jobs;
   HostRows<TsdfManyTrackJob> track_jobs;
   HostRows<TsdfManyPose> poses;
   DevBuf fuse_work, track_work, out;
+  // revo_map_tsdf_unfuse_many: its job table, two counter lines with a ticket each per job (the check pass's and the apply
+  // pass's), and the device records of a call with host results
+  HostRows<TsdfManyUnfuseJob> unfuse_jobs;
+  DevBuf unfuse_work, unfuse_out;
 };
 
 struct revo_map {

@@ -1,6 +1,7 @@
 // revo_map_tsdf_many.hip -- surfaces for many sequences at once: revo_map_tsdf_fuse_many, n (volume, view) fuses in one
 // launch; revo_map_tsdf_track_eval_many, the poses of n (volume, frame) jobs in one launch; revo_map_tsdf_track_many, the
-// Gauss-Newton loops of n jobs in lockstep with one launch, one copy and one wait per round.  Contract: include/revo_hip.h.  Every
+// Gauss-Newton loops of n jobs in lockstep with one launch, one copy and one wait per round; revo_map_tsdf_unfuse_many,
+// n (volume, view) unfuses in a check and an apply launch with no host wait between them.  Contract: include/revo_hip.h.  Every
 // output is the single call's (revo_map_tsdf.hip, revo_map_tsdf_track.hip) byte for byte: the per-cell and per-pixel rules are the
 // ones those kernels call, from the same headers; this unit holds the job tables, how a block finds its job, and the entry points.
 #include "revo_map_impl.h"
@@ -245,6 +246,254 @@ extern "C" int revo_map_tsdf_fuse_many(revo_map* m, int n_jobs, const revo_map_t
   HIPCHECK(hipMemsetAsync(w.fuse_work.p, 0, total, s));
   hipLaunchKernelGGL(k_tsdf_fuse_many, dim3((unsigned)total_blocks), dim3(TSDF_MANY_THREADS), 0, s, a);
   HIPCHECK(hipGetLastError());
+  return REVO_OK;
+}
+
+// ============================================================================================================ the unfuse ==
+// revo_map_tsdf_unfuse_many: the check pass and the apply pass of revo_map_tsdf_unfuse for n (volume, view) jobs, one
+// launch each, with the verdict left on the device between them.
+enum { TMU_CELLS = 0, TMU_UPDATES = 1, TMU_WEIGHTED = 2, TMU_INSIDE = 3, TMU_MISFITS = 4, TMU_CUPDATES = 5, TMU_COLORED = 6 };  // u64s of a revo_map_tsdf_unfuse_info
+#define TMU_LINE_VINFO 16  // a job's counter line, words: revo_map_tsdf_unfuse_info | revo_map_carve_view_info (the check pass's line alone)
+#define TMU_LINE 24
+#define TMU_RES_WORDS 20   // a revo_map_tsdf_unfuse_result: the info, the status, three zero words
+static_assert(sizeof(revo_map_tsdf_unfuse_job) == 192 && offsetof(revo_map_tsdf_unfuse_job, box) == 8 && offsetof(revo_map_tsdf_unfuse_job, trunc) == 32 &&
+              offsetof(revo_map_tsdf_unfuse_job, reserved) == 36 && offsetof(revo_map_tsdf_unfuse_job, tsdf) == 40 && offsetof(revo_map_tsdf_unfuse_job, color) == 48 &&
+              offsetof(revo_map_tsdf_unfuse_job, view) == 56 && offsetof(revo_map_tsdf_unfuse_job, bgr) == 168 && offsetof(revo_map_tsdf_unfuse_job, info) == 176 &&
+              offsetof(revo_map_tsdf_unfuse_job, view_info) == 184, "the unfuse job is the documented layout");
+static_assert(sizeof(revo_map_tsdf_unfuse_result) == 4 * TMU_RES_WORDS && offsetof(revo_map_tsdf_unfuse_result, info) == 0 &&
+              offsetof(revo_map_tsdf_unfuse_result, status) == 64 && offsetof(revo_map_tsdf_unfuse_result, reserved) == 68, "the unfuse result is the documented layout");
+static_assert(sizeof(revo_map_tsdf_unfuse_info) == 4 * TMU_LINE_VINFO && sizeof(revo_map_carve_view_info) == 4 * (TMU_LINE - TMU_LINE_VINFO) &&
+              TMU_LINE <= TSDF_MANY_LINE_TICKET, "a job's counter line is the two records side by side, in front of its ticket");
+static_assert(offsetof(revo_map_tsdf_unfuse_info, cells) == 8 * TMU_CELLS && offsetof(revo_map_tsdf_unfuse_info, updates) == 8 * TMU_UPDATES &&
+              offsetof(revo_map_tsdf_unfuse_info, cells_weighted) == 8 * TMU_WEIGHTED && offsetof(revo_map_tsdf_unfuse_info, cells_inside) == 8 * TMU_INSIDE &&
+              offsetof(revo_map_tsdf_unfuse_info, misfits) == 8 * TMU_MISFITS && offsetof(revo_map_tsdf_unfuse_info, color_updates) == 8 * TMU_CUPDATES &&
+              offsetof(revo_map_tsdf_unfuse_info, cells_colored) == 8 * TMU_COLORED && offsetof(revo_map_tsdf_unfuse_info, reserved) == 56, "the counters' places");
+
+struct TsdfManyUnfuseJob {  // one job of the two launches, in device memory
+  MapCarveView view;
+  const uint8_t* bgr;   // the view's colour image; not read without a colour volume
+  int2* tsdf;           // 16-byte aligned: thread t of the job's block b owns the cells 4 (256 b + t) .. + 3
+  uint4* color;         // NULL: the job's colour volume is not touched
+  unsigned* info;       // the job's own records, or NULL: revo_map_tsdf_unfuse_info, revo_map_carve_view_info
+  unsigned* vinfo;
+  unsigned* res;        // the job's revo_map_tsdf_unfuse_result of the call's results, or NULL
+  revo_map_df_box box;
+  unsigned cells;
+  unsigned first_block, blocks;  // the job's blocks of either launch: tsdf_many_find
+  float trunc, voxel;
+};
+struct TsdfManyUnfuseK {
+  const TsdfManyUnfuseJob* jobs; int n;
+  unsigned total_blocks;
+  unsigned* lines;    // 2 TSDF_MANY_STRIDE words per job, zero before the check launch: the check pass's line and ticket, then the apply pass's
+};
+
+// One block of one job: k_tsdf_unfuse's body for one view (revo_map_tsdf_unfuse.hip), over the same walk and through the same
+// per-cell rules.  The check pass (APPLY false) writes nothing to the volumes; s_cnt: the TMU_* counters of the block.
+template <bool COLOR, bool APPLY>
+__device__ __forceinline__ void tmy_unfuse_block(const TsdfManyUnfuseJob& a, unsigned blk, unsigned* s_cls, unsigned* s_cnt) {
+  CellRun r;
+  const size_t c0 = cell_run_first(blk);
+  int sum[CELL_RUN];
+  unsigned weight[CELL_RUN];
+  uint4 rgb[CELL_RUN];  // COLOR: the colour cells
+  TsdfDown down[CELL_RUN];
+#pragma unroll
+  for (int j = 0; j < CELL_RUN; ++j) {
+    cell_run_cell(c0, j, a.box, a.cells, a.voxel, r);
+    sum[j] = 0;
+    weight[j] = 0u;
+    rgb[j] = make_uint4(0u, 0u, 0u, 0u);
+    down[j] = TsdfDown{0u, 0u, 0, 0u, 0u, 0u};
+  }
+  cell_run_load(a.tsdf, c0, r, sum, weight);
+  cell_run_load_color<COLOR>(a.color, c0, r, rgb);
+  int cls[CELL_RUN];
+#pragma unroll
+  for (int j = 0; j < CELL_RUN; ++j) {
+    float z = 0.0f, dc = 0.0f;
+    unsigned pix = 0u;
+    if (COLOR) cls[j] = r.valid[j] ? map_carve_class_zdp(r.px[j], r.py[j], r.pz[j], a.view, 0, a.trunc, 0.0f, &z, &dc, &pix) : -1;
+    else cls[j] = r.valid[j] ? map_carve_class_zd(r.px[j], r.py[j], r.pz[j], a.view, 0, a.trunc, 0.0f, &z, &dc) : -1;
+    if (cls[j] == CARVE_FREE || cls[j] == CARVE_CONFIRMED) {
+      const bool confirmed = cls[j] == CARVE_CONFIRMED;
+      const int q = confirmed ? tsdf_quantum(dc, z, a.trunc) : TSDF_Q_ONE;
+      tsdf_down_add(down[j], confirmed, q, COLOR && confirmed ? a.bgr + (size_t)pix * 3 : nullptr);
+    }
+  }
+  if (!APPLY) cell_run_count_classes(cls, s_cls);  // uniform: the ballots see whole waves
+  unsigned n_upd = 0, n_cupd = 0, n_misfit = 0, n_weighted = 0, n_inside = 0, n_col = 0;
+#pragma unroll
+  for (int j = 0; j < CELL_RUN; ++j) {
+    if (!r.valid[j]) continue;
+    if (down[j].k) {
+      if (APPLY) {
+        tsdf_down_apply(sum[j], weight[j], down[j]);
+        n_upd += down[j].k;
+        if (COLOR) {
+          tsdf_down_color_apply(rgb[j].x, rgb[j].y, rgb[j].z, rgb[j].w, down[j]);
+          n_cupd += down[j].kc;
+        }
+      } else {
+        const bool fits = tsdf_down_fits(sum[j], weight[j], down[j]) &&
+                          (!COLOR || tsdf_down_color_fits(weight[j], rgb[j].x, rgb[j].y, rgb[j].z, rgb[j].w, down[j]));
+        n_misfit += fits ? 0u : 1u;
+      }
+    }
+    n_weighted += weight[j] > 0u;
+    n_inside += weight[j] > 0u && sum[j] < 0;
+    if (COLOR) n_col += rgb[j].w > 0u;
+  }
+  if (APPLY) {
+    cell_run_store(a.tsdf, c0, r, sum, weight);
+    cell_run_store_color<COLOR>(a.color, c0, r, rgb);
+  }
+  // the counters in TMU_*'s order, from TMU_UPDATES on
+  if (COLOR) cell_run_tally(s_cnt + TMU_UPDATES, n_upd, n_weighted, n_inside, n_misfit, n_cupd, n_col);
+  else cell_run_tally(s_cnt + TMU_UPDATES, n_upd, n_weighted, n_inside, n_misfit);
+}
+
+// Grid, job table, counters and ticket: k_tsdf_fuse_many's.  A job has two lines in the scratch, one per pass.
+// The check pass: the block that draws a job's last ticket writes the job's view_info and the check line as its info -- the single
+// call's refused info when there are misfits -- and the job's status into the results.
+// The apply pass: a block first reads its job's misfit count from the check pass's line (a uniform address; the kernel boundary on
+// the stream orders the read) and returns before it touches anything when the job is refused.  Otherwise it down-dates its cells,
+// and the job's last block overwrites the info with the apply line.  No block waits for another; no atomic touches a cell.
+template <bool APPLY>
+__global__ void __launch_bounds__(TSDF_MANY_THREADS) k_tsdf_unfuse_many(const TsdfManyUnfuseK a) {
+  __shared__ unsigned s_cls[CARVE_CLASSES];
+  __shared__ unsigned s_cnt[8];  // TMU_*
+  __shared__ unsigned s_last;
+  if (blockIdx.x >= a.total_blocks) return;
+  const int job = tsdf_many_find(a.n, blockIdx.x, [&](int j) { return a.jobs[j].first_block; });
+  unsigned* const check_line = a.lines + (size_t)job * (2 * TSDF_MANY_STRIDE);
+  if (APPLY && ((const u64*)check_line)[TMU_MISFITS] != 0) return;  // the job was refused: uniform over the block, before any barrier
+  const TsdfManyUnfuseJob J = a.jobs[job];  // a uniform address: scalar loads
+  const unsigned tid = threadIdx.x;
+  if (tid < CARVE_CLASSES) s_cls[tid] = 0;
+  if (tid < 8) s_cnt[tid] = 0;
+  __syncthreads();
+  const bool with_color = J.color != nullptr;
+  if (with_color) tmy_unfuse_block<true, APPLY>(J, blockIdx.x - J.first_block, s_cls, s_cnt);
+  else tmy_unfuse_block<false, APPLY>(J, blockIdx.x - J.first_block, s_cls, s_cnt);
+  __syncthreads();
+  unsigned* const line = check_line + (APPLY ? TSDF_MANY_STRIDE : 0);
+  u64* const info = (u64*)line;
+  if (tid >= TMU_UPDATES && tid <= TMU_COLORED && s_cnt[tid]) atomicAdd(&info[tid], (u64)s_cnt[tid]);
+  if (!APPLY && tid >= 16 && tid < 16 + CARVE_CLASSES && s_cls[tid - 16]) atomicAdd(&line[TMU_LINE_VINFO + tid - 16], s_cls[tid - 16]);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's counters have left this CU ...
+  __syncthreads();                                  // ... and so have every thread's of the block, before its ticket is drawn
+  if (tid == 0) s_last = __hip_atomic_fetch_add((tmy_gu32p)(line + TSDF_MANY_LINE_TICKET), 1u, TMY_RLX_AGENT) == J.blocks - 1u ? 1u : 0u;
+  __syncthreads();
+  if (!s_last || tid >= TMU_LINE + 4) return;
+  // the last block of the job to arrive in this pass: every block's counters are in the line
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (tid < TMU_LINE) {
+    unsigned w = __hip_atomic_load((tmy_gu32p)(line + tid), TMY_RLX_AGENT);
+    if (tid == 2 * TMU_CELLS) w = J.cells;  // revo_map_tsdf_unfuse_info.cells: below 2^32, its high word stays zero
+    if (tid < TMU_LINE_VINFO) {
+      if (J.info) J.info[tid] = w;
+      if (J.res) J.res[tid] = w;
+    } else if (!APPLY && J.vinfo) {
+      J.vinfo[tid - TMU_LINE_VINFO] = w;
+    }
+  } else if (!APPLY && J.res) {  // the status and the three zero words behind it; the apply pass runs only for REVO_OK
+    unsigned w = 0u;
+    if (tid == TMU_LINE) {
+      const unsigned lo = __hip_atomic_load((tmy_gu32p)(line + 2 * TMU_MISFITS), TMY_RLX_AGENT);
+      const unsigned hi = __hip_atomic_load((tmy_gu32p)(line + 2 * TMU_MISFITS + 1), TMY_RLX_AGENT);
+      w = (lo | hi) ? (unsigned)REVO_ERR_INVALID_ARG : (unsigned)REVO_OK;
+    }
+    J.res[TMU_LINE_VINFO + tid - TMU_LINE] = w;
+  }
+}
+
+extern "C" int revo_map_tsdf_unfuse_many(revo_map* m, int n_jobs, const revo_map_tsdf_unfuse_job* jobs, revo_map_tsdf_unfuse_result* results,
+                                         int device_out) {
+  if (!m || !jobs) return fail(REVO_ERR_INVALID_ARG, "null argument");
+  if (n_jobs < 1 || n_jobs > TSDF_MANY_MAX_JOBS) return fail(REVO_ERR_INVALID_ARG, "revo_map_tsdf_unfuse_many: n_jobs must be 1 .. 1024");
+  TRY(map_check_side(device_out, "device_out"));
+  const int dev = m->g.device;
+  if (results && device_out) {
+    TRY(map_check_aligned((uintptr_t)results, 16, "the device results are"));
+    if (!tmy_on_device(results, dev)) return fail(REVO_ERR_INVALID_ARG, "revo_map_tsdf_unfuse_many: the device results are not in device memory of the map's device");
+  }
+  std::vector<TsdfManyUnfuseJob> hj(n_jobs);
+  std::vector<std::pair<uintptr_t, size_t>> ranges;
+  ranges.reserve(2 * (size_t)n_jobs);
+  size_t total_blocks = 0;
+  for (int i = 0; i < n_jobs; ++i) {  // every job's own rules
+    const revo_map_tsdf_unfuse_job& j = jobs[i];
+    TsdfManyUnfuseJob& d = hj[i];
+    const std::string at = "revo_map_tsdf_unfuse_many: job " + std::to_string(i) + ": ";
+    revo_map* jm = nullptr;
+    TRY(tmy_job_map(m, j.map, at, &jm));
+    if (!j.tsdf) return fail(REVO_ERR_INVALID_ARG, at + "null volume");
+    if (j.reserved) return fail(REVO_ERR_INVALID_ARG, at + "a reserved word is not 0");
+    size_t cells = 0;
+    if (const char* why = map_df_box_check(&j.box, &cells)) return fail(REVO_ERR_INVALID_ARG, at + why);
+    TRY(map_check_aligned((uintptr_t)j.tsdf | (uintptr_t)j.color | (uintptr_t)j.info | (uintptr_t)j.view_info, 16, at + "a device output is"));
+    float tr = 0.0f;
+    if (const char* why = tsdf_unfuse_trunc(j.trunc, jm->voxel, &tr)) return fail(REVO_ERR_INVALID_ARG, at + why);
+    if (j.color) {
+      if (const char* why = tsdf_bgr_check(&j.view, j.bgr)) return fail(REVO_ERR_INVALID_ARG, at + why);
+    } else if (j.bgr) {
+      return fail(REVO_ERR_INVALID_ARG, at + "bgr goes with a colour volume");
+    }
+    TRY(tmy_view_check(m, &j.view, at, &d.view.v));
+    if (!tmy_on_device(j.tsdf, dev) || (j.color && !tmy_on_device(j.color, dev)) || (j.bgr && !tmy_on_device(j.bgr, dev)) || (j.info && !tmy_on_device(j.info, dev)) ||
+        (j.view_info && !tmy_on_device(j.view_info, dev)))
+      return fail(REVO_ERR_INVALID_ARG, at + "a volume, an image or a record is not in device memory of the map's device");
+    ranges.emplace_back((uintptr_t)j.tsdf, sizeof(revo_map_tsdf_cell) * cells);
+    if (j.color) ranges.emplace_back((uintptr_t)j.color, sizeof(revo_map_tsdf_color) * cells);
+    d.view.depth = j.view.depth;
+    d.bgr = j.color ? j.bgr : nullptr;
+    d.tsdf = (int2*)j.tsdf; d.color = (uint4*)j.color;
+    d.info = (unsigned*)j.info; d.vinfo = (unsigned*)j.view_info;
+    d.res = nullptr;
+    d.box = j.box;
+    d.cells = (unsigned)cells;
+    d.first_block = (unsigned)total_blocks; d.blocks = tsdf_many_blocks(cells);
+    d.trunc = tr; d.voxel = jm->voxel;
+    total_blocks += d.blocks;
+  }
+  if (tsdf_many_overlap(ranges)) return fail(REVO_ERR_INVALID_ARG, "revo_map_tsdf_unfuse_many: two volumes of the call share memory");
+  HIPCHECK(hipSetDevice(dev));
+  hipStream_t s = (hipStream_t)m->g.stream;
+  for (int i = 0; i < n_jobs; ++i) {  // the pyramids' planes: the tracker stream is ordered behind their builds
+    if (!jobs[i].view.kf) continue;
+    MapSource src;
+    TRY(revo_map_source_(const_cast<revo_pyr*>(jobs[i].view.kf), &src));
+    hj[i].view.depth = src.depth;
+    if (jobs[i].color) hj[i].bgr = src.bgr;
+  }
+  MapTsdfManyScratch& w = m->tsdfmany;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t total = up(sizeof(unsigned) * 2 * TSDF_MANY_STRIDE * n_jobs), res_bytes = sizeof(revo_map_tsdf_unfuse_result) * (size_t)n_jobs;
+  TRY(w.unfuse_jobs.reserve(n_jobs, s));  // waits until the previous call's upload has read the pinned rows
+  TRY(w.unfuse_work.reserve(total, s));
+  unsigned* d_res = (unsigned*)results;
+  if (results && !device_out) {
+    TRY(w.unfuse_out.reserve(res_bytes, s));
+    d_res = (unsigned*)w.unfuse_out.p;
+  }
+  if (d_res)
+    for (int i = 0; i < n_jobs; ++i) hj[i].res = d_res + (size_t)TMU_RES_WORDS * i;
+  memcpy(w.unfuse_jobs.h, hj.data(), sizeof(TsdfManyUnfuseJob) * n_jobs);
+  TRY(w.unfuse_jobs.upload(n_jobs, s));
+  TsdfManyUnfuseK a{};
+  a.jobs = w.unfuse_jobs.d; a.n = n_jobs;
+  a.total_blocks = (unsigned)total_blocks;
+  a.lines = (unsigned*)w.unfuse_work.p;
+  HIPCHECK(hipMemsetAsync(w.unfuse_work.p, 0, total, s));
+  hipLaunchKernelGGL(k_tsdf_unfuse_many<false>, dim3((unsigned)total_blocks), dim3(TSDF_MANY_THREADS), 0, s, a);
+  HIPCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_tsdf_unfuse_many<true>, dim3((unsigned)total_blocks), dim3(TSDF_MANY_THREADS), 0, s, a);
+  HIPCHECK(hipGetLastError());
+  if (results && !device_out) {
+    HIPCHECK(hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));  // the call's one wait
+  }
   return REVO_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "revo_multi.h"
 #include "revo_map.h"
 #include "revo_pose_host.h"
+#include "revo_surface_ring.h"
 
 namespace {
 struct Ref { void* set; int frame; double ts; };  // a frame of a step set
@@ -44,12 +45,39 @@ struct Stream {
   double info_kf_ts = 0.0;
 };
 // revo_vo_multi_attach_surface's per-stream state: the attachment, the last keyframe's report and the device record its fuse writes
+// A view a windowed surface holds, as it can be named again: device copies of the keyframe's level-0 depth plane and colour image
+// (allocated when the slot is first used; bgr stays NULL without a colour volume), the pose it was fused at, its time stamp.
+struct KeptView {
+  float* depth = nullptr;
+  uint8_t* bgr = nullptr;
+  float T[16] = {};
+  double ts = 0.0;
+};
 struct Surface {
   bool on = false, has_last = false;
   revo_vo_multi_surface s{};
   revo_vo_multi_surface_report last{};
   revo_map_carve_view_info* d_vinfo = nullptr;  // device, 32 bytes: the view info of the last fuse
+  // revo_vo_multi_surface_window: which views are held (revo_surface_ring.h), what names them again, and the device
+  // record the last eviction's job writes
+  SurfaceRing ring;
+  std::vector<KeptView> kept;                   // ring.slots() of them
+  revo_map_tsdf_unfuse_info* d_evict = nullptr; // device, 64 bytes
+  double evict_ts = 0.0;
+  bool evict_enqueued = false;                  // the last eviction's call was taken: d_evict holds (or will hold) its info
 };
+static_assert(sizeof(revo_vo_multi_surface_window_report) == 104 && offsetof(revo_vo_multi_surface_window_report, held) == 4 &&
+              offsetof(revo_vo_multi_surface_window_report, evictions) == 8 && offsetof(revo_vo_multi_surface_window_report, evicted_timestamp) == 16 &&
+              offsetof(revo_vo_multi_surface_window_report, evicted) == 24, "the window report is the documented layout");
+// The window's slots and its record go back; the ring is off.  hipFree waits for the work that may still read them.
+void window_free(Surface& f) {
+  for (KeptView& k : f.kept) { (void)hipFree(k.depth); (void)hipFree(k.bgr); }
+  f.kept.clear();
+  (void)hipFree(f.d_evict);
+  f.d_evict = nullptr;
+  f.ring.set(0);
+  f.evict_ts = 0.0; f.evict_enqueued = false;
+}
 static_assert(sizeof(revo_vo_multi_surface) == 120 && offsetof(revo_vo_multi_surface, trunc) == 32 && offsetof(revo_vo_multi_surface, tsdf) == 40 &&
               offsetof(revo_vo_multi_surface, track_prm) == 56 && offsetof(revo_vo_multi_surface, track_opts) == 88, "the surface record is the documented layout");
 static_assert(sizeof(revo_vo_multi_surface_report) == 408 && offsetof(revo_vo_multi_surface_report, T_fused) == 72 && offsetof(revo_vo_multi_surface_report, track) == 136 &&
@@ -109,7 +137,7 @@ extern "C" void revo_vo_multi_destroy(revo_vo_multi* m) {
     if (m->surf[s].on) revo_map_note_attach_(m->surf[s].s.map, m, s, 0);
   }
   revo_mdev_destroy_(m->dev);  // (synchronises the context's streams; the step sets go with it)
-  for (Surface& f : m->surf) (void)hipFree(f.d_vinfo);
+  for (Surface& f : m->surf) { (void)hipFree(f.d_vinfo); window_free(f); }
   revo_map_stage_destroy_(m->map_stage);
   revo_ctx_release_(m->ctx);
   delete m;
@@ -126,6 +154,7 @@ static void surface_detach(revo_vo_multi* m, int s) {
   if (!f.on) return;
   revo_map* old = f.s.map;
   f.on = false; f.has_last = false;
+  window_free(f);
   --m->n_surf;
   renote(m, s, old);
 }
@@ -191,7 +220,7 @@ extern "C" int revo_vo_multi_attach_map(revo_vo_multi* m, int s, revo_map* map) 
 extern "C" void revo_vo_multi_forget_map_(revo_vo_multi* m, int s, revo_map* map) {
   if (!stream_ok(m, s)) return;
   if (m->maps[s] == map) m->maps[s] = nullptr;
-  if (m->surf[s].on && m->surf[s].s.map == map) { m->surf[s].on = false; m->surf[s].has_last = false; --m->n_surf; }
+  if (m->surf[s].on && m->surf[s].s.map == map) { m->surf[s].on = false; m->surf[s].has_last = false; window_free(m->surf[s]); --m->n_surf; }
 }
 
 extern "C" int revo_vo_multi_attach_surface(revo_vo_multi* m, int s, const revo_vo_multi_surface* in) {
@@ -241,6 +270,91 @@ extern "C" int revo_vo_multi_surface_last(revo_vo_multi* m, int s, revo_vo_multi
   }
   *out = f.last;
   return REVO_OK;
+}
+
+extern "C" int revo_vo_multi_surface_window(revo_vo_multi* m, int s, int window) {
+  if (!stream_ok(m, s)) return fail(REVO_ERR_INVALID_ARG, "stream out of range");
+  Surface& f = m->surf[s];
+  if (!f.on) return fail(REVO_ERR_INVALID_ARG, "revo_vo_multi_surface_window: no surface is attached to the stream");
+  if (!SurfaceRing::valid(window)) return fail(REVO_ERR_INVALID_ARG, "revo_vo_multi_surface_window: window must be 0 (off) or 1 .. 1024 views");
+  window_free(f);
+  if (!window) return REVO_OK;
+  HIPCHECK(hipMalloc((void**)&f.d_evict, sizeof(revo_map_tsdf_unfuse_info)));
+  f.ring.set(window);
+  f.kept.resize((size_t)f.ring.slots());
+  return REVO_OK;
+}
+
+extern "C" int revo_vo_multi_surface_window_last(revo_vo_multi* m, int s, revo_vo_multi_surface_window_report* out) {
+  if (!stream_ok(m, s) || !out) return fail(REVO_ERR_INVALID_ARG, "bad argument");
+  Surface& f = m->surf[s];
+  if (!f.on || !f.ring.on()) return fail(REVO_ERR_INVALID_ARG, "no window report: no surface is attached to the stream or it has no window");
+  memset(out, 0, sizeof(*out));
+  out->window = f.ring.window; out->held = f.ring.held;
+  out->evictions = f.ring.evictions;
+  if (!f.ring.evictions) return REVO_OK;
+  out->evicted_timestamp = f.evict_ts;
+  out->evicted.status = REVO_ERR_INVALID_ARG;  // a call that was not taken took nothing out
+  if (f.evict_enqueued) {  // the record of that step's unfuse, behind it on the tracker stream
+    MapCtxGeom g;
+    const int rc = revo_map_ctx_geom_(m->ctx, &g);
+    if (rc) return rc;
+    HIPCHECK(hipStreamSynchronize((hipStream_t)g.stream));
+    HIPCHECK(hipMemcpy(&out->evicted.info, f.d_evict, sizeof(out->evicted.info), hipMemcpyDeviceToHost));
+    out->evicted.status = out->evicted.info.misfits ? REVO_ERR_INVALID_ARG : REVO_OK;
+  }
+  return REVO_OK;
+}
+
+// The windows of a step, behind its fuse on the tracker stream: every keyframe in `who` (streams whose keyframe was
+// fused) that has a window is kept -- device copies of its slot's level-0 depth plane and colour image, T_fused -- and every
+// stream that then holds more than its window has its oldest view taken out, all in one revo_map_tsdf_unfuse_many, as the raw view
+// of the kept copies.  Nothing waits and nothing fails the step: a keyframe that cannot be kept is not held, and an eviction
+// that the call or the device refuses forgets the view and leaves it in the volumes.
+static void windows_step(revo_vo_multi* m, const std::vector<int>& who) {
+  MapCtxGeom g;
+  if (revo_map_ctx_geom_(m->ctx, &g) != REVO_OK) return;
+  hipStream_t st = (hipStream_t)g.stream;
+  const size_t px = (size_t)g.w * (size_t)g.h;
+  std::vector<int> over;
+  for (int s : who) {
+    Surface& f = m->surf[s];
+    if (!f.ring.on()) continue;
+    MapSource src;
+    if (revo_map_source_(revo_mdev_keyframe_(m->dev, s), &src) != REVO_OK) continue;
+    KeptView& k = f.kept[(size_t)f.ring.next()];  // held only once its copies are enqueued
+    if (!k.depth && hipMalloc((void**)&k.depth, px * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); k.depth = nullptr; continue; }
+    if (f.s.color && !k.bgr && hipMalloc((void**)&k.bgr, px * 3) != hipSuccess) { (void)hipGetLastError(); k.bgr = nullptr; continue; }
+    if (hipMemcpyAsync(k.depth, src.depth, px * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        (f.s.color && hipMemcpyAsync(k.bgr, src.bgr, px * 3, hipMemcpyDeviceToDevice, st) != hipSuccess)) { (void)hipGetLastError(); continue; }
+    memcpy(k.T, f.last.T_fused, sizeof(k.T));
+    k.ts = f.last.timestamp;
+    (void)f.ring.push();
+    if (f.ring.over()) over.push_back(s);
+  }
+  if (over.empty()) return;
+  std::vector<revo_map_tsdf_unfuse_job> jobs(over.size());
+  for (size_t i = 0; i < over.size(); ++i) {
+    Surface& f = m->surf[over[i]];
+    const KeptView& k = f.kept[(size_t)f.ring.oldest()];
+    revo_map_tsdf_unfuse_job& j = jobs[i];
+    memset(&j, 0, sizeof(j));
+    j.map = f.s.map; j.box = f.s.box;
+    j.trunc = f.s.trunc;
+    j.tsdf = f.s.tsdf; j.color = f.s.color;
+    j.view.depth = k.depth;  // a raw view with the context's camera and depth range: the bytes of the pyramid view it was fused as
+    j.view.width = g.w; j.view.height = g.h;
+    memcpy(j.view.T_w_c, k.T, sizeof(j.view.T_w_c));
+    j.bgr = f.s.color ? k.bgr : nullptr;
+    j.info = f.d_evict;
+  }
+  const bool ok = revo_map_tsdf_unfuse_many(jobs[0].map, (int)jobs.size(), jobs.data(), nullptr, 1) == REVO_OK;
+  for (int s : over) {
+    Surface& f = m->surf[s];
+    f.evict_ts = f.kept[(size_t)f.ring.oldest()].ts;
+    f.evict_enqueued = ok;
+    (void)f.ring.evict();
+  }
 }
 
 // The promoted keyframes of a step whose streams have a surface, as the sequential driver handles each (vo.REVO): tracked against
@@ -327,10 +441,13 @@ static void surfaces_step(revo_vo_multi* m, const std::vector<MultiFrame>& promo
   }
   if (jobs.empty()) return;
   const bool ok = revo_map_tsdf_fuse_many(jobs[0].map, (int)jobs.size(), jobs.data()) == REVO_OK;
+  bool windows = false;
   for (int s : who) {
     revo_vo_multi_surface_report& r = m->surf[s].last;
     if (ok) { r.fused = 1; ++r.keyframes_fused; } else ++r.keyframes_skipped;
+    windows = windows || m->surf[s].ring.on();
   }
+  if (ok && windows) windows_step(m, who);  // without a window on any of them nothing more is enqueued
 }
 
 static int submit(revo_vo_multi* m, int n, const revo_stream_frame* frames, int depth_is_u16, double depth_scale_factor,

@@ -1185,10 +1185,11 @@ class TsdfUnfuseRefused(ValueError):
     """An unfuse that was refused (the library's REVO_ERR_INVALID_ARG for cells that do not FIT): nothing was changed.  misfits:
     how many cells; info: the dict of TSDF_UNFUSE_INFO_KEYS, the volumes as they stand."""
 
-    def __init__(self, misfits, info=None):
+    def __init__(self, misfits, info=None, counts=None):
         super().__init__("%d cells do not fit: a view that is not in them, a full weight, or sums no fuse can reach" % misfits)
         self.misfits = int(misfits)
         self.info = info
+        self.counts = counts  # one dict of CARVE_CLASSES counts per view: the fuse's, refused or not
 
 
 def tsdf_unfuse_records(cells, color, lo, voxel, views, trunc=None, bgr=None, chunk=1 << 20):
@@ -1239,7 +1240,7 @@ def tsdf_unfuse_records(cells, color, lo, voxel, views, trunc=None, bgr=None, ch
     if misfits:
         info = {"cells": int(cells.size), "updates": 0, "cells_weighted": int((w > 0).sum()), "cells_inside": int(((w > 0) & (s < 0)).sum()),
                 "misfits": misfits, "color_updates": 0, "cells_colored": 0 if color is None else int((cw > 0).sum())}
-        raise TsdfUnfuseRefused(misfits, info)
+        raise TsdfUnfuseRefused(misfits, info, counts)
     w1, s1 = np.where(hit, w1, w), np.where(hit, s1, s)
     out = np.zeros(cells.shape, TSDF_CELL_DTYPE)
     out["sum"], out["weight"] = s1.reshape(cells.shape), w1.reshape(cells.shape)
@@ -1254,6 +1255,31 @@ def tsdf_unfuse_records(cells, color, lo, voxel, views, trunc=None, bgr=None, ch
         cout["weight"] = c1.reshape(cells.shape)
         info["color_updates"], info["cells_colored"] = int(kc.sum()), int((c1 > 0).sum())
     return out, cout, info, counts
+
+
+def tsdf_unfuse_many_records(jobs):
+    """revo_map_tsdf_unfuse_many's contract without a GPU: per job, tsdf_unfuse_records for that job alone, with a
+    refusal captured as that job's result instead of raised -- every other job is applied all the same.  A job is a dict: cells,
+    lo, voxel, view (one view as tsdf_unfuse_records takes them) and optionally color with bgr (the view's image) and trunc.
+    -> one dict per job: cells and color (the inputs themselves for a refused job: no byte changed), info (the dict of
+    TSDF_UNFUSE_INFO_KEYS; a refused job's is the refusal's), counts (the view's CARVE_CLASSES counts, refused or not) and status
+    (0, or -1, the library's REVO_ERR_INVALID_ARG, for a refused job).  ValueError as the library's argument errors: the call as
+    a whole, before any job's result."""
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= 1024:
+        raise ValueError("1 .. 1024 jobs")
+    out = []
+    for job in jobs:
+        color, bgr = job.get("color"), job.get("bgr")
+        if color is None and bgr is not None:
+            raise ValueError("bgr goes with a colour volume")
+        args = (job["cells"], color, job["lo"], job["voxel"], [tuple(job["view"])], job.get("trunc"))
+        try:
+            cells, col, info, counts = tsdf_unfuse_records(*args, bgr=None if color is None else [bgr])
+            out.append({"cells": cells, "color": col, "info": info, "counts": counts[0], "status": 0})
+        except TsdfUnfuseRefused as e:
+            out.append({"cells": job["cells"], "color": color, "info": e.info, "counts": e.counts[0], "status": -1})
+    return out
 
 
 def tsdf_unfuse_file(path, views_dir, camera, zrange, depth_scale=5000.0, only=None):

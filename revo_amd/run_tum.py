@@ -54,6 +54,9 @@ revo_amd.mapfile surface-assemble` cuts boxes out of it).  --surface-store FILE.
 --surface-box (the sequential default), with --surface-trunc and --surface-min-weight as --surface takes them; FILE_<dataset>.ply is
 written per dataset, the sequential run's bytes.  --streams-surface-track tracks every keyframe against its stream's surface first,
 all loops in lockstep, and writes surface_poses_<dataset>.txt as --surface-track does.  An error without --streams or --map.
+--streams-surface-window N (with --streams-surface) keeps only the last N keyframes (1 .. 1024) in every dataset's surface
+(vo.MultiREVO's surface window): the step keeps device copies of each fused keyframe's images and takes the oldest
+keyframe out again, all streams in one batched unfuse and without a wait; the mesh written is that of the last N keyframes.
 --surface-views DIR (with --surface) ray-casts the finished surface from the estimated pose of every keyframe, or with
 --surface-views-every K of every K-th tracked frame, on the GPU (api.SurfaceVolume.raycast, DESIGN 28: depth and colour from the
 sign change of the fused field, sub-voxel accurate and without holes) and writes the TUM-layout data set that --map-views writes
@@ -74,7 +77,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-window N] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-window N] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--streams-surface-window N] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -270,12 +273,28 @@ def main(argv=None):
         if "--streams-surface" not in argv:
             print("--streams-surface-track tracks the keyframes against their stream's TSDF surface: it needs --streams-surface FILE.ply")
             return 2
+    ssurface_window = 0  # vo.MultiREVO's surface window: every dataset's surface holds its last N keyframes only
+    if "--streams-surface-window" in argv:
+        i = argv.index("--streams-surface-window")
+        try:
+            ssurface_window = int(argv[i + 1])
+        except (IndexError, ValueError):
+            ssurface_window = 0
+        argv = argv[:i] + argv[i + 2:]
+        if not 1 <= ssurface_window <= 1024:
+            print("--streams-surface-window needs a number of keyframes, 1 .. 1024")
+            return 2
+        if "--streams-surface" not in argv:
+            print("--streams-surface-window bounds every stream's TSDF surface: it needs --streams-surface FILE.ply")
+            return 2
     if "--streams-surface" in argv:
         i = argv.index("--streams-surface")
         if i + 1 >= len(argv) or argv[i + 1].startswith("--"):
             print("--streams-surface needs a file name")
             return 2
         ssurface = {"file": argv[i + 1]}
+        if ssurface_window:
+            ssurface["window"] = ssurface_window
         argv = argv[:i] + argv[i + 2:]
         if "--streams" not in argv:
             print("--streams-surface gives every dataset of a multi-stream run its surface: it needs --streams N (the sequential driver has --surface)")
@@ -603,6 +622,8 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
     if ssurface is not None:  # the box is decided here and does not move: voxel indices of each dataset's first camera frame
         box = ssurface.get("box", (-128, -128, -32, 256, 256, 256))
         surface = dict(lo=box[:3], n=box[3:], trunc=ssurface.get("trunc"), color=True)
+        if ssurface.get("window"):
+            surface["window"] = ssurface["window"]
     drv = vo.MultiREVO(pyr_settings, streams, trk_settings, device=device, depth_scale_factor=io["depth_scale_factor"],
                        exact_sums=exact_sums, map_voxel=map_voxel, map_dense=bool(sysd["do_generate_dense_pcl"]),
                        pair_info=covariances, surface=surface, surface_track=True if ssurface_track else None)
@@ -627,6 +648,9 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
             _save_esdf(r.map, esdf, name, True)
             if r.surface is not None:
                 _save_surface(r.surface, r, ssurface, name, True)
+                if ssurface.get("window"):
+                    print("surface window: %d keyframes held, %d evicted (%d refused and left in the volumes)"
+                          % (r.surface.views, r.surface_evictions, r.surface_evictions_refused))
                 if ssurface_track:
                     _save_surface_tracks(r, name)
             if views_dir is not None:

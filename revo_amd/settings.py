@@ -501,6 +501,22 @@ class MapTsdfTrackResult(C.Structure):
 assert (C.sizeof(MapTsdfFuseJob), C.sizeof(MapTsdfTrackJob), C.sizeof(MapTsdfTrackResult)) == (200, 200, 288)
 
 
+class MapTsdfUnfuseJob(C.Structure):
+    """revo_map_tsdf_unfuse_job (include/revo_hip.h), 192 bytes: one (volume, view) of revo_map_tsdf_unfuse_many -- MapTsdfFuseJob's
+    members with the unfuse's meaning: trunc is what the view was fused with, info a revo_map_tsdf_unfuse_info on the device."""
+    _fields_ = [("map", C.c_void_p), ("box", MapDfBox), ("trunc", C.c_float), ("reserved", C.c_uint32), ("tsdf", C.c_void_p), ("color", C.c_void_p),
+                ("view", MapCarveView), ("bgr", C.c_void_p), ("info", C.c_void_p), ("view_info", C.c_void_p)]
+
+
+class MapTsdfUnfuseResult(C.Structure):
+    """revo_map_tsdf_unfuse_result (include/revo_hip.h), 80 bytes: a job's info and its status -- 0, or -1 (REVO_ERR_INVALID_ARG) for a
+    job that had a misfit and changed nothing."""
+    _fields_ = [("info", MapTsdfUnfuseInfo), ("status", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+assert (C.sizeof(MapTsdfUnfuseJob), C.sizeof(MapTsdfUnfuseResult)) == (192, 80)
+
+
 class MultiSurface(C.Structure):
     """revo_vo_multi_surface (include/revo_hip.h), 120 bytes: the surface of one stream of revo_vo_multi -- the map that gives the voxel
     edge, the box, trunc (0: 4 voxel edges), whether each keyframe is tracked before it is fused, the caller-owned device volumes
@@ -517,6 +533,16 @@ class MultiSurfaceReport(C.Structure):
 
 
 assert (C.sizeof(MultiSurface), C.sizeof(MultiSurfaceReport)) == (120, 408)
+
+
+class MultiSurfaceWindowReport(C.Structure):
+    """revo_vo_multi_surface_window_report (include/revo_hip.h), 104 bytes: a stream's surface window as it stands -- its size, the views
+    held, the evictions so far, and the last eviction's keyframe time stamp and result (status -1: refused, the view stayed in the
+    volumes and was forgotten)."""
+    _fields_ = [("window", C.c_int32), ("held", C.c_int32), ("evictions", C.c_uint64), ("evicted_timestamp", C.c_double), ("evicted", MapTsdfUnfuseResult)]
+
+
+assert C.sizeof(MultiSurfaceWindowReport) == 104
 
 
 class PairIn(C.Structure):

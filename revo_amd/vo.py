@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib, api
 from ._lib import check, f32p, u16p, u8p, vp
-from .settings import MapTsdfTrackInfo, MultiSurface, MultiSurfaceReport, PairInfo, StreamFrame, StreamResult, TrackerSettings
+from .settings import MapTsdfTrackInfo, MultiSurface, MultiSurfaceReport, MultiSurfaceWindowReport, PairInfo, StreamFrame, StreamResult, TrackerSettings
 
 
 class REVO:
@@ -284,7 +284,9 @@ def tum_lines(poses):
 class SequenceResult(list):
     """One sequence of MultiREVO.run: [(4x4 pose, new_keyframe)] in frame order, `poses` [(timestamp, 4x4)], tum_lines(),
     `map`: its api.VoxelMap (MultiREVO(map_voxel=...)) or None, and `surface`, `surface_tracks`, `surface_skipped`: its
-    api.SurfaceVolume (MultiREVO(surface=...)) with what REVO.surface_tracks and REVO.surface_skipped hold for the sequence."""
+    api.SurfaceVolume (MultiREVO(surface=...)) with what REVO.surface_tracks and REVO.surface_skipped hold for the sequence.  With
+    MultiREVO(surface=dict(..., window=N)) surface.views is the number of views the window holds, and surface_evictions and
+    surface_evictions_refused count the views that left it and those of them the device refused to take out."""
 
     def __init__(self):
         super().__init__()
@@ -295,6 +297,10 @@ class SequenceResult(list):
         self.surface = None
         self.surface_tracks = []
         self.surface_skipped = 0
+        # MultiREVO(surface=dict(..., window=N)): the views that left the window, and those of them the device refused to take out
+        # (such a view was forgotten and stayed in the volumes)
+        self.surface_evictions = 0
+        self.surface_evictions_refused = 0
 
     def tum_lines(self):
         return tum_lines(self.poses)
@@ -346,8 +352,9 @@ class MultiREVO:
         self.map_dense = bool(map_dense)
         self.map_max_voxels = int(map_max_voxels)
         self._maps = [None] * self.n_streams
-        # run(): one api.SurfaceVolume per sequence on its map (surface: dict(lo=, n=[, trunc=, color=])), fed by the step's batched
-        # track and fuse of the keyframes its stream promotes; surface_track: None | True | dict, as REVO takes it
+        # run(): one api.SurfaceVolume per sequence on its map (surface: dict(lo=, n=[, trunc=, color=, window=])), fed by the step's batched
+        # track and fuse of the keyframes its stream promotes; surface_track: None | True | dict, as REVO takes it.
+        # window=N: each surface holds its stream's last N fused keyframes (attach_surface's window)
         if surface is not None and map_voxel is None:
             raise ValueError("surface= needs map_voxel: a sequence's surface lives on its map")
         if surface_track is not None and surface_track is not False and surface is None:
@@ -371,15 +378,24 @@ class MultiREVO:
         check(_lib.lib().revo_vo_multi_attach_map(self._h, int(stream), voxelMap._h if voxelMap is not None else None))
         self._maps[int(stream)] = voxelMap
 
-    def attach_surface(self, stream, surface, track=None, log=None):
+    def attach_surface(self, stream, surface, track=None, log=None, window=None):
         """Every keyframe `stream` promotes from now on is fused into `surface` (an api.SurfaceVolume on a map of this handle's
         context; None detaches; reset() detaches), in the step's one batched launch, as REVO(surface=) does it for one sequence.
         track: None | True | dict of SurfaceVolume.track's options (REVO's surface_track) -- the keyframe is tracked against the
         surface as it stands first, all streams' loops in lockstep, and fused at the refined pose where the loop converged.
         log: the object whose surface_tracks (REVO.surface_tracks' tuples) and surface_skipped are kept current (default: the
-        surface itself gets both attributes).  The surface's `views` and per-view counts are kept current too."""
+        surface itself gets both attributes).  The surface's `views` and per-view counts are kept current too.
+        window: None | N >= 1 -- the surface holds the stream's last N fused keyframes (revo_vo_multi_surface_window): the
+        step keeps device copies of each fused keyframe's depth and colour image and takes the oldest view out again, all streams'
+        evictions in one batched unfuse, without a wait.  `views` is then the number of views held; log.surface_evictions and
+        log.surface_evictions_refused count the views that left and those the device refused (forgotten, still in the volumes).
+        The ring lives in the driver: an api.SurfaceWindow is refused (two rings would disagree) -- pass a SurfaceVolume and window=."""
         from . import mapfile
         s = int(stream)
+        if isinstance(surface, api.SurfaceWindow):
+            raise ValueError("MultiREVO keeps the window itself: attach an api.SurfaceVolume with window=N, not an api.SurfaceWindow")
+        if window is not None and not 1 <= int(window) <= 1024:
+            raise ValueError("window= is None or 1 .. 1024 views")
         if surface is None:
             check(_lib.lib().revo_vo_multi_attach_surface(self._h, s, None))
             self._surfaces[s] = None
@@ -411,14 +427,24 @@ class MultiREVO:
         import torch
         torch.cuda.current_stream(surface.d_tsdf.device).synchronize()  # the volumes' earlier use is over before the tracker stream writes
         check(_lib.lib().revo_vo_multi_attach_surface(self._h, s, C.byref(rec)))
+        if window is not None:
+            check(_lib.lib().revo_vo_multi_surface_window(self._h, s, int(window)))
         log = surface if log is None else log
         log.surface_tracks, log.surface_skipped = [], 0
-        self._surfaces[s] = [surface, log, self.nKeyFrames(s), track is not None]
+        log.surface_evictions, log.surface_evictions_refused = 0, 0
+        self._surfaces[s] = [surface, log, self.nKeyFrames(s), track is not None, window is not None]
 
     def surface_last(self, stream):
         """The MultiSurfaceReport of the stream's last keyframe since its surface was attached; waits for that step's fuse."""
         rep = MultiSurfaceReport()
         check(_lib.lib().revo_vo_multi_surface_last(self._h, int(stream), C.byref(rep)))
+        return rep
+
+    def surface_window_last(self, stream):
+        """The MultiSurfaceWindowReport of the stream's surface window: the views held, the evictions so far and the last one's
+        keyframe time stamp and result; waits for that step's work."""
+        rep = MultiSurfaceWindowReport()
+        check(_lib.lib().revo_vo_multi_surface_window_last(self._h, int(stream), C.byref(rep)))
         return rep
 
     def _poll_surfaces(self):
@@ -430,7 +456,7 @@ class MultiREVO:
             if n == att[2]:
                 continue
             att[2] = n
-            surface, log, _, tracking = att
+            surface, log, _, tracking, windowed = att
             rep = self.surface_last(s)
             as44 = lambda a: np.array(list(a), np.float32).reshape(4, 4).T.copy()  # noqa: E731
             if tracking:
@@ -443,6 +469,13 @@ class MultiREVO:
                 row = [vi.outside, vi.unknown, vi.free_space, vi.confirmed, vi.occluded, vi.edge, 0, 0]
                 surface._vinfo.append(torch.tensor(np.array(row, np.uint32).view(np.int32), dtype=torch.int32, device=surface.d_tsdf.device))
                 surface.views += 1
+            if windowed:  # a step evicts at most one view per stream: the oldest row leaves with it, refused or not
+                win = self.surface_window_last(s)
+                if int(win.evictions) > log.surface_evictions:
+                    log.surface_evictions = int(win.evictions)
+                    log.surface_evictions_refused += 1 if win.evicted.status else 0
+                    del surface._vinfo[0]
+                surface.views = int(win.held)
 
     def __del__(self):
         try:
@@ -560,8 +593,9 @@ class MultiREVO:
                                                     max_voxels=self.map_max_voxels)
                         self.attach_map(s, out[nxt].map)
                         if self.surface is not None:
-                            out[nxt].surface = api.SurfaceVolume(out[nxt].map, **self.surface)
-                            self.attach_surface(s, out[nxt].surface, self.surface_track, log=out[nxt])
+                            box = {k: v for k, v in self.surface.items() if k != "window"}
+                            out[nxt].surface = api.SurfaceVolume(out[nxt].map, **box)
+                            self.attach_surface(s, out[nxt].surface, self.surface_track, log=out[nxt], window=self.surface.get("window"))
                     nxt += 1
 
         def feed():  # one submit: the next frame of every stream with room in its queue
