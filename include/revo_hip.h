@@ -1997,6 +1997,38 @@ typedef struct revo_map_tsdf_track_result {  /* 288 bytes, no padding holes */
 int revo_map_tsdf_track_many(revo_map* m, int n_jobs, const revo_map_tsdf_track_job* jobs, const revo_map_align_opts* opt,
                              revo_map_tsdf_track_result* results, int32_t* rounds);
 
+/* One ray-cast job: revo_map_tsdf_raycast's arguments for one volume, with device_tsdf = 1 and device_out = 1.  The
+ * volumes are only read, so, unlike the fuse, several jobs may name one volume: that is how a caller gets more than 64 views
+ * of a volume in one call. */
+typedef struct revo_map_tsdf_ray_job {   /* 120 bytes, no padding holes */
+  revo_map* map;                         /* offset   0: gives the voxel edge; of m's context; NULL: m                        */
+  revo_map_df_box box;                   /* offset   8: the box rules of revo_map_distance_field                             */
+  revo_map_tsdf_ray_params prm;          /* offset  32: by value; all zero: the defaults                                     */
+  const revo_map_tsdf_cell* tsdf;        /* offset  48: device, 16-byte aligned: n[0]*n[1]*n[2] cells                        */
+  const revo_map_tsdf_color* color;      /* offset  56: device, 16-byte aligned, or NULL: no colour is read                  */
+  int32_t n_views;                       /* offset  64: 1 .. 64                                                              */
+  uint32_t reserved;                     /* offset  68: zero                                                                 */
+  const revo_map_view* views;            /* offset  72: host array of n_views views, revo_map_tsdf_raycast's view rules      */
+  float* const* depth;                   /* offset  80: host array of n_views device pointers, each 16-byte aligned           */
+  float* const* normal;                  /* offset  88: likewise, or NULL: no normal images                                  */
+  uint8_t* const* bgr;                   /* offset  96: likewise, or NULL: no colour images; needs color                     */
+  uint32_t* hits;                        /* offset 104: device, 16-byte aligned, n_views words, or NULL                      */
+  revo_map_tsdf_ray_info* info;          /* offset 112: device, 16-byte aligned, one record for the job, or NULL             */
+} revo_map_tsdf_ray_job;
+/* n_jobs (1 .. 1024) ray-cast jobs with at most 4096 views between them, on m's context's tracker stream: one memset, one launch
+ * that marks the block masks of the call's distinct volumes, one launch that marches every view of every job, and one small
+ * launch that hands every job its counters.  The call only enqueues and never waits.  After it every job's images, hits and info
+ * hold exactly the bytes revo_map_tsdf_raycast leaves for that job alone (device_tsdf = 1, device_out = 1); neither the order of
+ * the jobs nor the other jobs show in them.  The block mask is built once per distinct (tsdf pointer, box, effective min_weight)
+ * of the call, not once per job.  REVO_MAP_TSDF_RAY_MASK=0 selects the plain march, as in the single call.
+ * REVO_ERR_INVALID_ARG, the call refused as a whole before anything is enqueued and with no byte written: NULL m or jobs; n_jobs
+ * outside 1 .. 1024; more than 4096 views; in any job: a map of another context, a NULL tsdf, views or depth, n_views outside
+ * 1 .. 64, a box, view, parameter or alignment rule of the single call broken, a NULL depth[i], normal[i] or bgr[i] of a given
+ * array, bgr without color, a reserved word that is not 0, a volume, an image or a record that is not in device memory of m's
+ * device; two outputs (images, hits, info, of any two views or jobs) whose byte ranges overlap; an output that overlaps a volume
+ * of the call. */
+int revo_map_tsdf_raycast_many(revo_map* m, int n_jobs, const revo_map_tsdf_ray_job* jobs);
+
 /* A surface for a stream of revo_vo_multi: the caller-owned device volumes of a box, fused from every keyframe the stream
  * promotes from now on, in the step, right behind the batched map integration of the step's promoted keyframes. */
 typedef struct revo_vo_multi_surface {  /* 120 bytes, no padding holes */

@@ -9,7 +9,7 @@ import re
 
 from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo,
                        PairResult, PairInfo, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo,
-                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MapTsdfUnfuseJob, MultiSurfaceWindowReport, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
+                       MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapDfBox, MapDfAlignInfo, MapObserveParams, MapGainParams, MapTsdfParams, MapTsdfRayParams, MapTsdfTrackParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfFuseJob, MapTsdfTrackJob, MapTsdfTrackResult, MapTsdfUnfuseJob, MapTsdfRayJob, MultiSurfaceWindowReport, MultiSurface, MultiSurfaceReport, MapView, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # REVO_HIP_SO: an alternative build of the same library (profiling builds under profiles/); never a fallback
@@ -202,6 +202,7 @@ def lib():
                                        C.POINTER(MapTsdfUnfuseInfo), vp]
     L.revo_map_tsdf_fuse_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfFuseJob)]
     L.revo_map_tsdf_unfuse_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfUnfuseJob), vp, C.c_int]
+    L.revo_map_tsdf_raycast_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfRayJob)]
     L.revo_map_tsdf_track_eval_many.argtypes = [vp, C.c_int, C.POINTER(MapTsdfTrackJob), vp, C.c_int]
     L.revo_vo_multi_attach_surface.argtypes = [vp, C.c_int, C.POINTER(MultiSurface)]
     L.revo_vo_multi_surface_last.argtypes = [vp, C.c_int, C.POINTER(MultiSurfaceReport)]

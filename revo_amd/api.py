@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RevoError, check, f32p, i32p, u8p, u16p, vp
-from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfUnfuseJob, MapTsdfUnfuseResult, MapTsdfTrackJob, MapTsdfTrackResult,
+from .settings import (ImgPyramidSettings, OptimizerSettings, TrackerSettings, ResidualInfo, PairResult, PairInfo, PairIn, MapInfo, MapView, MapAlignParams, MapAlignInfo, MapAlignOpts, MapNormalsParams, MapPlaneInfo, MapPoseInfo, MapCarveView, MapCarveParams, MapCarveInfo, MapCarveViewInfo, MapRayParams, MapRayInfo, MapDfBox, MapDfInfo, MapDfAlignInfo, MapPlanSeed, MapPlanInfo, MapPlanPath, MapObserveParams, MapObserveInfo, MapKnownInfo, MapGainParams, MapGain, MapGainInfo, MapTsdfParams, MapTsdfInfo, MapTsdfColorInfo, MapMeshInfo, MapTsdfRayParams, MapTsdfTrackInfo, MapTsdfShiftInfo, MapTsdfRefillInfo, MapTsdfUnfuseInfo, MapTsdfTrackParams, MapTsdfRayInfo, MapTsdfFuseJob, MapTsdfUnfuseJob, MapTsdfRayJob, MapTsdfUnfuseResult, MapTsdfTrackJob, MapTsdfTrackResult,
                        MAX_LEVELS, PLANE_GRAY, PLANE_DEPTH, PLANE_EDGES, PLANE_EDGES_ORIG, PLANE_DT,
                        PLANE_GRADTABLE, PLANE_EDGES3D, PLANE_HIST, PLANE_EDGES3D_TILED, TRACKER_STATE_OK, TRACKER_STATE_NEW_KF)
 
@@ -1411,6 +1411,61 @@ class VoxelMap:
         if wait:
             self.sync()
 
+    def surface_raycast_many_into(self, jobs, wait=True):
+        """The ray casts of many (volume, views) jobs in one call (revo_map_tsdf_raycast_many): every job's tensors hold
+        afterwards what surface_raycast_into leaves for that job alone.  A job is a dict: d_tsdf (int32 device tensor [n0, n1, n2, 2]),
+        lo, poses (one 4x4 or 1 .. 64 of them), d_depth (float32 [n, h, w], or [h, w] for one pose), and optionally camera, size,
+        zrange, step, min_weight, max_steps, d_color (int32 [n0, n1, n2, 4], needed for d_bgr), d_normals, d_bgr, d_hits (n 32-bit
+        entries), d_info (64 bytes), map (the VoxelMap that gives the job's voxel edge; default: this one).  The volumes are only
+        read, so jobs may share one: several jobs on a volume are more than 64 views of it in one call, and its block mask is built
+        once.  1 .. 1024 jobs with at most 4096 views between them, everything on the device; the call is only enqueued on the
+        context's tracker stream: wait=False returns at once."""
+        import torch
+        jobs = list(jobs)
+        arr = (MapTsdfRayJob * max(len(jobs), 1))()
+        keep = []
+        for j, job in zip(arr, jobs):
+            m = self._job_map(job)
+            d_tsdf, d_color, d_depth = job["d_tsdf"], job.get("d_color"), job["d_depth"]
+            d_normals, d_bgr, d_hits, d_info = job.get("d_normals"), job.get("d_bgr"), job.get("d_hits"), job.get("d_info")
+            self._surface_tensors(d_tsdf, d_color, "d_tsdf")
+            if d_bgr is not None and d_color is None:
+                raise ValueError("d_bgr needs the colour volume d_color")
+            views, n, single = m._surface_views(job["poses"], job.get("camera"), job.get("size"), job.get("zrange"))
+            h, w = views[0].height, views[0].width
+            shape = (h, w) if single else (n, h, w)
+            if tuple(d_depth.shape) != shape or any(t_ is not None and tuple(t_.shape) != shape + (3,) for t_ in (d_normals, d_bgr)):
+                raise ValueError("output tensors do not match the views")
+            if str(d_depth.dtype) != "torch.float32" or (d_normals is not None and str(d_normals.dtype) != "torch.float32") or \
+                    (d_bgr is not None and str(d_bgr.dtype) != "torch.uint8"):
+                raise ValueError("d_depth and d_normals must be float32 and d_bgr uint8")
+            for t_ in (d_depth, d_normals, d_bgr, d_hits, d_info):
+                if t_ is not None and not (t_.is_contiguous() and t_.is_cuda):
+                    raise ValueError("the tensors must be contiguous device tensors")
+            if d_hits is not None and (d_hits.numel() != n or d_hits.element_size() != 4):
+                raise ValueError("d_hits needs n 32-bit entries")
+            if d_info is not None and d_info.numel() * d_info.element_size() != 64:
+                raise ValueError("d_info needs 64 bytes")
+            ptrs = lambda t_, per: (vp * n)(*[t_.data_ptr() + per * h * w * i for i in range(n)]) if t_ is not None else None  # noqa: E731
+            rows = (ptrs(d_depth, 4), ptrs(d_normals, 12), ptrs(d_bgr, 3))
+            j.map = m._h
+            j.box = m._df_box(job["lo"], tuple(d_tsdf.shape[:3]), 0, 1)
+            j.prm = self._tsdf_ray_params(job.get("step"), job.get("min_weight", 1), job.get("max_steps", 4096))
+            j.tsdf = d_tsdf.data_ptr()
+            j.color = d_color.data_ptr() if d_color is not None else None
+            j.n_views = n
+            j.views = C.addressof(views)
+            j.depth, j.normal, j.bgr = (C.addressof(r) if r is not None else None for r in rows)
+            j.hits = d_hits.data_ptr() if d_hits is not None else None
+            j.info = d_info.data_ptr() if d_info is not None else None
+            keep.append((views, rows, job))
+        if jobs:
+            torch.cuda.current_stream(jobs[0]["d_tsdf"].device).synchronize()  # the tensors' earlier use is over before the tracker stream touches them
+        check(_lib.lib().revo_map_tsdf_raycast_many(self._h, len(jobs), arr))
+        if wait:
+            self.sync()
+        del keep
+
     # -- tracking a depth frame against the surface (revo_map_tsdf_track_eval / revo_map_tsdf_track, DESIGN 29)
     def _surface_track_args(self, tsdf, lo, trunc, frame, max_dist, stride, min_weight, centre):
         """(box, volume pointer, its side, the frame's MapCarveView array, its side, trunc, params, what keeps the memory alive) of a
@@ -2724,6 +2779,72 @@ def fuse_surfaces(pairs, wait=False):
         raise e
 
 
+def raycast_surfaces(entries, step=None, min_weight=1, max_steps=4096, normals=True, colors=True, device=False):
+    """[(surface, poses[, camera, size, zrange]), ...] -- views of the surfaces of as many running sequences, all in batched calls
+    (VoxelMap.surface_raycast_many_into) -> per entry what SurfaceVolume.raycast(poses, camera, size, ...) returns for
+    that surface alone, byte for byte (device=True: the torch device tensors, valid behind the map's sync()).  A surface is a
+    SurfaceVolume or a SurfaceWindow; the surfaces' maps share one context.  An entry with more than 64 poses is split into jobs
+    that share its volume, and its info is the sum over them; a list of more than 4096 views, or 1024 jobs, goes in several calls.
+    The calls are only enqueued behind the surfaces' integrations: no wait is needed between a fuse and the views."""
+    import torch
+    from . import mapfile
+    entries = [tuple(e) for e in entries]
+    if not entries:
+        return []
+    plans, jobs = [], []
+    for surf, poses, *rest in entries:
+        if isinstance(surf, FollowingSurface):
+            raise NotImplementedError("a FollowingSurface is not ray-cast in a batch: its box moves and part of its surface lies in its store")
+        camera, size, zrange = (list(rest) + [None, None, None])[:3]
+        T = np.asarray(poses, np.float32)
+        single = T.ndim == 2
+        T = np.ascontiguousarray(T.reshape(-1, 4, 4))
+        if len(T) < 1:
+            raise ValueError("an entry needs at least one pose")
+        col = bool(colors) and surf.d_color is not None
+        cam = surf.map._gain_camera(camera, size, zrange, 1)
+        h, w = int(cam.height), int(cam.width)
+        n, dev = len(T), surf.d_tsdf.device
+        if n > 1 and (h * w) % 16:  # every view's part of a stacked tensor is 16-byte aligned
+            raise ValueError("several device views at once need a pixel count that is a multiple of 16")
+        d_depth = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+        d_nrm = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if normals else None
+        d_bgr = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev) if col else None
+        parts = [(a, min(a + 64, n)) for a in range(0, n, 64)]
+        d_hits = torch.zeros(64 * len(parts), dtype=torch.int32, device=dev)  # a job's hit words start 16-byte aligned
+        d_info = torch.zeros((len(parts), 8), dtype=torch.int64, device=dev)
+        for k, (a, b) in enumerate(parts):
+            jobs.append(dict(map=surf.map, d_tsdf=surf.d_tsdf, d_color=surf.d_color if col else None, lo=surf.lo, poses=T[a:b], camera=camera, size=size,
+                             zrange=zrange, step=step, min_weight=min_weight, max_steps=max_steps, d_depth=d_depth[a:b],
+                             d_normals=None if d_nrm is None else d_nrm[a:b], d_bgr=None if d_bgr is None else d_bgr[a:b],
+                             d_hits=d_hits[64 * k:64 * k + (b - a)], d_info=d_info[k]))
+        plans.append((single, parts, d_depth, d_nrm, d_bgr, d_hits, d_info))
+    call, views = [], 0
+    m = entries[0][0].map
+    for job in jobs + [None]:  # calls of at most 1024 jobs and 4096 views
+        if call and (job is None or len(call) == 1024 or views + len(job["poses"]) > 4096):
+            m.surface_raycast_many_into(call, wait=False)
+            call, views = [], 0
+        if job is not None:
+            call.append(job)
+            views += len(job["poses"])
+    if not device or any(len(p[1]) > 1 for p in plans):
+        m.sync()  # the views are done before their counters are joined or anything is read
+    out = []
+    for single, parts, d_depth, d_nrm, d_bgr, d_hits, d_info in plans:
+        d_hits = d_hits[:parts[0][1]] if len(parts) == 1 else torch.cat([d_hits[64 * k:64 * k + (b - a)] for k, (a, b) in enumerate(parts)])
+        d_info = d_info[0] if len(parts) == 1 else d_info.sum(dim=0)
+        pick = (lambda t_: None if t_ is None else t_[0]) if single else (lambda t_: t_)
+        if device:
+            out.append({"depth": pick(d_depth), "normals": pick(d_nrm), "bgr": pick(d_bgr), "hits": d_hits, "info": d_info})
+            continue
+        host = lambda t_: None if t_ is None else (t_.cpu().numpy()[0] if single else list(t_.cpu().numpy()))  # noqa: E731
+        hits, info = d_hits.cpu().numpy(), d_info.cpu().numpy()
+        out.append({"depth": host(d_depth), "normals": host(d_nrm), "bgr": host(d_bgr), "hits": int(hits[0]) if single else [int(x) for x in hits],
+                    "info": {k: int(info[i]) for i, k in enumerate(mapfile.TSDF_RAY_INFO_KEYS)}})
+    return out
+
+
 def _unfuse_jobs(entries):
     """-> (the jobs of one unfuse_many_into, the place of each view in its window or None) for [(surface, view), ...]."""
     import torch
@@ -3211,6 +3332,10 @@ class MapWindow:
 
     def surface_raycast_into(self, *args, **kw):
         return self.map.surface_raycast_into(*args, **kw)
+
+    def surface_raycast_many_into(self, *args, **kw):
+        """The inner map's surface_raycast_many_into: the window's voxels play no part."""
+        return self.map.surface_raycast_many_into(*args, **kw)
 
     def surface_track_eval(self, *args, **kw):
         """The inner map's surface_track_eval: a depth frame against a TSDF volume (the window's voxels play no part)."""

@@ -314,6 +314,19 @@ struct MapTsdfManyScratch {
   DevBuf unfuse_work, unfuse_out;
 };
 
+// revo_map_tsdf_raycast_many (revo_map_tsdf_ray_many.hip): the job, view and distinct-volume tables of a call, and its
+// scratch: the jobs' counter lines and tickets, the views' hit words and the block masks, cleared by one memset.  Only this call
+// goes through them.
+struct TsdfRayManyJob;   // revo_map_tsdf_ray_many.hip: one job of a batched ray cast
+struct TsdfRayManyView;  // ... one view row of it, with its job
+struct TsdfRayManyVol;   // ... one distinct volume of its mask launch
+struct MapTsdfRayManyScratch {
+  HostRows<TsdfRayManyJob> jobs;
+  HostRows<TsdfRayManyView> views;
+  HostRows<TsdfRayManyVol> vols;
+  DevBuf work;
+};
+
 struct revo_map {
   revo_ctx* ctx = nullptr;
   MapCtxGeom g{};
@@ -379,6 +392,8 @@ struct revo_map {
   MapTsdfFollowScratch tsdffol;
   // revo_map_tsdf_fuse_many / revo_map_tsdf_track_eval_many / revo_map_tsdf_track_many: everything of theirs, in a type of its own
   MapTsdfManyScratch tsdfmany;
+  // revo_map_tsdf_raycast_many: everything of the call, in a type of its own
+  MapTsdfRayManyScratch tsdfraymany;
 };
 
 // The views of a carve or an observe call, checked and resolved in the order DESIGN 19 states: each view's own rules, then every

@@ -1,14 +1,10 @@
 // revo_map_tsdf_ray.hip -- views of the surface: revo_map_tsdf_raycast, depth, normal and colour images ray-cast from
 // the TSDF volume and its colour volume.  Contract: include/revo_hip.h.  The march and every rule of it are revo_tsdf_ray_host.h's,
-// one text for both sides; this unit holds the block mask's kernel, the kernel that gives every pixel its ray, and the entry point.
+// one text for both sides; the two kernels' bodies are revo_tsdf_ray_dev.h's, shared with the batched call; this unit
+// holds the block mask's kernel, the kernel that gives every pixel its ray, and the entry point.
 #include "revo_map_impl.h"
 #include "revo_tsdf_ray_host.h"
-
-struct TsdfRayView {  // one view of a launch, in device memory
-  RayView v;
-  float* depth; float* normal; uint8_t* bgr; unsigned* hits;  // normal, bgr: NULL when not asked for
-};
-enum { TR_RAYS = 0, TR_STATUS = 1, TR_SAMPLES = 5, TR_UNCOLORED = 6 };
+#include "revo_tsdf_ray_dev.h"
 
 static_assert(sizeof(revo_map_tsdf_ray_params) == 16 && offsetof(revo_map_tsdf_ray_params, step) == 0 && offsetof(revo_map_tsdf_ray_params, min_weight) == 4 &&
               offsetof(revo_map_tsdf_ray_params, max_steps) == 8 && offsetof(revo_map_tsdf_ray_params, reserved) == 12, "the parameter record is the documented layout");
@@ -22,88 +18,22 @@ static_assert(REVO_TSDF_RAY_HIT == TSDF_RAY_HIT && REVO_TSDF_RAY_RANGE == TSDF_R
               REVO_TSDF_RAY_EXHAUSTED == TSDF_RAY_EXHAUSTED, "the header's statuses are the kernel's");
 static_assert(sizeof(revo_map_tsdf_cell) == 8 && sizeof(revo_map_tsdf_color) == 16, "the volumes' cells are the documented words");
 
-// One thread per cell: an INSIDE cell is a corner of the sample bases cell - {0, 1}^3 (those inside 0 .. n - 2), and marks the block
-// of each.  A bit only ever goes from 0 to 1 during the launch, so a bit that a load finds set needs no atomic, and the mask is
-// the same whatever the order: integer atomicOr only.
+// One thread per cell: tsdf_ray_mask_cell (revo_tsdf_ray_dev.h).
 __global__ void __launch_bounds__(256) k_tsdf_ray_mask(const revo_map_tsdf_cell* __restrict__ tsdf, const revo_map_df_box box, unsigned cells,
                                                        unsigned min_weight, int nby, int nbz, unsigned* mask) {
   const unsigned c = blockIdx.x * 256u + threadIdx.x;
   if (c >= cells) return;
-  const revo_map_tsdf_cell v = tsdf[c];
-  if (!tsdf_inside(v.sum, v.weight, min_weight)) return;
-  const unsigned ny = (unsigned)box.n[1], nz = (unsigned)box.n[2];
-  const unsigned line = c / nz;
-  const int iz = (int)(c - line * nz), ix = (int)(line / ny), iy = (int)(line - (unsigned)ix * ny);
-#pragma unroll
-  for (int o = 0; o < 8; ++o) {
-    const int bx = ix - (o & 1), by = iy - ((o >> 1) & 1), bz = iz - ((o >> 2) & 1);
-    if (bx < 0 || bx > box.n[0] - 2 || by < 0 || by > box.n[1] - 2 || bz < 0 || bz > box.n[2] - 2) continue;
-    const unsigned blk = tsdf_ray_block(nby, nbz, bx, by, bz), bit = 1u << (blk & 31u);
-    if (!(__hip_atomic_load(&mask[blk >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(&mask[blk >> 5], bit);
-  }
+  tsdf_ray_mask_cell(tsdf, box, c, min_weight, nby, nbz, mask);
 }
 
-// One thread per pixel, blockIdx.y = view.  A wave is an 8 x 8 pixel tile, so neighbouring rays read neighbouring cells and end
-// after similar numbers of samples; a block is four tiles side by side, and blocks past a view's tiles leave at once.  The view is
-// read through uniform addresses.  The statuses of a wave are counted by ballots, its samples and uncoloured hits by a wave sum,
-// each into LDS with one atomic per wave; every counter takes one global atomic per block.
+// One thread per pixel, blockIdx.y = view; blocks past a view's tiles leave at once.  The view is read through uniform addresses.
+// The block's work is tsdf_ray_view_block (revo_tsdf_ray_dev.h).
 __global__ void __launch_bounds__(256) k_tsdf_raycast(const TsdfRayK a, const TsdfRayView* __restrict__ views, u64* info) {
-  __shared__ unsigned s_cnt[TSDF_RAY_STATUSES];
-  __shared__ unsigned s_unc;
-  __shared__ u64 s_samples;
+  __shared__ TsdfRayTally s;
   const TsdfRayView& vw = views[blockIdx.y];
-  const RayView& c = vw.v;
-  const unsigned bw = (unsigned)(c.w + 31) / 32, bh = (unsigned)(c.h + 7) / 8;
+  const unsigned bw = (unsigned)(vw.v.w + 31) / 32, bh = (unsigned)(vw.v.h + 7) / 8;
   if (blockIdx.x >= bw * bh) return;
-  if (threadIdx.x < TSDF_RAY_STATUSES) s_cnt[threadIdx.x] = 0;
-  if (threadIdx.x == 4) s_samples = 0;
-  if (threadIdx.x == 5) s_unc = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int x = (int)((blockIdx.x % bw) * 32 + (threadIdx.x >> 6) * 8 + (lane & 7));
-  const int y = (int)((blockIdx.x / bw) * 8 + (lane >> 3));
-  int status = -1;
-  TsdfRayOut o{};
-  if (x < c.w && y < c.h) {
-    const float dcx = tsdf_div((float)x - c.cx, c.fx), dcy = tsdf_div((float)y - c.cy, c.fy);
-    TsdfRay ray;
-    ray.ox = c.o[0]; ray.oy = c.o[1]; ray.oz = c.o[2];
-    ray.dx = ((c.R[0] * dcx) + (c.R[1] * dcy)) + c.R[2];
-    ray.dy = ((c.R[3] * dcx) + (c.R[4] * dcy)) + c.R[5];
-    ray.dz = ((c.R[6] * dcx) + (c.R[7] * dcy)) + c.R[8];
-    ray.zmin = c.zmin; ray.zmax = c.zmax;
-    status = a.mask ? tsdf_ray_march<true>(a, ray, &o) : tsdf_ray_march<false>(a, ray, &o);
-    const size_t p = (size_t)y * c.w + x;
-    vw.depth[p] = o.depth;  // 0 unless a hit
-    if (vw.normal) {
-      float* nrm = vw.normal + p * 3;
-      nrm[0] = o.nx; nrm[1] = o.ny; nrm[2] = o.nz;
-    }
-    if (vw.bgr) {
-      uint8_t* b = vw.bgr + p * 3;
-      b[0] = o.b; b[1] = o.g; b[2] = o.r;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < TSDF_RAY_STATUSES; ++k) {
-    const u64 b = __ballot(status == k);
-    if (lane == 0 && b) atomicAdd(&s_cnt[k], (unsigned)__popcll(b));
-  }
-  const u64 unc = __ballot(status == TSDF_RAY_HIT && a.color && o.colored == 0u);
-  if (lane == 0 && unc) atomicAdd(&s_unc, (unsigned)__popcll(unc));
-  unsigned n = status < 0 ? 0u : o.samples;  // <= 2^20 per ray: a wave's sum fits
-#pragma unroll
-  for (int off = 32; off; off >>= 1) n += __shfl_down(n, off, 64);
-  if (lane == 0 && n) atomicAdd(&s_samples, (u64)n);
-  __syncthreads();
-  if (threadIdx.x < TSDF_RAY_STATUSES && s_cnt[threadIdx.x]) atomicAdd(&info[TR_STATUS + threadIdx.x], (u64)s_cnt[threadIdx.x]);
-  if (threadIdx.x == 4 && s_samples) atomicAdd(&info[TR_SAMPLES], s_samples);
-  if (threadIdx.x == 5 && s_unc) atomicAdd(&info[TR_UNCOLORED], (u64)s_unc);
-  if (threadIdx.x == 6) {
-    const unsigned rays = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    if (rays) atomicAdd(&info[TR_RAYS], (u64)rays);
-  }
-  if (threadIdx.x == 7 && s_cnt[TSDF_RAY_HIT]) atomicAdd(vw.hits, s_cnt[TSDF_RAY_HIT]);
+  tsdf_ray_view_block(a, vw, blockIdx.x, s, info);
 }
 
 // REVO_MAP_TSDF_RAY_MASK=0: no block mask, every sample is evaluated (the exactness test and profiles/map_tsdf_ray_rates.py).

@@ -1680,6 +1680,31 @@ def tsdf_raycast_records(tsdf, color, lo, voxel, views, step=None, min_weight=1,
     return out
 
 
+def tsdf_raycast_many_records(jobs):
+    """revo_map_tsdf_raycast_many's contract without a GPU: per job, tsdf_raycast_records for that job alone.  A job is a
+    dict: cells, lo, voxel, views (1 .. 64, as tsdf_raycast_records takes them) and optionally color, step, min_weight and
+    max_steps.  Jobs may share a volume: it is only read.  1 .. 1024 jobs with at most 4096 views between them.  -> one
+    tsdf_raycast_records dict per job.  ValueError as the library's argument errors: the call as a whole, before any job's result."""
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= 1024:
+        raise ValueError("1 .. 1024 jobs")
+    views = [list(job["views"]) for job in jobs]
+    if any(not 1 <= len(v) <= 64 for v in views):
+        raise ValueError("a job takes 1 .. 64 views")
+    if sum(len(v) for v in views) > 4096:
+        raise ValueError("at most 4096 views in one call")
+    for job, v in zip(jobs, views):  # every job's own rules first: the call is refused as a whole
+        cells = _tsdf_volume(job["cells"])
+        check_box(job["lo"], np.asarray(cells.shape, np.int64))
+        if job.get("color") is not None:
+            _tsdf_color_volume(job["color"], cells.shape)
+        tsdf_ray_params(job["voxel"], job.get("step"), job.get("min_weight", 1), job.get("max_steps", 4096))
+        for vw in v:
+            ray_view(*vw)
+    return [tsdf_raycast_records(job["cells"], job.get("color"), job["lo"], job["voxel"], v, job.get("step"), job.get("min_weight", 1),
+                                 job.get("max_steps", 4096)) for job, v in zip(jobs, views)]
+
+
 def df_sample(d2, lo, voxel, points):
     """revo_map_df_sample restated: a DF_SAMPLE_DTYPE array, one entry per point ([N, 3] float32 metres).  All arithmetic is
     float32, every operation rounded on its own.  dist -1: outside the box (or not finite); +inf: the cell holds DF_NONE."""

@@ -57,6 +57,10 @@ all loops in lockstep, and writes surface_poses_<dataset>.txt as --surface-track
 --streams-surface-window N (with --streams-surface) keeps only the last N keyframes (1 .. 1024) in every dataset's surface
 (vo.MultiREVO's surface window): the step keeps device copies of each fused keyframe's images and takes the oldest
 keyframe out again, all streams in one batched unfuse and without a wait; the mesh written is that of the last N keyframes.
+--streams-surface-views DIR (with --streams-surface) ray-casts every dataset's finished surface from the estimated pose of each of
+its keyframes, or with --streams-surface-views-every K of every K-th tracked frame, all datasets in batched calls
+(api.raycast_surfaces), and writes DIR/<dataset>/ in --surface-views' layout: the files the sequential
+--surface --surface-views run of that dataset writes.
 --surface-views DIR (with --surface) ray-casts the finished surface from the estimated pose of every keyframe, or with
 --surface-views-every K of every K-th tracked frame, on the GPU (api.SurfaceVolume.raycast, DESIGN 28: depth and colour from the
 sign change of the fused field, sub-voxel accurate and without holes) and writes the TUM-layout data set that --map-views writes
@@ -77,7 +81,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) < 2:
         print("usage: python -m revo_amd.run_tum <settings.yaml> <dataset.yaml> [device] [--save-model DIR] [--decoders N] "
-              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-window N] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--streams-surface-window N] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
+              "[--streams N [--gpu-decode]] [--exact-sums] [--covariances] [--map VOXEL [--map-window N] [--map-save FILE] [--map-esdf FILE [--map-esdf-pad N]] [--map-views DIR [--map-views-every K] [--map-views-raycast]] [--map-carve [--map-carve-margin M] [--map-carve-views K]] [--surface FILE.ply [--surface-box I0 J0 K0 N0 N1 N2] [--surface-trunc M] [--surface-min-weight K] [--surface-views DIR [--surface-views-every K]] [--surface-track] [--surface-window N] [--surface-follow [--surface-follow-size N0 N1 N2] [--surface-follow-step K] [--surface-store FILE.npz]]] [--streams-surface FILE.ply [--streams-surface-track] [--streams-surface-window N] [--streams-surface-views DIR [--streams-surface-views-every K]] [--surface-box ...] [--surface-trunc M] [--surface-min-weight K]]]")
         return 2
     from . import api, config, ply, synth, tum, vo
     model_dir = None
@@ -287,6 +291,30 @@ def main(argv=None):
         if "--streams-surface" not in argv:
             print("--streams-surface-window bounds every stream's TSDF surface: it needs --streams-surface FILE.ply")
             return 2
+    ssviews_dir, ssviews_every = None, 0  # tum.write_surfaces_views of every dataset's finished surface
+    if "--streams-surface-views-every" in argv:
+        i = argv.index("--streams-surface-views-every")
+        try:
+            ssviews_every = int(argv[i + 1])
+        except (IndexError, ValueError):
+            ssviews_every = 0
+        argv = argv[:i] + argv[i + 2:]
+        if ssviews_every < 1:
+            print("--streams-surface-views-every needs a positive number of frames")
+            return 2
+        if "--streams-surface-views" not in argv:
+            print("--streams-surface-views-every needs --streams-surface-views DIR")
+            return 2
+    if "--streams-surface-views" in argv:
+        i = argv.index("--streams-surface-views")
+        if i + 1 >= len(argv) or argv[i + 1].startswith("--"):
+            print("--streams-surface-views needs a folder name")
+            return 2
+        ssviews_dir = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+        if "--streams-surface" not in argv:
+            print("--streams-surface-views ray-casts every stream's TSDF surface: it needs --streams-surface FILE.ply")
+            return 2
     if "--streams-surface" in argv:
         i = argv.index("--streams-surface")
         if i + 1 >= len(argv) or argv[i + 1].startswith("--"):
@@ -295,6 +323,8 @@ def main(argv=None):
         ssurface = {"file": argv[i + 1]}
         if ssurface_window:
             ssurface["window"] = ssurface_window
+        if ssviews_dir is not None:
+            ssurface["views"], ssurface["views_every"] = ssviews_dir, ssviews_every
         argv = argv[:i] + argv[i + 2:]
         if "--streams" not in argv:
             print("--streams-surface gives every dataset of a multi-stream run its surface: it needs --streams N (the sequential driver has --surface)")
@@ -635,6 +665,14 @@ def _run_streams(streams, pyr_settings, trk_settings, io, sysd, device, decoders
             group.close()
     dt = time.perf_counter() - t0
     total = 0
+    if ssurface is not None and ssurface.get("views") is not None:  # --streams-surface-views: all datasets' views in batched calls
+        every = ssurface["views_every"]
+        sel = [r.poses[::every] if every else [p for p, (_, kf) in zip(r.poses, r) if kf] for r in res]
+        counts = tum.write_surfaces_views([(os.path.join(ssurface["views"], name), r.surface, p) for name, r, p in zip(names, res, sel)],
+                                          depth_scale=io["depth_scale_factor"], min_weight=ssurface.get("min_weight", 1))
+        for name, n in zip(names, counts):
+            print("Surface views: %d views (%s) -> %s" % (n, ("every %d frames" % every) if every else "one per keyframe",
+                                                          os.path.join(ssurface["views"], name)))
     for name, folder, r in zip(names, folders, res):
         if sysd["do_output_poses"]:
             with open("poses_%s.txt" % name, "w") as f:

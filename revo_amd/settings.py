@@ -517,6 +517,19 @@ class MapTsdfUnfuseResult(C.Structure):
 assert (C.sizeof(MapTsdfUnfuseJob), C.sizeof(MapTsdfUnfuseResult)) == (192, 80)
 
 
+class MapTsdfRayJob(C.Structure):
+    """revo_map_tsdf_ray_job (include/revo_hip.h), 120 bytes: one (volume, views) of revo_map_tsdf_raycast_many -- the map that gives the
+    voxel edge (NULL: the call's), the box, the parameters by value (all zero: the defaults), the device volumes (color may be NULL),
+    1 .. 64 views in a host array, host arrays of the views' device images (normal and bgr may be NULL), and the job's optional
+    device hit words and info record.  Jobs may share a volume."""
+    _fields_ = [("map", C.c_void_p), ("box", MapDfBox), ("prm", MapTsdfRayParams), ("tsdf", C.c_void_p), ("color", C.c_void_p), ("n_views", C.c_int32),
+                ("reserved", C.c_uint32), ("views", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("bgr", C.c_void_p), ("hits", C.c_void_p),
+                ("info", C.c_void_p)]
+
+
+assert C.sizeof(MapTsdfRayJob) == 120
+
+
 class MultiSurface(C.Structure):
     """revo_vo_multi_surface (include/revo_hip.h), 120 bytes: the surface of one stream of revo_vo_multi -- the map that gives the voxel
     edge, the box, trunc (0: 4 voxel edges), whether each keyframe is tracked before it is fused, the caller-owned device volumes

@@ -485,6 +485,39 @@ def write_surface_views(folder, surface, poses, depth_scale=5000.0, batch=16, no
     return write_views(folder, poses, render, depth_scale, batch, what="the TSDF surface", normals=normals)
 
 
+def write_surfaces_views(items, depth_scale=5000.0, calls=256, **ray_kw):
+    """write_surface_views for many surfaces at once: items = [(folder, surface, poses), ...], every surface an api.SurfaceVolume.
+    The views of all surfaces are ray-cast in batched calls (api.raycast_surfaces, DESIGN 34: `calls` views per call at most, the
+    poses as each folder's poses.txt states them) and each folder is then written by write_views, so it holds the files
+    write_surface_views writes for that surface alone.  All views are held in host memory until they are written.
+    ray_kw: raycast_surfaces' step, min_weight, max_steps.  -> the number of views per item."""
+    from . import api, vo
+    items = [(folder, surface, list(poses)) for folder, surface, poses in items]
+    stated = []
+    for folder, _, poses in items:  # the poses as poses.txt will state them
+        os.makedirs(folder, exist_ok=True)
+        pose_file = os.path.join(folder, "poses.txt")
+        with open(pose_file, "w") as f:
+            f.write("".join(line + "\n" for line in vo.tum_lines(poses)))
+        stated.append([T for _, T in read_poses(pose_file)])
+    done = [([], []) for _ in items]  # per item: depth images, bgr images
+    at = [0] * len(items)
+    while any(a < len(p) for a, p in zip(at, stated)):
+        entries, who, room = [], [], int(calls)
+        for i, (p, a) in enumerate(zip(stated, at)):
+            take = min(len(p) - a, room)
+            if take > 0:
+                entries.append((items[i][1], np.stack(p[a:a + take])))
+                who.append(i)
+                at[i] += take
+                room -= take
+        for i, r in zip(who, api.raycast_surfaces(entries, normals=False, colors=True, **ray_kw)):
+            done[i][0].extend(r["depth"])
+            done[i][1].extend(r["bgr"] if r["bgr"] is not None else [np.zeros(d.shape + (3,), np.uint8) for d in r["depth"]])
+    return [write_views(folder, poses, lambda Ts, d=d: d, depth_scale, max(1, len(poses)), what="the TSDF surface")
+            for (folder, _, poses), d in zip(items, done)]
+
+
 def read_groundtruth_positions(path):
     out = {}
     for line in open(path):

@@ -447,6 +447,24 @@ class MultiREVO:
         check(_lib.lib().revo_vo_multi_surface_window_last(self._h, int(stream), C.byref(rep)))
         return rep
 
+    def surface_views(self, poses_by_stream, **kw):
+        """Views of the streams' attached surfaces as they stand (api.raycast_surfaces): all streams' views in batched
+        calls, enqueued on the tracker stream behind the last step's fuse, so views of running sequences need no wait in between.
+        poses_by_stream: {stream: poses} or a list with one entry per stream (None: no views of that stream); an entry is the poses
+        (one 4x4, or any number of them) or a tuple (poses[, camera, size, zrange]).  kw: raycast_surfaces' step, min_weight,
+        max_steps, normals, colors, device.  -> {stream: what SurfaceVolume.raycast returns for that stream's surface}."""
+        items = poses_by_stream.items() if isinstance(poses_by_stream, dict) else enumerate(poses_by_stream)
+        streams, entries = [], []
+        for s, entry in items:
+            if entry is None:
+                continue
+            s = int(s)
+            if not 0 <= s < self.n_streams or self._surfaces[s] is None:
+                raise ValueError("stream %d has no surface attached" % s)
+            streams.append(s)
+            entries.append((self._surfaces[s][0],) + (tuple(entry) if isinstance(entry, tuple) else (entry,)))
+        return dict(zip(streams, api.raycast_surfaces(entries, **kw)))
+
     def _poll_surfaces(self):
         """Behind a step: the report of every stream that promoted a keyframe in it goes to the stream's log and surface."""
         for s, att in enumerate(self._surfaces):
